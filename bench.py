@@ -11,11 +11,14 @@ One process per GPU.  A step = one pass of the whole computeFlow device pipeline
 GPU).  Triplets are independent, so ranks share nothing in the timed region: the only
 collective is the RCCL broadcast of the flat weight buffer at start-up (weak scaling).
 
-Prints ONE JSON line on rank 0 (see the task contract); `roofline` is the dominant kernel
-class (conv3x3 fp32-MFMA implicit GEMM), `roofline_corrwarp` the HBM-bound fused
-warp + cost-volume kernel that BASELINE.json's target is quoted on; both are timed live with
-HIP events on the launch stream in a second, un-timed eager pass of the same steps (the timed steps replay a hipGraph).  `cpu_baseline` times the CPU oracle
-(oracle/, kind "port") on a bounded sample on rank 0 at N=1.
+Prints ONE JSON line on rank 0.  A plain run only sets up, warms up, times the K steps
+(`ms_per_step` = one timed step) and prints the headline line; `--dump-outputs DIR` also writes what the last timed step
+computed (dump_outputs).  Everything else is measured or checked only with `--full`: `outputs_finite`, the weight
+checksums and per-rank rates of N > 1, `compute_flow_hard_exact`, `two_pipelines_in_flight`, `host_path`, and
+`roofline` -- the dominant kernel class (conv3x3 fp32-MFMA implicit GEMM) -- and `roofline_corrwarp` -- the HBM-bound
+fused warp + cost-volume kernel that BASELINE.json's target is quoted on; both are timed live with HIP events on the
+launch stream in a second, un-timed eager pass of the same steps (the timed steps replay a hipGraph).  `cpu_baseline`
+times the CPU oracle (oracle/, kind "port") on a bounded sample on rank 0 at N=1.
 """
 import argparse
 import json
@@ -182,6 +185,25 @@ def cpu_baseline(H, W, seed, n=2):
     return port, tch
 
 
+DUMP_BYTES = 60 * 2 ** 20     # --dump-outputs writes at most this much (all arrays together), under 64 MB
+
+
+def dump_outputs(torch, outs, H, W, path):
+    """--dump-outputs: the arrays the timed path wrote in its last step, as <path>/<name>.npy in float32.  Arrays that
+    together exceed DUMP_BYTES are sampled: every triplet and channel at one fixed, seeded set of pixel positions, the same
+    for every array (B x C x K instead of B x C x H x W), so two builds run with the same arguments compare output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    k = min(H * W, max(1, DUMP_BYTES // (4 * sum(t.shape[0] * t.shape[1] for t in outs.values()))))
+    idx = None
+    if k < H * W:
+        pix = np.sort(np.random.default_rng(0).choice(H * W, k, replace=False))
+        idx = torch.from_numpy(pix).to(next(iter(outs.values())).device)
+    for name, t in outs.items():
+        a = t if idx is None else t.reshape(t.shape[0], t.shape[1], H * W).index_select(2, idx)
+        np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
+
+
 def pmc_traffic(B, H, W):
     """HBM bytes per step from the committed PMC passes (profiles/*_traffic.json, produced by
     tools/collect_traffic.sh + tools/traffic_summary.py on this same command); only valid for
@@ -290,15 +312,20 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--graph", type=int, default=1,
                     help="1 (default, BASELINE.json configs[4]): the timed steps replay the captured hipGraph of the forward pass; "
-                         "0: eager launches.  Per-kernel times always come from a second, un-timed eager pass with HIP events")
+                         "0: eager launches.  Per-kernel times (--full) always come from a second, un-timed eager pass with HIP events")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for tests)")
     ap.add_argument("--share-gpu", action="store_true", help="tests only: every rank uses GPU 0 (needs --backend gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else the benchmark measures and checks (see the module doc); "
+                         "off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what rank 0's last timed step computed to DIR/<name>.npy (float32, a fixed seeded sample above 60 MiB)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only `value` and the per-kernel profile: no compute_flow_hard_exact, two_pipelines_in_flight, host_path or CPU "
+                    help="with --full: only `value` and the per-kernel profile: no compute_flow_hard_exact, two_pipelines_in_flight, host_path or CPU "
                          "columns -- every forward pass of the process is then the same pass, which is what tools/collect_profiles.sh "
                          "profiles (AverageNs x launches per step of its kernel stats = kernel_ms_per_step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU columns")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: no host_path")
     args = ap.parse_args()
     if args.no_extras:
         args.no_cpu_baseline = args.no_host_path = True
@@ -339,6 +366,7 @@ def main():
         # replacing nn.DataParallelTable's NCCL parameter sync (util.lua:27-48)
         from back2future_amd import dist as b2f_dist
         b2f_dist.broadcast_weights(model, src=0)
+    if world > 1 and args.full:
         mine = torch.tensor([b2f_dist.weights_checksum(model) & 0x7fffffffffffffff], device=dev, dtype=torch.int64)
         every = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
@@ -375,11 +403,14 @@ def main():
     per_rank = None
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        every_t = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(every_t, t)
-        per_rank = [B * args.steps / float(u.item()) for u in every_t]     # a straggler shows here
+        if args.full:
+            every_t = [torch.zeros_like(t) for _ in range(world)]
+            dist.all_gather(every_t, t)
+            per_rank = [B * args.steps / float(u.item()) for u in every_t]     # a straggler shows here
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:   # before anything below writes the same buffers again
+        dump_outputs(torch, {"flow": flow, "occ": occ, "est3": est3}, H, W, args.dump_outputs)
 
     # Beside `value` (never as it): what computeFlow() of an Ours-Hard model really needs -- flow and est[3] = warped frame 1
     # (back2future.lua:77,87 read est[1] and est[3] by position; for a Hard model the occlusion decoder of level 3 feeds
@@ -387,7 +418,7 @@ def main():
     def step_hard_exact():
         model.forward_device(x.data_ptr(), B, H, W, flow.data_ptr(), None, est3.data_ptr(), unit_input=True, stream=stream)
     hard_dt = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         for _ in range(3):
             step_hard_exact()
         torch.cuda.synchronize()
@@ -400,7 +431,7 @@ def main():
     # Beside `value` (never as it): two step pipelines in flight -- a second context (own arena, stream and captured graph) takes
     # every other step, so the launch-latency-bound coarse pyramid levels of one step run beside the wide kernels of the next
     two = None
-    if world == 1 and args.graph and not args.no_extras:
+    if args.full and world == 1 and args.graph and not args.no_extras:
         try:
             m2 = back2future.Model("random:hard:2:1.0", device=local_rank)
             m2.set_option("use_graph", 1)
@@ -433,20 +464,22 @@ def main():
 
     # per-kernel times: a second, UN-TIMED pass of the same steps, eager, with HIP events recorded by the library around
     # every launch on the launch stream (the event pairs cost ~2 % and graphs carry no events, so not in `value`)
-    model.set_option("use_graph", 0)
-    model.set_option("profile", 1)
-    step()
-    torch.cuda.synchronize()
-    model.profile_reset()
-    tp0 = time.perf_counter()
-    for _ in range(args.steps):
+    prof = finite = None
+    if args.full:
+        model.set_option("use_graph", 0)
+        model.set_option("profile", 1)
         step()
-    torch.cuda.synchronize()
-    prof_dt = time.perf_counter() - tp0
-    prof = model.profile_read()
-    model.set_option("profile", 0)
-    kernels = layer_kernels(model, step, torch)       # the library's kernel class per layer (one more un-timed eager pass)
-    finite = bool(torch.isfinite(flow).all().item() and torch.isfinite(occ).all().item())
+        torch.cuda.synchronize()
+        model.profile_reset()
+        tp0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        prof_dt = time.perf_counter() - tp0
+        prof = model.profile_read()
+        model.set_option("profile", 0)
+        kernels = layer_kernels(model, step, torch)       # the library's kernel class per layer (one more un-timed eager pass)
+        finite = bool(torch.isfinite(flow).all().item() and torch.isfinite(occ).all().item())
 
     if rank == 0:
         px = H * W * B
@@ -464,8 +497,9 @@ def main():
                        "batch_per_gpu": B, "global_batch": B * world, "height": H, "width": W,
                        "parallelism": "dp%d: independent triplets per rank, one RCCL weight broadcast at init" % world,
                        "hip_graph": bool(args.graph)},
-            "outputs_finite": finite,
         }
+        if finite is not None:
+            out["outputs_finite"] = finite
         if bcast:
             out["weights_broadcast"] = bcast
         if per_rank:
@@ -534,9 +568,9 @@ def main():
                                                    "its per-layer profile rows -- executed_flop_per_step follows from this, not from a rule restated here",
                                            "layers": {"%dto%d_%dx%d" % k: v for k, v in sorted(kernels.items())}}
             out["profiled_pass_ms_per_step"] = 1e3 * prof_dt / args.steps
-        if world == 1 and not args.no_host_path:
+        if args.full and world == 1 and not args.no_host_path:
             out["host_path"] = host_path(torch, model, H, W)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], out["cpu_baseline_torch"] = cpu_baseline(H, W, 2)
         print(json.dumps(out), flush=True)
     model.close()

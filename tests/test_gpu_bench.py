@@ -20,7 +20,7 @@ def _line(out):
 
 
 def test_single_gpu_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, capture_output=True, text=True, cwd=ROOT, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + SMALL, capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
@@ -42,7 +42,7 @@ def test_single_gpu_line_contract():
 
 
 def test_no_extras_line_is_the_plain_pass_only():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras"] + SMALL[:10], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras"] + SMALL[:10], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     for k in ("compute_flow_hard_exact", "two_pipelines_in_flight", "host_path", "cpu_baseline"):
@@ -50,10 +50,33 @@ def test_no_extras_line_is_the_plain_pass_only():
     assert d["value"] > 0 and "roofline" in d and "kernel_ms_per_step" in d
 
 
+def test_plain_line_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline figure only; --dump-outputs writes what the last timed step computed,
+    and two runs with the same arguments compute the same outputs."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d_out = tmp_path / str(i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(d_out)] + SMALL[:8],
+                           capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        for k in ("outputs_finite", "compute_flow_hard_exact", "two_pipelines_in_flight", "roofline", "kernel_ms_per_step", "host_path", "cpu_baseline"):
+            assert k not in d, k
+        dumps.append({n: np.load(str(d_out / (n + ".npy"))) for n in ("flow", "occ", "est3")})
+    for n, c in (("flow", 2), ("occ", 2), ("est3", 3)):
+        a = dumps[0][n]
+        assert a.shape == (2, c, 128, 256) and a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0, n
+        np.testing.assert_array_equal(a, dumps[1][n])
+
+
 def test_two_ranks_share_the_gpu_over_gloo():
     port = 29700 + os.getpid() % 200
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu"] + SMALL
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--full"] + SMALL
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
@@ -66,7 +89,7 @@ def test_plain_invocation_spawns_ranks():
     """`python bench.py --gpus 2` with no launcher and no WORLD_SIZE (how the driver's N=1 command line looks with another N):
     the parent starts the ranks itself, relays rank 0's one line and returns their exit code."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu"] + SMALL,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--full"] + SMALL,
                        capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)

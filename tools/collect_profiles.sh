@@ -1,19 +1,19 @@
 #!/bin/bash
 # Round profiles: rocprofv3 kernel-trace stats of the default bench command, the bench line printed
 # under the profiler, and the two PMC traffic passes.  Run on the GPU box:
-#   bash tools/collect_profiles.sh r01    ->  gpurun_out/profiles_r01/...  (copy the summaries into profiles/)
+#   B2F_OUT=<dir> bash tools/collect_profiles.sh r01    ->  $B2F_OUT/profiles_r01/...  (copy the summaries into profiles/)
 set -u
 TAG=${1:-r01}
 R=${GRAFT_REPO_ROOT:?set GRAFT_REPO_ROOT}
-OUT=$R/gpurun_out/profiles_$TAG
+OUT=${B2F_OUT:?set B2F_OUT to the directory the results go to}/profiles_$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 timeout 280 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o b2f -- \
-  python3 $R/bench.py --steps 5 --warmup 2 --no-extras > $OUT/bench_under_rocprof.log 2>&1
+  python3 $R/bench.py --full --steps 5 --warmup 2 --no-extras > $OUT/bench_under_rocprof.log 2>&1
 echo "stats rc=$?"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -o b2f -- \
-    python3 $R/bench.py --steps 1 --warmup 1 --no-extras > $OUT/pmc_$c.log 2>&1
+    python3 $R/bench.py --full --steps 1 --warmup 1 --no-extras > $OUT/pmc_$c.log 2>&1
   echo "$c rc=$?"
 done
 cd $R

@@ -4,6 +4,7 @@
 #   bash tools/collect_tcc.sh [tag]   -> gpurun_out/tcc_<tag>/passN/...; python3 tools/pmc_summary.py <csv> prints them per kernel
 set -u
 TAG=${1:-r03}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp; export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/tcc_$TAG
 P1="TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"
@@ -15,7 +16,7 @@ i=0
 for P in "$P1" "$P2" "$P3" "$P4" "$P5"; do
   i=$((i+1))
   timeout 200 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT/pass$i -o b2f -- \
-    python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --batch 16 --no-extras > $OUT.pass$i.log 2>&1
+    python3 $R/bench.py --full --steps 1 --warmup 1 --batch 16 --no-extras > $OUT.pass$i.log 2>&1
   echo "pass$i rc=$?"
   python3 $GRAFT_REPO_ROOT/tools/pmc_summary.py $(ls $OUT/pass$i/*counter_collection.csv $OUT/pass$i/*/*counter_collection.csv 2>/dev/null | head -1) | cut -c1-200 | head -14
 done

@@ -15,7 +15,7 @@ for line in open(src):
                  "ms_per_triplet": round(d["ms_per_step"] / b, 3), "roofline_frac_dominant_kernel": round(d["roofline"]["frac"], 3),
                  "dominant_kernel": d["roofline"]["kernel"][:24], "roofline_corrwarp_frac": round(d["roofline_corrwarp"]["frac"], 3)})
 lat = {"%dx%d" % (r["height"], r["width"]): r["ms_per_step"] for r in rows if r["batch"] == 1}
-out = {"source": "tools/other_shapes.sh at the round's HEAD: bench.py --batch B --height H --width W --steps 5 --warmup 2 --no-extras (device-resident, "
+out = {"source": "tools/other_shapes.sh at the round's HEAD: bench.py --full --batch B --height H --width W --steps 5 --warmup 2 --no-extras (device-resident, "
                  "hipGraph replay), one MI355X", "rows": rows, "single_triplet_latency_ms": lat}
 json.dump(out, open("profiles/%s_other_shapes.json" % tag, "w"), indent=1)
 print(json.dumps(lat))

@@ -7,7 +7,7 @@ s_waitcnt / s_barrier, stalled at issue, issuing), LDS bank-conflict share.
 
 Units (MI355X_MICROARCH.md, rocprofv3 PMC section): SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles summed over
 waves, SQ_VALU_MFMA_BUSY_CYCLES counts cycles summed over SIMDs; GRBM_GUI_ACTIVE is summed over the 8 XCDs.  Every forward pass
-of `bench.py --no-extras` is the same pass, so totals / (number of conv_first launches) = per step."""
+of `bench.py --full --no-extras` is the same pass, so totals / (number of conv_first launches) = per step."""
 import csv
 import glob
 import json
@@ -43,7 +43,7 @@ def main():
     base, tag = sys.argv[1], sys.argv[2]
     passes = [read_pass(os.path.join(base, "pass%d" % i)) for i in (1, 2, 3)]
     steps = [max(1, sum(c for k, c in p[2].items() if "conv_first" in k)) for p in passes]
-    out = {"source": "rocprofv3 --kernel-trace --pmc, three separate passes of `bench.py --steps 1 --warmup 1 --batch 16 --no-extras` "
+    out = {"source": "rocprofv3 --kernel-trace --pmc, three separate passes of `bench.py --full --steps 1 --warmup 1 --batch 16 --no-extras` "
                      "(tools/collect_sq.sh); per bench step", "kernels": {}}
     for k in sorted(passes[0][0], key=lambda k: -passes[0][1][k]):
         c = {}
