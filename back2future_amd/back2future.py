@@ -20,6 +20,9 @@ from . import _lib
 meanstd = {"mean": [0.485, 0.456, 0.406], "std": [0.229, 0.224, 0.225]}   # back2future.lua:33-36
 occ_threshold = 0.6666                                                     # back2future.lua:40
 
+# in_kind of the device entry points (include/b2f.h); IN_U8 is taken by the sequence entry only
+IN_NORMALIZED, IN_UNIT, IN_U8 = 0, 1, 2
+
 
 def normalize(imgs):
     """M.normalize = TF.ColorNormalize(meanstd) (back2future.lua:42-45, transforms.lua:33-45)."""
@@ -27,6 +30,55 @@ def normalize(imgs):
     for c in range(out.shape[0]):
         out[c] = (out[c] + np.float32(-meanstd["mean"][c % 3])) / np.float32(meanstd["std"][c % 3])
     return out
+
+
+def sequence_frames(frames):
+    """frames -> (contiguous T x 3 x H x W array, as_bytes) for the sequence entry points: one T x 3 x H x W array or a list
+    of 3 x H x W arrays, float (converted to float32) or uint8 (value = byte / 255, passed as bytes), never a mix of the two.
+    Raises ValueError on anything else, before any library call."""
+    if isinstance(frames, (list, tuple)):
+        arrs = [np.asarray(f) for f in frames]
+        if any(a.ndim != 3 or a.shape[0] != 3 for a in arrs):
+            raise ValueError("computeFlowSequence: every frame must be 3 x H x W")
+        if len({a.shape for a in arrs}) > 1:
+            raise ValueError("computeFlowSequence: the frames must have the same size")
+        kinds = {a.dtype == np.uint8 for a in arrs}
+        if len(kinds) > 1:
+            raise ValueError("computeFlowSequence: mixed dtypes (all frames uint8, or all float)")
+        as_bytes = kinds == {True}
+        v = np.stack(arrs) if arrs else np.empty((0, 3, 1, 1), np.float32)
+    else:
+        v = np.asarray(frames)
+        if v.ndim != 4 or v.shape[1] != 3:
+            raise ValueError("computeFlowSequence: expected T x 3 x H x W frames")
+        as_bytes = v.dtype == np.uint8
+    if v.shape[0] < 3:
+        raise ValueError("computeFlowSequence: a sequence needs T >= 3 frames, got %d" % v.shape[0])
+    v = np.ascontiguousarray(v) if as_bytes else _lib.f32(v)
+    return v, as_bytes
+
+
+def _sequence_outputs(n, H0, W0, out):
+    if out is not None:
+        flow, fwd, bwd = out
+        assert flow.dtype == np.float64 and flow.shape == (n, 2, H0, W0) and flow.flags.c_contiguous
+        for m in (fwd, bwd):
+            assert m.dtype == np.uint8 and m.shape == (n, 1, H0, W0) and m.flags.c_contiguous
+        return flow, fwd, bwd
+    return np.empty((n, 2, H0, W0), np.float64), np.empty((n, 1, H0, W0), np.uint8), np.empty((n, 1, H0, W0), np.uint8)
+
+
+def _call_sequence(fn_f32, fn_u8, h, frames, out):
+    v, as_bytes = sequence_frames(frames)
+    T, _, H0, W0 = v.shape
+    flow, fwd, bwd = _sequence_outputs(T - 2, H0, W0, out)
+    outp = (flow.ctypes.data_as(C.POINTER(C.c_double)), fwd.ctypes.data_as(C.POINTER(C.c_ubyte)),
+            bwd.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    if as_bytes:
+        _lib.check(getattr(_lib.lib(), fn_u8)(h, T, v.ctypes.data_as(C.POINTER(C.c_ubyte)), H0, W0, *outp))
+    else:
+        _lib.check(getattr(_lib.lib(), fn_f32)(h, T, _lib.fptr(v), H0, W0, *outp))
+    return flow, fwd, bwd
 
 
 class Model(object):
@@ -163,6 +215,12 @@ class Model(object):
             _lib.check(_lib.lib().b2f_compute_flow_batch(self._h, n, _lib.fptr(im1), _lib.fptr(im2), _lib.fptr(im3), H0, W0, *outp))
         return flow, fwd, bwd
 
+    def computeFlowSequence(self, frames, out=None):
+        """Flow for every centre frame of a video: frames is a T x 3 x H x W float32 or uint8 array (or a list of 3 x H x W
+        arrays); output i is computeFlow(frames[i], frames[i+1], frames[i+2]), i = 0 .. T-3, with the shapes and dtypes of
+        computeFlowBatch.  Every frame is uploaded and run through the feature pyramid once (b2f_compute_flow_sequence)."""
+        return _call_sequence("b2f_compute_flow_sequence", "b2f_compute_flow_sequence_u8", self._h, frames, out)
+
     def output_shapes(self, H, W):
         cap = 32
         ch, oh, ow = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
@@ -184,6 +242,16 @@ class Model(object):
         """model:forward on device pointers (ints); asynchronous on `stream`."""
         _lib.check(_lib.lib().b2f_forward_device(
             self._h, C.c_void_p(d_in), 1 if unit_input else 0, B, H, W,
+            C.c_void_p(d_flow) if d_flow else None, C.c_void_p(d_occ) if d_occ else None,
+            C.c_void_p(d_est3) if d_est3 else None, C.c_void_p(stream) if stream else None))
+
+    def forward_sequence_device(self, d_frames, T, H, W, d_flow=None, d_occ=None, d_est3=None, in_kind=IN_NORMALIZED, stream=None):
+        """b2f_forward_sequence_device on device pointers (ints): d_frames is T x 3 x H x W (float32, or uint8 with
+        in_kind=IN_U8); outputs (T-2) x 2|2|C3 x H x W, output i that of the triplet (i, i+1, i+2).  Asynchronous on `stream`."""
+        if T < 3:
+            raise ValueError("forward_sequence_device: a sequence needs T >= 3 frames, got %d" % T)
+        _lib.check(_lib.lib().b2f_forward_sequence_device(
+            self._h, C.c_void_p(d_frames), int(in_kind), T, H, W,
             C.c_void_p(d_flow) if d_flow else None, C.c_void_p(d_occ) if d_occ else None,
             C.c_void_p(d_est3) if d_est3 else None, C.c_void_p(stream) if stream else None))
 
@@ -242,6 +310,11 @@ class MultiModel(object):
         else:
             _lib.check(_lib.lib().b2f_multi_compute_flow_batch(self._h, n, _lib.fptr(im1), _lib.fptr(im2), _lib.fptr(im3), H0, W0, *outp))
         return flow, fwd, bwd
+
+    def computeFlowSequence(self, frames, out=None):
+        """Model.computeFlowSequence over the GPUs: the T-2 triplets are split with shard_range, every replica reads the
+        frames its triplets need (T_i = its triplets + 2)."""
+        return _call_sequence("b2f_multi_compute_flow_sequence", "b2f_multi_compute_flow_sequence_u8", self._h, frames, out)
 
 
 def shard_range(n, rank, world):

@@ -292,23 +292,29 @@ int find_conv(const b2f_ctx *c, int kind, int level, int idx)
 struct Plan {
     int B, H, W;
     bool full;          // full model:forward table (all decoders, image pyramid, image warps)
+    bool seq;           // sequence mode: the pyramid holds T = B + 2 frames, triplet b is frames (b, b + 1, b + 2)
+    int nimg;           // images of the feature pyramid: 3B (frame-major [3][B]) or T = B + 2
+    int fo;             // image offset of a triplet's second / third frame from its first one: B, or 1 in sequence mode
     int rec;            // cost-volume record size in floats
     int h[8], w[8];
     size_t img, tmp, cs[8], U[8], UB[8], cv, d[6], fs, bfs, logits, u2, flow_planar, ds[6], total;
 };
 
-Plan make_plan(int B, int H, int W, bool full, bool past_flow)
+Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false)
 {
     Plan p;
     p.B = B; p.H = H; p.W = W;
     p.full = full;
+    p.seq = seq;
+    p.nimg = seq ? B + 2 : 3 * B;
+    p.fo = seq ? 1 : B;
     p.rec = kCvRec;
     for (int l = 1; l <= 7; ++l) { p.h[l] = H >> (l - 1); p.w[l] = W >> (l - 1); }
     size_t off = 0;
     auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
     p.img = full ? take((size_t)3 * B * H * W * kImgC) : 0;   // packed frames: only the full table needs them
-    p.tmp = take((size_t)3 * B * p.h[2] * p.w[2] * kFeat[2]);
-    for (int l = 2; l <= 7; ++l) p.cs[l] = take((size_t)3 * B * p.h[l] * p.w[l] * kFeat[l]);
+    p.tmp = take((size_t)p.nimg * p.h[2] * p.w[2] * kFeat[2]);
+    for (int l = 2; l <= 7; ++l) p.cs[l] = take((size_t)p.nimg * p.h[l] * p.w[l] * kFeat[l]);
     for (int l = 3; l <= 6; ++l) p.U[l] = take((size_t)B * p.h[l] * p.w[l] * 2);
     for (int l = 3; l <= 6; ++l) p.UB[l] = (full && past_flow) ? take((size_t)B * p.h[l] * p.w[l] * 2) : 0;
     p.cv = take((size_t)B * p.h[3] * p.w[3] * p.rec + 64);
@@ -496,7 +502,7 @@ int run_decoder(b2f_ctx *c, hipStream_t s, bool cap, const Plan &P, int kind, in
     const int id1 = find_conv(c, kind, l, 1);
     if (id1 < 0) return fail("decoder not present in this model");
     ConvSeg segs[2];
-    const ConvSeg seg_ref = cp8_seg(A + P.cs[l] + (size_t)1 * B * hw * Cl, Cl, hw);
+    const ConvSeg seg_ref = cp8_seg(A + P.cs[l] + (size_t)P.fo * hw * Cl, Cl, hw);
     const ConvSeg seg_cv = cp8_seg(A + P.cv, kCvRec, hw);
     if (c->packed[id1].nseg == 2) { segs[0] = seg_ref; segs[1] = seg_cv; }
     else { segs[0] = seg_cv; segs[1] = seg_cv; }
@@ -518,7 +524,9 @@ struct Outs {
 };
 
 // The computeFlow graph: pruned to the live set or, with P.full, the
-// complete model:forward of models/pwc.lua.
+// complete model:forward of models/pwc.lua.  With P.seq the input is T = B + 2 frames (T x 3 x H x W) and the pyramid
+// runs on each frame once; from the cost volume on, the launches are those of B triplets, which read their frames
+// through base pointers P.fo images apart.
 int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in_kind, const Plan &P, const Outs &O)
 {
     c->cur_batch = c->req_batch > 0 ? c->req_batch : P.B;
@@ -530,7 +538,7 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
         Scope sc(c, s, "pack_input", cap);
         HIPCHK(launch_pack_input((const float *)dev_in, unit, B, P.H, P.W, A + P.img, s));
     }
-    // siamese feature pyramid, the three frames batched (shared weights, pwc.lua:169-211)
+    // siamese feature pyramid, the three frames batched (shared weights, pwc.lua:169-211); P.nimg images
     // (the head kernel reads the c16 / c16s2 packings of its two layers: B2F_WINO=0 packs them for the direct kernel instead)
     const int head_id1 = find_conv(c, KIND_FEAT, 2, 2), head_id2 = find_conv(c, KIND_FEAT, 3, 1);
     const bool head_fused = c->bf16_direct >= 2 && P.h[2] >= 4 && P.w[2] >= 4 && head_id1 >= 0 && head_id2 >= 0 &&
@@ -538,17 +546,21 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
     for (int l = 2; l <= 7; ++l) {
         const int hi = P.h[l - 1], wi = P.w[l - 1], ho = P.h[l], wo = P.w[l];
         const int Ci = (l == 2) ? kImgC : kFeat[l - 1], Co = kFeat[l];
-        if (l == 2) {
+        if (l == 2 && P.seq) {
+            Scope sc(c, s, "conv_first_seq", cap);
+            HIPCHK(launch_conv_first_seq(dev_in, in_kind, P.nimg, P.H, P.W, c->wpk_dev + c->first_w_off, c->wpk_dev + c->first_b_off,
+                                         A + P.tmp, s));
+        } else if (l == 2) {
             Scope sc(c, s, "conv_first", cap);
             HIPCHK(launch_conv_first((const float *)dev_in, unit, B, P.H, P.W, c->wpk_dev + c->first_w_off,
                                      c->wpk_dev + c->first_b_off, A + P.tmp, s));
         } else if (l == 3 && head_fused) {   // conv 1 of level 3 ran inside the fused head: its output sits in the (otherwise unused) cs[2] region
             const ConvSeg in2f = cp8_seg(A + P.cs[2], Co, (size_t)ho * wo);
-            CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 2), &in2f, 3 * B, ho, wo, 1, 1, A + P.cs[l]));
+            CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 2), &in2f, P.nimg, ho, wo, 1, 1, A + P.cs[l]));
             continue;
         } else {
             const ConvSeg in1 = cp8_seg(A + P.cs[l - 1], Ci, (size_t)hi * wi);
-            CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 1), &in1, 3 * B, hi, wi, 2, 1, A + P.tmp));
+            CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 1), &in1, P.nimg, hi, wi, 2, 1, A + P.tmp));
         }
         if (l == 2 && head_fused) {   // level-2 conv 2 + level-3 conv 1 in one streaming kernel (b2f_head.hip)
             const PackedConv &p1 = c->packed[find_conv(c, KIND_FEAT, 2, 2)], &p2 = c->packed[find_conv(c, KIND_FEAT, 3, 1)];
@@ -557,7 +569,7 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
             hl.H1 = ho; hl.W1 = wo;
             hl.w1 = c->wpk_dev + p1.w_off; hl.b1 = c->wpk_dev + p1.b_off; hl.w2 = c->wpk_dev + p2.w_off; hl.b2 = c->wpk_dev + p2.b_off;
             hl.out = A + P.cs[2];
-            hl.Ho = P.h[3]; hl.Wo = P.w[3]; hl.nimg = 3 * B;
+            hl.Ho = P.h[3]; hl.Wo = P.w[3]; hl.nimg = P.nimg;
             hl.out_img_stride = (long)((size_t)hl.Ho * hl.Wo * 32); hl.out_chunk_stride = (long)((size_t)hl.Ho * hl.Wo * 8); hl.out_pix_stride = 8;
             char hname[48];
             snprintf(hname, sizeof hname, c->profile_layers ? "convH16_16to32_%dx%d" : "conv_head16_bf16", ho, wo);
@@ -566,7 +578,7 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
             continue;
         }
         const ConvSeg in2 = cp8_seg(A + P.tmp, Co, (size_t)ho * wo);
-        CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 2), &in2, 3 * B, ho, wo, 1, 1, A + P.cs[l]));
+        CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 2), &in2, P.nimg, ho, wo, 1, 1, A + P.cs[l]));
     }
     if (full) {
         // image pyramid of frames 1 and 3 for the warped-image outputs (pwc.lua:148-158);
@@ -587,8 +599,8 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
         const int h = P.h[l], w = P.w[l], Cl = kFeat[l];
         const size_t hw = (size_t)h * w;
         CorrLaunch cl;
-        cl.ref = A + P.cs[l] + (size_t)1 * B * hw * Cl;
-        cl.nbr_fut = A + P.cs[l] + (size_t)2 * B * hw * Cl;
+        cl.ref = A + P.cs[l] + (size_t)P.fo * hw * Cl;
+        cl.nbr_fut = A + P.cs[l] + (size_t)2 * P.fo * hw * Cl;
         cl.nbr_past = A + P.cs[l];
         cl.img_stride = (long)(hw * Cl);
         cl.chunk_stride = (long)(hw * 8);
@@ -652,7 +664,10 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
             if (O.t_iw3[l]) HIPCHK(launch_warp_image_planar(im3, O.t_ufs[l], kk, B, hk, wk, O.t_iw3[l], s));
         }
     }
-    if (!full && O.est3 && !c->past_flow) {
+    if (!full && O.est3 && !c->past_flow && P.seq) {
+        Scope sc(c, s, "warp_image_seq", cap);
+        HIPCHK(launch_warp_input_seq(dev_in, in_kind, O.flow ? O.flow : A + P.flow_planar, -20.0f, B, P.H, P.W, O.est3, s));
+    } else if (!full && O.est3 && !c->past_flow) {
         // Hard: est[3] = iws[1][3] = warp(I1, skip_ufs[3] * 20*(1-2)/2^0)  (pwc.lua:422-446,459-489)
         Scope sc(c, s, "warp_image", cap);
         HIPCHK(launch_warp_input_planar((const float *)dev_in, unit, 0, O.flow ? O.flow : A + P.flow_planar, -20.0f, B, P.H, P.W,
@@ -1174,10 +1189,11 @@ B2F_CATCH("b2f_profile_read")
 // attributes, which must not happen inside a capture), the second one captures, later ones only replay.  Worth
 // ~0.5 ms per forward pass: 17 % of a single full-HD triplet, 2 % of a batch of 16.
 int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow, float *dev_occ,
-                        float *dev_est3, hipStream_t s, bool graph)
+                        float *dev_est3, hipStream_t s, bool graph, bool seq)
 {
     CHK(check_shape(B, H, W));
     HIPCHK(hipSetDevice(c->device));
+    if (seq && !c->g.shipped()) return fail("b2f_forward_sequence_device: sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
     if (!c->g.shipped()) {
         // other graph shapes: the whole output table through the generic executor (b2f_graph.hip), then est[1] / the
         // finest occlusion map / est[3] into the caller's buffers.  Asynchronous on the stream like the tuned path, no hipGraph: a correctness path.
@@ -1206,7 +1222,7 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
         if (dev_est3) HIPCHK(hipMemcpyAsync(dev_est3, dev[2], c->past_flow ? n2 : n2 / 2 * 3, hipMemcpyDeviceToDevice, s));
         return 0;
     }
-    const Plan P = make_plan(B, H, W, false, c->past_flow);
+    const Plan P = make_plan(B, H, W, false, c->past_flow, seq);
     CHK(ensure_workspace(c, P));
     Outs O;
     O.flow = dev_flow; O.occ = dev_occ; O.est3 = dev_est3;
@@ -1216,7 +1232,8 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
             drop_graphs(c);
         }
         const int req = c->req_batch > 0 ? c->req_batch : B;
-        const GraphKey key = {dev_in, dev_flow, dev_occ, dev_est3, in_kind, B, H, W, (c->adaptive_kernels > 0 || (c->adaptive_kernels < 0 && req == 1)) ? 1 : 0};
+        const GraphKey key = {dev_in, dev_flow, dev_occ, dev_est3, in_kind, B, H, W, (c->adaptive_kernels > 0 || (c->adaptive_kernels < 0 && req == 1)) ? 1 : 0,
+                              seq ? 1 : 0};
         auto it = c->graphs.find(key);
         if (it == c->graphs.end()) {
             c->graphs.emplace(key, nullptr);
@@ -1254,6 +1271,20 @@ int b2f_forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H
                           c->use_graph != 0);
 }
 B2F_CATCH("b2f_forward_device")
+
+int b2f_forward_sequence_device(b2f_ctx *c, const void *dev_frames, int in_kind, int T, int H, int W, float *dev_flow, float *dev_occ,
+                                float *dev_est3, void *stream) try
+{
+    if (!c || !dev_frames) return fail("b2f_forward_sequence_device: null argument");
+    if (T < 3) return fail("b2f_forward_sequence_device: a sequence needs T >= 3 frames (one triplet)");
+    if (in_kind != B2F_IN_NORMALIZED && in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8)
+        return fail("b2f_forward_sequence_device: in_kind must be B2F_IN_NORMALIZED, B2F_IN_UNIT or B2F_IN_U8");
+    if (((uintptr_t)dev_frames | (uintptr_t)dev_flow | (uintptr_t)dev_occ | (uintptr_t)dev_est3) & 15)
+        return fail("b2f_forward_sequence_device: device buffers must be 16-byte aligned");
+    return forward_device(c, dev_frames, in_kind, T - 2, H, W, dev_flow, dev_occ, dev_est3, stream ? (hipStream_t)stream : c->stream,
+                          c->use_graph != 0, true);
+}
+B2F_CATCH("b2f_forward_sequence_device")
 
 int b2f_output_shapes(const b2f_ctx *c, int H, int W, int *ch, int *oh, int *ow, int cap) try
 {

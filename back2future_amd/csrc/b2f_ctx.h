@@ -56,9 +56,10 @@ struct GraphKey {
     float *flow, *occ, *est3;
     int kind, B, H, W;
     int rule;                      // kernel-choice rule the captured launches follow (1 = per launch: a single-triplet request), part of the key
+    int seq;                       // 1 = sequence mode (in = B + 2 frames): never the graph of a triplet call with the same pointers and B
     bool operator<(const GraphKey &o) const
     {
-        return std::tie(in, flow, occ, est3, kind, B, H, W, rule) < std::tie(o.in, o.flow, o.occ, o.est3, o.kind, o.B, o.H, o.W, o.rule);
+        return std::tie(in, flow, occ, est3, kind, B, H, W, rule, seq) < std::tie(o.in, o.flow, o.occ, o.est3, o.kind, o.B, o.H, o.W, o.rule, o.seq);
     }
 };
 
@@ -303,9 +304,14 @@ namespace b2f {
 int check_shape(int B, int H, int W);
 void drop_graphs(b2f_ctx *c);
 void drop_gen_out(b2f_ctx *c);
-// model:forward on device pointers, optionally replayed from a hipGraph (see b2f_api.hip)
+// model:forward on device pointers, optionally replayed from a hipGraph (see b2f_api.hip); seq: dev_in holds the B + 2 frames
+// of a sequence (T x 3 x H x W) instead of B triplets (B x 9 x H x W)
 int forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow, float *dev_occ,
-                   float *dev_est3, hipStream_t s, bool graph);
+                   float *dev_est3, hipStream_t s, bool graph, bool seq = false);
+// b2f_pipeline.hip: the host pipeline on T frames (b2f_compute_flow_sequence*); req = the request's triplet count the kernel rule
+// follows (0: T - 2)
+int compute_flow_sequence(b2f_ctx *c, int T, const void *frames, bool bytes_in, int H0, int W0, double *flow, unsigned char *fwd_occ,
+                          unsigned char *bwd_occ, int req);
 // pieces of b2f_api.hip the generic graph executor (b2f_graph.hip) builds on
 ConvSeg cp8_seg(const float *ptr, int C, size_t hw);
 int find_conv_id(const b2f_ctx *c, int kind, int level, int idx);

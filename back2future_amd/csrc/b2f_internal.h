@@ -274,6 +274,12 @@ hipError_t launch_conv_first(const float *in, int normalize, int B, int H, int W
 // warp frame `frame` of the planar input (normalized on the fly) by k * planar flow
 hipError_t launch_warp_input_planar(const float *in, int normalize, int frame, const float *flow_planar,
                                     float k, int B, int H, int W, float *out, hipStream_t s);
+// b2f_seq.hip, sequence mode (frame-major T x 3 x H x W input, in_kind = B2F_IN_NORMALIZED | B2F_IN_UNIT | B2F_IN_U8):
+// first pyramid layer of every frame -> chunk-planar [T][2][H/2*W/2][8]; warp of frame b (the first frame of triplet b)
+hipError_t launch_conv_first_seq(const void *in, int in_kind, int T, int H, int W, const float *wt, const float *bias,
+                                 float *out, hipStream_t s);
+hipError_t launch_warp_input_seq(const void *in, int in_kind, const float *flow_planar, float k, int B, int H, int W,
+                                 float *out, hipStream_t s);
 // nn.BilinearSamplerBHWD forward (CUDA semantics), grid scaled by k
 hipError_t launch_warp_nhwc(const float *img, long img_stride, int pix_stride, int C, int ih,
                             int iw, const float *grid, float k, int B, int gh, int gw,

@@ -282,4 +282,34 @@ int b2f_multi_compute_flow_batch_u8(b2f_multi *m, int n, const unsigned char *im
 }
 B2F_CATCH("b2f_multi_compute_flow_batch_u8")
 
+// The T - 2 triplets of a sequence are sharded like a batch; replica i reads frames [lo, hi + 2) and writes outputs [lo, hi).
+// The kernel rule of every shard follows the caller's triplet count (req), so the bits do not depend on the number of GPUs.
+static int multi_sequence(b2f_multi *m, int T, const void *frames, bool bytes_in, int H0, int W0, double *flow, unsigned char *fwd_occ,
+                          unsigned char *bwd_occ, const char *who)
+{
+    if (!m || !frames || !flow || !fwd_occ || !bwd_occ) return api_fail(std::string(who) + ": null argument");
+    if (T < 3) return api_fail(std::string(who) + ": a sequence needs T >= 3 frames (one triplet)");
+    if (H0 <= 0 || W0 <= 0) return api_fail(std::string(who) + ": bad shape");
+    const size_t hw = (size_t)H0 * W0, esz = bytes_in ? 1 : 4;
+    const int n = T - 2;
+    return run_sharded(m, n, [&](int i, int lo, int hi) {
+        return compute_flow_sequence(m->ctx[(size_t)i], hi - lo + 2, (const char *)frames + (size_t)lo * 3 * hw * esz, bytes_in, H0, W0,
+                                     flow + (size_t)lo * 2 * hw, fwd_occ + (size_t)lo * hw, bwd_occ + (size_t)lo * hw, n);
+    });
+}
+
+int b2f_multi_compute_flow_sequence(b2f_multi *m, int T, const float *frames, int H0, int W0, double *flow, unsigned char *fwd_occ,
+                                    unsigned char *bwd_occ) try
+{
+    return multi_sequence(m, T, frames, false, H0, W0, flow, fwd_occ, bwd_occ, "b2f_multi_compute_flow_sequence");
+}
+B2F_CATCH("b2f_multi_compute_flow_sequence")
+
+int b2f_multi_compute_flow_sequence_u8(b2f_multi *m, int T, const unsigned char *frames, int H0, int W0, double *flow,
+                                       unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return multi_sequence(m, T, frames, true, H0, W0, flow, fwd_occ, bwd_occ, "b2f_multi_compute_flow_sequence_u8");
+}
+B2F_CATCH("b2f_multi_compute_flow_sequence_u8")
+
 }  // extern "C"

@@ -174,6 +174,39 @@ B2F_API int b2f_multi_compute_flow_batch_u8(b2f_multi *m, int n, const unsigned 
 enum { B2F_IN_NORMALIZED = 0, B2F_IN_UNIT = 1 };
 B2F_API int b2f_forward_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int B, int H, int W,
                        float *dev_flow, float *dev_occ, float *dev_est3, void *stream);
+/* ---- the hot path on a video: one flow per centre frame ----
+ * dev_frames: T x 3 x H x W planar frames on the GPU, frame-major, H and W multiples of 64;
+ * output i (i = 0 .. T-3) is what b2f_forward_device returns for the triplet of frames
+ * (i, i+1, i+2), bit for bit, but the siamese feature pyramid (pwc.lua:169-211) runs once
+ * per frame (T images) instead of three times (3 (T-2) images).  in_kind:
+ * B2F_IN_NORMALIZED / B2F_IN_UNIT as for b2f_forward_device (fp32 samples), or B2F_IN_U8 =
+ * 8-bit samples (value = byte / 255, what image.load makes of an 8-bit file) read as they
+ * are, with no float copy of the frames.  Outputs (any may be NULL), planar fp32 on the GPU:
+ *   dev_flow  (T-2) x 2 x H x W,  dev_occ  (T-2) x 2 x H x W,  dev_est3  (T-2) x C3 x H x W
+ * (same meaning as for b2f_forward_device).  T >= 3; the shipped graph only (a context made
+ * with b2f_init_ex options, two_frame among them, is refused); every device pointer
+ * 16-byte aligned.  Asynchronous on `stream` like b2f_forward_device; with use_graph = 1
+ * its launches are replayed from a hipGraph of their own, never one of a triplet call.   */
+enum { B2F_IN_U8 = 2 };   /* sequence entry only: bytes, value = byte / 255 */
+B2F_API int b2f_forward_sequence_device(b2f_ctx *ctx, const void *dev_frames, int in_kind, int T, int H, int W,
+                                float *dev_flow, float *dev_occ, float *dev_est3, void *stream);
+/* The same from host memory, with computeFlow's boundary (back2future.lua:47-95) around every
+ * output: frames T x 3 x H0 x W0 in [0,1] (floats) or 8-bit (value = byte / 255); flow
+ * (T-2) x 2 x H0 x W0 doubles, fwd_occ / bwd_occ (T-2) x H0 x W0 bytes -- output i equals
+ * b2f_compute_flow(frames[i], frames[i+1], frames[i+2]).  Each frame crosses the link once
+ * (the two frames a sub-batch shares with the next one twice), float frames that are all
+ * k / 255 as bytes; pinned caller buffers are DMA'd in place, as in b2f_compute_flow_batch.  */
+B2F_API int b2f_compute_flow_sequence(b2f_ctx *ctx, int T, const float *frames, int H0, int W0,
+                              double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_compute_flow_sequence_u8(b2f_ctx *ctx, int T, const unsigned char *frames, int H0, int W0,
+                                 double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* Several GPUs: the T-2 triplets are split with b2f_shard_range; replica i reads frames
+ * [lo, hi+2) and writes outputs [lo, hi).  Same arguments and results as the single-context
+ * entry points.                                                                             */
+B2F_API int b2f_multi_compute_flow_sequence(b2f_multi *m, int T, const float *frames, int H0, int W0,
+                                    double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_sequence_u8(b2f_multi *m, int T, const unsigned char *frames, int H0, int W0,
+                                       double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
 /* Full output table of model:forward (pwc.lua:459-489) into n_outs host buffers, in
  * table order; x is B x 9 x H x W normalized host memory.                           */
 B2F_API int b2f_forward(b2f_ctx *ctx, const float *x, int B, int H, int W, float **outs, int n_outs);

@@ -6,6 +6,7 @@
 --   computeFlow = back2future.init('Ours-Soft-ft-KITTI')
 --   flow, fwd_occ, bwd_occ = computeFlow(im1, im2, im3)
 --
+-- local computeFlow, computeFlowSequence = back2future.init(opt): the second closure takes a whole video.
 -- Same module table (init, normalize), same argument and return order and types
 -- as back2future.lua:45-130: im* are 3xHxW torch tensors in [0,1] (image.load),
 -- flow is a 2xHxW torch.DoubleTensor, the masks are 1xHxW torch.ByteTensor.
@@ -29,6 +30,10 @@ void b2f_destroy(b2f_ctx *ctx);
 int  b2f_info(const b2f_ctx *ctx, int *levels, int *win, int *past_flow, int *n_outputs, long long *n_params);
 int  b2f_compute_flow(b2f_ctx *ctx, const float *im1, const float *im2, const float *im3,
                       int H0, int W0, double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int  b2f_compute_flow_sequence(b2f_ctx *ctx, int T, const float *frames, int H0, int W0,
+                               double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int  b2f_compute_flow_sequence_u8(b2f_ctx *ctx, int T, const unsigned char *frames, int H0, int W0,
+                                  double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -85,7 +90,28 @@ local function init(opt)
                                  flow_est:data(), fwd_occ_est:data(), bwd_occ_est:data()))
       return flow_est, fwd_occ_est, bwd_occ_est
    end
-   return computeFlow
+
+   -- a video: frames is a T x 3 x H x W tensor (FloatTensor in [0,1], or ByteTensor: value = byte / 255); returns the
+   -- (T-2) x 2 x H x W flow and (T-2) x 1 x H x W masks, entry i = computeFlow(frames[i], frames[i+1], frames[i+2])
+   local computeFlowSequence = function(frames)
+      assert(frames:dim() == 4 and frames:size(2) == 3, 'expected T x 3 x H x W frames')
+      local T, height, width = frames:size(1), frames:size(3), frames:size(4)
+      assert(T >= 3, 'a sequence needs T >= 3 frames')
+      local flow_est = torch.DoubleTensor(T - 2, 2, height, width)
+      local fwd_occ_est = torch.ByteTensor(T - 2, 1, height, width)
+      local bwd_occ_est = torch.ByteTensor(T - 2, 1, height, width)
+      if torch.type(frames) == 'torch.ByteTensor' then
+         local f = frames:contiguous()
+         check(lib.b2f_compute_flow_sequence_u8(ctx, T, f:data(), height, width,
+                                                flow_est:data(), fwd_occ_est:data(), bwd_occ_est:data()))
+      else
+         local f = frames:float():contiguous()
+         check(lib.b2f_compute_flow_sequence(ctx, T, f:data(), height, width,
+                                             flow_est:data(), fwd_occ_est:data(), bwd_occ_est:data()))
+      end
+      return flow_est, fwd_occ_est, bwd_occ_est
+   end
+   return computeFlow, computeFlowSequence
 end
 M.init = init
 
