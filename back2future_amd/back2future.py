@@ -20,7 +20,7 @@ from . import _lib
 meanstd = {"mean": [0.485, 0.456, 0.406], "std": [0.229, 0.224, 0.225]}   # back2future.lua:33-36
 occ_threshold = 0.6666                                                     # back2future.lua:40
 
-# in_kind of the device entry points (include/b2f.h); IN_U8 is taken by the sequence entry only
+# in_kind of the device entry points (include/b2f.h); IN_U8 is taken by the sequence and float32 entries only
 IN_NORMALIZED, IN_UNIT, IN_U8 = 0, 1, 2
 
 
@@ -66,6 +66,70 @@ def _sequence_outputs(n, H0, W0, out):
             assert m.dtype == np.uint8 and m.shape == (n, 1, H0, W0) and m.flags.c_contiguous
         return flow, fwd, bwd
     return np.empty((n, 2, H0, W0), np.float64), np.empty((n, 1, H0, W0), np.uint8), np.empty((n, 1, H0, W0), np.uint8)
+
+
+def output_dtype(dtype, occ_prob, who):
+    """The `dtype=` / `occ_prob=` keywords of the computeFlow* wrappers: float64 (the f64 entries, the default) or float32
+    (the b2f_*_f32 entries); occ_prob=True needs float32.  Raises ValueError before any library call."""
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        raise ValueError("%s: dtype must be np.float64 or np.float32, got %r" % (who, dtype))
+    if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("%s: dtype must be np.float64 or np.float32, got %s" % (who, dt))
+    if occ_prob and dt != np.float32:
+        raise ValueError("%s: occ_prob=True needs dtype=np.float32 (the float64 entries have no occlusion probabilities)" % who)
+    return dt
+
+
+def _f32_outputs(n, H0, W0, occ_prob, out, who):
+    """(flow, fwd, bwd, occ_prob or None) for the f32 entries.  out = (flow float32 n x 2 x H x W, fwd uint8 n x 1 x H x W, bwd
+    [, occ_prob float32 n x 2 x H x W]) with occ_prob=True; fwd / bwd may be None (the masks are then not computed)."""
+    if out is None:
+        return (np.empty((n, 2, H0, W0), np.float32), np.empty((n, 1, H0, W0), np.uint8), np.empty((n, 1, H0, W0), np.uint8),
+                np.empty((n, 2, H0, W0), np.float32) if occ_prob else None)
+    out = tuple(out)
+    if len(out) != (4 if occ_prob else 3):
+        raise ValueError("%s: out must be (flow, fwd_occ, bwd_occ%s)" % (who, ", occ_prob" if occ_prob else ""))
+    spec = [(np.float32, (n, 2, H0, W0)), (np.uint8, (n, 1, H0, W0)), (np.uint8, (n, 1, H0, W0)), (np.float32, (n, 2, H0, W0))]
+    for i, (a, (dt, shape)) in enumerate(zip(out, spec)):
+        if a is None and i in (1, 2):
+            continue
+        if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError("%s: out[%d] must be a writeable C-contiguous %s array of shape %s" % (who, i, np.dtype(dt).name, shape))
+    return out + ((None,) if not occ_prob else ())
+
+
+def _call_f32(fn, h, count, in_kind, ins, H0, W0, outs, occ_prob):
+    flow, fwd, bwd, occ = outs
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+    _lib.check(getattr(_lib.lib(), fn)(h, count, in_kind, *[C.c_void_p(a.ctypes.data) for a in ins], H0, W0, _lib.fptr(flow),
+                                       _lib.fptr(occ) if occ is not None else None, u8p(fwd), u8p(bwd)))
+    return (flow, fwd, bwd) + ((occ,) if occ_prob else ())
+
+
+def _batch_inputs(im1, im2, im3):
+    as_bytes = all(np.asarray(a).dtype == np.uint8 for a in (im1, im2, im3))
+    if as_bytes:
+        im1, im2, im3 = (np.ascontiguousarray(a) for a in (im1, im2, im3))
+    else:
+        im1, im2, im3 = _lib.f32(im1), _lib.f32(im2), _lib.f32(im3)
+    assert im1.ndim == 4 and im1.shape == im2.shape == im3.shape and im1.shape[1] == 3, "expected three n x 3 x H x W arrays"
+    return im1, im2, im3, as_bytes
+
+
+def _call_batch_f32(fn, h, im1, im2, im3, out, occ_prob, who):
+    im1, im2, im3, as_bytes = _batch_inputs(im1, im2, im3)
+    n, _, H0, W0 = im1.shape
+    outs = _f32_outputs(n, H0, W0, occ_prob, out, who)
+    return _call_f32(fn, h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0, outs, occ_prob)
+
+
+def _call_sequence_f32(fn, h, frames, out, occ_prob, who):
+    v, as_bytes = sequence_frames(frames)
+    T, _, H0, W0 = v.shape
+    outs = _f32_outputs(T - 2, H0, W0, occ_prob, out, who)
+    return _call_f32(fn, h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0, outs, occ_prob)
 
 
 def _call_sequence(fn_f32, fn_u8, h, frames, out):
@@ -185,11 +249,16 @@ class Model(object):
             bwd.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return flow, fwd, bwd
 
-    def computeFlowBatch(self, im1, im2, im3, out=None):
+    def computeFlowBatch(self, im1, im2, im3, out=None, dtype=np.float64, occ_prob=False):
         """n independent triplets at once: inputs n x 3 x H x W.  The library pipelines sub-batches through
         pinned staging buffers; inputs / `out` = (flow f64 n x 2 x H x W, fwd u8 n x 1 x H x W, bwd) that already
         live in page-locked memory (e.g. views of torch pin_memory() tensors) are DMA'd in place instead.
-        uint8 inputs (frames as decoded from 8-bit files, value = byte / 255) are uploaded as bytes."""
+        uint8 inputs (frames as decoded from 8-bit files, value = byte / 255) are uploaded as bytes.
+        dtype=np.float32 (b2f_compute_flow_batch_f32): the flow is the float64 one rounded to float32, bit for bit, and
+        never widened on the host; occ_prob=True (float32 only) appends the n x 2 x H x W occlusion probabilities to the
+        returned tuple.  `out` then holds float32 flow / occ_prob buffers, and its masks may be None (not computed)."""
+        if output_dtype(dtype, occ_prob, "computeFlowBatch") == np.float32:
+            return _call_batch_f32("b2f_compute_flow_batch_f32", self._h, im1, im2, im3, out, occ_prob, "computeFlowBatch")
         as_bytes = all(np.asarray(a).dtype == np.uint8 for a in (im1, im2, im3))
         if as_bytes:
             im1, im2, im3 = (np.ascontiguousarray(a) for a in (im1, im2, im3))
@@ -215,11 +284,35 @@ class Model(object):
             _lib.check(_lib.lib().b2f_compute_flow_batch(self._h, n, _lib.fptr(im1), _lib.fptr(im2), _lib.fptr(im3), H0, W0, *outp))
         return flow, fwd, bwd
 
-    def computeFlowSequence(self, frames, out=None):
+    def computeFlowSequence(self, frames, out=None, dtype=np.float64, occ_prob=False):
         """Flow for every centre frame of a video: frames is a T x 3 x H x W float32 or uint8 array (or a list of 3 x H x W
         arrays); output i is computeFlow(frames[i], frames[i+1], frames[i+2]), i = 0 .. T-3, with the shapes and dtypes of
-        computeFlowBatch.  Every frame is uploaded and run through the feature pyramid once (b2f_compute_flow_sequence)."""
+        computeFlowBatch.  Every frame is uploaded and run through the feature pyramid once (b2f_compute_flow_sequence).
+        dtype / occ_prob / out as for computeFlowBatch (dtype=np.float32: b2f_compute_flow_sequence_f32)."""
+        if output_dtype(dtype, occ_prob, "computeFlowSequence") == np.float32:
+            return _call_sequence_f32("b2f_compute_flow_sequence_f32", self._h, frames, out, occ_prob, "computeFlowSequence")
         return _call_sequence("b2f_compute_flow_sequence", "b2f_compute_flow_sequence_u8", self._h, frames, out)
+
+    def computeFlowDevice(self, d_im1, d_im2, d_im3, n, H0, W0, d_flow, d_occ_prob=None, d_fwd_occ=None, d_bwd_occ=None,
+                          in_kind=IN_UNIT, stream=None):
+        """b2f_compute_flow_device on device pointers (ints): computeFlowBatch(dtype=np.float32) on frames that are already
+        in GPU memory, any H0 x W0.  d_im1..3: n x 3 x H0 x W0 float32 in [0,1] (in_kind=IN_UNIT) or uint8 (IN_U8);
+        d_flow / d_occ_prob: n x 2 x H0 x W0 float32, the masks n x H0 x W0 uint8 (all but d_flow may be None).
+        Asynchronous on `stream`."""
+        p = lambda v: C.c_void_p(v) if v else None
+        _lib.check(_lib.lib().b2f_compute_flow_device(self._h, int(n), int(in_kind), p(d_im1), p(d_im2), p(d_im3), int(H0), int(W0),
+                                                       p(d_flow), p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream)))
+
+    def computeFlowSequenceDevice(self, d_frames, T, H0, W0, d_flow, d_occ_prob=None, d_fwd_occ=None, d_bwd_occ=None,
+                                  in_kind=IN_UNIT, stream=None):
+        """b2f_compute_flow_sequence_device on device pointers (ints): computeFlowSequence(dtype=np.float32) on T x 3 x H0 x W0
+        device frames (float32 in [0,1] with in_kind=IN_UNIT, uint8 with IN_U8); outputs as computeFlowDevice with n = T - 2.
+        Asynchronous on `stream`."""
+        if T < 3:
+            raise ValueError("computeFlowSequenceDevice: a sequence needs T >= 3 frames, got %d" % T)
+        p = lambda v: C.c_void_p(v) if v else None
+        _lib.check(_lib.lib().b2f_compute_flow_sequence_device(self._h, int(T), int(in_kind), p(d_frames), int(H0), int(W0), p(d_flow),
+                                                                p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream)))
 
     def output_shapes(self, H, W):
         cap = 32
@@ -291,7 +384,10 @@ class MultiModel(object):
         for i in range(self.n_gpus):
             _lib.check(_lib.lib().b2f_set_option(C.c_void_p(_lib.lib().b2f_multi_context(self._h, i)), key.encode(), int(value)))
 
-    def computeFlowBatch(self, im1, im2, im3):
+    def computeFlowBatch(self, im1, im2, im3, out=None, dtype=np.float64, occ_prob=False):
+        """Model.computeFlowBatch over the GPUs, with the same keywords."""
+        if output_dtype(dtype, occ_prob, "computeFlowBatch") == np.float32:
+            return _call_batch_f32("b2f_multi_compute_flow_batch_f32", self._h, im1, im2, im3, out, occ_prob, "computeFlowBatch")
         as_bytes = all(np.asarray(a).dtype == np.uint8 for a in (im1, im2, im3))
         if as_bytes:
             im1, im2, im3 = (np.ascontiguousarray(a) for a in (im1, im2, im3))
@@ -299,9 +395,7 @@ class MultiModel(object):
             im1, im2, im3 = _lib.f32(im1), _lib.f32(im2), _lib.f32(im3)
         n, _, H0, W0 = im1.shape
         assert im1.shape == im2.shape == im3.shape and im1.shape[1] == 3, "expected three n x 3 x H x W arrays"
-        flow = np.empty((n, 2, H0, W0), np.float64)
-        fwd = np.empty((n, 1, H0, W0), np.uint8)
-        bwd = np.empty((n, 1, H0, W0), np.uint8)
+        flow, fwd, bwd = _sequence_outputs(n, H0, W0, out)
         outp = (flow.ctypes.data_as(C.POINTER(C.c_double)), fwd.ctypes.data_as(C.POINTER(C.c_ubyte)),
                 bwd.ctypes.data_as(C.POINTER(C.c_ubyte)))
         if as_bytes:
@@ -311,9 +405,11 @@ class MultiModel(object):
             _lib.check(_lib.lib().b2f_multi_compute_flow_batch(self._h, n, _lib.fptr(im1), _lib.fptr(im2), _lib.fptr(im3), H0, W0, *outp))
         return flow, fwd, bwd
 
-    def computeFlowSequence(self, frames, out=None):
+    def computeFlowSequence(self, frames, out=None, dtype=np.float64, occ_prob=False):
         """Model.computeFlowSequence over the GPUs: the T-2 triplets are split with shard_range, every replica reads the
-        frames its triplets need (T_i = its triplets + 2)."""
+        frames its triplets need (T_i = its triplets + 2).  dtype / occ_prob / out as for Model.computeFlowSequence."""
+        if output_dtype(dtype, occ_prob, "computeFlowSequence") == np.float32:
+            return _call_sequence_f32("b2f_multi_compute_flow_sequence_f32", self._h, frames, out, occ_prob, "computeFlowSequence")
         return _call_sequence("b2f_multi_compute_flow_sequence", "b2f_multi_compute_flow_sequence_u8", self._h, frames, out)
 
 

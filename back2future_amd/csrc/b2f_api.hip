@@ -940,6 +940,7 @@ void b2f_destroy(b2f_ctx *c)
     }
     if (c->s_in) (void)hipStreamDestroy(c->s_in);
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
+    if (c->dwork.dev) (void)hipFree(c->dwork.dev);
     if (c->arena) (void)hipFree(c->arena);
     if (c->wpk_dev) (void)hipFree(c->wpk_dev);
     if (c->w_dev) (void)hipFree(c->w_dev);

@@ -1,7 +1,7 @@
 // Device side of the computeFlow boundary (/root/reference/back2future.lua:48-93): what the reference does on the
 // host around model:forward -- ColorNormalize, image.scale(..., W, H) 'bilinear' down to multiples of 64, and
 // after the forward pass image.scale(..., 'simple') back to the input size and the 0.6666 thresholds -- runs here
-// on the uploaded planes, so the host only moves bytes (and widens the flow to f64, b2f_pipeline.hip).  The arithmetic
+// on the uploaded planes, so the host only moves bytes (and, on the f64 entries, widens the flow, b2f_pipeline.hip).  The arithmetic
 // is the CPU routines' (oracle/b2f_oracle.c) operation for operation: every output element is produced by one
 // thread with the same sequence of IEEE fp32 operations (the file is built with -ffp-contract=off and correctly
 // rounded division), so the results are bit-identical to the CPU ones.
@@ -109,6 +109,109 @@ hipError_t launch_postprocess(const float *flow_net, const float *est3, int est3
     const size_t n = (size_t)B * H0 * W0;
     hipLaunchKernelGGL(postprocess_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, flow_net, est3, est3_ch, B, fh,
                        fw, H0, W0, flow32, fwd_occ, bwd_occ);
+    return hipGetLastError();
+}
+
+// The float32 outputs of b2f_compute_flow*_f32 / b2f_compute_flow*_device, from the network's outputs at fh x fw to
+// H0 x W0 with postprocess_kernel's index rule:
+//   flow      (float)((double)est[1] * sc)   (sc_w for channel 0, sc_h for 1): the f64 entries' value rounded to nearest
+//   occ_prob  skip_occs[3] (occ: [B][2][fh][fw]; est[3] of a Soft model, est[2] of a Hard one)
+//   fwd_occ / bwd_occ  the thresholds of est[3] channels 2 / 1, as postprocess_kernel
+// Any output may be nullptr.  One thread per kOutPx consecutive pixels of an output row: 16-byte stores (4-byte for the
+// masks) where the row holds them and the address is aligned, scalar stores for a row's tail and misaligned rows.  When
+// the column map is the identity (fw == W0, so the 4 source samples are consecutive and 16-byte aligned) the planes are
+// read with 16-byte loads too (kVec: a separate instantiation, so that the compiler cannot fold the two load paths into one).
+constexpr int kOutPx = 4;
+
+template <bool kVec>
+__device__ __forceinline__ float4 gather4(const float *p, const size_t *s)
+{
+    if (kVec) return *reinterpret_cast<const float4 *>(p + s[0]);
+    return make_float4(p[s[0]], p[s[1]], p[s[2]], p[s[3]]);
+}
+
+__device__ __forceinline__ void store4(float *dst, float4 v, int n)
+{
+    if (n == kOutPx && ((uintptr_t)dst & 15) == 0) {
+        *reinterpret_cast<float4 *>(dst) = v;
+        return;
+    }
+    const float e[4] = {v.x, v.y, v.z, v.w};
+    for (int k = 0; k < n; ++k) dst[k] = e[k];
+}
+
+__device__ __forceinline__ void store4(unsigned char *dst, const unsigned char *e, int n)
+{
+    if (n == kOutPx && ((uintptr_t)dst & 3) == 0) {
+        *reinterpret_cast<uchar4 *>(dst) = make_uchar4(e[0], e[1], e[2], e[3]);
+        return;
+    }
+    for (int k = 0; k < n; ++k) dst[k] = e[k];
+}
+
+template <bool kVec>
+__global__ void outputs_f32_kernel(const float *flow_net, const float *occ, const float *est3, int est3_ch, int B, int fh, int fw,
+                                   int H0, int W0, double sc_w, double sc_h, float *flow, float *occ_prob, unsigned char *fwd_occ,
+                                   unsigned char *bwd_occ)
+{
+    const size_t hw0 = (size_t)H0 * W0, hw = (size_t)fh * fw;
+    const size_t nq = ((size_t)W0 + kOutPx - 1) / kOutPx;   // pixel groups per output row
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)B * H0 * nq) return;
+    const size_t row = t / nq, b = row / H0;
+    const int j = (int)(row - b * H0), i0 = (int)(t - row * nq) * kOutPx;
+    const int n = min(kOutPx, W0 - i0);
+    // image.scale 'simple' [3P]: src index = (long)(dst * (float)src_len / dst_len), clamped -- postprocess_kernel's arithmetic
+    const float scx = (float)fw / (float)W0, scy = (float)fh / (float)H0;
+    long jj = (long)((float)j * scy);
+    if (jj > fh - 1) jj = fh - 1;
+    size_t s[kOutPx];
+    for (int k = 0; k < kOutPx; ++k) {
+        const int i = i0 + min(k, n - 1);   // the tail repeats its last pixel: in-bounds loads, never stored
+        long ii = (long)((float)i * scx);
+        if (ii > fw - 1) ii = fw - 1;
+        s[k] = (size_t)jj * fw + ii;
+    }
+    const size_t d = (size_t)j * W0 + i0;   // first pixel of the group in an output plane
+    if (flow) {
+        const float *fn = flow_net + b * 2 * hw;
+        for (int ch = 0; ch < 2; ++ch) {
+            const float4 v = gather4<kVec>(fn + ch * hw, s);
+            const double sc = ch == 0 ? sc_w : sc_h;
+            store4(flow + (b * 2 + ch) * hw0 + d,
+                   make_float4((float)((double)v.x * sc), (float)((double)v.y * sc), (float)((double)v.z * sc), (float)((double)v.w * sc)), n);
+        }
+    }
+    if (occ_prob) {
+        const float *op = occ + b * 2 * hw;
+        for (int ch = 0; ch < 2; ++ch) store4(occ_prob + (b * 2 + ch) * hw0 + d, gather4<kVec>(op + ch * hw, s), n);
+    }
+    if (fwd_occ || bwd_occ) {
+        const float *e3 = est3 + b * est3_ch * hw;
+        for (int ch = 0; ch < 2; ++ch) {   // bwd_occ = ge(est[3][1]), fwd_occ = ge(est[3][2])
+            unsigned char *m = ch == 0 ? bwd_occ : fwd_occ;
+            if (!m) continue;
+            const float4 v = gather4<kVec>(e3 + ch * hw, s);
+            const unsigned char e[4] = {(double)v.x >= 0.6666, (double)v.y >= 0.6666, (double)v.z >= 0.6666, (double)v.w >= 0.6666};
+            store4(m + b * hw0 + d, e, n);
+        }
+    }
+}
+
+hipError_t launch_outputs_f32(const float *flow_net, const float *occ, const float *est3, int est3_ch, int B, int fh, int fw, int H0,
+                              int W0, double sc_w, double sc_h, float *flow, float *occ_prob, unsigned char *fwd_occ,
+                              unsigned char *bwd_occ, hipStream_t s)
+{
+    if (!flow && !occ_prob && !fwd_occ && !bwd_occ) return hipSuccess;
+    const size_t n = (size_t)B * H0 * (((size_t)W0 + kOutPx - 1) / kOutPx);
+    // fw == W0: the column map is the identity and every group of 4 source samples 16-byte aligned (fw and the planes' offsets
+    // are multiples of 64 floats; the network buffers are 256-byte aligned)
+    if (fw == W0)
+        hipLaunchKernelGGL(outputs_f32_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, flow_net, occ, est3, est3_ch, B, fh,
+                           fw, H0, W0, sc_w, sc_h, flow, occ_prob, fwd_occ, bwd_occ);
+    else
+        hipLaunchKernelGGL(outputs_f32_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, flow_net, occ, est3, est3_ch, B, fh,
+                           fw, H0, W0, sc_w, sc_h, flow, occ_prob, fwd_occ, bwd_occ);
     return hipGetLastError();
 }
 

@@ -72,12 +72,30 @@ struct HostSlot {
     size_t pin_bytes = 0;
     unsigned char *d_u8 = nullptr;   // 8-bit transport of the input planes (see pack_u8_piece)
     float *d_up = nullptr, *d_tmp = nullptr, *d_in = nullptr, *d_flow = nullptr, *d_est3 = nullptr;
-    float *d_flow32 = nullptr;       // flow at H0 x W0 (fp32, before the f64 sc_w / sc_h factors); = d_flow without a rescale
+    float *d_flow32 = nullptr;       // flow at H0 x W0 (fp32; f64 path: before the sc_w / sc_h factors); = d_flow without a rescale
+    float *d_occ = nullptr;          // f32 path of a Hard model with occ_prob: skip_occs[3] at the network size (Soft: it is d_est3)
+    float *d_prob = nullptr;         // f32 path: occ_prob at H0 x W0; unused without a rescale (the network's planes go down as they are)
     unsigned char *d_fo = nullptr, *d_bo = nullptr;
     unsigned char *h_u8 = nullptr;
-    float *h_in = nullptr, *h_flow32 = nullptr;
+    float *h_in = nullptr, *h_flow32 = nullptr, *h_prob = nullptr;
     unsigned char *h_fo = nullptr, *h_bo = nullptr;
     hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
+};
+
+// Where computeFlow's outputs go (host pointers for b2f_compute_flow*, device pointers for b2f_compute_flow*_device).  The
+// f64 path (flow64, both masks required) is the b2f_compute_flow* entries'; the f32 path (flow32) writes the same flow
+// rounded to fp32 and, when not nullptr, the occlusion probabilities and the masks.
+struct FlowOutputs {
+    double *flow64 = nullptr;
+    float *flow32 = nullptr, *occ_prob = nullptr;
+    unsigned char *fwd_occ = nullptr, *bwd_occ = nullptr;
+    bool f32() const { return flow64 == nullptr; }
+};
+
+// Context-owned device workspace of the device entries (b2f_compute_flow_device / _sequence_device): grows, never shrinks.
+struct DevWork {
+    char *dev = nullptr;
+    size_t bytes = 0;
 };
 
 // Host work items of the pipeline, cut into pieces and spread over a pool of threads.
@@ -281,6 +299,7 @@ struct b2f_ctx {
     hipStream_t s_in = nullptr, s_out = nullptr;
     b2f::HostSlot slot[2];
     std::unique_ptr<b2f::CopyPool> pool_in, pool_out;
+    b2f::DevWork dwork;           // b2f_compute_flow_device / b2f_compute_flow_sequence_device
 };
 
 #define HIPCHK(expr)                                                                         \
@@ -312,6 +331,14 @@ int forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, in
 // follows (0: T - 2)
 int compute_flow_sequence(b2f_ctx *c, int T, const void *frames, bool bytes_in, int H0, int W0, double *flow, unsigned char *fwd_occ,
                           unsigned char *bwd_occ, int req);
+// b2f_pipeline.hip: the f32 host entries (b2f_compute_flow_batch_f32 / _sequence_f32) on `count` triplets or, with seq, count = T
+// frames in im1 (im2 / im3 unused), with the request size req of the kernel rule (0: the triplets); `who` names the entry point in
+// error messages
+int compute_flow_f32(b2f_ctx *c, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
+                     const FlowOutputs &o, int req, const char *who);
+// argument checks of the f32 entries that need no context and no HIP call (in_kind, T / n, shape, output pointers); 0 = fine
+int check_f32_args(const char *who, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
+                   const float *flow);
 // pieces of b2f_api.hip the generic graph executor (b2f_graph.hip) builds on
 ConvSeg cp8_seg(const float *ptr, int C, size_t hw);
 int find_conv_id(const b2f_ctx *c, int kind, int level, int idx);

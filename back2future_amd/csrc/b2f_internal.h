@@ -318,6 +318,11 @@ hipError_t launch_image_scale(const float *src, int normalize, long planes, int 
 // written, the net size is the output size), u8 masks
 hipError_t launch_postprocess(const float *flow_net, const float *est3, int est3_ch, int B, int fh, int fw, int H0, int W0,
                               float *flow32, unsigned char *fwd_occ, unsigned char *bwd_occ, hipStream_t s);
+// the float32 outputs (b2f_*_f32, b2f_compute_flow*_device): flow = (float)((double)est[1] * sc_w | sc_h), occ_prob = occ, the
+// masks of postprocess, all nearest-rescaled to H0 x W0 with postprocess's index rule; nullptr outputs are not written
+hipError_t launch_outputs_f32(const float *flow_net, const float *occ, const float *est3, int est3_ch, int B, int fh, int fw, int H0,
+                              int W0, double sc_w, double sc_h, float *flow, float *occ_prob, unsigned char *fwd_occ,
+                              unsigned char *bwd_occ, hipStream_t s);
 // out[i] = in[i] / 255 (correctly rounded): device end of the 8-bit input transport
 hipError_t launch_unpack_u8(const unsigned char *in, size_t n, float *out, hipStream_t s);
 

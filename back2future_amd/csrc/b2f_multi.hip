@@ -298,6 +298,24 @@ static int multi_sequence(b2f_multi *m, int T, const void *frames, bool bytes_in
     });
 }
 
+// The f32 entries: batch and sequence sharded as above; both pass the caller's triplet count down as the kernel-rule request
+// size (multi_sequence's rule), so a triplet's bits do not depend on the number of GPUs.  count = n triplets, or T frames (seq).
+static int multi_f32(b2f_multi *m, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
+                     const FlowOutputs &o, const char *who)
+{
+    CHK(check_f32_args(who, count, in_kind, im1, im2, im3, seq, H0, W0, o.flow32));
+    if (!m) return api_fail(std::string(who) + ": null context");
+    const size_t hw = (size_t)H0 * W0, esz = in_kind == B2F_IN_U8 ? 1 : 4;
+    const int n = seq ? count - 2 : count;
+    auto at = [&](const void *p, int lo) { return p ? (const void *)((const char *)p + (size_t)lo * 3 * hw * esz) : nullptr; };
+    return run_sharded(m, n, [&](int i, int lo, int hi) {
+        const FlowOutputs oi{nullptr, o.flow32 + (size_t)lo * 2 * hw, o.occ_prob ? o.occ_prob + (size_t)lo * 2 * hw : nullptr,
+                             o.fwd_occ ? o.fwd_occ + (size_t)lo * hw : nullptr, o.bwd_occ ? o.bwd_occ + (size_t)lo * hw : nullptr};
+        return compute_flow_f32(m->ctx[(size_t)i], seq ? hi - lo + 2 : hi - lo, in_kind, at(im1, lo), at(im2, lo), at(im3, lo), seq, H0, W0, oi, n,
+                                who);
+    });
+}
+
 int b2f_multi_compute_flow_sequence(b2f_multi *m, int T, const float *frames, int H0, int W0, double *flow, unsigned char *fwd_occ,
                                     unsigned char *bwd_occ) try
 {
@@ -311,5 +329,21 @@ int b2f_multi_compute_flow_sequence_u8(b2f_multi *m, int T, const unsigned char 
     return multi_sequence(m, T, frames, true, H0, W0, flow, fwd_occ, bwd_occ, "b2f_multi_compute_flow_sequence_u8");
 }
 B2F_CATCH("b2f_multi_compute_flow_sequence_u8")
+
+int b2f_multi_compute_flow_batch_f32(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0,
+                                     float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return multi_f32(m, n, in_kind, im1, im2, im3, false, H0, W0, FlowOutputs{nullptr, flow, occ_prob, fwd_occ, bwd_occ},
+                     "b2f_multi_compute_flow_batch_f32");
+}
+B2F_CATCH("b2f_multi_compute_flow_batch_f32")
+
+int b2f_multi_compute_flow_sequence_f32(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0, float *flow, float *occ_prob,
+                                        unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return multi_f32(m, T, in_kind, frames, nullptr, nullptr, true, H0, W0, FlowOutputs{nullptr, flow, occ_prob, fwd_occ, bwd_occ},
+                     "b2f_multi_compute_flow_sequence_f32");
+}
+B2F_CATCH("b2f_multi_compute_flow_sequence_f32")
 
 }  // extern "C"

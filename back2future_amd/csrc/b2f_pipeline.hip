@@ -33,15 +33,25 @@ int mem_kind(const void *p, size_t bytes)
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// what a slot holds beyond the f64 path's buffers
+struct SlotNeeds {
+    bool same, stage_in, stage_masks, use_u8;
+    bool occ_net;      // d_occ: skip_occs[3] of a Hard model (f32 path with occ_prob)
+    bool prob;         // d_prob: occ_prob at H0 x W0 (f32 path with occ_prob and a rescale)
+    bool stage_flow;   // h_flow32: the f64 path always, the f32 path for a pageable flow buffer
+    bool stage_prob;   // h_prob: pageable occ_prob buffer
+};
+
 // carve the slot's device and pinned blobs for sub-batches of up to SB triplets; grows (never shrinks) the blobs
-int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0, int fw, bool same, int C3, bool stage_in,
-                bool stage_masks, bool use_u8)
+int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0, int fw, int C3, const SlotNeeds &q)
 {
-    const size_t n_up = align256((size_t)SB * 9 * hw0 * 4), n_u8 = use_u8 ? align256((size_t)SB * 9 * hw0) : 0,
+    const bool same = q.same;
+    const size_t n_up = align256((size_t)SB * 9 * hw0 * 4), n_u8 = q.use_u8 ? align256((size_t)SB * 9 * hw0) : 0,
                  n_in = same ? 0 : align256((size_t)SB * 9 * hw * 4), n_tmp = same ? 0 : align256((size_t)SB * 9 * H0 * fw * 4),
                  n_flow = align256((size_t)SB * 2 * hw * 4), n_est3 = align256((size_t)SB * C3 * hw * 4),
                  n_f32 = align256((size_t)SB * 2 * hw0 * 4), n_occ = align256((size_t)SB * hw0);
-    const size_t need_dev = n_up + n_u8 + n_in + n_tmp + n_flow + n_est3 + (same ? 0 : n_f32) + 2 * n_occ;
+    const size_t n_onet = q.occ_net ? n_flow : 0, n_prob = q.prob ? n_f32 : 0;
+    const size_t need_dev = n_up + n_u8 + n_in + n_tmp + n_flow + n_est3 + (same ? 0 : n_f32) + n_onet + n_prob + 2 * n_occ;
     if (need_dev > hs.dev_bytes) {
         if (hs.dev) {
             HIPCHK(hipDeviceSynchronize());
@@ -60,9 +70,12 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.d_flow = (float *)d; d += n_flow;
     hs.d_est3 = (float *)d; d += n_est3;
     hs.d_flow32 = same ? hs.d_flow : (float *)d; d += same ? 0 : n_f32;
+    hs.d_occ = q.occ_net ? (float *)d : nullptr; d += n_onet;
+    hs.d_prob = q.prob ? (float *)d : nullptr; d += n_prob;
     hs.d_fo = (unsigned char *)d; d += n_occ;
     hs.d_bo = (unsigned char *)d;
-    const size_t need_pin = (stage_in ? n_up : 0) + n_u8 + n_f32 + (stage_masks ? 2 * n_occ : 0);
+    const size_t n_hf = q.stage_flow ? n_f32 : 0, n_hp = q.stage_prob ? n_f32 : 0;
+    const size_t need_pin = (q.stage_in ? n_up : 0) + n_u8 + n_hf + n_hp + (q.stage_masks ? 2 * n_occ : 0);
     if (need_pin > hs.pin_bytes) {
         if (hs.pin) {
             HIPCHK(hipDeviceSynchronize());
@@ -73,10 +86,11 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
         hs.pin_bytes = need_pin;
     }
     char *h = hs.pin;
-    hs.h_in = (float *)h; h += stage_in ? n_up : 0;
+    hs.h_in = (float *)h; h += q.stage_in ? n_up : 0;
     hs.h_u8 = (unsigned char *)h; h += n_u8;
-    hs.h_flow32 = (float *)h; h += n_f32;
-    hs.h_fo = (unsigned char *)h; h += stage_masks ? n_occ : 0;
+    hs.h_flow32 = (float *)h; h += n_hf;
+    hs.h_prob = (float *)h; h += n_hp;
+    hs.h_fo = (unsigned char *)h; h += q.stage_masks ? n_occ : 0;
     hs.h_bo = (unsigned char *)h;
     for (hipEvent_t *e : {&hs.ev_in, &hs.ev_comp, &hs.ev_out})
         if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -101,11 +115,16 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
 // sub-batch go up (and through the pyramid) again there -- and runs the sequence forward; everything else is the
 // triplet pipeline with "frame" in place of "triplet" as the unit of upload, 8-bit detection and the sub-batch budget.
 // req: the request's triplet count that picks the kernel rule (0: n; b2f_multi passes the caller's count to its shards).
+// Outputs (FlowOutputs): the f64 path widens the flow on the host threads; the f32 path (b2f_*_f32) has the device write
+// every output in its final form (outputs_f32_kernel), so the drain step only copies -- or nothing at all: page-locked
+// flow / occ_prob / mask buffers are DMA'd in place -- and a NULL occ_prob or mask is neither written nor downloaded.
 namespace {
 int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, const void *im3, bool bytes_in, int H0,
-                          int W0, double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ, bool seq = false, int req = 0)
+                          int W0, const FlowOutputs &o, bool seq = false, int req = 0)
 {
-    if (!c || !im1 || (!seq && (!im2 || !im3)) || !flow || !fwd_occ || !bwd_occ) return fail("b2f_compute_flow: null argument");
+    const bool f32 = o.f32();
+    if (!c || !im1 || (!seq && (!im2 || !im3)) || (f32 ? !o.flow32 : !o.fwd_occ || !o.bwd_occ))
+        return fail("b2f_compute_flow: null argument");
     if (n <= 0 || H0 <= 0 || W0 <= 0) return fail("b2f_compute_flow: bad shape");
     if (c->debug_fail_next) {   // tests (option debug_fail_next): one forced failure, e.g. on one replica of a b2f_multi
         c->debug_fail_next = 0;
@@ -148,16 +167,25 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
     if (!c->s_out) HIPCHK(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
     const int k_in[3] = {mem_kind(im1, (size_t)(n + gu) * 3 * hw0 * esz), seq ? 1 : mem_kind(im2, (size_t)n * 3 * hw0 * esz),
                          seq ? 1 : mem_kind(im3, (size_t)n * 3 * hw0 * esz)};
-    const int k_out[3] = {mem_kind(flow, (size_t)n * 2 * hw0 * 8), mem_kind(fwd_occ, (size_t)n * hw0), mem_kind(bwd_occ, (size_t)n * hw0)};
-    for (int i = 0; i < 3; ++i)
-        if (k_in[i] < 0 || k_out[i] < 0)
-            return fail("b2f_compute_flow: device memory passed to a host-buffer entry point (use b2f_forward_device)");
+    double *flow = o.flow64;
+    unsigned char *fwd_occ = o.fwd_occ, *bwd_occ = o.bwd_occ;
+    // unrequested outputs (f32 path) count as page-locked: nothing is staged for them
+    auto out_kind = [&](const void *p, size_t bytes) { return p ? mem_kind(p, bytes) : 1; };
+    const int k_out[4] = {f32 ? out_kind(o.flow32, (size_t)n * 2 * hw0 * 4) : mem_kind(flow, (size_t)n * 2 * hw0 * 8), out_kind(fwd_occ, (size_t)n * hw0),
+                          out_kind(bwd_occ, (size_t)n * hw0), out_kind(o.occ_prob, (size_t)n * 2 * hw0 * 4)};
+    for (int i = 0; i < 4; ++i)
+        if ((i < 3 && k_in[i] < 0) || k_out[i] < 0)
+            return fail("b2f_compute_flow: device memory passed to a host-buffer entry point (use b2f_compute_flow_device / "
+                        "b2f_compute_flow_sequence_device)");
     const bool pinned_in = k_in[0] == 1 && k_in[1] == 1 && k_in[2] == 1;
     const bool stage_in = !pinned_in && !bytes_in;   // float staging buffer (byte inputs stage through h_u8)
     const bool stage_masks = !(k_out[1] == 1 && k_out[2] == 1);
+    const bool want_prob = f32 && o.occ_prob;
+    // f32 path: occ_prob is skip_occs[3] -- est[3] of a Soft model (d_est3), an extra forward output of a Hard one (d_occ)
+    SlotNeeds q{same, stage_in, stage_masks, use_u8, want_prob && C3 == 3, want_prob && !same, !f32 || k_out[0] != 1, want_prob && k_out[3] != 1};
     // (a sequence sub-batch's nb + 2 frames are 3 nb + 6 <= 9 nb planes: the triplet layout of the slot holds them)
     for (int k = 0; k < std::min(nsub, 2); ++k)
-        CHK(ensure_slot(c, c->slot[k], SB, hw0, hw, H0, fw, same, C3, stage_in, stage_masks, use_u8));
+        CHK(ensure_slot(c, c->slot[k], SB, hw0, hw, H0, fw, C3, q));
     // the calling thread and the drain thread each count as one worker of their pool
     const int w_out = std::max(0, nthreads / 3 - 1), w_in = std::max(0, nthreads - nthreads / 3 - 1);
     if (!c->pool_in || c->pool_in->workers() != w_in) c->pool_in.reset(new CopyPool(w_in));
@@ -187,14 +215,19 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
             if (e == hipSuccess) {
                 const size_t b0 = subs[k].first, nb = (size_t)subs[k].second;
                 std::vector<CopyJob> jobs;
-                // flow_est[1] * sc_w, flow_est[2] * sc_h on the :double() copy of est[1] (:80-84)
-                for (size_t t = 0; t < nb; ++t)
-                    for (int ch = 0; ch < 2; ++ch)
-                        jobs.push_back({flow + ((b0 + t) * 2 + ch) * hw0, hs.h_flow32 + (t * 2 + ch) * hw0, hw0 * 4, JOB_F32_TO_F64,
-                                        ch == 0 ? sc_w : sc_h, nullptr});
+                if (!f32) {
+                    // flow_est[1] * sc_w, flow_est[2] * sc_h on the :double() copy of est[1] (:80-84)
+                    for (size_t t = 0; t < nb; ++t)
+                        for (int ch = 0; ch < 2; ++ch)
+                            jobs.push_back({flow + ((b0 + t) * 2 + ch) * hw0, hs.h_flow32 + (t * 2 + ch) * hw0, hw0 * 4, JOB_F32_TO_F64,
+                                            ch == 0 ? sc_w : sc_h, nullptr});
+                } else {
+                    if (q.stage_flow) jobs.push_back({o.flow32 + b0 * 2 * hw0, hs.h_flow32, nb * 2 * hw0 * 4});
+                    if (q.stage_prob) jobs.push_back({o.occ_prob + b0 * 2 * hw0, hs.h_prob, nb * 2 * hw0 * 4});
+                }
                 if (stage_masks) {
-                    jobs.push_back({fwd_occ + b0 * hw0, hs.h_fo, nb * hw0});
-                    jobs.push_back({bwd_occ + b0 * hw0, hs.h_bo, nb * hw0});
+                    if (fwd_occ) jobs.push_back({fwd_occ + b0 * hw0, hs.h_fo, nb * hw0});
+                    if (bwd_occ) jobs.push_back({bwd_occ + b0 * hw0, hs.h_bo, nb * hw0});
                 }
                 c->pool_out->run(jobs);
             }
@@ -291,8 +324,13 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
         // network as they are and the first conv kernel normalizes on the fly
         if (!same) HIPCHK(launch_image_scale(hs.d_up, 1, (long)nu * fpu * 3, H0, W0, hs.d_tmp, hs.d_in, fh, fw, c->stream));
         CHK(forward_device(c, direct_u8 ? (const void *)hs.d_u8 : hs.d_in, direct_u8 ? B2F_IN_U8 : same ? B2F_IN_UNIT : B2F_IN_NORMALIZED, nb, fh,
-                           fw, hs.d_flow, nullptr, hs.d_est3, c->stream, c->host_graph != 0, seq));
-        HIPCHK(launch_postprocess(hs.d_flow, hs.d_est3, C3, nb, fh, fw, H0, W0, same ? nullptr : hs.d_flow32, hs.d_fo, hs.d_bo, c->stream));
+                           fw, hs.d_flow, hs.d_occ, hs.d_est3, c->stream, c->host_graph != 0, seq));
+        const float *occ_net = C3 == 3 ? hs.d_occ : hs.d_est3;
+        if (!f32)
+            HIPCHK(launch_postprocess(hs.d_flow, hs.d_est3, C3, nb, fh, fw, H0, W0, same ? nullptr : hs.d_flow32, hs.d_fo, hs.d_bo, c->stream));
+        else   // without a rescale the flow and occ_prob planes are the network's, downloaded as they are
+            HIPCHK(launch_outputs_f32(hs.d_flow, occ_net, hs.d_est3, C3, nb, fh, fw, H0, W0, sc_w, sc_h, same ? nullptr : hs.d_flow32,
+                                      q.prob ? hs.d_prob : nullptr, fwd_occ ? hs.d_fo : nullptr, bwd_occ ? hs.d_bo : nullptr, c->stream));
         HIPCHK(hipEventRecord(hs.ev_comp, c->stream));
         // ---- download: the set's pinned output buffers must have been handed over (k - 2 drained)
         if (k >= 2) {
@@ -301,9 +339,15 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
             if (abort) return fail(drain_err);
         }
         HIPCHK(hipStreamWaitEvent(c->s_out, hs.ev_comp, 0));
-        HIPCHK(hipMemcpyAsync(hs.h_flow32, hs.d_flow32, (size_t)nb * 2 * hw0 * 4, hipMemcpyDeviceToHost, c->s_out));
-        HIPCHK(hipMemcpyAsync(stage_masks ? hs.h_fo : fwd_occ + b0 * hw0, hs.d_fo, (size_t)nb * hw0, hipMemcpyDeviceToHost, c->s_out));
-        HIPCHK(hipMemcpyAsync(stage_masks ? hs.h_bo : bwd_occ + b0 * hw0, hs.d_bo, (size_t)nb * hw0, hipMemcpyDeviceToHost, c->s_out));
+        HIPCHK(hipMemcpyAsync(q.stage_flow ? hs.h_flow32 : o.flow32 + b0 * 2 * hw0, hs.d_flow32, (size_t)nb * 2 * hw0 * 4, hipMemcpyDeviceToHost,
+                              c->s_out));
+        if (want_prob)
+            HIPCHK(hipMemcpyAsync(q.stage_prob ? hs.h_prob : o.occ_prob + b0 * 2 * hw0, same ? occ_net : hs.d_prob, (size_t)nb * 2 * hw0 * 4,
+                                  hipMemcpyDeviceToHost, c->s_out));
+        if (fwd_occ)
+            HIPCHK(hipMemcpyAsync(stage_masks ? hs.h_fo : fwd_occ + b0 * hw0, hs.d_fo, (size_t)nb * hw0, hipMemcpyDeviceToHost, c->s_out));
+        if (bwd_occ)
+            HIPCHK(hipMemcpyAsync(stage_masks ? hs.h_bo : bwd_occ + b0 * hw0, hs.d_bo, (size_t)nb * hw0, hipMemcpyDeviceToHost, c->s_out));
         HIPCHK(hipEventRecord(hs.ev_out, c->s_out));
         {
             std::lock_guard<std::mutex> l(mu);
@@ -334,14 +378,143 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
     return 0;
 }
 
+// ---- device boundary: the kernels half of the pipeline's submit() on caller device buffers, no transfers ----
+// Per sub-batch, on `s`: gather the three frame sets into B x 9 x H0 x W0 (triplets) and unpack bytes, ColorNormalize +
+// image.scale to the /64 size, the forward pass, outputs_f32_kernel into the caller's buffers.  Sub-batches follow the host
+// pipeline's budget (host_subbatch_pixels, no ramp: there is no upload to overlap) and a sequence's overlap by two frames;
+// the buffers in between are the context's (c->dwork).  Every choice -- input kind of the forward pass, unpacking, the
+// kernel rule of the request's n -- is the host pipeline's, so the results are the f32 host entries' bit for bit.
+int compute_flow_device_impl(b2f_ctx *c, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0,
+                             int W0, const FlowOutputs &o, void *stream, const char *who)
+{
+    const std::string w(who);
+    CHK(check_f32_args(who, count, in_kind, im1, im2, im3, seq, H0, W0, o.flow32));
+    if (!c) return fail(w + ": null context");
+    const uintptr_t al = (uintptr_t)im1 | (uintptr_t)im2 | (uintptr_t)im3 | (uintptr_t)o.flow32 | (uintptr_t)o.occ_prob | (uintptr_t)o.fwd_occ |
+                         (uintptr_t)o.bwd_occ;
+    if (al & 15) return fail(w + ": device buffers must be 16-byte aligned");
+    const int n = seq ? count - 2 : count;
+    const int fw = W0 - W0 % 64, fh = H0 - H0 % 64;   // back2future.lua:54-67
+    CHK(check_shape(1, fh, fw));
+    if (seq && !c->g.shipped())
+        return fail(w + ": sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw0 = (size_t)H0 * W0, hw = (size_t)fh * fw;
+    const bool bytes_in = in_kind == B2F_IN_U8;
+    const size_t esz = bytes_in ? 1 : 4;
+    {
+        const size_t in_bytes = (size_t)(seq ? n + 2 : n) * 3 * hw0 * esz, hw0n = (size_t)n * hw0;
+        const std::pair<const void *, size_t> bufs[7] = {{im1, in_bytes}, {seq ? nullptr : im2, in_bytes}, {seq ? nullptr : im3, in_bytes},
+                                                         {o.flow32, hw0n * 8}, {o.occ_prob, hw0n * 8}, {o.fwd_occ, hw0n}, {o.bwd_occ, hw0n}};
+        for (const auto &pb : bufs)
+            if (pb.first && mem_kind(pb.first, pb.second) >= 0)
+                return fail(w + ": host memory passed to a device entry point (use b2f_compute_flow_batch_f32 / b2f_compute_flow_sequence_f32)");
+    }
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool same = (fw == W0 && fh == H0);
+    const int C3 = c->past_flow ? 2 : 3;
+    const double sc_h = (double)H0 / (double)fh, sc_w = (double)W0 / (double)fw;   // :78-79
+    const int gu = seq ? 2 : 0;
+    const int SBU = (int)std::min<long long>(n + gu, std::max<long long>(1 + gu, c->host_subbatch_pixels / (long long)hw0));
+    const int SB = SBU - gu;
+    // workspace: bytes of the gathered triplets, their floats, image.scale's two passes, the network's outputs
+    const bool unpack = bytes_in && !(seq && same);   // a /64 byte sequence is read as it is (the pipeline's direct_u8)
+    const size_t planes = (size_t)SBU * (seq ? 3 : 9);
+    const size_t n_u8 = (!seq && bytes_in) ? align256(planes * hw0) : 0, n_up = (!seq || unpack) ? align256(planes * hw0 * 4) : 0,
+                 n_tmp = same ? 0 : align256(planes * H0 * fw * 4), n_in = same ? 0 : align256(planes * hw * 4),
+                 n_flow = align256((size_t)SB * 2 * hw * 4), n_occ = (o.occ_prob && C3 == 3) ? n_flow : 0,
+                 n_est3 = align256((size_t)SB * C3 * hw * 4);
+    const size_t need = n_u8 + n_up + n_tmp + n_in + n_flow + n_occ + n_est3;
+    DevWork &dw = c->dwork;
+    if (need > dw.bytes) {
+        if (dw.dev) {
+            HIPCHK(hipDeviceSynchronize());   // earlier calls may still read it, on any stream
+            HIPCHK(hipFree(dw.dev));
+            dw.dev = nullptr; dw.bytes = 0;
+            drop_graphs(c);                   // graphs are keyed on its pointers
+        }
+        HIPCHK(hipMalloc(&dw.dev, need));
+        dw.bytes = need;
+    }
+    char *d = dw.dev;
+    unsigned char *d_u8 = (unsigned char *)d; d += n_u8;
+    float *d_up = (float *)d; d += n_up;
+    float *d_tmp = (float *)d; d += n_tmp;
+    float *d_in = (float *)d; d += n_in;
+    float *d_flow = (float *)d; d += n_flow;
+    float *d_occ = n_occ ? (float *)d : nullptr; d += n_occ;
+    float *d_est3 = (float *)d;
+    struct ReqBatch { b2f_ctx *c; ReqBatch(b2f_ctx *cc, int nn) : c(cc) { c->req_batch = nn; } ~ReqBatch() { c->req_batch = 0; } } req_guard(c, n);
+    const char *ims[3] = {(const char *)im1, (const char *)im2, (const char *)im3};
+    for (int b0 = 0; b0 < n; b0 += SB) {
+        const int nb = std::min(SB, n - b0);
+        const size_t np = (size_t)(seq ? nb + 2 : nb) * (seq ? 3 : 9);   // input planes of this sub-batch
+        const void *x = nullptr;   // what the forward pass reads
+        int kind = B2F_IN_UNIT;
+        if (!seq) {   // torch.cat({im1, im2, im3}, 1) (back2future.lua:48): triplet t's frames f = 0..2 at planes (t * 3 + f) * 3
+            char *g = bytes_in ? (char *)d_u8 : (char *)d_up;
+            for (int t = 0; t < nb; ++t)
+                for (int f = 0; f < 3; ++f)
+                    HIPCHK(hipMemcpyAsync(g + ((size_t)t * 3 + f) * 3 * hw0 * esz, ims[f] + (size_t)(b0 + t) * 3 * hw0 * esz, 3 * hw0 * esz,
+                                          hipMemcpyDeviceToDevice, s));
+            if (bytes_in) HIPCHK(launch_unpack_u8(d_u8, np * hw0, d_up, s));
+            x = d_up;
+        } else {
+            const char *fr = ims[0] + (size_t)b0 * 3 * hw0 * esz;
+            if (unpack) {
+                HIPCHK(launch_unpack_u8((const unsigned char *)fr, np * hw0, d_up, s));
+                x = d_up;
+            } else {
+                x = fr;
+                kind = bytes_in ? B2F_IN_U8 : B2F_IN_UNIT;
+            }
+        }
+        // ColorNormalize, then image.scale to the /64 size (:50-71); without a rescale the first conv kernel normalizes on the fly
+        if (!same) {
+            HIPCHK(launch_image_scale((const float *)x, 1, (long)np, H0, W0, d_tmp, d_in, fh, fw, s));
+            x = d_in;
+            kind = B2F_IN_NORMALIZED;
+        }
+        CHK(forward_device(c, x, kind, nb, fh, fw, d_flow, d_occ, d_est3, s, c->use_graph != 0, seq));
+        const size_t o2 = (size_t)b0 * 2 * hw0, o1 = (size_t)b0 * hw0;
+        HIPCHK(launch_outputs_f32(d_flow, C3 == 3 ? d_occ : d_est3, d_est3, C3, nb, fh, fw, H0, W0, sc_w, sc_h, o.flow32 + o2,
+                                  o.occ_prob ? o.occ_prob + o2 : nullptr, o.fwd_occ ? o.fwd_occ + o1 : nullptr,
+                                  o.bwd_occ ? o.bwd_occ + o1 : nullptr, s));
+    }
+    return 0;
+}
+
 }  // namespace
+
+int b2f::check_f32_args(const char *who, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
+                        const float *flow)
+{
+    const std::string w(who);
+    if (in_kind == B2F_IN_NORMALIZED)
+        return fail(w + ": in_kind B2F_IN_NORMALIZED is refused: computeFlow normalizes its frames itself (B2F_IN_UNIT or B2F_IN_U8)");
+    if (in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail(w + ": in_kind must be B2F_IN_UNIT or B2F_IN_U8");
+    if (seq && count < 3) return fail(w + ": a sequence needs T >= 3 frames (one triplet)");
+    if (count <= 0 || H0 <= 0 || W0 <= 0) return fail(w + ": bad shape");
+    if (H0 < 64 || W0 < 64) return fail(w + ": image smaller than 64 pixels");
+    if (!im1 || (!seq && (!im2 || !im3)) || !flow) return fail(w + ": null argument");
+    return 0;
+}
+
+int b2f::compute_flow_f32(b2f_ctx *c, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
+                          const FlowOutputs &o, int req, const char *who)
+{
+    CHK(check_f32_args(who, count, in_kind, im1, im2, im3, seq, H0, W0, o.flow32));
+    if (!c) return fail(std::string(who) + ": null context");
+    return compute_flow_pipeline(c, seq ? count - 2 : count, im1, im2, im3, in_kind == B2F_IN_U8, H0, W0, o, seq, req);
+}
 
 int b2f::compute_flow_sequence(b2f_ctx *c, int T, const void *frames, bool bytes_in, int H0, int W0, double *flow, unsigned char *fwd_occ,
                                unsigned char *bwd_occ, int req)
 {
     if (!c) return fail("b2f_compute_flow_sequence: null context");
     if (T < 3) return fail("b2f_compute_flow_sequence: a sequence needs T >= 3 frames (one triplet)");
-    return compute_flow_pipeline(c, T - 2, frames, nullptr, nullptr, bytes_in, H0, W0, flow, fwd_occ, bwd_occ, true, req);
+    return compute_flow_pipeline(c, T - 2, frames, nullptr, nullptr, bytes_in, H0, W0, FlowOutputs{flow, nullptr, nullptr, fwd_occ, bwd_occ},
+                                 true, req);
 }
 
 extern "C" {
@@ -349,7 +522,7 @@ extern "C" {
 int b2f_compute_flow_batch(b2f_ctx *c, int n, const float *im1, const float *im2, const float *im3, int H0,
                            int W0, double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    return compute_flow_pipeline(c, n, im1, im2, im3, false, H0, W0, flow, fwd_occ, bwd_occ);
+    return compute_flow_pipeline(c, n, im1, im2, im3, false, H0, W0, FlowOutputs{flow, nullptr, nullptr, fwd_occ, bwd_occ});
 }
 B2F_CATCH("b2f_compute_flow_batch")
 
@@ -357,7 +530,7 @@ int b2f_compute_flow_batch_u8(b2f_ctx *c, int n, const unsigned char *im1, const
                               const unsigned char *im3, int H0, int W0, double *flow, unsigned char *fwd_occ,
                               unsigned char *bwd_occ) try
 {
-    return compute_flow_pipeline(c, n, im1, im2, im3, true, H0, W0, flow, fwd_occ, bwd_occ);
+    return compute_flow_pipeline(c, n, im1, im2, im3, true, H0, W0, FlowOutputs{flow, nullptr, nullptr, fwd_occ, bwd_occ});
 }
 B2F_CATCH("b2f_compute_flow_batch_u8")
 
@@ -381,5 +554,38 @@ int b2f_compute_flow_sequence_u8(b2f_ctx *c, int T, const unsigned char *frames,
     return compute_flow_sequence(c, T, frames, true, H0, W0, flow, fwd_occ, bwd_occ, 0);
 }
 B2F_CATCH("b2f_compute_flow_sequence_u8")
+
+int b2f_compute_flow_batch_f32(b2f_ctx *c, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0, float *flow,
+                               float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_f32(c, n, in_kind, im1, im2, im3, false, H0, W0, FlowOutputs{nullptr, flow, occ_prob, fwd_occ, bwd_occ}, 0,
+                            "b2f_compute_flow_batch_f32");
+}
+B2F_CATCH("b2f_compute_flow_batch_f32")
+
+int b2f_compute_flow_sequence_f32(b2f_ctx *c, int T, int in_kind, const void *frames, int H0, int W0, float *flow, float *occ_prob,
+                                  unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_f32(c, T, in_kind, frames, nullptr, nullptr, true, H0, W0, FlowOutputs{nullptr, flow, occ_prob, fwd_occ, bwd_occ}, 0,
+                            "b2f_compute_flow_sequence_f32");
+}
+B2F_CATCH("b2f_compute_flow_sequence_f32")
+
+int b2f_compute_flow_device(b2f_ctx *c, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, int H0, int W0,
+                            float *dev_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream) try
+{
+    return compute_flow_device_impl(c, n, in_kind, dev_im1, dev_im2, dev_im3, false, H0, W0,
+                                    FlowOutputs{nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}, stream, "b2f_compute_flow_device");
+}
+B2F_CATCH("b2f_compute_flow_device")
+
+int b2f_compute_flow_sequence_device(b2f_ctx *c, int T, int in_kind, const void *dev_frames, int H0, int W0, float *dev_flow,
+                                     float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream) try
+{
+    return compute_flow_device_impl(c, T, in_kind, dev_frames, nullptr, nullptr, true, H0, W0,
+                                    FlowOutputs{nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}, stream,
+                                    "b2f_compute_flow_sequence_device");
+}
+B2F_CATCH("b2f_compute_flow_sequence_device")
 
 }  // extern "C"

@@ -187,7 +187,7 @@ B2F_API int b2f_forward_device(b2f_ctx *ctx, const void *dev_in, int in_kind, in
  * with b2f_init_ex options, two_frame among them, is refused); every device pointer
  * 16-byte aligned.  Asynchronous on `stream` like b2f_forward_device; with use_graph = 1
  * its launches are replayed from a hipGraph of their own, never one of a triplet call.   */
-enum { B2F_IN_U8 = 2 };   /* sequence entry only: bytes, value = byte / 255 */
+enum { B2F_IN_U8 = 2 };   /* sequence and f32 entries only: bytes, value = byte / 255 */
 B2F_API int b2f_forward_sequence_device(b2f_ctx *ctx, const void *dev_frames, int in_kind, int T, int H, int W,
                                 float *dev_flow, float *dev_occ, float *dev_est3, void *stream);
 /* The same from host memory, with computeFlow's boundary (back2future.lua:47-95) around every
@@ -207,6 +207,49 @@ B2F_API int b2f_multi_compute_flow_sequence(b2f_multi *m, int T, const float *fr
                                     double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
 B2F_API int b2f_multi_compute_flow_sequence_u8(b2f_multi *m, int T, const unsigned char *frames, int H0, int W0,
                                        double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* ---- float32 outputs with occlusion probabilities: computeFlow's boundary, one entry per family ----
+ * The same inputs as the f64 entries above, with in_kind = B2F_IN_UNIT (floats in [0,1]) or
+ * B2F_IN_U8 (bytes, value = byte / 255); B2F_IN_NORMALIZED is refused (computeFlow normalizes
+ * itself).  Outputs, n = triplets (T-2 for a sequence):
+ *   flow      n x 2 x H0 x W0 floats: the f64 entry's value rounded to nearest, (float)((double)f *
+ *             sc) with sc_w = W0 / fw, sc_h = H0 / fh (back2future.lua:80-84); est[1] itself
+ *             when H0 and W0 are multiples of 64.  Required.
+ *   occ_prob  n x 2 x H0 x W0 floats or NULL: skip_occs[3] (pwc.lua:308-321, the occlusion
+ *             softmax; channel c = channel c), nearest-rescaled like the masks.  For Soft models
+ *             this is est[3], so fwd_occ = (occ_prob[:,1] >= 0.6666) and bwd_occ =
+ *             (occ_prob[:,0] >= 0.6666).  For Hard models it is est[2], the real occlusion map,
+ *             while the masks keep the reference's thresholds of est[3] -- which is the warped
+ *             image 1 there -- so they are not thresholds of occ_prob.
+ *   fwd_occ / bwd_occ  n x H0 x W0 bytes or NULL: the f64 entries' masks, bit for bit.
+ * The kernel choice follows the caller's n as in the f64 entries, so the bits are the same.
+ * Host entries: page-locked output buffers are DMA'd in place, pageable ones are copied from the
+ * staging buffers; nothing is widened on the host.  A context made with b2f_init_ex options runs
+ * the batch entries; the sequence entries are refused there.                                 */
+B2F_API int b2f_compute_flow_batch_f32(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                               int H0, int W0, float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_compute_flow_sequence_f32(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                  float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* Several GPUs: sharded like b2f_multi_compute_flow_batch / _sequence; every shard's kernel choice
+ * follows the caller's n (the sequence rule), so the results equal one context's f32 entry.   */
+B2F_API int b2f_multi_compute_flow_batch_f32(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                     int H0, int W0, float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_sequence_f32(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                        float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* The same boundary on GPU memory, any H0 x W0 (frames decoded on the GPU at 1080p, ...): the
+ * inputs, unpacking, image.scale to the /64 size, the forward pass and the output stage all run
+ * on `stream`, asynchronously like b2f_forward_device (NULL = the context's blocking stream);
+ * the results equal the f32 host entries' bit for bit.  Triplets are cut into sub-batches of
+ * the host_subbatch_pixels budget (sequences overlapping by two frames) that run through a
+ * workspace owned by the context: two calls on different streams must be ordered by the caller
+ * (e.g. make the second stream wait for an event recorded after the first call), exactly as
+ * for b2f_forward_device, whose activations live in the context too.  Every pointer must be
+ * device memory (host pointers are refused) and 16-byte aligned.                              */
+B2F_API int b2f_compute_flow_device(b2f_ctx *ctx, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3,
+                            int H0, int W0, float *dev_flow, float *dev_occ_prob,
+                            unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
+B2F_API int b2f_compute_flow_sequence_device(b2f_ctx *ctx, int T, int in_kind, const void *dev_frames, int H0, int W0,
+                                     float *dev_flow, float *dev_occ_prob,
+                                     unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
 /* Full output table of model:forward (pwc.lua:459-489) into n_outs host buffers, in
  * table order; x is B x 9 x H x W normalized host memory.                           */
 B2F_API int b2f_forward(b2f_ctx *ctx, const float *x, int B, int H, int W, float **outs, int n_outs);

@@ -6,7 +6,8 @@
 --   computeFlow = back2future.init('Ours-Soft-ft-KITTI')
 --   flow, fwd_occ, bwd_occ = computeFlow(im1, im2, im3)
 --
--- local computeFlow, computeFlowSequence = back2future.init(opt): the second closure takes a whole video.
+-- local computeFlow, computeFlowSequence = back2future.init(opt): the second closure takes a whole video; the third and
+-- fourth (computeFlowBatchF32, computeFlowSequenceF32) return float flows and, on request, the occlusion probabilities.
 -- Same module table (init, normalize), same argument and return order and types
 -- as back2future.lua:45-130: im* are 3xHxW torch tensors in [0,1] (image.load),
 -- flow is a 2xHxW torch.DoubleTensor, the masks are 1xHxW torch.ByteTensor.
@@ -34,11 +35,25 @@ int  b2f_compute_flow_sequence(b2f_ctx *ctx, int T, const float *frames, int H0,
                                double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
 int  b2f_compute_flow_sequence_u8(b2f_ctx *ctx, int T, const unsigned char *frames, int H0, int W0,
                                   double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int  b2f_compute_flow_batch_f32(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                int H0, int W0, float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int  b2f_compute_flow_sequence_f32(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                   float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int  b2f_compute_flow_device(b2f_ctx *ctx, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3,
+                             int H0, int W0, float *dev_flow, float *dev_occ_prob,
+                             unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
+int  b2f_compute_flow_sequence_device(b2f_ctx *ctx, int T, int in_kind, const void *dev_frames, int H0, int W0,
+                                      float *dev_flow, float *dev_occ_prob,
+                                      unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
 int  b2f_multi_compute_flow_batch(b2f_multi *m, int n, const float *im1, const float *im2, const float *im3,
                                   int H0, int W0, double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int  b2f_multi_compute_flow_batch_f32(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                      int H0, int W0, float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int  b2f_multi_compute_flow_sequence_f32(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                         float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
 ]]
 
 local lib = ffi.load(os.getenv('B2F_LIB') or 'libb2f.so')
@@ -111,7 +126,43 @@ local function init(opt)
       end
       return flow_est, fwd_occ_est, bwd_occ_est
    end
-   return computeFlow, computeFlowSequence
+
+   -- float outputs (b2f_compute_flow_batch_f32 / _sequence_f32): the flow is a FloatTensor, computeFlow's DoubleTensor
+   -- rounded to float, never widened; with want_occ_prob a 4th result holds the n x 2 x H x W occlusion probabilities.
+   -- Frames: FloatTensors in [0,1] or, all of them, ByteTensors (value = byte / 255).
+   local function frames_of(...)
+      local ts, bytes = {...}, true
+      for _, t in ipairs(ts) do bytes = bytes and torch.type(t) == 'torch.ByteTensor' end
+      for i, t in ipairs(ts) do ts[i] = bytes and t:contiguous() or t:float():contiguous() end
+      return ts, bytes and 2 or 1   -- B2F_IN_U8 / B2F_IN_UNIT
+   end
+   local function f32_outputs(n, height, width, want_occ_prob)
+      return torch.FloatTensor(n, 2, height, width), torch.ByteTensor(n, 1, height, width),
+             torch.ByteTensor(n, 1, height, width), want_occ_prob and torch.FloatTensor(n, 2, height, width) or nil
+   end
+   local computeFlowBatchF32 = function(im1, im2, im3, want_occ_prob)
+      local ts, kind = frames_of(im1, im2, im3)
+      local a, b, c = ts[1], ts[2], ts[3]
+      assert(a:dim() == 4 and a:size(2) == 3, 'expected n x 3 x H x W batches')
+      assert(a:isSameSizeAs(b) and a:isSameSizeAs(c), 'the three frame batches must have the same size')
+      local n, height, width = a:size(1), a:size(3), a:size(4)
+      local flow_est, fwd_occ_est, bwd_occ_est, occ_prob = f32_outputs(n, height, width, want_occ_prob)
+      check(lib.b2f_compute_flow_batch_f32(ctx, n, kind, a:data(), b:data(), c:data(), height, width, flow_est:data(),
+                                           occ_prob and occ_prob:data() or nil, fwd_occ_est:data(), bwd_occ_est:data()))
+      return flow_est, fwd_occ_est, bwd_occ_est, occ_prob
+   end
+   local computeFlowSequenceF32 = function(frames, want_occ_prob)
+      local ts, kind = frames_of(frames)
+      local f = ts[1]
+      assert(f:dim() == 4 and f:size(2) == 3, 'expected T x 3 x H x W frames')
+      local T, height, width = f:size(1), f:size(3), f:size(4)
+      assert(T >= 3, 'a sequence needs T >= 3 frames')
+      local flow_est, fwd_occ_est, bwd_occ_est, occ_prob = f32_outputs(T - 2, height, width, want_occ_prob)
+      check(lib.b2f_compute_flow_sequence_f32(ctx, T, kind, f:data(), height, width, flow_est:data(),
+                                              occ_prob and occ_prob:data() or nil, fwd_occ_est:data(), bwd_occ_est:data()))
+      return flow_est, fwd_occ_est, bwd_occ_est, occ_prob
+   end
+   return computeFlow, computeFlowSequence, computeFlowBatchF32, computeFlowSequenceF32
 end
 M.init = init
 

@@ -1,0 +1,323 @@
+"""GPU: the float32 computeFlow outputs (b2f_compute_flow_batch_f32, b2f_compute_flow_sequence_f32, the b2f_multi forms, the device
+entries b2f_compute_flow_device / b2f_compute_flow_sequence_device).  Every output is defined from the float64 entries' or the
+network's: flow_f32 == np.float32(flow_f64) bit for bit, the masks are identical, occ_prob is skip_occs[3] nearest-rescaled with
+postprocess_kernel's index rule."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from back2future_amd import _lib, back2future, flow_io
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+THR = 0.6666
+
+
+@pytest.fixture(scope="module")
+def hard():
+    m = back2future.Model("random:hard:5:2.0")
+    yield m
+    m.close()
+
+
+@pytest.fixture(scope="module")
+def soft():
+    m = back2future.Model("random:soft:5:2.0")
+    yield m
+    m.close()
+
+
+def _clip(seed, T, H0, W0, kind):
+    """T x 3 x H0 x W0 frames: 'unit' random floats in [0,1), 'u8' bytes, 'k255' the floats of those bytes (cross the link as bytes)."""
+    r = np.random.default_rng(seed)
+    if kind == "unit":
+        return r.random((T, 3, H0, W0), dtype=np.float32)
+    b = r.integers(0, 256, (T, 3, H0, W0), dtype=np.uint8)
+    return b if kind == "u8" else b.astype(np.float32) / np.float32(255)
+
+
+def _triplets(V):
+    return V[:-2], V[1:-1], V[2:]
+
+
+def _eq(a, b, what):
+    """bit-for-bit equality"""
+    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
+    bits = np.uint8 if a.dtype == np.uint8 else np.uint32
+    x, y = np.ascontiguousarray(a).reshape(-1).view(bits), np.ascontiguousarray(b).reshape(-1).view(bits)
+    if not np.array_equal(x, y):
+        d = np.flatnonzero(x != y)
+        raise AssertionError("%s: %d elements differ, first at %d: %r vs %r" % (what, d.size, d[0], a.reshape(-1)[d[0]], b.reshape(-1)[d[0]]))
+
+
+def _nearest(plane_stack, H0, W0):
+    """image.scale 'simple' with postprocess_kernel's index rule: src = (long)((float)dst * ((float)src_len / (float)dst_len)), clamped."""
+    fh, fw = plane_stack.shape[-2:]
+    jj = np.minimum((np.arange(H0, dtype=np.float32) * (np.float32(fh) / np.float32(H0))).astype(np.int64), fh - 1)
+    ii = np.minimum((np.arange(W0, dtype=np.float32) * (np.float32(fw) / np.float32(W0))).astype(np.int64), fw - 1)
+    return plane_stack[..., jj, :][..., ii]
+
+
+def _net_occ(m, im1, im2, im3):
+    """skip_occs[3] of the network at the /64 size, on the input the pipeline builds: the raw [0,1] planes at /64 sizes,
+    else ColorNormalize + image.scale (b2f_op_image_scale(normalize=1), the pipeline's launch_image_scale)."""
+    n, _, H0, W0 = im1.shape
+    fh, fw = H0 - H0 % 64, W0 - W0 % 64
+    x = np.concatenate([np.asarray(a, np.float32) / (np.float32(255) if a.dtype == np.uint8 else 1) for a in (im1, im2, im3)], axis=1)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    unit = (fh, fw) == (H0, W0)
+    if not unit:
+        xs = np.empty((n, 9, fh, fw), np.float32)
+        for b in range(n):
+            _lib.check(_lib.lib().b2f_op_image_scale(m._h, _lib.fptr(x[b]), 9, H0, W0, 1, _lib.fptr(xs[b]), fh, fw))
+        x = xs
+    d_in = torch.from_numpy(x).cuda()
+    occ = torch.empty((n, 2, fh, fw), device="cuda")
+    torch.cuda.synchronize()
+    m.forward_device(d_in.data_ptr(), n, fh, fw, d_occ=occ.data_ptr(), unit_input=unit)
+    m.synchronize()
+    return occ.cpu().numpy()
+
+
+SIZES = [(128, 192), (130, 200), (375, 1242), (1080, 1920)]
+
+
+@pytest.mark.parametrize("which", ["hard", "soft"])
+@pytest.mark.parametrize("H0,W0", SIZES)
+def test_batch_f32_is_the_f64_flow_rounded_and_occ_prob_is_skip_occs(request, which, H0, W0):
+    m = request.getfixturevalue(which)
+    n = 1 if H0 >= 1080 else 2
+    for seed, kind in enumerate(["unit", "u8"]):
+        V = _clip(H0 + seed, n + 2, H0, W0, kind)
+        ims = [np.ascontiguousarray(a) for a in _triplets(V)]
+        f64, fo64, bo64 = m.computeFlowBatch(*ims)
+        flow, fo, bo, occ = m.computeFlowBatch(*ims, dtype=np.float32, occ_prob=True)
+        what = "%s %dx%d %s" % (which, H0, W0, kind)
+        _eq(flow, np.float32(f64), what + " flow")
+        _eq(fo, fo64, what + " fwd_occ")
+        _eq(bo, bo64, what + " bwd_occ")
+        net = _net_occ(m, *ims)
+        _eq(occ, net if (H0 % 64, W0 % 64) == (0, 0) else _nearest(net, H0, W0), what + " occ_prob")
+        if not m.past_flow:
+            continue
+        # Soft: occ_prob is est[3], the masks are its thresholds
+        _eq(fo, (occ[:, 1:2].astype(np.float64) >= THR).astype(np.uint8), what + " fwd = occ_prob[1] >= thr")
+        _eq(bo, (occ[:, 0:1].astype(np.float64) >= THR).astype(np.uint8), what + " bwd = occ_prob[0] >= thr")
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("which", ["hard", "soft"])
+@pytest.mark.parametrize("ramp", [0, 1])
+def test_sequence_f32_equals_batch_f32_over_several_subbatches(request, which, ramp):
+    m = request.getfixturevalue(which)
+    T, H0, W0 = 11, 100, 150
+    for kind in ("unit", "u8", "k255"):
+        V = _clip(70, T, H0, W0, kind)
+        exp = m.computeFlowBatch(*_triplets(V), dtype=np.float32, occ_prob=True)
+        with m.options(host_subbatch_pixels=4 * H0 * W0, host_ramp=ramp):
+            got = m.computeFlowSequence(V, dtype=np.float32, occ_prob=True)
+            got_b = m.computeFlowBatch(*_triplets(V), dtype=np.float32, occ_prob=True)
+        for i, (a, b, c) in enumerate(zip(got, got_b, exp)):
+            _eq(a, c, "ramp %d %s sequence output %d" % (ramp, kind, i))
+            _eq(b, c, "ramp %d %s batch output %d" % (ramp, kind, i))
+        f64 = m.computeFlowSequence(V)
+        _eq(got[0], np.float32(f64[0]), "sequence flow vs f64")
+        _eq(got[1], f64[1], "sequence fwd_occ vs f64")
+
+
+@pytest.mark.parametrize("H0,W0", [(128, 192), (100, 150)])
+def test_pinned_and_pageable_outputs_and_every_null_combination(hard, soft, H0, W0):
+    n = 3
+    for m in (hard, soft):
+        V = _clip(80, n + 2, H0, W0, "unit")
+        ims = _triplets(V)
+        full = m.computeFlowBatch(*ims, dtype=np.float32, occ_prob=True)
+        full_seq = m.computeFlowSequence(V, dtype=np.float32, occ_prob=True)
+        for pinned in (False, True):
+            for want_occ in (False, True):
+                for masks in ((True, True), (True, False), (False, True), (False, False)):
+                    def buf(shape, dt):
+                        t = torch.full(shape, 7, dtype=dt)
+                        return (t.pin_memory() if pinned else t).numpy()
+                    flow = buf((n, 2, H0, W0), torch.float32)
+                    fo = buf((n, 1, H0, W0), torch.uint8) if masks[0] else None
+                    bo = buf((n, 1, H0, W0), torch.uint8) if masks[1] else None
+                    occ = buf((n, 2, H0, W0), torch.float32) if want_occ else None
+                    out = (flow, fo, bo) + ((occ,) if want_occ else ())
+                    what = "pinned=%d occ=%d masks=%s" % (pinned, want_occ, masks)
+                    for call, ref in ((lambda: m.computeFlowBatch(*ims, dtype=np.float32, occ_prob=want_occ, out=out), full),
+                                      (lambda: m.computeFlowSequence(V, dtype=np.float32, occ_prob=want_occ, out=out), full_seq)):
+                        for a in out:
+                            if a is not None:
+                                a[...] = 7
+                        res = call()
+                        assert res[0] is flow and res[1] is fo and res[2] is bo
+                        _eq(flow, ref[0], what + " flow")
+                        if fo is not None:
+                            _eq(fo, ref[1], what + " fwd_occ")
+                        if bo is not None:
+                            _eq(bo, ref[2], what + " bwd_occ")
+                        if want_occ:
+                            assert res[3] is occ
+                            _eq(occ, ref[3], what + " occ_prob")
+
+
+def test_multi_f32_two_replicas_on_one_gpu(monkeypatch):
+    """n = 3 triplets (shards 2 + 1) and a T = 5 sequence on two replicas of one GPU equal one context's f32 entries."""
+    monkeypatch.setenv("B2F_MULTI_TRANSPORT", "peer")
+    monkeypatch.setenv("B2F_MULTI_ALLOW_DUPLICATE", "1")
+    H0, W0 = 100, 150
+    mm = back2future.MultiModel("random:hard:5:2.0", n_gpus=2, devices=[0, 0])
+    ref = back2future.Model("random:hard:5:2.0")
+    try:
+        assert mm.n_gpus == 2
+        for kind in ("unit", "u8"):
+            V = _clip(90, 5, H0, W0, kind)
+            ims = [np.ascontiguousarray(a) for a in _triplets(V)]
+            for a, b in zip(mm.computeFlowBatch(*ims, dtype=np.float32, occ_prob=True),
+                            ref.computeFlowBatch(*ims, dtype=np.float32, occ_prob=True)):
+                _eq(a, b, "batch %s" % kind)
+            for a, b in zip(mm.computeFlowSequence(V, dtype=np.float32, occ_prob=True),
+                            ref.computeFlowSequence(V, dtype=np.float32, occ_prob=True)):
+                _eq(a, b, "sequence %s" % kind)
+        # the default stays the f64 path
+        V = _clip(91, 5, H0, W0, "unit")
+        assert mm.computeFlowBatch(*_triplets(V))[0].dtype == np.float64
+    finally:
+        mm.close()
+        ref.close()
+
+
+def _dev_outputs(n, H0, W0):
+    return (torch.full((n, 2, H0, W0), 7.0, device="cuda"), torch.full((n, 2, H0, W0), 7.0, device="cuda"),
+            torch.full((n, 1, H0, W0), 7, dtype=torch.uint8, device="cuda"), torch.full((n, 1, H0, W0), 7, dtype=torch.uint8, device="cuda"))
+
+
+@pytest.mark.parametrize("which", ["hard", "soft"])
+@pytest.mark.parametrize("H0,W0", [(128, 192), (130, 200), (1080, 1920)])
+def test_device_entries_equal_host_f32_entries(request, which, H0, W0):
+    m = request.getfixturevalue(which)
+    T = 4 if H0 >= 1080 else 6
+    n = T - 2
+    stream = torch.cuda.Stream()
+    for kind in ("unit", "u8"):
+        V = _clip(100 + H0, T, H0, W0, kind)
+        in_kind = back2future.IN_U8 if kind == "u8" else back2future.IN_UNIT
+        ims = [np.ascontiguousarray(a) for a in _triplets(V)]
+        exp_b = m.computeFlowBatch(*ims, dtype=np.float32, occ_prob=True)
+        exp_s = m.computeFlowSequence(V, dtype=np.float32, occ_prob=True)
+        d_ims = [torch.from_numpy(a).cuda() for a in ims]
+        d_V = torch.from_numpy(V).cuda()
+        torch.cuda.synchronize()
+        for seq, exp in ((False, exp_b), (True, exp_s)):
+            flow, occ, fo, bo = _dev_outputs(n, H0, W0)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(stream):
+                if seq:
+                    m.computeFlowSequenceDevice(d_V.data_ptr(), T, H0, W0, flow.data_ptr(), occ.data_ptr(), fo.data_ptr(), bo.data_ptr(),
+                                                in_kind=in_kind, stream=stream.cuda_stream)
+                else:
+                    m.computeFlowDevice(*[d.data_ptr() for d in d_ims], n, H0, W0, flow.data_ptr(), occ.data_ptr(), fo.data_ptr(),
+                                        bo.data_ptr(), in_kind=in_kind, stream=stream.cuda_stream)
+            stream.synchronize()
+            what = "%s %dx%d %s %s" % (which, H0, W0, kind, "sequence" if seq else "triplets")
+            for got, ref, nm in zip((flow, fo, bo, occ), exp, ("flow", "fwd_occ", "bwd_occ", "occ_prob")):
+                _eq(got.cpu().numpy(), ref, what + " " + nm)
+        # several sub-batches of the device path, outputs without masks / occ_prob
+        with m.options(host_subbatch_pixels=max(1, 2 * H0 * W0)):
+            flow, _, _, _ = _dev_outputs(n, H0, W0)
+            m.computeFlowSequenceDevice(d_V.data_ptr(), T, H0, W0, flow.data_ptr(), in_kind=in_kind)
+            m.synchronize()
+            _eq(flow.cpu().numpy(), exp_s[0], "%s %dx%d %s sub-batched sequence flow" % (which, H0, W0, kind))
+            flow, occ, _, _ = _dev_outputs(n, H0, W0)
+            m.computeFlowDevice(*[d.data_ptr() for d in d_ims], n, H0, W0, flow.data_ptr(), occ.data_ptr(), in_kind=in_kind)
+            m.synchronize()
+            _eq(flow.cpu().numpy(), exp_b[0], "%s %dx%d %s sub-batched flow" % (which, H0, W0, kind))
+            _eq(occ.cpu().numpy(), exp_b[3], "%s %dx%d %s sub-batched occ_prob" % (which, H0, W0, kind))
+        del d_ims, d_V
+    torch.cuda.empty_cache()
+
+
+def test_device_entries_refuse_host_misaligned_and_null_pointers(hard):
+    H0, W0 = 128, 192
+    d = torch.zeros((3, 3, H0, W0), device="cuda")
+    flow = torch.zeros((1, 2, H0, W0), device="cuda")
+    host = np.zeros((3, 3, H0, W0), np.float32)
+    pinned = torch.zeros((3, 3, H0, W0)).pin_memory()
+    host_flow = np.zeros((1, 2, H0, W0), np.float32)
+    p = d.data_ptr()
+    with pytest.raises(_lib.B2FError, match="host memory"):
+        hard.computeFlowSequenceDevice(host.ctypes.data, 3, H0, W0, flow.data_ptr())
+    with pytest.raises(_lib.B2FError, match="host memory"):
+        hard.computeFlowSequenceDevice(pinned.data_ptr(), 3, H0, W0, flow.data_ptr())
+    with pytest.raises(_lib.B2FError, match="host memory"):
+        hard.computeFlowDevice(p, p, p, 1, H0, W0, host_flow.ctypes.data)
+    with pytest.raises(_lib.B2FError, match="16-byte aligned"):
+        hard.computeFlowDevice(p + 4, p, p, 1, H0, W0, flow.data_ptr())
+    with pytest.raises(_lib.B2FError, match="16-byte aligned"):
+        hard.computeFlowSequenceDevice(p, 3, H0, W0, flow.data_ptr() + 8)
+    with pytest.raises(_lib.B2FError, match="16-byte aligned"):
+        hard.computeFlowSequenceDevice(p, 3, H0, W0, flow.data_ptr(), d_fwd_occ=flow.data_ptr() + 1)
+    with pytest.raises(_lib.B2FError, match="null argument"):
+        hard.computeFlowDevice(p, None, p, 1, H0, W0, flow.data_ptr())
+    with pytest.raises(_lib.B2FError, match="null argument"):
+        hard.computeFlowSequenceDevice(p, 3, H0, W0, None)
+    with pytest.raises(_lib.B2FError, match="B2F_IN_NORMALIZED is refused"):
+        hard.computeFlowSequenceDevice(p, 3, H0, W0, flow.data_ptr(), in_kind=back2future.IN_NORMALIZED)
+    L = _lib.lib()
+    with pytest.raises(_lib.B2FError, match="T >= 3"):
+        _lib.check(L.b2f_compute_flow_sequence_device(hard._h, 2, 1, C.c_void_p(p), H0, W0, C.c_void_p(flow.data_ptr()), None, None, None,
+                                                      None))
+    # the host entries name the device entries when handed device memory
+    with pytest.raises(_lib.B2FError, match="device memory.*b2f_compute_flow_device"):
+        _lib.check(L.b2f_compute_flow_sequence_f32(hard._h, 3, 1, C.c_void_p(p), H0, W0, _lib.fptr(host_flow), None, None, None))
+
+
+def test_generic_graph_contexts_run_the_batch_entries_only():
+    g = back2future.Model("random:hard", graph="win=5")
+    try:
+        H0, W0 = 130, 200
+        V = _clip(5, 4, H0, W0, "unit")
+        f64, fo64, bo64 = g.computeFlowBatch(*_triplets(V))
+        flow, fo, bo = g.computeFlowBatch(*_triplets(V), dtype=np.float32)
+        _eq(flow, np.float32(f64), "generic flow")
+        _eq(fo, fo64, "generic fwd_occ")
+        _eq(bo, bo64, "generic bwd_occ")
+        with pytest.raises(_lib.B2FError, match="shipped graph"):
+            g.computeFlowSequence(V, dtype=np.float32)
+        d = torch.from_numpy(V).cuda()
+        out = torch.empty((2, 2, H0, W0), device="cuda")
+        with pytest.raises(_lib.B2FError, match="shipped graph"):
+            g.computeFlowSequenceDevice(d.data_ptr(), 4, H0, W0, out.data_ptr())
+    finally:
+        g.close()
+
+
+def test_run_sequence_example_keeps_its_flo_bytes(tmp_path, soft):
+    """examples/run_sequence.py takes the f32 entry: its .flo files are those of the f64 flow narrowed to float32, byte for byte;
+    --occ-prob writes the probabilities as .npy."""
+    from PIL import Image
+    r = np.random.default_rng(11)
+    src = tmp_path / "frames"
+    src.mkdir()
+    for t in range(4):
+        Image.fromarray(r.integers(0, 256, (70, 130, 3), dtype=np.uint8)).save(str(src / ("f%02d.png" % t)))
+    out = tmp_path / "out"
+    subprocess.run([sys.executable, os.path.join(ROOT, "examples", "run_sequence.py"), str(src), str(out), "random:soft:5:2.0", "--occ-prob"],
+                   check=True, timeout=300, capture_output=True)
+    frames = np.stack([flow_io.load_image(str(src / ("f%02d.png" % t))) for t in range(4)])
+    f64 = soft.computeFlowSequence(frames)[0]
+    occ = soft.computeFlowSequence(frames, dtype=np.float32, occ_prob=True)[3]
+    for i in range(2):
+        stem = "f%02d" % (i + 1)
+        flow_io.writeFLO(str(tmp_path / "ref.flo"), f64[i].astype("float32"))
+        assert (out / (stem + ".flo")).read_bytes() == (tmp_path / "ref.flo").read_bytes(), stem
+        _eq(np.load(str(out / (stem + "_occ_prob.npy"))), occ[i], stem + " occ_prob")
