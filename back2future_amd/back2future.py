@@ -58,7 +58,8 @@ def sequence_frames(frames):
     return v, as_bytes
 
 
-def _sequence_outputs(n, H0, W0, out):
+def _f64_outputs(n, H0, W0, out):
+    """(flow, fwd, bwd) for the float64 entries: out = (flow float64 n x 2 x H x W, fwd uint8 n x 1 x H x W, bwd), or new arrays."""
     if out is not None:
         flow, fwd, bwd = out
         assert flow.dtype == np.float64 and flow.shape == (n, 2, H0, W0) and flow.flags.c_contiguous
@@ -108,6 +109,15 @@ def _call_f32(fn, h, count, in_kind, ins, H0, W0, outs, occ_prob):
     return (flow, fwd, bwd) + ((occ,) if occ_prob else ())
 
 
+def _call_f64(fn, h, count, as_bytes, ins, H0, W0, outs):
+    """fn (float inputs) or fn + "_u8" (byte inputs) into the float64 outputs."""
+    flow, fwd, bwd = outs
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte))
+    _lib.check(getattr(_lib.lib(), fn + ("_u8" if as_bytes else ""))(h, count, *[u8p(a) if as_bytes else _lib.fptr(a) for a in ins], H0, W0,
+                                                                   flow.ctypes.data_as(C.POINTER(C.c_double)), u8p(fwd), u8p(bwd)))
+    return flow, fwd, bwd
+
+
 def _batch_inputs(im1, im2, im3):
     as_bytes = all(np.asarray(a).dtype == np.uint8 for a in (im1, im2, im3))
     if as_bytes:
@@ -118,31 +128,26 @@ def _batch_inputs(im1, im2, im3):
     return im1, im2, im3, as_bytes
 
 
-def _call_batch_f32(fn, h, im1, im2, im3, out, occ_prob, who):
+def _compute_flow_batch(prefix, h, im1, im2, im3, out, dtype, occ_prob):
+    """computeFlowBatch of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    f32 = output_dtype(dtype, occ_prob, "computeFlowBatch") == np.float32
     im1, im2, im3, as_bytes = _batch_inputs(im1, im2, im3)
     n, _, H0, W0 = im1.shape
-    outs = _f32_outputs(n, H0, W0, occ_prob, out, who)
-    return _call_f32(fn, h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0, outs, occ_prob)
+    if f32:
+        return _call_f32(prefix + "compute_flow_batch_f32", h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0,
+                         _f32_outputs(n, H0, W0, occ_prob, out, "computeFlowBatch"), occ_prob)
+    return _call_f64(prefix + "compute_flow_batch", h, n, as_bytes, (im1, im2, im3), H0, W0, _f64_outputs(n, H0, W0, out))
 
 
-def _call_sequence_f32(fn, h, frames, out, occ_prob, who):
+def _compute_flow_sequence(prefix, h, frames, out, dtype, occ_prob):
+    """computeFlowSequence of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    f32 = output_dtype(dtype, occ_prob, "computeFlowSequence") == np.float32
     v, as_bytes = sequence_frames(frames)
     T, _, H0, W0 = v.shape
-    outs = _f32_outputs(T - 2, H0, W0, occ_prob, out, who)
-    return _call_f32(fn, h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0, outs, occ_prob)
-
-
-def _call_sequence(fn_f32, fn_u8, h, frames, out):
-    v, as_bytes = sequence_frames(frames)
-    T, _, H0, W0 = v.shape
-    flow, fwd, bwd = _sequence_outputs(T - 2, H0, W0, out)
-    outp = (flow.ctypes.data_as(C.POINTER(C.c_double)), fwd.ctypes.data_as(C.POINTER(C.c_ubyte)),
-            bwd.ctypes.data_as(C.POINTER(C.c_ubyte)))
-    if as_bytes:
-        _lib.check(getattr(_lib.lib(), fn_u8)(h, T, v.ctypes.data_as(C.POINTER(C.c_ubyte)), H0, W0, *outp))
-    else:
-        _lib.check(getattr(_lib.lib(), fn_f32)(h, T, _lib.fptr(v), H0, W0, *outp))
-    return flow, fwd, bwd
+    if f32:
+        return _call_f32(prefix + "compute_flow_sequence_f32", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0,
+                         _f32_outputs(T - 2, H0, W0, occ_prob, out, "computeFlowSequence"), occ_prob)
+    return _call_f64(prefix + "compute_flow_sequence", h, T, as_bytes, (v,), H0, W0, _f64_outputs(T - 2, H0, W0, out))
 
 
 class Model(object):
@@ -257,41 +262,14 @@ class Model(object):
         dtype=np.float32 (b2f_compute_flow_batch_f32): the flow is the float64 one rounded to float32, bit for bit, and
         never widened on the host; occ_prob=True (float32 only) appends the n x 2 x H x W occlusion probabilities to the
         returned tuple.  `out` then holds float32 flow / occ_prob buffers, and its masks may be None (not computed)."""
-        if output_dtype(dtype, occ_prob, "computeFlowBatch") == np.float32:
-            return _call_batch_f32("b2f_compute_flow_batch_f32", self._h, im1, im2, im3, out, occ_prob, "computeFlowBatch")
-        as_bytes = all(np.asarray(a).dtype == np.uint8 for a in (im1, im2, im3))
-        if as_bytes:
-            im1, im2, im3 = (np.ascontiguousarray(a) for a in (im1, im2, im3))
-        else:
-            im1, im2, im3 = _lib.f32(im1), _lib.f32(im2), _lib.f32(im3)
-        n, _, H0, W0 = im1.shape
-        assert im1.shape == im2.shape == im3.shape and im1.shape[1] == 3, "expected three n x 3 x H x W arrays"
-        if out is not None:
-            flow, fwd, bwd = out
-            assert flow.dtype == np.float64 and flow.shape == (n, 2, H0, W0) and flow.flags.c_contiguous
-            for m in (fwd, bwd):
-                assert m.dtype == np.uint8 and m.shape == (n, 1, H0, W0) and m.flags.c_contiguous
-        else:
-            flow = np.empty((n, 2, H0, W0), np.float64)
-            fwd = np.empty((n, 1, H0, W0), np.uint8)
-            bwd = np.empty((n, 1, H0, W0), np.uint8)
-        outp = (flow.ctypes.data_as(C.POINTER(C.c_double)), fwd.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                bwd.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        if as_bytes:
-            u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte))
-            _lib.check(_lib.lib().b2f_compute_flow_batch_u8(self._h, n, u8p(im1), u8p(im2), u8p(im3), H0, W0, *outp))
-        else:
-            _lib.check(_lib.lib().b2f_compute_flow_batch(self._h, n, _lib.fptr(im1), _lib.fptr(im2), _lib.fptr(im3), H0, W0, *outp))
-        return flow, fwd, bwd
+        return _compute_flow_batch("b2f_", self._h, im1, im2, im3, out, dtype, occ_prob)
 
     def computeFlowSequence(self, frames, out=None, dtype=np.float64, occ_prob=False):
         """Flow for every centre frame of a video: frames is a T x 3 x H x W float32 or uint8 array (or a list of 3 x H x W
         arrays); output i is computeFlow(frames[i], frames[i+1], frames[i+2]), i = 0 .. T-3, with the shapes and dtypes of
         computeFlowBatch.  Every frame is uploaded and run through the feature pyramid once (b2f_compute_flow_sequence).
         dtype / occ_prob / out as for computeFlowBatch (dtype=np.float32: b2f_compute_flow_sequence_f32)."""
-        if output_dtype(dtype, occ_prob, "computeFlowSequence") == np.float32:
-            return _call_sequence_f32("b2f_compute_flow_sequence_f32", self._h, frames, out, occ_prob, "computeFlowSequence")
-        return _call_sequence("b2f_compute_flow_sequence", "b2f_compute_flow_sequence_u8", self._h, frames, out)
+        return _compute_flow_sequence("b2f_", self._h, frames, out, dtype, occ_prob)
 
     def computeFlowDevice(self, d_im1, d_im2, d_im3, n, H0, W0, d_flow, d_occ_prob=None, d_fwd_occ=None, d_bwd_occ=None,
                           in_kind=IN_UNIT, stream=None):
@@ -386,31 +364,12 @@ class MultiModel(object):
 
     def computeFlowBatch(self, im1, im2, im3, out=None, dtype=np.float64, occ_prob=False):
         """Model.computeFlowBatch over the GPUs, with the same keywords."""
-        if output_dtype(dtype, occ_prob, "computeFlowBatch") == np.float32:
-            return _call_batch_f32("b2f_multi_compute_flow_batch_f32", self._h, im1, im2, im3, out, occ_prob, "computeFlowBatch")
-        as_bytes = all(np.asarray(a).dtype == np.uint8 for a in (im1, im2, im3))
-        if as_bytes:
-            im1, im2, im3 = (np.ascontiguousarray(a) for a in (im1, im2, im3))
-        else:
-            im1, im2, im3 = _lib.f32(im1), _lib.f32(im2), _lib.f32(im3)
-        n, _, H0, W0 = im1.shape
-        assert im1.shape == im2.shape == im3.shape and im1.shape[1] == 3, "expected three n x 3 x H x W arrays"
-        flow, fwd, bwd = _sequence_outputs(n, H0, W0, out)
-        outp = (flow.ctypes.data_as(C.POINTER(C.c_double)), fwd.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                bwd.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        if as_bytes:
-            u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte))
-            _lib.check(_lib.lib().b2f_multi_compute_flow_batch_u8(self._h, n, u8p(im1), u8p(im2), u8p(im3), H0, W0, *outp))
-        else:
-            _lib.check(_lib.lib().b2f_multi_compute_flow_batch(self._h, n, _lib.fptr(im1), _lib.fptr(im2), _lib.fptr(im3), H0, W0, *outp))
-        return flow, fwd, bwd
+        return _compute_flow_batch("b2f_multi_", self._h, im1, im2, im3, out, dtype, occ_prob)
 
     def computeFlowSequence(self, frames, out=None, dtype=np.float64, occ_prob=False):
         """Model.computeFlowSequence over the GPUs: the T-2 triplets are split with shard_range, every replica reads the
         frames its triplets need (T_i = its triplets + 2).  dtype / occ_prob / out as for Model.computeFlowSequence."""
-        if output_dtype(dtype, occ_prob, "computeFlowSequence") == np.float32:
-            return _call_sequence_f32("b2f_multi_compute_flow_sequence_f32", self._h, frames, out, occ_prob, "computeFlowSequence")
-        return _call_sequence("b2f_multi_compute_flow_sequence", "b2f_multi_compute_flow_sequence_u8", self._h, frames, out)
+        return _compute_flow_sequence("b2f_multi_", self._h, frames, out, dtype, occ_prob)
 
 
 def shard_range(n, rank, world):

@@ -1,7 +1,8 @@
 // Device side of the computeFlow boundary (/root/reference/back2future.lua:48-93): what the reference does on the
 // host around model:forward -- ColorNormalize, image.scale(..., W, H) 'bilinear' down to multiples of 64, and
-// after the forward pass image.scale(..., 'simple') back to the input size and the 0.6666 thresholds -- runs here
-// on the uploaded planes, so the host only moves bytes (and, on the f64 entries, widens the flow, b2f_pipeline.hip).  The arithmetic
+// after the forward pass image.scale(..., 'simple') back to the input size and the 0.6666 thresholds, one output kernel for
+// every entry point -- runs here on the uploaded planes, so the host only moves bytes (and, on the f64 entries, widens the
+// flow, b2f_pipeline.hip).  The arithmetic
 // is the CPU routines' (oracle/b2f_oracle.c) operation for operation: every output element is produced by one
 // thread with the same sequence of IEEE fp32 operations (the file is built with -ffp-contract=off and correctly
 // rounded division), so the results are bit-identical to the CPU ones.
@@ -73,51 +74,15 @@ hipError_t launch_image_scale(const float *src, int normalize, long planes, int 
     return hipGetLastError();
 }
 
-// back2future.lua:77-93: image.scale(..., 'simple') of est[1] and est[3] to H0 x W0 and the thresholds
-// fwd_occ = ge(occ_est[2], 0.6666), bwd_occ = ge(occ_est[1], 0.6666).  The flow leaves the device as the network's
-// fp32 values (its :double() copy times sc_w / sc_h is formed by the host threads that hand it to the caller:
-// half the bytes on the link); flow32 == nullptr when H0 x W0 is the network size (the flow is downloaded as is).
-// flow_net [B][2][fh][fw], est3 [B][est3_ch][fh][fw] -> flow32 [B][2][H0][W0] f32, fwd/bwd [B][H0][W0] u8
-__global__ void postprocess_kernel(const float *flow_net, const float *est3, int est3_ch, int B, int fh, int fw, int H0,
-                                   int W0, float *flow32, unsigned char *fwd_occ, unsigned char *bwd_occ)
-{
-    const size_t hw0 = (size_t)H0 * W0, hw = (size_t)fh * fw;
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)B * hw0) return;
-    const size_t b = t / hw0, d = t - b * hw0;
-    const int j = (int)(d / W0), i = (int)(d - (size_t)j * W0);
-    // image.scale 'simple' [3P]: src index = (long)(dst * (float)src_len / dst_len), clamped
-    const float scx = (float)fw / (float)W0, scy = (float)fh / (float)H0;
-    long jj = (long)((float)j * scy);
-    if (jj > fh - 1) jj = fh - 1;
-    long ii = (long)((float)i * scx);
-    if (ii > fw - 1) ii = fw - 1;
-    const size_t s = (size_t)jj * fw + ii;
-    const float *e3 = est3 + b * est3_ch * hw;
-    if (flow32) {
-        const float *fn = flow_net + b * 2 * hw;
-        flow32[b * 2 * hw0 + d] = fn[s];
-        flow32[b * 2 * hw0 + hw0 + d] = fn[hw + s];
-    }
-    fwd_occ[t] = ((double)e3[hw + s] >= 0.6666) ? 1 : 0;
-    bwd_occ[t] = ((double)e3[s] >= 0.6666) ? 1 : 0;
-}
-
-hipError_t launch_postprocess(const float *flow_net, const float *est3, int est3_ch, int B, int fh, int fw, int H0, int W0,
-                              float *flow32, unsigned char *fwd_occ, unsigned char *bwd_occ, hipStream_t s)
-{
-    const size_t n = (size_t)B * H0 * W0;
-    hipLaunchKernelGGL(postprocess_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, flow_net, est3, est3_ch, B, fh,
-                       fw, H0, W0, flow32, fwd_occ, bwd_occ);
-    return hipGetLastError();
-}
-
-// The float32 outputs of b2f_compute_flow*_f32 / b2f_compute_flow*_device, from the network's outputs at fh x fw to
-// H0 x W0 with postprocess_kernel's index rule:
-//   flow      (float)((double)est[1] * sc)   (sc_w for channel 0, sc_h for 1): the f64 entries' value rounded to nearest
+// back2future.lua:77-93 for every computeFlow entry: image.scale(..., 'simple') of the network's outputs from fh x fw to H0 x W0
+// and the thresholds:
+//   flow      (float)((double)est[1] * sc)   (sc_w for channel 0, sc_h for 1): the f64 value rounded to nearest.  The f64 entries
+//             pass sc = 1 -- (float)((double)f * 1.0) == f -- and their host threads form the :double() copy times sc_w / sc_h
+//             (:80-84): half the bytes on the link
 //   occ_prob  skip_occs[3] (occ: [B][2][fh][fw]; est[3] of a Soft model, est[2] of a Hard one)
-//   fwd_occ / bwd_occ  the thresholds of est[3] channels 2 / 1, as postprocess_kernel
-// Any output may be nullptr.  One thread per kOutPx consecutive pixels of an output row: 16-byte stores (4-byte for the
+//   fwd_occ / bwd_occ  ge(est[3][2], 0.6666) / ge(est[3][1], 0.6666)
+// Any output may be nullptr (the host path passes no flow when H0 x W0 is the network size: it downloads the network's planes).
+// One thread per kOutPx consecutive pixels of an output row: 16-byte stores (4-byte for the
 // masks) where the row holds them and the address is aligned, scalar stores for a row's tail and misaligned rows.  When
 // the column map is the identity (fw == W0, so the 4 source samples are consecutive and 16-byte aligned) the planes are
 // read with 16-byte loads too (kVec: a separate instantiation, so that the compiler cannot fold the two load paths into one).
@@ -161,7 +126,7 @@ __global__ void outputs_f32_kernel(const float *flow_net, const float *occ, cons
     const size_t row = t / nq, b = row / H0;
     const int j = (int)(row - b * H0), i0 = (int)(t - row * nq) * kOutPx;
     const int n = min(kOutPx, W0 - i0);
-    // image.scale 'simple' [3P]: src index = (long)(dst * (float)src_len / dst_len), clamped -- postprocess_kernel's arithmetic
+    // image.scale 'simple' [3P]: src index = (long)(dst * (float)src_len / dst_len), clamped
     const float scx = (float)fw / (float)W0, scy = (float)fh / (float)H0;
     long jj = (long)((float)j * scy);
     if (jj > fh - 1) jj = fh - 1;

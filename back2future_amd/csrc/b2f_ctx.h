@@ -90,7 +90,39 @@ struct FlowOutputs {
     float *flow32 = nullptr, *occ_prob = nullptr;
     unsigned char *fwd_occ = nullptr, *bwd_occ = nullptr;
     bool f32() const { return flow64 == nullptr; }
+    // the outputs of triplets b, b + 1, ... (planes of hw0 pixels); nullptr stays nullptr
+    FlowOutputs from_triplet(size_t b, size_t hw0) const
+    {
+        auto at = [](auto *p, size_t off) { return p ? p + off : p; };
+        return {at(flow64, b * 2 * hw0), at(flow32, b * 2 * hw0), at(occ_prob, b * 2 * hw0), at(fwd_occ, b * hw0), at(bwd_occ, b * hw0)};
+    }
 };
+
+// One computeFlow call, whichever of the entry points it came through: n triplets (im1..im3, n x 3 x H0 x W0 each) or, with seq, the
+// n + 2 frames of a sequence in im1; inputs B2F_IN_UNIT (floats in [0,1]) or B2F_IN_U8 (bytes).  req: the request's triplet count the
+// kernel rule follows (0: n; b2f_multi passes the caller's n to its shards).  who names the entry point in messages.
+struct FlowRequest {
+    int n = 0;
+    bool seq = false;
+    int in_kind = B2F_IN_UNIT;
+    const void *im1 = nullptr, *im2 = nullptr, *im3 = nullptr;
+    int H0 = 0, W0 = 0;
+    FlowOutputs o;
+    int req = 0;
+    const char *who = "";
+};
+
+inline FlowRequest batch_request(const char *who, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0,
+                                 const FlowOutputs &o)
+{
+    return {n, false, in_kind, im1, im2, im3, H0, W0, o, 0, who};
+}
+
+// T frames hold T - 2 triplets (0 below three frames: check_request refuses the sequence)
+inline FlowRequest sequence_request(const char *who, int T, int in_kind, const void *frames, int H0, int W0, const FlowOutputs &o)
+{
+    return {T >= 3 ? T - 2 : 0, true, in_kind, frames, nullptr, nullptr, H0, W0, o, 0, who};
+}
 
 // Context-owned device workspace of the device entries (b2f_compute_flow_device / _sequence_device): grows, never shrinks.
 struct DevWork {
@@ -327,18 +359,12 @@ void drop_gen_out(b2f_ctx *c);
 // of a sequence (T x 3 x H x W) instead of B triplets (B x 9 x H x W)
 int forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow, float *dev_occ,
                    float *dev_est3, hipStream_t s, bool graph, bool seq = false);
-// b2f_pipeline.hip: the host pipeline on T frames (b2f_compute_flow_sequence*); req = the request's triplet count the kernel rule
-// follows (0: T - 2)
-int compute_flow_sequence(b2f_ctx *c, int T, const void *frames, bool bytes_in, int H0, int W0, double *flow, unsigned char *fwd_occ,
-                          unsigned char *bwd_occ, int req);
-// b2f_pipeline.hip: the f32 host entries (b2f_compute_flow_batch_f32 / _sequence_f32) on `count` triplets or, with seq, count = T
-// frames in im1 (im2 / im3 unused), with the request size req of the kernel rule (0: the triplets); `who` names the entry point in
-// error messages
-int compute_flow_f32(b2f_ctx *c, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
-                     const FlowOutputs &o, int req, const char *who);
-// argument checks of the f32 entries that need no context and no HIP call (in_kind, T / n, shape, output pointers); 0 = fine
-int check_f32_args(const char *who, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
-                   const float *flow);
+// b2f_pipeline.hip: the checks of a request that need no context and no HIP call (in_kind, T / n, shape, required pointers); 0 = fine
+int check_request(const FlowRequest &r);
+// b2f_pipeline.hip: a request on host buffers (the upload / kernels / download pipeline) and on device buffers (the kernels alone,
+// asynchronous on `stream`, nullptr: the context's)
+int compute_flow_host(b2f_ctx *c, const FlowRequest &r);
+int compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream);
 // pieces of b2f_api.hip the generic graph executor (b2f_graph.hip) builds on
 ConvSeg cp8_seg(const float *ptr, int C, size_t hw);
 int find_conv_id(const b2f_ctx *c, int kind, int level, int idx);

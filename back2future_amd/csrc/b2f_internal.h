@@ -314,12 +314,9 @@ hipError_t launch_fill(float *p, size_t n, float v, hipStream_t s);
 // ColorNormalize applied to the source samples (plane % 3 = colour); bit-identical to the host function
 hipError_t launch_image_scale(const float *src, int normalize, long planes, int Hs, int Ws, float *tmp, float *dst,
                               int Hd, int Wd, hipStream_t s);
-// nearest rescale + thresholds (back2future.lua:77-93): planar net outputs -> fp32 flow at H0 x W0 (nullptr: not
-// written, the net size is the output size), u8 masks
-hipError_t launch_postprocess(const float *flow_net, const float *est3, int est3_ch, int B, int fh, int fw, int H0, int W0,
-                              float *flow32, unsigned char *fwd_occ, unsigned char *bwd_occ, hipStream_t s);
-// the float32 outputs (b2f_*_f32, b2f_compute_flow*_device): flow = (float)((double)est[1] * sc_w | sc_h), occ_prob = occ, the
-// masks of postprocess, all nearest-rescaled to H0 x W0 with postprocess's index rule; nullptr outputs are not written
+// the outputs of every computeFlow entry (back2future.lua:77-93), nearest-rescaled (image.scale 'simple') from the planar net outputs
+// to H0 x W0: flow = (float)((double)est[1] * sc_w | sc_h) (the f64 entries pass 1 and scale on the host), occ_prob = occ, the masks
+// est[3] >= 0.6666; nullptr outputs are not written
 hipError_t launch_outputs_f32(const float *flow_net, const float *occ, const float *est3, int est3_ch, int B, int fh, int fw, int H0,
                               int W0, double sc_w, double sc_h, float *flow, float *occ_prob, unsigned char *fwd_occ,
                               unsigned char *bwd_occ, hipStream_t s);

@@ -144,6 +144,25 @@ int run_sharded(b2f_multi *m, int n, F call)
     return 0;
 }
 
+// A host request over the replicas: replica i computes triplets [lo, hi) of the caller's n, from their inputs (a sequence: frames
+// [lo, hi + 2)) into their slice of the caller's outputs.  Every shard passes the caller's n down as the request size of the kernel
+// rule, so a triplet's bits do not depend on the number of GPUs.
+int compute_flow_multi(b2f_multi *m, const FlowRequest &r)
+{
+    CHK(check_request(r));
+    if (!m) return api_fail(std::string(r.who) + ": null context");
+    const size_t hw = (size_t)r.H0 * r.W0, frame = 3 * hw * (r.in_kind == B2F_IN_U8 ? 1 : 4);   // bytes of an input frame
+    return run_sharded(m, r.n, [&](int i, int lo, int hi) {
+        auto in = [&](const void *p) { return p ? (const void *)((const char *)p + lo * frame) : nullptr; };
+        FlowRequest s = r;
+        s.n = hi - lo;
+        s.im1 = in(r.im1); s.im2 = in(r.im2); s.im3 = in(r.im3);
+        s.o = r.o.from_triplet(lo, hw);
+        s.req = r.n;
+        return compute_flow_host(m->ctx[(size_t)i], s);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -259,90 +278,42 @@ B2F_CATCH("b2f_multi_weights_checksum")
 int b2f_multi_compute_flow_batch(b2f_multi *m, int n, const float *im1, const float *im2, const float *im3, int H0, int W0,
                                  double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    if (!m || !im1 || !im2 || !im3 || !flow || !fwd_occ || !bwd_occ) return api_fail("b2f_multi_compute_flow_batch: null argument");
-    if (n <= 0 || H0 <= 0 || W0 <= 0) return api_fail("b2f_multi_compute_flow_batch: bad shape");
-    const size_t hw = (size_t)H0 * W0;
-    return run_sharded(m, n, [&](int i, int lo, int hi) {
-        return b2f_compute_flow_batch(m->ctx[(size_t)i], hi - lo, im1 + (size_t)lo * 3 * hw, im2 + (size_t)lo * 3 * hw, im3 + (size_t)lo * 3 * hw,
-                                      H0, W0, flow + (size_t)lo * 2 * hw, fwd_occ + (size_t)lo * hw, bwd_occ + (size_t)lo * hw);
-    });
+    return compute_flow_multi(m, batch_request(__func__, n, B2F_IN_UNIT, im1, im2, im3, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_multi_compute_flow_batch")
 
 int b2f_multi_compute_flow_batch_u8(b2f_multi *m, int n, const unsigned char *im1, const unsigned char *im2, const unsigned char *im3,
                                     int H0, int W0, double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    if (!m || !im1 || !im2 || !im3 || !flow || !fwd_occ || !bwd_occ) return api_fail("b2f_multi_compute_flow_batch_u8: null argument");
-    if (n <= 0 || H0 <= 0 || W0 <= 0) return api_fail("b2f_multi_compute_flow_batch_u8: bad shape");
-    const size_t hw = (size_t)H0 * W0;
-    return run_sharded(m, n, [&](int i, int lo, int hi) {
-        return b2f_compute_flow_batch_u8(m->ctx[(size_t)i], hi - lo, im1 + (size_t)lo * 3 * hw, im2 + (size_t)lo * 3 * hw, im3 + (size_t)lo * 3 * hw,
-                                         H0, W0, flow + (size_t)lo * 2 * hw, fwd_occ + (size_t)lo * hw, bwd_occ + (size_t)lo * hw);
-    });
+    return compute_flow_multi(m, batch_request(__func__, n, B2F_IN_U8, im1, im2, im3, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_multi_compute_flow_batch_u8")
-
-// The T - 2 triplets of a sequence are sharded like a batch; replica i reads frames [lo, hi + 2) and writes outputs [lo, hi).
-// The kernel rule of every shard follows the caller's triplet count (req), so the bits do not depend on the number of GPUs.
-static int multi_sequence(b2f_multi *m, int T, const void *frames, bool bytes_in, int H0, int W0, double *flow, unsigned char *fwd_occ,
-                          unsigned char *bwd_occ, const char *who)
-{
-    if (!m || !frames || !flow || !fwd_occ || !bwd_occ) return api_fail(std::string(who) + ": null argument");
-    if (T < 3) return api_fail(std::string(who) + ": a sequence needs T >= 3 frames (one triplet)");
-    if (H0 <= 0 || W0 <= 0) return api_fail(std::string(who) + ": bad shape");
-    const size_t hw = (size_t)H0 * W0, esz = bytes_in ? 1 : 4;
-    const int n = T - 2;
-    return run_sharded(m, n, [&](int i, int lo, int hi) {
-        return compute_flow_sequence(m->ctx[(size_t)i], hi - lo + 2, (const char *)frames + (size_t)lo * 3 * hw * esz, bytes_in, H0, W0,
-                                     flow + (size_t)lo * 2 * hw, fwd_occ + (size_t)lo * hw, bwd_occ + (size_t)lo * hw, n);
-    });
-}
-
-// The f32 entries: batch and sequence sharded as above; both pass the caller's triplet count down as the kernel-rule request
-// size (multi_sequence's rule), so a triplet's bits do not depend on the number of GPUs.  count = n triplets, or T frames (seq).
-static int multi_f32(b2f_multi *m, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
-                     const FlowOutputs &o, const char *who)
-{
-    CHK(check_f32_args(who, count, in_kind, im1, im2, im3, seq, H0, W0, o.flow32));
-    if (!m) return api_fail(std::string(who) + ": null context");
-    const size_t hw = (size_t)H0 * W0, esz = in_kind == B2F_IN_U8 ? 1 : 4;
-    const int n = seq ? count - 2 : count;
-    auto at = [&](const void *p, int lo) { return p ? (const void *)((const char *)p + (size_t)lo * 3 * hw * esz) : nullptr; };
-    return run_sharded(m, n, [&](int i, int lo, int hi) {
-        const FlowOutputs oi{nullptr, o.flow32 + (size_t)lo * 2 * hw, o.occ_prob ? o.occ_prob + (size_t)lo * 2 * hw : nullptr,
-                             o.fwd_occ ? o.fwd_occ + (size_t)lo * hw : nullptr, o.bwd_occ ? o.bwd_occ + (size_t)lo * hw : nullptr};
-        return compute_flow_f32(m->ctx[(size_t)i], seq ? hi - lo + 2 : hi - lo, in_kind, at(im1, lo), at(im2, lo), at(im3, lo), seq, H0, W0, oi, n,
-                                who);
-    });
-}
 
 int b2f_multi_compute_flow_sequence(b2f_multi *m, int T, const float *frames, int H0, int W0, double *flow, unsigned char *fwd_occ,
                                     unsigned char *bwd_occ) try
 {
-    return multi_sequence(m, T, frames, false, H0, W0, flow, fwd_occ, bwd_occ, "b2f_multi_compute_flow_sequence");
+    return compute_flow_multi(m, sequence_request(__func__, T, B2F_IN_UNIT, frames, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_multi_compute_flow_sequence")
 
 int b2f_multi_compute_flow_sequence_u8(b2f_multi *m, int T, const unsigned char *frames, int H0, int W0, double *flow,
                                        unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    return multi_sequence(m, T, frames, true, H0, W0, flow, fwd_occ, bwd_occ, "b2f_multi_compute_flow_sequence_u8");
+    return compute_flow_multi(m, sequence_request(__func__, T, B2F_IN_U8, frames, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_multi_compute_flow_sequence_u8")
 
 int b2f_multi_compute_flow_batch_f32(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0,
                                      float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    return multi_f32(m, n, in_kind, im1, im2, im3, false, H0, W0, FlowOutputs{nullptr, flow, occ_prob, fwd_occ, bwd_occ},
-                     "b2f_multi_compute_flow_batch_f32");
+    return compute_flow_multi(m, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0, {nullptr, flow, occ_prob, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_multi_compute_flow_batch_f32")
 
 int b2f_multi_compute_flow_sequence_f32(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0, float *flow, float *occ_prob,
                                         unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    return multi_f32(m, T, in_kind, frames, nullptr, nullptr, true, H0, W0, FlowOutputs{nullptr, flow, occ_prob, fwd_occ, bwd_occ},
-                     "b2f_multi_compute_flow_sequence_f32");
+    return compute_flow_multi(m, sequence_request(__func__, T, in_kind, frames, H0, W0, {nullptr, flow, occ_prob, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_multi_compute_flow_sequence_f32")
 

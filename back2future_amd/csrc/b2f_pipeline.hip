@@ -1,6 +1,8 @@
-// Host-buffer boundary of libb2f.so: b2f_compute_flow / b2f_compute_flow_batch[_u8] (back2future.lua:47-95) as a
-// double-buffered upload / kernels / download pipeline around model:forward.  Device kernels of the pre/post
-// processing: b2f_boundary.hip.
+// The computeFlow boundary of libb2f.so (back2future.lua:47-95): every b2f_compute_flow* entry point (and b2f_multi's, b2f_multi.hip)
+// builds one FlowRequest.  check_request() refuses a malformed one before any HIP call; compute_flow_host() runs it on host buffers as a
+// double-buffered upload / kernels / download pipeline around model:forward, compute_flow_device() runs the kernels half alone on
+// device buffers.  Both cut the request with plan_subbatches() and run every sub-batch through run_kernels().  Device kernels of the
+// pre/post processing: b2f_boundary.hip.
 #include "b2f_ctx.h"
 
 #include <cstdlib>
@@ -9,7 +11,6 @@ using namespace b2f;
 
 static int fail(const std::string &m) { return api_fail(m); }
 
-// ---- host-buffer entry point: a double-buffered upload / compute / download pipeline ----------------
 namespace {
 
 // 1 when [p, p + bytes) is page-locked host memory known to the HIP runtime (hipHostMalloc / hipHostRegister, e.g. a
@@ -97,8 +98,101 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     return 0;
 }
 
+// The sizes of a request: the network runs at fh x fw, H0 x W0 cut down to multiples of 64 (back2future.lua:54-67), and its flow is
+// rescaled to H0 x W0 by sc_w / sc_h (:78-79).  C3: channels of est[3].
+struct Geometry {
+    int H0, W0, fh, fw, C3;
+    bool same;        // H0 x W0 is the network size: no image.scale, the outputs are not rescaled
+    size_t hw0, hw;   // pixels of an input plane / of a network plane
+    double sc_w, sc_h;
+};
+
+Geometry geometry(const b2f_ctx *c, int H0, int W0)
+{
+    const int fw = W0 - W0 % 64, fh = H0 - H0 % 64;
+    return {H0, W0, fh, fw, c->past_flow ? 2 : 3, fw == W0 && fh == H0, (size_t)H0 * W0, (size_t)fh * fw, (double)W0 / (double)fw,
+            (double)H0 / (double)fh};
+}
+
+// The n triplets of a request cut into sub-batches of up to host_subbatch_pixels input pixels per plane set, counted in units: triplets,
+// or frames in sequence mode, where a sub-batch also holds the two frames it shares with the next one (and at least the 3 of one
+// triplet).  With ramp the sizes start at ~2 Mpx (one full-HD unit) and double up to the largest: the host pipeline's kernels start
+// after a small upload instead of a whole sub-batch's.  (first triplet, count) per sub-batch; *SB = triplets of the largest.
+std::vector<std::pair<int, int>> plan_subbatches(const b2f_ctx *c, int n, bool seq, size_t hw0, bool ramp, int *SB)
+{
+    const int gu = seq ? 2 : 0;   // units a sub-batch holds beyond its triplets
+    const int SBU = (int)std::min<long long>(n + gu, std::max<long long>(1 + gu, c->host_subbatch_pixels / (long long)hw0));
+    const int sz0 = ramp ? (int)std::min<long long>(SBU, std::max<long long>(1 + gu, (2ll << 20) / (long long)hw0)) : SBU;
+    std::vector<std::pair<int, int>> subs;
+    for (int b0 = 0, sz = sz0; b0 < n; sz = std::min(2 * sz, SBU)) {
+        const int nb = std::min(sz - gu, n - b0);
+        subs.push_back({b0, nb});
+        b0 += nb;
+    }
+    *SB = SBU - gu;
+    return subs;
+}
+
+// While it lives, the kernel choice of every sub-batch follows the request's n (a single-triplet request takes the per-launch rule, a
+// batch the map-size rule -- for ALL its sub-batches, also those of one triplet the ramp and the tail produce)
+struct ReqBatch {
+    b2f_ctx *c;
+    ReqBatch(b2f_ctx *cc, const FlowRequest &r) : c(cc) { c->req_batch = r.req > 0 ? r.req : r.n; }
+    ~ReqBatch() { c->req_batch = 0; }
+};
+
+// device buffers of a sub-batch between its input and its outputs
+struct NetBuffers {
+    float *tmp, *scaled;        // image.scale's row pass and result (unused at the network size)
+    float *flow, *occ, *est3;   // the forward pass's outputs at fh x fw; occ: skip_occs[3] of a Hard model, nullptr when not needed
+};
+
+// The kernels of a sub-batch of nb triplets on s.  x: its `planes` input planes at H0 x W0, B2F_IN_UNIT floats or, at the network
+// size only, B2F_IN_U8 bytes.  ColorNormalize, then image.scale to the /64 size (:50-71) -- without a rescale the raw planes go to the
+// network as they are and the first conv kernel normalizes on the fly --, the forward pass, and outputs_f32_kernel into `out` (device
+// buffers at H0 x W0; nullptr: not written).  The flow of an f64 request is left unscaled: the host threads form `double * sc` (:80-84).
+int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void *x, int kind, long planes, int nb, const NetBuffers &net,
+                const FlowOutputs &out, bool graph, hipStream_t s)
+{
+    if (!g.same) {
+        HIPCHK(launch_image_scale((const float *)x, 1, planes, g.H0, g.W0, net.tmp, net.scaled, g.fh, g.fw, s));
+        x = net.scaled;
+        kind = B2F_IN_NORMALIZED;
+    }
+    CHK(forward_device(c, x, kind, nb, g.fh, g.fw, net.flow, net.occ, net.est3, s, graph, r.seq));
+    const bool f32 = r.o.f32();
+    HIPCHK(launch_outputs_f32(net.flow, g.C3 == 3 ? net.occ : net.est3, net.est3, g.C3, nb, g.fh, g.fw, g.H0, g.W0, f32 ? g.sc_w : 1.0,
+                              f32 ? g.sc_h : 1.0, out.flow32, out.occ_prob, out.fwd_occ, out.bwd_occ, s));
+    return 0;
+}
+
+// check_request, then what both paths check of the context
+int check_context(b2f_ctx *c, const FlowRequest &r)
+{
+    CHK(check_request(r));
+    if (!c) return fail(std::string(r.who) + ": null context");
+    if (r.seq && !c->g.shipped())
+        return fail(std::string(r.who) + ": sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
+    return 0;
+}
+
 }  // namespace
 
+int b2f::check_request(const FlowRequest &r)
+{
+    const std::string w(r.who);
+    if (r.in_kind == B2F_IN_NORMALIZED)
+        return fail(w + ": in_kind B2F_IN_NORMALIZED is refused: computeFlow normalizes its frames itself (B2F_IN_UNIT or B2F_IN_U8)");
+    if (r.in_kind != B2F_IN_UNIT && r.in_kind != B2F_IN_U8) return fail(w + ": in_kind must be B2F_IN_UNIT or B2F_IN_U8");
+    if (r.seq && r.n <= 0) return fail(w + ": a sequence needs T >= 3 frames (one triplet)");
+    if (r.n <= 0 || r.H0 <= 0 || r.W0 <= 0) return fail(w + ": bad shape");
+    if (r.H0 < 64 || r.W0 < 64) return fail(w + ": image smaller than 64 pixels");
+    const FlowOutputs &o = r.o;
+    if (!r.im1 || (!r.seq && (!r.im2 || !r.im3)) || (o.f32() ? !o.flow32 : !o.fwd_occ || !o.bwd_occ)) return fail(w + ": null argument");
+    return 0;
+}
+
+// ---- host buffers: a double-buffered upload / compute / download pipeline --------------------------------------------------------
 // The n triplets are cut into sub-batches (up to B2F_HOST_SUBBATCH_PIXELS input pixels each, default 16 Mpx = eight
 // full-HD triplets) that flow through two buffer sets on three streams: uploads on s_in, ColorNormalize /
 // image.scale / the network / the nearest rescale + thresholds on the context's stream, downloads on s_out.
@@ -114,59 +208,24 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
 // (b, b + 1, b + 2).  A sub-batch of nb triplets uploads its nb + 2 frames once -- the two it shares with the next
 // sub-batch go up (and through the pyramid) again there -- and runs the sequence forward; everything else is the
 // triplet pipeline with "frame" in place of "triplet" as the unit of upload, 8-bit detection and the sub-batch budget.
-// req: the request's triplet count that picks the kernel rule (0: n; b2f_multi passes the caller's count to its shards).
 // Outputs (FlowOutputs): the f64 path widens the flow on the host threads; the f32 path (b2f_*_f32) has the device write
 // every output in its final form (outputs_f32_kernel), so the drain step only copies -- or nothing at all: page-locked
 // flow / occ_prob / mask buffers are DMA'd in place -- and a NULL occ_prob or mask is neither written nor downloaded.
-namespace {
-int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, const void *im3, bool bytes_in, int H0,
-                          int W0, const FlowOutputs &o, bool seq = false, int req = 0)
+int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
 {
-    const bool f32 = o.f32();
-    if (!c || !im1 || (!seq && (!im2 || !im3)) || (f32 ? !o.flow32 : !o.fwd_occ || !o.bwd_occ))
-        return fail("b2f_compute_flow: null argument");
-    if (n <= 0 || H0 <= 0 || W0 <= 0) return fail("b2f_compute_flow: bad shape");
-    if (c->debug_fail_next) {   // tests (option debug_fail_next): one forced failure, e.g. on one replica of a b2f_multi
-        c->debug_fail_next = 0;
-        return fail("b2f_compute_flow: forced failure (option debug_fail_next)");
-    }
-    const int fw = W0 - W0 % 64, fh = H0 - H0 % 64;   // back2future.lua:54-67
-    if (fw <= 0 || fh <= 0) return fail("b2f_compute_flow: image smaller than 64 pixels");
-    CHK(check_shape(1, fh, fw));
-    if (seq && !c->g.shipped())
-        return fail("b2f_compute_flow_sequence: sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
-    // the kernel choice of every sub-batch follows the caller's n (a single-triplet request takes the per-launch rule, a batch the map-size
-    // rule -- for ALL its sub-batches, also those of one triplet the ramp and the tail produce)
-    struct ReqBatch { b2f_ctx *c; ReqBatch(b2f_ctx *cc, int nn) : c(cc) { c->req_batch = nn; } ~ReqBatch() { c->req_batch = 0; } } req_guard(c, req > 0 ? req : n);
+    CHK(check_context(c, r));
+    const std::string w(r.who);
     HIPCHK(hipSetDevice(c->device));
-    const size_t hw0 = (size_t)H0 * W0, hw = (size_t)fh * fw;
-    const bool same = (fw == W0 && fh == H0);
-    const int C3 = c->past_flow ? 2 : 3;
-    const double sc_h = (double)H0 / (double)fh, sc_w = (double)W0 / (double)fw;   // :78-79
-    const long long sub_px = c->host_subbatch_pixels;
-    const int nthreads = std::max(2, c->host_threads > 0 ? c->host_threads : (int)std::min(16u, std::thread::hardware_concurrency()));
-    const bool use_u8 = bytes_in || c->host_u8 != 0;
+    const FlowOutputs &o = r.o;
+    const int n = r.n;
+    const bool seq = r.seq, f32 = o.f32(), bytes_in = r.in_kind == B2F_IN_U8;
+    const Geometry g = geometry(c, r.H0, r.W0);
+    const size_t hw0 = g.hw0;
+    const bool same = g.same;
     const size_t esz = bytes_in ? 1 : 4;   // bytes per input sample in the caller's buffers
-    // sub-batch sizes in units (triplets; frames in sequence mode, at least the 3 of one triplet): up to sub_px input
-    // pixels per plane set; they ramp up from ~2 Mpx (one full-HD unit) by doubling to SBU: the kernels start after a small
-    // upload instead of SBU units' (option host_ramp = 0: uniform sizes)
-    const int gu = seq ? 2 : 0;   // units a sub-batch holds beyond its triplets
-    const int SBU = (int)std::min<long long>(n + gu, std::max<long long>(1 + gu, sub_px / (long long)hw0));
-    const int SB = SBU - gu;     // triplets of the largest sub-batch
-    const bool ramp = c->host_ramp != 0;
-    const int sz0 = ramp ? (int)std::min<long long>(SBU, std::max<long long>(1 + gu, (2ll << 20) / (long long)hw0)) : SBU;
-    std::vector<std::pair<size_t, int>> subs;   // (first triplet, count)
-    for (int b0 = 0, sz = sz0; b0 < n; sz = std::min(2 * sz, SBU)) {
-        const int nb = std::min(sz - gu, n - b0);
-        subs.push_back({(size_t)b0, nb});
-        b0 += nb;
-    }
-    const int nsub = (int)subs.size();
-
-    if (!c->s_in) HIPCHK(hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
-    if (!c->s_out) HIPCHK(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
-    const int k_in[3] = {mem_kind(im1, (size_t)(n + gu) * 3 * hw0 * esz), seq ? 1 : mem_kind(im2, (size_t)n * 3 * hw0 * esz),
-                         seq ? 1 : mem_kind(im3, (size_t)n * 3 * hw0 * esz)};
+    const int gu = seq ? 2 : 0;            // frames of a sequence beyond its triplets
+    const int k_in[3] = {mem_kind(r.im1, (size_t)(n + gu) * 3 * hw0 * esz), seq ? 1 : mem_kind(r.im2, (size_t)n * 3 * hw0 * esz),
+                         seq ? 1 : mem_kind(r.im3, (size_t)n * 3 * hw0 * esz)};
     double *flow = o.flow64;
     unsigned char *fwd_occ = o.fwd_occ, *bwd_occ = o.bwd_occ;
     // unrequested outputs (f32 path) count as page-locked: nothing is staged for them
@@ -175,23 +234,36 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
                           out_kind(bwd_occ, (size_t)n * hw0), out_kind(o.occ_prob, (size_t)n * 2 * hw0 * 4)};
     for (int i = 0; i < 4; ++i)
         if ((i < 3 && k_in[i] < 0) || k_out[i] < 0)
-            return fail("b2f_compute_flow: device memory passed to a host-buffer entry point (use b2f_compute_flow_device / "
-                        "b2f_compute_flow_sequence_device)");
+            return fail(w + ": device memory passed to a host-buffer entry point (use b2f_compute_flow_device / "
+                            "b2f_compute_flow_sequence_device)");
+    if (c->debug_fail_next) {   // tests (option debug_fail_next): one forced failure, e.g. on one replica of a b2f_multi
+        c->debug_fail_next = 0;
+        return fail(w + ": forced failure (option debug_fail_next)");
+    }
+    const ReqBatch req_guard(c, r);
+    const int nthreads = std::max(2, c->host_threads > 0 ? c->host_threads : (int)std::min(16u, std::thread::hardware_concurrency()));
+    const bool use_u8 = bytes_in || c->host_u8 != 0;
+    int SB = 0;
+    const std::vector<std::pair<int, int>> subs = plan_subbatches(c, n, seq, hw0, c->host_ramp != 0, &SB);
+    const int nsub = (int)subs.size();
+
+    if (!c->s_in) HIPCHK(hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
+    if (!c->s_out) HIPCHK(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
     const bool pinned_in = k_in[0] == 1 && k_in[1] == 1 && k_in[2] == 1;
     const bool stage_in = !pinned_in && !bytes_in;   // float staging buffer (byte inputs stage through h_u8)
     const bool stage_masks = !(k_out[1] == 1 && k_out[2] == 1);
     const bool want_prob = f32 && o.occ_prob;
     // f32 path: occ_prob is skip_occs[3] -- est[3] of a Soft model (d_est3), an extra forward output of a Hard one (d_occ)
-    SlotNeeds q{same, stage_in, stage_masks, use_u8, want_prob && C3 == 3, want_prob && !same, !f32 || k_out[0] != 1, want_prob && k_out[3] != 1};
+    SlotNeeds q{same, stage_in, stage_masks, use_u8, want_prob && g.C3 == 3, want_prob && !same, !f32 || k_out[0] != 1, want_prob && k_out[3] != 1};
     // (a sequence sub-batch's nb + 2 frames are 3 nb + 6 <= 9 nb planes: the triplet layout of the slot holds them)
     for (int k = 0; k < std::min(nsub, 2); ++k)
-        CHK(ensure_slot(c, c->slot[k], SB, hw0, hw, H0, fw, C3, q));
+        CHK(ensure_slot(c, c->slot[k], SB, hw0, g.hw, g.H0, g.fw, g.C3, q));
     // the calling thread and the drain thread each count as one worker of their pool
     const int w_out = std::max(0, nthreads / 3 - 1), w_in = std::max(0, nthreads - nthreads / 3 - 1);
     if (!c->pool_in || c->pool_in->workers() != w_in) c->pool_in.reset(new CopyPool(w_in));
     if (!c->pool_out || c->pool_out->workers() != w_out) c->pool_out.reset(new CopyPool(w_out));
 
-    const char *ims[3] = {(const char *)im1, (const char *)im2, (const char *)im3};
+    const char *ims[3] = {(const char *)r.im1, (const char *)r.im2, (const char *)r.im3};
     // upload units: a triplet (3 frames, one from each of im1..im3) or, in sequence mode, one frame; frame f of unit u of
     // a sub-batch starting at triplet b0 comes from src(b0 + u, f) and lands at plane (u * fpu + f) * 3 of the slot
     const int fpu = seq ? 1 : 3;
@@ -220,7 +292,7 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
                     for (size_t t = 0; t < nb; ++t)
                         for (int ch = 0; ch < 2; ++ch)
                             jobs.push_back({flow + ((b0 + t) * 2 + ch) * hw0, hs.h_flow32 + (t * 2 + ch) * hw0, hw0 * 4, JOB_F32_TO_F64,
-                                            ch == 0 ? sc_w : sc_h, nullptr});
+                                            ch == 0 ? g.sc_w : g.sc_h, nullptr});
                 } else {
                     if (q.stage_flow) jobs.push_back({o.flow32 + b0 * 2 * hw0, hs.h_flow32, nb * 2 * hw0 * 4});
                     if (q.stage_prob) jobs.push_back({o.occ_prob + b0 * 2 * hw0, hs.h_prob, nb * 2 * hw0 * 4});
@@ -320,17 +392,12 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
         const bool direct_u8 = seq && same && std::all_of(as_u8.begin(), as_u8.end(), [](int v) { return v != 0; });
         for (int t = 0; t < nu && !direct_u8; ++t)
             if (as_u8[t]) HIPCHK(launch_unpack_u8(hs.d_u8 + (size_t)t * fpu * 3 * hw0, (size_t)fpu * 3 * hw0, hs.d_up + (size_t)t * fpu * 3 * hw0, c->stream));
-        // ColorNormalize, then image.scale to the /64 size (:50-71); without a rescale the raw planes go to the
-        // network as they are and the first conv kernel normalizes on the fly
-        if (!same) HIPCHK(launch_image_scale(hs.d_up, 1, (long)nu * fpu * 3, H0, W0, hs.d_tmp, hs.d_in, fh, fw, c->stream));
-        CHK(forward_device(c, direct_u8 ? (const void *)hs.d_u8 : hs.d_in, direct_u8 ? B2F_IN_U8 : same ? B2F_IN_UNIT : B2F_IN_NORMALIZED, nb, fh,
-                           fw, hs.d_flow, hs.d_occ, hs.d_est3, c->stream, c->host_graph != 0, seq));
-        const float *occ_net = C3 == 3 ? hs.d_occ : hs.d_est3;
-        if (!f32)
-            HIPCHK(launch_postprocess(hs.d_flow, hs.d_est3, C3, nb, fh, fw, H0, W0, same ? nullptr : hs.d_flow32, hs.d_fo, hs.d_bo, c->stream));
-        else   // without a rescale the flow and occ_prob planes are the network's, downloaded as they are
-            HIPCHK(launch_outputs_f32(hs.d_flow, occ_net, hs.d_est3, C3, nb, fh, fw, H0, W0, sc_w, sc_h, same ? nullptr : hs.d_flow32,
-                                      q.prob ? hs.d_prob : nullptr, fwd_occ ? hs.d_fo : nullptr, bwd_occ ? hs.d_bo : nullptr, c->stream));
+        // without a rescale the flow and occ_prob planes are the network's, downloaded as they are
+        const float *occ_net = g.C3 == 3 ? hs.d_occ : hs.d_est3;
+        CHK(run_kernels(c, r, g, direct_u8 ? (const void *)hs.d_u8 : hs.d_up, direct_u8 ? B2F_IN_U8 : B2F_IN_UNIT, (long)nu * fpu * 3, nb,
+                        {hs.d_tmp, hs.d_in, hs.d_flow, hs.d_occ, hs.d_est3},
+                        {nullptr, same ? nullptr : hs.d_flow32, q.prob ? hs.d_prob : nullptr, fwd_occ ? hs.d_fo : nullptr, bwd_occ ? hs.d_bo : nullptr},
+                        c->host_graph != 0, c->stream));
         HIPCHK(hipEventRecord(hs.ev_comp, c->stream));
         // ---- download: the set's pinned output buffers must have been handed over (k - 2 drained)
         if (k >= 2) {
@@ -369,7 +436,7 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
     // nothing of this call may still be in flight when the caller gets its buffers back
     for (hipStream_t st : {c->s_in, c->stream, c->s_out}) {
         const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess && !rc) { rc = 1; msg = std::string("b2f_compute_flow: ") + hipGetErrorString(e); }
+        if (e != hipSuccess && !rc) { rc = 1; msg = w + ": " + hipGetErrorString(e); }
     }
     if (rc) {
         (void)hipGetLastError();
@@ -378,52 +445,43 @@ int compute_flow_pipeline(b2f_ctx *c, int n, const void *im1, const void *im2, c
     return 0;
 }
 
-// ---- device boundary: the kernels half of the pipeline's submit() on caller device buffers, no transfers ----
-// Per sub-batch, on `s`: gather the three frame sets into B x 9 x H0 x W0 (triplets) and unpack bytes, ColorNormalize +
-// image.scale to the /64 size, the forward pass, outputs_f32_kernel into the caller's buffers.  Sub-batches follow the host
-// pipeline's budget (host_subbatch_pixels, no ramp: there is no upload to overlap) and a sequence's overlap by two frames;
-// the buffers in between are the context's (c->dwork).  Every choice -- input kind of the forward pass, unpacking, the
-// kernel rule of the request's n -- is the host pipeline's, so the results are the f32 host entries' bit for bit.
-int compute_flow_device_impl(b2f_ctx *c, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0,
-                             int W0, const FlowOutputs &o, void *stream, const char *who)
+// ---- device buffers: the kernels half of the pipeline's submit() on caller buffers, no transfers --------------------------------
+// Per sub-batch, on the caller's stream: gather the three frame sets into B x 9 x H0 x W0 (triplets) and unpack bytes, then
+// run_kernels into the caller's buffers.  Sub-batches follow the host pipeline's budget (no ramp: there is no upload to overlap) and a
+// sequence's overlap by two frames; the buffers in between are the context's (c->dwork).  Every choice -- input kind of the forward
+// pass, unpacking, the kernel rule of the request's n -- is the host pipeline's, so the results are the f32 host entries' bit for bit.
+int b2f::compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream)
 {
-    const std::string w(who);
-    CHK(check_f32_args(who, count, in_kind, im1, im2, im3, seq, H0, W0, o.flow32));
-    if (!c) return fail(w + ": null context");
-    const uintptr_t al = (uintptr_t)im1 | (uintptr_t)im2 | (uintptr_t)im3 | (uintptr_t)o.flow32 | (uintptr_t)o.occ_prob | (uintptr_t)o.fwd_occ |
-                         (uintptr_t)o.bwd_occ;
+    CHK(check_context(c, r));
+    const std::string w(r.who);
+    const FlowOutputs &o = r.o;
+    const uintptr_t al = (uintptr_t)r.im1 | (uintptr_t)r.im2 | (uintptr_t)r.im3 | (uintptr_t)o.flow32 | (uintptr_t)o.occ_prob |
+                         (uintptr_t)o.fwd_occ | (uintptr_t)o.bwd_occ;
     if (al & 15) return fail(w + ": device buffers must be 16-byte aligned");
-    const int n = seq ? count - 2 : count;
-    const int fw = W0 - W0 % 64, fh = H0 - H0 % 64;   // back2future.lua:54-67
-    CHK(check_shape(1, fh, fw));
-    if (seq && !c->g.shipped())
-        return fail(w + ": sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
     HIPCHK(hipSetDevice(c->device));
-    const size_t hw0 = (size_t)H0 * W0, hw = (size_t)fh * fw;
-    const bool bytes_in = in_kind == B2F_IN_U8;
-    const size_t esz = bytes_in ? 1 : 4;
+    const int n = r.n;
+    const bool seq = r.seq, bytes_in = r.in_kind == B2F_IN_U8;
+    const Geometry g = geometry(c, r.H0, r.W0);
+    const size_t hw0 = g.hw0, esz = bytes_in ? 1 : 4;
     {
         const size_t in_bytes = (size_t)(seq ? n + 2 : n) * 3 * hw0 * esz, hw0n = (size_t)n * hw0;
-        const std::pair<const void *, size_t> bufs[7] = {{im1, in_bytes}, {seq ? nullptr : im2, in_bytes}, {seq ? nullptr : im3, in_bytes},
-                                                         {o.flow32, hw0n * 8}, {o.occ_prob, hw0n * 8}, {o.fwd_occ, hw0n}, {o.bwd_occ, hw0n}};
+        const std::pair<const void *, size_t> bufs[7] = {{r.im1, in_bytes}, {r.im2, in_bytes}, {r.im3, in_bytes}, {o.flow32, hw0n * 8},
+                                                         {o.occ_prob, hw0n * 8}, {o.fwd_occ, hw0n}, {o.bwd_occ, hw0n}};
         for (const auto &pb : bufs)
             if (pb.first && mem_kind(pb.first, pb.second) >= 0)
                 return fail(w + ": host memory passed to a device entry point (use b2f_compute_flow_batch_f32 / b2f_compute_flow_sequence_f32)");
     }
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const bool same = (fw == W0 && fh == H0);
-    const int C3 = c->past_flow ? 2 : 3;
-    const double sc_h = (double)H0 / (double)fh, sc_w = (double)W0 / (double)fw;   // :78-79
-    const int gu = seq ? 2 : 0;
-    const int SBU = (int)std::min<long long>(n + gu, std::max<long long>(1 + gu, c->host_subbatch_pixels / (long long)hw0));
-    const int SB = SBU - gu;
+    const ReqBatch req_guard(c, r);
+    int SB = 0;
+    const std::vector<std::pair<int, int>> subs = plan_subbatches(c, n, seq, hw0, false, &SB);
     // workspace: bytes of the gathered triplets, their floats, image.scale's two passes, the network's outputs
-    const bool unpack = bytes_in && !(seq && same);   // a /64 byte sequence is read as it is (the pipeline's direct_u8)
-    const size_t planes = (size_t)SBU * (seq ? 3 : 9);
+    const bool unpack = bytes_in && !(seq && g.same);   // a /64 byte sequence is read as it is (the pipeline's direct_u8)
+    const size_t planes = (size_t)(seq ? SB + 2 : SB) * (seq ? 3 : 9);
     const size_t n_u8 = (!seq && bytes_in) ? align256(planes * hw0) : 0, n_up = (!seq || unpack) ? align256(planes * hw0 * 4) : 0,
-                 n_tmp = same ? 0 : align256(planes * H0 * fw * 4), n_in = same ? 0 : align256(planes * hw * 4),
-                 n_flow = align256((size_t)SB * 2 * hw * 4), n_occ = (o.occ_prob && C3 == 3) ? n_flow : 0,
-                 n_est3 = align256((size_t)SB * C3 * hw * 4);
+                 n_tmp = g.same ? 0 : align256(planes * g.H0 * g.fw * 4), n_in = g.same ? 0 : align256(planes * g.hw * 4),
+                 n_flow = align256((size_t)SB * 2 * g.hw * 4), n_occ = (o.occ_prob && g.C3 == 3) ? n_flow : 0,
+                 n_est3 = align256((size_t)SB * g.C3 * g.hw * 4);
     const size_t need = n_u8 + n_up + n_tmp + n_in + n_flow + n_occ + n_est3;
     DevWork &dw = c->dwork;
     if (need > dw.bytes) {
@@ -439,152 +497,103 @@ int compute_flow_device_impl(b2f_ctx *c, int count, int in_kind, const void *im1
     char *d = dw.dev;
     unsigned char *d_u8 = (unsigned char *)d; d += n_u8;
     float *d_up = (float *)d; d += n_up;
-    float *d_tmp = (float *)d; d += n_tmp;
-    float *d_in = (float *)d; d += n_in;
-    float *d_flow = (float *)d; d += n_flow;
-    float *d_occ = n_occ ? (float *)d : nullptr; d += n_occ;
-    float *d_est3 = (float *)d;
-    struct ReqBatch { b2f_ctx *c; ReqBatch(b2f_ctx *cc, int nn) : c(cc) { c->req_batch = nn; } ~ReqBatch() { c->req_batch = 0; } } req_guard(c, n);
-    const char *ims[3] = {(const char *)im1, (const char *)im2, (const char *)im3};
-    for (int b0 = 0; b0 < n; b0 += SB) {
-        const int nb = std::min(SB, n - b0);
+    NetBuffers net;
+    net.tmp = (float *)d; d += n_tmp;
+    net.scaled = (float *)d; d += n_in;
+    net.flow = (float *)d; d += n_flow;
+    net.occ = n_occ ? (float *)d : nullptr; d += n_occ;
+    net.est3 = (float *)d;
+    const char *ims[3] = {(const char *)r.im1, (const char *)r.im2, (const char *)r.im3};
+    for (const auto &sb : subs) {
+        const int b0 = sb.first, nb = sb.second;
         const size_t np = (size_t)(seq ? nb + 2 : nb) * (seq ? 3 : 9);   // input planes of this sub-batch
-        const void *x = nullptr;   // what the forward pass reads
+        const void *x = d_up;   // what the forward pass reads
         int kind = B2F_IN_UNIT;
         if (!seq) {   // torch.cat({im1, im2, im3}, 1) (back2future.lua:48): triplet t's frames f = 0..2 at planes (t * 3 + f) * 3
-            char *g = bytes_in ? (char *)d_u8 : (char *)d_up;
+            char *gp = bytes_in ? (char *)d_u8 : (char *)d_up;
             for (int t = 0; t < nb; ++t)
                 for (int f = 0; f < 3; ++f)
-                    HIPCHK(hipMemcpyAsync(g + ((size_t)t * 3 + f) * 3 * hw0 * esz, ims[f] + (size_t)(b0 + t) * 3 * hw0 * esz, 3 * hw0 * esz,
+                    HIPCHK(hipMemcpyAsync(gp + ((size_t)t * 3 + f) * 3 * hw0 * esz, ims[f] + (size_t)(b0 + t) * 3 * hw0 * esz, 3 * hw0 * esz,
                                           hipMemcpyDeviceToDevice, s));
             if (bytes_in) HIPCHK(launch_unpack_u8(d_u8, np * hw0, d_up, s));
-            x = d_up;
         } else {
             const char *fr = ims[0] + (size_t)b0 * 3 * hw0 * esz;
             if (unpack) {
                 HIPCHK(launch_unpack_u8((const unsigned char *)fr, np * hw0, d_up, s));
-                x = d_up;
             } else {
                 x = fr;
-                kind = bytes_in ? B2F_IN_U8 : B2F_IN_UNIT;
+                kind = r.in_kind;
             }
         }
-        // ColorNormalize, then image.scale to the /64 size (:50-71); without a rescale the first conv kernel normalizes on the fly
-        if (!same) {
-            HIPCHK(launch_image_scale((const float *)x, 1, (long)np, H0, W0, d_tmp, d_in, fh, fw, s));
-            x = d_in;
-            kind = B2F_IN_NORMALIZED;
-        }
-        CHK(forward_device(c, x, kind, nb, fh, fw, d_flow, d_occ, d_est3, s, c->use_graph != 0, seq));
-        const size_t o2 = (size_t)b0 * 2 * hw0, o1 = (size_t)b0 * hw0;
-        HIPCHK(launch_outputs_f32(d_flow, C3 == 3 ? d_occ : d_est3, d_est3, C3, nb, fh, fw, H0, W0, sc_w, sc_h, o.flow32 + o2,
-                                  o.occ_prob ? o.occ_prob + o2 : nullptr, o.fwd_occ ? o.fwd_occ + o1 : nullptr,
-                                  o.bwd_occ ? o.bwd_occ + o1 : nullptr, s));
+        CHK(run_kernels(c, r, g, x, kind, (long)np, nb, net, o.from_triplet(b0, hw0), c->use_graph != 0, s));
     }
     return 0;
 }
 
-}  // namespace
-
-int b2f::check_f32_args(const char *who, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
-                        const float *flow)
-{
-    const std::string w(who);
-    if (in_kind == B2F_IN_NORMALIZED)
-        return fail(w + ": in_kind B2F_IN_NORMALIZED is refused: computeFlow normalizes its frames itself (B2F_IN_UNIT or B2F_IN_U8)");
-    if (in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail(w + ": in_kind must be B2F_IN_UNIT or B2F_IN_U8");
-    if (seq && count < 3) return fail(w + ": a sequence needs T >= 3 frames (one triplet)");
-    if (count <= 0 || H0 <= 0 || W0 <= 0) return fail(w + ": bad shape");
-    if (H0 < 64 || W0 < 64) return fail(w + ": image smaller than 64 pixels");
-    if (!im1 || (!seq && (!im2 || !im3)) || !flow) return fail(w + ": null argument");
-    return 0;
-}
-
-int b2f::compute_flow_f32(b2f_ctx *c, int count, int in_kind, const void *im1, const void *im2, const void *im3, bool seq, int H0, int W0,
-                          const FlowOutputs &o, int req, const char *who)
-{
-    CHK(check_f32_args(who, count, in_kind, im1, im2, im3, seq, H0, W0, o.flow32));
-    if (!c) return fail(std::string(who) + ": null context");
-    return compute_flow_pipeline(c, seq ? count - 2 : count, im1, im2, im3, in_kind == B2F_IN_U8, H0, W0, o, seq, req);
-}
-
-int b2f::compute_flow_sequence(b2f_ctx *c, int T, const void *frames, bool bytes_in, int H0, int W0, double *flow, unsigned char *fwd_occ,
-                               unsigned char *bwd_occ, int req)
-{
-    if (!c) return fail("b2f_compute_flow_sequence: null context");
-    if (T < 3) return fail("b2f_compute_flow_sequence: a sequence needs T >= 3 frames (one triplet)");
-    return compute_flow_pipeline(c, T - 2, frames, nullptr, nullptr, bytes_in, H0, W0, FlowOutputs{flow, nullptr, nullptr, fwd_occ, bwd_occ},
-                                 true, req);
-}
-
 extern "C" {
 
-int b2f_compute_flow_batch(b2f_ctx *c, int n, const float *im1, const float *im2, const float *im3, int H0,
-                           int W0, double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+int b2f_compute_flow(b2f_ctx *c, const float *im1, const float *im2, const float *im3, int H0, int W0, double *flow, unsigned char *fwd_occ,
+                     unsigned char *bwd_occ) try
 {
-    return compute_flow_pipeline(c, n, im1, im2, im3, false, H0, W0, FlowOutputs{flow, nullptr, nullptr, fwd_occ, bwd_occ});
+    return compute_flow_host(c, batch_request(__func__, 1, B2F_IN_UNIT, im1, im2, im3, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
+}
+B2F_CATCH("b2f_compute_flow")
+
+int b2f_compute_flow_batch(b2f_ctx *c, int n, const float *im1, const float *im2, const float *im3, int H0, int W0, double *flow,
+                           unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, batch_request(__func__, n, B2F_IN_UNIT, im1, im2, im3, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_compute_flow_batch")
 
-int b2f_compute_flow_batch_u8(b2f_ctx *c, int n, const unsigned char *im1, const unsigned char *im2,
-                              const unsigned char *im3, int H0, int W0, double *flow, unsigned char *fwd_occ,
-                              unsigned char *bwd_occ) try
+int b2f_compute_flow_batch_u8(b2f_ctx *c, int n, const unsigned char *im1, const unsigned char *im2, const unsigned char *im3, int H0,
+                              int W0, double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    return compute_flow_pipeline(c, n, im1, im2, im3, true, H0, W0, FlowOutputs{flow, nullptr, nullptr, fwd_occ, bwd_occ});
+    return compute_flow_host(c, batch_request(__func__, n, B2F_IN_U8, im1, im2, im3, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_compute_flow_batch_u8")
-
-int b2f_compute_flow(b2f_ctx *c, const float *im1, const float *im2, const float *im3, int H0, int W0,
-                     double *flow, unsigned char *fwd_occ, unsigned char *bwd_occ) try
-{
-    return b2f_compute_flow_batch(c, 1, im1, im2, im3, H0, W0, flow, fwd_occ, bwd_occ);
-}
-B2F_CATCH("b2f_compute_flow")
 
 int b2f_compute_flow_sequence(b2f_ctx *c, int T, const float *frames, int H0, int W0, double *flow, unsigned char *fwd_occ,
                               unsigned char *bwd_occ) try
 {
-    return compute_flow_sequence(c, T, frames, false, H0, W0, flow, fwd_occ, bwd_occ, 0);
+    return compute_flow_host(c, sequence_request(__func__, T, B2F_IN_UNIT, frames, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_compute_flow_sequence")
 
 int b2f_compute_flow_sequence_u8(b2f_ctx *c, int T, const unsigned char *frames, int H0, int W0, double *flow, unsigned char *fwd_occ,
                                  unsigned char *bwd_occ) try
 {
-    return compute_flow_sequence(c, T, frames, true, H0, W0, flow, fwd_occ, bwd_occ, 0);
+    return compute_flow_host(c, sequence_request(__func__, T, B2F_IN_U8, frames, H0, W0, {flow, nullptr, nullptr, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_compute_flow_sequence_u8")
 
 int b2f_compute_flow_batch_f32(b2f_ctx *c, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0, float *flow,
                                float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    return compute_flow_f32(c, n, in_kind, im1, im2, im3, false, H0, W0, FlowOutputs{nullptr, flow, occ_prob, fwd_occ, bwd_occ}, 0,
-                            "b2f_compute_flow_batch_f32");
+    return compute_flow_host(c, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0, {nullptr, flow, occ_prob, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_compute_flow_batch_f32")
 
 int b2f_compute_flow_sequence_f32(b2f_ctx *c, int T, int in_kind, const void *frames, int H0, int W0, float *flow, float *occ_prob,
                                   unsigned char *fwd_occ, unsigned char *bwd_occ) try
 {
-    return compute_flow_f32(c, T, in_kind, frames, nullptr, nullptr, true, H0, W0, FlowOutputs{nullptr, flow, occ_prob, fwd_occ, bwd_occ}, 0,
-                            "b2f_compute_flow_sequence_f32");
+    return compute_flow_host(c, sequence_request(__func__, T, in_kind, frames, H0, W0, {nullptr, flow, occ_prob, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_compute_flow_sequence_f32")
 
 int b2f_compute_flow_device(b2f_ctx *c, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, int H0, int W0,
                             float *dev_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream) try
 {
-    return compute_flow_device_impl(c, n, in_kind, dev_im1, dev_im2, dev_im3, false, H0, W0,
-                                    FlowOutputs{nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}, stream, "b2f_compute_flow_device");
+    return compute_flow_device(c, batch_request(__func__, n, in_kind, dev_im1, dev_im2, dev_im3, H0, W0,
+                                                {nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}), stream);
 }
 B2F_CATCH("b2f_compute_flow_device")
 
 int b2f_compute_flow_sequence_device(b2f_ctx *c, int T, int in_kind, const void *dev_frames, int H0, int W0, float *dev_flow,
                                      float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream) try
 {
-    return compute_flow_device_impl(c, T, in_kind, dev_frames, nullptr, nullptr, true, H0, W0,
-                                    FlowOutputs{nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}, stream,
-                                    "b2f_compute_flow_sequence_device");
+    return compute_flow_device(c, sequence_request(__func__, T, in_kind, dev_frames, H0, W0,
+                                                   {nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}), stream);
 }
 B2F_CATCH("b2f_compute_flow_sequence_device")
 

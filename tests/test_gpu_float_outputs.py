@@ -1,7 +1,7 @@
 """GPU: the float32 computeFlow outputs (b2f_compute_flow_batch_f32, b2f_compute_flow_sequence_f32, the b2f_multi forms, the device
 entries b2f_compute_flow_device / b2f_compute_flow_sequence_device).  Every output is defined from the float64 entries' or the
 network's: flow_f32 == np.float32(flow_f64) bit for bit, the masks are identical, occ_prob is skip_occs[3] nearest-rescaled with
-postprocess_kernel's index rule."""
+the index rule of image.scale 'simple'."""
 import ctypes as C
 import os
 import subprocess
@@ -59,7 +59,7 @@ def _eq(a, b, what):
 
 
 def _nearest(plane_stack, H0, W0):
-    """image.scale 'simple' with postprocess_kernel's index rule: src = (long)((float)dst * ((float)src_len / (float)dst_len)), clamped."""
+    """The index rule of image.scale 'simple': src = (long)((float)dst * ((float)src_len / (float)dst_len)), clamped."""
     fh, fw = plane_stack.shape[-2:]
     jj = np.minimum((np.arange(H0, dtype=np.float32) * (np.float32(fh) / np.float32(H0))).astype(np.int64), fh - 1)
     ii = np.minimum((np.arange(W0, dtype=np.float32) * (np.float32(fw) / np.float32(W0))).astype(np.int64), fw - 1)

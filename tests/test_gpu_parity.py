@@ -921,7 +921,8 @@ def test_broadcast_weights_device_path():
 def test_multi_gpu_two_replicas_on_one_gpu(monkeypatch):
     """The N > 1 code of the one-process multi-GPU entry points on the one-GPU test box: B2F_MULTI_ALLOW_DUPLICATE=1 (honoured only
     with the peer transport) lists GPU 0 twice -> two contexts, two worker threads, two uneven shards (5 = 3 + 2), replica 1 created
-    from OTHER weights and brought in line by the peer broadcast; results bit-identical to one context; a failure on replica 1 is
+    from OTHER weights and brought in line by the peer broadcast; results bit-identical to one context, also where a shard holds a
+    single triplet of a larger request (n = 3, 2); a failure on replica 1 is
     handed over from its worker thread to the caller with the GPU named; the pair keeps working afterwards (util.lua:27-48)."""
     import ctypes as C
     from back2future_amd import _lib
@@ -946,6 +947,15 @@ def test_multi_gpu_two_replicas_on_one_gpu(monkeypatch):
         # one triplet: replica 1's shard is empty, only one worker thread runs
         for a, b in zip(mm.computeFlowBatch(*[x[:1] for x in ims]), [e[:1] for e in exp]):
             np.testing.assert_array_equal(a, b)
+        # shards of one triplet (n = 3 -> 2 + 1, n = 2 -> 1 + 1) keep the kernel rule of the caller's n: at 256 x 512 a lone
+        # triplet (per-launch rule) gets other bits than the same triplet in a batch (map-size rule)
+        big = [r.random((3, 3, 256, 512), dtype=np.float32) for _ in range(3)]
+        alone = ref.computeFlowBatch(*[x[2:] for x in big])
+        assert not np.array_equal(alone[0][0], ref.computeFlowBatch(*big)[0][2])
+        for ins in (big, [np.round(a * 255).astype(np.uint8) for a in big]):
+            for k in (3, 2):
+                for a, b in zip(mm.computeFlowBatch(*[x[:k] for x in ins]), ref.computeFlowBatch(*[x[:k] for x in ins])):
+                    np.testing.assert_array_equal(a, b, err_msg="n = %d, %s" % (k, ins[0].dtype))
         # replica 1 fails once: the message crosses from its worker thread to the caller
         L = _lib.lib()
         _lib.check(L.b2f_set_option(C.c_void_p(L.b2f_multi_context(mm._h, 1)), b"debug_fail_next", 1))
