@@ -99,7 +99,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 }
 
 // warp_input_planar_kernel (b2f_glue.hip) for the Hard models' est[3] = iws[1][3] (pwc.lua:422-446): the first frame of
-// triplet b, frame b of the sequence, normalized on the fly and warped by k * planar flow -> planar B x 3 x H x W
+// triplet b, frame b of the sequence, normalized on the fly and warped by k * planar flow -> planar B x 3 x H x W.
+// The dx / dy fold (here and in warp_input_planar_kernel): a tap past the last column / row is read from the top-left pixel again
+// instead of being replaced by 0, so every read stays inside frame b (src[dy + dx] on the last row and column is src[0]).  xl = W - 1
+// is reached only through the clamp, with c = W - 1 exactly: wx = 1 and the folded tap's weight 1 - wx is exactly 0, so it adds
+// 0 * pixel = 0 like the sampler's zero tap for every FINITE pixel; an Inf / NaN pixel in the last column or row would turn the
+// output NaN where the sampler gives Inf (tests/test_gpu_displaced.py runs both kernels through the clamp).
 template <typename T>
 __global__ void warp_input_seq_kernel(const T *in, int normalize, const float *flow, float k, int B, int H, int W, float *out)
 {

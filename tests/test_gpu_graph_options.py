@@ -5,6 +5,7 @@ import pytest
 
 from back2future_amd import back2future, weights as W
 from oracle import oracle as O
+from tests.displaced import set_flow_bias
 from tests.test_graph_options_cpu import CASES, _oracle_opts
 
 pytestmark = pytest.mark.gpu
@@ -22,9 +23,7 @@ def test_graph_options_full_table_vs_oracle(name, past):
         np.testing.assert_array_equal(m.get_weights(), p)         # same generator, same canonical order of this graph
         # a bias on the last layer of every flow decoder: every level predicts a flow of several pixels (in units of its own map), so
         # the feature / image warps sample whole pixels away and through the border clamp -- random weights alone move by < 1 px
-        for lname, shape, off in W.layout(past, o)[0]:
-            if lname.endswith(".conv6.b") and (".flow." in lname or ".past." in lname):
-                p[off:off + 2] = np.asarray((0.35, -0.25), np.float32) * (1.0 if ".flow." in lname else -1.0)
+        set_flow_bias(p, past, (0.35, -0.25), o)
         m.set_weights(p)
         rng = np.random.default_rng(len(name) + 7 * past)
         mlt = 1 << (o["levels"] - 1)

@@ -6,6 +6,7 @@ import pytest
 
 from back2future_amd import back2future, ops, weights as W
 from oracle import oracle as O
+from tests.displaced import set_flow_bias
 
 pytestmark = pytest.mark.gpu
 
@@ -344,11 +345,7 @@ def test_compute_flow_large_displacements(which, H, Wd, bias):
     other end-to-end tests, on every cost-volume instantiation."""
     past = which == "soft"
     flat = W.random_init(7, past, 1.0)
-    lay, n = W.layout(past)
-    for name, shape, off in lay:
-        if name.endswith(".conv6.b") and (".flow." in name or ".past." in name):
-            sign = 1.0 if ".flow." in name else -1.0
-            flat[off:off + 2] = np.asarray(bias, np.float32) * sign
+    set_flow_bias(flat, past, bias)
     r = _rng(H * 3 + Wd)
     im1, im2, im3 = _triplet(r, H, Wd)
     eflow, efo, ebo, fnet, onet = O.compute_flow(im1, im2, im3, flat, past, want_net=True)

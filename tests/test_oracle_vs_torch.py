@@ -216,3 +216,21 @@ def test_pwc_forward_end_to_end(past_flow):
     for i, (a, b) in enumerate(zip(outs, ref)):
         assert a.shape == b.shape
         assert np.abs(a - b).max() < 1e-3, (i, np.abs(a - b).max())
+
+
+@pytest.mark.parametrize("past_flow", [False, True])
+def test_pwc_forward_end_to_end_displaced(past_flow):
+    """The same witness on tests/displaced.py's weights (every level's warps move by about 3 pixels and run through the border clamp,
+    the occlusion logits are spread to quartiles of +/- 1): the oracle must be shown right here before a GPU is measured against it."""
+    from tests import displaced as D
+    H, Wd = 128, 192
+    rng = np.random.default_rng(7)
+    x = rng.standard_normal((1, 9, H, Wd)).astype(np.float32)
+    flat = D.displaced_weights(5, past_flow, x, disp_px=3.0, occ_spread=1.0)
+    outs = O.pwc_forward(x, flat, past_flow)
+    D.assert_conditions(outs, past_flow)
+    ref, inter = R.pwc_forward(x, W.views(flat, past_flow), past_flow)
+    assert len(outs) == len(ref) == (25 if past_flow else 20)
+    for i, (a, b) in enumerate(zip(outs, ref)):
+        assert a.shape == b.shape
+        assert np.abs(a - b).max() < 1e-3, (i, np.abs(a - b).max())
