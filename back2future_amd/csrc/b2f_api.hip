@@ -3,6 +3,7 @@
 // capture, per-kernel HIP-event profiling, and op-level entry points for parity tests.
 #include "b2f_ctx.h"
 
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -110,15 +111,112 @@ bool use_wino()
     return on;
 }
 
-// Kernel choice for a stride-1 layer: F(4x4) from B2F_WINO4_MIN_COUT outputs (default 32; 0 disables it),
-// F(2x2) down to B2F_WINO_MIN_COUT (default 16), direct kernel below; 2 outputs: VALU kernel.
-int wino_mode(int cout)
+// ---- the conv kernels ------------------------------------------------------------------
+// One row per ConvKernel, in the enum's order: everything the packing, the launch and the profile need to know about a kernel.
+// Adding a kernel = an enum value, a row here, its condition in `packs` and its rule in choose_kernel.
+struct KernelRow {
+    const char *tag[2];   // profile_layers rows conv<tag>_<cin>to<cout>_<H>x<W>, by stride - 1 (bench.py parses them)
+    const char *cls[2];   // profile class name, by stride - 1; %d = N tiles per block of the layer's fp32 packing
+    void (*tiles)(int co, int *nt, int *nblk);
+    size_t (*w_floats)(int chunks, int co, int nt, int nblk);
+    bool bias;            // the packing ends with nblk * nt * 32 bias floats
+    void (*pack)(const float *w, const float *b, int co, int ci, const int *cin_map, int chunks, int nt, int nblk, float *wpk, float *bpk);
+    hipError_t (*launch)(const ConvLaunch &, hipStream_t);   // nullptr: a second operand of another kernel's launcher
+};
+#define TL [](int co, int *nt, int *nblk)
+#define WF [](int chunks, int co, int nt, int nblk) -> size_t
+#define PK [](const float *w, const float *b, int co, int ci, const int *m, int chunks, int nt, int nblk, float *wpk, float *bpk)
+const KernelRow kKernels[K_COUNT] = {
+    {{"D1", "D2"}, {"conv3x3_s1_nt%d", "conv3x3_s2_nt%d"}, conv_choose_tiles, WF { return conv_wpk_floats(chunks, nt, nblk); }, true,
+     PK { conv_pack_weights(w, b, co, ci, m, chunks, nt, nblk, wpk, bpk); }, launch_conv3x3},
+    {{"N2", "N2"}, {"conv3x3_narrow2", "conv3x3_narrow2"}, TL { *nt = 1; *nblk = 1; }, WF { return narrow2_wpk_floats(chunks); }, true,
+     PK { narrow2_pack_weights(w, b, ci, m, chunks, wpk, bpk); }, launch_conv_narrow2},
+    {{"W2", "W2"}, {"conv3x3_wino_nt%d", "conv3x3_wino_nt%d"}, wino_choose_tiles, WF { return wino_wpk_floats(chunks, nt, nblk); }, true,
+     PK { wino_pack_weights(w, b, co, ci, m, chunks, nt, nblk, wpk, bpk); }, launch_conv3x3_wino},
+    {{"C16", "C16"}, {"conv3x3_c16_%d", "conv3x3_c16_%d"}, TL { *nt = 1; *nblk = 1; }, WF { return c16_wpk_floats(); }, true,
+     PK { c16_pack_weights(w, b, ci, m, wpk, bpk); }, launch_conv3x3_c16},
+    {{"S16", "S16"}, {"conv3x3_s2x16_%d", "conv3x3_s2x16_%d"}, TL { *nt = 1; *nblk = 1; }, WF { return c16s2_wpk_floats(); }, true,
+     PK { c16s2_pack_weights(w, b, ci, m, wpk, bpk); }, launch_conv3x3_c16s2},
+    {{"W4", "W4"}, {"conv3x3_wino4_nt%d", "conv3x3_wino4_nt%d"}, TL { *nt = 2; *nblk = wino4_nblk(co); }, WF { return wino4_wpk_floats(chunks, nblk); }, true,
+     PK { wino4_pack_weights(w, b, co, ci, m, chunks, nblk, wpk, bpk); }, launch_conv3x3_wino4},
+    {{"E1", "E2"}, {"conv3x3_s1_bf16_%d", "conv3x3_s2_bf16_%d"}, TL { *nt = 2; *nblk = convb_nblk(co); }, WF { return convb_wpk_floats(chunks, co); }, true,
+     PK { convb_pack_weights(w, b, co, ci, m, chunks, wpk, bpk); }, launch_conv3x3_bf6},
+    {{"L2", "L2"}, {"conv3x3_s2b_%d", "conv3x3_s2b_%d"}, TL { *nt = 1; *nblk = s2b_ntiles(co); }, WF { return s2b_wpk_floats(chunks, co); }, true,
+     PK { s2b_pack_weights(w, b, co, ci, m, chunks, wpk, bpk); }, launch_conv3x3_s2b},
+    // the n-blocks of more than 32 real outputs; a last block of <= 32 on the F(4x4) single-N-tile kernel, both in one profile row
+    {{"V1", "V1"}, {"conv3x3_w1b_%d", "conv3x3_w1b_%d"}, TL { *nt = 2; *nblk = w1b_nblk(co); }, WF { return w1b_wpk_floats(chunks, co); }, true,
+     PK { w1b_pack_weights(w, b, co, ci, m, chunks, wpk, bpk); },
+     [](const ConvLaunch &L, hipStream_t s) {
+         const hipError_t e = launch_conv3x3_w1b(L, s);
+         return e == hipSuccess && L.w1b_nblk < w1b_nblk(L.cout) ? launch_conv3x3_wino4_rem(L, s) : e;
+     }},
+    {{"W6", "W6"}, {"conv3x3_wino6_nt%d", "conv3x3_wino6_nt%d"}, TL { *nt = 2; *nblk = wino6_nblk(co); }, WF { return wino6_wpk_floats(chunks, co); }, true,
+     PK { wino6_pack_weights(w, b, co, ci, m, chunks, wpk, bpk); }, launch_conv3x3_wino6},
+#if B2F_EXPERIMENTS
+    {{nullptr, nullptr}, {nullptr, nullptr}, TL { *nt = 2; *nblk = wino4_nblk(co); }, WF { return wino4s_wpk_floats(chunks, nblk); }, false,
+     PK { wino4s_pack_weights(w, co, ci, m, chunks, nblk, wpk); }, nullptr},
+    {{nullptr, nullptr}, {nullptr, nullptr}, TL { *nt = 2; *nblk = wino4_nblk(co); }, WF { return wino2s_wpk_floats(chunks, nblk); }, false,
+     PK { wino2s_pack_weights(w, co, ci, m, chunks, nblk, wpk); }, nullptr},
+#endif
+};
+#undef TL
+#undef WF
+#undef PK
+
+// The kernel of a layer by its shape alone: stride-1 layers run F(4x4) from B2F_WINO4_MIN_COUT outputs (default 32; 0 disables it; it
+// stores 4 channels at a time), F(2x2) down to B2F_WINO_MIN_COUT (default 16), the direct kernel below; 2 outputs: the VALU kernel,
+// which takes one K segment; the two 16-channel layers of the head have kernels of their own.  Stride 2: the direct kernel.
+ConvKernel base_kernel(int ci, int co, bool stride1, bool two_segments)
 {
     static const int min4 = getenv("B2F_WINO4_MIN_COUT") ? atoi(getenv("B2F_WINO4_MIN_COUT")) : 32;
-    if (use_wino() && cout == 2) return 1;           // last decoder layer: VALU kernel
     static const int min2 = getenv("B2F_WINO_MIN_COUT") ? atoi(getenv("B2F_WINO_MIN_COUT")) : 16;
-    if (!use_wino() || cout < min2) return 0;
-    return (min4 > 0 && cout >= min4 && cout % 4 == 0) ? 4 : 2;   // F(4x4) stores 4 channels at a time
+    if (!use_wino()) return K_DIRECT;
+    if (ci == 16 && co == (stride1 ? 16 : 32)) return stride1 ? K_C16 : K_C16S2;
+    if (!stride1) return K_DIRECT;
+    if (co == 2) return two_segments ? K_DIRECT : K_NARROW2;
+    if (co < min2) return K_DIRECT;
+    return (min4 > 0 && co >= min4 && co % 4 == 0) ? K_WINO4 : K_WINO2;
+}
+
+// Does a layer carry kernel k's packing?  Its base kernel's always; the optional ones only while an option reads them (the setter
+// of such an option repacks when that changes, OptRow::repack).
+bool packs(const PackedConv &p, ConvKernel k, bool stride1, const KernelOpts &o)
+{
+    const bool w4 = p.base == K_WINO4;
+    switch (k) {
+    case K_BF6: return (p.base == K_DIRECT || (w4 && o.bf16_conv >= 2)) && (p.cout & 3) == 0;
+    case K_S2B: return p.base == K_DIRECT && !stride1 && (p.cout & 31) == 0 && p.cout <= 256;
+    case K_WINO2: return w4 || p.base == K_WINO2;   // F(4x4) layers: for small maps
+    case K_W1B: return w4 && o.wino1d;
+    case K_WINO6: return w4 && o.wino6;
+#if B2F_EXPERIMENTS
+    case K_WINO4S: return w4 && (o.wino4_split || o.wino4_hybrid);   // 1.5x the F(4x4) packing
+    case K_WINO2S: return w4 && o.wino2_split;
+#endif
+    default: return k == p.base;
+    }
+}
+
+// Lays the packings of a layer (base, cout and chunks set) out from float offset *total on.  Every packing starts 16-byte aligned
+// (conv_narrow2 reads its weights as float4, the split ones are read with dwordx4 loads).
+void place_packings(PackedConv &p, bool stride1, const KernelOpts &o, size_t *total)
+{
+    for (int k = 0; k < K_COUNT; ++k) {
+        if (!packs(p, (ConvKernel)k, stride1, o)) continue;
+        PackedConv::Packing &q = p.pk[k];
+        kKernels[k].tiles(p.cout, &q.nt, &q.nblk);
+        q.w_off = *total = (*total + 3) & ~(size_t)3;
+        q.b_off = *total += kKernels[k].w_floats(p.nchunks(), p.cout, q.nt, q.nblk);
+        if (kKernels[k].bias) *total += (size_t)q.nblk * q.nt * 32;
+    }
+}
+
+// Torch weights Co x Ci x 3 x 3 + bias -> every packing place_packings gave the layer
+void fill_packings(const PackedConv &p, const float *w, const float *b, int ci, const int *cin_map, float *host)
+{
+    for (int k = 0; k < K_COUNT; ++k)
+        if (p.has((ConvKernel)k))
+            kKernels[k].pack(w, b, p.cout, ci, cin_map, p.nchunks(), p.pk[k].nt, p.pk[k].nblk, host + p.pk[k].w_off, host + p.pk[k].b_off);
 }
 
 int pack_all(b2f_ctx *c, const float *flat)
@@ -131,17 +229,9 @@ int pack_all(b2f_ctx *c, const float *flat)
         const ConvDesc &d = c->lay[i];
         PackedConv &p = c->packed[i];
         p.cout = d.co;
-        // stride-1 layers with >= 16 outputs run on the Winograd kernel (the first conv of a convUnit
-        // has stride 2, the last decoder layer has 2 outputs: direct kernel)
-        const bool stride1 = !(d.kind == KIND_FEAT && d.idx == 1 && d.level >= 2);   // (the level-1 unit of pwc_skip = 0 has stride 1, pwc.lua:172)
-        p.wino = stride1 ? wino_mode(d.co) : 0;
-        if (p.wino == 1 && d.kind != KIND_FEAT && d.idx == 1) p.wino = 0;   // two K segments: not for the narrow kernel
-        if (stride1 && use_wino() && d.ci == 16 && d.co == 16) p.wino = 3;  // level-2 convUnit: dedicated kernel
-        if (!stride1 && use_wino() && d.ci == 16 && d.co == 32) p.wino = 5;  // first conv of the level-3 convUnit: dedicated kernel
-        if (p.wino == 4) { p.nt = 2; p.nblk = wino4_nblk(d.co); }
-        else if (p.wino == 1 || p.wino == 3 || p.wino == 5) { p.nt = 1; p.nblk = 1; }
-        else if (p.wino == 2) wino_choose_tiles(d.co, &p.nt, &p.nblk);
-        else conv_choose_tiles(d.co, &p.nt, &p.nblk);
+        // the first conv of a convUnit has stride 2 (the level-1 unit of pwc_skip = 0 has stride 1, pwc.lua:172); the first decoder layer has two K segments
+        const bool stride1 = !(d.kind == KIND_FEAT && d.idx == 1 && d.level >= 2);
+        p.base = base_kernel(d.ci, d.co, stride1, d.kind != KIND_FEAT && d.idx == 1);
         std::vector<int> &m = maps[i];
         if (d.kind != KIND_FEAT && d.idx == 1 && c->g.shipped()) {
             const int Cl = kFeat[d.level];
@@ -171,61 +261,7 @@ int pack_all(b2f_ctx *c, const float *flat)
             p.chunks[0] = (d.ci + kCK - 1) / kCK;
             for (int k = 0; k < p.chunks[0] * kCK; ++k) m.push_back(k < d.ci ? k : -1);
         }
-        const int chunks = p.chunks[0] + (p.nseg > 1 ? p.chunks[1] : 0);
-        total = (total + 3) & ~(size_t)3;   // every packing starts 16-byte aligned (conv_narrow2 reads its weights as float4)
-        p.w_off = total;
-        total += p.wino == 4 ? wino4_wpk_floats(chunks, p.nblk) : p.wino == 1 ? narrow2_wpk_floats(chunks)
-                 : p.wino == 3 ? c16_wpk_floats() : p.wino == 5 ? c16s2_wpk_floats() : p.wino == 2 ? wino_wpk_floats(chunks, p.nt, p.nblk)
-                 : conv_wpk_floats(chunks, p.nt, p.nblk);
-        p.b_off = total;
-        total += (size_t)p.nblk * p.nt * 32;
-        if ((p.wino == 0 || (p.wino == 4 && c->bf16_conv >= 2)) && (d.co & 3) == 0) {   // direct layers: also packed for the kernel on the bf16 pipe (F(4x4)-class ones only while bf16_conv >= 2 reads that packing)
-            total = (total + 3) & ~(size_t)3;
-            p.w_off5 = total;
-            total += convb_wpk_floats(chunks, d.co);
-            p.b_off5 = total;
-            total += (size_t)convb_nblk(d.co) * 64;
-        }
-        if (p.wino == 0 && !stride1 && (d.co & 31) == 0 && d.co <= 256) {   // stride-2 layers: the loader / consumer kernel's packing
-            total = (total + 3) & ~(size_t)3;
-            p.w_off7 = total;
-            total += s2b_wpk_floats(chunks, d.co);
-            p.b_off7 = total;
-            total += (size_t)s2b_ntiles(d.co) * 32;
-        }
-        if (p.wino == 4 && c->wino6) {   // only while the option reads it (as the other optional packings)
-            total = (total + 3) & ~(size_t)3;
-            p.w_off8 = total;
-            total += wino6_wpk_floats(chunks, d.co);
-            p.b_off8 = total;
-            total += (size_t)wino6_nblk(d.co) * 64;
-        }
-        if (p.wino == 4 && c->wino1d) {   // only while the option reads it (as the other optional packings)
-            total = (total + 3) & ~(size_t)3;
-            p.w_off6 = total;
-            total += w1b_wpk_floats(chunks, d.co);
-            p.b_off6 = total;
-            total += (size_t)w1b_nblk(d.co) * 64;
-        }
-        if (p.wino == 4) {
-            wino_choose_tiles(d.co, &p.nt2, &p.nblk2);
-            p.w_off2 = total;
-            total += wino_wpk_floats(chunks, p.nt2, p.nblk2);
-            p.b_off2 = total;
-            total += (size_t)p.nblk2 * p.nt2 * 32;
-#if B2F_EXPERIMENTS
-            if (c->wino2_split) {
-                total = (total + 3) & ~(size_t)3;
-                p.w_off4 = total;
-                total += wino2s_wpk_floats(chunks, p.nblk);
-            }
-            if (c->wino4_split || c->wino4_hybrid) { // only while an option that reads it is on: 1.5x the F(4x4) packing
-                total = (total + 3) & ~(size_t)3;    // 16-byte aligned: the split weights are read with dwordx4 loads
-                p.w_off3 = total;
-                total += wino4s_wpk_floats(chunks, p.nblk);
-            }
-#endif
-        }
+        place_packings(p, stride1, *c, &total);
     }
     c->first_w_off = total; total += 27 * 16;
     c->first_b_off = total; total += 16;
@@ -238,39 +274,8 @@ int pack_all(b2f_ctx *c, const float *flat)
             host[c->first_b_off + o] = flat[d.b_off + o];
         }
     }
-    for (size_t i = 0; i < n; ++i) {
-        const ConvDesc &d = c->lay[i];
-        const PackedConv &p = c->packed[i];
-        const int chunks = p.chunks[0] + (p.nseg > 1 ? p.chunks[1] : 0);
-        if (p.wino == 4) {
-            wino4_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, p.nblk,
-                               host.data() + p.w_off, host.data() + p.b_off);
-            wino_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, p.nt2, p.nblk2,
-                              host.data() + p.w_off2, host.data() + p.b_off2);
-            if (p.w_off5) convb_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, host.data() + p.w_off5, host.data() + p.b_off5);
-#if B2F_EXPERIMENTS
-            if (p.w_off4) wino2s_pack_weights(flat + d.w_off, d.co, d.ci, maps[i].data(), chunks, p.nblk, host.data() + p.w_off4);
-            if (p.w_off3) wino4s_pack_weights(flat + d.w_off, d.co, d.ci, maps[i].data(), chunks, p.nblk, host.data() + p.w_off3);
-#endif
-            if (p.w_off6) w1b_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, host.data() + p.w_off6, host.data() + p.b_off6);
-            if (p.w_off8) wino6_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, host.data() + p.w_off8, host.data() + p.b_off8);
-        } else if (p.wino == 1)
-            narrow2_pack_weights(flat + d.w_off, flat + d.b_off, d.ci, maps[i].data(), chunks, host.data() + p.w_off,
-                                 host.data() + p.b_off);
-        else if (p.wino == 3)
-            c16_pack_weights(flat + d.w_off, flat + d.b_off, d.ci, maps[i].data(), host.data() + p.w_off, host.data() + p.b_off);
-        else if (p.wino == 5)
-            c16s2_pack_weights(flat + d.w_off, flat + d.b_off, d.ci, maps[i].data(), host.data() + p.w_off, host.data() + p.b_off);
-        else if (p.wino == 2)
-            wino_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, p.nt, p.nblk,
-                              host.data() + p.w_off, host.data() + p.b_off);
-        else {
-            conv_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, p.nt, p.nblk,
-                              host.data() + p.w_off, host.data() + p.b_off);
-            if (p.w_off5) convb_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, host.data() + p.w_off5, host.data() + p.b_off5);
-            if (p.w_off7) s2b_pack_weights(flat + d.w_off, flat + d.b_off, d.co, d.ci, maps[i].data(), chunks, host.data() + p.w_off7, host.data() + p.b_off7);
-        }
-    }
+    for (size_t i = 0; i < n; ++i)
+        fill_packings(c->packed[i], flat + c->lay[i].w_off, flat + c->lay[i].b_off, c->lay[i].ci, maps[i].data(), host.data());
     if (c->wpk_floats != total) {
         if (c->wpk_dev) HIPCHK(hipFree(c->wpk_dev));
         c->wpk_dev = nullptr;
@@ -371,124 +376,134 @@ int ensure_workspace_floats(b2f_ctx *c, size_t total)
 int ensure_workspace(b2f_ctx *c, const Plan &p) { return ensure_workspace_floats(c, p.total); }
 
 // ---- one conv launch from the packed table -----------------------------------------------
+struct KernelChoice {
+    ConvKernel kernel;   // the kernel that runs
+    bool f2x2;           // an F(4x4) layer on its F(2x2) packing (kernel = K_WINO2)
+    int nsplit;          // ConvLaunch::nsplit
+    int w1b_blocks;      // K_W1B: the n-blocks of 64 outputs it computes (ConvLaunch::w1b_nblk)
+};
+
+// THE kernel choice: which kernel runs layer p on launch L (sizes, strides, chunk counts and the pointers of every packing the layer has
+// filled in: the *_supported predicates read them) under the options o, in a request of cur_batch triplets.  No HIP call.
+KernelChoice choose_kernel(const PackedConv &p, const KernelOpts &o, int cur_batch, const ConvLaunch &L)
+{
+    const int H = L.H, W = L.W;
+    // F(4x4) layers fall back to their F(2x2) packing when the launch would leave most of the chip idle.  An F(4x4) block (16 x 32
+    // pixels, one per CU) takes about three times as long as an F(2x2) block (8 x 16 pixels) that has its CU to itself and 1.5 times
+    // as long as one that shares it with a second block, so compare the number of block rounds each kernel needs on 256 CUs.
+    // That rule makes a triplet's result depend (at 1e-6 level) on the batch it is computed in, so it is opt-in (option
+    // adaptive_kernels); the default rule looks at the map size only: F(2x2) below wino4_min_pixels.
+    bool alt = false, split = false;
+    if (p.base == K_WINO4) {
+        const PackedConv::Packing &p2 = p.pk[K_WINO2];
+        // adaptive_kernels: -1 (default) = per launch for single-triplet calls (the reference's own calling pattern, back2future.lua:73:
+        // latency matters and most launches leave the chip half empty), by map size for batches; 0 never, 1 always per launch
+        const bool per_launch = o.adaptive_kernels > 0 || (o.adaptive_kernels < 0 && cur_batch == 1);
+        if (!per_launch) {
+            alt = H * W < o.wino4_min_pixels;
+            split = alt && p2.nt == 2 && H * W <= o.wino_split_pixels;
+        } else {
+            // cost in twentieths of a lone F(2x2) block: F(4x4) block 60; F(2x2) block 20 alone, 40 per pair sharing a CU;
+            // F(2x2) block that computes one of the two N tiles only 13 / 26
+            const long tiles2 = (long)L.nimg * ((H + 7) / 8) * ((W + 15) / 16);
+            const long b4 = (long)L.nimg * ((H + 15) / 16) * ((W + 31) / 32) * p.pk[K_WINO4].nblk;
+            const long b2 = tiles2 * p2.nblk, b2s = tiles2 * ((p.cout + 31) / 32);
+            const long t4 = 60 * ((b4 + 255) / 256);
+            const long t2 = b2 <= 256 ? 20 : 40 * ((b2 + 511) / 512);
+            const long t2s = p2.nt != 2 ? t2 : b2s <= 256 ? 13 : 26 * ((b2s + 511) / 512);
+            alt = std::min(t2, t2s) < t4;
+            split = alt && t2s < t2;
+        }
+    }
+    const ConvKernel mode = alt ? K_WINO2 : p.base;
+    KernelChoice ch = {mode, alt, split ? 1 : 0, 0};
+    const bool big4 = mode == K_WINO4 && L.stride == 1;   // F(4x4)-class launch: large maps may leave for another kernel
+    // the bf16 pipe: direct layers with bf16_conv; bf16_conv >= 2: also F(4x4)-class layers of large maps (2: the 32-output ones, 3: all)
+    if (p.has(K_BF6) && ((mode == K_DIRECT && o.bf16_conv) || (big4 && H * W >= o.bf16_conv_min_pixels && ((o.bf16_conv == 2 && p.cout <= 32) || o.bf16_conv >= 3))) &&
+        convb_supported(L))
+        ch.kernel = K_BF6;
+    // stride-2 layers on the bf16 pipe: the loader / consumer kernel.  (Layers of fewer than 64 input channels keep conv3x3_bf6: with four
+    // short chunks per tile the loader / consumer block is bound by its weight traffic -- 2 KB per six MFMAs -- 32 -> 64 measured 0.45
+    // against 0.43 ms; s2_loader = 2 sends them there too)
+    if (mode == K_DIRECT && L.stride == 2 && o.bf16_conv && o.s2_loader && p.has(K_S2B) && (o.s2_loader >= 2 || p.nchunks() >= 8) && s2b_supported(L)) {
+        ch.kernel = K_S2B;
+        ch.nsplit = o.s2_tile_groups ? 0 : -1;
+    }
+    if (big4 && ch.kernel == K_WINO4) {
+        // wino1d = 1: the n-blocks with more than 32 real outputs on the 1-D Winograd bf16 kernel, a last block of <= 32 outputs on the
+        // F(4x4) single-N-tile kernel (half the bf16 kernel's MFMAs would multiply zero padding); 2: every n-block
+        const int blocks = o.wino1d >= 2 ? w1b_nblk(p.cout) : p.cout / 64 + (p.cout % 64 > 32 ? 1 : 0);
+        if (o.wino1d && p.has(K_W1B) && blocks > 0 && w1b_supported(L)) {
+            ch.kernel = K_W1B;
+            ch.w1b_blocks = blocks;
+        } else if (o.wino6 && p.has(K_WINO6) && H * W >= o.wino6_min_pixels && wino6_supported(L)) {
+            // wino6 = 1: Winograd F(6x6) (blocks of 64 outputs, a last block of 32 when the outputs are <= 32 mod 64)
+            ch.kernel = K_WINO6;
+        }
+    }
+    return ch;
+}
+
+// Launches layer p, packed at wpk, on the kernel choose_kernel names: the one path of the forward pass (run_conv) and of b2f_op_conv3x3.
+// The caller has set L's segments (pointers and strides), output (pointer and strides), sizes, stride, nimg and leaky.
+int launch_layer(b2f_ctx *c, hipStream_t s, bool prof, const PackedConv &p, const float *wpk, const KernelOpts &o, int cur_batch, ConvLaunch &L)
+{
+    for (int i = 0; i < p.nseg; ++i) L.seg[i].nchunks = p.chunks[i];
+    if (p.nseg == 1) L.seg[1] = L.seg[0], L.seg[1].nchunks = 0;
+    L.nseg = p.nseg;
+    L.cout = p.cout;
+    L.Ho = (L.H + 2 - 3) / L.stride + 1;
+    L.Wo = (L.W + 2 - 3) / L.stride + 1;
+    L.tiles_per_block = o.s2_tiles_per_block;
+    L.w4_persist = o.wino4_persistent;
+    L.w8 = o.wino8;
+    L.bf16_direct = o.bf16_direct;
+    auto weights = [&](ConvKernel k) { return p.has(k) ? wpk + p.pk[k].w_off : nullptr; };
+    auto bias = [&](ConvKernel k) { return p.has(k) ? wpk + p.pk[k].b_off : nullptr; };
+    L.wpk_bf6 = weights(K_BF6); L.bias_bf6 = bias(K_BF6);
+    L.wpk_s2b = weights(K_S2B); L.bias_s2b = bias(K_S2B);
+    L.wpk_w1b = weights(K_W1B); L.bias_w1b = bias(K_W1B);
+    L.wpk_w6 = weights(K_WINO6); L.bias_w6 = bias(K_WINO6);
+    const KernelChoice ch = choose_kernel(p, o, cur_batch, L);
+    const PackedConv::Packing &q = p.pk[ch.f2x2 ? K_WINO2 : p.base];   // the fp32 packing every launch carries
+    L.wpk = wpk + q.w_off;
+    L.bias = wpk + q.b_off;
+    L.nt = q.nt;
+    L.nblk = q.nblk;
+    L.nsplit = ch.nsplit;
+    L.w1b_nblk = ch.w1b_blocks;
+#if B2F_EXPERIMENTS
+    if (!ch.f2x2) { L.wpk_split = weights(K_WINO4S); L.wpk_split2 = weights(K_WINO2S); }
+    L.w4_hybrid = o.wino4_hybrid;
+#endif
+    const KernelRow &k = kKernels[ch.kernel];
+    char name[48];
+    if (c->profile_layers)   // one profile row per (layer shape, map size)
+        snprintf(name, sizeof name, "conv%s_%dto%d_%dx%d", (B2F_EXPERIMENTS && ch.kernel == K_C16 && o.bf16_direct) ? "B16" : k.tag[L.stride - 1],
+                 p.nchunks() * 8, p.cout, L.H, L.W);
+    else
+        snprintf(name, sizeof name, k.cls[L.stride - 1], L.nt);
+    Scope sc(c, s, name, !prof);
+    HIPCHK(k.launch(L, s));
+    return 0;
+}
+
 // All activations are chunk-planar: [image][C/8][h][w][8].
 int run_conv(b2f_ctx *c, hipStream_t s, bool cap, int conv_id, const ConvSeg *segs, int nimg, int H, int W,
              int stride, int leaky, float *out)
 {
     const PackedConv &p = c->packed[conv_id];
-    // kernel for this call: F(4x4) layers fall back to their F(2x2) packing when the launch would leave most of
-    // the chip idle.  An F(4x4) block (16 x 32 pixels, one per CU) takes about three times as long as an F(2x2)
-    // block (8 x 16 pixels) that has its CU to itself and 1.5 times as long as one that shares it with a second
-    // block, so compare the number of block rounds each kernel needs on 256 CUs.
-    // That rule makes a triplet's result depend (at 1e-6 level) on the batch it is computed in, so it is opt-in
-    // (option adaptive_kernels); the default rule looks at the map size only: F(2x2) below wino4_min_pixels.
-    bool alt = false, split = false;
-    if (p.wino == 4) {
-        // adaptive_kernels: -1 (default) = per launch for single-triplet calls (the reference's own calling pattern, back2future.lua:73:
-        // latency matters and most launches leave the chip half empty), by map size for batches; 0 never, 1 always per launch
-        const bool per_launch = c->adaptive_kernels > 0 || (c->adaptive_kernels < 0 && c->cur_batch == 1);
-        if (!per_launch) {
-            alt = H * W < c->wino4_min_pixels;
-            split = alt && p.nt2 == 2 && H * W <= c->wino_split_pixels;
-        } else {
-            // cost in twentieths of a lone F(2x2) block: F(4x4) block 60; F(2x2) block 20 alone, 40 per pair sharing a CU;
-            // F(2x2) block that computes one of the two N tiles only 13 / 26
-            const long tiles2 = (long)nimg * ((H + 7) / 8) * ((W + 15) / 16);
-            const long b4 = (long)nimg * ((H + 15) / 16) * ((W + 31) / 32) * p.nblk;
-            const long b2 = tiles2 * p.nblk2, b2s = tiles2 * ((p.cout + 31) / 32);
-            const long t4 = 60 * ((b4 + 255) / 256);
-            const long t2 = b2 <= 256 ? 20 : 40 * ((b2 + 511) / 512);
-            const long t2s = p.nt2 != 2 ? t2 : b2s <= 256 ? 13 : 26 * ((b2s + 511) / 512);
-            alt = std::min(t2, t2s) < t4;
-            split = alt && t2s < t2;
-        }
-    }
-    const int mode = alt ? 2 : p.wino;
-    const int nt = alt ? p.nt2 : p.nt, nblk = alt ? p.nblk2 : p.nblk;
-    ConvLaunch L;
-    L.nseg = p.nseg;
-    for (int i = 0; i < p.nseg; ++i) {
-        L.seg[i] = segs[i];
-        L.seg[i].nchunks = p.chunks[i];
-    }
-    if (p.nseg == 1) L.seg[1] = L.seg[0], L.seg[1].nchunks = 0;
-    L.wpk = c->wpk_dev + (alt ? p.w_off2 : p.w_off);
-    L.bias = c->wpk_dev + (alt ? p.b_off2 : p.b_off);
+    ConvLaunch L{};
+    for (int i = 0; i < p.nseg; ++i) L.seg[i] = segs[i];
     L.out = out;
-    L.cout = p.cout;
-    L.nt = nt;
-    L.nblk = nblk;
     L.H = H; L.W = W; L.stride = stride;
-    L.Ho = (H + 2 - 3) / stride + 1;
-    L.Wo = (W + 2 - 3) / stride + 1;
-    L.out_img_stride = (long)((size_t)L.Ho * L.Wo * ((p.cout + 7) / 8 * 8));
-    L.out_chunk_stride = (long)((size_t)L.Ho * L.Wo * 8);
+    const size_t hwo = (size_t)((H + 2 - 3) / stride + 1) * ((W + 2 - 3) / stride + 1);
+    L.out_img_stride = (long)(hwo * ((p.cout + 7) / 8 * 8));
+    L.out_chunk_stride = (long)(hwo * 8);
     L.out_pix_stride = 8;
     L.nimg = nimg;
-    L.nsplit = split ? 1 : 0;
     L.leaky = leaky;
-    L.tiles_per_block = c->s2_tiles_per_block;
-    L.w4_persist = c->wino4_persistent;
-    L.w8 = c->wino8;
-#if B2F_EXPERIMENTS
-    L.wpk_split = (mode == 4 && (c->wino4_split || c->wino4_hybrid) && p.w_off3) ? c->wpk_dev + p.w_off3 : nullptr;
-    L.w4_hybrid = c->wino4_hybrid;
-    L.wpk_split2 = (mode == 4 && c->wino2_split && p.w_off4) ? c->wpk_dev + p.w_off4 : nullptr;
-#endif
-    L.bf16_direct = c->bf16_direct;
-    bool bf6 = p.w_off5 && ((mode == 0 && c->bf16_conv) || (mode == 4 && stride == 1 && H * W >= c->bf16_conv_min_pixels && ((c->bf16_conv == 2 && p.cout <= 32) || c->bf16_conv >= 3)));
-    if (bf6) {
-        L.wpk_bf6 = c->wpk_dev + p.w_off5; L.bias_bf6 = c->wpk_dev + p.b_off5;
-        bf6 = convb_supported(L);            // the profile row below names the kernel that really runs
-        if (!bf6) { L.wpk_bf6 = nullptr; L.bias_bf6 = nullptr; }
-    }
-    bool s2l = false;
-    // (layers of fewer than 64 input channels keep conv3x3_bf6: with four short chunks per tile the loader / consumer block is bound by
-    // its weight traffic -- 2 KB per six MFMAs -- 32 -> 64 measured 0.45 against 0.43 ms; s2_loader = 2 sends them there too)
-    if (mode == 0 && stride == 2 && c->bf16_conv && c->s2_loader && p.w_off7 && (c->s2_loader >= 2 || p.chunks[0] + (p.nseg > 1 ? p.chunks[1] : 0) >= 8)) {
-        L.wpk_s2b = c->wpk_dev + p.w_off7; L.bias_s2b = c->wpk_dev + p.b_off7;
-        s2l = s2b_supported(L);
-        if (s2l) { bf6 = false; L.nsplit = c->s2_tile_groups ? 0 : -1; }
-    }
-    // wino1d = 1: the n-blocks with more than 32 real outputs on the 1-D Winograd bf16 kernel, a last block of <= 32 outputs on the
-    // F(4x4) single-N-tile kernel (half the bf16 kernel's MFMAs would multiply zero padding); 2: every n-block
-    const int w1d_blocks = c->wino1d >= 2 ? w1b_nblk(p.cout) : p.cout / 64 + (p.cout % 64 > 32 ? 1 : 0);
-    bool w1d = !bf6 && mode == 4 && stride == 1 && c->wino1d && p.w_off6 && w1d_blocks > 0;
-    if (w1d) {
-        L.wpk_w1b = c->wpk_dev + p.w_off6; L.bias_w1b = c->wpk_dev + p.b_off6;
-        L.w1b_nblk = w1d_blocks;
-        w1d = w1b_supported(L);
-    }
-    // wino6 = 1: Winograd F(6x6) (blocks of 64 outputs, a last block of 32 when the outputs are <= 32 mod 64)
-    bool w6 = !bf6 && !w1d && mode == 4 && stride == 1 && c->wino6 && p.w_off8 && H * W >= c->wino6_min_pixels;
-    if (w6) {
-        L.wpk_w6 = c->wpk_dev + p.w_off8; L.bias_w6 = c->wpk_dev + p.b_off8;
-        w6 = wino6_supported(L);
-    }
-    char name[48];
-    const bool per_layer = c->profile_layers != 0;   // one profile row per (layer shape, map size)
-    if (per_layer)
-        snprintf(name, sizeof name, "conv%s_%dto%d_%dx%d", s2l ? "L2" : bf6 ? (stride == 1 ? "E1" : "E2") : w1d ? "V1" : w6 ? "W6" : mode == 4 ? "W4" : mode == 3 ? ((B2F_EXPERIMENTS && c->bf16_direct) ? "B16" : "C16") : mode == 5 ? "S16" : mode == 2 ? "W2" : mode == 1 ? "N2" : stride == 1 ? "D1" : "D2",
-                 (p.chunks[0] + (p.nseg > 1 ? p.chunks[1] : 0)) * 8, p.cout, H, W);
-    else
-        snprintf(name, sizeof name, s2l ? "conv3x3_s2b_%d" : bf6 ? (stride == 1 ? "conv3x3_s1_bf16_%d" : "conv3x3_s2_bf16_%d") : w1d ? "conv3x3_w1b_%d" : w6 ? "conv3x3_wino6_nt%d" : mode == 4 ? "conv3x3_wino4_nt%d" : mode == 3 ? "conv3x3_c16_%d" : mode == 5 ? "conv3x3_s2x16_%d" : mode == 2 ? "conv3x3_wino_nt%d"
-                                    : mode == 1 ? "conv3x3_narrow%d" : (stride == 1 ? "conv3x3_s1_nt%d" : "conv3x3_s2_nt%d"),
-                 mode == 1 ? 2 : nt);
-    Scope sc(c, s, name, cap);
-    if (s2l) HIPCHK(launch_conv3x3_s2b(L, s));
-    else if (bf6) HIPCHK(launch_conv3x3_bf6(L, s));
-    else if (w1d) {
-        HIPCHK(launch_conv3x3_w1b(L, s));
-        if (w1d_blocks < w1b_nblk(p.cout)) HIPCHK(launch_conv3x3_wino4_rem(L, s));
-    }
-    else if (w6) HIPCHK(launch_conv3x3_wino6(L, s));
-    else if (mode == 4) HIPCHK(launch_conv3x3_wino4(L, s));
-    else if (mode == 1) HIPCHK(launch_conv_narrow2(L, s));
-    else if (mode == 3) HIPCHK(launch_conv3x3_c16(L, s));
-    else if (mode == 5) HIPCHK(launch_conv3x3_c16s2(L, s));
-    else if (mode == 2) HIPCHK(launch_conv3x3_wino(L, s));
-    else HIPCHK(launch_conv3x3(L, s));
-    return 0;
+    return launch_layer(c, s, !cap, p, c->wpk_dev, *c, c->cur_batch, L);
 }
 
 // decoder(n) of pwc.lua:76-85 at level l; input = {cs[ref][l], cost-volume record}
@@ -542,7 +557,7 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
     // (the head kernel reads the c16 / c16s2 packings of its two layers: B2F_WINO=0 packs them for the direct kernel instead)
     const int head_id1 = find_conv(c, KIND_FEAT, 2, 2), head_id2 = find_conv(c, KIND_FEAT, 3, 1);
     const bool head_fused = c->bf16_direct >= 2 && P.h[2] >= 4 && P.w[2] >= 4 && head_id1 >= 0 && head_id2 >= 0 &&
-                            c->packed[(size_t)head_id1].wino == 3 && c->packed[(size_t)head_id2].wino == 5;   // level-2 conv 2 + level-3 conv 1 as one streaming kernel; cs[2] then holds the 32-channel level-3 map
+                            c->packed[(size_t)head_id1].base == K_C16 && c->packed[(size_t)head_id2].base == K_C16S2;   // level-2 conv 2 + level-3 conv 1 as one streaming kernel; cs[2] then holds the 32-channel level-3 map
     for (int l = 2; l <= 7; ++l) {
         const int hi = P.h[l - 1], wi = P.w[l - 1], ho = P.h[l], wo = P.w[l];
         const int Ci = (l == 2) ? kImgC : kFeat[l - 1], Co = kFeat[l];
@@ -563,7 +578,7 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
             CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 1), &in1, P.nimg, hi, wi, 2, 1, A + P.tmp));
         }
         if (l == 2 && head_fused) {   // level-2 conv 2 + level-3 conv 1 in one streaming kernel (b2f_head.hip)
-            const PackedConv &p1 = c->packed[find_conv(c, KIND_FEAT, 2, 2)], &p2 = c->packed[find_conv(c, KIND_FEAT, 3, 1)];
+            const PackedConv::Packing &p1 = c->packed[(size_t)head_id1].pk[K_C16], &p2 = c->packed[(size_t)head_id2].pk[K_C16S2];
             HeadLaunch hl;
             hl.in = A + P.tmp; hl.in_img_stride = (long)((size_t)ho * wo * 16); hl.in_chunk_stride = (long)((size_t)ho * wo * 8); hl.in_pix_stride = 8;
             hl.H1 = ho; hl.W1 = wo;
@@ -741,6 +756,79 @@ int install_weights(b2f_ctx *c, const float *flat, long long n, bool past)
     return pack_all(c, flat);
 }
 
+// ---- options ---------------------------------------------------------------------------
+// One row per b2f_set_option / b2f_get_option key; b2f_init seeds the OPT_ENV ones from B2F_<NAME IN CAPITALS>.
+enum {
+    OPT_ENV = 1,        // seeded from the environment at b2f_init
+    OPT_SYNC = 2,       // a different kernel mix: setting it synchronises the device and drops the captured graphs, which hold the old one
+    OPT_EXP_ONLY = 4,   // selects a kernel of tools/experiments/csrc: the product build has no such option (not seeded, only 0 accepted)
+};
+struct OptRow {
+    const char *name;
+    int b2f_ctx::*member;
+    int flags;
+    int repack;         // > 0: an optional packing exists only while an option of this group reads it (reads_packing); a set that changes that repacks
+};
+const OptRow kOptions[] = {
+    {"use_graph", &b2f_ctx::use_graph, OPT_ENV, 0},
+    {"host_graph", &b2f_ctx::host_graph, OPT_ENV, 0},
+    {"profile", &b2f_ctx::profile, OPT_ENV, 0},
+    {"profile_layers", &b2f_ctx::profile_layers, OPT_ENV, 0},
+    {"corr_variant", &b2f_ctx::corr_variant, OPT_ENV | OPT_SYNC, 0},
+    {"corr_ablate", &b2f_ctx::corr_ablate, OPT_ENV | OPT_SYNC, 0},
+    {"bf16_direct", &b2f_ctx::bf16_direct, OPT_ENV | OPT_SYNC, 0},
+    {"bf16_conv", &b2f_ctx::bf16_conv, OPT_ENV | OPT_SYNC, 1},
+    {"bf16_conv_min_pixels", &b2f_ctx::bf16_conv_min_pixels, OPT_SYNC, 0},
+    {"wino1d", &b2f_ctx::wino1d, OPT_ENV | OPT_SYNC, 2},
+    {"wino6", &b2f_ctx::wino6, OPT_ENV | OPT_SYNC, 3},
+    {"wino6_min_pixels", &b2f_ctx::wino6_min_pixels, OPT_ENV | OPT_SYNC, 0},
+    {"wino2_split", &b2f_ctx::wino2_split, OPT_ENV | OPT_SYNC | OPT_EXP_ONLY, 4},
+    {"wino4_split", &b2f_ctx::wino4_split, OPT_ENV | OPT_SYNC | OPT_EXP_ONLY, 5},
+    {"wino4_hybrid", &b2f_ctx::wino4_hybrid, OPT_ENV | OPT_SYNC | OPT_EXP_ONLY, 5},
+    {"s2_tiles_per_block", &b2f_ctx::s2_tiles_per_block, OPT_ENV | OPT_SYNC, 0},
+    {"wino4_persistent", &b2f_ctx::wino4_persistent, OPT_ENV | OPT_SYNC, 0},
+    {"s2_loader", &b2f_ctx::s2_loader, OPT_ENV | OPT_SYNC, 0},
+    {"s2_tile_groups", &b2f_ctx::s2_tile_groups, OPT_ENV | OPT_SYNC, 0},
+    {"wino_split_pixels", &b2f_ctx::wino_split_pixels, OPT_ENV | OPT_SYNC, 0},
+    {"wino8", &b2f_ctx::wino8, OPT_ENV | OPT_SYNC, 0},
+    {"wino4_min_pixels", &b2f_ctx::wino4_min_pixels, OPT_ENV | OPT_SYNC, 0},
+    {"adaptive_kernels", &b2f_ctx::adaptive_kernels, OPT_ENV | OPT_SYNC, 0},
+    {"op_wino_split", &b2f_ctx::op_wino_split, OPT_ENV, 0},
+    {"host_subbatch_pixels", nullptr, OPT_ENV, 0},   // long long b2f_ctx::host_subbatch_pixels
+    {"host_threads", &b2f_ctx::host_threads, OPT_ENV, 0},
+    {"host_u8", &b2f_ctx::host_u8, OPT_ENV, 0},
+    {"host_ramp", &b2f_ctx::host_ramp, OPT_ENV, 0},
+    {"debug_fail_next", &b2f_ctx::debug_fail_next, 0, 0},
+};
+
+const OptRow *find_option(const char *key)
+{
+    for (const OptRow &r : kOptions)
+        if (!strcmp(key, r.name)) return &r;
+    return nullptr;
+}
+
+// does an option of repack group `group` read the group's optional packing?  (F(4x4)-class layers carry the bf16 direct packing only while
+// bf16_conv >= 2; the other packings while an option of their group is not 0)
+bool reads_packing(const b2f_ctx *c, int group)
+{
+    for (const OptRow &r : kOptions)
+        if (r.repack == group && (r.member == &b2f_ctx::bf16_conv ? c->*r.member >= 2 : c->*r.member != 0)) return true;
+    return false;
+}
+
+// A value that names an experiment kernel, not in the product build: refused by b2f_set_option with this text; from the environment b2f_init
+// warns and keeps the default (an A/B run driven by the environment would otherwise time the default kernel under another label).  nullptr = fine.
+const char *experiment_value(const OptRow &r, int value)
+{
+    if (B2F_EXPERIMENTS) return nullptr;
+    if (r.member == &b2f_ctx::corr_variant && (value == 2 || value == 4 || value == 6 || value == 8))
+        return "b2f_set_option: corr_variant 2 / 4 / 6 / 8 are experiment kernels: build with `python -m back2future_amd.build --experiments`";
+    if (r.member == &b2f_ctx::bf16_direct && value == 1)
+        return "b2f_set_option: bf16_direct = 1 (the 16 -> 16 layer alone on the bf16 pipe) is an experiment: build with `python -m back2future_amd.build --experiments`";
+    return nullptr;
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -858,55 +946,31 @@ int b2f_init_ex(const char *name_or_path, int device, const char *graph_opts, b2
     {   // defaults of the tuning options may come from the environment; read here once, never on the hot path
         // B2F_<OPTION NAME IN CAPITALS> seeds the option of that name (b2f_set_option keys); a value that is set but not a
         // number (B2F_PROFILE_LAYERS=yes, or empty) counts as 1
-        auto env_int = [](const char *k, long long dflt) {
-            const char *v = getenv(k);
+        auto env_int = [](const std::string &k, long long dflt) {
+            const char *v = getenv(k.c_str());
             if (!v) return dflt;
             char *end = nullptr;
             const long long x = strtoll(v, &end, 10);
             return end == v ? 1ll : x;
         };
-        c->wino4_min_pixels = (int)env_int("B2F_WINO4_MIN_PIXELS", c->wino4_min_pixels);
-        c->wino_split_pixels = (int)env_int("B2F_WINO_SPLIT_PIXELS", c->wino_split_pixels);
-        c->wino8 = (int)env_int("B2F_WINO8", c->wino8);
-        c->adaptive_kernels = (int)env_int("B2F_ADAPTIVE_KERNELS", c->adaptive_kernels);
-        c->corr_variant = (int)env_int("B2F_CORR_VARIANT", env_int("B2F_CORR_LAT", c->corr_variant));   // B2F_CORR_LAT: the round-1 name
-        c->op_wino_split = (int)env_int("B2F_OP_WINO_SPLIT", c->op_wino_split);
-        c->use_graph = (int)env_int("B2F_USE_GRAPH", c->use_graph);
-        c->host_graph = (int)env_int("B2F_HOST_GRAPH", c->host_graph);
-        c->profile = (int)env_int("B2F_PROFILE", c->profile);
-        c->corr_ablate = (int)env_int("B2F_CORR_ABLATE", c->corr_ablate);
-        c->profile_layers = (int)env_int("B2F_PROFILE_LAYERS", c->profile_layers);
-        c->wino4_persistent = (int)env_int("B2F_WINO4_PERSISTENT", c->wino4_persistent);
-        c->wino1d = (int)env_int("B2F_WINO1D", c->wino1d);
-        c->wino6 = (int)env_int("B2F_WINO6", c->wino6);
-        c->wino6_min_pixels = (int)env_int("B2F_WINO6_MIN_PIXELS", c->wino6_min_pixels);
-        c->s2_loader = (int)env_int("B2F_S2_LOADER", c->s2_loader);
-        c->s2_tile_groups = (int)env_int("B2F_S2_TILE_GROUPS", c->s2_tile_groups);
-#if B2F_EXPERIMENTS
-        c->wino4_split = (int)env_int("B2F_WINO4_SPLIT", c->wino4_split);
-        c->wino4_hybrid = (int)env_int("B2F_WINO4_HYBRID", c->wino4_hybrid);
-        c->wino2_split = (int)env_int("B2F_WINO2_SPLIT", c->wino2_split);
-#endif
         if (!use_wino()) { c->bf16_conv = 0; c->bf16_direct = 0; }   // B2F_WINO=0: every layer on the direct fp32-MFMA kernel (bit-exact fmaf chains)
-        c->bf16_direct = (int)env_int("B2F_BF16_DIRECT", c->bf16_direct);
-        c->bf16_conv = (int)env_int("B2F_BF16_CONV", c->bf16_conv);
-        c->s2_tiles_per_block = (int)env_int("B2F_S2_TILES_PER_BLOCK", c->s2_tiles_per_block);
-        c->host_subbatch_pixels = env_int("B2F_HOST_SUBBATCH_PIXELS", c->host_subbatch_pixels);
-        c->host_threads = (int)env_int("B2F_HOST_THREADS", c->host_threads);
-        c->host_u8 = (int)env_int("B2F_HOST_U8", c->host_u8);
-        c->host_ramp = (int)env_int("B2F_HOST_RAMP", c->host_ramp);
-#if !B2F_EXPERIMENTS
-        // the same rule b2f_set_option enforces: an experiment kernel that is not in this build is not accepted under its name (an A/B
-        // run driven by the environment would otherwise time the default kernel under another label); get_option reports what runs
-        if (c->corr_variant == 2 || c->corr_variant == 4 || c->corr_variant == 6 || c->corr_variant == 8) {
-            fprintf(stderr, "b2f_init: B2F_CORR_VARIANT=%d is an experiment kernel (build with `python -m back2future_amd.build --experiments`): using the default\n", c->corr_variant);
-            c->corr_variant = -1;
+        c->corr_variant = (int)env_int("B2F_CORR_LAT", c->corr_variant);   // the round-1 name of B2F_CORR_VARIANT
+        for (const OptRow &r : kOptions) {
+            if (!(r.flags & OPT_ENV) || ((r.flags & OPT_EXP_ONLY) && !B2F_EXPERIMENTS)) continue;
+            std::string k = std::string("B2F_") + r.name;
+            for (char &ch : k) ch = (char)toupper((unsigned char)ch);
+            if (!r.member) {
+                c->host_subbatch_pixels = env_int(k, c->host_subbatch_pixels);
+                continue;
+            }
+            c->*r.member = (int)env_int(k, c->*r.member);
+            if (experiment_value(r, c->*r.member)) {
+                const bool corr = r.member == &b2f_ctx::corr_variant;
+                fprintf(stderr, "b2f_init: %s=%d is an experiment%s (build with `python -m back2future_amd.build --experiments`): using the default%s\n", k.c_str(),
+                        c->*r.member, corr ? " kernel" : "", corr ? "" : " (2)");
+                c->*r.member = corr ? -1 : 2;
+            }
         }
-        if (c->bf16_direct == 1) {
-            fprintf(stderr, "b2f_init: B2F_BF16_DIRECT=1 is an experiment (build with `python -m back2future_amd.build --experiments`): using the default (2)\n");
-            c->bf16_direct = 2;
-        }
-#endif
     }
     // a blocking stream: ordered with the legacy default stream like any such stream, so inputs that PyTorch (whose
     // default stream is the null stream) or hipMemcpy / hipMemset produced there are complete before our kernels read them
@@ -1008,104 +1072,25 @@ B2F_CATCH("b2f_commit_weights")
 int b2f_set_option(b2f_ctx *c, const char *key, int value) try
 {
     if (!c || !key) return fail("b2f_set_option: null argument");
-    if (!strcmp(key, "use_graph")) c->use_graph = value;
-    else if (!strcmp(key, "host_graph")) c->host_graph = value;
-    else if (!strcmp(key, "profile")) c->profile = value;
-    else if (!strcmp(key, "profile_layers")) c->profile_layers = value;
-    else if (!strcmp(key, "bf16_direct") || !strcmp(key, "bf16_conv") || !strcmp(key, "bf16_conv_min_pixels")) {
-        // a different kernel mix: captured graphs hold the old one
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        if (!strcmp(key, "bf16_direct")) {
-            if (value == 1 && !B2F_EXPERIMENTS) return fail("b2f_set_option: bf16_direct = 1 (the 16 -> 16 layer alone on the bf16 pipe) is an experiment: build with `python -m back2future_amd.build --experiments`");
-            c->bf16_direct = value;
-        } else if (!strcmp(key, "bf16_conv_min_pixels")) c->bf16_conv_min_pixels = value;
-        else {
-            const bool had = c->bf16_conv >= 2;
-            c->bf16_conv = value;
-            if (had != (value >= 2)) CHK(b2f_commit_weights(c));     // the F(4x4)-class layers carry the bf16 direct packing only while bf16_conv >= 2
-        }
+    const OptRow *r = find_option(key);
+    if (!r) return fail(std::string("b2f_set_option: unknown key ") + key);
+    if (!r->member) {
+        c->host_subbatch_pixels = value > 0 ? value : (16ll << 20);
+        return 0;
     }
-    else if (!strcmp(key, "wino1d")) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        const bool had = c->wino1d != 0;
-        c->wino1d = value;
-        if (had != (value != 0)) CHK(b2f_commit_weights(c));   // the packing exists only while the option reads it
-    }
-    else if (!strcmp(key, "wino6") || !strcmp(key, "wino6_min_pixels")) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        if (key[5] == '_') c->wino6_min_pixels = value;
-        else {
-            const bool had = c->wino6 != 0;
-            c->wino6 = value;
-            if (had != (value != 0)) CHK(b2f_commit_weights(c));   // the packing exists only while the option reads it
-        }
-    }
-#if !B2F_EXPERIMENTS
-    else if (!strcmp(key, "wino2_split") || !strcmp(key, "wino4_split") || !strcmp(key, "wino4_hybrid")) {
+    if ((r->flags & OPT_EXP_ONLY) && !B2F_EXPERIMENTS) {
         if (value != 0) return fail(std::string("b2f_set_option: ") + key + " selects an experiment kernel (tools/experiments/csrc): build with `python -m back2future_amd.build --experiments` and load libb2f_exp.so");
+        return 0;
     }
-#else
-    else if (!strcmp(key, "wino2_split")) {
+    if (r->flags & OPT_SYNC) {
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipDeviceSynchronize());
         drop_graphs(c);
-        const bool had = c->wino2_split != 0;
-        c->wino2_split = value;
-        if (had != (value != 0)) CHK(b2f_commit_weights(c));
     }
-    else if (!strcmp(key, "wino4_split") || !strcmp(key, "wino4_hybrid")) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        const bool had = c->wino4_split || c->wino4_hybrid;
-        (key[6] == 's' ? c->wino4_split : c->wino4_hybrid) = value;
-        if (had != (c->wino4_split || c->wino4_hybrid)) CHK(b2f_commit_weights(c));   // the split packing exists only while an option reads it
-    }
-#endif
-    else if (!strcmp(key, "s2_tiles_per_block") || !strcmp(key, "wino4_persistent")) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        (key[0] == 's' ? c->s2_tiles_per_block : c->wino4_persistent) = value;
-    }
-    else if (!strcmp(key, "s2_loader") || !strcmp(key, "s2_tile_groups")) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        (key[3] == 'l' ? c->s2_loader : c->s2_tile_groups) = value;
-    }
-    else if (!strcmp(key, "wino_split_pixels") || !strcmp(key, "wino8")) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        (key[4] == '8' ? c->wino8 : c->wino_split_pixels) = value;
-    }
-    else if (!strcmp(key, "wino4_min_pixels") || !strcmp(key, "adaptive_kernels")) {
-        // a different kernel mix: captured graphs hold the old one
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        (key[0] == 'w' ? c->wino4_min_pixels : c->adaptive_kernels) = value;
-    } else if (!strcmp(key, "corr_variant") || !strcmp(key, "corr_ablate")) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceSynchronize());
-        drop_graphs(c);
-        if (key[5] == 'v' && !B2F_EXPERIMENTS && (value == 2 || value == 4 || value == 6 || value == 8))
-            return fail("b2f_set_option: corr_variant 2 / 4 / 6 / 8 are experiment kernels: build with `python -m back2future_amd.build --experiments`");
-        (key[5] == 'v' ? c->corr_variant : c->corr_ablate) = value;
-    } else if (!strcmp(key, "op_wino_split")) c->op_wino_split = value;
-    else if (!strcmp(key, "host_subbatch_pixels")) c->host_subbatch_pixels = value > 0 ? value : (16ll << 20);
-    else if (!strcmp(key, "host_threads")) c->host_threads = value;
-    else if (!strcmp(key, "host_u8")) c->host_u8 = value;
-    else if (!strcmp(key, "host_ramp")) c->host_ramp = value;
-    else if (!strcmp(key, "debug_fail_next")) c->debug_fail_next = value;
-    else return fail(std::string("b2f_set_option: unknown key ") + key);
+    if (const char *refusal = experiment_value(*r, value)) return fail(refusal);
+    const bool had = r->repack && reads_packing(c, r->repack);
+    c->*r->member = value;
+    if (r->repack && had != reads_packing(c, r->repack)) CHK(b2f_commit_weights(c));
     return 0;
 }
 B2F_CATCH("b2f_set_option")
@@ -1113,38 +1098,11 @@ B2F_CATCH("b2f_set_option")
 int b2f_get_option(const b2f_ctx *c, const char *key, int *value) try
 {
     if (!c || !key || !value) return fail("b2f_get_option: null argument");
-    const std::string k(key);
-    if (k == "use_graph") *value = c->use_graph;
-    else if (k == "host_graph") *value = c->host_graph;
-    else if (k == "profile") *value = c->profile;
-    else if (k == "profile_layers") *value = c->profile_layers;
-    else if (k == "s2_tiles_per_block") *value = c->s2_tiles_per_block;
-    else if (k == "wino4_persistent") *value = c->wino4_persistent;
-    else if (k == "experiments") *value = B2F_EXPERIMENTS;
-    else if (k == "wino1d") *value = c->wino1d;
-    else if (k == "wino6") *value = c->wino6;
-    else if (k == "wino6_min_pixels") *value = c->wino6_min_pixels;
-    else if (k == "s2_loader") *value = c->s2_loader;
-    else if (k == "s2_tile_groups") *value = c->s2_tile_groups;
-    else if (k == "wino4_split") *value = c->wino4_split;
-    else if (k == "wino4_hybrid") *value = c->wino4_hybrid;
-    else if (k == "wino2_split") *value = c->wino2_split;
-    else if (k == "bf16_direct") *value = c->bf16_direct;
-    else if (k == "bf16_conv") *value = c->bf16_conv;
-    else if (k == "bf16_conv_min_pixels") *value = c->bf16_conv_min_pixels;
-    else if (k == "wino4_min_pixels") *value = c->wino4_min_pixels;
-    else if (k == "wino_split_pixels") *value = c->wino_split_pixels;
-    else if (k == "wino8") *value = c->wino8;
-    else if (k == "adaptive_kernels") *value = c->adaptive_kernels;
-    else if (k == "corr_variant") *value = c->corr_variant;
-    else if (k == "corr_ablate") *value = c->corr_ablate;
-    else if (k == "op_wino_split") *value = c->op_wino_split;
-    else if (k == "host_subbatch_pixels") *value = (int)std::min<long long>(c->host_subbatch_pixels, 0x7fffffff);
-    else if (k == "host_threads") *value = c->host_threads;
-    else if (k == "host_u8") *value = c->host_u8;
-    else if (k == "host_ramp") *value = c->host_ramp;
-    else if (k == "debug_fail_next") *value = c->debug_fail_next;
-    else return fail("b2f_get_option: unknown key " + k);
+    const OptRow *r = find_option(key);
+    if (!strcmp(key, "experiments")) *value = B2F_EXPERIMENTS;   // read-only: which build this is
+    else if (!r) return fail(std::string("b2f_get_option: unknown key ") + key);
+    else if (!r->member) *value = (int)std::min<long long>(c->host_subbatch_pixels, 0x7fffffff);
+    else *value = c->*r->member;
     return 0;
 }
 B2F_CATCH("b2f_get_option")
@@ -1505,123 +1463,33 @@ int b2f_op_conv3x3(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, cons
     if (!c || !x || !wt || !bias || !y) return fail("b2f_op_conv3x3: null argument");
     if (stride != 1 && stride != 2) return fail("b2f_op_conv3x3: stride must be 1 or 2");
     HIPCHK(hipSetDevice(c->device));
-    const int chunks = (Ci + kCK - 1) / kCK, Cp = chunks * kCK;
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-    int nt, nblk;
-    int wino = (stride == 1 && use_wino() && Ci == 16 && Co == 16) ? 3 : (stride == 2 && use_wino() && Ci == 16 && Co == 32) ? 5 : stride == 1 ? wino_mode(Co) : 0;
-    // tests: option op_wino_split = 1 runs F(4x4)-eligible layers on the F(2x2) kernel, one block per 32-output N tile
-    const bool op_split = c->op_wino_split && wino == 4 && Co > 32;
-    if (op_split) wino = 2;
-    if (wino == 4) { nt = 2; nblk = wino4_nblk(Co); }
-    else if (wino == 1 || wino == 3 || wino == 5) { nt = 1; nblk = 1; }
-    else if (wino == 2) wino_choose_tiles(Co, &nt, &nblk);
-    else conv_choose_tiles(Co, &nt, &nblk);
-    std::vector<float> wpk(wino == 4 ? wino4_wpk_floats(chunks, nblk) : wino == 1 ? narrow2_wpk_floats(chunks)
-                           : wino == 3 ? c16_wpk_floats() : wino == 5 ? c16s2_wpk_floats() : wino == 2 ? wino_wpk_floats(chunks, nt, nblk) : conv_wpk_floats(chunks, nt, nblk)),
-        bpk((size_t)nblk * nt * 32);
-    if (wino == 4) wino4_pack_weights(wt, bias, Co, Ci, nullptr, chunks, nblk, wpk.data(), bpk.data());
-    else if (wino == 1) narrow2_pack_weights(wt, bias, Ci, nullptr, chunks, wpk.data(), bpk.data());
-    else if (wino == 3) c16_pack_weights(wt, bias, Ci, nullptr, wpk.data(), bpk.data());
-    else if (wino == 5) c16s2_pack_weights(wt, bias, Ci, nullptr, wpk.data(), bpk.data());
-    else if (wino == 2) wino_pack_weights(wt, bias, Co, Ci, nullptr, chunks, nt, nblk, wpk.data(), bpk.data());
-    else conv_pack_weights(wt, bias, Co, Ci, nullptr, chunks, nt, nblk, wpk.data(), bpk.data());
-    DevBuf dpl, dx, dw, db, dy, dyp, dws, dws2;
+    // a one-layer model: packed as pack_all packs a layer, launched as run_conv launches it, on NHWC strides
+    PackedConv p;
+    p.cout = Co;
+    p.chunks[0] = (Ci + kCK - 1) / kCK;
+    p.base = base_kernel(Ci, Co, stride == 1, false);
+    const int Cp = p.chunks[0] * kCK, Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+    // The kernel tests address a layer's kernel at any map size, so the entry leaves the F(4x4) -> F(2x2) fallback of small maps out; with
+    // option op_wino_split = 1 (tests) layers of more than 32 outputs take it at every size, one block per 32-output N tile.
+    KernelOpts o = *c;
+    o.adaptive_kernels = 0;
+    o.wino4_min_pixels = o.wino_split_pixels = (c->op_wino_split && Co > 32) ? 0x7fffffff : 0;
+    size_t nw = 0;
+    place_packings(p, stride == 1, o, &nw);
+    std::vector<float> wpk(nw, 0.f);
+    fill_packings(p, wt, bias, Ci, nullptr, wpk.data());
+    DevBuf dpl, dx, dw, dy, dyp;
     const size_t nx = (size_t)B * Ci * H * W, nxp = (size_t)B * H * W * Cp, ny = (size_t)B * Co * Ho * Wo;
-    CHK(dpl.alloc(nx)); CHK(dx.alloc(nxp)); CHK(dw.alloc(wpk.size())); CHK(db.alloc(bpk.size())); CHK(dy.alloc(ny)); CHK(dyp.alloc(ny));
-#if B2F_EXPERIMENTS
-    if (wino == 4 && (c->wino4_split || c->wino4_hybrid)) {
-        std::vector<float> wps(wino4s_wpk_floats(chunks, nblk));
-        wino4s_pack_weights(wt, Co, Ci, nullptr, chunks, nblk, wps.data());
-        CHK(dws.alloc(wps.size()));
-        HIPCHK(hipMemcpy(dws.p, wps.data(), wps.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-#endif
+    CHK(dpl.alloc(nx)); CHK(dx.alloc(nxp)); CHK(dw.alloc(nw)); CHK(dy.alloc(ny)); CHK(dyp.alloc(ny));
     HIPCHK(hipMemcpy(dpl.p, x, nx * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw.p, wpk.data(), wpk.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db.p, bpk.data(), bpk.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dw.p, wpk.data(), nw * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(launch_planar_to_nhwc(dpl.p, Ci, B, H, W, dx.p, Cp, c->stream));
-    ConvLaunch L;
-    L.nseg = 1;
-    L.seg[0] = {dx.p, (long)((size_t)H * W * Cp), 8, Cp, chunks};
-    L.seg[1] = L.seg[0];
-    L.seg[1].nchunks = 0;
-    L.wpk = dw.p; L.bias = db.p; L.out = dy.p;
-    L.out_img_stride = (long)((size_t)Ho * Wo * Co); L.out_chunk_stride = 8; L.out_pix_stride = Co; L.cout = Co;
-    L.nt = nt; L.nblk = nblk; L.H = H; L.W = W; L.Ho = Ho; L.Wo = Wo; L.stride = stride; L.nimg = B; L.leaky = leaky;
-    L.nsplit = op_split ? 1 : 0;
-    L.nb0 = 0; L.trace = nullptr;
-    L.w4_persist = c->wino4_persistent;
-    L.w8 = c->wino8;
-    L.wpk_split = dws.p;
-    L.w4_hybrid = c->wino4_hybrid;
-    L.bf16_direct = c->bf16_direct;
-    DevBuf dw5, db5;
-    const bool bf6_op = (Co & 3) == 0 && ((wino == 0 && c->bf16_conv) || (wino == 4 && stride == 1 && H * W >= c->bf16_conv_min_pixels && ((c->bf16_conv == 2 && Co <= 32) || c->bf16_conv >= 3)));
-    if (bf6_op) {
-        std::vector<float> w5(convb_wpk_floats(chunks, Co)), b5((size_t)convb_nblk(Co) * 64);
-        convb_pack_weights(wt, bias, Co, Ci, nullptr, chunks, w5.data(), b5.data());
-        CHK(dw5.alloc(w5.size())); CHK(db5.alloc(b5.size()));
-        HIPCHK(hipMemcpy(dw5.p, w5.data(), w5.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db5.p, b5.data(), b5.size() * sizeof(float), hipMemcpyHostToDevice));
-        L.wpk_bf6 = dw5.p; L.bias_bf6 = db5.p;
-    }
-    DevBuf dw7, db7;
-    bool s2l_op = false;
-    if (wino == 0 && stride == 2 && c->bf16_conv && c->s2_loader && (Co & 3) == 0 && Co <= 256 && (c->s2_loader >= 2 || chunks >= 8)) {
-        std::vector<float> w7(s2b_wpk_floats(chunks, Co)), b7((size_t)s2b_ntiles(Co) * 32);
-        s2b_pack_weights(wt, bias, Co, Ci, nullptr, chunks, w7.data(), b7.data());
-        CHK(dw7.alloc(w7.size())); CHK(db7.alloc(b7.size()));
-        HIPCHK(hipMemcpy(dw7.p, w7.data(), w7.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db7.p, b7.data(), b7.size() * sizeof(float), hipMemcpyHostToDevice));
-        L.wpk_s2b = dw7.p; L.bias_s2b = db7.p;
-        s2l_op = s2b_supported(L);
-        if (s2l_op) L.nsplit = c->s2_tile_groups ? 0 : -1;
-    }
-    DevBuf dw6, db6;
-    bool w1d_op = false;
-    if (wino == 4 && stride == 1 && c->wino1d && !bf6_op) {
-        std::vector<float> w6(w1b_wpk_floats(chunks, Co)), b6((size_t)w1b_nblk(Co) * 64);
-        w1b_pack_weights(wt, bias, Co, Ci, nullptr, chunks, w6.data(), b6.data());
-        CHK(dw6.alloc(w6.size())); CHK(db6.alloc(b6.size()));
-        HIPCHK(hipMemcpy(dw6.p, w6.data(), w6.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db6.p, b6.data(), b6.size() * sizeof(float), hipMemcpyHostToDevice));
-        L.wpk_w1b = dw6.p; L.bias_w1b = db6.p;
-        L.w1b_nblk = c->wino1d >= 2 ? w1b_nblk(Co) : Co / 64 + (Co % 64 > 32 ? 1 : 0);
-        w1d_op = w1b_supported(L) && L.w1b_nblk > 0;
-    }
-    DevBuf dw8, db8;
-    bool w6_op = false;
-    if (wino == 4 && stride == 1 && c->wino6 && !bf6_op && !w1d_op && H * W >= c->wino6_min_pixels) {
-        std::vector<float> w8(wino6_wpk_floats(chunks, Co)), b8((size_t)wino6_nblk(Co) * 64);
-        wino6_pack_weights(wt, bias, Co, Ci, nullptr, chunks, w8.data(), b8.data());
-        CHK(dw8.alloc(w8.size())); CHK(db8.alloc(b8.size()));
-        HIPCHK(hipMemcpy(dw8.p, w8.data(), w8.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db8.p, b8.data(), b8.size() * sizeof(float), hipMemcpyHostToDevice));
-        L.wpk_w6 = dw8.p; L.bias_w6 = db8.p;
-        w6_op = wino6_supported(L);
-    }
-#if B2F_EXPERIMENTS
-    if (wino == 4 && c->wino2_split) {
-        std::vector<float> wps(wino2s_wpk_floats(chunks, nblk));
-        wino2s_pack_weights(wt, Co, Ci, nullptr, chunks, nblk, wps.data());
-        CHK(dws2.alloc(wps.size()));
-        HIPCHK(hipMemcpy(dws2.p, wps.data(), wps.size() * sizeof(float), hipMemcpyHostToDevice));
-        L.wpk_split2 = dws2.p;
-    }
-#endif
-    if (s2l_op) HIPCHK(launch_conv3x3_s2b(L, c->stream));
-    else if (bf6_op && convb_supported(L)) HIPCHK(launch_conv3x3_bf6(L, c->stream));
-    else if (w1d_op) {
-        HIPCHK(launch_conv3x3_w1b(L, c->stream));
-        if (L.w1b_nblk < w1b_nblk(Co)) HIPCHK(launch_conv3x3_wino4_rem(L, c->stream));
-    }
-    else if (w6_op) HIPCHK(launch_conv3x3_wino6(L, c->stream));
-    else if (wino == 4) HIPCHK(launch_conv3x3_wino4(L, c->stream));
-    else if (wino == 1) HIPCHK(launch_conv_narrow2(L, c->stream));
-    else if (wino == 3) HIPCHK(launch_conv3x3_c16(L, c->stream));
-    else if (wino == 5) HIPCHK(launch_conv3x3_c16s2(L, c->stream));
-    else if (wino == 2) HIPCHK(launch_conv3x3_wino(L, c->stream));
-    else HIPCHK(launch_conv3x3(L, c->stream));
+    ConvLaunch L{};
+    L.seg[0] = {dx.p, (long)((size_t)H * W * Cp), 8, Cp, 0};
+    L.out = dy.p;
+    L.out_img_stride = (long)((size_t)Ho * Wo * Co); L.out_chunk_stride = 8; L.out_pix_stride = Co;
+    L.H = H; L.W = W; L.stride = stride; L.nimg = B; L.leaky = leaky;
+    CHK(launch_layer(c, c->stream, false, p, dw.p, o, 0, L));
     HIPCHK(launch_nhwc_to_planar(dy.p, Co, Co, B, Ho, Wo, dyp.p, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(y, dyp.p, ny * sizeof(float), hipMemcpyDeviceToHost));

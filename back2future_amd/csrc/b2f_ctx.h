@@ -26,24 +26,75 @@ int api_fail(const std::string &m);
 const std::string &api_error();
 
 
+// The kernels that can run a conv layer; each reads its own packing of the layer's weights (b2f_api.hip: kKernels has one row per kernel).
+enum ConvKernel {
+    K_DIRECT = 0,   // direct implicit GEMM on the fp32 MFMA, stride 1 / 2 (b2f_conv.hip)
+    K_NARROW2,      // VALU kernel for 2 outputs (b2f_glue.hip)
+    K_WINO2,        // Winograd F(2x2,3x3) (b2f_wino.hip)
+    K_C16,          // 16 -> 16 stride-1 kernel (b2f_conv16.hip)
+    K_C16S2,        // 16 -> 32 stride-2 kernel (b2f_conv16.hip)
+    K_WINO4,        // Winograd F(4x4,3x3) (b2f_wino4.hip)
+    K_BF6,          // direct implicit GEMM on the bf16 pipe with split fp32 operands (b2f_convb.hip)
+    K_S2B,          // stride-2 loader / consumer kernel on the bf16 pipe (b2f_s2b.hip)
+    K_W1B,          // 1-D Winograd F(4,3) loader / consumer kernel on the bf16 pipe (b2f_w1b.hip)
+    K_WINO6,        // Winograd F(6x6,3x3) (b2f_wino6.hip)
+#if B2F_EXPERIMENTS
+    K_WINO4S,       // split weights the F(4x4) launcher reads with wino4_split / wino4_hybrid (b2f_wino4s.hip)
+    K_WINO2S,       // split weights it reads with wino2_split (b2f_wino2s.hip)
+#endif
+    K_COUNT
+};
+
 struct PackedConv {
     int nseg = 1;
     int chunks[2] = {0, 0};
-    int cout = 0, nt = 1, nblk = 1;
-    int wino = 0;                  // 0 direct kernel, 1 VALU kernel for 2 outputs, 2 Winograd F(2x2,3x3), 3 16->16 kernel,
-                                   // 4 Winograd F(4x4,3x3)
-    size_t w_off = 0, b_off = 0;   // float offsets into wpk_dev
-    // F(4x4) layers also carry an F(2x2) packing for small maps (one 16 x 32-pixel block per CU does not fill
-    // the chip below ~64 x 64 pixels; measured at 32 x 60: 0.05 ms vs 0.14 ms)
-    int nt2 = 0, nblk2 = 0;
-    size_t w_off2 = 0, b_off2 = 0;
-    // ... and the weights split into three bf16 terms for the kernel on the bf16 matrix pipe (b2f_wino4s.hip); 0 = none
-    size_t w_off3 = 0;
-    size_t w_off4 = 0;             // F(2x2) split packing (b2f_wino2s.hip); 0 = none
-    size_t w_off5 = 0, b_off5 = 0; // direct layers: weights pre-split for the bf16-pipe kernel (b2f_convb.hip) + bias padded to 64; 0 = none
-    size_t w_off7 = 0, b_off7 = 0; // stride-2 layers: packing of the loader / consumer kernel (b2f_s2b.hip); 0 = none
-    size_t w_off8 = 0, b_off8 = 0; // F(4x4)-class layers: Winograd F(6x6) packing (b2f_wino6.hip); 0 = none
-    size_t w_off6 = 0, b_off6 = 0; // F(4x4)-class layers: 1-D Winograd F(4,3) packing for the bf16-pipe loader / consumer kernel (b2f_w1b.hip); 0 = none
+    int cout = 0;
+    ConvKernel base = K_DIRECT;    // the layer's kernel while no option and no map size sends a launch elsewhere (choose_kernel)
+    // One packing per kernel that may run the layer, offsets in floats into the weight buffer; nblk = 0: the layer has none.  Next to the base
+    // packing: F(4x4) layers carry an F(2x2) one for small maps (one 16 x 32-pixel block per CU does not fill the chip below ~64 x 64 pixels;
+    // measured at 32 x 60: 0.05 ms vs 0.14 ms), and the optional ones exist only while an option reads them.
+    struct Packing {
+        size_t w_off = 0, b_off = 0;
+        int nt = 0, nblk = 0;      // 32-wide N tiles per block, N blocks: the bias is nblk * nt * 32 floats
+    } pk[K_COUNT];
+    bool has(ConvKernel k) const { return pk[k].nblk != 0; }
+    int nchunks() const { return chunks[0] + (nseg > 1 ? chunks[1] : 0); }
+};
+
+// The options that decide which kernel runs a conv layer and how it is launched (b2f_set_option; seeded once from the environment in
+// b2f_init, never read from it on the hot path): what choose_kernel reads.  b2f_op_conv3x3 passes a copy with its overrides.
+struct KernelOpts {
+    int wino8 = 1;                 // F(2x2) one-N-tile launches of at most one block per CU run the eight-wave form (conv3x3_wino8; same bits)
+    int wino_split_pixels = 512;   // F(2x2) launches on maps of at most this many pixels run one block per 32-output N tile (same bits;
+                                   // level 7 of a full-HD triplet: 64 tiles per launch at batch 16 -- 0.25 -> 0.20 ms for its six layers)
+    int wino4_min_pixels = 4096;   // F(4x4) for maps of at least this many pixels, F(2x2) below: depends on the map size
+                                   // only, so a triplet's result does not depend on the batch it is computed in
+    int adaptive_kernels = -1;     // -1 (default): per launch for single-triplet calls, by map size for batches; 0: by map size always;
+                                   // 1: choose the Winograd variant per launch by block rounds on the 256 CUs (faster for
+                                   // single triplets / small batches; results then depend on the batch size at 1e-6 level)
+    int bf16_direct = 2;           // the 16-channel layers of the head on the bf16 matrix pipe with exactly split fp32 operands: 0 = fp32-MFMA kernels,
+                                   // 1 = the 16 -> 16 layer alone (b2f_conv16b.hip), 2 = 16 -> 16 + 16 -> 32 stride 2 fused, the map between them in LDS (b2f_head.hip)
+    int bf16_conv_min_pixels = 65536;   // bf16_conv = 2: 32-output stride-1 layers on maps of at least this many pixels leave the F(4x4) kernel
+    int bf16_conv = 1;             // 1 (default): the direct (stride-2) layers on the bf16 matrix pipe with split fp32 operands (b2f_convb.hip);
+                                   // 2: also the 32-output stride-1 layers of large maps, 3: every F(4x4)-class layer of large maps (experiments: measured
+                                   // slower than the F(4x4) kernel, profiles/r04_bf16_direct_notes.txt (4)); 0: fp32-MFMA kernel
+    int wino2_split = 0;           // F(4x4)-class layers, blocks of 64 outputs: 1 = Winograd F(2x2) on the bf16 matrix pipe with exactly split
+                                   // fp32 operands (b2f_wino2s.hip) on maps of at least wino4_min_pixels pixels
+    int wino4_hybrid = 0;          // F(4x4) two-N-tile blocks: this many of a wave's nine xi steps on the bf16 pipe with split operands (needs the
+                                   // split packing: setting it > 0 packs it); 0 = all on the fp32 MFMA
+    int wino4_split = 0;           // F(4x4) layers with two full N tiles per block: 1 = on the bf16 matrix pipe with exactly split fp32 operands
+                                   // (b2f_wino4s.hip; fp32-level accuracy, measured no faster: profiles/r04_wino4s_notes.txt), 0 = on the fp32 MFMA
+    int wino6 = 1;                 // F(4x4)-class layers on maps of at least wino6_min_pixels pixels: 1 = Winograd F(6x6,3x3) on the fp32 MFMA (csrc/b2f_wino6.hip):
+                                   // blocks of 64 outputs, a last block of 32 when the outputs are <= 32 mod 64
+    int wino6_min_pixels = 16384;  // ... below that the F(4x4) kernel (items of 12 x 48 pixels quantise small maps badly)
+    int wino1d = 0;                // F(4x4)-class layers (stride 1, more than 32 outputs, maps of at least wino4_min_pixels pixels): 1 = one-dimensional
+                                   // Winograd F(4,3) on the bf16 matrix pipe with exactly split fp32 operands, loader / consumer persistent blocks
+                                   // (b2f_w1b.hip); 0 = the fp32-MFMA F(4x4) kernel of rounds 1-4 (b2f_wino4.hip)
+    int s2_tile_groups = 1;        // ... launches that cannot fill the chip: one output tile per block (conv3x3_s2b<1, 1>, ConvLaunch::nsplit); same bits
+    int s2_loader = 1;             // stride-2 layers on the bf16 pipe (bf16_conv >= 1): 1 = those of at least 64 input channels on the loader / consumer kernel
+                                   // that computes all outputs of a tile (b2f_s2b.hip), 2 = all of them, 0 = conv3x3_bf6 (b2f_convb.hip)
+    int wino4_persistent = 1;      // F(4x4) kernel: 1 = persistent blocks (one per CU, K pipeline continues across tiles), 0 = one tile per block, > 1 = that many persistent blocks (tests)
+    int s2_tiles_per_block = 0;    // direct stride-2 kernel: tiles chained per block (0 = launcher's rule; bit-identical either way)
 };
 
 struct ProfEvent {
@@ -254,7 +305,7 @@ private:
 
 }  // namespace b2f
 
-struct b2f_ctx {
+struct b2f_ctx : b2f::KernelOpts {
     int device = 0;
     bool past_flow = false;
     b2f::GraphOpts g;           // graph shape (createModelMulti options); g.past_flow == past_flow
@@ -270,49 +321,16 @@ struct b2f_ctx {
     float *arena = nullptr;
     size_t arena_floats = 0;
     int wsB = 0, wsH = 0, wsW = 0;
-    // options
+    // options (b2f_set_option: kOptions in b2f_api.hip; those of the kernel choice are the KernelOpts base)
     int use_graph = 0, profile = 0;
     int host_graph = 1;   // b2f_compute_flow*: replay hipGraphs for repeated (shape, sub-batch) combinations
-    // kernel selection and pipeline tuning (b2f_set_option; seeded once from the environment in b2f_init, never read
-    // from it on the hot path)
-    int wino8 = 1;                 // F(2x2) one-N-tile launches of at most one block per CU run the eight-wave form (conv3x3_wino8; same bits)
-    int wino_split_pixels = 512;   // F(2x2) launches on maps of at most this many pixels run one block per 32-output N tile (same bits;
-                                   // level 7 of a full-HD triplet: 64 tiles per launch at batch 16 -- 0.25 -> 0.20 ms for its six layers)
-    int wino4_min_pixels = 4096;   // F(4x4) for maps of at least this many pixels, F(2x2) below: depends on the map size
-                                   // only, so a triplet's result does not depend on the batch it is computed in
     int cur_batch = 0;             // triplets of the REQUEST the forward pass being issued belongs to (run_conv's per-launch rule for single-triplet calls)
     int req_batch = 0;             // set by the host-buffer entry points to the caller's n while they issue their sub-batches (0: a forward call's own B):
                                    // the kernel choice follows the caller's request, so a triplet's bits do not depend on its position in a batch
-    int adaptive_kernels = -1;     // -1 (default): per launch for single-triplet calls, by map size for batches; 0: by map size always;
-                                   // 1: choose the Winograd variant per launch by block rounds on the 256 CUs (faster for
-                                   // single triplets / small batches; results then depend on the batch size at 1e-6 level)
     int corr_ablate = 0;           // profiling only, see CorrLaunch::ablate
     int corr_variant = -1;         // warp + cost volume: -1 auto, 0 regular, 1 latency variant (bit-identical results)
     int op_wino_split = 0;         // b2f_op_conv3x3: F(2x2) kernel with one block per 32-output N tile (tests)
     int profile_layers = 0;        // one profile row per (layer shape, map size)
-    int bf16_direct = 2;           // the 16-channel layers of the head on the bf16 matrix pipe with exactly split fp32 operands: 0 = fp32-MFMA kernels,
-                                   // 1 = the 16 -> 16 layer alone (b2f_conv16b.hip), 2 = 16 -> 16 + 16 -> 32 stride 2 fused, the map between them in LDS (b2f_head.hip)
-    int bf16_conv_min_pixels = 65536;   // bf16_conv = 2: 32-output stride-1 layers on maps of at least this many pixels leave the F(4x4) kernel
-    int bf16_conv = 1;             // 1 (default): the direct (stride-2) layers on the bf16 matrix pipe with split fp32 operands (b2f_convb.hip);
-                                   // 2: also the 32-output stride-1 layers of large maps, 3: every F(4x4)-class layer of large maps (experiments: measured
-                                   // slower than the F(4x4) kernel, profiles/r04_bf16_direct_notes.txt (4)); 0: fp32-MFMA kernel
-    int wino2_split = 0;           // F(4x4)-class layers, blocks of 64 outputs: 1 = Winograd F(2x2) on the bf16 matrix pipe with exactly split
-                                   // fp32 operands (b2f_wino2s.hip) on maps of at least wino4_min_pixels pixels
-    int wino4_hybrid = 0;          // F(4x4) two-N-tile blocks: this many of a wave's nine xi steps on the bf16 pipe with split operands (needs the
-                                   // split packing: setting it > 0 packs it); 0 = all on the fp32 MFMA
-    int wino4_split = 0;           // F(4x4) layers with two full N tiles per block: 1 = on the bf16 matrix pipe with exactly split fp32 operands
-                                   // (b2f_wino4s.hip; fp32-level accuracy, measured no faster: profiles/r04_wino4s_notes.txt), 0 = on the fp32 MFMA
-    int wino6 = 1;                 // F(4x4)-class layers on maps of at least wino6_min_pixels pixels: 1 = Winograd F(6x6,3x3) on the fp32 MFMA (csrc/b2f_wino6.hip):
-                                   // blocks of 64 outputs, a last block of 32 when the outputs are <= 32 mod 64
-    int wino6_min_pixels = 16384;  // ... below that the F(4x4) kernel (items of 12 x 48 pixels quantise small maps badly)
-    int wino1d = 0;                // F(4x4)-class layers (stride 1, more than 32 outputs, maps of at least wino4_min_pixels pixels): 1 = one-dimensional
-                                   // Winograd F(4,3) on the bf16 matrix pipe with exactly split fp32 operands, loader / consumer persistent blocks
-                                   // (b2f_w1b.hip); 0 = the fp32-MFMA F(4x4) kernel of rounds 1-4 (b2f_wino4.hip)
-    int s2_tile_groups = 1;        // ... launches that cannot fill the chip: one output tile per block (conv3x3_s2b<1, 1>, ConvLaunch::nsplit); same bits
-    int s2_loader = 1;             // stride-2 layers on the bf16 pipe (bf16_conv >= 1): 1 = those of at least 64 input channels on the loader / consumer kernel
-                                   // that computes all outputs of a tile (b2f_s2b.hip), 2 = all of them, 0 = conv3x3_bf6 (b2f_convb.hip)
-    int wino4_persistent = 1;      // F(4x4) kernel: 1 = persistent blocks (one per CU, K pipeline continues across tiles), 0 = one tile per block, > 1 = that many persistent blocks (tests)
-    int s2_tiles_per_block = 0;    // direct stride-2 kernel: tiles chained per block (0 = launcher's rule; bit-identical either way)
     long long host_subbatch_pixels = 16ll << 20;
     int host_threads = 0;          // 0 = auto
     int host_u8 = 1, host_ramp = 1;

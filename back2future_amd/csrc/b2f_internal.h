@@ -1,6 +1,6 @@
 // Internal C++ interface between the C-ABI layer (b2f_api.hip) and the gfx950
-// kernels (b2f_conv.hip, b2f_corr.hip, b2f_glue.hip).  Device layout everywhere:
-// NHWC ("BHWD") fp32; see DESIGN.md "Data layout in HBM".
+// kernels (b2f_conv*.hip, b2f_wino*.hip, b2f_corr*.hip, b2f_glue.hip, ...).  Activations on the device are
+// chunk-planar fp32 (see below and DESIGN.md "Data layout in HBM"); the kernels take strides, so the op-level entry points pass NHWC.
 #pragma once
 #include <hip/hip_runtime.h>
 // B2F_EXPERIMENTS=1 (python -m back2future_amd.build --experiments -> libb2f_exp.so): the kernels of tools/experiments/csrc -- forms that
