@@ -22,6 +22,8 @@ occ_threshold = 0.6666                                                     # bac
 
 # in_kind of the device entry points (include/b2f.h); IN_U8 is taken by the sequence and float32 entries only
 IN_NORMALIZED, IN_UNIT, IN_U8 = 0, 1, 2
+# layout of the flow pictures (include/b2f.h): n x 3 x H x W, the reference's tensor order, or n x H x W x 3
+RGB_PLANAR, RGB_PACKED = 0, 1
 
 
 def normalize(imgs):
@@ -148,6 +150,73 @@ def _compute_flow_sequence(prefix, h, frames, out, dtype, occ_prob):
         return _call_f32(prefix + "compute_flow_sequence_f32", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0,
                          _f32_outputs(T - 2, H0, W0, occ_prob, out, "computeFlowSequence"), occ_prob)
     return _call_f64(prefix + "compute_flow_sequence", h, T, as_bytes, (v,), H0, W0, _f64_outputs(T - 2, H0, W0, out))
+
+
+def rgb_max_norm(max, who):
+    """The `max=` keyword of the flow-picture wrappers as the library's max_norm: None (each picture's own maximum) -> 0, else a
+    positive number (flowX.xy2rgb's third argument).  Raises ValueError before any library call."""
+    if max is None:
+        return 0.0
+    try:
+        m = float(max)
+    except (TypeError, ValueError):
+        raise ValueError("%s: max must be None or a positive number, got %r" % (who, max))
+    if not m > 0.0:
+        raise ValueError("%s: max must be None or a positive number, got %r" % (who, max))
+    return m
+
+
+def _rgb_outputs(n, H0, W0, packed, want_flow, want_masks, out, who):
+    """(rgb, max_used, flow or None, fwd or None, bwd or None) for the rgb entries; out = (rgb, max_used[, flow][, fwd_occ, bwd_occ]),
+    the buffers the call returns (page-locked ones are written by DMA), or new arrays."""
+    spec = [(np.uint8, (n, H0, W0, 3) if packed else (n, 3, H0, W0)), (np.float64, (n,))]
+    spec += [(np.float32, (n, 2, H0, W0))] if want_flow else []
+    spec += [(np.uint8, (n, 1, H0, W0))] * 2 if want_masks else []
+    if out is None:
+        bufs = [np.empty(shape, dt) for dt, shape in spec]
+    else:
+        bufs = list(out)
+        if len(bufs) != len(spec):
+            raise ValueError("%s: out must be (rgb, max_used%s%s)" % (who, ", flow" if want_flow else "", ", fwd_occ, bwd_occ" if want_masks else ""))
+        for i, (a, (dt, shape)) in enumerate(zip(bufs, spec)):
+            if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
+                raise ValueError("%s: out[%d] must be a writeable C-contiguous %s array of shape %s" % (who, i, np.dtype(dt).name, shape))
+    rest = bufs[2:]
+    flow = rest.pop(0) if want_flow else None
+    fwd, bwd = rest if want_masks else (None, None)
+    return bufs[0], bufs[1], flow, fwd, bwd
+
+
+def _call_rgb(fn, h, count, in_kind, ins, H0, W0, max_norm, packed, outs):
+    rgb, mx, flow, fwd, bwd = outs
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+    _lib.check(getattr(_lib.lib(), fn)(h, count, in_kind, *[C.c_void_p(a.ctypes.data) for a in ins], H0, W0, max_norm,
+                                       RGB_PACKED if packed else RGB_PLANAR, u8p(rgb), mx.ctypes.data_as(C.POINTER(C.c_double)),
+                                       _lib.fptr(flow) if flow is not None else None, u8p(fwd), u8p(bwd)))
+    return tuple(a for a in outs if a is not None)
+
+
+def _compute_flow_batch_rgb(prefix, h, im1, im2, im3, max, packed, want_flow, want_masks, out):
+    """computeFlowBatchRGB of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    who = "computeFlowBatchRGB"
+    max_norm = rgb_max_norm(max, who)
+    arrs = [np.asarray(a) for a in (im1, im2, im3)]
+    if any(a.ndim != 4 or a.shape[1] != 3 or a.shape[0] < 1 for a in arrs) or len({a.shape for a in arrs}) > 1:
+        raise ValueError("%s: expected three n x 3 x H x W arrays of one shape" % who)
+    im1, im2, im3, as_bytes = _batch_inputs(*arrs)
+    n, _, H0, W0 = im1.shape
+    outs = _rgb_outputs(n, H0, W0, packed, want_flow, want_masks, out, who)
+    return _call_rgb(prefix + "compute_flow_batch_rgb", h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0, max_norm, packed, outs)
+
+
+def _compute_flow_sequence_rgb(prefix, h, frames, max, packed, want_flow, want_masks, out):
+    """computeFlowSequenceRGB of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    who = "computeFlowSequenceRGB"
+    max_norm = rgb_max_norm(max, who)
+    v, as_bytes = sequence_frames(frames)
+    T, _, H0, W0 = v.shape
+    outs = _rgb_outputs(T - 2, H0, W0, packed, want_flow, want_masks, out, who)
+    return _call_rgb(prefix + "compute_flow_sequence_rgb", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0, max_norm, packed, outs)
 
 
 class Model(object):
@@ -292,6 +361,31 @@ class Model(object):
         _lib.check(_lib.lib().b2f_compute_flow_sequence_device(self._h, int(T), int(in_kind), p(d_frames), int(H0), int(W0), p(d_flow),
                                                                 p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream)))
 
+    def computeFlowBatchRGB(self, im1, im2, im3, max=None, packed=False, want_flow=False, want_masks=False, out=None):
+        """computeFlowBatch with the flow pictures as the output (b2f_compute_flow_batch_rgb): returns (rgb, max_used[, flow]
+        [, fwd_occ, bwd_occ]).  rgb is flowX.xy2rgb(flow[1], flow[2], max) of every triplet as bytes, n x 3 x H x W or, with
+        packed=True, n x H x W x 3 (what PNG and video encoders take); max=None scales every picture by its own largest flow,
+        and max_used (float64, n) is the maximum of each.  want_flow / want_masks append the float32 flow and the masks of
+        computeFlowBatch(dtype=np.float32); what is not asked for is not downloaded.  Inputs as for computeFlowBatch;
+        out = the returned tuple's buffers (page-locked ones are written by DMA)."""
+        return _compute_flow_batch_rgb("b2f_", self._h, im1, im2, im3, max, packed, want_flow, want_masks, out)
+
+    def computeFlowSequenceRGB(self, frames, max=None, packed=False, want_flow=False, want_masks=False, out=None):
+        """computeFlowSequence with the flow pictures as the output (b2f_compute_flow_sequence_rgb): one picture per centre
+        frame; keywords and results as for computeFlowBatchRGB with n = T - 2."""
+        return _compute_flow_sequence_rgb("b2f_", self._h, frames, max, packed, want_flow, want_masks, out)
+
+    def flowRGBDevice(self, d_flow, n, H, W, d_rgb, max=None, packed=False, d_max_used=None, stream=None):
+        """b2f_flow_rgb_device on device pointers (ints): the pictures of an n x 2 x H x W float32 flow into d_rgb (n x 3 x H x W
+        bytes, or n x H x W x 3 with packed), d_max_used (n float64) optional.  Asynchronous on `stream`: after
+        computeFlowDevice on the same stream it needs no synchronisation in between."""
+        max_norm = rgb_max_norm(max, "flowRGBDevice")
+        if n < 1 or H < 1 or W < 1:
+            raise ValueError("flowRGBDevice: bad shape %r" % ((n, H, W),))
+        p = lambda v: C.c_void_p(v) if v else None
+        _lib.check(_lib.lib().b2f_flow_rgb_device(self._h, p(d_flow), int(n), int(H), int(W), max_norm, RGB_PACKED if packed else RGB_PLANAR,
+                                                   p(d_rgb), p(d_max_used), p(stream)))
+
     def output_shapes(self, H, W):
         cap = 32
         ch, oh, ow = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
@@ -370,6 +464,14 @@ class MultiModel(object):
         """Model.computeFlowSequence over the GPUs: the T-2 triplets are split with shard_range, every replica reads the
         frames its triplets need (T_i = its triplets + 2).  dtype / occ_prob / out as for Model.computeFlowSequence."""
         return _compute_flow_sequence("b2f_multi_", self._h, frames, out, dtype, occ_prob)
+
+    def computeFlowBatchRGB(self, im1, im2, im3, max=None, packed=False, want_flow=False, want_masks=False, out=None):
+        """Model.computeFlowBatchRGB over the GPUs, with the same keywords and the same bytes."""
+        return _compute_flow_batch_rgb("b2f_multi_", self._h, im1, im2, im3, max, packed, want_flow, want_masks, out)
+
+    def computeFlowSequenceRGB(self, frames, max=None, packed=False, want_flow=False, want_masks=False, out=None):
+        """Model.computeFlowSequenceRGB over the GPUs, with the same keywords and the same bytes."""
+        return _compute_flow_sequence_rgb("b2f_multi_", self._h, frames, max, packed, want_flow, want_masks, out)
 
 
 def shard_range(n, rank, world):

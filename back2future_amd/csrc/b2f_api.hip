@@ -835,7 +835,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1000; }
+int b2f_version(void) { return 1001; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1005,6 +1005,7 @@ void b2f_destroy(b2f_ctx *c)
     if (c->s_in) (void)hipStreamDestroy(c->s_in);
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
     if (c->dwork.dev) (void)hipFree(c->dwork.dev);
+    if (c->vis_max.dev) (void)hipFree(c->vis_max.dev);
     if (c->arena) (void)hipFree(c->arena);
     if (c->wpk_dev) (void)hipFree(c->wpk_dev);
     if (c->w_dev) (void)hipFree(c->w_dev);

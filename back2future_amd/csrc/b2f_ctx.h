@@ -127,27 +127,45 @@ struct HostSlot {
     float *d_occ = nullptr;          // f32 path of a Hard model with occ_prob: skip_occs[3] at the network size (Soft: it is d_est3)
     float *d_prob = nullptr;         // f32 path: occ_prob at H0 x W0; unused without a rescale (the network's planes go down as they are)
     unsigned char *d_fo = nullptr, *d_bo = nullptr;
+    unsigned char *d_rgb = nullptr;  // rgb requests: the pictures of the sub-batch (3 bytes per pixel) ...
+    double *d_max = nullptr;         // ... and the maximum every one of them was scaled with
     unsigned char *h_u8 = nullptr;
     float *h_in = nullptr, *h_flow32 = nullptr, *h_prob = nullptr;
-    unsigned char *h_fo = nullptr, *h_bo = nullptr;
+    unsigned char *h_fo = nullptr, *h_bo = nullptr, *h_rgb = nullptr;
+    double *h_max = nullptr;
     hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
 };
 
 // Where computeFlow's outputs go (host pointers for b2f_compute_flow*, device pointers for b2f_compute_flow*_device).  The
 // f64 path (flow64, both masks required) is the b2f_compute_flow* entries'; the f32 path (flow32) writes the same flow
-// rounded to fp32 and, when not nullptr, the occlusion probabilities and the masks.
+// rounded to fp32 and, when not nullptr, the occlusion probabilities and the masks.  rgb (f32 path only): the flow pictures of
+// b2f_compute_flow*_rgb (xy2rgb of the f32 flow, launch_flow_rgb) in rgb_layout with max_norm, rgb_max their maxima; the flow itself
+// is then optional.
 struct FlowOutputs {
     double *flow64 = nullptr;
     float *flow32 = nullptr, *occ_prob = nullptr;
     unsigned char *fwd_occ = nullptr, *bwd_occ = nullptr;
+    unsigned char *rgb = nullptr;
+    double *rgb_max = nullptr;
+    double max_norm = 0.0;
+    int rgb_layout = B2F_RGB_PLANAR;
+    bool pictures = false;         // an rgb request: rgb is required (check_request), flow32 is not
     bool f32() const { return flow64 == nullptr; }
     // the outputs of triplets b, b + 1, ... (planes of hw0 pixels); nullptr stays nullptr
     FlowOutputs from_triplet(size_t b, size_t hw0) const
     {
         auto at = [](auto *p, size_t off) { return p ? p + off : p; };
-        return {at(flow64, b * 2 * hw0), at(flow32, b * 2 * hw0), at(occ_prob, b * 2 * hw0), at(fwd_occ, b * hw0), at(bwd_occ, b * hw0)};
+        return {at(flow64, b * 2 * hw0), at(flow32, b * 2 * hw0), at(occ_prob, b * 2 * hw0), at(fwd_occ, b * hw0), at(bwd_occ, b * hw0),
+                at(rgb, b * 3 * hw0), at(rgb_max, b), max_norm, rgb_layout, pictures};
     }
 };
+
+// the outputs of a b2f_*compute_flow_*_rgb entry
+inline FlowOutputs rgb_outputs(unsigned char *rgb, double *max_used, double max_norm, int layout, float *flow, unsigned char *fwd_occ,
+                               unsigned char *bwd_occ)
+{
+    return {nullptr, flow, nullptr, fwd_occ, bwd_occ, rgb, max_used, max_norm, layout, true};
+}
 
 // One computeFlow call, whichever of the entry points it came through: n triplets (im1..im3, n x 3 x H0 x W0 each) or, with seq, the
 // n + 2 frames of a sequence in im1; inputs B2F_IN_UNIT (floats in [0,1]) or B2F_IN_U8 (bytes).  req: the request's triplet count the
@@ -350,6 +368,7 @@ struct b2f_ctx : b2f::KernelOpts {
     b2f::HostSlot slot[2];
     std::unique_ptr<b2f::CopyPool> pool_in, pool_out;
     b2f::DevWork dwork;           // b2f_compute_flow_device / b2f_compute_flow_sequence_device
+    b2f::DevWork vis_max;         // b2f_flow_rgb_device without dev_max_used: the per-image maxima of the automatic mode
 };
 
 #define HIPCHK(expr)                                                                         \

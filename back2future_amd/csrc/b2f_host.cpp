@@ -2,6 +2,7 @@
 // the canonical weight layout.  No GPU code here (the pre/post-processing that back2future.lua
 // does around model:forward runs on the device, b2f_boundary.hip).
 #include "b2f_host.h"
+#include "b2f_flowcolor.h"
 
 #include <cmath>
 #include <cstdio>
@@ -138,6 +139,39 @@ void random_weights(unsigned long long seed, const GraphOpts &o, float gain, flo
             const float u = (float)(z >> 40) * (1.0f / 16777216.0f);
             const float t = 2.0f * u - 1.0f;
             out[d.w_off + i] = t * s;
+        }
+    }
+}
+
+}  // namespace b2f
+
+// ---- flow pictures on the CPU ---------------------------------------------------------------------------------------------------
+namespace b2f {
+
+void flow_rgb_host(const float *flow, int n, int H, int W, double max_norm, bool packed, unsigned char *rgb, double *max_used)
+{
+    const size_t hw = (size_t)H * W;
+    for (int b = 0; b < n; ++b) {
+        const float *fx = flow + (size_t)b * 2 * hw, *fy = fx + hw;
+        const bool saturate = max_norm > 0.0;
+        double m = max_norm;
+        if (!saturate) {
+            m = 0.0;
+            for (size_t i = 0; i < hw; ++i) {
+                const double v = flow_norm((double)fx[i], (double)fy[i]);
+                if (v > m) m = v;
+            }
+        }
+        if (!(m > 1e-2)) m = 1e-2;
+        if (max_used) max_used[b] = m;
+        unsigned char *o = rgb + (size_t)b * 3 * hw;
+        for (size_t i = 0; i < hw; ++i) {
+            const Rgb8 c = flow_color((double)fx[i], (double)fy[i], m, saturate);
+            if (packed) {
+                o[3 * i] = c.r; o[3 * i + 1] = c.g; o[3 * i + 2] = c.b;
+            } else {
+                o[i] = c.r; o[hw + i] = c.g; o[2 * hw + i] = c.b;
+            }
         }
     }
 }

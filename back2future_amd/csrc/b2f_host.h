@@ -64,6 +64,10 @@ std::vector<ConvDesc> weight_layout(bool past_flow, long long *total);
 long long param_count(bool past_flow);
 void random_weights(unsigned long long seed, bool past_flow, float gain, float *out);
 
+// xy2rgb of a planar n x 2 x H x W fp32 flow on the CPU (b2f_flowcolor.h per pixel; b2f_flow_rgb_host): rgb n x 3 x H x W bytes, or
+// n x H x W x 3 with packed; max_norm > 0 = the maximum of every image, else each image's own; max_used: n doubles or nullptr
+void flow_rgb_host(const float *flow, int n, int H, int W, double max_norm, bool packed, unsigned char *rgb, double *max_used);
+
 // .t7 reader (b2f_t7.cpp): returns false and fills err on failure.
 bool load_t7(const std::string &path, std::vector<float> &flat, bool &past_flow, std::string &err);
 // any graph shape: infer = true takes win / levels / skip from the file, false checks the file against g (see b2f_t7.cpp)

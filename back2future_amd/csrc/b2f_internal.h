@@ -323,4 +323,11 @@ hipError_t launch_outputs_f32(const float *flow_net, const float *occ, const flo
 // out[i] = in[i] / 255 (correctly rounded): device end of the 8-bit input transport
 hipError_t launch_unpack_u8(const unsigned char *in, size_t n, float *out, hipStream_t s);
 
+// ---- flow pictures (b2f_vis.hip; the per-pixel function: b2f_flowcolor.h) --------------------
+// xy2rgb of a planar n x 2 x H x W fp32 flow into bytes, layout B2F_RGB_PLANAR / B2F_RGB_PACKED.  max_norm > 0: every image
+// saturates at that maximum (max_used, when not nullptr, receives it); max_norm <= 0: the per-image maximum of the norm is
+// reduced into max_used (n doubles, required then) first, on the same stream
+hipError_t launch_flow_rgb(const float *flow, int n, int H, int W, double max_norm, int layout, unsigned char *rgb, double *max_used,
+                           hipStream_t s);
+
 }  // namespace b2f

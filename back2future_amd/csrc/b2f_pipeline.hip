@@ -41,6 +41,9 @@ struct SlotNeeds {
     bool prob;         // d_prob: occ_prob at H0 x W0 (f32 path with occ_prob and a rescale)
     bool stage_flow;   // h_flow32: the f64 path always, the f32 path for a pageable flow buffer
     bool stage_prob;   // h_prob: pageable occ_prob buffer
+    bool rgb;          // d_rgb, d_max: an rgb request
+    bool stage_rgb;    // h_rgb: pageable rgb buffer
+    bool stage_max;    // h_max: pageable max_used buffer
 };
 
 // carve the slot's device and pinned blobs for sub-batches of up to SB triplets; grows (never shrinks) the blobs
@@ -52,7 +55,8 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
                  n_flow = align256((size_t)SB * 2 * hw * 4), n_est3 = align256((size_t)SB * C3 * hw * 4),
                  n_f32 = align256((size_t)SB * 2 * hw0 * 4), n_occ = align256((size_t)SB * hw0);
     const size_t n_onet = q.occ_net ? n_flow : 0, n_prob = q.prob ? n_f32 : 0;
-    const size_t need_dev = n_up + n_u8 + n_in + n_tmp + n_flow + n_est3 + (same ? 0 : n_f32) + n_onet + n_prob + 2 * n_occ;
+    const size_t n_rgb = q.rgb ? align256((size_t)SB * 3 * hw0) : 0, n_max = q.rgb ? align256((size_t)SB * sizeof(double)) : 0;
+    const size_t need_dev = n_up + n_u8 + n_in + n_tmp + n_flow + n_est3 + (same ? 0 : n_f32) + n_onet + n_prob + 2 * n_occ + n_rgb + n_max;
     if (need_dev > hs.dev_bytes) {
         if (hs.dev) {
             HIPCHK(hipDeviceSynchronize());
@@ -74,9 +78,12 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.d_occ = q.occ_net ? (float *)d : nullptr; d += n_onet;
     hs.d_prob = q.prob ? (float *)d : nullptr; d += n_prob;
     hs.d_fo = (unsigned char *)d; d += n_occ;
-    hs.d_bo = (unsigned char *)d;
+    hs.d_bo = (unsigned char *)d; d += n_occ;
+    hs.d_rgb = q.rgb ? (unsigned char *)d : nullptr; d += n_rgb;
+    hs.d_max = q.rgb ? (double *)d : nullptr;
     const size_t n_hf = q.stage_flow ? n_f32 : 0, n_hp = q.stage_prob ? n_f32 : 0;
-    const size_t need_pin = (q.stage_in ? n_up : 0) + n_u8 + n_hf + n_hp + (q.stage_masks ? 2 * n_occ : 0);
+    const size_t n_hr = q.stage_rgb ? n_rgb : 0, n_hm = q.stage_max ? n_max : 0;
+    const size_t need_pin = (q.stage_in ? n_up : 0) + n_u8 + n_hf + n_hp + (q.stage_masks ? 2 * n_occ : 0) + n_hr + n_hm;
     if (need_pin > hs.pin_bytes) {
         if (hs.pin) {
             HIPCHK(hipDeviceSynchronize());
@@ -92,7 +99,9 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.h_flow32 = (float *)h; h += n_hf;
     hs.h_prob = (float *)h; h += n_hp;
     hs.h_fo = (unsigned char *)h; h += q.stage_masks ? n_occ : 0;
-    hs.h_bo = (unsigned char *)h;
+    hs.h_bo = (unsigned char *)h; h += q.stage_masks ? n_occ : 0;
+    hs.h_rgb = (unsigned char *)h; h += n_hr;
+    hs.h_max = (double *)h;
     for (hipEvent_t *e : {&hs.ev_in, &hs.ev_comp, &hs.ev_out})
         if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return 0;
@@ -151,6 +160,7 @@ struct NetBuffers {
 // size only, B2F_IN_U8 bytes.  ColorNormalize, then image.scale to the /64 size (:50-71) -- without a rescale the raw planes go to the
 // network as they are and the first conv kernel normalizes on the fly --, the forward pass, and outputs_f32_kernel into `out` (device
 // buffers at H0 x W0; nullptr: not written).  The flow of an f64 request is left unscaled: the host threads form `double * sc` (:80-84).
+// out.rgb: the pictures of that f32 flow (xy2rgb, b2f_vis.hip), read from out.flow32 or, at the network size, from net.flow itself.
 int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void *x, int kind, long planes, int nb, const NetBuffers &net,
                 const FlowOutputs &out, bool graph, hipStream_t s)
 {
@@ -163,6 +173,10 @@ int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void 
     const bool f32 = r.o.f32();
     HIPCHK(launch_outputs_f32(net.flow, g.C3 == 3 ? net.occ : net.est3, net.est3, g.C3, nb, g.fh, g.fw, g.H0, g.W0, f32 ? g.sc_w : 1.0,
                               f32 ? g.sc_h : 1.0, out.flow32, out.occ_prob, out.fwd_occ, out.bwd_occ, s));
+    if (out.rgb) {
+        if (!out.flow32 && !g.same) return fail(std::string(r.who) + ": a picture of a rescaled flow needs the flow buffer");
+        HIPCHK(launch_flow_rgb(out.flow32 ? out.flow32 : net.flow, nb, g.H0, g.W0, out.max_norm, out.rgb_layout, out.rgb, out.rgb_max, s));
+    }
     return 0;
 }
 
@@ -188,7 +202,11 @@ int b2f::check_request(const FlowRequest &r)
     if (r.n <= 0 || r.H0 <= 0 || r.W0 <= 0) return fail(w + ": bad shape");
     if (r.H0 < 64 || r.W0 < 64) return fail(w + ": image smaller than 64 pixels");
     const FlowOutputs &o = r.o;
-    if (!r.im1 || (!r.seq && (!r.im2 || !r.im3)) || (o.f32() ? !o.flow32 : !o.fwd_occ || !o.bwd_occ)) return fail(w + ": null argument");
+    // an rgb request (f32 path) needs its pictures and may leave the flow out
+    if (!r.im1 || (!r.seq && (!r.im2 || !r.im3)) || (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : !o.flow32))
+        return fail(w + ": null argument");
+    if (o.pictures && (!o.f32() || (o.rgb_layout != B2F_RGB_PLANAR && o.rgb_layout != B2F_RGB_PACKED)))
+        return fail(w + ": bad layout (B2F_RGB_PLANAR or B2F_RGB_PACKED)");
     return 0;
 }
 
@@ -210,7 +228,9 @@ int b2f::check_request(const FlowRequest &r)
 // triplet pipeline with "frame" in place of "triplet" as the unit of upload, 8-bit detection and the sub-batch budget.
 // Outputs (FlowOutputs): the f64 path widens the flow on the host threads; the f32 path (b2f_*_f32) has the device write
 // every output in its final form (outputs_f32_kernel), so the drain step only copies -- or nothing at all: page-locked
-// flow / occ_prob / mask buffers are DMA'd in place -- and a NULL occ_prob or mask is neither written nor downloaded.
+// flow / occ_prob / mask buffers are DMA'd in place -- and a NULL occ_prob or mask is neither written nor downloaded.  The pictures
+// and maxima of an rgb request (b2f_*_rgb) travel like occ_prob: slot buffers, DMA in place or staging + drain copy; its flow stays
+// on the device unless asked for.
 int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
 {
     CHK(check_context(c, r));
@@ -230,9 +250,10 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
     unsigned char *fwd_occ = o.fwd_occ, *bwd_occ = o.bwd_occ;
     // unrequested outputs (f32 path) count as page-locked: nothing is staged for them
     auto out_kind = [&](const void *p, size_t bytes) { return p ? mem_kind(p, bytes) : 1; };
-    const int k_out[4] = {f32 ? out_kind(o.flow32, (size_t)n * 2 * hw0 * 4) : mem_kind(flow, (size_t)n * 2 * hw0 * 8), out_kind(fwd_occ, (size_t)n * hw0),
-                          out_kind(bwd_occ, (size_t)n * hw0), out_kind(o.occ_prob, (size_t)n * 2 * hw0 * 4)};
-    for (int i = 0; i < 4; ++i)
+    const int k_out[6] = {f32 ? out_kind(o.flow32, (size_t)n * 2 * hw0 * 4) : mem_kind(flow, (size_t)n * 2 * hw0 * 8), out_kind(fwd_occ, (size_t)n * hw0),
+                          out_kind(bwd_occ, (size_t)n * hw0), out_kind(o.occ_prob, (size_t)n * 2 * hw0 * 4), out_kind(o.rgb, (size_t)n * 3 * hw0),
+                          out_kind(o.rgb_max, (size_t)n * sizeof(double))};
+    for (int i = 0; i < 6; ++i)
         if ((i < 3 && k_in[i] < 0) || k_out[i] < 0)
             return fail(w + ": device memory passed to a host-buffer entry point (use b2f_compute_flow_device / "
                             "b2f_compute_flow_sequence_device)");
@@ -254,7 +275,9 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
     const bool stage_masks = !(k_out[1] == 1 && k_out[2] == 1);
     const bool want_prob = f32 && o.occ_prob;
     // f32 path: occ_prob is skip_occs[3] -- est[3] of a Soft model (d_est3), an extra forward output of a Hard one (d_occ)
-    SlotNeeds q{same, stage_in, stage_masks, use_u8, want_prob && g.C3 == 3, want_prob && !same, !f32 || k_out[0] != 1, want_prob && k_out[3] != 1};
+    const bool want_rgb = o.rgb != nullptr;
+    SlotNeeds q{same, stage_in, stage_masks, use_u8, want_prob && g.C3 == 3, want_prob && !same, !f32 || k_out[0] != 1, want_prob && k_out[3] != 1,
+                want_rgb, want_rgb && k_out[4] != 1, want_rgb && k_out[5] != 1};
     // (a sequence sub-batch's nb + 2 frames are 3 nb + 6 <= 9 nb planes: the triplet layout of the slot holds them)
     for (int k = 0; k < std::min(nsub, 2); ++k)
         CHK(ensure_slot(c, c->slot[k], SB, hw0, g.hw, g.H0, g.fw, g.C3, q));
@@ -296,6 +319,8 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
                 } else {
                     if (q.stage_flow) jobs.push_back({o.flow32 + b0 * 2 * hw0, hs.h_flow32, nb * 2 * hw0 * 4});
                     if (q.stage_prob) jobs.push_back({o.occ_prob + b0 * 2 * hw0, hs.h_prob, nb * 2 * hw0 * 4});
+                    if (q.stage_rgb) jobs.push_back({o.rgb + b0 * 3 * hw0, hs.h_rgb, nb * 3 * hw0});
+                    if (q.stage_max) jobs.push_back({o.rgb_max + b0, hs.h_max, nb * sizeof(double)});
                 }
                 if (stage_masks) {
                     if (fwd_occ) jobs.push_back({fwd_occ + b0 * hw0, hs.h_fo, nb * hw0});
@@ -396,7 +421,8 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
         const float *occ_net = g.C3 == 3 ? hs.d_occ : hs.d_est3;
         CHK(run_kernels(c, r, g, direct_u8 ? (const void *)hs.d_u8 : hs.d_up, direct_u8 ? B2F_IN_U8 : B2F_IN_UNIT, (long)nu * fpu * 3, nb,
                         {hs.d_tmp, hs.d_in, hs.d_flow, hs.d_occ, hs.d_est3},
-                        {nullptr, same ? nullptr : hs.d_flow32, q.prob ? hs.d_prob : nullptr, fwd_occ ? hs.d_fo : nullptr, bwd_occ ? hs.d_bo : nullptr},
+                        {nullptr, same ? nullptr : hs.d_flow32, q.prob ? hs.d_prob : nullptr, fwd_occ ? hs.d_fo : nullptr, bwd_occ ? hs.d_bo : nullptr,
+                         hs.d_rgb, hs.d_max, o.max_norm, o.rgb_layout},
                         c->host_graph != 0, c->stream));
         HIPCHK(hipEventRecord(hs.ev_comp, c->stream));
         // ---- download: the set's pinned output buffers must have been handed over (k - 2 drained)
@@ -406,8 +432,13 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
             if (abort) return fail(drain_err);
         }
         HIPCHK(hipStreamWaitEvent(c->s_out, hs.ev_comp, 0));
-        HIPCHK(hipMemcpyAsync(q.stage_flow ? hs.h_flow32 : o.flow32 + b0 * 2 * hw0, hs.d_flow32, (size_t)nb * 2 * hw0 * 4, hipMemcpyDeviceToHost,
-                              c->s_out));
+        if (!f32 || o.flow32)   // an rgb request may leave the flow on the device
+            HIPCHK(hipMemcpyAsync(q.stage_flow ? hs.h_flow32 : o.flow32 + b0 * 2 * hw0, hs.d_flow32, (size_t)nb * 2 * hw0 * 4, hipMemcpyDeviceToHost,
+                                  c->s_out));
+        if (want_rgb)
+            HIPCHK(hipMemcpyAsync(q.stage_rgb ? hs.h_rgb : o.rgb + b0 * 3 * hw0, hs.d_rgb, (size_t)nb * 3 * hw0, hipMemcpyDeviceToHost, c->s_out));
+        if (o.rgb_max)
+            HIPCHK(hipMemcpyAsync(q.stage_max ? hs.h_max : o.rgb_max + b0, hs.d_max, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, c->s_out));
         if (want_prob)
             HIPCHK(hipMemcpyAsync(q.stage_prob ? hs.h_prob : o.occ_prob + b0 * 2 * hw0, same ? occ_net : hs.d_prob, (size_t)nb * 2 * hw0 * 4,
                                   hipMemcpyDeviceToHost, c->s_out));
@@ -580,6 +611,22 @@ int b2f_compute_flow_sequence_f32(b2f_ctx *c, int T, int in_kind, const void *fr
     return compute_flow_host(c, sequence_request(__func__, T, in_kind, frames, H0, W0, {nullptr, flow, occ_prob, fwd_occ, bwd_occ}));
 }
 B2F_CATCH("b2f_compute_flow_sequence_f32")
+
+int b2f_compute_flow_batch_rgb(b2f_ctx *c, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0, double max_norm,
+                               int layout, unsigned char *rgb, double *max_used, float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0,
+                                              rgb_outputs(rgb, max_used, max_norm, layout, flow, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_batch_rgb")
+
+int b2f_compute_flow_sequence_rgb(b2f_ctx *c, int T, int in_kind, const void *frames, int H0, int W0, double max_norm, int layout,
+                                  unsigned char *rgb, double *max_used, float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, sequence_request(__func__, T, in_kind, frames, H0, W0,
+                                                 rgb_outputs(rgb, max_used, max_norm, layout, flow, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_sequence_rgb")
 
 int b2f_compute_flow_device(b2f_ctx *c, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, int H0, int W0,
                             float *dev_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream) try

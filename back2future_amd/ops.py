@@ -1,6 +1,8 @@
 """Op-level calls through the C ABI, in the layouts of the reference modules
 (nn.CostVolMulti, nn.BilinearSamplerBHWD, nn.SpatialConvolution, ...).  Used by the parity
 tests; every call runs the HIP kernels of libb2f.so."""
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -100,3 +102,28 @@ def costvol_backward(model, ref, frm, grad_out, win=9, fwd=True):
     _lib.check(_lib.lib().b2f_op_costvol_backward(_h(model), _lib.fptr(ref), _lib.fptr(frm), _lib.fptr(grad_out), B, Cc, h, w, win,
                                                    int(bool(fwd)), _lib.fptr(gr), _lib.fptr(gf)))
     return gr, gf
+
+
+def flow_rgb(flow, max=None, packed=False, model=None):
+    """flowX.xy2rgb(flow[1], flow[2], max) (flowExtensions.lua:123-148) as bytes: flow 2 x H x W or n x 2 x H x W float32 ->
+    (rgb uint8, max_used float64[n]); rgb is [n x] 3 x H x W or, with packed, [n x] H x W x 3.  max=None scales every image by
+    its own largest norm.  model=None computes on the CPU (b2f_flow_rgb_host, no GPU), a Model on its GPU (b2f_op_flow_rgb)."""
+    from .back2future import RGB_PACKED, RGB_PLANAR, rgb_max_norm
+    max_norm = rgb_max_norm(max, "flow_rgb")
+    f = np.asarray(flow)
+    single = f.ndim == 3
+    if single:
+        f = f[None]
+    if f.ndim != 4 or f.shape[1] != 2 or min(f.shape) < 1:
+        raise ValueError("flow_rgb: expected a 2 x H x W or n x 2 x H x W flow, got shape %r" % (np.shape(flow),))
+    f = _lib.f32(f)
+    n, _, H, W = f.shape
+    rgb = np.empty((n, H, W, 3) if packed else (n, 3, H, W), np.uint8)
+    mx = np.empty(n, np.float64)
+    args = (_lib.fptr(f), n, H, W, max_norm, RGB_PACKED if packed else RGB_PLANAR, rgb.ctypes.data_as(C.POINTER(C.c_ubyte)),
+            mx.ctypes.data_as(C.POINTER(C.c_double)))
+    if model is None:
+        _lib.check(_lib.lib().b2f_flow_rgb_host(*args))
+    else:
+        _lib.check(_lib.lib().b2f_op_flow_rgb(_h(model), *args))
+    return (rgb[0] if single else rgb), mx

@@ -3,10 +3,11 @@
  *
  *   gcc -std=c99 -O2 -Iinclude examples/compute_flow.c -o compute_flow \
  *       -Lback2future_amd -lb2f -Wl,-rpath,$PWD/back2future_amd -Wl,-rpath,/opt/rocm/lib -L/opt/rocm/lib -lamdhip64
- *   ./compute_flow <model: name | path.t7 | random:hard|soft[:seed[:gain]]> <in.raw> <H> <W> <out.raw>
+ *   ./compute_flow <model: name | path.t7 | random:hard|soft[:seed[:gain]]> <in.raw> <H> <W> <out.raw> [flow.ppm]
  *
  * in.raw : three 3 x H x W planar RGB float32 images in [0,1] (im1, im2, im3), little endian
  * out.raw: flow 2 x H x W float64, then fwd_occ H x W bytes, then bwd_occ H x W bytes
+ * flow.ppm (optional): the flow picture, flowX.xy2rgb(flow[1], flow[2]) of the flow as float32 (b2f_flow_rgb_host: no GPU)
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -21,8 +22,8 @@ static int die(const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc != 6) {
-        fprintf(stderr, "usage: %s <model> <in.raw> <H> <W> <out.raw>\n", argv[0]);
+    if (argc != 6 && argc != 7) {
+        fprintf(stderr, "usage: %s <model> <in.raw> <H> <W> <out.raw> [flow.ppm]\n", argv[0]);
         return 2;
     }
     const int H = atoi(argv[3]), W = atoi(argv[4]);
@@ -55,6 +56,21 @@ int main(int argc, char **argv)
         return 3;
     }
     fclose(f);
+    if (argc == 7) {
+        /* the reference's next step (README.md:61-63): the picture of the flow, packed RGB = the body of a binary PPM */
+        float *flow32 = (float *)malloc(2 * hw * sizeof(float));
+        unsigned char *rgb = (unsigned char *)malloc(3 * hw);
+        if (!flow32 || !rgb) return 3;
+        for (size_t i = 0; i < 2 * hw; ++i) flow32[i] = (float)flow[i];
+        if (b2f_flow_rgb_host(flow32, 1, H, W, 0.0, B2F_RGB_PACKED, rgb, NULL)) return die("b2f_flow_rgb_host");
+        f = fopen(argv[6], "wb");
+        if (!f || fprintf(f, "P6\n%d %d\n255\n", W, H) < 0 || fwrite(rgb, 1, 3 * hw, f) != 3 * hw) {
+            fprintf(stderr, "cannot write %s\n", argv[6]);
+            return 3;
+        }
+        fclose(f);
+        free(flow32); free(rgb);
+    }
     free(im); free(flow); free(occ);
     return 0;
 }

@@ -4,10 +4,13 @@ frame that has a neighbour on both sides.  Every frame is uploaded and run throu
 (Model.computeFlowSequence); output t is computeFlow(frame[t-1], frame[t], frame[t+1]) bit for bit.  The flow comes from the
 float32 entry (dtype=np.float32: the float64 flow rounded to float32, which is what a .flo file stores).
 
-Usage: python examples/run_sequence.py DIR OUT/ [model] [--occ-prob]
+Usage: python examples/run_sequence.py DIR OUT/ [model] [--occ-prob] [--rgb [MAX]] [--flo]
 model: 'Ours-Hard' | 'Ours-Soft-ft-KITTI' | 'Ours-Soft-ft-Sintel' (needs models/RoamingImages_*.t7 in the current
 directory, as in the reference) or 'random:soft' / a .t7 / .b2fw path (default 'Ours-Soft-ft-KITTI').
 --occ-prob: also write the occlusion probabilities of every centre frame as a 2 x H x W float32 .npy file.
+--rgb [MAX]: write the flow picture of every centre frame (flowX.xy2rgb, coloured on the GPU: Model.computeFlowSequenceRGB) as
+a PNG instead; MAX is xy2rgb's `max` (default: every picture's own largest flow).  Only the pictures are downloaded; --flo
+writes the .flo files and masks as well.
 """
 import os
 import sys
@@ -22,8 +25,20 @@ EXTS = (".png", ".jpg", ".jpeg", ".ppm", ".bmp")
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--occ-prob"]
-    want_occ = len(args) < len(sys.argv) - 1
+    args = list(sys.argv[1:])
+    want_occ, want_flo, want_rgb, rgb_max = "--occ-prob" in args, "--flo" in args, "--rgb" in args, None
+    if want_rgb:
+        i = args.index("--rgb")
+        try:
+            rgb_max = float(args[i + 1])
+            del args[i + 1]
+        except (IndexError, ValueError):
+            pass
+        if rgb_max is not None and not rgb_max > 0:
+            sys.exit("--rgb MAX: MAX must be positive")
+        if want_occ:
+            sys.exit("--rgb and --occ-prob cannot be combined")
+    args = [a for a in args if a not in ("--occ-prob", "--flo", "--rgb")]
     if len(args) < 2:
         sys.exit(__doc__)
     src, out = args[0], args[1]
@@ -34,6 +49,19 @@ def main():
     frames = np.stack([flow_io.load_image(os.path.join(src, f)) for f in names])
     os.makedirs(out, exist_ok=True)
     m = back2future.Model(model)
+    if want_rgb:
+        from PIL import Image
+        res = m.computeFlowSequenceRGB(frames, max=rgb_max, packed=True, want_flow=want_flo, want_masks=want_flo)
+        for i in range(len(names) - 2):
+            stem = os.path.join(out, os.path.splitext(names[i + 1])[0])
+            Image.fromarray(res[0][i]).save(stem + "_flow.png")
+            if want_flo:
+                flow_io.writeFLO(stem + ".flo", res[2][i])
+                flow_io.save_mask(stem + "_fwd_occ.png", res[3][i])
+                flow_io.save_mask(stem + "_bwd_occ.png", res[4][i])
+        print("%d frames -> %d flow pictures in %s" % (len(names), len(names) - 2, out))
+        m.close()
+        return
     res = m.computeFlowSequence(frames, dtype=np.float32, occ_prob=want_occ)
     flow, fwd_occ, bwd_occ = res[:3]
     for i in range(len(names) - 2):

@@ -250,6 +250,47 @@ B2F_API int b2f_compute_flow_device(b2f_ctx *ctx, int n, int in_kind, const void
 B2F_API int b2f_compute_flow_sequence_device(b2f_ctx *ctx, int T, int in_kind, const void *dev_frames, int H0, int W0,
                                      float *dev_flow, float *dev_occ_prob,
                                      unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
+/* ---- flow pictures: flowX.xy2rgb(flow[1], flow[2][, max]) (flowExtensions.lua:17-150) as an output stage ----
+ * The colour coding of a flow field, quantised to bytes as image.save does (floor(clip(v, 0, 1) * 255 + 0.5)):
+ * hue = direction (atan(|y / x|) in degrees folded into the quadrant; x == 0: 90 for y >= 0, else 270), saturation
+ * s = tanh(norm / m) with a caller-given maximum (max_norm > 0: m = max(max_norm, 1e-2)) or norm / m with the
+ * automatic one (max_norm <= 0: m = max(largest norm of THAT image, 1e-2), never of the batch), lightness 1 - s / 2
+ * (null flow is white), then image.hsl2rgb.  All arithmetic is fp64 on the float32 flow, without fused multiply-adds,
+ * on the host and on the device, so the automatic maximum is the same double on both.
+ *   flow      n x 2 x H x W floats (channel 0 = x), any H, W >= 1
+ *   rgb       B2F_RGB_PLANAR: n x 3 x H x W bytes (the reference's tensor order, what image.save takes);
+ *             B2F_RGB_PACKED: n x H x W x 3 bytes (what PNG / video encoders take)
+ *   max_used  n doubles or NULL: the m of every image (the reference returns rgb, max)
+ * Non-finite flow values give unspecified colours.                                                           */
+enum { B2F_RGB_PLANAR = 0, B2F_RGB_PACKED = 1 };
+/* host only, no GPU: the same per-pixel function on the CPU */
+B2F_API int b2f_flow_rgb_host(const float *flow, int n, int H, int W, double max_norm, int layout,
+                      unsigned char *rgb, double *max_used);
+/* device pointers (16-byte aligned), asynchronous on `stream` like b2f_forward_device: after
+ * b2f_compute_flow_device on the same stream it needs no synchronisation in between.  The automatic maximum is
+ * reduced on the device (into dev_max_used when given, else into a buffer of the context).                  */
+B2F_API int b2f_flow_rgb_device(b2f_ctx *ctx, const float *dev_flow, int n, int H, int W, double max_norm, int layout,
+                        unsigned char *dev_rgb, double *dev_max_used, void *stream);
+/* host pointers through the GPU, like the b2f_op_* entries below */
+B2F_API int b2f_op_flow_rgb(b2f_ctx *ctx, const float *flow, int n, int H, int W, double max_norm, int layout,
+                    unsigned char *rgb, double *max_used);
+/* computeFlow with pictures: the f32 entries' inputs; rgb (n x 3 x H0 x W0 or n x H0 x W0 x 3 bytes) is required,
+ * max_used, flow, fwd_occ and bwd_occ are optional (NULL: neither written nor downloaded).  The pictures are
+ * those of b2f_op_flow_rgb on the float32 flow the f32 entries return, and the other outputs are theirs, bit for
+ * bit; a caller who wants pictures downloads 3 bytes per pixel instead of 10.  Sub-batches and the multi entries'
+ * shards colour every triplet from its own field, so the results do not depend on where the cuts fall.        */
+B2F_API int b2f_compute_flow_batch_rgb(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                               int H0, int W0, double max_norm, int layout, unsigned char *rgb, double *max_used,
+                               float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_compute_flow_sequence_rgb(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                  double max_norm, int layout, unsigned char *rgb, double *max_used,
+                                  float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_batch_rgb(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                     int H0, int W0, double max_norm, int layout, unsigned char *rgb, double *max_used,
+                                     float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_sequence_rgb(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                        double max_norm, int layout, unsigned char *rgb, double *max_used,
+                                        float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
 /* Full output table of model:forward (pwc.lua:459-489) into n_outs host buffers, in
  * table order; x is B x 9 x H x W normalized host memory.                           */
 B2F_API int b2f_forward(b2f_ctx *ctx, const float *x, int B, int H, int W, float **outs, int n_outs);

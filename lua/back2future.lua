@@ -45,6 +45,19 @@ int  b2f_compute_flow_device(b2f_ctx *ctx, int n, int in_kind, const void *dev_i
 int  b2f_compute_flow_sequence_device(b2f_ctx *ctx, int T, int in_kind, const void *dev_frames, int H0, int W0,
                                       float *dev_flow, float *dev_occ_prob,
                                       unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
+enum { B2F_RGB_PLANAR = 0, B2F_RGB_PACKED = 1 };
+int b2f_flow_rgb_host(const float *flow, int n, int H, int W, double max_norm, int layout,
+                      unsigned char *rgb, double *max_used);
+int b2f_flow_rgb_device(b2f_ctx *ctx, const float *dev_flow, int n, int H, int W, double max_norm, int layout,
+                        unsigned char *dev_rgb, double *dev_max_used, void *stream);
+int b2f_op_flow_rgb(b2f_ctx *ctx, const float *flow, int n, int H, int W, double max_norm, int layout,
+                    unsigned char *rgb, double *max_used);
+int b2f_compute_flow_batch_rgb(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                               int H0, int W0, double max_norm, int layout, unsigned char *rgb, double *max_used,
+                               float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_compute_flow_sequence_rgb(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                  double max_norm, int layout, unsigned char *rgb, double *max_used,
+                                  float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -54,6 +67,12 @@ int  b2f_multi_compute_flow_batch_f32(b2f_multi *m, int n, int in_kind, const vo
                                       int H0, int W0, float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
 int  b2f_multi_compute_flow_sequence_f32(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
                                          float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_compute_flow_batch_rgb(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                     int H0, int W0, double max_norm, int layout, unsigned char *rgb, double *max_used,
+                                     float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_compute_flow_sequence_rgb(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                        double max_norm, int layout, unsigned char *rgb, double *max_used,
+                                        float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
 ]]
 
 local lib = ffi.load(os.getenv('B2F_LIB') or 'libb2f.so')
