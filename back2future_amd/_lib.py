@@ -78,6 +78,17 @@ SIGNATURES = {
     "b2f_multi_compute_flow_sequence_rgb": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                       C.c_double, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(C.c_double), c_float_p,
                                                       C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "b2f_stream_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "b2f_stream_close": (None, [C.c_void_p]),
+    "b2f_stream_reset": (C.c_int, [C.c_void_p]),
+    "b2f_stream_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_longlong)]),
+    "b2f_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte),
+                                  C.POINTER(C.c_int)]),
+    "b2f_stream_push_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(C.c_double), c_float_p,
+                                      C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
+    "b2f_stream_push_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int)]),
     "b2f_forward": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(c_float_p), C.c_int]),
     "b2f_output_shapes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.c_int]),

@@ -12,6 +12,7 @@ back2future.lua:77-84), the masks are 1 x H x W uint8 arrays.  The Lua original 
 the returned closure, and `init` may be called several times.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -219,6 +220,114 @@ def _compute_flow_sequence_rgb(prefix, h, frames, max, packed, want_flow, want_m
     return _call_rgb(prefix + "compute_flow_sequence_rgb", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0, max_norm, packed, outs)
 
 
+class FlowStream(object):
+    """Frames that arrive one at a time (Model.openStream; b2f_stream_*): the features of the last frames stay on the GPU, every
+    pushed frame is uploaded and run through the feature pyramid once.  Pushes 1 and 2 return None; push k >= 3 returns the outputs
+    of the triplet of frames (k-2, k-1, k) with a leading `cams` axis -- with the model's default options output k-3 of
+    computeFlowSequence(dtype=np.float32) on the same frames, bit for bit.  A context manager: `with model.openStream(H, W) as st:`."""
+
+    def __init__(self, model, H0, W0, cams=1, dtype=np.uint8):
+        try:
+            dt = np.dtype(dtype)
+        except TypeError:
+            raise ValueError("openStream: dtype must be np.uint8 or np.float32, got %r" % (dtype,))
+        if dt not in (np.dtype(np.uint8), np.dtype(np.float32)):
+            raise ValueError("openStream: dtype must be np.uint8 or np.float32, got %s" % dt)
+        if int(cams) < 1 or int(H0) < 64 or int(W0) < 64:
+            raise ValueError("openStream: cams >= 1 and H0, W0 >= 64, got cams=%r H0=%r W0=%r" % (cams, H0, W0))
+        self._h = None
+        self.cams, self.H0, self.W0, self.dtype = int(cams), int(H0), int(W0), dt
+        self.in_kind = IN_U8 if dt == np.uint8 else IN_UNIT
+        h = C.c_void_p()
+        _lib.check(_lib.lib().b2f_stream_open(model._h, self.cams, self.in_kind, self.H0, self.W0, C.byref(h)))
+        self._h = h
+        self._model = model
+        model._streams.append(weakref.ref(self))   # Model.close closes the streams that are still open
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if _lib is not None:
+                _lib.lib().b2f_stream_close(self._h)
+            self._h = None
+            self._model._streams[:] = [r for r in self._model._streams if r() not in (None, self)]
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _open(self, who):
+        if not getattr(self, "_h", None):
+            raise ValueError("%s: the stream is closed" % who)
+
+    def _frames(self, frames, who):
+        """The cams x 3 x H0 x W0 array of a push: 3 x H0 x W0 is accepted for one camera; the stream's dtype exactly."""
+        self._open(who)
+        v = np.asarray(frames)
+        if v.dtype != self.dtype:
+            raise ValueError("%s: this stream takes %s frames, got %s" % (who, self.dtype.name, v.dtype))
+        if v.ndim == 3 and self.cams == 1:
+            v = v[None]
+        if v.shape != (self.cams, 3, self.H0, self.W0):
+            raise ValueError("%s: expected %s frames, got %s" % (who, "%d x 3 x %d x %d" % (self.cams, self.H0, self.W0), "x".join(map(str, v.shape))))
+        return np.ascontiguousarray(v)
+
+    @property
+    def frames_pushed(self):
+        self._open("frames_pushed")
+        n = C.c_longlong()
+        _lib.check(_lib.lib().b2f_stream_info(self._h, None, None, None, None, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """Forget the pushed frames (the next push is push 1) and clear the broken flag of a failed push."""
+        self._open("reset")
+        _lib.check(_lib.lib().b2f_stream_reset(self._h))
+
+    def push(self, frames, out=None, occ_prob=False):
+        """One new frame per camera (3 x H0 x W0 with one camera, else cams x 3 x H0 x W0).  Returns None for the first two pushes,
+        then (flow, fwd_occ, bwd_occ[, occ_prob]) as computeFlowBatch(dtype=np.float32) with n = cams; out = those buffers."""
+        v = self._frames(frames, "push")
+        flow, fwd, bwd, occ = _f32_outputs(self.cams, self.H0, self.W0, occ_prob, out, "push")
+        u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+        ready = C.c_int()
+        _lib.check(_lib.lib().b2f_stream_push(self._h, C.c_void_p(v.ctypes.data), _lib.fptr(flow), _lib.fptr(occ) if occ is not None else None,
+                                              u8p(fwd), u8p(bwd), C.byref(ready)))
+        if not ready.value:
+            return None
+        return (flow, fwd, bwd) + ((occ,) if occ_prob else ())
+
+    def pushRGB(self, frames, max=None, packed=False, want_flow=False, want_masks=False, out=None):
+        """push with the flow pictures as the output (b2f_stream_push_rgb): None, or (rgb, max_used[, flow][, fwd_occ, bwd_occ]) as
+        computeFlowBatchRGB with n = cams."""
+        max_norm = rgb_max_norm(max, "pushRGB")
+        v = self._frames(frames, "pushRGB")
+        outs = _rgb_outputs(self.cams, self.H0, self.W0, packed, want_flow, want_masks, out, "pushRGB")
+        rgb, mx, flow, fwd, bwd = outs
+        u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+        ready = C.c_int()
+        _lib.check(_lib.lib().b2f_stream_push_rgb(self._h, C.c_void_p(v.ctypes.data), max_norm, RGB_PACKED if packed else RGB_PLANAR, u8p(rgb),
+                                                  mx.ctypes.data_as(C.POINTER(C.c_double)), _lib.fptr(flow) if flow is not None else None,
+                                                  u8p(fwd), u8p(bwd), C.byref(ready)))
+        return tuple(a for a in outs if a is not None) if ready.value else None
+
+    def pushDevice(self, d_frames, d_flow, d_occ_prob=None, d_fwd_occ=None, d_bwd_occ=None, stream=None):
+        """b2f_stream_push_device on device pointers (ints): d_frames cams x 3 x H0 x W0 of the stream's dtype; outputs as
+        computeFlowDevice with n = cams, written only when the call returns True (from the third push on).  Asynchronous on `stream`."""
+        self._open("pushDevice")
+        if not d_frames or not d_flow:
+            raise ValueError("pushDevice: d_frames and d_flow are required")
+        p = lambda v: C.c_void_p(v) if v else None
+        ready = C.c_int()
+        _lib.check(_lib.lib().b2f_stream_push_device(self._h, p(d_frames), p(d_flow), p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream),
+                                                     C.byref(ready)))
+        return bool(ready.value)
+
+
 class Model(object):
     """Owns a b2f_ctx (the `model` global of back2future.lua:113)."""
 
@@ -229,6 +338,7 @@ class Model(object):
         _lib.check(L.b2f_init_ex(name.encode() if name is not None else None, int(device),
                                  graph.encode() if graph else None, C.byref(h)))
         self._h = h
+        self._streams = []
         self.name = name
         self.device = int(device)
         lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
@@ -238,6 +348,9 @@ class Model(object):
 
     def close(self):
         if getattr(self, "_h", None):
+            for ref in list(getattr(self, "_streams", [])):   # the context owns its streams: b2f_destroy would free them under their wrappers
+                if ref() is not None:
+                    ref().close()
             if _lib is not None:            # None while the interpreter tears the module down
                 _lib.lib().b2f_destroy(self._h)
             self._h = None
@@ -360,6 +473,12 @@ class Model(object):
         p = lambda v: C.c_void_p(v) if v else None
         _lib.check(_lib.lib().b2f_compute_flow_sequence_device(self._h, int(T), int(in_kind), p(d_frames), int(H0), int(W0), p(d_flow),
                                                                 p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream)))
+
+    def openStream(self, H0, W0, cams=1, dtype=np.uint8):
+        """A FlowStream of `cams` cameras delivering H0 x W0 frames of `dtype` (np.uint8 or np.float32 in [0,1]) one at a time."""
+        if not getattr(self, "_h", None):
+            raise ValueError("openStream: the model is closed")
+        return FlowStream(self, H0, W0, cams, dtype)
 
     def computeFlowBatchRGB(self, im1, im2, im3, max=None, packed=False, want_flow=False, want_masks=False, out=None):
         """computeFlowBatch with the flow pictures as the output (b2f_compute_flow_batch_rgb): returns (rgb, max_used[, flow]

@@ -298,20 +298,22 @@ struct Plan {
     int B, H, W;
     bool full;          // full model:forward table (all decoders, image pyramid, image warps)
     bool seq;           // sequence mode: the pyramid holds T = B + 2 frames, triplet b is frames (b, b + 1, b + 2)
-    int nimg;           // images of the feature pyramid: 3B (frame-major [3][B]) or T = B + 2
+    bool stream;        // a push of a stream: the pyramid runs on the B pushed frames, cs[3..7] live in the stream's ring, not in the arena
+    int nimg;           // images of the feature pyramid: 3B (frame-major [3][B]), T = B + 2, or B (stream)
     int fo;             // image offset of a triplet's second / third frame from its first one: B, or 1 in sequence mode
     int rec;            // cost-volume record size in floats
     int h[8], w[8];
     size_t img, tmp, cs[8], U[8], UB[8], cv, d[6], fs, bfs, logits, u2, flow_planar, ds[6], total;
 };
 
-Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false)
+Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false, bool stream = false)
 {
     Plan p;
     p.B = B; p.H = H; p.W = W;
     p.full = full;
     p.seq = seq;
-    p.nimg = seq ? B + 2 : 3 * B;
+    p.stream = stream;
+    p.nimg = stream ? B : seq ? B + 2 : 3 * B;
     p.fo = seq ? 1 : B;
     p.rec = kCvRec;
     for (int l = 1; l <= 7; ++l) { p.h[l] = H >> (l - 1); p.w[l] = W >> (l - 1); }
@@ -319,7 +321,7 @@ Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false)
     auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
     p.img = full ? take((size_t)3 * B * H * W * kImgC) : 0;   // packed frames: only the full table needs them
     p.tmp = take((size_t)p.nimg * p.h[2] * p.w[2] * kFeat[2]);
-    for (int l = 2; l <= 7; ++l) p.cs[l] = take((size_t)p.nimg * p.h[l] * p.w[l] * kFeat[l]);
+    for (int l = 2; l <= 7; ++l) p.cs[l] = take((stream && l >= 3) ? 0 : (size_t)p.nimg * p.h[l] * p.w[l] * kFeat[l]);
     for (int l = 3; l <= 6; ++l) p.U[l] = take((size_t)B * p.h[l] * p.w[l] * 2);
     for (int l = 3; l <= 6; ++l) p.UB[l] = (full && past_flow) ? take((size_t)B * p.h[l] * p.w[l] * 2) : 0;
     p.cv = take((size_t)B * p.h[3] * p.w[3] * p.rec + 64);
@@ -507,7 +509,7 @@ int run_conv(b2f_ctx *c, hipStream_t s, bool cap, int conv_id, const ConvSeg *se
 }
 
 // decoder(n) of pwc.lua:76-85 at level l; input = {cs[ref][l], cost-volume record}
-int run_decoder(b2f_ctx *c, hipStream_t s, bool cap, const Plan &P, int kind, int l, float *out2)
+int run_decoder(b2f_ctx *c, hipStream_t s, bool cap, const Plan &P, const float *ref, int kind, int l, float *out2)
 {
     const size_t *dbuf = P.d;
     float *A = c->arena;
@@ -517,7 +519,7 @@ int run_decoder(b2f_ctx *c, hipStream_t s, bool cap, const Plan &P, int kind, in
     const int id1 = find_conv(c, kind, l, 1);
     if (id1 < 0) return fail("decoder not present in this model");
     ConvSeg segs[2];
-    const ConvSeg seg_ref = cp8_seg(A + P.cs[l] + (size_t)P.fo * hw * Cl, Cl, hw);
+    const ConvSeg seg_ref = cp8_seg(ref, Cl, hw);
     const ConvSeg seg_cv = cp8_seg(A + P.cv, kCvRec, hw);
     if (c->packed[id1].nseg == 2) { segs[0] = seg_ref; segs[1] = seg_cv; }
     else { segs[0] = seg_cv; segs[1] = seg_cv; }
@@ -528,6 +530,31 @@ int run_decoder(b2f_ctx *c, hipStream_t s, bool cap, const Plan &P, int kind, in
         CHK(run_conv(c, s, cap, find_conv(c, kind, l, i), &in, B, h, w, 1, i < 6, o));
     }
     return 0;
+}
+
+// Where a pass finds the feature pyramid, per level: pyr = where its nimg images are written; past / ref / fut = the first image of each
+// role of the B triplets (image b of a role is triplet b's).  Triplet mode: [3][B] in the arena, the roles B images apart; sequence mode:
+// T = B + 2 frames in the arena, the roles one image apart; stream mode: the ring slots of three pushes (pyr[2], the level-2 / fused-head
+// map, stays in the arena: nothing reads it after the pyramid).
+struct Feat {
+    float *pyr[8];
+    const float *past[8], *ref[8], *fut[8];
+};
+
+Feat make_feat(const b2f_ctx *c, const Plan &P, const StreamPass *sp)
+{
+    Feat F{};
+    for (int l = 2; l <= 7; ++l) {
+        const size_t img = (size_t)P.h[l] * P.w[l] * kFeat[l];
+        if (sp && l >= 3) {
+            F.pyr[l] = sp->pyr[l];
+            F.past[l] = sp->past[l]; F.ref[l] = sp->ref[l]; F.fut[l] = sp->fut[l];
+        } else {
+            F.pyr[l] = c->arena + P.cs[l];
+            F.past[l] = F.pyr[l]; F.ref[l] = F.pyr[l] + (size_t)P.fo * img; F.fut[l] = F.pyr[l] + (size_t)2 * P.fo * img;
+        }
+    }
+    return F;
 }
 
 // Device outputs of one forward.  Pruned mode (computeFlow): flow / occ / est3 of the finest
@@ -541,11 +568,13 @@ struct Outs {
 // The computeFlow graph: pruned to the live set or, with P.full, the
 // complete model:forward of models/pwc.lua.  With P.seq the input is T = B + 2 frames (T x 3 x H x W) and the pyramid
 // runs on each frame once; from the cost volume on, the launches are those of B triplets, which read their frames
-// through base pointers P.fo images apart.
-int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in_kind, const Plan &P, const Outs &O)
+// through base pointers P.fo images apart.  With sp (a push of a stream) the input is the B = cams pushed frames, the pyramid writes
+// the ring slot of the push, and the rest -- only when the stream holds three frames -- reads the slots of three pushes (make_feat).
+int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in_kind, const Plan &P, const Outs &O, const StreamPass *sp = nullptr)
 {
     c->cur_batch = c->req_batch > 0 ? c->req_batch : P.B;
     float *A = c->arena;
+    const Feat F = make_feat(c, P, sp);
     const int B = P.B;
     const bool full = P.full, past = c->past_flow && full;
     const int unit = in_kind == B2F_IN_UNIT;
@@ -561,7 +590,7 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
     for (int l = 2; l <= 7; ++l) {
         const int hi = P.h[l - 1], wi = P.w[l - 1], ho = P.h[l], wo = P.w[l];
         const int Ci = (l == 2) ? kImgC : kFeat[l - 1], Co = kFeat[l];
-        if (l == 2 && P.seq) {
+        if (l == 2 && (P.seq || sp)) {
             Scope sc(c, s, "conv_first_seq", cap);
             HIPCHK(launch_conv_first_seq(dev_in, in_kind, P.nimg, P.H, P.W, c->wpk_dev + c->first_w_off, c->wpk_dev + c->first_b_off,
                                          A + P.tmp, s));
@@ -571,10 +600,10 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
                                      c->wpk_dev + c->first_b_off, A + P.tmp, s));
         } else if (l == 3 && head_fused) {   // conv 1 of level 3 ran inside the fused head: its output sits in the (otherwise unused) cs[2] region
             const ConvSeg in2f = cp8_seg(A + P.cs[2], Co, (size_t)ho * wo);
-            CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 2), &in2f, P.nimg, ho, wo, 1, 1, A + P.cs[l]));
+            CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 2), &in2f, P.nimg, ho, wo, 1, 1, F.pyr[l]));
             continue;
         } else {
-            const ConvSeg in1 = cp8_seg(A + P.cs[l - 1], Ci, (size_t)hi * wi);
+            const ConvSeg in1 = cp8_seg(F.pyr[l - 1], Ci, (size_t)hi * wi);
             CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 1), &in1, P.nimg, hi, wi, 2, 1, A + P.tmp));
         }
         if (l == 2 && head_fused) {   // level-2 conv 2 + level-3 conv 1 in one streaming kernel (b2f_head.hip)
@@ -593,8 +622,9 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
             continue;
         }
         const ConvSeg in2 = cp8_seg(A + P.tmp, Co, (size_t)ho * wo);
-        CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 2), &in2, P.nimg, ho, wo, 1, 1, A + P.cs[l]));
+        CHK(run_conv(c, s, cap, find_conv(c, KIND_FEAT, l, 2), &in2, P.nimg, ho, wo, 1, 1, F.pyr[l]));
     }
+    if (sp && !sp->ready) return 0;   // pushes 1 and 2 of a stream: the features are in the ring, there is no triplet yet
     if (full) {
         // image pyramid of frames 1 and 3 for the warped-image outputs (pwc.lua:148-158);
         // ds[k] holds [frame 1 | frame 3], level 1 is the packed input itself
@@ -614,9 +644,9 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
         const int h = P.h[l], w = P.w[l], Cl = kFeat[l];
         const size_t hw = (size_t)h * w;
         CorrLaunch cl;
-        cl.ref = A + P.cs[l] + (size_t)P.fo * hw * Cl;
-        cl.nbr_fut = A + P.cs[l] + (size_t)2 * P.fo * hw * Cl;
-        cl.nbr_past = A + P.cs[l];
+        cl.ref = F.ref[l];
+        cl.nbr_fut = F.fut[l];
+        cl.nbr_past = F.past[l];
         cl.img_stride = (long)(hw * Cl);
         cl.chunk_stride = (long)(hw * 8);
         cl.pix_stride = 8;
@@ -642,15 +672,15 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
         if (occ_out || occ_out2) {
             // (round 3 ran this decoder on a side stream beside the flow decoder: both chains are chip-filling persistent
             // kernels, measured no gain, and the second set of intermediates cost a third of the arena -- removed in round 4)
-            CHK(run_decoder(c, s, cap, P, KIND_OCC, l, A + P.logits));
+            CHK(run_decoder(c, s, cap, P, F.ref[l], KIND_OCC, l, A + P.logits));
             {
                 Scope sc(c, s, "softmax_nearest4", cap);
                 if (occ_out) HIPCHK(launch_softmax_nearest4_planar(A + P.logits, 8, B, h, w, occ_out, s));
                 if (occ_out2) HIPCHK(launch_softmax_nearest4_planar(A + P.logits, 8, B, h, w, occ_out2, s));
             }
         }
-        CHK(run_decoder(c, s, cap, P, KIND_FLOW, l, A + P.fs));
-        if (past) CHK(run_decoder(c, s, cap, P, KIND_PAST, l, A + P.bfs));
+        CHK(run_decoder(c, s, cap, P, F.ref[l], KIND_FLOW, l, A + P.fs));
+        if (past) CHK(run_decoder(c, s, cap, P, F.ref[l], KIND_PAST, l, A + P.bfs));
         // upsampling (pwc.lua:359-390): ufs = bilinear x2; skip_ufs = a second bilinear x2
         float *skip_f = full ? O.t_ufs[l] : (l == 3 ? (O.flow ? O.flow : A + P.flow_planar) : nullptr);
         {
@@ -679,9 +709,11 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
             if (O.t_iw3[l]) HIPCHK(launch_warp_image_planar(im3, O.t_ufs[l], kk, B, hk, wk, O.t_iw3[l], s));
         }
     }
-    if (!full && O.est3 && !c->past_flow && P.seq) {
+    if (!full && O.est3 && !c->past_flow && (P.seq || sp)) {
+        // frame b of the sequence, or camera b's frame of two pushes ago, is the first frame of triplet b
         Scope sc(c, s, "warp_image_seq", cap);
-        HIPCHK(launch_warp_input_seq(dev_in, in_kind, O.flow ? O.flow : A + P.flow_planar, -20.0f, B, P.H, P.W, O.est3, s));
+        HIPCHK(launch_warp_input_seq(sp ? sp->frame_past : dev_in, sp ? sp->frame_kind : in_kind, O.flow ? O.flow : A + P.flow_planar, -20.0f, B,
+                                     P.H, P.W, O.est3, s));
     } else if (!full && O.est3 && !c->past_flow) {
         // Hard: est[3] = iws[1][3] = warp(I1, skip_ufs[3] * 20*(1-2)/2^0)  (pwc.lua:422-446,459-489)
         Scope sc(c, s, "warp_image", cap);
@@ -992,6 +1024,7 @@ void b2f_destroy(b2f_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    while (!c->streams.empty()) b2f_stream_close(c->streams.back());   // the context owns its streams
     drop_graphs(c);
     drop_gen_out(c);
     for (ProfEvent &pe : c->prof_pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
@@ -1149,10 +1182,11 @@ B2F_CATCH("b2f_profile_read")
 // attributes, which must not happen inside a capture), the second one captures, later ones only replay.  Worth
 // ~0.5 ms per forward pass: 17 % of a single full-HD triplet, 2 % of a batch of 16.
 int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow, float *dev_occ,
-                        float *dev_est3, hipStream_t s, bool graph, bool seq)
+                        float *dev_est3, hipStream_t s, bool graph, bool seq, const StreamPass *sp)
 {
     CHK(check_shape(B, H, W));
     HIPCHK(hipSetDevice(c->device));
+    if (sp && !c->g.shipped()) return fail("b2f_stream_push: streams run on the shipped graph only (this context was made with b2f_init_ex options)");
     if (seq && !c->g.shipped()) return fail("b2f_forward_sequence_device: sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
     if (!c->g.shipped()) {
         // other graph shapes: the whole output table through the generic executor (b2f_graph.hip), then est[1] / the
@@ -1182,7 +1216,7 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
         if (dev_est3) HIPCHK(hipMemcpyAsync(dev_est3, dev[2], c->past_flow ? n2 : n2 / 2 * 3, hipMemcpyDeviceToDevice, s));
         return 0;
     }
-    const Plan P = make_plan(B, H, W, false, c->past_flow, seq);
+    const Plan P = make_plan(B, H, W, false, c->past_flow, seq, sp != nullptr);
     CHK(ensure_workspace(c, P));
     Outs O;
     O.flow = dev_flow; O.occ = dev_occ; O.est3 = dev_est3;
@@ -1193,16 +1227,16 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
         }
         const int req = c->req_batch > 0 ? c->req_batch : B;
         const GraphKey key = {dev_in, dev_flow, dev_occ, dev_est3, in_kind, B, H, W, (c->adaptive_kernels > 0 || (c->adaptive_kernels < 0 && req == 1)) ? 1 : 0,
-                              seq ? 1 : 0};
+                              seq ? 1 : 0, sp ? sp->ring : nullptr, sp ? 1 + 2 * sp->slot + (sp->ready ? 1 : 0) : 0};
         auto it = c->graphs.find(key);
         if (it == c->graphs.end()) {
             c->graphs.emplace(key, nullptr);
-            return forward_impl(c, s, false, dev_in, in_kind, P, O);
+            return forward_impl(c, s, false, dev_in, in_kind, P, O, sp);
         }
         if (!it->second) {
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const int rc = forward_impl(c, s, true, dev_in, in_kind, P, O);
+            const int rc = forward_impl(c, s, true, dev_in, in_kind, P, O, sp);
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
             HIPCHK(e);
@@ -1215,7 +1249,7 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
         HIPCHK(hipGraphLaunch(it->second, s));
         return 0;
     }
-    return forward_impl(c, s, false, dev_in, in_kind, P, O);
+    return forward_impl(c, s, false, dev_in, in_kind, P, O, sp);
 }
 
 extern "C" {

@@ -108,10 +108,27 @@ struct GraphKey {
     int kind, B, H, W;
     int rule;                      // kernel-choice rule the captured launches follow (1 = per launch: a single-triplet request), part of the key
     int seq;                       // 1 = sequence mode (in = B + 2 frames): never the graph of a triplet call with the same pointers and B
+    const void *ring = nullptr;    // stream mode (StreamPass): the stream's device block; in = the frame slot of the pushed frames ...
+    int phase = 0;                 // ... 1 + 2 * ring slot + ready: a stream captures one graph per ring phase, and one without the decoders
     bool operator<(const GraphKey &o) const
     {
-        return std::tie(in, flow, occ, est3, kind, B, H, W, rule, seq) < std::tie(o.in, o.flow, o.occ, o.est3, o.kind, o.B, o.H, o.W, o.rule, o.seq);
+        return std::tie(in, flow, occ, est3, kind, B, H, W, rule, seq, ring, phase) <
+               std::tie(o.in, o.flow, o.occ, o.est3, o.kind, o.B, o.H, o.W, o.rule, o.seq, o.ring, o.phase);
     }
+};
+
+// One push of a stream (b2f_stream) as the forward pass sees it: the pyramid of the B = cams pushed frames (dev_in of forward_device: their
+// frame slot) goes into pyr[3..7], the ring slot of this push; with `ready` the pass goes on from the cost volume, reading the three
+// frames of every camera's triplet from the ring slots of pushes k - 2, k - 1 and k (past / ref / fut: per level, B images each) and, for
+// the Hard models' est[3], the frames of push k - 2 as the pyramid read them (frame_past, frame_kind).
+struct StreamPass {
+    const void *ring = nullptr;
+    int slot = 0;
+    bool ready = false;
+    float *pyr[8] = {nullptr};
+    const float *past[8] = {nullptr}, *ref[8] = {nullptr}, *fut[8] = {nullptr};
+    const void *frame_past = nullptr;
+    int frame_kind = B2F_IN_UNIT;
 };
 
 // One of the two buffer sets the host-buffer entry point (b2f_compute_flow_batch) alternates between: while the
@@ -179,7 +196,15 @@ struct FlowRequest {
     FlowOutputs o;
     int req = 0;
     const char *who = "";
+    b2f_stream *stream = nullptr;   // a push: im1 holds the n = cams new frames, the other two frames of every triplet are the stream's
 };
+
+// n = cams frames pushed into st.  A stream is a clip: the kernel rule is a batch's (req >= 2) with one camera too, so that push k gives
+// the bits of output k - 3 of the sequence entries.
+inline FlowRequest push_request(const char *who, b2f_stream *st, int cams, int in_kind, const void *frames, int H0, int W0, const FlowOutputs &o)
+{
+    return {cams, false, in_kind, frames, nullptr, nullptr, H0, W0, o, std::max(cams, 2), who, st};
+}
 
 inline FlowRequest batch_request(const char *who, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0,
                                  const FlowOutputs &o)
@@ -323,6 +348,35 @@ private:
 
 }  // namespace b2f
 
+// A stream (include/b2f.h: b2f_stream_open): the features of the last frames of `cams` cameras, kept on the device between pushes.
+// ONE device block of its own, outside the arena and the workspaces of the other entries (those may be re-allocated between two pushes):
+//   ring     3 slots x [level 3..7] x [cam]: cs[l] of the frames of a push, chunk-planar; slot of push k = (k - 1) % 3
+//   frames   3 slots x [cam]: the frames as the pyramid read them (the caller's bytes / floats at a /64 size, else the normalized
+//            scaled frames): the input of the pyramid, and what est[3] of a Hard model warps two pushes later
+//   work     the buffers between the input and the outputs of a push (upload / image.scale / the network's outputs / the host
+//            entries' outputs), carved once at open for every output a push may ask for
+// and one page-locked block that stages pageable host buffers.
+struct b2f_stream {
+    b2f_ctx *ctx = nullptr;
+    int cams = 0, in_kind = B2F_IN_UNIT, H0 = 0, W0 = 0;
+    long long pushed = 0;          // frames pushed since open / the last reset
+    bool broken = false;           // a HIP call failed inside a push: the ring may hold half a frame; reset clears it
+    char *dev = nullptr;
+    size_t dev_bytes = 0;
+    float *lvl[3][8] = {{nullptr}};    // [slot][level]: cams images
+    char *frame[3] = {nullptr};        // [slot]: cams frames
+    int frame_kind = B2F_IN_UNIT;      // how the forward pass reads a frame slot
+    size_t frame_bytes = 0;            // of one slot
+    unsigned char *d_u8 = nullptr;     // a rescaled byte stream: the upload, unpacked into d_up
+    float *d_up = nullptr, *d_tmp = nullptr;   // a rescaled stream: the frames at H0 x W0 and image.scale's row pass
+    float *d_flow = nullptr, *d_occ = nullptr, *d_est3 = nullptr;   // the network's outputs (d_occ: Hard only)
+    float *d_flow32 = nullptr, *d_prob = nullptr;   // host pushes: outputs at H0 x W0 (= d_flow / the network's planes without a rescale)
+    unsigned char *d_fo = nullptr, *d_bo = nullptr, *d_rgb = nullptr;
+    double *d_max = nullptr;
+    char *pin = nullptr;               // staging of pageable host buffers: [frames | flow | occ_prob | masks | rgb | max]
+    size_t pin_bytes = 0;
+};
+
 struct b2f_ctx : b2f::KernelOpts {
     int device = 0;
     bool past_flow = false;
@@ -369,6 +423,7 @@ struct b2f_ctx : b2f::KernelOpts {
     std::unique_ptr<b2f::CopyPool> pool_in, pool_out;
     b2f::DevWork dwork;           // b2f_compute_flow_device / b2f_compute_flow_sequence_device
     b2f::DevWork vis_max;         // b2f_flow_rgb_device without dev_max_used: the per-image maxima of the automatic mode
+    std::vector<b2f_stream *> streams;   // open streams (b2f_stream_open); b2f_destroy closes what is left
 };
 
 #define HIPCHK(expr)                                                                         \
@@ -394,14 +449,19 @@ void drop_graphs(b2f_ctx *c);
 void drop_gen_out(b2f_ctx *c);
 // model:forward on device pointers, optionally replayed from a hipGraph (see b2f_api.hip); seq: dev_in holds the B + 2 frames
 // of a sequence (T x 3 x H x W) instead of B triplets (B x 9 x H x W)
+// sp: a push of a stream -- dev_in holds its B = cams frames (see StreamPass)
 int forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow, float *dev_occ,
-                   float *dev_est3, hipStream_t s, bool graph, bool seq = false);
+                   float *dev_est3, hipStream_t s, bool graph, bool seq = false, const StreamPass *sp = nullptr);
 // b2f_pipeline.hip: the checks of a request that need no context and no HIP call (in_kind, T / n, shape, required pointers); 0 = fine
 int check_request(const FlowRequest &r);
 // b2f_pipeline.hip: a request on host buffers (the upload / kernels / download pipeline) and on device buffers (the kernels alone,
 // asynchronous on `stream`, nullptr: the context's)
 int compute_flow_host(b2f_ctx *c, const FlowRequest &r);
 int compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream);
+// b2f_pipeline.hip: a push (r.stream) on host buffers, synchronous, and on device buffers, asynchronous on `stream`; *ready = 1 when
+// the outputs were written (from the third push on)
+int stream_push_host(const FlowRequest &r, int *ready);
+int stream_push_device(const FlowRequest &r, void *stream, int *ready);
 // pieces of b2f_api.hip the generic graph executor (b2f_graph.hip) builds on
 ConvSeg cp8_seg(const float *ptr, int C, size_t hw);
 int find_conv_id(const b2f_ctx *c, int kind, int level, int idx);

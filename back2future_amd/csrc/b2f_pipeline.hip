@@ -161,15 +161,18 @@ struct NetBuffers {
 // network as they are and the first conv kernel normalizes on the fly --, the forward pass, and outputs_f32_kernel into `out` (device
 // buffers at H0 x W0; nullptr: not written).  The flow of an f64 request is left unscaled: the host threads form `double * sc` (:80-84).
 // out.rgb: the pictures of that f32 flow (xy2rgb, b2f_vis.hip), read from out.flow32 or, at the network size, from net.flow itself.
+// sp: a push of a stream -- the nb = cams frames go through the pyramid into the ring (net.scaled, where image.scale writes, is their
+// frame slot); the rest runs, and the outputs are written, only from the third push on.
 int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void *x, int kind, long planes, int nb, const NetBuffers &net,
-                const FlowOutputs &out, bool graph, hipStream_t s)
+                const FlowOutputs &out, bool graph, hipStream_t s, const StreamPass *sp = nullptr)
 {
     if (!g.same) {
         HIPCHK(launch_image_scale((const float *)x, 1, planes, g.H0, g.W0, net.tmp, net.scaled, g.fh, g.fw, s));
         x = net.scaled;
         kind = B2F_IN_NORMALIZED;
     }
-    CHK(forward_device(c, x, kind, nb, g.fh, g.fw, net.flow, net.occ, net.est3, s, graph, r.seq));
+    CHK(forward_device(c, x, kind, nb, g.fh, g.fw, net.flow, net.occ, net.est3, s, graph, r.seq, sp));
+    if (sp && !sp->ready) return 0;
     const bool f32 = r.o.f32();
     HIPCHK(launch_outputs_f32(net.flow, g.C3 == 3 ? net.occ : net.est3, net.est3, g.C3, nb, g.fh, g.fw, g.H0, g.W0, f32 ? g.sc_w : 1.0,
                               f32 ? g.sc_h : 1.0, out.flow32, out.occ_prob, out.fwd_occ, out.bwd_occ, s));
@@ -180,6 +183,16 @@ int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void 
     return 0;
 }
 
+// the host threads of the pipeline (option host_threads, default 16: two thirds on the input side); the calling thread and the drain
+// thread each count as one worker of their pool.  Stream pushes stage through the same pools.
+void ensure_pools(b2f_ctx *c)
+{
+    const int nthreads = std::max(2, c->host_threads > 0 ? c->host_threads : (int)std::min(16u, std::thread::hardware_concurrency()));
+    const int w_out = std::max(0, nthreads / 3 - 1), w_in = std::max(0, nthreads - nthreads / 3 - 1);
+    if (!c->pool_in || c->pool_in->workers() != w_in) c->pool_in.reset(new CopyPool(w_in));
+    if (!c->pool_out || c->pool_out->workers() != w_out) c->pool_out.reset(new CopyPool(w_out));
+}
+
 // check_request, then what both paths check of the context
 int check_context(b2f_ctx *c, const FlowRequest &r)
 {
@@ -188,6 +201,137 @@ int check_context(b2f_ctx *c, const FlowRequest &r)
     if (r.seq && !c->g.shipped())
         return fail(std::string(r.who) + ": sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
     return 0;
+}
+
+// ---- streams ------------------------------------------------------------------------------------------------------------------
+// push k (k0 = k - 1 pushes before it) writes ring slot k0 % 3 and reads the slots of the two pushes before it
+StreamPass stream_pass(const b2f_stream *st)
+{
+    const int k0 = (int)(st->pushed % 3), s_ref = (k0 + 2) % 3, s_past = (k0 + 1) % 3;
+    StreamPass sp;
+    sp.ring = st->dev;
+    sp.slot = k0;
+    sp.ready = st->pushed >= 2;
+    for (int l = 3; l <= 7; ++l) {
+        sp.pyr[l] = st->lvl[k0][l];
+        sp.fut[l] = st->lvl[k0][l];
+        sp.ref[l] = st->lvl[s_ref][l];
+        sp.past[l] = st->lvl[s_past][l];
+    }
+    sp.frame_past = st->frame[s_past];
+    sp.frame_kind = st->frame_kind;
+    return sp;
+}
+
+// what both push paths check before any HIP work: the request (check_request), the stream and its context
+int check_push(const FlowRequest &r)
+{
+    const b2f_stream *st = r.stream;
+    if (!st) return fail(std::string(r.who) + ": null stream");
+    CHK(check_request(r));
+    if (st->broken)
+        return fail(std::string(r.who) + ": the stream is broken (a HIP call failed inside an earlier push): call b2f_stream_reset");
+    if (!st->ctx->g.shipped())
+        return fail(std::string(r.who) + ": streams run on the shipped graph only (this context was made with b2f_init_ex options)");
+    return 0;
+}
+
+// the device buffers of a push between its input and its outputs, and what the forward pass reads
+struct PushPlan {
+    Geometry g;
+    StreamPass sp;
+    NetBuffers net;
+    const float *occ_net;   // skip_occs[3] at the network size
+};
+
+PushPlan push_plan(const b2f_stream *st, bool want_prob)
+{
+    PushPlan p;
+    p.g = geometry(st->ctx, st->H0, st->W0);
+    p.sp = stream_pass(st);
+    p.net = {st->d_tmp, (float *)st->frame[p.sp.slot], st->d_flow, (want_prob && p.g.C3 == 3) ? st->d_occ : nullptr, st->d_est3};
+    p.occ_net = p.g.C3 == 3 ? st->d_occ : st->d_est3;
+    return p;
+}
+
+int push_host_work(b2f_stream *st, const FlowRequest &r, int k_in, const int *k_out)
+{
+    b2f_ctx *c = st->ctx;
+    const FlowOutputs &o = r.o;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->debug_fail_next) {   // tests (option debug_fail_next): one forced failure inside a push
+        c->debug_fail_next = 0;
+        return fail(std::string(r.who) + ": forced failure (option debug_fail_next)");
+    }
+    const ReqBatch req_guard(c, r);
+    const bool want_prob = o.occ_prob != nullptr, want_rgb = o.rgb != nullptr;
+    const PushPlan P = push_plan(st, want_prob);
+    const Geometry &g = P.g;
+    const bool same = g.same, bytes_in = st->in_kind == B2F_IN_U8;
+    const int n = st->cams;
+    const size_t hw0 = g.hw0, in_bytes = (size_t)n * 3 * hw0 * (bytes_in ? 1 : 4);
+    const size_t n_flow = (size_t)n * 2 * hw0 * 4, n_mask = (size_t)n * hw0, n_rgb = (size_t)n * 3 * hw0, n_max = (size_t)n * sizeof(double);
+    // staging of pageable buffers: [frames | flow | occ_prob | fwd | bwd | rgb | max], allocated with the first pageable push
+    size_t offs[8] = {0};
+    const size_t parts[7] = {in_bytes, n_flow, n_flow, n_mask, n_mask, n_rgb, n_max};
+    for (int i = 0; i < 7; ++i) offs[i + 1] = offs[i] + align256(parts[i]);
+    bool pageable = k_in != 1;
+    for (int i = 0; i < 6; ++i) pageable = pageable || k_out[i] != 1;
+    if (pageable && !st->pin) {
+        HIPCHK(hipHostMalloc(&st->pin, offs[7], hipHostMallocDefault));
+        st->pin_bytes = offs[7];
+    }
+    if (pageable) ensure_pools(c);   // the context's host threads do the staging copies
+    hipStream_t s = c->stream;
+    // ---- one upload of the cams frames: into their frame slot at a /64 size, else into the buffers image.scale reads
+    void *dst = same ? (void *)st->frame[P.sp.slot] : bytes_in ? (void *)st->d_u8 : (void *)st->d_up;
+    const void *src = r.im1;
+    if (k_in != 1) {
+        c->pool_in->run({{st->pin, r.im1, in_bytes}});
+        src = st->pin;
+    }
+    HIPCHK(hipMemcpyAsync(dst, src, in_bytes, hipMemcpyHostToDevice, s));
+    if (!same && bytes_in) HIPCHK(launch_unpack_u8(st->d_u8, (size_t)n * 3 * hw0, st->d_up, s));
+    CHK(run_kernels(c, r, g, same ? (const void *)st->frame[P.sp.slot] : st->d_up, same ? st->in_kind : B2F_IN_UNIT, (long)n * 3, n, P.net,
+                    {nullptr, same ? nullptr : st->d_flow32, (want_prob && !same) ? st->d_prob : nullptr, o.fwd_occ ? st->d_fo : nullptr,
+                     o.bwd_occ ? st->d_bo : nullptr, want_rgb ? st->d_rgb : nullptr, want_rgb ? st->d_max : nullptr, o.max_norm, o.rgb_layout},
+                    c->host_graph != 0, s, &P.sp));
+    // ---- download what was asked for: page-locked buffers in place, pageable ones through the staging block
+    struct Down { void *host; const void *dev; size_t bytes; int kind; size_t off; };
+    const Down downs[6] = {{o.flow32, st->d_flow32, n_flow, k_out[0], offs[1]}, {o.occ_prob, same ? (const void *)P.occ_net : st->d_prob, n_flow, k_out[3], offs[2]},
+                           {o.fwd_occ, st->d_fo, n_mask, k_out[1], offs[3]}, {o.bwd_occ, st->d_bo, n_mask, k_out[2], offs[4]},
+                           {o.rgb, st->d_rgb, n_rgb, k_out[4], offs[5]}, {o.rgb_max, st->d_max, n_max, k_out[5], offs[6]}};
+    std::vector<CopyJob> jobs;
+    for (const Down &d : downs) {
+        if (!d.host || !P.sp.ready) continue;
+        HIPCHK(hipMemcpyAsync(d.kind == 1 ? d.host : (void *)(st->pin + d.off), d.dev, d.bytes, hipMemcpyDeviceToHost, s));
+        if (d.kind != 1) jobs.push_back({d.host, st->pin + d.off, d.bytes});
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (!jobs.empty()) c->pool_out->run(jobs);
+    return 0;
+}
+
+int push_device_work(b2f_stream *st, const FlowRequest &r, hipStream_t s)
+{
+    b2f_ctx *c = st->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    const ReqBatch req_guard(c, r);
+    const PushPlan P = push_plan(st, r.o.occ_prob != nullptr);
+    const Geometry &g = P.g;
+    const bool bytes_in = st->in_kind == B2F_IN_U8;
+    const int n = st->cams;
+    const size_t samples = (size_t)n * 3 * g.hw0;
+    const void *x = r.im1;   // a rescaled float stream: image.scale reads the caller's frames themselves
+    if (g.same) {
+        // the frames must outlive the call (est[3] of a Hard model warps them two pushes later): into their frame slot
+        HIPCHK(hipMemcpyAsync(st->frame[P.sp.slot], r.im1, samples * (bytes_in ? 1 : 4), hipMemcpyDeviceToDevice, s));
+        x = st->frame[P.sp.slot];
+    } else if (bytes_in) {
+        HIPCHK(launch_unpack_u8((const unsigned char *)r.im1, samples, st->d_up, s));
+        x = st->d_up;
+    }
+    return run_kernels(c, r, g, x, g.same ? st->in_kind : B2F_IN_UNIT, (long)n * 3, n, P.net, r.o, c->use_graph != 0, s, &P.sp);
 }
 
 }  // namespace
@@ -203,7 +347,7 @@ int b2f::check_request(const FlowRequest &r)
     if (r.H0 < 64 || r.W0 < 64) return fail(w + ": image smaller than 64 pixels");
     const FlowOutputs &o = r.o;
     // an rgb request (f32 path) needs its pictures and may leave the flow out
-    if (!r.im1 || (!r.seq && (!r.im2 || !r.im3)) || (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : !o.flow32))
+    if (!r.im1 || (!r.seq && !r.stream && (!r.im2 || !r.im3)) || (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : !o.flow32))
         return fail(w + ": null argument");
     if (o.pictures && (!o.f32() || (o.rgb_layout != B2F_RGB_PLANAR && o.rgb_layout != B2F_RGB_PACKED)))
         return fail(w + ": bad layout (B2F_RGB_PLANAR or B2F_RGB_PACKED)");
@@ -262,7 +406,6 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
         return fail(w + ": forced failure (option debug_fail_next)");
     }
     const ReqBatch req_guard(c, r);
-    const int nthreads = std::max(2, c->host_threads > 0 ? c->host_threads : (int)std::min(16u, std::thread::hardware_concurrency()));
     const bool use_u8 = bytes_in || c->host_u8 != 0;
     int SB = 0;
     const std::vector<std::pair<int, int>> subs = plan_subbatches(c, n, seq, hw0, c->host_ramp != 0, &SB);
@@ -281,10 +424,7 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
     // (a sequence sub-batch's nb + 2 frames are 3 nb + 6 <= 9 nb planes: the triplet layout of the slot holds them)
     for (int k = 0; k < std::min(nsub, 2); ++k)
         CHK(ensure_slot(c, c->slot[k], SB, hw0, g.hw, g.H0, g.fw, g.C3, q));
-    // the calling thread and the drain thread each count as one worker of their pool
-    const int w_out = std::max(0, nthreads / 3 - 1), w_in = std::max(0, nthreads - nthreads / 3 - 1);
-    if (!c->pool_in || c->pool_in->workers() != w_in) c->pool_in.reset(new CopyPool(w_in));
-    if (!c->pool_out || c->pool_out->workers() != w_out) c->pool_out.reset(new CopyPool(w_out));
+    ensure_pools(c);
 
     const char *ims[3] = {(const char *)r.im1, (const char *)r.im2, (const char *)r.im3};
     // upload units: a triplet (3 frames, one from each of im1..im3) or, in sequence mode, one frame; frame f of unit u of
@@ -561,7 +701,182 @@ int b2f::compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream)
     return 0;
 }
 
+// ---- a push of a stream: one FlowRequest of n = cams that carries the stream ---------------------------------------------------
+// Host push: synchronous -- one upload of the cams frames, the kernels, the download of what was asked for, all on the context's
+// stream.  Device push: the kernels alone on the caller's stream.  Both validate first (check_push, the memory kinds, alignment): a
+// malformed push leaves the stream as it was.  Whatever fails after that marks the stream broken: the ring slot of the push may
+// hold half a frame.
+int b2f::stream_push_host(const FlowRequest &r, int *ready)
+{
+    if (ready) *ready = 0;
+    CHK(check_push(r));
+    b2f_stream *st = r.stream;
+    const FlowOutputs &o = r.o;
+    const size_t hw0 = (size_t)st->H0 * st->W0, n = (size_t)st->cams;
+    auto kind_of = [](const void *p, size_t bytes) { return p ? mem_kind(p, bytes) : 1; };   // unrequested outputs count as page-locked
+    const int k_in = mem_kind(r.im1, n * 3 * hw0 * (st->in_kind == B2F_IN_U8 ? 1 : 4));
+    const int k_out[6] = {kind_of(o.flow32, n * 2 * hw0 * 4), kind_of(o.fwd_occ, n * hw0), kind_of(o.bwd_occ, n * hw0), kind_of(o.occ_prob, n * 2 * hw0 * 4),
+                          kind_of(o.rgb, n * 3 * hw0), kind_of(o.rgb_max, n * sizeof(double))};
+    bool dev_mem = k_in < 0;
+    for (int k : k_out) dev_mem = dev_mem || k < 0;
+    if (dev_mem) return fail(std::string(r.who) + ": device memory passed to a host-buffer entry point (use b2f_stream_push_device)");
+    const bool is_ready = st->pushed >= 2;
+    if (push_host_work(st, r, k_in, k_out) != 0) {
+        const std::string msg = api_error();
+        (void)hipStreamSynchronize(st->ctx->stream);
+        (void)hipGetLastError();
+        st->broken = true;
+        return fail(msg);
+    }
+    ++st->pushed;
+    if (ready) *ready = is_ready ? 1 : 0;
+    return 0;
+}
+
+int b2f::stream_push_device(const FlowRequest &r, void *stream, int *ready)
+{
+    if (ready) *ready = 0;
+    CHK(check_push(r));
+    b2f_stream *st = r.stream;
+    const FlowOutputs &o = r.o;
+    if (((uintptr_t)r.im1 | (uintptr_t)o.flow32 | (uintptr_t)o.occ_prob | (uintptr_t)o.fwd_occ | (uintptr_t)o.bwd_occ) & 15)
+        return fail(std::string(r.who) + ": device buffers must be 16-byte aligned");
+    const size_t hw0n = (size_t)st->cams * st->H0 * st->W0;
+    const std::pair<const void *, size_t> bufs[5] = {{r.im1, hw0n * 3 * (st->in_kind == B2F_IN_U8 ? 1 : 4)}, {o.flow32, hw0n * 8}, {o.occ_prob, hw0n * 8},
+                                                     {o.fwd_occ, hw0n}, {o.bwd_occ, hw0n}};
+    for (const auto &pb : bufs)
+        if (pb.first && mem_kind(pb.first, pb.second) >= 0)
+            return fail(std::string(r.who) + ": host memory passed to a device entry point (use b2f_stream_push)");
+    const bool is_ready = st->pushed >= 2;
+    if (push_device_work(st, r, stream ? (hipStream_t)stream : st->ctx->stream) != 0) {
+        const std::string msg = api_error();
+        (void)hipGetLastError();
+        st->broken = true;
+        return fail(msg);
+    }
+    ++st->pushed;
+    if (ready) *ready = is_ready ? 1 : 0;
+    return 0;
+}
+
 extern "C" {
+
+int b2f_stream_open(b2f_ctx *c, int cams, int in_kind, int H0, int W0, b2f_stream **out) try
+{
+    if (!out) return fail("b2f_stream_open: null out");
+    *out = nullptr;
+    if (!c) return fail("b2f_stream_open: null context");
+    if (in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail("b2f_stream_open: in_kind must be B2F_IN_UNIT or B2F_IN_U8");
+    if (cams < 1) return fail("b2f_stream_open: a stream serves at least one camera");
+    if (H0 < 64 || W0 < 64) return fail("b2f_stream_open: image smaller than 64 pixels");
+    if (!c->g.shipped()) return fail("b2f_stream_open: streams run on the shipped graph only (this context was made with b2f_init_ex options)");
+    const Geometry g = geometry(c, H0, W0);
+    CHK(check_shape(cams, g.fh, g.fw));
+    if ((unsigned long long)cams * 3 * g.hw0 > 0x7fffffffull) return fail("b2f_stream_open: cams x 3 x H0 x W0 exceeds 2^31 - 1 samples");
+    HIPCHK(hipSetDevice(c->device));
+    std::unique_ptr<b2f_stream> st(new b2f_stream());
+    st->ctx = c; st->cams = cams; st->in_kind = in_kind; st->H0 = H0; st->W0 = W0;
+    const bool same = g.same, bytes_in = in_kind == B2F_IN_U8;
+    const size_t n = (size_t)cams, hw0 = g.hw0, hw = g.hw;
+    st->frame_kind = same ? in_kind : B2F_IN_NORMALIZED;
+    st->frame_bytes = same ? n * 3 * hw0 * (bytes_in ? 1 : 4) : n * 3 * hw * 4;
+    // carve: two passes over the same list, the first one without a base (every pointer stays null) to size the block
+    auto carve = [&](char *base) {
+        size_t off = 0;
+        auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += align256(bytes); return p; };
+        for (int sl = 0; sl < 3; ++sl)
+            for (int l = 3; l <= 7; ++l) st->lvl[sl][l] = (float *)take(n * (size_t)(g.fh >> (l - 1)) * (g.fw >> (l - 1)) * kFeat[l] * 4);
+        for (int sl = 0; sl < 3; ++sl) st->frame[sl] = take(st->frame_bytes);
+        st->d_u8 = (unsigned char *)take((!same && bytes_in) ? n * 3 * hw0 : 0);
+        st->d_up = (float *)take(same ? 0 : n * 3 * hw0 * 4);
+        st->d_tmp = (float *)take(same ? 0 : n * 3 * (size_t)H0 * g.fw * 4);
+        st->d_flow = (float *)take(n * 2 * hw * 4);
+        st->d_occ = (float *)take(n * 2 * hw * 4);
+        st->d_est3 = (float *)take(n * 3 * hw * 4);   // three channels: b2f_set_weights may turn a Soft context Hard
+        st->d_flow32 = same ? st->d_flow : (float *)take(n * 2 * hw0 * 4);
+        st->d_prob = (float *)take(same ? 0 : n * 2 * hw0 * 4);
+        st->d_fo = (unsigned char *)take(n * hw0);
+        st->d_bo = (unsigned char *)take(n * hw0);
+        st->d_rgb = (unsigned char *)take(n * 3 * hw0);
+        st->d_max = (double *)take(n * sizeof(double));
+        return off;
+    };
+    st->dev_bytes = carve(nullptr);
+    if (hipMalloc(&st->dev, st->dev_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("b2f_stream_open: out of device memory (" + std::to_string(st->dev_bytes >> 20) + " MB for the stream)");
+    }
+    carve(st->dev);
+    if (hipMemset(st->dev, 0, st->dev_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(st->dev);
+        return fail("b2f_stream_open: hipMemset failed");
+    }
+    c->streams.push_back(st.get());
+    *out = st.release();
+    return 0;
+}
+B2F_CATCH("b2f_stream_open")
+
+void b2f_stream_close(b2f_stream *st)
+{
+    if (!st) return;
+    b2f_ctx *c = st->ctx;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();   // pushes may still run, on any stream
+    drop_graphs(c);                 // they hold the stream's pointers
+    c->streams.erase(std::remove(c->streams.begin(), c->streams.end(), st), c->streams.end());
+    if (st->dev) (void)hipFree(st->dev);
+    if (st->pin) (void)hipHostFree(st->pin);
+    delete st;
+}
+
+int b2f_stream_reset(b2f_stream *st) try
+{
+    if (!st) return fail("b2f_stream_reset: null stream");
+    HIPCHK(hipSetDevice(st->ctx->device));
+    HIPCHK(hipDeviceSynchronize());   // a device push may still be writing the ring
+    st->pushed = 0;
+    st->broken = false;
+    return 0;
+}
+B2F_CATCH("b2f_stream_reset")
+
+int b2f_stream_info(const b2f_stream *st, int *cams, int *H0, int *W0, int *in_kind, long long *pushed) try
+{
+    if (!st) return fail("b2f_stream_info: null stream");
+    if (cams) *cams = st->cams;
+    if (H0) *H0 = st->H0;
+    if (W0) *W0 = st->W0;
+    if (in_kind) *in_kind = st->in_kind;
+    if (pushed) *pushed = st->pushed;
+    return 0;
+}
+B2F_CATCH("b2f_stream_info")
+
+int b2f_stream_push(b2f_stream *st, const void *frames, float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ, int *ready) try
+{
+    if (!st) return fail("b2f_stream_push: null stream");
+    return stream_push_host(push_request(__func__, st, st->cams, st->in_kind, frames, st->H0, st->W0, {nullptr, flow, occ_prob, fwd_occ, bwd_occ}), ready);
+}
+B2F_CATCH("b2f_stream_push")
+
+int b2f_stream_push_rgb(b2f_stream *st, const void *frames, double max_norm, int layout, unsigned char *rgb, double *max_used, float *flow,
+                        unsigned char *fwd_occ, unsigned char *bwd_occ, int *ready) try
+{
+    if (!st) return fail("b2f_stream_push_rgb: null stream");
+    return stream_push_host(push_request(__func__, st, st->cams, st->in_kind, frames, st->H0, st->W0,
+                                         rgb_outputs(rgb, max_used, max_norm, layout, flow, fwd_occ, bwd_occ)), ready);
+}
+B2F_CATCH("b2f_stream_push_rgb")
+
+int b2f_stream_push_device(b2f_stream *st, const void *dev_frames, float *dev_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ,
+                           unsigned char *dev_bwd_occ, void *stream, int *ready) try
+{
+    if (!st) return fail("b2f_stream_push_device: null stream");
+    return stream_push_device(push_request(__func__, st, st->cams, st->in_kind, dev_frames, st->H0, st->W0,
+                                           {nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}), stream, ready);
+}
+B2F_CATCH("b2f_stream_push_device")
 
 int b2f_compute_flow(b2f_ctx *c, const float *im1, const float *im2, const float *im3, int H0, int W0, double *flow, unsigned char *fwd_occ,
                      unsigned char *bwd_occ) try

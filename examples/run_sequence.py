@@ -4,13 +4,15 @@ frame that has a neighbour on both sides.  Every frame is uploaded and run throu
 (Model.computeFlowSequence); output t is computeFlow(frame[t-1], frame[t], frame[t+1]) bit for bit.  The flow comes from the
 float32 entry (dtype=np.float32: the float64 flow rounded to float32, which is what a .flo file stores).
 
-Usage: python examples/run_sequence.py DIR OUT/ [model] [--occ-prob] [--rgb [MAX]] [--flo]
+Usage: python examples/run_sequence.py DIR OUT/ [model] [--occ-prob] [--rgb [MAX]] [--flo] [--stream]
 model: 'Ours-Hard' | 'Ours-Soft-ft-KITTI' | 'Ours-Soft-ft-Sintel' (needs models/RoamingImages_*.t7 in the current
 directory, as in the reference) or 'random:soft' / a .t7 / .b2fw path (default 'Ours-Soft-ft-KITTI').
 --occ-prob: also write the occlusion probabilities of every centre frame as a 2 x H x W float32 .npy file.
 --rgb [MAX]: write the flow picture of every centre frame (flowX.xy2rgb, coloured on the GPU: Model.computeFlowSequenceRGB) as
 a PNG instead; MAX is xy2rgb's `max` (default: every picture's own largest flow).  Only the pictures are downloaded; --flo
 writes the .flo files and masks as well.
+--stream: push the frames one at a time (Model.openStream / FlowStream.push, the calling pattern of a camera) instead of handing
+over the clip; the files are the same, byte for byte.
 """
 import os
 import sys
@@ -27,6 +29,7 @@ EXTS = (".png", ".jpg", ".jpeg", ".ppm", ".bmp")
 def main():
     args = list(sys.argv[1:])
     want_occ, want_flo, want_rgb, rgb_max = "--occ-prob" in args, "--flo" in args, "--rgb" in args, None
+    stream = "--stream" in args
     if want_rgb:
         i = args.index("--rgb")
         try:
@@ -38,7 +41,7 @@ def main():
             sys.exit("--rgb MAX: MAX must be positive")
         if want_occ:
             sys.exit("--rgb and --occ-prob cannot be combined")
-    args = [a for a in args if a not in ("--occ-prob", "--flo", "--rgb")]
+    args = [a for a in args if a not in ("--occ-prob", "--flo", "--rgb", "--stream")]
     if len(args) < 2:
         sys.exit(__doc__)
     src, out = args[0], args[1]
@@ -49,9 +52,19 @@ def main():
     frames = np.stack([flow_io.load_image(os.path.join(src, f)) for f in names])
     os.makedirs(out, exist_ok=True)
     m = back2future.Model(model)
+
+    def pushed(push):
+        """The sequence call's results from a stream: output i is what the push of frame i + 2 returns."""
+        with m.openStream(frames.shape[2], frames.shape[3], dtype=frames.dtype) as st:
+            outs = [push(st, f) for f in frames][2:]
+        return tuple(np.concatenate(parts) for parts in zip(*outs))
+
     if want_rgb:
         from PIL import Image
-        res = m.computeFlowSequenceRGB(frames, max=rgb_max, packed=True, want_flow=want_flo, want_masks=want_flo)
+        if stream:
+            res = pushed(lambda st, f: st.pushRGB(f, max=rgb_max, packed=True, want_flow=want_flo, want_masks=want_flo))
+        else:
+            res = m.computeFlowSequenceRGB(frames, max=rgb_max, packed=True, want_flow=want_flo, want_masks=want_flo)
         for i in range(len(names) - 2):
             stem = os.path.join(out, os.path.splitext(names[i + 1])[0])
             Image.fromarray(res[0][i]).save(stem + "_flow.png")
@@ -62,7 +75,10 @@ def main():
         print("%d frames -> %d flow pictures in %s" % (len(names), len(names) - 2, out))
         m.close()
         return
-    res = m.computeFlowSequence(frames, dtype=np.float32, occ_prob=want_occ)
+    if stream:
+        res = pushed(lambda st, f: st.push(f, occ_prob=want_occ))
+    else:
+        res = m.computeFlowSequence(frames, dtype=np.float32, occ_prob=want_occ)
     flow, fwd_occ, bwd_occ = res[:3]
     for i in range(len(names) - 2):
         stem = os.path.join(out, os.path.splitext(names[i + 1])[0])   # named after the centre frame

@@ -291,6 +291,55 @@ B2F_API int b2f_multi_compute_flow_batch_rgb(b2f_multi *m, int n, int in_kind, c
 B2F_API int b2f_multi_compute_flow_sequence_rgb(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
                                         double max_norm, int layout, unsigned char *rgb, double *max_used,
                                         float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
+ * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
+ * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature
+ * pyramids for it.  A stream keeps the pyramid features of the last frames on the GPU: every pushed frame is
+ * uploaded once and goes through the pyramid (pwc.lua:169-211) once.  It serves `cams` cameras that deliver
+ * their frames in lockstep (1: one camera, 2: a stereo rig, ...).  Pushes are numbered k = 1, 2, 3, ... since
+ * open / the last reset: pushes 1 and 2 set *ready = 0 and write nothing; push k >= 3 sets *ready = 1 and
+ * writes, per camera, the outputs of the triplet of frames (k-2, k-1, k) -- the flow of centre frame k-1.
+ * With the context's default options these are output k-3 of b2f_compute_flow_sequence_f32 on the same
+ * frames (T >= 4) bit for bit: a stream follows the kernel rule of a batch whatever `cams` is; with option
+ * adaptive_kernels = 1 it follows the per-launch rule (the flow is then within 1e-3 of the default one).
+ *
+ * b2f_stream_open replaces the `model` global's implicit state (back2future.lua:113) for this pattern: cams >= 1,
+ * in_kind = B2F_IN_UNIT (floats in [0,1]) or B2F_IN_U8 (bytes, value = byte / 255), H0, W0 >= 64 (any size:
+ * frames are rescaled to multiples of 64 as in :54-71).  The stream owns one device block (three slots of
+ * features and frames per camera: about 3 x 28 MB per camera at 1024 x 1920, plus the frames and the
+ * buffers of a push) that no other call on the context touches; the shipped graph only (a context made with
+ * b2f_init_ex options is refused).  The context owns its streams: b2f_destroy closes those still open.   */
+typedef struct b2f_stream b2f_stream;
+B2F_API int b2f_stream_open(b2f_ctx *ctx, int cams, int in_kind, int H0, int W0, b2f_stream **out);
+/* Waits for the stream's work, frees its memory and drops the context's captured graphs (they hold its
+ * pointers).  NULL is a no-op.                                                                         */
+B2F_API void b2f_stream_close(b2f_stream *st);
+/* Forgets the pushed frames (the next push is push 1 again) and clears the broken flag a failed push sets. */
+B2F_API int b2f_stream_reset(b2f_stream *st);
+/* cams, H0, W0, in_kind and the frames pushed since open / the last reset (any pointer may be NULL). */
+B2F_API int b2f_stream_info(const b2f_stream *st, int *cams, int *H0, int *W0, int *in_kind, long long *pushed);
+/* One new frame per camera from host memory, replacing one computeFlow(im1, im2, im3) call
+ * (back2future.lua:47-95) per new frame.
+ * frames: cams x 3 x H0 x W0 floats or bytes (the stream's in_kind); outputs as b2f_compute_flow_batch_f32
+ * with n = cams: flow cams x 2 x H0 x W0 floats (required), occ_prob cams x 2 x H0 x W0 floats,
+ * fwd_occ / bwd_occ cams x H0 x W0 bytes (NULL: neither computed nor downloaded).  Synchronous: one upload of
+ * the cams frames (bytes as bytes; page-locked memory is DMA'd in place, pageable memory goes through the
+ * stream's staging block), the kernels, the download of what was asked for.  A malformed push (NULL required
+ * pointer, device memory) fails before any HIP work and leaves the stream as it was; a HIP failure inside a
+ * push marks the stream broken: later pushes fail, saying so, until b2f_stream_reset.                  */
+B2F_API int b2f_stream_push(b2f_stream *st, const void *frames, float *flow, float *occ_prob,
+                    unsigned char *fwd_occ, unsigned char *bwd_occ, int *ready);
+/* The same with flow pictures as the output, as b2f_compute_flow_batch_rgb with n = cams: rgb is required,
+ * max_used, flow and the masks are optional; a live preview downloads 3 bytes per pixel.                */
+B2F_API int b2f_stream_push_rgb(b2f_stream *st, const void *frames, double max_norm, int layout, unsigned char *rgb,
+                        double *max_used, float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ, int *ready);
+/* The same on GPU memory, asynchronous on `stream` like b2f_compute_flow_device (frames decoded on the GPU):
+ * every pointer device memory and 16-byte aligned; dev_frames is read before the call returns control to
+ * `stream`'s next work, so the caller may overwrite it after anything ordered behind the push.  Pushes of one
+ * stream must be ordered by the caller (one hipStream, or events).  Pictures on the device: b2f_flow_rgb_device
+ * on dev_flow, on the same stream.  *ready is known when the call returns.                               */
+B2F_API int b2f_stream_push_device(b2f_stream *st, const void *dev_frames, float *dev_flow, float *dev_occ_prob,
+                           unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream, int *ready);
 /* Full output table of model:forward (pwc.lua:459-489) into n_outs host buffers, in
  * table order; x is B x 9 x H x W normalized host memory.                           */
 B2F_API int b2f_forward(b2f_ctx *ctx, const float *x, int B, int H, int W, float **outs, int n_outs);

@@ -58,6 +58,17 @@ int b2f_compute_flow_batch_rgb(b2f_ctx *ctx, int n, int in_kind, const void *im1
 int b2f_compute_flow_sequence_rgb(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
                                   double max_norm, int layout, unsigned char *rgb, double *max_used,
                                   float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+typedef struct b2f_stream b2f_stream;
+int  b2f_stream_open(b2f_ctx *ctx, int cams, int in_kind, int H0, int W0, b2f_stream **out);
+void b2f_stream_close(b2f_stream *st);
+int  b2f_stream_reset(b2f_stream *st);
+int  b2f_stream_info(const b2f_stream *st, int *cams, int *H0, int *W0, int *in_kind, long long *pushed);
+int  b2f_stream_push(b2f_stream *st, const void *frames, float *flow, float *occ_prob,
+                     unsigned char *fwd_occ, unsigned char *bwd_occ, int *ready);
+int  b2f_stream_push_rgb(b2f_stream *st, const void *frames, double max_norm, int layout, unsigned char *rgb,
+                         double *max_used, float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ, int *ready);
+int  b2f_stream_push_device(b2f_stream *st, const void *dev_frames, float *dev_flow, float *dev_occ_prob,
+                            unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream, int *ready);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -181,7 +192,42 @@ local function init(opt)
                                               occ_prob and occ_prob:data() or nil, fwd_occ_est:data(), bwd_occ_est:data()))
       return flow_est, fwd_occ_est, bwd_occ_est, occ_prob
    end
-   return computeFlow, computeFlowSequence, computeFlowBatchF32, computeFlowSequenceF32
+   -- frames that arrive one at a time (a camera, a decoder): openStream(height, width[, cams[, bytes]]) returns a table with
+   -- push(frames[, want_occ_prob]) -> nil for the first two pushes, then flow, fwd_occ, bwd_occ[, occ_prob] of the triplet
+   -- (k-2, k-1, k) with a leading cams axis (FloatTensor flow, as computeFlowBatchF32), reset() and close().  frames:
+   -- cams x 3 x H x W (3 x H x W with one camera), FloatTensor in [0,1] or, with bytes = true, ByteTensor.
+   local openStream = function(height, width, cams, bytes)
+      cams = cams or 1
+      local pst = ffi.new('b2f_stream*[1]')
+      check(lib.b2f_stream_open(ctx, cams, bytes and 2 or 1, height, width, pst))
+      -- the finalizer captures ctx: the context cannot be collected (and b2f_destroy cannot close the stream under it) before the
+      -- stream's own finalizer has run
+      local st = ffi.gc(pst[0], function(p) lib.b2f_stream_close(p); ctx = nil end)
+      local S = {}
+      function S.push(frames, want_occ_prob)
+         assert((torch.type(frames) == 'torch.ByteTensor') == (bytes and true or false),
+                bytes and 'this stream takes ByteTensor frames' or 'this stream takes float frames in [0,1], not a ByteTensor')
+         local f = bytes and frames:contiguous() or frames:float():contiguous()
+         assert(f:nElement() == cams * 3 * height * width, 'expected cams x 3 x H x W frames')
+         local flow_est, fwd_occ_est, bwd_occ_est, occ_prob = f32_outputs(cams, height, width, want_occ_prob)
+         local ready = ffi.new('int[1]')
+         check(lib.b2f_stream_push(st, f:data(), flow_est:data(), occ_prob and occ_prob:data() or nil, fwd_occ_est:data(),
+                                   bwd_occ_est:data(), ready))
+         if ready[0] == 0 then return nil end
+         return flow_est, fwd_occ_est, bwd_occ_est, occ_prob
+      end
+      function S.reset() check(lib.b2f_stream_reset(st)) end
+      function S.framesPushed()
+         local n = ffi.new('long long[1]')
+         check(lib.b2f_stream_info(st, nil, nil, nil, nil, n))
+         return tonumber(n[0])
+      end
+      function S.close()
+         if st then lib.b2f_stream_close(ffi.gc(st, nil)); st = nil end
+      end
+      return S
+   end
+   return computeFlow, computeFlowSequence, computeFlowBatchF32, computeFlowSequenceF32, openStream
 end
 M.init = init
 
