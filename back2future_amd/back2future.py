@@ -25,6 +25,9 @@ occ_threshold = 0.6666                                                     # bac
 IN_NORMALIZED, IN_UNIT, IN_U8 = 0, 1, 2
 # layout of the flow pictures (include/b2f.h): n x 3 x H x W, the reference's tensor order, or n x H x W x 3
 RGB_PLANAR, RGB_PACKED = 0, 1
+# words of a score record (include/b2f.h, B2F_SCORE_*): counted pixels, Q20 error sums and Fl outliers per bucket (0 occluded "bwd",
+# 1 visible, 2 occluded "fwd", 3 unlabelled), the 3 x 3 occlusion matrix (ground-truth class major), NaN errors
+SCORE_PIXELS, SCORE_EPE_Q20, SCORE_OUTLIERS, SCORE_OCC, SCORE_NONFINITE, SCORE_WORDS = 0, 4, 8, 12, 21, 22
 
 
 def normalize(imgs):
@@ -328,6 +331,108 @@ class FlowStream(object):
         return bool(ready.value)
 
 
+def score_ground_truth(n, H, W, gt_flow, valid, gt_occ, who):
+    """The ground truth of the score wrappers in the library's layouts: gt_flow float32 n x 2 x H x W (pixels, as a .flo file holds
+    them), valid and gt_occ uint8 n x H x W or None (n x 1 x H x W and bool are taken too).  Arrays that already have the layout
+    are passed as they are, so page-locked ones stay page-locked.  Raises ValueError before any library call."""
+    gt = np.asarray(gt_flow)
+    if gt.shape != (n, 2, H, W):
+        raise ValueError("%s: gt_flow must have shape %r, got %r" % (who, (n, 2, H, W), gt.shape))
+    planes = []
+    for name, a in (("valid", valid), ("gt_occ", gt_occ)):
+        if a is None:
+            planes.append(None)
+            continue
+        a = np.asarray(a)
+        if a.shape == (n, 1, H, W):
+            a = a.reshape(n, H, W)
+        if a.shape != (n, H, W) or a.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+            raise ValueError("%s: %s must be uint8 (or bool) of shape %r, got %s %r" % (who, name, (n, H, W), a.dtype, a.shape))
+        planes.append(np.ascontiguousarray(a).view(np.uint8))
+    return _lib.f32(gt), planes[0], planes[1]
+
+
+def _score_outputs(n, H0, W0, want_flow, want_masks, out, who):
+    """(scores, flow or None, fwd or None, bwd or None) for the score entries; out = (scores[, flow][, fwd_occ, bwd_occ]), the buffers
+    the call returns (page-locked ones are written by DMA), or new arrays."""
+    spec = [(np.uint64, (n, SCORE_WORDS))]
+    spec += [(np.float32, (n, 2, H0, W0))] if want_flow else []
+    spec += [(np.uint8, (n, 1, H0, W0))] * 2 if want_masks else []
+    if out is None:
+        bufs = [np.empty(shape, dt) for dt, shape in spec]
+    else:
+        bufs = [out] if isinstance(out, np.ndarray) else list(out)
+        if len(bufs) != len(spec):
+            raise ValueError("%s: out must be (scores%s%s)" % (who, ", flow" if want_flow else "", ", fwd_occ, bwd_occ" if want_masks else ""))
+        for i, (a, (dt, shape)) in enumerate(zip(bufs, spec)):
+            if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
+                raise ValueError("%s: out[%d] must be a writeable C-contiguous %s array of shape %s" % (who, i, np.dtype(dt).name, shape))
+    rest = bufs[1:]
+    flow = rest.pop(0) if want_flow else None
+    fwd, bwd = rest if want_masks else (None, None)
+    return bufs[0], flow, fwd, bwd
+
+
+def _call_score(fn, h, count, in_kind, ins, H0, W0, flow_scale, truth, outs):
+    gt, valid, gt_occ = truth
+    scores, flow, fwd, bwd = outs
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+    _lib.check(getattr(_lib.lib(), fn)(h, count, in_kind, *[C.c_void_p(a.ctypes.data) for a in ins], H0, W0, float(flow_scale), _lib.fptr(gt),
+                                       u8p(valid), u8p(gt_occ), scores.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                       _lib.fptr(flow) if flow is not None else None, u8p(fwd), u8p(bwd)))
+    res = tuple(a for a in outs if a is not None)
+    return res[0] if len(res) == 1 else res
+
+
+def _compute_flow_batch_score(prefix, h, im1, im2, im3, gt_flow, valid, gt_occ, flow_scale, want_flow, want_masks, out):
+    """computeFlowBatchScore of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    who = "computeFlowBatchScore"
+    arrs = [np.asarray(a) for a in (im1, im2, im3)]
+    if any(a.ndim != 4 or a.shape[1] != 3 or a.shape[0] < 1 for a in arrs) or len({a.shape for a in arrs}) > 1:
+        raise ValueError("%s: expected three n x 3 x H x W arrays of one shape" % who)
+    im1, im2, im3, as_bytes = _batch_inputs(*arrs)
+    n, _, H0, W0 = im1.shape
+    truth = score_ground_truth(n, H0, W0, gt_flow, valid, gt_occ, who)
+    outs = _score_outputs(n, H0, W0, want_flow, want_masks, out, who)
+    return _call_score(prefix + "compute_flow_batch_score", h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0, flow_scale, truth, outs)
+
+
+def _compute_flow_sequence_score(prefix, h, frames, gt_flow, valid, gt_occ, flow_scale, want_flow, want_masks, out):
+    """computeFlowSequenceScore of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    who = "computeFlowSequenceScore"
+    v, as_bytes = sequence_frames(frames)
+    T, _, H0, W0 = v.shape
+    truth = score_ground_truth(T - 2, H0, W0, gt_flow, valid, gt_occ, who)
+    outs = _score_outputs(T - 2, H0, W0, want_flow, want_masks, out, who)
+    return _call_score(prefix + "compute_flow_sequence_score", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0, flow_scale, truth, outs)
+
+
+def score_summary(scores):
+    """The measures of test.lua:183-261 from score records (n x 22 or 22 uint64 words; ops.flow_score, computeFlow*Score), summed over
+    the images given: a dict of
+      epe       mean end-point error in pixels over the counted pixels (criterions/L2Criterion.lua:36-38 times flownet_factor)
+      epe_noc   the same over the pixels labelled visible (bucket 1), epe_occ over the occluded ones (buckets 0 and 2)
+      fl        share of the counted pixels whose error exceeds 3 px and 5 % of the ground truth (KITTI's Fl)
+      oacc      share of the labelled pixels whose occlusion class is right (test.lua:241-242); occ_acc_bwd / occ_acc_vis /
+                occ_acc_fwd: the same within ground-truth class 0 / 0.5 / 1 (test.lua:244-259)
+      pixels    counted pixels, nonfinite: valid pixels whose error was NaN (counted nowhere else)
+    A ratio whose denominator is 0 is nan.  The sums are exact integers; the errors carry the records' Q20 rounding (2^-21 px)."""
+    s = np.asarray(scores)
+    if s.dtype != np.uint64 or s.shape[-1:] != (SCORE_WORDS,) or s.ndim not in (1, 2):
+        raise ValueError("score_summary: expected uint64 records of %d words, got %s %r" % (SCORE_WORDS, s.dtype, s.shape))
+    t = [sum(int(v) for v in col) for col in s.reshape(-1, SCORE_WORDS).T]   # Python integers: no overflow over many images
+    pix, epe, out = t[SCORE_PIXELS:SCORE_PIXELS + 4], t[SCORE_EPE_Q20:SCORE_EPE_Q20 + 4], t[SCORE_OUTLIERS:SCORE_OUTLIERS + 4]
+    occ = [t[SCORE_OCC + 3 * g:SCORE_OCC + 3 * g + 3] for g in range(3)]
+    ratio = lambda a, b: a / b if b else float("nan")
+    px = lambda q, k: ratio(q / float(1 << 20), k)
+    return {"epe": px(sum(epe), sum(pix)), "epe_noc": px(epe[1], pix[1]), "epe_occ": px(epe[0] + epe[2], pix[0] + pix[2]),
+            "fl": ratio(sum(out), sum(pix)),
+            "oacc": ratio(sum(occ[g][g] for g in range(3)), sum(map(sum, occ))),
+            "occ_acc_bwd": ratio(occ[0][0], sum(occ[0])), "occ_acc_vis": ratio(occ[1][1], sum(occ[1])),
+            "occ_acc_fwd": ratio(occ[2][2], sum(occ[2])),
+            "pixels": sum(pix), "nonfinite": t[SCORE_NONFINITE]}
+
+
 class Model(object):
     """Owns a b2f_ctx (the `model` global of back2future.lua:113)."""
 
@@ -505,6 +610,33 @@ class Model(object):
         _lib.check(_lib.lib().b2f_flow_rgb_device(self._h, p(d_flow), int(n), int(H), int(W), max_norm, RGB_PACKED if packed else RGB_PLANAR,
                                                    p(d_rgb), p(d_max_used), p(stream)))
 
+    def computeFlowBatchScore(self, im1, im2, im3, gt_flow, valid=None, gt_occ=None, flow_scale=20.0, want_flow=False, want_masks=False,
+                              out=None):
+        """computeFlowBatch scored against ground truth on the GPU (b2f_compute_flow_batch_score; test.lua:183-261): returns the
+        records, uint64 n x 22 (score_summary turns them into EPE, Fl and the occlusion accuracies) -- alone, or as
+        (scores[, flow][, fwd_occ, bwd_occ]) with want_flow / want_masks, which append the float32 flow and the masks of
+        computeFlowBatch(dtype=np.float32); what is not asked for is not downloaded.  gt_flow: float32 n x 2 x H x W in pixels
+        (.flo); valid: uint8 n x H x W, nonzero = counted (None: every pixel); gt_occ: uint8 n x H x W, 0 / 1 / 2 = occluded
+        "bwd" / visible / occluded "fwd", other bytes unlabelled (None: no split, no occlusion accuracies); flow_scale: pixels per
+        unit of raw flow (20 for the shipped models).  The words are ops.flow_score of the float32 flow and occ_prob."""
+        return _compute_flow_batch_score("b2f_", self._h, im1, im2, im3, gt_flow, valid, gt_occ, flow_scale, want_flow, want_masks, out)
+
+    def computeFlowSequenceScore(self, frames, gt_flow, valid=None, gt_occ=None, flow_scale=20.0, want_flow=False, want_masks=False, out=None):
+        """computeFlowSequence scored against ground truth (b2f_compute_flow_sequence_score): ground truth i belongs to output i,
+        the flow of centre frame i + 1; keywords and results as for computeFlowBatchScore with n = T - 2."""
+        return _compute_flow_sequence_score("b2f_", self._h, frames, gt_flow, valid, gt_occ, flow_scale, want_flow, want_masks, out)
+
+    def flowScoreDevice(self, d_flow, n, H, W, d_gt_flow, d_scores, d_occ_prob=None, d_valid=None, d_gt_occ=None, flow_scale=20.0, stream=None):
+        """b2f_flow_score_device on device pointers (ints): the records (n x 22 uint64 in d_scores) of an n x 2 x H x W float32 flow
+        against d_gt_flow (n x 2 x H x W float32), d_valid / d_gt_occ (n x H x W bytes) and d_occ_prob (n x 2 x H x W float32), all
+        optional but the first.  Asynchronous on `stream`: after computeFlowDevice on the same stream it needs no synchronisation
+        in between."""
+        if n < 1 or H < 1 or W < 1:
+            raise ValueError("flowScoreDevice: bad shape %r" % ((n, H, W),))
+        p = lambda v: C.c_void_p(v) if v else None
+        _lib.check(_lib.lib().b2f_flow_score_device(self._h, p(d_flow), p(d_occ_prob), int(n), int(H), int(W), float(flow_scale), p(d_gt_flow),
+                                                     p(d_valid), p(d_gt_occ), p(d_scores), p(stream)))
+
     def output_shapes(self, H, W):
         cap = 32
         ch, oh, ow = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
@@ -591,6 +723,16 @@ class MultiModel(object):
     def computeFlowSequenceRGB(self, frames, max=None, packed=False, want_flow=False, want_masks=False, out=None):
         """Model.computeFlowSequenceRGB over the GPUs, with the same keywords and the same bytes."""
         return _compute_flow_sequence_rgb("b2f_multi_", self._h, frames, max, packed, want_flow, want_masks, out)
+
+
+    def computeFlowBatchScore(self, im1, im2, im3, gt_flow, valid=None, gt_occ=None, flow_scale=20.0, want_flow=False, want_masks=False,
+                              out=None):
+        """Model.computeFlowBatchScore over the GPUs, with the same keywords and the same words."""
+        return _compute_flow_batch_score("b2f_multi_", self._h, im1, im2, im3, gt_flow, valid, gt_occ, flow_scale, want_flow, want_masks, out)
+
+    def computeFlowSequenceScore(self, frames, gt_flow, valid=None, gt_occ=None, flow_scale=20.0, want_flow=False, want_masks=False, out=None):
+        """Model.computeFlowSequenceScore over the GPUs, with the same keywords and the same words."""
+        return _compute_flow_sequence_score("b2f_multi_", self._h, frames, gt_flow, valid, gt_occ, flow_scale, want_flow, want_masks, out)
 
 
 def shard_range(n, rank, world):

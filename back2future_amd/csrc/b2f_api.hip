@@ -867,7 +867,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1001; }
+int b2f_version(void) { return 1002; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1568,3 +1568,21 @@ int b2f_op_conv_head16(b2f_ctx *c, const float *x, int B, int H, int W, const fl
 B2F_CATCH("b2f_op_conv_head16")
 
 }  // extern "C"
+
+// The profile bracket for launches outside this file (the score stage of b2f_pipeline.hip): with profile = 1, a row `name` of
+// b2f_profile_read timed by HIP events on the launch stream, like the rows of the forward pass
+bool b2f::prof_open(b2f_ctx *c, hipStream_t s, const char *name, ProfEvent *pe)
+{
+    if (!c->profile) return false;
+    pe->name = prof_id(c, name);
+    pe->a = get_event(c);
+    pe->b = get_event(c);
+    (void)hipEventRecord(pe->a, s);
+    return true;
+}
+
+void b2f::prof_close(b2f_ctx *c, hipStream_t s, const ProfEvent &pe)
+{
+    (void)hipEventRecord(pe.b, s);
+    c->prof_pending.push_back(pe);
+}

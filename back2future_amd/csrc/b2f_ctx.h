@@ -150,6 +150,10 @@ struct HostSlot {
     float *h_in = nullptr, *h_flow32 = nullptr, *h_prob = nullptr;
     unsigned char *h_fo = nullptr, *h_bo = nullptr, *h_rgb = nullptr;
     double *h_max = nullptr;
+    // score requests: the ground truth of the sub-batch (uploaded with the frames) and its records; staging for pageable buffers
+    float *d_gt = nullptr, *h_gt = nullptr;
+    unsigned char *d_valid = nullptr, *d_gtocc = nullptr, *h_valid = nullptr, *h_gtocc = nullptr;
+    unsigned long long *d_score = nullptr, *h_score = nullptr;
     hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
 };
 
@@ -157,7 +161,8 @@ struct HostSlot {
 // f64 path (flow64, both masks required) is the b2f_compute_flow* entries'; the f32 path (flow32) writes the same flow
 // rounded to fp32 and, when not nullptr, the occlusion probabilities and the masks.  rgb (f32 path only): the flow pictures of
 // b2f_compute_flow*_rgb (xy2rgb of the f32 flow, launch_flow_rgb) in rgb_layout with max_norm, rgb_max their maxima; the flow itself
-// is then optional.
+// is then optional.  scores (f32 path only): the records of b2f_compute_flow*_score (launch_flow_score of the f32 flow and occ_prob
+// against gt_flow / valid / gt_occ, which are inputs that travel with the outputs they belong to); the flow is optional there too.
 struct FlowOutputs {
     double *flow64 = nullptr;
     float *flow32 = nullptr, *occ_prob = nullptr;
@@ -167,13 +172,19 @@ struct FlowOutputs {
     double max_norm = 0.0;
     int rgb_layout = B2F_RGB_PLANAR;
     bool pictures = false;         // an rgb request: rgb is required (check_request), flow32 is not
+    unsigned long long *scores = nullptr;
+    const float *gt_flow = nullptr;
+    const unsigned char *valid = nullptr, *gt_occ = nullptr;
+    double flow_scale = 0.0;
+    bool scoring = false;          // a score request: scores and gt_flow are required, flow32 is not
     bool f32() const { return flow64 == nullptr; }
     // the outputs of triplets b, b + 1, ... (planes of hw0 pixels); nullptr stays nullptr
     FlowOutputs from_triplet(size_t b, size_t hw0) const
     {
         auto at = [](auto *p, size_t off) { return p ? p + off : p; };
         return {at(flow64, b * 2 * hw0), at(flow32, b * 2 * hw0), at(occ_prob, b * 2 * hw0), at(fwd_occ, b * hw0), at(bwd_occ, b * hw0),
-                at(rgb, b * 3 * hw0), at(rgb_max, b), max_norm, rgb_layout, pictures};
+                at(rgb, b * 3 * hw0), at(rgb_max, b), max_norm, rgb_layout, pictures,
+                at(scores, b * B2F_SCORE_WORDS), at(gt_flow, b * 2 * hw0), at(valid, b * hw0), at(gt_occ, b * hw0), flow_scale, scoring};
     }
 };
 
@@ -182,6 +193,15 @@ inline FlowOutputs rgb_outputs(unsigned char *rgb, double *max_used, double max_
                                unsigned char *bwd_occ)
 {
     return {nullptr, flow, nullptr, fwd_occ, bwd_occ, rgb, max_used, max_norm, layout, true};
+}
+
+// the outputs (and the ground truth) of a b2f_*compute_flow_*_score entry
+inline FlowOutputs score_outputs(double flow_scale, const float *gt_flow, const unsigned char *valid, const unsigned char *gt_occ,
+                                 unsigned long long *scores, float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ)
+{
+    FlowOutputs o{nullptr, flow, nullptr, fwd_occ, bwd_occ};
+    o.scores = scores; o.gt_flow = gt_flow; o.valid = valid; o.gt_occ = gt_occ; o.flow_scale = flow_scale; o.scoring = true;
+    return o;
 }
 
 // One computeFlow call, whichever of the entry points it came through: n triplets (im1..im3, n x 3 x H0 x W0 each) or, with seq, the
@@ -445,6 +465,9 @@ struct b2f_ctx : b2f::KernelOpts {
 namespace b2f {
 // b2f_api.hip
 int check_shape(int B, int H, int W);
+// profile = 1: brackets a launch made outside b2f_api.hip with events on s, as a row `name` of b2f_profile_read (false: profiling is off)
+bool prof_open(b2f_ctx *c, hipStream_t s, const char *name, ProfEvent *pe);
+void prof_close(b2f_ctx *c, hipStream_t s, const ProfEvent &pe);
 void drop_graphs(b2f_ctx *c);
 void drop_gen_out(b2f_ctx *c);
 // model:forward on device pointers, optionally replayed from a hipGraph (see b2f_api.hip); seq: dev_in holds the B + 2 frames

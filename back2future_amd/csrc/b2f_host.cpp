@@ -3,6 +3,8 @@
 // does around model:forward runs on the device, b2f_boundary.hip).
 #include "b2f_host.h"
 #include "b2f_flowcolor.h"
+#include "b2f_flowscore.h"
+#include "../../include/b2f.h"
 
 #include <cmath>
 #include <cstdio>
@@ -172,6 +174,33 @@ void flow_rgb_host(const float *flow, int n, int H, int W, double max_norm, bool
             } else {
                 o[i] = c.r; o[hw + i] = c.g; o[2 * hw + i] = c.b;
             }
+        }
+    }
+}
+
+}  // namespace b2f
+
+// ---- flow scores on the CPU ------------------------------------------------------------------------------------------------------
+namespace b2f {
+
+void flow_score_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const float *gt_flow,
+                     const unsigned char *valid, const unsigned char *gt_occ, unsigned long long *scores)
+{
+    const size_t hw = (size_t)H * W;
+    for (int b = 0; b < n; ++b) {
+        const float *fx = flow + (size_t)b * 2 * hw, *fy = fx + hw, *gx = gt_flow + (size_t)b * 2 * hw, *gy = gx + hw;
+        const unsigned char *va = valid ? valid + (size_t)b * hw : nullptr, *lb = gt_occ ? gt_occ + (size_t)b * hw : nullptr;
+        const float *p0 = (occ_prob && gt_occ) ? occ_prob + (size_t)b * 2 * hw : nullptr, *p1 = p0 ? p0 + hw : nullptr;
+        unsigned long long *rec = scores + (size_t)b * B2F_SCORE_WORDS;
+        for (int k = 0; k < B2F_SCORE_WORDS; ++k) rec[k] = 0;
+        for (size_t i = 0; i < hw; ++i) {
+            const unsigned char label = lb ? lb[i] : 3;
+            const PixelScore s = score_flow_pixel(fx[i], fy[i], flow_scale, gx[i], gy[i], va ? va[i] : 1, label);
+            rec[B2F_SCORE_PIXELS + s.bucket] += s.counted;
+            rec[B2F_SCORE_EPE_Q20 + s.bucket] += s.q20;
+            rec[B2F_SCORE_OUTLIERS + s.bucket] += s.outlier;
+            rec[B2F_SCORE_NONFINITE] += s.nonfinite;
+            if (p0 && label <= 2) rec[B2F_SCORE_OCC + 3 * label + score_occ_class(p0[i], p1[i])] += 1;
         }
     }
 }

@@ -68,6 +68,11 @@ void random_weights(unsigned long long seed, bool past_flow, float gain, float *
 // n x H x W x 3 with packed; max_norm > 0 = the maximum of every image, else each image's own; max_used: n doubles or nullptr
 void flow_rgb_host(const float *flow, int n, int H, int W, double max_norm, bool packed, unsigned char *rgb, double *max_used);
 
+// The scores of a planar n x 2 x H x W fp32 flow against ground truth on the CPU (b2f_flowscore.h per pixel; b2f_flow_score_host):
+// scores n x B2F_SCORE_WORDS words; occ_prob, valid and gt_occ may be nullptr
+void flow_score_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const float *gt_flow,
+                     const unsigned char *valid, const unsigned char *gt_occ, unsigned long long *scores);
+
 // .t7 reader (b2f_t7.cpp): returns false and fills err on failure.
 bool load_t7(const std::string &path, std::vector<float> &flat, bool &past_flow, std::string &err);
 // any graph shape: infer = true takes win / levels / skip from the file, false checks the file against g (see b2f_t7.cpp)

@@ -330,4 +330,10 @@ hipError_t launch_unpack_u8(const unsigned char *in, size_t n, float *out, hipSt
 hipError_t launch_flow_rgb(const float *flow, int n, int H, int W, double max_norm, int layout, unsigned char *rgb, double *max_used,
                            hipStream_t s);
 
+// ---- flow scores (b2f_score.hip; the per-pixel function: b2f_flowscore.h) --------------------
+// The records (n x B2F_SCORE_WORDS words, zeroed on s first) of a planar n x 2 x H x W fp32 flow against gt_flow (n x 2 x H x W),
+// valid and gt_occ (n x H x W bytes or nullptr) and occ_prob (n x 2 x H x W or nullptr): one launch, H * W < 2^28
+hipError_t launch_flow_score(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const float *gt_flow,
+                             const unsigned char *valid, const unsigned char *gt_occ, unsigned long long *scores, hipStream_t s);
+
 }  // namespace b2f

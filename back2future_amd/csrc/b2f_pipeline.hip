@@ -44,6 +44,9 @@ struct SlotNeeds {
     bool rgb;          // d_rgb, d_max: an rgb request
     bool stage_rgb;    // h_rgb: pageable rgb buffer
     bool stage_max;    // h_max: pageable max_used buffer
+    bool score;        // d_gt, d_score: a score request
+    bool valid, gtocc; // d_valid, d_gtocc: the optional byte planes of the ground truth
+    bool stage_gt, stage_valid, stage_gtocc, stage_score;   // h_gt, h_valid, h_gtocc, h_score: pageable buffers
 };
 
 // carve the slot's device and pinned blobs for sub-batches of up to SB triplets; grows (never shrinks) the blobs
@@ -56,7 +59,10 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
                  n_f32 = align256((size_t)SB * 2 * hw0 * 4), n_occ = align256((size_t)SB * hw0);
     const size_t n_onet = q.occ_net ? n_flow : 0, n_prob = q.prob ? n_f32 : 0;
     const size_t n_rgb = q.rgb ? align256((size_t)SB * 3 * hw0) : 0, n_max = q.rgb ? align256((size_t)SB * sizeof(double)) : 0;
-    const size_t need_dev = n_up + n_u8 + n_in + n_tmp + n_flow + n_est3 + (same ? 0 : n_f32) + n_onet + n_prob + 2 * n_occ + n_rgb + n_max;
+    const size_t n_gt = q.score ? n_f32 : 0, n_va = q.valid ? n_occ : 0, n_lb = q.gtocc ? n_occ : 0,
+                 n_sc = q.score ? align256((size_t)SB * B2F_SCORE_WORDS * sizeof(unsigned long long)) : 0;
+    const size_t need_dev = n_up + n_u8 + n_in + n_tmp + n_flow + n_est3 + (same ? 0 : n_f32) + n_onet + n_prob + 2 * n_occ + n_rgb + n_max +
+                            n_gt + n_va + n_lb + n_sc;
     if (need_dev > hs.dev_bytes) {
         if (hs.dev) {
             HIPCHK(hipDeviceSynchronize());
@@ -80,10 +86,15 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.d_fo = (unsigned char *)d; d += n_occ;
     hs.d_bo = (unsigned char *)d; d += n_occ;
     hs.d_rgb = q.rgb ? (unsigned char *)d : nullptr; d += n_rgb;
-    hs.d_max = q.rgb ? (double *)d : nullptr;
+    hs.d_max = q.rgb ? (double *)d : nullptr; d += n_max;
+    hs.d_gt = q.score ? (float *)d : nullptr; d += n_gt;
+    hs.d_valid = q.valid ? (unsigned char *)d : nullptr; d += n_va;
+    hs.d_gtocc = q.gtocc ? (unsigned char *)d : nullptr; d += n_lb;
+    hs.d_score = q.score ? (unsigned long long *)d : nullptr;
     const size_t n_hf = q.stage_flow ? n_f32 : 0, n_hp = q.stage_prob ? n_f32 : 0;
     const size_t n_hr = q.stage_rgb ? n_rgb : 0, n_hm = q.stage_max ? n_max : 0;
-    const size_t need_pin = (q.stage_in ? n_up : 0) + n_u8 + n_hf + n_hp + (q.stage_masks ? 2 * n_occ : 0) + n_hr + n_hm;
+    const size_t n_hg = q.stage_gt ? n_gt : 0, n_hv = q.stage_valid ? n_va : 0, n_hl = q.stage_gtocc ? n_lb : 0, n_hs = q.stage_score ? n_sc : 0;
+    const size_t need_pin = (q.stage_in ? n_up : 0) + n_u8 + n_hf + n_hp + (q.stage_masks ? 2 * n_occ : 0) + n_hr + n_hm + n_hg + n_hv + n_hl + n_hs;
     if (need_pin > hs.pin_bytes) {
         if (hs.pin) {
             HIPCHK(hipDeviceSynchronize());
@@ -101,7 +112,11 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.h_fo = (unsigned char *)h; h += q.stage_masks ? n_occ : 0;
     hs.h_bo = (unsigned char *)h; h += q.stage_masks ? n_occ : 0;
     hs.h_rgb = (unsigned char *)h; h += n_hr;
-    hs.h_max = (double *)h;
+    hs.h_max = (double *)h; h += n_hm;
+    hs.h_gt = (float *)h; h += n_hg;
+    hs.h_valid = (unsigned char *)h; h += n_hv;
+    hs.h_gtocc = (unsigned char *)h; h += n_hl;
+    hs.h_score = (unsigned long long *)h;
     for (hipEvent_t *e : {&hs.ev_in, &hs.ev_comp, &hs.ev_out})
         if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return 0;
@@ -161,6 +176,8 @@ struct NetBuffers {
 // network as they are and the first conv kernel normalizes on the fly --, the forward pass, and outputs_f32_kernel into `out` (device
 // buffers at H0 x W0; nullptr: not written).  The flow of an f64 request is left unscaled: the host threads form `double * sc` (:80-84).
 // out.rgb: the pictures of that f32 flow (xy2rgb, b2f_vis.hip), read from out.flow32 or, at the network size, from net.flow itself.
+// out.scores: the records of that f32 flow and occ_prob against out.gt_flow / valid / gt_occ (device copies; b2f_score.hip), read like the
+// pictures' flow: from out.flow32 / out.occ_prob or, at the network size, from the network's own planes.
 // sp: a push of a stream -- the nb = cams frames go through the pyramid into the ring (net.scaled, where image.scale writes, is their
 // frame slot); the rest runs, and the outputs are written, only from the third push on.
 int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void *x, int kind, long planes, int nb, const NetBuffers &net,
@@ -179,6 +196,19 @@ int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void 
     if (out.rgb) {
         if (!out.flow32 && !g.same) return fail(std::string(r.who) + ": a picture of a rescaled flow needs the flow buffer");
         HIPCHK(launch_flow_rgb(out.flow32 ? out.flow32 : net.flow, nb, g.H0, g.W0, out.max_norm, out.rgb_layout, out.rgb, out.rgb_max, s));
+    }
+    if (out.scores) {
+        const bool want_occ = out.gt_occ != nullptr;
+        if (!g.same && (!out.flow32 || (want_occ && !out.occ_prob)))
+            return fail(std::string(r.who) + ": the score of a rescaled flow needs the flow and occ_prob buffers");
+        const float *prob = !want_occ ? nullptr : g.same ? (g.C3 == 3 ? net.occ : net.est3) : out.occ_prob;
+        if (want_occ && !prob) return fail(std::string(r.who) + ": the occlusion scores need skip_occs[3]");
+        ProfEvent pe;
+        const bool timed = prof_open(c, s, "flow_score", &pe);
+        const hipError_t e = launch_flow_score(out.flow32 ? out.flow32 : net.flow, prob, nb, g.H0, g.W0, out.flow_scale, out.gt_flow, out.valid,
+                                               out.gt_occ, out.scores, s);
+        if (timed) prof_close(c, s, pe);
+        HIPCHK(e);
     }
     return 0;
 }
@@ -347,8 +377,15 @@ int b2f::check_request(const FlowRequest &r)
     if (r.H0 < 64 || r.W0 < 64) return fail(w + ": image smaller than 64 pixels");
     const FlowOutputs &o = r.o;
     // an rgb request (f32 path) needs its pictures and may leave the flow out
-    if (!r.im1 || (!r.seq && !r.stream && (!r.im2 || !r.im3)) || (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : !o.flow32))
+    // a score request (f32 path too) needs its records and the ground-truth flow
+    if (!r.im1 || (!r.seq && !r.stream && (!r.im2 || !r.im3)) ||
+        (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : o.scoring ? !o.scores || !o.gt_flow : !o.flow32))
         return fail(w + ": null argument");
+    if (o.scoring) {
+        if (!o.f32() || r.stream) return fail(w + ": scores are an output of the float32 batch and sequence entries");
+        if (!(o.flow_scale > 0.0) || !std::isfinite(o.flow_scale)) return fail(w + ": flow_scale must be finite and > 0");
+        if ((long long)r.H0 * r.W0 >= (1ll << 28)) return fail(w + ": images of 2^28 pixels or more are refused (the Q20 sums could overflow)");
+    }
     if (o.pictures && (!o.f32() || (o.rgb_layout != B2F_RGB_PLANAR && o.rgb_layout != B2F_RGB_PACKED)))
         return fail(w + ": bad layout (B2F_RGB_PLANAR or B2F_RGB_PACKED)");
     return 0;
@@ -374,7 +411,8 @@ int b2f::check_request(const FlowRequest &r)
 // every output in its final form (outputs_f32_kernel), so the drain step only copies -- or nothing at all: page-locked
 // flow / occ_prob / mask buffers are DMA'd in place -- and a NULL occ_prob or mask is neither written nor downloaded.  The pictures
 // and maxima of an rgb request (b2f_*_rgb) travel like occ_prob: slot buffers, DMA in place or staging + drain copy; its flow stays
-// on the device unless asked for.
+// on the device unless asked for.  A score request (b2f_*_score) uploads the ground truth of every sub-batch's outputs with its frames
+// (page-locked buffers in place, pageable ones through the slot's staging block) and downloads the 176-byte records.
 int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
 {
     CHK(check_context(c, r));
@@ -397,8 +435,11 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
     const int k_out[6] = {f32 ? out_kind(o.flow32, (size_t)n * 2 * hw0 * 4) : mem_kind(flow, (size_t)n * 2 * hw0 * 8), out_kind(fwd_occ, (size_t)n * hw0),
                           out_kind(bwd_occ, (size_t)n * hw0), out_kind(o.occ_prob, (size_t)n * 2 * hw0 * 4), out_kind(o.rgb, (size_t)n * 3 * hw0),
                           out_kind(o.rgb_max, (size_t)n * sizeof(double))};
+    // a score request: the ground truth (inputs; absent planes count as page-locked) and the records
+    const int k_gt[4] = {out_kind(o.gt_flow, (size_t)n * 2 * hw0 * 4), out_kind(o.valid, (size_t)n * hw0), out_kind(o.gt_occ, (size_t)n * hw0),
+                         out_kind(o.scores, (size_t)n * B2F_SCORE_WORDS * sizeof(unsigned long long))};
     for (int i = 0; i < 6; ++i)
-        if ((i < 3 && k_in[i] < 0) || k_out[i] < 0)
+        if ((i < 3 && k_in[i] < 0) || k_out[i] < 0 || (i < 4 && k_gt[i] < 0))
             return fail(w + ": device memory passed to a host-buffer entry point (use b2f_compute_flow_device / "
                             "b2f_compute_flow_sequence_device)");
     if (c->debug_fail_next) {   // tests (option debug_fail_next): one forced failure, e.g. on one replica of a b2f_multi
@@ -417,10 +458,15 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
     const bool stage_in = !pinned_in && !bytes_in;   // float staging buffer (byte inputs stage through h_u8)
     const bool stage_masks = !(k_out[1] == 1 && k_out[2] == 1);
     const bool want_prob = f32 && o.occ_prob;
+    const bool want_score = o.scores != nullptr;
+    // the occlusion scores read occ_prob on the device whether or not the caller downloads it
+    const bool need_prob = want_prob || (want_score && o.gt_occ);
     // f32 path: occ_prob is skip_occs[3] -- est[3] of a Soft model (d_est3), an extra forward output of a Hard one (d_occ)
     const bool want_rgb = o.rgb != nullptr;
-    SlotNeeds q{same, stage_in, stage_masks, use_u8, want_prob && g.C3 == 3, want_prob && !same, !f32 || k_out[0] != 1, want_prob && k_out[3] != 1,
-                want_rgb, want_rgb && k_out[4] != 1, want_rgb && k_out[5] != 1};
+    SlotNeeds q{same, stage_in, stage_masks, use_u8, need_prob && g.C3 == 3, need_prob && !same, !f32 || k_out[0] != 1, want_prob && k_out[3] != 1,
+                want_rgb, want_rgb && k_out[4] != 1, want_rgb && k_out[5] != 1,
+                want_score, want_score && o.valid, want_score && o.gt_occ, want_score && k_gt[0] != 1, want_score && o.valid && k_gt[1] != 1,
+                want_score && o.gt_occ && k_gt[2] != 1, want_score && k_gt[3] != 1};
     // (a sequence sub-batch's nb + 2 frames are 3 nb + 6 <= 9 nb planes: the triplet layout of the slot holds them)
     for (int k = 0; k < std::min(nsub, 2); ++k)
         CHK(ensure_slot(c, c->slot[k], SB, hw0, g.hw, g.H0, g.fw, g.C3, q));
@@ -461,6 +507,7 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
                     if (q.stage_prob) jobs.push_back({o.occ_prob + b0 * 2 * hw0, hs.h_prob, nb * 2 * hw0 * 4});
                     if (q.stage_rgb) jobs.push_back({o.rgb + b0 * 3 * hw0, hs.h_rgb, nb * 3 * hw0});
                     if (q.stage_max) jobs.push_back({o.rgb_max + b0, hs.h_max, nb * sizeof(double)});
+                    if (q.stage_score) jobs.push_back({o.scores + b0 * B2F_SCORE_WORDS, hs.h_score, nb * B2F_SCORE_WORDS * sizeof(unsigned long long)});
                 }
                 if (stage_masks) {
                     if (fwd_occ) jobs.push_back({fwd_occ + b0 * hw0, hs.h_fo, nb * hw0});
@@ -549,6 +596,17 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
                     HIPCHK(hipMemcpyAsync(dst + (size_t)f * 3 * hw0, src(b0 + t, f), 3 * hw0 * 4, hipMemcpyHostToDevice, c->s_in));
             }
         }
+        if (want_score) {   // the ground truth of the sub-batch's nb outputs goes up with its frames
+            struct Up { void *dev; void *pin; const void *host; size_t bytes; bool stage; };
+            const Up ups[3] = {{hs.d_gt, hs.h_gt, o.gt_flow + b0 * 2 * hw0, (size_t)nb * 2 * hw0 * 4, q.stage_gt},
+                               {hs.d_valid, hs.h_valid, o.valid ? o.valid + b0 * hw0 : nullptr, (size_t)nb * hw0, q.stage_valid},
+                               {hs.d_gtocc, hs.h_gtocc, o.gt_occ ? o.gt_occ + b0 * hw0 : nullptr, (size_t)nb * hw0, q.stage_gtocc}};
+            for (const Up &u : ups) {
+                if (!u.host) continue;
+                if (u.stage) c->pool_in->run({{u.pin, u.host, u.bytes}});
+                HIPCHK(hipMemcpyAsync(u.dev, u.stage ? u.pin : u.host, u.bytes, hipMemcpyHostToDevice, c->s_in));
+            }
+        }
         HIPCHK(hipEventRecord(hs.ev_in, c->s_in));
         // ---- kernels: after the upload, and after download k - 2 has read this set's output buffers
         HIPCHK(hipStreamWaitEvent(c->stream, hs.ev_in, 0));
@@ -562,7 +620,8 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
         CHK(run_kernels(c, r, g, direct_u8 ? (const void *)hs.d_u8 : hs.d_up, direct_u8 ? B2F_IN_U8 : B2F_IN_UNIT, (long)nu * fpu * 3, nb,
                         {hs.d_tmp, hs.d_in, hs.d_flow, hs.d_occ, hs.d_est3},
                         {nullptr, same ? nullptr : hs.d_flow32, q.prob ? hs.d_prob : nullptr, fwd_occ ? hs.d_fo : nullptr, bwd_occ ? hs.d_bo : nullptr,
-                         hs.d_rgb, hs.d_max, o.max_norm, o.rgb_layout},
+                         hs.d_rgb, hs.d_max, o.max_norm, o.rgb_layout, o.pictures,
+                         hs.d_score, hs.d_gt, hs.d_valid, hs.d_gtocc, o.flow_scale, o.scoring},
                         c->host_graph != 0, c->stream));
         HIPCHK(hipEventRecord(hs.ev_comp, c->stream));
         // ---- download: the set's pinned output buffers must have been handed over (k - 2 drained)
@@ -579,6 +638,9 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
             HIPCHK(hipMemcpyAsync(q.stage_rgb ? hs.h_rgb : o.rgb + b0 * 3 * hw0, hs.d_rgb, (size_t)nb * 3 * hw0, hipMemcpyDeviceToHost, c->s_out));
         if (o.rgb_max)
             HIPCHK(hipMemcpyAsync(q.stage_max ? hs.h_max : o.rgb_max + b0, hs.d_max, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, c->s_out));
+        if (want_score)
+            HIPCHK(hipMemcpyAsync(q.stage_score ? hs.h_score : o.scores + b0 * B2F_SCORE_WORDS, hs.d_score,
+                                  (size_t)nb * B2F_SCORE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_out));
         if (want_prob)
             HIPCHK(hipMemcpyAsync(q.stage_prob ? hs.h_prob : o.occ_prob + b0 * 2 * hw0, same ? occ_net : hs.d_prob, (size_t)nb * 2 * hw0 * 4,
                                   hipMemcpyDeviceToHost, c->s_out));
@@ -942,6 +1004,24 @@ int b2f_compute_flow_sequence_rgb(b2f_ctx *c, int T, int in_kind, const void *fr
                                                  rgb_outputs(rgb, max_used, max_norm, layout, flow, fwd_occ, bwd_occ)));
 }
 B2F_CATCH("b2f_compute_flow_sequence_rgb")
+
+int b2f_compute_flow_batch_score(b2f_ctx *c, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0, double flow_scale,
+                                 const float *gt_flow, const unsigned char *valid, const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                 unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0,
+                                              score_outputs(flow_scale, gt_flow, valid, gt_occ, scores, flow, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_batch_score")
+
+int b2f_compute_flow_sequence_score(b2f_ctx *c, int T, int in_kind, const void *frames, int H0, int W0, double flow_scale, const float *gt_flow,
+                                    const unsigned char *valid, const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                    unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, sequence_request(__func__, T, in_kind, frames, H0, W0,
+                                                 score_outputs(flow_scale, gt_flow, valid, gt_occ, scores, flow, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_sequence_score")
 
 int b2f_compute_flow_device(b2f_ctx *c, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, int H0, int W0,
                             float *dev_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream) try

@@ -127,3 +127,33 @@ def flow_rgb(flow, max=None, packed=False, model=None):
     else:
         _lib.check(_lib.lib().b2f_op_flow_rgb(_h(model), *args))
     return (rgb[0] if single else rgb), mx
+
+
+def flow_score(flow, gt_flow, occ_prob=None, valid=None, gt_occ=None, flow_scale=20.0, model=None):
+    """The score records of test.lua:183-261 (masked end-point error of criterions/L2Criterion.lua:36-38 split by the occlusion label,
+    KITTI's Fl, the occlusion confusion matrix): flow n x 2 x H x W float32 raw network flow, gt_flow the same shape in pixels,
+    occ_prob n x 2 x H x W float32, valid / gt_occ uint8 n x H x W (see Model.computeFlowBatchScore) -> uint64 (n, 22);
+    back2future.score_summary turns them into EPE, Fl and the accuracies.  model=None computes on the CPU (b2f_flow_score_host, no
+    GPU), a Model on its GPU (b2f_op_flow_score): the words are the same."""
+    from .back2future import SCORE_WORDS, score_ground_truth
+    f = np.asarray(flow)
+    if f.ndim != 4 or f.shape[1] != 2 or min(f.shape) < 1:
+        raise ValueError("flow_score: expected an n x 2 x H x W flow, got shape %r" % (np.shape(flow),))
+    f = _lib.f32(f)
+    n, _, H, W = f.shape
+    gt, va, lb = score_ground_truth(n, H, W, gt_flow, valid, gt_occ, "flow_score")
+    prob = None
+    if occ_prob is not None:
+        prob = np.asarray(occ_prob)
+        if prob.shape != f.shape:
+            raise ValueError("flow_score: occ_prob must have the flow's shape %r, got %r" % (f.shape, prob.shape))
+        prob = _lib.f32(prob)
+    scores = np.empty((n, SCORE_WORDS), np.uint64)
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+    args = (_lib.fptr(f), _lib.fptr(prob) if prob is not None else None, n, H, W, float(flow_scale), _lib.fptr(gt), u8p(va), u8p(lb),
+            scores.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+    if model is None:
+        _lib.check(_lib.lib().b2f_flow_score_host(*args))
+    else:
+        _lib.check(_lib.lib().b2f_op_flow_score(_h(model), *args))
+    return scores

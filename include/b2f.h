@@ -291,6 +291,72 @@ B2F_API int b2f_multi_compute_flow_batch_rgb(b2f_multi *m, int n, int in_kind, c
 B2F_API int b2f_multi_compute_flow_sequence_rgb(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
                                         double max_norm, int layout, unsigned char *rgb, double *max_used,
                                         float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* ---- scores against ground truth: the evaluation of test.lua:183-261 as an output stage ----
+ * What a benchmark run does with every flow: the masked end-point error (criterions/L2Criterion.lua:36-38, times
+ * flownet_factor, test.lua:190-192), the same error split by the ground truth's occlusion label (test.lua:195-223), KITTI's
+ * outlier rate "Fl", and the occlusion confusion matrix behind oacc / occ_acc_* (test.lua:236-259).  Inputs per image, H x W:
+ *   flow        n x 2 x H x W floats: raw network flow (what the f32 entries return)
+ *   occ_prob    n x 2 x H x W floats or NULL: what the f32 entries return
+ *   flow_scale  finite, > 0: pixels per unit of raw flow; 20 for the shipped models (opts.lua flownet_factor)
+ *   gt_flow     n x 2 x H x W floats in pixels, as a .flo file holds them
+ *   valid       n x H x W bytes or NULL: nonzero = the pixel counts (the `masks` of test.lua); NULL = every pixel
+ *   gt_occ      n x H x W bytes or NULL: 0 / 1 / 2 = the labels 0 / 0.5 / 1 of test.lua:240-259 (occluded "bwd", visible,
+ *               occluded "fwd"), any other byte = unlabelled
+ * A pixel with valid != 0: err = |flow * flow_scale - gt_flow| in fp64 (sqrt(dy * dy + dx * dx), no fused multiply-adds), bucket
+ * k = min(gt_occ, 3) (3 without gt_occ).  A NaN err adds 1 to NONFINITE and nothing else; otherwise PIXELS[k] += 1,
+ * EPE_Q20[k] += (unsigned long long)(min(err, 65536) * 2^20 + 0.5), OUTLIERS[k] += (err > 3 && err > 0.05 * |gt_flow|).  Invalid
+ * pixels' values enter nothing (Sintel's 1e9 marker, NaN).  With gt_occ and occ_prob, every pixel with gt_occ <= 2 -- valid or
+ * not: test.lua:241-242 divides by nElement -- adds 1 to OCC[gt_occ][c], c = roundf((1 - p0) + p1) in fp32 (test.lua:236; halves
+ * away from zero, NaN = 0) clamped to 0 .. 2.
+ * scores: n records of B2F_SCORE_WORDS unsigned 64-bit words (176 bytes).  The sums are integers, so a record is the same words on
+ * the host and on the device, whatever the order of the additions and wherever sub-batches or GPU shards are cut.  Images of
+ * 2^28 pixels or more are refused (the Q20 sum could overflow).                                                              */
+enum {
+    B2F_SCORE_PIXELS = 0,      /* [4]  counted pixels per bucket */
+    B2F_SCORE_EPE_Q20 = 4,     /* [4]  sum of the errors, 2^-20 px */
+    B2F_SCORE_OUTLIERS = 8,    /* [4]  Fl outliers */
+    B2F_SCORE_OCC = 12,        /* [3][3] ground-truth class major, predicted class minor */
+    B2F_SCORE_NONFINITE = 21,  /* valid pixels with a NaN error */
+    B2F_SCORE_WORDS = 22
+};
+/* host only, no GPU: test.lua:183-261 / L2Criterion.lua:36-38 per pixel on the CPU */
+B2F_API int b2f_flow_score_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+                        const float *gt_flow, const unsigned char *valid, const unsigned char *gt_occ,
+                        unsigned long long *scores);
+/* test.lua:183-261 / L2Criterion.lua:36-38 on device pointers (16-byte aligned), asynchronous on `stream` like
+ * b2f_flow_rgb_device: right behind b2f_compute_flow_device or b2f_stream_push_device on the same stream it needs no
+ * synchronisation in between.  dev_scores (n x 22 words) is zeroed on the stream first.                                  */
+B2F_API int b2f_flow_score_device(b2f_ctx *ctx, const float *dev_flow, const float *dev_occ_prob, int n, int H, int W,
+                          double flow_scale, const float *dev_gt_flow, const unsigned char *dev_valid,
+                          const unsigned char *dev_gt_occ, unsigned long long *dev_scores, void *stream);
+/* test.lua:183-261 / L2Criterion.lua:36-38 on host pointers through the GPU, like b2f_op_flow_rgb */
+B2F_API int b2f_op_flow_score(b2f_ctx *ctx, const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+                      const float *gt_flow, const unsigned char *valid, const unsigned char *gt_occ,
+                      unsigned long long *scores);
+/* computeFlow with scores (test.lua:183-261 / L2Criterion.lua:36-38 behind back2future.lua:47-95): the f32 entries' inputs plus
+ * the ground truth, n x ... like the outputs -- record i belongs to output i, i.e. to centre frame i + 1 of a sequence.  scores
+ * (n x 22 words) is required; flow, fwd_occ and bwd_occ are optional (NULL: neither written nor downloaded), so a benchmark run
+ * downloads 176 bytes per triplet instead of 10 per pixel.  The scores are b2f_op_flow_score of the float32 flow and occ_prob
+ * the f32 entries return, and the other outputs are theirs, bit for bit.  The ground truth is uploaded with the frames
+ * (page-locked buffers in place).  A context made with b2f_init_ex options runs the batch entries; the sequence entries are
+ * refused there.                                                                                                          */
+B2F_API int b2f_compute_flow_batch_score(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                 int H0, int W0, double flow_scale, const float *gt_flow, const unsigned char *valid,
+                                 const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                 unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_compute_flow_sequence_score(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                    double flow_scale, const float *gt_flow, const unsigned char *valid,
+                                    const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                    unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* test.lua:183-261 / L2Criterion.lua:36-38 over several GPUs: sharded like the f32 entries, one context's words */
+B2F_API int b2f_multi_compute_flow_batch_score(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                       int H0, int W0, double flow_scale, const float *gt_flow, const unsigned char *valid,
+                                       const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                       unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_sequence_score(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                          double flow_scale, const float *gt_flow, const unsigned char *valid,
+                                          const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                          unsigned char *fwd_occ, unsigned char *bwd_occ);
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature

@@ -69,6 +69,31 @@ int  b2f_stream_push_rgb(b2f_stream *st, const void *frames, double max_norm, in
                          double *max_used, float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ, int *ready);
 int  b2f_stream_push_device(b2f_stream *st, const void *dev_frames, float *dev_flow, float *dev_occ_prob,
                             unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream, int *ready);
+enum {
+    B2F_SCORE_PIXELS = 0,
+    B2F_SCORE_EPE_Q20 = 4,
+    B2F_SCORE_OUTLIERS = 8,
+    B2F_SCORE_OCC = 12,
+    B2F_SCORE_NONFINITE = 21,
+    B2F_SCORE_WORDS = 22
+};
+int b2f_flow_score_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+                        const float *gt_flow, const unsigned char *valid, const unsigned char *gt_occ,
+                        unsigned long long *scores);
+int b2f_flow_score_device(b2f_ctx *ctx, const float *dev_flow, const float *dev_occ_prob, int n, int H, int W,
+                          double flow_scale, const float *dev_gt_flow, const unsigned char *dev_valid,
+                          const unsigned char *dev_gt_occ, unsigned long long *dev_scores, void *stream);
+int b2f_op_flow_score(b2f_ctx *ctx, const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+                      const float *gt_flow, const unsigned char *valid, const unsigned char *gt_occ,
+                      unsigned long long *scores);
+int b2f_compute_flow_batch_score(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                 int H0, int W0, double flow_scale, const float *gt_flow, const unsigned char *valid,
+                                 const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                 unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_compute_flow_sequence_score(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                    double flow_scale, const float *gt_flow, const unsigned char *valid,
+                                    const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                    unsigned char *fwd_occ, unsigned char *bwd_occ);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -84,6 +109,14 @@ int b2f_multi_compute_flow_batch_rgb(b2f_multi *m, int n, int in_kind, const voi
 int b2f_multi_compute_flow_sequence_rgb(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
                                         double max_norm, int layout, unsigned char *rgb, double *max_used,
                                         float *flow, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_compute_flow_batch_score(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                       int H0, int W0, double flow_scale, const float *gt_flow, const unsigned char *valid,
+                                       const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                       unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_compute_flow_sequence_score(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                          double flow_scale, const float *gt_flow, const unsigned char *valid,
+                                          const unsigned char *gt_occ, unsigned long long *scores, float *flow,
+                                          unsigned char *fwd_occ, unsigned char *bwd_occ);
 ]]
 
 local lib = ffi.load(os.getenv('B2F_LIB') or 'libb2f.so')
