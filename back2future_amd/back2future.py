@@ -514,11 +514,15 @@ class Model(object):
 
     def profile_read(self):
         cap = 256
-        names = C.create_string_buffer(32 * cap)
-        ms = (C.c_double * cap)()
-        cnt = (C.c_longlong * cap)()
-        n = C.c_int()
-        _lib.check(_lib.lib().b2f_profile_read(self._h, names, ms, cnt, cap, C.byref(n)))
+        while True:     # the library returns at most cap rows and keeps every row name a context has ever used: a full buffer may be cut
+            names = C.create_string_buffer(32 * cap)
+            ms = (C.c_double * cap)()
+            cnt = (C.c_longlong * cap)()
+            n = C.c_int()
+            _lib.check(_lib.lib().b2f_profile_read(self._h, names, ms, cnt, cap, C.byref(n)))
+            if n.value < cap:
+                break
+            cap *= 4
         out = {}
         for i in range(n.value):
             nm = names.raw[32 * i:32 * i + 32].split(b"\0", 1)[0].decode()

@@ -219,6 +219,42 @@ void fill_packings(const PackedConv &p, const float *w, const float *b, int ci, 
             kKernels[k].pack(w, b, p.cout, ci, cin_map, p.nchunks(), p.pk[k].nt, p.pk[k].nblk, host + p.pk[k].w_off, host + p.pk[k].b_off);
 }
 
+// The K-order of layer d: sets p.nseg and p.chunks and returns cin_map -- for packed input channel k (segment 0's chunks, then segment 1's)
+// the Torch input channel, or -1 (zero weights: channel padding, and the record slots this decoder does not read).
+std::vector<int> layer_cin_map(const ConvDesc &d, bool shipped, PackedConv &p)
+{
+    std::vector<int> m;
+    if (d.kind != KIND_FEAT && d.idx == 1 && shipped) {
+        const int Cl = kFeat[d.level];
+        const bool has_feat = d.ci >= kND + Cl;          // level-7 flow decoder takes the cost volume only
+        const bool has_flow = d.ci == kND + Cl + 2;
+        if (has_feat) {
+            p.nseg = 2;
+            p.chunks[0] = Cl / kCK;
+            for (int k = 0; k < Cl; ++k) m.push_back(kND + k);
+        } else {
+            p.nseg = 1;
+        }
+        p.chunks[p.nseg - 1] = kCvChunks;   // 21 chunks = 168 floats
+        // record slots: 0..79 fwd 0..79 | 80..159 bwd 0..79 | 160 fwd80 | 161 bwd80 | 162,163 ufs | 164,165 ubfs
+        const int flow_at = (d.kind == KIND_PAST) ? 164 : 162;   // pwc.lua:334 vs :337
+        for (int k = 0; k < kCvRec; ++k) {
+            int ci = -1;
+            if (k < 80) ci = k;                       // fwd channel k      (Torch cv channel k)
+            else if (k < 160) ci = 81 + (k - 80);     // bwd channel k - 80 (Torch cv channel 81 + ..)
+            else if (k == 160) ci = 80;
+            else if (k == 161) ci = 161;
+            else if (has_flow && k >= flow_at && k < flow_at + 2) ci = kND + Cl + (k - flow_at);
+            m.push_back(ci);
+        }
+    } else {
+        p.nseg = 1;
+        p.chunks[0] = (d.ci + kCK - 1) / kCK;
+        for (int k = 0; k < p.chunks[0] * kCK; ++k) m.push_back(k < d.ci ? k : -1);
+    }
+    return m;
+}
+
 int pack_all(b2f_ctx *c, const float *flat)
 {
     const size_t n = c->lay.size();
@@ -232,35 +268,7 @@ int pack_all(b2f_ctx *c, const float *flat)
         // the first conv of a convUnit has stride 2 (the level-1 unit of pwc_skip = 0 has stride 1, pwc.lua:172); the first decoder layer has two K segments
         const bool stride1 = !(d.kind == KIND_FEAT && d.idx == 1 && d.level >= 2);
         p.base = base_kernel(d.ci, d.co, stride1, d.kind != KIND_FEAT && d.idx == 1);
-        std::vector<int> &m = maps[i];
-        if (d.kind != KIND_FEAT && d.idx == 1 && c->g.shipped()) {
-            const int Cl = kFeat[d.level];
-            const bool has_feat = d.ci >= kND + Cl;          // level-7 flow decoder takes the cost volume only
-            const bool has_flow = d.ci == kND + Cl + 2;
-            if (has_feat) {
-                p.nseg = 2;
-                p.chunks[0] = Cl / kCK;
-                for (int k = 0; k < Cl; ++k) m.push_back(kND + k);
-            } else {
-                p.nseg = 1;
-            }
-            p.chunks[p.nseg - 1] = kCvChunks;   // 21 chunks = 168 floats
-            // record slots: 0..79 fwd 0..79 | 80..159 bwd 0..79 | 160 fwd80 | 161 bwd80 | 162,163 ufs | 164,165 ubfs
-            const int flow_at = (d.kind == KIND_PAST) ? 164 : 162;   // pwc.lua:334 vs :337
-            for (int k = 0; k < kCvRec; ++k) {
-                int ci = -1;
-                if (k < 80) ci = k;                       // fwd channel k      (Torch cv channel k)
-                else if (k < 160) ci = 81 + (k - 80);     // bwd channel k - 80 (Torch cv channel 81 + ..)
-                else if (k == 160) ci = 80;
-                else if (k == 161) ci = 161;
-                else if (has_flow && k >= flow_at && k < flow_at + 2) ci = kND + Cl + (k - flow_at);
-                m.push_back(ci);
-            }
-        } else {
-            p.nseg = 1;
-            p.chunks[0] = (d.ci + kCK - 1) / kCK;
-            for (int k = 0; k < p.chunks[0] * kCK; ++k) m.push_back(k < d.ci ? k : -1);
-        }
+        maps[i] = layer_cin_map(d, c->g.shipped(), p);
         place_packings(p, stride1, *c, &total);
     }
     c->first_w_off = total; total += 27 * 16;
@@ -826,6 +834,7 @@ const OptRow kOptions[] = {
     {"wino4_min_pixels", &b2f_ctx::wino4_min_pixels, OPT_ENV | OPT_SYNC, 0},
     {"adaptive_kernels", &b2f_ctx::adaptive_kernels, OPT_ENV | OPT_SYNC, 0},
     {"op_wino_split", &b2f_ctx::op_wino_split, OPT_ENV, 0},
+    {"op_hole_fill", &b2f_ctx::op_hole_fill, 0, 0},
     {"host_subbatch_pixels", nullptr, OPT_ENV, 0},   // long long b2f_ctx::host_subbatch_pixels
     {"host_threads", &b2f_ctx::host_threads, OPT_ENV, 0},
     {"host_u8", &b2f_ctx::host_u8, OPT_ENV, 0},
@@ -1531,6 +1540,132 @@ int b2f_op_conv3x3(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, cons
     return 0;
 }
 B2F_CATCH("b2f_op_conv3x3")
+
+// Conv (kind, level, idx) of the context's own packed table, launched exactly as the forward pass launches it: through run_conv, weights from
+// wpk_dev, the kernel by choose_kernel under the context's options with cur_batch = nimg, chunk-planar buffers, profile rows as in a forward.
+// x: nimg x Ci x H x W planar in the layer's Torch input order -- for a first decoder layer {cv 162, cs[ref] C_l, flow 2} (pwc.lua:308,334,337) --
+// scattered here into the feature segment and the cost-volume record (cv_slot, and the flow at the slots of the decoder's kind, as pack_all maps
+// them).  Every packed input channel that the layer's cin_map marks -1 -- the record slots this decoder does not read: the other decoder's
+// flow, slots 166 / 167, all six of level 7 -- is filled with the non-zero finite value 1 + op_hole_fill + slot / 256 (option op_hole_fill,
+// default 0): the layer's weights there are zero, so the result must not depend on them.  y: nimg x Co x Ho x Wo planar.
+// The shipped graph only; feat2.conv1 is launch_conv_first, not run_conv, and is refused.
+int b2f_op_layer(b2f_ctx *c, int kind, int level, int idx, int nimg, int H, int W, const float *x, float *y) try
+{
+    if (!c || !x || !y) return fail("b2f_op_layer: null argument");
+    if (!c->g.shipped()) return fail("b2f_op_layer: only the shipped graph (models/pwc.lua with the options of opts.lua) is covered");
+    if (nimg < 1 || H < 1 || W < 1) return fail("b2f_op_layer: bad size");
+    if (kind == KIND_FEAT && level == 2 && idx == 1) return fail("b2f_op_layer: feat2.conv1 runs in launch_conv_first, not in run_conv");
+    const int id = find_conv(c, kind, level, idx);
+    if (id < 0) return fail("b2f_op_layer: no conv (kind " + std::to_string(kind) + ", level " + std::to_string(level) + ", idx " + std::to_string(idx) + ") in this model");
+    if (!c->wpk_dev) return fail("b2f_op_layer: no weights loaded");
+    HIPCHK(hipSetDevice(c->device));
+    const ConvDesc &d = c->lay[(size_t)id];
+    const PackedConv &p = c->packed[(size_t)id];
+    PackedConv q;   // the layer's K order, as pack_all derived it: only nseg and chunks are set, cout and base are not
+    const std::vector<int> m = layer_cin_map(d, true, q);
+    if (q.nseg != p.nseg || q.chunks[0] != p.chunks[0] || (q.nseg == 2 && q.chunks[1] != p.chunks[1])) return fail("b2f_op_layer: the layer's K order is not the packed table's");
+    const int stride = (kind == KIND_FEAT && idx == 1) ? 2 : 1, leaky = (kind == KIND_FEAT || idx < 6) ? 1 : 0;
+    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1, Cop = (d.co + 7) / 8 * 8;
+    const size_t hw = (size_t)H * W, hwo = (size_t)Ho * Wo;
+    // host scatter: segment s is chunk-planar [image][chunk][H][W][8]
+    std::vector<float> host[2];
+    DevBuf dseg[2], dy;
+    ConvSeg segs[2];
+    for (int s = 0, k0 = 0; s < p.nseg; k0 += p.chunks[s] * kCK, ++s) {
+        const int Cs = p.chunks[s] * kCK;
+        host[s].resize((size_t)nimg * Cs * hw);
+        for (int n = 0; n < nimg; ++n)
+            for (int k = 0; k < Cs; ++k) {
+                const int ci = m[(size_t)(k0 + k)];
+                const float fill = 1.0f + (float)c->op_hole_fill + (float)k / 256.0f;
+                const float *src = ci >= 0 ? x + ((size_t)n * d.ci + ci) * hw : nullptr;
+                float *dst = host[s].data() + ((size_t)n * Cs + (size_t)(k / 8) * 8) * hw + (k & 7);
+                for (size_t i = 0; i < hw; ++i) dst[i * 8] = src ? src[i] : fill;
+            }
+        CHK(dseg[s].alloc(host[s].size() + 64));   // the arena rounds every buffer up to 64 floats (make_plan)
+        HIPCHK(hipMemset(dseg[s].p + host[s].size(), 0, 64 * sizeof(float)));
+        HIPCHK(hipMemcpy(dseg[s].p, host[s].data(), host[s].size() * sizeof(float), hipMemcpyHostToDevice));
+        segs[s] = cp8_seg(dseg[s].p, Cs, hw);
+    }
+    if (p.nseg == 1) segs[1] = segs[0];
+    const size_t ny = (size_t)nimg * Cop * hwo;
+    CHK(dy.alloc(ny));
+    HIPCHK(hipMemset(dy.p, 0, ny * sizeof(float)));
+    HIPCHK(hipDeviceSynchronize());   // the copies and the memset ran on the null stream, the layer runs on the context's
+    const int batch_before = c->cur_batch;   // run_conv chooses the kernel for a request of cur_batch triplets: nimg for this launch only
+    c->cur_batch = nimg;
+    const int rc = run_conv(c, c->stream, false, id, segs, nimg, H, W, stride, leaky, dy.p);
+    c->cur_batch = batch_before;
+    CHK(rc);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<float> out(ny);
+    HIPCHK(hipMemcpy(out.data(), dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
+    for (int n = 0; n < nimg; ++n)
+        for (int o = 0; o < d.co; ++o) {
+            const float *src = out.data() + ((size_t)n * Cop + (size_t)(o / 8) * 8) * hwo + (o & 7);
+            float *dst = y + ((size_t)n * d.co + o) * hwo;
+            for (size_t i = 0; i < hwo; ++i) dst[i] = src[i * 8];
+        }
+    return 0;
+}
+B2F_CATCH("b2f_op_layer")
+
+// launch_warp_costvol with the strides of the forward pass: the three maps (B x C x h x w planar here, C a multiple of 8) and the record
+// chunk-planar, flow / flow_b (B x 2 x h x w planar here, or NULL) as B x h x w x 2, the context's corr_variant.  rec: the whole record,
+// B x 168 x h x w planar in slot order (b2f_internal.h: fwd 0..79 | bwd 0..79 | fwd80 bwd80 u v ub vb 0 0).  The record buffer starts out as NaN, so a
+// slot the kernel does not write shows.
+int b2f_op_cv_record(b2f_ctx *c, const float *ref, const float *nbr_future, const float *nbr_past, const float *flow, const float *flow_b,
+                     float k, int B, int C, int h, int w, float *rec) try
+{
+    if (!c || !ref || !nbr_future || !nbr_past || !rec) return fail("b2f_op_cv_record: null argument");
+    if (B < 1 || C < 8 || C % 8 || h < 1 || w < 1) return fail("b2f_op_cv_record: bad shape (C must be a multiple of 8)");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw = (size_t)h * w, nmap = (size_t)B * C * hw, nrec = (size_t)B * kCvRec * hw, nfl = (size_t)B * 2 * hw;
+    DevBuf dmap[3], dfl[2], drec;
+    const float *maps[3] = {ref, nbr_future, nbr_past}, *flows[2] = {flow, flow_b};
+    std::vector<float> host(std::max(nmap, nrec));
+    for (int i = 0; i < 3; ++i) {
+        for (int b = 0; b < B; ++b)
+            for (int ch = 0; ch < C; ++ch) {
+                const float *src = maps[i] + ((size_t)b * C + ch) * hw;
+                float *dst = host.data() + ((size_t)b * C + (size_t)(ch / 8) * 8) * hw + (ch & 7);
+                for (size_t j = 0; j < hw; ++j) dst[j * 8] = src[j];
+            }
+        CHK(dmap[i].alloc(nmap));
+        HIPCHK(hipMemcpy(dmap[i].p, host.data(), nmap * sizeof(float), hipMemcpyHostToDevice));
+    }
+    for (int i = 0; i < 2; ++i) {
+        if (!flows[i]) continue;
+        for (int b = 0; b < B; ++b)
+            for (int ch = 0; ch < 2; ++ch)
+                for (size_t j = 0; j < hw; ++j) host[((size_t)b * hw + j) * 2 + ch] = flows[i][((size_t)b * 2 + ch) * hw + j];
+        CHK(dfl[i].alloc(nfl));
+        HIPCHK(hipMemcpy(dfl[i].p, host.data(), nfl * sizeof(float), hipMemcpyHostToDevice));
+    }
+    CHK(drec.alloc(nrec + 64));   // the slack the arena gives the record (make_plan)
+    HIPCHK(hipMemset(drec.p, 0xff, (nrec + 64) * sizeof(float)));
+    HIPCHK(hipDeviceSynchronize());
+    CorrLaunch cl;
+    cl.ref = dmap[0].p; cl.nbr_fut = dmap[1].p; cl.nbr_past = dmap[2].p;
+    cl.img_stride = (long)(hw * C); cl.chunk_stride = (long)(hw * 8); cl.pix_stride = 8;
+    cl.flow = dfl[0].p; cl.flow_b = dfl[1].p;
+    cl.k = k; cl.out = drec.p;
+    cl.out_img_stride = (long)(hw * kCvRec); cl.out_chunk_stride = (long)(hw * 8); cl.out_pix_stride = 8;
+    cl.B = B; cl.C = C; cl.h = h; cl.w = w;
+    cl.variant = c->corr_variant;
+    cl.ablate = c->corr_ablate;
+    HIPCHK(launch_warp_costvol(cl, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(host.data(), drec.p, nrec * sizeof(float), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b)
+        for (int slot = 0; slot < kCvRec; ++slot) {
+            const float *src = host.data() + ((size_t)b * kCvRec + (size_t)(slot / 8) * 8) * hw + (slot & 7);
+            float *dst = rec + ((size_t)b * kCvRec + slot) * hw;
+            for (size_t j = 0; j < hw; ++j) dst[j] = src[j * 8];
+        }
+    return 0;
+}
+B2F_CATCH("b2f_op_cv_record")
 
 int b2f_op_conv_head16(b2f_ctx *c, const float *x, int B, int H, int W, const float *w1, const float *b1, const float *w2,
                        const float *b2, float *y) try

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, weights
 
 
 def _h(model):
@@ -51,6 +51,37 @@ def conv3x3(model, x, w, b, stride=1, leaky=False):
     _lib.check(_lib.lib().b2f_op_conv3x3(_h(model), _lib.fptr(x), B, ci, H, W, _lib.fptr(w), _lib.fptr(b), co, stride,
                                          int(bool(leaky)), _lib.fptr(y)))
     return y
+
+
+KINDS = {"feat": 0, "occ": 1, "flow": 2, "past": 3}
+
+
+def layer(model, kind, level, idx, x):
+    """Conv (kind, level, idx) of the model's own packed weights on the launch path of the forward pass (chunk-planar buffers, the kernel the
+    model's options choose for a batch of len(x)); kind 'feat' / 'occ' / 'flow' / 'past'.  x: n x Ci x H x W in the layer's Torch input
+    order (a first decoder layer: {cv 162, cs[ref] C_l, flow 2}); returns n x Co x Ho x Wo."""
+    x = _lib.f32(x)
+    n, ci, H, W = x.shape
+    name = ("feat%d.conv%d" % (level, idx)) if kind == "feat" else "l%d.%s.conv%d" % (level, kind, idx)
+    co, ci_w = dict((nm, shape) for nm, shape, _ in weights.layout(model.past_flow)[0])[name + ".w"][:2]
+    if ci != ci_w:
+        raise ValueError("ops.layer: %s takes %d input channels, got %d" % (name, ci_w, ci))
+    stride = 2 if (kind == "feat" and idx == 1) else 1
+    y = np.empty((n, co, (H - 1) // stride + 1, (W - 1) // stride + 1), np.float32)
+    _lib.check(_lib.lib().b2f_op_layer(_h(model), KINDS[kind], level, idx, n, H, W, _lib.fptr(x), _lib.fptr(y)))
+    return y
+
+
+def cv_record(model, ref, nbr_future, nbr_past, flow, flow_b, k):
+    """The warp + cost-volume kernel on the forward's strides: the whole record, B x 168 x h x w in slot order; flow / flow_b may be None."""
+    ref, nf, npast = _lib.f32(ref), _lib.f32(nbr_future), _lib.f32(nbr_past)
+    B, Cc, h, w = ref.shape
+    fl = [_lib.f32(f) if f is not None else None for f in (flow, flow_b)]
+    assert all(f is None or f.shape == (B, 2, h, w) for f in fl)
+    rec = np.empty((B, 168, h, w), np.float32)
+    _lib.check(_lib.lib().b2f_op_cv_record(_h(model), _lib.fptr(ref), _lib.fptr(nf), _lib.fptr(npast), *[_lib.fptr(f) if f is not None else None for f in fl],
+                                           float(k), B, Cc, h, w, _lib.fptr(rec)))
+    return rec
 
 
 def conv_head16(model, x, w1, b1, w2, b2):

@@ -434,7 +434,9 @@ B2F_API int b2f_output_shapes(const b2f_ctx *ctx, int H, int W, int *ch, int *oh
  * B2F_<OPTION> as the initial value of the tuning options).                              */
 B2F_API int b2f_set_option(b2f_ctx *ctx, const char *key, int value);
 B2F_API int b2f_get_option(const b2f_ctx *ctx, const char *key, int *value);
-/* Per-kernel-class timings gathered while profile=1.  names: cap x 32 chars.        */
+/* Per-kernel-class timings gathered while profile=1.  names: cap x 32 chars.  A context keeps
+ * every row name it has used; *n = min(cap, rows): *n == cap means that rows may have been
+ * left out, *n < cap that these are all (call again with a larger cap).               */
 B2F_API int b2f_profile_read(b2f_ctx *ctx, char *names, double *total_ms, long long *launches,
                      int cap, int *n);
 B2F_API int b2f_profile_reset(b2f_ctx *ctx);
@@ -473,6 +475,19 @@ B2F_API int b2f_op_warp_costvol(b2f_ctx *ctx, const float *ref, const float *nbr
  * x: B x Ci x H x W, w: Co x Ci x 3 x 3, y: B x Co x Ho x Wo.                       */
 B2F_API int b2f_op_conv3x3(b2f_ctx *ctx, const float *x, int B, int Ci, int H, int W, const float *w,
                    const float *bias, int Co, int stride, int leaky, float *y);
+/* Two entries that run a piece of the loaded model in the forward pass's own layout (chunk-planar buffers, the context's packed
+ * weights and options), for the tests of tests/test_gpu_in_place.py.
+ * b2f_op_layer: conv (kind, level, idx) of the context's packed table -- kind 0 feature pyramid (level 2..7, idx 1..2; not feat2.conv1),
+ * 1 occlusion / 2 flow / 3 past-flow decoder (level 3..7, idx 1..6) -- through the launch path of the forward, the kernel chosen under the
+ * context's options for a batch of nimg.  x: nimg x Ci x H x W in the layer's Torch input order (a first decoder layer:
+ * {cv 162, cs[ref] C_l, flow 2}, pwc.lua:308,334,337), y: nimg x Co x Ho x Wo.  The cost-volume record slots the layer does not read
+ * hold 1 + op_hole_fill + slot / 256 (option op_hole_fill, default 0): non-zero, finite, and without effect on y.  Shipped graph only. */
+B2F_API int b2f_op_layer(b2f_ctx *ctx, int kind, int level, int idx, int nimg, int H, int W, const float *x, float *y);
+/* b2f_op_cv_record: the warp + cost-volume kernel on the forward's strides under option corr_variant.  ref / nbr_future / nbr_past:
+ * B x C x h x w (C a multiple of 8); flow, flow_b: B x 2 x h x w or NULL; rec: the whole record, B x 168 x h x w in slot order
+ * (fwd 0..79 | bwd 0..79 | fwd 80, bwd 80, flow u v, flow_b u v, 0, 0).                                                          */
+B2F_API int b2f_op_cv_record(b2f_ctx *ctx, const float *ref, const float *nbr_future, const float *nbr_past, const float *flow,
+                     const float *flow_b, float k, int B, int C, int h, int w, float *rec);
 /* The two 16-channel layers of the head of the pyramid as the pipeline runs them with option bf16_direct = 2, in one kernel:
  * nn.SpatialConvolution(16,16,3,3,1,1,1,1) + LeakyReLU(0.2) (pwc.lua:62, level-2 convUnit) followed by
  * nn.SpatialConvolution(16,32,3,3,2,2,1,1) + LeakyReLU(0.2) (pwc.lua:60, level-3 convUnit).

@@ -75,6 +75,97 @@ def test_full_table_vs_oracle(which, B, H, Wd):
     assert not worst, worst
 
 
+# ---- (a') the whole table under every kernel a user can select ----
+
+# Each setting also gets adaptive_kernels = 0 unless it sets that option.  Second entry: the profile tag (kKernels, csrc/b2f_api.hip) that
+# the first layer of the level-3 decoders -- two K segments, the record behind a permuted cin_map -- must run under, or None.
+KERNEL_SETTINGS = {
+    "f4x4": ({"wino4_min_pixels": 0, "wino6": 0}, "W4"),
+    "f6x6": ({"wino4_min_pixels": 0, "wino6": 1, "wino6_min_pixels": 0}, "W6"),
+    "wino1d-1": ({"wino4_min_pixels": 0, "wino6": 0, "wino1d": 1}, "V1"),
+    "wino1d-2": ({"wino4_min_pixels": 0, "wino6": 0, "wino1d": 2}, "V1"),
+    "bf16-wide": ({"wino4_min_pixels": 0, "bf16_conv": 3, "bf16_conv_min_pixels": 0}, "E1"),
+    "bf16_conv-0": ({"bf16_conv": 0}, None),
+    "s2_loader-0": ({"s2_loader": 0}, None),
+    "s2_loader-2": ({"s2_loader": 2}, None),
+    "adaptive": ({"adaptive_kernels": 1}, None),
+    "corr-0": ({"corr_variant": 0}, None),
+    "corr-1": ({"corr_variant": 1}, None),
+    "corr-3": ({"corr_variant": 3}, None),
+    "corr-5": ({"corr_variant": 5}, None),
+    "corr-7": ({"corr_variant": 7}, None),
+}
+# stride-2 layers of the pyramid (32 -> 64 ... 128 -> 192): the tags that must and must not appear
+STRIDE2_TAGS = {"bf16_conv-0": (["D2"], ["E2", "L2"]), "s2_loader-0": (["E2"], ["L2", "D2"]), "s2_loader-2": (["L2"], ["E2", "D2"])}
+
+_table_models = {}
+
+
+def _table_model(which, B, H, Wd):
+    """one context per model kind for the settings below, reloaded when the size (and with it the calibrated weights) changes"""
+    m, key = _table_models.get(which, (None, None))
+    if m is None:
+        m = back2future.Model("random:%s:%d:2.0" % (which, SEED))
+    if key != (B, H, Wd):
+        m.set_weights(_table_case(which, B, H, Wd)[1])
+        _table_models[which] = (m, (B, H, Wd))
+    return m
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _close_table_models():
+    yield
+    for m, _ in _table_models.values():
+        m.close()
+    _table_models.clear()
+
+
+@pytest.mark.parametrize("setting", list(KERNEL_SETTINGS))
+@pytest.mark.parametrize("B,H,Wd", TABLE_SIZES)
+@pytest.mark.parametrize("which", KINDS)
+def test_full_table_vs_oracle_under_every_kernel(which, B, H, Wd, setting):
+    """The contract of test_full_table_vs_oracle with the stride-1 layers, the stride-2 layers and the cost volume on each kernel an option
+    can put them on.  The full table is the only place where the past-flow decoders and flow_b run; at these sizes every map is below
+    wino4_min_pixels, so without the options all of it runs on the small-map kernels.  The profile rows say which kernel ran."""
+    past = which == "soft"
+    x, flat, exp, _ = _table_case(which, B, H, Wd)
+    D.assert_conditions(exp, past)
+    opts, tag = KERNEL_SETTINGS[setting]
+    m = _table_model(which, B, H, Wd)
+    with m.options(**dict({"adaptive_kernels": 0}, **opts)), m.options(profile=1, profile_layers=1):
+        m.profile_reset()
+        got = m.forward(x)
+        rows = {n: cnt for n, (ms, cnt) in m.profile_read().items() if cnt > 0}
+    assert len(got) == len(exp)
+    worst = []
+    for name, a, b in zip(_names(past), got, exp):
+        assert a.shape == b.shape and np.isfinite(a).all(), name
+        err = float(np.abs(a.astype(np.float64) - b).max())
+        print("table %s %dx%dx%d %-12s %-13s max|gpu - oracle| = %.3g  (max|oracle| = %.3g)" % (which, B, H, Wd, setting, name, err, float(np.abs(b).max())))
+        if not err <= BAR:
+            worst.append((name, err))
+    assert not worst, worst
+    h3, w3 = H // 4, Wd // 4
+    first3 = {n: c for n, c in rows.items() if n.endswith("_200to128_%dx%d" % (h3, w3))}      # 32 + 168 -> 128: occlusion, flow[, past flow]
+    print("table %s %dx%dx%d %-12s level-3 first decoder layers: %s" % (which, B, H, Wd, setting, first3))
+    assert sum(first3.values()) == (3 if past else 2), first3
+    if tag:
+        assert list(first3) == ["conv%s_200to128_%dx%d" % (tag, h3, w3)], first3
+        inner = [n for n in rows if n.startswith("conv%s_128to96_" % tag)]                    # and every level's third decoder layer
+        assert len(inner) == 5, (inner, sorted(rows))
+    if setting in STRIDE2_TAGS:
+        must, never = STRIDE2_TAGS[setting]
+        for t in must:
+            assert any(n.startswith("conv%s_64to96_" % t) for n in rows), (t, sorted(rows))
+        for t in never:
+            assert not any(n.startswith("conv%s_" % t) for n in rows), (t, sorted(rows))
+    if setting.startswith("corr-"):
+        # The row name does not carry the variant, and launch_warp_costvol runs variant 3 where warp_costvol_unit_supported refuses a
+        # launch: that variants 5 and 7 themselves run here rests on that predicate holding at these sizes (C a multiple of 16 at every
+        # level).  Variants 0, 1 and 3 have no such fallback.
+        assert sum(c for n, c in rows.items() if n.startswith("warp_costvol_")) == 5
+
+
 # ---- (b) every image warp against float64 on the GPU's own flow ----
 
 def _pool64(a):
