@@ -28,6 +28,10 @@ RGB_PLANAR, RGB_PACKED = 0, 1
 # words of a score record (include/b2f.h, B2F_SCORE_*): counted pixels, Q20 error sums and Fl outliers per bucket (0 occluded "bwd",
 # 1 visible, 2 occluded "fwd", 3 unlabelled), the 3 x 3 occlusion matrix (ground-truth class major), NaN errors
 SCORE_PIXELS, SCORE_EPE_Q20, SCORE_OUTLIERS, SCORE_OCC, SCORE_NONFINITE, SCORE_WORDS = 0, 4, 8, 12, 21, 22
+# words of a photometric record (include/b2f.h, B2F_PHOTO_*), each base + direction (0 the past frame, 1 the future one): pixels whose
+# target lies in / leaves the image, Q30 sums of the L1 penalty, of the squared difference, of the occlusion-weighted penalty and of
+# the weights over the inside pixels, pixels with a NaN coordinate, error or weight
+PHOTO_INSIDE, PHOTO_OUTSIDE, PHOTO_CHARB_Q30, PHOTO_SQ_Q30, PHOTO_OCHARB_Q30, PHOTO_WEIGHT_Q30, PHOTO_NONFINITE, PHOTO_WORDS = 0, 2, 4, 6, 8, 10, 12, 14
 
 
 def normalize(imgs):
@@ -433,6 +437,97 @@ def score_summary(scores):
             "pixels": sum(pix), "nonfinite": t[SCORE_NONFINITE]}
 
 
+def _warp_outputs(n, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who):
+    """[warped, photo, flow, fwd, bwd, occ_prob] (None: not asked for) for the warp entries; out = the buffers the call returns, in the
+    order (warped, photo[, flow][, fwd_occ, bwd_occ][, occ_prob]) without what is not asked for, or new arrays."""
+    if not want_warped and not want_photo:
+        raise ValueError("%s: at least one of want_warped and want_photo" % who)
+    spec = [(np.uint8 if as_bytes else np.float32, (n, 2, 3, H0, W0)) if want_warped else None,
+            (np.uint64, (n, PHOTO_WORDS)) if want_photo else None,
+            (np.float32, (n, 2, H0, W0)) if want_flow else None,
+            (np.uint8, (n, 1, H0, W0)) if want_masks else None, (np.uint8, (n, 1, H0, W0)) if want_masks else None,
+            (np.float32, (n, 2, H0, W0)) if want_prob else None]
+    asked = [s for s in spec if s is not None]
+    if out is None:
+        bufs = [np.empty(shape, dt) for dt, shape in asked]
+    else:
+        bufs = [out] if isinstance(out, np.ndarray) else list(out)
+        if len(bufs) != len(asked):
+            raise ValueError("%s: out must hold the %d arrays the call returns" % (who, len(asked)))
+        for i, (a, (dt, shape)) in enumerate(zip(bufs, asked)):
+            if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
+                raise ValueError("%s: out[%d] must be a writeable C-contiguous %s array of shape %s" % (who, i, np.dtype(dt).name, shape))
+    it = iter(bufs)
+    return [next(it) if s is not None else None for s in spec]
+
+
+def _call_warp(fn, h, count, in_kind, ins, H0, W0, flow_scale, outs):
+    warped, photo, flow, fwd, bwd, prob = outs
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+    _lib.check(getattr(_lib.lib(), fn)(h, count, in_kind, *[C.c_void_p(a.ctypes.data) for a in ins], H0, W0, float(flow_scale),
+                                       C.c_void_p(warped.ctypes.data) if warped is not None else None,
+                                       photo.ctypes.data_as(C.POINTER(C.c_ulonglong)) if photo is not None else None,
+                                       _lib.fptr(flow) if flow is not None else None, _lib.fptr(prob) if prob is not None else None,
+                                       u8p(fwd), u8p(bwd)))
+    res = tuple(a for a in outs if a is not None)
+    return res[0] if len(res) == 1 else res
+
+
+def _compute_flow_batch_warp(prefix, h, im1, im2, im3, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob):
+    """computeFlowBatchWarp of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    who = "computeFlowBatchWarp"
+    arrs = [np.asarray(a) for a in (im1, im2, im3)]
+    if any(a.ndim != 4 or a.shape[1] != 3 or a.shape[0] < 1 for a in arrs) or len({a.shape for a in arrs}) > 1:
+        raise ValueError("%s: expected three n x 3 x H x W arrays of one shape" % who)
+    im1, im2, im3, as_bytes = _batch_inputs(*arrs)
+    n, _, H0, W0 = im1.shape
+    outs = _warp_outputs(n, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who)
+    return _call_warp(prefix + "compute_flow_batch_warp", h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0, flow_scale, outs)
+
+
+def _compute_flow_sequence_warp(prefix, h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob):
+    """computeFlowSequenceWarp of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    who = "computeFlowSequenceWarp"
+    v, as_bytes = sequence_frames(frames)
+    T, _, H0, W0 = v.shape
+    outs = _warp_outputs(T - 2, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who)
+    return _call_warp(prefix + "compute_flow_sequence_warp", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0, flow_scale, outs)
+
+
+def photo_summary(photo):
+    """The photometric measures of test.lua:285 from photometric records (n x 14 or 14 uint64 words; ops.flow_warp,
+    computeFlow*Warp), summed over the images given: a dict of
+      pme            criterions/OBCCriterion.lua:updateOutput with the L1 penalty, penalty_out = 1 and sizeAverage, both directions:
+                     sum_d (OCHARB_d / 2^30 + 1.0 * OUTSIDE_d) / (3 * 2 * pixels); pixels = the images' pixels (a pixel that is
+                     non-finite in one direction counts half).  The weights are the occlusion probabilities the records were made with:
+                     est[2] of a Hard model, est[3] of a Soft one (what the f32 entries return as occ_prob); without them pme is 0 + the
+                     outside share
+      bc             sum CHARB / (3 * sum INSIDE): the unmasked L1 error per sample of the pixels that stay in the image
+      psnr_past, psnr_future   10 log10(3 * INSIDE_d * 2^30 / SQ_d) of the warped neighbour against the reference frame (inf: equal)
+      inside_past, inside_future   share of the pixels whose target lies in the image
+      pme_weighted   sum OCHARB / (3 * sum WEIGHT)
+      nonfinite      pixels (per direction) with a NaN coordinate, error or weight; they are counted nowhere else
+    A ratio whose denominator is 0 is nan.  The sums are exact integers; each pixel term carries the records' Q30 rounding (2^-31)."""
+    s = np.asarray(photo)
+    if s.dtype != np.uint64 or s.shape[-1:] != (PHOTO_WORDS,) or s.ndim not in (1, 2):
+        raise ValueError("photo_summary: expected uint64 records of %d words, got %s %r" % (PHOTO_WORDS, s.dtype, s.shape))
+    t = [sum(int(v) for v in col) for col in s.reshape(-1, PHOTO_WORDS).T]   # Python integers: no overflow over many images
+    pair = lambda base: t[base:base + 2]
+    ins, outs, charb, sq, ocharb, wsum, nonf = (pair(b) for b in (PHOTO_INSIDE, PHOTO_OUTSIDE, PHOTO_CHARB_Q30, PHOTO_SQ_Q30, PHOTO_OCHARB_Q30,
+                                                                  PHOTO_WEIGHT_Q30, PHOTO_NONFINITE))
+    one = float(1 << 30)
+    ratio = lambda a, b: a / b if b else float("nan")
+    seen = [ins[d] + outs[d] + nonf[d] for d in range(2)]   # every pixel of every image, per direction
+    pixels = (seen[0] + seen[1] - sum(nonf)) / 2.0
+    psnr = lambda d: float("nan") if not ins[d] else float("inf") if not sq[d] else 10.0 * np.log10(3.0 * ins[d] * one / sq[d])
+    return {"pme": ratio(sum(ocharb) / one + 1.0 * sum(outs), 3.0 * 2.0 * pixels),
+            "bc": ratio(sum(charb) / one, 3.0 * sum(ins)),
+            "psnr_past": float(psnr(0)), "psnr_future": float(psnr(1)),
+            "inside_past": ratio(ins[0], seen[0]), "inside_future": ratio(ins[1], seen[1]),
+            "pme_weighted": ratio(sum(ocharb) / one, 3.0 * (sum(wsum) / one)),
+            "nonfinite": sum(nonf)}
+
+
 class Model(object):
     """Owns a b2f_ctx (the `model` global of back2future.lua:113)."""
 
@@ -641,6 +736,35 @@ class Model(object):
         _lib.check(_lib.lib().b2f_flow_score_device(self._h, p(d_flow), p(d_occ_prob), int(n), int(H), int(W), float(flow_scale), p(d_gt_flow),
                                                      p(d_valid), p(d_gt_occ), p(d_scores), p(stream)))
 
+    def computeFlowBatchWarp(self, im1, im2, im3, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False,
+                             out=None, want_prob=False):
+        """computeFlowBatch with motion compensation on the GPU (b2f_compute_flow_batch_warp; models/pwc.lua:67-73,
+        criterions/OBCCriterion.lua:79-100): returns (warped, photo[, flow][, fwd_occ, bwd_occ][, occ_prob]) without what is not asked
+        for (a single array alone); what is not asked for is not downloaded.  warped: n x 2 x 3 x H x W in the frames' dtype, [:, 0]
+        im1 (the past frame) and [:, 1] im3 (the future frame) sampled where the flow says the reference pixels came from / go to --
+        not normalized, bytes rounded as image.save does; photo: uint64 n x 14 photometric records (photo_summary turns them into pme,
+        PSNR and the inside shares); flow_scale: pixels per unit of raw flow (20 for the shipped models).  The outputs are
+        ops.flow_warp of the float32 flow and occ_prob of computeFlowBatch(dtype=np.float32, occ_prob=True)."""
+        return _compute_flow_batch_warp("b2f_", self._h, im1, im2, im3, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob)
+
+    def computeFlowSequenceWarp(self, frames, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False, out=None,
+                                want_prob=False):
+        """computeFlowSequence with motion compensation (b2f_compute_flow_sequence_warp): output i belongs to centre frame i + 1, whose
+        neighbours are frames i and i + 2; keywords and results as for computeFlowBatchWarp with n = T - 2."""
+        return _compute_flow_sequence_warp("b2f_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob)
+
+    def flowWarpDevice(self, d_flow, n, H, W, d_im1, d_im2, d_im3, d_warped=None, d_photo=None, d_occ_prob=None, flow_scale=20.0, as_bytes=False,
+                       stream=None):
+        """b2f_flow_warp_device on device pointers (ints): the warped neighbours (n x 2 x 3 x H x W in d_warped, bytes with as_bytes,
+        float32 otherwise, like the frames d_im1 / d_im2 / d_im3, n x 3 x H x W each) and / or the photometric records (n x 14 uint64
+        in d_photo) of an n x 2 x H x W float32 flow and, optionally, d_occ_prob.  Asynchronous on `stream`: after computeFlowDevice
+        on the same stream it needs no synchronisation in between."""
+        if n < 1 or H < 1 or W < 1:
+            raise ValueError("flowWarpDevice: bad shape %r" % ((n, H, W),))
+        p = lambda v: C.c_void_p(v) if v else None
+        _lib.check(_lib.lib().b2f_flow_warp_device(self._h, p(d_flow), p(d_occ_prob), int(n), int(H), int(W), float(flow_scale),
+                                                    IN_U8 if as_bytes else IN_UNIT, p(d_im1), p(d_im2), p(d_im3), p(d_warped), p(d_photo), p(stream)))
+
     def output_shapes(self, H, W):
         cap = 32
         ch, oh, ow = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
@@ -737,6 +861,19 @@ class MultiModel(object):
     def computeFlowSequenceScore(self, frames, gt_flow, valid=None, gt_occ=None, flow_scale=20.0, want_flow=False, want_masks=False, out=None):
         """Model.computeFlowSequenceScore over the GPUs, with the same keywords and the same words."""
         return _compute_flow_sequence_score("b2f_multi_", self._h, frames, gt_flow, valid, gt_occ, flow_scale, want_flow, want_masks, out)
+
+
+    def computeFlowBatchWarp(self, im1, im2, im3, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False,
+                             out=None, want_prob=False):
+        """Model.computeFlowBatchWarp over the GPUs, with the same keywords, the same bytes and the same words."""
+        return _compute_flow_batch_warp("b2f_multi_", self._h, im1, im2, im3, flow_scale, want_warped, want_photo, want_flow, want_masks, out,
+                                        want_prob)
+
+    def computeFlowSequenceWarp(self, frames, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False, out=None,
+                                want_prob=False):
+        """Model.computeFlowSequenceWarp over the GPUs, with the same keywords, the same bytes and the same words."""
+        return _compute_flow_sequence_warp("b2f_multi_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out,
+                                           want_prob)
 
 
 def shard_range(n, rank, world):

@@ -154,6 +154,9 @@ struct HostSlot {
     float *d_gt = nullptr, *h_gt = nullptr;
     unsigned char *d_valid = nullptr, *d_gtocc = nullptr, *h_valid = nullptr, *h_gtocc = nullptr;
     unsigned long long *d_score = nullptr, *h_score = nullptr;
+    // warp requests: the warped neighbours of the sub-batch (in the request's element type) and its photometric records
+    void *d_warp = nullptr, *h_warp = nullptr;
+    unsigned long long *d_photo = nullptr, *h_photo = nullptr;
     hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
 };
 
@@ -163,6 +166,8 @@ struct HostSlot {
 // b2f_compute_flow*_rgb (xy2rgb of the f32 flow, launch_flow_rgb) in rgb_layout with max_norm, rgb_max their maxima; the flow itself
 // is then optional.  scores (f32 path only): the records of b2f_compute_flow*_score (launch_flow_score of the f32 flow and occ_prob
 // against gt_flow / valid / gt_occ, which are inputs that travel with the outputs they belong to); the flow is optional there too.
+// warped / photo (f32 path only): the outputs of b2f_compute_flow*_warp (launch_flow_warp of the f32 flow, occ_prob and the request's
+// own frames with flow_scale); at least one is required, everything else is optional.
 struct FlowOutputs {
     double *flow64 = nullptr;
     float *flow32 = nullptr, *occ_prob = nullptr;
@@ -177,6 +182,10 @@ struct FlowOutputs {
     const unsigned char *valid = nullptr, *gt_occ = nullptr;
     double flow_scale = 0.0;
     bool scoring = false;          // a score request: scores and gt_flow are required, flow32 is not
+    void *warped = nullptr;        // n x 2 x 3 x H0 x W0 of warped_kind (B2F_IN_UNIT floats or B2F_IN_U8 bytes)
+    int warped_kind = B2F_IN_UNIT;
+    unsigned long long *photo = nullptr;
+    bool warping = false;          // a warp request: warped or photo is required, flow32 is not
     bool f32() const { return flow64 == nullptr; }
     // the outputs of triplets b, b + 1, ... (planes of hw0 pixels); nullptr stays nullptr
     FlowOutputs from_triplet(size_t b, size_t hw0) const
@@ -184,7 +193,9 @@ struct FlowOutputs {
         auto at = [](auto *p, size_t off) { return p ? p + off : p; };
         return {at(flow64, b * 2 * hw0), at(flow32, b * 2 * hw0), at(occ_prob, b * 2 * hw0), at(fwd_occ, b * hw0), at(bwd_occ, b * hw0),
                 at(rgb, b * 3 * hw0), at(rgb_max, b), max_norm, rgb_layout, pictures,
-                at(scores, b * B2F_SCORE_WORDS), at(gt_flow, b * 2 * hw0), at(valid, b * hw0), at(gt_occ, b * hw0), flow_scale, scoring};
+                at(scores, b * B2F_SCORE_WORDS), at(gt_flow, b * 2 * hw0), at(valid, b * hw0), at(gt_occ, b * hw0), flow_scale, scoring,
+                warped ? (void *)((char *)warped + b * 6 * hw0 * (warped_kind == B2F_IN_U8 ? 1 : 4)) : nullptr, warped_kind,
+                at(photo, b * B2F_PHOTO_WORDS), warping};
     }
 };
 
@@ -201,6 +212,15 @@ inline FlowOutputs score_outputs(double flow_scale, const float *gt_flow, const 
 {
     FlowOutputs o{nullptr, flow, nullptr, fwd_occ, bwd_occ};
     o.scores = scores; o.gt_flow = gt_flow; o.valid = valid; o.gt_occ = gt_occ; o.flow_scale = flow_scale; o.scoring = true;
+    return o;
+}
+
+// the outputs of a b2f_*compute_flow_*_warp entry; in_kind: the element type of the request's frames, and so of warped
+inline FlowOutputs warp_outputs(double flow_scale, int in_kind, void *warped, unsigned long long *photo, float *flow, float *occ_prob,
+                                unsigned char *fwd_occ, unsigned char *bwd_occ)
+{
+    FlowOutputs o{nullptr, flow, occ_prob, fwd_occ, bwd_occ};
+    o.flow_scale = flow_scale; o.warped = warped; o.warped_kind = in_kind; o.photo = photo; o.warping = true;
     return o;
 }
 

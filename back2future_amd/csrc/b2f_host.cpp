@@ -4,6 +4,7 @@
 #include "b2f_host.h"
 #include "b2f_flowcolor.h"
 #include "b2f_flowscore.h"
+#include "b2f_flowwarp.h"
 #include "../../include/b2f.h"
 
 #include <cmath>
@@ -203,6 +204,74 @@ void flow_score_host(const float *flow, const float *occ_prob, int n, int H, int
             if (p0 && label <= 2) rec[B2F_SCORE_OCC + 3 * label + score_occ_class(p0[i], p1[i])] += 1;
         }
     }
+}
+
+}  // namespace b2f
+
+// ---- motion compensation on the CPU -----------------------------------------------------------------------------------------------
+namespace b2f {
+
+namespace {
+
+inline float frame_value(float v) { return v; }
+inline float frame_value(unsigned char k) { return (float)k / 255.0f; }
+inline void put_warped(float *p, float v) { *p = v; }
+inline void put_warped(unsigned char *p, float v) { *p = warp_quantise(v); }
+
+template <typename T>
+void flow_warp_host_t(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const T *im1, const T *im2, const T *im3,
+                      T *warped, unsigned long long *photo)
+{
+    const size_t hw = (size_t)H * W;
+    for (int b = 0; b < n; ++b) {
+        const float *fx = flow + (size_t)b * 2 * hw, *fy = fx + hw;
+        const float *p0 = occ_prob ? occ_prob + (size_t)b * 2 * hw : nullptr, *p1 = p0 ? p0 + hw : nullptr;
+        const T *ref = im2 + (size_t)b * 3 * hw;
+        unsigned long long *rec = photo ? photo + (size_t)b * B2F_PHOTO_WORDS : nullptr;
+        for (int k = 0; rec && k < B2F_PHOTO_WORDS; ++k) rec[k] = 0;
+        for (int d = 0; d < 2; ++d) {
+            const T *frm = (d == 0 ? im1 : im3) + (size_t)b * 3 * hw;
+            const float *pw = d == 0 ? p1 : p0;
+            const float k = d == 0 ? -(float)flow_scale : (float)flow_scale;
+            T *out = warped ? warped + ((size_t)b * 2 + d) * 3 * hw : nullptr;
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) {
+                    const size_t i = (size_t)y * W + x;
+                    const WarpTaps t = warp_taps(fx[i], fy[i], k, x, y, W, H);
+                    float wv[3] = {0.0f, 0.0f, 0.0f}, rv[3];
+                    for (int c = 0; c < 3 && !t.nan; ++c) {
+                        const T *tl = frm + (size_t)c * hw + (size_t)t.yt * W + t.xl;
+                        wv[c] = warp_blend(t, frame_value(tl[0]), t.x1 ? frame_value(tl[1]) : 0.0f, t.y1 ? frame_value(tl[W]) : 0.0f,
+                                           (t.x1 && t.y1) ? frame_value(tl[W + 1]) : 0.0f);
+                    }
+                    for (int c = 0; c < 3; ++c) {
+                        if (out) put_warped(out + (size_t)c * hw + i, wv[c]);
+                        rv[c] = frame_value(ref[(size_t)c * hw + i]);
+                    }
+                    if (!rec) continue;
+                    const PixelPhoto s = photo_pixel(t, wv, rv, pw != nullptr, pw ? pw[i] : 0.0f);
+                    rec[B2F_PHOTO_INSIDE + d] += s.inside;
+                    rec[B2F_PHOTO_OUTSIDE + d] += s.outside;
+                    rec[B2F_PHOTO_CHARB_Q30 + d] += s.charb;
+                    rec[B2F_PHOTO_SQ_Q30 + d] += s.sq;
+                    rec[B2F_PHOTO_OCHARB_Q30 + d] += s.ocharb;
+                    rec[B2F_PHOTO_WEIGHT_Q30 + d] += s.weight;
+                    rec[B2F_PHOTO_NONFINITE + d] += s.nonfinite;
+                }
+        }
+    }
+}
+
+}  // namespace
+
+void flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, bool bytes_in, const void *im1,
+                    const void *im2, const void *im3, void *warped, unsigned long long *photo)
+{
+    if (bytes_in)
+        flow_warp_host_t(flow, occ_prob, n, H, W, flow_scale, (const unsigned char *)im1, (const unsigned char *)im2, (const unsigned char *)im3,
+                         (unsigned char *)warped, photo);
+    else
+        flow_warp_host_t(flow, occ_prob, n, H, W, flow_scale, (const float *)im1, (const float *)im2, (const float *)im3, (float *)warped, photo);
 }
 
 }  // namespace b2f

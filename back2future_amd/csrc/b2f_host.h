@@ -73,6 +73,12 @@ void flow_rgb_host(const float *flow, int n, int H, int W, double max_norm, bool
 void flow_score_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const float *gt_flow,
                      const unsigned char *valid, const unsigned char *gt_occ, unsigned long long *scores);
 
+// Motion compensation on the CPU (b2f_flowwarp.h per pixel; b2f_flow_warp_host): the two warped neighbours (n x 2 x 3 x H x W in the
+// frames' element type, or nullptr) and the photometric records (n x B2F_PHOTO_WORDS words, or nullptr) of a planar n x 2 x H x W
+// fp32 flow; im1 / im2 / im3: n x 3 x H x W each, bytes with bytes_in, floats otherwise; occ_prob may be nullptr
+void flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, bool bytes_in, const void *im1,
+                    const void *im2, const void *im3, void *warped, unsigned long long *photo);
+
 // .t7 reader (b2f_t7.cpp): returns false and fills err on failure.
 bool load_t7(const std::string &path, std::vector<float> &flat, bool &past_flow, std::string &err);
 // any graph shape: infer = true takes win / levels / skip from the file, false checks the file against g (see b2f_t7.cpp)

@@ -336,4 +336,14 @@ hipError_t launch_flow_rgb(const float *flow, int n, int H, int W, double max_no
 hipError_t launch_flow_score(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const float *gt_flow,
                              const unsigned char *valid, const unsigned char *gt_occ, unsigned long long *scores, hipStream_t s);
 
+// ---- motion compensation (b2f_warp.hip; the per-pixel functions: b2f_flowwarp.h) --------------
+// The two warped neighbours (warped: n x 2 x 3 x H x W of warped_kind, B2F_IN_UNIT floats or B2F_IN_U8 bytes, or nullptr) and the
+// photometric records (photo: n x B2F_PHOTO_WORDS words, zeroed on s first, or nullptr) of a planar n x 2 x H x W fp32 flow and
+// occ_prob (or nullptr).  im1 / im2 / im3: the past, reference and future frame of image 0 (3 planes of in_kind each); image b lies
+// image_stride samples further: 3 H W for separate arrays and for a sequence (im2 = frames + 3 H W, im3 = frames + 6 H W), 9 H W for
+// the [triplet][frame][3][H W] layout.  One launch, H * W < 2^28
+hipError_t launch_flow_warp(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const void *im1, const void *im2,
+                            const void *im3, size_t image_stride, int in_kind, void *warped, int warped_kind, unsigned long long *photo,
+                            hipStream_t s);
+
 }  // namespace b2f

@@ -353,4 +353,22 @@ int b2f_multi_compute_flow_sequence_score(b2f_multi *m, int T, int in_kind, cons
 }
 B2F_CATCH("b2f_multi_compute_flow_sequence_score")
 
+int b2f_multi_compute_flow_batch_warp(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0,
+                                      double flow_scale, void *warped, unsigned long long *photo, float *flow, float *occ_prob,
+                                      unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_multi(m, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0,
+                                               warp_outputs(flow_scale, in_kind, warped, photo, flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_multi_compute_flow_batch_warp")
+
+int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0, double flow_scale, void *warped,
+                                         unsigned long long *photo, float *flow, float *occ_prob, unsigned char *fwd_occ,
+                                         unsigned char *bwd_occ) try
+{
+    return compute_flow_multi(m, sequence_request(__func__, T, in_kind, frames, H0, W0,
+                                                  warp_outputs(flow_scale, in_kind, warped, photo, flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_multi_compute_flow_sequence_warp")
+
 }  // extern "C"

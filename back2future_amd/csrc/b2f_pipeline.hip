@@ -47,6 +47,9 @@ struct SlotNeeds {
     bool score;        // d_gt, d_score: a score request
     bool valid, gtocc; // d_valid, d_gtocc: the optional byte planes of the ground truth
     bool stage_gt, stage_valid, stage_gtocc, stage_score;   // h_gt, h_valid, h_gtocc, h_score: pageable buffers
+    size_t warp_esz;   // d_warp: the warped neighbours of a warp request, bytes per sample (0: not asked for)
+    bool photo;        // d_photo: its photometric records
+    bool stage_warp, stage_photo;   // h_warp, h_photo: pageable buffers
 };
 
 // carve the slot's device and pinned blobs for sub-batches of up to SB triplets; grows (never shrinks) the blobs
@@ -61,8 +64,10 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     const size_t n_rgb = q.rgb ? align256((size_t)SB * 3 * hw0) : 0, n_max = q.rgb ? align256((size_t)SB * sizeof(double)) : 0;
     const size_t n_gt = q.score ? n_f32 : 0, n_va = q.valid ? n_occ : 0, n_lb = q.gtocc ? n_occ : 0,
                  n_sc = q.score ? align256((size_t)SB * B2F_SCORE_WORDS * sizeof(unsigned long long)) : 0;
+    const size_t n_wp = align256((size_t)SB * 6 * hw0 * q.warp_esz),
+                 n_ph = q.photo ? align256((size_t)SB * B2F_PHOTO_WORDS * sizeof(unsigned long long)) : 0;
     const size_t need_dev = n_up + n_u8 + n_in + n_tmp + n_flow + n_est3 + (same ? 0 : n_f32) + n_onet + n_prob + 2 * n_occ + n_rgb + n_max +
-                            n_gt + n_va + n_lb + n_sc;
+                            n_gt + n_va + n_lb + n_sc + n_wp + n_ph;
     if (need_dev > hs.dev_bytes) {
         if (hs.dev) {
             HIPCHK(hipDeviceSynchronize());
@@ -90,11 +95,15 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.d_gt = q.score ? (float *)d : nullptr; d += n_gt;
     hs.d_valid = q.valid ? (unsigned char *)d : nullptr; d += n_va;
     hs.d_gtocc = q.gtocc ? (unsigned char *)d : nullptr; d += n_lb;
-    hs.d_score = q.score ? (unsigned long long *)d : nullptr;
+    hs.d_score = q.score ? (unsigned long long *)d : nullptr; d += n_sc;
+    hs.d_warp = q.warp_esz ? (void *)d : nullptr; d += n_wp;
+    hs.d_photo = q.photo ? (unsigned long long *)d : nullptr;
     const size_t n_hf = q.stage_flow ? n_f32 : 0, n_hp = q.stage_prob ? n_f32 : 0;
     const size_t n_hr = q.stage_rgb ? n_rgb : 0, n_hm = q.stage_max ? n_max : 0;
     const size_t n_hg = q.stage_gt ? n_gt : 0, n_hv = q.stage_valid ? n_va : 0, n_hl = q.stage_gtocc ? n_lb : 0, n_hs = q.stage_score ? n_sc : 0;
-    const size_t need_pin = (q.stage_in ? n_up : 0) + n_u8 + n_hf + n_hp + (q.stage_masks ? 2 * n_occ : 0) + n_hr + n_hm + n_hg + n_hv + n_hl + n_hs;
+    const size_t n_hw = q.stage_warp ? n_wp : 0, n_hph = q.stage_photo ? n_ph : 0;
+    const size_t need_pin = (q.stage_in ? n_up : 0) + n_u8 + n_hf + n_hp + (q.stage_masks ? 2 * n_occ : 0) + n_hr + n_hm + n_hg + n_hv + n_hl + n_hs +
+                            n_hw + n_hph;
     if (need_pin > hs.pin_bytes) {
         if (hs.pin) {
             HIPCHK(hipDeviceSynchronize());
@@ -116,7 +125,9 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.h_gt = (float *)h; h += n_hg;
     hs.h_valid = (unsigned char *)h; h += n_hv;
     hs.h_gtocc = (unsigned char *)h; h += n_hl;
-    hs.h_score = (unsigned long long *)h;
+    hs.h_score = (unsigned long long *)h; h += n_hs;
+    hs.h_warp = (void *)h; h += n_hw;
+    hs.h_photo = (unsigned long long *)h;
     for (hipEvent_t *e : {&hs.ev_in, &hs.ev_comp, &hs.ev_out})
         if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return 0;
@@ -178,11 +189,16 @@ struct NetBuffers {
 // out.rgb: the pictures of that f32 flow (xy2rgb, b2f_vis.hip), read from out.flow32 or, at the network size, from net.flow itself.
 // out.scores: the records of that f32 flow and occ_prob against out.gt_flow / valid / gt_occ (device copies; b2f_score.hip), read like the
 // pictures' flow: from out.flow32 / out.occ_prob or, at the network size, from the network's own planes.
+// out.warped / out.photo: the motion-compensated neighbours and their photometric records (b2f_warp.hip) of that f32 flow and occ_prob,
+// chosen like the scores' inputs, and of the sub-batch's own frames: x as it came in, before image.scale replaces it, triplet b's
+// three frames 9 planes apart, or the frames of a sequence 3 planes apart.
 // sp: a push of a stream -- the nb = cams frames go through the pyramid into the ring (net.scaled, where image.scale writes, is their
 // frame slot); the rest runs, and the outputs are written, only from the third push on.
 int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void *x, int kind, long planes, int nb, const NetBuffers &net,
                 const FlowOutputs &out, bool graph, hipStream_t s, const StreamPass *sp = nullptr)
 {
+    const void *frames = x;   // the caller's frames at H0 x W0 and their kind: what a warp request samples
+    const int frames_kind = kind;
     if (!g.same) {
         HIPCHK(launch_image_scale((const float *)x, 1, planes, g.H0, g.W0, net.tmp, net.scaled, g.fh, g.fw, s));
         x = net.scaled;
@@ -207,6 +223,20 @@ int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void 
         const bool timed = prof_open(c, s, "flow_score", &pe);
         const hipError_t e = launch_flow_score(out.flow32 ? out.flow32 : net.flow, prob, nb, g.H0, g.W0, out.flow_scale, out.gt_flow, out.valid,
                                                out.gt_occ, out.scores, s);
+        if (timed) prof_close(c, s, pe);
+        HIPCHK(e);
+    }
+    if (out.warped || out.photo) {
+        if (!g.same && (!out.flow32 || (out.photo && !out.occ_prob)))
+            return fail(std::string(r.who) + ": the warp of a rescaled flow needs the flow and occ_prob buffers");
+        const float *prob = !out.photo ? nullptr : g.same ? (g.C3 == 3 ? net.occ : net.est3) : out.occ_prob;
+        if (out.photo && !prob) return fail(std::string(r.who) + ": the photometric record needs skip_occs[3]");
+        const size_t esz = frames_kind == B2F_IN_U8 ? 1 : 4, stride = (r.seq ? 3 : 9) * g.hw0;
+        const char *f0 = (const char *)frames;
+        ProfEvent pe;
+        const bool timed = prof_open(c, s, "flow_warp", &pe);
+        const hipError_t e = launch_flow_warp(out.flow32 ? out.flow32 : net.flow, prob, nb, g.H0, g.W0, out.flow_scale, f0, f0 + 3 * g.hw0 * esz,
+                                              f0 + 6 * g.hw0 * esz, stride, frames_kind, out.warped, out.warped_kind, out.photo, s);
         if (timed) prof_close(c, s, pe);
         HIPCHK(e);
     }
@@ -379,8 +409,15 @@ int b2f::check_request(const FlowRequest &r)
     // an rgb request (f32 path) needs its pictures and may leave the flow out
     // a score request (f32 path too) needs its records and the ground-truth flow
     if (!r.im1 || (!r.seq && !r.stream && (!r.im2 || !r.im3)) ||
-        (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : o.scoring ? !o.scores || !o.gt_flow : !o.flow32))
+        (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : o.scoring ? !o.scores || !o.gt_flow : o.warping ? false : !o.flow32))
         return fail(w + ": null argument");
+    // a warp request (f32 path as well) needs the warped frames or the photometric records
+    if (o.warping) {
+        if (!o.f32() || r.stream) return fail(w + ": warped frames are an output of the float32 batch and sequence entries");
+        if (!(o.flow_scale > 0.0) || !std::isfinite(o.flow_scale)) return fail(w + ": flow_scale must be finite and > 0");
+        if ((long long)r.H0 * r.W0 >= (1ll << 28)) return fail(w + ": images of 2^28 pixels or more are refused (the Q30 sums could overflow)");
+        if (!o.warped && !o.photo) return fail(w + ": at least one of warped and photo is required");
+    }
     if (o.scoring) {
         if (!o.f32() || r.stream) return fail(w + ": scores are an output of the float32 batch and sequence entries");
         if (!(o.flow_scale > 0.0) || !std::isfinite(o.flow_scale)) return fail(w + ": flow_scale must be finite and > 0");
@@ -412,7 +449,9 @@ int b2f::check_request(const FlowRequest &r)
 // flow / occ_prob / mask buffers are DMA'd in place -- and a NULL occ_prob or mask is neither written nor downloaded.  The pictures
 // and maxima of an rgb request (b2f_*_rgb) travel like occ_prob: slot buffers, DMA in place or staging + drain copy; its flow stays
 // on the device unless asked for.  A score request (b2f_*_score) uploads the ground truth of every sub-batch's outputs with its frames
-// (page-locked buffers in place, pageable ones through the slot's staging block) and downloads the 176-byte records.
+// (page-locked buffers in place, pageable ones through the slot's staging block) and downloads the 176-byte records.  A warp
+// request (b2f_*_warp) downloads the warped neighbours and the 112-byte photometric records like the pictures; whatever else it
+// leaves out stays on the device.
 int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
 {
     CHK(check_context(c, r));
@@ -438,8 +477,11 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
     // a score request: the ground truth (inputs; absent planes count as page-locked) and the records
     const int k_gt[4] = {out_kind(o.gt_flow, (size_t)n * 2 * hw0 * 4), out_kind(o.valid, (size_t)n * hw0), out_kind(o.gt_occ, (size_t)n * hw0),
                          out_kind(o.scores, (size_t)n * B2F_SCORE_WORDS * sizeof(unsigned long long))};
+    // a warp request: the warped neighbours in the frames' element type and the records
+    const size_t warp_esz = o.warped ? (o.warped_kind == B2F_IN_U8 ? 1 : 4) : 0;
+    const int k_wp[2] = {out_kind(o.warped, (size_t)n * 6 * hw0 * warp_esz), out_kind(o.photo, (size_t)n * B2F_PHOTO_WORDS * sizeof(unsigned long long))};
     for (int i = 0; i < 6; ++i)
-        if ((i < 3 && k_in[i] < 0) || k_out[i] < 0 || (i < 4 && k_gt[i] < 0))
+        if ((i < 3 && k_in[i] < 0) || k_out[i] < 0 || (i < 4 && k_gt[i] < 0) || (i < 2 && k_wp[i] < 0))
             return fail(w + ": device memory passed to a host-buffer entry point (use b2f_compute_flow_device / "
                             "b2f_compute_flow_sequence_device)");
     if (c->debug_fail_next) {   // tests (option debug_fail_next): one forced failure, e.g. on one replica of a b2f_multi
@@ -460,13 +502,16 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
     const bool want_prob = f32 && o.occ_prob;
     const bool want_score = o.scores != nullptr;
     // the occlusion scores read occ_prob on the device whether or not the caller downloads it
-    const bool need_prob = want_prob || (want_score && o.gt_occ);
+    // ... and so do the photometric records, for their weights
+    const bool want_photo = o.photo != nullptr;
+    const bool need_prob = want_prob || (want_score && o.gt_occ) || want_photo;
     // f32 path: occ_prob is skip_occs[3] -- est[3] of a Soft model (d_est3), an extra forward output of a Hard one (d_occ)
     const bool want_rgb = o.rgb != nullptr;
     SlotNeeds q{same, stage_in, stage_masks, use_u8, need_prob && g.C3 == 3, need_prob && !same, !f32 || k_out[0] != 1, want_prob && k_out[3] != 1,
                 want_rgb, want_rgb && k_out[4] != 1, want_rgb && k_out[5] != 1,
                 want_score, want_score && o.valid, want_score && o.gt_occ, want_score && k_gt[0] != 1, want_score && o.valid && k_gt[1] != 1,
-                want_score && o.gt_occ && k_gt[2] != 1, want_score && k_gt[3] != 1};
+                want_score && o.gt_occ && k_gt[2] != 1, want_score && k_gt[3] != 1,
+                warp_esz, want_photo, o.warped && k_wp[0] != 1, want_photo && k_wp[1] != 1};
     // (a sequence sub-batch's nb + 2 frames are 3 nb + 6 <= 9 nb planes: the triplet layout of the slot holds them)
     for (int k = 0; k < std::min(nsub, 2); ++k)
         CHK(ensure_slot(c, c->slot[k], SB, hw0, g.hw, g.H0, g.fw, g.C3, q));
@@ -508,6 +553,8 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
                     if (q.stage_rgb) jobs.push_back({o.rgb + b0 * 3 * hw0, hs.h_rgb, nb * 3 * hw0});
                     if (q.stage_max) jobs.push_back({o.rgb_max + b0, hs.h_max, nb * sizeof(double)});
                     if (q.stage_score) jobs.push_back({o.scores + b0 * B2F_SCORE_WORDS, hs.h_score, nb * B2F_SCORE_WORDS * sizeof(unsigned long long)});
+                    if (q.stage_warp) jobs.push_back({(char *)o.warped + b0 * 6 * hw0 * warp_esz, hs.h_warp, nb * 6 * hw0 * warp_esz});
+                    if (q.stage_photo) jobs.push_back({o.photo + b0 * B2F_PHOTO_WORDS, hs.h_photo, nb * B2F_PHOTO_WORDS * sizeof(unsigned long long)});
                 }
                 if (stage_masks) {
                     if (fwd_occ) jobs.push_back({fwd_occ + b0 * hw0, hs.h_fo, nb * hw0});
@@ -621,7 +668,8 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
                         {hs.d_tmp, hs.d_in, hs.d_flow, hs.d_occ, hs.d_est3},
                         {nullptr, same ? nullptr : hs.d_flow32, q.prob ? hs.d_prob : nullptr, fwd_occ ? hs.d_fo : nullptr, bwd_occ ? hs.d_bo : nullptr,
                          hs.d_rgb, hs.d_max, o.max_norm, o.rgb_layout, o.pictures,
-                         hs.d_score, hs.d_gt, hs.d_valid, hs.d_gtocc, o.flow_scale, o.scoring},
+                         hs.d_score, hs.d_gt, hs.d_valid, hs.d_gtocc, o.flow_scale, o.scoring,
+                         hs.d_warp, o.warped_kind, hs.d_photo, o.warping},
                         c->host_graph != 0, c->stream));
         HIPCHK(hipEventRecord(hs.ev_comp, c->stream));
         // ---- download: the set's pinned output buffers must have been handed over (k - 2 drained)
@@ -641,6 +689,12 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
         if (want_score)
             HIPCHK(hipMemcpyAsync(q.stage_score ? hs.h_score : o.scores + b0 * B2F_SCORE_WORDS, hs.d_score,
                                   (size_t)nb * B2F_SCORE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_out));
+        if (o.warped)
+            HIPCHK(hipMemcpyAsync(q.stage_warp ? hs.h_warp : (void *)((char *)o.warped + b0 * 6 * hw0 * warp_esz), hs.d_warp,
+                                  (size_t)nb * 6 * hw0 * warp_esz, hipMemcpyDeviceToHost, c->s_out));
+        if (want_photo)
+            HIPCHK(hipMemcpyAsync(q.stage_photo ? hs.h_photo : o.photo + b0 * B2F_PHOTO_WORDS, hs.d_photo,
+                                  (size_t)nb * B2F_PHOTO_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_out));
         if (want_prob)
             HIPCHK(hipMemcpyAsync(q.stage_prob ? hs.h_prob : o.occ_prob + b0 * 2 * hw0, same ? occ_net : hs.d_prob, (size_t)nb * 2 * hw0 * 4,
                                   hipMemcpyDeviceToHost, c->s_out));
@@ -1022,6 +1076,23 @@ int b2f_compute_flow_sequence_score(b2f_ctx *c, int T, int in_kind, const void *
                                                  score_outputs(flow_scale, gt_flow, valid, gt_occ, scores, flow, fwd_occ, bwd_occ)));
 }
 B2F_CATCH("b2f_compute_flow_sequence_score")
+
+int b2f_compute_flow_batch_warp(b2f_ctx *c, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0, double flow_scale,
+                                void *warped, unsigned long long *photo, float *flow, float *occ_prob, unsigned char *fwd_occ,
+                                unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0,
+                                              warp_outputs(flow_scale, in_kind, warped, photo, flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_batch_warp")
+
+int b2f_compute_flow_sequence_warp(b2f_ctx *c, int T, int in_kind, const void *frames, int H0, int W0, double flow_scale, void *warped,
+                                   unsigned long long *photo, float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, sequence_request(__func__, T, in_kind, frames, H0, W0,
+                                                 warp_outputs(flow_scale, in_kind, warped, photo, flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_sequence_warp")
 
 int b2f_compute_flow_device(b2f_ctx *c, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, int H0, int W0,
                             float *dev_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream) try

@@ -188,3 +188,43 @@ def flow_score(flow, gt_flow, occ_prob=None, valid=None, gt_occ=None, flow_scale
     else:
         _lib.check(_lib.lib().b2f_op_flow_score(_h(model), *args))
     return scores
+
+
+def flow_warp(flow, im1, im2, im3, occ_prob=None, flow_scale=20.0, want_warped=True, want_photo=True, model=None):
+    """Motion compensation (the warpingUnit of models/pwc.lua:67-73, nn.BilinearSamplerBHWD with CUDA semantics) and its photometric
+    error (criterions/OBCCriterion.lua:79-100 with the L1 penalty): flow n x 2 x H x W float32 raw network flow; im1 / im2 / im3 the
+    past, reference and future frames, n x 3 x H x W each, all uint8 (value byte / 255) or all float, not normalized; occ_prob
+    n x 2 x H x W float32 or None -> (warped, photo): warped n x 2 x 3 x H x W in the frames' dtype ([:, 0] im1 warped with
+    -flow_scale, [:, 1] im3 with +flow_scale), photo uint64 (n, 14) (back2future.photo_summary reads it); None for what is not
+    wanted.  model=None computes on the CPU (b2f_flow_warp_host, no GPU), a Model on its GPU (b2f_op_flow_warp): the bytes and the
+    words are the same."""
+    from .back2future import IN_U8, IN_UNIT, PHOTO_WORDS
+    f = np.asarray(flow)
+    if f.ndim != 4 or f.shape[1] != 2 or min(f.shape) < 1:
+        raise ValueError("flow_warp: expected an n x 2 x H x W flow, got shape %r" % (np.shape(flow),))
+    f = _lib.f32(f)
+    n, _, H, W = f.shape
+    ims = [np.asarray(a) for a in (im1, im2, im3)]
+    if any(a.shape != (n, 3, H, W) for a in ims):
+        raise ValueError("flow_warp: im1, im2 and im3 must have shape %r, got %r" % ((n, 3, H, W), [a.shape for a in ims]))
+    kinds = {a.dtype == np.uint8 for a in ims}
+    if len(kinds) > 1:
+        raise ValueError("flow_warp: mixed dtypes (all frames uint8, or all float)")
+    as_bytes = kinds == {True}
+    ims = [np.ascontiguousarray(a) if as_bytes else _lib.f32(a) for a in ims]
+    prob = None
+    if occ_prob is not None:
+        prob = np.asarray(occ_prob)
+        if prob.shape != f.shape:
+            raise ValueError("flow_warp: occ_prob must have the flow's shape %r, got %r" % (f.shape, prob.shape))
+        prob = _lib.f32(prob)
+    warped = np.empty((n, 2, 3, H, W), np.uint8 if as_bytes else np.float32) if want_warped else None
+    photo = np.empty((n, PHOTO_WORDS), np.uint64) if want_photo else None
+    args = (_lib.fptr(f), _lib.fptr(prob) if prob is not None else None, n, H, W, float(flow_scale), IN_U8 if as_bytes else IN_UNIT,
+            *[C.c_void_p(a.ctypes.data) for a in ims], C.c_void_p(warped.ctypes.data) if warped is not None else None,
+            photo.ctypes.data_as(C.POINTER(C.c_ulonglong)) if photo is not None else None)
+    if model is None:
+        _lib.check(_lib.lib().b2f_flow_warp_host(*args))
+    else:
+        _lib.check(_lib.lib().b2f_op_flow_warp(_h(model), *args))
+    return warped, photo

@@ -357,6 +357,76 @@ B2F_API int b2f_multi_compute_flow_sequence_score(b2f_multi *m, int T, int in_ki
                                           double flow_scale, const float *gt_flow, const unsigned char *valid,
                                           const unsigned char *gt_occ, unsigned long long *scores, float *flow,
                                           unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* ---- motion compensation: the warped neighbours and their photometric error as an output stage ----
+ * What the reference returns as warped_img_1 .. warped_img_N (back2future.lua:7-10, models/pwc.lua:67-73) and what test.lua:285
+ * reports beside the EPE through criterions/OBCCriterion.lua with the L1 penalty (opts.lua:56-63: -optimize pme, OBCC, L1), at the
+ * size of the caller's frames.  Inputs per image, H x W:
+ *   flow        n x 2 x H x W floats: raw network flow (what the f32 entries return)
+ *   occ_prob    n x 2 x H x W floats or NULL: what the f32 entries return (est[2] of a Hard model, est[3] of a Soft one)
+ *   flow_scale  finite, > 0: pixels per unit of raw flow; 20 for the shipped models
+ *   im1 im2 im3 past, reference and future frame, n x 3 x H x W each: B2F_IN_UNIT floats or B2F_IN_U8 bytes (value (float)k / 255.0f);
+ *               they are NOT normalized
+ * Direction d = 0 warps im1 with k = -(float)flow_scale, d = 1 warps im3 with k = +(float)flow_scale: the constant-velocity branch
+ * of OBCCriterion.lua:79-89 for both model kinds.  The warp is nn.BilinearSamplerBHWD with CUDA semantics
+ * (extras/stnbhwd/BilinearSamplerBHWD.cu:6-20,88-104) in fp32 without fused multiply-adds: xc = fx * k + (float)x, clamped to
+ * [0, W - 1]; xl = floorf(xc), xw = 1 - (xc - xl); the same for y; a tap outside the image contributes 0;
+ * out = (xw*yw)*tl + ((1-xw)*yw)*tr + (xw*(1-yw))*bl + ((1-xw)*(1-yw))*br, added left to right.  A pixel is inside iff
+ * 0 <= xc <= W - 1 and 0 <= yc <= H - 1 before the clamp (OBCCriterion.lua:97-100, 0-based).  A NaN coordinate makes the pixel
+ * non-finite for that direction: its warped value is 0 and nothing is loaded for it; +-Inf is clamped.
+ * warped: n x 2 x 3 x H x W, direction major, in the frames' element type: the float value, or for bytes what image.save writes,
+ * v > 0 ? (v < 1 ? (unsigned char)floorf(v * 255.0f + 0.5f) : 255) : 0.  Pixels that leave the image carry the clamped sample.
+ * photo: n records of B2F_PHOTO_WORDS unsigned 64-bit words (112 bytes), word = base + d.  A finite inside pixel adds 1 to INSIDE,
+ * q(e) to CHARB_Q30 with e = sum_c sqrt(dc * dc + 1e-6), dc = (double)warped_c - (double)ref_c in fp64 (L1_function.lua:20; the
+ * float warp value), q(sum_c dc * dc) to SQ_Q30 and, with occ_prob, q(w * e) to OCHARB_Q30 and q(w) to WEIGHT_Q30, w = p1 for
+ * d = 0 and p0 for d = 1 (OBCCriterion.lua:86,91).  A pixel with a finite coordinate that is not inside adds 1 to OUTSIDE and
+ * nothing else (its error and weight are not looked at).  A NaN coordinate, or an inside pixel whose e, w * e or w is NaN, adds 1 to
+ * NONFINITE and nothing else.  q(t) = (unsigned long long)(min(max(t, 0), 16) * 2^30 + 0.5).
+ * The sums are integers, so a record is the same words on the host and on the device, wherever a request is cut.  Images of 2^28
+ * pixels or more are refused (the Q30 sums could overflow).                                                                   */
+enum {
+    B2F_PHOTO_INSIDE = 0,       /* [2] finite pixels whose target lies in the image */
+    B2F_PHOTO_OUTSIDE = 2,      /* [2] finite pixels whose target leaves it */
+    B2F_PHOTO_CHARB_Q30 = 4,    /* [2] sum of the L1 (Charbonnier) penalties, 2^-30 */
+    B2F_PHOTO_SQ_Q30 = 6,       /* [2] sum of the squared differences, 2^-30 */
+    B2F_PHOTO_OCHARB_Q30 = 8,   /* [2] sum of the occlusion-weighted penalties, 2^-30 */
+    B2F_PHOTO_WEIGHT_Q30 = 10,  /* [2] sum of the occlusion weights, 2^-30 */
+    B2F_PHOTO_NONFINITE = 12,   /* [2] pixels with a NaN coordinate, error or weight */
+    B2F_PHOTO_WORDS = 14
+};
+/* host only, no GPU: BilinearSamplerBHWD.cu:88-104 and OBCCriterion.lua:79-100 per pixel on the CPU.  in_kind: B2F_IN_UNIT or
+ * B2F_IN_U8, the element type of im1..im3 and of warped.  warped or photo may be NULL, not both.                              */
+B2F_API int b2f_flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, int in_kind,
+                       const void *im1, const void *im2, const void *im3, void *warped, unsigned long long *photo);
+/* BilinearSamplerBHWD.cu:88-104 / OBCCriterion.lua:79-100 on device pointers (16-byte aligned), asynchronous on `stream` like
+ * b2f_flow_score_device: right behind b2f_compute_flow_device on the same stream it needs no synchronisation in between.
+ * dev_photo (n x 14 words) is zeroed on the stream first.                                                                     */
+B2F_API int b2f_flow_warp_device(b2f_ctx *ctx, const float *dev_flow, const float *dev_occ_prob, int n, int H, int W,
+                         double flow_scale, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3,
+                         void *dev_warped, unsigned long long *dev_photo, void *stream);
+/* BilinearSamplerBHWD.cu:88-104 / OBCCriterion.lua:79-100 on host pointers through the GPU, like b2f_op_flow_score */
+B2F_API int b2f_op_flow_warp(b2f_ctx *ctx, const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+                     int in_kind, const void *im1, const void *im2, const void *im3, void *warped,
+                     unsigned long long *photo);
+/* computeFlow with motion compensation (models/pwc.lua:67-73 / OBCCriterion.lua:79-100 behind back2future.lua:47-95): the f32
+ * entries' inputs plus flow_scale.  warped (n x 2 x 3 x H0 x W0 in the frames' element type) and photo (n x 14 words): at least
+ * one is required; flow, occ_prob, fwd_occ and bwd_occ are optional (NULL: neither written nor downloaded), so a clip's
+ * photometric error costs 112 bytes of download per triplet.  Output i belongs to triplet i, i.e. to centre frame i + 1 of a
+ * sequence.  The outputs are b2f_op_flow_warp of the float32 flow and occ_prob the f32 entries return and of the caller's own
+ * frames, bit for bit, and the other outputs are the f32 entries'.  A context made with b2f_init_ex options runs the batch
+ * entries; the sequence entries are refused there.  Streams have no such entry (their frame slots hold rescaled frames).     */
+B2F_API int b2f_compute_flow_batch_warp(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                int H0, int W0, double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_compute_flow_sequence_warp(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                   double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                   float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* models/pwc.lua:67-73 / OBCCriterion.lua:79-100 over several GPUs: sharded like the f32 entries, one context's bytes and words */
+B2F_API int b2f_multi_compute_flow_batch_warp(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                      int H0, int W0, double flow_scale, void *warped, unsigned long long *photo,
+                                      float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                         double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                         float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature

@@ -94,6 +94,20 @@ int b2f_compute_flow_sequence_score(b2f_ctx *ctx, int T, int in_kind, const void
                                     double flow_scale, const float *gt_flow, const unsigned char *valid,
                                     const unsigned char *gt_occ, unsigned long long *scores, float *flow,
                                     unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, int in_kind,
+                       const void *im1, const void *im2, const void *im3, void *warped, unsigned long long *photo);
+int b2f_flow_warp_device(b2f_ctx *ctx, const float *dev_flow, const float *dev_occ_prob, int n, int H, int W,
+                         double flow_scale, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3,
+                         void *dev_warped, unsigned long long *dev_photo, void *stream);
+int b2f_op_flow_warp(b2f_ctx *ctx, const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+                     int in_kind, const void *im1, const void *im2, const void *im3, void *warped,
+                     unsigned long long *photo);
+int b2f_compute_flow_batch_warp(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                int H0, int W0, double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_compute_flow_sequence_warp(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                   double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                   float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -117,6 +131,12 @@ int b2f_multi_compute_flow_sequence_score(b2f_multi *m, int T, int in_kind, cons
                                           double flow_scale, const float *gt_flow, const unsigned char *valid,
                                           const unsigned char *gt_occ, unsigned long long *scores, float *flow,
                                           unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_compute_flow_batch_warp(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                      int H0, int W0, double flow_scale, void *warped, unsigned long long *photo,
+                                      float *flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                         double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                         float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
 ]]
 
 local lib = ffi.load(os.getenv('B2F_LIB') or 'libb2f.so')
