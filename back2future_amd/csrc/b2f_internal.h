@@ -75,6 +75,8 @@ struct ConvLaunch {
     int w1b_nblk = 0;                  // ... n-blocks of 64 outputs it computes (the first ones; 0 = all)
     const void *wpk_w6 = nullptr;      // Winograd F(6x6) kernel (b2f_wino6.hip): its weights, or null
     const float *bias_w6 = nullptr;    // ... and its bias, padded to blocks of 64 outputs
+    unsigned w6_mul[3] = {0, 0, 0};    // ... its item decode without divisions: n / d = (n * mul) >> sh for 0 <= n < 2^31 and d = n-blocks of the launch,
+    int w6_sh[3] = {0, 0, 0};          //     items per row of a map, item rows per map (w6_div_magic; set by its launcher)
 };
 hipError_t launch_conv3x3(const ConvLaunch &p, hipStream_t s);
 // floats needed for the packed weights of a conv with `cin_chunks` K-chunks
@@ -226,6 +228,15 @@ inline int device_cu_count()
         n = v < 8 ? 8 : v;
     }
     return n;
+}
+// n / d without a division: mul = floor(2^sh / d) + 1 with sh = 31 + ceil(log2 d) fits 32 bits, and (n * mul) >> sh == n / d for every
+// 0 <= n < 2^31 (the error of mul, e = mul * d - 2^sh, lies in (0, d], and n * e < 2^31 * 2^ceil(log2 d) = 2^sh)
+inline void w6_div_magic(int d, unsigned *mul, int *sh)
+{
+    int l = 0;
+    while ((1ll << l) < (long long)d) ++l;
+    *sh = 31 + l;
+    *mul = (unsigned)((1ull << *sh) / (unsigned long long)d + 1ull);
 }
 #ifdef __HIPCC__
 // MI355X dispatches consecutive workgroup ids round-robin over its 8 XCDs (8 private L2s).  Give every XCD one

@@ -91,7 +91,7 @@ __device__ __host__ constexpr int cj(int j) { return j < 6 ? 9 * j : 9 * (j - 6)
 #define W6_NB_XCD 0
 #endif
 // Profiling only: -DW6_TRACE=1 + B2F_WINO_TRACE=<chunks of the layer> in the environment: s_memtime stamps of block 40 (waves 0 and 4) around the
-// K loop and inside the output stage of its first items, printed by the launcher
+// K loop and inside the output stage of its first items, printed by the launcher (B2F_WINO_TRACE_NT=2: of a 32-output launch instead of a 64-output one)
 #ifndef W6_TRACE
 #define W6_TRACE 0
 #endif
@@ -125,19 +125,24 @@ __device__ __host__ constexpr int cj(int j) { return j < 6 ? 9 * j : 9 * (j - 6)
 // ---- output stage of one item: A^T M A, LeakyReLU, stores (the bias is already in M).  acc[b][mt] = M[8 wave + b][co = 16 mt + 4 (lane >> 4) + r][tile = lane & 15] ----
 // The b direction (8 -> 6) happens in registers -- T[a][j] = sum_b M[a][b] A^T[j][b], the lane holds all eight b of its (tile, outputs) --, the
 // a direction goes through LDS in passes of 32 outputs (two MFMA output tiles): X[a 8][j 6] planes of XPS bytes, a plane = [tile 16][32 outputs]
-// with the 16-byte unit of output quad q of tile t at (q ^ (t & 7)).
+// with the 16-byte unit of output quad q of tile t at (q ^ (t & 7)), and the 8-byte half hf of that unit at 8 (hf ^ (t >> 3)).  Every access moves one
+// half (ds_write_b64 / ds_read_b64); tools/wino6_banks.py enumerates the bank of every lane of every one of them: no conflicts.
 //   * In-register part: packed ops in program order (volatile asm), one (output tile, register pair) at a time, every result written to LDS as
 //     soon as it exists: 20 transient registers.  (As elementwise vector code over whole accumulators the compiler interleaved everything
-//     and spilled the accumulators -- and the spills landed inside the K loop.)
-//   * Reads (ds_read_b128, item = (quad fastest, then x)): the eight quads of a pixel fill 128 bytes, the pixel's neighbour (j + 1, same tile: x
-//     pairs never straddle a tile, 6 is even) sits XPS = 128 (mod 256) bytes on -- the other half of the banks.
+//     and spilled the accumulators -- and the spills landed inside the K loop.)  A 16-lane write group holds tiles t and t + 8 at the same unit
+//     offset, 1 024 bytes apart: the swapped halves keep them on different banks.
 //   * Item = (quad q of the pass's 32 outputs, pixel x of the 48-wide row, tile row, parity): output rows i = parity, parity + 2, parity + 4 of
 //     the tile (the even rows need M0 and the sums M1+M2, M3+M4, M5+M6 of a column, the odd ones the differences and M7), 768 items per parity, 3 per
-//     thread of the four waves that take that parity (wave-uniform: its coefficients are scalars); lanes = (quad, x parity, x / 2 ...): a wave's stores cover 8 pixels x 32 bytes in each of four 8-channel chunks.
+//     thread of the four waves that take that parity (wave-uniform: its coefficients are scalars); lanes = (quad, x parity, tile row, x / 2):
+//     a wave's stores cover 4 pixels x 32 bytes of two rows in each of four 8-channel chunks.
+//   * Reads: a 32-lane read group is the eight quads of pixels (x, x + 1) of BOTH tile rows.  The quads of a pixel touch one half of each unit of a
+//     128-byte line; the pixel's neighbour (j + 1, same tile: x pairs never straddle a tile, 6 is even) sits XPS = 128 (mod 256) bytes on -- the
+//     other 32 banks --, and the other tile row (tile t + 8) has its halves swapped: the four pixels tile the 64 banks.  (Four pixels of ONE row,
+//     as the items were ordered first, put x and x + 2 on the same banks: 2-way on every read.)
 //   * Stores are buffer stores whose offset is -16 for anything outside the tensor (dropped by the range check): no control flow.
 template <int NT>
 __device__ __forceinline__ void wino6_output(wino6::f32x4 (&acc)[8][NT], char *smem, const ConvLaunch &p, int tid, int lane, int wave, int nb,
-                                             int img, int ox0, int oy0, bool tr_on, int tr_item, long long *tr_buf)
+                                             int img, int ox0, int oy0, int nb_next, bool tr_on, int tr_item, long long *tr_buf)
 {
     using namespace wino6;
     // the lane id through an opaque register: everything derived from it is computed HERE and not hoisted out of the K loop (hoisted, it sat
@@ -154,6 +159,19 @@ __device__ __forceinline__ void wino6_output(wino6::f32x4 (&acc)[8][NT], char *s
     const float slope = p.leaky ? 0.2f : 1.f;
     const f32x2 pSl = {slope, slope};
     const int rowstep = 2 * p.Wo * p.out_pix_stride * 4;                     // bytes between the rows an item stores
+    // The block's next item starts from these accumulators: zero, and in wave 1 the bias of its n-block nb_next for b = 1 (A^T's column of the
+    // point x = 1 is all ones, so a constant added to M[xi = (1, 1)] comes out of A^T M A as that constant in every output pixel).  The registers
+    // of a pass's two output tiles are dead once it has dumped them, and its rounds wait for LDS with the VALU idle: round rr resets b = 3 rr ..
+    // 3 rr + 2 of them there, off the path from the last store to the next item's first MFMA.  (After a block's last item: harmless.)
+    const float bsel = wave == 1 ? 1.f : 0.f;
+    const int bias_next = BIAS_OFF + (nb_next - p.nb0) * 256;                // (+ the lane's output quad, from tid where it is used: no register held across the dump)
+    // (through an empty asm: a plain constant is no instruction to the compiler -- it writes the zeros where the loop's paths meet, after the last round)
+#define W6_ACC_RESET(b_, mt_)                                                                       \
+    do {                                                                                            \
+        if ((b_) == 1) acc[1][mt_] = *reinterpret_cast<const f32x4 *>(smem + bias_next + 64 * (mt_) + (tid & 48)) * bsel; \
+        else acc[b_][mt_] = f32x4{0.f, 0.f, 0.f, 0.f};                                              \
+        asm volatile("" : "+v"(acc[b_][mt_]));                                                      \
+    } while (0)
 #pragma unroll
     for (int ps = 0; ps < NT / 2; ++ps) {
         if (ps > 0) W6_LDS_BARRIER();           // the previous pass's reads are over
@@ -161,7 +179,7 @@ __device__ __forceinline__ void wino6_output(wino6::f32x4 (&acc)[8][NT], char *s
         for (int mtp = 0; mtp < ((W6_ABLATE & 64) ? 0 : 2); ++mtp) {
             const int mt = 2 * ps + mtp;
             const int quad = mtp * 4 + q4;
-            char *dp = smem + X_OFF + (wave * 6) * XPS + t16 * 128 + ((quad ^ (t16 & 7)) * 16);
+            const int doff = X_OFF + (wave * 6) * XPS + t16 * 128 + ((quad ^ (t16 & 7)) * 16) + 8 * (t16 >> 3);      // (half hf at doff ^ 8 hf)
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 f32x2 m0 = W6_HALF(acc[0][mt], hf), m1 = W6_HALF(acc[1][mt], hf), m2 = W6_HALF(acc[2][mt], hf), m3 = W6_HALF(acc[3][mt], hf);
@@ -194,7 +212,7 @@ __device__ __forceinline__ void wino6_output(wino6::f32x4 (&acc)[8][NT], char *s
                              : "=&v"(s1), "=&v"(s2), "=&v"(s3), "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3), "+v"(m4), "+v"(m5), "+v"(m6), "+v"(m7)
                              : "s"(c2h), "s"(c4h), "s"(c8h), "s"(c16h), "s"(c32h));
                 const f32x2 t1 = m1, t2 = m5, t3 = m3, t4 = s1;
-                f32x2 *d2p = reinterpret_cast<f32x2 *>(dp + 8 * hf);
+                f32x2 *d2p = reinterpret_cast<f32x2 *>(smem + (doff ^ (8 * hf)));
                 d2p[0 * (XPS / 8)] = m0; d2p[1 * (XPS / 8)] = t1; d2p[2 * (XPS / 8)] = t2;
                 d2p[3 * (XPS / 8)] = t3; d2p[4 * (XPS / 8)] = t4; d2p[5 * (XPS / 8)] = m7;
             }
@@ -212,21 +230,28 @@ __device__ __forceinline__ void wino6_output(wino6::f32x4 (&acc)[8][NT], char *s
 #pragma unroll
         for (int rr = 0; rr < ((W6_ABLATE & 32) ? 0 : 3); ++rr) {
             const int idx = (tid & 255) + 256 * rr;                             // 768 items of this parity
-            const int quad = idx & 7, xl = (idx >> 3) & 1, mm = idx >> 4;       // mm in 0..47
-            const int tyy = mm >= 24 ? 1 : 0, x2 = mm - 24 * tyy;
+            const int quad = idx & 7, xl = (idx >> 3) & 1, tyy = (idx >> 4) & 1, x2 = idx >> 5;      // x2 in 0..23
             const int x = 2 * x2 + xl, txx = x / 6, j = x - 6 * txx;
             const int tile = tyy * 8 + txx;
-            const char *xb = smem + X_OFF + j * XPS + tile * 128 + ((quad ^ (tile & 7)) * 16);
+            const int xo = X_OFF + j * XPS + tile * 128 + ((quad ^ (tile & 7)) * 16) + 8 * tyy;                       // (half hf at xo ^ 8 hf)
             const int co0 = nb * 64 + ps * 32 + quad * 4;
             // even rows: y0 = M0 + s1 + s2 + s3, y2 = s1 + 4 s2 + s3/4, y4 = s1 + 16 s2 + s3/16;  odd: y1 = d1 + 2 d2 + d3/2, y3 = d1 + 8 d2 + d3/8,
             // y5 = d1 + 32 d2 + d3/32 + M7 -- one instruction stream with wave-uniform coefficients, one half (two outputs) of the quad at a time
             f32x2 y[3][2];
+            // all fourteen reads of the round first, ONE wait: the statement of the first half names the second half's registers as (unused) inputs.
+            // (Half by half -- seven reads, wait, eleven FMAs, twice -- a round exposed the LDS latency twice, and two waves per SIMD do not hide it.)
+            f32x2 mq[2][7];
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-                const f32x2 *xh = reinterpret_cast<const f32x2 *>(xb + 8 * hf);
-                f32x2 m1 = xh[1 * 6 * (XPS / 8)], m2 = xh[2 * 6 * (XPS / 8)], m3 = xh[3 * 6 * (XPS / 8)], m4 = xh[4 * 6 * (XPS / 8)];
-                f32x2 m5 = xh[5 * 6 * (XPS / 8)], m6 = xh[6 * 6 * (XPS / 8)];
-                const f32x2 me = *reinterpret_cast<const f32x2 *>(xb + 8 * hf + xe_off);
+                const f32x2 *xh = reinterpret_cast<const f32x2 *>(smem + (xo ^ (8 * hf)));
+#pragma unroll
+                for (int a = 1; a <= 6; ++a) mq[hf][a - 1] = xh[a * 6 * (XPS / 8)];
+                mq[hf][6] = xh[xe_off / 8];
+            }
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                f32x2 m1 = mq[hf][0], m2 = mq[hf][1], m3 = mq[hf][2], m4 = mq[hf][3], m5 = mq[hf][4], m6 = mq[hf][5];
+                const f32x2 me = mq[hf][6];
                 // in place: e1, e2, e3 over M1, M3, M5; the three rows over M2, M4, M6
                 asm volatile("v_pk_fma_f32 %0, %7, %1, %0" W6_SEL3_LO "\n\t"                   /* e1 = M1 +- M2 */
                              "v_pk_fma_f32 %2, %7, %3, %2" W6_SEL3_LO "\n\t"                   /* e2 = M3 +- M4 */
@@ -240,7 +265,8 @@ __device__ __forceinline__ void wino6_output(wino6::f32x4 (&acc)[8][NT], char *s
                              "v_pk_fma_f32 %1, %8, %4, %1" W6_SEL3_HI "\n\t"                   /* ... + a3 e3 */
                              "v_pk_fma_f32 %5, %11, %6, %5" W6_SEL3_LO                         /* ... + k7 Me */
                              : "+v"(m1), "+v"(m2), "+v"(m3), "+v"(m4), "+v"(m5), "+v"(m6)
-                             : "v"(me), "s"(pSK), "s"(pA), "s"(pB), "s"(pC), "s"(pK7));
+                             : "v"(me), "s"(pSK), "s"(pA), "s"(pB), "s"(pC), "s"(pK7),
+                               "v"(mq[1][0]), "v"(mq[1][1]), "v"(mq[1][2]), "v"(mq[1][3]), "v"(mq[1][4]), "v"(mq[1][5]), "v"(mq[1][6]));
                 y[0][hf] = m2; y[1][hf] = m4; y[2][hf] = m6;
             }
             const int oy = oy0 + 6 * tyy + par, ox = ox0 + x;
@@ -249,7 +275,7 @@ __device__ __forceinline__ void wino6_output(wino6::f32x4 (&acc)[8][NT], char *s
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 // LeakyReLU(0.2) = max(v, 0.2 v) (slope 1: identity): two packed multiplies, four plain maxima as asm (fmaxf() costs a second
-                // v_max per element: hipcc canonicalises NaNs first).  The bias came through the accumulators (W6_ITEM_START).
+                // v_max per element: hipcc canonicalises NaNs first).  The bias came through the accumulators (W6_ACC_RESET).
                 f32x2 tl0, tl1;
                 W6_PK_MUL(tl0, pSl, LO, y[i][0]);
                 W6_PK_MUL(tl1, pSl, LO, y[i][1]);
@@ -264,10 +290,23 @@ __device__ __forceinline__ void wino6_output(wino6::f32x4 (&acc)[8][NT], char *s
                 const unsigned vo = (ok && oy + 2 * i < p.Ho) ? ooff + (unsigned)(i * rowstep) : 0xfffffff0u;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), o_rsrc, (int)vo, 0, W6_OUT_AUX);
             }
+#pragma unroll
+            for (int b = 3 * rr; b < 3 * rr + 3 && b < 8; ++b) {
+                W6_ACC_RESET(b, 2 * ps);
+                W6_ACC_RESET(b, 2 * ps + 1);
+            }
             __builtin_amdgcn_sched_barrier(0);                                  // one round at a time: hoisting the next round's reads spilled registers
+        }
+        if (W6_ABLATE & 32) {                                                   // (timing builds without rounds)
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                W6_ACC_RESET(b, 2 * ps);
+                W6_ACC_RESET(b, 2 * ps + 1);
+            }
         }
         W6_T(4 + 3 * ps);
     }
+#undef W6_ACC_RESET
 }
 
 template <int NT>
@@ -340,6 +379,9 @@ __global__ __launch_bounds__(512) void conv3x3_wino6(const ConvLaunch p)
     // works on ONE n-block -- its L2 then holds that n-block's weights only (200 -> 128: 3.2 of 6.4 MB; an L2 has 4 MB) -- and a contiguous
     // range of tiles; the patch is read by nblk XCDs instead of one.
     const int nb_xcd = (W6_NB_XCD && p.nblk > 1 && 8 % p.nblk == 0 && (G & 7) == 0 && (total / p.nblk) % (8 / p.nblk) == 0) ? 1 : 0;
+    // (quotients by the launch's n-blocks, items per row and item rows: multiplications by the launcher's reciprocals, w6_div_magic -- as
+    // divisions by run-time values the three were some hundred instructions between the last store of an item and the first MFMA of the next)
+#define W6_DIV(n_, i_) ((int)(((u64)(unsigned)(n_) * p.w6_mul[i_]) >> p.w6_sh[i_]))
 #define W6_DECODE(v_, nb_, img_, ox0_, oy0_)                                                        \
     do {                                                                                            \
         int bid__;                                                                                  \
@@ -349,20 +391,26 @@ __global__ __launch_bounds__(512) void conv3x3_wino6(const ConvLaunch p)
             bid__ = (xcd__ / p.nblk) * ((total / p.nblk) / (8 / p.nblk)) + k__;                     \
         } else {                                                                                    \
             bid__ = xcd_remap((v_), total);                                                         \
-            nb_ = bid__ % p.nblk + p.nb0;                                                           \
-            bid__ /= p.nblk;                                                                        \
+            const int q__ = W6_DIV(bid__, 0);                                                       \
+            nb_ = bid__ - q__ * p.nblk + p.nb0;                                                     \
+            bid__ = q__;                                                                            \
         }                                                                                           \
-        ox0_ = (bid__ % tiles_x) * OW;                                                              \
-        bid__ /= tiles_x;                                                                           \
-        oy0_ = (bid__ % tiles_y) * OH;                                                              \
-        img_ = bid__ / tiles_y;                                                                     \
+        const int qx__ = W6_DIV(bid__, 1), qy__ = W6_DIV(qx__, 2);                                  \
+        ox0_ = (bid__ - qx__ * tiles_x) * OW;                                                       \
+        oy0_ = (qx__ - qy__ * tiles_y) * OH;                                                        \
+        img_ = qy__;                                                                                \
     } while (0)
 #define W6_MASKS(ox0_, oy0_, out_)                                                                  \
     do {                                                                                            \
-        const int gx__ = (ox0_) - 1 + s_px;                                                         \
+        /* (the thread's patch row and column again, from an opaque lane id: held in registers they would live through the K loop) */ \
+        int z__ = 0;                                                                                \
+        asm volatile("" : "+v"(z__));                                                               \
+        const int t__ = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z__)); \
+        const int si__ = min(t__, NSTG - 1) >> 1, r5__ = si__ / PW, px__ = si__ - r5__ * PW;        \
+        const int gx__ = (ox0_) - 1 + px__;                                                         \
         _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                             \
-            const int gy__ = (oy0_) - 1 + s_r5 + (i == 2 ? 9 : 5 * i);                              \
-            out_[i] = __builtin_amdgcn_ballot_w64(gy__ >= 0 && gy__ < p.H && gx__ >= 0 && gx__ < p.W); \
+            const int gy__ = (oy0_) - 1 + r5__ + (i == 2 ? 9 : 5 * i);                              \
+            out_[i] = __builtin_amdgcn_ballot_w64(((unsigned)gy__ < (unsigned)p.H) & ((unsigned)gx__ < (unsigned)p.W));   /* (no &&: it compiled to branches) */ \
         }                                                                                           \
     } while (0)
     // base addresses of the two K segments at the patch origin (oy0 - 1, ox0 - 1) of an item (may lie before the tensor: never dereferenced there)
@@ -596,6 +644,10 @@ __global__ __launch_bounds__(512) void conv3x3_wino6(const ConvLaunch p)
             W6_MASKS(nxt_ox0, nxt_oy0, mk_n);                                                       \
             W6_BASES(nxt_img, nxt_ox0, nxt_oy0, nxt_b0, nxt_b1);                                    \
         }                                                                                           \
+    } while (0)
+    // accumulators of the block's first item (every later one: the output stage of the item before it, W6_ACC_RESET)
+#define W6_ACC_INIT()                                                                               \
+    do {                                                                                            \
         _Pragma("unroll") for (int b = 0; b < 8; ++b)                                               \
             _Pragma("unroll") for (int mt = 0; mt < NT; ++mt) acc[b][mt] = f32x4{0.f, 0.f, 0.f, 0.f}; \
         /* the bias rides in the accumulators: A^T's column of the point x = 1 is all ones, so a constant added to M[xi = (1, 1)] comes out */ \
@@ -618,8 +670,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino6(const ConvLaunch p)
         bo_c = bo_n;                                                                                \
         if (++c == nchunks) {                                                                       \
             W6_T(1);                                                                                \
-            if (W6_ABLATE & 512) wino6_output<NT>(acc, smem, p, tid, lane, wave, cur_nb, first_img, first_ox0, first_oy0, tr_on, tr_item, tr_buf); /* (timing: every item of a block stores to its first item's place -- L2-resident) */ \
-            else wino6_output<NT>(acc, smem, p, tid, lane, wave, cur_nb, cur_img, cur_ox0, cur_oy0, tr_on, tr_item, tr_buf); \
+            if (W6_ABLATE & 512) wino6_output<NT>(acc, smem, p, tid, lane, wave, cur_nb, first_img, first_ox0, first_oy0, nxt_nb, tr_on, tr_item, tr_buf); /* (timing: every item of a block stores to its first item's place -- L2-resident) */ \
+            else wino6_output<NT>(acc, smem, p, tid, lane, wave, cur_nb, cur_img, cur_ox0, cur_oy0, nxt_nb, tr_on, tr_item, tr_buf); \
             if (!has_next) { more = false; }                                                        \
             else {                                                                                  \
                 v_cur += G;                                                                         \
@@ -634,6 +686,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino6(const ConvLaunch p)
     } while (0)
     const int first_img = cur_img, first_ox0 = cur_ox0, first_oy0 = cur_oy0;
     W6_ITEM_START();
+    W6_ACC_INIT();
     W6_T(0);
     while (more) {
         W6_RUN(0);
@@ -641,6 +694,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino6(const ConvLaunch p)
         W6_RUN(1);
     }
 #undef W6_RUN
+#undef W6_ACC_INIT
 #undef W6_ITEM_START
 #undef W6_PERIOD
 #undef W6_SLOT_VMEM
@@ -656,6 +710,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino6(const ConvLaunch p)
 #undef W6_BASES
 #undef W6_MASKS
 #undef W6_DECODE
+#undef W6_DIV
 }
 
 bool wino6_supported(const ConvLaunch &p)
@@ -695,13 +750,17 @@ static hipError_t launch_wino6_t(const ConvLaunch &p, int nb0, int nblk, hipStre
     q.bias = p.bias_w6;
     q.nb0 = nb0;
     q.nblk = nblk;
+    w6_div_magic(nblk, &q.w6_mul[0], &q.w6_sh[0]);
+    w6_div_magic((p.Wo + OW - 1) / OW, &q.w6_mul[1], &q.w6_sh[1]);
+    w6_div_magic((p.Ho + OH - 1) / OH, &q.w6_mul[2], &q.w6_sh[2]);
     q.trace = nullptr;
 #if W6_TRACE
     static long long *trace_dev = nullptr;
     static int traced = 0;
     const int tr_want = getenv("B2F_WINO_TRACE") ? atoi(getenv("B2F_WINO_TRACE")) : 0;
     const int nch = p.seg[0].nchunks + (p.nseg > 1 ? p.seg[1].nchunks : 0);
-    const bool do_trace = NT == 4 && tr_want == nch && traced < 1 && p.H * p.W >= 256 * 480;
+    const int tr_nt = getenv("B2F_WINO_TRACE_NT") ? atoi(getenv("B2F_WINO_TRACE_NT")) : 4;     // block form to stamp: 4 (64 outputs) or 2 (32 outputs)
+    const bool do_trace = NT == tr_nt && tr_want == nch && traced < 1 && p.H * p.W >= 256 * 480;
     if (do_trace) {
         if (!trace_dev) hipMalloc(&trace_dev, 512 * sizeof(long long));
         hipMemsetAsync(trace_dev, 0, 512 * sizeof(long long), s);
@@ -721,12 +780,12 @@ static hipError_t launch_wino6_t(const ConvLaunch &p, int nb0, int nblk, hipStre
         hipStreamSynchronize(s);
         hipMemcpy(h, trace_dev, sizeof h, hipMemcpyDeviceToHost);
         for (int w = 0; w < 2; ++w) {
-            fprintf(stderr, "wino6 trace, block 40 wave %d, %d chunks: per item, cycles: K loop (per chunk) | dump 0 | barrier | rounds 0 | barrier + dump 1 | barrier | rounds 1 | item switch\n", 4 * w, nch);
+            fprintf(stderr, "wino6<%d> trace, block 40 wave %d, %d chunks: per item, cycles: K loop (per chunk) | dump 0 | barrier | rounds 0 | barrier + dump 1 | barrier | rounds 1 | item switch\n", NT, 4 * w, nch);
             for (int it = 0; it < 6; ++it) {
                 const long long *t = h + w * 128 + it * 16;
                 if (!t[0]) continue;
                 fprintf(stderr, "  item %d: %7lld (%5lld) | %5lld | %5lld | %5lld | %5lld | %5lld | %5lld | %5lld\n", it, t[1] - t[0], (t[1] - t[0]) / nch, t[2] - t[1], t[3] - t[2], t[4] - t[3],
-                        t[5] - t[4], t[6] - t[5], t[7] - t[6], t[8] - t[7]);
+                        NT == 4 ? t[5] - t[4] : 0, NT == 4 ? t[6] - t[5] : 0, NT == 4 ? t[7] - t[6] : 0, t[8] - t[NT == 4 ? 7 : 4]);      // (32-output blocks: one pass)
             }
         }
     }
