@@ -123,6 +123,16 @@ SIGNATURES = {
     "b2f_multi_compute_flow_sequence_warp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
                                                        C.c_void_p, C.POINTER(C.c_ulonglong), c_float_p, c_float_p, C.POINTER(C.c_ubyte),
                                                        C.POINTER(C.c_ubyte)]),
+    "b2f_table_loss_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                      C.POINTER(C.c_ulonglong)]),
+    "b2f_table_loss_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                        C.c_void_p, C.c_void_p]),
+    "b2f_op_table_loss": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                    C.POINTER(C.c_ulonglong)]),
+    "b2f_forward_loss": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong),
+                                   C.POINTER(c_float_p), C.c_int]),
+    "b2f_forward_loss_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "b2f_multi_forward_loss": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong)]),
     "b2f_forward": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(c_float_p), C.c_int]),
     "b2f_output_shapes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.c_int]),

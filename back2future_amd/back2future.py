@@ -32,6 +32,13 @@ SCORE_PIXELS, SCORE_EPE_Q20, SCORE_OUTLIERS, SCORE_OCC, SCORE_NONFINITE, SCORE_W
 # target lies in / leaves the image, Q30 sums of the L1 penalty, of the squared difference, of the occlusion-weighted penalty and of
 # the weights over the inside pixels, pixels with a NaN coordinate, error or weight
 PHOTO_INSIDE, PHOTO_OUTSIDE, PHOTO_CHARB_Q30, PHOTO_SQ_Q30, PHOTO_OCHARB_Q30, PHOTO_WEIGHT_Q30, PHOTO_NONFINITE, PHOTO_WORDS = 0, 2, 4, 6, 8, 10, 12, 14
+# words of a loss record (include/b2f.h, B2F_LOSS_*; test.lua:266-297), one record per image and table level: the level's pixels, Q30
+# sums of the flow smoothness (future, past), the constant-velocity term, the occlusion smoothness and the occlusion prior, the photo
+# words (each base + direction, 0 the past frame, 1 the future one) and the pixels with a NaN smoothness, velocity or prior term
+LOSS_PIXELS, LOSS_SMOOTH_FLOW_Q30, LOSS_SMOOTH_PAST_Q30, LOSS_CONST_VEL_Q30, LOSS_SMOOTH_OCC_Q30, LOSS_PRIOR_OCC_Q30 = 0, 1, 2, 3, 4, 5
+LOSS_PHOTO_INSIDE, LOSS_PHOTO_OUTSIDE, LOSS_PHOTO_OCHARB_Q30, LOSS_PHOTO_NONFINITE, LOSS_NONFINITE, LOSS_WORDS = 6, 8, 10, 12, 14, 16
+LOSS_LEVEL_WEIGHTS = (0.005, 0.01, 0.02, 0.08, 0.32, 0.64, 1.28)                                               # test.lua:29-31
+LOSS_WEIGHTS = {"smooth_flow": 1.0, "const_vel": 1.0, "pme": 1.0, "smooth_occ": 0.1, "prior_occ": 0.1}       # opts.lua:61-73
 
 
 def normalize(imgs):
@@ -528,6 +535,67 @@ def photo_summary(photo):
             "nonfinite": sum(nonf)}
 
 
+def loss_summary(records, like="test", size_average=False, weights=None):
+    """The unsupervised validation loss of test.lua:266-297 from loss records (uint64 n x L x 16 or L x 16; ops.table_loss,
+    Model.forwardLoss).  Per level j
+        level_weights[j] * (smooth_flow * S + const_vel * cv + pme * ((OCHARB0 + OCHARB1) / 2^30 + OUTSIDE0 + OUTSIDE1) / (3 * 2)
+                            + smooth_occ * so + prior_occ * pr)
+    with the level weights of test.lua:29-31 and the weights of opts.lua:61-73 (1, 1, 1, 0.1, 0.1; `weights` replaces any of them).
+    like="test": S = n_flow * fs, test.lua:275-277 takes the future flow n_flow times (2 for a Soft table, 1 for a Hard one);
+    like="train": S = fs + fp (train.lua:428-432).  A table is Soft when its records carry past-flow or constant-velocity sums.
+    size_average=True applies the criteria's own norm factors per triplet: 1 / (2 h w) for the smoothness and velocity terms,
+    1 / (h w) for the photometric term and the prior.  Returns a dict: every term per triplet and level (n x L float64 arrays
+    "smooth_flow", "smooth_past", "const_vel", "pme", "smooth_occ", "prior_occ", weighted by neither), "level" (n x L, the weighted
+    sum above), "loss" (n, the sum over the levels), "mean" (the mean of "loss") and "nonfinite" (pixels left out of a sum because
+    a term was NaN, both kinds of words).  The sums are exact integers; each pixel term carries the Q30 rounding (2^-31)."""
+    s = np.asarray(records)
+    if s.dtype != np.uint64 or s.shape[-1:] != (LOSS_WORDS,) or s.ndim not in (2, 3):
+        raise ValueError("loss_summary: expected uint64 records of shape (n, L, %d) or (L, %d), got %s %r" % (LOSS_WORDS, LOSS_WORDS, s.dtype, s.shape))
+    if like not in ("test", "train"):
+        raise ValueError("loss_summary: like must be 'test' or 'train'")
+    s = s.reshape((-1,) + s.shape[-2:])
+    n, L, _ = s.shape
+    if L > len(LOSS_LEVEL_WEIGHTS):
+        raise ValueError("loss_summary: at most %d levels" % len(LOSS_LEVEL_WEIGHTS))
+    wt = dict(LOSS_WEIGHTS)
+    wt.update(weights or {})
+    one = float(1 << 30)
+    f = s.astype(np.float64)                    # a sum beyond 2^53 rounds by 2^-53 of itself here
+    px = f[:, :, LOSS_PIXELS]
+    fs, fp, cv = f[:, :, LOSS_SMOOTH_FLOW_Q30] / one, f[:, :, LOSS_SMOOTH_PAST_Q30] / one, f[:, :, LOSS_CONST_VEL_Q30] / one
+    so, pr = f[:, :, LOSS_SMOOTH_OCC_Q30] / one, f[:, :, LOSS_PRIOR_OCC_Q30] / one
+    pme = ((f[:, :, LOSS_PHOTO_OCHARB_Q30] + f[:, :, LOSS_PHOTO_OCHARB_Q30 + 1]) / one + f[:, :, LOSS_PHOTO_OUTSIDE] + f[:, :, LOSS_PHOTO_OUTSIDE + 1]) / (3.0 * 2.0)
+    if size_average:
+        fs, fp, cv, so = fs / (2.0 * px), fp / (2.0 * px), cv / (2.0 * px), so / (2.0 * px)
+        pme, pr = pme / px, pr / px
+    soft = bool((s[:, :, LOSS_SMOOTH_PAST_Q30].any() or s[:, :, LOSS_CONST_VEL_Q30].any()))
+    n_flow = float(wt.pop("n_flow", 2.0 if soft else 1.0))   # (weights={"n_flow": ...} overrides what the records suggest)
+    S = n_flow * fs if like == "test" else fs + fp
+    lw = np.asarray(LOSS_LEVEL_WEIGHTS[:L], np.float64)[None, :]
+    level = lw * (wt["smooth_flow"] * S + wt["const_vel"] * cv + wt["pme"] * pme + wt["smooth_occ"] * so + wt["prior_occ"] * pr)
+    loss = level.sum(axis=1)
+    nonf = int(sum(int(v) for v in s[:, :, [LOSS_NONFINITE, LOSS_PHOTO_NONFINITE, LOSS_PHOTO_NONFINITE + 1]].ravel()))
+    return {"smooth_flow": fs, "smooth_past": fp, "const_vel": cv, "pme": pme, "smooth_occ": so, "prior_occ": pr, "level": level,
+            "loss": loss, "mean": float(loss.mean()), "nonfinite": nonf}
+
+
+def _forward_loss(fn, h, x, flow_scale, L, shapes):
+    """x n x 9 x H x W normalized -> (records uint64 n x L x 16, table or None): b2f_forward_loss / b2f_multi_forward_loss"""
+    x = _lib.f32(x)
+    if x.ndim != 4 or x.shape[1] != 9:
+        raise ValueError("forwardLoss: expected an n x 9 x H x W normalized input, got shape %r" % (x.shape,))
+    n, _, H, W = x.shape
+    loss = np.empty((n, L, LOSS_WORDS), np.uint64)
+    lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong))
+    if shapes is None:
+        _lib.check(fn(h, _lib.fptr(x), n, H, W, float(flow_scale), lp))
+        return loss, None
+    outs = [np.empty((n, c, hh, ww), np.float32) for (c, hh, ww) in shapes(H, W)]
+    ptrs = (_lib.c_float_p * len(outs))(*[_lib.fptr(o) for o in outs])
+    _lib.check(fn(h, _lib.fptr(x), n, H, W, float(flow_scale), lp, ptrs, len(outs)))
+    return loss, outs
+
+
 class Model(object):
     """Owns a b2f_ctx (the `model` global of back2future.lua:113)."""
 
@@ -782,6 +850,30 @@ class Model(object):
         _lib.check(_lib.lib().b2f_forward(self._h, _lib.fptr(x), B, H, W, ptrs, len(outs)))
         return outs
 
+    def forwardLoss(self, x, flow_scale=20.0, want_table=False):
+        """model:forward followed by the unsupervised validation loss of test.lua:266-297 (b2f_forward_loss): x n x 9 x H x W,
+        already normalized -> uint64 records (n, L, 16), those of ops.table_loss(self.forward(x), x[:, 3:6]); the table stays on the
+        GPU.  want_table=True returns (records, table) with the table of Model.forward, bit for bit.  loss_summary reads the
+        records."""
+        L = self.n_outputs // (5 if self.past_flow else 4)
+        if want_table:
+            return _forward_loss(_lib.lib().b2f_forward_loss, self._h, x, flow_scale, L, self.output_shapes)
+        fn = lambda h, xp, n, H, W, fsc, lp: _lib.lib().b2f_forward_loss(h, xp, n, H, W, fsc, lp, None, 0)
+        return _forward_loss(fn, self._h, x, flow_scale, L, None)[0]
+
+    def forwardLossDevice(self, d_in, n, H, W, d_loss, flow_scale=20.0, stream=None):
+        """b2f_forward_loss_device on device pointers (ints): d_in n x 9 x H x W normalized float32, d_loss n x L x 16 uint64 (test.lua:266-297);
+        asynchronous on `stream`."""
+        _lib.check(_lib.lib().b2f_forward_loss_device(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale),
+                                                       C.c_void_p(d_loss), C.c_void_p(stream) if stream else None))
+
+    def tableLossDevice(self, d_table, n, H, W, d_ref, d_loss, flow_scale=20.0, stream=None):
+        """b2f_table_loss_device on device pointers (ints): d_table the L x 4 | 5 tensors of an output table in table order, d_ref
+        n x 3 x H x W, d_loss n x L x 16 uint64 (test.lua:266-297); asynchronous on `stream`."""
+        ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
+        _lib.check(_lib.lib().b2f_table_loss_device(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale),
+                                                     C.c_void_p(d_loss), C.c_void_p(stream) if stream else None))
+
     def forward_device(self, d_in, B, H, W, d_flow=None, d_occ=None, d_est3=None, unit_input=False, stream=None):
         """model:forward on device pointers (ints); asynchronous on `stream`."""
         _lib.check(_lib.lib().b2f_forward_device(
@@ -874,6 +966,13 @@ class MultiModel(object):
         """Model.computeFlowSequenceWarp over the GPUs, with the same keywords, the same bytes and the same words."""
         return _compute_flow_sequence_warp("b2f_multi_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out,
                                            want_prob)
+
+    def forwardLoss(self, x, flow_scale=20.0):
+        """Model.forwardLoss over the GPUs (b2f_multi_forward_loss; test.lua:266-297): the same words."""
+        c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
+        lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+        _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
+        return _forward_loss(_lib.lib().b2f_multi_forward_loss, self._h, x, flow_scale, no.value // (5 if pf.value else 4), None)[0]
 
 
 def shard_range(n, rank, world):

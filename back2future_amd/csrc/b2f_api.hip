@@ -876,7 +876,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1003; }
+int b2f_version(void) { return 1004; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1048,6 +1048,8 @@ void b2f_destroy(b2f_ctx *c)
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
     if (c->dwork.dev) (void)hipFree(c->dwork.dev);
     if (c->vis_max.dev) (void)hipFree(c->vis_max.dev);
+    if (c->loss_pyr.dev) (void)hipFree(c->loss_pyr.dev);
+    if (c->loss_work.dev) (void)hipFree(c->loss_work.dev);
     if (c->arena) (void)hipFree(c->arena);
     if (c->wpk_dev) (void)hipFree(c->wpk_dev);
     if (c->w_dev) (void)hipFree(c->w_dev);
@@ -1361,6 +1363,164 @@ int b2f_forward(b2f_ctx *c, const float *x, int B, int H, int W, float **outs, i
     return rc;
 }
 B2F_CATCH("b2f_forward")
+
+}  // extern "C"
+
+// ---- model:forward followed by the unsupervised validation loss of test.lua:266-297 -------------------------------
+namespace {
+
+// what a b2f_forward_loss* call needs from the context's loss workspace for sub-batches of nb triplets
+struct LossPlan {
+    int L = 0, per = 0, n_outs = 0;
+    std::vector<size_t> cnt, off;   // floats and byte offset of every tensor of the table
+    size_t in_off = 0, loss_off = 0, bytes = 0;
+};
+
+int check_forward_loss(const b2f_ctx *c, const std::string &w, int n, int H, int W, double flow_scale)
+{
+    if (c->g.two_frame) return fail(w + ": a two_frame model has no occlusions in its table; the loss of test.lua:266-297 is not defined for it");
+    if (c->g.shipped()) CHK(check_shape(n, H, W));
+    else if (n <= 0 || H <= 0 || W <= 0 || H % (1 << (c->g.levels - 1)) || W % (1 << (c->g.levels - 1)))
+        return fail(w + ": H and W must be positive multiples of 2^(levels - 1)");
+    int L = 0;
+    const char *why = table_loss_refusal(c->g.n_outputs(), c->past_flow ? 5 : 4, n, H, W, flow_scale, &L);
+    if (why) return fail(w + ": " + why);
+    return 0;
+}
+
+LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input)
+{
+    LossPlan p;
+    p.per = c->past_flow ? 5 : 4;
+    p.n_outs = c->g.n_outputs();
+    p.L = p.n_outs / p.per;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    p.in_off = take(with_input ? (size_t)nb * 9 * H * W * sizeof(float) : 0);
+    for (int i = 0; i < p.n_outs; ++i) {
+        const int j = i / p.per, ch = (i % p.per) >= p.per - 2 ? 3 : 2;
+        p.cnt.push_back((size_t)nb * ch * (H >> j) * (W >> j));
+        p.off.push_back(take(p.cnt.back() * sizeof(float)));
+    }
+    p.loss_off = take((size_t)nb * p.L * B2F_LOSS_WORDS * sizeof(unsigned long long));
+    p.bytes = off;
+    return p;
+}
+
+// the table of nb triplets into tab (device tensors in table order), then its records into d_loss; all on s
+int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const LossPlan &lp, float *const *tab,
+                     unsigned long long *d_loss)
+{
+    if (c->g.shipped()) {
+        const Plan P = make_plan(nb, H, W, true, c->past_flow);
+        CHK(ensure_workspace(c, P));
+        Outs O;
+        for (int j = 0; j < lp.L; ++j) {
+            const int l = c->g.l_st() + j;
+            int k = j * lp.per;
+            O.t_ufs[l] = tab[k++];
+            if (c->past_flow) O.t_ubfs[l] = tab[k++];
+            O.t_occ[l] = tab[k++];
+            O.t_iw1[l] = tab[k++];
+            O.t_iw3[l] = tab[k++];
+        }
+        CHK(forward_impl(c, s, false, d_in, B2F_IN_NORMALIZED, P, O));
+    } else {
+        CHK(graph_forward(c, s, false, d_in, B2F_IN_NORMALIZED, nb, H, W, tab));
+    }
+    CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(lp.L, nb, H, W) * sizeof(float)));
+    ProfEvent pe;
+    const bool timed = prof_open(c, s, "table_loss", &pe);
+    const size_t hw = (size_t)H * W;
+    const hipError_t e = launch_table_loss(tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, (float *)c->loss_pyr.dev, flow_scale, d_loss, s);
+    if (timed) prof_close(c, s, pe);
+    HIPCHK(e);
+    return 0;
+}
+
+struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub-batches run (b2f_ctx::req_batch)
+    b2f_ctx *c;
+    ReqBatchScope(b2f_ctx *cc, int n) : c(cc) { c->req_batch = n; }
+    ~ReqBatchScope() { c->req_batch = 0; }
+};
+
+}  // namespace
+
+// b2f_forward_loss on a shard: `req` is the caller's n (b2f_multi_forward_loss passes its own down)
+int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs)
+{
+    const std::string w("b2f_forward_loss");
+    if (!c || !x || !loss) return fail(w + ": null argument");
+    CHK(check_forward_loss(c, w, n, H, W, flow_scale));
+    if ((outs == nullptr) != (n_outs == 0)) return fail(w + ": outs and n_outs go together (NULL and 0: the table is not downloaded)");
+    if (outs && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be 0 or (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
+    for (int i = 0; i < n_outs; ++i)
+        if (!outs[i]) return fail(w + ": null tensor in outs");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw = (size_t)H * W;
+    const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
+    const LossPlan lp = make_loss_plan(c, sb, H, W, true);
+    CHK(ensure_dev_work(c->loss_work, lp.bytes));
+    char *base = c->loss_work.dev;
+    std::vector<float *> tab((size_t)lp.n_outs);
+    for (int i = 0; i < lp.n_outs; ++i) tab[(size_t)i] = (float *)(base + lp.off[(size_t)i]);
+    float *d_in = (float *)(base + lp.in_off);
+    unsigned long long *d_loss = (unsigned long long *)(base + lp.loss_off);
+    ReqBatchScope rb(c, req > 0 ? req : n);
+    hipStream_t s = c->stream;
+    for (int b0 = 0; b0 < n; b0 += sb) {
+        const int nb = std::min(sb, n - b0);
+        HIPCHK(hipMemcpyAsync(d_in, x + (size_t)b0 * 9 * hw, (size_t)nb * 9 * hw * sizeof(float), hipMemcpyHostToDevice, s));
+        // (a shorter last sub-batch lays its tensors out for nb images in the same buffers)
+        CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, lp, tab.data(), d_loss));
+        HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * B2F_LOSS_WORDS, d_loss, (size_t)nb * lp.L * B2F_LOSS_WORDS * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, s));
+        for (int i = 0; i < n_outs; ++i) {
+            const size_t per_img = lp.cnt[(size_t)i] / (size_t)sb;
+            HIPCHK(hipMemcpyAsync(outs[i] + (size_t)b0 * per_img, tab[(size_t)i], (size_t)nb * per_img * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+extern "C" {
+
+// model:forward + test.lua:266-297 from host memory
+int b2f_forward_loss(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try
+{
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs);
+}
+B2F_CATCH("b2f_forward_loss")
+
+// model:forward + test.lua:266-297 on device pointers
+int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
+                            void *stream) try
+{
+    const std::string w(__func__);
+    if (!c || !dev_in || !dev_loss) return fail(w + ": null argument");
+    if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
+    CHK(check_forward_loss(c, w, n, H, W, flow_scale));
+    if (((uintptr_t)dev_in | (uintptr_t)dev_loss) & 15) return fail(w + ": device buffers must be 16-byte aligned");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw = (size_t)H * W;
+    const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
+    const LossPlan lp = make_loss_plan(c, sb, H, W, false);
+    CHK(ensure_dev_work(c->loss_work, lp.bytes));
+    std::vector<float *> tab((size_t)lp.n_outs);
+    for (int i = 0; i < lp.n_outs; ++i) tab[(size_t)i] = (float *)(c->loss_work.dev + lp.off[(size_t)i]);
+    ReqBatchScope rb(c, n);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    for (int b0 = 0; b0 < n; b0 += sb)
+        CHK(forward_loss_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, lp, tab.data(),
+                             dev_loss + (size_t)b0 * lp.L * B2F_LOSS_WORDS));
+    return 0;
+}
+B2F_CATCH("b2f_forward_loss_device")
+
+}  // extern "C"
+
+extern "C" {
 
 // ---- op-level entry points (host pointers; reference module layouts) -----------------------
 namespace {

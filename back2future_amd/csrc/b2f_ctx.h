@@ -464,6 +464,8 @@ struct b2f_ctx : b2f::KernelOpts {
     std::unique_ptr<b2f::CopyPool> pool_in, pool_out;
     b2f::DevWork dwork;           // b2f_compute_flow_device / b2f_compute_flow_sequence_device
     b2f::DevWork vis_max;         // b2f_flow_rgb_device without dev_max_used: the per-image maxima of the automatic mode
+    b2f::DevWork loss_pyr;        // b2f_table_loss_device / b2f_forward_loss*: the pooled reference images R_1 .. R_{L-1} (test.lua:266-297)
+    b2f::DevWork loss_work;       // b2f_forward_loss*: [input | output table | records] of a sub-batch
     std::vector<b2f_stream *> streams;   // open streams (b2f_stream_open); b2f_destroy closes what is left
 };
 
@@ -490,6 +492,8 @@ int check_shape(int B, int H, int W);
 bool prof_open(b2f_ctx *c, hipStream_t s, const char *name, ProfEvent *pe);
 void prof_close(b2f_ctx *c, hipStream_t s, const ProfEvent &pe);
 void drop_graphs(b2f_ctx *c);
+// b2f_tableloss.hip: grows a workspace of the context to `bytes` (after a device synchronisation when it has to be replaced)
+int ensure_dev_work(DevWork &dw, size_t bytes);
 void drop_gen_out(b2f_ctx *c);
 // model:forward on device pointers, optionally replayed from a hipGraph (see b2f_api.hip); seq: dev_in holds the B + 2 frames
 // of a sequence (T x 3 x H x W) instead of B triplets (B x 9 x H x W)
@@ -501,6 +505,8 @@ int check_request(const FlowRequest &r);
 // b2f_pipeline.hip: a request on host buffers (the upload / kernels / download pipeline) and on device buffers (the kernels alone,
 // asynchronous on `stream`, nullptr: the context's)
 int compute_flow_host(b2f_ctx *c, const FlowRequest &r);
+// b2f_api.hip: b2f_forward_loss (test.lua:266-297 behind model:forward) on n of a request of `req` triplets (0: n)
+int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs);
 int compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream);
 // b2f_pipeline.hip: a push (r.stream) on host buffers, synchronous, and on device buffers, asynchronous on `stream`; *ready = 1 when
 // the outputs were written (from the third push on)

@@ -5,6 +5,7 @@
 #include "b2f_flowcolor.h"
 #include "b2f_flowscore.h"
 #include "b2f_flowwarp.h"
+#include "b2f_tableloss.h"
 #include "../../include/b2f.h"
 
 #include <cmath>
@@ -272,6 +273,89 @@ void flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int 
                          (unsigned char *)warped, photo);
     else
         flow_warp_host_t(flow, occ_prob, n, H, W, flow_scale, (const float *)im1, (const float *)im2, (const float *)im3, (float *)warped, photo);
+}
+
+}  // namespace b2f
+
+// ---- the unsupervised validation loss on the CPU (test.lua:266-297) ----------------------------------------------------------------
+namespace b2f {
+
+void table_loss_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                     unsigned long long *loss)
+{
+    const int per = past ? 5 : 4;
+    std::vector<float> cur, next;
+    for (int b = 0; b < n; ++b) {
+        const float *R = ref + (size_t)b * 3 * H * W;   // R_0: the normalized centre frame
+        for (int j = 0; j < L; ++j) {
+            const int h = H >> j, w = W >> j;
+            const size_t hw = (size_t)h * w;
+            if (j > 0) {   // R_j = the 2 x 2 mean of R_{j-1} (nn.SpatialAveragePooling(2,2,2,2), test.lua:132,269)
+                const int hp = H >> (j - 1), wp = W >> (j - 1);
+                next.resize(3 * hw);
+                for (int c = 0; c < 3; ++c)
+                    for (int y = 0; y < h; ++y)
+                        for (int x = 0; x < w; ++x) {
+                            const float *q = R + ((size_t)c * hp + 2 * y) * wp + 2 * x;
+                            next[((size_t)c * h + y) * w + x] = (((q[0] + q[1]) + q[wp]) + q[wp + 1]) / 4.0f;
+                        }
+                cur.swap(next);
+                R = cur.data();
+            }
+            const float *const *t = table + (size_t)j * per;
+            const float *f = t[0] + (size_t)b * 2 * hw, *p = past ? t[1] + (size_t)b * 2 * hw : nullptr;
+            const float *o = t[per - 3] + (size_t)b * 2 * hw, *iw[2] = {t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
+            const float *plane[9] = {f, f + hw, p, p ? p + hw : nullptr, o, o + hw, R, R + hw, R + 2 * hw};
+            const float kd = (float)(flow_scale / (double)(1 << j));
+            unsigned long long *rec = loss + ((size_t)b * L + j) * B2F_LOSS_WORDS;
+            for (int k = 0; k < B2F_LOSS_WORDS; ++k) rec[k] = 0;
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    const size_t i = (size_t)y * w + x;
+                    const bool has_x = x + 1 < w, has_y = y + 1 < h;
+                    float v[9], vx[9], vy[9];
+                    for (int c = 0; c < 9; ++c) {
+                        const float *q = plane[c];
+                        v[c] = q ? q[i] : 0.0f;
+                        vx[c] = (q && has_x) ? q[i + 1] : 0.0f;
+                        vy[c] = (q && has_y) ? q[i + w] : 0.0f;
+                    }
+                    const PixelLoss s = loss_pixel(v, vx, vy, has_x, has_y, past);
+                    rec[B2F_LOSS_PIXELS] += 1;
+                    rec[B2F_LOSS_SMOOTH_FLOW_Q30] += s.smooth_flow;
+                    rec[B2F_LOSS_SMOOTH_PAST_Q30] += s.smooth_past;
+                    rec[B2F_LOSS_CONST_VEL_Q30] += s.const_vel;
+                    rec[B2F_LOSS_SMOOTH_OCC_Q30] += s.smooth_occ;
+                    rec[B2F_LOSS_PRIOR_OCC_Q30] += s.prior_occ;
+                    rec[B2F_LOSS_NONFINITE] += s.nonfinite;
+                    for (int d = 0; d < 2; ++d) {
+                        const bool pf = d == 0 && past;   // OBCCriterion.lua:80-81
+                        const WarpTaps tp = warp_taps(pf ? v[2] : v[0], pf ? v[3] : v[1], d == 0 ? -kd : kd, x, y, w, h);
+                        const float w3[3] = {iw[d][i], iw[d][hw + i], iw[d][2 * hw + i]}, r3[3] = {v[6], v[7], v[8]};
+                        const PixelPhoto ph = photo_pixel(tp, w3, r3, true, d == 0 ? v[5] : v[4]);
+                        rec[B2F_LOSS_PHOTO_INSIDE + d] += ph.inside;
+                        rec[B2F_LOSS_PHOTO_OUTSIDE + d] += ph.outside;
+                        rec[B2F_LOSS_PHOTO_OCHARB_Q30 + d] += ph.ocharb;
+                        rec[B2F_LOSS_PHOTO_NONFINITE + d] += ph.nonfinite;
+                    }
+                }
+        }
+    }
+}
+
+// what every b2f_*table_loss* entry checks before anything else (no HIP call): 0 and *L, or the message
+const char *table_loss_refusal(int n_outs, int per, int n, int H, int W, double flow_scale, int *L)
+{
+    if (n <= 0 || H <= 0 || W <= 0) return "bad shape";
+    if (per != 4 && per != 5) return "a level holds 4 (Hard) or 5 (Soft) tensors";
+    if (n_outs <= 0 || n_outs % per) return "n_outs must be L x 4 (Hard) or L x 5 (Soft)";
+    const int lv = n_outs / per;
+    if (lv < 1 || lv > kLossMaxLevels) return "the table must have 1 .. 7 levels (the level weights of test.lua:29-31)";
+    if ((long long)H * W >= kPhotoMaxPixels) return "images of 2^28 pixels or more are refused (the Q30 sums could overflow)";
+    if (H % (1 << (lv - 1)) || W % (1 << (lv - 1))) return "H and W must be multiples of 2^(L - 1)";
+    if (!(flow_scale > 0.0) || !std::isfinite(flow_scale)) return "flow_scale must be finite and > 0";
+    *L = lv;
+    return nullptr;
 }
 
 }  // namespace b2f

@@ -79,6 +79,14 @@ void flow_score_host(const float *flow, const float *occ_prob, int n, int H, int
 void flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, bool bytes_in, const void *im1,
                     const void *im2, const void *im3, void *warped, unsigned long long *photo);
 
+// The unsupervised validation loss of test.lua:266-297 on the CPU (b2f_tableloss.h per pixel; b2f_table_loss_host): table = L x (4 | 5)
+// planar fp32 tensors in table order (per level f, [p,] o, iw1, iw3 at (H >> j) x (W >> j)), ref n x 3 x H x W, loss n x L x
+// B2F_LOSS_WORDS words
+void table_loss_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                     unsigned long long *loss);
+// the argument checks every table-loss entry shares (test.lua:266-297; no HIP call): nullptr and *L = n_outs / per, or why not
+const char *table_loss_refusal(int n_outs, int per, int n, int H, int W, double flow_scale, int *L);
+
 // .t7 reader (b2f_t7.cpp): returns false and fills err on failure.
 bool load_t7(const std::string &path, std::vector<float> &flat, bool &past_flow, std::string &err);
 // any graph shape: infer = true takes win / levels / skip from the file, false checks the file against g (see b2f_t7.cpp)

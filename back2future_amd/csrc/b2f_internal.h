@@ -357,4 +357,13 @@ hipError_t launch_flow_warp(const float *flow, const float *occ_prob, int n, int
                             const void *im3, size_t image_stride, int in_kind, void *warped, int warped_kind, unsigned long long *photo,
                             hipStream_t s);
 
+// ---- the unsupervised validation loss (b2f_tableloss.hip; the per-pixel functions: b2f_tableloss.h) --------------
+// test.lua:266-297 on the output table: table = L x (4 | 5) device tensors of n images in table order (a host array), ref = R_0 of
+// image 0, image b `ref_stride` samples further (3 H W for n x 3 x H x W, 9 H W for channels 3 .. 5 of the network's input), pyr =
+// table_loss_pyramid_floats(L, n, H, W) floats of workspace for R_1 .. R_{L-1}; loss: n x L x B2F_LOSS_WORDS words, zeroed on s first.
+// n <= 65535, H * W < 2^28, H and W multiples of 2^(L-1)
+size_t table_loss_pyramid_floats(int L, int n, int H, int W);
+hipError_t launch_table_loss(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr,
+                             double flow_scale, unsigned long long *loss, hipStream_t s);
+
 }  // namespace b2f

@@ -1,0 +1,346 @@
+// The unsupervised validation loss of test.lua:266-297 (the -optimize pme branch) on the device: one record of B2F_LOSS_WORDS integers
+// per image and per level of the output table of model:forward.  table_loss_kernel reads the level's flows, occlusions, warped images
+// and reference image once (the right and lower neighbours of the stencil through the cache), evaluates the per-pixel functions of
+// b2f_tableloss.h / b2f_flowwarp.h, which the host entry (b2f_table_loss_host) shares, and reduces them like flow_warp_kernel:
+// counters in registers, a wave reduction, the waves of a block through LDS, then at most one 64-bit atomicAdd per non-zero word per
+// block.  The reference image of level j + 1 comes from a small pooling pass over that of level j (ref_pool_kernel), into a workspace
+// of the context.
+#include "b2f_ctx.h"
+#include "b2f_tableloss.h"
+
+using namespace b2f;
+
+static int fail(const std::string &m) { return api_fail(m); }
+
+namespace b2f {
+
+namespace {
+
+constexpr int kPx = 4;        // consecutive pixels of a row per thread: one 16-byte load per plane and row
+constexpr int kThreads = 256;
+constexpr int kWave = 64;     // gfx950
+constexpr int kWaves = kThreads / kWave;
+constexpr int kWords = B2F_LOSS_WORDS;
+
+// n (1..4) samples of a row at p: one 16-byte load where the address allows -- rows of odd w are not aligned --, scalar loads
+// otherwise; v[n..] is left alone
+__device__ __forceinline__ void load_px(const float *p, int n, float *v)
+{
+    if (n == kPx && ((uintptr_t)p & 15) == 0) {
+        const float4 q = *reinterpret_cast<const float4 *>(p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        return;
+    }
+    for (int k = 0; k < kPx; ++k)
+        if (k < n) v[k] = p[k];
+}
+
+// the planes of one level: image 0; image b lies 2 hw (f, p, o), 3 hw (iw1, iw3) or ref_stride (ref) samples further
+struct LevelPtrs {
+    const float *f, *p, *o, *iw1, *iw3, *ref;
+    size_t ref_stride;
+};
+
+// Image blockIdx.y of one level: its blocks stride over the groups of kPx pixels of its rows.  loss: the record of image 0 at this
+// level, image b lies `rec_stride` words further; zeroed on the stream before.
+template <bool Past>
+__global__ void __launch_bounds__(kThreads) table_loss_kernel(LevelPtrs lp, int h, int w, float kd, unsigned long long *loss, size_t rec_stride)
+{
+    const size_t b = blockIdx.y, hw = (size_t)h * w;
+    constexpr int kPl = 9;   // f0 f1 p0 p1 o0 o1 R0 R1 R2 (b2f_tableloss.h: loss_pixel)
+    const float *pl[kPl];
+    pl[0] = lp.f + b * 2 * hw; pl[1] = pl[0] + hw;
+    pl[2] = Past ? lp.p + b * 2 * hw : nullptr; pl[3] = Past ? pl[2] + hw : nullptr;
+    pl[4] = lp.o + b * 2 * hw; pl[5] = pl[4] + hw;
+    pl[6] = lp.ref + b * lp.ref_stride; pl[7] = pl[6] + hw; pl[8] = pl[7] + hw;
+    const float *iw[2] = {lp.iw1 + b * 3 * hw, lp.iw3 + b * 3 * hw};
+    const size_t gpr = ((size_t)w + kPx - 1) / kPx, groups = gpr * (size_t)h;   // groups per row, per image
+    unsigned pixels = 0, nonfinite = 0, inside[2] = {0, 0}, outside[2] = {0, 0}, pnonf[2] = {0, 0};
+    unsigned long long s_flow = 0, s_past = 0, s_cv = 0, s_occ = 0, s_prior = 0, ocharb[2] = {0, 0};
+    for (size_t gi = (size_t)blockIdx.x * kThreads + threadIdx.x; gi < groups; gi += (size_t)gridDim.x * kThreads) {
+        const int y = (int)(gi / gpr), x0 = (int)(gi % gpr) * kPx;
+        const int n = w - x0 < kPx ? w - x0 : kPx;
+        const size_t i0 = (size_t)y * w + x0;
+        const bool has_y = y + 1 < h, more = x0 + kPx < w;   // a row below; a pixel right of the group
+        // cur[c][0..3] the group, cur[c][4] its right neighbour, low[c] the row below: every index lies in the plane (k < n, more, has_y)
+        float cur[kPl][kPx + 1], low[kPl][kPx];
+#pragma unroll
+        for (int c = 0; c < kPl; ++c) {
+#pragma unroll
+            for (int k = 0; k < kPx; ++k) cur[c][k] = low[c][k] = 0.0f;
+            cur[c][kPx] = 0.0f;
+            if (!Past && (c == 2 || c == 3)) continue;
+            load_px(pl[c] + i0, n, cur[c]);
+            if (more) cur[c][kPx] = pl[c][i0 + kPx];
+            if (has_y) load_px(pl[c] + i0 + w, n, low[c]);
+        }
+        float wv[2][3][kPx];
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                for (int k = 0; k < kPx; ++k) wv[d][c][k] = 0.0f;
+                load_px(iw[d] + (size_t)c * hw + i0, n, wv[d][c]);
+            }
+#pragma unroll
+        for (int k = 0; k < kPx; ++k) {
+            const bool live = k < n;
+            float v[kPl], vx[kPl], vy[kPl];
+#pragma unroll
+            for (int c = 0; c < kPl; ++c) {
+                v[c] = cur[c][k];
+                vx[c] = cur[c][k + 1];
+                vy[c] = low[c][k];
+            }
+            const PixelLoss s = loss_pixel(v, vx, vy, x0 + k + 1 < w, has_y, Past);
+            pixels += live ? 1u : 0u;
+            nonfinite += live ? s.nonfinite : 0u;
+            s_flow += live ? s.smooth_flow : 0ull;
+            s_past += live ? s.smooth_past : 0ull;
+            s_cv += live ? s.const_vel : 0ull;
+            s_occ += live ? s.smooth_occ : 0ull;
+            s_prior += live ? s.prior_occ : 0ull;
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                const bool pf = d == 0 && Past;   // OBCCriterion.lua:80-81
+                // a pixel past the row's end: zero values at the group's first pixel, which is in the image; it is not counted
+                const WarpTaps tp = warp_taps(pf ? v[2] : v[0], pf ? v[3] : v[1], d == 0 ? -kd : kd, live ? x0 + k : x0, y, w, h);
+                const float w3[3] = {wv[d][0][k], wv[d][1][k], wv[d][2][k]}, r3[3] = {v[6], v[7], v[8]};
+                const PixelPhoto ph = photo_pixel(tp, w3, r3, true, d == 0 ? v[5] : v[4]);
+                inside[d] += live ? ph.inside : 0u;
+                outside[d] += live ? ph.outside : 0u;
+                pnonf[d] += live ? ph.nonfinite : 0u;
+                ocharb[d] += live ? ph.ocharb : 0ull;
+            }
+        }
+    }
+    // the record of this thread, then of its wave
+    unsigned long long rec[kWords];
+    rec[B2F_LOSS_PIXELS] = pixels;
+    rec[B2F_LOSS_SMOOTH_FLOW_Q30] = s_flow;
+    rec[B2F_LOSS_SMOOTH_PAST_Q30] = s_past;
+    rec[B2F_LOSS_CONST_VEL_Q30] = s_cv;
+    rec[B2F_LOSS_SMOOTH_OCC_Q30] = s_occ;
+    rec[B2F_LOSS_PRIOR_OCC_Q30] = s_prior;
+    rec[B2F_LOSS_PHOTO_INSIDE] = inside[0];          rec[B2F_LOSS_PHOTO_INSIDE + 1] = inside[1];
+    rec[B2F_LOSS_PHOTO_OUTSIDE] = outside[0];        rec[B2F_LOSS_PHOTO_OUTSIDE + 1] = outside[1];
+    rec[B2F_LOSS_PHOTO_OCHARB_Q30] = ocharb[0];      rec[B2F_LOSS_PHOTO_OCHARB_Q30 + 1] = ocharb[1];
+    rec[B2F_LOSS_PHOTO_NONFINITE] = pnonf[0];        rec[B2F_LOSS_PHOTO_NONFINITE + 1] = pnonf[1];
+    rec[B2F_LOSS_NONFINITE] = nonfinite;
+    rec[kWords - 1] = 0;   // reserved
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+#pragma unroll
+        for (int j = 0; j < kWords - 1; ++j) rec[j] += __shfl_down(rec[j], off, kWave);
+    }
+    __shared__ unsigned long long part[kWaves][kWords];
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < kWords; ++j) part[wave][j] = rec[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < kWords) {
+        unsigned long long sum = 0;
+        for (int wv_ = 0; wv_ < kWaves; ++wv_) sum += part[wv_][threadIdx.x];
+        if (sum) atomicAdd(loss + b * rec_stride + threadIdx.x, sum);
+    }
+}
+
+// R_{j+1} from R_j: the 2 x 2 mean in fp32, (((tl + tr) + bl) + br) / 4 (nn.SpatialAveragePooling(2,2,2,2), test.lua:132,269).  in:
+// image 0's three planes of hi x wi, image b `in_stride` samples further; out: n x 3 x (hi / 2) x (wi / 2); one thread per output
+__global__ void __launch_bounds__(kThreads) ref_pool_kernel(const float *in, size_t in_stride, int hi, int wi, size_t total, float *out)
+{
+    const int ho = hi / 2, wo = wi / 2;
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const int x = (int)(i % wo), y = (int)((i / wo) % ho), c = (int)((i / ((size_t)wo * ho)) % 3);
+    const size_t b = i / ((size_t)wo * ho * 3);
+    const float *q = in + b * in_stride + ((size_t)c * hi + 2 * y) * wi + 2 * x;
+    out[i] = __fdiv_rn(((q[0] + q[1]) + q[wi]) + q[wi + 1], 4.0f);
+}
+
+}  // namespace
+
+size_t table_loss_pyramid_floats(int L, int n, int H, int W)
+{
+    size_t t = 0;
+    for (int j = 1; j < L; ++j) t += (((size_t)n * 3 * (H >> j) * (W >> j)) + 3) & ~(size_t)3;   // every level 16-byte aligned
+    return t;
+}
+
+hipError_t launch_table_loss(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr,
+                             double flow_scale, unsigned long long *loss, hipStream_t s)
+{
+    const int per = past ? 5 : 4;
+    if (n <= 0 || n > 65535 || L < 1 || L > kLossMaxLevels || H <= 0 || W <= 0 || (size_t)H * W >= (size_t)kPhotoMaxPixels || H % (1 << (L - 1)) ||
+        W % (1 << (L - 1)) || !table || !ref || !loss || (L > 1 && !pyr) || ref_stride < (size_t)3 * H * W)
+        return hipErrorInvalidValue;
+    for (int i = 0; i < L * per; ++i)
+        if (!table[i]) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(loss, 0, (size_t)n * L * kWords * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const float *R = ref;
+    size_t R_stride = ref_stride;
+    for (int j = 0; j < L; ++j) {
+        const int h = H >> j, w = W >> j;
+        const size_t hw = (size_t)h * w;
+        if (j > 0) {
+            const size_t total = (size_t)n * 3 * hw;
+            hipLaunchKernelGGL(ref_pool_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, R, R_stride, 2 * h, 2 * w,
+                               total, pyr);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            R = pyr;
+            R_stride = 3 * hw;
+            pyr += (total + 3) & ~(size_t)3;
+        }
+        const float *const *t = table + (size_t)j * per;
+        const LevelPtrs lp = {t[0], past ? t[1] : nullptr, t[per - 3], t[per - 2], t[per - 1], R, R_stride};
+        const size_t groups = (((size_t)w + kPx - 1) / kPx) * (size_t)h, blocks = (groups + kThreads - 1) / kThreads;
+        // a capped grid as for the photometric record: about eight blocks per CU over the whole call, at most 1024 per image (a
+        // full-HD image alone wraps the loop), so that few blocks add to a record
+        const size_t cap = std::min<size_t>(1024, std::max<size_t>(8, 2048 / (size_t)n));
+        const dim3 grid((unsigned)std::min(blocks, cap), (unsigned)n);
+        const float kd = (float)(flow_scale / (double)(1 << j));
+        unsigned long long *rec = loss + (size_t)j * kWords;
+        if (past)
+            hipLaunchKernelGGL(table_loss_kernel<true>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * kWords);
+        else
+            hipLaunchKernelGGL(table_loss_kernel<false>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * kWords);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+int ensure_dev_work(DevWork &dw, size_t bytes)
+{
+    if (bytes > dw.bytes) {
+        if (dw.dev) {
+            HIPCHK(hipDeviceSynchronize());   // an earlier call may still read it, on any stream
+            HIPCHK(hipFree(dw.dev));
+            dw.dev = nullptr; dw.bytes = 0;
+        }
+        HIPCHK(hipMalloc(&dw.dev, bytes));
+        dw.bytes = bytes;
+    }
+    return 0;
+}
+
+}  // namespace b2f
+
+namespace {
+
+struct DevBytes {
+    void *p = nullptr;
+    ~DevBytes() { if (p) (void)hipFree(p); }
+};
+
+// 1 when p is memory the host can read (pageable or page-locked), 0 for device memory
+bool host_memory(const void *p)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return !(a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeArray);
+}
+
+// the checks of test.lua:266-297's entries that need no HIP call; per: tensors per level
+int check_table_loss(const std::string &w, const float *const *table, int n_outs, int per, int n, int H, int W, const float *ref, double flow_scale,
+                     const void *loss, int *L)
+{
+    if (!table || !ref || !loss) return fail(w + ": null argument");
+    const char *why = table_loss_refusal(n_outs, per, n, H, W, flow_scale, L);
+    if (why) return fail(w + ": " + why);
+    for (int i = 0; i < n_outs; ++i)
+        if (!table[i]) return fail(w + ": null tensor in the table");
+    return 0;
+}
+
+// tensors per level of a table of n_outs tensors on this context: its own kind where that divides n_outs, else the other one
+int level_size(const b2f_ctx *c, int n_outs)
+{
+    const int own = c->past_flow ? 5 : 4, other = 9 - own;
+    return (n_outs > 0 && n_outs % own == 0) ? own : (n_outs > 0 && n_outs % other == 0) ? other : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// test.lua:266-297 on the CPU
+int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                        unsigned long long *loss) try
+{
+    int L = 0;
+    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
+    table_loss_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, loss);
+    return 0;
+}
+B2F_CATCH("b2f_table_loss_host")
+
+// test.lua:266-297 on device pointers
+int b2f_table_loss_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                          unsigned long long *dev_loss, void *stream) try
+{
+    const std::string w(__func__);
+    if (!c) return fail(w + ": null context");
+    const int per = level_size(c, n_outs);
+    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
+    int L = 0;
+    CHK(check_table_loss(w, dev_table, n_outs, per, n, H, W, dev_ref, flow_scale, dev_loss, &L));
+    if (n > 65535) return fail(w + ": at most 65535 images per call");
+    uintptr_t bits = (uintptr_t)dev_ref | (uintptr_t)dev_loss;
+    for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i];
+    if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
+    HIPCHK(hipSetDevice(c->device));
+    if (host_memory(dev_ref) || host_memory(dev_loss)) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss / b2f_table_loss_host)");
+    for (int i = 0; i < n_outs; ++i)
+        if (host_memory(dev_table[i])) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss / b2f_table_loss_host)");
+    CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    ProfEvent pe;
+    const bool timed = prof_open(c, s, "table_loss", &pe);
+    const hipError_t e = launch_table_loss(dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, (float *)c->loss_pyr.dev, flow_scale, dev_loss, s);
+    if (timed) prof_close(c, s, pe);
+    HIPCHK(e);
+    return 0;
+}
+B2F_CATCH("b2f_table_loss_device")
+
+// test.lua:266-297 on host pointers through the GPU
+int b2f_op_table_loss(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                      unsigned long long *loss) try
+{
+    const std::string w(__func__);
+    if (!c) return fail(w + ": null context");
+    const int per = level_size(c, n_outs);
+    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
+    int L = 0;
+    CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, loss, &L));
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<DevBytes> dt((size_t)n_outs);
+    std::vector<const float *> ptrs((size_t)n_outs);
+    DevBytes dr, dl;
+    auto up = [&](DevBytes &d, const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(&d.p, bytes);
+        return e != hipSuccess ? e : hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice);
+    };
+    for (int i = 0; i < n_outs; ++i) {
+        const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
+        HIPCHK(up(dt[(size_t)i], table[i], (size_t)n * ch * (H >> j) * (W >> j) * sizeof(float)));
+        ptrs[(size_t)i] = (const float *)dt[(size_t)i].p;
+    }
+    HIPCHK(up(dr, ref, (size_t)n * 3 * H * W * sizeof(float)));
+    const size_t nl = (size_t)n * L * B2F_LOSS_WORDS * sizeof(unsigned long long);
+    HIPCHK(hipMalloc(&dl.p, nl));
+    CHK(b2f_table_loss_device(c, ptrs.data(), n_outs, n, H, W, (const float *)dr.p, flow_scale, (unsigned long long *)dl.p, nullptr));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(loss, dl.p, nl, hipMemcpyDeviceToHost));
+    return 0;
+}
+B2F_CATCH("b2f_op_table_loss")
+
+}  // extern "C"

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""The unsupervised validation loss of a clip on the GPU: for every centre frame (a frame with a neighbour on both sides) the
+objective the reference validates a model trained without labels with -- the -optimize pme branch of test.lua:266-297: flow
+smoothness, constant velocity, the occlusion-aware photometric error of the model's own warped images, occlusion smoothness and
+the occlusion prior, on every level of the output table.  No ground truth is needed.  The table stays on the GPU
+(Model.forwardLoss); 128 bytes per level and centre frame come back.
+
+Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average]
+FRAMES_DIR: 8-bit frames, sorted by name; they are cropped (top left) to multiples of 64 and normalized with
+back2future.normalize.  MODEL as for examples/run_sequence.py.  --scale: pixels per unit of raw network flow (default 20).
+Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`.
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from back2future_amd import back2future   # noqa: E402
+
+EXTS = (".png", ".jpg", ".jpeg", ".ppm", ".bmp")
+BATCH = 8   # triplets per forwardLoss call
+
+
+def load_unit(path, H, W):
+    from PIL import Image
+    a = np.asarray(Image.open(path).convert("RGB"), np.uint8)[:H, :W]
+    return np.ascontiguousarray(a.transpose(2, 0, 1)).astype(np.float32) / np.float32(255)
+
+
+def main():
+    args = list(sys.argv[1:])
+    scale, like = 20.0, "test"
+    size_average = "--size-average" in args
+    args = [a for a in args if a != "--size-average"]
+    for flag in ("--scale", "--like"):
+        if flag in args:
+            i = args.index(flag)
+            try:
+                if flag == "--scale":
+                    scale = float(args[i + 1])
+                else:
+                    like = args[i + 1]
+            except (IndexError, ValueError):
+                sys.exit(flag + ": bad value")
+            del args[i:i + 2]
+    if len(args) != 2 or like not in ("test", "train"):
+        sys.exit(__doc__)
+    src, model = args
+    names = sorted(f for f in os.listdir(src) if f.lower().endswith(EXTS))
+    if len(names) < 3:
+        sys.exit("%s: need at least 3 frames, found %d" % (src, len(names)))
+    from PIL import Image
+    W0, H0 = Image.open(os.path.join(src, names[0])).size
+    H, W = H0 // 64 * 64, W0 // 64 * 64
+    if H < 64 or W < 64:
+        sys.exit("%s: frames of %d x %d are smaller than 64 x 64" % (src, H0, W0))
+    frames = [back2future.normalize(load_unit(os.path.join(src, f), H, W)) for f in names]
+    m = back2future.Model(model)
+    records = []
+    for b0 in range(0, len(frames) - 2, BATCH):
+        x = np.stack([np.concatenate(frames[i:i + 3], axis=0) for i in range(b0, min(b0 + BATCH, len(frames) - 2))])
+        records.append(m.forwardLoss(x, flow_scale=scale))
+    m.close()
+    s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average)
+    for f, v in zip(names[1:-1], s["loss"]):
+        print("%s %r" % (os.path.splitext(f)[0], float(v)))
+    print("mean %r" % s["mean"])
+    print("nonfinite %d" % s["nonfinite"])
+
+
+if __name__ == "__main__":
+    main()

@@ -427,6 +427,74 @@ B2F_API int b2f_multi_compute_flow_batch_warp(b2f_multi *m, int n, int in_kind, 
 B2F_API int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
                                          double flow_scale, void *warped, unsigned long long *photo, float *flow,
                                          float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* ---- the unsupervised validation loss: the -optimize pme branch of test.lua:266-297 on the output table ----
+ * What the reference validates a model trained without labels with: on every level j = 0 .. L-1 of the output table of model:forward
+ * (pwc.lua:459-489; level size h = H >> j, w = W >> j) the contrast-sensitive smoothness of the flows
+ * (criterions/SmoothnessCriterion.lua:45-63), the constant-velocity term (criterions/ConstVelCriterion.lua:36-38), the occlusion-aware
+ * photometric error of the table's own warped images (criterions/OBCCriterion.lua:79-100), the smoothness of the occlusions
+ * (os_criterion, model.lua:216) and the occlusion prior (criterions/OcclusionPriorCriterion.lua:39).  Inputs per level, planar fp32:
+ * f the future flow (2 channels), p the past flow (2, Soft tables only), o the occlusions (2), iw1 / iw3 the warped images (3 each),
+ * R_j the reference image (3): R_0 = the normalized centre frame, R_j = the 2 x 2 mean of R_{j-1} in fp32,
+ * (((tl + tr) + bl) + br) / 4 (nn.SpatialAveragePooling(2,2,2,2), test.lua:132,269).  All per-pixel arithmetic is fp64 without fused
+ * multiply-adds (the warp coordinate fp32):
+ *   dx(F,c) = (double)F[c][y][x+1] - (double)F[c][y][x] if x + 1 < w, else 0; dy the same over rows
+ *   wx = E(-20 * ((|dx(R,0)| + |dx(R,1)|) + |dx(R,2)|) / 3.0), wy the same with dy (SmoothnessCriterion.lua:58-59, cs = 20)
+ *   E(t), t <= 0: the library's own exponential -- t > 0 counts as 0, t < -708 gives 0, NaN stays NaN;
+ *        k = nearbyint(t * 1.44269504088896338700e+00), r = (t - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10,
+ *        p = c13, p = p * r + c_i for i = 12 .. 0 with c_0 = 1, c_i = c_{i-1} / i; E = ldexp(p, k)
+ *   P1(v) = sqrt(v * v + 1e-6) (L1_function.lua:20), P2(v) = v * v
+ *   s_flow = (P1(dx(f,0)) * wx + P1(dy(f,0)) * wy) + (P1(dx(f,1)) * wx + P1(dy(f,1)) * wy); s_past the same on p; s_occ the same with
+ *            P2 on o; cv = sqrt(d0 * d0 + d1 * d1), d_c = (double)f[c] - (double)p[c]; prior = 1.0 - (double)o[0] * (double)o[1]
+ * Each term adds q(term) to its word, q(t) = (unsigned long long)(min(max(t, 0), 16) * 2^30 + 0.5); a NaN term adds nothing and its
+ * pixel counts once in NONFINITE.  Photo words, direction d = 0 the past frame iw1, d = 1 the future frame iw3: the pixel's target is
+ * that of b2f_flow_warp with k_0 = -(float)(flow_scale / 2^j), k_1 = +(float)(flow_scale / 2^j) (pwc.lua:450-455, train.lua:425) on the
+ * past flow for d = 0 of a Soft table (OBCCriterion.lua:80-81) and on the future flow otherwise; INSIDE / OUTSIDE / OCHARB_Q30 /
+ * PHOTO_NONFINITE are the B2F_PHOTO_* words of that pixel with the warped value iw_d, the reference R_j and the weight o[1] (d = 0) or
+ * o[0] (d = 1).
+ * loss: n x L records of B2F_LOSS_WORDS unsigned 64-bit words (128 bytes), image-major.  The sums are integers, so a record is the same
+ * words on the host and on the device, wherever a request is cut.  Images of 2^28 pixels or more are refused; L is 1 .. 7; H and W
+ * are multiples of 2^(L-1).                                                                                                     */
+enum {
+    B2F_LOSS_PIXELS = 0,            /* h * w */
+    B2F_LOSS_SMOOTH_FLOW_Q30 = 1,   /* flow smoothness of the future flow, 2^-30 */
+    B2F_LOSS_SMOOTH_PAST_Q30 = 2,   /* flow smoothness of the past flow (0 for Hard) */
+    B2F_LOSS_CONST_VEL_Q30 = 3,     /* constant-velocity term (0 for Hard) */
+    B2F_LOSS_SMOOTH_OCC_Q30 = 4,    /* occlusion smoothness */
+    B2F_LOSS_PRIOR_OCC_Q30 = 5,     /* occlusion prior */
+    B2F_LOSS_PHOTO_INSIDE = 6,      /* [2] finite pixels whose target lies in the image, past / future */
+    B2F_LOSS_PHOTO_OUTSIDE = 8,     /* [2] finite pixels whose target leaves it */
+    B2F_LOSS_PHOTO_OCHARB_Q30 = 10, /* [2] occlusion-weighted Charbonnier error */
+    B2F_LOSS_PHOTO_NONFINITE = 12,  /* [2] non-finite photo pixels */
+    B2F_LOSS_NONFINITE = 14,        /* pixels with a NaN smoothness, velocity or prior term */
+    B2F_LOSS_WORDS = 16             /* word 15 is reserved, always 0 */
+};
+/* host only, no GPU: test.lua:266-297 per pixel on the CPU.  table: n_outs = L * (4 + past_flow) pointers in table order (per level
+ * f, [p,] o, iw1, iw3; shapes as b2f_output_shapes gives them); ref: n x 3 x H x W; loss: n x L x 16 words.                     */
+B2F_API int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                        double flow_scale, unsigned long long *loss);
+/* test.lua:266-297 on device pointers: dev_table is a host array of n_outs device pointers (16-byte aligned, as dev_ref and
+ * dev_loss); n_outs = 4 L (Hard) or 5 L (Soft), past_flow is taken from it with the context's kind (20 = 4 x 5 = 5 x 4 is read as
+ * the context's).  Asynchronous on `stream` like b2f_flow_warp_device; dev_loss (n x L x 16 words) is zeroed on the stream first.
+ * The pyramid of R lives in a workspace of the context: calls on different streams must be ordered by the caller.  At most 65535
+ * images per call.                                                                                                              */
+B2F_API int b2f_table_loss_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                          double flow_scale, unsigned long long *dev_loss, void *stream);
+/* test.lua:266-297 on host pointers through the GPU, like b2f_op_flow_warp */
+B2F_API int b2f_op_table_loss(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                      double flow_scale, unsigned long long *loss);
+/* model:forward followed by test.lua:266-297 without the download of the table: x is n x 9 x H x W normalized host memory (H, W as
+ * for b2f_forward), ref is its channels 3 .. 5; loss: n x L x 16 words with L = b2f_info's n_outputs / (4 | 5).  outs = NULL with
+ * n_outs = 0: the table stays on the device and the call returns n x L x 128 bytes; otherwise outs receives the table, bit for bit
+ * that of b2f_forward.  Requests are cut into sub-batches of the host_subbatch_pixels budget; the table lives in a workspace of the
+ * context.  A context made with b2f_init_ex options is served wherever its table has occlusions; two_frame is refused.         */
+B2F_API int b2f_forward_loss(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                     float **outs, int n_outs);
+/* test.lua:266-297 behind model:forward on device pointers: dev_in n x 9 x H x W, in_kind B2F_IN_NORMALIZED only; dev_loss
+ * n x L x 16 words; asynchronous on `stream` like b2f_forward_device.                                                           */
+B2F_API int b2f_forward_loss_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                            unsigned long long *dev_loss, void *stream);
+/* test.lua:266-297 over several GPUs: the n triplets are split with b2f_shard_range; one context's words */
+B2F_API int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature

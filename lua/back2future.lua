@@ -108,6 +108,17 @@ int b2f_compute_flow_batch_warp(b2f_ctx *ctx, int n, int in_kind, const void *im
 int b2f_compute_flow_sequence_warp(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
                                    double flow_scale, void *warped, unsigned long long *photo, float *flow,
                                    float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* the unsupervised validation loss of test.lua:266-297 on the output table (include/b2f.h, B2F_LOSS_*) */
+int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                        double flow_scale, unsigned long long *loss);
+int b2f_table_loss_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                          double flow_scale, unsigned long long *dev_loss, void *stream);
+int b2f_op_table_loss(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                      double flow_scale, unsigned long long *loss);
+int b2f_forward_loss(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                     float **outs, int n_outs);
+int b2f_forward_loss_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                            unsigned long long *dev_loss, void *stream);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -137,6 +148,7 @@ int b2f_multi_compute_flow_batch_warp(b2f_multi *m, int n, int in_kind, const vo
 int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
                                          double flow_scale, void *warped, unsigned long long *photo, float *flow,
                                          float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
 ]]
 
 local lib = ffi.load(os.getenv('B2F_LIB') or 'libb2f.so')
