@@ -123,6 +123,40 @@ SIGNATURES = {
     "b2f_multi_compute_flow_sequence_warp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
                                                        C.c_void_p, C.POINTER(C.c_ulonglong), c_float_p, c_float_p, C.POINTER(C.c_ubyte),
                                                        C.POINTER(C.c_ubyte)]),
+    "b2f_forward_device_past": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "b2f_forward_sequence_device_past": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "b2f_compute_flow_batch_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                              c_float_p, c_float_p, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "b2f_compute_flow_sequence_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                 c_float_p, c_float_p, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "b2f_multi_compute_flow_batch_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.c_int, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "b2f_multi_compute_flow_sequence_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                       c_float_p, c_float_p, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "b2f_compute_flow_device_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "b2f_compute_flow_sequence_device_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "b2f_flow_warp_past_host": (C.c_int, [c_float_p, c_float_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "b2f_flow_warp_past_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "b2f_op_flow_warp_past": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "b2f_compute_flow_batch_warp_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                   C.c_double, C.c_void_p, C.POINTER(C.c_ulonglong), c_float_p, c_float_p, c_float_p,
+                                                   C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "b2f_compute_flow_sequence_warp_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                      C.c_void_p, C.POINTER(C.c_ulonglong), c_float_p, c_float_p, c_float_p,
+                                                      C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "b2f_multi_compute_flow_batch_warp_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                         C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_ulonglong), c_float_p, c_float_p,
+                                                         c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "b2f_multi_compute_flow_sequence_warp_past": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                            C.c_void_p, C.POINTER(C.c_ulonglong), c_float_p, c_float_p, c_float_p,
+                                                            C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
     "b2f_table_loss_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
                                       C.POINTER(C.c_ulonglong)]),
     "b2f_table_loss_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,

@@ -167,6 +167,52 @@ def _compute_flow_sequence(prefix, h, frames, out, dtype, occ_prob):
     return _call_f64(prefix + "compute_flow_sequence", h, T, as_bytes, (v,), H0, W0, _f64_outputs(T - 2, H0, W0, out))
 
 
+def _past_outputs(n, H0, W0, occ_prob, out, who):
+    """(flow, past_flow, fwd, bwd, occ_prob or None) for the _past entries.  out = (flow, past_flow float32 n x 2 x H x W, fwd uint8
+    n x 1 x H x W, bwd[, occ_prob]); fwd / bwd may be None (the masks are then not computed)."""
+    if out is None:
+        flow, fwd, bwd, occ = _f32_outputs(n, H0, W0, occ_prob, None, who)
+        return flow, np.empty((n, 2, H0, W0), np.float32), fwd, bwd, occ
+    out = tuple(out)
+    if len(out) != (5 if occ_prob else 4):
+        raise ValueError("%s: out must be (flow, past_flow, fwd_occ, bwd_occ%s)" % (who, ", occ_prob" if occ_prob else ""))
+    past = out[1]
+    if not isinstance(past, np.ndarray) or past.dtype != np.float32 or past.shape != (n, 2, H0, W0) or not past.flags.c_contiguous or \
+            not past.flags.writeable:
+        raise ValueError("%s: out[1] must be a writeable C-contiguous float32 array of shape %s" % (who, (n, 2, H0, W0)))
+    flow, fwd, bwd, occ = _f32_outputs(n, H0, W0, occ_prob, out[:1] + out[2:], who)
+    return flow, past, fwd, bwd, occ
+
+
+def _call_past(fn, h, count, in_kind, ins, H0, W0, outs, occ_prob):
+    flow, past, fwd, bwd, occ = outs
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+    _lib.check(getattr(_lib.lib(), fn)(h, count, in_kind, *[C.c_void_p(a.ctypes.data) for a in ins], H0, W0, _lib.fptr(flow), _lib.fptr(past),
+                                       _lib.fptr(occ) if occ is not None else None, u8p(fwd), u8p(bwd)))
+    return (flow, past, fwd, bwd) + ((occ,) if occ_prob else ())
+
+
+def _compute_flow_batch_past(prefix, h, im1, im2, im3, out, occ_prob):
+    """computeFlowBatchPast of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    who = "computeFlowBatchPast"
+    arrs = [np.asarray(a) for a in (im1, im2, im3)]
+    if any(a.ndim != 4 or a.shape[1] != 3 or a.shape[0] < 1 for a in arrs) or len({a.shape for a in arrs}) > 1:
+        raise ValueError("%s: expected three n x 3 x H x W arrays of one shape" % who)
+    im1, im2, im3, as_bytes = _batch_inputs(*arrs)
+    n, _, H0, W0 = im1.shape
+    return _call_past(prefix + "compute_flow_batch_past", h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0,
+                      _past_outputs(n, H0, W0, occ_prob, out, who), occ_prob)
+
+
+def _compute_flow_sequence_past(prefix, h, frames, out, occ_prob):
+    """computeFlowSequencePast of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
+    who = "computeFlowSequencePast"
+    v, as_bytes = sequence_frames(frames)
+    T, _, H0, W0 = v.shape
+    return _call_past(prefix + "compute_flow_sequence_past", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0,
+                      _past_outputs(T - 2, H0, W0, occ_prob, out, who), occ_prob)
+
+
 def rgb_max_norm(max, who):
     """The `max=` keyword of the flow-picture wrappers as the library's max_norm: None (each picture's own maximum) -> 0, else a
     positive number (flowX.xy2rgb's third argument).  Raises ValueError before any library call."""
@@ -444,16 +490,18 @@ def score_summary(scores):
             "pixels": sum(pix), "nonfinite": t[SCORE_NONFINITE]}
 
 
-def _warp_outputs(n, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who):
-    """[warped, photo, flow, fwd, bwd, occ_prob] (None: not asked for) for the warp entries; out = the buffers the call returns, in the
-    order (warped, photo[, flow][, fwd_occ, bwd_occ][, occ_prob]) without what is not asked for, or new arrays."""
+def _warp_outputs(n, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who, want_past=False):
+    """[warped, photo, flow, fwd, bwd, occ_prob, past_flow] (None: not asked for) for the warp entries; out = the buffers the call
+    returns, in the order (warped, photo[, flow][, fwd_occ, bwd_occ][, occ_prob][, past_flow]) without what is not asked for, or new
+    arrays."""
     if not want_warped and not want_photo:
         raise ValueError("%s: at least one of want_warped and want_photo" % who)
     spec = [(np.uint8 if as_bytes else np.float32, (n, 2, 3, H0, W0)) if want_warped else None,
             (np.uint64, (n, PHOTO_WORDS)) if want_photo else None,
             (np.float32, (n, 2, H0, W0)) if want_flow else None,
             (np.uint8, (n, 1, H0, W0)) if want_masks else None, (np.uint8, (n, 1, H0, W0)) if want_masks else None,
-            (np.float32, (n, 2, H0, W0)) if want_prob else None]
+            (np.float32, (n, 2, H0, W0)) if want_prob else None,
+            (np.float32, (n, 2, H0, W0)) if want_past else None]
     asked = [s for s in spec if s is not None]
     if out is None:
         bufs = [np.empty(shape, dt) for dt, shape in asked]
@@ -468,37 +516,50 @@ def _warp_outputs(n, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_
     return [next(it) if s is not None else None for s in spec]
 
 
-def _call_warp(fn, h, count, in_kind, ins, H0, W0, flow_scale, outs):
-    warped, photo, flow, fwd, bwd, prob = outs
+def _own_past(own_past_flow, want_past, who):
+    """the own_past_flow / want_past keywords of the warp wrappers: the past flow is an output of the own-past-flow entries only"""
+    if want_past and not own_past_flow:
+        raise ValueError("%s: want_past needs own_past_flow=True" % who)
+    return bool(own_past_flow)
+
+
+def _call_warp(fn, h, count, in_kind, ins, H0, W0, flow_scale, outs, own_past=False):
+    """fn, or with own_past fn + "_past" (the past frame follows the model's own past flow; its argument list has past_flow after flow)"""
+    warped, photo, flow, fwd, bwd, prob, past = outs
     u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
-    _lib.check(getattr(_lib.lib(), fn)(h, count, in_kind, *[C.c_void_p(a.ctypes.data) for a in ins], H0, W0, float(flow_scale),
-                                       C.c_void_p(warped.ctypes.data) if warped is not None else None,
-                                       photo.ctypes.data_as(C.POINTER(C.c_ulonglong)) if photo is not None else None,
-                                       _lib.fptr(flow) if flow is not None else None, _lib.fptr(prob) if prob is not None else None,
-                                       u8p(fwd), u8p(bwd)))
+    fp = lambda a: _lib.fptr(a) if a is not None else None
+    _lib.check(getattr(_lib.lib(), fn + ("_past" if own_past else ""))(
+        h, count, in_kind, *[C.c_void_p(a.ctypes.data) for a in ins], H0, W0, float(flow_scale),
+        C.c_void_p(warped.ctypes.data) if warped is not None else None,
+        photo.ctypes.data_as(C.POINTER(C.c_ulonglong)) if photo is not None else None,
+        *((fp(flow), fp(past), fp(prob)) if own_past else (fp(flow), fp(prob))), u8p(fwd), u8p(bwd)))
     res = tuple(a for a in outs if a is not None)
     return res[0] if len(res) == 1 else res
 
 
-def _compute_flow_batch_warp(prefix, h, im1, im2, im3, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob):
+def _compute_flow_batch_warp(prefix, h, im1, im2, im3, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob,
+                             own_past_flow=False, want_past=False):
     """computeFlowBatchWarp of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
     who = "computeFlowBatchWarp"
+    own = _own_past(own_past_flow, want_past, who)
     arrs = [np.asarray(a) for a in (im1, im2, im3)]
     if any(a.ndim != 4 or a.shape[1] != 3 or a.shape[0] < 1 for a in arrs) or len({a.shape for a in arrs}) > 1:
         raise ValueError("%s: expected three n x 3 x H x W arrays of one shape" % who)
     im1, im2, im3, as_bytes = _batch_inputs(*arrs)
     n, _, H0, W0 = im1.shape
-    outs = _warp_outputs(n, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who)
-    return _call_warp(prefix + "compute_flow_batch_warp", h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0, flow_scale, outs)
+    outs = _warp_outputs(n, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who, want_past)
+    return _call_warp(prefix + "compute_flow_batch_warp", h, n, IN_U8 if as_bytes else IN_UNIT, (im1, im2, im3), H0, W0, flow_scale, outs, own)
 
 
-def _compute_flow_sequence_warp(prefix, h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob):
+def _compute_flow_sequence_warp(prefix, h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob,
+                                own_past_flow=False, want_past=False):
     """computeFlowSequenceWarp of Model (prefix "b2f_") and MultiModel ("b2f_multi_")."""
     who = "computeFlowSequenceWarp"
+    own = _own_past(own_past_flow, want_past, who)
     v, as_bytes = sequence_frames(frames)
     T, _, H0, W0 = v.shape
-    outs = _warp_outputs(T - 2, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who)
-    return _call_warp(prefix + "compute_flow_sequence_warp", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0, flow_scale, outs)
+    outs = _warp_outputs(T - 2, H0, W0, as_bytes, want_warped, want_photo, want_flow, want_masks, want_prob, out, who, want_past)
+    return _call_warp(prefix + "compute_flow_sequence_warp", h, T, IN_U8 if as_bytes else IN_UNIT, (v,), H0, W0, flow_scale, outs, own)
 
 
 def photo_summary(photo):
@@ -746,6 +807,37 @@ class Model(object):
         _lib.check(_lib.lib().b2f_compute_flow_sequence_device(self._h, int(T), int(in_kind), p(d_frames), int(H0), int(W0), p(d_flow),
                                                                 p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream)))
 
+    def computeFlowBatchPast(self, im1, im2, im3, out=None, occ_prob=False):
+        """computeFlowBatch(dtype=np.float32) of a Soft model with its past flow (b2f_compute_flow_batch_past): returns (flow,
+        past_flow, fwd_occ, bwd_occ[, occ_prob]).  past_flow is the network's skip_ubfs[3] (models/pwc.lua:328-385), float32
+        n x 2 x H x W, a raw flow rescaled like flow: the past frame is sampled at x - past_flow * 20, and under constant velocity
+        past_flow == flow.  The other outputs are computeFlowBatch(dtype=np.float32)'s, bit for bit.  out = those buffers (its masks
+        may be None).  A Hard model has no past flow and is refused."""
+        return _compute_flow_batch_past("b2f_", self._h, im1, im2, im3, out, occ_prob)
+
+    def computeFlowSequencePast(self, frames, out=None, occ_prob=False):
+        """computeFlowSequence(dtype=np.float32) of a Soft model with its past flow (b2f_compute_flow_sequence_past): (flow, past_flow,
+        fwd_occ, bwd_occ[, occ_prob]) with n = T - 2; output i belongs to centre frame i + 1, whose past frame is frame i."""
+        return _compute_flow_sequence_past("b2f_", self._h, frames, out, occ_prob)
+
+    def computeFlowDevicePast(self, d_im1, d_im2, d_im3, n, H0, W0, d_flow, d_past_flow, d_occ_prob=None, d_fwd_occ=None, d_bwd_occ=None,
+                              in_kind=IN_UNIT, stream=None):
+        """b2f_compute_flow_device_past on device pointers (ints): computeFlowDevice with the past flow of a Soft model in d_past_flow
+        (n x 2 x H0 x W0 float32).  Asynchronous on `stream`."""
+        p = lambda v: C.c_void_p(v) if v else None
+        _lib.check(_lib.lib().b2f_compute_flow_device_past(self._h, int(n), int(in_kind), p(d_im1), p(d_im2), p(d_im3), int(H0), int(W0),
+                                                            p(d_flow), p(d_past_flow), p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream)))
+
+    def computeFlowSequenceDevicePast(self, d_frames, T, H0, W0, d_flow, d_past_flow, d_occ_prob=None, d_fwd_occ=None, d_bwd_occ=None,
+                                      in_kind=IN_UNIT, stream=None):
+        """b2f_compute_flow_sequence_device_past on device pointers (ints): computeFlowSequenceDevice with the past flow of a Soft
+        model in d_past_flow ((T - 2) x 2 x H0 x W0 float32).  Asynchronous on `stream`."""
+        if T < 3:
+            raise ValueError("computeFlowSequenceDevicePast: a sequence needs T >= 3 frames, got %d" % T)
+        p = lambda v: C.c_void_p(v) if v else None
+        _lib.check(_lib.lib().b2f_compute_flow_sequence_device_past(self._h, int(T), int(in_kind), p(d_frames), int(H0), int(W0), p(d_flow),
+                                                                     p(d_past_flow), p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream)))
+
     def openStream(self, H0, W0, cams=1, dtype=np.uint8):
         """A FlowStream of `cams` cameras delivering H0 x W0 frames of `dtype` (np.uint8 or np.float32 in [0,1]) one at a time."""
         if not getattr(self, "_h", None):
@@ -805,31 +897,45 @@ class Model(object):
                                                      p(d_valid), p(d_gt_occ), p(d_scores), p(stream)))
 
     def computeFlowBatchWarp(self, im1, im2, im3, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False,
-                             out=None, want_prob=False):
+                             out=None, want_prob=False, own_past_flow=False, want_past=False):
         """computeFlowBatch with motion compensation on the GPU (b2f_compute_flow_batch_warp; models/pwc.lua:67-73,
         criterions/OBCCriterion.lua:79-100): returns (warped, photo[, flow][, fwd_occ, bwd_occ][, occ_prob]) without what is not asked
         for (a single array alone); what is not asked for is not downloaded.  warped: n x 2 x 3 x H x W in the frames' dtype, [:, 0]
         im1 (the past frame) and [:, 1] im3 (the future frame) sampled where the flow says the reference pixels came from / go to --
         not normalized, bytes rounded as image.save does; photo: uint64 n x 14 photometric records (photo_summary turns them into pme,
         PSNR and the inside shares); flow_scale: pixels per unit of raw flow (20 for the shipped models).  The outputs are
-        ops.flow_warp of the float32 flow and occ_prob of computeFlowBatch(dtype=np.float32, occ_prob=True)."""
-        return _compute_flow_batch_warp("b2f_", self._h, im1, im2, im3, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob)
+        ops.flow_warp of the float32 flow and occ_prob of computeFlowBatch(dtype=np.float32, occ_prob=True).
+        own_past_flow=True (Soft models; b2f_compute_flow_batch_warp_past): the past frame is sampled with the model's own past flow
+        instead of minus the future flow -- the reference's warped_img_1 and the past half of its pme (pwc.lua:425-432,
+        OBCCriterion.lua:80-81) --, i.e. ops.flow_warp(..., past_flow=) of computeFlowBatchPast's outputs; want_past=True then appends
+        that past flow to the returned tuple."""
+        return _compute_flow_batch_warp("b2f_", self._h, im1, im2, im3, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob,
+                                        own_past_flow, want_past)
 
     def computeFlowSequenceWarp(self, frames, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False, out=None,
-                                want_prob=False):
+                                want_prob=False, own_past_flow=False, want_past=False):
         """computeFlowSequence with motion compensation (b2f_compute_flow_sequence_warp): output i belongs to centre frame i + 1, whose
         neighbours are frames i and i + 2; keywords and results as for computeFlowBatchWarp with n = T - 2."""
-        return _compute_flow_sequence_warp("b2f_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob)
+        return _compute_flow_sequence_warp("b2f_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out, want_prob,
+                                           own_past_flow, want_past)
 
     def flowWarpDevice(self, d_flow, n, H, W, d_im1, d_im2, d_im3, d_warped=None, d_photo=None, d_occ_prob=None, flow_scale=20.0, as_bytes=False,
-                       stream=None):
+                       stream=None, own_past_flow=False, d_past_flow=None):
         """b2f_flow_warp_device on device pointers (ints): the warped neighbours (n x 2 x 3 x H x W in d_warped, bytes with as_bytes,
         float32 otherwise, like the frames d_im1 / d_im2 / d_im3, n x 3 x H x W each) and / or the photometric records (n x 14 uint64
         in d_photo) of an n x 2 x H x W float32 flow and, optionally, d_occ_prob.  Asynchronous on `stream`: after computeFlowDevice
-        on the same stream it needs no synchronisation in between."""
+        on the same stream it needs no synchronisation in between.  own_past_flow=True (b2f_flow_warp_past_device): the past frame
+        follows d_past_flow (n x 2 x H x W float32, e.g. computeFlowDevicePast's) instead of d_flow."""
         if n < 1 or H < 1 or W < 1:
             raise ValueError("flowWarpDevice: bad shape %r" % ((n, H, W),))
+        if bool(own_past_flow) != bool(d_past_flow):
+            raise ValueError("flowWarpDevice: own_past_flow=True and d_past_flow go together")
         p = lambda v: C.c_void_p(v) if v else None
+        if own_past_flow:
+            _lib.check(_lib.lib().b2f_flow_warp_past_device(self._h, p(d_flow), p(d_past_flow), p(d_occ_prob), int(n), int(H), int(W),
+                                                             float(flow_scale), IN_U8 if as_bytes else IN_UNIT, p(d_im1), p(d_im2), p(d_im3),
+                                                             p(d_warped), p(d_photo), p(stream)))
+            return
         _lib.check(_lib.lib().b2f_flow_warp_device(self._h, p(d_flow), p(d_occ_prob), int(n), int(H), int(W), float(flow_scale),
                                                     IN_U8 if as_bytes else IN_UNIT, p(d_im1), p(d_im2), p(d_im3), p(d_warped), p(d_photo), p(stream)))
 
@@ -874,18 +980,32 @@ class Model(object):
         _lib.check(_lib.lib().b2f_table_loss_device(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale),
                                                      C.c_void_p(d_loss), C.c_void_p(stream) if stream else None))
 
-    def forward_device(self, d_in, B, H, W, d_flow=None, d_occ=None, d_est3=None, unit_input=False, stream=None):
-        """model:forward on device pointers (ints); asynchronous on `stream`."""
+    def forward_device(self, d_in, B, H, W, d_flow=None, d_occ=None, d_est3=None, unit_input=False, stream=None, d_past_flow=None):
+        """model:forward on device pointers (ints); asynchronous on `stream`.  d_past_flow (B x 2 x H x W float32, Soft models;
+        b2f_forward_device_past): the network's past flow skip_ubfs[3]; the pruned pass then runs the past-flow decoders too."""
+        if d_past_flow:
+            _lib.check(_lib.lib().b2f_forward_device_past(
+                self._h, C.c_void_p(d_in), 1 if unit_input else 0, B, H, W,
+                C.c_void_p(d_flow) if d_flow else None, C.c_void_p(d_past_flow), C.c_void_p(d_occ) if d_occ else None,
+                C.c_void_p(d_est3) if d_est3 else None, C.c_void_p(stream) if stream else None))
+            return
         _lib.check(_lib.lib().b2f_forward_device(
             self._h, C.c_void_p(d_in), 1 if unit_input else 0, B, H, W,
             C.c_void_p(d_flow) if d_flow else None, C.c_void_p(d_occ) if d_occ else None,
             C.c_void_p(d_est3) if d_est3 else None, C.c_void_p(stream) if stream else None))
 
-    def forward_sequence_device(self, d_frames, T, H, W, d_flow=None, d_occ=None, d_est3=None, in_kind=IN_NORMALIZED, stream=None):
+    def forward_sequence_device(self, d_frames, T, H, W, d_flow=None, d_occ=None, d_est3=None, in_kind=IN_NORMALIZED, stream=None,
+                                d_past_flow=None):
         """b2f_forward_sequence_device on device pointers (ints): d_frames is T x 3 x H x W (float32, or uint8 with
         in_kind=IN_U8); outputs (T-2) x 2|2|C3 x H x W, output i that of the triplet (i, i+1, i+2).  Asynchronous on `stream`."""
         if T < 3:
             raise ValueError("forward_sequence_device: a sequence needs T >= 3 frames, got %d" % T)
+        if d_past_flow:   # b2f_forward_sequence_device_past: (T-2) x 2 x H x W, the past flow of every triplet (Soft models)
+            _lib.check(_lib.lib().b2f_forward_sequence_device_past(
+                self._h, C.c_void_p(d_frames), int(in_kind), T, H, W,
+                C.c_void_p(d_flow) if d_flow else None, C.c_void_p(d_past_flow), C.c_void_p(d_occ) if d_occ else None,
+                C.c_void_p(d_est3) if d_est3 else None, C.c_void_p(stream) if stream else None))
+            return
         _lib.check(_lib.lib().b2f_forward_sequence_device(
             self._h, C.c_void_p(d_frames), int(in_kind), T, H, W,
             C.c_void_p(d_flow) if d_flow else None, C.c_void_p(d_occ) if d_occ else None,
@@ -936,6 +1056,14 @@ class MultiModel(object):
         frames its triplets need (T_i = its triplets + 2).  dtype / occ_prob / out as for Model.computeFlowSequence."""
         return _compute_flow_sequence("b2f_multi_", self._h, frames, out, dtype, occ_prob)
 
+    def computeFlowBatchPast(self, im1, im2, im3, out=None, occ_prob=False):
+        """Model.computeFlowBatchPast over the GPUs, with the same keywords and the same bits."""
+        return _compute_flow_batch_past("b2f_multi_", self._h, im1, im2, im3, out, occ_prob)
+
+    def computeFlowSequencePast(self, frames, out=None, occ_prob=False):
+        """Model.computeFlowSequencePast over the GPUs, with the same keywords and the same bits."""
+        return _compute_flow_sequence_past("b2f_multi_", self._h, frames, out, occ_prob)
+
     def computeFlowBatchRGB(self, im1, im2, im3, max=None, packed=False, want_flow=False, want_masks=False, out=None):
         """Model.computeFlowBatchRGB over the GPUs, with the same keywords and the same bytes."""
         return _compute_flow_batch_rgb("b2f_multi_", self._h, im1, im2, im3, max, packed, want_flow, want_masks, out)
@@ -956,16 +1084,16 @@ class MultiModel(object):
 
 
     def computeFlowBatchWarp(self, im1, im2, im3, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False,
-                             out=None, want_prob=False):
+                             out=None, want_prob=False, own_past_flow=False, want_past=False):
         """Model.computeFlowBatchWarp over the GPUs, with the same keywords, the same bytes and the same words."""
         return _compute_flow_batch_warp("b2f_multi_", self._h, im1, im2, im3, flow_scale, want_warped, want_photo, want_flow, want_masks, out,
-                                        want_prob)
+                                        want_prob, own_past_flow, want_past)
 
     def computeFlowSequenceWarp(self, frames, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False, out=None,
-                                want_prob=False):
+                                want_prob=False, own_past_flow=False, want_past=False):
         """Model.computeFlowSequenceWarp over the GPUs, with the same keywords, the same bytes and the same words."""
         return _compute_flow_sequence_warp("b2f_multi_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out,
-                                           want_prob)
+                                           want_prob, own_past_flow, want_past)
 
     def forwardLoss(self, x, flow_scale=20.0):
         """Model.forwardLoss over the GPUs (b2f_multi_forward_loss; test.lua:266-297): the same words."""

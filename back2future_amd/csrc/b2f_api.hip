@@ -307,6 +307,7 @@ struct Plan {
     bool full;          // full model:forward table (all decoders, image pyramid, image warps)
     bool seq;           // sequence mode: the pyramid holds T = B + 2 frames, triplet b is frames (b, b + 1, b + 2)
     bool stream;        // a push of a stream: the pyramid runs on the B pushed frames, cs[3..7] live in the stream's ring, not in the arena
+    bool past;          // the past-flow decoder chain runs: the full table of a Soft model, or a pruned pass asked for Outs::past
     int nimg;           // images of the feature pyramid: 3B (frame-major [3][B]), T = B + 2, or B (stream)
     int fo;             // image offset of a triplet's second / third frame from its first one: B, or 1 in sequence mode
     int rec;            // cost-volume record size in floats
@@ -314,13 +315,14 @@ struct Plan {
     size_t img, tmp, cs[8], U[8], UB[8], cv, d[6], fs, bfs, logits, u2, flow_planar, ds[6], total;
 };
 
-Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false, bool stream = false)
+Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false, bool stream = false, bool want_past = false)
 {
     Plan p;
     p.B = B; p.H = H; p.W = W;
     p.full = full;
     p.seq = seq;
     p.stream = stream;
+    p.past = past_flow && (full || want_past);
     p.nimg = stream ? B : seq ? B + 2 : 3 * B;
     p.fo = seq ? 1 : B;
     p.rec = kCvRec;
@@ -331,7 +333,7 @@ Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false,
     p.tmp = take((size_t)p.nimg * p.h[2] * p.w[2] * kFeat[2]);
     for (int l = 2; l <= 7; ++l) p.cs[l] = take((stream && l >= 3) ? 0 : (size_t)p.nimg * p.h[l] * p.w[l] * kFeat[l]);
     for (int l = 3; l <= 6; ++l) p.U[l] = take((size_t)B * p.h[l] * p.w[l] * 2);
-    for (int l = 3; l <= 6; ++l) p.UB[l] = (full && past_flow) ? take((size_t)B * p.h[l] * p.w[l] * 2) : 0;
+    for (int l = 3; l <= 6; ++l) p.UB[l] = p.past ? take((size_t)B * p.h[l] * p.w[l] * 2) : 0;
     p.cv = take((size_t)B * p.h[3] * p.w[3] * p.rec + 64);
     const size_t px3 = (size_t)B * p.h[3] * p.w[3];
     for (int i = 1; i <= 5; ++i) p.d[i] = take(px3 * kDec[i]);
@@ -570,6 +572,7 @@ Feat make_feat(const b2f_ctx *c, const Plan &P, const StreamPass *sp)
 // skip_ufs, skip_ubfs (Soft), skip_occs, iws[1], iws[3], all planar at 4h_l x 4w_l.
 struct Outs {
     float *flow = nullptr, *occ = nullptr, *est3 = nullptr;
+    float *past = nullptr;   // pruned mode, Soft only: skip_ubfs[3], B x 2 x H x W planar (runs the past-flow decoder chain)
     float *t_ufs[8] = {nullptr}, *t_ubfs[8] = {nullptr}, *t_occ[8] = {nullptr}, *t_iw1[8] = {nullptr}, *t_iw3[8] = {nullptr};
 };
 
@@ -584,7 +587,7 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
     float *A = c->arena;
     const Feat F = make_feat(c, P, sp);
     const int B = P.B;
-    const bool full = P.full, past = c->past_flow && full;
+    const bool full = P.full, past = P.past;
     const int unit = in_kind == B2F_IN_UNIT;
     if (full) {   // the packed frames are only needed for the image pyramid / image warps of the full table
         Scope sc(c, s, "pack_input", cap);
@@ -700,7 +703,8 @@ int forward_impl(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in
                 // the past flow of level 3 has no next level: its x2 goes through the second half of u2's slot
                 float *ub = (l > 3) ? A + P.UB[l - 1] : A + P.d[1];
                 HIPCHK(launch_upsample_flow2x(A + P.bfs, 8, B, h, w, ub, s));
-                if (O.t_ubfs[l]) HIPCHK(launch_upsample_flow2x_planar(ub, 2, B, 2 * h, 2 * w, O.t_ubfs[l], s));
+                float *skip_b = full ? O.t_ubfs[l] : (l == 3 ? O.past : nullptr);
+                if (skip_b) HIPCHK(launch_upsample_flow2x_planar(ub, 2, B, 2 * h, 2 * w, skip_b, s));
             }
         }
         if (full) {
@@ -876,7 +880,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1004; }
+int b2f_version(void) { return 1005; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1193,9 +1197,12 @@ B2F_CATCH("b2f_profile_read")
 // attributes, which must not happen inside a capture), the second one captures, later ones only replay.  Worth
 // ~0.5 ms per forward pass: 17 % of a single full-HD triplet, 2 % of a batch of 16.
 int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow, float *dev_occ,
-                        float *dev_est3, hipStream_t s, bool graph, bool seq, const StreamPass *sp)
+                        float *dev_est3, hipStream_t s, bool graph, bool seq, const StreamPass *sp, float *dev_past)
 {
     CHK(check_shape(B, H, W));
+    if (dev_past && !c->past_flow)
+        return fail("b2f: this model has no past-flow decoders (a Hard or two_frame model estimates the future flow only): there is no past flow to return");
+    if (dev_past && sp) return fail("b2f_stream_push: a stream does not return the past flow");
     HIPCHK(hipSetDevice(c->device));
     if (sp && !c->g.shipped()) return fail("b2f_stream_push: streams run on the shipped graph only (this context was made with b2f_init_ex options)");
     if (seq && !c->g.shipped()) return fail("b2f_forward_sequence_device: sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
@@ -1225,12 +1232,13 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
         if (dev_flow) HIPCHK(hipMemcpyAsync(dev_flow, dev[0], n2, hipMemcpyDeviceToDevice, s));
         if (dev_occ) HIPCHK(hipMemcpyAsync(dev_occ, dev[(size_t)(c->past_flow ? 2 : 1)], n2, hipMemcpyDeviceToDevice, s));
         if (dev_est3) HIPCHK(hipMemcpyAsync(dev_est3, dev[2], c->past_flow ? n2 : n2 / 2 * 3, hipMemcpyDeviceToDevice, s));
+        if (dev_past) HIPCHK(hipMemcpyAsync(dev_past, dev[1], n2, hipMemcpyDeviceToDevice, s));
         return 0;
     }
-    const Plan P = make_plan(B, H, W, false, c->past_flow, seq, sp != nullptr);
+    const Plan P = make_plan(B, H, W, false, c->past_flow, seq, sp != nullptr, dev_past != nullptr);
     CHK(ensure_workspace(c, P));
     Outs O;
-    O.flow = dev_flow; O.occ = dev_occ; O.est3 = dev_est3;
+    O.flow = dev_flow; O.occ = dev_occ; O.est3 = dev_est3; O.past = dev_past;
     if (graph && !c->profile) {
         if (c->graphs.size() > 256) {   // callers that keep changing pointers: start over (replays may still be in flight)
             HIPCHK(hipDeviceSynchronize());
@@ -1238,7 +1246,7 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
         }
         const int req = c->req_batch > 0 ? c->req_batch : B;
         const GraphKey key = {dev_in, dev_flow, dev_occ, dev_est3, in_kind, B, H, W, (c->adaptive_kernels > 0 || (c->adaptive_kernels < 0 && req == 1)) ? 1 : 0,
-                              seq ? 1 : 0, sp ? sp->ring : nullptr, sp ? 1 + 2 * sp->slot + (sp->ready ? 1 : 0) : 0};
+                              seq ? 1 : 0, sp ? sp->ring : nullptr, sp ? 1 + 2 * sp->slot + (sp->ready ? 1 : 0) : 0, dev_past};
         auto it = c->graphs.find(key);
         if (it == c->graphs.end()) {
             c->graphs.emplace(key, nullptr);
@@ -1290,6 +1298,35 @@ int b2f_forward_sequence_device(b2f_ctx *c, const void *dev_frames, int in_kind,
                           c->use_graph != 0, true);
 }
 B2F_CATCH("b2f_forward_sequence_device")
+
+int b2f_forward_device_past(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow, float *dev_past_flow,
+                            float *dev_occ, float *dev_est3, void *stream) try
+{
+    if (!c || !dev_in) return fail("b2f_forward_device_past: null argument");
+    if (!c->past_flow)
+        return fail("b2f_forward_device_past: this model has no past-flow decoders (a Hard or two_frame model estimates the future flow only)");
+    if (((uintptr_t)dev_in | (uintptr_t)dev_flow | (uintptr_t)dev_past_flow | (uintptr_t)dev_occ | (uintptr_t)dev_est3) & 15)
+        return fail("b2f_forward_device_past: device buffers must be 16-byte aligned");
+    return forward_device(c, dev_in, in_kind, B, H, W, dev_flow, dev_occ, dev_est3, stream ? (hipStream_t)stream : c->stream,
+                          c->use_graph != 0, false, nullptr, dev_past_flow);
+}
+B2F_CATCH("b2f_forward_device_past")
+
+int b2f_forward_sequence_device_past(b2f_ctx *c, const void *dev_frames, int in_kind, int T, int H, int W, float *dev_flow,
+                                     float *dev_past_flow, float *dev_occ, float *dev_est3, void *stream) try
+{
+    if (!c || !dev_frames) return fail("b2f_forward_sequence_device_past: null argument");
+    if (!c->past_flow)
+        return fail("b2f_forward_sequence_device_past: this model has no past-flow decoders (a Hard or two_frame model estimates the future flow only)");
+    if (T < 3) return fail("b2f_forward_sequence_device_past: a sequence needs T >= 3 frames (one triplet)");
+    if (in_kind != B2F_IN_NORMALIZED && in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8)
+        return fail("b2f_forward_sequence_device_past: in_kind must be B2F_IN_NORMALIZED, B2F_IN_UNIT or B2F_IN_U8");
+    if (((uintptr_t)dev_frames | (uintptr_t)dev_flow | (uintptr_t)dev_past_flow | (uintptr_t)dev_occ | (uintptr_t)dev_est3) & 15)
+        return fail("b2f_forward_sequence_device_past: device buffers must be 16-byte aligned");
+    return forward_device(c, dev_frames, in_kind, T - 2, H, W, dev_flow, dev_occ, dev_est3, stream ? (hipStream_t)stream : c->stream,
+                          c->use_graph != 0, true, nullptr, dev_past_flow);
+}
+B2F_CATCH("b2f_forward_sequence_device_past")
 
 int b2f_output_shapes(const b2f_ctx *c, int H, int W, int *ch, int *oh, int *ow, int cap) try
 {

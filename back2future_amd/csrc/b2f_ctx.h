@@ -110,10 +110,11 @@ struct GraphKey {
     int seq;                       // 1 = sequence mode (in = B + 2 frames): never the graph of a triplet call with the same pointers and B
     const void *ring = nullptr;    // stream mode (StreamPass): the stream's device block; in = the frame slot of the pushed frames ...
     int phase = 0;                 // ... 1 + 2 * ring slot + ready: a stream captures one graph per ring phase, and one without the decoders
+    float *past = nullptr;         // the past-flow output: a graph with the past decoder chain is never the graph of a call without it
     bool operator<(const GraphKey &o) const
     {
-        return std::tie(in, flow, occ, est3, kind, B, H, W, rule, seq, ring, phase) <
-               std::tie(o.in, o.flow, o.occ, o.est3, o.kind, o.B, o.H, o.W, o.rule, o.seq, o.ring, o.phase);
+        return std::tie(in, flow, occ, est3, kind, B, H, W, rule, seq, ring, phase, past) <
+               std::tie(o.in, o.flow, o.occ, o.est3, o.kind, o.B, o.H, o.W, o.rule, o.seq, o.ring, o.phase, o.past);
     }
 };
 
@@ -157,6 +158,8 @@ struct HostSlot {
     // warp requests: the warped neighbours of the sub-batch (in the request's element type) and its photometric records
     void *d_warp = nullptr, *h_warp = nullptr;
     unsigned long long *d_photo = nullptr, *h_photo = nullptr;
+    // past-flow requests: skip_ubfs[3] at the network size, at H0 x W0 (= d_past without a rescale) and the staging of a pageable buffer
+    float *d_past = nullptr, *d_past32 = nullptr, *h_past = nullptr;
     hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
 };
 
@@ -167,7 +170,9 @@ struct HostSlot {
 // is then optional.  scores (f32 path only): the records of b2f_compute_flow*_score (launch_flow_score of the f32 flow and occ_prob
 // against gt_flow / valid / gt_occ, which are inputs that travel with the outputs they belong to); the flow is optional there too.
 // warped / photo (f32 path only): the outputs of b2f_compute_flow*_warp (launch_flow_warp of the f32 flow, occ_prob and the request's
-// own frames with flow_scale); at least one is required, everything else is optional.
+// own frames with flow_scale); at least one is required, everything else is optional.  past32 (f32 path only): the past flow of a Soft
+// model, skip_ubfs[3], rescaled like flow32; own_past: the warp of a warp request places the past frame's samples with that past flow
+// (on the device whether or not past32 is asked for).  Either one makes the forward pass run the past-flow decoder chain.
 struct FlowOutputs {
     double *flow64 = nullptr;
     float *flow32 = nullptr, *occ_prob = nullptr;
@@ -186,6 +191,9 @@ struct FlowOutputs {
     int warped_kind = B2F_IN_UNIT;
     unsigned long long *photo = nullptr;
     bool warping = false;          // a warp request: warped or photo is required, flow32 is not
+    float *past32 = nullptr;
+    bool own_past = false;
+    bool want_past() const { return past32 != nullptr || own_past; }
     bool f32() const { return flow64 == nullptr; }
     // the outputs of triplets b, b + 1, ... (planes of hw0 pixels); nullptr stays nullptr
     FlowOutputs from_triplet(size_t b, size_t hw0) const
@@ -195,7 +203,7 @@ struct FlowOutputs {
                 at(rgb, b * 3 * hw0), at(rgb_max, b), max_norm, rgb_layout, pictures,
                 at(scores, b * B2F_SCORE_WORDS), at(gt_flow, b * 2 * hw0), at(valid, b * hw0), at(gt_occ, b * hw0), flow_scale, scoring,
                 warped ? (void *)((char *)warped + b * 6 * hw0 * (warped_kind == B2F_IN_U8 ? 1 : 4)) : nullptr, warped_kind,
-                at(photo, b * B2F_PHOTO_WORDS), warping};
+                at(photo, b * B2F_PHOTO_WORDS), warping, at(past32, b * 2 * hw0), own_past};
     }
 };
 
@@ -221,6 +229,23 @@ inline FlowOutputs warp_outputs(double flow_scale, int in_kind, void *warped, un
 {
     FlowOutputs o{nullptr, flow, occ_prob, fwd_occ, bwd_occ};
     o.flow_scale = flow_scale; o.warped = warped; o.warped_kind = in_kind; o.photo = photo; o.warping = true;
+    return o;
+}
+
+// the outputs of a b2f_*compute_flow_*_past entry: those of the _f32 entries and the past flow (nullptr: a plain _f32 request)
+inline FlowOutputs past_outputs(float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ)
+{
+    FlowOutputs o{nullptr, flow, occ_prob, fwd_occ, bwd_occ};
+    o.past32 = past_flow;
+    return o;
+}
+
+// the outputs of a b2f_*compute_flow_*_warp_past entry: a warp request whose past frame follows the model's own past flow
+inline FlowOutputs warp_past_outputs(double flow_scale, int in_kind, void *warped, unsigned long long *photo, float *flow, float *past_flow,
+                                     float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ)
+{
+    FlowOutputs o = warp_outputs(flow_scale, in_kind, warped, photo, flow, occ_prob, fwd_occ, bwd_occ);
+    o.past32 = past_flow; o.own_past = true;
     return o;
 }
 
@@ -498,8 +523,9 @@ void drop_gen_out(b2f_ctx *c);
 // model:forward on device pointers, optionally replayed from a hipGraph (see b2f_api.hip); seq: dev_in holds the B + 2 frames
 // of a sequence (T x 3 x H x W) instead of B triplets (B x 9 x H x W)
 // sp: a push of a stream -- dev_in holds its B = cams frames (see StreamPass)
+// dev_past: the past flow skip_ubfs[3] (B x 2 x H x W); runs the past-flow decoder chain, refused on a model without one
 int forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow, float *dev_occ,
-                   float *dev_est3, hipStream_t s, bool graph, bool seq = false, const StreamPass *sp = nullptr);
+                   float *dev_est3, hipStream_t s, bool graph, bool seq = false, const StreamPass *sp = nullptr, float *dev_past = nullptr);
 // b2f_pipeline.hip: the checks of a request that need no context and no HIP call (in_kind, T / n, shape, required pointers); 0 = fine
 int check_request(const FlowRequest &r);
 // b2f_pipeline.hip: a request on host buffers (the upload / kernels / download pipeline) and on device buffers (the kernels alone,

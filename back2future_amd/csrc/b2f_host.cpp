@@ -220,12 +220,12 @@ inline void put_warped(float *p, float v) { *p = v; }
 inline void put_warped(unsigned char *p, float v) { *p = warp_quantise(v); }
 
 template <typename T>
-void flow_warp_host_t(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const T *im1, const T *im2, const T *im3,
-                      T *warped, unsigned long long *photo)
+void flow_warp_host_t(const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W, double flow_scale, const T *im1,
+                      const T *im2, const T *im3, T *warped, unsigned long long *photo)
 {
     const size_t hw = (size_t)H * W;
     for (int b = 0; b < n; ++b) {
-        const float *fx = flow + (size_t)b * 2 * hw, *fy = fx + hw;
+        const float *fx = flow + (size_t)b * 2 * hw;
         const float *p0 = occ_prob ? occ_prob + (size_t)b * 2 * hw : nullptr, *p1 = p0 ? p0 + hw : nullptr;
         const T *ref = im2 + (size_t)b * 3 * hw;
         unsigned long long *rec = photo ? photo + (size_t)b * B2F_PHOTO_WORDS : nullptr;
@@ -234,11 +234,13 @@ void flow_warp_host_t(const float *flow, const float *occ_prob, int n, int H, in
             const T *frm = (d == 0 ? im1 : im3) + (size_t)b * 3 * hw;
             const float *pw = d == 0 ? p1 : p0;
             const float k = d == 0 ? -(float)flow_scale : (float)flow_scale;
+            // the past frame's coordinate: from the model's own past flow when there is one (pwc.lua:425-432)
+            const float *cx = (d == 0 && past_flow) ? past_flow + (size_t)b * 2 * hw : fx, *cy = cx + hw;
             T *out = warped ? warped + ((size_t)b * 2 + d) * 3 * hw : nullptr;
             for (int y = 0; y < H; ++y)
                 for (int x = 0; x < W; ++x) {
                     const size_t i = (size_t)y * W + x;
-                    const WarpTaps t = warp_taps(fx[i], fy[i], k, x, y, W, H);
+                    const WarpTaps t = warp_taps(cx[i], cy[i], k, x, y, W, H);
                     float wv[3] = {0.0f, 0.0f, 0.0f}, rv[3];
                     for (int c = 0; c < 3 && !t.nan; ++c) {
                         const T *tl = frm + (size_t)c * hw + (size_t)t.yt * W + t.xl;
@@ -266,13 +268,13 @@ void flow_warp_host_t(const float *flow, const float *occ_prob, int n, int H, in
 }  // namespace
 
 void flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, bool bytes_in, const void *im1,
-                    const void *im2, const void *im3, void *warped, unsigned long long *photo)
+                    const void *im2, const void *im3, void *warped, unsigned long long *photo, const float *past_flow)
 {
     if (bytes_in)
-        flow_warp_host_t(flow, occ_prob, n, H, W, flow_scale, (const unsigned char *)im1, (const unsigned char *)im2, (const unsigned char *)im3,
+        flow_warp_host_t(flow, past_flow, occ_prob, n, H, W, flow_scale, (const unsigned char *)im1, (const unsigned char *)im2, (const unsigned char *)im3,
                          (unsigned char *)warped, photo);
     else
-        flow_warp_host_t(flow, occ_prob, n, H, W, flow_scale, (const float *)im1, (const float *)im2, (const float *)im3, (float *)warped, photo);
+        flow_warp_host_t(flow, past_flow, occ_prob, n, H, W, flow_scale, (const float *)im1, (const float *)im2, (const float *)im3, (float *)warped, photo);
 }
 
 }  // namespace b2f

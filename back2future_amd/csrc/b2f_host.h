@@ -75,9 +75,10 @@ void flow_score_host(const float *flow, const float *occ_prob, int n, int H, int
 
 // Motion compensation on the CPU (b2f_flowwarp.h per pixel; b2f_flow_warp_host): the two warped neighbours (n x 2 x 3 x H x W in the
 // frames' element type, or nullptr) and the photometric records (n x B2F_PHOTO_WORDS words, or nullptr) of a planar n x 2 x H x W
-// fp32 flow; im1 / im2 / im3: n x 3 x H x W each, bytes with bytes_in, floats otherwise; occ_prob may be nullptr
+// fp32 flow; im1 / im2 / im3: n x 3 x H x W each, bytes with bytes_in, floats otherwise; occ_prob may be nullptr.  past_flow (n x 2 x H x W
+// or nullptr): the model's own past flow, which then places the past frame's samples instead of flow (b2f_flow_warp_past_host)
 void flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, bool bytes_in, const void *im1,
-                    const void *im2, const void *im3, void *warped, unsigned long long *photo);
+                    const void *im2, const void *im3, void *warped, unsigned long long *photo, const float *past_flow = nullptr);
 
 // The unsupervised validation loss of test.lua:266-297 on the CPU (b2f_tableloss.h per pixel; b2f_table_loss_host): table = L x (4 | 5)
 // planar fp32 tensors in table order (per level f, [p,] o, iw1, iw3 at (H >> j) x (W >> j)), ref n x 3 x H x W, loss n x L x

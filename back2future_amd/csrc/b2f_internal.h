@@ -352,10 +352,11 @@ hipError_t launch_flow_score(const float *flow, const float *occ_prob, int n, in
 // photometric records (photo: n x B2F_PHOTO_WORDS words, zeroed on s first, or nullptr) of a planar n x 2 x H x W fp32 flow and
 // occ_prob (or nullptr).  im1 / im2 / im3: the past, reference and future frame of image 0 (3 planes of in_kind each); image b lies
 // image_stride samples further: 3 H W for separate arrays and for a sequence (im2 = frames + 3 H W, im3 = frames + 6 H W), 9 H W for
-// the [triplet][frame][3][H W] layout.  One launch, H * W < 2^28
+// the [triplet][frame][3][H W] layout.  past_flow (n x 2 x H x W or nullptr): the model's own past flow; the past frame is then sampled
+// at x - past_flow * flow_scale instead of x - flow * flow_scale (the OwnPast instantiations).  One launch, H * W < 2^28
 hipError_t launch_flow_warp(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const void *im1, const void *im2,
                             const void *im3, size_t image_stride, int in_kind, void *warped, int warped_kind, unsigned long long *photo,
-                            hipStream_t s);
+                            hipStream_t s, const float *past_flow = nullptr);
 
 // ---- the unsupervised validation loss (b2f_tableloss.hip; the per-pixel functions: b2f_tableloss.h) --------------
 // test.lua:266-297 on the output table: table = L x (4 | 5) device tensors of n images in table order (a host array), ref = R_0 of

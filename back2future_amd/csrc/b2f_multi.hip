@@ -371,6 +371,38 @@ int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kind, const
 }
 B2F_CATCH("b2f_multi_compute_flow_sequence_warp")
 
+int b2f_multi_compute_flow_batch_past(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0,
+                                      float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_multi(m, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0, past_outputs(flow, past_flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_multi_compute_flow_batch_past")
+
+int b2f_multi_compute_flow_sequence_past(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0, float *flow, float *past_flow,
+                                         float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_multi(m, sequence_request(__func__, T, in_kind, frames, H0, W0, past_outputs(flow, past_flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_multi_compute_flow_sequence_past")
+
+int b2f_multi_compute_flow_batch_warp_past(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0,
+                                           double flow_scale, void *warped, unsigned long long *photo, float *flow, float *past_flow,
+                                           float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_multi(m, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0,
+                                               warp_past_outputs(flow_scale, in_kind, warped, photo, flow, past_flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_multi_compute_flow_batch_warp_past")
+
+int b2f_multi_compute_flow_sequence_warp_past(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0, double flow_scale,
+                                              void *warped, unsigned long long *photo, float *flow, float *past_flow, float *occ_prob,
+                                              unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_multi(m, sequence_request(__func__, T, in_kind, frames, H0, W0,
+                                                  warp_past_outputs(flow_scale, in_kind, warped, photo, flow, past_flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_multi_compute_flow_sequence_warp_past")
+
 // test.lua:266-297 behind model:forward over several GPUs
 int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss) try
 {

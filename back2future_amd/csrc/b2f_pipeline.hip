@@ -50,6 +50,8 @@ struct SlotNeeds {
     size_t warp_esz;   // d_warp: the warped neighbours of a warp request, bytes per sample (0: not asked for)
     bool photo;        // d_photo: its photometric records
     bool stage_warp, stage_photo;   // h_warp, h_photo: pageable buffers
+    bool past;         // d_past, d_past32: a request with the past flow (FlowOutputs::want_past)
+    bool stage_past;   // h_past: pageable past_flow buffer
 };
 
 // carve the slot's device and pinned blobs for sub-batches of up to SB triplets; grows (never shrinks) the blobs
@@ -66,8 +68,9 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
                  n_sc = q.score ? align256((size_t)SB * B2F_SCORE_WORDS * sizeof(unsigned long long)) : 0;
     const size_t n_wp = align256((size_t)SB * 6 * hw0 * q.warp_esz),
                  n_ph = q.photo ? align256((size_t)SB * B2F_PHOTO_WORDS * sizeof(unsigned long long)) : 0;
+    const size_t n_pnet = q.past ? n_flow : 0, n_p32 = (q.past && !same) ? n_f32 : 0;
     const size_t need_dev = n_up + n_u8 + n_in + n_tmp + n_flow + n_est3 + (same ? 0 : n_f32) + n_onet + n_prob + 2 * n_occ + n_rgb + n_max +
-                            n_gt + n_va + n_lb + n_sc + n_wp + n_ph;
+                            n_gt + n_va + n_lb + n_sc + n_wp + n_ph + n_pnet + n_p32;
     if (need_dev > hs.dev_bytes) {
         if (hs.dev) {
             HIPCHK(hipDeviceSynchronize());
@@ -97,13 +100,15 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.d_gtocc = q.gtocc ? (unsigned char *)d : nullptr; d += n_lb;
     hs.d_score = q.score ? (unsigned long long *)d : nullptr; d += n_sc;
     hs.d_warp = q.warp_esz ? (void *)d : nullptr; d += n_wp;
-    hs.d_photo = q.photo ? (unsigned long long *)d : nullptr;
+    hs.d_photo = q.photo ? (unsigned long long *)d : nullptr; d += n_ph;
+    hs.d_past = q.past ? (float *)d : nullptr; d += n_pnet;
+    hs.d_past32 = !q.past ? nullptr : same ? hs.d_past : (float *)d;
     const size_t n_hf = q.stage_flow ? n_f32 : 0, n_hp = q.stage_prob ? n_f32 : 0;
     const size_t n_hr = q.stage_rgb ? n_rgb : 0, n_hm = q.stage_max ? n_max : 0;
     const size_t n_hg = q.stage_gt ? n_gt : 0, n_hv = q.stage_valid ? n_va : 0, n_hl = q.stage_gtocc ? n_lb : 0, n_hs = q.stage_score ? n_sc : 0;
-    const size_t n_hw = q.stage_warp ? n_wp : 0, n_hph = q.stage_photo ? n_ph : 0;
+    const size_t n_hw = q.stage_warp ? n_wp : 0, n_hph = q.stage_photo ? n_ph : 0, n_hpa = q.stage_past ? n_f32 : 0;
     const size_t need_pin = (q.stage_in ? n_up : 0) + n_u8 + n_hf + n_hp + (q.stage_masks ? 2 * n_occ : 0) + n_hr + n_hm + n_hg + n_hv + n_hl + n_hs +
-                            n_hw + n_hph;
+                            n_hw + n_hph + n_hpa;
     if (need_pin > hs.pin_bytes) {
         if (hs.pin) {
             HIPCHK(hipDeviceSynchronize());
@@ -127,7 +132,8 @@ int ensure_slot(b2f_ctx *c, HostSlot &hs, int SB, size_t hw0, size_t hw, int H0,
     hs.h_gtocc = (unsigned char *)h; h += n_hl;
     hs.h_score = (unsigned long long *)h; h += n_hs;
     hs.h_warp = (void *)h; h += n_hw;
-    hs.h_photo = (unsigned long long *)h;
+    hs.h_photo = (unsigned long long *)h; h += n_hph;
+    hs.h_past = (float *)h;
     for (hipEvent_t *e : {&hs.ev_in, &hs.ev_comp, &hs.ev_out})
         if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return 0;
@@ -180,6 +186,7 @@ struct ReqBatch {
 struct NetBuffers {
     float *tmp, *scaled;        // image.scale's row pass and result (unused at the network size)
     float *flow, *occ, *est3;   // the forward pass's outputs at fh x fw; occ: skip_occs[3] of a Hard model, nullptr when not needed
+    float *past = nullptr;      // skip_ubfs[3] at fh x fw: set when the request wants the past flow (the pass then runs the past chain)
 };
 
 // The kernels of a sub-batch of nb triplets on s.  x: its `planes` input planes at H0 x W0, B2F_IN_UNIT floats or, at the network
@@ -192,6 +199,9 @@ struct NetBuffers {
 // out.warped / out.photo: the motion-compensated neighbours and their photometric records (b2f_warp.hip) of that f32 flow and occ_prob,
 // chosen like the scores' inputs, and of the sub-batch's own frames: x as it came in, before image.scale replaces it, triplet b's
 // three frames 9 planes apart, or the frames of a sequence 3 planes apart.
+// net.past / out.past32: the past flow of a Soft model, rescaled by a second launch of outputs_f32_kernel on its planes (the launch
+// that writes the flow, the probabilities and the masks is the one of a request without it); with out.own_past the warp places the
+// past frame's samples with it, read like the flow: from out.past32 or, at the network size, from net.past.
 // sp: a push of a stream -- the nb = cams frames go through the pyramid into the ring (net.scaled, where image.scale writes, is their
 // frame slot); the rest runs, and the outputs are written, only from the third push on.
 int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void *x, int kind, long planes, int nb, const NetBuffers &net,
@@ -204,11 +214,13 @@ int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void 
         x = net.scaled;
         kind = B2F_IN_NORMALIZED;
     }
-    CHK(forward_device(c, x, kind, nb, g.fh, g.fw, net.flow, net.occ, net.est3, s, graph, r.seq, sp));
+    CHK(forward_device(c, x, kind, nb, g.fh, g.fw, net.flow, net.occ, net.est3, s, graph, r.seq, sp, net.past));
     if (sp && !sp->ready) return 0;
     const bool f32 = r.o.f32();
     HIPCHK(launch_outputs_f32(net.flow, g.C3 == 3 ? net.occ : net.est3, net.est3, g.C3, nb, g.fh, g.fw, g.H0, g.W0, f32 ? g.sc_w : 1.0,
                               f32 ? g.sc_h : 1.0, out.flow32, out.occ_prob, out.fwd_occ, out.bwd_occ, s));
+    if (out.past32)
+        HIPCHK(launch_outputs_f32(net.past, nullptr, nullptr, g.C3, nb, g.fh, g.fw, g.H0, g.W0, g.sc_w, g.sc_h, out.past32, nullptr, nullptr, nullptr, s));
     if (out.rgb) {
         if (!out.flow32 && !g.same) return fail(std::string(r.who) + ": a picture of a rescaled flow needs the flow buffer");
         HIPCHK(launch_flow_rgb(out.flow32 ? out.flow32 : net.flow, nb, g.H0, g.W0, out.max_norm, out.rgb_layout, out.rgb, out.rgb_max, s));
@@ -231,12 +243,14 @@ int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void 
             return fail(std::string(r.who) + ": the warp of a rescaled flow needs the flow and occ_prob buffers");
         const float *prob = !out.photo ? nullptr : g.same ? (g.C3 == 3 ? net.occ : net.est3) : out.occ_prob;
         if (out.photo && !prob) return fail(std::string(r.who) + ": the photometric record needs skip_occs[3]");
+        const float *own_past = !out.own_past ? nullptr : g.same ? net.past : out.past32;
+        if (out.own_past && !own_past) return fail(std::string(r.who) + ": the warp with the model's own past flow needs the past-flow buffer");
         const size_t esz = frames_kind == B2F_IN_U8 ? 1 : 4, stride = (r.seq ? 3 : 9) * g.hw0;
         const char *f0 = (const char *)frames;
         ProfEvent pe;
         const bool timed = prof_open(c, s, "flow_warp", &pe);
         const hipError_t e = launch_flow_warp(out.flow32 ? out.flow32 : net.flow, prob, nb, g.H0, g.W0, out.flow_scale, f0, f0 + 3 * g.hw0 * esz,
-                                              f0 + 6 * g.hw0 * esz, stride, frames_kind, out.warped, out.warped_kind, out.photo, s);
+                                              f0 + 6 * g.hw0 * esz, stride, frames_kind, out.warped, out.warped_kind, out.photo, s, own_past);
         if (timed) prof_close(c, s, pe);
         HIPCHK(e);
     }
@@ -260,6 +274,8 @@ int check_context(b2f_ctx *c, const FlowRequest &r)
     if (!c) return fail(std::string(r.who) + ": null context");
     if (r.seq && !c->g.shipped())
         return fail(std::string(r.who) + ": sequences run on the shipped graph only (this context was made with b2f_init_ex options)");
+    if (r.o.want_past() && !c->past_flow)
+        return fail(std::string(r.who) + ": this model has no past-flow decoders (a Hard or two_frame model estimates the future flow only)");
     return 0;
 }
 
@@ -411,6 +427,12 @@ int b2f::check_request(const FlowRequest &r)
     if (!r.im1 || (!r.seq && !r.stream && (!r.im2 || !r.im3)) ||
         (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : o.scoring ? !o.scores || !o.gt_flow : o.warping ? false : !o.flow32))
         return fail(w + ": null argument");
+    // the past flow is an output of the float32 batch and sequence entries of a Soft model (the model is check_context's to refuse)
+    if (o.want_past()) {
+        if (r.stream) return fail(w + ": a stream does not return the past flow (use the batch or sequence entries)");
+        if (!o.f32()) return fail(w + ": the past flow is an output of the float32 entries");
+        if (o.own_past && !o.warping) return fail(w + ": only a warp request can use the model's own past flow");
+    }
     // a warp request (f32 path as well) needs the warped frames or the photometric records
     if (o.warping) {
         if (!o.f32() || r.stream) return fail(w + ": warped frames are an output of the float32 batch and sequence entries");
@@ -480,8 +502,10 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
     // a warp request: the warped neighbours in the frames' element type and the records
     const size_t warp_esz = o.warped ? (o.warped_kind == B2F_IN_U8 ? 1 : 4) : 0;
     const int k_wp[2] = {out_kind(o.warped, (size_t)n * 6 * hw0 * warp_esz), out_kind(o.photo, (size_t)n * B2F_PHOTO_WORDS * sizeof(unsigned long long))};
+    const bool want_past = o.want_past();
+    const int k_past = out_kind(o.past32, (size_t)n * 2 * hw0 * 4);
     for (int i = 0; i < 6; ++i)
-        if ((i < 3 && k_in[i] < 0) || k_out[i] < 0 || (i < 4 && k_gt[i] < 0) || (i < 2 && k_wp[i] < 0))
+        if ((i < 3 && k_in[i] < 0) || k_out[i] < 0 || (i < 4 && k_gt[i] < 0) || (i < 2 && k_wp[i] < 0) || k_past < 0)
             return fail(w + ": device memory passed to a host-buffer entry point (use b2f_compute_flow_device / "
                             "b2f_compute_flow_sequence_device)");
     if (c->debug_fail_next) {   // tests (option debug_fail_next): one forced failure, e.g. on one replica of a b2f_multi
@@ -511,7 +535,8 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
                 want_rgb, want_rgb && k_out[4] != 1, want_rgb && k_out[5] != 1,
                 want_score, want_score && o.valid, want_score && o.gt_occ, want_score && k_gt[0] != 1, want_score && o.valid && k_gt[1] != 1,
                 want_score && o.gt_occ && k_gt[2] != 1, want_score && k_gt[3] != 1,
-                warp_esz, want_photo, o.warped && k_wp[0] != 1, want_photo && k_wp[1] != 1};
+                warp_esz, want_photo, o.warped && k_wp[0] != 1, want_photo && k_wp[1] != 1,
+                want_past, o.past32 && k_past != 1};
     // (a sequence sub-batch's nb + 2 frames are 3 nb + 6 <= 9 nb planes: the triplet layout of the slot holds them)
     for (int k = 0; k < std::min(nsub, 2); ++k)
         CHK(ensure_slot(c, c->slot[k], SB, hw0, g.hw, g.H0, g.fw, g.C3, q));
@@ -555,6 +580,7 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
                     if (q.stage_score) jobs.push_back({o.scores + b0 * B2F_SCORE_WORDS, hs.h_score, nb * B2F_SCORE_WORDS * sizeof(unsigned long long)});
                     if (q.stage_warp) jobs.push_back({(char *)o.warped + b0 * 6 * hw0 * warp_esz, hs.h_warp, nb * 6 * hw0 * warp_esz});
                     if (q.stage_photo) jobs.push_back({o.photo + b0 * B2F_PHOTO_WORDS, hs.h_photo, nb * B2F_PHOTO_WORDS * sizeof(unsigned long long)});
+                    if (q.stage_past) jobs.push_back({o.past32 + b0 * 2 * hw0, hs.h_past, nb * 2 * hw0 * 4});
                 }
                 if (stage_masks) {
                     if (fwd_occ) jobs.push_back({fwd_occ + b0 * hw0, hs.h_fo, nb * hw0});
@@ -665,11 +691,12 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
         // without a rescale the flow and occ_prob planes are the network's, downloaded as they are
         const float *occ_net = g.C3 == 3 ? hs.d_occ : hs.d_est3;
         CHK(run_kernels(c, r, g, direct_u8 ? (const void *)hs.d_u8 : hs.d_up, direct_u8 ? B2F_IN_U8 : B2F_IN_UNIT, (long)nu * fpu * 3, nb,
-                        {hs.d_tmp, hs.d_in, hs.d_flow, hs.d_occ, hs.d_est3},
+                        {hs.d_tmp, hs.d_in, hs.d_flow, hs.d_occ, hs.d_est3, hs.d_past},
                         {nullptr, same ? nullptr : hs.d_flow32, q.prob ? hs.d_prob : nullptr, fwd_occ ? hs.d_fo : nullptr, bwd_occ ? hs.d_bo : nullptr,
                          hs.d_rgb, hs.d_max, o.max_norm, o.rgb_layout, o.pictures,
                          hs.d_score, hs.d_gt, hs.d_valid, hs.d_gtocc, o.flow_scale, o.scoring,
-                         hs.d_warp, o.warped_kind, hs.d_photo, o.warping},
+                         hs.d_warp, o.warped_kind, hs.d_photo, o.warping,
+                         (q.past && !same) ? hs.d_past32 : nullptr, o.own_past},
                         c->host_graph != 0, c->stream));
         HIPCHK(hipEventRecord(hs.ev_comp, c->stream));
         // ---- download: the set's pinned output buffers must have been handed over (k - 2 drained)
@@ -695,6 +722,9 @@ int b2f::compute_flow_host(b2f_ctx *c, const FlowRequest &r)
         if (want_photo)
             HIPCHK(hipMemcpyAsync(q.stage_photo ? hs.h_photo : o.photo + b0 * B2F_PHOTO_WORDS, hs.d_photo,
                                   (size_t)nb * B2F_PHOTO_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_out));
+        if (o.past32)
+            HIPCHK(hipMemcpyAsync(q.stage_past ? hs.h_past : o.past32 + b0 * 2 * hw0, hs.d_past32, (size_t)nb * 2 * hw0 * 4, hipMemcpyDeviceToHost,
+                                  c->s_out));
         if (want_prob)
             HIPCHK(hipMemcpyAsync(q.stage_prob ? hs.h_prob : o.occ_prob + b0 * 2 * hw0, same ? occ_net : hs.d_prob, (size_t)nb * 2 * hw0 * 4,
                                   hipMemcpyDeviceToHost, c->s_out));
@@ -743,7 +773,7 @@ int b2f::compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream)
     const std::string w(r.who);
     const FlowOutputs &o = r.o;
     const uintptr_t al = (uintptr_t)r.im1 | (uintptr_t)r.im2 | (uintptr_t)r.im3 | (uintptr_t)o.flow32 | (uintptr_t)o.occ_prob |
-                         (uintptr_t)o.fwd_occ | (uintptr_t)o.bwd_occ;
+                         (uintptr_t)o.fwd_occ | (uintptr_t)o.bwd_occ | (uintptr_t)o.past32;
     if (al & 15) return fail(w + ": device buffers must be 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
     const int n = r.n;
@@ -752,8 +782,8 @@ int b2f::compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream)
     const size_t hw0 = g.hw0, esz = bytes_in ? 1 : 4;
     {
         const size_t in_bytes = (size_t)(seq ? n + 2 : n) * 3 * hw0 * esz, hw0n = (size_t)n * hw0;
-        const std::pair<const void *, size_t> bufs[7] = {{r.im1, in_bytes}, {r.im2, in_bytes}, {r.im3, in_bytes}, {o.flow32, hw0n * 8},
-                                                         {o.occ_prob, hw0n * 8}, {o.fwd_occ, hw0n}, {o.bwd_occ, hw0n}};
+        const std::pair<const void *, size_t> bufs[8] = {{r.im1, in_bytes}, {r.im2, in_bytes}, {r.im3, in_bytes}, {o.flow32, hw0n * 8},
+                                                         {o.occ_prob, hw0n * 8}, {o.fwd_occ, hw0n}, {o.bwd_occ, hw0n}, {o.past32, hw0n * 8}};
         for (const auto &pb : bufs)
             if (pb.first && mem_kind(pb.first, pb.second) >= 0)
                 return fail(w + ": host memory passed to a device entry point (use b2f_compute_flow_batch_f32 / b2f_compute_flow_sequence_f32)");
@@ -768,8 +798,8 @@ int b2f::compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream)
     const size_t n_u8 = (!seq && bytes_in) ? align256(planes * hw0) : 0, n_up = (!seq || unpack) ? align256(planes * hw0 * 4) : 0,
                  n_tmp = g.same ? 0 : align256(planes * g.H0 * g.fw * 4), n_in = g.same ? 0 : align256(planes * g.hw * 4),
                  n_flow = align256((size_t)SB * 2 * g.hw * 4), n_occ = (o.occ_prob && g.C3 == 3) ? n_flow : 0,
-                 n_est3 = align256((size_t)SB * g.C3 * g.hw * 4);
-    const size_t need = n_u8 + n_up + n_tmp + n_in + n_flow + n_occ + n_est3;
+                 n_est3 = align256((size_t)SB * g.C3 * g.hw * 4), n_past = o.want_past() ? n_flow : 0;
+    const size_t need = n_u8 + n_up + n_tmp + n_in + n_flow + n_occ + n_est3 + n_past;
     DevWork &dw = c->dwork;
     if (need > dw.bytes) {
         if (dw.dev) {
@@ -789,7 +819,8 @@ int b2f::compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream)
     net.scaled = (float *)d; d += n_in;
     net.flow = (float *)d; d += n_flow;
     net.occ = n_occ ? (float *)d : nullptr; d += n_occ;
-    net.est3 = (float *)d;
+    net.est3 = (float *)d; d += n_est3;
+    net.past = n_past ? (float *)d : nullptr;
     const char *ims[3] = {(const char *)r.im1, (const char *)r.im2, (const char *)r.im3};
     for (const auto &sb : subs) {
         const int b0 = sb.first, nb = sb.second;
@@ -1109,5 +1140,56 @@ int b2f_compute_flow_sequence_device(b2f_ctx *c, int T, int in_kind, const void 
                                                    {nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}), stream);
 }
 B2F_CATCH("b2f_compute_flow_sequence_device")
+
+// ---- the past flow of a Soft model (skip_ubfs[3]) beside the outputs of the _f32 / _warp / _device entries ----
+int b2f_compute_flow_batch_past(b2f_ctx *c, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0, float *flow,
+                                float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0, past_outputs(flow, past_flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_batch_past")
+
+int b2f_compute_flow_sequence_past(b2f_ctx *c, int T, int in_kind, const void *frames, int H0, int W0, float *flow, float *past_flow,
+                                   float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, sequence_request(__func__, T, in_kind, frames, H0, W0, past_outputs(flow, past_flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_sequence_past")
+
+int b2f_compute_flow_device_past(b2f_ctx *c, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, int H0, int W0,
+                                 float *dev_flow, float *dev_past_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ,
+                                 unsigned char *dev_bwd_occ, void *stream) try
+{
+    return compute_flow_device(c, batch_request(__func__, n, in_kind, dev_im1, dev_im2, dev_im3, H0, W0,
+                                                past_outputs(dev_flow, dev_past_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ)), stream);
+}
+B2F_CATCH("b2f_compute_flow_device_past")
+
+int b2f_compute_flow_sequence_device_past(b2f_ctx *c, int T, int in_kind, const void *dev_frames, int H0, int W0, float *dev_flow,
+                                          float *dev_past_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ,
+                                          void *stream) try
+{
+    return compute_flow_device(c, sequence_request(__func__, T, in_kind, dev_frames, H0, W0,
+                                                   past_outputs(dev_flow, dev_past_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ)), stream);
+}
+B2F_CATCH("b2f_compute_flow_sequence_device_past")
+
+int b2f_compute_flow_batch_warp_past(b2f_ctx *c, int n, int in_kind, const void *im1, const void *im2, const void *im3, int H0, int W0,
+                                     double flow_scale, void *warped, unsigned long long *photo, float *flow, float *past_flow, float *occ_prob,
+                                     unsigned char *fwd_occ, unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, batch_request(__func__, n, in_kind, im1, im2, im3, H0, W0,
+                                              warp_past_outputs(flow_scale, in_kind, warped, photo, flow, past_flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_batch_warp_past")
+
+int b2f_compute_flow_sequence_warp_past(b2f_ctx *c, int T, int in_kind, const void *frames, int H0, int W0, double flow_scale, void *warped,
+                                        unsigned long long *photo, float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                        unsigned char *bwd_occ) try
+{
+    return compute_flow_host(c, sequence_request(__func__, T, in_kind, frames, H0, W0,
+                                                 warp_past_outputs(flow_scale, in_kind, warped, photo, flow, past_flow, occ_prob, fwd_occ, bwd_occ)));
+}
+B2F_CATCH("b2f_compute_flow_sequence_warp_past")
 
 }  // extern "C"

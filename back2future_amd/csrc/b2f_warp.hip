@@ -127,14 +127,16 @@ __device__ __forceinline__ void warp_direction(const Tin *frm, size_t hw, int W,
 
 // Image blockIdx.y: its blocks stride over the groups of kPx pixels of its rows.  im1 / im2 / im3: the frames of image 0, image b
 // `stride` samples further; prob: the occlusion probabilities or nullptr; warped: n x 2 x 3 x hw or nullptr; photo[image] was zeroed
-// on the stream (WantPhoto).
-template <typename Tin, typename Tout, bool WantPhoto>
-__global__ void __launch_bounds__(kThreads) flow_warp_kernel(const float *flow, const float *prob, int H, int W, float scale, const Tin *im1,
-                                                             const Tin *im2, const Tin *im3, size_t stride, Tout *warped,
-                                                             unsigned long long *photo)
+// on the stream (WantPhoto).  OwnPast: direction 0 (the past frame) takes its coordinate from past_flow, the model's own past flow
+// (skip_ubfs of a Soft model, pwc.lua:425-432), instead of from flow; everything else of the direction is as without it.
+template <typename Tin, typename Tout, bool WantPhoto, bool OwnPast>
+__global__ void __launch_bounds__(kThreads) flow_warp_kernel(const float *flow, const float *past_flow, const float *prob, int H, int W,
+                                                             float scale, const Tin *im1, const Tin *im2, const Tin *im3, size_t stride,
+                                                             Tout *warped, unsigned long long *photo)
 {
     const size_t b = blockIdx.y, hw = (size_t)H * W;
     const float *fxp = flow + b * 2 * hw, *fyp = fxp + hw;
+    const float *bxp = OwnPast ? past_flow + b * 2 * hw : fxp, *byp = bxp + hw;
     const float *p0 = (WantPhoto && prob) ? prob + b * 2 * hw : nullptr, *p1 = p0 ? p0 + hw : nullptr;
     const Tin *past = im1 + b * stride, *refp = im2 + b * stride, *fut = im3 + b * stride;
     Tout *wout = warped ? warped + b * 6 * hw : nullptr;
@@ -148,6 +150,11 @@ __global__ void __launch_bounds__(kThreads) flow_warp_kernel(const float *flow, 
         float ref[3][kPx] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         load_px(fxp + i0, n, fx);
         load_px(fyp + i0, n, fy);
+        float bx[kPx] = {0.f, 0.f, 0.f, 0.f}, by[kPx] = {0.f, 0.f, 0.f, 0.f};
+        if (OwnPast) {
+            load_px(bxp + i0, n, bx);
+            load_px(byp + i0, n, by);
+        }
         if (WantPhoto) {
             if (p0) {
                 load_px(p0 + i0, n, q0);
@@ -156,7 +163,7 @@ __global__ void __launch_bounds__(kThreads) flow_warp_kernel(const float *flow, 
 #pragma unroll
             for (int c = 0; c < 3; ++c) load_px(refp + (size_t)c * hw + i0, n, ref[c]);
         }
-        warp_direction<Tin, Tout, WantPhoto>(past, hw, W, H, x0, y, n, -scale, fx, fy, ref, q1, p0 != nullptr, wout ? wout + i0 : nullptr, c0);
+        warp_direction<Tin, Tout, WantPhoto>(past, hw, W, H, x0, y, n, -scale, OwnPast ? bx : fx, OwnPast ? by : fy, ref, q1, p0 != nullptr, wout ? wout + i0 : nullptr, c0);
         warp_direction<Tin, Tout, WantPhoto>(fut, hw, W, H, x0, y, n, scale, fx, fy, ref, q0, p0 != nullptr,
                                              wout ? wout + 3 * hw + i0 : nullptr, c1);
     }
@@ -189,15 +196,16 @@ __global__ void __launch_bounds__(kThreads) flow_warp_kernel(const float *flow, 
     }
 }
 
-template <typename Tin, typename Tout, bool WantPhoto>
-hipError_t launch_t(const float *flow, const float *prob, int n, int H, int W, float scale, const void *im1, const void *im2, const void *im3,
+template <typename Tin, typename Tout, bool WantPhoto, bool OwnPast>
+hipError_t launch_t(const float *flow, const float *past_flow, const float *prob, int n, int H, int W, float scale, const void *im1, const void *im2, const void *im3,
                     size_t stride, void *warped, unsigned long long *photo, unsigned bx, hipStream_t s)
 {
     const size_t hw = (size_t)H * W;
     for (int b0 = 0; b0 < n; b0 += 65535) {   // grid.y holds 65535 images
         const int nb = std::min(n - b0, 65535);
         const size_t o = (size_t)b0;
-        hipLaunchKernelGGL((flow_warp_kernel<Tin, Tout, WantPhoto>), dim3(bx, (unsigned)nb), dim3(kThreads), 0, s, flow + o * 2 * hw,
+        hipLaunchKernelGGL((flow_warp_kernel<Tin, Tout, WantPhoto, OwnPast>), dim3(bx, (unsigned)nb), dim3(kThreads), 0, s, flow + o * 2 * hw,
+                           OwnPast ? past_flow + o * 2 * hw : nullptr,
                            prob ? prob + o * 2 * hw : nullptr, H, W, scale, (const Tin *)im1 + o * stride, (const Tin *)im2 + o * stride,
                            (const Tin *)im3 + o * stride, stride, warped ? (Tout *)warped + o * 6 * hw : nullptr,
                            photo ? photo + o * kWords : nullptr);
@@ -208,18 +216,22 @@ hipError_t launch_t(const float *flow, const float *prob, int n, int H, int W, f
 }
 
 template <typename Tin, typename Tout>
-hipError_t launch_p(bool want_photo, const float *flow, const float *prob, int n, int H, int W, float scale, const void *im1, const void *im2,
-                    const void *im3, size_t stride, void *warped, unsigned long long *photo, unsigned bx, hipStream_t s)
+hipError_t launch_p(bool want_photo, const float *flow, const float *past_flow, const float *prob, int n, int H, int W, float scale,
+                    const void *im1, const void *im2, const void *im3, size_t stride, void *warped, unsigned long long *photo, unsigned bx,
+                    hipStream_t s)
 {
-    return want_photo ? launch_t<Tin, Tout, true>(flow, prob, n, H, W, scale, im1, im2, im3, stride, warped, photo, bx, s)
-                      : launch_t<Tin, Tout, false>(flow, prob, n, H, W, scale, im1, im2, im3, stride, warped, photo, bx, s);
+    if (past_flow)
+        return want_photo ? launch_t<Tin, Tout, true, true>(flow, past_flow, prob, n, H, W, scale, im1, im2, im3, stride, warped, photo, bx, s)
+                          : launch_t<Tin, Tout, false, true>(flow, past_flow, prob, n, H, W, scale, im1, im2, im3, stride, warped, photo, bx, s);
+    return want_photo ? launch_t<Tin, Tout, true, false>(flow, nullptr, prob, n, H, W, scale, im1, im2, im3, stride, warped, photo, bx, s)
+                      : launch_t<Tin, Tout, false, false>(flow, nullptr, prob, n, H, W, scale, im1, im2, im3, stride, warped, photo, bx, s);
 }
 
 }  // namespace
 
 hipError_t launch_flow_warp(const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const void *im1, const void *im2,
                             const void *im3, size_t image_stride, int in_kind, void *warped, int warped_kind, unsigned long long *photo,
-                            hipStream_t s)
+                            hipStream_t s, const float *past_flow)
 {
     const size_t hw = (size_t)H * W;
     const bool bin = in_kind == B2F_IN_U8, bout = warped_kind == B2F_IN_U8;
@@ -238,10 +250,10 @@ hipError_t launch_flow_warp(const float *flow, const float *occ_prob, int n, int
     const float scale = (float)flow_scale;
     const bool wp = photo != nullptr;
     if (bin)
-        return bout ? launch_p<unsigned char, unsigned char>(wp, flow, occ_prob, n, H, W, scale, im1, im2, im3, image_stride, warped, photo, bx, s)
-                    : launch_p<unsigned char, float>(wp, flow, occ_prob, n, H, W, scale, im1, im2, im3, image_stride, warped, photo, bx, s);
-    return bout ? launch_p<float, unsigned char>(wp, flow, occ_prob, n, H, W, scale, im1, im2, im3, image_stride, warped, photo, bx, s)
-                : launch_p<float, float>(wp, flow, occ_prob, n, H, W, scale, im1, im2, im3, image_stride, warped, photo, bx, s);
+        return bout ? launch_p<unsigned char, unsigned char>(wp, flow, past_flow, occ_prob, n, H, W, scale, im1, im2, im3, image_stride, warped, photo, bx, s)
+                    : launch_p<unsigned char, float>(wp, flow, past_flow, occ_prob, n, H, W, scale, im1, im2, im3, image_stride, warped, photo, bx, s);
+    return bout ? launch_p<float, unsigned char>(wp, flow, past_flow, occ_prob, n, H, W, scale, im1, im2, im3, image_stride, warped, photo, bx, s)
+                : launch_p<float, float>(wp, flow, past_flow, occ_prob, n, H, W, scale, im1, im2, im3, image_stride, warped, photo, bx, s);
 }
 
 }  // namespace b2f
@@ -277,6 +289,12 @@ bool host_memory(const void *p)
     return !(a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeArray);
 }
 
+int warp_device(const char *who, b2f_ctx *c, const float *dev_flow, const float *dev_past_flow, const float *dev_occ_prob, int n, int H, int W,
+                double flow_scale, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, void *dev_warped,
+                unsigned long long *dev_photo, void *stream);
+int warp_op(const char *who, b2f_ctx *c, const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+            int in_kind, const void *im1, const void *im2, const void *im3, void *warped, unsigned long long *photo);
+
 }  // namespace
 
 extern "C" {
@@ -290,42 +308,92 @@ int b2f_flow_warp_host(const float *flow, const float *occ_prob, int n, int H, i
 }
 B2F_CATCH("b2f_flow_warp_host")
 
+int b2f_flow_warp_past_host(const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W, double flow_scale, int in_kind,
+                            const void *im1, const void *im2, const void *im3, void *warped, unsigned long long *photo) try
+{
+    CHK(check_flow_warp(__func__, flow, n, H, W, flow_scale, in_kind, im1, im2, im3, warped, photo));
+    if (!past_flow) return fail(std::string(__func__) + ": null past_flow");
+    flow_warp_host(flow, occ_prob, n, H, W, flow_scale, in_kind == B2F_IN_U8, im1, im2, im3, warped, photo, past_flow);
+    return 0;
+}
+B2F_CATCH("b2f_flow_warp_past_host")
+
 int b2f_flow_warp_device(b2f_ctx *c, const float *dev_flow, const float *dev_occ_prob, int n, int H, int W, double flow_scale, int in_kind,
                          const void *dev_im1, const void *dev_im2, const void *dev_im3, void *dev_warped, unsigned long long *dev_photo,
                          void *stream) try
 {
-    const std::string w(__func__);
-    CHK(check_flow_warp(w, dev_flow, n, H, W, flow_scale, in_kind, dev_im1, dev_im2, dev_im3, dev_warped, dev_photo));
-    if (((uintptr_t)dev_flow | (uintptr_t)dev_occ_prob | (uintptr_t)dev_im1 | (uintptr_t)dev_im2 | (uintptr_t)dev_im3 | (uintptr_t)dev_warped |
-         (uintptr_t)dev_photo) & 15)
-        return fail(w + ": device buffers must be 16-byte aligned");
-    if (!c) return fail(w + ": null context");
-    HIPCHK(hipSetDevice(c->device));
-    for (const void *p : {(const void *)dev_flow, (const void *)dev_occ_prob, dev_im1, dev_im2, dev_im3, (const void *)dev_warped,
-                          (const void *)dev_photo})
-        if (p && host_memory(p)) return fail(w + ": host memory passed to a device entry point (use b2f_op_flow_warp / b2f_flow_warp_host)");
-    HIPCHK(launch_flow_warp(dev_flow, dev_occ_prob, n, H, W, flow_scale, dev_im1, dev_im2, dev_im3, (size_t)3 * H * W, in_kind, dev_warped,
-                            in_kind, dev_photo, stream ? (hipStream_t)stream : c->stream));
-    return 0;
+    return warp_device(__func__, c, dev_flow, nullptr, dev_occ_prob, n, H, W, flow_scale, in_kind, dev_im1, dev_im2, dev_im3, dev_warped,
+                       dev_photo, stream);
 }
 B2F_CATCH("b2f_flow_warp_device")
+
+int b2f_flow_warp_past_device(b2f_ctx *c, const float *dev_flow, const float *dev_past_flow, const float *dev_occ_prob, int n, int H, int W,
+                              double flow_scale, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, void *dev_warped,
+                              unsigned long long *dev_photo, void *stream) try
+{
+    if (!dev_past_flow) return fail(std::string(__func__) + ": null past_flow");
+    return warp_device(__func__, c, dev_flow, dev_past_flow, dev_occ_prob, n, H, W, flow_scale, in_kind, dev_im1, dev_im2, dev_im3, dev_warped,
+                       dev_photo, stream);
+}
+B2F_CATCH("b2f_flow_warp_past_device")
 
 int b2f_op_flow_warp(b2f_ctx *c, const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, int in_kind, const void *im1,
                      const void *im2, const void *im3, void *warped, unsigned long long *photo) try
 {
-    const std::string w(__func__);
+    return warp_op(__func__, c, flow, nullptr, occ_prob, n, H, W, flow_scale, in_kind, im1, im2, im3, warped, photo);
+}
+B2F_CATCH("b2f_op_flow_warp")
+
+int b2f_op_flow_warp_past(b2f_ctx *c, const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+                          int in_kind, const void *im1, const void *im2, const void *im3, void *warped, unsigned long long *photo) try
+{
+    if (!past_flow) return fail(std::string(__func__) + ": null past_flow");
+    return warp_op(__func__, c, flow, past_flow, occ_prob, n, H, W, flow_scale, in_kind, im1, im2, im3, warped, photo);
+}
+B2F_CATCH("b2f_op_flow_warp_past")
+
+}  // extern "C"
+
+namespace {
+
+// b2f_flow_warp_device / b2f_flow_warp_past_device (dev_past_flow: nullptr without the own past flow)
+int warp_device(const char *who, b2f_ctx *c, const float *dev_flow, const float *dev_past_flow, const float *dev_occ_prob, int n, int H, int W,
+                double flow_scale, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, void *dev_warped,
+                unsigned long long *dev_photo, void *stream)
+{
+    const std::string w(who);
+    CHK(check_flow_warp(w, dev_flow, n, H, W, flow_scale, in_kind, dev_im1, dev_im2, dev_im3, dev_warped, dev_photo));
+    if (((uintptr_t)dev_flow | (uintptr_t)dev_past_flow | (uintptr_t)dev_occ_prob | (uintptr_t)dev_im1 | (uintptr_t)dev_im2 | (uintptr_t)dev_im3 | (uintptr_t)dev_warped |
+         (uintptr_t)dev_photo) & 15)
+        return fail(w + ": device buffers must be 16-byte aligned");
+    if (!c) return fail(w + ": null context");
+    HIPCHK(hipSetDevice(c->device));
+    for (const void *p : {(const void *)dev_flow, (const void *)dev_past_flow, (const void *)dev_occ_prob, dev_im1, dev_im2, dev_im3, (const void *)dev_warped,
+                          (const void *)dev_photo})
+        if (p && host_memory(p)) return fail(w + ": host memory passed to a device entry point (use b2f_op_flow_warp / b2f_flow_warp_host)");
+    HIPCHK(launch_flow_warp(dev_flow, dev_occ_prob, n, H, W, flow_scale, dev_im1, dev_im2, dev_im3, (size_t)3 * H * W, in_kind, dev_warped,
+                            in_kind, dev_photo, stream ? (hipStream_t)stream : c->stream, dev_past_flow));
+    return 0;
+}
+
+// b2f_op_flow_warp / b2f_op_flow_warp_past
+int warp_op(const char *who, b2f_ctx *c, const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W, double flow_scale,
+            int in_kind, const void *im1, const void *im2, const void *im3, void *warped, unsigned long long *photo)
+{
+    const std::string w(who);
     CHK(check_flow_warp(w, flow, n, H, W, flow_scale, in_kind, im1, im2, im3, warped, photo));
     if (!c) return fail(w + ": null context");
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W, esz = in_kind == B2F_IN_U8 ? 1 : 4;
     const size_t nf = (size_t)n * 2 * hw * sizeof(float), ni = (size_t)n * 3 * hw * esz, nw = 2 * ni,
                  np = (size_t)n * B2F_PHOTO_WORDS * sizeof(unsigned long long);
-    DevBytes df, dp, d1, d2, d3, dw, ds;
+    DevBytes df, db, dp, d1, d2, d3, dw, ds;
     auto up = [&](DevBytes &d, const void *src, size_t bytes) -> hipError_t {
         hipError_t e = hipMalloc(&d.p, bytes);
         return e != hipSuccess ? e : hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice);
     };
     HIPCHK(up(df, flow, nf));
+    if (past_flow) HIPCHK(up(db, past_flow, nf));
     if (occ_prob) HIPCHK(up(dp, occ_prob, nf));
     HIPCHK(up(d1, im1, ni));
     HIPCHK(up(d2, im2, ni));
@@ -333,12 +401,11 @@ int b2f_op_flow_warp(b2f_ctx *c, const float *flow, const float *occ_prob, int n
     if (warped) HIPCHK(hipMalloc(&dw.p, nw));
     if (photo) HIPCHK(hipMalloc(&ds.p, np));
     HIPCHK(launch_flow_warp((const float *)df.p, (const float *)dp.p, n, H, W, flow_scale, d1.p, d2.p, d3.p, 3 * hw, in_kind, dw.p, in_kind,
-                            (unsigned long long *)ds.p, c->stream));
+                            (unsigned long long *)ds.p, c->stream, (const float *)db.p));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (warped) HIPCHK(hipMemcpy(warped, dw.p, nw, hipMemcpyDeviceToHost));
     if (photo) HIPCHK(hipMemcpy(photo, ds.p, np, hipMemcpyDeviceToHost));
     return 0;
 }
-B2F_CATCH("b2f_op_flow_warp")
 
-}  // extern "C"
+}  // namespace

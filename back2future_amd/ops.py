@@ -190,14 +190,17 @@ def flow_score(flow, gt_flow, occ_prob=None, valid=None, gt_occ=None, flow_scale
     return scores
 
 
-def flow_warp(flow, im1, im2, im3, occ_prob=None, flow_scale=20.0, want_warped=True, want_photo=True, model=None):
+def flow_warp(flow, im1, im2, im3, occ_prob=None, flow_scale=20.0, want_warped=True, want_photo=True, model=None, own_past_flow=False,
+              past_flow=None):
     """Motion compensation (the warpingUnit of models/pwc.lua:67-73, nn.BilinearSamplerBHWD with CUDA semantics) and its photometric
     error (criterions/OBCCriterion.lua:79-100 with the L1 penalty): flow n x 2 x H x W float32 raw network flow; im1 / im2 / im3 the
     past, reference and future frames, n x 3 x H x W each, all uint8 (value byte / 255) or all float, not normalized; occ_prob
     n x 2 x H x W float32 or None -> (warped, photo): warped n x 2 x 3 x H x W in the frames' dtype ([:, 0] im1 warped with
     -flow_scale, [:, 1] im3 with +flow_scale), photo uint64 (n, 14) (back2future.photo_summary reads it); None for what is not
     wanted.  model=None computes on the CPU (b2f_flow_warp_host, no GPU), a Model on its GPU (b2f_op_flow_warp): the bytes and the
-    words are the same."""
+    words are the same.  own_past_flow=True with past_flow (n x 2 x H x W float32, a Soft model's own past flow, e.g.
+    computeFlowBatchPast's): im1 is sampled at x - past_flow * flow_scale instead of x - flow * flow_scale (pwc.lua:425-432,
+    OBCCriterion.lua:80-81; b2f_flow_warp_past_host / b2f_op_flow_warp_past); everything else is unchanged."""
     from .back2future import IN_U8, IN_UNIT, PHOTO_WORDS
     f = np.asarray(flow)
     if f.ndim != 4 or f.shape[1] != 2 or min(f.shape) < 1:
@@ -218,15 +221,24 @@ def flow_warp(flow, im1, im2, im3, occ_prob=None, flow_scale=20.0, want_warped=T
         if prob.shape != f.shape:
             raise ValueError("flow_warp: occ_prob must have the flow's shape %r, got %r" % (f.shape, prob.shape))
         prob = _lib.f32(prob)
+    if bool(own_past_flow) != (past_flow is not None):
+        raise ValueError("flow_warp: own_past_flow=True and past_flow go together")
+    past = None
+    if own_past_flow:
+        past = np.asarray(past_flow)
+        if past.shape != f.shape:
+            raise ValueError("flow_warp: past_flow must have the flow's shape %r, got %r" % (f.shape, past.shape))
+        past = _lib.f32(past)
     warped = np.empty((n, 2, 3, H, W), np.uint8 if as_bytes else np.float32) if want_warped else None
     photo = np.empty((n, PHOTO_WORDS), np.uint64) if want_photo else None
-    args = (_lib.fptr(f), _lib.fptr(prob) if prob is not None else None, n, H, W, float(flow_scale), IN_U8 if as_bytes else IN_UNIT,
+    args = (_lib.fptr(f), *((_lib.fptr(past),) if own_past_flow else ()), _lib.fptr(prob) if prob is not None else None, n, H, W, float(flow_scale), IN_U8 if as_bytes else IN_UNIT,
             *[C.c_void_p(a.ctypes.data) for a in ims], C.c_void_p(warped.ctypes.data) if warped is not None else None,
             photo.ctypes.data_as(C.POINTER(C.c_ulonglong)) if photo is not None else None)
+    L = _lib.lib()
     if model is None:
-        _lib.check(_lib.lib().b2f_flow_warp_host(*args))
+        _lib.check((L.b2f_flow_warp_past_host if own_past_flow else L.b2f_flow_warp_host)(*args))
     else:
-        _lib.check(_lib.lib().b2f_op_flow_warp(_h(model), *args))
+        _lib.check((L.b2f_op_flow_warp_past if own_past_flow else L.b2f_op_flow_warp)(_h(model), *args))
     return warped, photo
 
 

@@ -5,9 +5,11 @@ and the photometric error of those warps, the measure test.lua:285 reports throu
 penalty.  No ground truth is needed.  The frames are uploaded once as bytes (Model.computeFlowSequenceWarp); the warped frames and
 112 bytes per centre frame come back, or with --no-images the 112 bytes alone.
 
-Usage: python examples/compensate.py FRAMES_DIR OUT_DIR [model] [--scale S] [--no-images]
+Usage: python examples/compensate.py FRAMES_DIR OUT_DIR [model] [--scale S] [--no-images] [--own-past-flow]
 FRAMES_DIR: 8-bit frames, sorted by name.  OUT_DIR receives NAME_past.png and NAME_future.png for every centre frame NAME.
 model as for examples/run_sequence.py (default 'Ours-Soft-ft-KITTI'); --scale: pixels per unit of raw network flow (default 20).
+--own-past-flow (Soft models): the past frame is warped with the model's own past flow instead of minus the future flow, which is
+the reference's warped_img_1 and the past half of its photometric error (pwc.lua:425-432, OBCCriterion.lua:80-81).
 Prints one `name value` line per measure of back2future.photo_summary.
 """
 import os
@@ -31,7 +33,8 @@ def main():
     args = list(sys.argv[1:])
     scale = 20.0
     images = "--no-images" not in args
-    args = [a for a in args if a != "--no-images"]
+    own = "--own-past-flow" in args
+    args = [a for a in args if a not in ("--no-images", "--own-past-flow")]
     if "--scale" in args:
         i = args.index("--scale")
         try:
@@ -49,9 +52,9 @@ def main():
     frames = np.stack([load_bytes(os.path.join(src, f)) for f in names])
     m = back2future.Model(model)
     if images:
-        warped, photo = m.computeFlowSequenceWarp(frames, flow_scale=scale)
+        warped, photo = m.computeFlowSequenceWarp(frames, flow_scale=scale, own_past_flow=own)
     else:
-        photo = m.computeFlowSequenceWarp(frames, flow_scale=scale, want_warped=False)
+        photo = m.computeFlowSequenceWarp(frames, flow_scale=scale, want_warped=False, own_past_flow=own)
     m.close()
     if images:
         os.makedirs(dst, exist_ok=True)

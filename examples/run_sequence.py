@@ -4,10 +4,12 @@ frame that has a neighbour on both sides.  Every frame is uploaded and run throu
 (Model.computeFlowSequence); output t is computeFlow(frame[t-1], frame[t], frame[t+1]) bit for bit.  The flow comes from the
 float32 entry (dtype=np.float32: the float64 flow rounded to float32, which is what a .flo file stores).
 
-Usage: python examples/run_sequence.py DIR OUT/ [model] [--occ-prob] [--rgb [MAX]] [--flo] [--stream]
+Usage: python examples/run_sequence.py DIR OUT/ [model] [--occ-prob] [--past-flow] [--rgb [MAX]] [--flo] [--stream]
 model: 'Ours-Hard' | 'Ours-Soft-ft-KITTI' | 'Ours-Soft-ft-Sintel' (needs models/RoamingImages_*.t7 in the current
 directory, as in the reference) or 'random:soft' / a .t7 / .b2fw path (default 'Ours-Soft-ft-KITTI').
 --occ-prob: also write the occlusion probabilities of every centre frame as a 2 x H x W float32 .npy file.
+--past-flow: also write the past flow of every centre frame as NAME_past.flo (Soft models only: Model.computeFlowSequencePast; the
+past frame lies at x - past_flow, as the future frame lies at x + flow).
 --rgb [MAX]: write the flow picture of every centre frame (flowX.xy2rgb, coloured on the GPU: Model.computeFlowSequenceRGB) as
 a PNG instead; MAX is xy2rgb's `max` (default: every picture's own largest flow).  Only the pictures are downloaded; --flo
 writes the .flo files and masks as well.
@@ -30,6 +32,9 @@ def main():
     args = list(sys.argv[1:])
     want_occ, want_flo, want_rgb, rgb_max = "--occ-prob" in args, "--flo" in args, "--rgb" in args, None
     stream = "--stream" in args
+    want_past = "--past-flow" in args
+    if want_past and (want_rgb or stream):
+        sys.exit("--past-flow cannot be combined with --rgb or --stream")
     if want_rgb:
         i = args.index("--rgb")
         try:
@@ -41,7 +46,7 @@ def main():
             sys.exit("--rgb MAX: MAX must be positive")
         if want_occ:
             sys.exit("--rgb and --occ-prob cannot be combined")
-    args = [a for a in args if a not in ("--occ-prob", "--flo", "--rgb", "--stream")]
+    args = [a for a in args if a not in ("--occ-prob", "--flo", "--rgb", "--stream", "--past-flow")]
     if len(args) < 2:
         sys.exit(__doc__)
     src, out = args[0], args[1]
@@ -75,14 +80,20 @@ def main():
         print("%d frames -> %d flow pictures in %s" % (len(names), len(names) - 2, out))
         m.close()
         return
+    past = None
     if stream:
         res = pushed(lambda st, f: st.push(f, occ_prob=want_occ))
+    elif want_past:
+        res = m.computeFlowSequencePast(frames, occ_prob=want_occ)
+        past, res = res[1], res[:1] + res[2:]
     else:
         res = m.computeFlowSequence(frames, dtype=np.float32, occ_prob=want_occ)
     flow, fwd_occ, bwd_occ = res[:3]
     for i in range(len(names) - 2):
         stem = os.path.join(out, os.path.splitext(names[i + 1])[0])   # named after the centre frame
         flow_io.writeFLO(stem + ".flo", flow[i])
+        if past is not None:
+            flow_io.writeFLO(stem + "_past.flo", past[i])
         flow_io.save_mask(stem + "_fwd_occ.png", fwd_occ[i])
         flow_io.save_mask(stem + "_bwd_occ.png", bwd_occ[i])
         if want_occ:

@@ -367,7 +367,7 @@ B2F_API int b2f_multi_compute_flow_sequence_score(b2f_multi *m, int T, int in_ki
  *   im1 im2 im3 past, reference and future frame, n x 3 x H x W each: B2F_IN_UNIT floats or B2F_IN_U8 bytes (value (float)k / 255.0f);
  *               they are NOT normalized
  * Direction d = 0 warps im1 with k = -(float)flow_scale, d = 1 warps im3 with k = +(float)flow_scale: the constant-velocity branch
- * of OBCCriterion.lua:79-89 for both model kinds.  The warp is nn.BilinearSamplerBHWD with CUDA semantics
+ * of OBCCriterion.lua:79-89 (the b2f_flow_warp_past_* entries below use a Soft model's own past flow for d = 0).  The warp is nn.BilinearSamplerBHWD with CUDA semantics
  * (extras/stnbhwd/BilinearSamplerBHWD.cu:6-20,88-104) in fp32 without fused multiply-adds: xc = fx * k + (float)x, clamped to
  * [0, W - 1]; xl = floorf(xc), xw = 1 - (xc - xl); the same for y; a tap outside the image contributes 0;
  * out = (xw*yw)*tl + ((1-xw)*yw)*tr + (xw*(1-yw))*bl + ((1-xw)*(1-yw))*br, added left to right.  A pixel is inside iff
@@ -427,6 +427,67 @@ B2F_API int b2f_multi_compute_flow_batch_warp(b2f_multi *m, int n, int in_kind, 
 B2F_API int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
                                          double flow_scale, void *warped, unsigned long long *photo, float *flow,
                                          float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* ---- the past flow of the Soft models: skip_ubfs[3], and motion compensation with it ----
+ * A Soft model estimates two flows per reference frame (opts.lua:58 "Jointly predict future and past flow"): the future flow
+ * skip_ufs, which every entry above returns as `flow`, and the past flow skip_ubfs of its own decoder chain (models/pwc.lua:328-385).
+ * The reference warps the past frame with the past flow (pwc.lua:425-432) and forms the past half of the photometric error with it
+ * (criterions/OBCCriterion.lua:80-81).  The entries below return it beside the other outputs: `past_flow` (dev_past_flow) stands
+ * after `flow` and is otherwise like it -- n x 2 x H x W floats, a RAW network flow (pixels / 20 for the shipped models), at
+ * H0 x W0 (float)((double)f * sc) with the nearest-index rule of image.scale(..., 'simple'), the network's own planes at /64 sizes.
+ * Sign: the past frame is sampled at x - past_flow * flow_scale, as the future frame is sampled at x + flow * flow_scale; under
+ * constant velocity past_flow == flow.  A NULL past_flow is neither computed nor downloaded and the call is the entry's without
+ * the suffix; with it the pruned forward pass also runs the five past-flow decoders, and every other output keeps its bits.
+ * A context without past-flow decoders (a Hard model, two_frame) is refused, and so is a stream (b2f_stream_push has no such
+ * output); a refusal launches nothing.                                                                                          */
+B2F_API int b2f_forward_device_past(b2f_ctx *ctx, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow,
+                            float *dev_past_flow, float *dev_occ, float *dev_est3, void *stream);
+B2F_API int b2f_forward_sequence_device_past(b2f_ctx *ctx, const void *dev_frames, int in_kind, int T, int H, int W, float *dev_flow,
+                                     float *dev_past_flow, float *dev_occ, float *dev_est3, void *stream);
+B2F_API int b2f_compute_flow_batch_past(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                int H0, int W0, float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                unsigned char *bwd_occ);
+B2F_API int b2f_compute_flow_sequence_past(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0, float *flow,
+                                   float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_compute_flow_device_past(b2f_ctx *ctx, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3,
+                                 int H0, int W0, float *dev_flow, float *dev_past_flow, float *dev_occ_prob,
+                                 unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
+B2F_API int b2f_compute_flow_sequence_device_past(b2f_ctx *ctx, int T, int in_kind, const void *dev_frames, int H0, int W0,
+                                          float *dev_flow, float *dev_past_flow, float *dev_occ_prob,
+                                          unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
+B2F_API int b2f_multi_compute_flow_batch_past(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                      int H0, int W0, float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                      unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_sequence_past(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0, float *flow,
+                                         float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* Motion compensation with the model's own past flow: everything is b2f_flow_warp_* above except that direction d = 0 takes its
+ * coordinate from past_flow: xc = past_fx * k + (float)x with k = -(float)flow_scale, and inside / outside / non-finite are
+ * decided on that coordinate; the weights stay p1 / p0, the record layout stays B2F_PHOTO_*.  With past_flow == flow every byte
+ * and word is b2f_flow_warp_*'s.  On normalized frames the d = 0 planes are the reference's warped_img_1 of a Soft model.  The
+ * compute_flow forms take the outputs of the _warp entries plus the optional past_flow output: the past flow is produced on the
+ * device whenever such a request arrives and downloaded only when asked for.                                                   */
+B2F_API int b2f_flow_warp_past_host(const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W,
+                            double flow_scale, int in_kind, const void *im1, const void *im2, const void *im3, void *warped,
+                            unsigned long long *photo);
+B2F_API int b2f_flow_warp_past_device(b2f_ctx *ctx, const float *dev_flow, const float *dev_past_flow, const float *dev_occ_prob, int n,
+                              int H, int W, double flow_scale, int in_kind, const void *dev_im1, const void *dev_im2,
+                              const void *dev_im3, void *dev_warped, unsigned long long *dev_photo, void *stream);
+B2F_API int b2f_op_flow_warp_past(b2f_ctx *ctx, const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W,
+                          double flow_scale, int in_kind, const void *im1, const void *im2, const void *im3, void *warped,
+                          unsigned long long *photo);
+B2F_API int b2f_compute_flow_batch_warp_past(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                     int H0, int W0, double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                     float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_compute_flow_sequence_warp_past(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                        double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                        float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_batch_warp_past(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                           int H0, int W0, double flow_scale, void *warped, unsigned long long *photo,
+                                           float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                           unsigned char *bwd_occ);
+B2F_API int b2f_multi_compute_flow_sequence_warp_past(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                              double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                              float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                              unsigned char *bwd_occ);
 /* ---- the unsupervised validation loss: the -optimize pme branch of test.lua:266-297 on the output table ----
  * What the reference validates a model trained without labels with: on every level j = 0 .. L-1 of the output table of model:forward
  * (pwc.lua:459-489; level size h = H >> j, w = W >> j) the contrast-sensitive smoothness of the flows

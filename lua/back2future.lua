@@ -108,6 +108,37 @@ int b2f_compute_flow_batch_warp(b2f_ctx *ctx, int n, int in_kind, const void *im
 int b2f_compute_flow_sequence_warp(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
                                    double flow_scale, void *warped, unsigned long long *photo, float *flow,
                                    float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+/* the past flow of a Soft model (skip_ubfs[3]) and motion compensation with it (include/b2f.h) */
+int b2f_forward_device_past(b2f_ctx *ctx, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow,
+                            float *dev_past_flow, float *dev_occ, float *dev_est3, void *stream);
+int b2f_forward_sequence_device_past(b2f_ctx *ctx, const void *dev_frames, int in_kind, int T, int H, int W, float *dev_flow,
+                                     float *dev_past_flow, float *dev_occ, float *dev_est3, void *stream);
+int b2f_compute_flow_batch_past(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                int H0, int W0, float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                unsigned char *bwd_occ);
+int b2f_compute_flow_sequence_past(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0, float *flow,
+                                   float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_compute_flow_device_past(b2f_ctx *ctx, int n, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3,
+                                 int H0, int W0, float *dev_flow, float *dev_past_flow, float *dev_occ_prob,
+                                 unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
+int b2f_compute_flow_sequence_device_past(b2f_ctx *ctx, int T, int in_kind, const void *dev_frames, int H0, int W0,
+                                          float *dev_flow, float *dev_past_flow, float *dev_occ_prob,
+                                          unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream);
+int b2f_flow_warp_past_host(const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W,
+                            double flow_scale, int in_kind, const void *im1, const void *im2, const void *im3, void *warped,
+                            unsigned long long *photo);
+int b2f_flow_warp_past_device(b2f_ctx *ctx, const float *dev_flow, const float *dev_past_flow, const float *dev_occ_prob, int n,
+                              int H, int W, double flow_scale, int in_kind, const void *dev_im1, const void *dev_im2,
+                              const void *dev_im3, void *dev_warped, unsigned long long *dev_photo, void *stream);
+int b2f_op_flow_warp_past(b2f_ctx *ctx, const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W,
+                          double flow_scale, int in_kind, const void *im1, const void *im2, const void *im3, void *warped,
+                          unsigned long long *photo);
+int b2f_compute_flow_batch_warp_past(b2f_ctx *ctx, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                     int H0, int W0, double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                     float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_compute_flow_sequence_warp_past(b2f_ctx *ctx, int T, int in_kind, const void *frames, int H0, int W0,
+                                        double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                        float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
 /* the unsupervised validation loss of test.lua:266-297 on the output table (include/b2f.h, B2F_LOSS_*) */
 int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
                         double flow_scale, unsigned long long *loss);
@@ -148,6 +179,19 @@ int b2f_multi_compute_flow_batch_warp(b2f_multi *m, int n, int in_kind, const vo
 int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
                                          double flow_scale, void *warped, unsigned long long *photo, float *flow,
                                          float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_compute_flow_batch_past(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                      int H0, int W0, float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                      unsigned char *bwd_occ);
+int b2f_multi_compute_flow_sequence_past(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0, float *flow,
+                                         float *past_flow, float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ);
+int b2f_multi_compute_flow_batch_warp_past(b2f_multi *m, int n, int in_kind, const void *im1, const void *im2, const void *im3,
+                                           int H0, int W0, double flow_scale, void *warped, unsigned long long *photo,
+                                           float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                           unsigned char *bwd_occ);
+int b2f_multi_compute_flow_sequence_warp_past(b2f_multi *m, int T, int in_kind, const void *frames, int H0, int W0,
+                                              double flow_scale, void *warped, unsigned long long *photo, float *flow,
+                                              float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                                              unsigned char *bwd_occ);
 int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
 ]]
 
