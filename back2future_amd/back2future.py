@@ -39,6 +39,31 @@ LOSS_PIXELS, LOSS_SMOOTH_FLOW_Q30, LOSS_SMOOTH_PAST_Q30, LOSS_CONST_VEL_Q30, LOS
 LOSS_PHOTO_INSIDE, LOSS_PHOTO_OUTSIDE, LOSS_PHOTO_OCHARB_Q30, LOSS_PHOTO_NONFINITE, LOSS_NONFINITE, LOSS_WORDS = 6, 8, 10, 12, 14, 16
 LOSS_LEVEL_WEIGHTS = (0.005, 0.01, 0.02, 0.08, 0.32, 0.64, 1.28)                                               # test.lua:29-31
 LOSS_WEIGHTS = {"smooth_flow": 1.0, "const_vel": 1.0, "pme": 1.0, "smooth_occ": 0.1, "prior_occ": 0.1}       # opts.lua:61-73
+# further words of a fine-tuning record (include/b2f.h, B2F_LOSS_FT_*; objective="finetune"): Q30 sums of the second-order smoothness
+# (future, past; criterions/SecondOrderSmoothnessCriterion.lua) and of the occlusion-weighted gradient-constancy errors in x and y
+# (base + direction; criterions/OBGCCriterion.lua), pixels with a NaN second-order term, counted pixel-directions with a NaN gradient term
+LOSS_FT_SMOOTH2_FLOW_Q30, LOSS_FT_SMOOTH2_PAST_Q30, LOSS_FT_PHOTO_OGX_Q30, LOSS_FT_PHOTO_OGY_Q30 = 16, 17, 18, 20
+LOSS_FT_SMOOTH2_NONFINITE, LOSS_FT_GRAD_NONFINITE, LOSS_FT_WORDS = 22, 23, 24
+# what each released model was trained on (the reference's README.md:85-102; anything not named keeps opts.lua:61-73), by the names
+# of init.  pme_alpha is listed as given: OBGCCriterion.lua:97 never applies it.  (model.lua:171 assigns -pme_gamma to a field named
+# `gamm`, so a reference run keeps gamma = 1 whatever the option says; pass pme_gamma=1.0 to loss_summary for what such a run printed.)
+LOSS_OBJECTIVES = {
+    "Ours-Hard": {"weights": {"pme": 1.0, "smooth_flow": 2.0}, "pme_criterion": "OBCC", "smooth_second_order": False,
+                  "pme_alpha": 1.0, "pme_beta": 1.0, "pme_gamma": 1.0, "past_flow": False},
+    "Ours-Soft-ft-KITTI": {"weights": {"pme": 2.0, "smooth_flow": 0.1, "const_vel": 0.0001}, "pme_criterion": "OBGCC",
+                           "smooth_second_order": True, "pme_alpha": 0.0, "pme_beta": 1.0, "pme_gamma": 1.0, "past_flow": True},
+    "Ours-Soft-ft-Sintel": {"weights": {"pme": 4.0, "smooth_flow": 0.1, "const_vel": 0.0001}, "pme_criterion": "OBGCC",
+                            "smooth_second_order": True, "pme_alpha": 1.0, "pme_beta": 0.0, "pme_gamma": 0.0, "past_flow": True},
+}
+
+
+def loss_words(objective):
+    """words per record of objective "pme" (16; test.lua:266-297) or "finetune" (24; with the terms of README.md:89-102)"""
+    if objective == "pme":
+        return LOSS_WORDS
+    if objective == "finetune":
+        return LOSS_FT_WORDS
+    raise ValueError("objective must be 'pme' or 'finetune', got %r" % (objective,))
 
 
 def normalize(imgs):
@@ -596,36 +621,64 @@ def photo_summary(photo):
             "nonfinite": sum(nonf)}
 
 
-def loss_summary(records, like="test", size_average=False, weights=None):
+def loss_summary(records, like="test", size_average=False, weights=None, smooth_second_order=False, pme_criterion="OBCC", pme_beta=1.0,
+                 pme_gamma=1.0, objective=None):
     """The unsupervised validation loss of test.lua:266-297 from loss records (uint64 n x L x 16 or L x 16; ops.table_loss,
-    Model.forwardLoss).  Per level j
+    Model.forwardLoss; or n x L x 24 / L x 24 of objective="finetune").  Per level j
         level_weights[j] * (smooth_flow * S + const_vel * cv + pme * ((OCHARB0 + OCHARB1) / 2^30 + OUTSIDE0 + OUTSIDE1) / (3 * 2)
                             + smooth_occ * so + prior_occ * pr)
     with the level weights of test.lua:29-31 and the weights of opts.lua:61-73 (1, 1, 1, 0.1, 0.1; `weights` replaces any of them).
     like="test": S = n_flow * fs, test.lua:275-277 takes the future flow n_flow times (2 for a Soft table, 1 for a Hard one);
     like="train": S = fs + fp (train.lua:428-432).  A table is Soft when its records carry past-flow or constant-velocity sums.
     size_average=True applies the criteria's own norm factors per triplet: 1 / (2 h w) for the smoothness and velocity terms,
-    1 / (h w) for the photometric term and the prior.  Returns a dict: every term per triplet and level (n x L float64 arrays
-    "smooth_flow", "smooth_past", "const_vel", "pme", "smooth_occ", "prior_occ", weighted by neither), "level" (n x L, the weighted
-    sum above), "loss" (n, the sum over the levels), "mean" (the mean of "loss") and "nonfinite" (pixels left out of a sum because
-    a term was NaN, both kinds of words).  The sums are exact integers; each pixel term carries the Q30 rounding (2^-31)."""
+    1 / (h w) for the photometric term and the prior.
+    With 24-word records: smooth_second_order=True takes fs and fp from the second-order sums (-smooth_second_order,
+    SecondOrderSmoothnessCriterion.lua; like and size_average keep their meaning), and pme_criterion="OBGCC" makes the photometric term
+        sum over d of ((OCHARB_d + pme_beta * OGX_d + pme_gamma * OGY_d) / 2^30 + OUTSIDE_d) / (3 * 2)
+    (OBGCCriterion.lua:96-105,135-143: the brightness part is never multiplied by -pme_alpha, a quirk of updateOutput that is kept).
+    objective=NAME applies LOSS_OBJECTIVES[NAME], the options the named model was trained with, in place of these three arguments and
+    under `weights`.  With 16-word records any of them set away from its default raises ValueError.
+    Returns a dict: every term per triplet and level (n x L float64 arrays "smooth_flow", "smooth_past", "const_vel", "pme",
+    "smooth_occ", "prior_occ", weighted by neither), "level" (n x L, the weighted sum above), "loss" (n, the sum over the levels),
+    "mean" (the mean of "loss") and "nonfinite" (pixels left out of a sum that was used because a term was NaN).  The sums are exact
+    integers; each pixel term carries the Q30 rounding (2^-31)."""
     s = np.asarray(records)
-    if s.dtype != np.uint64 or s.shape[-1:] != (LOSS_WORDS,) or s.ndim not in (2, 3):
-        raise ValueError("loss_summary: expected uint64 records of shape (n, L, %d) or (L, %d), got %s %r" % (LOSS_WORDS, LOSS_WORDS, s.dtype, s.shape))
+    if s.dtype != np.uint64 or s.shape[-1:] not in ((LOSS_WORDS,), (LOSS_FT_WORDS,)) or s.ndim not in (2, 3):
+        raise ValueError("loss_summary: expected uint64 records of shape (n, L, w) or (L, w) with w = %d or %d, got %s %r"
+                         % (LOSS_WORDS, LOSS_FT_WORDS, s.dtype, s.shape))
     if like not in ("test", "train"):
         raise ValueError("loss_summary: like must be 'test' or 'train'")
+    wt = dict(LOSS_WEIGHTS)
+    if objective is not None:
+        if objective not in LOSS_OBJECTIVES:
+            raise ValueError("loss_summary: unknown objective %r (one of %s)" % (objective, ", ".join(sorted(LOSS_OBJECTIVES))))
+        if smooth_second_order or pme_criterion != "OBCC" or pme_beta != 1.0 or pme_gamma != 1.0:
+            raise ValueError("loss_summary: objective=%r sets smooth_second_order, pme_criterion, pme_beta and pme_gamma itself" % (objective,))
+        o = LOSS_OBJECTIVES[objective]
+        smooth_second_order, pme_criterion, pme_beta, pme_gamma = o["smooth_second_order"], o["pme_criterion"], o["pme_beta"], o["pme_gamma"]
+        wt.update(o["weights"])
+    if pme_criterion not in ("OBCC", "OBGCC"):
+        raise ValueError("loss_summary: pme_criterion must be 'OBCC' or 'OBGCC'")
+    gradients = pme_criterion == "OBGCC"
+    ft = s.shape[-1] == LOSS_FT_WORDS
+    if not ft and (smooth_second_order or gradients or pme_beta != 1.0 or pme_gamma != 1.0):
+        raise ValueError("loss_summary: 16-word records carry neither second-order nor gradient sums; compute them with objective='finetune'")
     s = s.reshape((-1,) + s.shape[-2:])
     n, L, _ = s.shape
     if L > len(LOSS_LEVEL_WEIGHTS):
         raise ValueError("loss_summary: at most %d levels" % len(LOSS_LEVEL_WEIGHTS))
-    wt = dict(LOSS_WEIGHTS)
     wt.update(weights or {})
     one = float(1 << 30)
     f = s.astype(np.float64)                    # a sum beyond 2^53 rounds by 2^-53 of itself here
     px = f[:, :, LOSS_PIXELS]
-    fs, fp, cv = f[:, :, LOSS_SMOOTH_FLOW_Q30] / one, f[:, :, LOSS_SMOOTH_PAST_Q30] / one, f[:, :, LOSS_CONST_VEL_Q30] / one
+    w_fs, w_fp = (LOSS_FT_SMOOTH2_FLOW_Q30, LOSS_FT_SMOOTH2_PAST_Q30) if smooth_second_order else (LOSS_SMOOTH_FLOW_Q30, LOSS_SMOOTH_PAST_Q30)
+    fs, fp, cv = f[:, :, w_fs] / one, f[:, :, w_fp] / one, f[:, :, LOSS_CONST_VEL_Q30] / one
     so, pr = f[:, :, LOSS_SMOOTH_OCC_Q30] / one, f[:, :, LOSS_PRIOR_OCC_Q30] / one
-    pme = ((f[:, :, LOSS_PHOTO_OCHARB_Q30] + f[:, :, LOSS_PHOTO_OCHARB_Q30 + 1]) / one + f[:, :, LOSS_PHOTO_OUTSIDE] + f[:, :, LOSS_PHOTO_OUTSIDE + 1]) / (3.0 * 2.0)
+    photo = f[:, :, LOSS_PHOTO_OCHARB_Q30] + f[:, :, LOSS_PHOTO_OCHARB_Q30 + 1]
+    if gradients:
+        photo = photo + float(pme_beta) * (f[:, :, LOSS_FT_PHOTO_OGX_Q30] + f[:, :, LOSS_FT_PHOTO_OGX_Q30 + 1]) \
+                      + float(pme_gamma) * (f[:, :, LOSS_FT_PHOTO_OGY_Q30] + f[:, :, LOSS_FT_PHOTO_OGY_Q30 + 1])
+    pme = (photo / one + f[:, :, LOSS_PHOTO_OUTSIDE] + f[:, :, LOSS_PHOTO_OUTSIDE + 1]) / (3.0 * 2.0)
     if size_average:
         fs, fp, cv, so = fs / (2.0 * px), fp / (2.0 * px), cv / (2.0 * px), so / (2.0 * px)
         pme, pr = pme / px, pr / px
@@ -635,18 +688,21 @@ def loss_summary(records, like="test", size_average=False, weights=None):
     lw = np.asarray(LOSS_LEVEL_WEIGHTS[:L], np.float64)[None, :]
     level = lw * (wt["smooth_flow"] * S + wt["const_vel"] * cv + wt["pme"] * pme + wt["smooth_occ"] * so + wt["prior_occ"] * pr)
     loss = level.sum(axis=1)
-    nonf = int(sum(int(v) for v in s[:, :, [LOSS_NONFINITE, LOSS_PHOTO_NONFINITE, LOSS_PHOTO_NONFINITE + 1]].ravel()))
+    counted = [LOSS_NONFINITE, LOSS_PHOTO_NONFINITE, LOSS_PHOTO_NONFINITE + 1]
+    counted += [LOSS_FT_SMOOTH2_NONFINITE] if smooth_second_order else []
+    counted += [LOSS_FT_GRAD_NONFINITE] if gradients else []
+    nonf = int(sum(int(v) for v in s[:, :, counted].ravel()))
     return {"smooth_flow": fs, "smooth_past": fp, "const_vel": cv, "pme": pme, "smooth_occ": so, "prior_occ": pr, "level": level,
             "loss": loss, "mean": float(loss.mean()), "nonfinite": nonf}
 
 
-def _forward_loss(fn, h, x, flow_scale, L, shapes):
-    """x n x 9 x H x W normalized -> (records uint64 n x L x 16, table or None): b2f_forward_loss / b2f_multi_forward_loss"""
+def _forward_loss(fn, h, x, flow_scale, L, shapes, words=LOSS_WORDS):
+    """x n x 9 x H x W normalized -> (records uint64 n x L x words, table or None): b2f_forward_loss* / b2f_multi_forward_loss*"""
     x = _lib.f32(x)
     if x.ndim != 4 or x.shape[1] != 9:
         raise ValueError("forwardLoss: expected an n x 9 x H x W normalized input, got shape %r" % (x.shape,))
     n, _, H, W = x.shape
-    loss = np.empty((n, L, LOSS_WORDS), np.uint64)
+    loss = np.empty((n, L, words), np.uint64)
     lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong))
     if shapes is None:
         _lib.check(fn(h, _lib.fptr(x), n, H, W, float(flow_scale), lp))
@@ -956,29 +1012,34 @@ class Model(object):
         _lib.check(_lib.lib().b2f_forward(self._h, _lib.fptr(x), B, H, W, ptrs, len(outs)))
         return outs
 
-    def forwardLoss(self, x, flow_scale=20.0, want_table=False):
+    def forwardLoss(self, x, flow_scale=20.0, want_table=False, objective="pme"):
         """model:forward followed by the unsupervised validation loss of test.lua:266-297 (b2f_forward_loss): x n x 9 x H x W,
         already normalized -> uint64 records (n, L, 16), those of ops.table_loss(self.forward(x), x[:, 3:6]); the table stays on the
         GPU.  want_table=True returns (records, table) with the table of Model.forward, bit for bit.  loss_summary reads the
-        records."""
+        records.  objective="finetune" (b2f_forward_loss_ft): records (n, L, 24), those of ops.table_loss(..., objective="finetune")."""
+        words = loss_words(objective)
+        entry = _lib.lib().b2f_forward_loss_ft if words != LOSS_WORDS else _lib.lib().b2f_forward_loss
         L = self.n_outputs // (5 if self.past_flow else 4)
         if want_table:
-            return _forward_loss(_lib.lib().b2f_forward_loss, self._h, x, flow_scale, L, self.output_shapes)
-        fn = lambda h, xp, n, H, W, fsc, lp: _lib.lib().b2f_forward_loss(h, xp, n, H, W, fsc, lp, None, 0)
-        return _forward_loss(fn, self._h, x, flow_scale, L, None)[0]
+            return _forward_loss(entry, self._h, x, flow_scale, L, self.output_shapes, words)
+        fn = lambda h, xp, n, H, W, fsc, lp: entry(h, xp, n, H, W, fsc, lp, None, 0)
+        return _forward_loss(fn, self._h, x, flow_scale, L, None, words)[0]
 
-    def forwardLossDevice(self, d_in, n, H, W, d_loss, flow_scale=20.0, stream=None):
+    def forwardLossDevice(self, d_in, n, H, W, d_loss, flow_scale=20.0, stream=None, objective="pme"):
         """b2f_forward_loss_device on device pointers (ints): d_in n x 9 x H x W normalized float32, d_loss n x L x 16 uint64 (test.lua:266-297);
-        asynchronous on `stream`."""
-        _lib.check(_lib.lib().b2f_forward_loss_device(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale),
-                                                       C.c_void_p(d_loss), C.c_void_p(stream) if stream else None))
+        asynchronous on `stream`.  objective="finetune" (b2f_forward_loss_ft_device): d_loss n x L x 24."""
+        entry = _lib.lib().b2f_forward_loss_ft_device if loss_words(objective) != LOSS_WORDS else _lib.lib().b2f_forward_loss_device
+        _lib.check(entry(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale), C.c_void_p(d_loss),
+                         C.c_void_p(stream) if stream else None))
 
-    def tableLossDevice(self, d_table, n, H, W, d_ref, d_loss, flow_scale=20.0, stream=None):
+    def tableLossDevice(self, d_table, n, H, W, d_ref, d_loss, flow_scale=20.0, stream=None, objective="pme"):
         """b2f_table_loss_device on device pointers (ints): d_table the L x 4 | 5 tensors of an output table in table order, d_ref
-        n x 3 x H x W, d_loss n x L x 16 uint64 (test.lua:266-297); asynchronous on `stream`."""
+        n x 3 x H x W, d_loss n x L x 16 uint64 (test.lua:266-297); asynchronous on `stream`.  objective="finetune"
+        (b2f_table_loss_ft_device): d_loss n x L x 24."""
         ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
-        _lib.check(_lib.lib().b2f_table_loss_device(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale),
-                                                     C.c_void_p(d_loss), C.c_void_p(stream) if stream else None))
+        entry = _lib.lib().b2f_table_loss_ft_device if loss_words(objective) != LOSS_WORDS else _lib.lib().b2f_table_loss_device
+        _lib.check(entry(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale), C.c_void_p(d_loss),
+                         C.c_void_p(stream) if stream else None))
 
     def forward_device(self, d_in, B, H, W, d_flow=None, d_occ=None, d_est3=None, unit_input=False, stream=None, d_past_flow=None):
         """model:forward on device pointers (ints); asynchronous on `stream`.  d_past_flow (B x 2 x H x W float32, Soft models;
@@ -1095,12 +1156,14 @@ class MultiModel(object):
         return _compute_flow_sequence_warp("b2f_multi_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out,
                                            want_prob, own_past_flow, want_past)
 
-    def forwardLoss(self, x, flow_scale=20.0):
-        """Model.forwardLoss over the GPUs (b2f_multi_forward_loss; test.lua:266-297): the same words."""
+    def forwardLoss(self, x, flow_scale=20.0, objective="pme"):
+        """Model.forwardLoss over the GPUs (b2f_multi_forward_loss / b2f_multi_forward_loss_ft; test.lua:266-297): the same words."""
+        words = loss_words(objective)
+        entry = _lib.lib().b2f_multi_forward_loss_ft if words != LOSS_WORDS else _lib.lib().b2f_multi_forward_loss
         c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
         lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
-        return _forward_loss(_lib.lib().b2f_multi_forward_loss, self._h, x, flow_scale, no.value // (5 if pf.value else 4), None)[0]
+        return _forward_loss(entry, self._h, x, flow_scale, no.value // (5 if pf.value else 4), None, words)[0]
 
 
 def shard_range(n, rank, world):

@@ -880,7 +880,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1005; }
+int b2f_version(void) { return 1006; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1409,6 +1409,7 @@ namespace {
 // what a b2f_forward_loss* call needs from the context's loss workspace for sub-batches of nb triplets
 struct LossPlan {
     int L = 0, per = 0, n_outs = 0;
+    int words = B2F_LOSS_WORDS;     // of a record: B2F_LOSS_FT_WORDS with the fine-tuning terms of README.md:89-102
     std::vector<size_t> cnt, off;   // floats and byte offset of every tensor of the table
     size_t in_off = 0, loss_off = 0, bytes = 0;
 };
@@ -1425,9 +1426,10 @@ int check_forward_loss(const b2f_ctx *c, const std::string &w, int n, int H, int
     return 0;
 }
 
-LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input)
+LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input, bool ft)
 {
     LossPlan p;
+    p.words = ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS;
     p.per = c->past_flow ? 5 : 4;
     p.n_outs = c->g.n_outputs();
     p.L = p.n_outs / p.per;
@@ -1439,7 +1441,7 @@ LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input)
         p.cnt.push_back((size_t)nb * ch * (H >> j) * (W >> j));
         p.off.push_back(take(p.cnt.back() * sizeof(float)));
     }
-    p.loss_off = take((size_t)nb * p.L * B2F_LOSS_WORDS * sizeof(unsigned long long));
+    p.loss_off = take((size_t)nb * p.L * p.words * sizeof(unsigned long long));
     p.bytes = off;
     return p;
 }
@@ -1469,8 +1471,14 @@ int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H
     ProfEvent pe;
     const bool timed = prof_open(c, s, "table_loss", &pe);
     const size_t hw = (size_t)H * W;
-    const hipError_t e = launch_table_loss(tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, (float *)c->loss_pyr.dev, flow_scale, d_loss, s);
+    hipError_t e = launch_table_loss(tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, (float *)c->loss_pyr.dev, flow_scale, d_loss, s, lp.words);
     if (timed) prof_close(c, s, pe);
+    HIPCHK(e);
+    if (lp.words == B2F_LOSS_WORDS) return 0;
+    ProfEvent pf;
+    const bool timed_ft = prof_open(c, s, "table_loss_ft", &pf);
+    e = launch_table_loss_ft_terms(tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, (float *)c->loss_pyr.dev, flow_scale, d_loss, s);
+    if (timed_ft) prof_close(c, s, pf);
     HIPCHK(e);
     return 0;
 }
@@ -1484,9 +1492,10 @@ struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub
 }  // namespace
 
 // b2f_forward_loss on a shard: `req` is the caller's n (b2f_multi_forward_loss passes its own down)
-int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs)
+int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
+                           bool ft)
 {
-    const std::string w("b2f_forward_loss");
+    const std::string w(ft ? "b2f_forward_loss_ft" : "b2f_forward_loss");
     if (!c || !x || !loss) return fail(w + ": null argument");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
     if ((outs == nullptr) != (n_outs == 0)) return fail(w + ": outs and n_outs go together (NULL and 0: the table is not downloaded)");
@@ -1496,7 +1505,7 @@ int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, in
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
     const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
-    const LossPlan lp = make_loss_plan(c, sb, H, W, true);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, true, ft);
     CHK(ensure_dev_work(c->loss_work, lp.bytes));
     char *base = c->loss_work.dev;
     std::vector<float *> tab((size_t)lp.n_outs);
@@ -1510,7 +1519,7 @@ int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, in
         HIPCHK(hipMemcpyAsync(d_in, x + (size_t)b0 * 9 * hw, (size_t)nb * 9 * hw * sizeof(float), hipMemcpyHostToDevice, s));
         // (a shorter last sub-batch lays its tensors out for nb images in the same buffers)
         CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, lp, tab.data(), d_loss));
-        HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * B2F_LOSS_WORDS, d_loss, (size_t)nb * lp.L * B2F_LOSS_WORDS * sizeof(unsigned long long),
+        HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * lp.words, d_loss, (size_t)nb * lp.L * lp.words * sizeof(unsigned long long),
                               hipMemcpyDeviceToHost, s));
         for (int i = 0; i < n_outs; ++i) {
             const size_t per_img = lp.cnt[(size_t)i] / (size_t)sb;
@@ -1526,15 +1535,21 @@ extern "C" {
 // model:forward + test.lua:266-297 from host memory
 int b2f_forward_loss(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try
 {
-    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, false);
 }
 B2F_CATCH("b2f_forward_loss")
 
-// model:forward + test.lua:266-297 on device pointers
-int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
-                            void *stream) try
+// model:forward + test.lua:266-297 + the fine-tuning terms of README.md:89-102 from host memory
+int b2f_forward_loss_ft(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try
 {
-    const std::string w(__func__);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, true);
+}
+B2F_CATCH("b2f_forward_loss_ft")
+
+// b2f_forward_loss_device / b2f_forward_loss_ft_device
+static int forward_loss_device(const std::string &w, bool ft, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                               unsigned long long *dev_loss, void *stream)
+{
     if (!c || !dev_in || !dev_loss) return fail(w + ": null argument");
     if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
@@ -1542,7 +1557,7 @@ int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, 
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
     const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
-    const LossPlan lp = make_loss_plan(c, sb, H, W, false);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, false, ft);
     CHK(ensure_dev_work(c->loss_work, lp.bytes));
     std::vector<float *> tab((size_t)lp.n_outs);
     for (int i = 0; i < lp.n_outs; ++i) tab[(size_t)i] = (float *)(c->loss_work.dev + lp.off[(size_t)i]);
@@ -1550,10 +1565,25 @@ int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, 
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     for (int b0 = 0; b0 < n; b0 += sb)
         CHK(forward_loss_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, lp, tab.data(),
-                             dev_loss + (size_t)b0 * lp.L * B2F_LOSS_WORDS));
+                             dev_loss + (size_t)b0 * lp.L * lp.words));
     return 0;
 }
+
+// model:forward + test.lua:266-297 on device pointers
+int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
+                            void *stream) try
+{
+    return forward_loss_device(__func__, false, c, dev_in, in_kind, n, H, W, flow_scale, dev_loss, stream);
+}
 B2F_CATCH("b2f_forward_loss_device")
+
+// ... with the fine-tuning terms of README.md:89-102: dev_loss n x L x 24 words
+int b2f_forward_loss_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
+                               void *stream) try
+{
+    return forward_loss_device(__func__, true, c, dev_in, in_kind, n, H, W, flow_scale, dev_loss, stream);
+}
+B2F_CATCH("b2f_forward_loss_ft_device")
 
 }  // extern "C"
 

@@ -532,7 +532,9 @@ int check_request(const FlowRequest &r);
 // asynchronous on `stream`, nullptr: the context's)
 int compute_flow_host(b2f_ctx *c, const FlowRequest &r);
 // b2f_api.hip: b2f_forward_loss (test.lua:266-297 behind model:forward) on n of a request of `req` triplets (0: n)
-int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs);
+// ft: b2f_forward_loss_ft, records of B2F_LOSS_FT_WORDS words
+int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
+                      bool ft = false);
 int compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream);
 // b2f_pipeline.hip: a push (r.stream) on host buffers, synchronous, and on device buffers, asynchronous on `stream`; *ready = 1 when
 // the outputs were written (from the third push on)

@@ -6,6 +6,7 @@
 #include "b2f_flowscore.h"
 #include "b2f_flowwarp.h"
 #include "b2f_tableloss.h"
+#include "b2f_tableloss_ft.h"
 #include "../../include/b2f.h"
 
 #include <cmath>
@@ -282,8 +283,21 @@ void flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int 
 // ---- the unsupervised validation loss on the CPU (test.lua:266-297) ----------------------------------------------------------------
 namespace b2f {
 
+// R_j from R_{j-1} (3 planes of hp x wp): the 2 x 2 mean in fp32 (nn.SpatialAveragePooling(2,2,2,2), test.lua:132,269)
+static void pool_ref(const float *R, int hp, int wp, std::vector<float> &out)
+{
+    const int h = hp / 2, w = wp / 2;
+    out.resize((size_t)3 * h * w);
+    for (int c = 0; c < 3; ++c)
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const float *q = R + ((size_t)c * hp + 2 * y) * wp + 2 * x;
+                out[((size_t)c * h + y) * w + x] = (((q[0] + q[1]) + q[wp]) + q[wp + 1]) / 4.0f;
+            }
+}
+
 void table_loss_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
-                     unsigned long long *loss)
+                     unsigned long long *loss, int words)
 {
     const int per = past ? 5 : 4;
     std::vector<float> cur, next;
@@ -293,14 +307,7 @@ void table_loss_host(const float *const *table, int L, bool past, int n, int H, 
             const int h = H >> j, w = W >> j;
             const size_t hw = (size_t)h * w;
             if (j > 0) {   // R_j = the 2 x 2 mean of R_{j-1} (nn.SpatialAveragePooling(2,2,2,2), test.lua:132,269)
-                const int hp = H >> (j - 1), wp = W >> (j - 1);
-                next.resize(3 * hw);
-                for (int c = 0; c < 3; ++c)
-                    for (int y = 0; y < h; ++y)
-                        for (int x = 0; x < w; ++x) {
-                            const float *q = R + ((size_t)c * hp + 2 * y) * wp + 2 * x;
-                            next[((size_t)c * h + y) * w + x] = (((q[0] + q[1]) + q[wp]) + q[wp + 1]) / 4.0f;
-                        }
+                pool_ref(R, H >> (j - 1), W >> (j - 1), next);
                 cur.swap(next);
                 R = cur.data();
             }
@@ -309,8 +316,8 @@ void table_loss_host(const float *const *table, int L, bool past, int n, int H, 
             const float *o = t[per - 3] + (size_t)b * 2 * hw, *iw[2] = {t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
             const float *plane[9] = {f, f + hw, p, p ? p + hw : nullptr, o, o + hw, R, R + hw, R + 2 * hw};
             const float kd = (float)(flow_scale / (double)(1 << j));
-            unsigned long long *rec = loss + ((size_t)b * L + j) * B2F_LOSS_WORDS;
-            for (int k = 0; k < B2F_LOSS_WORDS; ++k) rec[k] = 0;
+            unsigned long long *rec = loss + ((size_t)b * L + j) * words;
+            for (int k = 0; k < words; ++k) rec[k] = 0;
             for (int y = 0; y < h; ++y)
                 for (int x = 0; x < w; ++x) {
                     const size_t i = (size_t)y * w + x;
@@ -339,6 +346,69 @@ void table_loss_host(const float *const *table, int L, bool past, int n, int H, 
                         rec[B2F_LOSS_PHOTO_OUTSIDE + d] += ph.outside;
                         rec[B2F_LOSS_PHOTO_OCHARB_Q30 + d] += ph.ocharb;
                         rec[B2F_LOSS_PHOTO_NONFINITE + d] += ph.nonfinite;
+                    }
+                }
+        }
+    }
+}
+
+// the fine-tuning terms of README.md:89-102 beside test.lua:266-297
+void table_loss_ft_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                        unsigned long long *loss)
+{
+    table_loss_host(table, L, past, n, H, W, ref, flow_scale, loss, B2F_LOSS_FT_WORDS);
+    const int per = past ? 5 : 4;
+    std::vector<float> cur, next;
+    for (int b = 0; b < n; ++b) {
+        const float *R = ref + (size_t)b * 3 * H * W;
+        for (int j = 0; j < L; ++j) {
+            const int h = H >> j, w = W >> j;
+            const size_t hw = (size_t)h * w;
+            if (j > 0) {
+                pool_ref(R, H >> (j - 1), W >> (j - 1), next);
+                cur.swap(next);
+                R = cur.data();
+            }
+            const float *const *t = table + (size_t)j * per;
+            const float *f = t[0] + (size_t)b * 2 * hw, *p = past ? t[1] + (size_t)b * 2 * hw : nullptr;
+            const float *o = t[per - 3] + (size_t)b * 2 * hw, *iw[2] = {t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
+            const float *plane[7] = {f, f + hw, p, p ? p + hw : nullptr, R, R + hw, R + 2 * hw};
+            const float kd = (float)(flow_scale / (double)(1 << j));
+            unsigned long long *rec = loss + ((size_t)b * L + j) * B2F_LOSS_FT_WORDS;
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    const size_t i = (size_t)y * w + x;
+                    const bool has_l = x > 0, has_r = x + 1 < w, has_u = y > 0, has_d = y + 1 < h;
+                    float v[7], vl[7], vr[7], vu[7], vd[7];
+                    for (int c = 0; c < 7; ++c) {
+                        const float *q = plane[c];
+                        v[c] = q ? q[i] : 0.0f;
+                        vl[c] = (q && has_l) ? q[i - 1] : 0.0f;
+                        vr[c] = (q && has_r) ? q[i + 1] : 0.0f;
+                        vu[c] = (q && has_u) ? q[i - w] : 0.0f;
+                        vd[c] = (q && has_d) ? q[i + w] : 0.0f;
+                    }
+                    const PixelSmooth2 s = smooth2_pixel(v, vl, vr, vu, vd, has_l, has_r, has_u, has_d, past);
+                    rec[B2F_LOSS_FT_SMOOTH2_FLOW_Q30] += s.flow;
+                    rec[B2F_LOSS_FT_SMOOTH2_PAST_Q30] += s.past;
+                    rec[B2F_LOSS_FT_SMOOTH2_NONFINITE] += s.nonfinite;
+                    const float r3[3] = {v[4], v[5], v[6]}, r3x[3] = {vr[4], vr[5], vr[6]}, r3y[3] = {vd[4], vd[5], vd[6]};
+                    for (int d = 0; d < 2; ++d) {
+                        const bool pf = d == 0 && past;   // OBGCCriterion.lua:110-111
+                        const WarpTaps tp = warp_taps(pf ? v[2] : v[0], pf ? v[3] : v[1], d == 0 ? -kd : kd, x, y, w, h);
+                        float w3[3], w3x[3], w3y[3];
+                        for (int c = 0; c < 3; ++c) {
+                            const float *q = iw[d] + (size_t)c * hw + i;
+                            w3[c] = q[0];
+                            w3x[c] = has_r ? q[1] : 0.0f;
+                            w3y[c] = has_d ? q[w] : 0.0f;
+                        }
+                        const float wt = d == 0 ? o[hw + i] : o[i];
+                        const PixelPhoto ph = photo_pixel(tp, w3, r3, true, wt);
+                        const PixelGrad g = grad_pixel(w3, w3x, w3y, r3, r3x, r3y, has_r, has_d, ph.inside != 0u, wt);
+                        rec[B2F_LOSS_FT_PHOTO_OGX_Q30 + d] += g.ogx;
+                        rec[B2F_LOSS_FT_PHOTO_OGY_Q30 + d] += g.ogy;
+                        rec[B2F_LOSS_FT_GRAD_NONFINITE] += g.nonfinite;
                     }
                 }
         }

@@ -82,9 +82,13 @@ void flow_warp_host(const float *flow, const float *occ_prob, int n, int H, int 
 
 // The unsupervised validation loss of test.lua:266-297 on the CPU (b2f_tableloss.h per pixel; b2f_table_loss_host): table = L x (4 | 5)
 // planar fp32 tensors in table order (per level f, [p,] o, iw1, iw3 at (H >> j) x (W >> j)), ref n x 3 x H x W, loss n x L x
-// B2F_LOSS_WORDS words
+// `words` words (B2F_LOSS_WORDS; a wider record keeps its further words zero)
 void table_loss_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
-                     unsigned long long *loss);
+                     unsigned long long *loss, int words = 16);
+// table_loss_host with records of B2F_LOSS_FT_WORDS words, and in words 16 .. 23 the fine-tuning terms of README.md:89-102
+// (b2f_tableloss_ft.h per pixel; b2f_table_loss_ft_host)
+void table_loss_ft_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                        unsigned long long *loss);
 // the argument checks every table-loss entry shares (test.lua:266-297; no HIP call): nullptr and *L = n_outs / per, or why not
 const char *table_loss_refusal(int n_outs, int per, int n, int H, int W, double flow_scale, int *L);
 

@@ -362,9 +362,15 @@ hipError_t launch_flow_warp(const float *flow, const float *occ_prob, int n, int
 // test.lua:266-297 on the output table: table = L x (4 | 5) device tensors of n images in table order (a host array), ref = R_0 of
 // image 0, image b `ref_stride` samples further (3 H W for n x 3 x H x W, 9 H W for channels 3 .. 5 of the network's input), pyr =
 // table_loss_pyramid_floats(L, n, H, W) floats of workspace for R_1 .. R_{L-1}; loss: n x L x B2F_LOSS_WORDS words, zeroed on s first.
-// n <= 65535, H * W < 2^28, H and W multiples of 2^(L-1)
+// n <= 65535, H * W < 2^28, H and W multiples of 2^(L-1).  words: the width of a record (B2F_LOSS_WORDS, or B2F_LOSS_FT_WORDS with
+// the words from 16 on left zero)
 size_t table_loss_pyramid_floats(int L, int n, int H, int W);
 hipError_t launch_table_loss(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr,
-                             double flow_scale, unsigned long long *loss, hipStream_t s);
+                             double flow_scale, unsigned long long *loss, hipStream_t s, int words = 16);
+// the fine-tuning terms of README.md:89-102 (b2f_tableloss_ft.hip; the per-pixel functions: b2f_tableloss_ft.h) into words 16 .. 23 of
+// records of B2F_LOSS_FT_WORDS words, behind launch_table_loss(..., B2F_LOSS_FT_WORDS) with the same arguments on the same stream:
+// that call zeroes the records and lays R_1 .. R_{L-1} into pyr, which this one reads
+hipError_t launch_table_loss_ft_terms(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
+                                      const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s);
 
 }  // namespace b2f

@@ -403,17 +403,34 @@ int b2f_multi_compute_flow_sequence_warp_past(b2f_multi *m, int T, int in_kind, 
 }
 B2F_CATCH("b2f_multi_compute_flow_sequence_warp_past")
 
+}  // extern "C"
+
+// b2f_multi_forward_loss / b2f_multi_forward_loss_ft
+static int multi_forward_loss(const std::string &w, bool ft, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss)
+{
+    if (!m) return api_fail(w + ": null context");
+    if (!x || !loss || n <= 0 || H <= 0 || W <= 0) return api_fail(w + ": bad arguments");
+    const b2f_ctx *c0 = m->ctx[0];
+    const size_t rec = (size_t)(c0->g.n_outputs() / (c0->past_flow ? 5 : 4)) * (ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
+    return run_sharded(m, n, [&](int i, int lo, int hi) {
+        return forward_loss_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, loss + (size_t)lo * rec, nullptr, 0, ft);
+    });
+}
+
+extern "C" {
+
 // test.lua:266-297 behind model:forward over several GPUs
 int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss) try
 {
-    if (!m) return api_fail("b2f_multi_forward_loss: null context");
-    if (!x || !loss || n <= 0 || H <= 0 || W <= 0) return api_fail("b2f_multi_forward_loss: bad arguments");
-    const b2f_ctx *c0 = m->ctx[0];
-    const size_t rec = (size_t)(c0->g.n_outputs() / (c0->past_flow ? 5 : 4)) * B2F_LOSS_WORDS;
-    return run_sharded(m, n, [&](int i, int lo, int hi) {
-        return forward_loss_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, loss + (size_t)lo * rec, nullptr, 0);
-    });
+    return multi_forward_loss(__func__, false, m, x, n, H, W, flow_scale, loss);
 }
 B2F_CATCH("b2f_multi_forward_loss")
+
+// ... with the fine-tuning terms of README.md:89-102 in words 16 .. 23
+int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss) try
+{
+    return multi_forward_loss(__func__, true, m, x, n, H, W, flow_scale, loss);
+}
+B2F_CATCH("b2f_multi_forward_loss_ft")
 
 }  // extern "C"

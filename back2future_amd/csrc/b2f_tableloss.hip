@@ -7,6 +7,7 @@
 // of the context.
 #include "b2f_ctx.h"
 #include "b2f_tableloss.h"
+#include "b2f_tableloss_dev.h"
 
 using namespace b2f;
 
@@ -16,30 +17,11 @@ namespace b2f {
 
 namespace {
 
-constexpr int kPx = 4;        // consecutive pixels of a row per thread: one 16-byte load per plane and row
+constexpr int kPx = kLossPx;  // consecutive pixels of a row per thread (b2f_tableloss_dev.h: load_px)
 constexpr int kThreads = 256;
 constexpr int kWave = 64;     // gfx950
 constexpr int kWaves = kThreads / kWave;
 constexpr int kWords = B2F_LOSS_WORDS;
-
-// n (1..4) samples of a row at p: one 16-byte load where the address allows -- rows of odd w are not aligned --, scalar loads
-// otherwise; v[n..] is left alone
-__device__ __forceinline__ void load_px(const float *p, int n, float *v)
-{
-    if (n == kPx && ((uintptr_t)p & 15) == 0) {
-        const float4 q = *reinterpret_cast<const float4 *>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        return;
-    }
-    for (int k = 0; k < kPx; ++k)
-        if (k < n) v[k] = p[k];
-}
-
-// the planes of one level: image 0; image b lies 2 hw (f, p, o), 3 hw (iw1, iw3) or ref_stride (ref) samples further
-struct LevelPtrs {
-    const float *f, *p, *o, *iw1, *iw3, *ref;
-    size_t ref_stride;
-};
 
 // Image blockIdx.y of one level: its blocks stride over the groups of kPx pixels of its rows.  loss: the record of image 0 at this
 // level, image b lies `rec_stride` words further; zeroed on the stream before.
@@ -171,15 +153,16 @@ size_t table_loss_pyramid_floats(int L, int n, int H, int W)
 }
 
 hipError_t launch_table_loss(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr,
-                             double flow_scale, unsigned long long *loss, hipStream_t s)
+                             double flow_scale, unsigned long long *loss, hipStream_t s, int words)
 {
     const int per = past ? 5 : 4;
+    if (words < kWords) return hipErrorInvalidValue;
     if (n <= 0 || n > 65535 || L < 1 || L > kLossMaxLevels || H <= 0 || W <= 0 || (size_t)H * W >= (size_t)kPhotoMaxPixels || H % (1 << (L - 1)) ||
         W % (1 << (L - 1)) || !table || !ref || !loss || (L > 1 && !pyr) || ref_stride < (size_t)3 * H * W)
         return hipErrorInvalidValue;
     for (int i = 0; i < L * per; ++i)
         if (!table[i]) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(loss, 0, (size_t)n * L * kWords * sizeof(unsigned long long), s);
+    hipError_t e = hipMemsetAsync(loss, 0, (size_t)n * L * words * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     const float *R = ref;
     size_t R_stride = ref_stride;
@@ -203,11 +186,11 @@ hipError_t launch_table_loss(const float *const *table, int L, bool past, int n,
         const size_t cap = std::min<size_t>(1024, std::max<size_t>(8, 2048 / (size_t)n));
         const dim3 grid((unsigned)std::min(blocks, cap), (unsigned)n);
         const float kd = (float)(flow_scale / (double)(1 << j));
-        unsigned long long *rec = loss + (size_t)j * kWords;
+        unsigned long long *rec = loss + (size_t)j * words;
         if (past)
-            hipLaunchKernelGGL(table_loss_kernel<true>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * kWords);
+            hipLaunchKernelGGL(table_loss_kernel<true>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * words);
         else
-            hipLaunchKernelGGL(table_loss_kernel<false>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * kWords);
+            hipLaunchKernelGGL(table_loss_kernel<false>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * words);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
@@ -266,26 +249,10 @@ int level_size(const b2f_ctx *c, int n_outs)
     return (n_outs > 0 && n_outs % own == 0) ? own : (n_outs > 0 && n_outs % other == 0) ? other : 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-// test.lua:266-297 on the CPU
-int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
-                        unsigned long long *loss) try
+// b2f_table_loss_device / b2f_table_loss_ft_device (ft: records of B2F_LOSS_FT_WORDS words with the fine-tuning terms)
+int table_loss_device(const std::string &w, bool ft, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                      double flow_scale, unsigned long long *dev_loss, void *stream)
 {
-    int L = 0;
-    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
-    table_loss_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, loss);
-    return 0;
-}
-B2F_CATCH("b2f_table_loss_host")
-
-// test.lua:266-297 on device pointers
-int b2f_table_loss_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
-                          unsigned long long *dev_loss, void *stream) try
-{
-    const std::string w(__func__);
     if (!c) return fail(w + ": null context");
     const int per = level_size(c, n_outs);
     if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
@@ -303,18 +270,23 @@ int b2f_table_loss_device(b2f_ctx *c, const float *const *dev_table, int n_outs,
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     ProfEvent pe;
     const bool timed = prof_open(c, s, "table_loss", &pe);
-    const hipError_t e = launch_table_loss(dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, (float *)c->loss_pyr.dev, flow_scale, dev_loss, s);
+    hipError_t e = launch_table_loss(dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, (float *)c->loss_pyr.dev, flow_scale, dev_loss, s,
+                                     ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
     if (timed) prof_close(c, s, pe);
+    HIPCHK(e);
+    if (!ft) return 0;
+    ProfEvent pf;
+    const bool timed_ft = prof_open(c, s, "table_loss_ft", &pf);
+    e = launch_table_loss_ft_terms(dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, (float *)c->loss_pyr.dev, flow_scale, dev_loss, s);
+    if (timed_ft) prof_close(c, s, pf);
     HIPCHK(e);
     return 0;
 }
-B2F_CATCH("b2f_table_loss_device")
 
-// test.lua:266-297 on host pointers through the GPU
-int b2f_op_table_loss(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
-                      unsigned long long *loss) try
+// b2f_op_table_loss / b2f_op_table_loss_ft
+int op_table_loss(const std::string &w, bool ft, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                  unsigned long long *loss)
 {
-    const std::string w(__func__);
     if (!c) return fail(w + ": null context");
     const int per = level_size(c, n_outs);
     if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
@@ -334,13 +306,68 @@ int b2f_op_table_loss(b2f_ctx *c, const float *const *table, int n_outs, int n, 
         ptrs[(size_t)i] = (const float *)dt[(size_t)i].p;
     }
     HIPCHK(up(dr, ref, (size_t)n * 3 * H * W * sizeof(float)));
-    const size_t nl = (size_t)n * L * B2F_LOSS_WORDS * sizeof(unsigned long long);
+    const size_t nl = (size_t)n * L * (ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS) * sizeof(unsigned long long);
     HIPCHK(hipMalloc(&dl.p, nl));
-    CHK(b2f_table_loss_device(c, ptrs.data(), n_outs, n, H, W, (const float *)dr.p, flow_scale, (unsigned long long *)dl.p, nullptr));
+    CHK(table_loss_device(w, ft, c, ptrs.data(), n_outs, n, H, W, (const float *)dr.p, flow_scale, (unsigned long long *)dl.p, nullptr));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(loss, dl.p, nl, hipMemcpyDeviceToHost));
     return 0;
 }
+
+}  // namespace
+
+extern "C" {
+
+// test.lua:266-297 on the CPU
+int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                        unsigned long long *loss) try
+{
+    int L = 0;
+    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
+    table_loss_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, loss);
+    return 0;
+}
+B2F_CATCH("b2f_table_loss_host")
+
+// test.lua:266-297 on device pointers
+int b2f_table_loss_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                          unsigned long long *dev_loss, void *stream) try
+{
+    return table_loss_device(__func__, false, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
+}
+B2F_CATCH("b2f_table_loss_device")
+
+// test.lua:266-297 on host pointers through the GPU
+int b2f_op_table_loss(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                      unsigned long long *loss) try
+{
+    return op_table_loss(__func__, false, c, table, n_outs, n, H, W, ref, flow_scale, loss);
+}
 B2F_CATCH("b2f_op_table_loss")
+
+// ---- the same three with the fine-tuning terms of README.md:89-102 in words 16 .. 23 (b2f_tableloss_ft.hip) ----
+int b2f_table_loss_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                           unsigned long long *loss) try
+{
+    int L = 0;
+    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
+    table_loss_ft_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, loss);
+    return 0;
+}
+B2F_CATCH("b2f_table_loss_ft_host")
+
+int b2f_table_loss_ft_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                             unsigned long long *dev_loss, void *stream) try
+{
+    return table_loss_device(__func__, true, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
+}
+B2F_CATCH("b2f_table_loss_ft_device")
+
+int b2f_op_table_loss_ft(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                         unsigned long long *loss) try
+{
+    return op_table_loss(__func__, true, c, table, n_outs, n, H, W, ref, flow_scale, loss);
+}
+B2F_CATCH("b2f_op_table_loss_ft")
 
 }  // extern "C"

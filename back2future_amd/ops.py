@@ -242,14 +242,18 @@ def flow_warp(flow, im1, im2, im3, occ_prob=None, flow_scale=20.0, want_warped=T
     return warped, photo
 
 
-def table_loss(table, ref, flow_scale=20.0, model=None):
+def table_loss(table, ref, flow_scale=20.0, model=None, objective="pme"):
     """The records of the unsupervised validation loss (the -optimize pme branch of test.lua:266-297) of an output table of
     model:forward: table a list of L x 4 (Hard: per level future flow, occlusions, warped image 1, warped image 3) or L x 5 (Soft:
     the past flow second) float32 arrays n x C x (H >> j) x (W >> j), what Model.forward returns; ref n x 3 x H x W float32, the
     normalized centre frame (x[:, 3:6] of the network's input) -> uint64 (n, L, 16) (back2future.LOSS_*; back2future.loss_summary
     reads it).  model=None computes on the CPU (b2f_table_loss_host, no GPU), a Model on its GPU (b2f_op_table_loss; a table whose
-    length fits both kinds, 20 tensors, is read as the model's kind): the words are the same."""
-    from .back2future import LOSS_WORDS
+    length fits both kinds, 20 tensors, is read as the model's kind): the words are the same.  objective="finetune" returns
+    (n, L, 24) (b2f_table_loss_ft_host / b2f_op_table_loss_ft): the same 16 words, then the second-order smoothness and the
+    gradient-constancy sums the Soft models were fine-tuned on (back2future.LOSS_FT_*)."""
+    from .back2future import LOSS_WORDS, loss_words
+    words = loss_words(objective)
+    ft = "_ft" if words != LOSS_WORDS else ""
     r = np.asarray(ref)
     if r.ndim != 4 or r.shape[1] != 3 or min(r.shape) < 1:
         raise ValueError("table_loss: expected an n x 3 x H x W reference image, got shape %r" % (np.shape(ref),))
@@ -267,13 +271,13 @@ def table_loss(table, ref, flow_scale=20.0, model=None):
         if t.shape != want:
             raise ValueError("table_loss: tensor %d of the table must have shape %r, got %r" % (i, want, t.shape))
     ptrs = (_lib.c_float_p * len(tab))(*[_lib.fptr(t) for t in tab])
-    loss = np.empty((n, L, LOSS_WORDS), np.uint64)
+    loss = np.empty((n, L, words), np.uint64)
     lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong))
     if model is None:
-        _lib.check(_lib.lib().b2f_table_loss_host(ptrs, len(tab), n, H, W, int(per == 5), _lib.fptr(r), float(flow_scale), lp))
+        _lib.check(getattr(_lib.lib(), "b2f_table_loss%s_host" % ft)(ptrs, len(tab), n, H, W, int(per == 5), _lib.fptr(r), float(flow_scale), lp))
     else:
         if per != (5 if model.past_flow else 4) and len(tab) % (5 if model.past_flow else 4) == 0:
             raise ValueError("table_loss: a %s table of %d tensors on a %s model would be read as the model's kind; use a model of the "
                              "table's kind or model=None" % ("Soft" if per == 5 else "Hard", len(tab), "Soft" if model.past_flow else "Hard"))
-        _lib.check(_lib.lib().b2f_op_table_loss(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), lp))
+        _lib.check(getattr(_lib.lib(), "b2f_op_table_loss" + ft)(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), lp))
     return loss

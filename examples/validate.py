@@ -3,9 +3,11 @@
 objective the reference validates a model trained without labels with -- the -optimize pme branch of test.lua:266-297: flow
 smoothness, constant velocity, the occlusion-aware photometric error of the model's own warped images, occlusion smoothness and
 the occlusion prior, on every level of the output table.  No ground truth is needed.  The table stays on the GPU
-(Model.forwardLoss); 128 bytes per level and centre frame come back.
+(Model.forwardLoss); 128 bytes per level and centre frame come back.  --objective NAME prints instead the objective the named model
+was trained on (back2future.LOSS_OBJECTIVES, the commands of the reference's README.md:85-102): for the two Soft models the
+second-order smoothness and the brightness and gradient constancy of OBGCC, from records of 192 bytes (objective="finetune").
 
-Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average]
+Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME]
 FRAMES_DIR: 8-bit frames, sorted by name; they are cropped (top left) to multiples of 64 and normalized with
 back2future.normalize.  MODEL as for examples/run_sequence.py.  --scale: pixels per unit of raw network flow (default 20).
 Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`.
@@ -31,22 +33,26 @@ def load_unit(path, H, W):
 
 def main():
     args = list(sys.argv[1:])
-    scale, like = 20.0, "test"
+    scale, like, objective = 20.0, "test", None
     size_average = "--size-average" in args
     args = [a for a in args if a != "--size-average"]
-    for flag in ("--scale", "--like"):
+    for flag in ("--scale", "--like", "--objective"):
         if flag in args:
             i = args.index(flag)
             try:
                 if flag == "--scale":
                     scale = float(args[i + 1])
-                else:
+                elif flag == "--like":
                     like = args[i + 1]
+                else:
+                    objective = args[i + 1]
             except (IndexError, ValueError):
                 sys.exit(flag + ": bad value")
             del args[i:i + 2]
     if len(args) != 2 or like not in ("test", "train"):
         sys.exit(__doc__)
+    if objective is not None and objective not in back2future.LOSS_OBJECTIVES:
+        sys.exit("--objective: one of " + ", ".join(sorted(back2future.LOSS_OBJECTIVES)))
     src, model = args
     names = sorted(f for f in os.listdir(src) if f.lower().endswith(EXTS))
     if len(names) < 3:
@@ -61,9 +67,9 @@ def main():
     records = []
     for b0 in range(0, len(frames) - 2, BATCH):
         x = np.stack([np.concatenate(frames[i:i + 3], axis=0) for i in range(b0, min(b0 + BATCH, len(frames) - 2))])
-        records.append(m.forwardLoss(x, flow_scale=scale))
+        records.append(m.forwardLoss(x, flow_scale=scale, objective="pme" if objective is None else "finetune"))
     m.close()
-    s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average)
+    s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, objective=objective)
     for f, v in zip(names[1:-1], s["loss"]):
         print("%s %r" % (os.path.splitext(f)[0], float(v)))
     print("mean %r" % s["mean"])

@@ -556,6 +556,48 @@ B2F_API int b2f_forward_loss_device(b2f_ctx *ctx, const void *dev_in, int in_kin
                             unsigned long long *dev_loss, void *stream);
 /* test.lua:266-297 over several GPUs: the n triplets are split with b2f_shard_range; one context's words */
 B2F_API int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
+/* ---- the fine-tuning objective of the Soft models: the terms of README.md:89-102 beside those above ----
+ * Ours-Soft-ft-KITTI and Ours-Soft-ft-Sintel were trained with -smooth_second_order and -pme_criterion OBGCC.  The *_ft entries
+ * return records of 24 words per image and level: words 0 .. 15 are those of the entries above, bit for bit, and words 16 .. 23 carry
+ * the second-order smoothness (criterions/SecondOrderSmoothnessCriterion.lua:45-65) and the gradient-constancy sums of
+ * criterions/OBGCCriterion.lua:67-68,91-105, both with the L1 penalty P1.  Same inputs, same fp64 arithmetic without fused
+ * multiply-adds, same E, P1 and q as above.  Per pixel (x, y) of a level of h x w, a missing neighbour giving no term (so levels
+ * the reference cannot slice, h < 3 or w < 3, are defined too):
+ *   gx(F,c) = (2.0 * F[c][y][x] - F[c][y][x-1]) - F[c][y][x+1] if 0 < x and x + 1 < w, else 0; gy the same over rows
+ *   m(a, b) = ((|R0(a) - R0(b)| + |R1(a) - R1(b)|) + |R2(a) - R2(b)|) / 3.0
+ *   igx = (x > 0 ? m((x,y), (x-1,y)) : 0) + (0 < x and x + 1 < w ? m((x,y), (x+1,y)) : 0); igy the same over rows (lines 55-58)
+ *   wx = E(-20.0 * igx), wy = E(-20.0 * igy)
+ *   the four products of a flow F: P1(gx(F,0)) * wx, P1(gy(F,0)) * wy, P1(gx(F,1)) * wx, P1(gy(F,1)) * wy: a border pixel adds
+ *           P1(0) = 1e-3 times its weight, not 0 (lines 38-39 zero the second differences, line 65 applies the penalty to them)
+ * SMOOTH2_FLOW_Q30 sums q of each of the four products of f, SMOOTH2_PAST_Q30 of p (0 for Hard): q saturates at 16, which a sum of
+ * products could reach and one product of a plausible flow cannot.  If a product of a flow is NaN the pixel adds nothing for that flow
+ * and counts once in SMOOTH2_NONFINITE.  Gradient constancy, direction d as above with its warped image I = iw_d and weight o[1 - d]:
+ *   dx_c = (I[c][y][x+1] - I[c][y][x]) - (R[c][y][x+1] - R[c][y][x]) if x + 1 < w, else 0 (lines 67-68, 91-92: both forward
+ *          differences are 0 in the last column); dy_c the same over rows
+ * A pixel-direction that counts in PHOTO_INSIDE adds (q(o * P1(dx_0)) + q(o * P1(dx_1))) + q(o * P1(dx_2)) to PHOTO_OGX_Q30[d] and
+ * the same with dy to PHOTO_OGY_Q30[d] (per channel: the three-channel sum of normalized images can pass q's saturation at 16, one
+ * channel cannot); if any of the six products is NaN it adds to neither and counts in GRAD_NONFINITE.  Any other pixel-direction
+ * adds nothing.  The brightness part of OBGCC is PHOTO_OCHARB_Q30: line 97 never applies alpha to it, only beta and gamma weigh the
+ * two gradient sums (back2future.loss_summary).  The words are macros, below the entries: the enumeration above stays as it is.  */
+/* The six entries above with records of 24 words (192 bytes): same arguments, same checks, same sub-batching, same workspaces. */
+B2F_API int b2f_table_loss_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                           double flow_scale, unsigned long long *loss);
+B2F_API int b2f_table_loss_ft_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                             double flow_scale, unsigned long long *dev_loss, void *stream);
+B2F_API int b2f_op_table_loss_ft(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                         double flow_scale, unsigned long long *loss);
+B2F_API int b2f_forward_loss_ft(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                        float **outs, int n_outs);
+B2F_API int b2f_forward_loss_ft_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                               unsigned long long *dev_loss, void *stream);
+B2F_API int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
+#define B2F_LOSS_FT_SMOOTH2_FLOW_Q30 16   /* second-order smoothness of the future flow, 2^-30 */
+#define B2F_LOSS_FT_SMOOTH2_PAST_Q30 17   /* second-order smoothness of the past flow (0 for Hard) */
+#define B2F_LOSS_FT_PHOTO_OGX_Q30 18      /* [2] occlusion-weighted gradient-constancy error in x, past / future */
+#define B2F_LOSS_FT_PHOTO_OGY_Q30 20      /* [2] the same in y */
+#define B2F_LOSS_FT_SMOOTH2_NONFINITE 22  /* pixels with a NaN second-order term */
+#define B2F_LOSS_FT_GRAD_NONFINITE 23     /* pixel-directions of PHOTO_INSIDE with a NaN gradient term */
+#define B2F_LOSS_FT_WORDS 24
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature

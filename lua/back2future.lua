@@ -150,6 +150,17 @@ int b2f_forward_loss(b2f_ctx *ctx, const float *x, int n, int H, int W, double f
                      float **outs, int n_outs);
 int b2f_forward_loss_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                             unsigned long long *dev_loss, void *stream);
+/* ... with the fine-tuning terms of README.md:89-102 in words 16 .. 23 of records of 24 words (include/b2f.h, B2F_LOSS_FT_*) */
+int b2f_table_loss_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                           double flow_scale, unsigned long long *loss);
+int b2f_table_loss_ft_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                             double flow_scale, unsigned long long *dev_loss, void *stream);
+int b2f_op_table_loss_ft(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                         double flow_scale, unsigned long long *loss);
+int b2f_forward_loss_ft(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                        float **outs, int n_outs);
+int b2f_forward_loss_ft_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                               unsigned long long *dev_loss, void *stream);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -193,6 +204,7 @@ int b2f_multi_compute_flow_sequence_warp_past(b2f_multi *m, int T, int in_kind, 
                                               float *past_flow, float *occ_prob, unsigned char *fwd_occ,
                                               unsigned char *bwd_occ);
 int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
+int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
 ]]
 
 local lib = ffi.load(os.getenv('B2F_LIB') or 'libb2f.so')
