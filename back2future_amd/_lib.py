@@ -12,6 +12,15 @@ _lib = None
 
 c_float_p = C.POINTER(C.c_float)
 
+
+class LossGradOpts(C.Structure):
+    """b2f_loss_grad_opts of include/b2f.h: the option weights of opts.lua:61-73, the level weights of test.lua:29-31, sizeAverage"""
+    _fields_ = [("smooth_flow", C.c_double), ("const_vel", C.c_double), ("pme", C.c_double), ("smooth_occ", C.c_double),
+                ("prior_occ", C.c_double), ("level_weights", C.c_double * 7), ("size_average", C.c_int)]
+
+
+c_grad_opts_p = C.POINTER(LossGradOpts)
+
 # name -> (restype, argtypes); must list every symbol include/b2f.h declares
 SIGNATURES = {
     "b2f_last_error": (C.c_char_p, []),
@@ -177,6 +186,19 @@ SIGNATURES = {
                                    C.POINTER(c_float_p), C.c_int]),
     "b2f_forward_loss_ft_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "b2f_multi_forward_loss_ft": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong)]),
+    "b2f_loss_grad_defaults": (C.c_int, [c_grad_opts_p]),
+    "b2f_table_loss_grad_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double, c_grad_opts_p,
+                                           C.POINTER(c_float_p)]),
+    "b2f_table_loss_grad_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                             c_grad_opts_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "b2f_op_table_loss_grad": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double, c_grad_opts_p,
+                                         C.POINTER(c_float_p)]),
+    "b2f_forward_loss_grad": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_opts_p, C.POINTER(C.c_ulonglong),
+                                        C.POINTER(c_float_p), C.c_int, C.POINTER(c_float_p)]),
+    "b2f_forward_loss_grad_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_opts_p, C.c_void_p,
+                                               C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
+    "b2f_multi_forward_loss_grad": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_opts_p, C.POINTER(C.c_ulonglong),
+                                              C.POINTER(c_float_p), C.c_int]),
     "b2f_forward": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(c_float_p), C.c_int]),
     "b2f_output_shapes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.c_int]),

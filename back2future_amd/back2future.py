@@ -696,6 +696,69 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
             "loss": loss, "mean": float(loss.mean()), "nonfinite": nonf}
 
 
+def loss_grad_options(weights=None, size_average=False, objective=None):
+    """The options of the gradient table of train.lua:428-468 (a _lib.LossGradOpts, b2f_loss_grad_opts of include/b2f.h), from
+    b2f_loss_grad_defaults: the weights of opts.lua:61-73, the level weights of test.lua:29-31, sizeAverage off.  objective=NAME
+    applies the weights of LOSS_OBJECTIVES[NAME] first; only "Ours-Hard" is accepted: the two Soft models were fine-tuned with
+    SecondOrderSmoothnessCriterion and OBGCCriterion, whose gradients are not provided.  `weights` then replaces any of
+    "smooth_flow", "const_vel", "pme", "smooth_occ", "prior_occ" and, as "level_weights", the first level weights (at most 7).  A
+    weight of exactly 0 switches its term off (it is not evaluated); negative and non-finite weights are refused."""
+    o = _lib.LossGradOpts()
+    _lib.check(_lib.lib().b2f_loss_grad_defaults(C.byref(o)))
+    wt = {}
+    if objective is not None:
+        if objective not in LOSS_OBJECTIVES:
+            raise ValueError("loss_grad_options: unknown objective %r (one of %s)" % (objective, ", ".join(sorted(LOSS_OBJECTIVES))))
+        ob = LOSS_OBJECTIVES[objective]
+        if ob["smooth_second_order"] or ob["pme_criterion"] != "OBCC":
+            raise ValueError("loss_grad_options: the gradient of objective %r is not provided: it uses SecondOrderSmoothnessCriterion and "
+                             "OBGCCriterion, and only the gradients of the first-order pme objective (\"Ours-Hard\") are" % (objective,))
+        wt.update(ob["weights"])
+    wt.update(weights or {})
+    for k, v in wt.items():
+        if k == "level_weights":
+            v = [float(t) for t in v]
+            if len(v) > len(LOSS_LEVEL_WEIGHTS):
+                raise ValueError("loss_grad_options: at most %d level weights" % len(LOSS_LEVEL_WEIGHTS))
+            bad = [t for t in v if not (t >= 0.0 and np.isfinite(t))]
+            for j, t in enumerate(v):
+                o.level_weights[j] = t
+        elif k in LOSS_WEIGHTS:
+            bad = [] if (float(v) >= 0.0 and np.isfinite(float(v))) else [v]
+            setattr(o, k, float(v))
+        else:
+            raise ValueError("loss_grad_options: unknown weight %r" % (k,))
+        if bad:
+            raise ValueError("loss_grad_options: %s must be finite and >= 0, got %r" % (k, bad[0]))
+    o.size_average = 1 if size_average else 0
+    return o
+
+
+def _grad_opts_ptr(options):
+    if options is None:
+        return None
+    if not isinstance(options, _lib.LossGradOpts):
+        raise ValueError("expected the result of back2future.loss_grad_options (or None for the defaults)")
+    return C.byref(options)
+
+
+def _forward_loss_grad(fn, h, x, flow_scale, options, shapes, L, want_loss, want_table):
+    """x n x 9 x H x W normalized -> (gradient table, records or None, table or None): b2f_forward_loss_grad / b2f_multi_forward_loss_grad"""
+    x = _lib.f32(x)
+    if x.ndim != 4 or x.shape[1] != 9:
+        raise ValueError("forwardLossGrad: expected an n x 9 x H x W normalized input, got shape %r" % (x.shape,))
+    n, _, H, W = x.shape
+    sh = shapes(H, W)
+    grad = [np.empty((n, c, hh, ww), np.float32) for (c, hh, ww) in sh]
+    gp = (_lib.c_float_p * len(grad))(*[_lib.fptr(g) for g in grad])
+    loss = np.empty((n, L, LOSS_WORDS), np.uint64) if want_loss else None
+    lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong)) if want_loss else None
+    outs = [np.empty((n, c, hh, ww), np.float32) for (c, hh, ww) in sh] if want_table else None
+    op = (_lib.c_float_p * len(outs))(*[_lib.fptr(t) for t in outs]) if want_table else None
+    _lib.check(fn(h, _lib.fptr(x), n, H, W, float(flow_scale), _grad_opts_ptr(options), lp, gp, len(grad), op))
+    return grad, loss, outs
+
+
 def _forward_loss(fn, h, x, flow_scale, L, shapes, words=LOSS_WORDS):
     """x n x 9 x H x W normalized -> (records uint64 n x L x words, table or None): b2f_forward_loss* / b2f_multi_forward_loss*"""
     x = _lib.f32(x)
@@ -1041,6 +1104,37 @@ class Model(object):
         _lib.check(entry(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale), C.c_void_p(d_loss),
                          C.c_void_p(stream) if stream else None))
 
+    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, want_table=False):
+        """model:forward followed by `gradOutputs` of train.lua:428-468 (b2f_forward_loss_grad): x n x 9 x H x W, already normalized ->
+        the gradient of the pme objective with respect to every tensor of the output table, a list with the shapes of
+        Model.forward's, that of ops.table_loss_grad(self.forward(x), x[:, 3:6]); the table stays on the GPU.  options: of
+        loss_grad_options (None: the defaults).  want_loss=True returns (gradient, records) with the records of forwardLoss, from the
+        same pass; want_table=True appends the table of Model.forward, bit for bit."""
+        L = self.n_outputs // (5 if self.past_flow else 4)
+        grad, loss, outs = _forward_loss_grad(_lib.lib().b2f_forward_loss_grad, self._h, x, flow_scale, options, self.output_shapes, L,
+                                              want_loss, want_table)
+        if not want_loss and not want_table:
+            return grad
+        return (grad,) + ((loss,) if want_loss else ()) + ((outs,) if want_table else ())
+
+    def forwardLossGradDevice(self, d_in, n, H, W, d_grad, d_loss=None, flow_scale=20.0, options=None, stream=None):
+        """b2f_forward_loss_grad_device on device pointers (ints): d_in n x 9 x H x W normalized float32, d_grad the n_outputs tensors
+        of the gradient table (train.lua:428-468), d_loss n x L x 16 uint64 or None; asynchronous on `stream`."""
+        ptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad])
+        _lib.check(_lib.lib().b2f_forward_loss_grad_device(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale),
+                                                            _grad_opts_ptr(options), C.c_void_p(d_loss) if d_loss else None, ptrs, len(d_grad),
+                                                            C.c_void_p(stream) if stream else None))
+
+    def tableLossGradDevice(self, d_table, n, H, W, d_ref, d_grad, flow_scale=20.0, options=None, stream=None):
+        """b2f_table_loss_grad_device on device pointers (ints): d_table the L x 4 | 5 tensors of an output table in table order, d_ref
+        n x 3 x H x W, d_grad as many tensors of the same shapes (train.lua:428-468); asynchronous on `stream`."""
+        ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
+        gptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad])
+        if len(d_grad) != len(d_table):
+            raise ValueError("tableLossGradDevice: the gradient table must have the table's %d tensors" % len(d_table))
+        _lib.check(_lib.lib().b2f_table_loss_grad_device(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale),
+                                                          _grad_opts_ptr(options), gptrs, C.c_void_p(stream) if stream else None))
+
     def forward_device(self, d_in, B, H, W, d_flow=None, d_occ=None, d_est3=None, unit_input=False, stream=None, d_past_flow=None):
         """model:forward on device pointers (ints); asynchronous on `stream`.  d_past_flow (B x 2 x H x W float32, Soft models;
         b2f_forward_device_past): the network's past flow skip_ubfs[3]; the pruned pass then runs the past-flow decoders too."""
@@ -1164,6 +1258,21 @@ class MultiModel(object):
         lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
         return _forward_loss(entry, self._h, x, flow_scale, no.value // (5 if pf.value else 4), None, words)[0]
+
+    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True):
+        """Model.forwardLossGrad over the GPUs (b2f_multi_forward_loss_grad; train.lua:428-468): the same bits."""
+        c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
+        lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+        _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
+
+        def shapes(H, W):
+            ch, oh, ow = (C.c_int * 64)(), (C.c_int * 64)(), (C.c_int * 64)()
+            _lib.check(_lib.lib().b2f_output_shapes(c0, H, W, ch, oh, ow, 64))
+            return [(ch[i], oh[i], ow[i]) for i in range(no.value)]
+
+        fn = lambda h, xp, n, H, W, fsc, op, lp, gp, ng, outs: _lib.lib().b2f_multi_forward_loss_grad(h, xp, n, H, W, fsc, op, lp, gp, ng)
+        grad, loss, _ = _forward_loss_grad(fn, self._h, x, flow_scale, options, shapes, no.value // (5 if pf.value else 4), want_loss, False)
+        return (grad, loss) if want_loss else grad
 
 
 def shard_range(n, rank, world):

@@ -880,7 +880,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1006; }
+int b2f_version(void) { return 1007; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1411,6 +1411,7 @@ struct LossPlan {
     int L = 0, per = 0, n_outs = 0;
     int words = B2F_LOSS_WORDS;     // of a record: B2F_LOSS_FT_WORDS with the fine-tuning terms of README.md:89-102
     std::vector<size_t> cnt, off;   // floats and byte offset of every tensor of the table
+    std::vector<size_t> goff;       // byte offset of every tensor of the gradient table (b2f_forward_loss_grad only)
     size_t in_off = 0, loss_off = 0, bytes = 0;
 };
 
@@ -1426,7 +1427,7 @@ int check_forward_loss(const b2f_ctx *c, const std::string &w, int n, int H, int
     return 0;
 }
 
-LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input, bool ft)
+LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input, bool ft, bool with_grad = false)
 {
     LossPlan p;
     p.words = ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS;
@@ -1442,13 +1443,14 @@ LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input,
         p.off.push_back(take(p.cnt.back() * sizeof(float)));
     }
     p.loss_off = take((size_t)nb * p.L * p.words * sizeof(unsigned long long));
+    if (with_grad)
+        for (int i = 0; i < p.n_outs; ++i) p.goff.push_back(take(p.cnt[(size_t)i] * sizeof(float)));
     p.bytes = off;
     return p;
 }
 
-// the table of nb triplets into tab (device tensors in table order), then its records into d_loss; all on s
-int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const LossPlan &lp, float *const *tab,
-                     unsigned long long *d_loss)
+// the table of nb triplets into tab (device tensors in table order) on s
+int forward_table_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, const LossPlan &lp, float *const *tab)
 {
     if (c->g.shipped()) {
         const Plan P = make_plan(nb, H, W, true, c->past_flow);
@@ -1467,6 +1469,14 @@ int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H
     } else {
         CHK(graph_forward(c, s, false, d_in, B2F_IN_NORMALIZED, nb, H, W, tab));
     }
+    return 0;
+}
+
+// the table of nb triplets into tab, then its records into d_loss; all on s
+int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const LossPlan &lp, float *const *tab,
+                     unsigned long long *d_loss)
+{
+    CHK(forward_table_run(c, s, d_in, nb, H, W, lp, tab));
     CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(lp.L, nb, H, W) * sizeof(float)));
     ProfEvent pe;
     const bool timed = prof_open(c, s, "table_loss", &pe);
@@ -1481,6 +1491,32 @@ int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H
     if (timed_ft) prof_close(c, s, pf);
     HIPCHK(e);
     return 0;
+}
+
+// the table of nb triplets into tab, its records into d_loss where wanted, its gradient table (train.lua:428-468) into grad; all on s.
+// The pyramid of R is built once: by the records' launch where there is one.
+int forward_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const b2f_loss_grad_opts &o,
+                          const LossPlan &lp, float *const *tab, unsigned long long *d_loss, float *const *grad)
+{
+    if (d_loss) CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, lp, tab, d_loss));
+    else CHK(forward_table_run(c, s, d_in, nb, H, W, lp, tab));
+    const size_t hw = (size_t)H * W;
+    return table_loss_grad_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, o, d_loss == nullptr);
+}
+
+// what b2f_forward_loss_grad* check beyond check_forward_loss: the options (into *o) and the gradient table's pointers
+int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, const b2f_loss_grad_opts *opts, float *const *grad, int n_outs, b2f_loss_grad_opts *o)
+{
+    if (n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
+    for (int i = 0; i < n_outs; ++i) {
+        if (!grad[i]) return fail(w + ": null tensor in the gradient table");
+        for (int k = 0; k < i; ++k)
+            if (grad[i] == grad[k]) return fail(w + ": the gradient table must not alias itself");
+    }
+    if (opts) *o = *opts;
+    else (void)b2f_loss_grad_defaults(o);
+    const char *why = loss_grad_refusal(*o);
+    return why ? fail(w + ": " + why) : 0;
 }
 
 struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub-batches run (b2f_ctx::req_batch)
@@ -1530,7 +1566,93 @@ int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, in
     return 0;
 }
 
+// b2f_forward_loss_grad on a shard: `req` is the caller's n (b2f_multi_forward_loss_grad passes its own down)
+int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
+                                unsigned long long *loss, float *const *grad, int n_outs, float *const *outs)
+{
+    const std::string w("b2f_forward_loss_grad");
+    if (!c || !x || !grad) return fail(w + ": null argument");
+    CHK(check_forward_loss(c, w, n, H, W, flow_scale));
+    b2f_loss_grad_opts o;
+    CHK(check_forward_loss_grad(c, w, opts, grad, n_outs, &o));
+    for (int i = 0; outs && i < n_outs; ++i) {
+        if (!outs[i]) return fail(w + ": null tensor in outs");
+        for (int k = 0; k < n_outs; ++k)
+            if (outs[i] == grad[k]) return fail(w + ": the gradient table must not alias outs");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw = (size_t)H * W;
+    const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
+    const LossPlan lp = make_loss_plan(c, sb, H, W, true, false, true);
+    CHK(ensure_dev_work(c->loss_work, lp.bytes));
+    char *base = c->loss_work.dev;
+    std::vector<float *> tab((size_t)lp.n_outs), gr((size_t)lp.n_outs);
+    for (int i = 0; i < lp.n_outs; ++i) {
+        tab[(size_t)i] = (float *)(base + lp.off[(size_t)i]);
+        gr[(size_t)i] = (float *)(base + lp.goff[(size_t)i]);
+    }
+    float *d_in = (float *)(base + lp.in_off);
+    unsigned long long *d_loss = loss ? (unsigned long long *)(base + lp.loss_off) : nullptr;
+    ReqBatchScope rb(c, req > 0 ? req : n);
+    hipStream_t s = c->stream;
+    for (int b0 = 0; b0 < n; b0 += sb) {
+        const int nb = std::min(sb, n - b0);
+        HIPCHK(hipMemcpyAsync(d_in, x + (size_t)b0 * 9 * hw, (size_t)nb * 9 * hw * sizeof(float), hipMemcpyHostToDevice, s));
+        CHK(forward_loss_grad_run(c, s, d_in, nb, H, W, flow_scale, o, lp, tab.data(), d_loss, gr.data()));
+        if (loss)
+            HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * lp.words, d_loss, (size_t)nb * lp.L * lp.words * sizeof(unsigned long long),
+                                  hipMemcpyDeviceToHost, s));
+        for (int i = 0; i < n_outs; ++i) {
+            const size_t per_img = lp.cnt[(size_t)i] / (size_t)sb;
+            HIPCHK(hipMemcpyAsync(grad[i] + (size_t)b0 * per_img, gr[(size_t)i], (size_t)nb * per_img * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (outs) HIPCHK(hipMemcpyAsync(outs[i] + (size_t)b0 * per_img, tab[(size_t)i], (size_t)nb * per_img * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
 extern "C" {
+
+// model:forward + the gradient table of train.lua:428-468 from host memory
+int b2f_forward_loss_grad(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts, unsigned long long *loss,
+                          float *const *grad, int n_outs, float *const *outs) try
+{
+    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, opts, loss, grad, n_outs, outs);
+}
+B2F_CATCH("b2f_forward_loss_grad")
+
+// model:forward + the gradient table of train.lua:428-468 on device pointers
+int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
+                                 unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
+{
+    const std::string w(__func__);
+    if (!c || !dev_in || !dev_grad) return fail(w + ": null argument");
+    if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
+    CHK(check_forward_loss(c, w, n, H, W, flow_scale));
+    b2f_loss_grad_opts o;
+    CHK(check_forward_loss_grad(c, w, opts, dev_grad, n_outs, &o));
+    uintptr_t bits = (uintptr_t)dev_in | (uintptr_t)dev_loss;
+    for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_grad[i];
+    if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw = (size_t)H * W;
+    const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
+    const LossPlan lp = make_loss_plan(c, sb, H, W, false, false);
+    CHK(ensure_dev_work(c->loss_work, lp.bytes));
+    std::vector<float *> tab((size_t)lp.n_outs), gr((size_t)lp.n_outs);
+    for (int i = 0; i < lp.n_outs; ++i) tab[(size_t)i] = (float *)(c->loss_work.dev + lp.off[(size_t)i]);
+    ReqBatchScope rb(c, n);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    for (int b0 = 0; b0 < n; b0 += sb) {
+        // the sub-batch's part of the caller's gradient tensors: image b0 of every one
+        for (int i = 0; i < lp.n_outs; ++i) gr[(size_t)i] = dev_grad[i] + (size_t)b0 * (lp.cnt[(size_t)i] / (size_t)sb);
+        CHK(forward_loss_grad_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, o, lp, tab.data(),
+                                  dev_loss ? dev_loss + (size_t)b0 * lp.L * lp.words : nullptr, gr.data()));
+    }
+    return 0;
+}
+B2F_CATCH("b2f_forward_loss_grad_device")
 
 // model:forward + test.lua:266-297 from host memory
 int b2f_forward_loss(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try

@@ -6,6 +6,7 @@
 #include "b2f_flowscore.h"
 #include "b2f_flowwarp.h"
 #include "b2f_tableloss.h"
+#include "b2f_tableloss_grad.h"
 #include "b2f_tableloss_ft.h"
 #include "../../include/b2f.h"
 
@@ -428,6 +429,118 @@ const char *table_loss_refusal(int n_outs, int per, int n, int H, int W, double 
     if (!(flow_scale > 0.0) || !std::isfinite(flow_scale)) return "flow_scale must be finite and > 0";
     *L = lv;
     return nullptr;
+}
+
+}  // namespace b2f
+
+// ---- the gradient of the pme objective with respect to the output table on the CPU (train.lua:428-468) ------------------------------
+namespace b2f {
+
+const char *loss_grad_refusal(const b2f_loss_grad_opts &o)
+{
+    const double wt[5] = {o.smooth_flow, o.const_vel, o.pme, o.smooth_occ, o.prior_occ};
+    for (double v : wt)
+        if (!(v >= 0.0) || !std::isfinite(v)) return "the weights of b2f_loss_grad_opts must be finite and >= 0";
+    for (double v : o.level_weights)
+        if (!(v >= 0.0) || !std::isfinite(v)) return "the level weights of b2f_loss_grad_opts must be finite and >= 0";
+    return nullptr;
+}
+
+void loss_grad_coef(const b2f_loss_grad_opts &o, int j, int h, int w, GradCoef *k)
+{
+    const double c = o.level_weights[j];
+    const double n2 = o.size_average ? 1.0 / ((2.0 * (double)h) * (double)w) : 1.0, n1 = o.size_average ? 1.0 / ((double)h * (double)w) : 1.0;
+    k->k_s = (c * o.smooth_flow) * n2;
+    k->k_cv = (c * o.const_vel) * n1;
+    k->k_p = ((c * o.pme) * n1) / 6.0;
+    k->k_so = (c * o.smooth_occ) * n2;
+    k->k_pr = (c * o.prior_occ) * n1;
+    k->on = (o.smooth_flow != 0.0 ? kGradSmooth : 0u) | (o.const_vel != 0.0 ? kGradConstVel : 0u) | (o.pme != 0.0 ? kGradPhoto : 0u) |
+            (o.smooth_occ != 0.0 ? kGradSmoothOcc : 0u) | (o.prior_occ != 0.0 ? kGradPrior : 0u);
+}
+
+void table_loss_grad_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                          const b2f_loss_grad_opts &opts, float *const *grad)
+{
+    const int per = past ? 5 : 4;
+    std::vector<float> cur, next;
+    for (int b = 0; b < n; ++b) {
+        const float *R = ref + (size_t)b * 3 * H * W;
+        for (int j = 0; j < L; ++j) {
+            const int h = H >> j, w = W >> j;
+            const size_t hw = (size_t)h * w;
+            if (j > 0) {   // R_j as in table_loss_host
+                const int hp = H >> (j - 1), wp = W >> (j - 1);
+                next.resize(3 * hw);
+                for (int c = 0; c < 3; ++c)
+                    for (int y = 0; y < h; ++y)
+                        for (int x = 0; x < w; ++x) {
+                            const float *q = R + ((size_t)c * hp + 2 * y) * wp + 2 * x;
+                            next[((size_t)c * h + y) * w + x] = (((q[0] + q[1]) + q[wp]) + q[wp + 1]) / 4.0f;
+                        }
+                cur.swap(next);
+                R = cur.data();
+            }
+            GradCoef k;
+            loss_grad_coef(opts, j, h, w, &k);
+            const bool want_w = (k.on & (kGradSmooth | kGradSmoothOcc)) != 0;
+            const float *const *t = table + (size_t)j * per;
+            float *const *g = grad + (size_t)j * per;
+            const float *f = t[0] + (size_t)b * 2 * hw, *p = past ? t[1] + (size_t)b * 2 * hw : nullptr, *o = t[per - 3] + (size_t)b * 2 * hw;
+            const float *iw[2] = {t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
+            float *gf = g[0] + (size_t)b * 2 * hw, *gp = past ? g[1] + (size_t)b * 2 * hw : nullptr, *go = g[per - 3] + (size_t)b * 2 * hw;
+            float *giw[2] = {g[per - 2] + (size_t)b * 3 * hw, g[per - 1] + (size_t)b * 3 * hw};
+            const float kd = (float)(flow_scale / (double)(1 << j));
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    const size_t i = (size_t)y * w + x;
+                    const bool has_l = x > 0, has_r = x + 1 < w, has_u = y > 0, has_d = y + 1 < h;
+                    // the offsets of the four neighbours; a missing one is not read (its pair has no term)
+                    const size_t il = has_l ? i - 1 : i, ir = has_r ? i + 1 : i, iu = has_u ? i - w : i, id = has_d ? i + w : i;
+                    double wxc = 1.0, wxl = 1.0, wyc = 1.0, wyu = 1.0;
+                    if (want_w) {
+                        const float *R0 = R, *R1 = R + hw, *R2 = R + 2 * hw;
+                        wxc = grad_weight(has_r, R0[i], R0[ir], R1[i], R1[ir], R2[i], R2[ir]);
+                        wxl = grad_weight(has_l, R0[il], R0[i], R1[il], R1[i], R2[il], R2[i]);
+                        wyc = grad_weight(has_d, R0[i], R0[id], R1[i], R1[id], R2[i], R2[id]);
+                        wyu = grad_weight(has_u, R0[iu], R0[i], R1[iu], R1[i], R2[iu], R2[i]);
+                    }
+                    auto S1 = [&](const float *q) {
+                        return grad_s(grad_edge<false>(has_r, q[i], q[ir], wxc), grad_edge<false>(has_l, q[il], q[i], wxl),
+                                      grad_edge<false>(has_d, q[i], q[id], wyc), grad_edge<false>(has_u, q[iu], q[i], wyu));
+                    };
+                    auto S2 = [&](const float *q) {
+                        return grad_s(grad_edge<true>(has_r, q[i], q[ir], wxc), grad_edge<true>(has_l, q[il], q[i], wxl),
+                                      grad_edge<true>(has_d, q[i], q[id], wyc), grad_edge<true>(has_u, q[iu], q[i], wyu));
+                    };
+                    double cv[2] = {0.0, 0.0};
+                    if (past && (k.on & kGradConstVel)) grad_const_vel(f[i], f[hw + i], p[i], p[hw + i], cv);
+                    for (int c = 0; c < 2; ++c) {
+                        const double sf = (k.on & kGradSmooth) ? S1(f + c * hw) : 0.0;
+                        gf[c * hw + i] = grad_flow(k, sf, cv[c], past, false);
+                        if (past) {
+                            const double sp = (k.on & kGradSmooth) ? S1(p + c * hw) : 0.0;
+                            gp[c * hw + i] = grad_flow(k, sp, cv[c], true, true);
+                        }
+                    }
+                    double po[2] = {0.0, 0.0};   // po[c] = PO_c: direction d fills channel 1 - d
+                    for (int d = 0; d < 2; ++d) {
+                        float gi[3] = {0.0f, 0.0f, 0.0f};
+                        if (k.on & kGradPhoto) {
+                            const bool pf = d == 0 && past;   // OBCCriterion.lua:166-170
+                            const WarpTaps tp = warp_taps(pf ? p[i] : f[i], pf ? p[hw + i] : f[hw + i], d == 0 ? -kd : kd, x, y, w, h);
+                            const float w3[3] = {iw[d][i], iw[d][hw + i], iw[d][2 * hw + i]}, r3[3] = {R[i], R[hw + i], R[2 * hw + i]};
+                            grad_photo(k, tp.inside, w3, r3, o[(size_t)(1 - d) * hw + i], &po[1 - d], gi);
+                        }
+                        for (int c = 0; c < 3; ++c) giw[d][c * hw + i] = gi[c];
+                    }
+                    for (int c = 0; c < 2; ++c) {
+                        const double so = (k.on & kGradSmoothOcc) ? S2(o + c * hw) : 0.0;
+                        go[c * hw + i] = grad_occ(k, po[c], so, o[(size_t)(1 - c) * hw + i]);
+                    }
+                }
+        }
+    }
 }
 
 }  // namespace b2f

@@ -91,6 +91,18 @@ void table_loss_ft_host(const float *const *table, int L, bool past, int n, int 
                         unsigned long long *loss);
 // the argument checks every table-loss entry shares (test.lua:266-297; no HIP call): nullptr and *L = n_outs / per, or why not
 const char *table_loss_refusal(int n_outs, int per, int n, int H, int W, double flow_scale, int *L);
+}  // namespace b2f
+struct b2f_loss_grad_opts;
+namespace b2f {
+struct GradCoef;
+// The gradient of the pme objective with respect to the output table on the CPU (train.lua:428-468; b2f_tableloss_grad.h per element;
+// b2f_table_loss_grad_host): grad = the table's L x (4 | 5) tensors, every element written
+void table_loss_grad_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                          const b2f_loss_grad_opts &opts, float *const *grad);
+// nullptr, or why the options are refused (a negative or non-finite weight)
+const char *loss_grad_refusal(const b2f_loss_grad_opts &o);
+// the coefficients of level j of h x w (include/b2f.h: k_s .. k_pr) and which terms are evaluated
+void loss_grad_coef(const b2f_loss_grad_opts &o, int j, int h, int w, GradCoef *k);
 
 // .t7 reader (b2f_t7.cpp): returns false and fills err on failure.
 bool load_t7(const std::string &path, std::vector<float> &flat, bool &past_flow, std::string &err);

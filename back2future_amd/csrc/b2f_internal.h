@@ -372,5 +372,13 @@ hipError_t launch_table_loss(const float *const *table, int L, bool past, int n,
 // that call zeroes the records and lays R_1 .. R_{L-1} into pyr, which this one reads
 hipError_t launch_table_loss_ft_terms(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
                                       const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s);
+// b2f_tableloss.hip: R_1 .. R_{L-1} alone, laid out in pyr as launch_table_loss lays them (for a caller that wants no records)
+hipError_t launch_table_loss_pyramid(int L, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr, hipStream_t s);
+// b2f_tableloss_grad.hip: the gradient table of train.lua:428-468 (include/b2f.h: G_f, G_p, G_o, G_iw_d) behind either of the two on the
+// same stream: grad = L x (4 | 5) device tensors of n images with the table's shapes (a host array), none of them a tensor of the table
+// or ref; coef[j]: the coefficients of level j (b2f_host.h: loss_grad_coef).  Every element of grad is written.
+struct GradCoef;
+hipError_t launch_table_loss_grad(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
+                                  const float *pyr, double flow_scale, const GradCoef *coef, hipStream_t s);
 
 }  // namespace b2f

@@ -433,4 +433,28 @@ int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H, int W,
 }
 B2F_CATCH("b2f_multi_forward_loss_ft")
 
+// the gradient table of train.lua:428-468 behind model:forward over several GPUs
+int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
+                                unsigned long long *loss, float *const *grad, int n_outs) try
+{
+    if (!m) return api_fail("b2f_multi_forward_loss_grad: null context");
+    if (!x || !grad || n <= 0 || H <= 0 || W <= 0) return api_fail("b2f_multi_forward_loss_grad: bad arguments");
+    const b2f_ctx *c0 = m->ctx[0];
+    if (n_outs != c0->g.n_outputs()) return api_fail("b2f_multi_forward_loss_grad: n_outs must be the contexts' n_outputs");
+    const int per = c0->past_flow ? 5 : 4;
+    const size_t rec = (size_t)(n_outs / per) * B2F_LOSS_WORDS;
+    for (int i = 0; i < n_outs; ++i)
+        if (!grad[i]) return api_fail("b2f_multi_forward_loss_grad: null tensor in the gradient table");
+    return run_sharded(m, n, [&](int i, int lo, int hi) {
+        std::vector<float *> g((size_t)n_outs);   // the shard's part of every tensor: image lo
+        for (int t = 0; t < n_outs; ++t) {
+            const int j = t / per, ch = (t % per) >= per - 2 ? 3 : 2;
+            g[(size_t)t] = grad[t] + (size_t)lo * ch * (H >> j) * (W >> j);
+        }
+        return forward_loss_grad_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, opts, loss ? loss + (size_t)lo * rec : nullptr,
+                                      g.data(), n_outs, nullptr);
+    });
+}
+B2F_CATCH("b2f_multi_forward_loss_grad")
+
 }  // extern "C"

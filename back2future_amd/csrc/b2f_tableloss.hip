@@ -7,6 +7,7 @@
 // of the context.
 #include "b2f_ctx.h"
 #include "b2f_tableloss.h"
+#include "b2f_tableloss_grad.h"
 #include "b2f_tableloss_dev.h"
 
 using namespace b2f;
@@ -196,6 +197,28 @@ hipError_t launch_table_loss(const float *const *table, int L, bool past, int n,
     return hipSuccess;
 }
 
+// R_1 .. R_{L-1} alone, laid out in pyr as launch_table_loss lays them (for a caller that wants no records)
+hipError_t launch_table_loss_pyramid(int L, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr, hipStream_t s)
+{
+    if (n <= 0 || L < 1 || L > kLossMaxLevels || H <= 0 || W <= 0 || H % (1 << (L - 1)) || W % (1 << (L - 1)) || !ref || (L > 1 && !pyr) ||
+        ref_stride < (size_t)3 * H * W)
+        return hipErrorInvalidValue;
+    const float *R = ref;
+    size_t R_stride = ref_stride;
+    for (int j = 1; j < L; ++j) {
+        const int h = H >> j, w = W >> j;
+        const size_t total = (size_t)n * 3 * h * w;
+        hipLaunchKernelGGL(ref_pool_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, R, R_stride, 2 * h, 2 * w, total,
+                           pyr);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        R = pyr;
+        R_stride = (size_t)3 * h * w;
+        pyr += (total + 3) & ~(size_t)3;
+    }
+    return hipSuccess;
+}
+
 int ensure_dev_work(DevWork &dw, size_t bytes)
 {
     if (bytes > dw.bytes) {
@@ -314,9 +337,147 @@ int op_table_loss(const std::string &w, bool ft, b2f_ctx *c, const float *const 
     return 0;
 }
 
+// ---- the gradient table of train.lua:428-468 (b2f_tableloss_grad.hip) ----
+// opts or the defaults into *o, refused where a weight is negative or not finite
+int resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts, b2f_loss_grad_opts *o)
+{
+    if (opts) *o = *opts;
+    else (void)b2f_loss_grad_defaults(o);
+    const char *why = loss_grad_refusal(*o);
+    return why ? fail(w + ": " + why) : 0;
+}
+
+// grad: n_outs tensors, none null, none a tensor of the table, ref or another one of grad
+int check_grad_table(const std::string &w, const float *const *table, int n_outs, const float *ref, float *const *grad)
+{
+    if (!grad) return fail(w + ": null argument");
+    for (int i = 0; i < n_outs; ++i) {
+        if (!grad[i]) return fail(w + ": null tensor in the gradient table");
+        if (grad[i] == ref) return fail(w + ": the gradient table must not alias ref");
+        for (int k = 0; k < n_outs; ++k)
+            if ((table && grad[i] == table[k]) || (k != i && grad[i] == grad[k])) return fail(w + ": the gradient table must not alias the table or itself");
+    }
+    return 0;
+}
+
+}  // namespace
+
+// b2f_table_loss_grad_device on checked options; with_pyr: build R_1 .. R_{L-1} first (false: launch_table_loss has)
+int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
+                             const float *dev_ref, size_t ref_stride, double flow_scale, const b2f_loss_grad_opts &o, bool with_pyr)
+{
+    GradCoef coef[kLossMaxLevels];
+    for (int j = 0; j < L; ++j) loss_grad_coef(o, j, H >> j, W >> j, &coef[j]);
+    CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
+    if (with_pyr) HIPCHK(launch_table_loss_pyramid(L, n, H, W, dev_ref, ref_stride, (float *)c->loss_pyr.dev, s));
+    ProfEvent pe;
+    const bool timed = prof_open(c, s, "table_loss_grad", &pe);
+    const hipError_t e = launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, (const float *)c->loss_pyr.dev, flow_scale, coef, s);
+    if (timed) prof_close(c, s, pe);
+    HIPCHK(e);
+    return 0;
+}
+
+namespace {
+
+int table_loss_grad_device(const std::string &w, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                           double flow_scale, const b2f_loss_grad_opts *opts, float *const *dev_grad, void *stream)
+{
+    if (!c) return fail(w + ": null context");
+    const int per = level_size(c, n_outs);
+    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
+    int L = 0;
+    CHK(check_table_loss(w, dev_table, n_outs, per, n, H, W, dev_ref, flow_scale, dev_grad, &L));
+    CHK(check_grad_table(w, dev_table, n_outs, dev_ref, dev_grad));
+    b2f_loss_grad_opts o;
+    CHK(resolve_grad_opts(w, opts, &o));
+    if (n > 65535) return fail(w + ": at most 65535 images per call");
+    uintptr_t bits = (uintptr_t)dev_ref;
+    for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i] | (uintptr_t)dev_grad[i];
+    if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
+    HIPCHK(hipSetDevice(c->device));
+    if (host_memory(dev_ref)) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss_grad / b2f_table_loss_grad_host)");
+    for (int i = 0; i < n_outs; ++i)
+        if (host_memory(dev_table[i]) || host_memory(dev_grad[i]))
+            return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss_grad / b2f_table_loss_grad_host)");
+    return table_loss_grad_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, dev_grad, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, flow_scale,
+                               o, true);
+}
+
 }  // namespace
 
 extern "C" {
+
+// opts.lua:61-73, test.lua:29-31
+int b2f_loss_grad_defaults(b2f_loss_grad_opts *o)
+{
+    if (!o) return fail("b2f_loss_grad_defaults: null argument");
+    const double lw[kLossMaxLevels] = {0.005, 0.01, 0.02, 0.08, 0.32, 0.64, 1.28};
+    o->smooth_flow = 1.0; o->const_vel = 1.0; o->pme = 1.0; o->smooth_occ = 0.1; o->prior_occ = 0.1;
+    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = lw[j];
+    o->size_average = 0;
+    return 0;
+}
+
+// train.lua:428-468 on the CPU
+int b2f_table_loss_grad_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                             const b2f_loss_grad_opts *opts, float *const *grad) try
+{
+    const std::string w(__func__);
+    int L = 0;
+    CHK(check_table_loss(w, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, grad, &L));
+    CHK(check_grad_table(w, table, n_outs, ref, grad));
+    b2f_loss_grad_opts o;
+    CHK(resolve_grad_opts(w, opts, &o));
+    table_loss_grad_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o, grad);
+    return 0;
+}
+B2F_CATCH("b2f_table_loss_grad_host")
+
+// train.lua:428-468 on device pointers
+int b2f_table_loss_grad_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                               const b2f_loss_grad_opts *opts, float *const *dev_grad, void *stream) try
+{
+    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, opts, dev_grad, stream);
+}
+B2F_CATCH("b2f_table_loss_grad_device")
+
+// train.lua:428-468 on host pointers through the GPU
+int b2f_op_table_loss_grad(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                           const b2f_loss_grad_opts *opts, float *const *grad) try
+{
+    const std::string w(__func__);
+    if (!c) return fail(w + ": null context");
+    const int per = level_size(c, n_outs);
+    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
+    int L = 0;
+    CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, grad, &L));
+    CHK(check_grad_table(w, table, n_outs, ref, grad));
+    b2f_loss_grad_opts o;
+    CHK(resolve_grad_opts(w, opts, &o));
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<DevBytes> dt((size_t)n_outs), dg((size_t)n_outs);
+    std::vector<const float *> ptrs((size_t)n_outs);
+    std::vector<float *> gptrs((size_t)n_outs);
+    std::vector<size_t> bytes((size_t)n_outs);
+    DevBytes dr;
+    for (int i = 0; i < n_outs; ++i) {
+        const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
+        bytes[(size_t)i] = (size_t)n * ch * (H >> j) * (W >> j) * sizeof(float);
+        HIPCHK(hipMalloc(&dt[(size_t)i].p, bytes[(size_t)i]));
+        HIPCHK(hipMemcpy(dt[(size_t)i].p, table[i], bytes[(size_t)i], hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&dg[(size_t)i].p, bytes[(size_t)i]));
+        ptrs[(size_t)i] = (const float *)dt[(size_t)i].p;
+        gptrs[(size_t)i] = (float *)dg[(size_t)i].p;
+    }
+    HIPCHK(hipMalloc(&dr.p, (size_t)n * 3 * H * W * sizeof(float)));
+    HIPCHK(hipMemcpy(dr.p, ref, (size_t)n * 3 * H * W * sizeof(float), hipMemcpyHostToDevice));
+    CHK(table_loss_grad_device(w, c, ptrs.data(), n_outs, n, H, W, (const float *)dr.p, flow_scale, &o, gptrs.data(), nullptr));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n_outs; ++i) HIPCHK(hipMemcpy(grad[i], gptrs[(size_t)i], bytes[(size_t)i], hipMemcpyDeviceToHost));
+    return 0;
+}
+B2F_CATCH("b2f_op_table_loss_grad")
 
 // test.lua:266-297 on the CPU
 int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,

@@ -281,3 +281,38 @@ def table_loss(table, ref, flow_scale=20.0, model=None, objective="pme"):
                              "table's kind or model=None" % ("Soft" if per == 5 else "Hard", len(tab), "Soft" if model.past_flow else "Hard"))
         _lib.check(getattr(_lib.lib(), "b2f_op_table_loss" + ft)(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), lp))
     return loss
+
+
+def table_loss_grad(table, ref, flow_scale=20.0, options=None, model=None):
+    """`gradOutputs` of train.lua:428-468 for an output table of model:forward: the gradient of the -optimize pme objective
+    (first-order smoothness with L1, constant velocity, OBCC with L1, occlusion smoothness, occlusion prior; include/b2f.h gives every
+    element) with respect to each tensor of the table.  table, ref, model as for table_loss; options: of
+    back2future.loss_grad_options (None: the defaults of opts.lua:61-73) -> a list of float32 arrays with the table's shapes.
+    model=None computes on the CPU (b2f_table_loss_grad_host), a Model on its GPU (b2f_op_table_loss_grad): the bits are the same."""
+    from .back2future import _grad_opts_ptr
+    r = np.asarray(ref)
+    if r.ndim != 4 or r.shape[1] != 3 or min(r.shape) < 1:
+        raise ValueError("table_loss_grad: expected an n x 3 x H x W reference image, got shape %r" % (np.shape(ref),))
+    r = _lib.f32(r)
+    n, _, H, W = r.shape
+    tab = [_lib.f32(t) for t in table]
+    if not tab or any(t.ndim != 4 or t.shape[0] != n for t in tab):
+        raise ValueError("table_loss_grad: the table must be a non-empty list of n x C x h x w arrays with the reference's n")
+    per = 5 if (len(tab) >= 5 and tab[1].shape[1] == 2 and tab[2].shape[1] == 2) else 4
+    if len(tab) % per:
+        raise ValueError("table_loss_grad: %d tensors are no whole number of levels of %d" % (len(tab), per))
+    for i, t in enumerate(tab):
+        want = (n, 3 if i % per >= per - 2 else 2, H >> (i // per), W >> (i // per))
+        if t.shape != want:
+            raise ValueError("table_loss_grad: tensor %d of the table must have shape %r, got %r" % (i, want, t.shape))
+    ptrs = (_lib.c_float_p * len(tab))(*[_lib.fptr(t) for t in tab])
+    grad = [np.empty(t.shape, np.float32) for t in tab]
+    gp = (_lib.c_float_p * len(grad))(*[_lib.fptr(g) for g in grad])
+    if model is None:
+        _lib.check(_lib.lib().b2f_table_loss_grad_host(ptrs, len(tab), n, H, W, int(per == 5), _lib.fptr(r), float(flow_scale), _grad_opts_ptr(options), gp))
+    else:
+        if per != (5 if model.past_flow else 4) and len(tab) % (5 if model.past_flow else 4) == 0:
+            raise ValueError("table_loss_grad: a %s table of %d tensors on a %s model would be read as the model's kind; use a model of the "
+                             "table's kind or model=None" % ("Soft" if per == 5 else "Hard", len(tab), "Soft" if model.past_flow else "Hard"))
+        _lib.check(_lib.lib().b2f_op_table_loss_grad(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), _grad_opts_ptr(options), gp))
+    return grad

@@ -6,11 +6,16 @@ the occlusion prior, on every level of the output table.  No ground truth is nee
 (Model.forwardLoss); 128 bytes per level and centre frame come back.  --objective NAME prints instead the objective the named model
 was trained on (back2future.LOSS_OBJECTIVES, the commands of the reference's README.md:85-102): for the two Soft models the
 second-order smoothness and the brightness and gradient constancy of OBGCC, from records of 192 bytes (objective="finetune").
+--grad also computes `gradOutputs` of train.lua:428-468, the gradient of the pme objective with respect to every tensor of the output
+table (Model.forwardLossGrad, in the same pass as the records), under the chosen options (--size-average; --objective Ours-Hard --
+the gradients of the two Soft objectives are not provided), and prints per level and tensor its L2 norm and largest magnitude over
+the clip.
 
-Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME]
+Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME] [--grad]
 FRAMES_DIR: 8-bit frames, sorted by name; they are cropped (top left) to multiples of 64 and normalized with
 back2future.normalize.  MODEL as for examples/run_sequence.py.  --scale: pixels per unit of raw network flow (default 20).
-Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`.
+Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`; with --grad then one line
+`grad LEVEL TENSOR l2 max` per level and tensor (f, p for Soft models, o, iw1, iw3).
 """
 import os
 import sys
@@ -34,8 +39,8 @@ def load_unit(path, H, W):
 def main():
     args = list(sys.argv[1:])
     scale, like, objective = 20.0, "test", None
-    size_average = "--size-average" in args
-    args = [a for a in args if a != "--size-average"]
+    size_average, grad = "--size-average" in args, "--grad" in args
+    args = [a for a in args if a not in ("--size-average", "--grad")]
     for flag in ("--scale", "--like", "--objective"):
         if flag in args:
             i = args.index(flag)
@@ -53,6 +58,12 @@ def main():
         sys.exit(__doc__)
     if objective is not None and objective not in back2future.LOSS_OBJECTIVES:
         sys.exit("--objective: one of " + ", ".join(sorted(back2future.LOSS_OBJECTIVES)))
+    options = None
+    if grad:
+        try:
+            options = back2future.loss_grad_options(size_average=size_average, objective=objective)
+        except ValueError as e:
+            sys.exit("--grad: %s" % e)
     src, model = args
     names = sorted(f for f in os.listdir(src) if f.lower().endswith(EXTS))
     if len(names) < 3:
@@ -64,16 +75,28 @@ def main():
         sys.exit("%s: frames of %d x %d are smaller than 64 x 64" % (src, H0, W0))
     frames = [back2future.normalize(load_unit(os.path.join(src, f), H, W)) for f in names]
     m = back2future.Model(model)
-    records = []
+    records, sumsq, largest = [], None, None
     for b0 in range(0, len(frames) - 2, BATCH):
         x = np.stack([np.concatenate(frames[i:i + 3], axis=0) for i in range(b0, min(b0 + BATCH, len(frames) - 2))])
-        records.append(m.forwardLoss(x, flow_scale=scale, objective="pme" if objective is None else "finetune"))
+        if grad:
+            g, rec = m.forwardLossGrad(x, flow_scale=scale, options=options)
+            records.append(rec)
+            sq = [float((t.astype(np.float64) ** 2).sum()) for t in g]
+            mx = [float(np.abs(t).max()) for t in g]
+            sumsq = sq if sumsq is None else [a + b for a, b in zip(sumsq, sq)]
+            largest = mx if largest is None else [max(a, b) if a == a and b == b else float("nan") for a, b in zip(largest, mx)]
+        else:
+            records.append(m.forwardLoss(x, flow_scale=scale, objective="pme" if objective is None else "finetune"))
+    tensors = ("f", "p", "o", "iw1", "iw3") if m.past_flow else ("f", "o", "iw1", "iw3")
     m.close()
     s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, objective=objective)
     for f, v in zip(names[1:-1], s["loss"]):
         print("%s %r" % (os.path.splitext(f)[0], float(v)))
     print("mean %r" % s["mean"])
     print("nonfinite %d" % s["nonfinite"])
+    if grad:
+        for i, (sq, mx) in enumerate(zip(sumsq, largest)):
+            print("grad %d %s %r %r" % (i // len(tensors), tensors[i % len(tensors)], float(np.sqrt(sq)), mx))
 
 
 if __name__ == "__main__":

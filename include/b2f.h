@@ -598,6 +598,72 @@ B2F_API int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H
 #define B2F_LOSS_FT_SMOOTH2_NONFINITE 22  /* pixels with a NaN second-order term */
 #define B2F_LOSS_FT_GRAD_NONFINITE 23     /* pixel-directions of PHOTO_INSIDE with a NaN gradient term */
 #define B2F_LOSS_FT_WORDS 24
+/* ---- the gradient of the pme objective with respect to the output table: `gradOutputs` of train.lua:279-472 ----
+ * What the fine-tuning commands of README.md:85-102 hand to model:backward: a table with the shapes of the output table, into which
+ * every criterion's backward, times its option weight and level_weights[l], is added (train.lua:428-468).  The scope is -optimize
+ * pme with the defaults of opts.lua: SmoothnessCriterion with the L1 penalty for the flows and the quadratic one for the
+ * occlusions, ConstVelCriterion, OBCCriterion with L1, OcclusionPriorCriterion -- the objective of Ours-Hard.  The gradients of
+ * SecondOrderSmoothnessCriterion and OBGCCriterion (the *_ft entries' two criteria) are not provided.
+ * The specification is the reference's updateGradInput functions, not the mathematical derivative of their outputs; they differ in
+ * three places, all kept:
+ *   1. OcclusionPriorCriterion.lua:64-65 returns 1 - o[other]; the derivative of 1 - o0 * o1 is -o[other].  The value is larger by
+ *      the constant k_pr on both channels, which the softmax below the occlusions cancels.
+ *   2. OBCCriterion.lua:181-182,210-211: a pixel-direction whose target leaves the image adds penalty_out = 1 to the occlusion
+ *      gradient of channel 1 - d; the forward value has a constant there.
+ *   3. ConstVelCriterion.lua:69-70 divides the gradient by h w with sizeAverage, line 33 the output by 2 h w.
+ * Inputs, R_j, dx, dy, wx, wy, E, P1 and the direction's target (`inside` of b2f_flow_warp's coordinate, fp32; a NaN coordinate is
+ * not inside, as Lua's comparisons decide) are those of the loss records above; all other arithmetic is fp64 without fused
+ * multiply-adds.  With D1(v) = v / sqrt(v * v + 1e-6), D2(v) = 2.0 * v, per level j of h x w and c_j = level_weights[j]:
+ *   a(F,D)(x,y) = D(dx(F)(x,y)) * wx(x,y) where x + 1 < w, otherwise exactly 0 (no multiplication by a weight); b the same over rows
+ *   S(F,D)(x,y) = (((-a(x,y)) + a(x-1,y)) - b(x,y)) + b(x,y-1), a term with x - 1 < 0 or y - 1 < 0 being 0
+ *   d_c = (double)f[c] - (double)p[c], CV_c = d_c / (sqrt(d0 * d0 + d1 * d1) + 1e-12)
+ *   direction d (0: iw1, the target on the past flow of a Soft table, weight o[1]; 1: iw3, weight o[0]): m_d = inside,
+ *   delta_c = (double)iw_d[c] - (double)R_j[c], e_d = (P1(delta_0) + P1(delta_1)) + P1(delta_2), PO_{1-d} = m_d ? e_d : 1.0
+ *   k_s = (c_j * smooth_flow) * N2, k_cv = (c_j * const_vel) * N1, k_p = ((c_j * pme) * N1) / 6.0, k_so = (c_j * smooth_occ) * N2,
+ *   k_pr = (c_j * prior_occ) * N1; N2 = 1.0 / ((2.0 * h) * w) and N1 = 1.0 / ((double)h * w) with size_average (per triplet, as
+ *   back2future.loss_summary(size_average=True) counts), otherwise 1
+ *   G_f[c]    = k_s * S(f[c],D1) + k_cv * CV_c                       (the second term on Soft tables only)
+ *   G_p[c]    = k_s * S(p[c],D1) - k_cv * CV_c                       (Soft tables only)
+ *   G_o[c]    = (k_p * PO_c + k_so * S(o[c],D2)) + k_pr * (1.0 - (double)o[1-c])
+ *   G_iw_d[c] = m_d ? k_p * (D1(delta_c) * (double)o[1-d]) : +0.0
+ * A term whose option weight is exactly 0 is not evaluated and adds nothing (train.lua:458,465 do this for the two occlusion terms;
+ * here all five): the remaining terms are added left to right, an element without one is +0.0.  Everything else follows IEEE: a
+ * NaN input gives NaN in the elements that read it.  Every element is summed in fp64 and rounded to fp32 once, on store, so the
+ * host entry and the kernel give the same bits; the reference accumulates in fp32 and rounds after every add.
+ * The gradient table has the output table's n_outs tensors and shapes; it must not alias the table or ref.                      */
+typedef struct b2f_loss_grad_opts {
+    double smooth_flow, const_vel, pme, smooth_occ, prior_occ;   /* opts.lua:61-73; each finite and >= 0 */
+    double level_weights[7];                                     /* test.lua:29-31; each finite and >= 0 */
+    int size_average;                                            /* the criteria's sizeAverage, per triplet */
+} b2f_loss_grad_opts;
+/* opts.lua:61-73 (1, 1, 1, 0.1, 0.1), test.lua:29-31 (0.005, 0.01, 0.02, 0.08, 0.32, 0.64, 1.28), size_average = 0 */
+B2F_API int b2f_loss_grad_defaults(b2f_loss_grad_opts *opts);
+/* host only, no GPU.  table, n_outs, past_flow, ref as for b2f_table_loss_host; opts = NULL: the defaults; grad: n_outs pointers
+ * to tensors of the table's shapes.                                                                                             */
+B2F_API int b2f_table_loss_grad_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                             double flow_scale, const b2f_loss_grad_opts *opts, float *const *grad);
+/* on device pointers: dev_table and dev_grad are host arrays of n_outs device pointers (16-byte aligned, as dev_ref); checks,
+ * stream and the pyramid's workspace as for b2f_table_loss_device.  Every element of dev_grad is written.                        */
+B2F_API int b2f_table_loss_grad_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W,
+                               const float *dev_ref, double flow_scale, const b2f_loss_grad_opts *opts, float *const *dev_grad,
+                               void *stream);
+/* on host pointers through the GPU, like b2f_op_table_loss */
+B2F_API int b2f_op_table_loss_grad(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                           double flow_scale, const b2f_loss_grad_opts *opts, float *const *grad);
+/* model:forward followed by the gradient table: x as for b2f_forward_loss; grad: n_outs = b2f_info's n_outputs host tensors of the
+ * output table's shapes.  loss (optional, NULL: none): the n x L x 16 words of b2f_forward_loss, from the same pyramid; outs
+ * (optional, NULL: none): n_outs tensors that receive the table, bit for bit that of b2f_forward.  Sub-batches and workspaces as
+ * for b2f_forward_loss; two_frame is refused.                                                                                   */
+B2F_API int b2f_forward_loss_grad(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
+                          unsigned long long *loss, float *const *grad, int n_outs, float *const *outs);
+/* the same on device pointers: dev_in n x 9 x H x W, in_kind B2F_IN_NORMALIZED only; dev_loss optional; dev_grad a host array of
+ * n_outs device tensors for all n triplets; asynchronous on `stream` like b2f_forward_loss_device.                               */
+B2F_API int b2f_forward_loss_grad_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                 const b2f_loss_grad_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs,
+                                 void *stream);
+/* b2f_forward_loss_grad over several GPUs: the n triplets are split with b2f_shard_range; one context's bits */
+B2F_API int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
+                                const b2f_loss_grad_opts *opts, unsigned long long *loss, float *const *grad, int n_outs);
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature
