@@ -1769,6 +1769,28 @@ int b2f_op_upsample_flow2x(b2f_ctx *c, const float *x, int B, int h, int w, floa
 }
 B2F_CATCH("b2f_op_upsample_flow2x")
 
+// The shape, stride and option fields of the CorrLaunch of b2f_op_warp_costvol (layout 0: NHWC strides, C a multiple of 8 after padding) and
+// of b2f_op_cv_record (layout 1: the forward's chunk-planar strides, option corr_ablate); b2f_op_cv_variant asks the launcher's rule about the
+// same structure, so what it reports is what those two run.  Pointers and k are left to the caller.
+static CorrLaunch op_corr_launch(const b2f_ctx *c, int layout, int B, int C, int h, int w)
+{
+    const size_t hw = (size_t)h * w;
+    CorrLaunch cl{};
+    cl.img_stride = (long)(hw * C);
+    cl.out_img_stride = (long)(hw * kCvRec);
+    if (layout == 0) {   // NHWC expressed with strides
+        cl.chunk_stride = 8; cl.pix_stride = C;
+        cl.out_chunk_stride = 8; cl.out_pix_stride = kCvRec;
+    } else {
+        cl.chunk_stride = (long)(hw * 8); cl.pix_stride = 8;
+        cl.out_chunk_stride = (long)(hw * 8); cl.out_pix_stride = 8;
+        cl.ablate = c->corr_ablate;
+    }
+    cl.B = B; cl.C = C; cl.h = h; cl.w = w;
+    cl.variant = c->corr_variant;
+    return cl;
+}
+
 int b2f_op_warp_costvol(b2f_ctx *c, const float *ref, const float *nbr_future, const float *nbr_past,
                         const float *flow, float k, int B, int C, int h, int w, float *out) try
 {
@@ -1791,15 +1813,11 @@ int b2f_op_warp_costvol(b2f_ctx *c, const float *ref, const float *nbr_future, c
         HIPCHK(hipMemcpy(dfl_pl.p, flow, (size_t)B * 2 * hw * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(launch_planar_to_nhwc(dfl_pl.p, 2, B, h, w, dfl.p, 2, c->stream));
     }
-    CorrLaunch cl;
+    CorrLaunch cl = op_corr_launch(c, 0, B, Cp, h, w);
     cl.ref = dr.p; cl.nbr_fut = df.p; cl.nbr_past = dpa.p;
-    cl.img_stride = (long)(hw * Cp); cl.chunk_stride = 8; cl.pix_stride = Cp;   // NHWC expressed with strides
     cl.flow = flow ? dfl.p : nullptr;
     cl.flow_b = nullptr;
     cl.k = k; cl.out = dcv.p;
-    cl.out_img_stride = (long)(hw * kCvRec); cl.out_chunk_stride = 8; cl.out_pix_stride = kCvRec;
-    cl.B = B; cl.C = Cp; cl.h = h; cl.w = w;
-    cl.variant = c->corr_variant;
     HIPCHK(launch_warp_costvol(cl, c->stream));
     std::vector<float> rec((size_t)B * hw * kCvRec);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1994,15 +2012,10 @@ int b2f_op_cv_record(b2f_ctx *c, const float *ref, const float *nbr_future, cons
     CHK(drec.alloc(nrec + 64));   // the slack the arena gives the record (make_plan)
     HIPCHK(hipMemset(drec.p, 0xff, (nrec + 64) * sizeof(float)));
     HIPCHK(hipDeviceSynchronize());
-    CorrLaunch cl;
+    CorrLaunch cl = op_corr_launch(c, 1, B, C, h, w);
     cl.ref = dmap[0].p; cl.nbr_fut = dmap[1].p; cl.nbr_past = dmap[2].p;
-    cl.img_stride = (long)(hw * C); cl.chunk_stride = (long)(hw * 8); cl.pix_stride = 8;
     cl.flow = dfl[0].p; cl.flow_b = dfl[1].p;
     cl.k = k; cl.out = drec.p;
-    cl.out_img_stride = (long)(hw * kCvRec); cl.out_chunk_stride = (long)(hw * 8); cl.out_pix_stride = 8;
-    cl.B = B; cl.C = C; cl.h = h; cl.w = w;
-    cl.variant = c->corr_variant;
-    cl.ablate = c->corr_ablate;
     HIPCHK(launch_warp_costvol(cl, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(host.data(), drec.p, nrec * sizeof(float), hipMemcpyDeviceToHost));
@@ -2015,6 +2028,20 @@ int b2f_op_cv_record(b2f_ctx *c, const float *ref, const float *nbr_future, cons
     return 0;
 }
 B2F_CATCH("b2f_op_cv_record")
+
+// The variant launch_warp_costvol would run for a B x C x h x w call under the context's options: choose_corr_variant on the CorrLaunch that
+// b2f_op_warp_costvol (layout 0, C padded to a multiple of 8) or b2f_op_cv_record (layout 1) fills through op_corr_launch, no buffers.
+int b2f_op_cv_variant(b2f_ctx *c, int B, int C, int h, int w, int layout) try
+{
+    if (!c) { fail("b2f_op_cv_variant: null argument"); return -1; }
+    if (layout != 0 && layout != 1) { fail("b2f_op_cv_variant: layout must be 0 (b2f_op_warp_costvol) or 1 (b2f_op_cv_record)"); return -1; }
+    if (B < 1 || C < 1 || h < 1 || w < 1 || (layout == 1 && C % 8)) { fail("b2f_op_cv_variant: bad shape (layout 1: C must be a multiple of 8)"); return -1; }
+    if (hipSetDevice(c->device) != hipSuccess) { fail("b2f_op_cv_variant: hipSetDevice failed"); return -1; }
+    const CorrLaunch cl = op_corr_launch(c, layout, B, layout == 0 ? (C + 7) / 8 * 8 : C, h, w);
+    return choose_corr_variant(cl);
+}
+catch (const std::exception &e) { fail(std::string("b2f_op_cv_variant: ") + e.what()); return -1; }
+catch (...) { fail("b2f_op_cv_variant: unknown exception"); return -1; }
 
 int b2f_op_conv_head16(b2f_ctx *c, const float *x, int B, int H, int W, const float *w1, const float *b1, const float *w2,
                        const float *b2, float *y) try

@@ -1068,13 +1068,12 @@ __global__ __launch_bounds__(128, 2) void warp_costvol_win_kernel(const CorrLaun
 
 #endif  // B2F_EXPERIMENTS
 
-hipError_t launch_warp_costvol(const CorrLaunch &p_in, hipStream_t s)
+// The instantiation launch_warp_costvol runs for p: the forced one (p.variant >= 0) or the automatic choice below, after the fallbacks
+// (experiment kernels outside their build and the unit forms where warp_costvol_unit_supported refuses run variant 3).  Host only: reads
+// the device's CU count, launches nothing.
+int choose_corr_variant(const CorrLaunch &p_in)
 {
-    if (p_in.C % 8 != 0 || p_in.pix_stride % 4 != 0 || p_in.chunk_stride % 4 != 0 || p_in.out_pix_stride % 4 != 0 ||
-        p_in.out_chunk_stride % 4 != 0)
-        return hipErrorInvalidValue;
     CorrLaunch p = p_in;
-    const bool pow2 = (p.C & (p.C - 1)) == 0;
     const int tiles_x = (p.w + TW - 1) / TW, tiles_y = (p.h + TH - 1) / TH;
     const dim3 grid((unsigned)(tiles_x * tiles_y * p.B));
     const int t2x = (p.w + v2::TW2 - 1) / v2::TW2, t2y = (p.h + v2::TH2 - 1) / v2::TH2;
@@ -1109,6 +1108,20 @@ hipError_t launch_warp_costvol(const CorrLaunch &p_in, hipStream_t s)
     int variant = p.variant >= 0 ? (p.variant == 4 && !win_ok ? 3 : p.variant)
                   : (p.ablate ? 0 : ((p.h * p.w <= 2048 || 2 * g2.x < round2) && warp_costvol_unit_supported(p)) ? 7 : 2 * g2.x >= round2 ? 3 : grid.x <= 2u * n_cu ? 1 : 0);
     if ((variant == 5 || variant == 6 || variant == 7) && !warp_costvol_unit_supported(p)) variant = 3;
+    return variant;
+}
+
+hipError_t launch_warp_costvol(const CorrLaunch &p, hipStream_t s)
+{
+    if (p.C % 8 != 0 || p.pix_stride % 4 != 0 || p.chunk_stride % 4 != 0 || p.out_pix_stride % 4 != 0 ||
+        p.out_chunk_stride % 4 != 0)
+        return hipErrorInvalidValue;
+    const bool pow2 = (p.C & (p.C - 1)) == 0;
+    const int tiles_x = (p.w + TW - 1) / TW, tiles_y = (p.h + TH - 1) / TH;
+    const dim3 grid((unsigned)(tiles_x * tiles_y * p.B));
+    const int t2x = (p.w + v2::TW2 - 1) / v2::TW2, t2y = (p.h + v2::TH2 - 1) / v2::TH2;
+    const dim3 g2((unsigned)(t2x * t2y * p.B));
+    const int variant = choose_corr_variant(p);
     if (variant == 5) return launch_warp_costvol_unit(p, s);
     if (variant == 7) return launch_warp_costvol_gw(p, s);
 #if B2F_EXPERIMENTS

@@ -263,6 +263,8 @@ __device__ __forceinline__ void bhwd_top_left(float coord, int size, int &pt, fl
 // slot of cost-volume channel c (0..80) of direction dir (0 fwd, 1 bwd) inside a record
 inline int cv_slot(int dir, int c) { return c < 80 ? dir * 80 + c : 160 + dir; }
 hipError_t launch_warp_costvol(const CorrLaunch &p, hipStream_t s);
+// the instantiation launch_warp_costvol runs for p (p.variant forced or the automatic rule, fallbacks applied); launches nothing
+int choose_corr_variant(const CorrLaunch &p);
 // b2f_corr5.hip: the persistent "unit" form (variant 5; C a multiple of 32), same bits as the others
 bool warp_costvol_unit_supported(const CorrLaunch &p);
 hipError_t launch_warp_costvol_unit(const CorrLaunch &p, hipStream_t s);

@@ -84,6 +84,15 @@ def cv_record(model, ref, nbr_future, nbr_past, flow, flow_b, k):
     return rec
 
 
+def cv_variant(model, B, Cc, h, w, layout=0):
+    """The variant of the warp + cost-volume kernel that the launcher runs for a B x Cc x h x w call under the model's options, on the
+    strides of warp_costvol (layout 0) or of cv_record (layout 1).  Launches nothing."""
+    v = _lib.lib().b2f_op_cv_variant(_h(model), int(B), int(Cc), int(h), int(w), int(layout))
+    if v < 0:
+        _lib.check(1)
+    return v
+
+
 def conv_head16(model, x, w1, b1, w2, b2):
     """conv(16,16,s1) + LeakyReLU(0.2) + conv(16,32,s2) + LeakyReLU(0.2) in the fused streaming kernel (pwc.lua:60-62)."""
     x, w1, b1, w2, b2 = _lib.f32(x), _lib.f32(w1), _lib.f32(b1), _lib.f32(w2), _lib.f32(b2)

@@ -795,6 +795,11 @@ B2F_API int b2f_op_layer(b2f_ctx *ctx, int kind, int level, int idx, int nimg, i
  * (fwd 0..79 | bwd 0..79 | fwd 80, bwd 80, flow u v, flow_b u v, 0, 0).                                                          */
 B2F_API int b2f_op_cv_record(b2f_ctx *ctx, const float *ref, const float *nbr_future, const float *nbr_past, const float *flow,
                      const float *flow_b, float k, int B, int C, int h, int w, float *rec);
+/* b2f_op_cv_variant: which instantiation of the warp + cost-volume kernel (0, 1, 3, 5 or 7; the experiments build adds 2, 4, 6, 8) the
+ * launcher runs for a B x C x h x w call under the context's options (corr_variant -1: the automatic rule, by map size, launch size, the
+ * device's compute-unit count and C), on the strides of b2f_op_warp_costvol (layout 0) or of b2f_op_cv_record (layout 1).  Launches
+ * nothing.  Returns the variant, or -1 with b2f_last_error set.                                                                   */
+B2F_API int b2f_op_cv_variant(b2f_ctx *ctx, int B, int C, int h, int w, int layout);
 /* The two 16-channel layers of the head of the pyramid as the pipeline runs them with option bf16_direct = 2, in one kernel:
  * nn.SpatialConvolution(16,16,3,3,1,1,1,1) + LeakyReLU(0.2) (pwc.lua:62, level-2 convUnit) followed by
  * nn.SpatialConvolution(16,32,3,3,2,2,1,1) + LeakyReLU(0.2) (pwc.lua:60, level-3 convUnit).
