@@ -21,6 +21,16 @@ class LossGradOpts(C.Structure):
 
 c_grad_opts_p = C.POINTER(LossGradOpts)
 
+
+class LossGradFtOpts(C.Structure):
+    """b2f_loss_grad_ft_opts of include/b2f.h: the fields of LossGradOpts, -smooth_second_order, -pme_criterion (0 OBCC, 1 OBGCC) and
+    OBGCCriterion's alpha, beta, gamma"""
+    _fields_ = LossGradOpts._fields_ + [("smooth_second_order", C.c_int), ("pme_criterion", C.c_int), ("pme_alpha", C.c_double),
+                                        ("pme_beta", C.c_double), ("pme_gamma", C.c_double)]
+
+
+c_grad_ft_opts_p = C.POINTER(LossGradFtOpts)
+
 # name -> (restype, argtypes); must list every symbol include/b2f.h declares
 SIGNATURES = {
     "b2f_last_error": (C.c_char_p, []),
@@ -199,6 +209,19 @@ SIGNATURES = {
                                                C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
     "b2f_multi_forward_loss_grad": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_opts_p, C.POINTER(C.c_ulonglong),
                                               C.POINTER(c_float_p), C.c_int]),
+    "b2f_loss_grad_ft_defaults": (C.c_int, [c_grad_ft_opts_p]),
+    "b2f_table_loss_grad_ft_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                              c_grad_ft_opts_p, C.POINTER(c_float_p)]),
+    "b2f_table_loss_grad_ft_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                                c_grad_ft_opts_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "b2f_op_table_loss_grad_ft": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                            c_grad_ft_opts_p, C.POINTER(c_float_p)]),
+    "b2f_forward_loss_grad_ft": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ft_opts_p,
+                                           C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int, C.POINTER(c_float_p)]),
+    "b2f_forward_loss_grad_ft_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ft_opts_p,
+                                                  C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
+    "b2f_multi_forward_loss_grad_ft": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ft_opts_p,
+                                                 C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int]),
     "b2f_forward": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(c_float_p), C.c_int]),
     "b2f_output_shapes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.c_int]),

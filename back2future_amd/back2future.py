@@ -696,6 +696,25 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
             "loss": loss, "mean": float(loss.mean()), "nonfinite": nonf}
 
 
+def _apply_grad_weights(who, o, wt):
+    """the weights of loss_grad_options / loss_grad_ft_options into the options struct"""
+    for k, v in wt.items():
+        if k == "level_weights":
+            v = [float(t) for t in v]
+            if len(v) > len(LOSS_LEVEL_WEIGHTS):
+                raise ValueError(who + ": at most %d level weights" % len(LOSS_LEVEL_WEIGHTS))
+            bad = [t for t in v if not (t >= 0.0 and np.isfinite(t))]
+            for j, t in enumerate(v):
+                o.level_weights[j] = t
+        elif k in LOSS_WEIGHTS:
+            bad = [] if (float(v) >= 0.0 and np.isfinite(float(v))) else [v]
+            setattr(o, k, float(v))
+        else:
+            raise ValueError(who + ": unknown weight %r" % (k,))
+        if bad:
+            raise ValueError(who + ": %s must be finite and >= 0, got %r" % (k, bad[0]))
+
+
 def loss_grad_options(weights=None, size_average=False, objective=None):
     """The options of the gradient table of train.lua:428-468 (a _lib.LossGradOpts, b2f_loss_grad_opts of include/b2f.h), from
     b2f_loss_grad_defaults: the weights of opts.lua:61-73, the level weights of test.lua:29-31, sizeAverage off.  objective=NAME
@@ -715,21 +734,44 @@ def loss_grad_options(weights=None, size_average=False, objective=None):
                              "OBGCCriterion, and only the gradients of the first-order pme objective (\"Ours-Hard\") are" % (objective,))
         wt.update(ob["weights"])
     wt.update(weights or {})
-    for k, v in wt.items():
-        if k == "level_weights":
-            v = [float(t) for t in v]
-            if len(v) > len(LOSS_LEVEL_WEIGHTS):
-                raise ValueError("loss_grad_options: at most %d level weights" % len(LOSS_LEVEL_WEIGHTS))
-            bad = [t for t in v if not (t >= 0.0 and np.isfinite(t))]
-            for j, t in enumerate(v):
-                o.level_weights[j] = t
-        elif k in LOSS_WEIGHTS:
-            bad = [] if (float(v) >= 0.0 and np.isfinite(float(v))) else [v]
+    _apply_grad_weights("loss_grad_options", o, wt)
+    o.size_average = 1 if size_average else 0
+    return o
+
+
+def loss_grad_ft_options(weights=None, size_average=False, objective=None, smooth_second_order=None, pme_criterion=None, pme_alpha=None,
+                         pme_beta=None, pme_gamma=None):
+    """The options of the gradient table for objectives with SecondOrderSmoothnessCriterion and / or OBGCCriterion (a
+    _lib.LossGradFtOpts, b2f_loss_grad_ft_opts of include/b2f.h), from b2f_loss_grad_ft_defaults: those of loss_grad_options,
+    -smooth_second_order on, -pme_criterion OBGCC, alpha = beta = gamma = 1.  objective=NAME (any of LOSS_OBJECTIVES) applies the
+    weights, the two flags and alpha, beta, gamma the named model was trained with first (gamma as given: LOSS_OBJECTIVES);
+    `weights` and the five keywords then replace what they name.  pme_criterion: "OBCC" or "OBGCC".  A weight of exactly 0, alpha, beta
+    and gamma included, switches its term off; negative and non-finite ones are refused.  Every entry point that takes the options of
+    loss_grad_options takes these too."""
+    o = _lib.LossGradFtOpts()
+    _lib.check(_lib.lib().b2f_loss_grad_ft_defaults(C.byref(o)))
+    wt = {}
+    if objective is not None:
+        if objective not in LOSS_OBJECTIVES:
+            raise ValueError("loss_grad_ft_options: unknown objective %r (one of %s)" % (objective, ", ".join(sorted(LOSS_OBJECTIVES))))
+        ob = LOSS_OBJECTIVES[objective]
+        wt.update(ob["weights"])
+        o.smooth_second_order = 1 if ob["smooth_second_order"] else 0
+        o.pme_criterion = 1 if ob["pme_criterion"] == "OBGCC" else 0
+        o.pme_alpha, o.pme_beta, o.pme_gamma = ob["pme_alpha"], ob["pme_beta"], ob["pme_gamma"]
+    wt.update(weights or {})
+    _apply_grad_weights("loss_grad_ft_options", o, wt)
+    if smooth_second_order is not None:
+        o.smooth_second_order = 1 if smooth_second_order else 0
+    if pme_criterion is not None:
+        if pme_criterion not in ("OBCC", "OBGCC"):
+            raise ValueError("loss_grad_ft_options: pme_criterion must be 'OBCC' or 'OBGCC'")
+        o.pme_criterion = 1 if pme_criterion == "OBGCC" else 0
+    for k, v in (("pme_alpha", pme_alpha), ("pme_beta", pme_beta), ("pme_gamma", pme_gamma)):
+        if v is not None:
+            if not (float(v) >= 0.0 and np.isfinite(float(v))):
+                raise ValueError("loss_grad_ft_options: %s must be finite and >= 0, got %r" % (k, v))
             setattr(o, k, float(v))
-        else:
-            raise ValueError("loss_grad_options: unknown weight %r" % (k,))
-        if bad:
-            raise ValueError("loss_grad_options: %s must be finite and >= 0, got %r" % (k, bad[0]))
     o.size_average = 1 if size_average else 0
     return o
 
@@ -737,9 +779,21 @@ def loss_grad_options(weights=None, size_average=False, objective=None):
 def _grad_opts_ptr(options):
     if options is None:
         return None
-    if not isinstance(options, _lib.LossGradOpts):
-        raise ValueError("expected the result of back2future.loss_grad_options (or None for the defaults)")
+    if not isinstance(options, (_lib.LossGradOpts, _lib.LossGradFtOpts)):
+        raise ValueError("expected the result of back2future.loss_grad_options or loss_grad_ft_options (or None for the defaults)")
     return C.byref(options)
+
+
+def _grad_entry(name, options):
+    """the entry `name` of the library for these options: b2f_*_grad* or, for loss_grad_ft_options, its b2f_*_grad_ft* twin"""
+    if isinstance(options, _lib.LossGradFtOpts):
+        name = name.replace("_grad", "_grad_ft", 1)
+    return getattr(_lib.lib(), name)
+
+
+def _grad_words(options):
+    """words per record beside a gradient table: the fine-tuning options give the 24-word records of objective "finetune"""
+    return LOSS_FT_WORDS if isinstance(options, _lib.LossGradFtOpts) else LOSS_WORDS
 
 
 def _forward_loss_grad(fn, h, x, flow_scale, options, shapes, L, want_loss, want_table):
@@ -751,7 +805,7 @@ def _forward_loss_grad(fn, h, x, flow_scale, options, shapes, L, want_loss, want
     sh = shapes(H, W)
     grad = [np.empty((n, c, hh, ww), np.float32) for (c, hh, ww) in sh]
     gp = (_lib.c_float_p * len(grad))(*[_lib.fptr(g) for g in grad])
-    loss = np.empty((n, L, LOSS_WORDS), np.uint64) if want_loss else None
+    loss = np.empty((n, L, _grad_words(options)), np.uint64) if want_loss else None
     lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong)) if want_loss else None
     outs = [np.empty((n, c, hh, ww), np.float32) for (c, hh, ww) in sh] if want_table else None
     op = (_lib.c_float_p * len(outs))(*[_lib.fptr(t) for t in outs]) if want_table else None
@@ -1108,10 +1162,11 @@ class Model(object):
         """model:forward followed by `gradOutputs` of train.lua:428-468 (b2f_forward_loss_grad): x n x 9 x H x W, already normalized ->
         the gradient of the pme objective with respect to every tensor of the output table, a list with the shapes of
         Model.forward's, that of ops.table_loss_grad(self.forward(x), x[:, 3:6]); the table stays on the GPU.  options: of
-        loss_grad_options (None: the defaults).  want_loss=True returns (gradient, records) with the records of forwardLoss, from the
-        same pass; want_table=True appends the table of Model.forward, bit for bit."""
+        loss_grad_options (None: the defaults) or of loss_grad_ft_options (b2f_forward_loss_grad_ft: the fine-tuning objectives of the
+        Soft models).  want_loss=True returns (gradient, records) with the records of forwardLoss (of forwardLoss(objective="finetune")
+        with loss_grad_ft_options), from the same pass; want_table=True appends the table of Model.forward, bit for bit."""
         L = self.n_outputs // (5 if self.past_flow else 4)
-        grad, loss, outs = _forward_loss_grad(_lib.lib().b2f_forward_loss_grad, self._h, x, flow_scale, options, self.output_shapes, L,
+        grad, loss, outs = _forward_loss_grad(_grad_entry("b2f_forward_loss_grad", options), self._h, x, flow_scale, options, self.output_shapes, L,
                                               want_loss, want_table)
         if not want_loss and not want_table:
             return grad
@@ -1119,20 +1174,22 @@ class Model(object):
 
     def forwardLossGradDevice(self, d_in, n, H, W, d_grad, d_loss=None, flow_scale=20.0, options=None, stream=None):
         """b2f_forward_loss_grad_device on device pointers (ints): d_in n x 9 x H x W normalized float32, d_grad the n_outputs tensors
-        of the gradient table (train.lua:428-468), d_loss n x L x 16 uint64 or None; asynchronous on `stream`."""
+        of the gradient table (train.lua:428-468), d_loss n x L x 16 uint64 or None; asynchronous on `stream`.  With the options of
+        loss_grad_ft_options: b2f_forward_loss_grad_ft_device, d_loss n x L x 24."""
         ptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad])
-        _lib.check(_lib.lib().b2f_forward_loss_grad_device(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale),
+        _lib.check(_grad_entry("b2f_forward_loss_grad_device", options)(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale),
                                                             _grad_opts_ptr(options), C.c_void_p(d_loss) if d_loss else None, ptrs, len(d_grad),
                                                             C.c_void_p(stream) if stream else None))
 
     def tableLossGradDevice(self, d_table, n, H, W, d_ref, d_grad, flow_scale=20.0, options=None, stream=None):
         """b2f_table_loss_grad_device on device pointers (ints): d_table the L x 4 | 5 tensors of an output table in table order, d_ref
-        n x 3 x H x W, d_grad as many tensors of the same shapes (train.lua:428-468); asynchronous on `stream`."""
+        n x 3 x H x W, d_grad as many tensors of the same shapes (train.lua:428-468); asynchronous on `stream`.  With the options of
+        loss_grad_ft_options: b2f_table_loss_grad_ft_device."""
         ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
         gptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad])
         if len(d_grad) != len(d_table):
             raise ValueError("tableLossGradDevice: the gradient table must have the table's %d tensors" % len(d_table))
-        _lib.check(_lib.lib().b2f_table_loss_grad_device(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale),
+        _lib.check(_grad_entry("b2f_table_loss_grad_device", options)(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale),
                                                           _grad_opts_ptr(options), gptrs, C.c_void_p(stream) if stream else None))
 
     def forward_device(self, d_in, B, H, W, d_flow=None, d_occ=None, d_est3=None, unit_input=False, stream=None, d_past_flow=None):
@@ -1260,7 +1317,8 @@ class MultiModel(object):
         return _forward_loss(entry, self._h, x, flow_scale, no.value // (5 if pf.value else 4), None, words)[0]
 
     def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True):
-        """Model.forwardLossGrad over the GPUs (b2f_multi_forward_loss_grad; train.lua:428-468): the same bits."""
+        """Model.forwardLossGrad over the GPUs (b2f_multi_forward_loss_grad, b2f_multi_forward_loss_grad_ft; train.lua:428-468): the
+        same bits."""
         c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
         lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
@@ -1270,7 +1328,8 @@ class MultiModel(object):
             _lib.check(_lib.lib().b2f_output_shapes(c0, H, W, ch, oh, ow, 64))
             return [(ch[i], oh[i], ow[i]) for i in range(no.value)]
 
-        fn = lambda h, xp, n, H, W, fsc, op, lp, gp, ng, outs: _lib.lib().b2f_multi_forward_loss_grad(h, xp, n, H, W, fsc, op, lp, gp, ng)
+        entry = _grad_entry("b2f_multi_forward_loss_grad", options)
+        fn = lambda h, xp, n, H, W, fsc, op, lp, gp, ng, outs: entry(h, xp, n, H, W, fsc, op, lp, gp, ng)
         grad, loss, _ = _forward_loss_grad(fn, self._h, x, flow_scale, options, shapes, no.value // (5 if pf.value else 4), want_loss, False)
         return (grad, loss) if want_loss else grad
 

@@ -880,7 +880,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1007; }
+int b2f_version(void) { return 1008; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1495,7 +1495,7 @@ int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H
 
 // the table of nb triplets into tab, its records into d_loss where wanted, its gradient table (train.lua:428-468) into grad; all on s.
 // The pyramid of R is built once: by the records' launch where there is one.
-int forward_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const b2f_loss_grad_opts &o,
+int forward_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const GradOpts &o,
                           const LossPlan &lp, float *const *tab, unsigned long long *d_loss, float *const *grad)
 {
     if (d_loss) CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, lp, tab, d_loss));
@@ -1505,7 +1505,8 @@ int forward_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, 
 }
 
 // what b2f_forward_loss_grad* check beyond check_forward_loss: the options (into *o) and the gradient table's pointers
-int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, const b2f_loss_grad_opts *opts, float *const *grad, int n_outs, b2f_loss_grad_opts *o)
+int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft,
+                            float *const *grad, int n_outs, GradOpts *o)
 {
     if (n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
     for (int i = 0; i < n_outs; ++i) {
@@ -1513,10 +1514,7 @@ int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, const b2f_lo
         for (int k = 0; k < i; ++k)
             if (grad[i] == grad[k]) return fail(w + ": the gradient table must not alias itself");
     }
-    if (opts) *o = *opts;
-    else (void)b2f_loss_grad_defaults(o);
-    const char *why = loss_grad_refusal(*o);
-    return why ? fail(w + ": " + why) : 0;
+    return resolve_grad_opts(w, opts, ft_opts, ft, o);
 }
 
 struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub-batches run (b2f_ctx::req_batch)
@@ -1566,15 +1564,17 @@ int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, in
     return 0;
 }
 
-// b2f_forward_loss_grad on a shard: `req` is the caller's n (b2f_multi_forward_loss_grad passes its own down)
+// b2f_forward_loss_grad (ft = false) or b2f_forward_loss_grad_ft on a shard: `req` is the caller's n (b2f_multi_forward_loss_grad* pass
+// their own down)
 int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
-                                unsigned long long *loss, float *const *grad, int n_outs, float *const *outs)
+                                const b2f_loss_grad_ft_opts *ft_opts, bool ft, unsigned long long *loss, float *const *grad, int n_outs,
+                                float *const *outs)
 {
-    const std::string w("b2f_forward_loss_grad");
+    const std::string w(ft ? "b2f_forward_loss_grad_ft" : "b2f_forward_loss_grad");
     if (!c || !x || !grad) return fail(w + ": null argument");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
-    b2f_loss_grad_opts o;
-    CHK(check_forward_loss_grad(c, w, opts, grad, n_outs, &o));
+    GradOpts o;
+    CHK(check_forward_loss_grad(c, w, opts, ft_opts, ft, grad, n_outs, &o));
     for (int i = 0; outs && i < n_outs; ++i) {
         if (!outs[i]) return fail(w + ": null tensor in outs");
         for (int k = 0; k < n_outs; ++k)
@@ -1583,7 +1583,7 @@ int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int 
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
     const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
-    const LossPlan lp = make_loss_plan(c, sb, H, W, true, false, true);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, true, ft, true);
     CHK(ensure_dev_work(c->loss_work, lp.bytes));
     char *base = c->loss_work.dev;
     std::vector<float *> tab((size_t)lp.n_outs), gr((size_t)lp.n_outs);
@@ -1618,27 +1618,36 @@ extern "C" {
 int b2f_forward_loss_grad(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts, unsigned long long *loss,
                           float *const *grad, int n_outs, float *const *outs) try
 {
-    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, opts, loss, grad, n_outs, outs);
+    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, opts, nullptr, false, loss, grad, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_grad")
 
-// model:forward + the gradient table of train.lua:428-468 on device pointers
-int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
-                                 unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
+// the same with the fine-tuning criteria of README.md:89-102 and the 24-word records
+int b2f_forward_loss_grad_ft(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ft_opts *opts,
+                             unsigned long long *loss, float *const *grad, int n_outs, float *const *outs) try
 {
-    const std::string w(__func__);
+    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, nullptr, opts, true, loss, grad, n_outs, outs);
+}
+B2F_CATCH("b2f_forward_loss_grad_ft")
+
+extern "C++" {
+// b2f_forward_loss_grad_device (ft = false) and b2f_forward_loss_grad_ft_device
+static int forward_loss_grad_device(const std::string &w, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                    const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, unsigned long long *dev_loss,
+                                    float *const *dev_grad, int n_outs, void *stream)
+{
     if (!c || !dev_in || !dev_grad) return fail(w + ": null argument");
     if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
-    b2f_loss_grad_opts o;
-    CHK(check_forward_loss_grad(c, w, opts, dev_grad, n_outs, &o));
+    GradOpts o;
+    CHK(check_forward_loss_grad(c, w, opts, ft_opts, ft, dev_grad, n_outs, &o));
     uintptr_t bits = (uintptr_t)dev_in | (uintptr_t)dev_loss;
     for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_grad[i];
     if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
     const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
-    const LossPlan lp = make_loss_plan(c, sb, H, W, false, false);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, false, ft);
     CHK(ensure_dev_work(c->loss_work, lp.bytes));
     std::vector<float *> tab((size_t)lp.n_outs), gr((size_t)lp.n_outs);
     for (int i = 0; i < lp.n_outs; ++i) tab[(size_t)i] = (float *)(c->loss_work.dev + lp.off[(size_t)i]);
@@ -1652,7 +1661,22 @@ int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, in
     }
     return 0;
 }
+}  // extern "C++"
+
+// model:forward + the gradient table of train.lua:428-468 on device pointers
+int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
+                                 unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
+{
+    return forward_loss_grad_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, opts, nullptr, false, dev_loss, dev_grad, n_outs, stream);
+}
 B2F_CATCH("b2f_forward_loss_grad_device")
+
+int b2f_forward_loss_grad_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                    const b2f_loss_grad_ft_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
+{
+    return forward_loss_grad_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, opts, true, dev_loss, dev_grad, n_outs, stream);
+}
+B2F_CATCH("b2f_forward_loss_grad_ft_device")
 
 // model:forward + test.lua:266-297 from host memory
 int b2f_forward_loss(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try

@@ -535,13 +535,23 @@ int compute_flow_host(b2f_ctx *c, const FlowRequest &r);
 // ft: b2f_forward_loss_ft, records of B2F_LOSS_FT_WORDS words
 int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
                       bool ft = false);
+// checked options of either gradient table: ft = false: the *_grad entries (o's two flags are 0, table_loss_grad_kernel, 16-word
+// records); ft = true: the *_grad_ft entries (table_loss_grad_ft_kernel, 24-word records)
+struct GradOpts {
+    b2f_loss_grad_ft_opts o;
+    bool ft;
+};
+// b2f_tableloss.hip: opts (ft = false) or ft_opts (ft = true), or that kind's defaults where it is null, into *o; refused as
+// include/b2f.h says
+int resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, GradOpts *o);
 // b2f_tableloss.hip: the gradient table of train.lua:428-468 of n images on s, from checked options; with_pyr: R_1 .. R_{L-1} are built
 // first (false: launch_table_loss has built them on s)
 int table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
-                        const float *dev_ref, size_t ref_stride, double flow_scale, const b2f_loss_grad_opts &o, bool with_pyr);
-// b2f_api.hip: b2f_forward_loss_grad on n of a request of `req` triplets (0: n)
+                        const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, bool with_pyr);
+// b2f_api.hip: b2f_forward_loss_grad (ft = false, opts) or b2f_forward_loss_grad_ft (ft = true, ft_opts) on n of a request of `req`
+// triplets (0: n)
 int forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
-                           unsigned long long *loss, float *const *grad, int n_outs, float *const *outs);
+                           const b2f_loss_grad_ft_opts *ft_opts, bool ft, unsigned long long *loss, float *const *grad, int n_outs, float *const *outs);
 int compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream);
 // b2f_pipeline.hip: a push (r.stream) on host buffers, synchronous, and on device buffers, asynchronous on `stream`; *ready = 1 when
 // the outputs were written (from the third push on)

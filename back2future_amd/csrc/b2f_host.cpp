@@ -7,6 +7,7 @@
 #include "b2f_flowwarp.h"
 #include "b2f_tableloss.h"
 #include "b2f_tableloss_grad.h"
+#include "b2f_tableloss_grad_ft.h"
 #include "b2f_tableloss_ft.h"
 #include "../../include/b2f.h"
 
@@ -459,8 +460,53 @@ void loss_grad_coef(const b2f_loss_grad_opts &o, int j, int h, int w, GradCoef *
             (o.smooth_occ != 0.0 ? kGradSmoothOcc : 0u) | (o.prior_occ != 0.0 ? kGradPrior : 0u);
 }
 
+b2f_loss_grad_opts loss_grad_ft_base(const b2f_loss_grad_ft_opts &o)
+{
+    b2f_loss_grad_opts r;
+    r.smooth_flow = o.smooth_flow; r.const_vel = o.const_vel; r.pme = o.pme; r.smooth_occ = o.smooth_occ; r.prior_occ = o.prior_occ;
+    for (int j = 0; j < kLossMaxLevels; ++j) r.level_weights[j] = o.level_weights[j];
+    r.size_average = o.size_average;
+    return r;
+}
+
+b2f_loss_grad_ft_opts loss_grad_ft_from(const b2f_loss_grad_opts &o)
+{
+    b2f_loss_grad_ft_opts r;
+    r.smooth_flow = o.smooth_flow; r.const_vel = o.const_vel; r.pme = o.pme; r.smooth_occ = o.smooth_occ; r.prior_occ = o.prior_occ;
+    for (int j = 0; j < kLossMaxLevels; ++j) r.level_weights[j] = o.level_weights[j];
+    r.size_average = o.size_average;
+    r.smooth_second_order = 0; r.pme_criterion = 0;
+    r.pme_alpha = r.pme_beta = r.pme_gamma = 1.0;
+    return r;
+}
+
+const char *loss_grad_ft_refusal(const b2f_loss_grad_ft_opts &o)
+{
+    if (const char *why = loss_grad_refusal(loss_grad_ft_base(o))) return why;
+    if (o.pme_criterion != 0 && o.pme_criterion != 1) return "pme_criterion of b2f_loss_grad_ft_opts must be 0 (OBCC) or 1 (OBGCC)";
+    const double wt[3] = {o.pme_alpha, o.pme_beta, o.pme_gamma};
+    for (double v : wt)
+        if (!(v >= 0.0) || !std::isfinite(v)) return "pme_alpha, pme_beta and pme_gamma of b2f_loss_grad_ft_opts must be finite and >= 0";
+    return nullptr;
+}
+
+void loss_grad_ft_coef(const b2f_loss_grad_ft_opts &o, int j, int h, int w, GradFtCoef *k)
+{
+    loss_grad_coef(loss_grad_ft_base(o), j, h, w, &k->k);
+    k->alpha = o.pme_alpha; k->beta = o.pme_beta; k->gamma = o.pme_gamma;
+    k->ft = (o.smooth_second_order ? kGradFtSecond : 0u) | (o.pme_criterion == 1 ? kGradFtObgcc : 0u) | (o.pme_alpha != 0.0 ? kGradFtAlpha : 0u) |
+            (o.pme_beta != 0.0 ? kGradFtBeta : 0u) | (o.pme_gamma != 0.0 ? kGradFtGamma : 0u);
+}
+
 void table_loss_grad_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
                           const b2f_loss_grad_opts &opts, float *const *grad)
+{
+    table_loss_grad_ft_host(table, L, past, n, H, W, ref, flow_scale, loss_grad_ft_from(opts), grad);
+}
+
+// both gradient tables: with neither flag of opts set every element takes the path of b2f_tableloss_grad.h alone
+void table_loss_grad_ft_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                             const b2f_loss_grad_ft_opts &opts, float *const *grad)
 {
     const int per = past ? 5 : 4;
     std::vector<float> cur, next;
@@ -481,9 +527,11 @@ void table_loss_grad_host(const float *const *table, int L, bool past, int n, in
                 cur.swap(next);
                 R = cur.data();
             }
-            GradCoef k;
-            loss_grad_coef(opts, j, h, w, &k);
-            const bool want_w = (k.on & (kGradSmooth | kGradSmoothOcc)) != 0;
+            GradFtCoef kf;
+            loss_grad_ft_coef(opts, j, h, w, &kf);
+            const GradCoef &k = kf.k;
+            const bool second = (kf.ft & kGradFtSecond) != 0, obgcc = (kf.ft & kGradFtObgcc) != 0;
+            const bool want_w = (k.on & kGradSmoothOcc) != 0 || (!second && (k.on & kGradSmooth) != 0);
             const float *const *t = table + (size_t)j * per;
             float *const *g = grad + (size_t)j * per;
             const float *f = t[0] + (size_t)b * 2 * hw, *p = past ? t[1] + (size_t)b * 2 * hw : nullptr, *o = t[per - 3] + (size_t)b * 2 * hw;
@@ -498,8 +546,8 @@ void table_loss_grad_host(const float *const *table, int L, bool past, int n, in
                     // the offsets of the four neighbours; a missing one is not read (its pair has no term)
                     const size_t il = has_l ? i - 1 : i, ir = has_r ? i + 1 : i, iu = has_u ? i - w : i, id = has_d ? i + w : i;
                     double wxc = 1.0, wxl = 1.0, wyc = 1.0, wyu = 1.0;
+                    const float *R0 = R, *R1 = R + hw, *R2 = R + 2 * hw;
                     if (want_w) {
-                        const float *R0 = R, *R1 = R + hw, *R2 = R + 2 * hw;
                         wxc = grad_weight(has_r, R0[i], R0[ir], R1[i], R1[ir], R2[i], R2[ir]);
                         wxl = grad_weight(has_l, R0[il], R0[i], R1[il], R1[i], R2[il], R2[i]);
                         wyc = grad_weight(has_d, R0[i], R0[id], R1[i], R1[id], R2[i], R2[id]);
@@ -513,13 +561,33 @@ void table_loss_grad_host(const float *const *table, int L, bool past, int n, in
                         return grad_s(grad_edge<true>(has_r, q[i], q[ir], wxc), grad_edge<true>(has_l, q[il], q[i], wxl),
                                       grad_edge<true>(has_d, q[i], q[id], wyc), grad_edge<true>(has_u, q[iu], q[i], wyu));
                     };
+                    // the second-order weights of the pixel and its four neighbours, where they are interior on the axis
+                    auto in_x = [&](int xx) { return xx >= 1 && xx + 1 < w; };
+                    auto in_y = [&](int yy) { return yy >= 1 && yy + 1 < h; };
+                    double w2x[3] = {1.0, 1.0, 1.0}, w2y[3] = {1.0, 1.0, 1.0};
+                    if (second && (k.on & kGradSmooth))
+                        for (int t = -1; t <= 1; ++t) {
+                            const size_t ix = i + t, iy = i + (ptrdiff_t)t * w;
+                            if (in_x(x + t)) w2x[t + 1] = grad2_weight(R0[ix - 1], R0[ix], R0[ix + 1], R1[ix - 1], R1[ix], R1[ix + 1], R2[ix - 1], R2[ix], R2[ix + 1]);
+                            if (in_y(y + t)) w2y[t + 1] = grad2_weight(R0[iy - w], R0[iy], R0[iy + w], R1[iy - w], R1[iy], R1[iy + w], R2[iy - w], R2[iy], R2[iy + w]);
+                        }
+                    auto SS = [&](const float *q) {   // S2 of the plane: a q off the interior is not formed and not read
+                        double qx[3], qy[3];
+                        for (int t = -1; t <= 1; ++t) {
+                            const size_t ix = i + t, iy = i + (ptrdiff_t)t * w;
+                            const bool ax = in_x(x + t), ay = in_y(y + t);
+                            qx[t + 1] = grad2_q(ax, ax ? q[ix - 1] : 0.0f, ax ? q[ix] : 0.0f, ax ? q[ix + 1] : 0.0f, w2x[t + 1]);
+                            qy[t + 1] = grad2_q(ay, ay ? q[iy - w] : 0.0f, ay ? q[iy] : 0.0f, ay ? q[iy + w] : 0.0f, w2y[t + 1]);
+                        }
+                        return grad2_s(qy[1], qx[1], qy[2], qx[2], qy[0], qx[0]);
+                    };
                     double cv[2] = {0.0, 0.0};
                     if (past && (k.on & kGradConstVel)) grad_const_vel(f[i], f[hw + i], p[i], p[hw + i], cv);
                     for (int c = 0; c < 2; ++c) {
-                        const double sf = (k.on & kGradSmooth) ? S1(f + c * hw) : 0.0;
+                        const double sf = (k.on & kGradSmooth) ? (second ? SS(f + c * hw) : S1(f + c * hw)) : 0.0;
                         gf[c * hw + i] = grad_flow(k, sf, cv[c], past, false);
                         if (past) {
-                            const double sp = (k.on & kGradSmooth) ? S1(p + c * hw) : 0.0;
+                            const double sp = (k.on & kGradSmooth) ? (second ? SS(p + c * hw) : S1(p + c * hw)) : 0.0;
                             gp[c * hw + i] = grad_flow(k, sp, cv[c], true, true);
                         }
                     }
@@ -530,7 +598,24 @@ void table_loss_grad_host(const float *const *table, int L, bool past, int n, in
                             const bool pf = d == 0 && past;   // OBCCriterion.lua:166-170
                             const WarpTaps tp = warp_taps(pf ? p[i] : f[i], pf ? p[hw + i] : f[hw + i], d == 0 ? -kd : kd, x, y, w, h);
                             const float w3[3] = {iw[d][i], iw[d][hw + i], iw[d][2 * hw + i]}, r3[3] = {R[i], R[hw + i], R[2 * hw + i]};
-                            grad_photo(k, tp.inside, w3, r3, o[(size_t)(1 - d) * hw + i], &po[1 - d], gi);
+                            if (obgcc) {
+                                double sums[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+                                for (int c = 0; c < 3; ++c) {
+                                    const float *I = iw[d] + c * hw, *Rc = R + c * hw;
+                                    ObgccErr e;
+                                    e.d = (double)I[i] - (double)Rc[i];
+                                    e.ey = obgcc_e(has_d, I[i], I[id], Rc[i], Rc[id]);
+                                    e.eyu = has_u ? obgcc_e(true, I[iu], I[i], Rc[iu], Rc[i]) : 0.0;
+                                    e.ex = obgcc_e(has_r, I[i], I[ir], Rc[i], Rc[ir]);
+                                    e.exl = has_l ? obgcc_e(true, I[il], I[i], Rc[il], Rc[i]) : 0.0;
+                                    if (tp.inside) {
+                                        gi[c] = obgcc_image(kf, has_u, has_l, e, o[(size_t)(1 - d) * hw + i]);
+                                        obgcc_p1_add(kf, has_u, has_l, e, c == 0, sums);
+                                    }
+                                }
+                                po[1 - d] = tp.inside ? obgcc_po(kf, has_u, has_l, sums) : 1.0;
+                            } else
+                                grad_photo(k, tp.inside, w3, r3, o[(size_t)(1 - d) * hw + i], &po[1 - d], gi);
                         }
                         for (int c = 0; c < 3; ++c) giw[d][c * hw + i] = gi[c];
                     }

@@ -101,6 +101,20 @@ void table_loss_grad_host(const float *const *table, int L, bool past, int n, in
                           const b2f_loss_grad_opts &opts, float *const *grad);
 // nullptr, or why the options are refused (a negative or non-finite weight)
 const char *loss_grad_refusal(const b2f_loss_grad_opts &o);
+}  // namespace b2f
+struct b2f_loss_grad_ft_opts;
+namespace b2f {
+struct GradFtCoef;
+// The same with the fine-tuning criteria where the options' flags ask for them (b2f_tableloss_grad_ft.h per element;
+// b2f_table_loss_grad_ft_host); with both flags 0 the bits of table_loss_grad_host, which calls it
+void table_loss_grad_ft_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                             const b2f_loss_grad_ft_opts &opts, float *const *grad);
+// nullptr, or why (as above, a pme_criterion outside {0, 1}, a negative or non-finite alpha, beta or gamma)
+const char *loss_grad_ft_refusal(const b2f_loss_grad_ft_opts &o);
+// the first-order options as fine-tuning options with both flags 0, and the first-order fields of fine-tuning options
+b2f_loss_grad_ft_opts loss_grad_ft_from(const b2f_loss_grad_opts &o);
+b2f_loss_grad_opts loss_grad_ft_base(const b2f_loss_grad_ft_opts &o);
+void loss_grad_ft_coef(const b2f_loss_grad_ft_opts &o, int j, int h, int w, GradFtCoef *k);
 // the coefficients of level j of h x w (include/b2f.h: k_s .. k_pr) and which terms are evaluated
 void loss_grad_coef(const b2f_loss_grad_opts &o, int j, int h, int w, GradCoef *k);
 

@@ -382,5 +382,10 @@ hipError_t launch_table_loss_pyramid(int L, int n, int H, int W, const float *re
 struct GradCoef;
 hipError_t launch_table_loss_grad(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
                                   const float *pyr, double flow_scale, const GradCoef *coef, hipStream_t s);
+// b2f_tableloss_grad_ft.hip: the same with SecondOrderSmoothnessCriterion / OBGCCriterion where coef[j].ft asks for them (b2f_host.h:
+// loss_grad_ft_coef)
+struct GradFtCoef;
+hipError_t launch_table_loss_grad_ft(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref,
+                                     size_t ref_stride, const float *pyr, double flow_scale, const GradFtCoef *coef, hipStream_t s);
 
 }  // namespace b2f

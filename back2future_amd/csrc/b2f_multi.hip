@@ -433,28 +433,42 @@ int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H, int W,
 }
 B2F_CATCH("b2f_multi_forward_loss_ft")
 
-// the gradient table of train.lua:428-468 behind model:forward over several GPUs
-int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
-                                unsigned long long *loss, float *const *grad, int n_outs) try
+// b2f_multi_forward_loss_grad (ft = false) and b2f_multi_forward_loss_grad_ft
+static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
+                                   const b2f_loss_grad_ft_opts *ft_opts, bool ft, unsigned long long *loss, float *const *grad, int n_outs)
 {
-    if (!m) return api_fail("b2f_multi_forward_loss_grad: null context");
-    if (!x || !grad || n <= 0 || H <= 0 || W <= 0) return api_fail("b2f_multi_forward_loss_grad: bad arguments");
+    if (!m) return api_fail((w + ": null context").c_str());
+    if (!x || !grad || n <= 0 || H <= 0 || W <= 0) return api_fail((w + ": bad arguments").c_str());
     const b2f_ctx *c0 = m->ctx[0];
-    if (n_outs != c0->g.n_outputs()) return api_fail("b2f_multi_forward_loss_grad: n_outs must be the contexts' n_outputs");
+    if (n_outs != c0->g.n_outputs()) return api_fail((w + ": n_outs must be the contexts' n_outputs").c_str());
     const int per = c0->past_flow ? 5 : 4;
-    const size_t rec = (size_t)(n_outs / per) * B2F_LOSS_WORDS;
+    const size_t rec = (size_t)(n_outs / per) * (ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
     for (int i = 0; i < n_outs; ++i)
-        if (!grad[i]) return api_fail("b2f_multi_forward_loss_grad: null tensor in the gradient table");
+        if (!grad[i]) return api_fail((w + ": null tensor in the gradient table").c_str());
     return run_sharded(m, n, [&](int i, int lo, int hi) {
         std::vector<float *> g((size_t)n_outs);   // the shard's part of every tensor: image lo
         for (int t = 0; t < n_outs; ++t) {
             const int j = t / per, ch = (t % per) >= per - 2 ? 3 : 2;
             g[(size_t)t] = grad[t] + (size_t)lo * ch * (H >> j) * (W >> j);
         }
-        return forward_loss_grad_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, opts, loss ? loss + (size_t)lo * rec : nullptr,
-                                      g.data(), n_outs, nullptr);
+        return forward_loss_grad_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, opts, ft_opts, ft,
+                                      loss ? loss + (size_t)lo * rec : nullptr, g.data(), n_outs, nullptr);
     });
 }
+
+// the gradient table of train.lua:428-468 behind model:forward over several GPUs
+int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
+                                unsigned long long *loss, float *const *grad, int n_outs) try
+{
+    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, opts, nullptr, false, loss, grad, n_outs);
+}
 B2F_CATCH("b2f_multi_forward_loss_grad")
+
+int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ft_opts *opts,
+                                   unsigned long long *loss, float *const *grad, int n_outs) try
+{
+    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, nullptr, opts, true, loss, grad, n_outs);
+}
+B2F_CATCH("b2f_multi_forward_loss_grad_ft")
 
 }  // extern "C"

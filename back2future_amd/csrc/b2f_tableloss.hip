@@ -7,7 +7,7 @@
 // of the context.
 #include "b2f_ctx.h"
 #include "b2f_tableloss.h"
-#include "b2f_tableloss_grad.h"
+#include "b2f_tableloss_grad_ft.h"
 #include "b2f_tableloss_dev.h"
 
 using namespace b2f;
@@ -338,15 +338,6 @@ int op_table_loss(const std::string &w, bool ft, b2f_ctx *c, const float *const 
 }
 
 // ---- the gradient table of train.lua:428-468 (b2f_tableloss_grad.hip) ----
-// opts or the defaults into *o, refused where a weight is negative or not finite
-int resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts, b2f_loss_grad_opts *o)
-{
-    if (opts) *o = *opts;
-    else (void)b2f_loss_grad_defaults(o);
-    const char *why = loss_grad_refusal(*o);
-    return why ? fail(w + ": " + why) : 0;
-}
-
 // grad: n_outs tensors, none null, none a tensor of the table, ref or another one of grad
 int check_grad_table(const std::string &w, const float *const *table, int n_outs, const float *ref, float *const *grad)
 {
@@ -362,17 +353,42 @@ int check_grad_table(const std::string &w, const float *const *table, int n_outs
 
 }  // namespace
 
-// b2f_table_loss_grad_device on checked options; with_pyr: build R_1 .. R_{L-1} first (false: launch_table_loss has)
-int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
-                             const float *dev_ref, size_t ref_stride, double flow_scale, const b2f_loss_grad_opts &o, bool with_pyr)
+int b2f::resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, GradOpts *o)
 {
-    GradCoef coef[kLossMaxLevels];
-    for (int j = 0; j < L; ++j) loss_grad_coef(o, j, H >> j, W >> j, &coef[j]);
+    o->ft = ft;
+    const char *why = nullptr;
+    if (ft) {
+        if (ft_opts) o->o = *ft_opts;
+        else (void)b2f_loss_grad_ft_defaults(&o->o);
+        why = loss_grad_ft_refusal(o->o);
+    } else {
+        b2f_loss_grad_opts t;
+        if (opts) t = *opts;
+        else (void)b2f_loss_grad_defaults(&t);
+        o->o = loss_grad_ft_from(t);
+        why = loss_grad_refusal(t);
+    }
+    return why ? fail(w + ": " + why) : 0;
+}
+
+// b2f_table_loss_grad_device / b2f_table_loss_grad_ft_device on checked options; with_pyr: build R_1 .. R_{L-1} first (false:
+// launch_table_loss has)
+int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
+                             const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, bool with_pyr)
+{
+    GradFtCoef coef[kLossMaxLevels];
+    GradCoef first[kLossMaxLevels];
+    for (int j = 0; j < L; ++j) {
+        loss_grad_ft_coef(o.o, j, H >> j, W >> j, &coef[j]);
+        first[j] = coef[j].k;
+    }
     CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
     if (with_pyr) HIPCHK(launch_table_loss_pyramid(L, n, H, W, dev_ref, ref_stride, (float *)c->loss_pyr.dev, s));
     ProfEvent pe;
-    const bool timed = prof_open(c, s, "table_loss_grad", &pe);
-    const hipError_t e = launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, (const float *)c->loss_pyr.dev, flow_scale, coef, s);
+    const bool timed = prof_open(c, s, o.ft ? "table_loss_grad_ft" : "table_loss_grad", &pe);
+    const float *pyr = (const float *)c->loss_pyr.dev;
+    const hipError_t e = o.ft ? launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s)
+                              : launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, first, s);
     if (timed) prof_close(c, s, pe);
     HIPCHK(e);
     return 0;
@@ -380,8 +396,9 @@ int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_
 
 namespace {
 
+// b2f_table_loss_grad_device and b2f_table_loss_grad_ft_device on checked options (resolve_grad_opts)
 int table_loss_grad_device(const std::string &w, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
-                           double flow_scale, const b2f_loss_grad_opts *opts, float *const *dev_grad, void *stream)
+                           double flow_scale, const GradOpts &o, float *const *dev_grad, void *stream)
 {
     if (!c) return fail(w + ": null context");
     const int per = level_size(c, n_outs);
@@ -389,19 +406,65 @@ int table_loss_grad_device(const std::string &w, b2f_ctx *c, const float *const 
     int L = 0;
     CHK(check_table_loss(w, dev_table, n_outs, per, n, H, W, dev_ref, flow_scale, dev_grad, &L));
     CHK(check_grad_table(w, dev_table, n_outs, dev_ref, dev_grad));
-    b2f_loss_grad_opts o;
-    CHK(resolve_grad_opts(w, opts, &o));
     if (n > 65535) return fail(w + ": at most 65535 images per call");
     uintptr_t bits = (uintptr_t)dev_ref;
     for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i] | (uintptr_t)dev_grad[i];
     if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
-    if (host_memory(dev_ref)) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss_grad / b2f_table_loss_grad_host)");
+    const std::string use = o.ft ? "b2f_op_table_loss_grad_ft / b2f_table_loss_grad_ft_host" : "b2f_op_table_loss_grad / b2f_table_loss_grad_host";
+    if (host_memory(dev_ref)) return fail(w + ": host memory passed to a device entry point (use " + use + ")");
     for (int i = 0; i < n_outs; ++i)
-        if (host_memory(dev_table[i]) || host_memory(dev_grad[i]))
-            return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss_grad / b2f_table_loss_grad_host)");
+        if (host_memory(dev_table[i]) || host_memory(dev_grad[i])) return fail(w + ": host memory passed to a device entry point (use " + use + ")");
     return table_loss_grad_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, dev_grad, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, flow_scale,
                                o, true);
+}
+
+// b2f_table_loss_grad_host and b2f_table_loss_grad_ft_host
+int table_loss_grad_host_entry(const std::string &w, const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                               double flow_scale, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, float *const *grad)
+{
+    int L = 0;
+    CHK(check_table_loss(w, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, grad, &L));
+    CHK(check_grad_table(w, table, n_outs, ref, grad));
+    GradOpts o;
+    CHK(resolve_grad_opts(w, opts, ft_opts, ft, &o));
+    table_loss_grad_ft_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, grad);
+    return 0;
+}
+
+// b2f_op_table_loss_grad and b2f_op_table_loss_grad_ft
+int op_table_loss_grad(const std::string &w, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                       const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, float *const *grad)
+{
+    if (!c) return fail(w + ": null context");
+    const int per = level_size(c, n_outs);
+    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
+    int L = 0;
+    CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, grad, &L));
+    CHK(check_grad_table(w, table, n_outs, ref, grad));
+    GradOpts o;
+    CHK(resolve_grad_opts(w, opts, ft_opts, ft, &o));
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<DevBytes> dt((size_t)n_outs), dg((size_t)n_outs);
+    std::vector<const float *> ptrs((size_t)n_outs);
+    std::vector<float *> gptrs((size_t)n_outs);
+    std::vector<size_t> bytes((size_t)n_outs);
+    DevBytes dr;
+    for (int i = 0; i < n_outs; ++i) {
+        const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
+        bytes[(size_t)i] = (size_t)n * ch * (H >> j) * (W >> j) * sizeof(float);
+        HIPCHK(hipMalloc(&dt[(size_t)i].p, bytes[(size_t)i]));
+        HIPCHK(hipMemcpy(dt[(size_t)i].p, table[i], bytes[(size_t)i], hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&dg[(size_t)i].p, bytes[(size_t)i]));
+        ptrs[(size_t)i] = (const float *)dt[(size_t)i].p;
+        gptrs[(size_t)i] = (float *)dg[(size_t)i].p;
+    }
+    HIPCHK(hipMalloc(&dr.p, (size_t)n * 3 * H * W * sizeof(float)));
+    HIPCHK(hipMemcpy(dr.p, ref, (size_t)n * 3 * H * W * sizeof(float), hipMemcpyHostToDevice));
+    CHK(table_loss_grad_device(w, c, ptrs.data(), n_outs, n, H, W, (const float *)dr.p, flow_scale, o, gptrs.data(), nullptr));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n_outs; ++i) HIPCHK(hipMemcpy(grad[i], gptrs[(size_t)i], bytes[(size_t)i], hipMemcpyDeviceToHost));
+    return 0;
 }
 
 }  // namespace
@@ -423,14 +486,7 @@ int b2f_loss_grad_defaults(b2f_loss_grad_opts *o)
 int b2f_table_loss_grad_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
                              const b2f_loss_grad_opts *opts, float *const *grad) try
 {
-    const std::string w(__func__);
-    int L = 0;
-    CHK(check_table_loss(w, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, grad, &L));
-    CHK(check_grad_table(w, table, n_outs, ref, grad));
-    b2f_loss_grad_opts o;
-    CHK(resolve_grad_opts(w, opts, &o));
-    table_loss_grad_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o, grad);
-    return 0;
+    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, opts, nullptr, false, grad);
 }
 B2F_CATCH("b2f_table_loss_grad_host")
 
@@ -438,7 +494,9 @@ B2F_CATCH("b2f_table_loss_grad_host")
 int b2f_table_loss_grad_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
                                const b2f_loss_grad_opts *opts, float *const *dev_grad, void *stream) try
 {
-    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, opts, dev_grad, stream);
+    GradOpts o;
+    CHK(resolve_grad_opts(__func__, opts, nullptr, false, &o));
+    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
 }
 B2F_CATCH("b2f_table_loss_grad_device")
 
@@ -446,38 +504,44 @@ B2F_CATCH("b2f_table_loss_grad_device")
 int b2f_op_table_loss_grad(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                            const b2f_loss_grad_opts *opts, float *const *grad) try
 {
-    const std::string w(__func__);
-    if (!c) return fail(w + ": null context");
-    const int per = level_size(c, n_outs);
-    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
-    int L = 0;
-    CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, grad, &L));
-    CHK(check_grad_table(w, table, n_outs, ref, grad));
-    b2f_loss_grad_opts o;
-    CHK(resolve_grad_opts(w, opts, &o));
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<DevBytes> dt((size_t)n_outs), dg((size_t)n_outs);
-    std::vector<const float *> ptrs((size_t)n_outs);
-    std::vector<float *> gptrs((size_t)n_outs);
-    std::vector<size_t> bytes((size_t)n_outs);
-    DevBytes dr;
-    for (int i = 0; i < n_outs; ++i) {
-        const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
-        bytes[(size_t)i] = (size_t)n * ch * (H >> j) * (W >> j) * sizeof(float);
-        HIPCHK(hipMalloc(&dt[(size_t)i].p, bytes[(size_t)i]));
-        HIPCHK(hipMemcpy(dt[(size_t)i].p, table[i], bytes[(size_t)i], hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc(&dg[(size_t)i].p, bytes[(size_t)i]));
-        ptrs[(size_t)i] = (const float *)dt[(size_t)i].p;
-        gptrs[(size_t)i] = (float *)dg[(size_t)i].p;
-    }
-    HIPCHK(hipMalloc(&dr.p, (size_t)n * 3 * H * W * sizeof(float)));
-    HIPCHK(hipMemcpy(dr.p, ref, (size_t)n * 3 * H * W * sizeof(float), hipMemcpyHostToDevice));
-    CHK(table_loss_grad_device(w, c, ptrs.data(), n_outs, n, H, W, (const float *)dr.p, flow_scale, &o, gptrs.data(), nullptr));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n_outs; ++i) HIPCHK(hipMemcpy(grad[i], gptrs[(size_t)i], bytes[(size_t)i], hipMemcpyDeviceToHost));
-    return 0;
+    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, opts, nullptr, false, grad);
 }
 B2F_CATCH("b2f_op_table_loss_grad")
+
+// ---- the same with the fine-tuning criteria of README.md:89-102 (b2f_tableloss_grad_ft.hip) ----
+int b2f_loss_grad_ft_defaults(b2f_loss_grad_ft_opts *o)
+{
+    if (!o) return fail("b2f_loss_grad_ft_defaults: null argument");
+    b2f_loss_grad_opts t;
+    (void)b2f_loss_grad_defaults(&t);
+    *o = loss_grad_ft_from(t);
+    o->smooth_second_order = 1;
+    o->pme_criterion = 1;
+    return 0;
+}
+
+int b2f_table_loss_grad_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                                const b2f_loss_grad_ft_opts *opts, float *const *grad) try
+{
+    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, nullptr, opts, true, grad);
+}
+B2F_CATCH("b2f_table_loss_grad_ft_host")
+
+int b2f_table_loss_grad_ft_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                                  const b2f_loss_grad_ft_opts *opts, float *const *dev_grad, void *stream) try
+{
+    GradOpts o;
+    CHK(resolve_grad_opts(__func__, nullptr, opts, true, &o));
+    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
+}
+B2F_CATCH("b2f_table_loss_grad_ft_device")
+
+int b2f_op_table_loss_grad_ft(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                              const b2f_loss_grad_ft_opts *opts, float *const *grad) try
+{
+    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, nullptr, opts, true, grad);
+}
+B2F_CATCH("b2f_op_table_loss_grad_ft")
 
 // test.lua:266-297 on the CPU
 int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,

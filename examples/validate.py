@@ -8,13 +8,15 @@ was trained on (back2future.LOSS_OBJECTIVES, the commands of the reference's REA
 second-order smoothness and the brightness and gradient constancy of OBGCC, from records of 192 bytes (objective="finetune").
 --grad also computes `gradOutputs` of train.lua:428-468, the gradient of the pme objective with respect to every tensor of the output
 table (Model.forwardLossGrad, in the same pass as the records), under the chosen options (--size-average; --objective Ours-Hard --
-the gradients of the two Soft objectives are not provided), and prints per level and tensor its L2 norm and largest magnitude over
-the clip.
+--grad refuses the two Soft objectives), and prints per level and tensor its L2 norm and largest magnitude over the clip.  --grad-ft
+does the same with the gradients of SecondOrderSmoothnessCriterion and OBGCCriterion (back2future.loss_grad_ft_options): any
+--objective NAME, or without one both criteria with alpha = beta = gamma = 1; its loss lines come from the 192-byte records.
 
-Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME] [--grad]
+Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME]
+       [--grad | --grad-ft]
 FRAMES_DIR: 8-bit frames, sorted by name; they are cropped (top left) to multiples of 64 and normalized with
 back2future.normalize.  MODEL as for examples/run_sequence.py.  --scale: pixels per unit of raw network flow (default 20).
-Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`; with --grad then one line
+Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`; with --grad or --grad-ft then one line
 `grad LEVEL TENSOR l2 max` per level and tensor (f, p for Soft models, o, iw1, iw3).
 """
 import os
@@ -39,8 +41,11 @@ def load_unit(path, H, W):
 def main():
     args = list(sys.argv[1:])
     scale, like, objective = 20.0, "test", None
-    size_average, grad = "--size-average" in args, "--grad" in args
-    args = [a for a in args if a not in ("--size-average", "--grad")]
+    size_average, grad_ft = "--size-average" in args, "--grad-ft" in args
+    grad = "--grad" in args or grad_ft
+    if "--grad" in args and grad_ft:
+        sys.exit("--grad and --grad-ft exclude one another")
+    args = [a for a in args if a not in ("--size-average", "--grad", "--grad-ft")]
     for flag in ("--scale", "--like", "--objective"):
         if flag in args:
             i = args.index(flag)
@@ -61,9 +66,10 @@ def main():
     options = None
     if grad:
         try:
-            options = back2future.loss_grad_options(size_average=size_average, objective=objective)
+            make = back2future.loss_grad_ft_options if grad_ft else back2future.loss_grad_options
+            options = make(size_average=size_average, objective=objective)
         except ValueError as e:
-            sys.exit("--grad: %s" % e)
+            sys.exit("%s: %s" % ("--grad-ft" if grad_ft else "--grad", e))
     src, model = args
     names = sorted(f for f in os.listdir(src) if f.lower().endswith(EXTS))
     if len(names) < 3:
@@ -89,7 +95,10 @@ def main():
             records.append(m.forwardLoss(x, flow_scale=scale, objective="pme" if objective is None else "finetune"))
     tensors = ("f", "p", "o", "iw1", "iw3") if m.past_flow else ("f", "o", "iw1", "iw3")
     m.close()
-    s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, objective=objective)
+    if grad_ft and objective is None:     # the defaults of loss_grad_ft_options
+        s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, smooth_second_order=True, pme_criterion="OBGCC")
+    else:
+        s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, objective=objective)
     for f, v in zip(names[1:-1], s["loss"]):
         print("%s %r" % (os.path.splitext(f)[0], float(v)))
     print("mean %r" % s["mean"])

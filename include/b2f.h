@@ -603,7 +603,7 @@ B2F_API int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H
  * every criterion's backward, times its option weight and level_weights[l], is added (train.lua:428-468).  The scope is -optimize
  * pme with the defaults of opts.lua: SmoothnessCriterion with the L1 penalty for the flows and the quadratic one for the
  * occlusions, ConstVelCriterion, OBCCriterion with L1, OcclusionPriorCriterion -- the objective of Ours-Hard.  The gradients of
- * SecondOrderSmoothnessCriterion and OBGCCriterion (the *_ft entries' two criteria) are not provided.
+ * SecondOrderSmoothnessCriterion and OBGCCriterion (the *_ft entries' two criteria) are those of the *_grad_ft entries below.
  * The specification is the reference's updateGradInput functions, not the mathematical derivative of their outputs; they differ in
  * three places, all kept:
  *   1. OcclusionPriorCriterion.lua:64-65 returns 1 - o[other]; the derivative of 1 - o0 * o1 is -o[other].  The value is larger by
@@ -664,6 +664,63 @@ B2F_API int b2f_forward_loss_grad_device(b2f_ctx *ctx, const void *dev_in, int i
 /* b2f_forward_loss_grad over several GPUs: the n triplets are split with b2f_shard_range; one context's bits */
 B2F_API int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
                                 const b2f_loss_grad_opts *opts, unsigned long long *loss, float *const *grad, int n_outs);
+/* ---- the gradient of the Soft models' fine-tuning objective with respect to the output table ----
+ * Ours-Soft-ft-KITTI and Ours-Soft-ft-Sintel were fine-tuned with -smooth_second_order -pme_criterion OBGCC (README.md:89-102).  The
+ * *_grad_ft entries are the *_grad entries above with two terms of a level replaced where their flag is set; everything not named
+ * here -- inputs, coefficients, CV_c, S(o[c],D2), the prior, the rule for a weight of exactly 0, one rounding to fp32 on store -- is as
+ * above, and with both flags 0 every element is the expression above, bit for bit.  The specification is again updateGradInput:
+ * criterions/SecondOrderSmoothnessCriterion.lua:77-104 and criterions/OBGCCriterion.lua:151-300, both with the L1 penalty.
+ * smooth_second_order: S(f[c],D1) and S(p[c],D1) become S2(f[c]) and S2(p[c]).  With gx, gy, m and E of the *_ft records above:
+ *   wx(x,y) = E(-20.0 * (m((x,y), (x-1,y)) + m((x,y), (x+1,y)))) and qx(F)(x,y) = D1(gx(F)(x,y)) * wx(x,y) where 0 < x and x + 1 < w;
+ *   elsewhere qx is not formed and counts as +0.0; wy, qy the same over rows (a map with w < 3 or h < 3 has no term on that axis,
+ *   the per-pixel rule of the records; the Lua slices cannot express it)
+ *   S2(F)(x,y) = (((((2.0 * qy(x,y)) + (2.0 * qx(x,y))) - qy(x,y+1)) - qx(x+1,y)) - qy(x,y-1)) - qx(x-1,y)      (lines 92-97)
+ *   G_f[c] = k_s * S2(f[c]) + k_cv * CV_c, G_p[c] = k_s * S2(p[c]) - k_cv * CV_c
+ * pme_criterion = 1 (OBGCC): per direction d with I = iw_d, R = R_j, m_d and the weight o[1-d] as above, per channel c
+ *   delta_c = (double)I[c] - (double)R[c]; ex_c = dx_c and ey_c = dy_c of the *_ft records (0 in the last column / row)
+ *   T(F) = the enabled ones of  alpha * F(delta), -(gamma * F(ey(x,y))), gamma * F(ey(x,y-1)), -(beta * F(ex(x,y))),
+ *          beta * F(ex(x-1,y))  added left to right; the third only where y > 0, the fifth only where x > 0; a term whose weight
+ *          alpha, beta or gamma is exactly 0 is not evaluated; +0.0 without a term
+ *   G_iw_d[c] = m_d ? k_p * (T(D1 of channel c) * (double)o[1-d]) : +0.0
+ *   PO_{1-d}  = m_d ? T(v -> (P1(v_0) + P1(v_1)) + P1(v_2), the sum over the three channels) : 1.0
+ * alpha = 1, beta = gamma = 0 give OBCC's bits.  Four more places where the gradient is not the derivative of the records' value,
+ * all kept:
+ *   1. alpha multiplies the gradient (lines 202, 215); updateOutput never applies it (line 97).
+ *   2. Lines 207 and 212 add the neighbour's derivative D1(ey(x,y-1)), D1(ex(x-1,y)) to the pixel (x,y) before lines 246 and 254
+ *      mask and weigh it: with the pixel's own m_d and o[1-d], where the derivative has the neighbour's.
+ *   3. Lines 215-219 build the occlusion gradient from the penalty's values with the derivative's signs, so PO is not the pixel's
+ *      error e_d + beta ... ; in the last column and row, where ex / ey is 0, it subtracts P1(0) = 1e-3 per channel.
+ *   4. model.lua:171 writes -pme_gamma into a field named `gamm`, so a reference run keeps gamma = 1; the option is honoured here as
+ *      given (back2future.LOSS_OBJECTIVES).
+ * (The Lua accumulates the warped images' forward differences over the two directions, lines 194-195 without a reset; like the
+ * records, each direction takes its own image here.)                                                                             */
+typedef struct b2f_loss_grad_ft_opts {
+    double smooth_flow, const_vel, pme, smooth_occ, prior_occ;   /* as b2f_loss_grad_opts */
+    double level_weights[7];
+    int size_average;
+    int smooth_second_order;                                     /* -smooth_second_order: 0 | 1 */
+    int pme_criterion;                                           /* -pme_criterion: 0 OBCC, 1 OBGCC */
+    double pme_alpha, pme_beta, pme_gamma;                       /* OBGCC's weights; each finite and >= 0 */
+} b2f_loss_grad_ft_opts;
+/* b2f_loss_grad_defaults, smooth_second_order = 1, pme_criterion = 1, alpha = beta = gamma = 1 */
+B2F_API int b2f_loss_grad_ft_defaults(b2f_loss_grad_ft_opts *opts);
+/* The six entries above with these options: same arguments, same checks (and pme_criterion in {0, 1}), same sub-batching, same
+ * workspaces; a refusal writes nothing.  The optional records of the two forward entries are the 24 words of b2f_forward_loss_ft. */
+B2F_API int b2f_table_loss_grad_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                                double flow_scale, const b2f_loss_grad_ft_opts *opts, float *const *grad);
+B2F_API int b2f_table_loss_grad_ft_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W,
+                                  const float *dev_ref, double flow_scale, const b2f_loss_grad_ft_opts *opts,
+                                  float *const *dev_grad, void *stream);
+B2F_API int b2f_op_table_loss_grad_ft(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                              double flow_scale, const b2f_loss_grad_ft_opts *opts, float *const *grad);
+B2F_API int b2f_forward_loss_grad_ft(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale,
+                             const b2f_loss_grad_ft_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                             float *const *outs);
+B2F_API int b2f_forward_loss_grad_ft_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                    const b2f_loss_grad_ft_opts *opts, unsigned long long *dev_loss, float *const *dev_grad,
+                                    int n_outs, void *stream);
+B2F_API int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
+                                   const b2f_loss_grad_ft_opts *opts, unsigned long long *loss, float *const *grad, int n_outs);
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature
