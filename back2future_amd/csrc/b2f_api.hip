@@ -1472,36 +1472,33 @@ int forward_table_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int 
     return 0;
 }
 
-// the table of nb triplets into tab, then its records into d_loss; all on s
-int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const LossPlan &lp, float *const *tab,
-                     unsigned long long *d_loss)
+// the table of nb triplets into tab, its records into d_loss where wanted (else nullptr), its gradient table (train.lua:428-468) from the
+// checked options *o into grad where wanted; all on s.  The pyramid of R is built once: by the records' launch where there is one.
+int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const GradOpts *o, const LossPlan &lp,
+                     float *const *tab, unsigned long long *d_loss, float *const *grad)
 {
     CHK(forward_table_run(c, s, d_in, nb, H, W, lp, tab));
-    CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(lp.L, nb, H, W) * sizeof(float)));
-    ProfEvent pe;
-    const bool timed = prof_open(c, s, "table_loss", &pe);
     const size_t hw = (size_t)H * W;
-    hipError_t e = launch_table_loss(tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, (float *)c->loss_pyr.dev, flow_scale, d_loss, s, lp.words);
-    if (timed) prof_close(c, s, pe);
-    HIPCHK(e);
-    if (lp.words == B2F_LOSS_WORDS) return 0;
-    ProfEvent pf;
-    const bool timed_ft = prof_open(c, s, "table_loss_ft", &pf);
-    e = launch_table_loss_ft_terms(tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, (float *)c->loss_pyr.dev, flow_scale, d_loss, s);
-    if (timed_ft) prof_close(c, s, pf);
-    HIPCHK(e);
+    if (d_loss) CHK(table_loss_run(c, s, tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, d_loss, lp.words));
+    if (grad) CHK(table_loss_grad_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, *o, d_loss == nullptr));
     return 0;
 }
 
-// the table of nb triplets into tab, its records into d_loss where wanted, its gradient table (train.lua:428-468) into grad; all on s.
-// The pyramid of R is built once: by the records' launch where there is one.
-int forward_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const GradOpts &o,
-                          const LossPlan &lp, float *const *tab, unsigned long long *d_loss, float *const *grad)
+// triplets per sub-batch of a b2f_forward_loss* call: the host_subbatch_pixels budget, within the launchers' limit of images
+int loss_subbatch(const b2f_ctx *c, int n, int H, int W)
 {
-    if (d_loss) CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, lp, tab, d_loss));
-    else CHK(forward_table_run(c, s, d_in, nb, H, W, lp, tab));
-    const size_t hw = (size_t)H * W;
-    return table_loss_grad_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, o, d_loss == nullptr);
+    return (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / ((long long)H * W)));
+}
+
+// grows the context's loss workspace to the plan and points tab, and gr where asked (a plan with_grad), at the plan's tensors in it
+int loss_work_tables(b2f_ctx *c, const LossPlan &lp, std::vector<float *> &tab, std::vector<float *> *gr)
+{
+    CHK(ensure_dev_work(c->loss_work, lp.bytes));
+    for (int i = 0; i < lp.n_outs; ++i) {
+        tab.push_back((float *)(c->loss_work.dev + lp.off[(size_t)i]));
+        if (gr) gr->push_back((float *)(c->loss_work.dev + lp.goff[(size_t)i]));
+    }
+    return 0;
 }
 
 // what b2f_forward_loss_grad* check beyond check_forward_loss: the options (into *o) and the gradient table's pointers
@@ -1523,6 +1520,39 @@ struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub
     ~ReqBatchScope() { c->req_batch = 0; }
 };
 
+// the sub-batch loop of b2f_forward_loss* and b2f_forward_loss_grad* on checked arguments: upload, forward_loss_run, download of the
+// records (loss), the gradient table (grad, from *o) and the table (outs), each where not null
+int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, bool ft, const GradOpts *o, unsigned long long *loss,
+                          float *const *grad, float *const *outs)
+{
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw = (size_t)H * W;
+    const int sb = loss_subbatch(c, n, H, W);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, true, ft, grad != nullptr);
+    std::vector<float *> tab, gr;
+    CHK(loss_work_tables(c, lp, tab, grad ? &gr : nullptr));
+    float *d_in = (float *)(c->loss_work.dev + lp.in_off);
+    unsigned long long *d_loss = loss ? (unsigned long long *)(c->loss_work.dev + lp.loss_off) : nullptr;
+    ReqBatchScope rb(c, req > 0 ? req : n);
+    hipStream_t s = c->stream;
+    for (int b0 = 0; b0 < n; b0 += sb) {
+        const int nb = std::min(sb, n - b0);
+        HIPCHK(hipMemcpyAsync(d_in, x + (size_t)b0 * 9 * hw, (size_t)nb * 9 * hw * sizeof(float), hipMemcpyHostToDevice, s));
+        // (a shorter last sub-batch lays its tensors out for nb images in the same buffers)
+        CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, o, lp, tab.data(), d_loss, grad ? gr.data() : nullptr));
+        if (loss)
+            HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * lp.words, d_loss, (size_t)nb * lp.L * lp.words * sizeof(unsigned long long),
+                                  hipMemcpyDeviceToHost, s));
+        for (int i = 0; i < lp.n_outs; ++i) {
+            const size_t per_img = lp.cnt[(size_t)i] / (size_t)sb;
+            if (grad) HIPCHK(hipMemcpyAsync(grad[i] + (size_t)b0 * per_img, gr[(size_t)i], (size_t)nb * per_img * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (outs) HIPCHK(hipMemcpyAsync(outs[i] + (size_t)b0 * per_img, tab[(size_t)i], (size_t)nb * per_img * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
 }  // namespace
 
 // b2f_forward_loss on a shard: `req` is the caller's n (b2f_multi_forward_loss passes its own down)
@@ -1536,32 +1566,7 @@ int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, in
     if (outs && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be 0 or (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
     for (int i = 0; i < n_outs; ++i)
         if (!outs[i]) return fail(w + ": null tensor in outs");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)H * W;
-    const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
-    const LossPlan lp = make_loss_plan(c, sb, H, W, true, ft);
-    CHK(ensure_dev_work(c->loss_work, lp.bytes));
-    char *base = c->loss_work.dev;
-    std::vector<float *> tab((size_t)lp.n_outs);
-    for (int i = 0; i < lp.n_outs; ++i) tab[(size_t)i] = (float *)(base + lp.off[(size_t)i]);
-    float *d_in = (float *)(base + lp.in_off);
-    unsigned long long *d_loss = (unsigned long long *)(base + lp.loss_off);
-    ReqBatchScope rb(c, req > 0 ? req : n);
-    hipStream_t s = c->stream;
-    for (int b0 = 0; b0 < n; b0 += sb) {
-        const int nb = std::min(sb, n - b0);
-        HIPCHK(hipMemcpyAsync(d_in, x + (size_t)b0 * 9 * hw, (size_t)nb * 9 * hw * sizeof(float), hipMemcpyHostToDevice, s));
-        // (a shorter last sub-batch lays its tensors out for nb images in the same buffers)
-        CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, lp, tab.data(), d_loss));
-        HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * lp.words, d_loss, (size_t)nb * lp.L * lp.words * sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost, s));
-        for (int i = 0; i < n_outs; ++i) {
-            const size_t per_img = lp.cnt[(size_t)i] / (size_t)sb;
-            HIPCHK(hipMemcpyAsync(outs[i] + (size_t)b0 * per_img, tab[(size_t)i], (size_t)nb * per_img * sizeof(float), hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return 0;
+    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, ft, nullptr, loss, nullptr, outs);
 }
 
 // b2f_forward_loss_grad (ft = false) or b2f_forward_loss_grad_ft on a shard: `req` is the caller's n (b2f_multi_forward_loss_grad* pass
@@ -1580,36 +1585,7 @@ int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int 
         for (int k = 0; k < n_outs; ++k)
             if (outs[i] == grad[k]) return fail(w + ": the gradient table must not alias outs");
     }
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)H * W;
-    const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
-    const LossPlan lp = make_loss_plan(c, sb, H, W, true, ft, true);
-    CHK(ensure_dev_work(c->loss_work, lp.bytes));
-    char *base = c->loss_work.dev;
-    std::vector<float *> tab((size_t)lp.n_outs), gr((size_t)lp.n_outs);
-    for (int i = 0; i < lp.n_outs; ++i) {
-        tab[(size_t)i] = (float *)(base + lp.off[(size_t)i]);
-        gr[(size_t)i] = (float *)(base + lp.goff[(size_t)i]);
-    }
-    float *d_in = (float *)(base + lp.in_off);
-    unsigned long long *d_loss = loss ? (unsigned long long *)(base + lp.loss_off) : nullptr;
-    ReqBatchScope rb(c, req > 0 ? req : n);
-    hipStream_t s = c->stream;
-    for (int b0 = 0; b0 < n; b0 += sb) {
-        const int nb = std::min(sb, n - b0);
-        HIPCHK(hipMemcpyAsync(d_in, x + (size_t)b0 * 9 * hw, (size_t)nb * 9 * hw * sizeof(float), hipMemcpyHostToDevice, s));
-        CHK(forward_loss_grad_run(c, s, d_in, nb, H, W, flow_scale, o, lp, tab.data(), d_loss, gr.data()));
-        if (loss)
-            HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * lp.words, d_loss, (size_t)nb * lp.L * lp.words * sizeof(unsigned long long),
-                                  hipMemcpyDeviceToHost, s));
-        for (int i = 0; i < n_outs; ++i) {
-            const size_t per_img = lp.cnt[(size_t)i] / (size_t)sb;
-            HIPCHK(hipMemcpyAsync(grad[i] + (size_t)b0 * per_img, gr[(size_t)i], (size_t)nb * per_img * sizeof(float), hipMemcpyDeviceToHost, s));
-            if (outs) HIPCHK(hipMemcpyAsync(outs[i] + (size_t)b0 * per_img, tab[(size_t)i], (size_t)nb * per_img * sizeof(float), hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return 0;
+    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, ft, &o, loss, grad, outs);
 }
 
 extern "C" {
@@ -1631,33 +1607,34 @@ int b2f_forward_loss_grad_ft(b2f_ctx *c, const float *x, int n, int H, int W, do
 B2F_CATCH("b2f_forward_loss_grad_ft")
 
 extern "C++" {
-// b2f_forward_loss_grad_device (ft = false) and b2f_forward_loss_grad_ft_device
-static int forward_loss_grad_device(const std::string &w, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
-                                    const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, unsigned long long *dev_loss,
-                                    float *const *dev_grad, int n_outs, void *stream)
+// the four device entries: b2f_forward_loss_device / _ft_device (with_grad = false: dev_loss required, no gradient table) and
+// b2f_forward_loss_grad_device / _grad_ft_device (with_grad: dev_grad required, dev_loss optional)
+static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                               const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, bool with_grad, unsigned long long *dev_loss,
+                               float *const *dev_grad, int n_outs, void *stream)
 {
-    if (!c || !dev_in || !dev_grad) return fail(w + ": null argument");
+    if (!c || !dev_in || (with_grad ? !dev_grad : !dev_loss)) return fail(w + ": null argument");
     if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
     GradOpts o;
-    CHK(check_forward_loss_grad(c, w, opts, ft_opts, ft, dev_grad, n_outs, &o));
+    if (with_grad) CHK(check_forward_loss_grad(c, w, opts, ft_opts, ft, dev_grad, n_outs, &o));
     uintptr_t bits = (uintptr_t)dev_in | (uintptr_t)dev_loss;
-    for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_grad[i];
+    for (int i = 0; with_grad && i < n_outs; ++i) bits |= (uintptr_t)dev_grad[i];
     if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
-    const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
+    const int sb = loss_subbatch(c, n, H, W);
     const LossPlan lp = make_loss_plan(c, sb, H, W, false, ft);
-    CHK(ensure_dev_work(c->loss_work, lp.bytes));
-    std::vector<float *> tab((size_t)lp.n_outs), gr((size_t)lp.n_outs);
-    for (int i = 0; i < lp.n_outs; ++i) tab[(size_t)i] = (float *)(c->loss_work.dev + lp.off[(size_t)i]);
+    std::vector<float *> tab, gr((size_t)lp.n_outs);
+    CHK(loss_work_tables(c, lp, tab, nullptr));
     ReqBatchScope rb(c, n);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     for (int b0 = 0; b0 < n; b0 += sb) {
         // the sub-batch's part of the caller's gradient tensors: image b0 of every one
-        for (int i = 0; i < lp.n_outs; ++i) gr[(size_t)i] = dev_grad[i] + (size_t)b0 * (lp.cnt[(size_t)i] / (size_t)sb);
-        CHK(forward_loss_grad_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, o, lp, tab.data(),
-                                  dev_loss ? dev_loss + (size_t)b0 * lp.L * lp.words : nullptr, gr.data()));
+        for (int i = 0; with_grad && i < lp.n_outs; ++i) gr[(size_t)i] = dev_grad[i] + (size_t)b0 * (lp.cnt[(size_t)i] / (size_t)sb);
+        // (without a gradient table o is unresolved and forward_loss_run does not read it)
+        CHK(forward_loss_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, &o, lp, tab.data(),
+                             dev_loss ? dev_loss + (size_t)b0 * lp.L * lp.words : nullptr, with_grad ? gr.data() : nullptr));
     }
     return 0;
 }
@@ -1667,14 +1644,14 @@ static int forward_loss_grad_device(const std::string &w, b2f_ctx *c, const void
 int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
                                  unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    return forward_loss_grad_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, opts, nullptr, false, dev_loss, dev_grad, n_outs, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, opts, nullptr, false, true, dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_device")
 
 int b2f_forward_loss_grad_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                                     const b2f_loss_grad_ft_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    return forward_loss_grad_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, opts, true, dev_loss, dev_grad, n_outs, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, opts, true, true, dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_ft_device")
 
@@ -1692,34 +1669,11 @@ int b2f_forward_loss_ft(b2f_ctx *c, const float *x, int n, int H, int W, double 
 }
 B2F_CATCH("b2f_forward_loss_ft")
 
-// b2f_forward_loss_device / b2f_forward_loss_ft_device
-static int forward_loss_device(const std::string &w, bool ft, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
-                               unsigned long long *dev_loss, void *stream)
-{
-    if (!c || !dev_in || !dev_loss) return fail(w + ": null argument");
-    if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
-    CHK(check_forward_loss(c, w, n, H, W, flow_scale));
-    if (((uintptr_t)dev_in | (uintptr_t)dev_loss) & 15) return fail(w + ": device buffers must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)H * W;
-    const int sb = (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / (long long)hw));
-    const LossPlan lp = make_loss_plan(c, sb, H, W, false, ft);
-    CHK(ensure_dev_work(c->loss_work, lp.bytes));
-    std::vector<float *> tab((size_t)lp.n_outs);
-    for (int i = 0; i < lp.n_outs; ++i) tab[(size_t)i] = (float *)(c->loss_work.dev + lp.off[(size_t)i]);
-    ReqBatchScope rb(c, n);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    for (int b0 = 0; b0 < n; b0 += sb)
-        CHK(forward_loss_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, lp, tab.data(),
-                             dev_loss + (size_t)b0 * lp.L * lp.words));
-    return 0;
-}
-
 // model:forward + test.lua:266-297 on device pointers
 int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                             void *stream) try
 {
-    return forward_loss_device(__func__, false, c, dev_in, in_kind, n, H, W, flow_scale, dev_loss, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, false, false, dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_device")
 
@@ -1727,7 +1681,7 @@ B2F_CATCH("b2f_forward_loss_device")
 int b2f_forward_loss_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                                void *stream) try
 {
-    return forward_loss_device(__func__, true, c, dev_in, in_kind, n, H, W, flow_scale, dev_loss, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, true, false, dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_ft_device")
 

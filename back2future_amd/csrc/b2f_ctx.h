@@ -544,8 +544,12 @@ struct GradOpts {
 // b2f_tableloss.hip: opts (ft = false) or ft_opts (ft = true), or that kind's defaults where it is null, into *o; refused as
 // include/b2f.h says
 int resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, GradOpts *o);
+// b2f_tableloss.hip: the records of test.lua:266-297 of n images on s, under the profile row table_loss; words = B2F_LOSS_WORDS, or
+// B2F_LOSS_FT_WORDS with the fine-tuning terms behind them (table_loss_ft).  Builds R_1 .. R_{L-1} in c->loss_pyr first.
+int table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, int L, bool past, int n, int H, int W, const float *dev_ref,
+                   size_t ref_stride, double flow_scale, unsigned long long *dev_loss, int words);
 // b2f_tableloss.hip: the gradient table of train.lua:428-468 of n images on s, from checked options; with_pyr: R_1 .. R_{L-1} are built
-// first (false: launch_table_loss has built them on s)
+// first (false: table_loss_run has built them on s)
 int table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
                         const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, bool with_pyr);
 // b2f_api.hip: b2f_forward_loss_grad (ft = false, opts) or b2f_forward_loss_grad_ft (ft = true, ft_opts) on n of a request of `req`

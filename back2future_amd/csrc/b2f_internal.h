@@ -360,25 +360,20 @@ hipError_t launch_flow_warp(const float *flow, const float *occ_prob, int n, int
                             const void *im3, size_t image_stride, int in_kind, void *warped, int warped_kind, unsigned long long *photo,
                             hipStream_t s, const float *past_flow = nullptr);
 
-// ---- the unsupervised validation loss (b2f_tableloss.hip; the per-pixel functions: b2f_tableloss.h) --------------
-// test.lua:266-297 on the output table: table = L x (4 | 5) device tensors of n images in table order (a host array), ref = R_0 of
-// image 0, image b `ref_stride` samples further (3 H W for n x 3 x H x W, 9 H W for channels 3 .. 5 of the network's input), pyr =
-// table_loss_pyramid_floats(L, n, H, W) floats of workspace for R_1 .. R_{L-1}; loss: n x L x B2F_LOSS_WORDS words, zeroed on s first.
-// n <= 65535, H * W < 2^28, H and W multiples of 2^(L-1).  words: the width of a record (B2F_LOSS_WORDS, or B2F_LOSS_FT_WORDS with
-// the words from 16 on left zero)
+// ---- the unsupervised validation loss and its gradient (b2f_tableloss*.hip; the per-pixel functions: b2f_tableloss*.h) --------------
+// What the launchers share: table = L x (4 | 5) device tensors of n images in table order (a host array), ref = R_0 of image 0, image
+// b `ref_stride` samples further (3 H W for n x 3 x H x W, 9 H W for channels 3 .. 5 of the network's input), pyr =
+// table_loss_pyramid_floats(L, n, H, W) floats of workspace for R_1 .. R_{L-1}.  n <= 65535, H * W < 2^28, H and W multiples of 2^(L-1).
+// The records of test.lua:266-297 and R_1 .. R_{L-1} come from b2f_tableloss.hip (b2f_ctx.h: table_loss_run); the launchers below run
+// behind it, or behind its pyramid, on the same stream and read pyr.
 size_t table_loss_pyramid_floats(int L, int n, int H, int W);
-hipError_t launch_table_loss(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr,
-                             double flow_scale, unsigned long long *loss, hipStream_t s, int words = 16);
-// the fine-tuning terms of README.md:89-102 (b2f_tableloss_ft.hip; the per-pixel functions: b2f_tableloss_ft.h) into words 16 .. 23 of
-// records of B2F_LOSS_FT_WORDS words, behind launch_table_loss(..., B2F_LOSS_FT_WORDS) with the same arguments on the same stream:
-// that call zeroes the records and lays R_1 .. R_{L-1} into pyr, which this one reads
+// b2f_tableloss_ft.hip: the fine-tuning terms of README.md:89-102 into words 16 .. 23 of records of B2F_LOSS_FT_WORDS words, which the
+// records' launch has zeroed
 hipError_t launch_table_loss_ft_terms(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
                                       const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s);
-// b2f_tableloss.hip: R_1 .. R_{L-1} alone, laid out in pyr as launch_table_loss lays them (for a caller that wants no records)
-hipError_t launch_table_loss_pyramid(int L, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr, hipStream_t s);
-// b2f_tableloss_grad.hip: the gradient table of train.lua:428-468 (include/b2f.h: G_f, G_p, G_o, G_iw_d) behind either of the two on the
-// same stream: grad = L x (4 | 5) device tensors of n images with the table's shapes (a host array), none of them a tensor of the table
-// or ref; coef[j]: the coefficients of level j (b2f_host.h: loss_grad_coef).  Every element of grad is written.
+// b2f_tableloss_grad.hip: the gradient table of train.lua:428-468 (include/b2f.h: G_f, G_p, G_o, G_iw_d): grad = L x (4 | 5) device
+// tensors of n images with the table's shapes (a host array), none of them a tensor of the table or ref; coef[j]: the
+// coefficients of level j (b2f_host.h: loss_grad_coef).  Every element of grad is written.
 struct GradCoef;
 hipError_t launch_table_loss_grad(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
                                   const float *pyr, double flow_scale, const GradCoef *coef, hipStream_t s);

@@ -19,7 +19,7 @@ namespace b2f {
 namespace {
 
 constexpr int kPx = kLossPx;  // consecutive pixels of a row per thread (b2f_tableloss_dev.h: load_px)
-constexpr int kThreads = 256;
+constexpr int kThreads = kLossThreads;
 constexpr int kWave = 64;     // gfx950
 constexpr int kWaves = kThreads / kWave;
 constexpr int kWords = B2F_LOSS_WORDS;
@@ -149,75 +149,58 @@ __global__ void __launch_bounds__(kThreads) ref_pool_kernel(const float *in, siz
 size_t table_loss_pyramid_floats(int L, int n, int H, int W)
 {
     size_t t = 0;
-    for (int j = 1; j < L; ++j) t += (((size_t)n * 3 * (H >> j) * (W >> j)) + 3) & ~(size_t)3;   // every level 16-byte aligned
+    for (int j = 1; j < L; ++j) t += loss_level_floats(n, H >> j, W >> j);
     return t;
 }
 
+namespace {
+
+// R_j (j >= 1) from R_{j-1}, into its place in pyr
+hipError_t launch_ref_pool(const LossLevel *lv, int j, int n, float *pyr, hipStream_t s)
+{
+    const size_t total = (size_t)n * 3 * lv[j].h * lv[j].w;
+    hipLaunchKernelGGL(ref_pool_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, lv[j - 1].lp.ref, lv[j - 1].lp.ref_stride,
+                       2 * lv[j].h, 2 * lv[j].w, total, pyr + lv[j].pyr_off);
+    return hipGetLastError();
+}
+
+// R_1 .. R_{L-1} alone, for a caller that wants no records
+hipError_t launch_table_loss_pyramid(int L, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr, hipStream_t s)
+{
+    LossLevel lv[kLossMaxLevels];
+    if (!loss_levels(L, n, H, W, ref, ref_stride, pyr, lv)) return hipErrorInvalidValue;
+    for (int j = 1; j < L; ++j) {
+        const hipError_t e = launch_ref_pool(lv, j, n, pyr, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// The records of test.lua:266-297: see b2f_internal.h for the arguments.  loss: n x L x words words, zeroed on s first; words:
+// B2F_LOSS_WORDS, or B2F_LOSS_FT_WORDS with the words from 16 on left zero.  Lays R_1 .. R_{L-1} into pyr on the way: R_j is pooled
+// behind the records of level j - 1, whose long first launch gives the host time to enqueue the rest (with all the pooling passes in
+// front the stage measured 1 - 2 % slower: DESIGN.md 7.12).
 hipError_t launch_table_loss(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr,
                              double flow_scale, unsigned long long *loss, hipStream_t s, int words)
 {
-    const int per = past ? 5 : 4;
-    if (words < kWords) return hipErrorInvalidValue;
-    if (n <= 0 || n > 65535 || L < 1 || L > kLossMaxLevels || H <= 0 || W <= 0 || (size_t)H * W >= (size_t)kPhotoMaxPixels || H % (1 << (L - 1)) ||
-        W % (1 << (L - 1)) || !table || !ref || !loss || (L > 1 && !pyr) || ref_stride < (size_t)3 * H * W)
-        return hipErrorInvalidValue;
-    for (int i = 0; i < L * per; ++i)
-        if (!table[i]) return hipErrorInvalidValue;
+    LossLevel lv[kLossMaxLevels];
+    if (words < kWords || !loss || !loss_levels(table, nullptr, L, past, n, H, W, ref, ref_stride, pyr, flow_scale, lv)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(loss, 0, (size_t)n * L * words * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
-    const float *R = ref;
-    size_t R_stride = ref_stride;
     for (int j = 0; j < L; ++j) {
-        const int h = H >> j, w = W >> j;
-        const size_t hw = (size_t)h * w;
-        if (j > 0) {
-            const size_t total = (size_t)n * 3 * hw;
-            hipLaunchKernelGGL(ref_pool_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, R, R_stride, 2 * h, 2 * w,
-                               total, pyr);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            R = pyr;
-            R_stride = 3 * hw;
-            pyr += (total + 3) & ~(size_t)3;
-        }
-        const float *const *t = table + (size_t)j * per;
-        const LevelPtrs lp = {t[0], past ? t[1] : nullptr, t[per - 3], t[per - 2], t[per - 1], R, R_stride};
-        const size_t groups = (((size_t)w + kPx - 1) / kPx) * (size_t)h, blocks = (groups + kThreads - 1) / kThreads;
-        // a capped grid as for the photometric record: about eight blocks per CU over the whole call, at most 1024 per image (a
-        // full-HD image alone wraps the loop), so that few blocks add to a record
-        const size_t cap = std::min<size_t>(1024, std::max<size_t>(8, 2048 / (size_t)n));
-        const dim3 grid((unsigned)std::min(blocks, cap), (unsigned)n);
-        const float kd = (float)(flow_scale / (double)(1 << j));
+        const LossLevel &v = lv[j];
+        if (j > 0 && (e = launch_ref_pool(lv, j, n, pyr, s)) != hipSuccess) return e;
         unsigned long long *rec = loss + (size_t)j * words;
         if (past)
-            hipLaunchKernelGGL(table_loss_kernel<true>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * words);
+            hipLaunchKernelGGL(table_loss_kernel<true>, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, v.kd, rec, (size_t)L * words);
         else
-            hipLaunchKernelGGL(table_loss_kernel<false>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * words);
+            hipLaunchKernelGGL(table_loss_kernel<false>, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, v.kd, rec, (size_t)L * words);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-// R_1 .. R_{L-1} alone, laid out in pyr as launch_table_loss lays them (for a caller that wants no records)
-hipError_t launch_table_loss_pyramid(int L, int n, int H, int W, const float *ref, size_t ref_stride, float *pyr, hipStream_t s)
-{
-    if (n <= 0 || L < 1 || L > kLossMaxLevels || H <= 0 || W <= 0 || H % (1 << (L - 1)) || W % (1 << (L - 1)) || !ref || (L > 1 && !pyr) ||
-        ref_stride < (size_t)3 * H * W)
-        return hipErrorInvalidValue;
-    const float *R = ref;
-    size_t R_stride = ref_stride;
-    for (int j = 1; j < L; ++j) {
-        const int h = H >> j, w = W >> j;
-        const size_t total = (size_t)n * 3 * h * w;
-        hipLaunchKernelGGL(ref_pool_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, R, R_stride, 2 * h, 2 * w, total,
-                           pyr);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        R = pyr;
-        R_stride = (size_t)3 * h * w;
-        pyr += (total + 3) & ~(size_t)3;
-    }
-    return hipSuccess;
-}
+}  // namespace
 
 int ensure_dev_work(DevWork &dw, size_t bytes)
 {
@@ -289,21 +272,8 @@ int table_loss_device(const std::string &w, bool ft, b2f_ctx *c, const float *co
     if (host_memory(dev_ref) || host_memory(dev_loss)) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss / b2f_table_loss_host)");
     for (int i = 0; i < n_outs; ++i)
         if (host_memory(dev_table[i])) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss / b2f_table_loss_host)");
-    CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    ProfEvent pe;
-    const bool timed = prof_open(c, s, "table_loss", &pe);
-    hipError_t e = launch_table_loss(dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, (float *)c->loss_pyr.dev, flow_scale, dev_loss, s,
-                                     ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
-    if (timed) prof_close(c, s, pe);
-    HIPCHK(e);
-    if (!ft) return 0;
-    ProfEvent pf;
-    const bool timed_ft = prof_open(c, s, "table_loss_ft", &pf);
-    e = launch_table_loss_ft_terms(dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, (float *)c->loss_pyr.dev, flow_scale, dev_loss, s);
-    if (timed_ft) prof_close(c, s, pf);
-    HIPCHK(e);
-    return 0;
+    return table_loss_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, flow_scale, dev_loss,
+                          ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
 }
 
 // b2f_op_table_loss / b2f_op_table_loss_ft
@@ -371,8 +341,40 @@ int b2f::resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts,
     return why ? fail(w + ": " + why) : 0;
 }
 
+namespace {
+
+// a launch on s as the row `name` of b2f_profile_read
+template <class Launch>
+int timed_launch(b2f_ctx *c, hipStream_t s, const char *name, Launch launch)
+{
+    ProfEvent pe;
+    const bool timed = prof_open(c, s, name, &pe);
+    const hipError_t e = launch();
+    if (timed) prof_close(c, s, pe);
+    HIPCHK(e);
+    return 0;
+}
+
+}  // namespace
+
+// the records of n images on s: words = B2F_LOSS_WORDS, or B2F_LOSS_FT_WORDS with the fine-tuning terms behind them.  Builds R_1 ..
+// R_{L-1} in the context's workspace, where table_loss_grad_run(..., with_pyr = false) on the same arguments and stream finds them.
+int b2f::table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, int L, bool past, int n, int H, int W, const float *dev_ref,
+                        size_t ref_stride, double flow_scale, unsigned long long *dev_loss, int words)
+{
+    CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
+    float *pyr = (float *)c->loss_pyr.dev;
+    CHK(timed_launch(c, s, "table_loss", [&] {
+        return launch_table_loss(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s, words);
+    }));
+    if (words != B2F_LOSS_FT_WORDS) return 0;
+    return timed_launch(c, s, "table_loss_ft", [&] {
+        return launch_table_loss_ft_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
+    });
+}
+
 // b2f_table_loss_grad_device / b2f_table_loss_grad_ft_device on checked options; with_pyr: build R_1 .. R_{L-1} first (false:
-// launch_table_loss has)
+// table_loss_run has)
 int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
                              const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, bool with_pyr)
 {
@@ -384,14 +386,11 @@ int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_
     }
     CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
     if (with_pyr) HIPCHK(launch_table_loss_pyramid(L, n, H, W, dev_ref, ref_stride, (float *)c->loss_pyr.dev, s));
-    ProfEvent pe;
-    const bool timed = prof_open(c, s, o.ft ? "table_loss_grad_ft" : "table_loss_grad", &pe);
     const float *pyr = (const float *)c->loss_pyr.dev;
-    const hipError_t e = o.ft ? launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s)
-                              : launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, first, s);
-    if (timed) prof_close(c, s, pe);
-    HIPCHK(e);
-    return 0;
+    return timed_launch(c, s, o.ft ? "table_loss_grad_ft" : "table_loss_grad", [&] {
+        return o.ft ? launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s)
+                    : launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, first, s);
+    });
 }
 
 namespace {

@@ -16,7 +16,7 @@ namespace b2f {
 namespace {
 
 constexpr int kPx = kLossPx;  // consecutive pixels of a row per thread (b2f_tableloss_dev.h: load_px)
-constexpr int kThreads = 256;
+constexpr int kThreads = kLossThreads;
 constexpr int kWave = 64;     // gfx950
 constexpr int kWaves = kThreads / kWave;
 constexpr int kFirst = B2F_LOSS_FT_SMOOTH2_FLOW_Q30;   // the first word this kernel writes
@@ -149,35 +149,17 @@ hipError_t launch_table_loss_ft_terms(const float *const *table, int L, bool pas
                                       const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s)
 {
     constexpr int kRec = B2F_LOSS_FT_WORDS;
-    // (the checks of launch_table_loss, which ran on the same arguments before)
-    if (n <= 0 || n > 65535 || L < 1 || L > kLossMaxLevels || H <= 0 || W <= 0 || (size_t)H * W >= (size_t)kPhotoMaxPixels || H % (1 << (L - 1)) ||
-        W % (1 << (L - 1)) || !table || !ref || !loss || (L > 1 && !pyr) || ref_stride < (size_t)3 * H * W)
-        return hipErrorInvalidValue;
-    hipError_t e = hipSuccess;
-    const int per = past ? 5 : 4;
-    const float *R = ref;
-    size_t R_stride = ref_stride;
+    LossLevel lv[kLossMaxLevels];
+    if (!loss || !loss_levels(table, nullptr, L, past, n, H, W, ref, ref_stride, pyr, flow_scale, lv)) return hipErrorInvalidValue;
     for (int j = 0; j < L; ++j) {
-        const int h = H >> j, w = W >> j;
-        const size_t hw = (size_t)h * w;
-        if (j > 0) {   // where launch_table_loss laid R_j
-            R = pyr;
-            R_stride = 3 * hw;
-            pyr += ((size_t)n * 3 * hw + 3) & ~(size_t)3;
-        }
-        const float *const *t = table + (size_t)j * per;
-        const LevelPtrs lp = {t[0], past ? t[1] : nullptr, t[per - 3], t[per - 2], t[per - 1], R, R_stride};
-        const size_t groups = (((size_t)w + kPx - 1) / kPx) * (size_t)h, blocks = (groups + kThreads - 1) / kThreads;
-        // the capped grid of launch_table_loss: about eight blocks per CU over the whole call, at most 1024 per image
-        const size_t cap = std::min<size_t>(1024, std::max<size_t>(8, 2048 / (size_t)n));
-        const dim3 grid((unsigned)std::min(blocks, cap), (unsigned)n);
-        const float kd = (float)(flow_scale / (double)(1 << j));
+        const LossLevel &v = lv[j];
         unsigned long long *rec = loss + (size_t)j * kRec;
         if (past)
-            hipLaunchKernelGGL(table_loss_ft_kernel<true>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * kRec);
+            hipLaunchKernelGGL(table_loss_ft_kernel<true>, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, v.kd, rec, (size_t)L * kRec);
         else
-            hipLaunchKernelGGL(table_loss_ft_kernel<false>, grid, dim3(kThreads), 0, s, lp, h, w, kd, rec, (size_t)L * kRec);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+            hipLaunchKernelGGL(table_loss_ft_kernel<false>, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, v.kd, rec, (size_t)L * kRec);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }

@@ -22,18 +22,7 @@ namespace b2f {
 namespace {
 
 constexpr int kPx = kLossPx;  // consecutive pixels of a row per thread (b2f_tableloss_dev.h: load_px, store_px)
-constexpr int kThreads = 256;
-
-struct GradPtrs {   // the gradient planes of one level: image 0; image b lies as far on as in the table
-    float *f, *p, *o, *iw1, *iw3;
-};
-
-// where a group lies: its first pixel, how many of its pixels are in the row, which neighbours exist
-struct Group {
-    size_t i0;
-    int x0, n, w;
-    bool u1, u2, d1, d2;   // the rows y - 1, y - 2, y + 1, y + 2 exist
-};
+constexpr int kThreads = kLossThreads;
 
 // the radius-2 cross of a group in one plane: cur[2..5] the group, cur[0..1] / cur[6..7] the two pixels left / right of it, up2, up1,
 // low1, low2 the rows y - 2 .. y + 2 over the group's columns; what does not exist is 0 and is not read
@@ -56,37 +45,12 @@ __device__ __forceinline__ void load_cross2(const float *pl, const Group &g, flo
     if (g.d2) load_px(pl + g.i0 + 2 * (size_t)g.w, g.n, low2);
 }
 
-// the five-point cross: cur[1..4] the group, cur[0] / cur[5] the pixel left / right of it, up / low the rows above / below
-__device__ __forceinline__ void load_cross1(const float *pl, const Group &g, float *cur, float *up, float *low)
-{
-#pragma unroll
-    for (int k = 0; k < kPx; ++k) up[k] = low[k] = cur[k + 1] = 0.0f;
-    cur[0] = cur[kPx + 1] = 0.0f;
-    load_px(pl + g.i0, g.n, cur + 1);
-    if (g.x0 > 0) cur[0] = pl[g.i0 - 1];
-    if (g.x0 + kPx < g.w) cur[kPx + 1] = pl[g.i0 + kPx];
-    if (g.u1) load_px(pl + g.i0 - g.w, g.n, up);
-    if (g.d1) load_px(pl + g.i0 + g.w, g.n, low);
-}
-
 // the contrast weights of a group: first-order wx[i] of the pair of columns x0 - 1 + i and x0 + i, wyc / wyu of the pairs with the row
 // below / above; second-order w2x[i] of column x0 - 1 + i, w2y[r] of row y - 1 + r.  A weight whose pixels do not all exist is not used.
 struct Weights {
     double wx[kPx + 1], wyc[kPx], wyu[kPx];
     double w2x[kPx + 2], w2y[3][kPx];
 };
-
-// S of the group's four pixels in one plane from its five-point cross (b2f_tableloss_grad.hip: smooth4)
-template <bool Quad>
-__device__ __forceinline__ void smooth4(const float *cur, const float *up, const float *low, const Group &g, const Weights &wt, double *S)
-{
-    double a[kPx + 1];
-#pragma unroll
-    for (int i = 0; i <= kPx; ++i) a[i] = grad_edge<Quad>(g.x0 - 1 + i >= 0 && g.x0 + i < g.w, cur[i], cur[i + 1], wt.wx[i]);
-#pragma unroll
-    for (int k = 0; k < kPx; ++k)
-        S[k] = grad_s(a[k + 1], a[k], grad_edge<Quad>(g.d1, cur[k + 1], low[k], wt.wyc[k]), grad_edge<Quad>(g.u1, up[k], cur[k + 1], wt.wyu[k]));
-}
 
 // S or S2 of the group's four pixels in one plane of a flow
 template <bool Second>
@@ -106,8 +70,8 @@ __device__ __forceinline__ void smooth_flow4(const float *pl, const Group &g, co
             S[k] = grad2_s(qc, qx[k + 1], qd, qx[k + 2], qu, qx[k]);
         }
     } else {
-        load_cross1(pl, g, cur, up1, low1);
-        smooth4<false>(cur, up1, low1, g, wt, S);
+        load_cross<true>(pl, g, cur, up1, low1);
+        smooth4<false>(cur, up1, low1, g, wt.wx, wt.wyc, wt.wyu, S);
     }
 }
 
@@ -128,11 +92,7 @@ __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs 
     const size_t gpr = ((size_t)w + kPx - 1) / kPx, groups = gpr * (size_t)h;   // groups per row, per image
     for (size_t gi = (size_t)blockIdx.x * kThreads + threadIdx.x; gi < groups; gi += (size_t)gridDim.x * kThreads) {
         const int y = (int)(gi / gpr), x0 = (int)(gi % gpr) * kPx;
-        Group g;
-        g.x0 = x0; g.w = w;
-        g.n = w - x0 < kPx ? w - x0 : kPx;
-        g.i0 = (size_t)y * w + x0;
-        g.u1 = y > 0; g.u2 = y > 1; g.d1 = y + 1 < h; g.d2 = y + 2 < h;
+        const Group g = group_at(y, x0, h, w);
         // 1. the reference: the sums of the pairs, then the weights
         Weights wt;
         if (want_w1 || want_w2) {
@@ -144,7 +104,7 @@ __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs 
                 if (want_w2) {
                     load_cross2(R + (size_t)c * hw, g, cur, up2, up1, low1, low2);
                 } else {
-                    load_cross1(R + (size_t)c * hw, g, cur + 1, up1, low1);
+                    load_cross<true>(R + (size_t)c * hw, g, cur + 1, up1, low1);
                     cur[0] = cur[kPx + 3] = 0.0f;
 #pragma unroll
                     for (int q = 0; q < kPx; ++q) up2[q] = low2[q] = 0.0f;
@@ -229,8 +189,8 @@ __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs 
 #pragma unroll
             for (int q = 0; q < kPx; ++q) So[c][q] = 0.0;
             if (on_so) {
-                load_cross1(o + (size_t)c * hw, g, cur, up, low);
-                smooth4<true>(cur, up, low, g, wt, So[c]);
+                load_cross<true>(o + (size_t)c * hw, g, cur, up, low);
+                smooth4<true>(cur, up, low, g, wt.wx, wt.wyc, wt.wyu, So[c]);
             } else {
 #pragma unroll
                 for (int q = 0; q < kPx; ++q) cur[q + 1] = 0.0f;
@@ -255,8 +215,8 @@ __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs 
                 float out[kPx] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if (on_p && obgcc) {
                     float ic[kPx + 2], iu[kPx], il[kPx], rc[kPx + 2], ru[kPx], rl[kPx];
-                    load_cross1(iw[d] + (size_t)c * hw, g, ic, iu, il);
-                    load_cross1(R + (size_t)c * hw, g, rc, ru, rl);
+                    load_cross<true>(iw[d] + (size_t)c * hw, g, ic, iu, il);
+                    load_cross<true>(R + (size_t)c * hw, g, rc, ru, rl);
 #pragma unroll
                     for (int q = 0; q < kPx; ++q) {
                         const bool has_l = x0 + q > 0, has_r = x0 + q + 1 < w;
@@ -305,42 +265,21 @@ __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs 
 hipError_t launch_table_loss_grad_ft(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref,
                                      size_t ref_stride, const float *pyr, double flow_scale, const GradFtCoef *coef, hipStream_t s)
 {
-    if (n <= 0 || n > 65535 || L < 1 || L > kLossMaxLevels || H <= 0 || W <= 0 || (size_t)H * W >= (size_t)kPhotoMaxPixels || H % (1 << (L - 1)) ||
-        W % (1 << (L - 1)) || !table || !grad || !ref || !coef || (L > 1 && !pyr) || ref_stride < (size_t)3 * H * W)
-        return hipErrorInvalidValue;
-    const int per = past ? 5 : 4;
-    for (int i = 0; i < L * per; ++i)
-        if (!table[i] || !grad[i]) return hipErrorInvalidValue;
-    hipError_t e = hipSuccess;
-    const float *R = ref;
-    size_t R_stride = ref_stride;
+    LossLevel lv[kLossMaxLevels];
+    if (!grad || !coef || !loss_levels(table, grad, L, past, n, H, W, ref, ref_stride, pyr, flow_scale, lv)) return hipErrorInvalidValue;
     for (int j = 0; j < L; ++j) {
-        const int h = H >> j, w = W >> j;
-        const size_t hw = (size_t)h * w;
-        if (j > 0) {   // where launch_table_loss / launch_table_loss_pyramid laid R_j
-            R = pyr;
-            R_stride = 3 * hw;
-            pyr += ((size_t)n * 3 * hw + 3) & ~(size_t)3;
-        }
-        const float *const *t = table + (size_t)j * per;
-        float *const *g = grad + (size_t)j * per;
-        const LevelPtrs lp = {t[0], past ? t[1] : nullptr, t[per - 3], t[per - 2], t[per - 1], R, R_stride};
-        const GradPtrs gp = {g[0], past ? g[1] : nullptr, g[per - 3], g[per - 2], g[per - 1]};
-        const size_t groups = (((size_t)w + kPx - 1) / kPx) * (size_t)h, blocks = (groups + kThreads - 1) / kThreads;
-        // the capped grid of launch_table_loss: about eight blocks per CU over the whole call, at most 1024 per image
-        const size_t cap = std::min<size_t>(1024, std::max<size_t>(8, 2048 / (size_t)n));
-        const dim3 grid((unsigned)std::min(blocks, cap), (unsigned)n);
-        const float kd = (float)(flow_scale / (double)(1 << j));
+        const LossLevel &v = lv[j];
         const bool second = (coef[j].ft & kGradFtSecond) != 0;
         if (past && second)
-            hipLaunchKernelGGL((table_loss_grad_ft_kernel<true, true>), grid, dim3(kThreads), 0, s, lp, gp, h, w, kd, coef[j]);
+            hipLaunchKernelGGL((table_loss_grad_ft_kernel<true, true>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, coef[j]);
         else if (past)
-            hipLaunchKernelGGL((table_loss_grad_ft_kernel<true, false>), grid, dim3(kThreads), 0, s, lp, gp, h, w, kd, coef[j]);
+            hipLaunchKernelGGL((table_loss_grad_ft_kernel<true, false>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, coef[j]);
         else if (second)
-            hipLaunchKernelGGL((table_loss_grad_ft_kernel<false, true>), grid, dim3(kThreads), 0, s, lp, gp, h, w, kd, coef[j]);
+            hipLaunchKernelGGL((table_loss_grad_ft_kernel<false, true>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, coef[j]);
         else
-            hipLaunchKernelGGL((table_loss_grad_ft_kernel<false, false>), grid, dim3(kThreads), 0, s, lp, gp, h, w, kd, coef[j]);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+            hipLaunchKernelGGL((table_loss_grad_ft_kernel<false, false>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, coef[j]);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
