@@ -262,6 +262,9 @@ SIGNATURES = {
     "b2f_op_conv_head16": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]),
     "b2f_op_upsample_flow2x": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, c_float_p]),
     "b2f_op_image_scale": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int]),
+    "b2f_arena_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "b2f_guard_selftest": (C.c_int, [C.c_void_p, C.c_int]),
+    "b2f_arena_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_longlong)]),
 }
 
 

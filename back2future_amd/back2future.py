@@ -906,6 +906,21 @@ class Model(object):
     def synchronize(self):
         _lib.check(_lib.lib().b2f_synchronize(self._h))
 
+    def arena_check(self, detail=False):
+        """b2f_arena_check (tests; options arena_guard / arena_fill): the number of guard words of the workspace that a kernel has
+        overwritten since the workspace was filled.  detail: (count, buffer index, offset, message) with the first such word."""
+        i, off = C.c_int(), C.c_longlong()
+        n = _lib.lib().b2f_arena_check(self._h, C.byref(i), C.byref(off))
+        if n < 0:
+            _lib.check(1)
+        if not detail:
+            return n
+        return n, i.value, off.value, (_lib.lib().b2f_last_error().decode("utf-8", "replace") if n else "")
+
+    def guard_selftest(self, which):
+        """b2f_guard_selftest: overwrite one guard word from the host (0 / 1: the workspace's, 2 / 3: a guarded op-level buffer's)."""
+        _lib.check(_lib.lib().b2f_guard_selftest(self._h, int(which)))
+
     def profile_reset(self):
         _lib.check(_lib.lib().b2f_profile_reset(self._h))
 
@@ -1332,6 +1347,21 @@ class MultiModel(object):
         fn = lambda h, xp, n, H, W, fsc, op, lp, gp, ng, outs: entry(h, xp, n, H, W, fsc, op, lp, gp, ng)
         grad, loss, _ = _forward_loss_grad(fn, self._h, x, flow_scale, options, shapes, no.value // (5 if pf.value else 4), want_loss, False)
         return (grad, loss) if want_loss else grad
+
+
+ARENA_BUFFERS = (["img", "tmp"] + ["cs[%d]" % l for l in range(2, 8)] + ["U[%d]" % l for l in range(3, 7)] + ["UB[%d]" % l for l in range(3, 7)]
+                 + ["cv"] + ["d[%d]" % i for i in range(1, 6)] + ["fs", "bfs", "logits", "u2", "flow_planar"] + ["ds[%d]" % k for k in range(2, 6)])
+
+
+def arena_plan(B, H, W, full=False, past_flow=False, seq=False, stream=False, want_past=False, arena_guard=0):
+    """b2f_arena_plan (host only): ({buffer name: float offset}, total floats) of the workspace of such a pass."""
+    off, total = (C.c_longlong * 40)(), C.c_longlong()
+    flags = (1 if full else 0) | (2 if past_flow else 0) | (4 if seq else 0) | (8 if stream else 0) | (16 if want_past else 0)
+    n = _lib.lib().b2f_arena_plan(int(arena_guard), int(B), int(H), int(W), flags, off, 40, C.byref(total))
+    if n < 0:
+        _lib.check(1)
+    assert n == len(ARENA_BUFFERS)
+    return dict(zip(ARENA_BUFFERS, list(off)[:n])), total.value
 
 
 def shard_range(n, rank, world):

@@ -30,6 +30,43 @@ ConvSeg cp8_seg(const float *ptr, int C, size_t hw)
     sgm.nchunks = 0;
     return sgm;
 }
+
+int DevBuf::alloc(size_t count, const char *what)
+{
+    n = std::max<size_t>(count, 1);
+    name = what;
+    const size_t all = n + 2 * kGuardFloats;
+    HIPCHK(hipMalloc(&raw, all * sizeof(float)));
+    p = raw + kGuardFloats;   // hipMalloc aligns to 256 bytes and the guard is a multiple of that
+    HIPCHK(hipMemsetD32((hipDeviceptr_t)raw, (int)kGuardWord, all));
+    HIPCHK(hipStreamSynchronize(nullptr));   // the fill is asynchronous on the null stream
+    return 0;
+}
+
+int DevBuf::check() const
+{
+    if (!raw) return 0;
+    std::vector<uint32_t> g(2 * kGuardFloats);
+    HIPCHK(hipMemcpy(g.data(), raw, kGuardFloats * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(g.data() + kGuardFloats, p + n, kGuardFloats * sizeof(float), hipMemcpyDeviceToHost));
+    long long first = 0, bad = 0;
+    bool before = false;
+    for (size_t i = 0; i < g.size(); ++i) {
+        if (g[i] == kGuardWord) continue;
+        if (!bad++) { before = i < kGuardFloats; first = before ? (long long)i - (long long)kGuardFloats : (long long)(i - kGuardFloats); }
+    }
+    if (!bad) return 0;
+    char msg[256];
+    snprintf(msg, sizeof msg, "guard of device buffer '%s' (%zu floats) overwritten: %lld words, the first one %s the buffer at offset %+lld from its %s",
+             name, n, bad, before ? "before" : "after", first, before ? "start" : "end");
+    return api_fail(msg);
+}
+
+int check_guards(std::initializer_list<const DevBuf *> bufs)
+{
+    for (const DevBuf *b : bufs) CHK(b->check());
+    return 0;
+}
 }  // namespace b2f
 static int fail(const std::string &m) { return api_fail(m); }
 
@@ -313,11 +350,25 @@ struct Plan {
     int rec;            // cost-volume record size in floats
     int h[8], w[8];
     size_t img, tmp, cs[8], U[8], UB[8], cv, d[6], fs, bfs, logits, u2, flow_planar, ds[6], total;
+    // option arena_guard (tests): the buffers make_plan took, in order: where each one ends (its own slack included), where the next
+    // one may start at the earliest (end rounded to 64 floats + the guard), and its name.  nbuf = 0 without the option.
+    enum { kMaxBuf = 40 };
+    struct Buf { size_t end, next; const char *name; };
+    int nbuf = 0;
+    size_t guard = 0;
+    Buf buf[kMaxBuf];
 };
 
-Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false, bool stream = false, bool want_past = false)
+// guard: option arena_guard.  0 lays the arena out as ever: every buffer rounded up to 64 floats, one behind the other.  Otherwise that many
+// floats lie in front of the first buffer and behind every buffer (behind the slack a buffer owns: the record's + 64 is the record's).
+Plan make_plan(size_t guard, int B, int H, int W, bool full, bool past_flow, bool seq = false, bool stream = false, bool want_past = false)
 {
+    static const char *const kCs[8] = {"", "", "cs[2]", "cs[3]", "cs[4]", "cs[5]", "cs[6]", "cs[7]"};
+    static const char *const kU[8] = {"", "", "", "U[3]", "U[4]", "U[5]", "U[6]", ""}, *const kUB[8] = {"", "", "", "UB[3]", "UB[4]", "UB[5]", "UB[6]", ""};
+    static const char *const kD[6] = {"", "d[1]", "d[2]", "d[3]", "d[4]", "d[5]"}, *const kDs[6] = {"", "", "ds[2]", "ds[3]", "ds[4]", "ds[5]"};
     Plan p;
+    p.nbuf = 0;
+    p.guard = guard;
     p.B = B; p.H = H; p.W = W;
     p.full = full;
     p.seq = seq;
@@ -327,23 +378,31 @@ Plan make_plan(int B, int H, int W, bool full, bool past_flow, bool seq = false,
     p.fo = seq ? 1 : B;
     p.rec = kCvRec;
     for (int l = 1; l <= 7; ++l) { p.h[l] = H >> (l - 1); p.w[l] = W >> (l - 1); }
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
-    p.img = full ? take((size_t)3 * B * H * W * kImgC) : 0;   // packed frames: only the full table needs them
-    p.tmp = take((size_t)p.nimg * p.h[2] * p.w[2] * kFeat[2]);
-    for (int l = 2; l <= 7; ++l) p.cs[l] = take((stream && l >= 3) ? 0 : (size_t)p.nimg * p.h[l] * p.w[l] * kFeat[l]);
-    for (int l = 3; l <= 6; ++l) p.U[l] = take((size_t)B * p.h[l] * p.w[l] * 2);
-    for (int l = 3; l <= 6; ++l) p.UB[l] = p.past ? take((size_t)B * p.h[l] * p.w[l] * 2) : 0;
-    p.cv = take((size_t)B * p.h[3] * p.w[3] * p.rec + 64);
+    size_t off = guard;
+    auto take = [&](size_t n, const char *name) {
+        size_t o = off;
+        off += (n + 63) & ~(size_t)63;
+        if (guard) {
+            off += guard;
+            p.buf[p.nbuf++] = {o + n, off, name};
+        }
+        return o;
+    };
+    p.img = full ? take((size_t)3 * B * H * W * kImgC, "img") : 0;   // packed frames: only the full table needs them
+    p.tmp = take((size_t)p.nimg * p.h[2] * p.w[2] * kFeat[2], "tmp");
+    for (int l = 2; l <= 7; ++l) p.cs[l] = take((stream && l >= 3) ? 0 : (size_t)p.nimg * p.h[l] * p.w[l] * kFeat[l], kCs[l]);
+    for (int l = 3; l <= 6; ++l) p.U[l] = take((size_t)B * p.h[l] * p.w[l] * 2, kU[l]);
+    for (int l = 3; l <= 6; ++l) p.UB[l] = p.past ? take((size_t)B * p.h[l] * p.w[l] * 2, kUB[l]) : 0;
+    p.cv = take((size_t)B * p.h[3] * p.w[3] * p.rec + 64, "cv");
     const size_t px3 = (size_t)B * p.h[3] * p.w[3];
-    for (int i = 1; i <= 5; ++i) p.d[i] = take(px3 * kDec[i]);
-    p.fs = take(px3 * 8);       // conv outputs are chunk-planar: 2 channels live in one 8-float chunk
-    p.bfs = take(px3 * 8);
-    p.logits = take(px3 * 8);
-    p.u2 = take(px3 * 4 * 2);
-    p.flow_planar = take((size_t)B * 2 * H * W);
+    for (int i = 1; i <= 5; ++i) p.d[i] = take(px3 * kDec[i], kD[i]);
+    p.fs = take(px3 * 8, "fs");       // conv outputs are chunk-planar: 2 channels live in one 8-float chunk
+    p.bfs = take(px3 * 8, "bfs");
+    p.logits = take(px3 * 8, "logits");
+    p.u2 = take(px3 * 4 * 2, "u2");
+    p.flow_planar = take((size_t)B * 2 * H * W, "flow_planar");
     // image pyramid ds[f][k], f in {1,3}, k = 2..5 (pwc.lua:148-158): [2][B][H/2^(k-1)][W/2^(k-1)][8]
-    for (int k = 2; k <= 5; ++k) p.ds[k] = full ? take((size_t)2 * B * (H >> (k - 1)) * (W >> (k - 1)) * kImgC) : 0;
+    for (int k = 2; k <= 5; ++k) p.ds[k] = full ? take((size_t)2 * B * (H >> (k - 1)) * (W >> (k - 1)) * kImgC, kDs[k]) : 0;
     p.total = off;
     return p;
 }
@@ -379,13 +438,41 @@ int ensure_workspace_floats(b2f_ctx *c, size_t total)
             drop_graphs(c);
         }
         HIPCHK(hipMalloc(&c->arena, total * sizeof(float)));
-        HIPCHK(hipMemset(c->arena, 0, total * sizeof(float)));
+        HIPCHK(c->arena_fill ? hipMemsetD32((hipDeviceptr_t)c->arena, (int)kGuardWord, total) : hipMemset(c->arena, 0, total * sizeof(float)));
         HIPCHK(hipDeviceSynchronize());
         c->arena_floats = total;
+        c->guards.clear();
+        c->arena_layout[0] = 0;
     }
     return 0;
 }
-int ensure_workspace(b2f_ctx *c, const Plan &p) { return ensure_workspace_floats(c, p.total); }
+
+// Options arena_guard / arena_fill (tests): the arena is in the state of a fresh allocation whenever a pass lays it out differently from the
+// pass before -- an arena that has grown once serves smaller shapes and other plans, whose guards would otherwise lie where an earlier
+// plan's buffers were -- and the context remembers the plan's guards for b2f_arena_check.  The refill also wipes what the pass before
+// left outside the new plan's guards: a stray write is seen only by a b2f_arena_check made after the pass that did it and before the
+// next pass with another layout, which is why the tests check after every call.
+int prepare_test_arena(b2f_ctx *c, const Plan &p)
+{
+    const long long key[9] = {1, p.B, p.H, p.W, (p.full ? 1 : 0) | (p.seq ? 2 : 0) | (p.stream ? 4 : 0) | (p.past ? 8 : 0), (long long)p.total, (long long)p.guard,
+                              c->arena_fill, (long long)(uintptr_t)c->arena};
+    if (!memcmp(key, c->arena_layout, sizeof key)) return 0;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(c->arena_fill ? hipMemsetD32((hipDeviceptr_t)c->arena, (int)kGuardWord, c->arena_floats) : hipMemset(c->arena, 0, c->arena_floats * sizeof(float)));
+    HIPCHK(hipDeviceSynchronize());
+    memcpy(c->arena_layout, key, sizeof key);
+    c->guards.clear();
+    if (p.nbuf) c->guards.push_back({0, p.guard, 0, true, p.buf[0].name});
+    for (int i = 0; i < p.nbuf; ++i) c->guards.push_back({p.buf[i].end, p.buf[i].next - p.buf[i].end, i, false, p.buf[i].name});
+    return 0;
+}
+
+int ensure_workspace(b2f_ctx *c, const Plan &p)
+{
+    CHK(ensure_workspace_floats(c, p.total));
+    if (c->arena_guard | c->arena_fill) CHK(prepare_test_arena(c, p));
+    return 0;
+}
 
 // ---- one conv launch from the packed table -----------------------------------------------
 struct KernelChoice {
@@ -743,7 +830,13 @@ int b2f::run_conv_layer(b2f_ctx *c, hipStream_t s, bool cap, int conv_id, const 
     if (conv_id < 0) return fail("b2f: layer not present in this model");
     return run_conv(c, s, cap, conv_id, segs, nimg, H, W, stride, leaky, out);
 }
-int b2f::ensure_arena(b2f_ctx *c, size_t floats) { return ensure_workspace_floats(c, floats); }
+int b2f::ensure_arena(b2f_ctx *c, size_t floats)
+{
+    CHK(ensure_workspace_floats(c, floats));
+    c->guards.clear();          // the generic executor lays the arena out itself: no plan's guards, and the next plan refills
+    c->arena_layout[0] = 0;
+    return 0;
+}
 int b2f::check_shape(int B, int H, int W)
 {
     if (B <= 0 || H <= 0 || W <= 0) return fail("b2f: non-positive shape");
@@ -806,6 +899,7 @@ enum {
     OPT_ENV = 1,        // seeded from the environment at b2f_init
     OPT_SYNC = 2,       // a different kernel mix: setting it synchronises the device and drops the captured graphs, which hold the old one
     OPT_EXP_ONLY = 4,   // selects a kernel of tools/experiments/csrc: the product build has no such option (not seeded, only 0 accepted)
+    OPT_ARENA = 8,      // lays out or fills the arena differently: setting it synchronises the device, frees the arena and drops the captured graphs
 };
 struct OptRow {
     const char *name;
@@ -844,6 +938,8 @@ const OptRow kOptions[] = {
     {"host_u8", &b2f_ctx::host_u8, OPT_ENV, 0},
     {"host_ramp", &b2f_ctx::host_ramp, OPT_ENV, 0},
     {"debug_fail_next", &b2f_ctx::debug_fail_next, 0, 0},
+    {"arena_guard", &b2f_ctx::arena_guard, OPT_ARENA, 0},
+    {"arena_fill", &b2f_ctx::arena_fill, OPT_ARENA, 0},
 };
 
 const OptRow *find_option(const char *key)
@@ -1137,6 +1233,18 @@ int b2f_set_option(b2f_ctx *c, const char *key, int value) try
         drop_graphs(c);
     }
     if (const char *refusal = experiment_value(*r, value)) return fail(refusal);
+    if (r->flags & OPT_ARENA) {
+        if (r->member == &b2f_ctx::arena_guard && (value < 0 || value % 64)) return fail("b2f_set_option: arena_guard is a count of floats, a multiple of 64");
+        if (r->member == &b2f_ctx::arena_fill && value != 0 && value != 1) return fail("b2f_set_option: arena_fill is 0 or 1");
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipDeviceSynchronize());
+        drop_graphs(c);   // the next pass allocates and fills afresh, as after a growth of the arena
+        if (c->arena) HIPCHK(hipFree(c->arena));
+        c->arena = nullptr;
+        c->arena_floats = 0;
+        c->guards.clear();
+        c->arena_layout[0] = 0;
+    }
     const bool had = r->repack && reads_packing(c, r->repack);
     c->*r->member = value;
     if (r->repack && had != reads_packing(c, r->repack)) CHK(b2f_commit_weights(c));
@@ -1235,7 +1343,7 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
         if (dev_past) HIPCHK(hipMemcpyAsync(dev_past, dev[1], n2, hipMemcpyDeviceToDevice, s));
         return 0;
     }
-    const Plan P = make_plan(B, H, W, false, c->past_flow, seq, sp != nullptr, dev_past != nullptr);
+    const Plan P = make_plan((size_t)c->arena_guard, B, H, W, false, c->past_flow, seq, sp != nullptr, dev_past != nullptr);
     CHK(ensure_workspace(c, P));
     Outs O;
     O.flow = dev_flow; O.occ = dev_occ; O.est3 = dev_est3; O.past = dev_past;
@@ -1359,7 +1467,7 @@ int b2f_forward(b2f_ctx *c, const float *x, int B, int H, int W, float **outs, i
     // arena first (it may be re-allocated), then the per-output device buffers
     Plan P;
     if (shipped) {
-        P = make_plan(B, H, W, true, c->past_flow);
+        P = make_plan((size_t)c->arena_guard, B, H, W, true, c->past_flow);
         CHK(ensure_workspace(c, P));
     }
     std::vector<float *> dev(n_outs, nullptr);
@@ -1453,7 +1561,7 @@ LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input,
 int forward_table_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, const LossPlan &lp, float *const *tab)
 {
     if (c->g.shipped()) {
-        const Plan P = make_plan(nb, H, W, true, c->past_flow);
+        const Plan P = make_plan((size_t)c->arena_guard, nb, H, W, true, c->past_flow);
         CHK(ensure_workspace(c, P));
         Outs O;
         for (int j = 0; j < lp.L; ++j) {
@@ -1689,14 +1797,98 @@ B2F_CATCH("b2f_forward_loss_ft_device")
 
 extern "C" {
 
+// ---- guards (tests) -------------------------------------------------------------
+
+// The guards of the plan the arena was last filled for: how many of their words no longer hold what the arena was filled with (kGuardWord
+// with arena_fill = 1, else 0), compared on bits.  *buffer_index / *offset: the first such word -- the plan's buffer it belongs to and its
+// offset from that buffer's end (>= 0: behind the buffer) or from its start (< 0: the guard in front of buffer 0).  b2f_last_error names
+// the buffer.  0 without arena_guard; -1 on an error.
+int b2f_arena_check(b2f_ctx *c, int *buffer_index, long long *offset) try
+{
+    if (buffer_index) *buffer_index = -1;
+    if (offset) *offset = 0;
+    if (!c) { fail("b2f_arena_check: null context"); return -1; }
+    if (!c->arena_guard || !c->arena || c->guards.empty()) return 0;
+    if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { fail(std::string("b2f_arena_check: ") + hipGetErrorString(hipGetLastError())); return -1; }
+    const uint32_t want = c->arena_fill ? kGuardWord : 0u;
+    long long bad = 0;
+    std::vector<uint32_t> host;
+    for (const ArenaGuard &g : c->guards) {
+        host.resize(g.len);
+        if (g.off + g.len > c->arena_floats) { fail("b2f_arena_check: a guard lies outside the arena"); return -1; }
+        if (hipMemcpy(host.data(), c->arena + g.off, g.len * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fail("b2f_arena_check: hipMemcpy failed"); return -1; }
+        for (size_t i = 0; i < g.len; ++i) {
+            if (host[i] == want) continue;
+            if (!bad++) {
+                const long long o = g.before ? (long long)i - (long long)g.len : (long long)i;
+                if (buffer_index) *buffer_index = g.buffer;
+                if (offset) *offset = o;
+                char msg[200];
+                snprintf(msg, sizeof msg, "arena guard overwritten: the first word %s buffer '%s' (buffer %d of the plan) at offset %+lld from its %s holds 0x%08x",
+                         g.before ? "before" : "after", g.name, g.buffer, o, g.before ? "start" : "end", host[i]);
+                fail(msg);
+            }
+        }
+    }
+    return (int)std::min<long long>(bad, 0x7fffffff);
+}
+catch (const std::exception &e) { fail(std::string("b2f_arena_check: ") + e.what()); return -1; }
+catch (...) { fail("b2f_arena_check: unknown exception"); return -1; }
+
+// Proof that the two detectors detect.  One guard word is overwritten by a hipMemcpy from the host (no kernel stores out of range):
+// which = 0: offset +3 behind buffer 1 of the arena's current plan; 1: offset -2 in front of its buffer 0 (b2f_arena_check then reports
+// exactly that; needs arena_guard and a pass that has laid the arena out); 2 / 3: offset +2 behind / -1 in front of a guarded device
+// buffer 'selftest' of the op-level entries, whose check then fails this call with the buffer's name.
+int b2f_guard_selftest(b2f_ctx *c, int which) try
+{
+    if (!c) return fail("b2f_guard_selftest: null context");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    const uint32_t word = 0x3f800000u;
+    if (which == 0 || which == 1) {
+        if (!c->arena_guard || !c->arena || c->guards.size() < 3) return fail("b2f_guard_selftest: no guarded plan (set arena_guard and run a pass first)");
+        const ArenaGuard &g = c->guards[which == 0 ? 2 : 0];   // guards[0]: before buffer 0; guards[1 + i]: after buffer i
+        const size_t at = which == 0 ? g.off + 3 : g.off + g.len - 2;
+        HIPCHK(hipMemcpy(c->arena + at, &word, sizeof word, hipMemcpyHostToDevice));
+        return 0;
+    }
+    if (which == 2 || which == 3) {
+        DevBuf b;
+        CHK(b.alloc(1000, "selftest"));
+        HIPCHK(hipMemcpy(which == 2 ? b.p + b.n + 2 : b.p - 1, &word, sizeof word, hipMemcpyHostToDevice));
+        return b.check();
+    }
+    return fail("b2f_guard_selftest: which must be 0 .. 3");
+}
+B2F_CATCH("b2f_guard_selftest")
+
+// make_plan without a context or a device: the float offset of every buffer of the arena, in the order img, tmp, cs[2..7], U[3..6],
+// UB[3..6], cv, d[1..5], fs, bfs, logits, u2, flow_planar, ds[2..5] (33 values; 0 for a buffer the plan does not hold), and the total.
+// flags: 1 full table, 2 Soft model, 4 sequence, 8 stream push, 16 past-flow output.  Returns 33, or -1.
+int b2f_arena_plan(int arena_guard, int B, int H, int W, int flags, long long *offsets, int cap, long long *total) try
+{
+    if (!offsets || cap < 33 || arena_guard < 0 || arena_guard % 64) { fail("b2f_arena_plan: bad argument"); return -1; }
+    if (check_shape(B, H, W)) return -1;
+    const Plan p = make_plan((size_t)arena_guard, B, H, W, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (flags & 8) != 0, (flags & 16) != 0);
+    int n = 0;
+    offsets[n++] = (long long)p.img;
+    offsets[n++] = (long long)p.tmp;
+    for (int l = 2; l <= 7; ++l) offsets[n++] = (long long)p.cs[l];
+    for (int l = 3; l <= 6; ++l) offsets[n++] = (long long)p.U[l];
+    for (int l = 3; l <= 6; ++l) offsets[n++] = (long long)p.UB[l];
+    offsets[n++] = (long long)p.cv;
+    for (int i = 1; i <= 5; ++i) offsets[n++] = (long long)p.d[i];
+    for (size_t o : {p.fs, p.bfs, p.logits, p.u2, p.flow_planar}) offsets[n++] = (long long)o;
+    for (int k = 2; k <= 5; ++k) offsets[n++] = (long long)p.ds[k];
+    if (total) *total = (long long)p.total;
+    return n;
+}
+catch (const std::exception &e) { fail(std::string("b2f_arena_plan: ") + e.what()); return -1; }
+catch (...) { fail("b2f_arena_plan: unknown exception"); return -1; }
+
 // ---- op-level entry points (host pointers; reference module layouts) -----------------------
-namespace {
-struct DevBuf {
-    float *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { HIPCHK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(float))); return 0; }
-};
-}  // namespace
+// Every device buffer is a DevBuf (b2f_ctx.h): guarded on both sides, kGuardWord inside until something writes it, checked once the
+// stream has been synchronised.
 
 int b2f_op_warp_bhwd(b2f_ctx *c, const float *img, const float *grid, int B, int ih, int iw, int C, int gh,
                      int gw, float *out) try
@@ -1705,11 +1897,12 @@ int b2f_op_warp_bhwd(b2f_ctx *c, const float *img, const float *grid, int B, int
     HIPCHK(hipSetDevice(c->device));
     DevBuf di, dg, dout;
     const size_t ni = (size_t)B * ih * iw * C, ng = (size_t)B * gh * gw * 2, no = (size_t)B * gh * gw * C;
-    CHK(di.alloc(ni)); CHK(dg.alloc(ng)); CHK(dout.alloc(no));
+    CHK(di.alloc(ni, "img")); CHK(dg.alloc(ng, "grid")); CHK(dout.alloc(no, "out"));
     HIPCHK(hipMemcpy(di.p, img, ni * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dg.p, grid, ng * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(launch_warp_nhwc(di.p, (long)((size_t)ih * iw * C), C, C, ih, iw, dg.p, 1.0f, B, gh, gw, dout.p, C, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&di, &dg, &dout}));
     HIPCHK(hipMemcpy(out, dout.p, no * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1722,10 +1915,11 @@ int b2f_op_image_scale(b2f_ctx *c, const float *src, int C, int Hs, int Ws, int 
     HIPCHK(hipSetDevice(c->device));
     DevBuf ds, dt, dd;
     const size_t ns = (size_t)C * Hs * Ws, nt = (size_t)C * Hs * Wd, nd = (size_t)C * Hd * Wd;
-    CHK(ds.alloc(ns)); CHK(dt.alloc(nt)); CHK(dd.alloc(nd));
+    CHK(ds.alloc(ns, "src")); CHK(dt.alloc(nt, "row pass")); CHK(dd.alloc(nd, "dst"));
     HIPCHK(hipMemcpy(ds.p, src, ns * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(launch_image_scale(ds.p, normalize, C, Hs, Ws, dt.p, dd.p, Hd, Wd, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&ds, &dt, &dd}));
     HIPCHK(hipMemcpy(dst, dd.p, nd * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1737,11 +1931,12 @@ int b2f_op_upsample_flow2x(b2f_ctx *c, const float *x, int B, int h, int w, floa
     HIPCHK(hipSetDevice(c->device));
     DevBuf dp, dn, dy;
     const size_t n = (size_t)B * 2 * h * w;
-    CHK(dp.alloc(n)); CHK(dn.alloc(n)); CHK(dy.alloc(4 * n));
+    CHK(dp.alloc(n, "x planar")); CHK(dn.alloc(n, "x")); CHK(dy.alloc(4 * n, "y"));
     HIPCHK(hipMemcpy(dp.p, x, n * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(launch_planar_to_nhwc(dp.p, 2, B, h, w, dn.p, 2, c->stream));
     HIPCHK(launch_upsample_flow2x_planar(dn.p, 2, B, h, w, dy.p, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dp, &dn, &dy}));
     HIPCHK(hipMemcpy(y, dy.p, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1777,8 +1972,8 @@ int b2f_op_warp_costvol(b2f_ctx *c, const float *ref, const float *nbr_future, c
     const int Cp = (C + 7) / 8 * 8;   // the fused kernel walks channels in chunks of 8; zero channels add 0
     const size_t hw = (size_t)h * w, nplanar = (size_t)B * C * hw, nn = (size_t)B * hw * Cp;
     DevBuf dpl, dr, df, dpa, dfl_pl, dfl, dcv;
-    CHK(dpl.alloc(nplanar)); CHK(dr.alloc(nn)); CHK(df.alloc(nn)); CHK(dpa.alloc(nn));
-    CHK(dcv.alloc((size_t)B * hw * kCvRec));
+    CHK(dpl.alloc(nplanar, "planar staging")); CHK(dr.alloc(nn, "ref")); CHK(df.alloc(nn, "nbr_future")); CHK(dpa.alloc(nn, "nbr_past"));
+    CHK(dcv.alloc((size_t)B * hw * kCvRec, "record"));
     const float *srcs[3] = {ref, nbr_future, nbr_past};
     float *dsts[3] = {dr.p, df.p, dpa.p};
     for (int i = 0; i < 3; ++i) {
@@ -1787,7 +1982,7 @@ int b2f_op_warp_costvol(b2f_ctx *c, const float *ref, const float *nbr_future, c
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     if (flow) {
-        CHK(dfl_pl.alloc((size_t)B * 2 * hw)); CHK(dfl.alloc((size_t)B * 2 * hw));
+        CHK(dfl_pl.alloc((size_t)B * 2 * hw, "flow planar")); CHK(dfl.alloc((size_t)B * 2 * hw, "flow"));
         HIPCHK(hipMemcpy(dfl_pl.p, flow, (size_t)B * 2 * hw * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(launch_planar_to_nhwc(dfl_pl.p, 2, B, h, w, dfl.p, 2, c->stream));
     }
@@ -1799,6 +1994,7 @@ int b2f_op_warp_costvol(b2f_ctx *c, const float *ref, const float *nbr_future, c
     HIPCHK(launch_warp_costvol(cl, c->stream));
     std::vector<float> rec((size_t)B * hw * kCvRec);
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dpl, &dr, &df, &dpa, &dfl_pl, &dfl, &dcv}));
     HIPCHK(hipMemcpy(rec.data(), dcv.p, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
     // record slots -> the reference's JoinTable order {fwd 81, bwd 81}; the kernel divided by Cp,
     // CostVolMulti.lua:100 divides by N = C
@@ -1832,7 +2028,7 @@ int b2f_op_costvol(b2f_ctx *c, const float *ref, const float *frm, int B, int C,
     }
     DevBuf dpl, dr, df, dcv, dout;
     const size_t nin = (size_t)B * C * hw, nout = (size_t)B * win * win * hw;
-    CHK(dpl.alloc(nin)); CHK(dr.alloc(nin)); CHK(df.alloc(nin)); CHK(dcv.alloc(nout)); CHK(dout.alloc(nout));
+    CHK(dpl.alloc(nin, "planar staging")); CHK(dr.alloc(nin, "ref")); CHK(df.alloc(nin, "frm")); CHK(dcv.alloc(nout, "cost volume")); CHK(dout.alloc(nout, "out"));
     HIPCHK(hipMemcpy(dpl.p, ref, nin * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(launch_planar_to_nhwc(dpl.p, C, B, h, w, dr.p, C, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1841,6 +2037,7 @@ int b2f_op_costvol(b2f_ctx *c, const float *ref, const float *frm, int B, int C,
     HIPCHK(launch_costvol_generic(dr.p, df.p, B, C, h, w, win, fwd, dcv.p, c->stream));
     HIPCHK(launch_nhwc_to_planar(dcv.p, win * win, win * win, B, h, w, dout.p, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dpl, &dr, &df, &dcv, &dout}));
     HIPCHK(hipMemcpy(out, dout.p, nout * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1869,7 +2066,7 @@ int b2f_op_conv3x3(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, cons
     fill_packings(p, wt, bias, Ci, nullptr, wpk.data());
     DevBuf dpl, dx, dw, dy, dyp;
     const size_t nx = (size_t)B * Ci * H * W, nxp = (size_t)B * H * W * Cp, ny = (size_t)B * Co * Ho * Wo;
-    CHK(dpl.alloc(nx)); CHK(dx.alloc(nxp)); CHK(dw.alloc(nw)); CHK(dy.alloc(ny)); CHK(dyp.alloc(ny));
+    CHK(dpl.alloc(nx, "x planar")); CHK(dx.alloc(nxp, "x")); CHK(dw.alloc(nw, "weights")); CHK(dy.alloc(ny, "y")); CHK(dyp.alloc(ny, "y planar"));
     HIPCHK(hipMemcpy(dpl.p, x, nx * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dw.p, wpk.data(), nw * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(launch_planar_to_nhwc(dpl.p, Ci, B, H, W, dx.p, Cp, c->stream));
@@ -1881,6 +2078,7 @@ int b2f_op_conv3x3(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, cons
     CHK(launch_layer(c, c->stream, false, p, dw.p, o, 0, L));
     HIPCHK(launch_nhwc_to_planar(dy.p, Co, Co, B, Ho, Wo, dyp.p, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dpl, &dx, &dw, &dy, &dyp}));
     HIPCHK(hipMemcpy(y, dyp.p, ny * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1927,22 +2125,22 @@ int b2f_op_layer(b2f_ctx *c, int kind, int level, int idx, int nimg, int H, int 
                 float *dst = host[s].data() + ((size_t)n * Cs + (size_t)(k / 8) * 8) * hw + (k & 7);
                 for (size_t i = 0; i < hw; ++i) dst[i * 8] = src ? src[i] : fill;
             }
-        CHK(dseg[s].alloc(host[s].size() + 64));   // the arena rounds every buffer up to 64 floats (make_plan)
-        HIPCHK(hipMemset(dseg[s].p + host[s].size(), 0, 64 * sizeof(float)));
+        // (the arena promises nothing about what lies behind a buffer: here it is the guard's kGuardWord)
+        CHK(dseg[s].alloc(host[s].size(), s == 0 ? "segment 0" : "segment 1"));
         HIPCHK(hipMemcpy(dseg[s].p, host[s].data(), host[s].size() * sizeof(float), hipMemcpyHostToDevice));
         segs[s] = cp8_seg(dseg[s].p, Cs, hw);
     }
     if (p.nseg == 1) segs[1] = segs[0];
     const size_t ny = (size_t)nimg * Cop * hwo;
-    CHK(dy.alloc(ny));
-    HIPCHK(hipMemset(dy.p, 0, ny * sizeof(float)));
-    HIPCHK(hipDeviceSynchronize());   // the copies and the memset ran on the null stream, the layer runs on the context's
+    CHK(dy.alloc(ny, "y"));
+    HIPCHK(hipDeviceSynchronize());   // the copies ran on the null stream, the layer runs on the context's
     const int batch_before = c->cur_batch;   // run_conv chooses the kernel for a request of cur_batch triplets: nimg for this launch only
     c->cur_batch = nimg;
     const int rc = run_conv(c, c->stream, false, id, segs, nimg, H, W, stride, leaky, dy.p);
     c->cur_batch = batch_before;
     CHK(rc);
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dseg[0], &dseg[1], &dy}));
     std::vector<float> out(ny);
     HIPCHK(hipMemcpy(out.data(), dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
     for (int n = 0; n < nimg; ++n)
@@ -1957,8 +2155,8 @@ B2F_CATCH("b2f_op_layer")
 
 // launch_warp_costvol with the strides of the forward pass: the three maps (B x C x h x w planar here, C a multiple of 8) and the record
 // chunk-planar, flow / flow_b (B x 2 x h x w planar here, or NULL) as B x h x w x 2, the context's corr_variant.  rec: the whole record,
-// B x 168 x h x w planar in slot order (b2f_internal.h: fwd 0..79 | bwd 0..79 | fwd80 bwd80 u v ub vb 0 0).  The record buffer starts out as NaN, so a
-// slot the kernel does not write shows.
+// B x 168 x h x w planar in slot order (b2f_internal.h: fwd 0..79 | bwd 0..79 | fwd80 bwd80 u v ub vb 0 0).  The record buffer starts out as NaN
+// (kGuardWord, like every DevBuf), so a slot the kernel does not write shows.
 int b2f_op_cv_record(b2f_ctx *c, const float *ref, const float *nbr_future, const float *nbr_past, const float *flow, const float *flow_b,
                      float k, int B, int C, int h, int w, float *rec) try
 {
@@ -1976,7 +2174,7 @@ int b2f_op_cv_record(b2f_ctx *c, const float *ref, const float *nbr_future, cons
                 float *dst = host.data() + ((size_t)b * C + (size_t)(ch / 8) * 8) * hw + (ch & 7);
                 for (size_t j = 0; j < hw; ++j) dst[j * 8] = src[j];
             }
-        CHK(dmap[i].alloc(nmap));
+        CHK(dmap[i].alloc(nmap, i == 0 ? "ref" : i == 1 ? "nbr_future" : "nbr_past"));
         HIPCHK(hipMemcpy(dmap[i].p, host.data(), nmap * sizeof(float), hipMemcpyHostToDevice));
     }
     for (int i = 0; i < 2; ++i) {
@@ -1984,11 +2182,10 @@ int b2f_op_cv_record(b2f_ctx *c, const float *ref, const float *nbr_future, cons
         for (int b = 0; b < B; ++b)
             for (int ch = 0; ch < 2; ++ch)
                 for (size_t j = 0; j < hw; ++j) host[((size_t)b * hw + j) * 2 + ch] = flows[i][((size_t)b * 2 + ch) * hw + j];
-        CHK(dfl[i].alloc(nfl));
+        CHK(dfl[i].alloc(nfl, i == 0 ? "flow" : "flow_b"));
         HIPCHK(hipMemcpy(dfl[i].p, host.data(), nfl * sizeof(float), hipMemcpyHostToDevice));
     }
-    CHK(drec.alloc(nrec + 64));   // the slack the arena gives the record (make_plan)
-    HIPCHK(hipMemset(drec.p, 0xff, (nrec + 64) * sizeof(float)));
+    CHK(drec.alloc(nrec + 64, "record"));   // the slack the arena gives the record (make_plan); the guard lies behind it, as in the arena
     HIPCHK(hipDeviceSynchronize());
     CorrLaunch cl = op_corr_launch(c, 1, B, C, h, w);
     cl.ref = dmap[0].p; cl.nbr_fut = dmap[1].p; cl.nbr_past = dmap[2].p;
@@ -1996,6 +2193,7 @@ int b2f_op_cv_record(b2f_ctx *c, const float *ref, const float *nbr_future, cons
     cl.k = k; cl.out = drec.p;
     HIPCHK(launch_warp_costvol(cl, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dmap[0], &dmap[1], &dmap[2], &dfl[0], &dfl[1], &drec}));
     HIPCHK(hipMemcpy(host.data(), drec.p, nrec * sizeof(float), hipMemcpyDeviceToHost));
     for (int b = 0; b < B; ++b)
         for (int slot = 0; slot < kCvRec; ++slot) {
@@ -2033,8 +2231,8 @@ int b2f_op_conv_head16(b2f_ctx *c, const float *x, int B, int H, int W, const fl
     c16s2_pack_weights(w2, b2, 16, nullptr, p2.data(), pb2.data());
     DevBuf dpl, dx, dw1, db1, dw2, db2, dy, dyp;
     const size_t nx = (size_t)B * 16 * H * W, ny = (size_t)B * 32 * Ho * Wo;
-    CHK(dpl.alloc(nx)); CHK(dx.alloc(nx)); CHK(dw1.alloc(p1.size())); CHK(db1.alloc(32)); CHK(dw2.alloc(p2.size())); CHK(db2.alloc(32));
-    CHK(dy.alloc(ny)); CHK(dyp.alloc(ny));
+    CHK(dpl.alloc(nx, "x planar")); CHK(dx.alloc(nx, "x")); CHK(dw1.alloc(p1.size(), "w1")); CHK(db1.alloc(32, "b1")); CHK(dw2.alloc(p2.size(), "w2")); CHK(db2.alloc(32, "b2"));
+    CHK(dy.alloc(ny, "y")); CHK(dyp.alloc(ny, "y planar"));
     HIPCHK(hipMemcpy(dpl.p, x, nx * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dw1.p, p1.data(), p1.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(db1.p, pb1.data(), 32 * sizeof(float), hipMemcpyHostToDevice));
@@ -2051,6 +2249,7 @@ int b2f_op_conv_head16(b2f_ctx *c, const float *x, int B, int H, int W, const fl
     HIPCHK(launch_conv_head16(hl, c->stream));
     HIPCHK(launch_nhwc_to_planar(dy.p, 32, 32, B, Ho, Wo, dyp.p, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dpl, &dx, &dw1, &db1, &dw2, &db2, &dy, &dyp}));
     HIPCHK(hipMemcpy(y, dyp.p, ny * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }

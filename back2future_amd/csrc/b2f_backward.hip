@@ -90,12 +90,6 @@ __global__ void costvol_backward_kernel(const float *ref, const float *frm, cons
     gfrm[i] = af / div;
 }
 
-struct DevB {
-    float *p = nullptr;
-    ~DevB() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { HIPCHK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(float))); return 0; }
-};
-
 }  // namespace
 }  // namespace b2f
 
@@ -109,15 +103,15 @@ int b2f_op_warp_bhwd_backward(b2f_ctx *c, const float *img, const float *grid, c
     if (!c || !img || !grid || !grad_out || !grad_grid) return api_fail("b2f_op_warp_bhwd_backward: null argument");
     if (B <= 0 || ih <= 0 || iw <= 0 || C <= 0 || gh <= 0 || gw <= 0) return api_fail("b2f_op_warp_bhwd_backward: bad shape");
     HIPCHK(hipSetDevice(c->device));
-    DevB di, dg, dgo, dgi, dgg;
+    DevBuf di, dg, dgo, dgi, dgg;   // guarded (b2f_ctx.h)
     const size_t ni = (size_t)B * ih * iw * C, ng = (size_t)B * gh * gw * 2, no = (size_t)B * gh * gw * C;
-    CHK(di.alloc(ni)); CHK(dg.alloc(ng)); CHK(dgo.alloc(no)); CHK(dgg.alloc(ng));
+    CHK(di.alloc(ni, "img")); CHK(dg.alloc(ng, "grid")); CHK(dgo.alloc(no, "grad_out")); CHK(dgg.alloc(ng, "grad_grid"));
     HIPCHK(hipMemcpy(di.p, img, ni * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dg.p, grid, ng * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dgo.p, grad_out, no * sizeof(float), hipMemcpyHostToDevice));
     const unsigned blocks = (unsigned)(((size_t)B * gh * gw + 7) / 8);
     if (grad_img) {
-        CHK(dgi.alloc(ni));
+        CHK(dgi.alloc(ni, "grad_img"));
         HIPCHK(hipMemsetAsync(dgi.p, 0, ni * sizeof(float), c->stream));   // BilinearSamplerBHWD.lua:98-99
         hipLaunchKernelGGL((warp_bhwd_backward_kernel<false>), dim3(blocks), dim3(256), 0, c->stream, di.p, dg.p, dgo.p, B, ih, iw, C, gh, gw, dgi.p, dgg.p);
     } else {
@@ -125,6 +119,7 @@ int b2f_op_warp_bhwd_backward(b2f_ctx *c, const float *img, const float *grid, c
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&di, &dg, &dgo, &dgi, &dgg}));
     if (grad_img) HIPCHK(hipMemcpy(grad_img, dgi.p, ni * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(grad_grid, dgg.p, ng * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
@@ -139,14 +134,15 @@ int b2f_op_costvol_backward(b2f_ctx *c, const float *ref, const float *frm, cons
     if (B <= 0 || C <= 0 || h <= 0 || w <= 0) return api_fail("b2f_op_costvol_backward: bad shape");
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)h * w, nin = (size_t)B * C * hw, ngo = (size_t)B * win * win * hw;
-    DevB dr, df, dgo, dgr, dgf;
-    CHK(dr.alloc(nin)); CHK(df.alloc(nin)); CHK(dgo.alloc(ngo)); CHK(dgr.alloc(nin)); CHK(dgf.alloc(nin));
+    DevBuf dr, df, dgo, dgr, dgf;
+    CHK(dr.alloc(nin, "ref")); CHK(df.alloc(nin, "frm")); CHK(dgo.alloc(ngo, "grad_out")); CHK(dgr.alloc(nin, "grad_ref")); CHK(dgf.alloc(nin, "grad_frm"));
     HIPCHK(hipMemcpy(dr.p, ref, nin * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(df.p, frm, nin * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dgo.p, grad_out, ngo * sizeof(float), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(costvol_backward_kernel, dim3((unsigned)((nin + 255) / 256)), dim3(256), 0, c->stream, dr.p, df.p, dgo.p, B, C, h, w, win, fwd, dgr.p, dgf.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dr, &df, &dgo, &dgr, &dgf}));
     HIPCHK(hipMemcpy(grad_ref, dgr.p, nin * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(grad_frm, dgf.p, nin * sizeof(float), hipMemcpyDeviceToHost));
     return 0;

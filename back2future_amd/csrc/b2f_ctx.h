@@ -8,6 +8,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -283,6 +284,39 @@ inline FlowRequest sequence_request(const char *who, int T, int in_kind, const v
     return {T >= 3 ? T - 2 : 0, true, in_kind, frames, nullptr, nullptr, H0, W0, o, 0, who};
 }
 
+// The word every byte a kernel has no business touching holds in the guarded test set-ups: a quiet NaN whose payload no arithmetic
+// produces.  Compared on bits.
+constexpr uint32_t kGuardWord = 0x7fc0a5a5u;
+
+// One guard of the arena (option arena_guard): floats [off, off + len) of the arena.  An "after" guard starts at the end of buffer `buffer`
+// of the plan (the buffer's own slack included, e.g. the record's + 64) and covers the rounding of its size to 64 floats and the arena_guard
+// floats behind that; the one "before" guard is the arena_guard floats in front of buffer 0.
+struct ArenaGuard {
+    size_t off, len;
+    int buffer;
+    bool before;
+    const char *name;
+};
+
+// A device buffer of the kernel test entries (b2f_op_*): kGuardFloats floats of kGuardWord on each side of the n floats handed to the
+// kernel, which start as kGuardWord too, so that an element the kernel does not write shows.  p is 256-byte aligned.  check(), after the
+// stream has been synchronised, fails with the buffer's name, the side and the offset of the first guard word that changed.
+struct DevBuf {
+    static constexpr size_t kGuardFloats = 4096;
+    float *p = nullptr;
+    float *raw = nullptr;
+    size_t n = 0;
+    const char *name = "";
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (raw) (void)hipFree(raw); }
+    int alloc(size_t count, const char *what);
+    int check() const;
+};
+// check() of every allocated buffer of the list
+int check_guards(std::initializer_list<const DevBuf *> bufs);
+
 // Context-owned device workspace of the device entries (b2f_compute_flow_device / _sequence_device): grows, never shrinks.
 struct DevWork {
     char *dev = nullptr;
@@ -473,6 +507,11 @@ struct b2f_ctx : b2f::KernelOpts {
     int host_threads = 0;          // 0 = auto
     int host_u8 = 1, host_ramp = 1;
     int debug_fail_next = 0;       // tests: the next b2f_compute_flow* call on this context fails (cross-thread error hand-over of b2f_multi_*)
+    // tests ("Guards"): neither is seeded from the environment; setting either frees the arena and drops the captured graphs
+    int arena_guard = 0;           // floats (a multiple of 64) that make_plan places before the first buffer and after every buffer
+    int arena_fill = 0;            // 1: the arena (guards included) and a stream's device block start as kGuardWord instead of 0
+    std::vector<b2f::ArenaGuard> guards;   // arena_guard > 0: the guards of the plan the arena was last filled for (b2f_arena_check)
+    long long arena_layout[9] = {0};       // arena_guard / arena_fill set: that plan's identity; a pass with another one refills the arena first
     std::map<b2f::GraphKey, hipGraphExec_t> graphs;
     // output table of the generic executor (non-shipped graph shapes), kept between calls of one (B, H, W)
     std::vector<float *> gen_out;

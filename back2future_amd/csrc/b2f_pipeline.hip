@@ -954,7 +954,9 @@ int b2f_stream_open(b2f_ctx *c, int cams, int in_kind, int H0, int W0, b2f_strea
         return fail("b2f_stream_open: out of device memory (" + std::to_string(st->dev_bytes >> 20) + " MB for the stream)");
     }
     carve(st->dev);
-    if (hipMemset(st->dev, 0, st->dev_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    // option arena_fill (tests): the block starts as kGuardWord instead of 0, like the arena (carve rounds every piece to 256 bytes)
+    if ((c->arena_fill ? hipMemsetD32((hipDeviceptr_t)st->dev, (int)kGuardWord, st->dev_bytes / 4) : hipMemset(st->dev, 0, st->dev_bytes)) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
         (void)hipFree(st->dev);
         return fail("b2f_stream_open: hipMemset failed");
     }

@@ -872,6 +872,29 @@ B2F_API int b2f_op_upsample_flow2x(b2f_ctx *ctx, const float *x, int B, int h, i
 B2F_API int b2f_op_image_scale(b2f_ctx *ctx, const float *src, int C, int Hs, int Ws, int normalize,
                        float *dst, int Hd, int Wd);
 
+
+/* ---- guards (tests) ----
+ * Options arena_guard (floats, a multiple of 64; default 0) and arena_fill (0 / 1; default 0), b2f_set_option only: the workspace of the
+ * forward pass gets arena_guard floats in front of its first buffer and behind every buffer, and starts as the 32-bit pattern 0x7fc0a5a5
+ * (a quiet NaN) instead of zero, as does the device block of a stream opened afterwards.  Setting either frees the workspace and drops
+ * the captured graphs.  A kernel may read outside its tensors only if the value cannot reach a result, and may write nowhere outside them:
+ * under the two options a result that changes, or a guard word that changes, shows a kernel that does not keep to that.
+ * b2f_arena_check: synchronises, and returns the number of guard words of the last pass's layout that no longer hold what the workspace
+ * was filled with (compared on bits); *buffer_index / *offset (either may be NULL): the first one -- the buffer of the layout it belongs to
+ * and its offset from that buffer's end (>= 0), or from the first buffer's start (< 0: the guard in front of it); b2f_last_error names the
+ * buffer.  0 without arena_guard, -1 on an error.                                                                                  */
+B2F_API int b2f_arena_check(b2f_ctx *ctx, int *buffer_index, long long *offset);
+/* b2f_guard_selftest: overwrites ONE guard word by a copy from the host, so that the checks can be seen to fire.  which = 0: offset +3
+ * behind buffer 1 of the workspace's layout, 1: offset -2 in front of buffer 0 (both need arena_guard and a pass before; b2f_arena_check
+ * then reports that word); 2 / 3: offset +2 behind / -1 in front of a guarded device buffer "selftest" as the b2f_op_* entries allocate
+ * them -- the call then fails as such an entry fails, b2f_last_error naming the buffer, the side and the offset.                   */
+B2F_API int b2f_guard_selftest(b2f_ctx *ctx, int which);
+/* b2f_arena_plan: the workspace layout of a pass, computed on the host (no context, no device): the float offset of each of its 33 buffers
+ * in the order img, tmp, cs[2..7], U[3..6], UB[3..6], cv, d[1..5], fs, bfs, logits, u2, flow_planar, ds[2..5] (0 for one the pass does
+ * not have) and the total.  flags: 1 the full table, 2 a Soft model, 4 a sequence (B = T - 2), 8 a push of a stream, 16 with the past-flow
+ * output.  Returns 33, or -1 with b2f_last_error set.                                                                              */
+B2F_API int b2f_arena_plan(int arena_guard, int B, int H, int W, int flags, long long *offsets, int cap, long long *total);
+
 #ifdef __cplusplus
 }
 #endif
