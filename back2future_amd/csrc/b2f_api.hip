@@ -2075,7 +2075,7 @@ int b2f_op_conv3x3(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, cons
     L.out = dy.p;
     L.out_img_stride = (long)((size_t)Ho * Wo * Co); L.out_chunk_stride = 8; L.out_pix_stride = Co;
     L.H = H; L.W = W; L.stride = stride; L.nimg = B; L.leaky = leaky;
-    CHK(launch_layer(c, c->stream, false, p, dw.p, o, 0, L));
+    CHK(launch_layer(c, c->stream, true, p, dw.p, o, 0, L));   // with option profile: the row names the kernel that ran (tests read the tag)
     HIPCHK(launch_nhwc_to_planar(dy.p, Co, Co, B, Ho, Wo, dyp.p, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     CHK(check_guards({&dpl, &dx, &dw, &dy, &dyp}));
@@ -2254,6 +2254,35 @@ int b2f_op_conv_head16(b2f_ctx *c, const float *x, int B, int H, int W, const fl
     return 0;
 }
 B2F_CATCH("b2f_op_conv_head16")
+
+// The first pyramid conv as the forward launches it (launch_conv_first, pwc.lua:59: conv(3, 16, s2) + LeakyReLU on each of the three
+// frames, after ColorNormalize when normalize != 0).  x: B x 9 x H x W planar, frame f in channels 3 f .. 3 f + 2, H and W even (the
+// kernel computes H / 2 x W / 2 outputs); wt: 16 x 3 x 3 x 3, bias: 16; y: 3 B x 16 x H/2 x W/2 planar, image f * B + b.
+int b2f_op_conv_first(b2f_ctx *c, const float *x, int B, int H, int W, int normalize, const float *wt, const float *bias, float *y) try
+{
+    if (!c || !x || !wt || !bias || !y) return fail("b2f_op_conv_first: null argument");
+    if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail("b2f_op_conv_first: H and W must be even and at least 2");
+    HIPCHK(hipSetDevice(c->device));
+    const int Ho = H / 2, Wo = W / 2;
+    const size_t hwo = (size_t)Ho * Wo, nx = (size_t)B * 9 * H * W, ny = (size_t)3 * B * 16 * hwo;
+    std::vector<float> wp(27 * 16), out(ny);
+    for (int o = 0; o < 16; ++o)
+        for (int t = 0; t < 27; ++t) wp[(size_t)t * 16 + o] = wt[(size_t)o * 27 + t];   // as pack_all packs it
+    DevBuf dx, dw, db, dy;
+    CHK(dx.alloc(nx, "x")); CHK(dw.alloc(wp.size(), "weights")); CHK(db.alloc(16, "bias")); CHK(dy.alloc(ny, "y"));
+    HIPCHK(hipMemcpy(dx.p, x, nx * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dw.p, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db.p, bias, 16 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(launch_conv_first(dx.p, normalize ? 1 : 0, B, H, W, dw.p, db.p, dy.p, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dx, &dw, &db, &dy}));
+    HIPCHK(hipMemcpy(out.data(), dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t img = 0; img < (size_t)3 * B; ++img)          // chunk-planar [img][2][hw][8] -> planar
+        for (int o = 0; o < 16; ++o)
+            for (size_t q = 0; q < hwo; ++q) y[(img * 16 + o) * hwo + q] = out[((img * 2 + (o >> 3)) * hwo + q) * 8 + (o & 7)];
+    return 0;
+}
+B2F_CATCH("b2f_op_conv_first")
 
 }  // extern "C"
 

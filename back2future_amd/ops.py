@@ -104,6 +104,17 @@ def conv_head16(model, x, w1, b1, w2, b2):
     return y
 
 
+def conv_first(model, x, w, b, normalize=False):
+    """The first pyramid conv as the forward launches it: conv(3, 16, s2) + LeakyReLU(0.2) on each of the three frames of x (B x 9 x H x W,
+    H and W even), after ColorNormalize when normalize; returns 3 B x 16 x H/2 x W/2, image f * B + b (pwc.lua:59)."""
+    x, w, b = _lib.f32(x), _lib.f32(w), _lib.f32(b)
+    B, nine, H, W = x.shape
+    assert nine == 9 and w.shape == (16, 3, 3, 3) and b.shape == (16,)
+    y = np.empty((3 * B, 16, H // 2, W // 2), np.float32)
+    _lib.check(_lib.lib().b2f_op_conv_first(_h(model), _lib.fptr(x), B, H, W, int(bool(normalize)), _lib.fptr(w), _lib.fptr(b), _lib.fptr(y)))
+    return y
+
+
 def upsample_flow2x(model, x):
     x = _lib.f32(x)
     B, two, h, w = x.shape

@@ -863,6 +863,10 @@ B2F_API int b2f_op_cv_variant(b2f_ctx *ctx, int B, int C, int h, int w, int layo
  * x: B x 16 x H x W, w1: 16 x 16 x 3 x 3, w2: 32 x 16 x 3 x 3, y: B x 32 x ceil(H/2) x ceil(W/2).                       */
 B2F_API int b2f_op_conv_head16(b2f_ctx *ctx, const float *x, int B, int H, int W, const float *w1, const float *b1,
                        const float *w2, const float *b2, float *y);
+/* The first conv of the pyramid as the forward launches it: nn.SpatialConvolution(3,16,3,3,2,2,1,1) + LeakyReLU(0.2) (pwc.lua:59) on each
+ * of the three frames, after ColorNormalize when normalize != 0.  x: B x 9 x H x W (frame f in planes 3f .. 3f + 2), H and W even;
+ * w: 16 x 3 x 3 x 3, b: 16; y: 3B x 16 x H/2 x W/2, image f * B + b.                                                       */
+B2F_API int b2f_op_conv_first(b2f_ctx *ctx, const float *x, int B, int H, int W, int normalize, const float *w, const float *b, float *y);
 /* nn.SpatialUpSamplingBilinear(2) on a 2-channel flow field -- pwc.lua:360-381;
  * x: B x 2 x h x w -> y: B x 2 x 2h x 2w.                                            */
 B2F_API int b2f_op_upsample_flow2x(b2f_ctx *ctx, const float *x, int B, int h, int w, float *y);

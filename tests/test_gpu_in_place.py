@@ -16,32 +16,16 @@ import pytest
 
 from back2future_amd import _lib, back2future, ops, weights as W
 from oracle import oracle as O
+from tests.layer_models import BIG, SETTINGS, flat as _flat, name as _name, open_model  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 FEAT = W.FEAT
-BIG = 1 << 30
 SIZES = [(1, 1), (8, 16), (17, 33), (24, 40)]     # of the output: smallest; one F(2x2) tile; one past an F(4x4) block both ways, ragged for 6 x 6 tiles; a level of the forward
 HOLE_SIZE = (17, 33)
 
-# option sets; every one also gets adaptive_kernels = 0 unless it sets that option
-SETTINGS = {
-    "default": {"adaptive_kernels": -1},
-    "f4x4": {"wino4_min_pixels": 0, "wino6": 0},
-    "f6x6": {"wino4_min_pixels": 0, "wino6": 1, "wino6_min_pixels": 0},
-    "wino1d-1": {"wino4_min_pixels": 0, "wino6": 0, "wino1d": 1},
-    "wino1d-2": {"wino4_min_pixels": 0, "wino6": 0, "wino1d": 2},
-    "bf16-wide": {"wino4_min_pixels": 0, "bf16_conv": 3, "bf16_conv_min_pixels": 0},
-    "f2x2-split": {"wino4_min_pixels": BIG, "wino_split_pixels": BIG},
-    "adaptive": {"adaptive_kernels": 1},
-    "bf16_conv-0": {"bf16_conv": 0},
-    "s2_loader-0": {"s2_loader": 0},
-    "s2_loader-2": {"s2_loader": 2},
-    "s2_tile_groups-0": {"s2_loader": 2, "s2_tile_groups": 0},
-    "s2_tiles_per_block-2": {"bf16_conv": 0, "s2_tiles_per_block": 2},
-}
 WIDE = ["default", "f4x4", "f6x6", "wino1d-1", "wino1d-2", "bf16-wide", "f2x2-split", "adaptive"]      # stride 1, >= 32 outputs: the F(4x4) class
 STRIDE2 = ["default", "bf16_conv-0", "s2_loader-0", "s2_loader-2", "s2_tile_groups-0", "s2_tiles_per_block-2"]
 FIXED = ["default"]                                                                                   # 16 -> 16, 16 -> 32, 32 -> 2: one kernel each
@@ -86,34 +70,13 @@ def _expected_tags(cls, setting, co):
 
 # ---- models: one context per (kind, setting), alive for the module ----
 
-@functools.lru_cache(maxsize=None)
-def _flat(which):
-    """normal weights of variance 1 / (9 Ci) per layer, normal bias: what the op tests draw"""
-    past = which == "soft"
-    lay, total = W.layout(past)
-    r = np.random.default_rng(71 + past)
-    flat = np.empty(total, np.float32)
-    for name, shape, off in lay:
-        n = int(np.prod(shape))
-        if name.endswith(".w"):
-            flat[off:off + n] = (r.standard_normal(n, dtype=np.float32) / np.sqrt(9 * shape[1])).astype(np.float32)
-        else:
-            flat[off:off + n] = r.standard_normal(n, dtype=np.float32)
-    return flat
-
-
 _MODELS = {}
 
 
 def _model(which, setting):
     key = (which, setting)
     if key not in _MODELS:
-        m = back2future.Model("random:%s:5:2.0" % which)
-        m.set_weights(_flat(which))
-        opts = dict({"adaptive_kernels": 0}, **SETTINGS[setting])
-        for k, v in dict(opts, profile=1, profile_layers=1).items():
-            m.set_option(k, v)
-        _MODELS[key] = m
+        _MODELS[key] = open_model(which, setting)
     return _MODELS[key]
 
 
@@ -153,10 +116,6 @@ def _layers():
         for idx in range(2, 7):
             out.append((which, kind, l, idx, "fixed" if idx == 6 else "wide"))
     return out
-
-
-def _name(kind, level, idx):
-    return ("feat%d.conv%d" % (level, idx)) if kind == "feat" else "l%d.%s.conv%d" % (level, kind, idx)
 
 
 def _float64(x, wt, b, stride, leaky):
