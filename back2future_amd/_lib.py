@@ -263,6 +263,21 @@ SIGNATURES = {
     "b2f_op_conv_head16": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]),
     "b2f_op_upsample_flow2x": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, c_float_p]),
     "b2f_op_image_scale": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int]),
+    "b2f_op_upsample_flow2x_ex": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "b2f_op_softmax_nearest4": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "b2f_op_avgpool2": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "b2f_op_pack_input": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "b2f_op_warp_image": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_float, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "b2f_op_conv_first_seq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p]),
+    "b2f_op_layout": (C.c_int, [C.c_void_p, C.c_int, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "b2f_op_graph_put_channels": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int]),
+    "b2f_op_graph_costvol": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       c_float_p, C.c_int, c_float_p, C.c_int]),
+    "b2f_op_graph_warp": (C.c_int, [C.c_void_p, c_float_p, C.c_int, c_float_p, C.c_float, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "b2f_op_graph_add_flow": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_longlong]),
+    "b2f_op_graph_scale": (C.c_int, [C.c_void_p, c_float_p, C.c_longlong, C.c_float]),
+    "b2f_op_graph_softmax_nearest": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "b2f_op_expf": (C.c_int, [C.c_void_p, c_float_p, C.c_longlong, c_float_p]),
     "b2f_arena_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "b2f_guard_selftest": (C.c_int, [C.c_void_p, C.c_int]),
     "b2f_arena_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_longlong)]),

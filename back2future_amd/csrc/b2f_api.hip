@@ -976,7 +976,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1008; }
+int b2f_version(void) { return 1009; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -2283,6 +2283,159 @@ int b2f_op_conv_first(b2f_ctx *c, const float *x, int B, int H, int W, int norma
     return 0;
 }
 B2F_CATCH("b2f_op_conv_first")
+
+}  // extern "C"
+
+// ---- the forward's small kernels (b2f_glue.hip, b2f_seq.hip), one entry per launcher on the caller's own strides: the host hands over the
+// records as the forward lays them out (e.g. 8-float flow records whose slots 2..7 hold NaN), nothing is repacked on the way in.
+// tests/test_gpu_glue_float64.py
+namespace {
+int op_upload(DevBuf &d, const void *host, size_t bytes, const char *what)
+{
+    CHK(d.alloc((bytes + 3) / 4, what));
+    HIPCHK(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+inline int op_upload(DevBuf &d, const float *host, size_t n, const char *what) { return op_upload(d, (const void *)host, n * sizeof(float), what); }
+inline bool small_dims(long long a, long long b, long long c) { return a >= 1 && b >= 1 && c >= 1 && a * b * c <= (1LL << 26); }
+}  // namespace
+
+extern "C" {
+
+int b2f_op_upsample_flow2x_ex(b2f_ctx *c, const float *x, int ps, int B, int h, int w, int planar, float *y) try
+{
+    if (!c || !x || !y) return fail("b2f_op_upsample_flow2x_ex: null argument");
+    if (!small_dims(B, h, w) || ps < 2 || (ps & 1) || ps > 64) return fail("b2f_op_upsample_flow2x_ex: bad shape (B, h, w >= 1, ps even in 2..64)");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t nx = (size_t)B * h * w * ps, ny = (size_t)B * 8 * h * w;
+    DevBuf dx, dy;
+    CHK(op_upload(dx, x, nx, "x")); CHK(dy.alloc(ny, "y"));
+    if (planar) HIPCHK(launch_upsample_flow2x_planar(dx.p, ps, B, h, w, dy.p, c->stream));
+    else HIPCHK(launch_upsample_flow2x(dx.p, ps, B, h, w, dy.p, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dx, &dy}));
+    HIPCHK(hipMemcpy(y, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+B2F_CATCH("b2f_op_upsample_flow2x_ex")
+
+int b2f_op_softmax_nearest4(b2f_ctx *c, const float *logits, int ps, int B, int h, int w, float *out) try
+{
+    if (!c || !logits || !out) return fail("b2f_op_softmax_nearest4: null argument");
+    if (!small_dims(B, h, w) || ps < 2 || (ps & 1) || ps > 64) return fail("b2f_op_softmax_nearest4: bad shape (B, h, w >= 1, ps even in 2..64)");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t nx = (size_t)B * h * w * ps, ny = (size_t)B * 32 * h * w;
+    DevBuf dx, dy;
+    CHK(op_upload(dx, logits, nx, "logits")); CHK(dy.alloc(ny, "out"));
+    HIPCHK(launch_softmax_nearest4_planar(dx.p, ps, B, h, w, dy.p, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dx, &dy}));
+    HIPCHK(hipMemcpy(out, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+B2F_CATCH("b2f_op_softmax_nearest4")
+
+int b2f_op_avgpool2(b2f_ctx *c, const float *x, int nimg, int H, int W, int C, float *y) try
+{
+    if (!c || !x || !y) return fail("b2f_op_avgpool2: null argument");
+    if (!small_dims(nimg, H, W) || H < 2 || W < 2 || C < 4 || (C & 3) || C > 1024) return fail("b2f_op_avgpool2: bad shape (H, W >= 2, C a multiple of 4)");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t nx = (size_t)nimg * H * W * C, ny = (size_t)nimg * (H / 2) * (W / 2) * C;
+    DevBuf dx, dy;
+    CHK(op_upload(dx, x, nx, "x")); CHK(dy.alloc(ny, "y"));
+    HIPCHK(launch_avgpool2_nhwc(dx.p, nimg, H, W, C, dy.p, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dx, &dy}));
+    HIPCHK(hipMemcpy(y, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+B2F_CATCH("b2f_op_avgpool2")
+
+int b2f_op_pack_input(b2f_ctx *c, const float *x, int normalize, int B, int H, int W, float *img) try
+{
+    if (!c || !x || !img) return fail("b2f_op_pack_input: null argument");
+    if (!small_dims(B, H, W)) return fail("b2f_op_pack_input: bad shape");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t nx = (size_t)B * 9 * H * W, ny = (size_t)3 * B * H * W * kImgC;
+    DevBuf dx, dy;
+    CHK(op_upload(dx, x, nx, "x")); CHK(dy.alloc(ny, "img"));
+    HIPCHK(launch_pack_input(dx.p, normalize ? 1 : 0, B, H, W, dy.p, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dx, &dy}));
+    HIPCHK(hipMemcpy(img, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+B2F_CATCH("b2f_op_pack_input")
+
+int b2f_op_warp_image(b2f_ctx *c, int which, const void *in, int in_kind, int frame, const float *flow, float k, int B, int H, int W,
+                      float *out) try
+{
+    if (!c || !in || !flow || !out) return fail("b2f_op_warp_image: null argument");
+    if (!small_dims(B, H, W)) return fail("b2f_op_warp_image: bad shape");
+    if (which < 0 || which > 2) return fail("b2f_op_warp_image: which must be 0 (warp_image_planar), 1 (warp_input_planar) or 2 (warp_input_seq)");
+    if (which == 1 && (frame < 0 || frame > 2 || (in_kind != B2F_IN_NORMALIZED && in_kind != B2F_IN_UNIT)))
+        return fail("b2f_op_warp_image: warp_input_planar takes frame 0..2 and float samples");
+    if (which == 2 && in_kind != B2F_IN_NORMALIZED && in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail("b2f_op_warp_image: bad in_kind");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw = (size_t)H * W, samples = which == 0 ? (size_t)B * hw * kImgC : (which == 1 ? (size_t)B * 9 * hw : (size_t)B * 3 * hw);
+    const size_t bytes = samples * ((which == 2 && in_kind == B2F_IN_U8) ? 1 : sizeof(float)), no = (size_t)B * 3 * hw;
+    DevBuf di, df, dout;
+    CHK(op_upload(di, in, bytes, "in")); CHK(op_upload(df, flow, (size_t)B * 2 * hw, "flow")); CHK(dout.alloc(no, "out"));
+    if (which == 0) HIPCHK(launch_warp_image_planar(di.p, df.p, k, B, H, W, dout.p, c->stream));
+    else if (which == 1) HIPCHK(launch_warp_input_planar(di.p, in_kind == B2F_IN_UNIT ? 1 : 0, frame, df.p, k, B, H, W, dout.p, c->stream));
+    else HIPCHK(launch_warp_input_seq(di.p, in_kind, df.p, k, B, H, W, dout.p, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&di, &df, &dout}));
+    HIPCHK(hipMemcpy(out, dout.p, no * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+B2F_CATCH("b2f_op_warp_image")
+
+int b2f_op_conv_first_seq(b2f_ctx *c, const void *x, int in_kind, int T, int H, int W, const float *wt, const float *bias, float *y) try
+{
+    if (!c || !x || !wt || !bias || !y) return fail("b2f_op_conv_first_seq: null argument");
+    if (!small_dims(T, H, W) || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail("b2f_op_conv_first_seq: H and W must be even and at least 2");
+    if (in_kind != B2F_IN_NORMALIZED && in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail("b2f_op_conv_first_seq: bad in_kind");
+    HIPCHK(hipSetDevice(c->device));
+    const int Ho = H / 2, Wo = W / 2;
+    const size_t hwo = (size_t)Ho * Wo, nx = (size_t)T * 3 * H * W, ny = (size_t)T * 16 * hwo;
+    std::vector<float> wp(27 * 16), out(ny);
+    for (int o = 0; o < 16; ++o)
+        for (int t = 0; t < 27; ++t) wp[(size_t)t * 16 + o] = wt[(size_t)o * 27 + t];   // as pack_all packs it
+    DevBuf dx, dw, db, dy;
+    CHK(op_upload(dx, x, nx * (in_kind == B2F_IN_U8 ? 1 : sizeof(float)), "x")); CHK(op_upload(dw, wp.data(), wp.size(), "weights"));
+    CHK(op_upload(db, bias, 16, "bias")); CHK(dy.alloc(ny, "y"));
+    HIPCHK(launch_conv_first_seq(dx.p, in_kind, T, H, W, dw.p, db.p, dy.p, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&dx, &dw, &db, &dy}));
+    HIPCHK(hipMemcpy(out.data(), dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t img = 0; img < (size_t)T; ++img)          // chunk-planar [img][2][hw][8] -> planar
+        for (int o = 0; o < 16; ++o)
+            for (size_t q = 0; q < hwo; ++q) y[(img * 16 + o) * hwo + q] = out[((img * 2 + (o >> 3)) * hwo + q) * 8 + (o & 7)];
+    return 0;
+}
+B2F_CATCH("b2f_op_conv_first_seq")
+
+int b2f_op_layout(b2f_ctx *c, int which, const float *in, int C, int pix_stride, int B, int h, int w, float *out) try
+{
+    if (!c || !in || !out) return fail("b2f_op_layout: null argument");
+    if (!small_dims(B, h, w) || C < 1 || C > 4096) return fail("b2f_op_layout: bad shape");
+    if (which < 0 || which > 2) return fail("b2f_op_layout: which must be 0 (nhwc_to_planar), 1 (cp8_to_planar) or 2 (planar_to_nhwc)");
+    if (which != 1 && (pix_stride < C || pix_stride > 8192)) return fail("b2f_op_layout: pix_stride must be at least C");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t hw = (size_t)h * w, planar = (size_t)B * C * hw, nhwc = (size_t)B * hw * pix_stride, cp8 = (size_t)B * ((C + 7) / 8) * hw * 8;
+    const size_t ni = which == 0 ? nhwc : (which == 1 ? cp8 : planar), no = which == 2 ? nhwc : planar;
+    DevBuf di, dout;
+    CHK(op_upload(di, in, ni, "in")); CHK(dout.alloc(no, "out"));
+    if (which == 0) HIPCHK(launch_nhwc_to_planar(di.p, pix_stride, C, B, h, w, dout.p, c->stream));
+    else if (which == 1) HIPCHK(launch_cp8_to_planar(di.p, C, B, h, w, dout.p, c->stream));
+    else HIPCHK(launch_planar_to_nhwc(di.p, C, B, h, w, dout.p, pix_stride, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(check_guards({&di, &dout}));
+    HIPCHK(hipMemcpy(out, dout.p, no * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+B2F_CATCH("b2f_op_layout")
 
 }  // extern "C"
 

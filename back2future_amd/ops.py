@@ -338,3 +338,159 @@ def table_loss_grad(table, ref, flow_scale=20.0, options=None, model=None):
                              "table's kind or model=None" % ("Soft" if per == 5 else "Hard", len(tab), "Soft" if model.past_flow else "Hard"))
         _lib.check(_grad_entry("b2f_op_table_loss_grad", options)(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), _grad_opts_ptr(options), gp))
     return grad
+
+
+# ---- the small kernels of a forward pass, one launcher each, on the caller's own strides (tests/glue_float64.py) ----------------------
+
+def _u8_or_f32(a):
+    a = np.asarray(a)
+    return np.ascontiguousarray(a) if a.dtype == np.uint8 else _lib.f32(a)
+
+
+def _in_kind(a, normalized):
+    from .back2future import IN_NORMALIZED, IN_U8, IN_UNIT
+    return IN_U8 if a.dtype == np.uint8 else (IN_NORMALIZED if normalized else IN_UNIT)
+
+
+def upsample_flow2x_records(model, x, planar=False):
+    """nn.SpatialUpSamplingBilinear(2) of slots 0..1 of the records x: B x h x w x ps -> B x 2h x 2w x 2, or planar B x 2 x 2h x 2w."""
+    x = _lib.f32(x)
+    B, h, w, ps = x.shape
+    y = np.empty((B, 2, 2 * h, 2 * w) if planar else (B, 2 * h, 2 * w, 2), np.float32)
+    _lib.check(_lib.lib().b2f_op_upsample_flow2x_ex(_h(model), _lib.fptr(x), ps, B, h, w, int(bool(planar)), _lib.fptr(y)))
+    return y
+
+
+def softmax_nearest4(model, logits):
+    """softmax over slots 0..1 of the records logits: B x h x w x ps, repeated 4 x 4 -> B x 2 x 4h x 4w"""
+    x = _lib.f32(logits)
+    B, h, w, ps = x.shape
+    y = np.empty((B, 2, 4 * h, 4 * w), np.float32)
+    _lib.check(_lib.lib().b2f_op_softmax_nearest4(_h(model), _lib.fptr(x), ps, B, h, w, _lib.fptr(y)))
+    return y
+
+
+def avgpool2(model, x):
+    """nn.SpatialAveragePooling(2,2,2,2) on n x H x W x C -> n x H/2 x W/2 x C"""
+    x = _lib.f32(x)
+    n, H, W, Cc = x.shape
+    y = np.empty((n, H // 2, W // 2, Cc), np.float32)
+    _lib.check(_lib.lib().b2f_op_avgpool2(_h(model), _lib.fptr(x), n, H, W, Cc, _lib.fptr(y)))
+    return y
+
+
+def pack_input(model, x, normalize=False):
+    """B x 9 x H x W -> the packed frames 3 x B x H x W x 8"""
+    x = _lib.f32(x)
+    B, nine, H, W = x.shape
+    assert nine == 9
+    y = np.empty((3, B, H, W, 8), np.float32)
+    _lib.check(_lib.lib().b2f_op_pack_input(_h(model), _lib.fptr(x), int(bool(normalize)), B, H, W, _lib.fptr(y)))
+    return y
+
+
+def warp_image(model, which, x, flow, k, normalized=True, frame=0):
+    """which 'image': x B x H x W x 8 packed (launch_warp_image_planar); 'input': x B x 9 x H x W, its frame `frame`, normalized on the
+    fly unless `normalized` (launch_warp_input_planar); 'seq': x B x 3 x H x W float32 or uint8 (launch_warp_input_seq).
+    flow B x 2 x H x W -> B x 3 x H x W."""
+    w_i = {"image": 0, "input": 1, "seq": 2}[which]
+    x, flow = _u8_or_f32(x), _lib.f32(flow)
+    B, _two, H, W = flow.shape
+    assert x.shape == {0: (B, H, W, 8), 1: (B, 9, H, W), 2: (B, 3, H, W)}[w_i] and (w_i == 2 or x.dtype == np.float32)
+    out = np.empty((B, 3, H, W), np.float32)
+    _lib.check(_lib.lib().b2f_op_warp_image(_h(model), w_i, C.c_void_p(x.ctypes.data), _in_kind(x, normalized), int(frame), _lib.fptr(flow),
+                                            float(k), B, H, W, _lib.fptr(out)))
+    return out
+
+
+def conv_first_seq(model, x, w, b, normalized=True):
+    """ops.conv_first on the frames of a sequence: x T x 3 x H x W float32 (normalized or unit) or uint8 -> T x 16 x H/2 x W/2"""
+    x, w, b = _u8_or_f32(x), _lib.f32(w), _lib.f32(b)
+    T, three, H, W = x.shape
+    assert three == 3 and w.shape == (16, 3, 3, 3) and b.shape == (16,)
+    y = np.empty((T, 16, H // 2, W // 2), np.float32)
+    _lib.check(_lib.lib().b2f_op_conv_first_seq(_h(model), C.c_void_p(x.ctypes.data), _in_kind(x, normalized), T, H, W, _lib.fptr(w), _lib.fptr(b),
+                                                _lib.fptr(y)))
+    return y
+
+
+def layout(model, which, x, Cc, pix_stride=0):
+    """'nhwc_to_planar': B x h x w x pix_stride -> B x Cc x h x w; 'cp8_to_planar': B x ceil(Cc/8) x h x w x 8 -> B x Cc x h x w;
+    'planar_to_nhwc': B x Cc x h x w -> B x h x w x pix_stride"""
+    w_i = {"nhwc_to_planar": 0, "cp8_to_planar": 1, "planar_to_nhwc": 2}[which]
+    x = _lib.f32(x)
+    if w_i == 0:
+        B, h, w, pix_stride = x.shape
+    elif w_i == 1:
+        B, _chunks, h, w, _eight = x.shape
+        assert _chunks == (Cc + 7) // 8 and _eight == 8
+    else:
+        B, _c, h, w = x.shape
+        assert _c == Cc
+    out = np.empty((B, h, w, pix_stride) if w_i == 2 else (B, Cc, h, w), np.float32)
+    _lib.check(_lib.lib().b2f_op_layout(_h(model), w_i, _lib.fptr(x), Cc, pix_stride, B, h, w, _lib.fptr(out)))
+    return out
+
+
+def graph_put_channels(model, src, kind, Cc, dst, c_off):
+    """put_channels of the generic executor: Cc channels of src (kind 0: B x chunks x hw x 8, 1: B x hw x Cc, 2: B x Cc x hw) into
+    channels c_off .. of a copy of dst (B x chunks x hw x 8), which is returned"""
+    src, dst = _lib.f32(src), _lib.f32(dst).copy()
+    B, dch, hw, _e = dst.shape
+    _lib.check(_lib.lib().b2f_op_graph_put_channels(_h(model), _lib.fptr(src), kind, src.shape[1] if kind == 0 else 0, Cc, B, hw, _lib.fptr(dst),
+                                                    dch, c_off))
+    return dst
+
+
+def graph_costvol(model, ref, frmF, frmB, Cc, win, chunksJ, chunksS=0):
+    """costvol_cp8 of the generic executor on chunk-planar maps B x chunks x h x w x 8: (dstJ B x chunksJ x h x w x 8, dstS or None)"""
+    ref, frmF = _lib.f32(ref), _lib.f32(frmF)
+    frmB = _lib.f32(frmB) if frmB is not None else None
+    B, ch, h, w, _e = ref.shape
+    J = np.empty((B, chunksJ, h, w, 8), np.float32)
+    S = np.empty((B, chunksS, h, w, 8), np.float32) if chunksS else None
+    _lib.check(_lib.lib().b2f_op_graph_costvol(_h(model), _lib.fptr(ref), _lib.fptr(frmF), _lib.fptr(frmB) if frmB is not None else None, ch, Cc, B,
+                                               h, w, win, _lib.fptr(J), chunksJ, _lib.fptr(S) if S is not None else None, chunksS))
+    return J, S
+
+
+def graph_warp(model, img, flow, k):
+    """warp_cp8 of the generic executor: img B x chunks x h x w x 8, flow B x h x w x 2"""
+    img, flow = _lib.f32(img), _lib.f32(flow)
+    B, ch, h, w, _e = img.shape
+    assert flow.shape == (B, h, w, 2)
+    out = np.empty_like(img)
+    _lib.check(_lib.lib().b2f_op_graph_warp(_h(model), _lib.fptr(img), ch, _lib.fptr(flow), float(k), B, h, w, _lib.fptr(out)))
+    return out
+
+
+def graph_add_flow(model, fs, u):
+    """fs: npix x 8 records, u: npix x 2 -> fs with u added to slots 0..1"""
+    fs, u = _lib.f32(fs).copy(), _lib.f32(u)
+    assert fs.ndim == 2 and fs.shape[1] == 8 and u.shape == (fs.shape[0], 2)
+    _lib.check(_lib.lib().b2f_op_graph_add_flow(_h(model), _lib.fptr(fs), _lib.fptr(u), fs.shape[0]))
+    return fs
+
+
+def graph_scale(model, p, k):
+    p = _lib.f32(p).copy()
+    _lib.check(_lib.lib().b2f_op_graph_scale(_h(model), _lib.fptr(p), p.size, float(k)))
+    return p
+
+
+def graph_softmax_nearest(model, logits, f):
+    """softmax_nearest of the generic executor: logits B x h x w x 8 -> B x 2 x f h x f w"""
+    x = _lib.f32(logits)
+    B, h, w, _e = x.shape
+    assert _e == 8
+    out = np.empty((B, 2, f * h, f * w), np.float32)
+    _lib.check(_lib.lib().b2f_op_graph_softmax_nearest(_h(model), _lib.fptr(x), B, h, w, int(f), _lib.fptr(out)))
+    return out
+
+
+def expf(model, x):
+    """expf of the device library, elementwise, as the softmax kernels call it"""
+    x = _lib.f32(x)
+    y = np.empty_like(x)
+    _lib.check(_lib.lib().b2f_op_expf(_h(model), _lib.fptr(x), x.size, _lib.fptr(y)))
+    return y

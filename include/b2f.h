@@ -876,6 +876,52 @@ B2F_API int b2f_op_upsample_flow2x(b2f_ctx *ctx, const float *x, int B, int h, i
 B2F_API int b2f_op_image_scale(b2f_ctx *ctx, const float *src, int C, int Hs, int Ws, int normalize,
                        float *dst, int Hd, int Wd);
 
+/* ---- the small kernels of a forward pass, one entry per launcher (tests/test_gpu_glue_float64.py; b2f_version() >= 1009) ----
+ * Each entry uploads the host arrays as they are, runs ONE launcher with the stride arguments it is given, and downloads the result:
+ * nothing is repacked, so the caller lays records out as the forward does (an 8-float record whose slots the kernel does not own may
+ * hold NaN).  Outputs start as a NaN pattern: an element the kernel leaves out stays NaN.
+ * b2f_op_upsample_flow2x_ex: nn.SpatialUpSamplingBilinear(2) (pwc.lua:360-381) of the first two floats of the ps-float records
+ * x: B x h x w x ps (ps even; the forward: 8, and 2 for the second step); planar = 0: y B x 2h x 2w x 2 (launch_upsample_flow2x),
+ * planar = 1: y B x 2 x 2h x 2w (launch_upsample_flow2x_planar).  2h > 65535 is an error.                                     */
+B2F_API int b2f_op_upsample_flow2x_ex(b2f_ctx *ctx, const float *x, int ps, int B, int h, int w, int planar, float *y);
+/* nn.SpatialSoftMax over the first two floats of the ps-float records logits: B x h x w x ps + two nn.SpatialUpSamplingNearest(2)
+ * (pwc.lua:308-321) -> out: B x 2 x 4h x 4w.  4h > 65535 is an error.                                                          */
+B2F_API int b2f_op_softmax_nearest4(b2f_ctx *ctx, const float *logits, int ps, int B, int h, int w, float *out);
+/* nn.SpatialAveragePooling(2,2,2,2) (pwc.lua:155) on x: nimg x H x W x C (C a multiple of 4) -> y: nimg x H/2 x W/2 x C.        */
+B2F_API int b2f_op_avgpool2(b2f_ctx *ctx, const float *x, int nimg, int H, int W, int C, float *y);
+/* The packed frames of a triplet batch: x B x 9 x H x W -> img 3 x B x H x W x 8 (frame-major; RGB, ColorNormalize when normalize != 0,
+ * then five zeros).                                                                                                              */
+B2F_API int b2f_op_pack_input(b2f_ctx *ctx, const float *x, int normalize, int B, int H, int W, float *img);
+/* The three image warps by k * flow (flow: B x 2 x H x W planar; out: B x 3 x H x W).  which = 0: launch_warp_image_planar, in = B x H x W
+ * x 8 packed frames; 1: launch_warp_input_planar, in = B x 9 x H x W, frame 0..2, in_kind B2F_IN_NORMALIZED / B2F_IN_UNIT; 2:
+ * launch_warp_input_seq, in = B x 3 x H x W samples of in_kind (B2F_IN_U8: bytes).                                               */
+B2F_API int b2f_op_warp_image(b2f_ctx *ctx, int which, const void *in, int in_kind, int frame, const float *flow, float k, int B,
+                      int H, int W, float *out);
+/* b2f_op_conv_first on the frames of a sequence (launch_conv_first_seq): x T x 3 x H x W samples of in_kind, H and W even;
+ * w: 16 x 3 x 3 x 3, b: 16; y: T x 16 x H/2 x W/2.                                                                               */
+B2F_API int b2f_op_conv_first_seq(b2f_ctx *ctx, const void *x, int in_kind, int T, int H, int W, const float *w, const float *b, float *y);
+/* Layout changes.  which = 0: launch_nhwc_to_planar, in B x h x w x pix_stride -> out B x C x h x w; 1: launch_cp8_to_planar, in
+ * B x ceil(C/8) x h x w x 8 -> out B x C x h x w; 2: launch_planar_to_nhwc, in B x C x h x w -> out B x h x w x pix_stride (zeros
+ * from channel C on).                                                                                                            */
+B2F_API int b2f_op_layout(b2f_ctx *ctx, int which, const float *in, int C, int pix_stride, int B, int h, int w, float *out);
+/* The node kernels of the generic executor (csrc/b2f_graph.hip), chunk-planar maps B x chunks x hw x 8.
+ * put_channels: C channels of src (kind 0: chunk-planar with src_chunks planes, 1: packed B x hw x C, 2: planar B x C x hw) into
+ * channels c_off .. c_off + C - 1 of dst (in and out).
+ * costvol: nn.CostVolMulti(win){ref, frmF} joined with (win, false){ref, frmB} (frmB may be NULL) into dstJ (chunksJ planes; what
+ * the kernel does not write stays NaN), and their sum into dstS (or NULL).
+ * warp: warpingUnit(img, k * flow), flow packed B x hw x 2.  add_flow: fs[pix][0..1] += u[pix][0..1] on 8-float records.
+ * scale: p[i] *= k.  softmax_nearest: as b2f_op_softmax_nearest4 with ps = 8 and any factor f.                                   */
+B2F_API int b2f_op_graph_put_channels(b2f_ctx *ctx, const float *src, int kind, int src_chunks, int C, int B, int hw, float *dst,
+                              int dst_chunks, int c_off);
+B2F_API int b2f_op_graph_costvol(b2f_ctx *ctx, const float *ref, const float *frmF, const float *frmB, int chunks, int C, int B, int h,
+                         int w, int win, float *dstJ, int chunksJ, float *dstS, int chunksS);
+B2F_API int b2f_op_graph_warp(b2f_ctx *ctx, const float *img, int chunks, const float *flow, float k, int B, int h, int w, float *out);
+B2F_API int b2f_op_graph_add_flow(b2f_ctx *ctx, float *fs, const float *u, long long npix);
+B2F_API int b2f_op_graph_scale(b2f_ctx *ctx, float *p, long long n, float k);
+B2F_API int b2f_op_graph_softmax_nearest(b2f_ctx *ctx, const float *logits, int B, int h, int w, int f, float *out);
+/* y[i] = expf(x[i]), the library function of the two softmax kernels as their sources compile it: the yardstick of their bound.  */
+B2F_API int b2f_op_expf(b2f_ctx *ctx, const float *x, long long n, float *y);
+
 
 /* ---- guards (tests) ----
  * Options arena_guard (floats, a multiple of 64; default 0) and arena_fill (0 / 1; default 0), b2f_set_option only: the workspace of the
