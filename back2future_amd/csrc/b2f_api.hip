@@ -830,11 +830,28 @@ int b2f::run_conv_layer(b2f_ctx *c, hipStream_t s, bool cap, int conv_id, const 
     if (conv_id < 0) return fail("b2f: layer not present in this model");
     return run_conv(c, s, cap, conv_id, segs, nimg, H, W, stride, leaky, out);
 }
-int b2f::ensure_arena(b2f_ctx *c, size_t floats)
+// The generic executor lays the arena out itself (graph_run's Bump): no plan's guards, and the next plan refills.  With arena_guard /
+// arena_fill its layout is treated as prepare_test_arena treats a plan: refilled whenever it differs from the pass before -- another
+// shape, guard width, fill, arena, or a plan in between -- and its guards remembered, by role and level, for b2f_arena_check.
+int b2f::ensure_arena(b2f_ctx *c, size_t floats, std::vector<GraphBuf> &&bufs, int B, int H, int W)
 {
     CHK(ensure_workspace_floats(c, floats));
-    c->guards.clear();          // the generic executor lays the arena out itself: no plan's guards, and the next plan refills
-    c->arena_layout[0] = 0;
+    if (!(c->arena_guard | c->arena_fill)) {
+        c->guards.clear();
+        c->arena_layout[0] = 0;
+        return 0;
+    }
+    const long long key[9] = {2, B, H, W, 0, (long long)floats, (long long)c->arena_guard, c->arena_fill, (long long)(uintptr_t)c->arena};
+    if (!memcmp(key, c->arena_layout, sizeof key)) return 0;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(c->arena_fill ? hipMemsetD32((hipDeviceptr_t)c->arena, (int)kGuardWord, c->arena_floats) : hipMemset(c->arena, 0, c->arena_floats * sizeof(float)));
+    HIPCHK(hipDeviceSynchronize());
+    memcpy(c->arena_layout, key, sizeof key);
+    c->guards.clear();
+    c->graph_bufs = std::move(bufs);
+    const std::vector<GraphBuf> &gb = c->graph_bufs;
+    if (!gb.empty()) c->guards.push_back({0, (size_t)c->arena_guard, 0, true, gb[0].name.c_str()});
+    for (size_t i = 0; i < gb.size(); ++i) c->guards.push_back({gb[i].end, gb[i].next - gb[i].end, (int)i, false, gb[i].name.c_str()});
     return 0;
 }
 int b2f::check_shape(int B, int H, int W)
@@ -1470,12 +1487,18 @@ int b2f_forward(b2f_ctx *c, const float *x, int B, int H, int W, float **outs, i
         P = make_plan((size_t)c->arena_guard, B, H, W, true, c->past_flow);
         CHK(ensure_workspace(c, P));
     }
+    // option arena_guard (tests): every tensor of the table is a guarded device buffer that starts as kGuardWord, checked below
+    const bool guarded = c->arena_guard > 0;
+    static const char *const kSlot[2][5] = {{"ufs", "occs", "iw1", "iw3", ""}, {"ufs", "ubfs", "occs", "iw1", "iw3"}};
+    std::vector<std::string> gname(guarded ? n_outs : 0);
+    std::unique_ptr<DevBuf[]> gbuf(guarded ? new DevBuf[n_outs] : nullptr);
     std::vector<float *> dev(n_outs, nullptr);
     std::vector<size_t> cnt(n_outs, 0);
     float *d_in = nullptr;
     int rc = 0;
     auto cleanup = [&]() {
-        for (float *p : dev) if (p) (void)hipFree(p);
+        if (!guarded)
+            for (float *p : dev) if (p) (void)hipFree(p);
         if (d_in) (void)hipFree(d_in);
     };
     Outs O;
@@ -1485,7 +1508,11 @@ int b2f_forward(b2f_ctx *c, const float *x, int B, int H, int W, float **outs, i
         for (int j = 0; j < per; ++j) {
             const int ch = (j >= per - 2) ? 3 : 2;
             cnt[no] = px * ch;
-            if (hipMalloc(&dev[no], cnt[no] * sizeof(float)) != hipSuccess) { rc = fail("b2f_forward: out of device memory"); break; }
+            if (guarded) {
+                gname[no] = std::string("b2f_forward output ") + kSlot[c->past_flow ? 1 : 0][j] + "[" + std::to_string(l) + "]";
+                if (gbuf[no].alloc(cnt[no], gname[no].c_str())) { rc = 1; break; }
+                dev[no] = gbuf[no].p;
+            } else if (hipMalloc(&dev[no], cnt[no] * sizeof(float)) != hipSuccess) { rc = fail("b2f_forward: out of device memory"); break; }
             ++no;
         }
         if (rc) break;
@@ -1501,6 +1528,10 @@ int b2f_forward(b2f_ctx *c, const float *x, int B, int H, int W, float **outs, i
     if (!rc && hipMemcpyAsync(d_in, x, nin * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail("b2f_forward: H2D copy failed");
     if (!rc) rc = shipped ? forward_impl(c, c->stream, false, d_in, B2F_IN_NORMALIZED, P, O)
                           : graph_forward(c, c->stream, false, d_in, B2F_IN_NORMALIZED, B, H, W, dev.data());
+    if (!rc && guarded) {
+        if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(std::string("b2f_forward: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n_outs && !rc; ++i) rc = gbuf[i].check();
+    }
     for (int i = 0; i < n_outs && !rc; ++i)
         if (hipMemcpyAsync(outs[i], dev[i], cnt[i] * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail("b2f_forward: D2H copy failed");
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(std::string("b2f_forward: ") + hipGetErrorString(hipGetLastError()));

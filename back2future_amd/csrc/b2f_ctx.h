@@ -298,6 +298,13 @@ struct ArenaGuard {
     const char *name;
 };
 
+// One buffer of the generic executor's own layout of the arena (b2f_graph.hip, option arena_guard), as Plan::Buf describes a plan's: where
+// it ends, where the next one may start at the earliest (end rounded to 64 floats + the guard), and its role and level, e.g. "occ.in[4]".
+struct GraphBuf {
+    size_t end, next;
+    std::string name;
+};
+
 // A device buffer of the kernel test entries (b2f_op_*): kGuardFloats floats of kGuardWord on each side of the n floats handed to the
 // kernel, which start as kGuardWord too, so that an element the kernel does not write shows.  p is 256-byte aligned.  check(), after the
 // stream has been synchronised, fails with the buffer's name, the side and the offset of the first guard word that changed.
@@ -531,6 +538,8 @@ struct b2f_ctx : b2f::KernelOpts {
     b2f::DevWork loss_pyr;        // b2f_table_loss_device / b2f_forward_loss*: the pooled reference images R_1 .. R_{L-1} (test.lua:266-297)
     b2f::DevWork loss_work;       // b2f_forward_loss*: [input | output table | records] of a sub-batch
     std::vector<b2f_stream *> streams;   // open streams (b2f_stream_open); b2f_destroy closes what is left
+    // arena_guard on a non-shipped graph: the generic executor's buffers of the layout in arena_layout; guards[].name points into their names
+    std::vector<b2f::GraphBuf> graph_bufs;
 };
 
 #define HIPCHK(expr)                                                                         \
@@ -605,7 +614,8 @@ ConvSeg cp8_seg(const float *ptr, int C, size_t hw);
 int find_conv_id(const b2f_ctx *c, int kind, int level, int idx);
 int run_conv_layer(b2f_ctx *c, hipStream_t s, bool cap, int conv_id, const ConvSeg *segs, int nimg, int H, int W, int stride, int leaky,
                    float *out);
-int ensure_arena(b2f_ctx *c, size_t floats);
+// the arena for a pass of the generic executor over `floats` floats laid out as `bufs` (empty without arena_guard) for shape B x H x W
+int ensure_arena(b2f_ctx *c, size_t floats, std::vector<GraphBuf> &&bufs, int B, int H, int W);
 // b2f_graph.hip: model:forward for the non-shipped graph shapes; outs = the whole output table (planar device buffers)
 int graph_forward(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in_kind, int B, int H, int W, float *const *outs);
 }  // namespace b2f

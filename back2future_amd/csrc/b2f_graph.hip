@@ -12,6 +12,8 @@
 #include "b2f_ctx.h"
 
 #include <cmath>
+#include <string>
+#include <vector>
 
 namespace b2f {
 namespace {
@@ -160,13 +162,24 @@ __global__ void expf_kernel(const float *x, size_t n, float *y)
 
 inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
 
+// The executor's own layout of the arena: every piece rounded up to 64 floats, one behind the other.  guard (option arena_guard) > 0:
+// that many floats in front of the first piece and behind the rounding of every piece, as make_plan lays a plan out; rec (the dry
+// pass) receives every piece's end, the earliest start of the next one, and its role and level.
 struct Bump {
     float *base;
+    size_t guard = 0;
+    std::vector<GraphBuf> *rec = nullptr;
     size_t off = 0;
-    float *take(size_t n)
+    Bump(float *b, size_t g, std::vector<GraphBuf> *r) : base(b), guard(g), rec(r), off(g) {}
+    float *take(size_t n, const char *role, int level = -1)
     {
         float *p = base ? base + off : nullptr;
+        const size_t o = off;
         off += (n + 63) & ~(size_t)63;
+        if (guard) {
+            off += guard;
+            if (rec) rec->push_back({o + n, off, level < 0 ? std::string(role) : std::string(role) + "[" + std::to_string(level) + "]"});
+        }
         return p;
     }
 };
@@ -174,27 +187,27 @@ struct Bump {
 }  // namespace
 
 // model:forward for a non-shipped graph.  outs: the output table in order (pwc.lua:459-489), planar device buffers, all
-// present.  dry: only size the workspace (returns floats needed in *need).
+// present.  dry: only size the workspace (returns floats needed in *need, and with arena_guard the layout's buffers in *bufs).
 static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in_kind, int B, int H, int W, float *const *outs,
-                     bool dry, size_t *need)
+                     bool dry, size_t *need, std::vector<GraphBuf> *bufs)
 {
     const GraphOpts &g = c->g;
     const int L = g.levels, LST = g.l_st(), nd = g.nd();
     const bool past = g.past_flow;
     const int unit = in_kind == B2F_IN_UNIT;
     c->cur_batch = c->req_batch > 0 ? c->req_batch : B;   // run_conv's kernel rule reads it (as forward_impl sets it for the shipped graph)
-    Bump A{dry ? nullptr : c->arena};
+    Bump A(dry ? nullptr : c->arena, (size_t)c->arena_guard, dry ? bufs : nullptr);
     int hh[8], ww[8];
     for (int l = 1; l <= 7; ++l) { hh[l] = H >> (l - 1); ww[l] = W >> (l - 1); }
 #define GK(...) do { if (!dry) { hipLaunchKernelGGL(__VA_ARGS__); HIPCHK(hipGetLastError()); } } while (0)
 #define GL(expr) do { if (!dry) HIPCHK(expr); } while (0)
 
     // packed frames + image pyramid ds[f][k], f in {1, 3} (pwc.lua:148-158): NHWC8, [frame][B][h][w][8]
-    float *img = A.take((size_t)3 * B * H * W * kImgC);
+    float *img = A.take((size_t)3 * B * H * W * kImgC, "img");
     GL(launch_pack_input((const float *)dev_in, unit, B, H, W, img, s));
     float *ds[8] = {nullptr};
     for (int k = 2; k <= L - LST + 1; ++k) {
-        ds[k] = A.take((size_t)2 * B * (H >> (k - 1)) * (W >> (k - 1)) * kImgC);
+        ds[k] = A.take((size_t)2 * B * (H >> (k - 1)) * (W >> (k - 1)) * kImgC, "ds", k);
         const int hk = H >> (k - 2), wk = W >> (k - 2);
         for (int f = 0; f < 2; ++f) {
             const float *src = (k == 2) ? img + (size_t)(f == 0 ? 0 : 2) * B * H * W * kImgC : ds[k - 1] + (size_t)f * B * hk * wk * kImgC;
@@ -207,14 +220,14 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
     if (!g.siamese) {   // pwc.lua:175,182: nn.Identity / nn.SpatialAveragePooling(2,2,2,2) of the image
         cs[1] = img;
         for (int l = 2; l <= L; ++l) {
-            cs[l] = A.take((size_t)3 * B * hh[l] * ww[l] * kImgC);
+            cs[l] = A.take((size_t)3 * B * hh[l] * ww[l] * kImgC, "cs", l);
             GL(launch_avgpool2_nhwc(cs[l - 1], 3 * B, hh[l - 1], ww[l - 1], kImgC, cs[l], s));
         }
     } else {
         const int l0 = g.feat_first();
-        float *tmp = A.take((size_t)3 * B * hh[l0] * ww[l0] * FS(l0));
+        float *tmp = A.take((size_t)3 * B * hh[l0] * ww[l0] * FS(l0), "tmp");
         for (int l = l0; l <= L; ++l) {
-            cs[l] = A.take((size_t)3 * B * hh[l] * ww[l] * FS(l));
+            cs[l] = A.take((size_t)3 * B * hh[l] * ww[l] * FS(l), "cs", l);
             if (dry) continue;
             if (l == 1) {            // convUnit(3, featMaps[1], 1) on the packed frames (pwc.lua:171-173)
                 const ConvSeg in1 = cp8_seg(img, 3, (size_t)H * W);
@@ -235,7 +248,6 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
     float *ufs[9] = {nullptr}, *ubfs[9] = {nullptr};   // packed B x (2h x 2w) x 2, index = the level they come from
     float *uoccs[9] = {nullptr};            // planar B x 2 x 2h x 2w
     const int per = past ? 5 : 4;
-    auto dec_buf = [&](size_t px, int i) { return A.take(px * kDec[i]); };
 
     for (int l = L; l >= LST; --l) {   // pwc.lua:237
         const int h = hh[l], w = ww[l], C = g.feat(l), chunksC = (C + 7) / 8;
@@ -245,7 +257,7 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
         const float *in_past = g.two_frame ? nullptr : ((l == L) ? frame(l, 1) : ws[1][l]);
         // cost volumes (pwc.lua:246-285)
         const int ndo = g.nd_occ(), chJ = (ndo + 7) / 8, chS = (nd + 7) / 8;
-        float *cvJ = A.take(px * chJ * 8), *cvS = g.sum_cvs && !g.two_frame ? A.take(px * chS * 8) : nullptr;
+        float *cvJ = A.take(px * chJ * 8, "cv.join", l), *cvS = g.sum_cvs && !g.two_frame ? A.take(px * chS * 8, "cv.sum", l) : nullptr;
         GL(hipMemsetAsync(cvJ, 0, px * chJ * 8 * sizeof(float), s));
         if (cvS) GL(hipMemsetAsync(cvS, 0, px * chS * 8 * sizeof(float), s));
         GK(costvol_cp8_kernel, dim3(nblk(px * nd)), dim3(256), 0, s, ref, in_fut, in_past, chunksC, C, B, h, w, g.win, cvJ, chJ, cvS, chS);
@@ -253,7 +265,8 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
         const int ndf = g.nd_flow(), chF = (ndf + 7) / 8;
 
         float *d[6];
-        for (int i = 1; i <= 5; ++i) d[i] = dec_buf(px, i);
+        static const char *const kD[6] = {"", "d1", "d2", "d3", "d4", "d5"};
+        for (int i = 1; i <= 5; ++i) d[i] = A.take(px * kDec[i], kD[i], l);
         auto decoder = [&](int kind, const float *din, int n, float *out2) -> int {
             if (dry) return 0;
             const ConvSeg in0 = cp8_seg(din, n, hw);
@@ -272,7 +285,7 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
         // occlusion decoder + SpatialSoftMax + nearest upsampling (pwc.lua:288-321)
         {
             const int n = g.occ_in(l), chn = (n + 7) / 8;
-            float *din = A.take(px * chn * 8), *logits = A.take(px * 8);
+            float *din = A.take(px * chn * 8, "occ.in", l), *logits = A.take(px * 8, "occ.logits", l);
             GL(hipMemsetAsync(din, 0, px * chn * 8 * sizeof(float), s));
             int off = 0;
             CHK(put(cvJ, 0, chJ, ndo, din, chn, off)); off += ndo;
@@ -284,7 +297,7 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
             }
             CHK(decoder(KIND_OCC, din, n, logits));
             if (g.occ_input) {
-                uoccs[l] = A.take(px * 4 * 2);
+                uoccs[l] = A.take(px * 4 * 2, "uoccs", l);
                 GK(softmax_nearest_kernel, dim3(nblk(px * 4)), dim3(256), 0, s, logits, B, h, w, 2, uoccs[l]);
             }
             const int f = 1 << g.skip;   // skip_occs = skip x nearest x2; pwc_skip = 0: occs[l] itself (pwc.lua:468-470)
@@ -292,7 +305,7 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
             GK(softmax_nearest_kernel, dim3(nblk(px * f * f)), dim3(256), 0, s, logits, B, h, w, f, o);
         }
         // flow decoders (pwc.lua:325-352)
-        float *fs = A.take(px * 8), *bfs = past ? A.take(px * 8) : nullptr;
+        float *fs = A.take(px * 8, "fs", l), *bfs = past ? A.take(px * 8, "bfs", l) : nullptr;
         for (int pass = 0; pass < (past ? 2 : 1); ++pass) {
             const int kind = pass ? KIND_PAST : KIND_FLOW;
             float *o2 = pass ? bfs : fs;
@@ -301,7 +314,7 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
                 CHK(decoder(kind, cv_flow, ndf, o2));
             } else {
                 const int n = g.flow_in(l), chn = (n + 7) / 8;
-                float *din = A.take(px * chn * 8);
+                float *din = A.take(px * chn * 8, pass ? "past.in" : "flow.in", l);
                 GL(hipMemsetAsync(din, 0, px * chn * 8 * sizeof(float), s));
                 CHK(put(cv_flow, 0, chF, ndf, din, chn, 0));
                 CHK(put(ref, 0, chunksC, C, din, chn, ndf));
@@ -318,14 +331,14 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
                 GL(launch_nhwc_to_planar(src, 8, 2, B, h, w, o, s));
                 if (l == LST) continue;
             }
-            float *u = A.take(px * 4 * 2);
+            float *u = A.take(px * 4 * 2, pass ? "ubfs" : "ufs", l);
             GL(launch_upsample_flow2x(src, 8, B, h, w, u, s));
             if (g.rescale_flow) GK(scale_kernel, dim3(nblk(px * 8)), dim3(256), 0, s, u, px * 8, 2.0f);
             (pass ? ubfs : ufs)[l] = u;
             float *cur = u;
             int ch_ = 2 * h, cw_ = 2 * w;
             for (int i = 2; i <= LST - 1; ++i) {
-                float *nx = A.take((size_t)B * ch_ * cw_ * 4 * 2);
+                float *nx = A.take((size_t)B * ch_ * cw_ * 4 * 2, pass ? (i == 2 ? "skip_ubfs.2" : "skip_ubfs.3+") : (i == 2 ? "skip_ufs.2" : "skip_ufs.3+"), l);
                 GL(launch_upsample_flow2x(cur, 2, B, ch_, cw_, nx, s));
                 if (g.rescale_flow) GK(scale_kernel, dim3(nblk((size_t)B * ch_ * cw_ * 8)), dim3(256), 0, s, nx, (size_t)B * ch_ * cw_ * 8, 2.0f);
                 cur = nx; ch_ *= 2; cw_ *= 2;
@@ -340,7 +353,7 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
             if (l > LST && f >= f_i && f <= l_i) {
                 const float k = g.rescale_flow ? (float)((double)g.flownet_factor * (f - 2)) : (float)((double)g.flownet_factor * (f - 2) / std::pow(2.0, l - 2));
                 const int Cn = FS(l - 1);
-                ws[f][l - 1] = A.take(px * 4 * Cn);
+                ws[f][l - 1] = A.take(px * 4 * Cn, f == 1 ? "ws1" : "ws3", l - 1);
                 GK(warp_cp8_kernel, dim3(nblk(px * 4 * Cn)), dim3(256), 0, s, frame(l - 1, f), Cn / 8, ufs[l], k, B, 2 * h, 2 * w, ws[f][l - 1]);
             }
             // image warps iws[f][l] (pwc.lua:410-446)
@@ -364,9 +377,10 @@ static int graph_run(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, in
 int graph_forward(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int in_kind, int B, int H, int W, float *const *outs)
 {
     size_t need = 0;
-    CHK(graph_run(c, s, cap, dev_in, in_kind, B, H, W, outs, true, &need));
-    CHK(ensure_arena(c, need));
-    return graph_run(c, s, cap, dev_in, in_kind, B, H, W, outs, false, nullptr);
+    std::vector<GraphBuf> bufs;
+    CHK(graph_run(c, s, cap, dev_in, in_kind, B, H, W, outs, true, &need, &bufs));
+    CHK(ensure_arena(c, need, std::move(bufs), B, H, W));
+    return graph_run(c, s, cap, dev_in, in_kind, B, H, W, outs, false, nullptr, nullptr);
 }
 
 }  // namespace b2f

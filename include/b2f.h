@@ -928,7 +928,10 @@ B2F_API int b2f_op_expf(b2f_ctx *ctx, const float *x, long long n, float *y);
  * forward pass gets arena_guard floats in front of its first buffer and behind every buffer, and starts as the 32-bit pattern 0x7fc0a5a5
  * (a quiet NaN) instead of zero, as does the device block of a stream opened afterwards.  Setting either frees the workspace and drops
  * the captured graphs.  A kernel may read outside its tensors only if the value cannot reach a result, and may write nowhere outside them:
- * under the two options a result that changes, or a guard word that changes, shows a kernel that does not keep to that.
+ * under the two options a result that changes, or a guard word that changes, shows a kernel that does not keep to that.  A context made
+ * with graph options lays its workspace out buffer by buffer in the same way, each buffer named by role and level ("occ.in[4]"); and with
+ * arena_guard set every tensor of b2f_forward's output table is a device buffer with the pattern on both sides and inside until it is
+ * written, checked before the download: a changed word fails the call, b2f_last_error naming the tensor ("b2f_forward output occs[4]").
  * b2f_arena_check: synchronises, and returns the number of guard words of the last pass's layout that no longer hold what the workspace
  * was filled with (compared on bits); *buffer_index / *offset (either may be NULL): the first one -- the buffer of the layout it belongs to
  * and its offset from that buffer's end (>= 0), or from the first buffer's start (< 0: the guard in front of it); b2f_last_error names the

@@ -13,6 +13,10 @@ of these sizes (80 pixels x 8 floats), so an overrun by such a piece or row land
 access with a stride that steps over it, reaches the next buffer and may go unseen; so does a stray write of the very bits the guard
 holds, and a stray read whose value a select throws away (which the contract allows).
 
+Covered here: the shipped graph's plans -- the full table (with b2f_forward's output tensors as guarded buffers), the pruned pass eager,
+captured and replayed, sequences, streams, a warm context.  The generic executor of the other option sets (graph_run, its own layout of
+the arena with a guard behind every buffer, named by role and level) is held to the same contract in tests/test_gpu_graph_guards.py.
+
 The op-level entries (b2f_op_*) carry the same guards on every device buffer, always on: the shapes of test_gpu_parity.py,
 test_gpu_in_place.py and test_gpu_cv_float64.py are that coverage.  The self-test at the end shows both detectors firing on one word
 overwritten from the host."""
@@ -124,6 +128,20 @@ def test_full_table(which, B, H, Wd, setting):
     assert len(got) == (25 if which == "soft" else 20)
     assert all(np.isfinite(a).all() for a in exp), what
     _assert_bit_equal(got, exp, what)
+
+
+def test_forward_output_table_is_guarded():
+    """With arena_guard set, every tensor of b2f_forward's output table is a guarded device buffer that starts as the NaN pattern and is
+    checked before the download (shipped and generic contexts alike; the generic ones: tests/test_gpu_graph_guards.py): the kernels that
+    store straight into the table -- the flow and occlusion outputs, the image warps -- write every element and nothing else, so the
+    guarded context gives the plain context's bits with no word of the pattern among them."""
+    for which in KINDS:
+        x, flat = _case(which, 1, 192, 320)
+        g, p = _pair(which, flat, (1, 192, 320))
+        got = g.forward(x)
+        _assert_clean(g, "output table %s" % which)
+        assert not any((a.view(np.uint32) == 0x7fc0a5a5).any() for a in got), which
+        _assert_bit_equal(got, p.forward(x), "output table %s" % which)
 
 
 # ---- the pruned graph: eager, capture, replay ----
