@@ -918,7 +918,7 @@ class Model(object):
         return n, i.value, off.value, (_lib.lib().b2f_last_error().decode("utf-8", "replace") if n else "")
 
     def guard_selftest(self, which):
-        """b2f_guard_selftest: overwrite one guard word from the host (0 / 1: the workspace's, 2 / 3: a guarded op-level buffer's)."""
+        """b2f_guard_selftest: overwrite one guard word from the host (0 / 1: the workspace's, 2 / 3: a guarded op-level buffer's, 4 / 5: one of an op-level staging scope's three)."""
         _lib.check(_lib.lib().b2f_guard_selftest(self._h, int(which)))
 
     def profile_reset(self):

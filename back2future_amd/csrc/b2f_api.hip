@@ -1,6 +1,6 @@
 // C-ABI layer of libb2f.so (include/b2f.h): context, weight packing, workspace, the forward
 // pass of models/pwc.lua's graph (the host-buffer boundary around it: b2f_pipeline.hip), hipGraph
-// capture, per-kernel HIP-event profiling, and op-level entry points for parity tests.
+// capture and per-kernel HIP-event profiling.  The op-level entry points of the kernel tests: b2f_ops.hip.
 #include "b2f_ctx.h"
 
 #include <cctype>
@@ -31,42 +31,6 @@ ConvSeg cp8_seg(const float *ptr, int C, size_t hw)
     return sgm;
 }
 
-int DevBuf::alloc(size_t count, const char *what)
-{
-    n = std::max<size_t>(count, 1);
-    name = what;
-    const size_t all = n + 2 * kGuardFloats;
-    HIPCHK(hipMalloc(&raw, all * sizeof(float)));
-    p = raw + kGuardFloats;   // hipMalloc aligns to 256 bytes and the guard is a multiple of that
-    HIPCHK(hipMemsetD32((hipDeviceptr_t)raw, (int)kGuardWord, all));
-    HIPCHK(hipStreamSynchronize(nullptr));   // the fill is asynchronous on the null stream
-    return 0;
-}
-
-int DevBuf::check() const
-{
-    if (!raw) return 0;
-    std::vector<uint32_t> g(2 * kGuardFloats);
-    HIPCHK(hipMemcpy(g.data(), raw, kGuardFloats * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(g.data() + kGuardFloats, p + n, kGuardFloats * sizeof(float), hipMemcpyDeviceToHost));
-    long long first = 0, bad = 0;
-    bool before = false;
-    for (size_t i = 0; i < g.size(); ++i) {
-        if (g[i] == kGuardWord) continue;
-        if (!bad++) { before = i < kGuardFloats; first = before ? (long long)i - (long long)kGuardFloats : (long long)(i - kGuardFloats); }
-    }
-    if (!bad) return 0;
-    char msg[256];
-    snprintf(msg, sizeof msg, "guard of device buffer '%s' (%zu floats) overwritten: %lld words, the first one %s the buffer at offset %+lld from its %s",
-             name, n, bad, before ? "before" : "after", first, before ? "start" : "end");
-    return api_fail(msg);
-}
-
-int check_guards(std::initializer_list<const DevBuf *> bufs)
-{
-    for (const DevBuf *b : bufs) CHK(b->check());
-    return 0;
-}
 }  // namespace b2f
 static int fail(const std::string &m) { return api_fail(m); }
 
@@ -203,7 +167,8 @@ const KernelRow kKernels[K_COUNT] = {
 // The kernel of a layer by its shape alone: stride-1 layers run F(4x4) from B2F_WINO4_MIN_COUT outputs (default 32; 0 disables it; it
 // stores 4 channels at a time), F(2x2) down to B2F_WINO_MIN_COUT (default 16), the direct kernel below; 2 outputs: the VALU kernel,
 // which takes one K segment; the two 16-channel layers of the head have kernels of their own.  Stride 2: the direct kernel.
-ConvKernel base_kernel(int ci, int co, bool stride1, bool two_segments)
+}  // namespace
+ConvKernel b2f::base_kernel(int ci, int co, bool stride1, bool two_segments)
 {
     static const int min4 = getenv("B2F_WINO4_MIN_COUT") ? atoi(getenv("B2F_WINO4_MIN_COUT")) : 32;
     static const int min2 = getenv("B2F_WINO_MIN_COUT") ? atoi(getenv("B2F_WINO_MIN_COUT")) : 16;
@@ -214,6 +179,7 @@ ConvKernel base_kernel(int ci, int co, bool stride1, bool two_segments)
     if (co < min2) return K_DIRECT;
     return (min4 > 0 && co >= min4 && co % 4 == 0) ? K_WINO4 : K_WINO2;
 }
+namespace {
 
 // Does a layer carry kernel k's packing?  Its base kernel's always; the optional ones only while an option reads them (the setter
 // of such an option repacks when that changes, OptRow::repack).
@@ -234,9 +200,11 @@ bool packs(const PackedConv &p, ConvKernel k, bool stride1, const KernelOpts &o)
     }
 }
 
+}  // namespace
+
 // Lays the packings of a layer (base, cout and chunks set) out from float offset *total on.  Every packing starts 16-byte aligned
 // (conv_narrow2 reads its weights as float4, the split ones are read with dwordx4 loads).
-void place_packings(PackedConv &p, bool stride1, const KernelOpts &o, size_t *total)
+void b2f::place_packings(PackedConv &p, bool stride1, const KernelOpts &o, size_t *total)
 {
     for (int k = 0; k < K_COUNT; ++k) {
         if (!packs(p, (ConvKernel)k, stride1, o)) continue;
@@ -249,7 +217,7 @@ void place_packings(PackedConv &p, bool stride1, const KernelOpts &o, size_t *to
 }
 
 // Torch weights Co x Ci x 3 x 3 + bias -> every packing place_packings gave the layer
-void fill_packings(const PackedConv &p, const float *w, const float *b, int ci, const int *cin_map, float *host)
+void b2f::fill_packings(const PackedConv &p, const float *w, const float *b, int ci, const int *cin_map, float *host)
 {
     for (int k = 0; k < K_COUNT; ++k)
         if (p.has((ConvKernel)k))
@@ -258,7 +226,7 @@ void fill_packings(const PackedConv &p, const float *w, const float *b, int ci, 
 
 // The K-order of layer d: sets p.nseg and p.chunks and returns cin_map -- for packed input channel k (segment 0's chunks, then segment 1's)
 // the Torch input channel, or -1 (zero weights: channel padding, and the record slots this decoder does not read).
-std::vector<int> layer_cin_map(const ConvDesc &d, bool shipped, PackedConv &p)
+std::vector<int> b2f::layer_cin_map(const ConvDesc &d, bool shipped, PackedConv &p)
 {
     std::vector<int> m;
     if (d.kind != KIND_FEAT && d.idx == 1 && shipped) {
@@ -292,6 +260,7 @@ std::vector<int> layer_cin_map(const ConvDesc &d, bool shipped, PackedConv &p)
     return m;
 }
 
+namespace {
 int pack_all(b2f_ctx *c, const float *flat)
 {
     const size_t n = c->lay.size();
@@ -314,10 +283,8 @@ int pack_all(b2f_ctx *c, const float *flat)
     const int id_first = find_conv(c, KIND_FEAT, 2, 1);   // Torch 16 x 3 x 3 x 3 -> [tap (c,ky,kx)][cout]
     if (id_first >= 0 && c->lay[(size_t)id_first].ci == 3 && c->lay[(size_t)id_first].co == 16) {   // (absent with pwc_siamese = 0, 16 -> 16 with pwc_skip = 0)
         const ConvDesc &d = c->lay[(size_t)id_first];
-        for (int o = 0; o < 16; ++o) {
-            for (int t = 0; t < 27; ++t) host[c->first_w_off + (size_t)t * 16 + o] = flat[d.w_off + (size_t)o * 27 + t];
-            host[c->first_b_off + o] = flat[d.b_off + o];
-        }
+        pack_first_conv(flat + d.w_off, host.data() + c->first_w_off);
+        for (int o = 0; o < 16; ++o) host[c->first_b_off + o] = flat[d.b_off + o];
     }
     for (size_t i = 0; i < n; ++i)
         fill_packings(c->packed[i], flat + c->lay[i].w_off, flat + c->lay[i].b_off, c->lay[i].ci, maps[i].data(), host.data());
@@ -543,9 +510,11 @@ KernelChoice choose_kernel(const PackedConv &p, const KernelOpts &o, int cur_bat
     return ch;
 }
 
+}  // namespace
+
 // Launches layer p, packed at wpk, on the kernel choose_kernel names: the one path of the forward pass (run_conv) and of b2f_op_conv3x3.
 // The caller has set L's segments (pointers and strides), output (pointer and strides), sizes, stride, nimg and leaky.
-int launch_layer(b2f_ctx *c, hipStream_t s, bool prof, const PackedConv &p, const float *wpk, const KernelOpts &o, int cur_batch, ConvLaunch &L)
+int b2f::launch_layer(b2f_ctx *c, hipStream_t s, bool prof, const PackedConv &p, const float *wpk, const KernelOpts &o, int cur_batch, ConvLaunch &L)
 {
     for (int i = 0; i < p.nseg; ++i) L.seg[i].nchunks = p.chunks[i];
     if (p.nseg == 1) L.seg[1] = L.seg[0], L.seg[1].nchunks = 0;
@@ -587,6 +556,7 @@ int launch_layer(b2f_ctx *c, hipStream_t s, bool prof, const PackedConv &p, cons
     return 0;
 }
 
+namespace {
 // All activations are chunk-planar: [image][C/8][h][w][8].
 int run_conv(b2f_ctx *c, hipStream_t s, bool cap, int conv_id, const ConvSeg *segs, int nimg, int H, int W,
              int stride, int leaky, float *out)
@@ -1869,7 +1839,9 @@ catch (...) { fail("b2f_arena_check: unknown exception"); return -1; }
 // Proof that the two detectors detect.  One guard word is overwritten by a hipMemcpy from the host (no kernel stores out of range):
 // which = 0: offset +3 behind buffer 1 of the arena's current plan; 1: offset -2 in front of its buffer 0 (b2f_arena_check then reports
 // exactly that; needs arena_guard and a pass that has laid the arena out); 2 / 3: offset +2 behind / -1 in front of a guarded device
-// buffer 'selftest' of the op-level entries, whose check then fails this call with the buffer's name.
+// buffer 'selftest' of the op-level entries, whose check then fails this call with the buffer's name; 4 / 5: offset +2 behind buffer 'b' /
+// -1 in front of buffer 'c' of an OpStage that holds 'a' (10 floats, uploaded), 'b' (1000 floats) and 'c' (7 bytes, uploaded): its finish()
+// fails in the same words, though nobody handed it a list of its buffers.
 int b2f_guard_selftest(b2f_ctx *c, int which) try
 {
     if (!c) return fail("b2f_guard_selftest: null context");
@@ -1889,7 +1861,17 @@ int b2f_guard_selftest(b2f_ctx *c, int which) try
         HIPCHK(hipMemcpy(which == 2 ? b.p + b.n + 2 : b.p - 1, &word, sizeof word, hipMemcpyHostToDevice));
         return b.check();
     }
-    return fail("b2f_guard_selftest: which must be 0 .. 3");
+    if (which == 4 || which == 5) {
+        const float a10[10] = {0.f};
+        const unsigned char c7[7] = {0};
+        float *a, *b;
+        unsigned char *cc;
+        OpStage st(c, __func__);
+        CHK(st.in(a10, 10, "a", &a)); CHK(st.out(1000, "b", &b)); CHK(st.in(c7, 7, "c", &cc));
+        HIPCHK(hipMemcpy(which == 4 ? b + 1000 + 2 : (float *)cc - 1, &word, sizeof word, hipMemcpyHostToDevice));
+        return st.finish();
+    }
+    return fail("b2f_guard_selftest: which must be 0 .. 5");
 }
 B2F_CATCH("b2f_guard_selftest")
 
@@ -1916,557 +1898,6 @@ int b2f_arena_plan(int arena_guard, int B, int H, int W, int flags, long long *o
 }
 catch (const std::exception &e) { fail(std::string("b2f_arena_plan: ") + e.what()); return -1; }
 catch (...) { fail("b2f_arena_plan: unknown exception"); return -1; }
-
-// ---- op-level entry points (host pointers; reference module layouts) -----------------------
-// Every device buffer is a DevBuf (b2f_ctx.h): guarded on both sides, kGuardWord inside until something writes it, checked once the
-// stream has been synchronised.
-
-int b2f_op_warp_bhwd(b2f_ctx *c, const float *img, const float *grid, int B, int ih, int iw, int C, int gh,
-                     int gw, float *out) try
-{
-    if (!c || !img || !grid || !out) return fail("b2f_op_warp_bhwd: null argument");
-    HIPCHK(hipSetDevice(c->device));
-    DevBuf di, dg, dout;
-    const size_t ni = (size_t)B * ih * iw * C, ng = (size_t)B * gh * gw * 2, no = (size_t)B * gh * gw * C;
-    CHK(di.alloc(ni, "img")); CHK(dg.alloc(ng, "grid")); CHK(dout.alloc(no, "out"));
-    HIPCHK(hipMemcpy(di.p, img, ni * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dg.p, grid, ng * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_warp_nhwc(di.p, (long)((size_t)ih * iw * C), C, C, ih, iw, dg.p, 1.0f, B, gh, gw, dout.p, C, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&di, &dg, &dout}));
-    HIPCHK(hipMemcpy(out, dout.p, no * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_warp_bhwd")
-
-int b2f_op_image_scale(b2f_ctx *c, const float *src, int C, int Hs, int Ws, int normalize, float *dst, int Hd, int Wd) try
-{
-    if (!c || !src || !dst) return fail("b2f_op_image_scale: null argument");
-    if (C <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return fail("b2f_op_image_scale: bad shape");
-    HIPCHK(hipSetDevice(c->device));
-    DevBuf ds, dt, dd;
-    const size_t ns = (size_t)C * Hs * Ws, nt = (size_t)C * Hs * Wd, nd = (size_t)C * Hd * Wd;
-    CHK(ds.alloc(ns, "src")); CHK(dt.alloc(nt, "row pass")); CHK(dd.alloc(nd, "dst"));
-    HIPCHK(hipMemcpy(ds.p, src, ns * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_image_scale(ds.p, normalize, C, Hs, Ws, dt.p, dd.p, Hd, Wd, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&ds, &dt, &dd}));
-    HIPCHK(hipMemcpy(dst, dd.p, nd * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_image_scale")
-
-int b2f_op_upsample_flow2x(b2f_ctx *c, const float *x, int B, int h, int w, float *y) try
-{
-    if (!c || !x || !y) return fail("b2f_op_upsample_flow2x: null argument");
-    HIPCHK(hipSetDevice(c->device));
-    DevBuf dp, dn, dy;
-    const size_t n = (size_t)B * 2 * h * w;
-    CHK(dp.alloc(n, "x planar")); CHK(dn.alloc(n, "x")); CHK(dy.alloc(4 * n, "y"));
-    HIPCHK(hipMemcpy(dp.p, x, n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_planar_to_nhwc(dp.p, 2, B, h, w, dn.p, 2, c->stream));
-    HIPCHK(launch_upsample_flow2x_planar(dn.p, 2, B, h, w, dy.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dp, &dn, &dy}));
-    HIPCHK(hipMemcpy(y, dy.p, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_upsample_flow2x")
-
-// The shape, stride and option fields of the CorrLaunch of b2f_op_warp_costvol (layout 0: NHWC strides, C a multiple of 8 after padding) and
-// of b2f_op_cv_record (layout 1: the forward's chunk-planar strides, option corr_ablate); b2f_op_cv_variant asks the launcher's rule about the
-// same structure, so what it reports is what those two run.  Pointers and k are left to the caller.
-static CorrLaunch op_corr_launch(const b2f_ctx *c, int layout, int B, int C, int h, int w)
-{
-    const size_t hw = (size_t)h * w;
-    CorrLaunch cl{};
-    cl.img_stride = (long)(hw * C);
-    cl.out_img_stride = (long)(hw * kCvRec);
-    if (layout == 0) {   // NHWC expressed with strides
-        cl.chunk_stride = 8; cl.pix_stride = C;
-        cl.out_chunk_stride = 8; cl.out_pix_stride = kCvRec;
-    } else {
-        cl.chunk_stride = (long)(hw * 8); cl.pix_stride = 8;
-        cl.out_chunk_stride = (long)(hw * 8); cl.out_pix_stride = 8;
-        cl.ablate = c->corr_ablate;
-    }
-    cl.B = B; cl.C = C; cl.h = h; cl.w = w;
-    cl.variant = c->corr_variant;
-    return cl;
-}
-
-int b2f_op_warp_costvol(b2f_ctx *c, const float *ref, const float *nbr_future, const float *nbr_past,
-                        const float *flow, float k, int B, int C, int h, int w, float *out) try
-{
-    if (!c || !ref || !nbr_future || !nbr_past || !out) return fail("b2f_op_warp_costvol: null argument");
-    HIPCHK(hipSetDevice(c->device));
-    const int Cp = (C + 7) / 8 * 8;   // the fused kernel walks channels in chunks of 8; zero channels add 0
-    const size_t hw = (size_t)h * w, nplanar = (size_t)B * C * hw, nn = (size_t)B * hw * Cp;
-    DevBuf dpl, dr, df, dpa, dfl_pl, dfl, dcv;
-    CHK(dpl.alloc(nplanar, "planar staging")); CHK(dr.alloc(nn, "ref")); CHK(df.alloc(nn, "nbr_future")); CHK(dpa.alloc(nn, "nbr_past"));
-    CHK(dcv.alloc((size_t)B * hw * kCvRec, "record"));
-    const float *srcs[3] = {ref, nbr_future, nbr_past};
-    float *dsts[3] = {dr.p, df.p, dpa.p};
-    for (int i = 0; i < 3; ++i) {
-        HIPCHK(hipMemcpyAsync(dpl.p, srcs[i], nplanar * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(launch_planar_to_nhwc(dpl.p, C, B, h, w, dsts[i], Cp, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    if (flow) {
-        CHK(dfl_pl.alloc((size_t)B * 2 * hw, "flow planar")); CHK(dfl.alloc((size_t)B * 2 * hw, "flow"));
-        HIPCHK(hipMemcpy(dfl_pl.p, flow, (size_t)B * 2 * hw * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(launch_planar_to_nhwc(dfl_pl.p, 2, B, h, w, dfl.p, 2, c->stream));
-    }
-    CorrLaunch cl = op_corr_launch(c, 0, B, Cp, h, w);
-    cl.ref = dr.p; cl.nbr_fut = df.p; cl.nbr_past = dpa.p;
-    cl.flow = flow ? dfl.p : nullptr;
-    cl.flow_b = nullptr;
-    cl.k = k; cl.out = dcv.p;
-    HIPCHK(launch_warp_costvol(cl, c->stream));
-    std::vector<float> rec((size_t)B * hw * kCvRec);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dpl, &dr, &df, &dpa, &dfl_pl, &dfl, &dcv}));
-    HIPCHK(hipMemcpy(rec.data(), dcv.p, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
-    // record slots -> the reference's JoinTable order {fwd 81, bwd 81}; the kernel divided by Cp,
-    // CostVolMulti.lua:100 divides by N = C
-    const float fix = (Cp != C) ? (float)Cp / (float)C : 1.f;
-    for (int b = 0; b < B; ++b)
-        for (int d = 0; d < 2; ++d)
-            for (int ch = 0; ch < 81; ++ch) {
-                const int slot = cv_slot(d, ch);
-                float *dst = out + ((size_t)b * kND + d * 81 + ch) * hw;
-                const float *src = rec.data() + (size_t)b * hw * kCvRec + slot;
-                for (size_t i = 0; i < hw; ++i) dst[i] = src[i * kCvRec] * fix;
-            }
-    return 0;
-}
-B2F_CATCH("b2f_op_warp_costvol")
-
-int b2f_op_costvol(b2f_ctx *c, const float *ref, const float *frm, int B, int C, int h, int w, int win, int fwd,
-                   float *out) try
-{
-    if (!c || !ref || !frm || !out) return fail("b2f_op_costvol: null argument");
-    if (win < 1 || win % 2 == 0) return fail("b2f_op_costvol: win must be odd");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)h * w;
-    if (win == kWin && C % 8 == 0) {
-        // the shipped 9x9 window goes through the fused kernel (no warp): one half of its record
-        std::vector<float> both((size_t)B * kND * hw);
-        CHK(b2f_op_warp_costvol(c, ref, frm, frm, nullptr, 0.f, B, C, h, w, both.data()));
-        for (int b = 0; b < B; ++b)
-            memcpy(out + (size_t)b * 81 * hw, both.data() + ((size_t)b * kND + (fwd ? 0 : 81)) * hw, 81 * hw * sizeof(float));
-        return 0;
-    }
-    DevBuf dpl, dr, df, dcv, dout;
-    const size_t nin = (size_t)B * C * hw, nout = (size_t)B * win * win * hw;
-    CHK(dpl.alloc(nin, "planar staging")); CHK(dr.alloc(nin, "ref")); CHK(df.alloc(nin, "frm")); CHK(dcv.alloc(nout, "cost volume")); CHK(dout.alloc(nout, "out"));
-    HIPCHK(hipMemcpy(dpl.p, ref, nin * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_planar_to_nhwc(dpl.p, C, B, h, w, dr.p, C, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(dpl.p, frm, nin * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_planar_to_nhwc(dpl.p, C, B, h, w, df.p, C, c->stream));
-    HIPCHK(launch_costvol_generic(dr.p, df.p, B, C, h, w, win, fwd, dcv.p, c->stream));
-    HIPCHK(launch_nhwc_to_planar(dcv.p, win * win, win * win, B, h, w, dout.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dpl, &dr, &df, &dcv, &dout}));
-    HIPCHK(hipMemcpy(out, dout.p, nout * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_costvol")
-
-int b2f_op_conv3x3(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, const float *wt, const float *bias,
-                   int Co, int stride, int leaky, float *y) try
-{
-    if (!c || !x || !wt || !bias || !y) return fail("b2f_op_conv3x3: null argument");
-    if (stride != 1 && stride != 2) return fail("b2f_op_conv3x3: stride must be 1 or 2");
-    HIPCHK(hipSetDevice(c->device));
-    // a one-layer model: packed as pack_all packs a layer, launched as run_conv launches it, on NHWC strides
-    PackedConv p;
-    p.cout = Co;
-    p.chunks[0] = (Ci + kCK - 1) / kCK;
-    p.base = base_kernel(Ci, Co, stride == 1, false);
-    const int Cp = p.chunks[0] * kCK, Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-    // The kernel tests address a layer's kernel at any map size, so the entry leaves the F(4x4) -> F(2x2) fallback of small maps out; with
-    // option op_wino_split = 1 (tests) layers of more than 32 outputs take it at every size, one block per 32-output N tile.
-    KernelOpts o = *c;
-    o.adaptive_kernels = 0;
-    o.wino4_min_pixels = o.wino_split_pixels = (c->op_wino_split && Co > 32) ? 0x7fffffff : 0;
-    size_t nw = 0;
-    place_packings(p, stride == 1, o, &nw);
-    std::vector<float> wpk(nw, 0.f);
-    fill_packings(p, wt, bias, Ci, nullptr, wpk.data());
-    DevBuf dpl, dx, dw, dy, dyp;
-    const size_t nx = (size_t)B * Ci * H * W, nxp = (size_t)B * H * W * Cp, ny = (size_t)B * Co * Ho * Wo;
-    CHK(dpl.alloc(nx, "x planar")); CHK(dx.alloc(nxp, "x")); CHK(dw.alloc(nw, "weights")); CHK(dy.alloc(ny, "y")); CHK(dyp.alloc(ny, "y planar"));
-    HIPCHK(hipMemcpy(dpl.p, x, nx * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw.p, wpk.data(), nw * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_planar_to_nhwc(dpl.p, Ci, B, H, W, dx.p, Cp, c->stream));
-    ConvLaunch L{};
-    L.seg[0] = {dx.p, (long)((size_t)H * W * Cp), 8, Cp, 0};
-    L.out = dy.p;
-    L.out_img_stride = (long)((size_t)Ho * Wo * Co); L.out_chunk_stride = 8; L.out_pix_stride = Co;
-    L.H = H; L.W = W; L.stride = stride; L.nimg = B; L.leaky = leaky;
-    CHK(launch_layer(c, c->stream, true, p, dw.p, o, 0, L));   // with option profile: the row names the kernel that ran (tests read the tag)
-    HIPCHK(launch_nhwc_to_planar(dy.p, Co, Co, B, Ho, Wo, dyp.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dpl, &dx, &dw, &dy, &dyp}));
-    HIPCHK(hipMemcpy(y, dyp.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_conv3x3")
-
-// Conv (kind, level, idx) of the context's own packed table, launched exactly as the forward pass launches it: through run_conv, weights from
-// wpk_dev, the kernel by choose_kernel under the context's options with cur_batch = nimg, chunk-planar buffers, profile rows as in a forward.
-// x: nimg x Ci x H x W planar in the layer's Torch input order -- for a first decoder layer {cv 162, cs[ref] C_l, flow 2} (pwc.lua:308,334,337) --
-// scattered here into the feature segment and the cost-volume record (cv_slot, and the flow at the slots of the decoder's kind, as pack_all maps
-// them).  Every packed input channel that the layer's cin_map marks -1 -- the record slots this decoder does not read: the other decoder's
-// flow, slots 166 / 167, all six of level 7 -- is filled with the non-zero finite value 1 + op_hole_fill + slot / 256 (option op_hole_fill,
-// default 0): the layer's weights there are zero, so the result must not depend on them.  y: nimg x Co x Ho x Wo planar.
-// The shipped graph only; feat2.conv1 is launch_conv_first, not run_conv, and is refused.
-int b2f_op_layer(b2f_ctx *c, int kind, int level, int idx, int nimg, int H, int W, const float *x, float *y) try
-{
-    if (!c || !x || !y) return fail("b2f_op_layer: null argument");
-    if (!c->g.shipped()) return fail("b2f_op_layer: only the shipped graph (models/pwc.lua with the options of opts.lua) is covered");
-    if (nimg < 1 || H < 1 || W < 1) return fail("b2f_op_layer: bad size");
-    if (kind == KIND_FEAT && level == 2 && idx == 1) return fail("b2f_op_layer: feat2.conv1 runs in launch_conv_first, not in run_conv");
-    const int id = find_conv(c, kind, level, idx);
-    if (id < 0) return fail("b2f_op_layer: no conv (kind " + std::to_string(kind) + ", level " + std::to_string(level) + ", idx " + std::to_string(idx) + ") in this model");
-    if (!c->wpk_dev) return fail("b2f_op_layer: no weights loaded");
-    HIPCHK(hipSetDevice(c->device));
-    const ConvDesc &d = c->lay[(size_t)id];
-    const PackedConv &p = c->packed[(size_t)id];
-    PackedConv q;   // the layer's K order, as pack_all derived it: only nseg and chunks are set, cout and base are not
-    const std::vector<int> m = layer_cin_map(d, true, q);
-    if (q.nseg != p.nseg || q.chunks[0] != p.chunks[0] || (q.nseg == 2 && q.chunks[1] != p.chunks[1])) return fail("b2f_op_layer: the layer's K order is not the packed table's");
-    const int stride = (kind == KIND_FEAT && idx == 1) ? 2 : 1, leaky = (kind == KIND_FEAT || idx < 6) ? 1 : 0;
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1, Cop = (d.co + 7) / 8 * 8;
-    const size_t hw = (size_t)H * W, hwo = (size_t)Ho * Wo;
-    // host scatter: segment s is chunk-planar [image][chunk][H][W][8]
-    std::vector<float> host[2];
-    DevBuf dseg[2], dy;
-    ConvSeg segs[2];
-    for (int s = 0, k0 = 0; s < p.nseg; k0 += p.chunks[s] * kCK, ++s) {
-        const int Cs = p.chunks[s] * kCK;
-        host[s].resize((size_t)nimg * Cs * hw);
-        for (int n = 0; n < nimg; ++n)
-            for (int k = 0; k < Cs; ++k) {
-                const int ci = m[(size_t)(k0 + k)];
-                const float fill = 1.0f + (float)c->op_hole_fill + (float)k / 256.0f;
-                const float *src = ci >= 0 ? x + ((size_t)n * d.ci + ci) * hw : nullptr;
-                float *dst = host[s].data() + ((size_t)n * Cs + (size_t)(k / 8) * 8) * hw + (k & 7);
-                for (size_t i = 0; i < hw; ++i) dst[i * 8] = src ? src[i] : fill;
-            }
-        // (the arena promises nothing about what lies behind a buffer: here it is the guard's kGuardWord)
-        CHK(dseg[s].alloc(host[s].size(), s == 0 ? "segment 0" : "segment 1"));
-        HIPCHK(hipMemcpy(dseg[s].p, host[s].data(), host[s].size() * sizeof(float), hipMemcpyHostToDevice));
-        segs[s] = cp8_seg(dseg[s].p, Cs, hw);
-    }
-    if (p.nseg == 1) segs[1] = segs[0];
-    const size_t ny = (size_t)nimg * Cop * hwo;
-    CHK(dy.alloc(ny, "y"));
-    HIPCHK(hipDeviceSynchronize());   // the copies ran on the null stream, the layer runs on the context's
-    const int batch_before = c->cur_batch;   // run_conv chooses the kernel for a request of cur_batch triplets: nimg for this launch only
-    c->cur_batch = nimg;
-    const int rc = run_conv(c, c->stream, false, id, segs, nimg, H, W, stride, leaky, dy.p);
-    c->cur_batch = batch_before;
-    CHK(rc);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dseg[0], &dseg[1], &dy}));
-    std::vector<float> out(ny);
-    HIPCHK(hipMemcpy(out.data(), dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    for (int n = 0; n < nimg; ++n)
-        for (int o = 0; o < d.co; ++o) {
-            const float *src = out.data() + ((size_t)n * Cop + (size_t)(o / 8) * 8) * hwo + (o & 7);
-            float *dst = y + ((size_t)n * d.co + o) * hwo;
-            for (size_t i = 0; i < hwo; ++i) dst[i] = src[i * 8];
-        }
-    return 0;
-}
-B2F_CATCH("b2f_op_layer")
-
-// launch_warp_costvol with the strides of the forward pass: the three maps (B x C x h x w planar here, C a multiple of 8) and the record
-// chunk-planar, flow / flow_b (B x 2 x h x w planar here, or NULL) as B x h x w x 2, the context's corr_variant.  rec: the whole record,
-// B x 168 x h x w planar in slot order (b2f_internal.h: fwd 0..79 | bwd 0..79 | fwd80 bwd80 u v ub vb 0 0).  The record buffer starts out as NaN
-// (kGuardWord, like every DevBuf), so a slot the kernel does not write shows.
-int b2f_op_cv_record(b2f_ctx *c, const float *ref, const float *nbr_future, const float *nbr_past, const float *flow, const float *flow_b,
-                     float k, int B, int C, int h, int w, float *rec) try
-{
-    if (!c || !ref || !nbr_future || !nbr_past || !rec) return fail("b2f_op_cv_record: null argument");
-    if (B < 1 || C < 8 || C % 8 || h < 1 || w < 1) return fail("b2f_op_cv_record: bad shape (C must be a multiple of 8)");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)h * w, nmap = (size_t)B * C * hw, nrec = (size_t)B * kCvRec * hw, nfl = (size_t)B * 2 * hw;
-    DevBuf dmap[3], dfl[2], drec;
-    const float *maps[3] = {ref, nbr_future, nbr_past}, *flows[2] = {flow, flow_b};
-    std::vector<float> host(std::max(nmap, nrec));
-    for (int i = 0; i < 3; ++i) {
-        for (int b = 0; b < B; ++b)
-            for (int ch = 0; ch < C; ++ch) {
-                const float *src = maps[i] + ((size_t)b * C + ch) * hw;
-                float *dst = host.data() + ((size_t)b * C + (size_t)(ch / 8) * 8) * hw + (ch & 7);
-                for (size_t j = 0; j < hw; ++j) dst[j * 8] = src[j];
-            }
-        CHK(dmap[i].alloc(nmap, i == 0 ? "ref" : i == 1 ? "nbr_future" : "nbr_past"));
-        HIPCHK(hipMemcpy(dmap[i].p, host.data(), nmap * sizeof(float), hipMemcpyHostToDevice));
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (!flows[i]) continue;
-        for (int b = 0; b < B; ++b)
-            for (int ch = 0; ch < 2; ++ch)
-                for (size_t j = 0; j < hw; ++j) host[((size_t)b * hw + j) * 2 + ch] = flows[i][((size_t)b * 2 + ch) * hw + j];
-        CHK(dfl[i].alloc(nfl, i == 0 ? "flow" : "flow_b"));
-        HIPCHK(hipMemcpy(dfl[i].p, host.data(), nfl * sizeof(float), hipMemcpyHostToDevice));
-    }
-    CHK(drec.alloc(nrec + 64, "record"));   // the slack the arena gives the record (make_plan); the guard lies behind it, as in the arena
-    HIPCHK(hipDeviceSynchronize());
-    CorrLaunch cl = op_corr_launch(c, 1, B, C, h, w);
-    cl.ref = dmap[0].p; cl.nbr_fut = dmap[1].p; cl.nbr_past = dmap[2].p;
-    cl.flow = dfl[0].p; cl.flow_b = dfl[1].p;
-    cl.k = k; cl.out = drec.p;
-    HIPCHK(launch_warp_costvol(cl, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dmap[0], &dmap[1], &dmap[2], &dfl[0], &dfl[1], &drec}));
-    HIPCHK(hipMemcpy(host.data(), drec.p, nrec * sizeof(float), hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b)
-        for (int slot = 0; slot < kCvRec; ++slot) {
-            const float *src = host.data() + ((size_t)b * kCvRec + (size_t)(slot / 8) * 8) * hw + (slot & 7);
-            float *dst = rec + ((size_t)b * kCvRec + slot) * hw;
-            for (size_t j = 0; j < hw; ++j) dst[j] = src[j * 8];
-        }
-    return 0;
-}
-B2F_CATCH("b2f_op_cv_record")
-
-// The variant launch_warp_costvol would run for a B x C x h x w call under the context's options: choose_corr_variant on the CorrLaunch that
-// b2f_op_warp_costvol (layout 0, C padded to a multiple of 8) or b2f_op_cv_record (layout 1) fills through op_corr_launch, no buffers.
-int b2f_op_cv_variant(b2f_ctx *c, int B, int C, int h, int w, int layout) try
-{
-    if (!c) { fail("b2f_op_cv_variant: null argument"); return -1; }
-    if (layout != 0 && layout != 1) { fail("b2f_op_cv_variant: layout must be 0 (b2f_op_warp_costvol) or 1 (b2f_op_cv_record)"); return -1; }
-    if (B < 1 || C < 1 || h < 1 || w < 1 || (layout == 1 && C % 8)) { fail("b2f_op_cv_variant: bad shape (layout 1: C must be a multiple of 8)"); return -1; }
-    if (hipSetDevice(c->device) != hipSuccess) { fail("b2f_op_cv_variant: hipSetDevice failed"); return -1; }
-    const CorrLaunch cl = op_corr_launch(c, layout, B, layout == 0 ? (C + 7) / 8 * 8 : C, h, w);
-    return choose_corr_variant(cl);
-}
-catch (const std::exception &e) { fail(std::string("b2f_op_cv_variant: ") + e.what()); return -1; }
-catch (...) { fail("b2f_op_cv_variant: unknown exception"); return -1; }
-
-int b2f_op_conv_head16(b2f_ctx *c, const float *x, int B, int H, int W, const float *w1, const float *b1, const float *w2,
-                       const float *b2, float *y) try
-{
-    if (!c || !x || !w1 || !b1 || !w2 || !b2 || !y) return fail("b2f_op_conv_head16: null argument");
-    if (B < 1 || H < 1 || W < 1) return fail("b2f_op_conv_head16: bad size");
-    HIPCHK(hipSetDevice(c->device));
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    std::vector<float> p1(c16_wpk_floats()), pb1(32), p2(c16s2_wpk_floats()), pb2(32);
-    c16_pack_weights(w1, b1, 16, nullptr, p1.data(), pb1.data());
-    c16s2_pack_weights(w2, b2, 16, nullptr, p2.data(), pb2.data());
-    DevBuf dpl, dx, dw1, db1, dw2, db2, dy, dyp;
-    const size_t nx = (size_t)B * 16 * H * W, ny = (size_t)B * 32 * Ho * Wo;
-    CHK(dpl.alloc(nx, "x planar")); CHK(dx.alloc(nx, "x")); CHK(dw1.alloc(p1.size(), "w1")); CHK(db1.alloc(32, "b1")); CHK(dw2.alloc(p2.size(), "w2")); CHK(db2.alloc(32, "b2"));
-    CHK(dy.alloc(ny, "y")); CHK(dyp.alloc(ny, "y planar"));
-    HIPCHK(hipMemcpy(dpl.p, x, nx * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw1.p, p1.data(), p1.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db1.p, pb1.data(), 32 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw2.p, p2.data(), p2.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db2.p, pb2.data(), 32 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_planar_to_nhwc(dpl.p, 16, B, H, W, dx.p, 16, c->stream));
-    HeadLaunch hl;
-    hl.in = dx.p; hl.in_img_stride = (long)((size_t)H * W * 16); hl.in_chunk_stride = 8; hl.in_pix_stride = 16;
-    hl.H1 = H; hl.W1 = W;
-    hl.w1 = dw1.p; hl.b1 = db1.p; hl.w2 = dw2.p; hl.b2 = db2.p;
-    hl.out = dy.p; hl.out_img_stride = (long)((size_t)Ho * Wo * 32); hl.out_chunk_stride = 8; hl.out_pix_stride = 32;
-    hl.Ho = Ho; hl.Wo = Wo; hl.nimg = B;
-    if (!head16_supported(hl)) return fail("b2f_op_conv_head16: unsupported shape");
-    HIPCHK(launch_conv_head16(hl, c->stream));
-    HIPCHK(launch_nhwc_to_planar(dy.p, 32, 32, B, Ho, Wo, dyp.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dpl, &dx, &dw1, &db1, &dw2, &db2, &dy, &dyp}));
-    HIPCHK(hipMemcpy(y, dyp.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_conv_head16")
-
-// The first pyramid conv as the forward launches it (launch_conv_first, pwc.lua:59: conv(3, 16, s2) + LeakyReLU on each of the three
-// frames, after ColorNormalize when normalize != 0).  x: B x 9 x H x W planar, frame f in channels 3 f .. 3 f + 2, H and W even (the
-// kernel computes H / 2 x W / 2 outputs); wt: 16 x 3 x 3 x 3, bias: 16; y: 3 B x 16 x H/2 x W/2 planar, image f * B + b.
-int b2f_op_conv_first(b2f_ctx *c, const float *x, int B, int H, int W, int normalize, const float *wt, const float *bias, float *y) try
-{
-    if (!c || !x || !wt || !bias || !y) return fail("b2f_op_conv_first: null argument");
-    if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail("b2f_op_conv_first: H and W must be even and at least 2");
-    HIPCHK(hipSetDevice(c->device));
-    const int Ho = H / 2, Wo = W / 2;
-    const size_t hwo = (size_t)Ho * Wo, nx = (size_t)B * 9 * H * W, ny = (size_t)3 * B * 16 * hwo;
-    std::vector<float> wp(27 * 16), out(ny);
-    for (int o = 0; o < 16; ++o)
-        for (int t = 0; t < 27; ++t) wp[(size_t)t * 16 + o] = wt[(size_t)o * 27 + t];   // as pack_all packs it
-    DevBuf dx, dw, db, dy;
-    CHK(dx.alloc(nx, "x")); CHK(dw.alloc(wp.size(), "weights")); CHK(db.alloc(16, "bias")); CHK(dy.alloc(ny, "y"));
-    HIPCHK(hipMemcpy(dx.p, x, nx * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw.p, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db.p, bias, 16 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_conv_first(dx.p, normalize ? 1 : 0, B, H, W, dw.p, db.p, dy.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dx, &dw, &db, &dy}));
-    HIPCHK(hipMemcpy(out.data(), dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t img = 0; img < (size_t)3 * B; ++img)          // chunk-planar [img][2][hw][8] -> planar
-        for (int o = 0; o < 16; ++o)
-            for (size_t q = 0; q < hwo; ++q) y[(img * 16 + o) * hwo + q] = out[((img * 2 + (o >> 3)) * hwo + q) * 8 + (o & 7)];
-    return 0;
-}
-B2F_CATCH("b2f_op_conv_first")
-
-}  // extern "C"
-
-// ---- the forward's small kernels (b2f_glue.hip, b2f_seq.hip), one entry per launcher on the caller's own strides: the host hands over the
-// records as the forward lays them out (e.g. 8-float flow records whose slots 2..7 hold NaN), nothing is repacked on the way in.
-// tests/test_gpu_glue_float64.py
-namespace {
-int op_upload(DevBuf &d, const void *host, size_t bytes, const char *what)
-{
-    CHK(d.alloc((bytes + 3) / 4, what));
-    HIPCHK(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));
-    return 0;
-}
-inline int op_upload(DevBuf &d, const float *host, size_t n, const char *what) { return op_upload(d, (const void *)host, n * sizeof(float), what); }
-inline bool small_dims(long long a, long long b, long long c) { return a >= 1 && b >= 1 && c >= 1 && a * b * c <= (1LL << 26); }
-}  // namespace
-
-extern "C" {
-
-int b2f_op_upsample_flow2x_ex(b2f_ctx *c, const float *x, int ps, int B, int h, int w, int planar, float *y) try
-{
-    if (!c || !x || !y) return fail("b2f_op_upsample_flow2x_ex: null argument");
-    if (!small_dims(B, h, w) || ps < 2 || (ps & 1) || ps > 64) return fail("b2f_op_upsample_flow2x_ex: bad shape (B, h, w >= 1, ps even in 2..64)");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t nx = (size_t)B * h * w * ps, ny = (size_t)B * 8 * h * w;
-    DevBuf dx, dy;
-    CHK(op_upload(dx, x, nx, "x")); CHK(dy.alloc(ny, "y"));
-    if (planar) HIPCHK(launch_upsample_flow2x_planar(dx.p, ps, B, h, w, dy.p, c->stream));
-    else HIPCHK(launch_upsample_flow2x(dx.p, ps, B, h, w, dy.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dx, &dy}));
-    HIPCHK(hipMemcpy(y, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_upsample_flow2x_ex")
-
-int b2f_op_softmax_nearest4(b2f_ctx *c, const float *logits, int ps, int B, int h, int w, float *out) try
-{
-    if (!c || !logits || !out) return fail("b2f_op_softmax_nearest4: null argument");
-    if (!small_dims(B, h, w) || ps < 2 || (ps & 1) || ps > 64) return fail("b2f_op_softmax_nearest4: bad shape (B, h, w >= 1, ps even in 2..64)");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t nx = (size_t)B * h * w * ps, ny = (size_t)B * 32 * h * w;
-    DevBuf dx, dy;
-    CHK(op_upload(dx, logits, nx, "logits")); CHK(dy.alloc(ny, "out"));
-    HIPCHK(launch_softmax_nearest4_planar(dx.p, ps, B, h, w, dy.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dx, &dy}));
-    HIPCHK(hipMemcpy(out, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_softmax_nearest4")
-
-int b2f_op_avgpool2(b2f_ctx *c, const float *x, int nimg, int H, int W, int C, float *y) try
-{
-    if (!c || !x || !y) return fail("b2f_op_avgpool2: null argument");
-    if (!small_dims(nimg, H, W) || H < 2 || W < 2 || C < 4 || (C & 3) || C > 1024) return fail("b2f_op_avgpool2: bad shape (H, W >= 2, C a multiple of 4)");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t nx = (size_t)nimg * H * W * C, ny = (size_t)nimg * (H / 2) * (W / 2) * C;
-    DevBuf dx, dy;
-    CHK(op_upload(dx, x, nx, "x")); CHK(dy.alloc(ny, "y"));
-    HIPCHK(launch_avgpool2_nhwc(dx.p, nimg, H, W, C, dy.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dx, &dy}));
-    HIPCHK(hipMemcpy(y, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_avgpool2")
-
-int b2f_op_pack_input(b2f_ctx *c, const float *x, int normalize, int B, int H, int W, float *img) try
-{
-    if (!c || !x || !img) return fail("b2f_op_pack_input: null argument");
-    if (!small_dims(B, H, W)) return fail("b2f_op_pack_input: bad shape");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t nx = (size_t)B * 9 * H * W, ny = (size_t)3 * B * H * W * kImgC;
-    DevBuf dx, dy;
-    CHK(op_upload(dx, x, nx, "x")); CHK(dy.alloc(ny, "img"));
-    HIPCHK(launch_pack_input(dx.p, normalize ? 1 : 0, B, H, W, dy.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dx, &dy}));
-    HIPCHK(hipMemcpy(img, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_pack_input")
-
-int b2f_op_warp_image(b2f_ctx *c, int which, const void *in, int in_kind, int frame, const float *flow, float k, int B, int H, int W,
-                      float *out) try
-{
-    if (!c || !in || !flow || !out) return fail("b2f_op_warp_image: null argument");
-    if (!small_dims(B, H, W)) return fail("b2f_op_warp_image: bad shape");
-    if (which < 0 || which > 2) return fail("b2f_op_warp_image: which must be 0 (warp_image_planar), 1 (warp_input_planar) or 2 (warp_input_seq)");
-    if (which == 1 && (frame < 0 || frame > 2 || (in_kind != B2F_IN_NORMALIZED && in_kind != B2F_IN_UNIT)))
-        return fail("b2f_op_warp_image: warp_input_planar takes frame 0..2 and float samples");
-    if (which == 2 && in_kind != B2F_IN_NORMALIZED && in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail("b2f_op_warp_image: bad in_kind");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)H * W, samples = which == 0 ? (size_t)B * hw * kImgC : (which == 1 ? (size_t)B * 9 * hw : (size_t)B * 3 * hw);
-    const size_t bytes = samples * ((which == 2 && in_kind == B2F_IN_U8) ? 1 : sizeof(float)), no = (size_t)B * 3 * hw;
-    DevBuf di, df, dout;
-    CHK(op_upload(di, in, bytes, "in")); CHK(op_upload(df, flow, (size_t)B * 2 * hw, "flow")); CHK(dout.alloc(no, "out"));
-    if (which == 0) HIPCHK(launch_warp_image_planar(di.p, df.p, k, B, H, W, dout.p, c->stream));
-    else if (which == 1) HIPCHK(launch_warp_input_planar(di.p, in_kind == B2F_IN_UNIT ? 1 : 0, frame, df.p, k, B, H, W, dout.p, c->stream));
-    else HIPCHK(launch_warp_input_seq(di.p, in_kind, df.p, k, B, H, W, dout.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&di, &df, &dout}));
-    HIPCHK(hipMemcpy(out, dout.p, no * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_warp_image")
-
-int b2f_op_conv_first_seq(b2f_ctx *c, const void *x, int in_kind, int T, int H, int W, const float *wt, const float *bias, float *y) try
-{
-    if (!c || !x || !wt || !bias || !y) return fail("b2f_op_conv_first_seq: null argument");
-    if (!small_dims(T, H, W) || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail("b2f_op_conv_first_seq: H and W must be even and at least 2");
-    if (in_kind != B2F_IN_NORMALIZED && in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail("b2f_op_conv_first_seq: bad in_kind");
-    HIPCHK(hipSetDevice(c->device));
-    const int Ho = H / 2, Wo = W / 2;
-    const size_t hwo = (size_t)Ho * Wo, nx = (size_t)T * 3 * H * W, ny = (size_t)T * 16 * hwo;
-    std::vector<float> wp(27 * 16), out(ny);
-    for (int o = 0; o < 16; ++o)
-        for (int t = 0; t < 27; ++t) wp[(size_t)t * 16 + o] = wt[(size_t)o * 27 + t];   // as pack_all packs it
-    DevBuf dx, dw, db, dy;
-    CHK(op_upload(dx, x, nx * (in_kind == B2F_IN_U8 ? 1 : sizeof(float)), "x")); CHK(op_upload(dw, wp.data(), wp.size(), "weights"));
-    CHK(op_upload(db, bias, 16, "bias")); CHK(dy.alloc(ny, "y"));
-    HIPCHK(launch_conv_first_seq(dx.p, in_kind, T, H, W, dw.p, db.p, dy.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dx, &dw, &db, &dy}));
-    HIPCHK(hipMemcpy(out.data(), dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t img = 0; img < (size_t)T; ++img)          // chunk-planar [img][2][hw][8] -> planar
-        for (int o = 0; o < 16; ++o)
-            for (size_t q = 0; q < hwo; ++q) y[(img * 16 + o) * hwo + q] = out[((img * 2 + (o >> 3)) * hwo + q) * 8 + (o & 7)];
-    return 0;
-}
-B2F_CATCH("b2f_op_conv_first_seq")
-
-int b2f_op_layout(b2f_ctx *c, int which, const float *in, int C, int pix_stride, int B, int h, int w, float *out) try
-{
-    if (!c || !in || !out) return fail("b2f_op_layout: null argument");
-    if (!small_dims(B, h, w) || C < 1 || C > 4096) return fail("b2f_op_layout: bad shape");
-    if (which < 0 || which > 2) return fail("b2f_op_layout: which must be 0 (nhwc_to_planar), 1 (cp8_to_planar) or 2 (planar_to_nhwc)");
-    if (which != 1 && (pix_stride < C || pix_stride > 8192)) return fail("b2f_op_layout: pix_stride must be at least C");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)h * w, planar = (size_t)B * C * hw, nhwc = (size_t)B * hw * pix_stride, cp8 = (size_t)B * ((C + 7) / 8) * hw * 8;
-    const size_t ni = which == 0 ? nhwc : (which == 1 ? cp8 : planar), no = which == 2 ? nhwc : planar;
-    DevBuf di, dout;
-    CHK(op_upload(di, in, ni, "in")); CHK(dout.alloc(no, "out"));
-    if (which == 0) HIPCHK(launch_nhwc_to_planar(di.p, pix_stride, C, B, h, w, dout.p, c->stream));
-    else if (which == 1) HIPCHK(launch_cp8_to_planar(di.p, C, B, h, w, dout.p, c->stream));
-    else HIPCHK(launch_planar_to_nhwc(di.p, C, B, h, w, dout.p, pix_stride, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&di, &dout}));
-    HIPCHK(hipMemcpy(out, dout.p, no * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-B2F_CATCH("b2f_op_layout")
 
 }  // extern "C"
 

@@ -100,52 +100,41 @@ extern "C" {
 int b2f_op_warp_bhwd_backward(b2f_ctx *c, const float *img, const float *grid, const float *grad_out, int B, int ih, int iw, int C, int gh,
                               int gw, float *grad_img, float *grad_grid) try
 {
-    if (!c || !img || !grid || !grad_out || !grad_grid) return api_fail("b2f_op_warp_bhwd_backward: null argument");
+    OpStage st(c, __func__);   // guarded (b2f_ctx.h)
+    CHK(st.begin(img && grid && grad_out && grad_grid));
     if (B <= 0 || ih <= 0 || iw <= 0 || C <= 0 || gh <= 0 || gw <= 0) return api_fail("b2f_op_warp_bhwd_backward: bad shape");
-    HIPCHK(hipSetDevice(c->device));
-    DevBuf di, dg, dgo, dgi, dgg;   // guarded (b2f_ctx.h)
     const size_t ni = (size_t)B * ih * iw * C, ng = (size_t)B * gh * gw * 2, no = (size_t)B * gh * gw * C;
-    CHK(di.alloc(ni, "img")); CHK(dg.alloc(ng, "grid")); CHK(dgo.alloc(no, "grad_out")); CHK(dgg.alloc(ng, "grad_grid"));
-    HIPCHK(hipMemcpy(di.p, img, ni * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dg.p, grid, ng * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dgo.p, grad_out, no * sizeof(float), hipMemcpyHostToDevice));
+    float *di, *dg, *dgo, *dgi = nullptr, *dgg;
+    CHK(st.in(img, ni, "img", &di)); CHK(st.in(grid, ng, "grid", &dg)); CHK(st.in(grad_out, no, "grad_out", &dgo)); CHK(st.out(ng, "grad_grid", &dgg));
     const unsigned blocks = (unsigned)(((size_t)B * gh * gw + 7) / 8);
     if (grad_img) {
-        CHK(dgi.alloc(ni, "grad_img"));
-        HIPCHK(hipMemsetAsync(dgi.p, 0, ni * sizeof(float), c->stream));   // BilinearSamplerBHWD.lua:98-99
-        hipLaunchKernelGGL((warp_bhwd_backward_kernel<false>), dim3(blocks), dim3(256), 0, c->stream, di.p, dg.p, dgo.p, B, ih, iw, C, gh, gw, dgi.p, dgg.p);
+        CHK(st.out(ni, "grad_img", &dgi));
+        HIPCHK(hipMemsetAsync(dgi, 0, ni * sizeof(float), c->stream));   // BilinearSamplerBHWD.lua:98-99
+        hipLaunchKernelGGL((warp_bhwd_backward_kernel<false>), dim3(blocks), dim3(256), 0, c->stream, di, dg, dgo, B, ih, iw, C, gh, gw, dgi, dgg);
     } else {
-        hipLaunchKernelGGL((warp_bhwd_backward_kernel<true>), dim3(blocks), dim3(256), 0, c->stream, di.p, dg.p, dgo.p, B, ih, iw, C, gh, gw, (float *)nullptr, dgg.p);
+        hipLaunchKernelGGL((warp_bhwd_backward_kernel<true>), dim3(blocks), dim3(256), 0, c->stream, di, dg, dgo, B, ih, iw, C, gh, gw, dgi, dgg);
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&di, &dg, &dgo, &dgi, &dgg}));
-    if (grad_img) HIPCHK(hipMemcpy(grad_img, dgi.p, ni * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(grad_grid, dgg.p, ng * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    CHK(st.finish());
+    if (grad_img) CHK(st.get(grad_img, dgi, ni));
+    return st.get(grad_grid, dgg, ng);
 }
 B2F_CATCH("b2f_op_warp_bhwd_backward")
 
 int b2f_op_costvol_backward(b2f_ctx *c, const float *ref, const float *frm, const float *grad_out, int B, int C, int h, int w, int win, int fwd,
                             float *grad_ref, float *grad_frm) try
 {
-    if (!c || !ref || !frm || !grad_out || !grad_ref || !grad_frm) return api_fail("b2f_op_costvol_backward: null argument");
+    OpStage st(c, __func__);
+    CHK(st.begin(ref && frm && grad_out && grad_ref && grad_frm));
     if (win < 1 || win % 2 == 0) return api_fail("b2f_op_costvol_backward: win must be odd");
     if (B <= 0 || C <= 0 || h <= 0 || w <= 0) return api_fail("b2f_op_costvol_backward: bad shape");
-    HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)h * w, nin = (size_t)B * C * hw, ngo = (size_t)B * win * win * hw;
-    DevBuf dr, df, dgo, dgr, dgf;
-    CHK(dr.alloc(nin, "ref")); CHK(df.alloc(nin, "frm")); CHK(dgo.alloc(ngo, "grad_out")); CHK(dgr.alloc(nin, "grad_ref")); CHK(dgf.alloc(nin, "grad_frm"));
-    HIPCHK(hipMemcpy(dr.p, ref, nin * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(df.p, frm, nin * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dgo.p, grad_out, ngo * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(costvol_backward_kernel, dim3((unsigned)((nin + 255) / 256)), dim3(256), 0, c->stream, dr.p, df.p, dgo.p, B, C, h, w, win, fwd, dgr.p, dgf.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dr, &df, &dgo, &dgr, &dgf}));
-    HIPCHK(hipMemcpy(grad_ref, dgr.p, nin * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(grad_frm, dgf.p, nin * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    float *dr, *df, *dgo, *dgr, *dgf;
+    CHK(st.in(ref, nin, "ref", &dr)); CHK(st.in(frm, nin, "frm", &df)); CHK(st.in(grad_out, ngo, "grad_out", &dgo));
+    CHK(st.out(nin, "grad_ref", &dgr)); CHK(st.out(nin, "grad_frm", &dgf));
+    hipLaunchKernelGGL(costvol_backward_kernel, dim3((unsigned)((nin + 255) / 256)), dim3(256), 0, c->stream, dr, df, dgo, B, C, h, w, win, fwd, dgr, dgf);
+    CHK(st.finish());
+    CHK(st.get(grad_ref, dgr, nin));
+    return st.get(grad_frm, dgf, nin);
 }
 B2F_CATCH("b2f_op_costvol_backward")
 

@@ -1,5 +1,5 @@
 // Internal to libb2f.so: the context behind the opaque b2f_ctx of include/b2f.h, shared by the C-ABI layer
-// (b2f_api.hip) and the host-buffer pipeline (b2f_pipeline.hip).
+// (b2f_api.hip), the kernel test entries (b2f_ops.hip) and the host-buffer pipeline (b2f_pipeline.hip).
 #pragma once
 #include "../../include/b2f.h"
 
@@ -7,8 +7,8 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstring>
+#include <deque>
 #include <exception>
-#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -321,8 +321,41 @@ struct DevBuf {
     int alloc(size_t count, const char *what);
     int check() const;
 };
-// check() of every allocated buffer of the list
-int check_guards(std::initializer_list<const DevBuf *> bufs);
+
+// The device buffers of one kernel test entry (b2f_op_*, b2f_ops.hip): every one is a DevBuf the scope owns, and finish() checks every one
+// of them, so an entry keeps no list of its buffers and cannot leave one out.  Sizes are in elements of T and are rounded up to whole
+// floats, (bytes + 3) / 4: the up-to-3-byte tail of a byte buffer is not watched.  An optional buffer is one the entry never asks for.
+class OpStage {
+public:
+    OpStage(b2f_ctx *c, std::string fn) : c_(c), fn_(std::move(fn)) {}
+    // refuses a null context, or !args_ok, with "<fn>: <what>"; then hipSetDevice
+    int begin(bool args_ok = true, const char *what = "null argument");
+    // *dev: a buffer that holds host[0 .. n); the copy blocks, so it is complete before the entry's first launch
+    template <class T> int in(const T *host, size_t n, const char *name, T **dev) { return typed(host, n * sizeof(T), name, dev); }
+    // *dev: a buffer of n elements that holds kGuardWord
+    template <class T> int out(size_t n, const char *name, T **dev) { return typed(nullptr, n * sizeof(T), name, dev); }
+    // hipGetLastError, hipStreamSynchronize of the context's stream, then check() of every buffer in allocation order
+    int finish();
+    // dev[0 .. n) to the host; refused before finish()
+    template <class T> int get(T *host, const T *dev, size_t n) const { return download(host, dev, n * sizeof(T)); }
+
+private:
+    int stage(const void *host, size_t bytes, const char *name, void **dev);
+    template <class T> int typed(const void *host, size_t bytes, const char *name, T **dev)
+    {
+        void *p = nullptr;
+        const int rc = stage(host, bytes, name, &p);
+        *dev = static_cast<T *>(p);
+        return rc;
+    }
+    int download(void *host, const void *dev, size_t bytes) const;
+    b2f_ctx *c_;
+    std::string fn_;
+    std::deque<DevBuf> bufs_;   // never moves an element: DevBuf stays non-copyable
+    bool finished_ = false;
+};
+// the sizes an op entry accepts: three positive factors whose product is at most 2^26 elements
+inline bool small_dims(long long a, long long b, long long c) { return a >= 1 && b >= 1 && c >= 1 && a * b * c <= (1LL << 26); }
 
 // Context-owned device workspace of the device entries (b2f_compute_flow_device / _sequence_device): grows, never shrinks.
 struct DevWork {
@@ -609,11 +642,19 @@ int compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream);
 // the outputs were written (from the third push on)
 int stream_push_host(const FlowRequest &r, int *ready);
 int stream_push_device(const FlowRequest &r, void *stream, int *ready);
-// pieces of b2f_api.hip the generic graph executor (b2f_graph.hip) builds on
+// pieces of b2f_api.hip the generic graph executor (b2f_graph.hip) and the kernel test entries (b2f_ops.hip) build on
 ConvSeg cp8_seg(const float *ptr, int C, size_t hw);
 int find_conv_id(const b2f_ctx *c, int kind, int level, int idx);
 int run_conv_layer(b2f_ctx *c, hipStream_t s, bool cap, int conv_id, const ConvSeg *segs, int nimg, int H, int W, int stride, int leaky,
                    float *out);
+// the conv table as b2f_op_conv3x3 and b2f_op_layer use it (b2f_api.hip, "the conv kernels" and launch_layer)
+ConvKernel base_kernel(int ci, int co, bool stride1, bool two_segments);
+void place_packings(PackedConv &p, bool stride1, const KernelOpts &o, size_t *total);
+void fill_packings(const PackedConv &p, const float *w, const float *b, int ci, const int *cin_map, float *host);
+std::vector<int> layer_cin_map(const ConvDesc &d, bool shipped, PackedConv &p);
+int launch_layer(b2f_ctx *c, hipStream_t s, bool prof, const PackedConv &p, const float *wpk, const KernelOpts &o, int cur_batch, ConvLaunch &L);
+// b2f_ops.hip: the first pyramid conv's weights, Torch 16 x 3 x 3 x 3, as conv_first_kernel reads them: [tap (c, ky, kx)][cout]
+void pack_first_conv(const float *w, float *wp);
 // the arena for a pass of the generic executor over `floats` floats laid out as `bufs` (empty without arena_guard) for shape B x H x W
 int ensure_arena(b2f_ctx *c, size_t floats, std::vector<GraphBuf> &&bufs, int B, int H, int W);
 // b2f_graph.hip: model:forward for the non-shipped graph shapes; outs = the whole output table (planar device buffers)

@@ -386,148 +386,117 @@ int graph_forward(b2f_ctx *c, hipStream_t s, bool cap, const void *dev_in, int i
 }  // namespace b2f
 
 // ---- test entries of the executor's node kernels (tests/test_gpu_glue_float64.py): host pointers in the kernels' own layouts, every
-// device buffer a DevBuf; graph_run is not touched ----
+// device buffer in an OpStage (b2f_ctx.h); graph_run is not touched ----
 using namespace b2f;
-
-namespace {
-int up(DevBuf &d, const float *host, size_t n, const char *what)
-{
-    CHK(d.alloc(n, what));
-    HIPCHK(hipMemcpy(d.p, host, n * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-}
-inline bool dims_ok(long long B, long long hw, long long per) { return B >= 1 && hw >= 1 && per >= 1 && B * hw * per <= (1LL << 26); }
-}  // namespace
 
 extern "C" {
 
 int b2f_op_graph_put_channels(b2f_ctx *c, const float *src, int kind, int src_chunks, int C, int B, int hw, float *dst, int dst_chunks,
                               int c_off) try
 {
-    if (!c || !src || !dst) return api_fail("b2f_op_graph_put_channels: null argument");
-    if (kind < 0 || kind > 2 || C < 1 || c_off < 0 || dst_chunks < 1 || c_off + C > dst_chunks * 8 || !dims_ok(B, hw, (long long)dst_chunks * 8) ||
-        (kind == 0 && (src_chunks < 1 || C > src_chunks * 8 || !dims_ok(B, hw, (long long)src_chunks * 8))))
+    OpStage st(c, __func__);
+    CHK(st.begin(src && dst));
+    if (kind < 0 || kind > 2 || C < 1 || c_off < 0 || dst_chunks < 1 || c_off + C > dst_chunks * 8 || !small_dims(B, hw, (long long)dst_chunks * 8) ||
+        (kind == 0 && (src_chunks < 1 || C > src_chunks * 8 || !small_dims(B, hw, (long long)src_chunks * 8))))
         return api_fail("b2f_op_graph_put_channels: bad shape (kind 0..2, c_off + C <= 8 dst_chunks, kind 0: C <= 8 src_chunks)");
-    HIPCHK(hipSetDevice(c->device));
     const size_t ns = kind == 0 ? (size_t)B * src_chunks * hw * 8 : (size_t)B * hw * C, nd = (size_t)B * dst_chunks * hw * 8;
-    DevBuf ds, dd;
-    CHK(up(ds, src, ns, "src")); CHK(up(dd, dst, nd, "dst"));
-    hipLaunchKernelGGL(put_channels_kernel, dim3(nblk((size_t)B * hw * C)), dim3(256), 0, c->stream, ds.p, kind, src_chunks, C, B, (size_t)hw, dd.p,
+    float *ds, *dd;
+    CHK(st.in(src, ns, "src", &ds)); CHK(st.in(dst, nd, "dst", &dd));
+    hipLaunchKernelGGL(put_channels_kernel, dim3(nblk((size_t)B * hw * C)), dim3(256), 0, c->stream, ds, kind, src_chunks, C, B, (size_t)hw, dd,
                        dst_chunks, c_off);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&ds, &dd}));
-    HIPCHK(hipMemcpy(dst, dd.p, nd * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    CHK(st.finish());
+    return st.get(dst, dd, nd);
 }
 B2F_CATCH("b2f_op_graph_put_channels")
 
 int b2f_op_graph_costvol(b2f_ctx *c, const float *ref, const float *frmF, const float *frmB, int chunks, int C, int B, int h, int w, int win,
                          float *dstJ, int chunksJ, float *dstS, int chunksS) try
 {
-    if (!c || !ref || !frmF || !dstJ) return api_fail("b2f_op_graph_costvol: null argument");
+    OpStage st(c, __func__);
+    CHK(st.begin(ref && frmF && dstJ));
     const int nd = win * win;
     if (win < 1 || win > 31 || win % 2 == 0) return api_fail("b2f_op_graph_costvol: win must be odd, 1..31");
     if (h < 1 || w < 1 || C < 1 || chunks < 1 || C > chunks * 8 || chunksJ * 8 < nd * (frmB ? 2 : 1) || (dstS && chunksS * 8 < nd) || (dstS && !frmB) ||
-        !dims_ok(B, (long long)h * w, (long long)chunks * 8) || !dims_ok(B, (long long)h * w, (long long)chunksJ * 8))
+        !small_dims(B, (long long)h * w, (long long)chunks * 8) || !small_dims(B, (long long)h * w, (long long)chunksJ * 8))
         return api_fail("b2f_op_graph_costvol: bad shape (C <= 8 chunks, 8 chunksJ >= win^2 per direction, 8 chunksS >= win^2, dstS needs frmB)");
-    HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)h * w, nm = (size_t)B * chunks * hw * 8, nj = (size_t)B * chunksJ * hw * 8, nsum = dstS ? (size_t)B * chunksS * hw * 8 : 0;
-    DevBuf dr, df, db, dj, dsum;
-    CHK(up(dr, ref, nm, "ref")); CHK(up(df, frmF, nm, "frmF"));
-    if (frmB) CHK(up(db, frmB, nm, "frmB"));
-    CHK(dj.alloc(nj, "dstJ"));
-    if (dstS) CHK(dsum.alloc(nsum, "dstS"));
-    hipLaunchKernelGGL(costvol_cp8_kernel, dim3(nblk((size_t)B * hw * nd)), dim3(256), 0, c->stream, dr.p, df.p, frmB ? db.p : nullptr, chunks, C, B, h, w,
-                       win, dj.p, chunksJ, dstS ? dsum.p : nullptr, chunksS);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dr, &df, &db, &dj, &dsum}));
-    HIPCHK(hipMemcpy(dstJ, dj.p, nj * sizeof(float), hipMemcpyDeviceToHost));
-    if (dstS) HIPCHK(hipMemcpy(dstS, dsum.p, nsum * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    float *dr, *df, *db = nullptr, *dj, *dsum = nullptr;
+    CHK(st.in(ref, nm, "ref", &dr)); CHK(st.in(frmF, nm, "frmF", &df));
+    if (frmB) CHK(st.in(frmB, nm, "frmB", &db));
+    CHK(st.out(nj, "dstJ", &dj));
+    if (dstS) CHK(st.out(nsum, "dstS", &dsum));
+    hipLaunchKernelGGL(costvol_cp8_kernel, dim3(nblk((size_t)B * hw * nd)), dim3(256), 0, c->stream, dr, df, db, chunks, C, B, h, w, win, dj, chunksJ, dsum,
+                       chunksS);
+    CHK(st.finish());
+    CHK(st.get(dstJ, dj, nj));
+    return dstS ? st.get(dstS, dsum, nsum) : 0;
 }
 B2F_CATCH("b2f_op_graph_costvol")
 
 int b2f_op_graph_warp(b2f_ctx *c, const float *img, int chunks, const float *flow, float k, int B, int h, int w, float *out) try
 {
-    if (!c || !img || !flow || !out) return api_fail("b2f_op_graph_warp: null argument");
-    if (h < 1 || w < 1 || chunks < 1 || !dims_ok(B, (long long)h * w, (long long)chunks * 8)) return api_fail("b2f_op_graph_warp: bad shape");
-    HIPCHK(hipSetDevice(c->device));
+    OpStage st(c, __func__);
+    CHK(st.begin(img && flow && out));
+    if (h < 1 || w < 1 || chunks < 1 || !small_dims(B, (long long)h * w, (long long)chunks * 8)) return api_fail("b2f_op_graph_warp: bad shape");
     const size_t hw = (size_t)h * w, n = (size_t)B * chunks * hw * 8;
-    DevBuf di, df, dout;
-    CHK(up(di, img, n, "img")); CHK(up(df, flow, (size_t)B * hw * 2, "flow")); CHK(dout.alloc(n, "out"));
-    hipLaunchKernelGGL(warp_cp8_kernel, dim3(nblk(n)), dim3(256), 0, c->stream, di.p, chunks, df.p, k, B, h, w, dout.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&di, &df, &dout}));
-    HIPCHK(hipMemcpy(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    float *di, *df, *dout;
+    CHK(st.in(img, n, "img", &di)); CHK(st.in(flow, (size_t)B * hw * 2, "flow", &df)); CHK(st.out(n, "out", &dout));
+    hipLaunchKernelGGL(warp_cp8_kernel, dim3(nblk(n)), dim3(256), 0, c->stream, di, chunks, df, k, B, h, w, dout);
+    CHK(st.finish());
+    return st.get(out, dout, n);
 }
 B2F_CATCH("b2f_op_graph_warp")
 
 int b2f_op_graph_add_flow(b2f_ctx *c, float *fs, const float *u, long long npix) try
 {
-    if (!c || !fs || !u) return api_fail("b2f_op_graph_add_flow: null argument");
-    if (!dims_ok(1, npix, 8)) return api_fail("b2f_op_graph_add_flow: bad size");
-    HIPCHK(hipSetDevice(c->device));
-    DevBuf dfs, du;
-    CHK(up(dfs, fs, (size_t)npix * 8, "fs")); CHK(up(du, u, (size_t)npix * 2, "u"));
-    hipLaunchKernelGGL(add_flow_kernel, dim3(nblk((size_t)npix * 2)), dim3(256), 0, c->stream, dfs.p, du.p, (size_t)npix);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dfs, &du}));
-    HIPCHK(hipMemcpy(fs, dfs.p, (size_t)npix * 8 * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    OpStage st(c, __func__);
+    CHK(st.begin(fs && u));
+    if (!small_dims(1, npix, 8)) return api_fail("b2f_op_graph_add_flow: bad size");
+    float *dfs, *du;
+    CHK(st.in(fs, (size_t)npix * 8, "fs", &dfs)); CHK(st.in(u, (size_t)npix * 2, "u", &du));
+    hipLaunchKernelGGL(add_flow_kernel, dim3(nblk((size_t)npix * 2)), dim3(256), 0, c->stream, dfs, du, (size_t)npix);
+    CHK(st.finish());
+    return st.get(fs, dfs, (size_t)npix * 8);
 }
 B2F_CATCH("b2f_op_graph_add_flow")
 
 int b2f_op_graph_scale(b2f_ctx *c, float *p, long long n, float k) try
 {
-    if (!c || !p) return api_fail("b2f_op_graph_scale: null argument");
-    if (!dims_ok(1, n, 1)) return api_fail("b2f_op_graph_scale: bad size");
-    HIPCHK(hipSetDevice(c->device));
-    DevBuf dp;
-    CHK(up(dp, p, (size_t)n, "p"));
-    hipLaunchKernelGGL(scale_kernel, dim3(nblk((size_t)n)), dim3(256), 0, c->stream, dp.p, (size_t)n, k);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dp}));
-    HIPCHK(hipMemcpy(p, dp.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    OpStage st(c, __func__);
+    CHK(st.begin(p != nullptr));
+    if (!small_dims(1, n, 1)) return api_fail("b2f_op_graph_scale: bad size");
+    float *dp;
+    CHK(st.in(p, (size_t)n, "p", &dp));
+    hipLaunchKernelGGL(scale_kernel, dim3(nblk((size_t)n)), dim3(256), 0, c->stream, dp, (size_t)n, k);
+    CHK(st.finish());
+    return st.get(p, dp, (size_t)n);
 }
 B2F_CATCH("b2f_op_graph_scale")
 
 int b2f_op_graph_softmax_nearest(b2f_ctx *c, const float *logits, int B, int h, int w, int f, float *out) try
 {
-    if (!c || !logits || !out) return api_fail("b2f_op_graph_softmax_nearest: null argument");
-    if (h < 1 || w < 1 || f < 1 || f > 64 || !dims_ok(B, (long long)h * w, (long long)2 * f * f)) return api_fail("b2f_op_graph_softmax_nearest: bad shape (f in 1..64)");
-    HIPCHK(hipSetDevice(c->device));
+    OpStage st(c, __func__);
+    CHK(st.begin(logits && out));
+    if (h < 1 || w < 1 || f < 1 || f > 64 || !small_dims(B, (long long)h * w, (long long)2 * f * f)) return api_fail("b2f_op_graph_softmax_nearest: bad shape (f in 1..64)");
     const size_t ni = (size_t)B * h * w * 8, no = (size_t)B * 2 * h * w * f * f;
-    DevBuf di, dout;
-    CHK(up(di, logits, ni, "logits")); CHK(dout.alloc(no, "out"));
-    hipLaunchKernelGGL(softmax_nearest_kernel, dim3(nblk(no / 2)), dim3(256), 0, c->stream, di.p, B, h, w, f, dout.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&di, &dout}));
-    HIPCHK(hipMemcpy(out, dout.p, no * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    float *di, *dout;
+    CHK(st.in(logits, ni, "logits", &di)); CHK(st.out(no, "out", &dout));
+    hipLaunchKernelGGL(softmax_nearest_kernel, dim3(nblk(no / 2)), dim3(256), 0, c->stream, di, B, h, w, f, dout);
+    CHK(st.finish());
+    return st.get(out, dout, no);
 }
 B2F_CATCH("b2f_op_graph_softmax_nearest")
 
 int b2f_op_expf(b2f_ctx *c, const float *x, long long n, float *y) try
 {
-    if (!c || !x || !y) return api_fail("b2f_op_expf: null argument");
-    if (!dims_ok(1, n, 1)) return api_fail("b2f_op_expf: bad size");
-    HIPCHK(hipSetDevice(c->device));
-    DevBuf dx, dy;
-    CHK(up(dx, x, (size_t)n, "x")); CHK(dy.alloc((size_t)n, "y"));
-    hipLaunchKernelGGL(expf_kernel, dim3(nblk((size_t)n)), dim3(256), 0, c->stream, dx.p, (size_t)n, dy.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    CHK(check_guards({&dx, &dy}));
-    HIPCHK(hipMemcpy(y, dy.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    OpStage st(c, __func__);
+    CHK(st.begin(x && y));
+    if (!small_dims(1, n, 1)) return api_fail("b2f_op_expf: bad size");
+    float *dx, *dy;
+    CHK(st.in(x, (size_t)n, "x", &dx)); CHK(st.out((size_t)n, "y", &dy));
+    hipLaunchKernelGGL(expf_kernel, dim3(nblk((size_t)n)), dim3(256), 0, c->stream, dx, (size_t)n, dy);
+    CHK(st.finish());
+    return st.get(y, dy, (size_t)n);
 }
 B2F_CATCH("b2f_op_expf")
 

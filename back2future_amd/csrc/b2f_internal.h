@@ -1,4 +1,4 @@
-// Internal C++ interface between the C-ABI layer (b2f_api.hip) and the gfx950
+// Internal C++ interface between the C-ABI layer (b2f_api.hip; the op-level entry points: b2f_ops.hip) and the gfx950
 // kernels (b2f_conv*.hip, b2f_wino*.hip, b2f_corr*.hip, b2f_glue.hip, ...).  Activations on the device are
 // chunk-planar fp32 (see below and DESIGN.md "Data layout in HBM"); the kernels take strides, so the op-level entry points pass NHWC.
 #pragma once

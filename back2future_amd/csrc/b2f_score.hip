@@ -166,11 +166,6 @@ int check_flow_score(const std::string &w, const void *flow, int n, int H, int W
     return 0;
 }
 
-struct DevBytes {
-    void *p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-};
-
 // 1 when p is memory the host can read (pageable or page-locked), 0 for device memory
 bool host_memory(const void *p)
 {
@@ -218,27 +213,21 @@ B2F_CATCH("b2f_flow_score_device")
 int b2f_op_flow_score(b2f_ctx *c, const float *flow, const float *occ_prob, int n, int H, int W, double flow_scale, const float *gt_flow,
                       const unsigned char *valid, const unsigned char *gt_occ, unsigned long long *scores) try
 {
-    const std::string w(__func__);
-    CHK(check_flow_score(w, flow, n, H, W, flow_scale, gt_flow, scores));
-    if (!c) return fail(w + ": null context");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)H * W, nf = (size_t)n * 2 * hw * sizeof(float), nb = (size_t)n * hw, ns = (size_t)n * B2F_SCORE_WORDS * sizeof(unsigned long long);
-    DevBytes df, dp, dg, dv, dl, ds;
-    auto up = [&](DevBytes &d, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(&d.p, bytes);
-        return e != hipSuccess ? e : hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice);
-    };
-    HIPCHK(up(df, flow, nf));
-    HIPCHK(up(dg, gt_flow, nf));
-    if (occ_prob) HIPCHK(up(dp, occ_prob, nf));
-    if (valid) HIPCHK(up(dv, valid, nb));
-    if (gt_occ) HIPCHK(up(dl, gt_occ, nb));
-    HIPCHK(hipMalloc(&ds.p, ns));
-    HIPCHK(launch_flow_score((const float *)df.p, (const float *)dp.p, n, H, W, flow_scale, (const float *)dg.p, (const unsigned char *)dv.p,
-                             (const unsigned char *)dl.p, (unsigned long long *)ds.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(scores, ds.p, ns, hipMemcpyDeviceToHost));
-    return 0;
+    CHK(check_flow_score(__func__, flow, n, H, W, flow_scale, gt_flow, scores));
+    OpStage st(c, __func__);
+    CHK(st.begin(true, "null context"));
+    const size_t hw = (size_t)H * W, nf = (size_t)n * 2 * hw, nb = (size_t)n * hw, ns = (size_t)n * B2F_SCORE_WORDS;
+    float *df, *dg, *dp = nullptr;
+    unsigned char *dv = nullptr, *dl = nullptr;
+    unsigned long long *ds;
+    CHK(st.in(flow, nf, "flow", &df)); CHK(st.in(gt_flow, nf, "gt_flow", &dg));
+    if (occ_prob) CHK(st.in(occ_prob, nf, "occ_prob", &dp));
+    if (valid) CHK(st.in(valid, nb, "valid", &dv));
+    if (gt_occ) CHK(st.in(gt_occ, nb, "gt_occ", &dl));
+    CHK(st.out(ns, "scores", &ds));
+    HIPCHK(launch_flow_score(df, dp, n, H, W, flow_scale, dg, dv, dl, ds, c->stream));
+    CHK(st.finish());
+    return st.get(scores, ds, ns);
 }
 B2F_CATCH("b2f_op_flow_score")
 

@@ -220,11 +220,6 @@ int ensure_dev_work(DevWork &dw, size_t bytes)
 
 namespace {
 
-struct DevBytes {
-    void *p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-};
-
 // 1 when p is memory the host can read (pageable or page-locked), 0 for device memory
 bool host_memory(const void *p)
 {
@@ -280,31 +275,25 @@ int table_loss_device(const std::string &w, bool ft, b2f_ctx *c, const float *co
 int op_table_loss(const std::string &w, bool ft, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                   unsigned long long *loss)
 {
-    if (!c) return fail(w + ": null context");
+    OpStage st(c, w);
+    CHK(st.begin(true, "null context"));
     const int per = level_size(c, n_outs);
     if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
     int L = 0;
     CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, loss, &L));
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<DevBytes> dt((size_t)n_outs);
     std::vector<const float *> ptrs((size_t)n_outs);
-    DevBytes dr, dl;
-    auto up = [&](DevBytes &d, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(&d.p, bytes);
-        return e != hipSuccess ? e : hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice);
-    };
+    float *dr;
     for (int i = 0; i < n_outs; ++i) {
         const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
-        HIPCHK(up(dt[(size_t)i], table[i], (size_t)n * ch * (H >> j) * (W >> j) * sizeof(float)));
-        ptrs[(size_t)i] = (const float *)dt[(size_t)i].p;
+        CHK(st.in(table[i], (size_t)n * ch * (H >> j) * (W >> j), "table", &dr));
+        ptrs[(size_t)i] = dr;
     }
-    HIPCHK(up(dr, ref, (size_t)n * 3 * H * W * sizeof(float)));
-    const size_t nl = (size_t)n * L * (ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS) * sizeof(unsigned long long);
-    HIPCHK(hipMalloc(&dl.p, nl));
-    CHK(table_loss_device(w, ft, c, ptrs.data(), n_outs, n, H, W, (const float *)dr.p, flow_scale, (unsigned long long *)dl.p, nullptr));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(loss, dl.p, nl, hipMemcpyDeviceToHost));
-    return 0;
+    unsigned long long *dl;
+    const size_t nl = (size_t)n * L * (ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
+    CHK(st.in(ref, (size_t)n * 3 * H * W, "ref", &dr)); CHK(st.out(nl, "loss", &dl));
+    CHK(table_loss_device(w, ft, c, ptrs.data(), n_outs, n, H, W, dr, flow_scale, dl, nullptr));
+    CHK(st.finish());
+    return st.get(loss, dl, nl);
 }
 
 // ---- the gradient table of train.lua:428-468 (b2f_tableloss_grad.hip) ----
@@ -435,7 +424,8 @@ int table_loss_grad_host_entry(const std::string &w, const float *const *table, 
 int op_table_loss_grad(const std::string &w, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                        const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, float *const *grad)
 {
-    if (!c) return fail(w + ": null context");
+    OpStage st(c, w);
+    CHK(st.begin(true, "null context"));
     const int per = level_size(c, n_outs);
     if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
     int L = 0;
@@ -443,26 +433,20 @@ int op_table_loss_grad(const std::string &w, b2f_ctx *c, const float *const *tab
     CHK(check_grad_table(w, table, n_outs, ref, grad));
     GradOpts o;
     CHK(resolve_grad_opts(w, opts, ft_opts, ft, &o));
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<DevBytes> dt((size_t)n_outs), dg((size_t)n_outs);
     std::vector<const float *> ptrs((size_t)n_outs);
     std::vector<float *> gptrs((size_t)n_outs);
-    std::vector<size_t> bytes((size_t)n_outs);
-    DevBytes dr;
+    std::vector<size_t> floats((size_t)n_outs);
+    float *dr;
     for (int i = 0; i < n_outs; ++i) {
         const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
-        bytes[(size_t)i] = (size_t)n * ch * (H >> j) * (W >> j) * sizeof(float);
-        HIPCHK(hipMalloc(&dt[(size_t)i].p, bytes[(size_t)i]));
-        HIPCHK(hipMemcpy(dt[(size_t)i].p, table[i], bytes[(size_t)i], hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc(&dg[(size_t)i].p, bytes[(size_t)i]));
-        ptrs[(size_t)i] = (const float *)dt[(size_t)i].p;
-        gptrs[(size_t)i] = (float *)dg[(size_t)i].p;
+        floats[(size_t)i] = (size_t)n * ch * (H >> j) * (W >> j);
+        CHK(st.in(table[i], floats[(size_t)i], "table", &dr)); CHK(st.out(floats[(size_t)i], "grad", &gptrs[(size_t)i]));
+        ptrs[(size_t)i] = dr;
     }
-    HIPCHK(hipMalloc(&dr.p, (size_t)n * 3 * H * W * sizeof(float)));
-    HIPCHK(hipMemcpy(dr.p, ref, (size_t)n * 3 * H * W * sizeof(float), hipMemcpyHostToDevice));
-    CHK(table_loss_grad_device(w, c, ptrs.data(), n_outs, n, H, W, (const float *)dr.p, flow_scale, o, gptrs.data(), nullptr));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n_outs; ++i) HIPCHK(hipMemcpy(grad[i], gptrs[(size_t)i], bytes[(size_t)i], hipMemcpyDeviceToHost));
+    CHK(st.in(ref, (size_t)n * 3 * H * W, "ref", &dr));
+    CHK(table_loss_grad_device(w, c, ptrs.data(), n_outs, n, H, W, dr, flow_scale, o, gptrs.data(), nullptr));
+    CHK(st.finish());
+    for (int i = 0; i < n_outs; ++i) CHK(st.get(grad[i], gptrs[(size_t)i], floats[(size_t)i]));
     return 0;
 }
 

@@ -146,11 +146,6 @@ int check_flow_rgb(const std::string &w, const void *flow, int n, int H, int W, 
     return 0;
 }
 
-struct DevBytes {
-    void *p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -192,21 +187,18 @@ B2F_CATCH("b2f_flow_rgb_device")
 int b2f_op_flow_rgb(b2f_ctx *c, const float *flow, int n, int H, int W, double max_norm, int layout, unsigned char *rgb,
                     double *max_used) try
 {
-    const std::string w(__func__);
-    CHK(check_flow_rgb(w, flow, n, H, W, layout, rgb));
-    if (!c) return fail(w + ": null context");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t hw = (size_t)H * W, nf = (size_t)n * 2 * hw * sizeof(float), nc = (size_t)n * 3 * hw;
-    DevBytes df, dc, dm;
-    HIPCHK(hipMalloc(&df.p, nf));
-    HIPCHK(hipMalloc(&dc.p, nc));
-    HIPCHK(hipMalloc(&dm.p, (size_t)n * sizeof(double)));
-    HIPCHK(hipMemcpy(df.p, flow, nf, hipMemcpyHostToDevice));
-    HIPCHK(launch_flow_rgb((const float *)df.p, n, H, W, max_norm, layout, (unsigned char *)dc.p, (double *)dm.p, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(rgb, dc.p, nc, hipMemcpyDeviceToHost));
-    if (max_used) HIPCHK(hipMemcpy(max_used, dm.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    CHK(check_flow_rgb(__func__, flow, n, H, W, layout, rgb));
+    OpStage st(c, __func__);
+    CHK(st.begin(true, "null context"));
+    const size_t hw = (size_t)H * W, nf = (size_t)n * 2 * hw, nc = (size_t)n * 3 * hw;
+    float *df;
+    unsigned char *dc;
+    double *dm;
+    CHK(st.in(flow, nf, "flow", &df)); CHK(st.out(nc, "rgb", &dc)); CHK(st.out((size_t)n, "max_used", &dm));
+    HIPCHK(launch_flow_rgb(df, n, H, W, max_norm, layout, dc, dm, c->stream));
+    CHK(st.finish());
+    CHK(st.get(rgb, dc, nc));
+    return max_used ? st.get(max_used, dm, (size_t)n) : 0;
 }
 B2F_CATCH("b2f_op_flow_rgb")
 

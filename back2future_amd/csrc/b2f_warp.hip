@@ -273,11 +273,6 @@ int check_flow_warp(const std::string &w, const void *flow, int n, int H, int W,
     return 0;
 }
 
-struct DevBytes {
-    void *p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-};
-
 // 1 when p is memory the host can read (pageable or page-locked), 0 for device memory
 bool host_memory(const void *p)
 {
@@ -380,32 +375,25 @@ int warp_device(const char *who, b2f_ctx *c, const float *dev_flow, const float 
 int warp_op(const char *who, b2f_ctx *c, const float *flow, const float *past_flow, const float *occ_prob, int n, int H, int W, double flow_scale,
             int in_kind, const void *im1, const void *im2, const void *im3, void *warped, unsigned long long *photo)
 {
-    const std::string w(who);
-    CHK(check_flow_warp(w, flow, n, H, W, flow_scale, in_kind, im1, im2, im3, warped, photo));
-    if (!c) return fail(w + ": null context");
-    HIPCHK(hipSetDevice(c->device));
+    CHK(check_flow_warp(who, flow, n, H, W, flow_scale, in_kind, im1, im2, im3, warped, photo));
+    OpStage st(c, who);
+    CHK(st.begin(true, "null context"));
     const size_t hw = (size_t)H * W, esz = in_kind == B2F_IN_U8 ? 1 : 4;
-    const size_t nf = (size_t)n * 2 * hw * sizeof(float), ni = (size_t)n * 3 * hw * esz, nw = 2 * ni,
-                 np = (size_t)n * B2F_PHOTO_WORDS * sizeof(unsigned long long);
-    DevBytes df, db, dp, d1, d2, d3, dw, ds;
-    auto up = [&](DevBytes &d, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(&d.p, bytes);
-        return e != hipSuccess ? e : hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice);
-    };
-    HIPCHK(up(df, flow, nf));
-    if (past_flow) HIPCHK(up(db, past_flow, nf));
-    if (occ_prob) HIPCHK(up(dp, occ_prob, nf));
-    HIPCHK(up(d1, im1, ni));
-    HIPCHK(up(d2, im2, ni));
-    HIPCHK(up(d3, im3, ni));
-    if (warped) HIPCHK(hipMalloc(&dw.p, nw));
-    if (photo) HIPCHK(hipMalloc(&ds.p, np));
-    HIPCHK(launch_flow_warp((const float *)df.p, (const float *)dp.p, n, H, W, flow_scale, d1.p, d2.p, d3.p, 3 * hw, in_kind, dw.p, in_kind,
-                            (unsigned long long *)ds.p, c->stream, (const float *)db.p));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (warped) HIPCHK(hipMemcpy(warped, dw.p, nw, hipMemcpyDeviceToHost));
-    if (photo) HIPCHK(hipMemcpy(photo, ds.p, np, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t nf = (size_t)n * 2 * hw, ni = (size_t)n * 3 * hw * esz, nw = 2 * ni, np = (size_t)n * B2F_PHOTO_WORDS;
+    float *df, *db = nullptr, *dp = nullptr;
+    unsigned char *d1, *d2, *d3, *dw = nullptr;   // bytes or floats, by in_kind
+    unsigned long long *ds = nullptr;
+    CHK(st.in(flow, nf, "flow", &df));
+    if (past_flow) CHK(st.in(past_flow, nf, "past_flow", &db));
+    if (occ_prob) CHK(st.in(occ_prob, nf, "occ_prob", &dp));
+    CHK(st.in((const unsigned char *)im1, ni, "im1", &d1)); CHK(st.in((const unsigned char *)im2, ni, "im2", &d2));
+    CHK(st.in((const unsigned char *)im3, ni, "im3", &d3));
+    if (warped) CHK(st.out(nw, "warped", &dw));
+    if (photo) CHK(st.out(np, "photo", &ds));
+    HIPCHK(launch_flow_warp(df, dp, n, H, W, flow_scale, d1, d2, d3, 3 * hw, in_kind, dw, in_kind, ds, c->stream, db));
+    CHK(st.finish());
+    if (warped) CHK(st.get((unsigned char *)warped, dw, nw));
+    return photo ? st.get(photo, ds, np) : 0;
 }
 
 }  // namespace

@@ -940,7 +940,9 @@ B2F_API int b2f_arena_check(b2f_ctx *ctx, int *buffer_index, long long *offset);
 /* b2f_guard_selftest: overwrites ONE guard word by a copy from the host, so that the checks can be seen to fire.  which = 0: offset +3
  * behind buffer 1 of the workspace's layout, 1: offset -2 in front of buffer 0 (both need arena_guard and a pass before; b2f_arena_check
  * then reports that word); 2 / 3: offset +2 behind / -1 in front of a guarded device buffer "selftest" as the b2f_op_* entries allocate
- * them -- the call then fails as such an entry fails, b2f_last_error naming the buffer, the side and the offset.                   */
+ * them -- the call then fails as such an entry fails, b2f_last_error naming the buffer, the side and the offset; 4 / 5: offset +2 behind
+ * buffer "b" (1000 floats) / -1 in front of buffer "c" (7 bytes: 2 floats) of the staging scope those entries take their buffers from,
+ * which holds "a" (10 floats), "b" and "c" and fails in the same words when it checks what it owns.                               */
 B2F_API int b2f_guard_selftest(b2f_ctx *ctx, int which);
 /* b2f_arena_plan: the workspace layout of a pass, computed on the host (no context, no device): the float offset of each of its 33 buffers
  * in the order img, tmp, cs[2..7], U[3..6], UB[3..6], cv, d[1..5], fs, bfs, logits, u2, flow_planar, ds[2..5] (0 for one the pass does

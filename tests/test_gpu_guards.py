@@ -280,6 +280,11 @@ def test_selftest_reports_the_overwritten_word():
             m.guard_selftest(2)
         with pytest.raises(_lib.B2FError, match=r"'selftest' \(1000 floats\) overwritten: 1 words, the first one before the buffer at offset -1 from its start"):
             m.guard_selftest(3)
+        # the op entries' staging scope holds 'a' (10 floats), 'b' (1000 floats) and 'c' (7 bytes): it checks what it owns, without a list
+        with pytest.raises(_lib.B2FError, match=r"'b' \(1000 floats\) overwritten: 1 words, the first one after the buffer at offset \+2 from its end"):
+            m.guard_selftest(4)
+        with pytest.raises(_lib.B2FError, match=r"'c' \(2 floats\) overwritten: 1 words, the first one before the buffer at offset -1 from its start"):
+            m.guard_selftest(5)
         with pytest.raises(_lib.B2FError):
             m.set_option("arena_guard", 100)                 # not a multiple of 64
         m.set_option("arena_guard", 0)
