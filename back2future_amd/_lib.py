@@ -196,6 +196,19 @@ SIGNATURES = {
                                    C.POINTER(c_float_p), C.c_int]),
     "b2f_forward_loss_ft_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "b2f_multi_forward_loss_ft": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong)]),
+    "b2f_table_loss_ssim_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                           C.POINTER(C.c_ulonglong), C.c_int, c_float_p]),
+    "b2f_table_loss_ssim_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                             C.c_void_p, C.c_void_p, C.c_int, c_float_p]),
+    "b2f_op_table_loss_ssim": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                         C.POINTER(C.c_ulonglong), C.c_int, c_float_p]),
+    "b2f_forward_loss_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong),
+                                        C.POINTER(c_float_p), C.c_int, C.c_int, c_float_p]),
+    "b2f_forward_loss_ssim_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                               C.c_int, c_float_p]),
+    "b2f_multi_forward_loss_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong),
+                                              C.c_int, c_float_p]),
+    "b2f_loss_ssim_weights": (C.c_int, [C.POINTER(C.c_double)]),
     "b2f_loss_grad_defaults": (C.c_int, [c_grad_opts_p]),
     "b2f_table_loss_grad_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double, c_grad_opts_p,
                                            C.POINTER(c_float_p)]),

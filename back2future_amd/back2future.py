@@ -44,6 +44,12 @@ LOSS_WEIGHTS = {"smooth_flow": 1.0, "const_vel": 1.0, "pme": 1.0, "smooth_occ": 
 # (base + direction; criterions/OBGCCriterion.lua), pixels with a NaN second-order term, counted pixel-directions with a NaN gradient term
 LOSS_FT_SMOOTH2_FLOW_Q30, LOSS_FT_SMOOTH2_PAST_Q30, LOSS_FT_PHOTO_OGX_Q30, LOSS_FT_PHOTO_OGY_Q30 = 16, 17, 18, 20
 LOSS_FT_SMOOTH2_NONFINITE, LOSS_FT_GRAD_NONFINITE, LOSS_FT_WORDS = 22, 23, 24
+# further words of an SSIM record (include/b2f.h, B2F_LOSS_SSIM_*; objective="ssim"; criterions/OSSIML1Criterion.lua), each base +
+# direction or + (minimum, maximum): Q30 sums of the occlusion-weighted 1 - SSIM and of the L1 penalty of the range-normalised
+# difference, counted pixel-directions with a NaN product or an unusable range, float bits of the range used and of the image's own
+LOSS_SSIM_Q30, LOSS_SSIM_L1N_Q30, LOSS_SSIM_NONFINITE, LOSS_SSIM_RANGE_USED, LOSS_SSIM_RANGE_OWN, LOSS_SSIM_WORDS = 16, 18, 20, 22, 24, 32
+SSIM_RANGE_BATCH, SSIM_RANGE_IMAGE, SSIM_RANGE_GIVEN = 0, 1, 2   # range_mode of the *_ssim entries (include/b2f.h, B2F_SSIM_RANGE_*)
+SSIM_ALPHA = {"OSSIM": 1.0, "OSSIML1": 0.85}                      # model.lua:172-179
 # what each released model was trained on (the reference's README.md:85-102; anything not named keeps opts.lua:61-73), by the names
 # of init.  pme_alpha is listed as given: OBGCCriterion.lua:97 never applies it.  (model.lua:171 assigns -pme_gamma to a field named
 # `gamm`, so a reference run keeps gamma = 1 whatever the option says; pass pme_gamma=1.0 to loss_summary for what such a run printed.)
@@ -58,12 +64,37 @@ LOSS_OBJECTIVES = {
 
 
 def loss_words(objective):
-    """words per record of objective "pme" (16; test.lua:266-297) or "finetune" (24; with the terms of README.md:89-102)"""
+    """words per record of objective "pme" (16; test.lua:266-297), "finetune" (24; with the terms of README.md:89-102) or "ssim" (32;
+    with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua)"""
     if objective == "pme":
         return LOSS_WORDS
     if objective == "finetune":
         return LOSS_FT_WORDS
-    raise ValueError("objective must be 'pme' or 'finetune', got %r" % (objective,))
+    if objective == "ssim":
+        return LOSS_SSIM_WORDS
+    raise ValueError("objective must be 'pme', 'finetune' or 'ssim', got %r" % (objective,))
+
+
+def loss_entry(pattern, objective):
+    """the library's entry for an objective: `pattern` with %s replaced by "", "_ft" or "_ssim" """
+    return getattr(_lib.lib(), pattern % {LOSS_WORDS: "", LOSS_FT_WORDS: "_ft", LOSS_SSIM_WORDS: "_ssim"}[loss_words(objective)])
+
+
+def ssim_range_args(objective, ssim_range, L, who, batch_ok=True):
+    """The trailing (range_mode, ranges) arguments of a b2f_*_ssim entry as a tuple, () for the other objectives.  ssim_range: "batch"
+    (the minimum and maximum over the call's images, OSSIML1Criterion.lua:62-67), "image" (each image's own) or L x 2 numbers
+    (mn, mx per level)."""
+    if loss_words(objective) != LOSS_SSIM_WORDS:
+        return ()
+    if isinstance(ssim_range, str):
+        modes = {"batch": SSIM_RANGE_BATCH, "image": SSIM_RANGE_IMAGE}
+        if ssim_range not in modes or (ssim_range == "batch" and not batch_ok):
+            raise ValueError("%s: ssim_range must be %s'image' or an L x 2 array, got %r" % (who, "'batch', " if batch_ok else "", ssim_range))
+        return (modes[ssim_range], None)
+    r = np.ascontiguousarray(ssim_range, np.float32)
+    if r.shape != (L, 2):
+        raise ValueError("%s: an ssim_range array must have shape (%d, 2): mn, mx per level; got %r" % (who, L, r.shape))
+    return (SSIM_RANGE_GIVEN, _lib.fptr(r))   # (the pointer keeps r alive)
 
 
 def normalize(imgs):
@@ -622,7 +653,7 @@ def photo_summary(photo):
 
 
 def loss_summary(records, like="test", size_average=False, weights=None, smooth_second_order=False, pme_criterion="OBCC", pme_beta=1.0,
-                 pme_gamma=1.0, objective=None):
+                 pme_gamma=1.0, objective=None, ssim_alpha=None):
     """The unsupervised validation loss of test.lua:266-297 from loss records (uint64 n x L x 16 or L x 16; ops.table_loss,
     Model.forwardLoss; or n x L x 24 / L x 24 of objective="finetune").  Per level j
         level_weights[j] * (smooth_flow * S + const_vel * cv + pme * ((OCHARB0 + OCHARB1) / 2^30 + OUTSIDE0 + OUTSIDE1) / (3 * 2)
@@ -636,6 +667,10 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
     SecondOrderSmoothnessCriterion.lua; like and size_average keep their meaning), and pme_criterion="OBGCC" makes the photometric term
         sum over d of ((OCHARB_d + pme_beta * OGX_d + pme_gamma * OGY_d) / 2^30 + OUTSIDE_d) / (3 * 2)
     (OBGCCriterion.lua:96-105,135-143: the brightness part is never multiplied by -pme_alpha, a quirk of updateOutput that is kept).
+    With 32-word records (objective="ssim"): pme_criterion="OSSIM" | "OSSIML1" makes the photometric term
+        sum over d of ((alpha * SSIM_d + (1 - alpha) * L1N_d) / 2^30 + OUTSIDE_d) / (3 * 2)
+    (OSSIML1Criterion.lua:119,149-157) with alpha = 1 for OSSIM and 0.85 for OSSIML1 (model.lua:172-179; ssim_alpha replaces it);
+    "OBCC" reads their first 16 words as before.  Records of another width raise ValueError for these two criteria.
     objective=NAME applies LOSS_OBJECTIVES[NAME], the options the named model was trained with, in place of these three arguments and
     under `weights`.  With 16-word records any of them set away from its default raises ValueError.
     Returns a dict: every term per triplet and level (n x L float64 arrays "smooth_flow", "smooth_past", "const_vel", "pme",
@@ -643,9 +678,9 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
     "mean" (the mean of "loss") and "nonfinite" (pixels left out of a sum that was used because a term was NaN).  The sums are exact
     integers; each pixel term carries the Q30 rounding (2^-31)."""
     s = np.asarray(records)
-    if s.dtype != np.uint64 or s.shape[-1:] not in ((LOSS_WORDS,), (LOSS_FT_WORDS,)) or s.ndim not in (2, 3):
-        raise ValueError("loss_summary: expected uint64 records of shape (n, L, w) or (L, w) with w = %d or %d, got %s %r"
-                         % (LOSS_WORDS, LOSS_FT_WORDS, s.dtype, s.shape))
+    if s.dtype != np.uint64 or s.shape[-1:] not in ((LOSS_WORDS,), (LOSS_FT_WORDS,), (LOSS_SSIM_WORDS,)) or s.ndim not in (2, 3):
+        raise ValueError("loss_summary: expected uint64 records of shape (n, L, w) or (L, w) with w = %d, %d or %d, got %s %r"
+                         % (LOSS_WORDS, LOSS_FT_WORDS, LOSS_SSIM_WORDS, s.dtype, s.shape))
     if like not in ("test", "train"):
         raise ValueError("loss_summary: like must be 'test' or 'train'")
     wt = dict(LOSS_WEIGHTS)
@@ -657,12 +692,20 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
         o = LOSS_OBJECTIVES[objective]
         smooth_second_order, pme_criterion, pme_beta, pme_gamma = o["smooth_second_order"], o["pme_criterion"], o["pme_beta"], o["pme_gamma"]
         wt.update(o["weights"])
-    if pme_criterion not in ("OBCC", "OBGCC"):
-        raise ValueError("loss_summary: pme_criterion must be 'OBCC' or 'OBGCC'")
+    if pme_criterion not in ("OBCC", "OBGCC", "OSSIM", "OSSIML1"):
+        raise ValueError("loss_summary: pme_criterion must be 'OBCC', 'OBGCC', 'OSSIM' or 'OSSIML1'")
     gradients = pme_criterion == "OBGCC"
+    ssim = pme_criterion in SSIM_ALPHA
+    if ssim and s.shape[-1] != LOSS_SSIM_WORDS:
+        raise ValueError("loss_summary: pme_criterion=%r needs the %d-word records of objective='ssim', got records of %d words"
+                         % (pme_criterion, LOSS_SSIM_WORDS, s.shape[-1]))
+    if ssim_alpha is not None and not ssim:
+        raise ValueError("loss_summary: ssim_alpha goes with pme_criterion 'OSSIM' or 'OSSIML1'")
+    if ssim_alpha is not None and not (0.0 <= float(ssim_alpha) <= 1.0):
+        raise ValueError("loss_summary: ssim_alpha must lie in [0, 1], got %r" % (ssim_alpha,))
     ft = s.shape[-1] == LOSS_FT_WORDS
     if not ft and (smooth_second_order or gradients or pme_beta != 1.0 or pme_gamma != 1.0):
-        raise ValueError("loss_summary: 16-word records carry neither second-order nor gradient sums; compute them with objective='finetune'")
+        raise ValueError("loss_summary: only 24-word records carry second-order and gradient sums; compute them with objective='finetune'")
     s = s.reshape((-1,) + s.shape[-2:])
     n, L, _ = s.shape
     if L > len(LOSS_LEVEL_WEIGHTS):
@@ -678,6 +721,9 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
     if gradients:
         photo = photo + float(pme_beta) * (f[:, :, LOSS_FT_PHOTO_OGX_Q30] + f[:, :, LOSS_FT_PHOTO_OGX_Q30 + 1]) \
                       + float(pme_gamma) * (f[:, :, LOSS_FT_PHOTO_OGY_Q30] + f[:, :, LOSS_FT_PHOTO_OGY_Q30 + 1])
+    if ssim:
+        alpha = SSIM_ALPHA[pme_criterion] if ssim_alpha is None else float(ssim_alpha)
+        photo = alpha * (f[:, :, LOSS_SSIM_Q30] + f[:, :, LOSS_SSIM_Q30 + 1]) + (1.0 - alpha) * (f[:, :, LOSS_SSIM_L1N_Q30] + f[:, :, LOSS_SSIM_L1N_Q30 + 1])
     pme = (photo / one + f[:, :, LOSS_PHOTO_OUTSIDE] + f[:, :, LOSS_PHOTO_OUTSIDE + 1]) / (3.0 * 2.0)
     if size_average:
         fs, fp, cv, so = fs / (2.0 * px), fp / (2.0 * px), cv / (2.0 * px), so / (2.0 * px)
@@ -691,6 +737,7 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
     counted = [LOSS_NONFINITE, LOSS_PHOTO_NONFINITE, LOSS_PHOTO_NONFINITE + 1]
     counted += [LOSS_FT_SMOOTH2_NONFINITE] if smooth_second_order else []
     counted += [LOSS_FT_GRAD_NONFINITE] if gradients else []
+    counted += [LOSS_SSIM_NONFINITE, LOSS_SSIM_NONFINITE + 1] if ssim else []
     nonf = int(sum(int(v) for v in s[:, :, counted].ravel()))
     return {"smooth_flow": fs, "smooth_past": fp, "const_vel": cv, "pme": pme, "smooth_occ": so, "prior_occ": pr, "level": level,
             "loss": loss, "mean": float(loss.mean()), "nonfinite": nonf}
@@ -1144,34 +1191,41 @@ class Model(object):
         _lib.check(_lib.lib().b2f_forward(self._h, _lib.fptr(x), B, H, W, ptrs, len(outs)))
         return outs
 
-    def forwardLoss(self, x, flow_scale=20.0, want_table=False, objective="pme"):
+    def forwardLoss(self, x, flow_scale=20.0, want_table=False, objective="pme", ssim_range="batch"):
         """model:forward followed by the unsupervised validation loss of test.lua:266-297 (b2f_forward_loss): x n x 9 x H x W,
         already normalized -> uint64 records (n, L, 16), those of ops.table_loss(self.forward(x), x[:, 3:6]); the table stays on the
         GPU.  want_table=True returns (records, table) with the table of Model.forward, bit for bit.  loss_summary reads the
-        records.  objective="finetune" (b2f_forward_loss_ft): records (n, L, 24), those of ops.table_loss(..., objective="finetune")."""
+        records.  objective="finetune" (b2f_forward_loss_ft): records (n, L, 24), those of ops.table_loss(..., objective="finetune").
+        objective="ssim" (b2f_forward_loss_ssim): records (n, L, 32) with the SSIM + L1 sums of OSSIML1Criterion.lua; ssim_range as for
+        ops.table_loss: "batch" is refused when the request is cut into sub-batches, "image" and an L x 2 array do not depend on the cut."""
         words = loss_words(objective)
-        entry = _lib.lib().b2f_forward_loss_ft if words != LOSS_WORDS else _lib.lib().b2f_forward_loss
         L = self.n_outputs // (5 if self.past_flow else 4)
+        base, tail = loss_entry("b2f_forward_loss%s", objective), ssim_range_args(objective, ssim_range, L, "forwardLoss")
+        entry = lambda *a: base(*(a + tail))
         if want_table:
             return _forward_loss(entry, self._h, x, flow_scale, L, self.output_shapes, words)
         fn = lambda h, xp, n, H, W, fsc, lp: entry(h, xp, n, H, W, fsc, lp, None, 0)
         return _forward_loss(fn, self._h, x, flow_scale, L, None, words)[0]
 
-    def forwardLossDevice(self, d_in, n, H, W, d_loss, flow_scale=20.0, stream=None, objective="pme"):
+    def forwardLossDevice(self, d_in, n, H, W, d_loss, flow_scale=20.0, stream=None, objective="pme", ssim_range="batch"):
         """b2f_forward_loss_device on device pointers (ints): d_in n x 9 x H x W normalized float32, d_loss n x L x 16 uint64 (test.lua:266-297);
-        asynchronous on `stream`.  objective="finetune" (b2f_forward_loss_ft_device): d_loss n x L x 24."""
-        entry = _lib.lib().b2f_forward_loss_ft_device if loss_words(objective) != LOSS_WORDS else _lib.lib().b2f_forward_loss_device
+        asynchronous on `stream`.  objective="finetune" (b2f_forward_loss_ft_device): d_loss n x L x 24; objective="ssim"
+        (b2f_forward_loss_ssim_device): d_loss n x L x 32, ssim_range as for forwardLoss."""
+        entry = loss_entry("b2f_forward_loss%s_device", objective)
+        tail = ssim_range_args(objective, ssim_range, self.n_outputs // (5 if self.past_flow else 4), "forwardLossDevice")
         _lib.check(entry(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale), C.c_void_p(d_loss),
-                         C.c_void_p(stream) if stream else None))
+                         C.c_void_p(stream) if stream else None, *tail))
 
-    def tableLossDevice(self, d_table, n, H, W, d_ref, d_loss, flow_scale=20.0, stream=None, objective="pme"):
+    def tableLossDevice(self, d_table, n, H, W, d_ref, d_loss, flow_scale=20.0, stream=None, objective="pme", ssim_range="batch"):
         """b2f_table_loss_device on device pointers (ints): d_table the L x 4 | 5 tensors of an output table in table order, d_ref
         n x 3 x H x W, d_loss n x L x 16 uint64 (test.lua:266-297); asynchronous on `stream`.  objective="finetune"
-        (b2f_table_loss_ft_device): d_loss n x L x 24."""
+        (b2f_table_loss_ft_device): d_loss n x L x 24; objective="ssim" (b2f_table_loss_ssim_device): d_loss n x L x 32, ssim_range
+        "batch" (over the call's n images), "image" or an L x 2 array."""
         ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
-        entry = _lib.lib().b2f_table_loss_ft_device if loss_words(objective) != LOSS_WORDS else _lib.lib().b2f_table_loss_device
+        entry = loss_entry("b2f_table_loss%s_device", objective)
+        tail = ssim_range_args(objective, ssim_range, len(d_table) // (5 if self.past_flow else 4), "tableLossDevice")
         _lib.check(entry(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale), C.c_void_p(d_loss),
-                         C.c_void_p(stream) if stream else None))
+                         C.c_void_p(stream) if stream else None, *tail))
 
     def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, want_table=False):
         """model:forward followed by `gradOutputs` of train.lua:428-468 (b2f_forward_loss_grad): x n x 9 x H x W, already normalized ->
@@ -1322,14 +1376,18 @@ class MultiModel(object):
         return _compute_flow_sequence_warp("b2f_multi_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out,
                                            want_prob, own_past_flow, want_past)
 
-    def forwardLoss(self, x, flow_scale=20.0, objective="pme"):
-        """Model.forwardLoss over the GPUs (b2f_multi_forward_loss / b2f_multi_forward_loss_ft; test.lua:266-297): the same words."""
+    def forwardLoss(self, x, flow_scale=20.0, objective="pme", ssim_range="image"):
+        """Model.forwardLoss over the GPUs (b2f_multi_forward_loss / b2f_multi_forward_loss_ft / b2f_multi_forward_loss_ssim;
+        test.lua:266-297): the same words.  objective="ssim" takes ssim_range="image" or an L x 2 array: the batch's range would depend
+        on how the images are split over the GPUs."""
         words = loss_words(objective)
-        entry = _lib.lib().b2f_multi_forward_loss_ft if words != LOSS_WORDS else _lib.lib().b2f_multi_forward_loss
         c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
         lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
-        return _forward_loss(entry, self._h, x, flow_scale, no.value // (5 if pf.value else 4), None, words)[0]
+        L = no.value // (5 if pf.value else 4)
+        base = loss_entry("b2f_multi_forward_loss%s", objective)
+        tail = ssim_range_args(objective, ssim_range, L, "MultiModel.forwardLoss", batch_ok=False)
+        return _forward_loss(lambda *a: base(*(a + tail)), self._h, x, flow_scale, L, None, words)[0]
 
     def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True):
         """Model.forwardLossGrad over the GPUs (b2f_multi_forward_loss_grad, b2f_multi_forward_loss_grad_ft; train.lua:428-468): the

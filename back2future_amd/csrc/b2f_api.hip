@@ -963,7 +963,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1009; }
+int b2f_version(void) { return 1010; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1518,7 +1518,8 @@ namespace {
 // what a b2f_forward_loss* call needs from the context's loss workspace for sub-batches of nb triplets
 struct LossPlan {
     int L = 0, per = 0, n_outs = 0;
-    int words = B2F_LOSS_WORDS;     // of a record: B2F_LOSS_FT_WORDS with the fine-tuning terms of README.md:89-102
+    LossKind kind;                  // of a record: words, and the range of the SSIM sums
+    int words = B2F_LOSS_WORDS;     // kind.words: B2F_LOSS_FT_WORDS with the fine-tuning terms of README.md:89-102, B2F_LOSS_SSIM_WORDS with OSSIML1Criterion's
     std::vector<size_t> cnt, off;   // floats and byte offset of every tensor of the table
     std::vector<size_t> goff;       // byte offset of every tensor of the gradient table (b2f_forward_loss_grad only)
     size_t in_off = 0, loss_off = 0, bytes = 0;
@@ -1536,10 +1537,11 @@ int check_forward_loss(const b2f_ctx *c, const std::string &w, int n, int H, int
     return 0;
 }
 
-LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input, bool ft, bool with_grad = false)
+LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input, const LossKind &kind, bool with_grad = false)
 {
     LossPlan p;
-    p.words = ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS;
+    p.kind = kind;
+    p.words = kind.words;
     p.per = c->past_flow ? 5 : 4;
     p.n_outs = c->g.n_outputs();
     p.L = p.n_outs / p.per;
@@ -1588,7 +1590,7 @@ int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H
 {
     CHK(forward_table_run(c, s, d_in, nb, H, W, lp, tab));
     const size_t hw = (size_t)H * W;
-    if (d_loss) CHK(table_loss_run(c, s, tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, d_loss, lp.words));
+    if (d_loss) CHK(table_loss_run(c, s, tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, d_loss, lp.kind));
     if (grad) CHK(table_loss_grad_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, *o, d_loss == nullptr));
     return 0;
 }
@@ -1597,6 +1599,19 @@ int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H
 int loss_subbatch(const b2f_ctx *c, int n, int H, int W)
 {
     return (int)std::min<long long>(std::min(n, 65535), std::max<long long>(1, c->host_subbatch_pixels / ((long long)H * W)));
+}
+
+// what b2f_forward_loss_ssim* check beyond check_forward_loss: the range, and that the batch's range is asked of one sub-batch only (a
+// record would depend on where the request is cut otherwise)
+int check_forward_loss_kind(const b2f_ctx *c, const std::string &w, const LossKind &k, int n, int H, int W)
+{
+    if (!k.ssim()) return 0;
+    const char *why = ssim_range_refusal(k.range_mode, k.ranges);
+    if (why) return fail(w + ": " + why);
+    if (k.range_mode == B2F_SSIM_RANGE_BATCH && loss_subbatch(c, n, H, W) < n)
+        return fail(w + ": B2F_SSIM_RANGE_BATCH needs the request in one sub-batch and this one would be cut (host_subbatch_pixels): use "
+                        "B2F_SSIM_RANGE_IMAGE or B2F_SSIM_RANGE_GIVEN, which do not depend on the cut");
+    return 0;
 }
 
 // grows the context's loss workspace to the plan and points tab, and gr where asked (a plan with_grad), at the plan's tensors in it
@@ -1631,13 +1646,13 @@ struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub
 
 // the sub-batch loop of b2f_forward_loss* and b2f_forward_loss_grad* on checked arguments: upload, forward_loss_run, download of the
 // records (loss), the gradient table (grad, from *o) and the table (outs), each where not null
-int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, bool ft, const GradOpts *o, unsigned long long *loss,
-                          float *const *grad, float *const *outs)
+int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const LossKind &k, const GradOpts *o,
+                          unsigned long long *loss, float *const *grad, float *const *outs)
 {
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
     const int sb = loss_subbatch(c, n, H, W);
-    const LossPlan lp = make_loss_plan(c, sb, H, W, true, ft, grad != nullptr);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, true, k, grad != nullptr);
     std::vector<float *> tab, gr;
     CHK(loss_work_tables(c, lp, tab, grad ? &gr : nullptr));
     float *d_in = (float *)(c->loss_work.dev + lp.in_off);
@@ -1666,16 +1681,17 @@ int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int
 
 // b2f_forward_loss on a shard: `req` is the caller's n (b2f_multi_forward_loss passes its own down)
 int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
-                           bool ft)
+                           const LossKind &k)
 {
-    const std::string w(ft ? "b2f_forward_loss_ft" : "b2f_forward_loss");
+    const std::string w = std::string("b2f_forward_loss") + k.suffix();
     if (!c || !x || !loss) return fail(w + ": null argument");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
+    CHK(check_forward_loss_kind(c, w, k, n, H, W));
     if ((outs == nullptr) != (n_outs == 0)) return fail(w + ": outs and n_outs go together (NULL and 0: the table is not downloaded)");
     if (outs && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be 0 or (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
     for (int i = 0; i < n_outs; ++i)
         if (!outs[i]) return fail(w + ": null tensor in outs");
-    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, ft, nullptr, loss, nullptr, outs);
+    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, k, nullptr, loss, nullptr, outs);
 }
 
 // b2f_forward_loss_grad (ft = false) or b2f_forward_loss_grad_ft on a shard: `req` is the caller's n (b2f_multi_forward_loss_grad* pass
@@ -1694,7 +1710,7 @@ int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int 
         for (int k = 0; k < n_outs; ++k)
             if (outs[i] == grad[k]) return fail(w + ": the gradient table must not alias outs");
     }
-    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, ft, &o, loss, grad, outs);
+    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, loss_kind(ft), &o, loss, grad, outs);
 }
 
 extern "C" {
@@ -1716,15 +1732,16 @@ int b2f_forward_loss_grad_ft(b2f_ctx *c, const float *x, int n, int H, int W, do
 B2F_CATCH("b2f_forward_loss_grad_ft")
 
 extern "C++" {
-// the four device entries: b2f_forward_loss_device / _ft_device (with_grad = false: dev_loss required, no gradient table) and
-// b2f_forward_loss_grad_device / _grad_ft_device (with_grad: dev_grad required, dev_loss optional)
+// the five device entries: b2f_forward_loss_device / _ft_device / _ssim_device (with_grad = false: dev_loss required, no gradient table;
+// k: which records) and b2f_forward_loss_grad_device / _grad_ft_device (with_grad: dev_grad required, dev_loss optional, k = loss_kind(ft))
 static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
-                               const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, bool with_grad, unsigned long long *dev_loss,
-                               float *const *dev_grad, int n_outs, void *stream)
+                               const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, const LossKind &k, bool with_grad,
+                               unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream)
 {
     if (!c || !dev_in || (with_grad ? !dev_grad : !dev_loss)) return fail(w + ": null argument");
     if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
+    CHK(check_forward_loss_kind(c, w, k, n, H, W));
     GradOpts o;
     if (with_grad) CHK(check_forward_loss_grad(c, w, opts, ft_opts, ft, dev_grad, n_outs, &o));
     uintptr_t bits = (uintptr_t)dev_in | (uintptr_t)dev_loss;
@@ -1733,7 +1750,7 @@ static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
     const int sb = loss_subbatch(c, n, H, W);
-    const LossPlan lp = make_loss_plan(c, sb, H, W, false, ft);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, false, k);
     std::vector<float *> tab, gr((size_t)lp.n_outs);
     CHK(loss_work_tables(c, lp, tab, nullptr));
     ReqBatchScope rb(c, n);
@@ -1753,28 +1770,28 @@ static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev
 int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
                                  unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, opts, nullptr, false, true, dev_loss, dev_grad, n_outs, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, opts, nullptr, false, loss_kind(false), true, dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_device")
 
 int b2f_forward_loss_grad_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                                     const b2f_loss_grad_ft_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, opts, true, true, dev_loss, dev_grad, n_outs, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, opts, true, loss_kind(true), true, dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_ft_device")
 
 // model:forward + test.lua:266-297 from host memory
 int b2f_forward_loss(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try
 {
-    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, false);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, loss_kind(false));
 }
 B2F_CATCH("b2f_forward_loss")
 
 // model:forward + test.lua:266-297 + the fine-tuning terms of README.md:89-102 from host memory
 int b2f_forward_loss_ft(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try
 {
-    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, true);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, loss_kind(true));
 }
 B2F_CATCH("b2f_forward_loss_ft")
 
@@ -1782,7 +1799,7 @@ B2F_CATCH("b2f_forward_loss_ft")
 int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                             void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, false, false, dev_loss, nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, false, loss_kind(false), false, dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_device")
 
@@ -1790,9 +1807,26 @@ B2F_CATCH("b2f_forward_loss_device")
 int b2f_forward_loss_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                                void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, true, false, dev_loss, nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, true, loss_kind(true), false, dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_ft_device")
+
+// model:forward + test.lua:266-297 + the SSIM + L1 sums of criterions/OSSIML1Criterion.lua:47-163 from host memory: loss n x L x 32 words
+int b2f_forward_loss_ssim(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
+                          int range_mode, const float *ranges) try
+{
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges});
+}
+B2F_CATCH("b2f_forward_loss_ssim")
+
+// ... on device pointers: dev_loss n x L x 32 words
+int b2f_forward_loss_ssim_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
+                                 void *stream, int range_mode, const float *ranges) try
+{
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, false, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges},
+                               false, dev_loss, nullptr, 0, stream);
+}
+B2F_CATCH("b2f_forward_loss_ssim_device")
 
 }  // extern "C"
 

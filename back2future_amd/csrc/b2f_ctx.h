@@ -612,10 +612,21 @@ int check_request(const FlowRequest &r);
 // b2f_pipeline.hip: a request on host buffers (the upload / kernels / download pipeline) and on device buffers (the kernels alone,
 // asynchronous on `stream`, nullptr: the context's)
 int compute_flow_host(b2f_ctx *c, const FlowRequest &r);
+// which records a table-loss entry writes: words = B2F_LOSS_WORDS (test.lua:266-297), B2F_LOSS_FT_WORDS (with the fine-tuning terms of
+// README.md:89-102 behind them) or B2F_LOSS_SSIM_WORDS (with the SSIM + L1 sums of OSSIML1Criterion.lua and their range: range_mode
+// B2F_SSIM_RANGE_*, ranges L x 2 host floats with B2F_SSIM_RANGE_GIVEN)
+struct LossKind {
+    int words = B2F_LOSS_WORDS;
+    int range_mode = 0;
+    const float *ranges = nullptr;
+    bool ssim() const { return words == B2F_LOSS_SSIM_WORDS; }
+    const char *suffix() const { return words == B2F_LOSS_FT_WORDS ? "_ft" : ssim() ? "_ssim" : ""; }
+};
+inline LossKind loss_kind(bool ft) { return LossKind{ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS, 0, nullptr}; }
 // b2f_api.hip: b2f_forward_loss (test.lua:266-297 behind model:forward) on n of a request of `req` triplets (0: n)
-// ft: b2f_forward_loss_ft, records of B2F_LOSS_FT_WORDS words
+// k: the records of b2f_forward_loss, b2f_forward_loss_ft or b2f_forward_loss_ssim
 int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
-                      bool ft = false);
+                      const LossKind &k = LossKind());
 // checked options of either gradient table: ft = false: the *_grad entries (o's two flags are 0, table_loss_grad_kernel, 16-word
 // records); ft = true: the *_grad_ft entries (table_loss_grad_ft_kernel, 24-word records)
 struct GradOpts {
@@ -625,10 +636,11 @@ struct GradOpts {
 // b2f_tableloss.hip: opts (ft = false) or ft_opts (ft = true), or that kind's defaults where it is null, into *o; refused as
 // include/b2f.h says
 int resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, GradOpts *o);
-// b2f_tableloss.hip: the records of test.lua:266-297 of n images on s, under the profile row table_loss; words = B2F_LOSS_WORDS, or
-// B2F_LOSS_FT_WORDS with the fine-tuning terms behind them (table_loss_ft).  Builds R_1 .. R_{L-1} in c->loss_pyr first.
+// b2f_tableloss.hip: the records of test.lua:266-297 of n images on s, under the profile row table_loss; k.words = B2F_LOSS_WORDS,
+// B2F_LOSS_FT_WORDS with the fine-tuning terms behind them (table_loss_ft), or B2F_LOSS_SSIM_WORDS with the ranges and the SSIM + L1
+// sums (table_loss_range, table_loss_ssim).  Builds R_1 .. R_{L-1} in c->loss_pyr first.
 int table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, int L, bool past, int n, int H, int W, const float *dev_ref,
-                   size_t ref_stride, double flow_scale, unsigned long long *dev_loss, int words);
+                   size_t ref_stride, double flow_scale, unsigned long long *dev_loss, const LossKind &k);
 // b2f_tableloss.hip: the gradient table of train.lua:428-468 of n images on s, from checked options; with_pyr: R_1 .. R_{L-1} are built
 // first (false: table_loss_run has built them on s)
 int table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,

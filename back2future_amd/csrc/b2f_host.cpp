@@ -9,8 +9,10 @@
 #include "b2f_tableloss_grad.h"
 #include "b2f_tableloss_grad_ft.h"
 #include "b2f_tableloss_ft.h"
+#include "b2f_tableloss_ssim.h"
 #include "../../include/b2f.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -415,6 +417,139 @@ void table_loss_ft_host(const float *const *table, int L, bool past, int n, int 
                 }
         }
     }
+}
+
+// the SSIM + L1 photometric sums of criterions/OSSIML1Criterion.lua:47-163 beside test.lua:266-297
+void table_loss_ssim_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                          int range_mode, const float *ranges, unsigned long long *loss)
+{
+    constexpr int kRec = B2F_LOSS_SSIM_WORDS;
+    table_loss_host(table, L, past, n, H, W, ref, flow_scale, loss, kRec);
+    const int per = past ? 5 : 4;
+    std::vector<float> cur, next;
+    // R_j of image b while j runs from 0 up: the 2 x 2 mean of R_{j-1} as in table_loss_host
+    auto level_ref = [&](int b, int j, const float *prev) {
+        if (j == 0) return ref + (size_t)b * 3 * H * W;
+        pool_ref(prev, H >> (j - 1), W >> (j - 1), next);
+        cur.swap(next);
+        return (const float *)cur.data();
+    };
+    // every image's own range per level, on the encoding whose minimum and maximum do not depend on the order; then the one used
+    std::vector<unsigned> lo((size_t)L, 0xffffffffu), hi((size_t)L, 0u);
+    for (int b = 0; b < n; ++b) {
+        const float *R = nullptr;
+        for (int j = 0; j < L; ++j) {
+            const size_t hw = (size_t)(H >> j) * (W >> j);
+            R = level_ref(b, j, R);
+            const float *const *t = table + (size_t)j * per;
+            const float *seg[3] = {R, t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
+            unsigned l = 0xffffffffu, h = 0u;
+            for (const float *p : seg)
+                for (size_t i = 0; i < 3 * hw; ++i)
+                    if (p[i] == p[i]) {
+                        const unsigned e = ssim_enc(p[i]);
+                        l = std::min(l, e);
+                        h = std::max(h, e);
+                    }
+            unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
+            rec[B2F_LOSS_SSIM_RANGE_OWN] = ssim_dec_bits(l);
+            rec[B2F_LOSS_SSIM_RANGE_OWN + 1] = ssim_dec_bits(h);
+            lo[(size_t)j] = std::min(lo[(size_t)j], l);
+            hi[(size_t)j] = std::max(hi[(size_t)j], h);
+        }
+    }
+    auto float_bits = [](float v) {
+        unsigned u;
+        std::memcpy(&u, &v, sizeof u);
+        return u;
+    };
+    auto bits_float = [](unsigned long long u64) {
+        const unsigned u = (unsigned)u64;
+        float v;
+        std::memcpy(&v, &u, sizeof v);
+        return v;
+    };
+    std::vector<double> tv[3][3];   // the normalised planes of a level: [R, iw1, iw3][channel]
+    for (int b = 0; b < n; ++b) {
+        const float *R = nullptr;
+        for (int j = 0; j < L; ++j) {
+            const int h = H >> j, w = W >> j;
+            const size_t hw = (size_t)h * w;
+            R = level_ref(b, j, R);
+            unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
+            if (range_mode == B2F_SSIM_RANGE_BATCH) {
+                rec[B2F_LOSS_SSIM_RANGE_USED] = ssim_dec_bits(lo[(size_t)j]);
+                rec[B2F_LOSS_SSIM_RANGE_USED + 1] = ssim_dec_bits(hi[(size_t)j]);
+            } else if (range_mode == B2F_SSIM_RANGE_GIVEN) {
+                rec[B2F_LOSS_SSIM_RANGE_USED] = float_bits(ranges[2 * j]);
+                rec[B2F_LOSS_SSIM_RANGE_USED + 1] = float_bits(ranges[2 * j + 1]);
+            } else {
+                rec[B2F_LOSS_SSIM_RANGE_USED] = rec[B2F_LOSS_SSIM_RANGE_OWN];
+                rec[B2F_LOSS_SSIM_RANGE_USED + 1] = rec[B2F_LOSS_SSIM_RANGE_OWN + 1];
+            }
+            const SsimRange rg = ssim_range(bits_float(rec[B2F_LOSS_SSIM_RANGE_USED]), bits_float(rec[B2F_LOSS_SSIM_RANGE_USED + 1]));
+            const float *const *t = table + (size_t)j * per;
+            const float *f = t[0] + (size_t)b * 2 * hw, *p = past ? t[1] + (size_t)b * 2 * hw : nullptr;
+            const float *o = t[per - 3] + (size_t)b * 2 * hw, *iw[2] = {t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
+            const float *src[3] = {R, iw[0], iw[1]};
+            if (rg.ok)
+                for (int s = 0; s < 3; ++s)
+                    for (int c = 0; c < 3; ++c) {
+                        tv[s][c].resize(hw);
+                        for (size_t i = 0; i < hw; ++i) tv[s][c][i] = ssim_norm(src[s][(size_t)c * hw + i], rg);
+                    }
+            const float kd = (float)(flow_scale / (double)(1 << j));
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    const size_t i = (size_t)y * w + x;
+                    const size_t xs[3] = {(size_t)(x > 0 ? x - 1 : x), (size_t)x, (size_t)(x + 1 < w ? x + 1 : x)};
+                    const size_t ys[3] = {(size_t)(y > 0 ? y - 1 : y) * w, (size_t)y * w, (size_t)(y + 1 < h ? y + 1 : y) * w};
+                    // the window sum of a * b2 (b2 == nullptr: of a) at the pixel, indices clamped to the plane
+                    auto G = [&](const double *a, const double *b2) {
+                        double col[3];
+                        for (int k = 0; k < 3; ++k) {
+                            const size_t i0 = ys[0] + xs[k], i1 = ys[1] + xs[k], i2 = ys[2] + xs[k];
+                            col[k] = b2 ? ssim_tap3(a[i0] * b2[i0], a[i1] * b2[i1], a[i2] * b2[i2]) : ssim_tap3(a[i0], a[i1], a[i2]);
+                        }
+                        return ssim_tap3(col[0], col[1], col[2]);
+                    };
+                    const float r3[3] = {R[i], R[hw + i], R[2 * hw + i]};
+                    bool counted[2];
+                    for (int d = 0; d < 2; ++d) {
+                        const float *fl = (d == 0 && past) ? p : f;   // OSSIML1Criterion.lua:131-132
+                        const WarpTaps tp = warp_taps(fl[i], fl[hw + i], d == 0 ? -kd : kd, x, y, w, h);
+                        const float w3[3] = {iw[d][i], iw[d][hw + i], iw[d][2 * hw + i]};
+                        counted[d] = photo_pixel(tp, w3, r3, true, d == 0 ? o[hw + i] : o[i]).inside != 0u;
+                    }
+                    double S[2] = {0.0, 0.0}, B[2] = {0.0, 0.0};
+                    if (rg.ok && (counted[0] || counted[1]))
+                        for (int c = 0; c < 3; ++c) {
+                            const double *ty = tv[0][c].data();
+                            const double mu_y = G(ty, nullptr), gyy = G(ty, ty);
+                            for (int d = 0; d < 2; ++d) {
+                                const double *tx = tv[1 + d][c].data();
+                                const double s = ssim_term(G(tx, nullptr), mu_y, G(tx, tx), gyy, G(tx, ty)), e = loss_p1(tx[i] - ty[i]);
+                                S[d] = c == 0 ? s : S[d] + s;
+                                B[d] = c == 0 ? e : B[d] + e;
+                            }
+                        }
+                    for (int d = 0; d < 2; ++d) {
+                        const PixelSsim ps = ssim_pixel(S[d], B[d], counted[d], rg.ok, d == 0 ? o[hw + i] : o[i]);
+                        rec[B2F_LOSS_SSIM_Q30 + d] += ps.ssim;
+                        rec[B2F_LOSS_SSIM_L1N_Q30 + d] += ps.l1n;
+                        rec[B2F_LOSS_SSIM_NONFINITE + d] += ps.nonfinite;
+                    }
+                }
+        }
+    }
+}
+
+const char *ssim_range_refusal(int range_mode, const float *ranges)
+{
+    if (range_mode != B2F_SSIM_RANGE_BATCH && range_mode != B2F_SSIM_RANGE_IMAGE && range_mode != B2F_SSIM_RANGE_GIVEN)
+        return "range_mode must be B2F_SSIM_RANGE_BATCH, B2F_SSIM_RANGE_IMAGE or B2F_SSIM_RANGE_GIVEN";
+    if (range_mode == B2F_SSIM_RANGE_GIVEN && !ranges) return "B2F_SSIM_RANGE_GIVEN needs ranges (L x 2 floats)";
+    return nullptr;
 }
 
 // what every b2f_*table_loss* entry checks before anything else (no HIP call): 0 and *L, or the message

@@ -89,6 +89,13 @@ void table_loss_host(const float *const *table, int L, bool past, int n, int H, 
 // (b2f_tableloss_ft.h per pixel; b2f_table_loss_ft_host)
 void table_loss_ft_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
                         unsigned long long *loss);
+// table_loss_host with records of B2F_LOSS_SSIM_WORDS words, and in words 16 .. 25 the SSIM + L1 photometric sums and the ranges of
+// criterions/OSSIML1Criterion.lua:47-163 (b2f_tableloss_ssim.h per pixel; b2f_table_loss_ssim_host); range_mode: B2F_SSIM_RANGE_*,
+// ranges: L x 2 floats with B2F_SSIM_RANGE_GIVEN
+void table_loss_ssim_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                          int range_mode, const float *ranges, unsigned long long *loss);
+// what every *_ssim entry checks of its range (no HIP call): nullptr, or why not
+const char *ssim_range_refusal(int range_mode, const float *ranges);
 // the argument checks every table-loss entry shares (test.lua:266-297; no HIP call): nullptr and *L = n_outs / per, or why not
 const char *table_loss_refusal(int n_outs, int per, int n, int H, int W, double flow_scale, int *L);
 }  // namespace b2f

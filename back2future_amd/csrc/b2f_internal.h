@@ -371,6 +371,13 @@ size_t table_loss_pyramid_floats(int L, int n, int H, int W);
 // records' launch has zeroed
 hipError_t launch_table_loss_ft_terms(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
                                       const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s);
+// b2f_tableloss_ssim.hip: the ranges of criterions/OSSIML1Criterion.lua:62-67 into words 22 .. 25 of records of B2F_LOSS_SSIM_WORDS words,
+// which the records' launch has zeroed (range_mode: B2F_SSIM_RANGE_*; ranges: L x 2 host floats with B2F_SSIM_RANGE_GIVEN), and behind
+// them the SSIM + L1 sums of lines 69-151 into words 16 .. 21
+hipError_t launch_table_loss_range(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, const float *pyr,
+                                   int range_mode, const float *ranges, unsigned long long *loss, hipStream_t s);
+hipError_t launch_table_loss_ssim_terms(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
+                                        const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s);
 // b2f_tableloss_grad.hip: the gradient table of train.lua:428-468 (include/b2f.h: G_f, G_p, G_o, G_iw_d): grad = L x (4 | 5) device
 // tensors of n images with the table's shapes (a host array), none of them a tensor of the table or ref; coef[j]: the
 // coefficients of level j (b2f_host.h: loss_grad_coef).  Every element of grad is written.

@@ -405,15 +405,19 @@ B2F_CATCH("b2f_multi_compute_flow_sequence_warp_past")
 
 }  // extern "C"
 
-// b2f_multi_forward_loss / b2f_multi_forward_loss_ft
-static int multi_forward_loss(const std::string &w, bool ft, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss)
+// b2f_multi_forward_loss / b2f_multi_forward_loss_ft / b2f_multi_forward_loss_ssim
+static int multi_forward_loss(const std::string &w, const LossKind &k, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss)
 {
     if (!m) return api_fail(w + ": null context");
     if (!x || !loss || n <= 0 || H <= 0 || W <= 0) return api_fail(w + ": bad arguments");
+    // (a shard's batch range would depend on how the request is split over the GPUs)
+    if (k.ssim() && k.range_mode == B2F_SSIM_RANGE_BATCH)
+        return api_fail(w + ": B2F_SSIM_RANGE_BATCH is not served over several GPUs: the images of a request are split; use B2F_SSIM_RANGE_IMAGE or "
+                            "B2F_SSIM_RANGE_GIVEN");
     const b2f_ctx *c0 = m->ctx[0];
-    const size_t rec = (size_t)(c0->g.n_outputs() / (c0->past_flow ? 5 : 4)) * (ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
+    const size_t rec = (size_t)(c0->g.n_outputs() / (c0->past_flow ? 5 : 4)) * k.words;
     return run_sharded(m, n, [&](int i, int lo, int hi) {
-        return forward_loss_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, loss + (size_t)lo * rec, nullptr, 0, ft);
+        return forward_loss_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, loss + (size_t)lo * rec, nullptr, 0, k);
     });
 }
 
@@ -422,16 +426,24 @@ extern "C" {
 // test.lua:266-297 behind model:forward over several GPUs
 int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss) try
 {
-    return multi_forward_loss(__func__, false, m, x, n, H, W, flow_scale, loss);
+    return multi_forward_loss(__func__, loss_kind(false), m, x, n, H, W, flow_scale, loss);
 }
 B2F_CATCH("b2f_multi_forward_loss")
 
 // ... with the fine-tuning terms of README.md:89-102 in words 16 .. 23
 int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss) try
 {
-    return multi_forward_loss(__func__, true, m, x, n, H, W, flow_scale, loss);
+    return multi_forward_loss(__func__, loss_kind(true), m, x, n, H, W, flow_scale, loss);
 }
 B2F_CATCH("b2f_multi_forward_loss_ft")
+
+// ... with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua:47-163 in words 16 .. 25; the batch range is refused
+int b2f_multi_forward_loss_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, int range_mode,
+                                const float *ranges) try
+{
+    return multi_forward_loss(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, m, x, n, H, W, flow_scale, loss);
+}
+B2F_CATCH("b2f_multi_forward_loss_ssim")
 
 // b2f_multi_forward_loss_grad (ft = false) and b2f_multi_forward_loss_grad_ft
 static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,

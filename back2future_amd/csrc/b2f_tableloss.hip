@@ -8,6 +8,7 @@
 #include "b2f_ctx.h"
 #include "b2f_tableloss.h"
 #include "b2f_tableloss_grad_ft.h"
+#include "b2f_tableloss_ssim.h"
 #include "b2f_tableloss_dev.h"
 
 using namespace b2f;
@@ -250,8 +251,15 @@ int level_size(const b2f_ctx *c, int n_outs)
     return (n_outs > 0 && n_outs % own == 0) ? own : (n_outs > 0 && n_outs % other == 0) ? other : 0;
 }
 
-// b2f_table_loss_device / b2f_table_loss_ft_device (ft: records of B2F_LOSS_FT_WORDS words with the fine-tuning terms)
-int table_loss_device(const std::string &w, bool ft, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+// what the *_ssim entries check of their range
+int check_loss_kind(const std::string &w, const LossKind &k)
+{
+    const char *why = k.ssim() ? ssim_range_refusal(k.range_mode, k.ranges) : nullptr;
+    return why ? fail(w + ": " + why) : 0;
+}
+
+// b2f_table_loss_device / b2f_table_loss_ft_device / b2f_table_loss_ssim_device (k: which records)
+int table_loss_device(const std::string &w, const LossKind &k, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
                       double flow_scale, unsigned long long *dev_loss, void *stream)
 {
     if (!c) return fail(w + ": null context");
@@ -259,6 +267,7 @@ int table_loss_device(const std::string &w, bool ft, b2f_ctx *c, const float *co
     if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
     int L = 0;
     CHK(check_table_loss(w, dev_table, n_outs, per, n, H, W, dev_ref, flow_scale, dev_loss, &L));
+    CHK(check_loss_kind(w, k));
     if (n > 65535) return fail(w + ": at most 65535 images per call");
     uintptr_t bits = (uintptr_t)dev_ref | (uintptr_t)dev_loss;
     for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i];
@@ -267,12 +276,11 @@ int table_loss_device(const std::string &w, bool ft, b2f_ctx *c, const float *co
     if (host_memory(dev_ref) || host_memory(dev_loss)) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss / b2f_table_loss_host)");
     for (int i = 0; i < n_outs; ++i)
         if (host_memory(dev_table[i])) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss / b2f_table_loss_host)");
-    return table_loss_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, flow_scale, dev_loss,
-                          ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
+    return table_loss_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, flow_scale, dev_loss, k);
 }
 
-// b2f_op_table_loss / b2f_op_table_loss_ft
-int op_table_loss(const std::string &w, bool ft, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+// b2f_op_table_loss / b2f_op_table_loss_ft / b2f_op_table_loss_ssim
+int op_table_loss(const std::string &w, const LossKind &k, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                   unsigned long long *loss)
 {
     OpStage st(c, w);
@@ -281,6 +289,7 @@ int op_table_loss(const std::string &w, bool ft, b2f_ctx *c, const float *const 
     if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
     int L = 0;
     CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, loss, &L));
+    CHK(check_loss_kind(w, k));
     std::vector<const float *> ptrs((size_t)n_outs);
     float *dr;
     for (int i = 0; i < n_outs; ++i) {
@@ -289,9 +298,9 @@ int op_table_loss(const std::string &w, bool ft, b2f_ctx *c, const float *const 
         ptrs[(size_t)i] = dr;
     }
     unsigned long long *dl;
-    const size_t nl = (size_t)n * L * (ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
+    const size_t nl = (size_t)n * L * k.words;
     CHK(st.in(ref, (size_t)n * 3 * H * W, "ref", &dr)); CHK(st.out(nl, "loss", &dl));
-    CHK(table_loss_device(w, ft, c, ptrs.data(), n_outs, n, H, W, dr, flow_scale, dl, nullptr));
+    CHK(table_loss_device(w, k, c, ptrs.data(), n_outs, n, H, W, dr, flow_scale, dl, nullptr));
     CHK(st.finish());
     return st.get(loss, dl, nl);
 }
@@ -346,16 +355,26 @@ int timed_launch(b2f_ctx *c, hipStream_t s, const char *name, Launch launch)
 
 }  // namespace
 
-// the records of n images on s: words = B2F_LOSS_WORDS, or B2F_LOSS_FT_WORDS with the fine-tuning terms behind them.  Builds R_1 ..
-// R_{L-1} in the context's workspace, where table_loss_grad_run(..., with_pyr = false) on the same arguments and stream finds them.
+// the records of n images on s: k.words = B2F_LOSS_WORDS, B2F_LOSS_FT_WORDS with the fine-tuning terms behind them, or B2F_LOSS_SSIM_WORDS
+// with the ranges and the SSIM + L1 sums behind them.  Builds R_1 .. R_{L-1} in the context's workspace, where
+// table_loss_grad_run(..., with_pyr = false) on the same arguments and stream finds them.
 int b2f::table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, int L, bool past, int n, int H, int W, const float *dev_ref,
-                        size_t ref_stride, double flow_scale, unsigned long long *dev_loss, int words)
+                        size_t ref_stride, double flow_scale, unsigned long long *dev_loss, const LossKind &k)
 {
+    const int words = k.words;
     CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
     float *pyr = (float *)c->loss_pyr.dev;
     CHK(timed_launch(c, s, "table_loss", [&] {
         return launch_table_loss(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s, words);
     }));
+    if (k.ssim()) {
+        CHK(timed_launch(c, s, "table_loss_range", [&] {
+            return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, k.range_mode, k.ranges, dev_loss, s);
+        }));
+        return timed_launch(c, s, "table_loss_ssim", [&] {
+            return launch_table_loss_ssim_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
+        });
+    }
     if (words != B2F_LOSS_FT_WORDS) return 0;
     return timed_launch(c, s, "table_loss_ft", [&] {
         return launch_table_loss_ft_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
@@ -541,7 +560,7 @@ B2F_CATCH("b2f_table_loss_host")
 int b2f_table_loss_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
                           unsigned long long *dev_loss, void *stream) try
 {
-    return table_loss_device(__func__, false, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
+    return table_loss_device(__func__, loss_kind(false), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
 }
 B2F_CATCH("b2f_table_loss_device")
 
@@ -549,7 +568,7 @@ B2F_CATCH("b2f_table_loss_device")
 int b2f_op_table_loss(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                       unsigned long long *loss) try
 {
-    return op_table_loss(__func__, false, c, table, n_outs, n, H, W, ref, flow_scale, loss);
+    return op_table_loss(__func__, loss_kind(false), c, table, n_outs, n, H, W, ref, flow_scale, loss);
 }
 B2F_CATCH("b2f_op_table_loss")
 
@@ -567,15 +586,51 @@ B2F_CATCH("b2f_table_loss_ft_host")
 int b2f_table_loss_ft_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
                              unsigned long long *dev_loss, void *stream) try
 {
-    return table_loss_device(__func__, true, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
+    return table_loss_device(__func__, loss_kind(true), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
 }
 B2F_CATCH("b2f_table_loss_ft_device")
 
 int b2f_op_table_loss_ft(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                          unsigned long long *loss) try
 {
-    return op_table_loss(__func__, true, c, table, n_outs, n, H, W, ref, flow_scale, loss);
+    return op_table_loss(__func__, loss_kind(true), c, table, n_outs, n, H, W, ref, flow_scale, loss);
 }
 B2F_CATCH("b2f_op_table_loss_ft")
+
+// ---- the same three with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua:47-163 in words 16 .. 25 (b2f_tableloss_ssim.hip) ----
+int b2f_table_loss_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                             unsigned long long *loss, int range_mode, const float *ranges) try
+{
+    int L = 0;
+    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
+    CHK(check_loss_kind(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}));
+    table_loss_ssim_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, range_mode, ranges, loss);
+    return 0;
+}
+B2F_CATCH("b2f_table_loss_ssim_host")
+
+int b2f_table_loss_ssim_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                               unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges) try
+{
+    return table_loss_device(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
+}
+B2F_CATCH("b2f_table_loss_ssim_device")
+
+int b2f_op_table_loss_ssim(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                           unsigned long long *loss, int range_mode, const float *ranges) try
+{
+    return op_table_loss(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, c, table, n_outs, n, H, W, ref, flow_scale, loss);
+}
+B2F_CATCH("b2f_op_table_loss_ssim")
+
+// ge, gc of the window (b2f_tableloss_ssim.h)
+int b2f_loss_ssim_weights(double out[2]) try
+{
+    if (!out) return fail("b2f_loss_ssim_weights: null argument");
+    out[0] = kSsimGe;
+    out[1] = kSsimGc;
+    return 0;
+}
+B2F_CATCH("b2f_loss_ssim_weights")
 
 }  // extern "C"

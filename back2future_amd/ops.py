@@ -262,7 +262,7 @@ def flow_warp(flow, im1, im2, im3, occ_prob=None, flow_scale=20.0, want_warped=T
     return warped, photo
 
 
-def table_loss(table, ref, flow_scale=20.0, model=None, objective="pme"):
+def table_loss(table, ref, flow_scale=20.0, model=None, objective="pme", ssim_range="batch"):
     """The records of the unsupervised validation loss (the -optimize pme branch of test.lua:266-297) of an output table of
     model:forward: table a list of L x 4 (Hard: per level future flow, occlusions, warped image 1, warped image 3) or L x 5 (Soft:
     the past flow second) float32 arrays n x C x (H >> j) x (W >> j), what Model.forward returns; ref n x 3 x H x W float32, the
@@ -270,10 +270,12 @@ def table_loss(table, ref, flow_scale=20.0, model=None, objective="pme"):
     reads it).  model=None computes on the CPU (b2f_table_loss_host, no GPU), a Model on its GPU (b2f_op_table_loss; a table whose
     length fits both kinds, 20 tensors, is read as the model's kind): the words are the same.  objective="finetune" returns
     (n, L, 24) (b2f_table_loss_ft_host / b2f_op_table_loss_ft): the same 16 words, then the second-order smoothness and the
-    gradient-constancy sums the Soft models were fine-tuned on (back2future.LOSS_FT_*)."""
-    from .back2future import LOSS_WORDS, loss_words
+    gradient-constancy sums the Soft models were fine-tuned on (back2future.LOSS_FT_*).  objective="ssim" returns (n, L, 32)
+    (b2f_table_loss_ssim_host / b2f_op_table_loss_ssim): the same 16 words, then the SSIM + L1 sums of -pme_criterion OSSIM | OSSIML1
+    (criterions/OSSIML1Criterion.lua; back2future.LOSS_SSIM_*) on values normalised by ssim_range: "batch", the minimum and maximum
+    over the n images of the call as in the reference; "image", each image's own; or an L x 2 array of (mn, mx) per level."""
+    from .back2future import loss_words, loss_entry, ssim_range_args
     words = loss_words(objective)
-    ft = "_ft" if words != LOSS_WORDS else ""
     r = np.asarray(ref)
     if r.ndim != 4 or r.shape[1] != 3 or min(r.shape) < 1:
         raise ValueError("table_loss: expected an n x 3 x H x W reference image, got shape %r" % (np.shape(ref),))
@@ -293,13 +295,14 @@ def table_loss(table, ref, flow_scale=20.0, model=None, objective="pme"):
     ptrs = (_lib.c_float_p * len(tab))(*[_lib.fptr(t) for t in tab])
     loss = np.empty((n, L, words), np.uint64)
     lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong))
+    tail = ssim_range_args(objective, ssim_range, L, "table_loss")
     if model is None:
-        _lib.check(getattr(_lib.lib(), "b2f_table_loss%s_host" % ft)(ptrs, len(tab), n, H, W, int(per == 5), _lib.fptr(r), float(flow_scale), lp))
+        _lib.check(loss_entry("b2f_table_loss%s_host", objective)(ptrs, len(tab), n, H, W, int(per == 5), _lib.fptr(r), float(flow_scale), lp, *tail))
     else:
         if per != (5 if model.past_flow else 4) and len(tab) % (5 if model.past_flow else 4) == 0:
             raise ValueError("table_loss: a %s table of %d tensors on a %s model would be read as the model's kind; use a model of the "
                              "table's kind or model=None" % ("Soft" if per == 5 else "Hard", len(tab), "Soft" if model.past_flow else "Hard"))
-        _lib.check(getattr(_lib.lib(), "b2f_op_table_loss" + ft)(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), lp))
+        _lib.check(loss_entry("b2f_op_table_loss%s", objective)(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), lp, *tail))
     return loss
 
 

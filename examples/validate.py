@@ -6,6 +6,10 @@ the occlusion prior, on every level of the output table.  No ground truth is nee
 (Model.forwardLoss); 128 bytes per level and centre frame come back.  --objective NAME prints instead the objective the named model
 was trained on (back2future.LOSS_OBJECTIVES, the commands of the reference's README.md:85-102): for the two Soft models the
 second-order smoothness and the brightness and gradient constancy of OBGCC, from records of 192 bytes (objective="finetune").
+--pme-criterion OSSIM | OSSIML1 replaces the photometric term by the occlusion-aware SSIM (+ L1) term of
+criterions/OSSIML1Criterion.lua, from records of 256 bytes (objective="ssim"); --ssim-range image (the default) normalises every
+triplet by its own minimum and maximum, which does not depend on how the clip is cut into calls; --ssim-range batch takes them over
+the triplets of a call as the reference does over a batch.
 --grad also computes `gradOutputs` of train.lua:428-468, the gradient of the pme objective with respect to every tensor of the output
 table (Model.forwardLossGrad, in the same pass as the records), under the chosen options (--size-average; --objective Ours-Hard --
 --grad refuses the two Soft objectives), and prints per level and tensor its L2 norm and largest magnitude over the clip.  --grad-ft
@@ -13,7 +17,7 @@ does the same with the gradients of SecondOrderSmoothnessCriterion and OBGCCrite
 --objective NAME, or without one both criteria with alpha = beta = gamma = 1; its loss lines come from the 192-byte records.
 
 Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME]
-       [--grad | --grad-ft]
+       [--pme-criterion OSSIM|OSSIML1 [--ssim-range image|batch]] [--grad | --grad-ft]
 FRAMES_DIR: 8-bit frames, sorted by name; they are cropped (top left) to multiples of 64 and normalized with
 back2future.normalize.  MODEL as for examples/run_sequence.py.  --scale: pixels per unit of raw network flow (default 20).
 Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`; with --grad or --grad-ft then one line
@@ -40,13 +44,13 @@ def load_unit(path, H, W):
 
 def main():
     args = list(sys.argv[1:])
-    scale, like, objective = 20.0, "test", None
+    scale, like, objective, criterion, ssim_range = 20.0, "test", None, None, "image"
     size_average, grad_ft = "--size-average" in args, "--grad-ft" in args
     grad = "--grad" in args or grad_ft
     if "--grad" in args and grad_ft:
         sys.exit("--grad and --grad-ft exclude one another")
     args = [a for a in args if a not in ("--size-average", "--grad", "--grad-ft")]
-    for flag in ("--scale", "--like", "--objective"):
+    for flag in ("--scale", "--like", "--objective", "--pme-criterion", "--ssim-range"):
         if flag in args:
             i = args.index(flag)
             try:
@@ -54,6 +58,10 @@ def main():
                     scale = float(args[i + 1])
                 elif flag == "--like":
                     like = args[i + 1]
+                elif flag == "--pme-criterion":
+                    criterion = args[i + 1]
+                elif flag == "--ssim-range":
+                    ssim_range = args[i + 1]
                 else:
                     objective = args[i + 1]
             except (IndexError, ValueError):
@@ -63,6 +71,12 @@ def main():
         sys.exit(__doc__)
     if objective is not None and objective not in back2future.LOSS_OBJECTIVES:
         sys.exit("--objective: one of " + ", ".join(sorted(back2future.LOSS_OBJECTIVES)))
+    if criterion is not None and criterion not in back2future.SSIM_ALPHA:
+        sys.exit("--pme-criterion: one of " + ", ".join(sorted(back2future.SSIM_ALPHA)))
+    if ssim_range not in ("image", "batch"):
+        sys.exit("--ssim-range: image or batch")
+    if criterion is not None and (objective is not None or grad):
+        sys.exit("--pme-criterion goes without --objective, --grad and --grad-ft (the gradient of this criterion is not provided)")
     options = None
     if grad:
         try:
@@ -91,11 +105,15 @@ def main():
             mx = [float(np.abs(t).max()) for t in g]
             sumsq = sq if sumsq is None else [a + b for a, b in zip(sumsq, sq)]
             largest = mx if largest is None else [max(a, b) if a == a and b == b else float("nan") for a, b in zip(largest, mx)]
+        elif criterion is not None:
+            records.append(m.forwardLoss(x, flow_scale=scale, objective="ssim", ssim_range=ssim_range))
         else:
             records.append(m.forwardLoss(x, flow_scale=scale, objective="pme" if objective is None else "finetune"))
     tensors = ("f", "p", "o", "iw1", "iw3") if m.past_flow else ("f", "o", "iw1", "iw3")
     m.close()
-    if grad_ft and objective is None:     # the defaults of loss_grad_ft_options
+    if criterion is not None:
+        s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, pme_criterion=criterion)
+    elif grad_ft and objective is None:     # the defaults of loss_grad_ft_options
         s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, smooth_second_order=True, pme_criterion="OBGCC")
     else:
         s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, objective=objective)

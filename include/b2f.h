@@ -721,6 +721,57 @@ B2F_API int b2f_forward_loss_grad_ft_device(b2f_ctx *ctx, const void *dev_in, in
                                     int n_outs, void *stream);
 B2F_API int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
                                    const b2f_loss_grad_ft_opts *opts, unsigned long long *loss, float *const *grad, int n_outs);
+/* ---- the occlusion-aware SSIM + L1 photometric term: -pme_criterion OSSIM | OSSIML1 (opts.lua:62, model.lua:172-179) ----
+ * criterions/OSSIML1Criterion.lua:47-163 beside the terms above.  The *_ssim entries return records of 32 words per image and level:
+ * words 0 .. 15 are those of b2f_table_loss*, bit for bit, words 16 .. 25 the sums below, words 26 .. 31 are 0.  Same inputs, same fp64
+ * arithmetic without fused multiply-adds, same P1 and q.  Per level j of h x w, image by image:
+ *   range: (mn, mx), two floats, from range_mode --
+ *     B2F_SSIM_RANGE_BATCH  the minimum and maximum over R_j, iw1 and iw3 of all n images of the call (lines 62-67: the reference's);
+ *                           a record then depends on the other images of its call, so the b2f_forward_loss_ssim* entries refuse
+ *                           it when the request would be cut into more than one sub-batch, and b2f_multi_forward_loss_ssim always
+ *     B2F_SSIM_RANGE_IMAGE  the image's own minimum and maximum (the reference's at batch size 1)
+ *     B2F_SSIM_RANGE_GIVEN  ranges[2 j], ranges[2 j + 1]: `ranges` is a host array of L x 2 floats (NULL in the other modes)
+ *     NaNs are skipped, infinities kept, -0 < +0.  The image's own pair is returned in words 24 / 25 in every mode, the pair used in
+ *     words 22 / 23, as float bits.
+ *   t(v) = ((double)v - (double)mn) / ((double)mx - (double)mn)
+ *   window: G(a)(x, y) = (ge * col(x-1) + gc * col(x)) + ge * col(x+1), col(x') = (ge * a(x', y-1) + gc * a(x', y)) + ge * a(x', y+1),
+ *     indices clamped to the plane (SpatialReplicationPadding(1), lines 38-44), so that 1 x 1, 1 x w and h x 1 levels are defined;
+ *     e = exp(-8/9), ge = e / (1 + 2 e), gc = 1 / (1 + 2 e): image.gaussian{size = 3, normalize = true} as restated in
+ *     csrc/b2f_tableloss_ssim.h, which says where the weights come from (b2f_loss_ssim_weights returns ge, gc)
+ *   per direction d (0 the past frame iw1, 1 the future frame iw3) and channel c, x = t(iw_d[c]), y = t(R_j[c]):
+ *     mu_x = G(x), mu_y = G(y), s_x = G(x * x) - mu_x * mu_x, s_y = G(y * y) - mu_y * mu_y, s_xy = G(x * y) - mu_x * mu_y
+ *     l = (2.0 * (mu_x * mu_y) + 1e-4) / ((mu_x * mu_x + mu_y * mu_y) + 1e-4), cs = (2.0 * s_xy + 9e-4) / ((s_x + s_y) + 9e-4)
+ *     S = ((1.0 - l * cs)_0 + (..)_1) + (..)_2, B = (P1(x_0 - y_0) + P1(x_1 - y_1)) + P1(x_2 - y_2)
+ * A pixel-direction that counts in PHOTO_INSIDE adds q(o * S) to SSIM_Q30[d] and q(o * B) to L1N_Q30[d], o = o[1 - d] as above
+ * (S <= 6 and B <= 3 sqrt(1 + 1e-6) on a range that holds the values: q cannot saturate).  If either product is NaN, or the range is
+ * unusable (not mx > mn, or either not finite), it adds to neither and counts in SSIM_NONFINITE[d].  Any other pixel-direction adds
+ * nothing: OUTSIDE and the occlusion weight are those of OBCCriterion (lines 121-151 against OBCCriterion.lua:78-105).  The criterion's
+ * value is sum over d of ((alpha * SSIM_d + (1 - alpha) * L1N_d) / 2^30 + OUTSIDE_d) / (3 * 2) with alpha = 1 (OSSIM) or 0.85 (OSSIML1)
+ * (back2future.loss_summary).  updateGradInput is not provided.                                                                  */
+/* The six b2f_*_loss_ft entries with records of 32 words (256 bytes) and the range: same checks, same sub-batching, same workspaces. */
+B2F_API int b2f_table_loss_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                             double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
+B2F_API int b2f_table_loss_ssim_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                               double flow_scale, unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges);
+B2F_API int b2f_op_table_loss_ssim(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                           double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
+B2F_API int b2f_forward_loss_ssim(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                          float **outs, int n_outs, int range_mode, const float *ranges);
+B2F_API int b2f_forward_loss_ssim_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                 unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges);
+B2F_API int b2f_multi_forward_loss_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                                int range_mode, const float *ranges);
+/* out[0] = ge, out[1] = gc: the 1-D weights of the window */
+B2F_API int b2f_loss_ssim_weights(double out[2]);
+#define B2F_SSIM_RANGE_BATCH 0          /* range_mode: the minimum and maximum over the n images of the call */
+#define B2F_SSIM_RANGE_IMAGE 1          /* each image's own */
+#define B2F_SSIM_RANGE_GIVEN 2          /* ranges[2 j], ranges[2 j + 1] */
+#define B2F_LOSS_SSIM_Q30 16           /* [2] occlusion-weighted sum over the channels of 1 - l * cs, past / future, 2^-30 */
+#define B2F_LOSS_SSIM_L1N_Q30 18       /* [2] occlusion-weighted L1 penalty of the range-normalised difference */
+#define B2F_LOSS_SSIM_NONFINITE 20     /* [2] pixel-directions of PHOTO_INSIDE with a NaN product or an unusable range */
+#define B2F_LOSS_SSIM_RANGE_USED 22    /* [2] float bits, zero-extended, of the mn / mx used for this image and level */
+#define B2F_LOSS_SSIM_RANGE_OWN 24     /* [2] float bits of this image's own minimum / maximum at this level */
+#define B2F_LOSS_SSIM_WORDS 32         /* words 26 .. 31 are reserved, always 0 */
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature

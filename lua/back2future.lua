@@ -161,6 +161,19 @@ int b2f_forward_loss_ft(b2f_ctx *ctx, const float *x, int n, int H, int W, doubl
                         float **outs, int n_outs);
 int b2f_forward_loss_ft_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                                unsigned long long *dev_loss, void *stream);
+/* ... with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua in words 16 .. 25 of records of 32 words (include/b2f.h, B2F_LOSS_SSIM_*);
+   range_mode: 0 the batch's range, 1 each image's own, 2 `ranges` (L x 2 floats) */
+int b2f_table_loss_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                             double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
+int b2f_table_loss_ssim_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                               double flow_scale, unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges);
+int b2f_op_table_loss_ssim(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                           double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
+int b2f_forward_loss_ssim(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                          float **outs, int n_outs, int range_mode, const float *ranges);
+int b2f_forward_loss_ssim_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                 unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges);
+int b2f_loss_ssim_weights(double out[2]);
 /* the gradient of the pme objective with respect to the output table: gradOutputs of train.lua:279-472 (include/b2f.h) */
 typedef struct b2f_loss_grad_opts {
     double smooth_flow, const_vel, pme, smooth_occ, prior_occ;
@@ -247,6 +260,8 @@ int b2f_multi_compute_flow_sequence_warp_past(b2f_multi *m, int T, int in_kind, 
                                               unsigned char *bwd_occ);
 int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
 int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss);
+int b2f_multi_forward_loss_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                                int range_mode, const float *ranges);
 int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
                                 const b2f_loss_grad_opts *opts, unsigned long long *loss, float *const *grad, int n_outs);
 int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
