@@ -295,14 +295,8 @@ static hipError_t launch_t(const ConvLaunch &p, hipStream_t s)
 {
     using G = ConvGeom<S, TW, NW>;
     const size_t lds = 2 * sizeof(f32x4) * (G::A_F4 + 9 * 2 * NT * 32);
-    static bool attr_done_dev[64] = {false};
-    bool &attr_done = attr_done_dev[attr_slot()];   // one flag per template instance
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_mfma<S, NT, TW, NW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    static LdsOnce once;   // one per template instance
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_mfma<S, NT, TW, NW>), (int)lds)) return e;
     const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + G::TH - 1) / G::TH;
     const int ntiles = tiles_x * tiles_y * p.nimg;
     // tiles per block: shallow layers (few K chunks) of launches with many rounds of blocks chain tiles into one pipeline

@@ -152,21 +152,14 @@ bool c16_supported(const ConvLaunch &p)
 }
 
 // persistent launch shared by the two kernels of this file: BPC blocks per CU (fewer when the launch has fewer tiles)
-template <typename K>
-static hipError_t launch_persistent(K kernel, const ConvLaunch &p, int tiles_x, int tiles_y, int lds_bytes, int bpc, bool &attr_done, int &n_cu, hipStream_t s)
+template <auto kernel>
+static hipError_t launch_persistent(const ConvLaunch &p, int tiles_x, int tiles_y, int lds_bytes, int bpc, hipStream_t s)
 {
     const int ntiles = tiles_x * tiles_y * p.nimg;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    if (!n_cu) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        n &= ~7;                                  // the XCD banding of the logical tile index wants a multiple of 8
-        n_cu = n < 8 ? 8 : n;
-    }
+    static LdsOnce once;   // one per kernel
+    const int slot = current_device_slot();
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(kernel), lds_bytes, slot)) return e;
+    const int n_cu = persistent_block_cap(slot);   // the XCD banding of the logical tile index wants a multiple of 8
     int grid = bpc * n_cu < ntiles ? bpc * n_cu : ntiles;
     if (grid >= 8) grid &= ~7;
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds_bytes, s, p, ntiles, tiles_x, tiles_y);
@@ -179,11 +172,7 @@ hipError_t launch_conv3x3_c16(const ConvLaunch &p, hipStream_t s)
 #if B2F_EXPERIMENTS
     if (p.bf16_direct) return launch_conv3x3_c16b(p, s);
 #endif
-    static bool attr_done_dev[64] = {false};
-    static int n_cu_dev[64] = {0};
-    const int slot = attr_slot();
-    return launch_persistent(conv3x3_c16_kernel, p, (p.W + c16::TW - 1) / c16::TW, (p.H + c16::TH - 1) / c16::TH, c16::LDS_BYTES, 2,
-                             attr_done_dev[slot], n_cu_dev[slot], s);
+    return launch_persistent<conv3x3_c16_kernel>(p, (p.W + c16::TW - 1) / c16::TW, (p.H + c16::TH - 1) / c16::TH, c16::LDS_BYTES, 2, s);
 }
 
 size_t c16_wpk_floats() { return 9 * 4 * 16 * 4; }
@@ -361,11 +350,8 @@ bool c16s2_supported(const ConvLaunch &p)
 hipError_t launch_conv3x3_c16s2(const ConvLaunch &p, hipStream_t s)
 {
     if (!c16s2_supported(p)) return hipErrorInvalidValue;
-    static bool attr_done_dev[64] = {false};
-    static int n_cu_dev[64] = {0};
-    const int slot = attr_slot();
-    return launch_persistent(conv3x3_c16s2_kernel, p, (p.Wo + c16s2::TW - 1) / c16s2::TW, (p.Ho + c16s2::TH - 1) / c16s2::TH, c16s2::LDS_BYTES,
-                             c16s2::BLOCKS_PER_CU, attr_done_dev[slot], n_cu_dev[slot], s);
+    return launch_persistent<conv3x3_c16s2_kernel>(p, (p.Wo + c16s2::TW - 1) / c16s2::TW, (p.Ho + c16s2::TH - 1) / c16s2::TH, c16s2::LDS_BYTES,
+                                                   c16s2::BLOCKS_PER_CU, s);
 }
 
 size_t c16s2_wpk_floats() { return 9 * 2 * 4 * 16 * 4; }

@@ -272,13 +272,8 @@ template <int S, int NT, bool DB>
 static hipError_t convb_launch_t(const ConvLaunch &p, int nb0, int nblk, hipStream_t s)
 {
     using G = ConvbGeom<S>;
-    static bool attr_done_dev[64] = {false};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_bf6<S, NT, DB>), hipFuncAttributeMaxDynamicSharedMemorySize, (DB ? 2 : 1) * G::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    static LdsOnce once;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_bf6<S, NT, DB>), (DB ? 2 : 1) * G::LDS_BYTES)) return e;
     const int tiles = ((p.Wo + G::TW - 1) / G::TW) * ((p.Ho + G::TH - 1) / G::TH);
     ConvLaunch q = p;
     q.nb0 = nb0;

@@ -1164,42 +1164,36 @@ bool warp_costvol_unit_supported(const CorrLaunch &p)
            (double)p.h * p.w * p.out_pix_stride * 4.0 < 2147483648.0;
 }
 
-#if B2F_EXPERIMENTS
-hipError_t launch_warp_costvol_spec(const CorrLaunch &p, hipStream_t s)
+// what the stage trace of a profiling build (B2F_C5_TRACE) prints for one kernel
+struct C5TraceText { const char *label, *columns, *wave[4]; };
+
+// persistent launch shared by the kernels of this file: KP / KA = the instantiation for a power-of-two C / for any C, `bpc` blocks per CU
+// (fewer when the launch has fewer (tile, direction) items).  Callers name <true> before <false>: the order of first use is the
+// order of the kernels in the device code, which tools/device_code_diff.py compares byte for byte.
+template <auto KP, auto KA>
+static hipError_t launch_c5(const CorrLaunch &p, int nthr, int lds_bytes, int bpc, const C5TraceText *tr, hipStream_t s)
 {
     using namespace v5;
     if (!warp_costvol_unit_supported(p)) return hipErrorInvalidValue;
-    static bool attr_done_dev[64][2] = {{false}};
-    static int n_cu_dev[64] = {0};
-    const int slot = attr_slot();
+    static LdsOnce once[2];
+    const int slot = current_device_slot();
     const bool pow2 = (p.C & (p.C - 1)) == 0;
-    if (!attr_done_dev[slot][pow2 ? 1 : 0]) {
-        const void *fn = pow2 ? reinterpret_cast<const void *>(&warp_costvol_spec_kernel<true>) : reinterpret_cast<const void *>(&warp_costvol_spec_kernel<false>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, v6::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done_dev[slot][pow2 ? 1 : 0] = true;
-    }
-    if (!n_cu_dev[slot]) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        n &= ~7;
-        n_cu_dev[slot] = n < 8 ? 8 : n;
-    }
+    if (hipError_t e = once[pow2].ensure(pow2 ? reinterpret_cast<const void *>(KP) : reinterpret_cast<const void *>(KA), lds_bytes, slot)) return e;
     const int tiles_x = (p.w + TW - 1) / TW, tiles_y = (p.h + TH - 1) / TH;
     const int ntd = 2 * tiles_x * tiles_y * p.B;
-    int grid = n_cu_dev[slot] < ntd ? n_cu_dev[slot] : ntd;
+    const int cap = bpc * persistent_block_cap(slot);   // the XCD banding of the logical index wants a multiple of 8
+    int grid = cap < ntd ? cap : ntd;
     if (grid >= 8) grid &= ~7;
-    if (pow2) hipLaunchKernelGGL((warp_costvol_spec_kernel<true>), dim3((unsigned)grid), dim3(v6::NTHR), v6::LDS_BYTES, s, p, ntd, tiles_x, tiles_y);
-    else hipLaunchKernelGGL((warp_costvol_spec_kernel<false>), dim3((unsigned)grid), dim3(v6::NTHR), v6::LDS_BYTES, s, p, ntd, tiles_x, tiles_y);
+    if (pow2) hipLaunchKernelGGL(KP, dim3((unsigned)grid), dim3((unsigned)nthr), lds_bytes, s, p, ntd, tiles_x, tiles_y);
+    else hipLaunchKernelGGL(KA, dim3((unsigned)grid), dim3((unsigned)nthr), lds_bytes, s, p, ntd, tiles_x, tiles_y);
 #if B2F_C5_TRACE
     static int traced = 0;
-    if (ntd / grid >= 50 && traced++ == 2) {
+    if (tr && ntd / grid >= 50 && traced++ == 2) {
         static long long h[4 * 64 * 8];
         hipStreamSynchronize(s);
         hipMemcpyFromSymbol(h, HIP_SYMBOL(c5_trace_buf), sizeof h);
-        const char *nm[4] = {"F wave 0", "F wave 3", "G wave 4", "G wave 7"};
         for (int w = 0; w < 4; ++w) {
-            fprintf(stderr, "c6 trace %s (C %d, %d x %d): per stage, cycles: top | G: window DMA + flows | ref DMA | blend (F: FMAs) | records | vmcnt(0) (F: stores) | barrier\n", nm[w], p.C, p.h, p.w);
+            fprintf(stderr, "%s trace %s (C %d, %d x %d): per stage, cycles: %s\n", tr->label, tr->wave[w], p.C, p.h, p.w, tr->columns);
             for (int st = 1; st < 24; ++st) {
                 const long long *t = h + (w * 64 + st) * 8, *tp = h + (w * 64 + st - 1) * 8;
                 fprintf(stderr, "  stage %2d  %6lld |", st, t[0] - tp[6]);
@@ -1208,87 +1202,31 @@ hipError_t launch_warp_costvol_spec(const CorrLaunch &p, hipStream_t s)
             }
         }
     }
+#else
+    (void)tr;
 #endif
     return hipGetLastError();
 }
 
+#if B2F_EXPERIMENTS
+hipError_t launch_warp_costvol_spec(const CorrLaunch &p, hipStream_t s)
+{
+    static const C5TraceText tr = {"c6", "top | G: window DMA + flows | ref DMA | blend (F: FMAs) | records | vmcnt(0) (F: stores) | barrier",
+                                   {"F wave 0", "F wave 3", "G wave 4", "G wave 7"}};
+    return launch_c5<&warp_costvol_spec_kernel<true>, &warp_costvol_spec_kernel<false>>(p, v6::NTHR, v6::LDS_BYTES, 1, &tr, s);
+}
 #endif  // B2F_EXPERIMENTS
 
 hipError_t launch_warp_costvol_gw(const CorrLaunch &p, hipStream_t s)
 {
-    using namespace v5;
-    if (!warp_costvol_unit_supported(p)) return hipErrorInvalidValue;
-    static bool attr_done_dev[64][2] = {{false}};
-    static int n_cu_dev[64] = {0};
-    const int slot = attr_slot();
-    const bool pow2 = (p.C & (p.C - 1)) == 0;
-    if (!attr_done_dev[slot][pow2 ? 1 : 0]) {
-        const void *fn = pow2 ? reinterpret_cast<const void *>(&warp_costvol_gw_kernel<true>) : reinterpret_cast<const void *>(&warp_costvol_gw_kernel<false>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, v7::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done_dev[slot][pow2 ? 1 : 0] = true;
-    }
-    if (!n_cu_dev[slot]) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        n &= ~7;
-        n_cu_dev[slot] = n < 8 ? 8 : n;
-    }
-    const int tiles_x = (p.w + TW - 1) / TW, tiles_y = (p.h + TH - 1) / TH;
-    const int ntd = 2 * tiles_x * tiles_y * p.B;
-    int grid = n_cu_dev[slot] < ntd ? n_cu_dev[slot] : ntd;
-    if (grid >= 8) grid &= ~7;
-    if (pow2) hipLaunchKernelGGL((warp_costvol_gw_kernel<true>), dim3((unsigned)grid), dim3(v7::NTHR), v7::LDS_BYTES, s, p, ntd, tiles_x, tiles_y);
-    else hipLaunchKernelGGL((warp_costvol_gw_kernel<false>), dim3((unsigned)grid), dim3(v7::NTHR), v7::LDS_BYTES, s, p, ntd, tiles_x, tiles_y);
-    return hipGetLastError();
+    return launch_c5<&warp_costvol_gw_kernel<true>, &warp_costvol_gw_kernel<false>>(p, v7::NTHR, v7::LDS_BYTES, 1, nullptr, s);
 }
 
 hipError_t launch_warp_costvol_unit(const CorrLaunch &p, hipStream_t s)
 {
-    using namespace v5;
-    constexpr int U_LDS = LDS_BYTES - (B2F_C5_WINDOW ? 0 : 16 * 2 * WIN_F4);
-    if (!warp_costvol_unit_supported(p)) return hipErrorInvalidValue;
-    static bool attr_done_dev[64][2] = {{false}};
-    static int n_cu_dev[64] = {0};
-    const int slot = attr_slot();
-    const bool pow2 = (p.C & (p.C - 1)) == 0;
-    if (!attr_done_dev[slot][pow2 ? 1 : 0]) {
-        const void *fn = pow2 ? reinterpret_cast<const void *>(&warp_costvol_unit_kernel<true>) : reinterpret_cast<const void *>(&warp_costvol_unit_kernel<false>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, U_LDS);
-        if (e != hipSuccess) return e;
-        attr_done_dev[slot][pow2 ? 1 : 0] = true;
-    }
-    if (!n_cu_dev[slot]) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        n &= ~7;                                  // the XCD banding of the logical index wants a multiple of 8
-        n_cu_dev[slot] = n < 8 ? 8 : n;
-    }
-    const int tiles_x = (p.w + TW - 1) / TW, tiles_y = (p.h + TH - 1) / TH;
-    const int ntd = 2 * tiles_x * tiles_y * p.B;
-    int grid = B2F_C5_BLOCKS * n_cu_dev[slot] < ntd ? B2F_C5_BLOCKS * n_cu_dev[slot] : ntd;
-    if (grid >= 8) grid &= ~7;
-    if (pow2) hipLaunchKernelGGL((warp_costvol_unit_kernel<true>), dim3((unsigned)grid), dim3(NTHR), U_LDS, s, p, ntd, tiles_x, tiles_y);
-    else hipLaunchKernelGGL((warp_costvol_unit_kernel<false>), dim3((unsigned)grid), dim3(NTHR), U_LDS, s, p, ntd, tiles_x, tiles_y);
-#if B2F_C5_TRACE
-    static int traced = 0;
-    if (ntd / grid >= 50 && traced++ == 2) {
-        static long long h[4 * 64 * 8];
-        hipStreamSynchronize(s);
-        hipMemcpyFromSymbol(h, HIP_SYMBOL(c5_trace_buf), sizeof h);
-        const char *nm[4] = {"wave 0", "wave 4", "wave 9", "wave 10 (aux)"};
-        for (int w = 0; w < 4; ++w) {
-            fprintf(stderr, "c5 trace %s (C %d, %d x %d): per stage, cycles: top | DMA issue | blend | FMAs / records | vmcnt(0) | stores | barrier\n", nm[w], p.C, p.h, p.w);
-            for (int st = 1; st < 24; ++st) {
-                const long long *t = h + (w * 64 + st) * 8, *tp = h + (w * 64 + st - 1) * 8;
-                fprintf(stderr, "  stage %2d  %6lld |", st, t[0] - tp[6]);
-                for (int q = 1; q <= 6; ++q) fprintf(stderr, " %6lld", t[q] - t[q - 1]);
-                fprintf(stderr, "   total %6lld\n", t[6] - tp[6]);
-            }
-        }
-    }
-#endif
-    return hipGetLastError();
+    constexpr int U_LDS = v5::LDS_BYTES - (B2F_C5_WINDOW ? 0 : 16 * 2 * v5::WIN_F4);
+    static const C5TraceText tr = {"c5", "top | DMA issue | blend | FMAs / records | vmcnt(0) | stores | barrier", {"wave 0", "wave 4", "wave 9", "wave 10 (aux)"}};
+    return launch_c5<&warp_costvol_unit_kernel<true>, &warp_costvol_unit_kernel<false>>(p, v5::NTHR, U_LDS, B2F_C5_BLOCKS, &tr, s);
 }
 
 }  // namespace b2f

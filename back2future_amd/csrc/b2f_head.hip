@@ -293,13 +293,8 @@ bool head16_supported(const HeadLaunch &p)
 hipError_t launch_conv_head16(HeadLaunch p, hipStream_t s)
 {
     using namespace head;
-    static bool attr_done_dev[64] = {false};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_head16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    static LdsOnce once;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv_head16_kernel), LDS_BYTES)) return e;
     p.nsx = (p.Wo + WO - 1) / WO;
     // cut every strip into row blocks so that the launch has at least ~6 blocks per CU slot pair (two blocks per CU); a block
     // recomputes one intermediate row at its top, so not finer than 16 rows

@@ -9,6 +9,7 @@
 #ifndef B2F_EXPERIMENTS
 #define B2F_EXPERIMENTS 0
 #endif
+#include <atomic>
 #include <cstdint>
 
 namespace b2f {
@@ -208,27 +209,58 @@ struct CorrLaunch {
     int ablate = 0;                          // profiling only (option corr_ablate): 1 no gather loads, 2 no FMAs, 4 no stores, 8 no XCD remap
     int variant = -1;                        // -1 auto, 0 regular, 1 latency, 2 two-pixel, 3 two-pixel one-direction-per-block instantiation (same bits)
 };
-// hipFuncSetAttribute is per device: launchers keep one "done" flag per device (b2f_init_multi drives several GPUs from one
-// process, one worker thread each); returns the slot of the current device
-inline int attr_slot()
+// ---- per-device launcher setup ------------------------------------------------------
+// What a launcher knows about "the current device" is cached per device ordinal, in atomics: b2f_init_multi drives several GPUs
+// (or one GPU several times) from one process, one worker thread each, and those threads meet in the same launchers.  A launcher
+// asks for the slot once and hands it to the calls below: one hipGetDevice per launch once the device's slot is filled.  The
+// first use on a device, and every use on a device without a slot, asks again inside device_cu_count.
+constexpr int kMaxDeviceSlots = 64;
+// slot of the current device: its ordinal; 0 when hipGetDevice fails (that call then has nothing better, and the launch reports
+// the error); -1 for an ordinal past the tables, which is looked up every time and never cached
+inline int current_device_slot()
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-    return dev & 63;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
+    return dev < kMaxDeviceSlots ? dev : -1;
 }
-// compute units of the current device (cached per device; 256 on an MI355X in SPX mode, fewer in a partition mode): the launchers'
-// "does this launch fit in one round of blocks" thresholds scale with it
-inline int device_cu_count()
+// compute units of the current device (256 on an MI355X in SPX mode, fewer in a partition mode; 256 when the query fails, at least
+// 8): the launchers' "does this launch fit in one round of blocks" thresholds scale with it
+inline int device_cu_count(int slot = current_device_slot())
 {
-    static int n_cu_dev[64] = {0};
-    int &n = n_cu_dev[attr_slot()];
+    static std::atomic<int> n_cu_dev[kMaxDeviceSlots];   // static storage: zero = not asked yet
+    int n = slot >= 0 ? n_cu_dev[slot].load(std::memory_order_relaxed) : 0;
     if (!n) {
         int dev = 0, v = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         n = v < 8 ? 8 : v;
+        if (slot >= 0) n_cu_dev[slot].store(n, std::memory_order_relaxed);
     }
     return n;
 }
+// grid of a persistent kernel: one block per CU, a multiple of 8 for the XCD remap (at least 8, as the CU count is)
+inline int persistent_block_cap(int slot = current_device_slot()) { return device_cu_count(slot) & ~7; }
+// A kernel that needs more than the default dynamic LDS is told so once per device (hipFuncSetAttribute is per device).  One
+// LdsOnce per kernel instantiation, a function-local static of its launcher:
+//     static LdsOnce once;
+//     if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&kernel), LDS_BYTES, slot)) return e;
+// A slot that is done costs one acquire load.  A failed call leaves the slot open, so the next launch tries again.  Two threads
+// that meet on a first use may both make the (idempotent) call.
+class LdsOnce {
+    std::atomic<bool> done[kMaxDeviceSlots];   // objects of static storage only: zero-initialised
+public:
+    // the once-logic by itself (tools/launch_once_tsan.cpp runs it without HIP): set() returns hipSuccess or an error
+    template <class Set> hipError_t ensure_with(int slot, Set &&set)
+    {
+        if (slot >= 0 && done[slot].load(std::memory_order_acquire)) return hipSuccess;
+        const hipError_t e = set();
+        if (e == hipSuccess && slot >= 0) done[slot].store(true, std::memory_order_release);
+        return e;
+    }
+    hipError_t ensure(const void *kernel, int lds_bytes, int slot = current_device_slot())
+    {
+        return ensure_with(slot, [&] { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); });
+    }
+};
 // n / d without a division: mul = floor(2^sh / d) + 1 with sh = 31 + ceil(log2 d) fits 32 bits, and (n * mul) >> sh == n / d for every
 // 0 <= n < 2^31 (the error of mul, e = mul * d - 2^sh, lies in (0, d], and n * e < 2^31 * 2^ceil(log2 d) = 2^sh)
 inline void w6_div_magic(int d, unsigned *mul, int *sh)

@@ -333,15 +333,10 @@ bool s2b_supported(const ConvLaunch &p)
 }
 
 template <int MTC, int NTC>
-static hipError_t s2b_launch_t(const ConvLaunch &p, int grid, hipStream_t s)
+static hipError_t s2b_launch_t(const ConvLaunch &p, int grid, int slot, hipStream_t s)
 {
-    static bool attr_done_dev[64] = {false};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&s2b::conv3x3_s2b<MTC, NTC>), hipFuncAttributeMaxDynamicSharedMemorySize, s2b::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    static LdsOnce once;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&s2b::conv3x3_s2b<MTC, NTC>), s2b::LDS_BYTES, slot)) return e;
     hipLaunchKernelGGL((s2b::conv3x3_s2b<MTC, NTC>), dim3((unsigned)grid), dim3(512), s2b::LDS_BYTES, s, p);
     return hipGetLastError();
 }
@@ -350,16 +345,9 @@ hipError_t launch_conv3x3_s2b(const ConvLaunch &p, hipStream_t s)
 {
     using namespace s2b;
     if (!s2b_supported(p)) return hipErrorInvalidValue;
-    static int n_cu_dev[64] = {0};
-    int &n_cu = n_cu_dev[attr_slot()];
-    if (!n_cu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-        n_cu &= ~7;
-        if (n_cu < 8) n_cu = 8;
-    }
+    const int slot = current_device_slot();
     const int total = ((p.Wo + TW - 1) / TW) * ((p.Ho + TH - 1) / TH) * p.nimg;
-    const int cap = p.w4_persist > 1 ? p.w4_persist : n_cu;          // tests: exactly that many blocks
+    const int cap = p.w4_persist > 1 ? p.w4_persist : persistent_block_cap(slot);   // tests: exactly that many blocks
     const int grid = total < cap ? total : cap;
     const int NT = s2b_ntiles(p.cout);
     // consumers: two output-tile groups x two pixel-tile groups for <= 2 output tiles, four output tiles (each consumer all four pixel
@@ -372,12 +360,12 @@ hipError_t launch_conv3x3_s2b(const ConvLaunch &p, hipStream_t s)
         const int gp = total * NT <= cap ? total : (cap / NT > 0 ? cap / NT : 1);
         q.nb0 = 0;
         q.nsplit = NT;
-        return s2b_launch_t<1, 1>(q, gp * NT, s);
+        return s2b_launch_t<1, 1>(q, gp * NT, slot, s);
     }
-    if (NT <= 2) { q.nb0 = 0; return s2b_launch_t<2, 1>(q, grid, s); }
+    if (NT <= 2) { q.nb0 = 0; return s2b_launch_t<2, 1>(q, grid, slot, s); }
     for (int t0 = 0; t0 < NT; t0 += 4) {
         q.nb0 = t0;
-        hipError_t e = s2b_launch_t<4, 1>(q, grid, s);
+        hipError_t e = s2b_launch_t<4, 1>(q, grid, slot, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

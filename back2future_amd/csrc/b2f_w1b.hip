@@ -506,24 +506,14 @@ hipError_t launch_conv3x3_w1b(const ConvLaunch &p, hipStream_t s)
 {
     using namespace w1b;
     if (!w1b_supported(p)) return hipErrorInvalidValue;
-    static bool attr_done_dev[64] = {false};
-    static int n_cu_dev[64] = {0};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    int &n_cu = n_cu_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_w1b), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-        n_cu &= ~7;                         // the XCD remap of the virtual block index wants a multiple of 8
-        if (n_cu < 8) n_cu = 8;
-        attr_done = true;
-    }
+    static LdsOnce once;
+    const int slot = current_device_slot();
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_w1b), LDS_BYTES, slot)) return e;
     ConvLaunch q = p;
     q.nblk = p.w1b_nblk > 0 ? p.w1b_nblk : w1b_nblk(p.cout);
     q.nb0 = 0;
     const int total = ((p.Wo + TW - 1) / TW) * ((p.Ho + TH - 1) / TH) * p.nimg * q.nblk;
-    const int cap = p.w4_persist > 1 ? p.w4_persist : n_cu;          // tests: exactly that many blocks
+    const int cap = p.w4_persist > 1 ? p.w4_persist : persistent_block_cap(slot);   // tests: exactly that many blocks
     const int grid = total < cap ? total : cap;
 #if B2F_W1B_TRACE
     static long long *trace_dev = nullptr;

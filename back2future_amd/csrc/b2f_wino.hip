@@ -544,18 +544,13 @@ __global__ __launch_bounds__(512) void conv3x3_wino8(const ConvLaunch p)
 }
 
 template <int NT>
-static hipError_t launch_wino8_t(const ConvLaunch &p, int nb0, int nblk, hipStream_t s)
+static hipError_t launch_wino8_t(const ConvLaunch &p, int nb0, int nblk, int slot, hipStream_t s)
 {
     using namespace wino;
     constexpr int stage = 16 * (2 * V_F4 + 2 * RAW_F4), xch = 16 * 32 * (32 + 8) * 4;
     constexpr int lds = stage > xch ? stage : xch;
-    static bool attr_done_dev[64] = {false};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wino8<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    static LdsOnce once;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_wino8<NT>), lds, slot)) return e;
     ConvLaunch q = p;
     q.nb0 = nb0;
     q.nsplit = NT == 2 ? p.nsplit : 0;
@@ -567,18 +562,12 @@ static hipError_t launch_wino8_t(const ConvLaunch &p, int nb0, int nblk, hipStre
 }
 
 template <int NT, int NTV>
-static hipError_t launch_wino_t(const ConvLaunch &p, int nb0, int nblk, hipStream_t s)
+static hipError_t launch_wino_t(const ConvLaunch &p, int nb0, int nblk, int slot, hipStream_t s)
 {
     using namespace wino;
     constexpr int lds = lds_bytes(NT);
-    static bool attr_done_dev[64] = {false};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wino<NT, NTV>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    static LdsOnce once;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_wino<NT, NTV>), lds, slot)) return e;
     ConvLaunch q = p;
     q.nb0 = nb0;
     q.nsplit = (NT == 2 && NTV == 1) ? p.nsplit : 0;
@@ -626,19 +615,20 @@ hipError_t launch_conv3x3_wino(const ConvLaunch &p, hipStream_t s)
     // one-N-tile launches of at most one block per CU: the eight-wave form (same bits; p.w8 = 0 switches it off)
     const long tiles8 = (long)((p.Wo + wino::TW - 1) / wino::TW) * ((p.Ho + wino::TH - 1) / wino::TH) * p.nimg;
     const bool w8 = p.w8 != 0;
-    const long n_cu = device_cu_count();
-    if (p.nt == 1) return (w8 && tiles8 * p.nblk <= n_cu) ? launch_wino8_t<1>(p, 0, p.nblk, s) : launch_wino_t<1, 1>(p, 0, p.nblk, s);
+    const int slot = current_device_slot();
+    const long n_cu = device_cu_count(slot);
+    if (p.nt == 1) return (w8 && tiles8 * p.nblk <= n_cu) ? launch_wino8_t<1>(p, 0, p.nblk, slot, s) : launch_wino_t<1, 1>(p, 0, p.nblk, slot, s);
     if (p.nt != 2) return hipErrorInvalidValue;
     if (p.nsplit) {   // one block per 32 outputs
         const int n32 = (p.cout + 31) / 32;
-        return (w8 && tiles8 * n32 <= n_cu) ? launch_wino8_t<2>(p, 0, n32, s) : launch_wino_t<2, 1>(p, 0, n32, s);
+        return (w8 && tiles8 * n32 <= n_cu) ? launch_wino8_t<2>(p, 0, n32, slot, s) : launch_wino_t<2, 1>(p, 0, n32, slot, s);
     }
     // n-blocks whose two N tiles both hold real channels, then the half-empty last one (cout = 96)
     const int nfull = p.cout / 64, part = (p.cout % 64) ? 1 : 0;
     const bool part_full = (p.cout % 64) > 32;
     hipError_t e = hipSuccess;
-    if (nfull + (part_full ? 1 : 0) > 0) e = launch_wino_t<2, 2>(p, 0, nfull + (part_full ? 1 : 0), s);
-    if (e == hipSuccess && part && !part_full) e = (w8 && tiles8 <= n_cu) ? launch_wino8_t<2>(p, nfull, 1, s) : launch_wino_t<2, 1>(p, nfull, 1, s);
+    if (nfull + (part_full ? 1 : 0) > 0) e = launch_wino_t<2, 2>(p, 0, nfull + (part_full ? 1 : 0), slot, s);
+    if (e == hipSuccess && part && !part_full) e = (w8 && tiles8 <= n_cu) ? launch_wino8_t<2>(p, nfull, 1, slot, s) : launch_wino_t<2, 1>(p, nfull, 1, slot, s);
     return e;
 }
 

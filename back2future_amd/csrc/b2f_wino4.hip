@@ -1454,14 +1454,9 @@ template <int NTV>
 static hipError_t launch_wino4_t(const ConvLaunch &p, int nb0, int nblk, hipStream_t s)
 {
     using namespace wino4;
-    static bool attr_done_dev[64] = {false};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wino4<NTV>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    static LdsOnce once, once_p;   // the one-tile form, the persistent form
+    const int slot = current_device_slot();
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_wino4<NTV>), LDS_BYTES, slot)) return e;
     ConvLaunch q = p;
     q.nb0 = nb0;
     q.trace = nullptr;
@@ -1489,34 +1484,20 @@ static hipError_t launch_wino4_t(const ConvLaunch &p, int nb0, int nblk, hipStre
     dim3 grid((unsigned)(tiles * p.nimg * nblk));
     if (p.w4_persist) {
         // persistent form
-        static int n_cu_dev[64] = {0};                  // per device, like the attribute flags (b2f_init_multi: one worker thread per GPU)
-        static bool pattr_done_dev[64] = {false};
-        bool &pattr_done = pattr_done_dev[attr_slot()];
-        int &n_cu = n_cu_dev[attr_slot()];
-        if (!n_cu) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-            n_cu &= ~7;                     // the XCD remap of the virtual block index needs a multiple of 8
-            if (n_cu < 8) n_cu = 8;
-        }
         // one block per CU (fewer when the launch has fewer tiles); w4_persist > 1 (tests): exactly that many blocks.
         // Round 3: every launch whose K loop is long enough for the prologue (4 chunks = 32 input channels) runs the persistent
         // form -- with the row-pair input transform the one-tile two-N-tile kernel no longer fits its 256 registers (22
         // spills, reloaded behind vmcnt(0)); it remains the path of shallower layers and of wino4_persistent = 0, bit-identical.
-        const int pcap = p.w4_persist > 1 ? p.w4_persist : n_cu;
+        const int pcap = p.w4_persist > 1 ? p.w4_persist : persistent_block_cap(slot);   // a multiple of 8: the XCD remap of the virtual block index needs it
         const int pgrid = pcap < (int)grid.x ? pcap : (int)grid.x;
         const int nchunks_p = p.seg[0].nchunks + (p.nseg > 1 ? p.seg[1].nchunks : 0);
         if (nchunks_p >= 4) {
-            if (!pattr_done) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wino4p<NTV>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES + 2304 * B2F_WINO_TRACE);
-                if (e != hipSuccess) return e;
-                pattr_done = true;
-            }
+            if (hipError_t e = once_p.ensure(reinterpret_cast<const void *>(&conv3x3_wino4p<NTV>), P_LDS_BYTES + 2304 * B2F_WINO_TRACE, slot)) return e;
             // hybrid forms (two-N-tile blocks with the split packing): p.w4_hybrid = number of bf16 steps per wave
 #if B2F_EXPERIMENTS
             if (NTV == 2 && p.wpk_split && p.w4_hybrid > 0) {
                 auto go = [&](auto kern) -> hipError_t {
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES + 2304 * B2F_WINO_TRACE);
+                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES + 2304 * B2F_WINO_TRACE);   // every launch: experiments only
                     if (e != hipSuccess) return e;
                     hipLaunchKernelGGL(kern, dim3((unsigned)pgrid), dim3(512), P_LDS_BYTES + 2304 * B2F_WINO_TRACE, s, q);
                     hipError_t le = hipGetLastError();

@@ -732,19 +732,9 @@ template <int NT>
 static hipError_t launch_wino6_t(const ConvLaunch &p, int nb0, int nblk, hipStream_t s)
 {
     using namespace wino6;
-    static bool attr_done_dev[64] = {false};
-    static int n_cu_dev[64] = {0};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    int &n_cu = n_cu_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wino6<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-        n_cu &= ~7;                         // the XCD remap of the virtual block index wants a multiple of 8
-        if (n_cu < 8) n_cu = 8;
-        attr_done = true;
-    }
+    static LdsOnce once;
+    const int slot = current_device_slot();
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_wino6<NT>), LDS_BYTES, slot)) return e;
     ConvLaunch q = p;
     q.wpk = reinterpret_cast<const float *>(p.wpk_w6);
     q.bias = p.bias_w6;
@@ -770,7 +760,7 @@ static hipError_t launch_wino6_t(const ConvLaunch &p, int nb0, int nblk, hipStre
     q.w8 = do_trace ? 77 : 0;            // (the kernel does not read w8: marks the traced launch)
 #endif
     const long items = (long)((p.Wo + OW - 1) / OW) * ((p.Ho + OH - 1) / OH) * p.nimg * nblk;
-    const int pcap = p.w4_persist > 1 ? p.w4_persist : n_cu;               // (tests: exactly that many blocks)
+    const int pcap = p.w4_persist > 1 ? p.w4_persist : persistent_block_cap(slot);   // (tests: exactly that many blocks)
     const int grid = (int)(items < pcap ? items : pcap);
     hipLaunchKernelGGL((conv3x3_wino6<NT>), dim3((unsigned)grid), dim3(512), LDS_BYTES, s, q);
 #if W6_TRACE

@@ -168,24 +168,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16b_kernel(const ConvLaunch p
 hipError_t launch_conv3x3_c16b(const ConvLaunch &p, hipStream_t s)
 {
     using namespace c16b;
-    static bool attr_done_dev[64] = {false};
-    static int n_cu_dev[64] = {0};
-    const int slot = attr_slot();
-    bool &attr_done = attr_done_dev[slot];
-    int &n_cu = n_cu_dev[slot];
+    static LdsOnce once;
+    const int slot = current_device_slot();
     const int tiles_x = (p.W + TW - 1) / TW, tiles_y = (p.H + TH - 1) / TH;
     const int ntiles = tiles_x * tiles_y * p.nimg;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_c16b_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    if (!n_cu) {
-        int dev = 0, nn = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0) nn = 256;
-        nn &= ~7;
-        n_cu = nn < 8 ? 8 : nn;
-    }
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_c16b_kernel), LDS_BYTES, slot)) return e;
+    const int n_cu = persistent_block_cap(slot);
     int grid = 2 * n_cu < ntiles ? 2 * n_cu : ntiles;
     if (grid >= 8) grid &= ~7;
     hipLaunchKernelGGL(conv3x3_c16b_kernel, dim3((unsigned)grid), dim3(256), LDS_BYTES, s, p, ntiles, tiles_x, tiles_y);

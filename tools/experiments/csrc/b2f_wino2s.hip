@@ -347,13 +347,8 @@ bool wino2s_supported(const ConvLaunch &p)
 hipError_t launch_conv3x3_wino2s(const ConvLaunch &p, int nb0, int nblk, hipStream_t s)
 {
     using namespace wino2s;
-    static bool attr_done_dev[64] = {false};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wino2s), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    static LdsOnce once;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_wino2s), LDS_BYTES)) return e;
     ConvLaunch q = p;
     q.nb0 = nb0;
     q.nblk = nblk;

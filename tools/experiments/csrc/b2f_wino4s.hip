@@ -596,21 +596,9 @@ bool wino4s_supported(const ConvLaunch &p)
 hipError_t launch_conv3x3_wino4s(const ConvLaunch &p, int nb0, int nblk, hipStream_t s)
 {
     using namespace wino4s;
-    static bool attr_done_dev[64] = {false};
-    static int n_cu_dev[64] = {0};
-    bool &attr_done = attr_done_dev[attr_slot()];
-    int &n_cu = n_cu_dev[attr_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wino4s), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    if (!n_cu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-        n_cu &= ~7;                     // the XCD remap of the virtual block index needs a multiple of 8
-        if (n_cu < 8) n_cu = 8;
-    }
+    static LdsOnce once;
+    const int slot = current_device_slot();
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_wino4s), LDS_BYTES, slot)) return e;
     ConvLaunch q = p;
     q.nb0 = nb0;
     q.nblk = nblk;
@@ -618,7 +606,7 @@ hipError_t launch_conv3x3_wino4s(const ConvLaunch &p, int nb0, int nblk, hipStre
     q.wpk = reinterpret_cast<const float *>(p.wpk_split);
     const int tiles = ((p.Wo + TW - 1) / TW) * ((p.Ho + TH - 1) / TH);
     const int total = tiles * p.nimg * nblk;
-    const int pcap = p.w4_persist > 1 ? p.w4_persist : n_cu;
+    const int pcap = p.w4_persist > 1 ? p.w4_persist : persistent_block_cap(slot);   // a multiple of 8: the XCD remap of the virtual block index needs it
     const int pgrid = pcap < total ? pcap : total;
     hipLaunchKernelGGL(conv3x3_wino4s, dim3((unsigned)pgrid), dim3(512), LDS_BYTES, s, q);
     return hipGetLastError();
