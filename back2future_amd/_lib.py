@@ -31,6 +31,15 @@ class LossGradFtOpts(C.Structure):
 
 c_grad_ft_opts_p = C.POINTER(LossGradFtOpts)
 
+
+class LossGradSsimOpts(C.Structure):
+    """b2f_loss_grad_ssim_opts of include/b2f.h: the fields of LossGradOpts, -smooth_second_order and the alpha of
+    OSSIML1Criterion (1: OSSIM, 0.85: OSSIML1)"""
+    _fields_ = LossGradOpts._fields_ + [("smooth_second_order", C.c_int), ("ssim_alpha", C.c_double)]
+
+
+c_grad_ssim_opts_p = C.POINTER(LossGradSsimOpts)
+
 # name -> (restype, argtypes); must list every symbol include/b2f.h declares
 SIGNATURES = {
     "b2f_last_error": (C.c_char_p, []),
@@ -235,6 +244,19 @@ SIGNATURES = {
                                                   C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
     "b2f_multi_forward_loss_grad_ft": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ft_opts_p,
                                                  C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int]),
+    "b2f_loss_grad_ssim_defaults": (C.c_int, [c_grad_ssim_opts_p]),
+    "b2f_table_loss_grad_ssim_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                                c_grad_ssim_opts_p, C.POINTER(c_float_p), C.c_int, c_float_p]),
+    "b2f_table_loss_grad_ssim_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                                  c_grad_ssim_opts_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, c_float_p]),
+    "b2f_op_table_loss_grad_ssim": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                              c_grad_ssim_opts_p, C.POINTER(c_float_p), C.c_int, c_float_p]),
+    "b2f_forward_loss_grad_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ssim_opts_p,
+                                             C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int, C.POINTER(c_float_p), C.c_int, c_float_p]),
+    "b2f_forward_loss_grad_ssim_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ssim_opts_p,
+                                                    C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, c_float_p]),
+    "b2f_multi_forward_loss_grad_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ssim_opts_p,
+                                                   C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int, C.c_int, c_float_p]),
     "b2f_forward": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(c_float_p), C.c_int]),
     "b2f_output_shapes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.c_int]),

@@ -823,28 +823,60 @@ def loss_grad_ft_options(weights=None, size_average=False, objective=None, smoot
     return o
 
 
+def loss_grad_ssim_options(weights=None, size_average=False, smooth_second_order=False, pme_criterion="OSSIML1", ssim_alpha=None):
+    """The options of the gradient table with the occlusion-aware SSIM + L1 photometric term (a _lib.LossGradSsimOpts,
+    b2f_loss_grad_ssim_opts of include/b2f.h; criterions/OSSIML1Criterion.lua:165-302), from b2f_loss_grad_ssim_defaults: those of
+    loss_grad_options, -smooth_second_order off, alpha 0.85.  pme_criterion: "OSSIML1" or "OSSIM" (SSIM_ALPHA); an explicit
+    ssim_alpha, finite and in [0, 1], overrides its value.  Every entry point that takes the options of loss_grad_options takes these
+    too, with a keyword ssim_range as for the objective "ssim"."""
+    o = _lib.LossGradSsimOpts()
+    _lib.check(_lib.lib().b2f_loss_grad_ssim_defaults(C.byref(o)))
+    _apply_grad_weights("loss_grad_ssim_options", o, dict(weights or {}))
+    if pme_criterion not in SSIM_ALPHA:
+        raise ValueError("loss_grad_ssim_options: pme_criterion must be 'OSSIML1' or 'OSSIM'")
+    o.ssim_alpha = SSIM_ALPHA[pme_criterion]
+    if ssim_alpha is not None:
+        if not (0.0 <= float(ssim_alpha) <= 1.0):
+            raise ValueError("loss_grad_ssim_options: ssim_alpha must be in [0, 1], got %r" % (ssim_alpha,))
+        o.ssim_alpha = float(ssim_alpha)
+    o.smooth_second_order = 1 if smooth_second_order else 0
+    o.size_average = 1 if size_average else 0
+    return o
+
+
 def _grad_opts_ptr(options):
     if options is None:
         return None
-    if not isinstance(options, (_lib.LossGradOpts, _lib.LossGradFtOpts)):
-        raise ValueError("expected the result of back2future.loss_grad_options or loss_grad_ft_options (or None for the defaults)")
+    if not isinstance(options, (_lib.LossGradOpts, _lib.LossGradFtOpts, _lib.LossGradSsimOpts)):
+        raise ValueError("expected the result of back2future.loss_grad_options or loss_grad_ft_options, or of loss_grad_ssim_options (or None "
+                         "for the defaults)")
     return C.byref(options)
 
 
 def _grad_entry(name, options):
-    """the entry `name` of the library for these options: b2f_*_grad* or, for loss_grad_ft_options, its b2f_*_grad_ft* twin"""
+    """the entry `name` of the library for these options: b2f_*_grad* or, for loss_grad_ft_options / loss_grad_ssim_options, its
+    b2f_*_grad_ft* / b2f_*_grad_ssim* twin"""
     if isinstance(options, _lib.LossGradFtOpts):
         name = name.replace("_grad", "_grad_ft", 1)
+    elif isinstance(options, _lib.LossGradSsimOpts):
+        name = name.replace("_grad", "_grad_ssim", 1)
     return getattr(_lib.lib(), name)
 
 
 def _grad_words(options):
-    """words per record beside a gradient table: the fine-tuning options give the 24-word records of objective "finetune"""
-    return LOSS_FT_WORDS if isinstance(options, _lib.LossGradFtOpts) else LOSS_WORDS
+    """words per record beside a gradient table: the fine-tuning options give the 24-word records of objective "finetune", the SSIM +
+    L1 options the 32-word records of objective "ssim"""
+    return LOSS_FT_WORDS if isinstance(options, _lib.LossGradFtOpts) else LOSS_SSIM_WORDS if isinstance(options, _lib.LossGradSsimOpts) else LOSS_WORDS
 
 
-def _forward_loss_grad(fn, h, x, flow_scale, options, shapes, L, want_loss, want_table):
-    """x n x 9 x H x W normalized -> (gradient table, records or None, table or None): b2f_forward_loss_grad / b2f_multi_forward_loss_grad"""
+def _grad_range_args(options, ssim_range, L, who, batch_ok=True):
+    """the trailing (range_mode, ranges) of a b2f_*_grad_ssim entry (ssim_range_args), () for the other options"""
+    return ssim_range_args("ssim", ssim_range, L, who, batch_ok) if isinstance(options, _lib.LossGradSsimOpts) else ()
+
+
+def _forward_loss_grad(fn, h, x, flow_scale, options, shapes, L, want_loss, want_table, tail=()):
+    """x n x 9 x H x W normalized -> (gradient table, records or None, table or None): b2f_forward_loss_grad / b2f_multi_forward_loss_grad;
+    tail: _grad_range_args"""
     x = _lib.f32(x)
     if x.ndim != 4 or x.shape[1] != 9:
         raise ValueError("forwardLossGrad: expected an n x 9 x H x W normalized input, got shape %r" % (x.shape,))
@@ -856,7 +888,7 @@ def _forward_loss_grad(fn, h, x, flow_scale, options, shapes, L, want_loss, want
     lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong)) if want_loss else None
     outs = [np.empty((n, c, hh, ww), np.float32) for (c, hh, ww) in sh] if want_table else None
     op = (_lib.c_float_p * len(outs))(*[_lib.fptr(t) for t in outs]) if want_table else None
-    _lib.check(fn(h, _lib.fptr(x), n, H, W, float(flow_scale), _grad_opts_ptr(options), lp, gp, len(grad), op))
+    _lib.check(fn(h, _lib.fptr(x), n, H, W, float(flow_scale), _grad_opts_ptr(options), lp, gp, len(grad), op, *tail))
     return grad, loss, outs
 
 
@@ -1227,39 +1259,44 @@ class Model(object):
         _lib.check(entry(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale), C.c_void_p(d_loss),
                          C.c_void_p(stream) if stream else None, *tail))
 
-    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, want_table=False):
+    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, want_table=False, ssim_range="batch"):
         """model:forward followed by `gradOutputs` of train.lua:428-468 (b2f_forward_loss_grad): x n x 9 x H x W, already normalized ->
         the gradient of the pme objective with respect to every tensor of the output table, a list with the shapes of
         Model.forward's, that of ops.table_loss_grad(self.forward(x), x[:, 3:6]); the table stays on the GPU.  options: of
         loss_grad_options (None: the defaults) or of loss_grad_ft_options (b2f_forward_loss_grad_ft: the fine-tuning objectives of the
         Soft models).  want_loss=True returns (gradient, records) with the records of forwardLoss (of forwardLoss(objective="finetune")
-        with loss_grad_ft_options), from the same pass; want_table=True appends the table of Model.forward, bit for bit."""
+        with loss_grad_ft_options), from the same pass; want_table=True appends the table of Model.forward, bit for bit.  With the options
+        of loss_grad_ssim_options: b2f_forward_loss_grad_ssim, the records of forwardLoss(objective="ssim"), ssim_range as there."""
         L = self.n_outputs // (5 if self.past_flow else 4)
         grad, loss, outs = _forward_loss_grad(_grad_entry("b2f_forward_loss_grad", options), self._h, x, flow_scale, options, self.output_shapes, L,
-                                              want_loss, want_table)
+                                              want_loss, want_table, _grad_range_args(options, ssim_range, L, "forwardLossGrad"))
         if not want_loss and not want_table:
             return grad
         return (grad,) + ((loss,) if want_loss else ()) + ((outs,) if want_table else ())
 
-    def forwardLossGradDevice(self, d_in, n, H, W, d_grad, d_loss=None, flow_scale=20.0, options=None, stream=None):
+    def forwardLossGradDevice(self, d_in, n, H, W, d_grad, d_loss=None, flow_scale=20.0, options=None, stream=None, ssim_range="batch"):
         """b2f_forward_loss_grad_device on device pointers (ints): d_in n x 9 x H x W normalized float32, d_grad the n_outputs tensors
         of the gradient table (train.lua:428-468), d_loss n x L x 16 uint64 or None; asynchronous on `stream`.  With the options of
-        loss_grad_ft_options: b2f_forward_loss_grad_ft_device, d_loss n x L x 24."""
+        loss_grad_ft_options: b2f_forward_loss_grad_ft_device, d_loss n x L x 24; of loss_grad_ssim_options:
+        b2f_forward_loss_grad_ssim_device, d_loss n x L x 32, ssim_range as for forwardLoss."""
         ptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad])
+        tail = _grad_range_args(options, ssim_range, self.n_outputs // (5 if self.past_flow else 4), "forwardLossGradDevice")
         _lib.check(_grad_entry("b2f_forward_loss_grad_device", options)(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale),
                                                             _grad_opts_ptr(options), C.c_void_p(d_loss) if d_loss else None, ptrs, len(d_grad),
-                                                            C.c_void_p(stream) if stream else None))
+                                                            C.c_void_p(stream) if stream else None, *tail))
 
-    def tableLossGradDevice(self, d_table, n, H, W, d_ref, d_grad, flow_scale=20.0, options=None, stream=None):
+    def tableLossGradDevice(self, d_table, n, H, W, d_ref, d_grad, flow_scale=20.0, options=None, stream=None, ssim_range="batch"):
         """b2f_table_loss_grad_device on device pointers (ints): d_table the L x 4 | 5 tensors of an output table in table order, d_ref
         n x 3 x H x W, d_grad as many tensors of the same shapes (train.lua:428-468); asynchronous on `stream`.  With the options of
-        loss_grad_ft_options: b2f_table_loss_grad_ft_device."""
+        loss_grad_ft_options: b2f_table_loss_grad_ft_device; of loss_grad_ssim_options: b2f_table_loss_grad_ssim_device, ssim_range as for
+        tableLossDevice."""
         ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
         gptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad])
         if len(d_grad) != len(d_table):
             raise ValueError("tableLossGradDevice: the gradient table must have the table's %d tensors" % len(d_table))
+        tail = _grad_range_args(options, ssim_range, len(d_table) // (5 if self.past_flow else 4), "tableLossGradDevice")
         _lib.check(_grad_entry("b2f_table_loss_grad_device", options)(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale),
-                                                          _grad_opts_ptr(options), gptrs, C.c_void_p(stream) if stream else None))
+                                                          _grad_opts_ptr(options), gptrs, C.c_void_p(stream) if stream else None, *tail))
 
     def forward_device(self, d_in, B, H, W, d_flow=None, d_occ=None, d_est3=None, unit_input=False, stream=None, d_past_flow=None):
         """model:forward on device pointers (ints); asynchronous on `stream`.  d_past_flow (B x 2 x H x W float32, Soft models;
@@ -1389,9 +1426,10 @@ class MultiModel(object):
         tail = ssim_range_args(objective, ssim_range, L, "MultiModel.forwardLoss", batch_ok=False)
         return _forward_loss(lambda *a: base(*(a + tail)), self._h, x, flow_scale, L, None, words)[0]
 
-    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True):
-        """Model.forwardLossGrad over the GPUs (b2f_multi_forward_loss_grad, b2f_multi_forward_loss_grad_ft; train.lua:428-468): the
-        same bits."""
+    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, ssim_range="image"):
+        """Model.forwardLossGrad over the GPUs (b2f_multi_forward_loss_grad, b2f_multi_forward_loss_grad_ft,
+        b2f_multi_forward_loss_grad_ssim; train.lua:428-468): the same bits.  With loss_grad_ssim_options ssim_range is "image" or an
+        L x 2 array, as for MultiModel.forwardLoss."""
         c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
         lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
@@ -1402,8 +1440,10 @@ class MultiModel(object):
             return [(ch[i], oh[i], ow[i]) for i in range(no.value)]
 
         entry = _grad_entry("b2f_multi_forward_loss_grad", options)
-        fn = lambda h, xp, n, H, W, fsc, op, lp, gp, ng, outs: entry(h, xp, n, H, W, fsc, op, lp, gp, ng)
-        grad, loss, _ = _forward_loss_grad(fn, self._h, x, flow_scale, options, shapes, no.value // (5 if pf.value else 4), want_loss, False)
+        fn = lambda h, xp, n, H, W, fsc, op, lp, gp, ng, outs, *tail: entry(h, xp, n, H, W, fsc, op, lp, gp, ng, *tail)
+        L = no.value // (5 if pf.value else 4)
+        grad, loss, _ = _forward_loss_grad(fn, self._h, x, flow_scale, options, shapes, L, want_loss, False,
+                                           _grad_range_args(options, ssim_range, L, "MultiModel.forwardLossGrad", batch_ok=False))
         return (grad, loss) if want_loss else grad
 
 

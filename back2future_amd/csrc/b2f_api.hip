@@ -963,7 +963,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1010; }
+int b2f_version(void) { return 1011; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1136,6 +1136,7 @@ void b2f_destroy(b2f_ctx *c)
     if (c->dwork.dev) (void)hipFree(c->dwork.dev);
     if (c->vis_max.dev) (void)hipFree(c->vis_max.dev);
     if (c->loss_pyr.dev) (void)hipFree(c->loss_pyr.dev);
+    if (c->loss_rec.dev) (void)hipFree(c->loss_rec.dev);
     if (c->loss_work.dev) (void)hipFree(c->loss_work.dev);
     if (c->arena) (void)hipFree(c->arena);
     if (c->wpk_dev) (void)hipFree(c->wpk_dev);
@@ -1591,7 +1592,7 @@ int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H
     CHK(forward_table_run(c, s, d_in, nb, H, W, lp, tab));
     const size_t hw = (size_t)H * W;
     if (d_loss) CHK(table_loss_run(c, s, tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, d_loss, lp.kind));
-    if (grad) CHK(table_loss_grad_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, *o, d_loss == nullptr));
+    if (grad) CHK(table_loss_grad_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, *o, d_loss));
     return 0;
 }
 
@@ -1626,8 +1627,7 @@ int loss_work_tables(b2f_ctx *c, const LossPlan &lp, std::vector<float *> &tab, 
 }
 
 // what b2f_forward_loss_grad* check beyond check_forward_loss: the options (into *o) and the gradient table's pointers
-int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft,
-                            float *const *grad, int n_outs, GradOpts *o)
+int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, const GradArgs &a, float *const *grad, int n_outs, GradOpts *o)
 {
     if (n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
     for (int i = 0; i < n_outs; ++i) {
@@ -1635,7 +1635,7 @@ int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, const b2f_lo
         for (int k = 0; k < i; ++k)
             if (grad[i] == grad[k]) return fail(w + ": the gradient table must not alias itself");
     }
-    return resolve_grad_opts(w, opts, ft_opts, ft, o);
+    return resolve_grad_opts(w, a, o);
 }
 
 struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub-batches run (b2f_ctx::req_batch)
@@ -1694,23 +1694,23 @@ int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, in
     return forward_loss_host_run(c, x, n, req, H, W, flow_scale, k, nullptr, loss, nullptr, outs);
 }
 
-// b2f_forward_loss_grad (ft = false) or b2f_forward_loss_grad_ft on a shard: `req` is the caller's n (b2f_multi_forward_loss_grad* pass
-// their own down)
-int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
-                                const b2f_loss_grad_ft_opts *ft_opts, bool ft, unsigned long long *loss, float *const *grad, int n_outs,
-                                float *const *outs)
+// b2f_forward_loss_grad, b2f_forward_loss_grad_ft or b2f_forward_loss_grad_ssim on a shard: `req` is the caller's n
+// (b2f_multi_forward_loss_grad* pass their own down)
+int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const GradArgs &a, unsigned long long *loss,
+                                float *const *grad, int n_outs, float *const *outs)
 {
-    const std::string w(ft ? "b2f_forward_loss_grad_ft" : "b2f_forward_loss_grad");
+    const std::string w = std::string("b2f_forward_loss") + a.suffix();
     if (!c || !x || !grad) return fail(w + ": null argument");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
+    CHK(check_forward_loss_kind(c, w, a.rec(), n, H, W));
     GradOpts o;
-    CHK(check_forward_loss_grad(c, w, opts, ft_opts, ft, grad, n_outs, &o));
+    CHK(check_forward_loss_grad(c, w, a, grad, n_outs, &o));
     for (int i = 0; outs && i < n_outs; ++i) {
         if (!outs[i]) return fail(w + ": null tensor in outs");
         for (int k = 0; k < n_outs; ++k)
             if (outs[i] == grad[k]) return fail(w + ": the gradient table must not alias outs");
     }
-    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, loss_kind(ft), &o, loss, grad, outs);
+    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, o.rec, &o, loss, grad, outs);
 }
 
 extern "C" {
@@ -1719,7 +1719,7 @@ extern "C" {
 int b2f_forward_loss_grad(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts, unsigned long long *loss,
                           float *const *grad, int n_outs, float *const *outs) try
 {
-    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, opts, nullptr, false, loss, grad, n_outs, outs);
+    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, grad_args(opts), loss, grad, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_grad")
 
@@ -1727,23 +1727,23 @@ B2F_CATCH("b2f_forward_loss_grad")
 int b2f_forward_loss_grad_ft(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ft_opts *opts,
                              unsigned long long *loss, float *const *grad, int n_outs, float *const *outs) try
 {
-    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, nullptr, opts, true, loss, grad, n_outs, outs);
+    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, grad_args(opts), loss, grad, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_grad_ft")
 
 extern "C++" {
-// the five device entries: b2f_forward_loss_device / _ft_device / _ssim_device (with_grad = false: dev_loss required, no gradient table;
-// k: which records) and b2f_forward_loss_grad_device / _grad_ft_device (with_grad: dev_grad required, dev_loss optional, k = loss_kind(ft))
+// the six device entries: b2f_forward_loss_device / _ft_device / _ssim_device (a == nullptr: dev_loss required, no gradient table; k:
+// which records) and b2f_forward_loss_grad_device / _grad_ft_device / _grad_ssim_device (a: dev_grad required, dev_loss optional, k = a->rec())
 static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
-                               const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, const LossKind &k, bool with_grad,
-                               unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream)
+                               const GradArgs *a, const LossKind &k, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream)
 {
+    const bool with_grad = a != nullptr;
     if (!c || !dev_in || (with_grad ? !dev_grad : !dev_loss)) return fail(w + ": null argument");
     if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
     CHK(check_forward_loss_kind(c, w, k, n, H, W));
     GradOpts o;
-    if (with_grad) CHK(check_forward_loss_grad(c, w, opts, ft_opts, ft, dev_grad, n_outs, &o));
+    if (with_grad) CHK(check_forward_loss_grad(c, w, *a, dev_grad, n_outs, &o));
     uintptr_t bits = (uintptr_t)dev_in | (uintptr_t)dev_loss;
     for (int i = 0; with_grad && i < n_outs; ++i) bits |= (uintptr_t)dev_grad[i];
     if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
@@ -1770,16 +1770,35 @@ static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev
 int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
                                  unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, opts, nullptr, false, loss_kind(false), true, dev_loss, dev_grad, n_outs, stream);
+    const GradArgs a = grad_args(opts);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_device")
 
 int b2f_forward_loss_grad_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                                     const b2f_loss_grad_ft_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, opts, true, loss_kind(true), true, dev_loss, dev_grad, n_outs, stream);
+    const GradArgs a = grad_args(opts);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_ft_device")
+
+// model:forward + the gradient table with the SSIM + L1 photometric term and the 32-word records, from host memory
+int b2f_forward_loss_grad_ssim(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ssim_opts *opts,
+                               unsigned long long *loss, float *const *grad, int n_outs, float *const *outs, int range_mode, const float *ranges) try
+{
+    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs, outs);
+}
+B2F_CATCH("b2f_forward_loss_grad_ssim")
+
+int b2f_forward_loss_grad_ssim_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                      const b2f_loss_grad_ssim_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream,
+                                      int range_mode, const float *ranges) try
+{
+    const GradArgs a = grad_args(opts, range_mode, ranges);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
+}
+B2F_CATCH("b2f_forward_loss_grad_ssim_device")
 
 // model:forward + test.lua:266-297 from host memory
 int b2f_forward_loss(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try
@@ -1799,7 +1818,7 @@ B2F_CATCH("b2f_forward_loss_ft")
 int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                             void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, false, loss_kind(false), false, dev_loss, nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, loss_kind(false), dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_device")
 
@@ -1807,7 +1826,7 @@ B2F_CATCH("b2f_forward_loss_device")
 int b2f_forward_loss_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                                void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, true, loss_kind(true), false, dev_loss, nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, loss_kind(true), dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_ft_device")
 
@@ -1823,8 +1842,8 @@ B2F_CATCH("b2f_forward_loss_ssim")
 int b2f_forward_loss_ssim_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                                  void *stream, int range_mode, const float *ranges) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, nullptr, false, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges},
-                               false, dev_loss, nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, dev_loss,
+                               nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_ssim_device")
 

@@ -570,6 +570,7 @@ struct b2f_ctx : b2f::KernelOpts {
     b2f::DevWork vis_max;         // b2f_flow_rgb_device without dev_max_used: the per-image maxima of the automatic mode
     b2f::DevWork loss_pyr;        // b2f_table_loss_device / b2f_forward_loss*: the pooled reference images R_1 .. R_{L-1} (test.lua:266-297)
     b2f::DevWork loss_work;       // b2f_forward_loss*: [input | output table | records] of a sub-batch
+    b2f::DevWork loss_rec;        // the *_grad_ssim entries without records: n x L x 32 words for the ranges (table_loss_grad_run)
     std::vector<b2f_stream *> streams;   // open streams (b2f_stream_open); b2f_destroy closes what is left
     // arena_guard on a non-shipped graph: the generic executor's buffers of the layout in arena_layout; guards[].name points into their names
     std::vector<b2f::GraphBuf> graph_bufs;
@@ -627,28 +628,52 @@ inline LossKind loss_kind(bool ft) { return LossKind{ft ? B2F_LOSS_FT_WORDS : B2
 // k: the records of b2f_forward_loss, b2f_forward_loss_ft or b2f_forward_loss_ssim
 int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
                       const LossKind &k = LossKind());
-// checked options of either gradient table: ft = false: the *_grad entries (o's two flags are 0, table_loss_grad_kernel, 16-word
-// records); ft = true: the *_grad_ft entries (table_loss_grad_ft_kernel, 24-word records)
+// which gradient table an entry writes: the *_grad entries (b2f_loss_grad_opts, table_loss_grad_kernel, 16-word records), the *_grad_ft
+// entries (b2f_loss_grad_ft_opts, table_loss_grad_ft_kernel, 24-word records) or the *_grad_ssim entries (b2f_loss_grad_ssim_opts,
+// table_loss_grad_ft_kernel's flow planes + table_loss_grad_ssim_kernel, 32-word records)
+enum GradKind { kGradKindFirst = 0, kGradKindFt = 1, kGradKindSsim = 2 };
+// the options an entry was given: opts points at the struct of `kind` (nullptr: that kind's defaults); range_mode / ranges: the
+// trailing arguments of the *_grad_ssim entries
+struct GradArgs {
+    GradKind kind;
+    const void *opts;
+    int range_mode;
+    const float *ranges;
+    // the records that go with this gradient table
+    LossKind rec() const
+    {
+        return kind == kGradKindSsim ? LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges} : loss_kind(kind == kGradKindFt);
+    }
+    const char *suffix() const { return kind == kGradKindFt ? "_grad_ft" : kind == kGradKindSsim ? "_grad_ssim" : "_grad"; }
+};
+inline GradArgs grad_args(const b2f_loss_grad_opts *o) { return GradArgs{kGradKindFirst, o, 0, nullptr}; }
+inline GradArgs grad_args(const b2f_loss_grad_ft_opts *o) { return GradArgs{kGradKindFt, o, 0, nullptr}; }
+inline GradArgs grad_args(const b2f_loss_grad_ssim_opts *o, int range_mode, const float *ranges) { return GradArgs{kGradKindSsim, o, range_mode, ranges}; }
+// checked options of a gradient table: o holds the first-order fields and smooth_second_order of every kind (the *_grad entries: both
+// flags 0; the *_grad_ssim entries: pme_criterion 0, unused), ssim_alpha and rec the rest of kGradKindSsim
 struct GradOpts {
     b2f_loss_grad_ft_opts o;
-    bool ft;
+    GradKind kind;
+    double ssim_alpha;
+    LossKind rec;
 };
-// b2f_tableloss.hip: opts (ft = false) or ft_opts (ft = true), or that kind's defaults where it is null, into *o; refused as
-// include/b2f.h says
-int resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, GradOpts *o);
+// b2f_tableloss.hip: the options of a, or its kind's defaults where they are null, into *o; refused as include/b2f.h says (the range
+// of kGradKindSsim included)
+int resolve_grad_opts(const std::string &w, const GradArgs &a, GradOpts *o);
 // b2f_tableloss.hip: the records of test.lua:266-297 of n images on s, under the profile row table_loss; k.words = B2F_LOSS_WORDS,
 // B2F_LOSS_FT_WORDS with the fine-tuning terms behind them (table_loss_ft), or B2F_LOSS_SSIM_WORDS with the ranges and the SSIM + L1
 // sums (table_loss_range, table_loss_ssim).  Builds R_1 .. R_{L-1} in c->loss_pyr first.
 int table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, int L, bool past, int n, int H, int W, const float *dev_ref,
                    size_t ref_stride, double flow_scale, unsigned long long *dev_loss, const LossKind &k);
-// b2f_tableloss.hip: the gradient table of train.lua:428-468 of n images on s, from checked options; with_pyr: R_1 .. R_{L-1} are built
-// first (false: table_loss_run has built them on s)
+// b2f_tableloss.hip: the gradient table of train.lua:428-468 of n images on s, from checked options; dev_loss: the records
+// table_loss_run(.., o.rec) has written on s with R_1 .. R_{L-1}, or nullptr: the pyramid is built first, and with kGradKindSsim the
+// ranges into a zeroed record buffer of the context (c->loss_rec)
 int table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
-                        const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, bool with_pyr);
-// b2f_api.hip: b2f_forward_loss_grad (ft = false, opts) or b2f_forward_loss_grad_ft (ft = true, ft_opts) on n of a request of `req`
+                        const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, unsigned long long *dev_loss);
+// b2f_api.hip: b2f_forward_loss_grad, b2f_forward_loss_grad_ft or b2f_forward_loss_grad_ssim (a.kind) on n of a request of `req`
 // triplets (0: n)
-int forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
-                           const b2f_loss_grad_ft_opts *ft_opts, bool ft, unsigned long long *loss, float *const *grad, int n_outs, float *const *outs);
+int forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const GradArgs &a, unsigned long long *loss,
+                           float *const *grad, int n_outs, float *const *outs);
 int compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream);
 // b2f_pipeline.hip: a push (r.stream) on host buffers, synchronous, and on device buffers, asynchronous on `stream`; *ready = 1 when
 // the outputs were written (from the third push on)

@@ -10,6 +10,7 @@
 #include "b2f_tableloss_grad_ft.h"
 #include "b2f_tableloss_ft.h"
 #include "b2f_tableloss_ssim.h"
+#include "b2f_tableloss_grad_ssim.h"
 #include "../../include/b2f.h"
 
 #include <algorithm>
@@ -419,28 +420,33 @@ void table_loss_ft_host(const float *const *table, int L, bool past, int n, int 
     }
 }
 
-// the SSIM + L1 photometric sums of criterions/OSSIML1Criterion.lua:47-163 beside test.lua:266-297
-void table_loss_ssim_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
-                          int range_mode, const float *ranges, unsigned long long *loss)
+// the float whose bits a record's word holds
+static float word_float(unsigned long long u64)
+{
+    const unsigned u = (unsigned)u64;
+    float v;
+    std::memcpy(&v, &u, sizeof v);
+    return v;
+}
+
+// every image's own range per level, on the encoding whose minimum and maximum do not depend on the order; then the one used
+void ssim_ranges_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, int range_mode, const float *ranges,
+                      unsigned long long *loss)
 {
     constexpr int kRec = B2F_LOSS_SSIM_WORDS;
-    table_loss_host(table, L, past, n, H, W, ref, flow_scale, loss, kRec);
     const int per = past ? 5 : 4;
     std::vector<float> cur, next;
-    // R_j of image b while j runs from 0 up: the 2 x 2 mean of R_{j-1} as in table_loss_host
-    auto level_ref = [&](int b, int j, const float *prev) {
-        if (j == 0) return ref + (size_t)b * 3 * H * W;
-        pool_ref(prev, H >> (j - 1), W >> (j - 1), next);
-        cur.swap(next);
-        return (const float *)cur.data();
-    };
-    // every image's own range per level, on the encoding whose minimum and maximum do not depend on the order; then the one used
     std::vector<unsigned> lo((size_t)L, 0xffffffffu), hi((size_t)L, 0u);
     for (int b = 0; b < n; ++b) {
         const float *R = nullptr;
         for (int j = 0; j < L; ++j) {
             const size_t hw = (size_t)(H >> j) * (W >> j);
-            R = level_ref(b, j, R);
+            if (j == 0) R = ref + (size_t)b * 3 * H * W;
+            else {   // R_j as in table_loss_host
+                pool_ref(R, H >> (j - 1), W >> (j - 1), next);
+                cur.swap(next);
+                R = cur.data();
+            }
             const float *const *t = table + (size_t)j * per;
             const float *seg[3] = {R, t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
             unsigned l = 0xffffffffu, h = 0u;
@@ -463,19 +469,8 @@ void table_loss_ssim_host(const float *const *table, int L, bool past, int n, in
         std::memcpy(&u, &v, sizeof u);
         return u;
     };
-    auto bits_float = [](unsigned long long u64) {
-        const unsigned u = (unsigned)u64;
-        float v;
-        std::memcpy(&v, &u, sizeof v);
-        return v;
-    };
-    std::vector<double> tv[3][3];   // the normalised planes of a level: [R, iw1, iw3][channel]
-    for (int b = 0; b < n; ++b) {
-        const float *R = nullptr;
+    for (int b = 0; b < n; ++b)
         for (int j = 0; j < L; ++j) {
-            const int h = H >> j, w = W >> j;
-            const size_t hw = (size_t)h * w;
-            R = level_ref(b, j, R);
             unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
             if (range_mode == B2F_SSIM_RANGE_BATCH) {
                 rec[B2F_LOSS_SSIM_RANGE_USED] = ssim_dec_bits(lo[(size_t)j]);
@@ -487,7 +482,34 @@ void table_loss_ssim_host(const float *const *table, int L, bool past, int n, in
                 rec[B2F_LOSS_SSIM_RANGE_USED] = rec[B2F_LOSS_SSIM_RANGE_OWN];
                 rec[B2F_LOSS_SSIM_RANGE_USED + 1] = rec[B2F_LOSS_SSIM_RANGE_OWN + 1];
             }
-            const SsimRange rg = ssim_range(bits_float(rec[B2F_LOSS_SSIM_RANGE_USED]), bits_float(rec[B2F_LOSS_SSIM_RANGE_USED + 1]));
+        }
+}
+
+// the SSIM + L1 photometric sums of criterions/OSSIML1Criterion.lua:47-163 beside test.lua:266-297
+void table_loss_ssim_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                          int range_mode, const float *ranges, unsigned long long *loss)
+{
+    constexpr int kRec = B2F_LOSS_SSIM_WORDS;
+    table_loss_host(table, L, past, n, H, W, ref, flow_scale, loss, kRec);
+    ssim_ranges_host(table, L, past, n, H, W, ref, range_mode, ranges, loss);
+    const int per = past ? 5 : 4;
+    std::vector<float> cur, next;
+    // R_j of image b while j runs from 0 up: the 2 x 2 mean of R_{j-1} as in table_loss_host
+    auto level_ref = [&](int b, int j, const float *prev) {
+        if (j == 0) return ref + (size_t)b * 3 * H * W;
+        pool_ref(prev, H >> (j - 1), W >> (j - 1), next);
+        cur.swap(next);
+        return (const float *)cur.data();
+    };
+    std::vector<double> tv[3][3];   // the normalised planes of a level: [R, iw1, iw3][channel]
+    for (int b = 0; b < n; ++b) {
+        const float *R = nullptr;
+        for (int j = 0; j < L; ++j) {
+            const int h = H >> j, w = W >> j;
+            const size_t hw = (size_t)h * w;
+            R = level_ref(b, j, R);
+            unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
+            const SsimRange rg = ssim_range(word_float(rec[B2F_LOSS_SSIM_RANGE_USED]), word_float(rec[B2F_LOSS_SSIM_RANGE_USED + 1]));
             const float *const *t = table + (size_t)j * per;
             const float *f = t[0] + (size_t)b * 2 * hw, *p = past ? t[1] + (size_t)b * 2 * hw : nullptr;
             const float *o = t[per - 3] + (size_t)b * 2 * hw, *iw[2] = {t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
@@ -639,12 +661,66 @@ void table_loss_grad_host(const float *const *table, int L, bool past, int n, in
     table_loss_grad_ft_host(table, L, past, n, H, W, ref, flow_scale, loss_grad_ft_from(opts), grad);
 }
 
+const char *loss_grad_ssim_refusal(const b2f_loss_grad_ssim_opts &o)
+{
+    if (const char *why = loss_grad_refusal(loss_grad_ft_base(loss_grad_ssim_base(o)))) return why;
+    if (!(o.ssim_alpha >= 0.0 && o.ssim_alpha <= 1.0)) return "ssim_alpha of b2f_loss_grad_ssim_opts must be in [0, 1]";
+    return nullptr;
+}
+
+b2f_loss_grad_ft_opts loss_grad_ssim_base(const b2f_loss_grad_ssim_opts &o)
+{
+    b2f_loss_grad_opts t;
+    t.smooth_flow = o.smooth_flow; t.const_vel = o.const_vel; t.pme = o.pme; t.smooth_occ = o.smooth_occ; t.prior_occ = o.prior_occ;
+    for (int j = 0; j < kLossMaxLevels; ++j) t.level_weights[j] = o.level_weights[j];
+    t.size_average = o.size_average;
+    b2f_loss_grad_ft_opts r = loss_grad_ft_from(t);
+    r.smooth_second_order = o.smooth_second_order ? 1 : 0;
+    return r;
+}
+
+void loss_grad_ssim_coef(const b2f_loss_grad_ft_opts &o, double ssim_alpha, int j, int h, int w, GradSsimCoef *k)
+{
+    loss_grad_coef(loss_grad_ft_base(o), j, h, w, &k->k);
+    k->alpha = ssim_alpha;
+    k->beta = 1.0 - ssim_alpha;
+    k->ss = (k->alpha != 0.0 ? kGradSsimAlpha : 0u) | (k->beta != 0.0 ? kGradSsimBeta : 0u);
+}
+
+// what table_loss_grad_host_impl needs for the SSIM + L1 photometric term: alpha, and records that hold the ranges
+struct GradSsimHost {
+    double alpha;
+    const unsigned long long *rec;   // n x L x B2F_LOSS_SSIM_WORDS words
+};
+
+static void table_loss_grad_host_impl(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                                      const b2f_loss_grad_ft_opts &opts, const GradSsimHost *ss, float *const *grad);
+
 // both gradient tables: with neither flag of opts set every element takes the path of b2f_tableloss_grad.h alone
 void table_loss_grad_ft_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
                              const b2f_loss_grad_ft_opts &opts, float *const *grad)
 {
+    table_loss_grad_host_impl(table, L, past, n, H, W, ref, flow_scale, opts, nullptr, grad);
+}
+
+void table_loss_grad_ssim_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                               const b2f_loss_grad_ft_opts &opts, double ssim_alpha, int range_mode, const float *ranges, float *const *grad)
+{
+    std::vector<unsigned long long> rec((size_t)n * L * B2F_LOSS_SSIM_WORDS, 0ull);
+    ssim_ranges_host(table, L, past, n, H, W, ref, range_mode, ranges, rec.data());
+    const GradSsimHost ss = {ssim_alpha, rec.data()};
+    b2f_loss_grad_ft_opts o = opts;
+    o.pme_criterion = 0;
+    table_loss_grad_host_impl(table, L, past, n, H, W, ref, flow_scale, o, &ss, grad);
+}
+
+// every gradient table; ss: the photometric term is that of b2f_tableloss_grad_ssim.h (else opts.pme_criterion's)
+static void table_loss_grad_host_impl(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                                      const b2f_loss_grad_ft_opts &opts, const GradSsimHost *ss, float *const *grad)
+{
     const int per = past ? 5 : 4;
     std::vector<float> cur, next;
+    std::vector<double> tv[3][3];   // ss: the normalised planes of a level, [R, iw1, iw3][channel]
     for (int b = 0; b < n; ++b) {
         const float *R = ref + (size_t)b * 3 * H * W;
         for (int j = 0; j < L; ++j) {
@@ -674,6 +750,18 @@ void table_loss_grad_ft_host(const float *const *table, int L, bool past, int n,
             float *gf = g[0] + (size_t)b * 2 * hw, *gp = past ? g[1] + (size_t)b * 2 * hw : nullptr, *go = g[per - 3] + (size_t)b * 2 * hw;
             float *giw[2] = {g[per - 2] + (size_t)b * 3 * hw, g[per - 1] + (size_t)b * 3 * hw};
             const float kd = (float)(flow_scale / (double)(1 << j));
+            GradSsimCoef ks = {};
+            if (ss && (k.on & kGradPhoto)) {
+                loss_grad_ssim_coef(opts, ss->alpha, j, h, w, &ks);
+                const unsigned long long *rec = ss->rec + ((size_t)b * L + j) * B2F_LOSS_SSIM_WORDS;
+                const SsimRange rg = ssim_range(word_float(rec[B2F_LOSS_SSIM_RANGE_USED]), word_float(rec[B2F_LOSS_SSIM_RANGE_USED + 1]));
+                const float *src[3] = {R, iw[0], iw[1]};
+                for (int q = 0; q < 3; ++q)
+                    for (int c = 0; c < 3; ++c) {
+                        tv[q][c].resize(hw);
+                        for (size_t i = 0; i < hw; ++i) tv[q][c][i] = ssim_norm(src[q][(size_t)c * hw + i], rg);
+                    }
+            }
             for (int y = 0; y < h; ++y)
                 for (int x = 0; x < w; ++x) {
                     const size_t i = (size_t)y * w + x;
@@ -733,7 +821,27 @@ void table_loss_grad_ft_host(const float *const *table, int L, bool past, int n,
                             const bool pf = d == 0 && past;   // OBCCriterion.lua:166-170
                             const WarpTaps tp = warp_taps(pf ? p[i] : f[i], pf ? p[hw + i] : f[hw + i], d == 0 ? -kd : kd, x, y, w, h);
                             const float w3[3] = {iw[d][i], iw[d][hw + i], iw[d][2 * hw + i]}, r3[3] = {R[i], R[hw + i], R[2 * hw + i]};
-                            if (obgcc) {
+                            if (ss) {
+                                const size_t xs[3] = {il - (i - x), (size_t)x, ir - (i - x)}, ys[3] = {iu - x, i - x, id - x};   // clamped columns, rows
+                                // the window sum of a * b2 (b2 == nullptr: of a) at the pixel, as table_loss_ssim_host forms it
+                                auto G = [&](const double *a, const double *b2) {
+                                    double col[3];
+                                    for (int t = 0; t < 3; ++t) {
+                                        const size_t i0 = ys[0] + xs[t], i1 = ys[1] + xs[t], i2 = ys[2] + xs[t];
+                                        col[t] = b2 ? ssim_tap3(a[i0] * b2[i0], a[i1] * b2[i1], a[i2] * b2[i2]) : ssim_tap3(a[i0], a[i1], a[i2]);
+                                    }
+                                    return ssim_tap3(col[0], col[1], col[2]);
+                                };
+                                double S = 0.0, B = 0.0;
+                                for (int c = 0; c < 3; ++c) {
+                                    const double *ty = tv[0][c].data(), *tx = tv[1 + d][c].data();
+                                    const GradSsimChannel ch = grad_ssim_channel(ks, tx[i], ty[i], G(tx, nullptr), G(ty, nullptr), G(tx, tx), G(ty, ty), G(tx, ty));
+                                    gi[c] = grad_ssim_image(ks, tp.inside, ch.t, o[(size_t)(1 - d) * hw + i]);
+                                    S = c == 0 ? ch.s : S + ch.s;
+                                    B = c == 0 ? ch.e : B + ch.e;
+                                }
+                                po[1 - d] = grad_ssim_po(ks, tp.inside, S, B);
+                            } else if (obgcc) {
                                 double sums[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
                                 for (int c = 0; c < 3; ++c) {
                                     const float *I = iw[d] + c * hw, *Rc = R + c * hw;

@@ -122,6 +122,22 @@ const char *loss_grad_ft_refusal(const b2f_loss_grad_ft_opts &o);
 b2f_loss_grad_ft_opts loss_grad_ft_from(const b2f_loss_grad_opts &o);
 b2f_loss_grad_opts loss_grad_ft_base(const b2f_loss_grad_ft_opts &o);
 void loss_grad_ft_coef(const b2f_loss_grad_ft_opts &o, int j, int h, int w, GradFtCoef *k);
+}  // namespace b2f
+struct b2f_loss_grad_ssim_opts;
+namespace b2f {
+struct GradSsimCoef;
+// The same with the SSIM + L1 photometric term of criterions/OSSIML1Criterion.lua:165-302 (b2f_tableloss_grad_ssim.h per element;
+// b2f_table_loss_grad_ssim_host): opts' first-order fields and smooth_second_order (pme_criterion is not read), alpha and the range
+void table_loss_grad_ssim_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                               const b2f_loss_grad_ft_opts &opts, double ssim_alpha, int range_mode, const float *ranges, float *const *grad);
+// nullptr, or why (as loss_grad_refusal, an ssim_alpha outside [0, 1] or NaN)
+const char *loss_grad_ssim_refusal(const b2f_loss_grad_ssim_opts &o);
+// the fields the SSIM + L1 options share with the fine-tuning options (pme_criterion 0, alpha = beta = gamma = 1)
+b2f_loss_grad_ft_opts loss_grad_ssim_base(const b2f_loss_grad_ssim_opts &o);
+void loss_grad_ssim_coef(const b2f_loss_grad_ft_opts &o, double ssim_alpha, int j, int h, int w, GradSsimCoef *k);
+// words RANGE_OWN and RANGE_USED of records of B2F_LOSS_SSIM_WORDS words (OSSIML1Criterion.lua:62-67), every other word left alone
+void ssim_ranges_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, int range_mode, const float *ranges,
+                      unsigned long long *loss);
 // the coefficients of level j of h x w (include/b2f.h: k_s .. k_pr) and which terms are evaluated
 void loss_grad_coef(const b2f_loss_grad_opts &o, int j, int h, int w, GradCoef *k);
 

@@ -417,9 +417,16 @@ struct GradCoef;
 hipError_t launch_table_loss_grad(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
                                   const float *pyr, double flow_scale, const GradCoef *coef, hipStream_t s);
 // b2f_tableloss_grad_ft.hip: the same with SecondOrderSmoothnessCriterion / OBGCCriterion where coef[j].ft asks for them (b2f_host.h:
-// loss_grad_ft_coef)
+// loss_grad_ft_coef); flow_only: the flow planes alone (the other planes of grad are not touched: launch_table_loss_grad_ssim writes them)
 struct GradFtCoef;
 hipError_t launch_table_loss_grad_ft(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref,
-                                     size_t ref_stride, const float *pyr, double flow_scale, const GradFtCoef *coef, hipStream_t s);
+                                     size_t ref_stride, const float *pyr, double flow_scale, const GradFtCoef *coef, hipStream_t s, bool flow_only = false);
+// b2f_tableloss_grad_ssim.hip: the occlusion and image planes of the gradient table with the SSIM + L1 photometric term of
+// criterions/OSSIML1Criterion.lua:165-302 (b2f_tableloss_grad_ssim.h).  rec: records of B2F_LOSS_SSIM_WORDS words per image and level
+// whose words B2F_LOSS_SSIM_RANGE_USED hold the ranges (launch_table_loss_range on s before).  The flow planes are not touched.
+struct GradSsimCoef;
+hipError_t launch_table_loss_grad_ssim(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref,
+                                       size_t ref_stride, const float *pyr, double flow_scale, const GradSsimCoef *coef, const unsigned long long *rec,
+                                       hipStream_t s);
 
 }  // namespace b2f

@@ -445,16 +445,20 @@ int b2f_multi_forward_loss_ssim(b2f_multi *m, const float *x, int n, int H, int 
 }
 B2F_CATCH("b2f_multi_forward_loss_ssim")
 
-// b2f_multi_forward_loss_grad (ft = false) and b2f_multi_forward_loss_grad_ft
-static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
-                                   const b2f_loss_grad_ft_opts *ft_opts, bool ft, unsigned long long *loss, float *const *grad, int n_outs)
+// b2f_multi_forward_loss_grad, b2f_multi_forward_loss_grad_ft and b2f_multi_forward_loss_grad_ssim
+static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const GradArgs &a,
+                                   unsigned long long *loss, float *const *grad, int n_outs)
 {
     if (!m) return api_fail((w + ": null context").c_str());
     if (!x || !grad || n <= 0 || H <= 0 || W <= 0) return api_fail((w + ": bad arguments").c_str());
+    // (a shard's batch range would depend on how the request is split over the GPUs)
+    if (a.kind == kGradKindSsim && a.range_mode == B2F_SSIM_RANGE_BATCH)
+        return api_fail(w + ": B2F_SSIM_RANGE_BATCH is not served over several GPUs: the images of a request are split; use B2F_SSIM_RANGE_IMAGE or "
+                            "B2F_SSIM_RANGE_GIVEN");
     const b2f_ctx *c0 = m->ctx[0];
     if (n_outs != c0->g.n_outputs()) return api_fail((w + ": n_outs must be the contexts' n_outputs").c_str());
     const int per = c0->past_flow ? 5 : 4;
-    const size_t rec = (size_t)(n_outs / per) * (ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS);
+    const size_t rec = (size_t)(n_outs / per) * a.rec().words;
     for (int i = 0; i < n_outs; ++i)
         if (!grad[i]) return api_fail((w + ": null tensor in the gradient table").c_str());
     return run_sharded(m, n, [&](int i, int lo, int hi) {
@@ -463,7 +467,7 @@ static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const flo
             const int j = t / per, ch = (t % per) >= per - 2 ? 3 : 2;
             g[(size_t)t] = grad[t] + (size_t)lo * ch * (H >> j) * (W >> j);
         }
-        return forward_loss_grad_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, opts, ft_opts, ft,
+        return forward_loss_grad_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, a,
                                       loss ? loss + (size_t)lo * rec : nullptr, g.data(), n_outs, nullptr);
     });
 }
@@ -472,15 +476,23 @@ static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const flo
 int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
                                 unsigned long long *loss, float *const *grad, int n_outs) try
 {
-    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, opts, nullptr, false, loss, grad, n_outs);
+    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts), loss, grad, n_outs);
 }
 B2F_CATCH("b2f_multi_forward_loss_grad")
 
 int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ft_opts *opts,
                                    unsigned long long *loss, float *const *grad, int n_outs) try
 {
-    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, nullptr, opts, true, loss, grad, n_outs);
+    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts), loss, grad, n_outs);
 }
 B2F_CATCH("b2f_multi_forward_loss_grad_ft")
+
+// ... with the SSIM + L1 photometric term; the batch range is refused
+int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ssim_opts *opts,
+                                     unsigned long long *loss, float *const *grad, int n_outs, int range_mode, const float *ranges) try
+{
+    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs);
+}
+B2F_CATCH("b2f_multi_forward_loss_grad_ssim")
 
 }  // extern "C"

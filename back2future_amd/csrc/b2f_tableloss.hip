@@ -9,6 +9,7 @@
 #include "b2f_tableloss.h"
 #include "b2f_tableloss_grad_ft.h"
 #include "b2f_tableloss_ssim.h"
+#include "b2f_tableloss_grad_ssim.h"
 #include "b2f_tableloss_dev.h"
 
 using namespace b2f;
@@ -321,17 +322,27 @@ int check_grad_table(const std::string &w, const float *const *table, int n_outs
 
 }  // namespace
 
-int b2f::resolve_grad_opts(const std::string &w, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, GradOpts *o)
+int b2f::resolve_grad_opts(const std::string &w, const GradArgs &a, GradOpts *o)
 {
-    o->ft = ft;
+    o->kind = a.kind;
+    o->ssim_alpha = 0.0;
+    o->rec = a.rec();
     const char *why = nullptr;
-    if (ft) {
-        if (ft_opts) o->o = *ft_opts;
+    if (a.kind == kGradKindSsim) {
+        b2f_loss_grad_ssim_opts t;
+        if (a.opts) t = *static_cast<const b2f_loss_grad_ssim_opts *>(a.opts);
+        else (void)b2f_loss_grad_ssim_defaults(&t);
+        o->o = loss_grad_ssim_base(t);
+        o->ssim_alpha = t.ssim_alpha;
+        why = loss_grad_ssim_refusal(t);
+        if (!why) why = ssim_range_refusal(a.range_mode, a.ranges);
+    } else if (a.kind == kGradKindFt) {
+        if (a.opts) o->o = *static_cast<const b2f_loss_grad_ft_opts *>(a.opts);
         else (void)b2f_loss_grad_ft_defaults(&o->o);
         why = loss_grad_ft_refusal(o->o);
     } else {
         b2f_loss_grad_opts t;
-        if (opts) t = *opts;
+        if (a.opts) t = *static_cast<const b2f_loss_grad_opts *>(a.opts);
         else (void)b2f_loss_grad_defaults(&t);
         o->o = loss_grad_ft_from(t);
         why = loss_grad_refusal(t);
@@ -381,29 +392,49 @@ int b2f::table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table
     });
 }
 
-// b2f_table_loss_grad_device / b2f_table_loss_grad_ft_device on checked options; with_pyr: build R_1 .. R_{L-1} first (false:
-// table_loss_run has)
+// b2f_table_loss_grad_device / _grad_ft_device / _grad_ssim_device on checked options; dev_loss: the records table_loss_run has written
+// on s (it has built R_1 .. R_{L-1}, and with kGradKindSsim the ranges), or nullptr: both are made here
 int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
-                             const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, bool with_pyr)
+                             const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, unsigned long long *dev_loss)
 {
     GradFtCoef coef[kLossMaxLevels];
     GradCoef first[kLossMaxLevels];
+    GradSsimCoef ssim[kLossMaxLevels];
     for (int j = 0; j < L; ++j) {
         loss_grad_ft_coef(o.o, j, H >> j, W >> j, &coef[j]);
         first[j] = coef[j].k;
+        loss_grad_ssim_coef(o.o, o.ssim_alpha, j, H >> j, W >> j, &ssim[j]);
     }
     CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
-    if (with_pyr) HIPCHK(launch_table_loss_pyramid(L, n, H, W, dev_ref, ref_stride, (float *)c->loss_pyr.dev, s));
+    if (!dev_loss) HIPCHK(launch_table_loss_pyramid(L, n, H, W, dev_ref, ref_stride, (float *)c->loss_pyr.dev, s));
     const float *pyr = (const float *)c->loss_pyr.dev;
-    return timed_launch(c, s, o.ft ? "table_loss_grad_ft" : "table_loss_grad", [&] {
-        return o.ft ? launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s)
-                    : launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, first, s);
+    if (o.kind == kGradKindSsim) {
+        const unsigned long long *rec = dev_loss;
+        if (!rec) {   // no records asked for: the ranges into a zeroed record buffer of the context, by the same two kernels
+            const size_t bytes = (size_t)n * L * B2F_LOSS_SSIM_WORDS * sizeof(unsigned long long);
+            CHK(ensure_dev_work(c->loss_rec, bytes));
+            unsigned long long *scratch = (unsigned long long *)c->loss_rec.dev;
+            HIPCHK(hipMemsetAsync(scratch, 0, bytes, s));
+            CHK(timed_launch(c, s, "table_loss_range", [&] {
+                return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, o.rec.range_mode, o.rec.ranges, scratch, s);
+            }));
+            rec = scratch;
+        }
+        return timed_launch(c, s, "table_loss_grad_ssim", [&] {
+            const hipError_t e = launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s, true);
+            return e != hipSuccess ? e : launch_table_loss_grad_ssim(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, ssim, rec, s);
+        });
+    }
+    const bool ft = o.kind == kGradKindFt;
+    return timed_launch(c, s, ft ? "table_loss_grad_ft" : "table_loss_grad", [&] {
+        return ft ? launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s)
+                  : launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, first, s);
     });
 }
 
 namespace {
 
-// b2f_table_loss_grad_device and b2f_table_loss_grad_ft_device on checked options (resolve_grad_opts)
+// b2f_table_loss_grad_device, _grad_ft_device and _grad_ssim_device on checked options (resolve_grad_opts)
 int table_loss_grad_device(const std::string &w, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
                            double flow_scale, const GradOpts &o, float *const *dev_grad, void *stream)
 {
@@ -418,30 +449,35 @@ int table_loss_grad_device(const std::string &w, b2f_ctx *c, const float *const 
     for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i] | (uintptr_t)dev_grad[i];
     if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
-    const std::string use = o.ft ? "b2f_op_table_loss_grad_ft / b2f_table_loss_grad_ft_host" : "b2f_op_table_loss_grad / b2f_table_loss_grad_host";
+    const std::string use = o.kind == kGradKindSsim ? "b2f_op_table_loss_grad_ssim / b2f_table_loss_grad_ssim_host"
+                            : o.kind == kGradKindFt ? "b2f_op_table_loss_grad_ft / b2f_table_loss_grad_ft_host"
+                                                    : "b2f_op_table_loss_grad / b2f_table_loss_grad_host";
     if (host_memory(dev_ref)) return fail(w + ": host memory passed to a device entry point (use " + use + ")");
     for (int i = 0; i < n_outs; ++i)
         if (host_memory(dev_table[i]) || host_memory(dev_grad[i])) return fail(w + ": host memory passed to a device entry point (use " + use + ")");
     return table_loss_grad_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, dev_grad, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, flow_scale,
-                               o, true);
+                               o, nullptr);
 }
 
-// b2f_table_loss_grad_host and b2f_table_loss_grad_ft_host
+// b2f_table_loss_grad_host, b2f_table_loss_grad_ft_host and b2f_table_loss_grad_ssim_host
 int table_loss_grad_host_entry(const std::string &w, const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
-                               double flow_scale, const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, float *const *grad)
+                               double flow_scale, const GradArgs &a, float *const *grad)
 {
     int L = 0;
     CHK(check_table_loss(w, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, grad, &L));
     CHK(check_grad_table(w, table, n_outs, ref, grad));
     GradOpts o;
-    CHK(resolve_grad_opts(w, opts, ft_opts, ft, &o));
-    table_loss_grad_ft_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, grad);
+    CHK(resolve_grad_opts(w, a, &o));
+    if (o.kind == kGradKindSsim)
+        table_loss_grad_ssim_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, o.ssim_alpha, o.rec.range_mode, o.rec.ranges, grad);
+    else
+        table_loss_grad_ft_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, grad);
     return 0;
 }
 
-// b2f_op_table_loss_grad and b2f_op_table_loss_grad_ft
+// b2f_op_table_loss_grad, b2f_op_table_loss_grad_ft and b2f_op_table_loss_grad_ssim
 int op_table_loss_grad(const std::string &w, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
-                       const b2f_loss_grad_opts *opts, const b2f_loss_grad_ft_opts *ft_opts, bool ft, float *const *grad)
+                       const GradArgs &a, float *const *grad)
 {
     OpStage st(c, w);
     CHK(st.begin(true, "null context"));
@@ -451,7 +487,7 @@ int op_table_loss_grad(const std::string &w, b2f_ctx *c, const float *const *tab
     CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, grad, &L));
     CHK(check_grad_table(w, table, n_outs, ref, grad));
     GradOpts o;
-    CHK(resolve_grad_opts(w, opts, ft_opts, ft, &o));
+    CHK(resolve_grad_opts(w, a, &o));
     std::vector<const float *> ptrs((size_t)n_outs);
     std::vector<float *> gptrs((size_t)n_outs);
     std::vector<size_t> floats((size_t)n_outs);
@@ -488,7 +524,7 @@ int b2f_loss_grad_defaults(b2f_loss_grad_opts *o)
 int b2f_table_loss_grad_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
                              const b2f_loss_grad_opts *opts, float *const *grad) try
 {
-    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, opts, nullptr, false, grad);
+    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, grad_args(opts), grad);
 }
 B2F_CATCH("b2f_table_loss_grad_host")
 
@@ -497,7 +533,7 @@ int b2f_table_loss_grad_device(b2f_ctx *c, const float *const *dev_table, int n_
                                const b2f_loss_grad_opts *opts, float *const *dev_grad, void *stream) try
 {
     GradOpts o;
-    CHK(resolve_grad_opts(__func__, opts, nullptr, false, &o));
+    CHK(resolve_grad_opts(__func__, grad_args(opts), &o));
     return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
 }
 B2F_CATCH("b2f_table_loss_grad_device")
@@ -506,7 +542,7 @@ B2F_CATCH("b2f_table_loss_grad_device")
 int b2f_op_table_loss_grad(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                            const b2f_loss_grad_opts *opts, float *const *grad) try
 {
-    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, opts, nullptr, false, grad);
+    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, grad_args(opts), grad);
 }
 B2F_CATCH("b2f_op_table_loss_grad")
 
@@ -525,7 +561,7 @@ int b2f_loss_grad_ft_defaults(b2f_loss_grad_ft_opts *o)
 int b2f_table_loss_grad_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
                                 const b2f_loss_grad_ft_opts *opts, float *const *grad) try
 {
-    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, nullptr, opts, true, grad);
+    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, grad_args(opts), grad);
 }
 B2F_CATCH("b2f_table_loss_grad_ft_host")
 
@@ -533,7 +569,7 @@ int b2f_table_loss_grad_ft_device(b2f_ctx *c, const float *const *dev_table, int
                                   const b2f_loss_grad_ft_opts *opts, float *const *dev_grad, void *stream) try
 {
     GradOpts o;
-    CHK(resolve_grad_opts(__func__, nullptr, opts, true, &o));
+    CHK(resolve_grad_opts(__func__, grad_args(opts), &o));
     return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
 }
 B2F_CATCH("b2f_table_loss_grad_ft_device")
@@ -541,9 +577,46 @@ B2F_CATCH("b2f_table_loss_grad_ft_device")
 int b2f_op_table_loss_grad_ft(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                               const b2f_loss_grad_ft_opts *opts, float *const *grad) try
 {
-    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, nullptr, opts, true, grad);
+    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, grad_args(opts), grad);
 }
 B2F_CATCH("b2f_op_table_loss_grad_ft")
+
+// ---- the same with the SSIM + L1 photometric term of criterions/OSSIML1Criterion.lua:165-302 (b2f_tableloss_grad_ssim.hip) ----
+int b2f_loss_grad_ssim_defaults(b2f_loss_grad_ssim_opts *o)
+{
+    if (!o) return fail("b2f_loss_grad_ssim_defaults: null argument");
+    b2f_loss_grad_opts t;
+    (void)b2f_loss_grad_defaults(&t);
+    o->smooth_flow = t.smooth_flow; o->const_vel = t.const_vel; o->pme = t.pme; o->smooth_occ = t.smooth_occ; o->prior_occ = t.prior_occ;
+    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = t.level_weights[j];
+    o->size_average = t.size_average;
+    o->smooth_second_order = 0;
+    o->ssim_alpha = 0.85;
+    return 0;
+}
+
+int b2f_table_loss_grad_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                                  const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode, const float *ranges) try
+{
+    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, grad_args(opts, range_mode, ranges), grad);
+}
+B2F_CATCH("b2f_table_loss_grad_ssim_host")
+
+int b2f_table_loss_grad_ssim_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                                    const b2f_loss_grad_ssim_opts *opts, float *const *dev_grad, void *stream, int range_mode, const float *ranges) try
+{
+    GradOpts o;
+    CHK(resolve_grad_opts(__func__, grad_args(opts, range_mode, ranges), &o));
+    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
+}
+B2F_CATCH("b2f_table_loss_grad_ssim_device")
+
+int b2f_op_table_loss_grad_ssim(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                                const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode, const float *ranges) try
+{
+    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, grad_args(opts, range_mode, ranges), grad);
+}
+B2F_CATCH("b2f_op_table_loss_grad_ssim")
 
 // test.lua:266-297 on the CPU
 int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,

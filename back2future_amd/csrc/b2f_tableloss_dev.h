@@ -1,6 +1,6 @@
-// What the four kernel files of the table loss share (b2f_tableloss.hip: test.lua:266-297; b2f_tableloss_ft.hip: the fine-tuning terms of
-// README.md:89-102; b2f_tableloss_grad.hip: the gradient table of train.lua:428-468; b2f_tableloss_grad_ft.hip: that gradient with the
-// fine-tuning criteria).  Device side: how a thread loads and stores its pixels of a row, where the planes of a level lie, the
+// What the kernel files of the table loss share (b2f_tableloss.hip: test.lua:266-297; b2f_tableloss_ft.hip: the fine-tuning terms of
+// README.md:89-102; b2f_tableloss_ssim.hip: the SSIM + L1 sums; b2f_tableloss_grad.hip: the gradient table of train.lua:428-468;
+// b2f_tableloss_grad_ft.hip: that gradient with the fine-tuning criteria; b2f_tableloss_grad_ssim.hip: with the SSIM + L1 term).  Device side: how a thread loads and stores its pixels of a row, where the planes of a level lie, the
 // five-point cross and the first-order smoothness of the two gradient kernels.  Host side: the one walk over the levels that every
 // launcher makes (loss_levels).  For .hip files only.
 #pragma once

@@ -75,8 +75,10 @@ __device__ __forceinline__ void smooth_flow4(const float *pl, const Group &g, co
     }
 }
 
-// Image blockIdx.y of one level: its blocks stride over the groups of kPx pixels of its rows.
-template <bool Past, bool Second>
+// Image blockIdx.y of one level: its blocks stride over the groups of kPx pixels of its rows.  FlowOnly: phases 1 and 2 alone -- the
+// flow planes of a table whose occlusion and image planes table_loss_grad_ssim_kernel writes (b2f_tableloss_grad_ssim.hip); gp.o,
+// gp.iw1 and gp.iw3 are not touched.
+template <bool Past, bool Second, bool FlowOnly>
 __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs lp, GradPtrs gp, int h, int w, float kd, GradFtCoef kf)
 {
     const GradCoef &k = kf.k;
@@ -86,8 +88,8 @@ __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs 
     const float *iw[2] = {lp.iw1 + b * 3 * hw, lp.iw3 + b * 3 * hw};
     float *gf = gp.f + b * 2 * hw, *gpp = Past ? gp.p + b * 2 * hw : nullptr, *go = gp.o + b * 2 * hw;
     float *giw[2] = {gp.iw1 + b * 3 * hw, gp.iw3 + b * 3 * hw};
-    const bool on_s = (k.on & kGradSmooth) != 0, on_cv = Past && (k.on & kGradConstVel) != 0, on_p = (k.on & kGradPhoto) != 0,
-               on_so = (k.on & kGradSmoothOcc) != 0, obgcc = (kf.ft & kGradFtObgcc) != 0;
+    const bool on_s = (k.on & kGradSmooth) != 0, on_cv = Past && (k.on & kGradConstVel) != 0, on_p = !FlowOnly && (k.on & kGradPhoto) != 0,
+               on_so = !FlowOnly && (k.on & kGradSmoothOcc) != 0, obgcc = (kf.ft & kGradFtObgcc) != 0;
     const bool want_w1 = on_so || (!Second && on_s), want_w2 = Second && on_s;
     const size_t gpr = ((size_t)w + kPx - 1) / kPx, groups = gpr * (size_t)h;   // groups per row, per image
     for (size_t gi = (size_t)blockIdx.x * kThreads + threadIdx.x; gi < groups; gi += (size_t)gridDim.x * kThreads) {
@@ -180,6 +182,7 @@ __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs 
                 store_px(gpp + (size_t)c * hw + g.i0, g.n, out);
             }
         }
+        if (FlowOnly) continue;
         // 3. the occlusions: their centres and S with the quadratic penalty
         float oc[2][kPx];
         double So[2][kPx];
@@ -262,22 +265,30 @@ __global__ void __launch_bounds__(kThreads) table_loss_grad_ft_kernel(LevelPtrs 
 
 }  // namespace
 
+// one level's launch of an instantiation
+template <bool Past, bool Second, bool FlowOnly>
+static void launch_level(const LossLevel &v, const GradFtCoef &kf, hipStream_t s)
+{
+    hipLaunchKernelGGL((table_loss_grad_ft_kernel<Past, Second, FlowOnly>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, kf);
+}
+
 hipError_t launch_table_loss_grad_ft(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref,
-                                     size_t ref_stride, const float *pyr, double flow_scale, const GradFtCoef *coef, hipStream_t s)
+                                     size_t ref_stride, const float *pyr, double flow_scale, const GradFtCoef *coef, hipStream_t s, bool flow_only)
 {
     LossLevel lv[kLossMaxLevels];
     if (!grad || !coef || !loss_levels(table, grad, L, past, n, H, W, ref, ref_stride, pyr, flow_scale, lv)) return hipErrorInvalidValue;
     for (int j = 0; j < L; ++j) {
         const LossLevel &v = lv[j];
         const bool second = (coef[j].ft & kGradFtSecond) != 0;
-        if (past && second)
-            hipLaunchKernelGGL((table_loss_grad_ft_kernel<true, true>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, coef[j]);
-        else if (past)
-            hipLaunchKernelGGL((table_loss_grad_ft_kernel<true, false>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, coef[j]);
-        else if (second)
-            hipLaunchKernelGGL((table_loss_grad_ft_kernel<false, true>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, coef[j]);
-        else
-            hipLaunchKernelGGL((table_loss_grad_ft_kernel<false, false>), v.grid, dim3(kThreads), 0, s, v.lp, v.gp, v.h, v.w, v.kd, coef[j]);
+        if (flow_only) {
+            if (past && second) launch_level<true, true, true>(v, coef[j], s);
+            else if (past) launch_level<true, false, true>(v, coef[j], s);
+            else if (second) launch_level<false, true, true>(v, coef[j], s);
+            else launch_level<false, false, true>(v, coef[j], s);
+        } else if (past && second) launch_level<true, true, false>(v, coef[j], s);
+        else if (past) launch_level<true, false, false>(v, coef[j], s);
+        else if (second) launch_level<false, true, false>(v, coef[j], s);
+        else launch_level<false, false, false>(v, coef[j], s);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

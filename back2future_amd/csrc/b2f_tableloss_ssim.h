@@ -68,15 +68,31 @@ B2F_HD inline double ssim_tap3(double a, double c, double b)
     return (kSsimGe * a + kSsimGc * c) + kSsimGe * b;
 }
 
-// 1 - l * cs of one channel from its five window sums: mu_x = G(x), mu_y = G(y), gxx = G(x x), gyy = G(y y), gxy = G(x y)
-B2F_HD inline double ssim_term(double mu_x, double mu_y, double gxx, double gyy, double gxy)
+// l, cs and their denominators A, Bd of one channel from its five window sums: mu_x = G(x), mu_y = G(y), gxx = G(x x), gyy = G(y y),
+// gxy = G(x y) (OSSIML1Criterion.lua:115-116; the gradient of b2f_tableloss_grad_ssim.h divides by A and Bd again)
+struct SsimParts {
+    double l, cs, A, Bd;
+};
+
+B2F_HD inline SsimParts ssim_parts(double mu_x, double mu_y, double gxx, double gyy, double gxy)
 {
 #pragma clang fp contract(off)
     const double xx = mu_x * mu_x, yy = mu_y * mu_y, xy = mu_x * mu_y;
     const double s_x = gxx - xx, s_y = gyy - yy, s_xy = gxy - xy;
-    const double l = (2.0 * xy + kSsimC1) / ((xx + yy) + kSsimC1);
-    const double cs = (2.0 * s_xy + kSsimC2) / ((s_x + s_y) + kSsimC2);
-    return 1.0 - l * cs;
+    SsimParts p;
+    p.A = (xx + yy) + kSsimC1;
+    p.Bd = (s_x + s_y) + kSsimC2;
+    p.l = (2.0 * xy + kSsimC1) / p.A;
+    p.cs = (2.0 * s_xy + kSsimC2) / p.Bd;
+    return p;
+}
+
+// 1 - l * cs of one channel
+B2F_HD inline double ssim_term(double mu_x, double mu_y, double gxx, double gyy, double gxy)
+{
+#pragma clang fp contract(off)
+    const SsimParts p = ssim_parts(mu_x, mu_y, gxx, gyy, gxy);
+    return 1.0 - p.l * p.cs;
 }
 
 // what one pixel of one direction adds to words 16 .. 21 of its record

@@ -13,8 +13,7 @@
 //     for both directions.
 // The per-pixel functions are those of b2f_tableloss_ssim.h, which the host entry (b2f_table_loss_ssim_host) shares.
 #include "b2f_ctx.h"
-#include "b2f_tableloss_ssim.h"
-#include "b2f_tableloss_dev.h"
+#include "b2f_tableloss_ssim_dev.h"
 
 namespace b2f {
 
@@ -27,7 +26,7 @@ constexpr int kWaves = kThreads / kWave;
 constexpr int kRec = B2F_LOSS_SSIM_WORDS;
 constexpr int kFirst = B2F_LOSS_SSIM_Q30;   // the first word table_loss_ssim_kernel adds to
 constexpr int kWords = B2F_LOSS_SSIM_RANGE_USED - kFirst;
-constexpr int kCols = kPx + 2;              // the columns x0 - 1 .. x0 + 4 of a group's windows
+constexpr int kCols = kSsimCols;            // the columns x0 - 1 .. x0 + 4 of a group's windows (b2f_tableloss_ssim_dev.h)
 
 // the encoded minimum (lo) and maximum (hi) of p[0 .. len) but its NaNs, over the threads of a block's stride
 __device__ __forceinline__ void range_of(const float *p, size_t len, size_t t0, size_t stride, unsigned &lo, unsigned &hi)
@@ -126,43 +125,6 @@ __global__ void __launch_bounds__(kThreads) table_loss_range_finish_kernel(unsig
         rec[B2F_LOSS_SSIM_RANGE_USED] = mn;
         rec[B2F_LOSS_SSIM_RANGE_USED + 1] = mx;
     }
-}
-
-// The columns x0 - 1 .. x0 + 4 of one row of a plane, clamped to the row (replication), normalised: p points at the group's first pixel,
-// n of its pixels are in the row.  Every index lies in the row (k < n, before, more).
-__device__ __forceinline__ void load_row(const float *p, int n, bool before, bool more, const SsimRange &rg, double *t)
-{
-    float v[kCols];
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) v[k] = 0.0f;
-    load_px(p, n, v + 1);
-    v[0] = before ? p[-1] : v[1];
-#pragma unroll
-    for (int k = 1; k < kPx; ++k) v[k + 1] = k < n ? v[k + 1] : v[k];   // past the row's end: its last pixel
-    v[kPx + 1] = more ? p[kPx] : v[kPx];
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) t[k] = ssim_norm(v[k], rg);
-}
-
-// the three clamped rows of a group in one plane
-__device__ __forceinline__ void load_rows(const float *pl, size_t i0, size_t up, size_t down, int n, bool before, bool more, const SsimRange &rg,
-                                          double (*t)[kCols])
-{
-    load_row(pl + i0 - up, n, before, more, rg, t[0]);
-    load_row(pl + i0, n, before, more, rg, t[1]);
-    load_row(pl + i0 + down, n, before, more, rg, t[2]);
-}
-
-// the window sums of the group's four pixels from the three rows of a product a * b (a == b: of squares; b == nullptr: of a itself)
-__device__ __forceinline__ void window4(const double (*a)[kCols], const double (*b)[kCols], double *g)
-{
-#pragma clang fp contract(off)
-    double col[kCols];
-#pragma unroll
-    for (int i = 0; i < kCols; ++i)
-        col[i] = b ? ssim_tap3(a[0][i] * b[0][i], a[1][i] * b[1][i], a[2][i] * b[2][i]) : ssim_tap3(a[0][i], a[1][i], a[2][i]);
-#pragma unroll
-    for (int k = 0; k < kPx; ++k) g[k] = ssim_tap3(col[k], col[k + 1], col[k + 2]);
 }
 
 // Image blockIdx.y of one level: its blocks stride over the groups of kPx pixels of its rows.  loss: the record of image 0 at this

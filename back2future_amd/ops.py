@@ -306,15 +306,17 @@ def table_loss(table, ref, flow_scale=20.0, model=None, objective="pme", ssim_ra
     return loss
 
 
-def table_loss_grad(table, ref, flow_scale=20.0, options=None, model=None):
+def table_loss_grad(table, ref, flow_scale=20.0, options=None, model=None, ssim_range="batch"):
     """`gradOutputs` of train.lua:428-468 for an output table of model:forward: the gradient of the -optimize pme objective
     (first-order smoothness with L1, constant velocity, OBCC with L1, occlusion smoothness, occlusion prior; include/b2f.h gives every
     element) with respect to each tensor of the table.  table, ref, model as for table_loss; options: of
     back2future.loss_grad_options (None: the defaults of opts.lua:61-73), or of back2future.loss_grad_ft_options for the objectives
     with second-order smoothness and / or OBGCC (b2f_table_loss_grad_ft_host, b2f_op_table_loss_grad_ft) -> a list of float32 arrays
-    with the table's shapes.
+    with the table's shapes.  With the options of back2future.loss_grad_ssim_options the photometric term is the occlusion-aware SSIM +
+    L1 of criterions/OSSIML1Criterion.lua:165-302 (b2f_table_loss_grad_ssim_host, b2f_op_table_loss_grad_ssim) on values normalised by
+    ssim_range, as for table_loss; ssim_range is not read otherwise.
     model=None computes on the CPU (b2f_table_loss_grad_host), a Model on its GPU (b2f_op_table_loss_grad): the bits are the same."""
-    from .back2future import _grad_opts_ptr, _grad_entry
+    from .back2future import _grad_opts_ptr, _grad_entry, _grad_range_args
     r = np.asarray(ref)
     if r.ndim != 4 or r.shape[1] != 3 or min(r.shape) < 1:
         raise ValueError("table_loss_grad: expected an n x 3 x H x W reference image, got shape %r" % (np.shape(ref),))
@@ -333,13 +335,14 @@ def table_loss_grad(table, ref, flow_scale=20.0, options=None, model=None):
     ptrs = (_lib.c_float_p * len(tab))(*[_lib.fptr(t) for t in tab])
     grad = [np.empty(t.shape, np.float32) for t in tab]
     gp = (_lib.c_float_p * len(grad))(*[_lib.fptr(g) for g in grad])
+    tail = _grad_range_args(options, ssim_range, len(tab) // per, "table_loss_grad")
     if model is None:
-        _lib.check(_grad_entry("b2f_table_loss_grad_host", options)(ptrs, len(tab), n, H, W, int(per == 5), _lib.fptr(r), float(flow_scale), _grad_opts_ptr(options), gp))
+        _lib.check(_grad_entry("b2f_table_loss_grad_host", options)(ptrs, len(tab), n, H, W, int(per == 5), _lib.fptr(r), float(flow_scale), _grad_opts_ptr(options), gp, *tail))
     else:
         if per != (5 if model.past_flow else 4) and len(tab) % (5 if model.past_flow else 4) == 0:
             raise ValueError("table_loss_grad: a %s table of %d tensors on a %s model would be read as the model's kind; use a model of the "
                              "table's kind or model=None" % ("Soft" if per == 5 else "Hard", len(tab), "Soft" if model.past_flow else "Hard"))
-        _lib.check(_grad_entry("b2f_op_table_loss_grad", options)(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), _grad_opts_ptr(options), gp))
+        _lib.check(_grad_entry("b2f_op_table_loss_grad", options)(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(r), float(flow_scale), _grad_opts_ptr(options), gp, *tail))
     return grad
 
 

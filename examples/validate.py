@@ -15,12 +15,14 @@ table (Model.forwardLossGrad, in the same pass as the records), under the chosen
 --grad refuses the two Soft objectives), and prints per level and tensor its L2 norm and largest magnitude over the clip.  --grad-ft
 does the same with the gradients of SecondOrderSmoothnessCriterion and OBGCCriterion (back2future.loss_grad_ft_options): any
 --objective NAME, or without one both criteria with alpha = beta = gamma = 1; its loss lines come from the 192-byte records.
+--grad-ssim does the same with the gradient of the SSIM (+ L1) term (back2future.loss_grad_ssim_options; OSSIML1Criterion.lua:165-302):
+--pme-criterion OSSIM | OSSIML1 (the default) and --ssim-range as above; its loss lines come from the 256-byte records of the same pass.
 
 Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME]
-       [--pme-criterion OSSIM|OSSIML1 [--ssim-range image|batch]] [--grad | --grad-ft]
+       [--pme-criterion OSSIM|OSSIML1 [--ssim-range image|batch]] [--grad | --grad-ft | --grad-ssim]
 FRAMES_DIR: 8-bit frames, sorted by name; they are cropped (top left) to multiples of 64 and normalized with
 back2future.normalize.  MODEL as for examples/run_sequence.py.  --scale: pixels per unit of raw network flow (default 20).
-Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`; with --grad or --grad-ft then one line
+Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`; with --grad, --grad-ft or --grad-ssim then one line
 `grad LEVEL TENSOR l2 max` per level and tensor (f, p for Soft models, o, iw1, iw3).
 """
 import os
@@ -45,11 +47,11 @@ def load_unit(path, H, W):
 def main():
     args = list(sys.argv[1:])
     scale, like, objective, criterion, ssim_range = 20.0, "test", None, None, "image"
-    size_average, grad_ft = "--size-average" in args, "--grad-ft" in args
-    grad = "--grad" in args or grad_ft
-    if "--grad" in args and grad_ft:
-        sys.exit("--grad and --grad-ft exclude one another")
-    args = [a for a in args if a not in ("--size-average", "--grad", "--grad-ft")]
+    size_average, grad_ft, grad_ssim = "--size-average" in args, "--grad-ft" in args, "--grad-ssim" in args
+    grad = "--grad" in args or grad_ft or grad_ssim
+    if ("--grad" in args) + grad_ft + grad_ssim > 1:
+        sys.exit("--grad, --grad-ft and --grad-ssim exclude one another")
+    args = [a for a in args if a not in ("--size-average", "--grad", "--grad-ft", "--grad-ssim")]
     for flag in ("--scale", "--like", "--objective", "--pme-criterion", "--ssim-range"):
         if flag in args:
             i = args.index(flag)
@@ -75,10 +77,14 @@ def main():
         sys.exit("--pme-criterion: one of " + ", ".join(sorted(back2future.SSIM_ALPHA)))
     if ssim_range not in ("image", "batch"):
         sys.exit("--ssim-range: image or batch")
-    if criterion is not None and (objective is not None or grad):
-        sys.exit("--pme-criterion goes without --objective, --grad and --grad-ft (the gradient of this criterion is not provided)")
+    if grad_ssim and criterion is None:
+        criterion = "OSSIML1"
+    if criterion is not None and (objective is not None or (grad and not grad_ssim)):
+        sys.exit("--pme-criterion goes without --objective, --grad and --grad-ft (the gradient of this criterion is that of --grad-ssim)")
     options = None
-    if grad:
+    if grad_ssim:
+        options = back2future.loss_grad_ssim_options(size_average=size_average, pme_criterion=criterion)
+    elif grad:
         try:
             make = back2future.loss_grad_ft_options if grad_ft else back2future.loss_grad_options
             options = make(size_average=size_average, objective=objective)
@@ -99,7 +105,7 @@ def main():
     for b0 in range(0, len(frames) - 2, BATCH):
         x = np.stack([np.concatenate(frames[i:i + 3], axis=0) for i in range(b0, min(b0 + BATCH, len(frames) - 2))])
         if grad:
-            g, rec = m.forwardLossGrad(x, flow_scale=scale, options=options)
+            g, rec = m.forwardLossGrad(x, flow_scale=scale, options=options, ssim_range=ssim_range)
             records.append(rec)
             sq = [float((t.astype(np.float64) ** 2).sum()) for t in g]
             mx = [float(np.abs(t).max()) for t in g]

@@ -747,7 +747,7 @@ B2F_API int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, 
  * unusable (not mx > mn, or either not finite), it adds to neither and counts in SSIM_NONFINITE[d].  Any other pixel-direction adds
  * nothing: OUTSIDE and the occlusion weight are those of OBCCriterion (lines 121-151 against OBCCriterion.lua:78-105).  The criterion's
  * value is sum over d of ((alpha * SSIM_d + (1 - alpha) * L1N_d) / 2^30 + OUTSIDE_d) / (3 * 2) with alpha = 1 (OSSIM) or 0.85 (OSSIML1)
- * (back2future.loss_summary).  updateGradInput is not provided.                                                                  */
+ * (back2future.loss_summary).  updateGradInput is that of the *_grad_ssim entries below.                                      */
 /* The six b2f_*_loss_ft entries with records of 32 words (256 bytes) and the range: same checks, same sub-batching, same workspaces. */
 B2F_API int b2f_table_loss_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
                              double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
@@ -772,6 +772,68 @@ B2F_API int b2f_loss_ssim_weights(double out[2]);
 #define B2F_LOSS_SSIM_RANGE_USED 22    /* [2] float bits, zero-extended, of the mn / mx used for this image and level */
 #define B2F_LOSS_SSIM_RANGE_OWN 24     /* [2] float bits of this image's own minimum / maximum at this level */
 #define B2F_LOSS_SSIM_WORDS 32         /* words 26 .. 31 are reserved, always 0 */
+/* ---- the gradient of the SSIM + L1 photometric term with respect to the output table (b2f_version() >= 1011) ----
+ * The *_grad_ssim entries are the *_grad_ft entries above with the photometric term of a level replaced by that of
+ * criterions/OSSIML1Criterion.lua:165-302 (updateGradInput), combined with the other terms as train.lua:428-468 does.  Everything
+ * not named here -- inputs, R_j, m_d (the past flow for d = 0 on Soft tables), the coefficients k_*, N1, N2, CV_c, S, S2, the prior,
+ * the rule for a weight of exactly 0, the range (mn, mx) with its three modes, t(v), the window G in its fixed order, ge, gc, C1 =
+ * 1e-4, C2 = 9e-4, P1, D1, fp64 without fused multiply-adds, one rounding to fp32 on store -- is as stated above.  Per level,
+ * direction d and channel c, with x = t(iw_d[c]), y = t(R_j[c]) and the five window sums mu_x, mu_y, gxx = G(x x), gyy = G(y y),
+ * gxy = G(x y):
+ *   xx = mu_x * mu_x, yy = mu_y * mu_y, xy = mu_x * mu_y; s_x = gxx - xx, s_y = gyy - yy, s_xy = gxy - xy
+ *   A = (xx + yy) + C1, Bd = (s_x + s_y) + C2; l = (2.0 * xy + C1) / A, cs = (2.0 * s_xy + C2) / Bd
+ *   gw = gc * gc                                                       (the window's centre tap, lines 204, 216)
+ *   dl = ((2.0 * gw) * (mu_y - mu_x * l)) / A                           (line 217)
+ *   dcs = ((2.0 * gw) * ((y - mu_y) - cs * (x - mu_x))) / Bd            (line 218)
+ *   Q_c = dl * cs + l * dcs
+ *   T_c = the enabled ones of  -(alpha * Q_c),  (1.0 - alpha) * D1(x - y)  added left to right; alpha == 0 resp. (1.0 - alpha) == 0:
+ *         not evaluated; +0.0 without a term
+ *   G_iw_d[c] = m_d ? k_p * (T_c * (double)o[1-d]) : +0.0
+ *   PO_{1-d}  = m_d ? (the enabled ones of alpha * S, (1.0 - alpha) * B, with S and B of the records above) : 1.0
+ *   G_o[c]    = (k_p * PO_c + k_so * S(o[c],D2)) + k_pr * (1.0 - (double)o[1-c])
+ * G_f and G_p are those of the *_grad entries, with smooth_second_order those of the *_grad_ft entries.  The range is not checked
+ * for usability: on a zero or non-finite span the values follow IEEE (NaN or Inf in the elements that read them), which is what the
+ * Lua gives; a pixel-direction outside the image is +0.0 / 1.0 whatever the range.  Five places where this is not the derivative of
+ * the records' value, all kept:
+ *   1. Centre tap only: dl and dcs are the derivative of the pixel's own window term with respect to the pixel's own value; the eight
+ *      neighbouring windows that also contain the pixel are dropped.
+ *   2. Border: under replication padding a border pixel occurs several times in its own window (a corner pixel has the weight
+ *      (gc + ge)^2); the Lua uses gw everywhere.
+ *   3. Range: the gradient is with respect to the normalised image; the factor 1 / (mx - mn) and the dependence of mn and mx on the
+ *      inputs are absent.
+ *   4. Outside the image: a pixel-direction whose target leaves the image adds penalty_out = 1 to the occlusion gradient.
+ *   5. Occlusion prior: its 1 - o[other] comes along unchanged.                                                                  */
+typedef struct b2f_loss_grad_ssim_opts {
+    double smooth_flow, const_vel, pme, smooth_occ, prior_occ;   /* as b2f_loss_grad_opts */
+    double level_weights[7];
+    int size_average;
+    int smooth_second_order;                                     /* -smooth_second_order: 0 | 1 (orthogonal in model.lua) */
+    double ssim_alpha;                                           /* finite, in [0, 1]: 1 is OSSIM, 0.85 OSSIML1 */
+} b2f_loss_grad_ssim_opts;
+/* b2f_loss_grad_defaults, smooth_second_order = 0, ssim_alpha = 0.85 */
+B2F_API int b2f_loss_grad_ssim_defaults(b2f_loss_grad_ssim_opts *opts);
+/* The six *_grad_ft entries with these options and the range of the *_ssim entries: the checks of both families (and ssim_alpha in
+ * [0, 1]), same sub-batching, same workspaces; a refusal writes nothing.  B2F_SSIM_RANGE_BATCH is refused by the forward entries when
+ * the request would be cut into more than one sub-batch, and by the multi entry always.  The optional records of the forward entries
+ * are the 32 words of b2f_forward_loss_ssim, from the same pyramid and the same ranges.                                            */
+B2F_API int b2f_table_loss_grad_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                                  double flow_scale, const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode,
+                                  const float *ranges);
+B2F_API int b2f_table_loss_grad_ssim_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W,
+                                    const float *dev_ref, double flow_scale, const b2f_loss_grad_ssim_opts *opts,
+                                    float *const *dev_grad, void *stream, int range_mode, const float *ranges);
+B2F_API int b2f_op_table_loss_grad_ssim(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                                double flow_scale, const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode,
+                                const float *ranges);
+B2F_API int b2f_forward_loss_grad_ssim(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale,
+                               const b2f_loss_grad_ssim_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                               float *const *outs, int range_mode, const float *ranges);
+B2F_API int b2f_forward_loss_grad_ssim_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                      const b2f_loss_grad_ssim_opts *opts, unsigned long long *dev_loss, float *const *dev_grad,
+                                      int n_outs, void *stream, int range_mode, const float *ranges);
+B2F_API int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
+                                     const b2f_loss_grad_ssim_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                                     int range_mode, const float *ranges);
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature

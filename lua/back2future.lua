@@ -216,6 +216,29 @@ int b2f_forward_loss_grad_ft(b2f_ctx *ctx, const float *x, int n, int H, int W, 
 int b2f_forward_loss_grad_ft_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                                     const b2f_loss_grad_ft_opts *opts, unsigned long long *dev_loss, float *const *dev_grad,
                                     int n_outs, void *stream);
+typedef struct b2f_loss_grad_ssim_opts {
+    double smooth_flow, const_vel, pme, smooth_occ, prior_occ;
+    double level_weights[7];
+    int size_average;
+    int smooth_second_order;
+    double ssim_alpha;
+} b2f_loss_grad_ssim_opts;
+int b2f_loss_grad_ssim_defaults(b2f_loss_grad_ssim_opts *opts);
+int b2f_table_loss_grad_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                                  double flow_scale, const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode,
+                                  const float *ranges);
+int b2f_table_loss_grad_ssim_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W,
+                                    const float *dev_ref, double flow_scale, const b2f_loss_grad_ssim_opts *opts,
+                                    float *const *dev_grad, void *stream, int range_mode, const float *ranges);
+int b2f_op_table_loss_grad_ssim(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                                double flow_scale, const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode,
+                                const float *ranges);
+int b2f_forward_loss_grad_ssim(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale,
+                               const b2f_loss_grad_ssim_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                               float *const *outs, int range_mode, const float *ranges);
+int b2f_forward_loss_grad_ssim_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                      const b2f_loss_grad_ssim_opts *opts, unsigned long long *dev_loss, float *const *dev_grad,
+                                      int n_outs, void *stream, int range_mode, const float *ranges);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -266,6 +289,9 @@ int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int 
                                 const b2f_loss_grad_opts *opts, unsigned long long *loss, float *const *grad, int n_outs);
 int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
                                    const b2f_loss_grad_ft_opts *opts, unsigned long long *loss, float *const *grad, int n_outs);
+int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
+                                     const b2f_loss_grad_ssim_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                                     int range_mode, const float *ranges);
 ]]
 
 local lib = ffi.load(os.getenv('B2F_LIB') or 'libb2f.so')
