@@ -117,6 +117,16 @@ SIGNATURES = {
                                       C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "b2f_stream_push_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int)]),
+    "b2f_stream_open_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "b2f_stream_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "b2f_stream_push_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_ulonglong), c_float_p, c_float_p,
+                                       C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), c_float_p, C.POINTER(C.c_int)]),
+    "b2f_stream_push_warp_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "b2f_stream_push_past": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte),
+                                       C.POINTER(C.c_int)]),
+    "b2f_stream_push_past_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int)]),
     "b2f_flow_score_host": (C.c_int, [c_float_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_float_p, C.POINTER(C.c_ubyte),
                                       C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong)]),
     "b2f_flow_score_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,

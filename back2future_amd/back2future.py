@@ -25,6 +25,7 @@ occ_threshold = 0.6666                                                     # bac
 IN_NORMALIZED, IN_UNIT, IN_U8 = 0, 1, 2
 # layout of the flow pictures (include/b2f.h): n x 3 x H x W, the reference's tensor order, or n x H x W x 3
 RGB_PLANAR, RGB_PACKED = 0, 1
+STREAM_WARP, STREAM_PAST = 1, 2   # B2F_STREAM_*: the flags of b2f_stream_open_ex
 # words of a score record (include/b2f.h, B2F_SCORE_*): counted pixels, Q20 error sums and Fl outliers per bucket (0 occluded "bwd",
 # 1 visible, 2 occluded "fwd", 3 unlabelled), the 3 x 3 occlusion matrix (ground-truth class major), NaN errors
 SCORE_PIXELS, SCORE_EPE_Q20, SCORE_OUTLIERS, SCORE_OCC, SCORE_NONFINITE, SCORE_WORDS = 0, 4, 8, 12, 21, 22
@@ -342,7 +343,7 @@ class FlowStream(object):
     of the triplet of frames (k-2, k-1, k) with a leading `cams` axis -- with the model's default options output k-3 of
     computeFlowSequence(dtype=np.float32) on the same frames, bit for bit.  A context manager: `with model.openStream(H, W) as st:`."""
 
-    def __init__(self, model, H0, W0, cams=1, dtype=np.uint8):
+    def __init__(self, model, H0, W0, cams=1, dtype=np.uint8, flags=0):
         try:
             dt = np.dtype(dtype)
         except TypeError:
@@ -354,8 +355,12 @@ class FlowStream(object):
         self._h = None
         self.cams, self.H0, self.W0, self.dtype = int(cams), int(H0), int(W0), dt
         self.in_kind = IN_U8 if dt == np.uint8 else IN_UNIT
+        self.flags = int(flags)   # STREAM_*: what the stream was opened for (0: a plain stream, b2f_stream_open itself)
         h = C.c_void_p()
-        _lib.check(_lib.lib().b2f_stream_open(model._h, self.cams, self.in_kind, self.H0, self.W0, C.byref(h)))
+        if self.flags:
+            _lib.check(_lib.lib().b2f_stream_open_ex(model._h, self.cams, self.in_kind, self.H0, self.W0, self.flags, C.byref(h)))
+        else:
+            _lib.check(_lib.lib().b2f_stream_open(model._h, self.cams, self.in_kind, self.H0, self.W0, C.byref(h)))
         self._h = h
         self._model = model
         model._streams.append(weakref.ref(self))   # Model.close closes the streams that are still open
@@ -441,6 +446,82 @@ class FlowStream(object):
         ready = C.c_int()
         _lib.check(_lib.lib().b2f_stream_push_device(self._h, p(d_frames), p(d_flow), p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream),
                                                      C.byref(ready)))
+        return bool(ready.value)
+
+
+class MotionStream(FlowStream):
+    """What Model.openStream(warp=True) / openStream(past=True) returns: a FlowStream opened with flags (b2f_stream_open_ex), which adds
+    the pushes that need them -- motion compensation per pushed frame (warp=True: the stream keeps the caller's frames of its last
+    three pushes) and the past flow of a Soft model (past=True).  Every push of FlowStream works on it as well, and may alternate with
+    the new ones.  A push the stream was not opened for is refused by the library with a message that names the missing flag, and
+    leaves the stream as it was.  A stream opened without either stays a plain FlowStream, which has none of these pushes."""
+
+    def __init__(self, model, H0, W0, cams=1, dtype=np.uint8, warp=False, past=False):
+        FlowStream.__init__(self, model, H0, W0, cams, dtype, (STREAM_WARP if warp else 0) | (STREAM_PAST if past else 0))
+
+    def pushWarp(self, frames, flow_scale=20.0, want_warped=True, want_photo=True, want_flow=False, want_masks=False, want_prob=False,
+                 own_past_flow=False, want_past=False, out=None):
+        """push with motion compensation as the output (b2f_stream_push_warp; a stream opened with warp=True): None for the first two
+        pushes, then what computeFlowSequenceWarp returns for one centre frame per camera, in its order and with its keywords --
+        (warped, photo[, flow][, fwd_occ, bwd_occ][, occ_prob][, past_flow]) with n = cams, a single array alone -- where warped[:, 0]
+        is the frame of two pushes ago and warped[:, 1] the frame of this push, both sampled onto the frame of the push before.
+        own_past_flow / want_past need a stream opened with past=True as well.  photo_summary reads the records."""
+        who = "pushWarp"
+        own = _own_past(own_past_flow, want_past, who)
+        v = self._frames(frames, who)
+        outs = _warp_outputs(self.cams, self.H0, self.W0, self.in_kind == IN_U8, want_warped, want_photo, want_flow, want_masks, want_prob, out,
+                             who, want_past)
+        warped, photo, flow, fwd, bwd, prob, past = outs
+        u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+        fp = lambda a: _lib.fptr(a) if a is not None else None
+        ready = C.c_int()
+        _lib.check(_lib.lib().b2f_stream_push_warp(self._h, C.c_void_p(v.ctypes.data), float(flow_scale), 1 if own else 0,
+                                                   C.c_void_p(warped.ctypes.data) if warped is not None else None,
+                                                   photo.ctypes.data_as(C.POINTER(C.c_ulonglong)) if photo is not None else None,
+                                                   fp(flow), fp(prob), u8p(fwd), u8p(bwd), fp(past), C.byref(ready)))
+        if not ready.value:
+            return None
+        res = tuple(a for a in outs if a is not None)
+        return res[0] if len(res) == 1 else res
+
+    def pushPast(self, frames, out=None, occ_prob=False):
+        """push with the past flow of a Soft model (b2f_stream_push_past; a stream opened with past=True): None for the first two
+        pushes, then (flow, past_flow, fwd_occ, bwd_occ[, occ_prob]) as computeFlowSequencePast for one centre frame per camera;
+        out = those buffers (its masks may be None)."""
+        v = self._frames(frames, "pushPast")
+        flow, past, fwd, bwd, occ = _past_outputs(self.cams, self.H0, self.W0, occ_prob, out, "pushPast")
+        u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+        ready = C.c_int()
+        _lib.check(_lib.lib().b2f_stream_push_past(self._h, C.c_void_p(v.ctypes.data), _lib.fptr(flow), _lib.fptr(past),
+                                                   _lib.fptr(occ) if occ is not None else None, u8p(fwd), u8p(bwd), C.byref(ready)))
+        if not ready.value:
+            return None
+        return (flow, past, fwd, bwd) + ((occ,) if occ_prob else ())
+
+    def pushDeviceWarp(self, d_frames, flow_scale=20.0, d_warped=None, d_photo=None, d_flow=None, d_occ_prob=None, d_fwd_occ=None,
+                       d_bwd_occ=None, own_past_flow=False, d_past_flow=None, stream=None):
+        """b2f_stream_push_warp_device on device pointers (ints): d_frames cams x 3 x H0 x W0 of the stream's dtype, d_warped
+        cams x 2 x 3 x H0 x W0 of that dtype, d_photo cams x 14 uint64; at least one of the two, the rest optional.  Written only when
+        the call returns True (from the third push on).  Asynchronous on `stream`."""
+        self._open("pushDeviceWarp")
+        if not d_frames or not (d_warped or d_photo):
+            raise ValueError("pushDeviceWarp: d_frames and at least one of d_warped and d_photo are required")
+        p = lambda v: C.c_void_p(v) if v else None
+        ready = C.c_int()
+        _lib.check(_lib.lib().b2f_stream_push_warp_device(self._h, p(d_frames), float(flow_scale), 1 if own_past_flow else 0, p(d_warped), p(d_photo),
+                                                          p(d_flow), p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(d_past_flow), p(stream),
+                                                          C.byref(ready)))
+        return bool(ready.value)
+
+    def pushDevicePast(self, d_frames, d_flow, d_past_flow, d_occ_prob=None, d_fwd_occ=None, d_bwd_occ=None, stream=None):
+        """b2f_stream_push_past_device on device pointers (ints): pushDevice with the past flow in d_past_flow (cams x 2 x H0 x W0)."""
+        self._open("pushDevicePast")
+        if not d_frames or not d_flow or not d_past_flow:
+            raise ValueError("pushDevicePast: d_frames, d_flow and d_past_flow are required")
+        p = lambda v: C.c_void_p(v) if v else None
+        ready = C.c_int()
+        _lib.check(_lib.lib().b2f_stream_push_past_device(self._h, p(d_frames), p(d_flow), p(d_past_flow), p(d_occ_prob), p(d_fwd_occ),
+                                                          p(d_bwd_occ), p(stream), C.byref(ready)))
         return bool(ready.value)
 
 
@@ -1105,11 +1186,14 @@ class Model(object):
         _lib.check(_lib.lib().b2f_compute_flow_sequence_device_past(self._h, int(T), int(in_kind), p(d_frames), int(H0), int(W0), p(d_flow),
                                                                      p(d_past_flow), p(d_occ_prob), p(d_fwd_occ), p(d_bwd_occ), p(stream)))
 
-    def openStream(self, H0, W0, cams=1, dtype=np.uint8):
-        """A FlowStream of `cams` cameras delivering H0 x W0 frames of `dtype` (np.uint8 or np.float32 in [0,1]) one at a time."""
+    def openStream(self, H0, W0, cams=1, dtype=np.uint8, warp=False, past=False):
+        """A FlowStream of `cams` cameras delivering H0 x W0 frames of `dtype` (np.uint8 or np.float32 in [0,1]) one at a time.
+        warp=True: the stream keeps the caller's frames of its last three pushes, for pushWarp / pushDeviceWarp; past=True (Soft
+        models): it may return the past flow, for pushPast and the own_past_flow / want_past keywords of pushWarp.  With either the
+        stream is a MotionStream, the FlowStream that has those pushes."""
         if not getattr(self, "_h", None):
             raise ValueError("openStream: the model is closed")
-        return FlowStream(self, H0, W0, cams, dtype)
+        return MotionStream(self, H0, W0, cams, dtype, warp, past) if (warp or past) else FlowStream(self, H0, W0, cams, dtype)
 
     def computeFlowBatchRGB(self, im1, im2, im3, max=None, packed=False, want_flow=False, want_masks=False, out=None):
         """computeFlowBatch with the flow pictures as the output (b2f_compute_flow_batch_rgb): returns (rgb, max_used[, flow]

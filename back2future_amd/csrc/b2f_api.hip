@@ -1298,7 +1298,6 @@ int b2f::forward_device(b2f_ctx *c, const void *dev_in, int in_kind, int B, int 
     CHK(check_shape(B, H, W));
     if (dev_past && !c->past_flow)
         return fail("b2f: this model has no past-flow decoders (a Hard or two_frame model estimates the future flow only): there is no past flow to return");
-    if (dev_past && sp) return fail("b2f_stream_push: a stream does not return the past flow");
     HIPCHK(hipSetDevice(c->device));
     if (sp && !c->g.shipped()) return fail("b2f_stream_push: streams run on the shipped graph only (this context was made with b2f_init_ex options)");
     if (seq && !c->g.shipped()) return fail("b2f_forward_sequence_device: sequences run on the shipped graph only (this context was made with b2f_init_ex options)");

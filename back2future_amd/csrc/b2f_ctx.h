@@ -131,6 +131,10 @@ struct StreamPass {
     const float *past[8] = {nullptr}, *ref[8] = {nullptr}, *fut[8] = {nullptr};
     const void *frame_past = nullptr;
     int frame_kind = B2F_IN_UNIT;
+    // a stream opened with B2F_STREAM_WARP: the caller's own frames (H0 x W0, raw_kind bytes or floats, B images 3 planes apart) of
+    // pushes k - 2, k - 1 and k, which the warp of a push samples as im1 / im2 / im3; nullptr on a stream without the flag
+    const void *raw_past = nullptr, *raw_ref = nullptr, *raw_fut = nullptr;
+    int raw_kind = B2F_IN_UNIT;
 };
 
 // One of the two buffer sets the host-buffer entry point (b2f_compute_flow_batch) alternates between: while the
@@ -494,7 +498,11 @@ private:
 //            scaled frames): the input of the pyramid, and what est[3] of a Hard model warps two pushes later
 //   work     the buffers between the input and the outputs of a push (upload / image.scale / the network's outputs / the host
 //            entries' outputs), carved once at open for every output a push may ask for
-// and one page-locked block that stages pageable host buffers.
+//   raw      B2F_STREAM_WARP at a size that is no multiple of 64 only: 3 slots x [cam] of the caller's frames as pushed (at a /64 size
+//            the frame slots hold them): what the warp of a push samples, and the upload target of a host push
+//   warp     B2F_STREAM_WARP: the warped neighbours and the photometric records of a host push; B2F_STREAM_PAST: the past flow
+// and one page-locked block that stages pageable host buffers.  The pieces of a flag lie behind everything else, so a stream opened
+// without flags (b2f_stream_open) has the block it always had.
 struct b2f_stream {
     b2f_ctx *ctx = nullptr;
     int cams = 0, in_kind = B2F_IN_UNIT, H0 = 0, W0 = 0;
@@ -512,7 +520,13 @@ struct b2f_stream {
     float *d_flow32 = nullptr, *d_prob = nullptr;   // host pushes: outputs at H0 x W0 (= d_flow / the network's planes without a rescale)
     unsigned char *d_fo = nullptr, *d_bo = nullptr, *d_rgb = nullptr;
     double *d_max = nullptr;
-    char *pin = nullptr;               // staging of pageable host buffers: [frames | flow | occ_prob | masks | rgb | max]
+    int flags = 0;                     // B2F_STREAM_* of b2f_stream_open_ex
+    char *raw[3] = {nullptr};          // [slot]: cams frames as pushed (B2F_STREAM_WARP at a rescaled size; else null: frame[] holds them)
+    size_t raw_bytes = 0;              // of one slot
+    void *d_warp = nullptr;            // B2F_STREAM_WARP, host pushes: cams x 2 x 3 x H0 x W0 in the stream's element type ...
+    unsigned long long *d_photo = nullptr;   // ... and cams x B2F_PHOTO_WORDS words
+    float *d_past = nullptr, *d_past32 = nullptr;   // B2F_STREAM_PAST: skip_ubfs[3] at the network size and at H0 x W0 (= d_past without a rescale)
+    char *pin = nullptr;               // staging of pageable host buffers: [frames | flow | occ_prob | masks | rgb | max | warped | photo | past_flow]
     size_t pin_bytes = 0;
 };
 

@@ -203,7 +203,8 @@ struct NetBuffers {
 // that writes the flow, the probabilities and the masks is the one of a request without it); with out.own_past the warp places the
 // past frame's samples with it, read like the flow: from out.past32 or, at the network size, from net.past.
 // sp: a push of a stream -- the nb = cams frames go through the pyramid into the ring (net.scaled, where image.scale writes, is their
-// frame slot); the rest runs, and the outputs are written, only from the third push on.
+// frame slot); the rest runs, and the outputs are written, only from the third push on.  Its warp samples the frames of three pushes:
+// sp->raw_past / raw_ref / raw_fut, camera b's frames 3 planes apart.
 int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void *x, int kind, long planes, int nb, const NetBuffers &net,
                 const FlowOutputs &out, bool graph, hipStream_t s, const StreamPass *sp = nullptr)
 {
@@ -245,12 +246,15 @@ int run_kernels(b2f_ctx *c, const FlowRequest &r, const Geometry &g, const void 
         if (out.photo && !prob) return fail(std::string(r.who) + ": the photometric record needs skip_occs[3]");
         const float *own_past = !out.own_past ? nullptr : g.same ? net.past : out.past32;
         if (out.own_past && !own_past) return fail(std::string(r.who) + ": the warp with the model's own past flow needs the past-flow buffer");
-        const size_t esz = frames_kind == B2F_IN_U8 ? 1 : 4, stride = (r.seq ? 3 : 9) * g.hw0;
+        if (sp && (!sp->raw_past || !sp->raw_ref || !sp->raw_fut)) return fail(std::string(r.who) + ": the stream keeps no frames for the warp");
+        const int wkind = sp ? sp->raw_kind : frames_kind;
+        const size_t esz = wkind == B2F_IN_U8 ? 1 : 4, stride = ((r.seq || sp) ? 3 : 9) * g.hw0;
         const char *f0 = (const char *)frames;
+        const void *w1 = sp ? sp->raw_past : f0, *w2 = sp ? sp->raw_ref : f0 + 3 * g.hw0 * esz, *w3 = sp ? sp->raw_fut : f0 + 6 * g.hw0 * esz;
         ProfEvent pe;
         const bool timed = prof_open(c, s, "flow_warp", &pe);
-        const hipError_t e = launch_flow_warp(out.flow32 ? out.flow32 : net.flow, prob, nb, g.H0, g.W0, out.flow_scale, f0, f0 + 3 * g.hw0 * esz,
-                                              f0 + 6 * g.hw0 * esz, stride, frames_kind, out.warped, out.warped_kind, out.photo, s, own_past);
+        const hipError_t e = launch_flow_warp(out.flow32 ? out.flow32 : net.flow, prob, nb, g.H0, g.W0, out.flow_scale, w1, w2, w3, stride, wkind,
+                                              out.warped, out.warped_kind, out.photo, s, own_past);
         if (timed) prof_close(c, s, pe);
         HIPCHK(e);
     }
@@ -296,8 +300,16 @@ StreamPass stream_pass(const b2f_stream *st)
     }
     sp.frame_past = st->frame[s_past];
     sp.frame_kind = st->frame_kind;
+    if (st->flags & B2F_STREAM_WARP) {   // the caller's frames: the raw ring, or at a /64 size the frame slots themselves
+        char *const *raw = st->raw[0] ? st->raw : st->frame;
+        sp.raw_past = raw[s_past]; sp.raw_ref = raw[s_ref]; sp.raw_fut = raw[k0];
+        sp.raw_kind = st->in_kind;
+    }
     return sp;
 }
+
+// the slot of the raw ring a push writes (nullptr: the stream keeps none, or its frame slots serve)
+char *raw_slot(const b2f_stream *st) { return st->raw[st->pushed % 3]; }
 
 // what both push paths check before any HIP work: the request (check_request), the stream and its context
 int check_push(const FlowRequest &r)
@@ -309,6 +321,8 @@ int check_push(const FlowRequest &r)
         return fail(std::string(r.who) + ": the stream is broken (a HIP call failed inside an earlier push): call b2f_stream_reset");
     if (!st->ctx->g.shipped())
         return fail(std::string(r.who) + ": streams run on the shipped graph only (this context was made with b2f_init_ex options)");
+    if (r.o.want_past() && !st->ctx->past_flow)   // b2f_set_weights may have turned the context Hard since the stream was opened
+        return fail(std::string(r.who) + ": this model has no past-flow decoders (a Hard or two_frame model estimates the future flow only)");
     return 0;
 }
 
@@ -320,12 +334,15 @@ struct PushPlan {
     const float *occ_net;   // skip_occs[3] at the network size
 };
 
-PushPlan push_plan(const b2f_stream *st, bool want_prob)
+// want_prob: the push needs skip_occs[3] (occ_prob asked for, or a photometric record that is weighted with it); want_past: it runs the
+// past-flow decoder chain into d_past
+PushPlan push_plan(const b2f_stream *st, bool want_prob, bool want_past)
 {
     PushPlan p;
     p.g = geometry(st->ctx, st->H0, st->W0);
     p.sp = stream_pass(st);
     p.net = {st->d_tmp, (float *)st->frame[p.sp.slot], st->d_flow, (want_prob && p.g.C3 == 3) ? st->d_occ : nullptr, st->d_est3};
+    p.net.past = want_past ? st->d_past : nullptr;
     p.occ_net = p.g.C3 == 3 ? st->d_occ : st->d_est3;
     return p;
 }
@@ -340,43 +357,61 @@ int push_host_work(b2f_stream *st, const FlowRequest &r, int k_in, const int *k_
         return fail(std::string(r.who) + ": forced failure (option debug_fail_next)");
     }
     const ReqBatch req_guard(c, r);
-    const bool want_prob = o.occ_prob != nullptr, want_rgb = o.rgb != nullptr;
-    const PushPlan P = push_plan(st, want_prob);
+    // the photometric record is weighted with occ_prob on the device whether or not the caller downloads it
+    const bool want_prob = o.occ_prob != nullptr, need_prob = want_prob || o.photo != nullptr, want_rgb = o.rgb != nullptr;
+    const bool want_past = o.want_past();
+    const PushPlan P = push_plan(st, need_prob, want_past);
     const Geometry &g = P.g;
     const bool same = g.same, bytes_in = st->in_kind == B2F_IN_U8;
     const int n = st->cams;
     const size_t hw0 = g.hw0, in_bytes = (size_t)n * 3 * hw0 * (bytes_in ? 1 : 4);
     const size_t n_flow = (size_t)n * 2 * hw0 * 4, n_mask = (size_t)n * hw0, n_rgb = (size_t)n * 3 * hw0, n_max = (size_t)n * sizeof(double);
-    // staging of pageable buffers: [frames | flow | occ_prob | fwd | bwd | rgb | max], allocated with the first pageable push
-    size_t offs[8] = {0};
-    const size_t parts[7] = {in_bytes, n_flow, n_flow, n_mask, n_mask, n_rgb, n_max};
-    for (int i = 0; i < 7; ++i) offs[i + 1] = offs[i] + align256(parts[i]);
+    // the outputs of the stream's flags (0 bytes without the flag: a plain stream stages what it always did)
+    const size_t n_warp = (st->flags & B2F_STREAM_WARP) ? 2 * in_bytes : 0,
+                 n_photo = (st->flags & B2F_STREAM_WARP) ? (size_t)n * B2F_PHOTO_WORDS * sizeof(unsigned long long) : 0,
+                 n_past = (st->flags & B2F_STREAM_PAST) ? n_flow : 0;
+    // staging of pageable buffers: [frames | flow | occ_prob | fwd | bwd | rgb | max | warped | photo | past_flow], allocated with the
+    // first pageable push
+    constexpr int kOuts = 9;
+    size_t offs[kOuts + 2] = {0};
+    const size_t parts[kOuts + 1] = {in_bytes, n_flow, n_flow, n_mask, n_mask, n_rgb, n_max, n_warp, n_photo, n_past};
+    for (int i = 0; i <= kOuts; ++i) offs[i + 1] = offs[i] + align256(parts[i]);
     bool pageable = k_in != 1;
-    for (int i = 0; i < 6; ++i) pageable = pageable || k_out[i] != 1;
+    for (int i = 0; i < kOuts; ++i) pageable = pageable || k_out[i] != 1;
     if (pageable && !st->pin) {
-        HIPCHK(hipHostMalloc(&st->pin, offs[7], hipHostMallocDefault));
-        st->pin_bytes = offs[7];
+        HIPCHK(hipHostMalloc(&st->pin, offs[kOuts + 1], hipHostMallocDefault));
+        st->pin_bytes = offs[kOuts + 1];
     }
     if (pageable) ensure_pools(c);   // the context's host threads do the staging copies
     hipStream_t s = c->stream;
-    // ---- one upload of the cams frames: into their frame slot at a /64 size, else into the buffers image.scale reads
-    void *dst = same ? (void *)st->frame[P.sp.slot] : bytes_in ? (void *)st->d_u8 : (void *)st->d_up;
+    // ---- one upload of the cams frames: into their frame slot at a /64 size, else into the buffers image.scale reads -- or, on a
+    // stream that keeps the caller's frames for the warp, into the push's slot of the raw ring, which then stands in for them
+    char *const raw = raw_slot(st);
+    unsigned char *const up_u8 = raw ? (unsigned char *)raw : st->d_u8;
+    const float *const up_f32 = (raw && !bytes_in) ? (const float *)raw : st->d_up;   // what image.scale reads
+    void *dst = same ? (void *)st->frame[P.sp.slot] : bytes_in ? (void *)up_u8 : (void *)up_f32;
     const void *src = r.im1;
     if (k_in != 1) {
         c->pool_in->run({{st->pin, r.im1, in_bytes}});
         src = st->pin;
     }
     HIPCHK(hipMemcpyAsync(dst, src, in_bytes, hipMemcpyHostToDevice, s));
-    if (!same && bytes_in) HIPCHK(launch_unpack_u8(st->d_u8, (size_t)n * 3 * hw0, st->d_up, s));
-    CHK(run_kernels(c, r, g, same ? (const void *)st->frame[P.sp.slot] : st->d_up, same ? st->in_kind : B2F_IN_UNIT, (long)n * 3, n, P.net,
-                    {nullptr, same ? nullptr : st->d_flow32, (want_prob && !same) ? st->d_prob : nullptr, o.fwd_occ ? st->d_fo : nullptr,
-                     o.bwd_occ ? st->d_bo : nullptr, want_rgb ? st->d_rgb : nullptr, want_rgb ? st->d_max : nullptr, o.max_norm, o.rgb_layout},
+    if (!same && bytes_in) HIPCHK(launch_unpack_u8(up_u8, (size_t)n * 3 * hw0, st->d_up, s));
+    FlowOutputs d{nullptr, same ? nullptr : st->d_flow32, (need_prob && !same) ? st->d_prob : nullptr, o.fwd_occ ? st->d_fo : nullptr,
+                  o.bwd_occ ? st->d_bo : nullptr, want_rgb ? st->d_rgb : nullptr, want_rgb ? st->d_max : nullptr, o.max_norm, o.rgb_layout};
+    d.flow_scale = o.flow_scale; d.warping = o.warping;
+    d.warped = o.warped ? st->d_warp : nullptr; d.warped_kind = o.warped_kind;
+    d.photo = o.photo ? st->d_photo : nullptr;
+    d.past32 = (want_past && !same) ? st->d_past32 : nullptr; d.own_past = o.own_past;
+    CHK(run_kernels(c, r, g, same ? (const void *)st->frame[P.sp.slot] : up_f32, same ? st->in_kind : B2F_IN_UNIT, (long)n * 3, n, P.net, d,
                     c->host_graph != 0, s, &P.sp));
     // ---- download what was asked for: page-locked buffers in place, pageable ones through the staging block
     struct Down { void *host; const void *dev; size_t bytes; int kind; size_t off; };
-    const Down downs[6] = {{o.flow32, st->d_flow32, n_flow, k_out[0], offs[1]}, {o.occ_prob, same ? (const void *)P.occ_net : st->d_prob, n_flow, k_out[3], offs[2]},
-                           {o.fwd_occ, st->d_fo, n_mask, k_out[1], offs[3]}, {o.bwd_occ, st->d_bo, n_mask, k_out[2], offs[4]},
-                           {o.rgb, st->d_rgb, n_rgb, k_out[4], offs[5]}, {o.rgb_max, st->d_max, n_max, k_out[5], offs[6]}};
+    const Down downs[kOuts] = {{o.flow32, st->d_flow32, n_flow, k_out[0], offs[1]}, {o.occ_prob, same ? (const void *)P.occ_net : st->d_prob, n_flow, k_out[3], offs[2]},
+                               {o.fwd_occ, st->d_fo, n_mask, k_out[1], offs[3]}, {o.bwd_occ, st->d_bo, n_mask, k_out[2], offs[4]},
+                               {o.rgb, st->d_rgb, n_rgb, k_out[4], offs[5]}, {o.rgb_max, st->d_max, n_max, k_out[5], offs[6]},
+                               {o.warped, st->d_warp, n_warp, k_out[6], offs[7]}, {o.photo, st->d_photo, n_photo, k_out[7], offs[8]},
+                               {o.past32, st->d_past32, n_past, k_out[8], offs[9]}};
     std::vector<CopyJob> jobs;
     for (const Down &d : downs) {
         if (!d.host || !P.sp.ready) continue;
@@ -393,7 +428,8 @@ int push_device_work(b2f_stream *st, const FlowRequest &r, hipStream_t s)
     b2f_ctx *c = st->ctx;
     HIPCHK(hipSetDevice(c->device));
     const ReqBatch req_guard(c, r);
-    const PushPlan P = push_plan(st, r.o.occ_prob != nullptr);
+    FlowOutputs o = r.o;
+    const PushPlan P = push_plan(st, o.occ_prob != nullptr || o.photo != nullptr, o.want_past());
     const Geometry &g = P.g;
     const bool bytes_in = st->in_kind == B2F_IN_U8;
     const int n = st->cams;
@@ -403,11 +439,20 @@ int push_device_work(b2f_stream *st, const FlowRequest &r, hipStream_t s)
         // the frames must outlive the call (est[3] of a Hard model warps them two pushes later): into their frame slot
         HIPCHK(hipMemcpyAsync(st->frame[P.sp.slot], r.im1, samples * (bytes_in ? 1 : 4), hipMemcpyDeviceToDevice, s));
         x = st->frame[P.sp.slot];
-    } else if (bytes_in) {
-        HIPCHK(launch_unpack_u8((const unsigned char *)r.im1, samples, st->d_up, s));
-        x = st->d_up;
+    } else {
+        // a stream that keeps the caller's frames for the warp: into the push's slot of the raw ring
+        if (char *raw = raw_slot(st)) HIPCHK(hipMemcpyAsync(raw, r.im1, samples * (bytes_in ? 1 : 4), hipMemcpyDeviceToDevice, s));
+        if (bytes_in) {
+            HIPCHK(launch_unpack_u8((const unsigned char *)r.im1, samples, st->d_up, s));
+            x = st->d_up;
+        }
     }
-    return run_kernels(c, r, g, x, g.same ? st->in_kind : B2F_IN_UNIT, (long)n * 3, n, P.net, r.o, c->use_graph != 0, s, &P.sp);
+    if (!g.same) {   // what the warp of a rescaled flow reads at H0 x W0 and the caller left out: the stream's own buffers
+        if (o.warping && !o.flow32) o.flow32 = st->d_flow32;
+        if (o.photo && !o.occ_prob) o.occ_prob = st->d_prob;
+        if (o.own_past && !o.past32) o.past32 = st->d_past32;
+    }
+    return run_kernels(c, r, g, x, g.same ? st->in_kind : B2F_IN_UNIT, (long)n * 3, n, P.net, o, c->use_graph != 0, s, &P.sp);
 }
 
 }  // namespace
@@ -428,14 +473,19 @@ int b2f::check_request(const FlowRequest &r)
         (!o.f32() ? !o.fwd_occ || !o.bwd_occ : o.pictures ? !o.rgb : o.scoring ? !o.scores || !o.gt_flow : o.warping ? false : !o.flow32))
         return fail(w + ": null argument");
     // the past flow is an output of the float32 batch and sequence entries of a Soft model (the model is check_context's to refuse)
+    // ... and of a stream that was opened for it
     if (o.want_past()) {
-        if (r.stream) return fail(w + ": a stream does not return the past flow (use the batch or sequence entries)");
+        if (r.stream && !(r.stream->flags & B2F_STREAM_PAST))
+            return fail(w + ": this stream was opened without B2F_STREAM_PAST (b2f_stream_open_ex): it does not return the past flow");
         if (!o.f32()) return fail(w + ": the past flow is an output of the float32 entries");
         if (o.own_past && !o.warping) return fail(w + ": only a warp request can use the model's own past flow");
     }
-    // a warp request (f32 path as well) needs the warped frames or the photometric records
+    // a warp request (f32 path as well) needs the warped frames or the photometric records; a stream keeps the frames it samples
+    // only when it was opened for it
     if (o.warping) {
-        if (!o.f32() || r.stream) return fail(w + ": warped frames are an output of the float32 batch and sequence entries");
+        if (r.stream && !(r.stream->flags & B2F_STREAM_WARP))
+            return fail(w + ": this stream was opened without B2F_STREAM_WARP (b2f_stream_open_ex): it keeps no frames to warp");
+        if (!o.f32()) return fail(w + ": warped frames are an output of the float32 batch and sequence entries");
         if (!(o.flow_scale > 0.0) || !std::isfinite(o.flow_scale)) return fail(w + ": flow_scale must be finite and > 0");
         if ((long long)r.H0 * r.W0 >= (1ll << 28)) return fail(w + ": images of 2^28 pixels or more are refused (the Q30 sums could overflow)");
         if (!o.warped && !o.photo) return fail(w + ": at least one of warped and photo is required");
@@ -862,8 +912,10 @@ int b2f::stream_push_host(const FlowRequest &r, int *ready)
     const size_t hw0 = (size_t)st->H0 * st->W0, n = (size_t)st->cams;
     auto kind_of = [](const void *p, size_t bytes) { return p ? mem_kind(p, bytes) : 1; };   // unrequested outputs count as page-locked
     const int k_in = mem_kind(r.im1, n * 3 * hw0 * (st->in_kind == B2F_IN_U8 ? 1 : 4));
-    const int k_out[6] = {kind_of(o.flow32, n * 2 * hw0 * 4), kind_of(o.fwd_occ, n * hw0), kind_of(o.bwd_occ, n * hw0), kind_of(o.occ_prob, n * 2 * hw0 * 4),
-                          kind_of(o.rgb, n * 3 * hw0), kind_of(o.rgb_max, n * sizeof(double))};
+    const int k_out[9] = {kind_of(o.flow32, n * 2 * hw0 * 4), kind_of(o.fwd_occ, n * hw0), kind_of(o.bwd_occ, n * hw0), kind_of(o.occ_prob, n * 2 * hw0 * 4),
+                          kind_of(o.rgb, n * 3 * hw0), kind_of(o.rgb_max, n * sizeof(double)),
+                          kind_of(o.warped, n * 6 * hw0 * (o.warped_kind == B2F_IN_U8 ? 1 : 4)),
+                          kind_of(o.photo, n * B2F_PHOTO_WORDS * sizeof(unsigned long long)), kind_of(o.past32, n * 2 * hw0 * 4)};
     bool dev_mem = k_in < 0;
     for (int k : k_out) dev_mem = dev_mem || k < 0;
     if (dev_mem) return fail(std::string(r.who) + ": device memory passed to a host-buffer entry point (use b2f_stream_push_device)");
@@ -886,11 +938,13 @@ int b2f::stream_push_device(const FlowRequest &r, void *stream, int *ready)
     CHK(check_push(r));
     b2f_stream *st = r.stream;
     const FlowOutputs &o = r.o;
-    if (((uintptr_t)r.im1 | (uintptr_t)o.flow32 | (uintptr_t)o.occ_prob | (uintptr_t)o.fwd_occ | (uintptr_t)o.bwd_occ) & 15)
+    if (((uintptr_t)r.im1 | (uintptr_t)o.flow32 | (uintptr_t)o.occ_prob | (uintptr_t)o.fwd_occ | (uintptr_t)o.bwd_occ | (uintptr_t)o.warped |
+         (uintptr_t)o.photo | (uintptr_t)o.past32) & 15)
         return fail(std::string(r.who) + ": device buffers must be 16-byte aligned");
-    const size_t hw0n = (size_t)st->cams * st->H0 * st->W0;
-    const std::pair<const void *, size_t> bufs[5] = {{r.im1, hw0n * 3 * (st->in_kind == B2F_IN_U8 ? 1 : 4)}, {o.flow32, hw0n * 8}, {o.occ_prob, hw0n * 8},
-                                                     {o.fwd_occ, hw0n}, {o.bwd_occ, hw0n}};
+    const size_t hw0n = (size_t)st->cams * st->H0 * st->W0, in_bytes = hw0n * 3 * (st->in_kind == B2F_IN_U8 ? 1 : 4);
+    const std::pair<const void *, size_t> bufs[8] = {{r.im1, in_bytes}, {o.flow32, hw0n * 8}, {o.occ_prob, hw0n * 8}, {o.fwd_occ, hw0n}, {o.bwd_occ, hw0n},
+                                                     {o.warped, 2 * in_bytes}, {o.photo, (size_t)st->cams * B2F_PHOTO_WORDS * sizeof(unsigned long long)},
+                                                     {o.past32, hw0n * 8}};
     for (const auto &pb : bufs)
         if (pb.first && mem_kind(pb.first, pb.second) >= 0)
             return fail(std::string(r.who) + ": host memory passed to a device entry point (use b2f_stream_push)");
@@ -906,27 +960,36 @@ int b2f::stream_push_device(const FlowRequest &r, void *stream, int *ready)
     return 0;
 }
 
-extern "C" {
+namespace {
 
-int b2f_stream_open(b2f_ctx *c, int cams, int in_kind, int H0, int W0, b2f_stream **out) try
+// b2f_stream_open (flags = 0) and b2f_stream_open_ex
+int stream_open(const char *who, b2f_ctx *c, int cams, int in_kind, int H0, int W0, int flags, b2f_stream **out)
 {
-    if (!out) return fail("b2f_stream_open: null out");
+    const std::string w(who);
+    if (!out) return fail(w + ": null out");
     *out = nullptr;
-    if (!c) return fail("b2f_stream_open: null context");
-    if (in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail("b2f_stream_open: in_kind must be B2F_IN_UNIT or B2F_IN_U8");
-    if (cams < 1) return fail("b2f_stream_open: a stream serves at least one camera");
-    if (H0 < 64 || W0 < 64) return fail("b2f_stream_open: image smaller than 64 pixels");
-    if (!c->g.shipped()) return fail("b2f_stream_open: streams run on the shipped graph only (this context was made with b2f_init_ex options)");
+    if (!c) return fail(w + ": null context");
+    if (in_kind != B2F_IN_UNIT && in_kind != B2F_IN_U8) return fail(w + ": in_kind must be B2F_IN_UNIT or B2F_IN_U8");
+    if (cams < 1) return fail(w + ": a stream serves at least one camera");
+    if (H0 < 64 || W0 < 64) return fail(w + ": image smaller than 64 pixels");
+    if (!c->g.shipped()) return fail(w + ": streams run on the shipped graph only (this context was made with b2f_init_ex options)");
+    if (flags & ~(B2F_STREAM_WARP | B2F_STREAM_PAST)) return fail(w + ": unknown flags (B2F_STREAM_WARP, B2F_STREAM_PAST)");
+    if ((flags & B2F_STREAM_PAST) && !c->past_flow)
+        return fail(w + ": this model has no past-flow decoders (a Hard or two_frame model estimates the future flow only)");
+    if ((flags & B2F_STREAM_WARP) && (long long)H0 * W0 >= (1ll << 28))
+        return fail(w + ": images of 2^28 pixels or more are refused (the Q30 sums could overflow)");
     const Geometry g = geometry(c, H0, W0);
     CHK(check_shape(cams, g.fh, g.fw));
-    if ((unsigned long long)cams * 3 * g.hw0 > 0x7fffffffull) return fail("b2f_stream_open: cams x 3 x H0 x W0 exceeds 2^31 - 1 samples");
+    if ((unsigned long long)cams * 3 * g.hw0 > 0x7fffffffull) return fail(w + ": cams x 3 x H0 x W0 exceeds 2^31 - 1 samples");
     HIPCHK(hipSetDevice(c->device));
     std::unique_ptr<b2f_stream> st(new b2f_stream());
-    st->ctx = c; st->cams = cams; st->in_kind = in_kind; st->H0 = H0; st->W0 = W0;
+    st->ctx = c; st->cams = cams; st->in_kind = in_kind; st->H0 = H0; st->W0 = W0; st->flags = flags;
     const bool same = g.same, bytes_in = in_kind == B2F_IN_U8;
+    const bool warp = (flags & B2F_STREAM_WARP) != 0, past = (flags & B2F_STREAM_PAST) != 0;
     const size_t n = (size_t)cams, hw0 = g.hw0, hw = g.hw;
     st->frame_kind = same ? in_kind : B2F_IN_NORMALIZED;
     st->frame_bytes = same ? n * 3 * hw0 * (bytes_in ? 1 : 4) : n * 3 * hw * 4;
+    st->raw_bytes = (warp && !same) ? n * 3 * hw0 * (bytes_in ? 1 : 4) : 0;
     // carve: two passes over the same list, the first one without a base (every pointer stays null) to size the block
     auto carve = [&](char *base) {
         size_t off = 0;
@@ -946,25 +1009,63 @@ int b2f_stream_open(b2f_ctx *c, int cams, int in_kind, int H0, int W0, b2f_strea
         st->d_bo = (unsigned char *)take(n * hw0);
         st->d_rgb = (unsigned char *)take(n * 3 * hw0);
         st->d_max = (double *)take(n * sizeof(double));
+        // the pieces of the flags, behind everything a plain stream has
+        for (int sl = 0; sl < 3; ++sl) st->raw[sl] = st->raw_bytes ? take(st->raw_bytes) : nullptr;
+        st->d_warp = warp ? (void *)take(n * 6 * hw0 * (bytes_in ? 1 : 4)) : nullptr;
+        st->d_photo = warp ? (unsigned long long *)take(n * B2F_PHOTO_WORDS * sizeof(unsigned long long)) : nullptr;
+        st->d_past = past ? (float *)take(n * 2 * hw * 4) : nullptr;
+        st->d_past32 = !past ? nullptr : same ? st->d_past : (float *)take(n * 2 * hw0 * 4);
         return off;
     };
     st->dev_bytes = carve(nullptr);
     if (hipMalloc(&st->dev, st->dev_bytes) != hipSuccess) {
         (void)hipGetLastError();
-        return fail("b2f_stream_open: out of device memory (" + std::to_string(st->dev_bytes >> 20) + " MB for the stream)");
+        return fail(w + ": out of device memory (" + std::to_string(st->dev_bytes >> 20) + " MB for the stream)");
     }
     carve(st->dev);
     // option arena_fill (tests): the block starts as kGuardWord instead of 0, like the arena (carve rounds every piece to 256 bytes)
     if ((c->arena_fill ? hipMemsetD32((hipDeviceptr_t)st->dev, (int)kGuardWord, st->dev_bytes / 4) : hipMemset(st->dev, 0, st->dev_bytes)) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
         (void)hipFree(st->dev);
-        return fail("b2f_stream_open: hipMemset failed");
+        return fail(w + ": hipMemset failed");
     }
     c->streams.push_back(st.get());
     *out = st.release();
     return 0;
 }
+
+// the outputs of b2f_stream_push_warp[_device]: a warp request in the stream's element type, with the past flow when asked for
+FlowOutputs push_warp_outputs(const b2f_stream *st, double flow_scale, int own_past, void *warped, unsigned long long *photo, float *flow,
+                              float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ, float *past_flow)
+{
+    FlowOutputs o = warp_outputs(flow_scale, st->in_kind, warped, photo, flow, occ_prob, fwd_occ, bwd_occ);
+    o.past32 = past_flow; o.own_past = own_past != 0;
+    return o;
+}
+
+}  // namespace
+
+extern "C" {
+
+int b2f_stream_open(b2f_ctx *c, int cams, int in_kind, int H0, int W0, b2f_stream **out) try
+{
+    return stream_open(__func__, c, cams, in_kind, H0, W0, 0, out);
+}
 B2F_CATCH("b2f_stream_open")
+
+int b2f_stream_open_ex(b2f_ctx *c, int cams, int in_kind, int H0, int W0, int flags, b2f_stream **out) try
+{
+    return stream_open(__func__, c, cams, in_kind, H0, W0, flags, out);
+}
+B2F_CATCH("b2f_stream_open_ex")
+
+int b2f_stream_flags(const b2f_stream *st, int *flags) try
+{
+    if (!st) return fail("b2f_stream_flags: null stream");
+    if (flags) *flags = st->flags;
+    return 0;
+}
+B2F_CATCH("b2f_stream_flags")
 
 void b2f_stream_close(b2f_stream *st)
 {
@@ -1026,6 +1127,45 @@ int b2f_stream_push_device(b2f_stream *st, const void *dev_frames, float *dev_fl
                                            {nullptr, dev_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ}), stream, ready);
 }
 B2F_CATCH("b2f_stream_push_device")
+
+// ---- pushes of a stream opened with B2F_STREAM_WARP / B2F_STREAM_PAST: the requests of the _warp[_past] and _past entries ----
+int b2f_stream_push_warp(b2f_stream *st, const void *frames, double flow_scale, int own_past, void *warped, unsigned long long *photo, float *flow,
+                         float *occ_prob, unsigned char *fwd_occ, unsigned char *bwd_occ, float *past_flow, int *ready) try
+{
+    if (!st) return fail("b2f_stream_push_warp: null stream");
+    return stream_push_host(push_request(__func__, st, st->cams, st->in_kind, frames, st->H0, st->W0,
+                                         push_warp_outputs(st, flow_scale, own_past, warped, photo, flow, occ_prob, fwd_occ, bwd_occ, past_flow)), ready);
+}
+B2F_CATCH("b2f_stream_push_warp")
+
+int b2f_stream_push_warp_device(b2f_stream *st, const void *dev_frames, double flow_scale, int own_past, void *dev_warped,
+                                unsigned long long *dev_photo, float *dev_flow, float *dev_occ_prob, unsigned char *dev_fwd_occ,
+                                unsigned char *dev_bwd_occ, float *dev_past_flow, void *stream, int *ready) try
+{
+    if (!st) return fail("b2f_stream_push_warp_device: null stream");
+    return stream_push_device(push_request(__func__, st, st->cams, st->in_kind, dev_frames, st->H0, st->W0,
+                                           push_warp_outputs(st, flow_scale, own_past, dev_warped, dev_photo, dev_flow, dev_occ_prob, dev_fwd_occ,
+                                                             dev_bwd_occ, dev_past_flow)), stream, ready);
+}
+B2F_CATCH("b2f_stream_push_warp_device")
+
+int b2f_stream_push_past(b2f_stream *st, const void *frames, float *flow, float *past_flow, float *occ_prob, unsigned char *fwd_occ,
+                         unsigned char *bwd_occ, int *ready) try
+{
+    if (!st) return fail("b2f_stream_push_past: null stream");
+    return stream_push_host(push_request(__func__, st, st->cams, st->in_kind, frames, st->H0, st->W0,
+                                         past_outputs(flow, past_flow, occ_prob, fwd_occ, bwd_occ)), ready);
+}
+B2F_CATCH("b2f_stream_push_past")
+
+int b2f_stream_push_past_device(b2f_stream *st, const void *dev_frames, float *dev_flow, float *dev_past_flow, float *dev_occ_prob,
+                                unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream, int *ready) try
+{
+    if (!st) return fail("b2f_stream_push_past_device: null stream");
+    return stream_push_device(push_request(__func__, st, st->cams, st->in_kind, dev_frames, st->H0, st->W0,
+                                           past_outputs(dev_flow, dev_past_flow, dev_occ_prob, dev_fwd_occ, dev_bwd_occ)), stream, ready);
+}
+B2F_CATCH("b2f_stream_push_past_device")
 
 int b2f_compute_flow(b2f_ctx *c, const float *im1, const float *im2, const float *im3, int H0, int W0, double *flow, unsigned char *fwd_occ,
                      unsigned char *bwd_occ) try

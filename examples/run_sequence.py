@@ -14,7 +14,8 @@ past frame lies at x - past_flow, as the future frame lies at x + flow).
 a PNG instead; MAX is xy2rgb's `max` (default: every picture's own largest flow).  Only the pictures are downloaded; --flo
 writes the .flo files and masks as well.
 --stream: push the frames one at a time (Model.openStream / FlowStream.push, the calling pattern of a camera) instead of handing
-over the clip; the files are the same, byte for byte.
+over the clip; the files are the same, byte for byte.  With --past-flow the stream is opened for the past flow
+(Model.openStream(past=True) / MotionStream.pushPast).
 """
 import os
 import sys
@@ -33,8 +34,8 @@ def main():
     want_occ, want_flo, want_rgb, rgb_max = "--occ-prob" in args, "--flo" in args, "--rgb" in args, None
     stream = "--stream" in args
     want_past = "--past-flow" in args
-    if want_past and (want_rgb or stream):
-        sys.exit("--past-flow cannot be combined with --rgb or --stream")
+    if want_past and want_rgb:
+        sys.exit("--past-flow cannot be combined with --rgb")
     if want_rgb:
         i = args.index("--rgb")
         try:
@@ -60,7 +61,7 @@ def main():
 
     def pushed(push):
         """The sequence call's results from a stream: output i is what the push of frame i + 2 returns."""
-        with m.openStream(frames.shape[2], frames.shape[3], dtype=frames.dtype) as st:
+        with m.openStream(frames.shape[2], frames.shape[3], dtype=frames.dtype, past=want_past) as st:
             outs = [push(st, f) for f in frames][2:]
         return tuple(np.concatenate(parts) for parts in zip(*outs))
 
@@ -81,11 +82,14 @@ def main():
         m.close()
         return
     past = None
-    if stream:
-        res = pushed(lambda st, f: st.push(f, occ_prob=want_occ))
-    elif want_past:
-        res = m.computeFlowSequencePast(frames, occ_prob=want_occ)
+    if want_past:
+        if stream:
+            res = pushed(lambda st, f: st.pushPast(f, occ_prob=want_occ))
+        else:
+            res = m.computeFlowSequencePast(frames, occ_prob=want_occ)
         past, res = res[1], res[:1] + res[2:]
+    elif stream:
+        res = pushed(lambda st, f: st.push(f, occ_prob=want_occ))
     else:
         res = m.computeFlowSequence(frames, dtype=np.float32, occ_prob=want_occ)
     flow, fwd_occ, bwd_occ = res[:3]

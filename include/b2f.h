@@ -437,8 +437,8 @@ B2F_API int b2f_multi_compute_flow_sequence_warp(b2f_multi *m, int T, int in_kin
  * Sign: the past frame is sampled at x - past_flow * flow_scale, as the future frame is sampled at x + flow * flow_scale; under
  * constant velocity past_flow == flow.  A NULL past_flow is neither computed nor downloaded and the call is the entry's without
  * the suffix; with it the pruned forward pass also runs the five past-flow decoders, and every other output keeps its bits.
- * A context without past-flow decoders (a Hard model, two_frame) is refused, and so is a stream (b2f_stream_push has no such
- * output); a refusal launches nothing.                                                                                          */
+ * A context without past-flow decoders (a Hard model, two_frame) is refused, and so is a stream that was not opened with
+ * B2F_STREAM_PAST (b2f_stream_open_ex, b2f_stream_push_past); a refusal launches nothing.                                        */
 B2F_API int b2f_forward_device_past(b2f_ctx *ctx, const void *dev_in, int in_kind, int B, int H, int W, float *dev_flow,
                             float *dev_past_flow, float *dev_occ, float *dev_est3, void *stream);
 B2F_API int b2f_forward_sequence_device_past(b2f_ctx *ctx, const void *dev_frames, int in_kind, int T, int H, int W, float *dev_flow,
@@ -883,6 +883,48 @@ B2F_API int b2f_stream_push_rgb(b2f_stream *st, const void *frames, double max_n
  * on dev_flow, on the same stream.  *ready is known when the call returns.                               */
 B2F_API int b2f_stream_push_device(b2f_stream *st, const void *dev_frames, float *dev_flow, float *dev_occ_prob,
                            unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream, int *ready);
+/* ---- streams with motion compensation and the past flow per pushed frame ----
+ * b2f_stream_open_ex is b2f_stream_open with `flags`, a sum of B2F_STREAM_*; flags = 0 is b2f_stream_open itself, with the
+ * same device block.  What a flag adds is kept for the stream's lifetime:
+ *   B2F_STREAM_WARP  the stream keeps the caller's own frames of its last three pushes, which the warp of
+ *                    models/pwc.lua:67-73 samples at H0 x W0: at a /64 size its frame slots hold them already, at any
+ *                    other size (where those hold the normalized, rescaled frames of back2future.lua:54-71) a ring of
+ *                    3 slots x cams frames as pushed, 3 x H0 x W0 bytes or floats per camera and slot.  Every push of
+ *                    such a stream, of whichever entry, keeps its frames, so plain and warp pushes may alternate.  It
+ *                    also holds the warped frames and the photometric records of a host push.
+ *   B2F_STREAM_PAST  the stream may run the past-flow decoders (models/pwc.lua:328-385) and holds the past flow of a
+ *                    push; refused, in the words of the _past entries, on a context without them.
+ * b2f_stream_flags returns the flags a stream was opened with.                                                        */
+enum { B2F_STREAM_WARP = 1, B2F_STREAM_PAST = 2 };
+B2F_API int b2f_stream_open_ex(b2f_ctx *ctx, int cams, int in_kind, int H0, int W0, int flags, b2f_stream **out);
+B2F_API int b2f_stream_flags(const b2f_stream *st, int *flags);
+/* b2f_compute_flow_sequence_warp (own_past = 0) and b2f_compute_flow_sequence_warp_past (own_past != 0) for one new frame
+ * per camera: from the third push on the outputs of the triplet (k-2, k-1, k) -- the frames of pushes k-2 and k
+ * warped onto the frame of push k-1 (test.lua:285's inputs, models/pwc.lua:67-73) and the photometric record
+ * (criterions/OBCCriterion.lua:79-100) -- which are output k-3 of that sequence entry on the same frames, bit for bit.
+ * warped: cams x 2 x 3 x H0 x W0 in the stream's element type; photo: cams x B2F_PHOTO_WORDS words; at least one of
+ * the two is required, every other output is optional (NULL: neither computed nor downloaded).  past_flow: the past
+ * flow as in the _past entries; it and own_past need B2F_STREAM_PAST, the call itself B2F_STREAM_WARP.  A push the
+ * stream was not opened for, one with neither warped nor photo, or with a flow_scale that is not finite and > 0
+ * fails before any HIP work, names the flag or the argument, and leaves the stream as it was.  A host entry,
+ * synchronous like b2f_stream_push.                                                                              */
+B2F_API int b2f_stream_push_warp(b2f_stream *st, const void *frames, double flow_scale, int own_past, void *warped,
+                         unsigned long long *photo, float *flow, float *occ_prob, unsigned char *fwd_occ,
+                         unsigned char *bwd_occ, float *past_flow, int *ready);
+/* The same on GPU memory, asynchronous on `stream` like b2f_stream_push_device (every pointer device memory, 16-byte
+ * aligned); dev_frames is copied into the stream before the call returns control to `stream`'s next work.          */
+B2F_API int b2f_stream_push_warp_device(b2f_stream *st, const void *dev_frames, double flow_scale, int own_past, void *dev_warped,
+                                unsigned long long *dev_photo, float *dev_flow, float *dev_occ_prob,
+                                unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, float *dev_past_flow, void *stream,
+                                int *ready);
+/* b2f_compute_flow_sequence_past / b2f_compute_flow_sequence_device_past for one new frame per camera: b2f_stream_push
+ * and b2f_stream_push_device with the past flow (skip_ubfs[3], models/pwc.lua:328-385) behind the flow; needs
+ * B2F_STREAM_PAST.  A NULL past_flow makes it the plain push.                                                     */
+B2F_API int b2f_stream_push_past(b2f_stream *st, const void *frames, float *flow, float *past_flow, float *occ_prob,
+                         unsigned char *fwd_occ, unsigned char *bwd_occ, int *ready);
+B2F_API int b2f_stream_push_past_device(b2f_stream *st, const void *dev_frames, float *dev_flow, float *dev_past_flow,
+                                float *dev_occ_prob, unsigned char *dev_fwd_occ, unsigned char *dev_bwd_occ, void *stream,
+                                int *ready);
 /* Full output table of model:forward (pwc.lua:459-489) into n_outs host buffers, in
  * table order; x is B x 9 x H x W normalized host memory.                           */
 B2F_API int b2f_forward(b2f_ctx *ctx, const float *x, int B, int H, int W, float **outs, int n_outs);

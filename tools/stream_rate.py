@@ -13,9 +13,15 @@ tools/sequence_rate.py).  Every row is the median of `--pushes` steady-state cal
   f  host push, page-locked buffers
   g  pushRGB(packed=True), pageable
   h  cams = 4, pushDevice, per camera-frame
-plus the profile_layers = 1 split of one push into the pyramid and the rest, and the two conditions of DESIGN.md section 7.4.
---parent-root DIR: a built checkout of the parent commit; row (a) is measured there too, by this tool in a process of its own
-(--only-a --root DIR), to show that the triplet path did not move.
+  i  host push(occ_prob=True), pageable: what (j) is held against
+  j  pushWarp(want_warped=False) on a stream opened with warp=True, pageable: 112 bytes down instead of 10 B/px, one kernel more
+  k  pushWarp with warped frames and photo, pageable
+  l  host computeFlowBatchWarp with n = 1 per new frame (three uploads, three pyramids): today's way to (k)'s outputs
+plus the profile_layers = 1 split of one push into the pyramid and the rest, the flow_warp profile row of a push and of a
+three-frame sequence (one image each) against 31 B/px at the copy rate of DESIGN.md section 7.6, and the conditions of DESIGN.md
+sections 7.4 and 7.15.
+--parent-root DIR: a built checkout of the parent commit; rows (a), (b) and (e) are measured there too, by this tool in a process
+of its own (--only-plain --root DIR), to show that the triplet path and the plain pushes did not move.
 """
 import argparse
 import json
@@ -64,6 +70,7 @@ def main():
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--root", default=None)
     ap.add_argument("--only-a", action="store_true", help="row (a) alone: the call a parent commit can run")
+    ap.add_argument("--only-plain", action="store_true", help="rows (a), (b) and (e): the triplet call and the plain pushes of a parent commit")
     a = ap.parse_args()
     H, W, N = a.height, a.width, a.pushes
     T = 12
@@ -86,6 +93,15 @@ def main():
         print(json.dumps(res))
         m.close()
         return
+    out1 = (np.empty((1, 2, H, W), np.float32), np.empty((1, 1, H, W), np.uint8), np.empty((1, 1, H, W), np.uint8))
+    if a.only_plain:
+        with m.options(use_graph=1), m.openStream(H, W) as st:
+            R["b"] = row(timed(m, lambda i: st.pushDevice(p(d[i % T]), p(flow), None, p(fo), p(bo)), N, warm=9))
+        with m.openStream(H, W) as st:
+            R["e"] = row(timed(m, lambda i: st.push(Vn[i % T], out=out1), N, warm=9, device=False))
+        print(json.dumps(res))
+        m.close()
+        return
     with m.options(use_graph=1):
         for key, opts in (("b", {}), ("c", {"adaptive_kernels": 1})):
             with m.options(**opts), m.openStream(H, W) as st:
@@ -96,7 +112,6 @@ def main():
         with m.openStream(H, W, cams=4) as st:
             R["h"] = row(timed(m, lambda i: st.pushDevice(p(d4[i % T]), p(flow), None, p(fo), p(bo)), N, warm=9), per=4)
         R["h"]["path"] = "pushDevice cams=4, per camera-frame, use_graph=1"
-    out1 = (np.empty((1, 2, H, W), np.float32), np.empty((1, 1, H, W), np.uint8), np.empty((1, 1, H, W), np.uint8))
     R["d"] = row(timed(m, lambda i: m.computeFlowBatch(Vn[i % 10:i % 10 + 1], Vn[i % 10 + 1:i % 10 + 2], Vn[i % 10 + 2:i % 10 + 3], out=out1,
                                                        dtype=np.float32), N, device=False))
     R["d"]["path"] = "computeFlowBatch(dtype=float32) n=1, u8 host frames, pageable"
@@ -114,6 +129,41 @@ def main():
     with m.openStream(H, W) as st:
         R["g"] = row(timed(m, lambda i: st.pushRGB(Vn[i % T], packed=True, out=rgb_out), N, warm=9, device=False))
     R["g"]["path"] = "pushRGB(packed=True), pageable"
+    # ---- motion compensation per pushed frame
+    out_prob = out1 + (np.empty((1, 2, H, W), np.float32),)
+    with m.openStream(H, W) as st:
+        R["i"] = row(timed(m, lambda i: st.push(Vn[i % T], out=out_prob, occ_prob=True), N, warm=9, device=False))
+    R["i"]["path"] = "push(occ_prob=True), pageable"
+    photo1, warped1 = np.empty((1, back2future.PHOTO_WORDS), np.uint64), np.empty((1, 2, 3, H, W), np.uint8)
+    with m.openStream(H, W, warp=True) as st:
+        R["j"] = row(timed(m, lambda i: st.pushWarp(Vn[i % T], want_warped=False, out=photo1), N, warm=9, device=False))
+    R["j"]["path"] = "pushWarp(want_warped=False), pageable"
+    with m.openStream(H, W, warp=True) as st:
+        R["k"] = row(timed(m, lambda i: st.pushWarp(Vn[i % T], out=(warped1, photo1)), N, warm=9, device=False))
+    R["k"]["path"] = "pushWarp, warped frames + photo, pageable"
+    R["l"] = row(timed(m, lambda i: m.computeFlowBatchWarp(Vn[i % 10:i % 10 + 1], Vn[i % 10 + 1:i % 10 + 2], Vn[i % 10 + 2:i % 10 + 3],
+                                                           out=(warped1, photo1)), N, device=False))
+    R["l"]["path"] = "computeFlowBatchWarp n=1, warped frames + photo, u8 host frames, pageable"
+    # the stage alone: the flow_warp profile row of one push and of a three-frame sequence (one image each), against 31 B/px
+    with m.options(profile=1):
+        with m.openStream(H, W, warp=True) as st:
+            for k in range(3):
+                st.pushWarp(Vn[k], out=(warped1, photo1))
+            m.profile_reset()
+            for k in range(3, 8):
+                st.pushWarp(Vn[k], out=(warped1, photo1))
+            push_ms, push_n = m.profile_read()["flow_warp"]
+        m.computeFlowSequenceWarp(Vn[:3], out=(warped1, photo1))
+        m.profile_reset()
+        for k in range(5):
+            m.computeFlowSequenceWarp(Vn[k:k + 3], out=(warped1, photo1))
+        seq_ms, seq_n = m.profile_read()["flow_warp"]
+        m.profile_reset()
+    copy_tb_s, bpp = 6.29, 31   # tools/warp_rate.py: the copy rate and the compulsory bytes per pixel of DESIGN.md section 7.6
+    stage = lambda ms, n: {"ms": round(ms / n, 4), "launches": n, "TB_per_s": round(H * W * bpp / (ms / n * 1e-3) / 1e12, 3),
+                           "share_of_hbm_copy_rate": round(H * W * bpp / (ms / n * 1e-3) / 1e12 / copy_tb_s, 3)}
+    res["flow_warp_stage"] = {"push": stage(push_ms, push_n), "sequence_of_3_frames": stage(seq_ms, seq_n), "bytes_per_px": bpp,
+                              "hbm_copy_TB_per_s": copy_tb_s}
     # one push split into pyramid and rest
     with m.options(profile=1, profile_layers=1), m.openStream(H, W) as st:
         for k in range(3):
@@ -141,14 +191,23 @@ def main():
         "e_no_slower_than_d": {"e_ms": R["e"]["median_ms"], "d_ms": R["d"]["median_ms"], "margin_ms": round(R["d"]["max_ms"] - R["d"]["min_ms"], 4),
                                "holds": R["e"]["median_ms"] <= R["d"]["median_ms"] + (R["d"]["max_ms"] - R["d"]["min_ms"])},
         "b_vs_a": round(R["a"]["median_ms"] / R["b"]["median_ms"], 4),
+        "j_no_slower_than_i": {"j_ms": R["j"]["median_ms"], "i_ms": R["i"]["median_ms"], "margin_ms": round(R["i"]["max_ms"] - R["i"]["min_ms"], 4),
+                               "holds": R["j"]["median_ms"] <= R["i"]["median_ms"] + (R["i"]["max_ms"] - R["i"]["min_ms"])},
+        "l_vs_k": round(R["l"]["median_ms"] / R["k"]["median_ms"], 4),
     }
     m.close()
     if a.parent_root:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--only-a", "--root", a.parent_root, "--height", str(H), "--width", str(W),
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--only-plain", "--root", a.parent_root, "--height", str(H), "--width", str(W),
                             "--pushes", str(N)], capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
-            sys.exit("row (a) on the parent checkout failed:\n" + r.stdout + r.stderr)
-        res["a_on_parent_commit"] = json.loads(r.stdout.strip().splitlines()[-1])["rows"]["a"]
+            sys.exit("rows (a), (b), (e) on the parent checkout failed:\n" + r.stdout + r.stderr)
+        parent = json.loads(r.stdout.strip().splitlines()[-1])["rows"]
+        res["a_on_parent_commit"] = parent["a"]
+        res["plain_on_parent_commit"] = {k: parent[k] for k in ("b", "e")}
+        # a plain push does not move: this commit's median within the parent row's own min-max spread of the parent's median
+        res["conditions"]["plain_push_did_not_move"] = {
+            k: {"ms": R[k]["median_ms"], "parent_ms": parent[k]["median_ms"], "margin_ms": round(parent[k]["max_ms"] - parent[k]["min_ms"], 4),
+                "holds": R[k]["median_ms"] <= parent[k]["median_ms"] + (parent[k]["max_ms"] - parent[k]["min_ms"])} for k in ("b", "e")}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
