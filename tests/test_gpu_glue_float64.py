@@ -33,7 +33,7 @@ KERNEL_CASES = {
     "put_channels_kernel": "test_put_channels", "costvol_cp8_kernel": "test_costvol_cp8", "warp_cp8_kernel": "test_warp_cp8",
     "add_flow_kernel": "test_add_flow_and_scale", "scale_kernel": "test_add_flow_and_scale", "softmax_nearest_kernel": "test_softmax_nearest4",
     # held elsewhere
-    "warp_nhwc_kernel": "tests/test_gpu_parity.py (ops.warp_bhwd)", "conv_first_kernel": "tests/test_gpu_conv_float64.py",
+    "warp_nhwc_kernel": "tests/test_gpu_reference_sampler.py (ops.warp_bhwd)", "conv_first_kernel": "tests/test_gpu_conv_float64.py",
     "conv_narrow2_kernel": "tests/test_gpu_conv_float64.py", "fill_kernel": "excepted: a memset",
 }
 
