@@ -40,6 +40,15 @@ class LossGradSsimOpts(C.Structure):
 
 c_grad_ssim_opts_p = C.POINTER(LossGradSsimOpts)
 
+
+class LossEpeOpts(C.Structure):
+    """b2f_loss_epe_opts of include/b2f.h: -epe, the weight of the opt-in occlusion term (train.lua:316-332), -sizeAverage and the
+    level weights of train.lua:56-58"""
+    _fields_ = [("epe", C.c_double), ("occ", C.c_double), ("size_average", C.c_int), ("level_weights", C.c_double * 7)]
+
+
+c_epe_opts_p = C.POINTER(LossEpeOpts)
+
 # name -> (restype, argtypes); must list every symbol include/b2f.h declares
 SIGNATURES = {
     "b2f_last_error": (C.c_char_p, []),
@@ -267,6 +276,24 @@ SIGNATURES = {
                                                     C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, c_float_p]),
     "b2f_multi_forward_loss_grad_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ssim_opts_p,
                                                    C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int, C.c_int, c_float_p]),
+    "b2f_loss_epe_defaults": (C.c_int, [c_epe_opts_p]),
+    "b2f_table_loss_epe_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.POINTER(C.c_ubyte),
+                                          C.POINTER(C.c_ubyte), C.c_double, C.c_int, c_epe_opts_p, C.c_int, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_ulonglong), C.POINTER(c_float_p)]),
+    "b2f_table_loss_epe_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_double, c_epe_opts_p, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "b2f_op_table_loss_epe": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.POINTER(C.c_ubyte),
+                                        C.POINTER(C.c_ubyte), C.c_double, c_epe_opts_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong),
+                                        C.POINTER(c_float_p)]),
+    "b2f_forward_loss_epe": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte),
+                                       C.c_double, c_epe_opts_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), C.POINTER(c_float_p),
+                                       C.c_int, C.POINTER(c_float_p)]),
+    "b2f_forward_loss_epe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_double, c_epe_opts_p, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_void_p), C.c_int,
+                                              C.c_void_p]),
+    "b2f_multi_forward_loss_epe": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte),
+                                             C.c_double, c_epe_opts_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), C.POINTER(c_float_p),
+                                             C.c_int]),
     "b2f_forward": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(c_float_p), C.c_int]),
     "b2f_output_shapes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.c_int]),

@@ -51,6 +51,12 @@ LOSS_FT_SMOOTH2_NONFINITE, LOSS_FT_GRAD_NONFINITE, LOSS_FT_WORDS = 22, 23, 24
 LOSS_SSIM_Q30, LOSS_SSIM_L1N_Q30, LOSS_SSIM_NONFINITE, LOSS_SSIM_RANGE_USED, LOSS_SSIM_RANGE_OWN, LOSS_SSIM_WORDS = 16, 18, 20, 22, 24, 32
 SSIM_RANGE_BATCH, SSIM_RANGE_IMAGE, SSIM_RANGE_GIVEN = 0, 1, 2   # range_mode of the *_ssim entries (include/b2f.h, B2F_SSIM_RANGE_*)
 SSIM_ALPHA = {"OSSIM": 1.0, "OSSIML1": 0.85}                      # model.lua:172-179
+# words of a record of the supervised objective (include/b2f.h, B2F_LOSS_EPE_*; objective="epe"; train.lua:296-334 with
+# criterions/L2Criterion.lua): the level's pixels, the valid pixels with a finite end-point error, its Q20 sum in units of flow_scale
+# pixels, the valid pixels with a non-finite one, and the same three of the occlusion term over the labelled pixels (0 unless occ > 0)
+LOSS_EPE_PIXELS, LOSS_EPE_VALID, LOSS_EPE_Q20, LOSS_EPE_FLOW_NONFINITE = 0, 1, 2, 3
+LOSS_EPE_LABELLED, LOSS_EPE_OCC_Q20, LOSS_EPE_OCC_NONFINITE, LOSS_EPE_WORDS = 4, 5, 6, 8
+EPE_COUNT_BATCH, EPE_COUNT_IMAGE, EPE_COUNT_GIVEN = 0, 1, 2       # count_mode of the *_epe entries (include/b2f.h, B2F_EPE_COUNT_*)
 # what each released model was trained on (the reference's README.md:85-102; anything not named keeps opts.lua:61-73), by the names
 # of init.  pme_alpha is listed as given: OBGCCriterion.lua:97 never applies it.  (model.lua:171 assigns -pme_gamma to a field named
 # `gamm`, so a reference run keeps gamma = 1 whatever the option says; pass pme_gamma=1.0 to loss_summary for what such a run printed.)
@@ -65,19 +71,24 @@ LOSS_OBJECTIVES = {
 
 
 def loss_words(objective):
-    """words per record of objective "pme" (16; test.lua:266-297), "finetune" (24; with the terms of README.md:89-102) or "ssim" (32;
-    with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua)"""
+    """words per record of objective "pme" (16; test.lua:266-297), "finetune" (24; with the terms of README.md:89-102), "ssim" (32;
+    with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua) or "epe" (8; the supervised objective of train.lua:296-334)"""
     if objective == "pme":
         return LOSS_WORDS
     if objective == "finetune":
         return LOSS_FT_WORDS
     if objective == "ssim":
         return LOSS_SSIM_WORDS
-    raise ValueError("objective must be 'pme', 'finetune' or 'ssim', got %r" % (objective,))
+    if objective == "epe":
+        return LOSS_EPE_WORDS
+    raise ValueError("objective must be 'pme', 'finetune', 'ssim' or 'epe', got %r" % (objective,))
 
 
 def loss_entry(pattern, objective):
-    """the library's entry for an objective: `pattern` with %s replaced by "", "_ft" or "_ssim" """
+    """the library's entry for an unsupervised objective: `pattern` with %s replaced by "", "_ft" or "_ssim" """
+    if objective == "epe":
+        raise ValueError("objective 'epe' needs ground truth: use ops.table_loss_epe, Model.tableLossDevice(objective='epe', gt_flow=...) or "
+                         "Model.tableLossGradDevice(objective='epe', gt_flow=...)")
     return getattr(_lib.lib(), pattern % {LOSS_WORDS: "", LOSS_FT_WORDS: "_ft", LOSS_SSIM_WORDS: "_ssim"}[loss_words(objective)])
 
 
@@ -734,8 +745,10 @@ def photo_summary(photo):
 
 
 def loss_summary(records, like="test", size_average=False, weights=None, smooth_second_order=False, pme_criterion="OBCC", pme_beta=1.0,
-                 pme_gamma=1.0, objective=None, ssim_alpha=None):
-    """The unsupervised validation loss of test.lua:266-297 from loss records (uint64 n x L x 16 or L x 16; ops.table_loss,
+                 pme_gamma=1.0, objective=None, ssim_alpha=None, flow_scale=20.0, count="batch"):
+    """objective="epe": the supervised objective from the 8-word records of ops.table_loss_epe; see _loss_summary_epe, which takes
+    size_average, weights ("epe", "occ", "level_weights"), flow_scale and count.  Otherwise:
+    The unsupervised validation loss of test.lua:266-297 from loss records (uint64 n x L x 16 or L x 16; ops.table_loss,
     Model.forwardLoss; or n x L x 24 / L x 24 of objective="finetune").  Per level j
         level_weights[j] * (smooth_flow * S + const_vel * cv + pme * ((OCHARB0 + OCHARB1) / 2^30 + OUTSIDE0 + OUTSIDE1) / (3 * 2)
                             + smooth_occ * so + prior_occ * pr)
@@ -759,6 +772,11 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
     "mean" (the mean of "loss") and "nonfinite" (pixels left out of a sum that was used because a term was NaN).  The sums are exact
     integers; each pixel term carries the Q30 rounding (2^-31)."""
     s = np.asarray(records)
+    if objective == "epe":
+        if like != "test" or smooth_second_order or pme_criterion != "OBCC" or pme_beta != 1.0 or pme_gamma != 1.0 or ssim_alpha is not None:
+            raise ValueError("loss_summary: objective='epe' takes size_average, weights, flow_scale and count only (train.lua is its definition; "
+                             "there is no like='test' of it)")
+        return _loss_summary_epe(s, size_average, weights, flow_scale, count)
     if s.dtype != np.uint64 or s.shape[-1:] not in ((LOSS_WORDS,), (LOSS_FT_WORDS,), (LOSS_SSIM_WORDS,)) or s.ndim not in (2, 3):
         raise ValueError("loss_summary: expected uint64 records of shape (n, L, w) or (L, w) with w = %d, %d or %d, got %s %r"
                          % (LOSS_WORDS, LOSS_FT_WORDS, LOSS_SSIM_WORDS, s.dtype, s.shape))
@@ -822,6 +840,110 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
     nonf = int(sum(int(v) for v in s[:, :, counted].ravel()))
     return {"smooth_flow": fs, "smooth_past": fp, "const_vel": cv, "pme": pme, "smooth_occ": so, "prior_occ": pr, "level": level,
             "loss": loss, "mean": float(loss.mean()), "nonfinite": nonf}
+
+
+def _epe_weights(who, weights):
+    """(epe, occ, level weights) from a `weights` dict over the defaults of b2f_loss_epe_defaults; negative and non-finite ones raise"""
+    wt = {"epe": 1.0, "occ": 0.0, "level_weights": LOSS_LEVEL_WEIGHTS}
+    for k, v in (weights or {}).items():
+        if k not in wt:
+            raise ValueError(who + ": unknown weight %r (one of 'epe', 'occ', 'level_weights')" % (k,))
+        wt[k] = v
+    lw = [float(t) for t in wt["level_weights"]]
+    if len(lw) > len(LOSS_LEVEL_WEIGHTS):
+        raise ValueError(who + ": at most %d level weights" % len(LOSS_LEVEL_WEIGHTS))
+    lw = lw + list(LOSS_LEVEL_WEIGHTS[len(lw):])
+    for k, t in [("epe", float(wt["epe"])), ("occ", float(wt["occ"]))] + [("level_weights", t) for t in lw]:
+        if not (t >= 0.0 and np.isfinite(t)):
+            raise ValueError(who + ": %s must be finite and >= 0, got %r" % (k, t))
+    return float(wt["epe"]), float(wt["occ"]), lw
+
+
+def loss_epe_options(weights=None, size_average=False):
+    """The options of the supervised objective, -optimize epe (a _lib.LossEpeOpts, b2f_loss_epe_opts of include/b2f.h), from
+    b2f_loss_epe_defaults: epe 1 (-epe), occ 0, the level weights of train.lua:56-58, sizeAverage off.  `weights` replaces "epe", "occ"
+    and, as "level_weights", the first level weights (at most 7).  occ > 0 switches on the occlusion term that train.lua:316-332
+    intends (the Lua as written cannot run); it needs gt_occ.  size_average=True: every level weight counts as 1 (train.lua:60-64)
+    and a level is divided by its valid resp. labelled pixels (L2Criterion.lua:40-42,66-68)."""
+    o = _lib.LossEpeOpts()
+    _lib.check(_lib.lib().b2f_loss_epe_defaults(C.byref(o)))
+    o.epe, o.occ, lw = _epe_weights("loss_epe_options", weights)
+    for j, t in enumerate(lw):
+        o.level_weights[j] = t
+    o.size_average = 1 if size_average else 0
+    return o
+
+
+def epe_count_args(count, L, who, batch_ok=True):
+    """(count_mode, counts) of a b2f_*_epe entry.  count: "batch" (N_j over the call's images, mask:sum() of L2Criterion.lua:34,56),
+    "image" (each image's own) or L x 2 numbers (valid, labelled pixels per level)."""
+    if isinstance(count, str):
+        modes = {"batch": EPE_COUNT_BATCH, "image": EPE_COUNT_IMAGE}
+        if count not in modes or (count == "batch" and not batch_ok):
+            raise ValueError("%s: count must be %s'image' or an L x 2 array, got %r" % (who, "'batch', " if batch_ok else "", count))
+        return (modes[count], None)
+    r = np.ascontiguousarray(count, np.float64)
+    if r.shape != (L, 2):
+        raise ValueError("%s: a count array must have shape (%d, 2): valid, labelled pixels per level; got %r" % (who, L, r.shape))
+    return (EPE_COUNT_GIVEN, r.ctypes.data_as(C.POINTER(C.c_double)))   # (the pointer keeps r alive)
+
+
+def _epe_opts_ptr(options):
+    if options is None:
+        return None
+    if not isinstance(options, _lib.LossEpeOpts):
+        raise ValueError("objective 'epe': expected the result of back2future.loss_epe_options (or None for the defaults)")
+    return C.byref(options)
+
+
+def _loss_summary_epe(records, size_average=False, weights=None, flow_scale=20.0, count="batch"):
+    """The supervised objective of train.lua:296-334 from its records (uint64 n x L x 8 or L x 8; ops.table_loss_epe).  Per level j
+        flow_j = epe * lw_j * sum EPE_Q20 / 2^20,    occ_j = occ * lw_j * sum OCC_Q20 / 2^20
+    summed over the records' images as criterion:forward sums over its batch (train.lua:312-313,328-329; lw: train.lua:56-58);
+    size_average=True: lw_j = 1 and each sum is divided by N_j = VALID + FLOW_NONFINITE resp. N'_j = LABELLED + OCC_NONFINITE
+    (mask:sum(), L2Criterion.lua:34,40-42), taken over all records (count="batch"), per image, the per-image values then added
+    ("image"), or from an L x 2 array; a level without a counted pixel adds 0.  weights: "epe", "occ", "level_weights" as for
+    loss_epe_options (the occlusion sums are 0 unless the records were made with occ > 0).  Returns a dict: "flow" and "occ" (L
+    float64 each, weighted), "err" (their sum over the levels, what train.lua accumulates), "epe" (flow_scale * sum EPE_Q20[level 0] /
+    2^20 / sum VALID[level 0], train.lua:340-344; nan without a valid pixel) and "nonfinite".  The sums are exact integers; each pixel
+    term carries the Q20 rounding (2^-21)."""
+    s = np.asarray(records)
+    if s.dtype != np.uint64 or s.shape[-1:] != (LOSS_EPE_WORDS,) or s.ndim not in (2, 3):
+        raise ValueError("loss_summary: objective='epe' expects uint64 records of shape (n, L, %d) or (L, %d), got %s %r"
+                         % (LOSS_EPE_WORDS, LOSS_EPE_WORDS, s.dtype, s.shape))
+    s = s.reshape((-1,) + s.shape[-2:])
+    n, L, _ = s.shape
+    if L > len(LOSS_LEVEL_WEIGHTS):
+        raise ValueError("loss_summary: at most %d levels" % len(LOSS_LEVEL_WEIGHTS))
+    w_epe, w_occ, lw = _epe_weights("loss_summary", weights)
+    one = float(1 << 20)
+    parts = []
+    for w_sum, w_cnt, w_nonf in ((LOSS_EPE_Q20, LOSS_EPE_VALID, LOSS_EPE_FLOW_NONFINITE), (LOSS_EPE_OCC_Q20, LOSS_EPE_LABELLED, LOSS_EPE_OCC_NONFINITE)):
+        t = len(parts)
+        level = np.zeros(L, np.float64)
+        for j in range(L):
+            q = [int(v) for v in s[:, j, w_sum]]
+            if not size_average:
+                level[j] = sum(q) / one
+                continue
+            if isinstance(count, str) and count in ("batch", "image"):
+                N = [int(a) + int(b) for a, b in zip(s[:, j, w_cnt], s[:, j, w_nonf])]
+                N = [sum(N)] * n if count == "batch" else N
+            elif isinstance(count, str):
+                raise ValueError("loss_summary: count must be 'batch', 'image' or an L x 2 array, got %r" % (count,))
+            else:
+                c = np.asarray(count, np.float64)
+                if c.shape != (L, 2):
+                    raise ValueError("loss_summary: a count array must have shape (%d, 2), got %r" % (L, c.shape))
+                N = [float(c[j, t])] * n
+            level[j] = sum((qi / one) / Ni for qi, Ni in zip(q, N) if Ni > 0)
+        parts.append(level)
+    lwj = np.ones(L) if size_average else np.asarray(lw[:L], np.float64)
+    flow, occ = w_epe * lwj * parts[0], w_occ * lwj * parts[1]
+    valid0 = int(s[:, 0, LOSS_EPE_VALID].sum())
+    epe = float(flow_scale) * (sum(int(v) for v in s[:, 0, LOSS_EPE_Q20]) / one) / valid0 if valid0 else float("nan")
+    nonf = int(s[:, :, LOSS_EPE_FLOW_NONFINITE].sum()) + int(s[:, :, LOSS_EPE_OCC_NONFINITE].sum())
+    return {"flow": flow, "occ": occ, "err": float(flow.sum() + occ.sum()), "epe": epe, "nonfinite": nonf}
 
 
 def _apply_grad_weights(who, o, wt):
@@ -971,6 +1093,30 @@ def _forward_loss_grad(fn, h, x, flow_scale, options, shapes, L, want_loss, want
     op = (_lib.c_float_p * len(outs))(*[_lib.fptr(t) for t in outs]) if want_table else None
     _lib.check(fn(h, _lib.fptr(x), n, H, W, float(flow_scale), _grad_opts_ptr(options), lp, gp, len(grad), op, *tail))
     return grad, loss, outs
+
+
+def _forward_loss_epe(fn, h, who, x, gt_flow, valid, gt_occ, flow_scale, options, count, shapes, L, want_loss, want_grad, want_table, multi=False):
+    """x n x 9 x H x W normalized and its ground truth -> (records or None, gradient table or None, table or None):
+    b2f_forward_loss_epe / b2f_multi_forward_loss_epe (train.lua:296-334 behind model:forward)"""
+    x = _lib.f32(x)
+    if x.ndim != 4 or x.shape[1] != 9:
+        raise ValueError("%s: expected an n x 9 x H x W normalized input, got shape %r" % (who, x.shape))
+    if gt_flow is None:
+        raise ValueError("%s: objective='epe' needs gt_flow (n x 2 x H x W, pixels)" % who)
+    n, _, H, W = x.shape
+    gt, va, lb = score_ground_truth(n, H, W, gt_flow, valid, gt_occ, who)
+    sh = shapes(H, W)
+    mode, counts = epe_count_args(count, L, who, batch_ok=not multi)
+    loss = np.empty((n, L, LOSS_EPE_WORDS), np.uint64) if want_loss else None
+    lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong)) if want_loss else None
+    grad = [np.empty((n, c, hh, ww), np.float32) for (c, hh, ww) in sh] if want_grad else None
+    gp = (_lib.c_float_p * len(grad))(*[_lib.fptr(g) for g in grad]) if want_grad else None
+    outs = [np.empty((n, c, hh, ww), np.float32) for (c, hh, ww) in sh] if want_table else None
+    op = (_lib.c_float_p * len(outs))(*[_lib.fptr(t) for t in outs]) if want_table else None
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+    args = (h, _lib.fptr(x), n, H, W, _lib.fptr(gt), u8p(va), u8p(lb), float(flow_scale), _epe_opts_ptr(options), mode, counts, lp, gp, len(sh))
+    _lib.check(fn(*(args if multi else args + (op,))))
+    return loss, grad, outs
 
 
 def _forward_loss(fn, h, x, flow_scale, L, shapes, words=LOSS_WORDS):
@@ -1307,15 +1453,22 @@ class Model(object):
         _lib.check(_lib.lib().b2f_forward(self._h, _lib.fptr(x), B, H, W, ptrs, len(outs)))
         return outs
 
-    def forwardLoss(self, x, flow_scale=20.0, want_table=False, objective="pme", ssim_range="batch"):
+    def forwardLoss(self, x, flow_scale=20.0, want_table=False, objective="pme", ssim_range="batch", gt_flow=None, valid=None, gt_occ=None,
+                    options=None):
         """model:forward followed by the unsupervised validation loss of test.lua:266-297 (b2f_forward_loss): x n x 9 x H x W,
         already normalized -> uint64 records (n, L, 16), those of ops.table_loss(self.forward(x), x[:, 3:6]); the table stays on the
         GPU.  want_table=True returns (records, table) with the table of Model.forward, bit for bit.  loss_summary reads the
         records.  objective="finetune" (b2f_forward_loss_ft): records (n, L, 24), those of ops.table_loss(..., objective="finetune").
         objective="ssim" (b2f_forward_loss_ssim): records (n, L, 32) with the SSIM + L1 sums of OSSIML1Criterion.lua; ssim_range as for
-        ops.table_loss: "batch" is refused when the request is cut into sub-batches, "image" and an L x 2 array do not depend on the cut."""
+        ops.table_loss: "batch" is refused when the request is cut into sub-batches, "image" and an L x 2 array do not depend on the cut.
+        objective="epe" (b2f_forward_loss_epe; train.lua:296-334): records (n, L, 8), those of ops.table_loss_epe(self.forward(x), gt_flow,
+        valid, gt_occ, options=options); the ground truth of a sub-batch is uploaded with its frames."""
         words = loss_words(objective)
         L = self.n_outputs // (5 if self.past_flow else 4)
+        if objective == "epe":
+            loss, _, outs = _forward_loss_epe(_lib.lib().b2f_forward_loss_epe, self._h, "forwardLoss", x, gt_flow, valid, gt_occ, flow_scale, options,
+                                              "batch", self.output_shapes, L, True, False, want_table)
+            return (loss, outs) if want_table else loss
         base, tail = loss_entry("b2f_forward_loss%s", objective), ssim_range_args(objective, ssim_range, L, "forwardLoss")
         entry = lambda *a: base(*(a + tail))
         if want_table:
@@ -1323,57 +1476,117 @@ class Model(object):
         fn = lambda h, xp, n, H, W, fsc, lp: entry(h, xp, n, H, W, fsc, lp, None, 0)
         return _forward_loss(fn, self._h, x, flow_scale, L, None, words)[0]
 
-    def forwardLossDevice(self, d_in, n, H, W, d_loss, flow_scale=20.0, stream=None, objective="pme", ssim_range="batch"):
+    def _forward_loss_epe_device(self, who, d_in, n, H, W, d_loss, d_grad, flow_scale, stream, gt_flow, valid, gt_occ, count, options):
+        """b2f_forward_loss_epe_device: gt_flow (n x 2 x H x W float32), valid and gt_occ (n x H x W uint8, or None) are device pointers"""
+        if not gt_flow:
+            raise ValueError(who + ": objective='epe' needs gt_flow, a device pointer to n x 2 x H x W float32")
+        gptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad]) if d_grad is not None else None
+        mode, counts = epe_count_args(count, self.n_outputs // (5 if self.past_flow else 4), who)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        _lib.check(_lib.lib().b2f_forward_loss_epe_device(self._h, p(d_in), IN_NORMALIZED, int(n), int(H), int(W), p(gt_flow), p(valid), p(gt_occ),
+                                                          float(flow_scale), _epe_opts_ptr(options), mode, counts, p(d_loss), gptrs,
+                                                          len(d_grad) if d_grad is not None else 0, p(stream)))
+
+    def forwardLossDevice(self, d_in, n, H, W, d_loss, flow_scale=20.0, stream=None, objective="pme", ssim_range="batch", gt_flow=None, valid=None,
+                          gt_occ=None, options=None):
         """b2f_forward_loss_device on device pointers (ints): d_in n x 9 x H x W normalized float32, d_loss n x L x 16 uint64 (test.lua:266-297);
         asynchronous on `stream`.  objective="finetune" (b2f_forward_loss_ft_device): d_loss n x L x 24; objective="ssim"
-        (b2f_forward_loss_ssim_device): d_loss n x L x 32, ssim_range as for forwardLoss."""
+        (b2f_forward_loss_ssim_device): d_loss n x L x 32, ssim_range as for forwardLoss.  objective="epe" (b2f_forward_loss_epe_device): d_loss
+        n x L x 8, gt_flow / valid / gt_occ device pointers, options of loss_epe_options."""
+        if objective == "epe":
+            return self._forward_loss_epe_device("forwardLossDevice", d_in, n, H, W, d_loss, None, flow_scale, stream, gt_flow, valid, gt_occ, "batch", options)
         entry = loss_entry("b2f_forward_loss%s_device", objective)
         tail = ssim_range_args(objective, ssim_range, self.n_outputs // (5 if self.past_flow else 4), "forwardLossDevice")
         _lib.check(entry(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale), C.c_void_p(d_loss),
                          C.c_void_p(stream) if stream else None, *tail))
 
-    def tableLossDevice(self, d_table, n, H, W, d_ref, d_loss, flow_scale=20.0, stream=None, objective="pme", ssim_range="batch"):
+    def _table_loss_epe_device(self, who, d_table, n, H, W, d_loss, d_grad, flow_scale, stream, gt_flow, valid, gt_occ, count, options):
+        """b2f_table_loss_epe_device: gt_flow (n x 2 x H x W float32), valid and gt_occ (n x H x W uint8, or None) are device pointers"""
+        if not gt_flow:
+            raise ValueError(who + ": objective='epe' needs gt_flow, a device pointer to n x 2 x H x W float32")
+        if d_grad is not None and len(d_grad) != len(d_table):
+            raise ValueError(who + ": the gradient table must have the table's %d tensors" % len(d_table))
+        ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
+        gptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad]) if d_grad is not None else None
+        mode, counts = epe_count_args(count, len(d_table) // (5 if self.past_flow else 4), who)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        _lib.check(_lib.lib().b2f_table_loss_epe_device(self._h, ptrs, len(d_table), int(n), int(H), int(W), p(gt_flow), p(valid), p(gt_occ),
+                                                        float(flow_scale), _epe_opts_ptr(options), mode, counts, p(d_loss), gptrs, p(stream)))
+
+    def tableLossDevice(self, d_table, n, H, W, d_ref, d_loss, flow_scale=20.0, stream=None, objective="pme", ssim_range="batch", gt_flow=None,
+                        valid=None, gt_occ=None, count="batch", options=None):
         """b2f_table_loss_device on device pointers (ints): d_table the L x 4 | 5 tensors of an output table in table order, d_ref
         n x 3 x H x W, d_loss n x L x 16 uint64 (test.lua:266-297); asynchronous on `stream`.  objective="finetune"
         (b2f_table_loss_ft_device): d_loss n x L x 24; objective="ssim" (b2f_table_loss_ssim_device): d_loss n x L x 32, ssim_range
-        "batch" (over the call's n images), "image" or an L x 2 array."""
+        "batch" (over the call's n images), "image" or an L x 2 array.  objective="epe" (b2f_table_loss_epe_device; train.lua:296-334):
+        d_loss n x L x 8, d_ref is not read (None), gt_flow / valid / gt_occ device pointers as for flowScoreDevice, options of
+        loss_epe_options; count is read by the gradient only."""
+        if objective == "epe":
+            return self._table_loss_epe_device("tableLossDevice", d_table, n, H, W, d_loss, None, flow_scale, stream, gt_flow, valid, gt_occ, count, options)
         ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
         entry = loss_entry("b2f_table_loss%s_device", objective)
         tail = ssim_range_args(objective, ssim_range, len(d_table) // (5 if self.past_flow else 4), "tableLossDevice")
         _lib.check(entry(self._h, ptrs, len(d_table), int(n), int(H), int(W), C.c_void_p(d_ref), float(flow_scale), C.c_void_p(d_loss),
                          C.c_void_p(stream) if stream else None, *tail))
 
-    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, want_table=False, ssim_range="batch"):
+    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, want_table=False, ssim_range="batch", objective=None, gt_flow=None,
+                        valid=None, gt_occ=None, count="batch"):
         """model:forward followed by `gradOutputs` of train.lua:428-468 (b2f_forward_loss_grad): x n x 9 x H x W, already normalized ->
         the gradient of the pme objective with respect to every tensor of the output table, a list with the shapes of
         Model.forward's, that of ops.table_loss_grad(self.forward(x), x[:, 3:6]); the table stays on the GPU.  options: of
         loss_grad_options (None: the defaults) or of loss_grad_ft_options (b2f_forward_loss_grad_ft: the fine-tuning objectives of the
         Soft models).  want_loss=True returns (gradient, records) with the records of forwardLoss (of forwardLoss(objective="finetune")
         with loss_grad_ft_options), from the same pass; want_table=True appends the table of Model.forward, bit for bit.  With the options
-        of loss_grad_ssim_options: b2f_forward_loss_grad_ssim, the records of forwardLoss(objective="ssim"), ssim_range as there."""
+        of loss_grad_ssim_options: b2f_forward_loss_grad_ssim, the records of forwardLoss(objective="ssim"), ssim_range as there.
+        objective="epe" (b2f_forward_loss_epe; train.lua:296-334): options of loss_epe_options, gt_flow / valid / gt_occ as for
+        ops.table_loss_epe, whose gradient and records of self.forward(x) these are; count "batch" takes the counts of sizeAverage over the
+        whole request before its first sub-batch, so a cut changes nothing."""
         L = self.n_outputs // (5 if self.past_flow else 4)
+        if objective == "epe":
+            loss, grad, outs = _forward_loss_epe(_lib.lib().b2f_forward_loss_epe, self._h, "forwardLossGrad", x, gt_flow, valid, gt_occ, flow_scale,
+                                                 options, count, self.output_shapes, L, want_loss, True, want_table)
+            if not want_loss and not want_table:
+                return grad
+            return (grad,) + ((loss,) if want_loss else ()) + ((outs,) if want_table else ())
+        if objective is not None:
+            raise ValueError("forwardLossGrad: objective is 'epe' or None (the options name every other objective)")
         grad, loss, outs = _forward_loss_grad(_grad_entry("b2f_forward_loss_grad", options), self._h, x, flow_scale, options, self.output_shapes, L,
                                               want_loss, want_table, _grad_range_args(options, ssim_range, L, "forwardLossGrad"))
         if not want_loss and not want_table:
             return grad
         return (grad,) + ((loss,) if want_loss else ()) + ((outs,) if want_table else ())
 
-    def forwardLossGradDevice(self, d_in, n, H, W, d_grad, d_loss=None, flow_scale=20.0, options=None, stream=None, ssim_range="batch"):
+    def forwardLossGradDevice(self, d_in, n, H, W, d_grad, d_loss=None, flow_scale=20.0, options=None, stream=None, ssim_range="batch", objective=None,
+                              gt_flow=None, valid=None, gt_occ=None, count="batch"):
         """b2f_forward_loss_grad_device on device pointers (ints): d_in n x 9 x H x W normalized float32, d_grad the n_outputs tensors
         of the gradient table (train.lua:428-468), d_loss n x L x 16 uint64 or None; asynchronous on `stream`.  With the options of
         loss_grad_ft_options: b2f_forward_loss_grad_ft_device, d_loss n x L x 24; of loss_grad_ssim_options:
-        b2f_forward_loss_grad_ssim_device, d_loss n x L x 32, ssim_range as for forwardLoss."""
+        b2f_forward_loss_grad_ssim_device, d_loss n x L x 32, ssim_range as for forwardLoss.  objective="epe"
+        (b2f_forward_loss_epe_device): options of loss_epe_options, gt_flow / valid / gt_occ device pointers, d_loss n x L x 8; with
+        size_average, count "batch" is refused when the request would be cut into sub-batches."""
+        if objective == "epe":
+            return self._forward_loss_epe_device("forwardLossGradDevice", d_in, n, H, W, d_loss, d_grad, flow_scale, stream, gt_flow, valid, gt_occ, count,
+                                                 options)
+        if objective is not None:
+            raise ValueError("forwardLossGradDevice: objective is 'epe' or None (the options name every other objective)")
         ptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad])
         tail = _grad_range_args(options, ssim_range, self.n_outputs // (5 if self.past_flow else 4), "forwardLossGradDevice")
         _lib.check(_grad_entry("b2f_forward_loss_grad_device", options)(self._h, C.c_void_p(d_in), IN_NORMALIZED, int(n), int(H), int(W), float(flow_scale),
                                                             _grad_opts_ptr(options), C.c_void_p(d_loss) if d_loss else None, ptrs, len(d_grad),
                                                             C.c_void_p(stream) if stream else None, *tail))
 
-    def tableLossGradDevice(self, d_table, n, H, W, d_ref, d_grad, flow_scale=20.0, options=None, stream=None, ssim_range="batch"):
+    def tableLossGradDevice(self, d_table, n, H, W, d_ref, d_grad, flow_scale=20.0, options=None, stream=None, ssim_range="batch", objective=None,
+                            gt_flow=None, valid=None, gt_occ=None, count="batch", d_loss=None):
         """b2f_table_loss_grad_device on device pointers (ints): d_table the L x 4 | 5 tensors of an output table in table order, d_ref
         n x 3 x H x W, d_grad as many tensors of the same shapes (train.lua:428-468); asynchronous on `stream`.  With the options of
         loss_grad_ft_options: b2f_table_loss_grad_ft_device; of loss_grad_ssim_options: b2f_table_loss_grad_ssim_device, ssim_range as for
-        tableLossDevice."""
+        tableLossDevice.  objective="epe" (b2f_table_loss_epe_device; train.lua:296-334): options of loss_epe_options, d_ref is not read
+        (None), gt_flow / valid / gt_occ device pointers, count "batch" (N_j over the call's images), "image" or an L x 2 array, d_loss
+        (n x L x 8 uint64) or None for the records of the same launches."""
+        if objective == "epe":
+            return self._table_loss_epe_device("tableLossGradDevice", d_table, n, H, W, d_loss, d_grad, flow_scale, stream, gt_flow, valid, gt_occ, count, options)
+        if objective is not None:
+            raise ValueError("tableLossGradDevice: objective is 'epe' or None (the options name every other objective)")
         ptrs = (C.c_void_p * len(d_table))(*[C.c_void_p(int(p)) for p in d_table])
         gptrs = (C.c_void_p * len(d_grad))(*[C.c_void_p(int(p)) for p in d_grad])
         if len(d_grad) != len(d_table):
@@ -1497,11 +1710,29 @@ class MultiModel(object):
         return _compute_flow_sequence_warp("b2f_multi_", self._h, frames, flow_scale, want_warped, want_photo, want_flow, want_masks, out,
                                            want_prob, own_past_flow, want_past)
 
-    def forwardLoss(self, x, flow_scale=20.0, objective="pme", ssim_range="image"):
+    def _shapes_and_levels(self):
+        """(output_shapes(H, W), L) of the replicas' model"""
+        c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
+        lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+        _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
+
+        def shapes(H, W):
+            ch, oh, ow = (C.c_int * 64)(), (C.c_int * 64)(), (C.c_int * 64)()
+            _lib.check(_lib.lib().b2f_output_shapes(c0, H, W, ch, oh, ow, 64))
+            return [(ch[i], oh[i], ow[i]) for i in range(no.value)]
+
+        return shapes, no.value // (5 if pf.value else 4)
+
+    def forwardLoss(self, x, flow_scale=20.0, objective="pme", ssim_range="image", gt_flow=None, valid=None, gt_occ=None, options=None):
         """Model.forwardLoss over the GPUs (b2f_multi_forward_loss / b2f_multi_forward_loss_ft / b2f_multi_forward_loss_ssim;
         test.lua:266-297): the same words.  objective="ssim" takes ssim_range="image" or an L x 2 array: the batch's range would depend
-        on how the images are split over the GPUs."""
+        on how the images are split over the GPUs.  objective="epe" (b2f_multi_forward_loss_epe): gt_flow / valid / gt_occ / options as
+        for Model.forwardLoss; the ground truth is split with the triplets."""
         words = loss_words(objective)
+        if objective == "epe":
+            shapes, L = self._shapes_and_levels()
+            return _forward_loss_epe(_lib.lib().b2f_multi_forward_loss_epe, self._h, "MultiModel.forwardLoss", x, gt_flow, valid, gt_occ, flow_scale,
+                                     options, "image", shapes, L, True, False, False, multi=True)[0]
         c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
         lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))
@@ -1510,10 +1741,19 @@ class MultiModel(object):
         tail = ssim_range_args(objective, ssim_range, L, "MultiModel.forwardLoss", batch_ok=False)
         return _forward_loss(lambda *a: base(*(a + tail)), self._h, x, flow_scale, L, None, words)[0]
 
-    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, ssim_range="image"):
+    def forwardLossGrad(self, x, flow_scale=20.0, options=None, want_loss=True, ssim_range="image", objective=None, gt_flow=None, valid=None,
+                        gt_occ=None, count="image"):
         """Model.forwardLossGrad over the GPUs (b2f_multi_forward_loss_grad, b2f_multi_forward_loss_grad_ft,
         b2f_multi_forward_loss_grad_ssim; train.lua:428-468): the same bits.  With loss_grad_ssim_options ssim_range is "image" or an
-        L x 2 array, as for MultiModel.forwardLoss."""
+        L x 2 array, as for MultiModel.forwardLoss.  objective="epe" (b2f_multi_forward_loss_epe): as Model.forwardLossGrad, with count
+        "image" (the default here) or an L x 2 array: the batch's counts would depend on how the images are split over the GPUs."""
+        if objective == "epe":
+            shapes, L = self._shapes_and_levels()
+            loss, grad, _ = _forward_loss_epe(_lib.lib().b2f_multi_forward_loss_epe, self._h, "MultiModel.forwardLossGrad", x, gt_flow, valid, gt_occ,
+                                              flow_scale, options, count, shapes, L, want_loss, True, False, multi=True)
+            return (grad, loss) if want_loss else grad
+        if objective is not None:
+            raise ValueError("MultiModel.forwardLossGrad: objective is 'epe' or None (the options name every other objective)")
         c0 = C.c_void_p(_lib.lib().b2f_multi_context(self._h, 0))
         lv, win, pf, no, npar = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         _lib.check(_lib.lib().b2f_info(c0, C.byref(lv), C.byref(win), C.byref(pf), C.byref(no), C.byref(npar)))

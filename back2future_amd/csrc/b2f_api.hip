@@ -963,7 +963,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1011; }
+int b2f_version(void) { return 1012; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1523,6 +1523,7 @@ struct LossPlan {
     std::vector<size_t> cnt, off;   // floats and byte offset of every tensor of the table
     std::vector<size_t> goff;       // byte offset of every tensor of the gradient table (b2f_forward_loss_grad only)
     size_t in_off = 0, loss_off = 0, bytes = 0;
+    size_t gt_off = 0, valid_off = 0, occ_off = 0;   // the ground truth of a sub-batch (b2f_forward_loss_epe only)
 };
 
 int check_forward_loss(const b2f_ctx *c, const std::string &w, int n, int H, int W, double flow_scale)
@@ -1537,7 +1538,7 @@ int check_forward_loss(const b2f_ctx *c, const std::string &w, int n, int H, int
     return 0;
 }
 
-LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input, const LossKind &kind, bool with_grad = false)
+LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input, const LossKind &kind, bool with_grad = false, bool with_truth = false)
 {
     LossPlan p;
     p.kind = kind;
@@ -1548,6 +1549,9 @@ LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input,
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     p.in_off = take(with_input ? (size_t)nb * 9 * H * W * sizeof(float) : 0);
+    p.gt_off = take(with_truth ? (size_t)nb * 2 * H * W * sizeof(float) : 0);
+    p.valid_off = take(with_truth ? (size_t)nb * H * W : 0);
+    p.occ_off = take(with_truth ? (size_t)nb * H * W : 0);
     for (int i = 0; i < p.n_outs; ++i) {
         const int j = i / p.per, ch = (i % p.per) >= p.per - 2 ? 3 : 2;
         p.cnt.push_back((size_t)nb * ch * (H >> j) * (W >> j));
@@ -1585,10 +1589,14 @@ int forward_table_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int 
 
 // the table of nb triplets into tab, its records into d_loss where wanted (else nullptr), its gradient table (train.lua:428-468) from the
 // checked options *o into grad where wanted; all on s.  The pyramid of R is built once: by the records' launch where there is one.
+// epe: the supervised objective of train.lua:296-334 instead, against the device ground truth of these nb triplets (o is not read).
 int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const GradOpts *o, const LossPlan &lp,
-                     float *const *tab, unsigned long long *d_loss, float *const *grad)
+                     float *const *tab, unsigned long long *d_loss, float *const *grad, const EpeArgs *epe = nullptr)
 {
     CHK(forward_table_run(c, s, d_in, nb, H, W, lp, tab));
+    if (epe)
+        return table_loss_epe_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, epe->gt_flow, epe->valid, epe->gt_occ, flow_scale, epe->o, epe->count_mode,
+                                  epe->counts, d_loss);
     const size_t hw = (size_t)H * W;
     if (d_loss) CHK(table_loss_run(c, s, tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, d_loss, lp.kind));
     if (grad) CHK(table_loss_grad_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, *o, d_loss));
@@ -1645,13 +1653,14 @@ struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub
 
 // the sub-batch loop of b2f_forward_loss* and b2f_forward_loss_grad* on checked arguments: upload, forward_loss_run, download of the
 // records (loss), the gradient table (grad, from *o) and the table (outs), each where not null
+// epe: the supervised objective instead, against host ground truth of the n triplets, uploaded with the frames of each sub-batch
 int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const LossKind &k, const GradOpts *o,
-                          unsigned long long *loss, float *const *grad, float *const *outs)
+                          unsigned long long *loss, float *const *grad, float *const *outs, const EpeArgs *epe = nullptr)
 {
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
     const int sb = loss_subbatch(c, n, H, W);
-    const LossPlan lp = make_loss_plan(c, sb, H, W, true, k, grad != nullptr);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, true, k, grad != nullptr, epe != nullptr);
     std::vector<float *> tab, gr;
     CHK(loss_work_tables(c, lp, tab, grad ? &gr : nullptr));
     float *d_in = (float *)(c->loss_work.dev + lp.in_off);
@@ -1661,8 +1670,20 @@ int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int
     for (int b0 = 0; b0 < n; b0 += sb) {
         const int nb = std::min(sb, n - b0);
         HIPCHK(hipMemcpyAsync(d_in, x + (size_t)b0 * 9 * hw, (size_t)nb * 9 * hw * sizeof(float), hipMemcpyHostToDevice, s));
+        EpeArgs de;
+        if (epe) {   // the sub-batch's ground truth, behind its frames on the same stream
+            de = *epe;
+            float *d_gt = (float *)(c->loss_work.dev + lp.gt_off);
+            unsigned char *d_valid = (unsigned char *)(c->loss_work.dev + lp.valid_off), *d_occ = (unsigned char *)(c->loss_work.dev + lp.occ_off);
+            HIPCHK(hipMemcpyAsync(d_gt, epe->gt_flow + (size_t)b0 * 2 * hw, (size_t)nb * 2 * hw * sizeof(float), hipMemcpyHostToDevice, s));
+            if (epe->valid) HIPCHK(hipMemcpyAsync(d_valid, epe->valid + (size_t)b0 * hw, (size_t)nb * hw, hipMemcpyHostToDevice, s));
+            if (epe->gt_occ) HIPCHK(hipMemcpyAsync(d_occ, epe->gt_occ + (size_t)b0 * hw, (size_t)nb * hw, hipMemcpyHostToDevice, s));
+            de.gt_flow = d_gt;
+            de.valid = epe->valid ? d_valid : nullptr;
+            de.gt_occ = epe->gt_occ ? d_occ : nullptr;
+        }
         // (a shorter last sub-batch lays its tensors out for nb images in the same buffers)
-        CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, o, lp, tab.data(), d_loss, grad ? gr.data() : nullptr));
+        CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, o, lp, tab.data(), d_loss, grad ? gr.data() : nullptr, epe ? &de : nullptr));
         if (loss)
             HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * lp.words, d_loss, (size_t)nb * lp.L * lp.words * sizeof(unsigned long long),
                                   hipMemcpyDeviceToHost, s));
@@ -1712,6 +1733,68 @@ int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int 
     return forward_loss_host_run(c, x, n, req, H, W, flow_scale, o.rec, &o, loss, grad, outs);
 }
 
+namespace {
+
+// what the b2f_forward_loss_epe* entries check beyond check_forward_loss: the options (into e->o), the ground truth, the counts and the
+// optional gradient table's pointers
+int check_forward_loss_epe(const b2f_ctx *c, const std::string &w, const b2f_loss_epe_opts *opts, float *const *grad, int n_outs, EpeArgs *e)
+{
+    if (opts) e->o = *opts;
+    else (void)b2f_loss_epe_defaults(&e->o);
+    const int L = c->g.n_outputs() / (c->past_flow ? 5 : 4);
+    const char *why = loss_epe_refusal(e->o, e->gt_flow, e->gt_occ, e->count_mode, e->counts, L);
+    if (why) return fail(w + ": " + why);
+    if (!grad) return 0;
+    if (n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
+    for (int i = 0; i < n_outs; ++i) {
+        if (!grad[i]) return fail(w + ": null tensor in the gradient table");
+        if ((const void *)grad[i] == (const void *)e->gt_flow || (const void *)grad[i] == (const void *)e->valid || (const void *)grad[i] == (const void *)e->gt_occ)
+            return fail(w + ": the gradient table must not alias the ground truth");
+        for (int k = 0; k < i; ++k)
+            if (grad[i] == grad[k]) return fail(w + ": the gradient table must not alias itself");
+    }
+    return 0;
+}
+
+const LossKind kEpeRecords = LossKind{B2F_LOSS_EPE_WORDS, 0, nullptr};
+
+}  // namespace
+
+// b2f_forward_loss_epe on a shard: `req` is the caller's n (b2f_multi_forward_loss_epe passes its own down, and counts of its own)
+int b2f::forward_loss_epe_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, const float *gt_flow, const unsigned char *valid,
+                               const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
+                               unsigned long long *loss, float *const *grad, int n_outs, float *const *outs)
+{
+    const std::string w = "b2f_forward_loss_epe";
+    if (!c || !x) return fail(w + ": null argument");
+    if (!loss && !grad) return fail(w + ": loss and grad are both null: nothing to compute");
+    CHK(check_forward_loss(c, w, n, H, W, flow_scale));
+    EpeArgs e = {gt_flow, valid, gt_occ, {}, count_mode, counts};
+    CHK(check_forward_loss_epe(c, w, opts, grad, n_outs, &e));
+    if (!grad && outs && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
+    for (int i = 0; outs && i < n_outs; ++i) {
+        if (!outs[i]) return fail(w + ": null tensor in outs");
+        for (int k = 0; grad && k < n_outs; ++k)
+            if (outs[i] == grad[k]) return fail(w + ": the gradient table must not alias outs");
+    }
+    // N_j, N'_j of the batch over the caller's whole n first: a cut into sub-batches changes nothing
+    const int L = c->g.n_outputs() / (c->past_flow ? 5 : 4);
+    std::vector<double> whole;
+    if (grad && e.o.size_average && count_mode == B2F_EPE_COUNT_BATCH && loss_subbatch(c, n, H, W) < n) {
+        std::vector<unsigned long long> cnt((size_t)n * L * 2);
+        epe_counts_host(valid, e.o.occ > 0.0 ? gt_occ : nullptr, L, n, H, W, cnt.data());
+        whole.assign((size_t)L * 2, 0.0);
+        for (int j = 0; j < 2 * L; ++j) {
+            unsigned long long all = 0;
+            for (int b = 0; b < n; ++b) all += cnt[(size_t)b * L * 2 + j];
+            whole[(size_t)j] = (double)all;
+        }
+        e.count_mode = B2F_EPE_COUNT_GIVEN;
+        e.counts = whole.data();
+    }
+    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, kEpeRecords, nullptr, loss, grad, outs, &e);
+}
+
 extern "C" {
 
 // model:forward + the gradient table of train.lua:428-468 from host memory
@@ -1734,21 +1817,31 @@ extern "C++" {
 // the six device entries: b2f_forward_loss_device / _ft_device / _ssim_device (a == nullptr: dev_loss required, no gradient table; k:
 // which records) and b2f_forward_loss_grad_device / _grad_ft_device / _grad_ssim_device (a: dev_grad required, dev_loss optional, k = a->rec())
 static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
-                               const GradArgs *a, const LossKind &k, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream)
+                               const GradArgs *a, const LossKind &k, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream,
+                               const EpeArgs *epe = nullptr)
 {
-    const bool with_grad = a != nullptr;
-    if (!c || !dev_in || (with_grad ? !dev_grad : !dev_loss)) return fail(w + ": null argument");
+    // (b2f_forward_loss_epe_device: a == nullptr, epe the device ground truth of the n triplets; dev_loss and dev_grad each optional)
+    const bool with_grad = epe ? dev_grad != nullptr : a != nullptr;
+    if (!c || !dev_in || (epe ? (!dev_grad && !dev_loss) : with_grad ? !dev_grad : !dev_loss)) return fail(w + ": null argument");
     if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
     CHK(check_forward_loss_kind(c, w, k, n, H, W));
     GradOpts o;
-    if (with_grad) CHK(check_forward_loss_grad(c, w, *a, dev_grad, n_outs, &o));
+    EpeArgs e = {};
+    const int sb = loss_subbatch(c, n, H, W);
+    if (epe) {
+        e = *epe;
+        CHK(check_forward_loss_epe(c, w, &epe->o, dev_grad, n_outs, &e));
+        if (with_grad && e.o.size_average && e.count_mode == B2F_EPE_COUNT_BATCH && sb < n)
+            return fail(w + ": B2F_EPE_COUNT_BATCH needs the request in one sub-batch and this one would be cut (host_subbatch_pixels): use "
+                            "B2F_EPE_COUNT_IMAGE or B2F_EPE_COUNT_GIVEN, which do not depend on the cut");
+        if ((uintptr_t)e.gt_flow & 15) return fail(w + ": device buffers must be 16-byte aligned");
+    } else if (with_grad) CHK(check_forward_loss_grad(c, w, *a, dev_grad, n_outs, &o));
     uintptr_t bits = (uintptr_t)dev_in | (uintptr_t)dev_loss;
     for (int i = 0; with_grad && i < n_outs; ++i) bits |= (uintptr_t)dev_grad[i];
     if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
-    const int sb = loss_subbatch(c, n, H, W);
     const LossPlan lp = make_loss_plan(c, sb, H, W, false, k);
     std::vector<float *> tab, gr((size_t)lp.n_outs);
     CHK(loss_work_tables(c, lp, tab, nullptr));
@@ -1758,12 +1851,39 @@ static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev
         // the sub-batch's part of the caller's gradient tensors: image b0 of every one
         for (int i = 0; with_grad && i < lp.n_outs; ++i) gr[(size_t)i] = dev_grad[i] + (size_t)b0 * (lp.cnt[(size_t)i] / (size_t)sb);
         // (without a gradient table o is unresolved and forward_loss_run does not read it)
+        EpeArgs de = e;
+        if (epe) {   // the sub-batch's part of the ground truth: image b0
+            de.gt_flow = e.gt_flow + (size_t)b0 * 2 * hw;
+            de.valid = e.valid ? e.valid + (size_t)b0 * hw : nullptr;
+            de.gt_occ = e.gt_occ ? e.gt_occ + (size_t)b0 * hw : nullptr;
+        }
         CHK(forward_loss_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, &o, lp, tab.data(),
-                             dev_loss ? dev_loss + (size_t)b0 * lp.L * lp.words : nullptr, with_grad ? gr.data() : nullptr));
+                             dev_loss ? dev_loss + (size_t)b0 * lp.L * lp.words : nullptr, with_grad ? gr.data() : nullptr, epe ? &de : nullptr));
     }
     return 0;
 }
 }  // extern "C++"
+
+// model:forward + the supervised objective of train.lua:296-334 (criterions/L2Criterion.lua:27-71) from host memory
+int b2f_forward_loss_epe(b2f_ctx *c, const float *x, int n, int H, int W, const float *gt_flow, const unsigned char *valid, const unsigned char *gt_occ,
+                         double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts, unsigned long long *loss,
+                         float *const *grad, int n_outs, float *const *outs) try
+{
+    return forward_loss_epe_host(c, x, n, 0, H, W, gt_flow, valid, gt_occ, flow_scale, opts, count_mode, counts, loss, grad, n_outs, outs);
+}
+B2F_CATCH("b2f_forward_loss_epe")
+
+// the same on device pointers
+int b2f_forward_loss_epe_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, const float *dev_gt_flow,
+                                const unsigned char *dev_valid, const unsigned char *dev_gt_occ, double flow_scale, const b2f_loss_epe_opts *opts,
+                                int count_mode, const double *counts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
+{
+    EpeArgs e = {dev_gt_flow, dev_valid, dev_gt_occ, {}, count_mode, counts};
+    if (opts) e.o = *opts;
+    else (void)b2f_loss_epe_defaults(&e.o);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, kEpeRecords, dev_loss, dev_grad, n_outs, stream, &e);
+}
+B2F_CATCH("b2f_forward_loss_epe_device")
 
 // model:forward + the gradient table of train.lua:428-468 on device pointers
 int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,

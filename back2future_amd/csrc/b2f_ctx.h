@@ -684,6 +684,25 @@ int table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, int
 // ranges into a zeroed record buffer of the context (c->loss_rec)
 int table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
                         const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, unsigned long long *dev_loss);
+// b2f_tableloss_epe.hip: the records (dev_loss, or nullptr) and / or the gradient table (dev_grad, or nullptr) of the supervised objective
+// of train.lua:296-334 of n images on s, from checked options and counts, under the profile row table_loss_epe; rescale is the context's
+// rescale_flow; the counting pass of size_average goes into c->loss_rec
+int table_loss_epe_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
+                       const float *dev_gt_flow, const unsigned char *dev_valid, const unsigned char *dev_gt_occ, double flow_scale,
+                       const b2f_loss_epe_opts &o, int count_mode, const double *counts, unsigned long long *dev_loss);
+// what the b2f_forward_loss_epe* entries hand down beside the input: the ground truth of image 0 of the request (host memory for the host
+// entries, device memory for the device entry; valid and gt_occ may be null), the checked options and the counts
+struct EpeArgs {
+    const float *gt_flow;
+    const unsigned char *valid, *gt_occ;
+    b2f_loss_epe_opts o;
+    int count_mode;
+    const double *counts;
+};
+// b2f_api.hip: b2f_forward_loss_epe on n of a request of `req` triplets (0: n); loss, grad and outs may each be null, loss and grad not both
+int forward_loss_epe_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, const float *gt_flow, const unsigned char *valid,
+                          const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
+                          unsigned long long *loss, float *const *grad, int n_outs, float *const *outs);
 // b2f_api.hip: b2f_forward_loss_grad, b2f_forward_loss_grad_ft or b2f_forward_loss_grad_ssim (a.kind) on n of a request of `req`
 // triplets (0: n)
 int forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const GradArgs &a, unsigned long long *loss,

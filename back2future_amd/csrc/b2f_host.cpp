@@ -11,6 +11,7 @@
 #include "b2f_tableloss_ft.h"
 #include "b2f_tableloss_ssim.h"
 #include "b2f_tableloss_grad_ssim.h"
+#include "b2f_tableloss_epe.h"
 #include "../../include/b2f.h"
 
 #include <algorithm>
@@ -865,6 +866,129 @@ static void table_loss_grad_host_impl(const float *const *table, int L, bool pas
                     for (int c = 0; c < 2; ++c) {
                         const double so = (k.on & kGradSmoothOcc) ? S2(o + c * hw) : 0.0;
                         go[c * hw + i] = grad_occ(k, po[c], so, o[(size_t)(1 - c) * hw + i]);
+                    }
+                }
+        }
+    }
+}
+
+}  // namespace b2f
+
+// ---- the supervised objective on the CPU (train.lua:296-334, criterions/L2Criterion.lua:27-71) ---------------------------------------
+namespace b2f {
+
+const char *loss_epe_refusal(const b2f_loss_epe_opts &o, const void *gt_flow, const void *gt_occ, int count_mode, const double *counts, int L)
+{
+    if (!gt_flow) return "null gt_flow";
+    if (!(o.epe >= 0.0) || !std::isfinite(o.epe) || !(o.occ >= 0.0) || !std::isfinite(o.occ)) return "epe and occ of b2f_loss_epe_opts must be finite and >= 0";
+    for (double v : o.level_weights)
+        if (!(v >= 0.0) || !std::isfinite(v)) return "the level weights of b2f_loss_epe_opts must be finite and >= 0";
+    if (o.occ > 0.0 && !gt_occ) return "occ > 0 needs gt_occ";
+    if (count_mode != B2F_EPE_COUNT_BATCH && count_mode != B2F_EPE_COUNT_IMAGE && count_mode != B2F_EPE_COUNT_GIVEN)
+        return "count_mode must be B2F_EPE_COUNT_BATCH, B2F_EPE_COUNT_IMAGE or B2F_EPE_COUNT_GIVEN";
+    if (count_mode == B2F_EPE_COUNT_GIVEN) {
+        if (!counts) return "B2F_EPE_COUNT_GIVEN needs counts (L x 2 doubles)";
+        for (int i = 0; i < 2 * L; ++i)
+            if (!(counts[i] >= 0.0) || !std::isfinite(counts[i])) return "counts must be finite and >= 0";
+    }
+    return nullptr;
+}
+
+void loss_epe_base(const b2f_loss_epe_opts &o, int j, double *kf, double *ko)
+{
+    const double lw = o.size_average ? 1.0 : o.level_weights[j];
+    *kf = o.epe * lw;
+    *ko = o.occ * lw;
+}
+
+void epe_counts_host(const unsigned char *valid, const unsigned char *gt_occ, int L, int n, int H, int W, unsigned long long *cnt)
+{
+    const size_t HW = (size_t)H * W;
+    for (int b = 0; b < n; ++b)
+        for (int j = 0; j < L; ++j) {
+            unsigned long long nv = 0, nl = 0;
+            for (int y = 0; y < (H >> j); ++y)
+                for (int x = 0; x < (W >> j); ++x) {
+                    const size_t S = (size_t)b * HW + ((size_t)y << j) * W + ((size_t)x << j);
+                    nv += (!valid || valid[S]) ? 1u : 0u;
+                    nl += (gt_occ && epe_labelled(gt_occ[S])) ? 1u : 0u;
+                }
+            cnt[((size_t)b * L + j) * 2] = nv;
+            cnt[((size_t)b * L + j) * 2 + 1] = nl;
+        }
+}
+
+void table_loss_epe_host(const float *const *table, int L, bool past, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
+                         const unsigned char *gt_occ, double flow_scale, bool rescale, const b2f_loss_epe_opts &opts, int count_mode,
+                         const double *counts, unsigned long long *loss, float *const *grad)
+{
+    const int per = past ? 5 : 4;
+    const size_t HW = (size_t)H * W;
+    const bool with_occ = opts.occ > 0.0;
+    // N_j, N'_j per image and level as the mode says; read with a gradient table under size_average only
+    std::vector<double> N((size_t)n * L * 2, 0.0);
+    if (grad && opts.size_average) {
+        std::vector<unsigned long long> cnt((size_t)n * L * 2);
+        if (count_mode != B2F_EPE_COUNT_GIVEN) epe_counts_host(valid, gt_occ, L, n, H, W, cnt.data());
+        for (int j = 0; j < L; ++j)
+            for (int t = 0; t < 2; ++t) {
+                unsigned long long all = 0;
+                for (int b = 0; b < n && count_mode == B2F_EPE_COUNT_BATCH; ++b) all += cnt[((size_t)b * L + j) * 2 + t];
+                for (int b = 0; b < n; ++b)
+                    N[((size_t)b * L + j) * 2 + t] = count_mode == B2F_EPE_COUNT_GIVEN ? counts[2 * j + t]
+                                                    : count_mode == B2F_EPE_COUNT_BATCH ? (double)all
+                                                                                        : (double)cnt[((size_t)b * L + j) * 2 + t];
+            }
+    }
+    for (int j = 0; j < L; ++j) {
+        const int h = H >> j, w = W >> j;
+        const size_t hw = (size_t)h * w;
+        const double div = rescale ? (double)(1 << j) : 1.0;
+        double bf, bo;
+        loss_epe_base(opts, j, &bf, &bo);
+        for (int b = 0; b < n; ++b) {
+            const float *f = table[(size_t)j * per] + (size_t)b * 2 * hw, *o = table[(size_t)j * per + per - 3] + (size_t)b * 2 * hw;
+            unsigned long long *rec = loss ? loss + ((size_t)b * L + j) * B2F_LOSS_EPE_WORDS : nullptr;
+            if (rec) {
+                for (int k = 0; k < B2F_LOSS_EPE_WORDS; ++k) rec[k] = 0;
+                rec[B2F_LOSS_EPE_PIXELS] = hw;
+            }
+            if (grad)
+                for (int t = 0; t < per; ++t) {
+                    float *g = grad[(size_t)j * per + t];
+                    const size_t cnt = (t >= per - 2 ? 3 : 2) * hw;
+                    for (size_t i = 0; i < cnt; ++i) g[(size_t)b * cnt + i] = 0.0f;
+                }
+            float *gf = grad ? grad[(size_t)j * per] + (size_t)b * 2 * hw : nullptr, *go = grad ? grad[(size_t)j * per + per - 3] + (size_t)b * 2 * hw : nullptr;
+            const double kf = grad ? epe_factor(bf, opts.size_average != 0, N[((size_t)b * L + j) * 2]) : 0.0;
+            const double ko = grad ? epe_factor(bo, opts.size_average != 0, N[((size_t)b * L + j) * 2 + 1]) : 0.0;
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    const size_t i = (size_t)y * w + x, S = ((size_t)y << j) * W + ((size_t)x << j);
+                    if (!valid || valid[(size_t)b * HW + S]) {
+                        const float *g = gt_flow + (size_t)b * 2 * HW;
+                        const EpeTerm t = epe_flow_pixel(f[i], f[hw + i], g[S], g[HW + S], flow_scale, div, kf);
+                        if (rec) {
+                            rec[B2F_LOSS_EPE_VALID] += t.counted;
+                            rec[B2F_LOSS_EPE_Q20] += t.q20;
+                            rec[B2F_LOSS_EPE_FLOW_NONFINITE] += t.nonfinite;
+                        }
+                        if (gf) {
+                            gf[i] = (float)t.g0;
+                            gf[hw + i] = (float)t.g1;
+                        }
+                    }
+                    if (with_occ && epe_labelled(gt_occ[(size_t)b * HW + S])) {
+                        const EpeTerm t = epe_occ_pixel(o[i], o[hw + i], gt_occ[(size_t)b * HW + S], ko);
+                        if (rec) {
+                            rec[B2F_LOSS_EPE_LABELLED] += t.counted;
+                            rec[B2F_LOSS_EPE_OCC_Q20] += t.q20;
+                            rec[B2F_LOSS_EPE_OCC_NONFINITE] += t.nonfinite;
+                        }
+                        if (go) {
+                            go[i] = (float)t.g0;
+                            go[hw + i] = (float)t.g1;
+                        }
                     }
                 }
         }

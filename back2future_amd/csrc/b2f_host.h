@@ -140,6 +140,21 @@ void ssim_ranges_host(const float *const *table, int L, bool past, int n, int H,
                       unsigned long long *loss);
 // the coefficients of level j of h x w (include/b2f.h: k_s .. k_pr) and which terms are evaluated
 void loss_grad_coef(const b2f_loss_grad_opts &o, int j, int h, int w, GradCoef *k);
+}  // namespace b2f
+struct b2f_loss_epe_opts;
+namespace b2f {
+// The supervised objective on the CPU (train.lua:296-334, criterions/L2Criterion.lua:27-71; b2f_tableloss_epe.h per pixel;
+// b2f_table_loss_epe_host): gt_flow n x 2 x H x W, valid / gt_occ n x H x W bytes or nullptr, read at (y << j, x << j); loss n x L x
+// B2F_LOSS_EPE_WORDS words and grad the table's L x (4 | 5) tensors, each or nullptr; counts: L x 2 doubles with B2F_EPE_COUNT_GIVEN
+void table_loss_epe_host(const float *const *table, int L, bool past, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
+                         const unsigned char *gt_occ, double flow_scale, bool rescale, const b2f_loss_epe_opts &opts, int count_mode,
+                         const double *counts, unsigned long long *loss, float *const *grad);
+// nullptr, or why the *_epe entries refuse their options, ground truth or counts (no HIP call)
+const char *loss_epe_refusal(const b2f_loss_epe_opts &o, const void *gt_flow, const void *gt_occ, int count_mode, const double *counts, int L);
+// epe * lw_j and occ * lw_j of level j (train.lua:313-314,328-331; lw_j = 1 with size_average, train.lua:60-64)
+void loss_epe_base(const b2f_loss_epe_opts &o, int j, double *kf, double *ko);
+// the valid and the labelled source pixels of every image and level: cnt n x L x 2
+void epe_counts_host(const unsigned char *valid, const unsigned char *gt_occ, int L, int n, int H, int W, unsigned long long *cnt);
 
 // .t7 reader (b2f_t7.cpp): returns false and fills err on failure.
 bool load_t7(const std::string &path, std::vector<float> &flat, bool &past_flow, std::string &err);

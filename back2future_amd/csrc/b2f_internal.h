@@ -428,5 +428,17 @@ struct GradSsimCoef;
 hipError_t launch_table_loss_grad_ssim(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref,
                                        size_t ref_stride, const float *pyr, double flow_scale, const GradSsimCoef *coef, const unsigned long long *rec,
                                        hipStream_t s);
+}  // namespace b2f
+// b2f_tableloss_epe.hip: the supervised objective of train.lua:296-334 (criterions/L2Criterion.lua:27-71; include/b2f.h, the *_epe
+// entries): the records (loss: n x L x B2F_LOSS_EPE_WORDS words, zeroed on s first, or nullptr) and / or the gradient table (grad as
+// above, every element written, or nullptr) of the table against gt_flow (n x 2 x H x W), valid and gt_occ (n x H x W bytes or
+// nullptr; gt_occ is read with o.occ > 0 only), all device memory, none an output.  o and counts are checked (b2f_host.h:
+// loss_epe_refusal).  cnt_work: n x L x 2 words of workspace for the counting pass, needed with a gradient table, o.size_average and a
+// count_mode other than B2F_EPE_COUNT_GIVEN.  One launch per level for records and gradient together.
+struct b2f_loss_epe_opts;
+namespace b2f {
+hipError_t launch_table_loss_epe(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *gt_flow,
+                                 const unsigned char *valid, const unsigned char *gt_occ, double flow_scale, bool rescale, const b2f_loss_epe_opts &o,
+                                 int count_mode, const double *counts, unsigned long long *cnt_work, unsigned long long *loss, hipStream_t s);
 
 }  // namespace b2f

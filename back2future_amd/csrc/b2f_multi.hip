@@ -445,6 +445,37 @@ int b2f_multi_forward_loss_ssim(b2f_multi *m, const float *x, int n, int H, int 
 }
 B2F_CATCH("b2f_multi_forward_loss_ssim")
 
+// the supervised objective of train.lua:296-334 behind model:forward over several GPUs; the batch's counts are refused
+int b2f_multi_forward_loss_epe(b2f_multi *m, const float *x, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
+                               const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
+                               unsigned long long *loss, float *const *grad, int n_outs) try
+{
+    const std::string w = __func__;
+    if (!m) return api_fail(w + ": null context");
+    if (!x || !gt_flow || (!loss && !grad) || n <= 0 || H <= 0 || W <= 0) return api_fail(w + ": bad arguments");
+    // (a shard's counts would depend on how the request is split over the GPUs)
+    if (count_mode == B2F_EPE_COUNT_BATCH)
+        return api_fail(w + ": B2F_EPE_COUNT_BATCH is not served over several GPUs: the images of a request are split; use B2F_EPE_COUNT_IMAGE or "
+                            "B2F_EPE_COUNT_GIVEN");
+    const b2f_ctx *c0 = m->ctx[0];
+    const int per = c0->past_flow ? 5 : 4, n_tab = c0->g.n_outputs();
+    if (grad && n_outs != n_tab) return api_fail(w + ": n_outs must be the contexts' n_outputs");
+    for (int i = 0; grad && i < n_outs; ++i)
+        if (!grad[i]) return api_fail(w + ": null tensor in the gradient table");
+    const size_t rec = (size_t)(n_tab / per) * B2F_LOSS_EPE_WORDS, hw = (size_t)H * W;
+    return run_sharded(m, n, [&](int i, int lo, int hi) {
+        std::vector<float *> g((size_t)n_tab);   // the shard's part of every tensor: image lo
+        for (int t = 0; grad && t < n_tab; ++t) {
+            const int j = t / per, ch = (t % per) >= per - 2 ? 3 : 2;
+            g[(size_t)t] = grad[t] + (size_t)lo * ch * (H >> j) * (W >> j);
+        }
+        return forward_loss_epe_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * hw, hi - lo, n, H, W, gt_flow + (size_t)lo * 2 * hw,
+                                     valid ? valid + (size_t)lo * hw : nullptr, gt_occ ? gt_occ + (size_t)lo * hw : nullptr, flow_scale, opts, count_mode,
+                                     counts, loss ? loss + (size_t)lo * rec : nullptr, grad ? g.data() : nullptr, n_outs, nullptr);
+    });
+}
+B2F_CATCH("b2f_multi_forward_loss_epe")
+
 // b2f_multi_forward_loss_grad, b2f_multi_forward_loss_grad_ft and b2f_multi_forward_loss_grad_ssim
 static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const GradArgs &a,
                                    unsigned long long *loss, float *const *grad, int n_outs)

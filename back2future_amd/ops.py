@@ -346,6 +346,56 @@ def table_loss_grad(table, ref, flow_scale=20.0, options=None, model=None, ssim_
     return grad
 
 
+def table_loss_epe(table, gt_flow, valid=None, gt_occ=None, flow_scale=20.0, options=None, count="batch", want_loss=True, want_grad=False,
+                   model=None, rescale=False):
+    """The supervised objective, -optimize epe (train.lua:296-334 with criterions/L2Criterion.lua:27-71; include/b2f.h gives every
+    word and element), of an output table of model:forward against ground truth: table as for table_loss; gt_flow n x 2 x H x W
+    float32, the true flow in pixels at the size of level 0; valid and gt_occ uint8 n x H x W or None (the conventions of flow_score:
+    gt_occ bytes 0 / 1 / 2 are the labels 0 / 0.5 / 1, anything else is unlabelled); level j reads them at (y << j, x << j).
+    options: of back2future.loss_epe_options (None: the defaults: epe 1, no occlusion term, no sizeAverage).  -> the records, uint64
+    (n, L, 8) (back2future.LOSS_EPE_*; back2future.loss_summary(objective="epe") reads them), with want_grad the gradient table, a
+    list of float32 arrays with the table's shapes (the future flow and, with occ > 0, the occlusions; every other tensor is +0.0);
+    both as a tuple when both are wanted.  count: where sizeAverage takes its pixel counts from: "batch" (the n images of the call, as
+    the reference), "image" or an L x 2 array (valid, labelled pixels per level); read by the gradient only.  model=None computes on
+    the CPU (b2f_table_loss_epe_host, no GPU; rescale: the rescale_flow of the model that made the table, train.lua:300-302), a Model
+    on its GPU (b2f_op_table_loss_epe, the model's own rescale_flow): the words and the bits are the same."""
+    from .back2future import LOSS_EPE_WORDS, _epe_opts_ptr, epe_count_args, score_ground_truth
+    if not want_loss and not want_grad:
+        raise ValueError("table_loss_epe: want_loss and want_grad are both False")
+    tab = [_lib.f32(t) for t in table]
+    if not tab or any(t.ndim != 4 or t.shape[0] != tab[0].shape[0] or min(t.shape) < 1 for t in tab):
+        raise ValueError("table_loss_epe: the table must be a non-empty list of n x C x h x w arrays of one n")
+    n, _, H, W = tab[0].shape
+    gt, va, lb = score_ground_truth(n, H, W, gt_flow, valid, gt_occ, "table_loss_epe")
+    per = 5 if (len(tab) >= 5 and tab[1].shape[1] == 2 and tab[2].shape[1] == 2) else 4
+    if len(tab) % per:
+        raise ValueError("table_loss_epe: %d tensors are no whole number of levels of %d" % (len(tab), per))
+    L = len(tab) // per
+    for i, t in enumerate(tab):
+        want = (n, 3 if i % per >= per - 2 else 2, H >> (i // per), W >> (i // per))
+        if t.shape != want:
+            raise ValueError("table_loss_epe: tensor %d of the table must have shape %r, got %r" % (i, want, t.shape))
+    ptrs = (_lib.c_float_p * len(tab))(*[_lib.fptr(t) for t in tab])
+    loss = np.empty((n, L, LOSS_EPE_WORDS), np.uint64) if want_loss else None
+    lp = loss.ctypes.data_as(C.POINTER(C.c_ulonglong)) if want_loss else None
+    grad = [np.empty(t.shape, np.float32) for t in tab] if want_grad else None
+    gp = (_lib.c_float_p * len(grad))(*[_lib.fptr(g) for g in grad]) if want_grad else None
+    u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+    mode, counts = epe_count_args(count, L, "table_loss_epe")
+    if model is None:
+        _lib.check(_lib.lib().b2f_table_loss_epe_host(ptrs, len(tab), n, H, W, int(per == 5), _lib.fptr(gt), u8p(va), u8p(lb), float(flow_scale),
+                                                      int(bool(rescale)), _epe_opts_ptr(options), mode, counts, lp, gp))
+    else:
+        if per != (5 if model.past_flow else 4) and len(tab) % (5 if model.past_flow else 4) == 0:
+            raise ValueError("table_loss_epe: a %s table of %d tensors on a %s model would be read as the model's kind; use a model of the "
+                             "table's kind or model=None" % ("Soft" if per == 5 else "Hard", len(tab), "Soft" if model.past_flow else "Hard"))
+        _lib.check(_lib.lib().b2f_op_table_loss_epe(_h(model), ptrs, len(tab), n, H, W, _lib.fptr(gt), u8p(va), u8p(lb), float(flow_scale),
+                                                    _epe_opts_ptr(options), mode, counts, lp, gp))
+    if want_loss and want_grad:
+        return loss, grad
+    return loss if want_loss else grad
+
+
 # ---- the small kernels of a forward pass, one launcher each, on the caller's own strides (tests/glue_float64.py) ----------------------
 
 def _u8_or_f32(a):

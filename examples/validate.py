@@ -17,9 +17,17 @@ does the same with the gradients of SecondOrderSmoothnessCriterion and OBGCCrite
 --objective NAME, or without one both criteria with alpha = beta = gamma = 1; its loss lines come from the 192-byte records.
 --grad-ssim does the same with the gradient of the SSIM (+ L1) term (back2future.loss_grad_ssim_options; OSSIML1Criterion.lua:165-302):
 --pme-criterion OSSIM | OSSIML1 (the default) and --ssim-range as above; its loss lines come from the 256-byte records of the same pass.
+--objective epe --gt GT_DIR prints the supervised objective instead (-optimize epe, train.lua:296-334: the masked end-point error of
+the future flow of every level against ground truth; Model.forwardLoss(objective="epe"), 64 bytes per level and centre frame come
+back).  GT_DIR holds, per centre frame NAME, what examples/evaluate.py reads: NAME.flo, and optionally NAME_valid.png and NAME_occ.png
+(cropped like the frames).  --occ-weight W > 0 adds the occlusion term that train.lua:316-332 intends (it needs every NAME_occ.png);
+--size-average divides every level by its valid (labelled) pixels, per triplet; --grad also computes its `gradOutputs`
+(Model.forwardLossGrad(objective="epe")).  It prints `err`, `flow LEVEL value` and `occ LEVEL value` per level, `epe` in pixels
+(train.lua:340-344) and `nonfinite`, the values of back2future.loss_summary(objective="epe"), then the grad lines.
 
 Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME]
        [--pme-criterion OSSIM|OSSIML1 [--ssim-range image|batch]] [--grad | --grad-ft | --grad-ssim]
+       python examples/validate.py FRAMES_DIR MODEL --objective epe --gt GT_DIR [--scale S] [--occ-weight W] [--size-average] [--grad]
 FRAMES_DIR: 8-bit frames, sorted by name; they are cropped (top left) to multiples of 64 and normalized with
 back2future.normalize.  MODEL as for examples/run_sequence.py.  --scale: pixels per unit of raw network flow (default 20).
 Prints one `name loss` line per centre frame, then `mean loss` and `nonfinite count`; with --grad, --grad-ft or --grad-ssim then one line
@@ -44,15 +52,83 @@ def load_unit(path, H, W):
     return np.ascontiguousarray(a.transpose(2, 0, 1)).astype(np.float32) / np.float32(255)
 
 
+def load_grey(path, H, W):
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("L"), np.uint8)[:H, :W]
+
+
+def main_epe(src, model, gt_dir, scale, occ_weight, size_average, grad):
+    """--objective epe: the supervised objective of train.lua:296-334 over the clip"""
+    from back2future_amd import flow_io
+    names = sorted(f for f in os.listdir(src) if f.lower().endswith(EXTS))
+    if len(names) < 3:
+        sys.exit("%s: need at least 3 frames, found %d" % (src, len(names)))
+    from PIL import Image
+    W0, H0 = Image.open(os.path.join(src, names[0])).size
+    H, W = H0 // 64 * 64, W0 // 64 * 64
+    if H < 64 or W < 64:
+        sys.exit("%s: frames of %d x %d are smaller than 64 x 64" % (src, H0, W0))
+    stems = [os.path.join(gt_dir, os.path.splitext(f)[0]) for f in names[1:-1]]
+    for s in stems:
+        if not os.path.exists(s + ".flo"):
+            sys.exit("%s.flo: no ground truth for this centre frame" % s)
+    gt = np.stack([flow_io.loadFLO(s + ".flo") for s in stems])
+    if gt.shape[2:] != (H0, W0):
+        sys.exit("the ground truth is %d x %d, the frames are %d x %d" % (gt.shape[2:] + (H0, W0)))
+    gt = np.ascontiguousarray(gt[:, :, :H, :W], np.float32)
+    valid = occ = None
+    if all(os.path.exists(s + "_valid.png") for s in stems):
+        valid = np.stack([(load_grey(s + "_valid.png", H, W) != 0).astype(np.uint8) for s in stems])
+    if all(os.path.exists(s + "_occ.png") for s in stems):
+        lut = np.full(256, 255, np.uint8)     # the labels of examples/evaluate.py: 0 occluded "bwd", 127 / 128 visible, 255 occluded "fwd"
+        lut[0], lut[127], lut[128], lut[255] = 0, 1, 1, 2
+        occ = np.stack([lut[load_grey(s + "_occ.png", H, W)] for s in stems])
+    if occ_weight > 0 and occ is None:
+        sys.exit("--occ-weight: needs NAME_occ.png for every centre frame")
+    weights = {"occ": occ_weight}
+    options = back2future.loss_epe_options(weights=weights, size_average=size_average)
+    frames = [back2future.normalize(load_unit(os.path.join(src, f), H, W)) for f in names]
+    m = back2future.Model(model)
+    records, sumsq, largest = [], None, None
+    for b0 in range(0, len(frames) - 2, BATCH):
+        b1 = min(b0 + BATCH, len(frames) - 2)
+        x = np.stack([np.concatenate(frames[i:i + 3], axis=0) for i in range(b0, b1)])
+        kw = dict(flow_scale=scale, objective="epe", gt_flow=gt[b0:b1], valid=None if valid is None else valid[b0:b1],
+                  gt_occ=None if occ is None else occ[b0:b1], options=options)
+        if grad:
+            g, rec = m.forwardLossGrad(x, count="image", **kw)
+            sq = [float((t.astype(np.float64) ** 2).sum()) for t in g]
+            mx = [float(np.abs(t).max()) for t in g]
+            sumsq = sq if sumsq is None else [a + b for a, b in zip(sumsq, sq)]
+            largest = mx if largest is None else [max(a, b) if a == a and b == b else float("nan") for a, b in zip(largest, mx)]
+        else:
+            rec = m.forwardLoss(x, **kw)
+        records.append(rec)
+    tensors = ("f", "p", "o", "iw1", "iw3") if m.past_flow else ("f", "o", "iw1", "iw3")
+    m.close()
+    s = back2future.loss_summary(np.concatenate(records), objective="epe", size_average=size_average, weights=weights, flow_scale=scale, count="image")
+    print("err %r" % s["err"])
+    for j, v in enumerate(s["flow"]):
+        print("flow %d %r" % (j, float(v)))
+    for j, v in enumerate(s["occ"]):
+        print("occ %d %r" % (j, float(v)))
+    print("epe %r" % s["epe"])
+    print("nonfinite %d" % s["nonfinite"])
+    if grad:
+        for i, (sq, mx) in enumerate(zip(sumsq, largest)):
+            print("grad %d %s %r %r" % (i // len(tensors), tensors[i % len(tensors)], float(np.sqrt(sq)), mx))
+
+
 def main():
     args = list(sys.argv[1:])
     scale, like, objective, criterion, ssim_range = 20.0, "test", None, None, "image"
+    gt_dir, occ_weight = None, 0.0
     size_average, grad_ft, grad_ssim = "--size-average" in args, "--grad-ft" in args, "--grad-ssim" in args
     grad = "--grad" in args or grad_ft or grad_ssim
     if ("--grad" in args) + grad_ft + grad_ssim > 1:
         sys.exit("--grad, --grad-ft and --grad-ssim exclude one another")
     args = [a for a in args if a not in ("--size-average", "--grad", "--grad-ft", "--grad-ssim")]
-    for flag in ("--scale", "--like", "--objective", "--pme-criterion", "--ssim-range"):
+    for flag in ("--scale", "--like", "--objective", "--pme-criterion", "--ssim-range", "--gt", "--occ-weight"):
         if flag in args:
             i = args.index(flag)
             try:
@@ -64,6 +140,10 @@ def main():
                     criterion = args[i + 1]
                 elif flag == "--ssim-range":
                     ssim_range = args[i + 1]
+                elif flag == "--gt":
+                    gt_dir = args[i + 1]
+                elif flag == "--occ-weight":
+                    occ_weight = float(args[i + 1])
                 else:
                     objective = args[i + 1]
             except (IndexError, ValueError):
@@ -71,8 +151,14 @@ def main():
             del args[i:i + 2]
     if len(args) != 2 or like not in ("test", "train"):
         sys.exit(__doc__)
+    if objective == "epe":
+        if gt_dir is None or criterion is not None or grad_ft or grad_ssim or like != "test" or not (occ_weight >= 0.0 and np.isfinite(occ_weight)):
+            sys.exit("--objective epe: needs --gt GT_DIR, takes --scale, --occ-weight W >= 0, --size-average and --grad")
+        return main_epe(args[0], args[1], gt_dir, scale, occ_weight, size_average, grad)
+    if gt_dir is not None or occ_weight != 0.0:
+        sys.exit("--gt and --occ-weight go with --objective epe")
     if objective is not None and objective not in back2future.LOSS_OBJECTIVES:
-        sys.exit("--objective: one of " + ", ".join(sorted(back2future.LOSS_OBJECTIVES)))
+        sys.exit("--objective: epe, or one of " + ", ".join(sorted(back2future.LOSS_OBJECTIVES)))
     if criterion is not None and criterion not in back2future.SSIM_ALPHA:
         sys.exit("--pme-criterion: one of " + ", ".join(sorted(back2future.SSIM_ALPHA)))
     if ssim_range not in ("image", "batch"):

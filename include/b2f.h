@@ -834,6 +834,91 @@ B2F_API int b2f_forward_loss_grad_ssim_device(b2f_ctx *ctx, const void *dev_in, 
 B2F_API int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
                                      const b2f_loss_grad_ssim_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
                                      int range_mode, const float *ranges);
+/* ---- the supervised objective: -optimize epe (opts.lua:56; b2f_version() >= 1012) ----
+ * The supervised branch of train.lua:295-335 at the output table: the masked end-point error of the future flow of every level against
+ * ground truth (criterion = nn.L2Criterion, model.lua:145-146,249-251; criterions/L2Criterion.lua:27-71) as integer records per image
+ * and level, and its `gradOutputs`.  Inputs beside the table, with the conventions of b2f_flow_score: gt_flow float n x 2 x H x W, the
+ * true flow in pixels at the size of level 0; valid uint8 n x H x W or NULL (all valid); gt_occ uint8 n x H x W or NULL, its bytes
+ * 0 / 1 / 2 the reference's labels 0 / 0.5 / 1 and anything else unlabelled; rescale = the context's rescale_flow.  Level j reads
+ * the full-resolution planes at S = (y << j, x << j): train.lua:298-299 sub-samples with SpatialAveragePooling(1,1,2,2), every second
+ * pixel and no averaging.  Per-pixel arithmetic is fp64 without fused multiply-adds, + - * / and sqrt only:
+ *   flow (train.lua:312-314):  g_c = ((double)gt_flow[c][S] / flow_scale) / (rescale ? 2^j : 1)   (train.lua:300-302)
+ *     d_c = (double)f_c - g_c, e = sqrt(d_0 * d_0 + d_1 * d_1)                                     (L2Criterion.lua:36-37)
+ *     valid[S] == 0: nothing is added whatever the values, the gradient is +0.0 (b2f_flow_score's rule; the Lua has NaN * 0 here)
+ *     valid, e not finite: FLOW_NONFINITE += 1; valid and finite: VALID += 1, EPE_Q20 += (uint64)(min(e, 65536) * 2^20 + 0.5)
+ *     gradient of f_c = (k_j * d_c) / (e + 1e-12), also where e is not finite                      (L2Criterion.lua:58-64)
+ *   occlusions (train.lua:316-332, opt-in: evaluated only when occ > 0, else words 4 .. 6 are 0 and the planes +0.0).  The Lua as written
+ *     cannot run (it slices the labels to one channel, then indexes channel 2, and hands L2Criterion a tensor for {target, mask}); its
+ *     intent, consistent with train.lua:387: t_0 = [g == 0] + 0.5 [g == 0.5], t_1 = [g == 1] + 0.5 [g == 0.5], on labelled pixels
+ *     whatever `valid` says: q = sqrt((o_0 - t_0)^2 + (o_1 - t_1)^2); LABELLED, OCC_Q20, OCC_NONFINITE as above; gradient of
+ *     o_c = (k'_j * (o_c - t_c)) / (q + 1e-12); unlabelled pixels add nothing and get +0.0
+ *   k_j = epe * lw_j, k'_j = occ * lw_j (train.lua:328,331 give the occlusion term no option weight); with size_average lw_j = 1
+ *     (train.lua:60-64) and k_j = epe / N_j, k'_j = occ / N'_j, N_j / N'_j the valid / labelled source pixels of level j (mask:sum(),
+ *     L2Criterion.lua:34,56) by count_mode: B2F_EPE_COUNT_BATCH over the n images of the call (the reference's), B2F_EPE_COUNT_IMAGE each
+ *     image's own, B2F_EPE_COUNT_GIVEN counts[2 j] / counts[2 j + 1] (a host array of L x 2 doubles, NULL in the other modes).  A
+ *     factor of exactly 0 -- a weight of 0, or no counted pixel, where the Lua divides by zero -- gives +0.0, not evaluated.
+ *   Every gradient element is formed in fp64 and rounded to fp32 once, on store.  The gradient table has the shapes of the table; the
+ *   future flow and, with occ > 0, the occlusions are as above, every other tensor is +0.0.
+ * loss: n x L records of B2F_LOSS_EPE_WORDS words, image-major; integer sums, so a record does not depend on the grid or on where a
+ * request is cut.  The reported epe of train.lua:340-344 is flow_scale * sum EPE_Q20[level 0] / 2^20 / sum VALID[level 0]
+ * (back2future.loss_summary(objective="epe")).  test.lua:150-180 (three arguments to criterion:forward, a 2 x 2 mean of the flow) is
+ * not followed.  Checks: those of b2f_table_loss*; in addition a null gt_flow, negative or non-finite weights or counts, occ > 0
+ * without gt_occ, a bad count_mode, loss and grad both NULL, and an output that aliases an input are refused with nothing written. */
+#define B2F_LOSS_EPE_PIXELS 0          /* h * w of the level */
+#define B2F_LOSS_EPE_VALID 1           /* valid pixels with a finite error */
+#define B2F_LOSS_EPE_Q20 2             /* their end-point error in units of flow_scale pixels, 2^-20 */
+#define B2F_LOSS_EPE_FLOW_NONFINITE 3  /* valid pixels with a non-finite error */
+#define B2F_LOSS_EPE_LABELLED 4        /* labelled pixels with a finite occlusion error (0 unless occ > 0) */
+#define B2F_LOSS_EPE_OCC_Q20 5         /* their occlusion error, 2^-20 */
+#define B2F_LOSS_EPE_OCC_NONFINITE 6   /* labelled pixels with a non-finite occlusion error */
+#define B2F_LOSS_EPE_WORDS 8           /* word 7 is reserved, always 0 */
+#define B2F_EPE_COUNT_BATCH 0          /* count_mode: N_j, N'_j over the n images of the call */
+#define B2F_EPE_COUNT_IMAGE 1          /* each image's own */
+#define B2F_EPE_COUNT_GIVEN 2          /* counts[2 j], counts[2 j + 1] */
+typedef struct b2f_loss_epe_opts {
+    double epe;                /* -epe, opts.lua: the weight of the flow term */
+    double occ;                /* the weight of the occlusion term; 0 (the default) leaves it out */
+    int size_average;          /* -sizeAverage */
+    double level_weights[7];   /* train.lua:56-58; not read with size_average */
+} b2f_loss_epe_opts;
+/* epe = 1, occ = 0, size_average = 0, the level weights of train.lua:56-58 */
+B2F_API int b2f_loss_epe_defaults(b2f_loss_epe_opts *opts);
+/* host only, no GPU: train.lua:296-334 per pixel on the CPU.  table as for b2f_table_loss_host; loss (n x L x 8 words) and grad (the
+ * table's n_outs tensors) may each be NULL, not both; opts NULL: the defaults.                                                      */
+B2F_API int b2f_table_loss_epe_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *gt_flow,
+                            const unsigned char *valid, const unsigned char *gt_occ, double flow_scale, int rescale,
+                            const b2f_loss_epe_opts *opts, int count_mode, const double *counts, unsigned long long *loss,
+                            float *const *grad);
+/* train.lua:296-334 on device pointers (L2Criterion.lua:27-71 per pixel): dev_table and dev_grad are host arrays of n_outs device
+ * pointers, 16-byte aligned like dev_gt_flow and dev_loss; dev_valid and dev_gt_occ need no alignment.  Asynchronous on `stream`;
+ * dev_loss is zeroed on the stream first.  With size_average and a gradient table, a counting pass over dev_valid / dev_gt_occ runs
+ * first, into a workspace of the context: calls on different streams must be ordered by the caller.  At most 65535 images per call. */
+B2F_API int b2f_table_loss_epe_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W,
+                              const float *dev_gt_flow, const unsigned char *dev_valid, const unsigned char *dev_gt_occ,
+                              double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
+                              unsigned long long *dev_loss, float *const *dev_grad, void *stream);
+/* train.lua:296-334 on host pointers through the GPU, like b2f_op_table_loss */
+B2F_API int b2f_op_table_loss_epe(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *gt_flow,
+                          const unsigned char *valid, const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts,
+                          int count_mode, const double *counts, unsigned long long *loss, float *const *grad);
+/* model:forward followed by train.lua:296-334 without the download of the table: x as for b2f_forward_loss; gt_flow / valid / gt_occ of
+ * the n triplets in host memory, uploaded with the frames of each sub-batch (host_subbatch_pixels); loss (n x L x 8 words), grad (the
+ * table's n_outs tensors) and outs (the table itself, n_outs tensors) may each be NULL, loss and grad not both.  B2F_EPE_COUNT_BATCH
+ * counts over the caller's whole n before the first sub-batch, so a cut changes nothing.  two_frame is refused.                   */
+B2F_API int b2f_forward_loss_epe(b2f_ctx *ctx, const float *x, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
+                         const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode,
+                         const double *counts, unsigned long long *loss, float *const *grad, int n_outs, float *const *outs);
+/* the same on device pointers (dev_in as for b2f_forward_loss_device, B2F_IN_NORMALIZED only); asynchronous on `stream`; with a
+ * gradient table and size_average, B2F_EPE_COUNT_BATCH is refused when the request would be cut into more than one sub-batch      */
+B2F_API int b2f_forward_loss_epe_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, const float *dev_gt_flow,
+                                const unsigned char *dev_valid, const unsigned char *dev_gt_occ, double flow_scale,
+                                const b2f_loss_epe_opts *opts, int count_mode, const double *counts, unsigned long long *dev_loss,
+                                float *const *dev_grad, int n_outs, void *stream);
+/* ... over several GPUs: the n triplets and their ground truth are split with b2f_shard_range; B2F_EPE_COUNT_BATCH is refused (a
+ * shard's counts would depend on the split); one context's words and bits                                                        */
+B2F_API int b2f_multi_forward_loss_epe(b2f_multi *m, const float *x, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
+                               const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode,
+                               const double *counts, unsigned long long *loss, float *const *grad, int n_outs);
 /* ---- streams: frames that arrive one at a time (a camera, a decoder, a ROS node) ----
  * back2future.lua:47-95 takes three whole frames per call, so a live caller of the reference hands every
  * frame to computeFlow three times (as im3, then im2, then im1) and pays three uploads and three feature

@@ -239,6 +239,31 @@ int b2f_forward_loss_grad_ssim(b2f_ctx *ctx, const float *x, int n, int H, int W
 int b2f_forward_loss_grad_ssim_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                                       const b2f_loss_grad_ssim_opts *opts, unsigned long long *dev_loss, float *const *dev_grad,
                                       int n_outs, void *stream, int range_mode, const float *ranges);
+typedef struct b2f_loss_epe_opts {
+    double epe;
+    double occ;
+    int size_average;
+    double level_weights[7];
+} b2f_loss_epe_opts;
+int b2f_loss_epe_defaults(b2f_loss_epe_opts *opts);
+int b2f_table_loss_epe_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *gt_flow,
+                            const unsigned char *valid, const unsigned char *gt_occ, double flow_scale, int rescale,
+                            const b2f_loss_epe_opts *opts, int count_mode, const double *counts, unsigned long long *loss,
+                            float *const *grad);
+int b2f_table_loss_epe_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W,
+                              const float *dev_gt_flow, const unsigned char *dev_valid, const unsigned char *dev_gt_occ,
+                              double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
+                              unsigned long long *dev_loss, float *const *dev_grad, void *stream);
+int b2f_op_table_loss_epe(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *gt_flow,
+                          const unsigned char *valid, const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts,
+                          int count_mode, const double *counts, unsigned long long *loss, float *const *grad);
+int b2f_forward_loss_epe(b2f_ctx *ctx, const float *x, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
+                         const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode,
+                         const double *counts, unsigned long long *loss, float *const *grad, int n_outs, float *const *outs);
+int b2f_forward_loss_epe_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, const float *dev_gt_flow,
+                                const unsigned char *dev_valid, const unsigned char *dev_gt_occ, double flow_scale,
+                                const b2f_loss_epe_opts *opts, int count_mode, const double *counts, unsigned long long *dev_loss,
+                                float *const *dev_grad, int n_outs, void *stream);
 typedef struct b2f_multi b2f_multi;
 int  b2f_init_multi(const char *name_or_path, int n_gpus, const int *devices, b2f_multi **out);
 void b2f_destroy_multi(b2f_multi *m);
@@ -292,6 +317,9 @@ int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, i
 int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
                                      const b2f_loss_grad_ssim_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
                                      int range_mode, const float *ranges);
+int b2f_multi_forward_loss_epe(b2f_multi *m, const float *x, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
+                               const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode,
+                               const double *counts, unsigned long long *loss, float *const *grad, int n_outs);
 ]]
 
 local lib = ffi.load(os.getenv('B2F_LIB') or 'libb2f.so')
