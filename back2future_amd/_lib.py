@@ -41,6 +41,15 @@ class LossGradSsimOpts(C.Structure):
 c_grad_ssim_opts_p = C.POINTER(LossGradSsimOpts)
 
 
+class LossGradPlainOpts(C.Structure):
+    """b2f_loss_grad_plain_opts of include/b2f.h: the fields of LossGradOpts, -smooth_second_order, the criterion (0 BCC, 1 SSIM), the
+    penalty (0 L1, 1 quadratic; BCC only) and the alpha of MSSIML1Criterion (1: SSIM, 0.85: SSIML1)"""
+    _fields_ = LossGradOpts._fields_ + [("smooth_second_order", C.c_int), ("criterion", C.c_int), ("penalty", C.c_int), ("ssim_alpha", C.c_double)]
+
+
+c_grad_plain_opts_p = C.POINTER(LossGradPlainOpts)
+
+
 class LossEpeOpts(C.Structure):
     """b2f_loss_epe_opts of include/b2f.h: -epe, the weight of the opt-in occlusion term (train.lua:316-332), -sizeAverage and the
     level weights of train.lua:56-58"""
@@ -226,15 +235,27 @@ SIGNATURES = {
     "b2f_multi_forward_loss_ft": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong)]),
     "b2f_table_loss_ssim_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
                                            C.POINTER(C.c_ulonglong), C.c_int, c_float_p]),
+    "b2f_table_loss_plain_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                           C.POINTER(C.c_ulonglong), C.c_int, c_float_p]),
     "b2f_table_loss_ssim_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                             C.c_void_p, C.c_void_p, C.c_int, c_float_p]),
+    "b2f_table_loss_plain_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                              C.c_void_p, C.c_void_p, C.c_int, c_float_p]),
     "b2f_op_table_loss_ssim": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
                                          C.POINTER(C.c_ulonglong), C.c_int, c_float_p]),
+    "b2f_op_table_loss_plain": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                         C.POINTER(C.c_ulonglong), C.c_int, c_float_p]),
     "b2f_forward_loss_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong),
+                                        C.POINTER(c_float_p), C.c_int, C.c_int, c_float_p]),
+    "b2f_forward_loss_plain": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong),
                                         C.POINTER(c_float_p), C.c_int, C.c_int, c_float_p]),
     "b2f_forward_loss_ssim_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                                C.c_int, c_float_p]),
+    "b2f_forward_loss_plain_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                               C.c_int, c_float_p]),
     "b2f_multi_forward_loss_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong),
+                                              C.c_int, c_float_p]),
+    "b2f_multi_forward_loss_plain": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ulonglong),
                                               C.c_int, c_float_p]),
     "b2f_loss_ssim_weights": (C.c_int, [C.POINTER(C.c_double)]),
     "b2f_loss_grad_defaults": (C.c_int, [c_grad_opts_p]),
@@ -264,17 +285,30 @@ SIGNATURES = {
     "b2f_multi_forward_loss_grad_ft": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ft_opts_p,
                                                  C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int]),
     "b2f_loss_grad_ssim_defaults": (C.c_int, [c_grad_ssim_opts_p]),
+    "b2f_loss_grad_plain_defaults": (C.c_int, [c_grad_plain_opts_p]),
     "b2f_table_loss_grad_ssim_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
                                                 c_grad_ssim_opts_p, C.POINTER(c_float_p), C.c_int, c_float_p]),
+    "b2f_table_loss_grad_plain_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                                c_grad_plain_opts_p, C.POINTER(c_float_p), C.c_int, c_float_p]),
     "b2f_table_loss_grad_ssim_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                                   c_grad_ssim_opts_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, c_float_p]),
+    "b2f_table_loss_grad_plain_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                                  c_grad_plain_opts_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, c_float_p]),
     "b2f_op_table_loss_grad_ssim": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
                                               c_grad_ssim_opts_p, C.POINTER(c_float_p), C.c_int, c_float_p]),
+    "b2f_op_table_loss_grad_plain": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_double,
+                                              c_grad_plain_opts_p, C.POINTER(c_float_p), C.c_int, c_float_p]),
     "b2f_forward_loss_grad_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ssim_opts_p,
+                                             C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int, C.POINTER(c_float_p), C.c_int, c_float_p]),
+    "b2f_forward_loss_grad_plain": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_plain_opts_p,
                                              C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int, C.POINTER(c_float_p), C.c_int, c_float_p]),
     "b2f_forward_loss_grad_ssim_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ssim_opts_p,
                                                     C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, c_float_p]),
+    "b2f_forward_loss_grad_plain_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_plain_opts_p,
+                                                    C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, c_float_p]),
     "b2f_multi_forward_loss_grad_ssim": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_ssim_opts_p,
+                                                   C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int, C.c_int, c_float_p]),
+    "b2f_multi_forward_loss_grad_plain": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_double, c_grad_plain_opts_p,
                                                    C.POINTER(C.c_ulonglong), C.POINTER(c_float_p), C.c_int, C.c_int, c_float_p]),
     "b2f_loss_epe_defaults": (C.c_int, [c_epe_opts_p]),
     "b2f_table_loss_epe_host": (C.c_int, [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.POINTER(C.c_ubyte),

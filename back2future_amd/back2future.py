@@ -51,6 +51,15 @@ LOSS_FT_SMOOTH2_NONFINITE, LOSS_FT_GRAD_NONFINITE, LOSS_FT_WORDS = 22, 23, 24
 LOSS_SSIM_Q30, LOSS_SSIM_L1N_Q30, LOSS_SSIM_NONFINITE, LOSS_SSIM_RANGE_USED, LOSS_SSIM_RANGE_OWN, LOSS_SSIM_WORDS = 16, 18, 20, 22, 24, 32
 SSIM_RANGE_BATCH, SSIM_RANGE_IMAGE, SSIM_RANGE_GIVEN = 0, 1, 2   # range_mode of the *_ssim entries (include/b2f.h, B2F_SSIM_RANGE_*)
 SSIM_ALPHA = {"OSSIM": 1.0, "OSSIML1": 0.85}                      # model.lua:172-179
+# further words of a record of the photometric terms without occlusion masking (include/b2f.h, B2F_LOSS_PLAIN_*; objective="plain";
+# criterions/MBCCriterion.lua, criterions/MSSIML1Criterion.lua), each base + direction or + (minimum, maximum): Q30 sums over PHOTO_INSIDE
+# of the L1 and of the quadratic penalty of the raw difference, of 1 - SSIM and of the L1 penalty of the range-normalised difference,
+# counted pixel-directions with a NaN term or an unusable range, float bits of the range used and of the image's own (which covers the
+# occlusions and, on Soft tables, the past flow: MSSIML1Criterion.lua:63-68)
+LOSS_PLAIN_L1_Q30, LOSS_PLAIN_SQ_Q30, LOSS_PLAIN_SSIM_Q30, LOSS_PLAIN_L1N_Q30, LOSS_PLAIN_SSIM_NONFINITE = 16, 18, 20, 22, 24
+LOSS_PLAIN_RANGE_USED, LOSS_PLAIN_RANGE_OWN, LOSS_PLAIN_WORDS = 26, 28, 40
+PLAIN_ALPHA = {"SSIM": 1.0, "SSIML1": 0.85}                       # model.lua:149-159
+PLAIN_BCC, PLAIN_SSIM, PLAIN_L1, PLAIN_QUADRATIC = 0, 1, 0, 1     # criterion / penalty of b2f_loss_grad_plain_opts (B2F_PLAIN_*)
 # words of a record of the supervised objective (include/b2f.h, B2F_LOSS_EPE_*; objective="epe"; train.lua:296-334 with
 # criterions/L2Criterion.lua): the level's pixels, the valid pixels with a finite end-point error, its Q20 sum in units of flow_scale
 # pixels, the valid pixels with a non-finite one, and the same three of the occlusion term over the labelled pixels (0 unless occ > 0)
@@ -72,31 +81,34 @@ LOSS_OBJECTIVES = {
 
 def loss_words(objective):
     """words per record of objective "pme" (16; test.lua:266-297), "finetune" (24; with the terms of README.md:89-102), "ssim" (32;
-    with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua) or "epe" (8; the supervised objective of train.lua:296-334)"""
+    with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua), "plain" (40; with the photometric sums without occlusion masking of
+    criterions/MBCCriterion.lua and MSSIML1Criterion.lua) or "epe" (8; the supervised objective of train.lua:296-334)"""
     if objective == "pme":
         return LOSS_WORDS
     if objective == "finetune":
         return LOSS_FT_WORDS
     if objective == "ssim":
         return LOSS_SSIM_WORDS
+    if objective == "plain":
+        return LOSS_PLAIN_WORDS
     if objective == "epe":
         return LOSS_EPE_WORDS
-    raise ValueError("objective must be 'pme', 'finetune', 'ssim' or 'epe', got %r" % (objective,))
+    raise ValueError("objective must be 'pme', 'finetune', 'ssim', 'plain' or 'epe', got %r" % (objective,))
 
 
 def loss_entry(pattern, objective):
-    """the library's entry for an unsupervised objective: `pattern` with %s replaced by "", "_ft" or "_ssim" """
+    """the library's entry for an unsupervised objective: `pattern` with %s replaced by "", "_ft", "_ssim" or "_plain" """
     if objective == "epe":
         raise ValueError("objective 'epe' needs ground truth: use ops.table_loss_epe, Model.tableLossDevice(objective='epe', gt_flow=...) or "
                          "Model.tableLossGradDevice(objective='epe', gt_flow=...)")
-    return getattr(_lib.lib(), pattern % {LOSS_WORDS: "", LOSS_FT_WORDS: "_ft", LOSS_SSIM_WORDS: "_ssim"}[loss_words(objective)])
+    return getattr(_lib.lib(), pattern % {LOSS_WORDS: "", LOSS_FT_WORDS: "_ft", LOSS_SSIM_WORDS: "_ssim", LOSS_PLAIN_WORDS: "_plain"}[loss_words(objective)])
 
 
 def ssim_range_args(objective, ssim_range, L, who, batch_ok=True):
-    """The trailing (range_mode, ranges) arguments of a b2f_*_ssim entry as a tuple, () for the other objectives.  ssim_range: "batch"
+    """The trailing (range_mode, ranges) arguments of a b2f_*_ssim or b2f_*_plain entry as a tuple, () for the other objectives.  ssim_range: "batch"
     (the minimum and maximum over the call's images, OSSIML1Criterion.lua:62-67), "image" (each image's own) or L x 2 numbers
     (mn, mx per level)."""
-    if loss_words(objective) != LOSS_SSIM_WORDS:
+    if loss_words(objective) not in (LOSS_SSIM_WORDS, LOSS_PLAIN_WORDS):
         return ()
     if isinstance(ssim_range, str):
         modes = {"batch": SSIM_RANGE_BATCH, "image": SSIM_RANGE_IMAGE}
@@ -745,7 +757,7 @@ def photo_summary(photo):
 
 
 def loss_summary(records, like="test", size_average=False, weights=None, smooth_second_order=False, pme_criterion="OBCC", pme_beta=1.0,
-                 pme_gamma=1.0, objective=None, ssim_alpha=None, flow_scale=20.0, count="batch"):
+                 pme_gamma=1.0, objective=None, ssim_alpha=None, flow_scale=20.0, count="batch", pme_penalty="L1", no_occ=False):
     """objective="epe": the supervised objective from the 8-word records of ops.table_loss_epe; see _loss_summary_epe, which takes
     size_average, weights ("epe", "occ", "level_weights"), flow_scale and count.  Otherwise:
     The unsupervised validation loss of test.lua:266-297 from loss records (uint64 n x L x 16 or L x 16; ops.table_loss,
@@ -765,6 +777,12 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
         sum over d of ((alpha * SSIM_d + (1 - alpha) * L1N_d) / 2^30 + OUTSIDE_d) / (3 * 2)
     (OSSIML1Criterion.lua:119,149-157) with alpha = 1 for OSSIM and 0.85 for OSSIML1 (model.lua:172-179; ssim_alpha replaces it);
     "OBCC" reads their first 16 words as before.  Records of another width raise ValueError for these two criteria.
+    With 40-word records (objective="plain"): pme_criterion="BCC" | "SSIM" | "SSIML1" makes the photometric term that of
+    criterions/MBCCriterion.lua resp. MSSIML1Criterion.lua, which do not mask occlusions and have no penalty_out:
+        BCC:            sum over d of PLAIN_L1_d / 2^30 / (3 * 2)     (pme_penalty="Quadratic": PLAIN_SQ_d; model.lua:189-190)
+        SSIM | SSIML1:  sum over d of (alpha * PLAIN_SSIM_d + (1 - alpha) * PLAIN_L1N_d) / 2^30 / (3 * 2), alpha = 1 | 0.85
+    no_occ=True (opts.lua:85, train.lua:456, test.lua:289) drops the occlusions' smoothness and prior from "level", "loss" and "mean",
+    whatever the records' width; the two terms are still returned.  "OBCC" reads the first 16 words of 40-word records as before.
     objective=NAME applies LOSS_OBJECTIVES[NAME], the options the named model was trained with, in place of these three arguments and
     under `weights`.  With 16-word records any of them set away from its default raises ValueError.
     Returns a dict: every term per triplet and level (n x L float64 arrays "smooth_flow", "smooth_past", "const_vel", "pme",
@@ -777,9 +795,9 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
             raise ValueError("loss_summary: objective='epe' takes size_average, weights, flow_scale and count only (train.lua is its definition; "
                              "there is no like='test' of it)")
         return _loss_summary_epe(s, size_average, weights, flow_scale, count)
-    if s.dtype != np.uint64 or s.shape[-1:] not in ((LOSS_WORDS,), (LOSS_FT_WORDS,), (LOSS_SSIM_WORDS,)) or s.ndim not in (2, 3):
-        raise ValueError("loss_summary: expected uint64 records of shape (n, L, w) or (L, w) with w = %d, %d or %d, got %s %r"
-                         % (LOSS_WORDS, LOSS_FT_WORDS, LOSS_SSIM_WORDS, s.dtype, s.shape))
+    if s.dtype != np.uint64 or s.shape[-1:] not in ((LOSS_WORDS,), (LOSS_FT_WORDS,), (LOSS_SSIM_WORDS,), (LOSS_PLAIN_WORDS,)) or s.ndim not in (2, 3):
+        raise ValueError("loss_summary: expected uint64 records of shape (n, L, w) or (L, w) with w = %d, %d, %d or %d, got %s %r"
+                         % (LOSS_WORDS, LOSS_FT_WORDS, LOSS_SSIM_WORDS, LOSS_PLAIN_WORDS, s.dtype, s.shape))
     if like not in ("test", "train"):
         raise ValueError("loss_summary: like must be 'test' or 'train'")
     wt = dict(LOSS_WEIGHTS)
@@ -791,15 +809,24 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
         o = LOSS_OBJECTIVES[objective]
         smooth_second_order, pme_criterion, pme_beta, pme_gamma = o["smooth_second_order"], o["pme_criterion"], o["pme_beta"], o["pme_gamma"]
         wt.update(o["weights"])
-    if pme_criterion not in ("OBCC", "OBGCC", "OSSIM", "OSSIML1"):
-        raise ValueError("loss_summary: pme_criterion must be 'OBCC', 'OBGCC', 'OSSIM' or 'OSSIML1'")
+    if pme_criterion not in ("OBCC", "OBGCC", "OSSIM", "OSSIML1", "BCC", "SSIM", "SSIML1"):
+        raise ValueError("loss_summary: pme_criterion must be 'OBCC', 'OBGCC', 'OSSIM', 'OSSIML1', 'BCC', 'SSIM' or 'SSIML1'")
+    plain = pme_criterion in ("BCC", "SSIM", "SSIML1")
+    if plain and s.shape[-1] != LOSS_PLAIN_WORDS:
+        raise ValueError("loss_summary: pme_criterion=%r needs the %d-word records of objective='plain', got records of %d words"
+                         % (pme_criterion, LOSS_PLAIN_WORDS, s.shape[-1]))
+    if pme_penalty not in ("L1", "Quadratic"):
+        raise ValueError("loss_summary: pme_penalty must be 'L1' or 'Quadratic' (the Lorentzian penalty is not provided)")
+    if pme_penalty == "Quadratic" and pme_criterion != "BCC":
+        raise ValueError("loss_summary: pme_penalty='Quadratic' goes with pme_criterion='BCC' only (model.lua:189-190 replaces the penalty of every "
+                         "other criterion by the L1 one or leaves it without effect)")
     gradients = pme_criterion == "OBGCC"
     ssim = pme_criterion in SSIM_ALPHA
     if ssim and s.shape[-1] != LOSS_SSIM_WORDS:
         raise ValueError("loss_summary: pme_criterion=%r needs the %d-word records of objective='ssim', got records of %d words"
                          % (pme_criterion, LOSS_SSIM_WORDS, s.shape[-1]))
-    if ssim_alpha is not None and not ssim:
-        raise ValueError("loss_summary: ssim_alpha goes with pme_criterion 'OSSIM' or 'OSSIML1'")
+    if ssim_alpha is not None and not ssim and pme_criterion not in PLAIN_ALPHA:
+        raise ValueError("loss_summary: ssim_alpha goes with pme_criterion 'OSSIM', 'OSSIML1', 'SSIM' or 'SSIML1'")
     if ssim_alpha is not None and not (0.0 <= float(ssim_alpha) <= 1.0):
         raise ValueError("loss_summary: ssim_alpha must lie in [0, 1], got %r" % (ssim_alpha,))
     ft = s.shape[-1] == LOSS_FT_WORDS
@@ -824,6 +851,15 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
         alpha = SSIM_ALPHA[pme_criterion] if ssim_alpha is None else float(ssim_alpha)
         photo = alpha * (f[:, :, LOSS_SSIM_Q30] + f[:, :, LOSS_SSIM_Q30 + 1]) + (1.0 - alpha) * (f[:, :, LOSS_SSIM_L1N_Q30] + f[:, :, LOSS_SSIM_L1N_Q30 + 1])
     pme = (photo / one + f[:, :, LOSS_PHOTO_OUTSIDE] + f[:, :, LOSS_PHOTO_OUTSIDE + 1]) / (3.0 * 2.0)
+    if plain:   # no occlusion weight and no penalty_out (MBCCriterion.lua:89-99, MSSIML1Criterion.lua:140-150)
+        if pme_criterion == "BCC":
+            w_b = LOSS_PLAIN_L1_Q30 if pme_penalty == "L1" else LOSS_PLAIN_SQ_Q30
+            photo = f[:, :, w_b] + f[:, :, w_b + 1]
+        else:
+            alpha = PLAIN_ALPHA[pme_criterion] if ssim_alpha is None else float(ssim_alpha)
+            photo = alpha * (f[:, :, LOSS_PLAIN_SSIM_Q30] + f[:, :, LOSS_PLAIN_SSIM_Q30 + 1]) \
+                    + (1.0 - alpha) * (f[:, :, LOSS_PLAIN_L1N_Q30] + f[:, :, LOSS_PLAIN_L1N_Q30 + 1])
+        pme = photo / one / (3.0 * 2.0)
     if size_average:
         fs, fp, cv, so = fs / (2.0 * px), fp / (2.0 * px), cv / (2.0 * px), so / (2.0 * px)
         pme, pr = pme / px, pr / px
@@ -831,12 +867,16 @@ def loss_summary(records, like="test", size_average=False, weights=None, smooth_
     n_flow = float(wt.pop("n_flow", 2.0 if soft else 1.0))   # (weights={"n_flow": ...} overrides what the records suggest)
     S = n_flow * fs if like == "test" else fs + fp
     lw = np.asarray(LOSS_LEVEL_WEIGHTS[:L], np.float64)[None, :]
-    level = lw * (wt["smooth_flow"] * S + wt["const_vel"] * cv + wt["pme"] * pme + wt["smooth_occ"] * so + wt["prior_occ"] * pr)
+    level = wt["smooth_flow"] * S + wt["const_vel"] * cv + wt["pme"] * pme
+    if not no_occ:   # train.lua:456, test.lua:289
+        level = level + wt["smooth_occ"] * so + wt["prior_occ"] * pr
+    level = lw * level
     loss = level.sum(axis=1)
     counted = [LOSS_NONFINITE, LOSS_PHOTO_NONFINITE, LOSS_PHOTO_NONFINITE + 1]
     counted += [LOSS_FT_SMOOTH2_NONFINITE] if smooth_second_order else []
     counted += [LOSS_FT_GRAD_NONFINITE] if gradients else []
     counted += [LOSS_SSIM_NONFINITE, LOSS_SSIM_NONFINITE + 1] if ssim else []
+    counted += [LOSS_PLAIN_SSIM_NONFINITE, LOSS_PLAIN_SSIM_NONFINITE + 1] if pme_criterion in PLAIN_ALPHA else []
     nonf = int(sum(int(v) for v in s[:, :, counted].ravel()))
     return {"smooth_flow": fs, "smooth_past": fp, "const_vel": cv, "pme": pme, "smooth_occ": so, "prior_occ": pr, "level": level,
             "loss": loss, "mean": float(loss.mean()), "nonfinite": nonf}
@@ -1047,12 +1087,46 @@ def loss_grad_ssim_options(weights=None, size_average=False, smooth_second_order
     return o
 
 
+def loss_grad_plain_options(weights=None, size_average=False, smooth_second_order=False, pme_criterion="BCC", pme_penalty="L1", ssim_alpha=None,
+                            no_occ=False):
+    """The options of the gradient table with the photometric terms that do not mask occlusions (a _lib.LossGradPlainOpts,
+    b2f_loss_grad_plain_opts of include/b2f.h; criterions/MBCCriterion.lua:104-186, MSSIML1Criterion.lua:155-261), from
+    b2f_loss_grad_plain_defaults: those of loss_grad_options, -smooth_second_order off, BCC with the L1 penalty.  pme_criterion: "BCC",
+    "SSIM" or "SSIML1" (PLAIN_ALPHA; an explicit ssim_alpha, finite and in [0, 1], overrides its value); pme_penalty: "L1" or, with
+    "BCC" only, "Quadratic" (model.lua:189-190).  no_occ=True (opts.lua:85, train.lua:456) sets the weights of the occlusions'
+    smoothness and prior to 0, after `weights`: the occlusion planes of the gradient are then +0.0.  Every entry point that takes the
+    options of loss_grad_options takes these too, with a keyword ssim_range as for the objective "plain"."""
+    o = _lib.LossGradPlainOpts()
+    _lib.check(_lib.lib().b2f_loss_grad_plain_defaults(C.byref(o)))
+    _apply_grad_weights("loss_grad_plain_options", o, dict(weights or {}))
+    if pme_criterion not in ("BCC", "SSIM", "SSIML1"):
+        raise ValueError("loss_grad_plain_options: pme_criterion must be 'BCC', 'SSIM' or 'SSIML1'")
+    if pme_penalty not in ("L1", "Quadratic"):
+        raise ValueError("loss_grad_plain_options: pme_penalty must be 'L1' or 'Quadratic' (the Lorentzian penalty is not provided)")
+    if pme_penalty == "Quadratic" and pme_criterion != "BCC":
+        raise ValueError("loss_grad_plain_options: pme_penalty='Quadratic' goes with pme_criterion='BCC' only")
+    if ssim_alpha is not None and pme_criterion == "BCC":
+        raise ValueError("loss_grad_plain_options: ssim_alpha goes with pme_criterion 'SSIM' or 'SSIML1'")
+    o.criterion = PLAIN_BCC if pme_criterion == "BCC" else PLAIN_SSIM
+    o.penalty = PLAIN_QUADRATIC if pme_penalty == "Quadratic" else PLAIN_L1
+    o.ssim_alpha = PLAIN_ALPHA.get(pme_criterion, 0.85)
+    if ssim_alpha is not None:
+        if not (0.0 <= float(ssim_alpha) <= 1.0):
+            raise ValueError("loss_grad_plain_options: ssim_alpha must be in [0, 1], got %r" % (ssim_alpha,))
+        o.ssim_alpha = float(ssim_alpha)
+    o.smooth_second_order = 1 if smooth_second_order else 0
+    o.size_average = 1 if size_average else 0
+    if no_occ:
+        o.smooth_occ = o.prior_occ = 0.0
+    return o
+
+
 def _grad_opts_ptr(options):
     if options is None:
         return None
-    if not isinstance(options, (_lib.LossGradOpts, _lib.LossGradFtOpts, _lib.LossGradSsimOpts)):
-        raise ValueError("expected the result of back2future.loss_grad_options or loss_grad_ft_options, or of loss_grad_ssim_options (or None "
-                         "for the defaults)")
+    if not isinstance(options, (_lib.LossGradOpts, _lib.LossGradFtOpts, _lib.LossGradSsimOpts, _lib.LossGradPlainOpts)):
+        raise ValueError("expected the result of back2future.loss_grad_options or loss_grad_ft_options, of loss_grad_ssim_options or of "
+                         "loss_grad_plain_options (or None for the defaults)")
     return C.byref(options)
 
 
@@ -1063,18 +1137,22 @@ def _grad_entry(name, options):
         name = name.replace("_grad", "_grad_ft", 1)
     elif isinstance(options, _lib.LossGradSsimOpts):
         name = name.replace("_grad", "_grad_ssim", 1)
+    elif isinstance(options, _lib.LossGradPlainOpts):
+        name = name.replace("_grad", "_grad_plain", 1)
     return getattr(_lib.lib(), name)
 
 
 def _grad_words(options):
     """words per record beside a gradient table: the fine-tuning options give the 24-word records of objective "finetune", the SSIM +
-    L1 options the 32-word records of objective "ssim"""
+    L1 options the 32-word records of objective "ssim", the options of loss_grad_plain_options the 40-word records of objective "plain"""
+    if isinstance(options, _lib.LossGradPlainOpts):
+        return LOSS_PLAIN_WORDS
     return LOSS_FT_WORDS if isinstance(options, _lib.LossGradFtOpts) else LOSS_SSIM_WORDS if isinstance(options, _lib.LossGradSsimOpts) else LOSS_WORDS
 
 
 def _grad_range_args(options, ssim_range, L, who, batch_ok=True):
-    """the trailing (range_mode, ranges) of a b2f_*_grad_ssim entry (ssim_range_args), () for the other options"""
-    return ssim_range_args("ssim", ssim_range, L, who, batch_ok) if isinstance(options, _lib.LossGradSsimOpts) else ()
+    """the trailing (range_mode, ranges) of a b2f_*_grad_ssim or b2f_*_grad_plain entry (ssim_range_args), () for the other options"""
+    return ssim_range_args("ssim", ssim_range, L, who, batch_ok) if isinstance(options, (_lib.LossGradSsimOpts, _lib.LossGradPlainOpts)) else ()
 
 
 def _forward_loss_grad(fn, h, x, flow_scale, options, shapes, L, want_loss, want_table, tail=()):
@@ -1461,6 +1539,9 @@ class Model(object):
         records.  objective="finetune" (b2f_forward_loss_ft): records (n, L, 24), those of ops.table_loss(..., objective="finetune").
         objective="ssim" (b2f_forward_loss_ssim): records (n, L, 32) with the SSIM + L1 sums of OSSIML1Criterion.lua; ssim_range as for
         ops.table_loss: "batch" is refused when the request is cut into sub-batches, "image" and an L x 2 array do not depend on the cut.
+        objective="plain" (b2f_forward_loss_plain): records (n, L, 40) with the sums of the photometric terms that do not mask occlusions
+        (MBCCriterion.lua, MSSIML1Criterion.lua); ssim_range likewise.  The other loss and gradient methods of Model and MultiModel take
+        objective="plain", resp. the options of loss_grad_plain_options, in the same way as "ssim" and loss_grad_ssim_options.
         objective="epe" (b2f_forward_loss_epe; train.lua:296-334): records (n, L, 8), those of ops.table_loss_epe(self.forward(x), gt_flow,
         valid, gt_occ, options=options); the ground truth of a sub-batch is uploaded with its frames."""
         words = loss_words(objective)

@@ -963,7 +963,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1012; }
+int b2f_version(void) { return 1013; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 
@@ -1613,7 +1613,7 @@ int loss_subbatch(const b2f_ctx *c, int n, int H, int W)
 // record would depend on where the request is cut otherwise)
 int check_forward_loss_kind(const b2f_ctx *c, const std::string &w, const LossKind &k, int n, int H, int W)
 {
-    if (!k.ssim()) return 0;
+    if (!k.ranged()) return 0;
     const char *why = ssim_range_refusal(k.range_mode, k.ranges);
     if (why) return fail(w + ": " + why);
     if (k.range_mode == B2F_SSIM_RANGE_BATCH && loss_subbatch(c, n, H, W) < n)
@@ -1918,6 +1918,41 @@ int b2f_forward_loss_grad_ssim_device(b2f_ctx *c, const void *dev_in, int in_kin
     return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_ssim_device")
+
+// model:forward + the gradient table with the photometric terms without occlusion masking and the 40-word records, from host memory
+int b2f_forward_loss_grad_plain(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_plain_opts *opts,
+                                unsigned long long *loss, float *const *grad, int n_outs, float *const *outs, int range_mode, const float *ranges) try
+{
+    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs, outs);
+}
+B2F_CATCH("b2f_forward_loss_grad_plain")
+
+int b2f_forward_loss_grad_plain_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                       const b2f_loss_grad_plain_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream,
+                                       int range_mode, const float *ranges) try
+{
+    const GradArgs a = grad_args(opts, range_mode, ranges);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
+}
+B2F_CATCH("b2f_forward_loss_grad_plain_device")
+
+// model:forward + test.lua:266-297 + the photometric sums of criterions/MBCCriterion.lua:35-102 and MSSIML1Criterion.lua:45-153 from
+// host memory: loss n x L x 40 words
+int b2f_forward_loss_plain(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
+                           int range_mode, const float *ranges) try
+{
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges});
+}
+B2F_CATCH("b2f_forward_loss_plain")
+
+// ... on device pointers: dev_loss n x L x 40 words
+int b2f_forward_loss_plain_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
+                                  void *stream, int range_mode, const float *ranges) try
+{
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}, dev_loss,
+                               nullptr, 0, stream);
+}
+B2F_CATCH("b2f_forward_loss_plain_device")
 
 // model:forward + test.lua:266-297 from host memory
 int b2f_forward_loss(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try

@@ -584,7 +584,7 @@ struct b2f_ctx : b2f::KernelOpts {
     b2f::DevWork vis_max;         // b2f_flow_rgb_device without dev_max_used: the per-image maxima of the automatic mode
     b2f::DevWork loss_pyr;        // b2f_table_loss_device / b2f_forward_loss*: the pooled reference images R_1 .. R_{L-1} (test.lua:266-297)
     b2f::DevWork loss_work;       // b2f_forward_loss*: [input | output table | records] of a sub-batch
-    b2f::DevWork loss_rec;        // the *_grad_ssim entries without records: n x L x 32 words for the ranges (table_loss_grad_run)
+    b2f::DevWork loss_rec;        // the *_grad_ssim / *_grad_plain entries without records: n x L x 32 / 40 words for the ranges (table_loss_grad_run)
     std::vector<b2f_stream *> streams;   // open streams (b2f_stream_open); b2f_destroy closes what is left
     // arena_guard on a non-shipped graph: the generic executor's buffers of the layout in arena_layout; guards[].name points into their names
     std::vector<b2f::GraphBuf> graph_bufs;
@@ -635,7 +635,10 @@ struct LossKind {
     int range_mode = 0;
     const float *ranges = nullptr;
     bool ssim() const { return words == B2F_LOSS_SSIM_WORDS; }
-    const char *suffix() const { return words == B2F_LOSS_FT_WORDS ? "_ft" : ssim() ? "_ssim" : ""; }
+    // B2F_LOSS_PLAIN_WORDS: with the photometric sums without occlusion masking of MBCCriterion.lua / MSSIML1Criterion.lua and their range
+    bool plain() const { return words == B2F_LOSS_PLAIN_WORDS; }
+    bool ranged() const { return ssim() || plain(); }   // range_mode and ranges are read
+    const char *suffix() const { return words == B2F_LOSS_FT_WORDS ? "_ft" : ssim() ? "_ssim" : plain() ? "_plain" : ""; }
 };
 inline LossKind loss_kind(bool ft) { return LossKind{ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS, 0, nullptr}; }
 // b2f_api.hip: b2f_forward_loss (test.lua:266-297 behind model:forward) on n of a request of `req` triplets (0: n)
@@ -645,7 +648,8 @@ int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, 
 // which gradient table an entry writes: the *_grad entries (b2f_loss_grad_opts, table_loss_grad_kernel, 16-word records), the *_grad_ft
 // entries (b2f_loss_grad_ft_opts, table_loss_grad_ft_kernel, 24-word records) or the *_grad_ssim entries (b2f_loss_grad_ssim_opts,
 // table_loss_grad_ft_kernel's flow planes + table_loss_grad_ssim_kernel, 32-word records)
-enum GradKind { kGradKindFirst = 0, kGradKindFt = 1, kGradKindSsim = 2 };
+// or the *_grad_plain entries (b2f_loss_grad_plain_opts, the flow planes likewise + table_loss_grad_plain_kernel, 40-word records)
+enum GradKind { kGradKindFirst = 0, kGradKindFt = 1, kGradKindSsim = 2, kGradKindPlain = 3 };
 // the options an entry was given: opts points at the struct of `kind` (nullptr: that kind's defaults); range_mode / ranges: the
 // trailing arguments of the *_grad_ssim entries
 struct GradArgs {
@@ -656,13 +660,20 @@ struct GradArgs {
     // the records that go with this gradient table
     LossKind rec() const
     {
-        return kind == kGradKindSsim ? LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges} : loss_kind(kind == kGradKindFt);
+        return kind == kGradKindSsim    ? LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}
+               : kind == kGradKindPlain ? LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}
+                                        : loss_kind(kind == kGradKindFt);
     }
-    const char *suffix() const { return kind == kGradKindFt ? "_grad_ft" : kind == kGradKindSsim ? "_grad_ssim" : "_grad"; }
+    bool ranged() const { return kind == kGradKindSsim || kind == kGradKindPlain; }
+    const char *suffix() const
+    {
+        return kind == kGradKindFt ? "_grad_ft" : kind == kGradKindSsim ? "_grad_ssim" : kind == kGradKindPlain ? "_grad_plain" : "_grad";
+    }
 };
 inline GradArgs grad_args(const b2f_loss_grad_opts *o) { return GradArgs{kGradKindFirst, o, 0, nullptr}; }
 inline GradArgs grad_args(const b2f_loss_grad_ft_opts *o) { return GradArgs{kGradKindFt, o, 0, nullptr}; }
 inline GradArgs grad_args(const b2f_loss_grad_ssim_opts *o, int range_mode, const float *ranges) { return GradArgs{kGradKindSsim, o, range_mode, ranges}; }
+inline GradArgs grad_args(const b2f_loss_grad_plain_opts *o, int range_mode, const float *ranges) { return GradArgs{kGradKindPlain, o, range_mode, ranges}; }
 // checked options of a gradient table: o holds the first-order fields and smooth_second_order of every kind (the *_grad entries: both
 // flags 0; the *_grad_ssim entries: pme_criterion 0, unused), ssim_alpha and rec the rest of kGradKindSsim
 struct GradOpts {
@@ -670,6 +681,7 @@ struct GradOpts {
     GradKind kind;
     double ssim_alpha;
     LossKind rec;
+    int plain_criterion = 0, plain_penalty = 0;   // kGradKindPlain: B2F_PLAIN_*
 };
 // b2f_tableloss.hip: the options of a, or its kind's defaults where they are null, into *o; refused as include/b2f.h says (the range
 // of kGradKindSsim included)

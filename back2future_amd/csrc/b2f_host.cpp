@@ -11,6 +11,7 @@
 #include "b2f_tableloss_ft.h"
 #include "b2f_tableloss_ssim.h"
 #include "b2f_tableloss_grad_ssim.h"
+#include "b2f_tableloss_plain.h"
 #include "b2f_tableloss_epe.h"
 #include "../../include/b2f.h"
 
@@ -431,10 +432,11 @@ static float word_float(unsigned long long u64)
 }
 
 // every image's own range per level, on the encoding whose minimum and maximum do not depend on the order; then the one used
-void ssim_ranges_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, int range_mode, const float *ranges,
-                      unsigned long long *loss)
+// kRec: words per record; own / used: where the two pairs go; plain: the planes of MSSIML1Criterion.lua:63-68 (`for i = 2,#input`: the
+// occlusions and, on Soft tables, the past flow as well) instead of OSSIML1Criterion.lua:62-67's
+static void ranges_host_impl(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, int range_mode, const float *ranges,
+                             unsigned long long *loss, int kRec, int own, int used, bool plain)
 {
-    constexpr int kRec = B2F_LOSS_SSIM_WORDS;
     const int per = past ? 5 : 4;
     std::vector<float> cur, next;
     std::vector<unsigned> lo((size_t)L, 0xffffffffu), hi((size_t)L, 0u);
@@ -449,18 +451,22 @@ void ssim_ranges_host(const float *const *table, int L, bool past, int n, int H,
                 R = cur.data();
             }
             const float *const *t = table + (size_t)j * per;
-            const float *seg[3] = {R, t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
+            const float *seg[5] = {R, t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw, plain ? t[per - 3] + (size_t)b * 2 * hw : nullptr,
+                                   plain && past ? t[1] + (size_t)b * 2 * hw : nullptr};
             unsigned l = 0xffffffffu, h = 0u;
-            for (const float *p : seg)
-                for (size_t i = 0; i < 3 * hw; ++i)
+            for (int q = 0; q < 5; ++q) {
+                const float *p = seg[q];
+                const size_t len = (q < 3 ? 3 : 2) * hw;
+                for (size_t i = 0; p && i < len; ++i)
                     if (p[i] == p[i]) {
                         const unsigned e = ssim_enc(p[i]);
                         l = std::min(l, e);
                         h = std::max(h, e);
                     }
+            }
             unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
-            rec[B2F_LOSS_SSIM_RANGE_OWN] = ssim_dec_bits(l);
-            rec[B2F_LOSS_SSIM_RANGE_OWN + 1] = ssim_dec_bits(h);
+            rec[own] = ssim_dec_bits(l);
+            rec[own + 1] = ssim_dec_bits(h);
             lo[(size_t)j] = std::min(lo[(size_t)j], l);
             hi[(size_t)j] = std::max(hi[(size_t)j], h);
         }
@@ -474,16 +480,28 @@ void ssim_ranges_host(const float *const *table, int L, bool past, int n, int H,
         for (int j = 0; j < L; ++j) {
             unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
             if (range_mode == B2F_SSIM_RANGE_BATCH) {
-                rec[B2F_LOSS_SSIM_RANGE_USED] = ssim_dec_bits(lo[(size_t)j]);
-                rec[B2F_LOSS_SSIM_RANGE_USED + 1] = ssim_dec_bits(hi[(size_t)j]);
+                rec[used] = ssim_dec_bits(lo[(size_t)j]);
+                rec[used + 1] = ssim_dec_bits(hi[(size_t)j]);
             } else if (range_mode == B2F_SSIM_RANGE_GIVEN) {
-                rec[B2F_LOSS_SSIM_RANGE_USED] = float_bits(ranges[2 * j]);
-                rec[B2F_LOSS_SSIM_RANGE_USED + 1] = float_bits(ranges[2 * j + 1]);
+                rec[used] = float_bits(ranges[2 * j]);
+                rec[used + 1] = float_bits(ranges[2 * j + 1]);
             } else {
-                rec[B2F_LOSS_SSIM_RANGE_USED] = rec[B2F_LOSS_SSIM_RANGE_OWN];
-                rec[B2F_LOSS_SSIM_RANGE_USED + 1] = rec[B2F_LOSS_SSIM_RANGE_OWN + 1];
+                rec[used] = rec[own];
+                rec[used + 1] = rec[own + 1];
             }
         }
+}
+
+void ssim_ranges_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, int range_mode, const float *ranges,
+                      unsigned long long *loss)
+{
+    ranges_host_impl(table, L, past, n, H, W, ref, range_mode, ranges, loss, B2F_LOSS_SSIM_WORDS, B2F_LOSS_SSIM_RANGE_OWN, B2F_LOSS_SSIM_RANGE_USED, false);
+}
+
+void plain_ranges_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, int range_mode, const float *ranges,
+                       unsigned long long *loss)
+{
+    ranges_host_impl(table, L, past, n, H, W, ref, range_mode, ranges, loss, B2F_LOSS_PLAIN_WORDS, B2F_LOSS_PLAIN_RANGE_OWN, B2F_LOSS_PLAIN_RANGE_USED, true);
 }
 
 // the SSIM + L1 photometric sums of criterions/OSSIML1Criterion.lua:47-163 beside test.lua:266-297
@@ -561,6 +579,88 @@ void table_loss_ssim_host(const float *const *table, int L, bool past, int n, in
                         rec[B2F_LOSS_SSIM_Q30 + d] += ps.ssim;
                         rec[B2F_LOSS_SSIM_L1N_Q30 + d] += ps.l1n;
                         rec[B2F_LOSS_SSIM_NONFINITE + d] += ps.nonfinite;
+                    }
+                }
+        }
+    }
+}
+
+// the photometric sums without occlusion masking (criterions/MBCCriterion.lua:35-102, MSSIML1Criterion.lua:45-153) beside test.lua:266-297
+void table_loss_plain_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                           int range_mode, const float *ranges, unsigned long long *loss)
+{
+    constexpr int kRec = B2F_LOSS_PLAIN_WORDS;
+    table_loss_host(table, L, past, n, H, W, ref, flow_scale, loss, kRec);
+    plain_ranges_host(table, L, past, n, H, W, ref, range_mode, ranges, loss);
+    const int per = past ? 5 : 4;
+    std::vector<float> cur, next;
+    std::vector<double> tv[3][3];   // the normalised planes of a level: [R, iw1, iw3][channel]
+    for (int b = 0; b < n; ++b) {
+        const float *R = nullptr;
+        for (int j = 0; j < L; ++j) {
+            const int h = H >> j, w = W >> j;
+            const size_t hw = (size_t)h * w;
+            if (j == 0) R = ref + (size_t)b * 3 * H * W;
+            else {   // R_j as in table_loss_host
+                pool_ref(R, H >> (j - 1), W >> (j - 1), next);
+                cur.swap(next);
+                R = cur.data();
+            }
+            unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
+            const SsimRange rg = ssim_range(word_float(rec[B2F_LOSS_PLAIN_RANGE_USED]), word_float(rec[B2F_LOSS_PLAIN_RANGE_USED + 1]));
+            const float *const *t = table + (size_t)j * per;
+            const float *f = t[0] + (size_t)b * 2 * hw, *p = past ? t[1] + (size_t)b * 2 * hw : nullptr;
+            const float *o = t[per - 3] + (size_t)b * 2 * hw, *iw[2] = {t[per - 2] + (size_t)b * 3 * hw, t[per - 1] + (size_t)b * 3 * hw};
+            const float *src[3] = {R, iw[0], iw[1]};
+            if (rg.ok)
+                for (int s = 0; s < 3; ++s)
+                    for (int c = 0; c < 3; ++c) {
+                        tv[s][c].resize(hw);
+                        for (size_t i = 0; i < hw; ++i) tv[s][c][i] = ssim_norm(src[s][(size_t)c * hw + i], rg);
+                    }
+            const float kd = (float)(flow_scale / (double)(1 << j));
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    const size_t i = (size_t)y * w + x;
+                    const size_t xs[3] = {(size_t)(x > 0 ? x - 1 : x), (size_t)x, (size_t)(x + 1 < w ? x + 1 : x)};
+                    const size_t ys[3] = {(size_t)(y > 0 ? y - 1 : y) * w, (size_t)y * w, (size_t)(y + 1 < h ? y + 1 : y) * w};
+                    // the window sum of a * b2 (b2 == nullptr: of a) at the pixel, as table_loss_ssim_host forms it
+                    auto G = [&](const double *a, const double *b2) {
+                        double col[3];
+                        for (int k = 0; k < 3; ++k) {
+                            const size_t i0 = ys[0] + xs[k], i1 = ys[1] + xs[k], i2 = ys[2] + xs[k];
+                            col[k] = b2 ? ssim_tap3(a[i0] * b2[i0], a[i1] * b2[i1], a[i2] * b2[i2]) : ssim_tap3(a[i0], a[i1], a[i2]);
+                        }
+                        return ssim_tap3(col[0], col[1], col[2]);
+                    };
+                    const float r3[3] = {R[i], R[hw + i], R[2 * hw + i]};
+                    bool counted[2];
+                    for (int d = 0; d < 2; ++d) {
+                        const float *fl = (d == 0 && past) ? p : f;   // MBCCriterion.lua:73-81
+                        const WarpTaps tp = warp_taps(fl[i], fl[hw + i], d == 0 ? -kd : kd, x, y, w, h);
+                        const float w3[3] = {iw[d][i], iw[d][hw + i], iw[d][2 * hw + i]};
+                        const PixelPlainRaw pr = plain_raw(photo_pixel(tp, w3, r3, true, d == 0 ? o[hw + i] : o[i]));
+                        counted[d] = pr.counted;
+                        rec[B2F_LOSS_PLAIN_L1_Q30 + d] += pr.l1;
+                        rec[B2F_LOSS_PLAIN_SQ_Q30 + d] += pr.sq;
+                    }
+                    double S[2] = {0.0, 0.0}, B[2] = {0.0, 0.0};
+                    if (rg.ok && (counted[0] || counted[1]))
+                        for (int c = 0; c < 3; ++c) {
+                            const double *ty = tv[0][c].data();
+                            const double mu_y = G(ty, nullptr), gyy = G(ty, ty);
+                            for (int d = 0; d < 2; ++d) {
+                                const double *tx = tv[1 + d][c].data();
+                                const double s = ssim_term(G(tx, nullptr), mu_y, G(tx, tx), gyy, G(tx, ty)), e = loss_p1(tx[i] - ty[i]);
+                                S[d] = c == 0 ? s : S[d] + s;
+                                B[d] = c == 0 ? e : B[d] + e;
+                            }
+                        }
+                    for (int d = 0; d < 2; ++d) {
+                        const PixelPlainSsim pp = plain_ssim(counted[d], S[d], B[d], rg.ok);
+                        rec[B2F_LOSS_PLAIN_SSIM_Q30 + d] += pp.ssim;
+                        rec[B2F_LOSS_PLAIN_L1N_Q30 + d] += pp.l1n;
+                        rec[B2F_LOSS_PLAIN_SSIM_NONFINITE + d] += pp.nonfinite;
                     }
                 }
         }
@@ -691,7 +791,11 @@ void loss_grad_ssim_coef(const b2f_loss_grad_ft_opts &o, double ssim_alpha, int 
 // what table_loss_grad_host_impl needs for the SSIM + L1 photometric term: alpha, and records that hold the ranges
 struct GradSsimHost {
     double alpha;
-    const unsigned long long *rec;   // n x L x B2F_LOSS_SSIM_WORDS words
+    const unsigned long long *rec;   // n x L x B2F_LOSS_SSIM_WORDS words (plain: B2F_LOSS_PLAIN_WORDS; not read with B2F_PLAIN_BCC)
+    // plain: the terms without occlusion masking of b2f_tableloss_plain.h instead, with this criterion and penalty (B2F_PLAIN_*)
+    bool plain = false;
+    int criterion = B2F_PLAIN_SSIM, penalty = B2F_PLAIN_L1;
+    bool bcc() const { return plain && criterion == B2F_PLAIN_BCC; }
 };
 
 static void table_loss_grad_host_impl(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
@@ -713,6 +817,53 @@ void table_loss_grad_ssim_host(const float *const *table, int L, bool past, int 
     b2f_loss_grad_ft_opts o = opts;
     o.pme_criterion = 0;
     table_loss_grad_host_impl(table, L, past, n, H, W, ref, flow_scale, o, &ss, grad);
+}
+
+void table_loss_grad_plain_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                                const b2f_loss_grad_ft_opts &opts, int criterion, int penalty, double ssim_alpha, int range_mode, const float *ranges,
+                                float *const *grad)
+{
+    std::vector<unsigned long long> rec;
+    GradSsimHost ss = {ssim_alpha, nullptr};
+    ss.plain = true;
+    ss.criterion = criterion;
+    ss.penalty = penalty;
+    if (!ss.bcc()) {
+        rec.assign((size_t)n * L * B2F_LOSS_PLAIN_WORDS, 0ull);
+        plain_ranges_host(table, L, past, n, H, W, ref, range_mode, ranges, rec.data());
+        ss.rec = rec.data();
+    }
+    b2f_loss_grad_ft_opts o = opts;
+    o.pme_criterion = 0;
+    table_loss_grad_host_impl(table, L, past, n, H, W, ref, flow_scale, o, &ss, grad);
+}
+
+void loss_grad_plain_coef(const b2f_loss_grad_ft_opts &o, int criterion, int penalty, double ssim_alpha, int j, int h, int w, GradPlainCoef *k)
+{
+    loss_grad_ssim_coef(o, ssim_alpha, j, h, w, &k->s);
+    k->pl = (criterion == B2F_PLAIN_SSIM ? kGradPlainSsim : 0u) | (penalty == B2F_PLAIN_QUADRATIC ? kGradPlainQuad : 0u);
+}
+
+const char *loss_grad_plain_refusal(const b2f_loss_grad_plain_opts &o)
+{
+    if (const char *why = loss_grad_refusal(loss_grad_ft_base(loss_grad_plain_base(o)))) return why;
+    if (o.criterion != B2F_PLAIN_BCC && o.criterion != B2F_PLAIN_SSIM) return "criterion of b2f_loss_grad_plain_opts must be B2F_PLAIN_BCC or B2F_PLAIN_SSIM";
+    if (o.penalty != B2F_PLAIN_L1 && o.penalty != B2F_PLAIN_QUADRATIC) return "penalty of b2f_loss_grad_plain_opts must be B2F_PLAIN_L1 or B2F_PLAIN_QUADRATIC";
+    if (o.penalty == B2F_PLAIN_QUADRATIC && o.criterion != B2F_PLAIN_BCC)
+        return "B2F_PLAIN_QUADRATIC goes with B2F_PLAIN_BCC only (model.lua:189-190 leaves the penalty of MBCCriterion alone in place)";
+    if (!(o.ssim_alpha >= 0.0 && o.ssim_alpha <= 1.0)) return "ssim_alpha of b2f_loss_grad_plain_opts must be in [0, 1]";
+    return nullptr;
+}
+
+b2f_loss_grad_ft_opts loss_grad_plain_base(const b2f_loss_grad_plain_opts &o)
+{
+    b2f_loss_grad_ssim_opts t;
+    t.smooth_flow = o.smooth_flow; t.const_vel = o.const_vel; t.pme = o.pme; t.smooth_occ = o.smooth_occ; t.prior_occ = o.prior_occ;
+    for (int j = 0; j < kLossMaxLevels; ++j) t.level_weights[j] = o.level_weights[j];
+    t.size_average = o.size_average;
+    t.smooth_second_order = o.smooth_second_order;
+    t.ssim_alpha = o.ssim_alpha;
+    return loss_grad_ssim_base(t);
 }
 
 // every gradient table; ss: the photometric term is that of b2f_tableloss_grad_ssim.h (else opts.pme_criterion's)
@@ -752,10 +903,14 @@ static void table_loss_grad_host_impl(const float *const *table, int L, bool pas
             float *giw[2] = {g[per - 2] + (size_t)b * 3 * hw, g[per - 1] + (size_t)b * 3 * hw};
             const float kd = (float)(flow_scale / (double)(1 << j));
             GradSsimCoef ks = {};
-            if (ss && (k.on & kGradPhoto)) {
-                loss_grad_ssim_coef(opts, ss->alpha, j, h, w, &ks);
-                const unsigned long long *rec = ss->rec + ((size_t)b * L + j) * B2F_LOSS_SSIM_WORDS;
-                const SsimRange rg = ssim_range(word_float(rec[B2F_LOSS_SSIM_RANGE_USED]), word_float(rec[B2F_LOSS_SSIM_RANGE_USED + 1]));
+            GradPlainCoef kp = {};
+            if (ss && ss->plain) loss_grad_plain_coef(opts, ss->criterion, ss->penalty, ss->alpha, j, h, w, &kp);
+            if (ss && !ss->bcc() && (k.on & kGradPhoto)) {
+                if (ss->plain) ks = kp.s;
+                else loss_grad_ssim_coef(opts, ss->alpha, j, h, w, &ks);
+                const int words = ss->plain ? B2F_LOSS_PLAIN_WORDS : B2F_LOSS_SSIM_WORDS, used = ss->plain ? B2F_LOSS_PLAIN_RANGE_USED : B2F_LOSS_SSIM_RANGE_USED;
+                const unsigned long long *rec = ss->rec + ((size_t)b * L + j) * words;
+                const SsimRange rg = ssim_range(word_float(rec[used]), word_float(rec[used + 1]));
                 const float *src[3] = {R, iw[0], iw[1]};
                 for (int q = 0; q < 3; ++q)
                     for (int c = 0; c < 3; ++c) {
@@ -822,7 +977,9 @@ static void table_loss_grad_host_impl(const float *const *table, int L, bool pas
                             const bool pf = d == 0 && past;   // OBCCriterion.lua:166-170
                             const WarpTaps tp = warp_taps(pf ? p[i] : f[i], pf ? p[hw + i] : f[hw + i], d == 0 ? -kd : kd, x, y, w, h);
                             const float w3[3] = {iw[d][i], iw[d][hw + i], iw[d][2 * hw + i]}, r3[3] = {R[i], R[hw + i], R[2 * hw + i]};
-                            if (ss) {
+                            if (ss && ss->bcc()) {
+                                for (int c = 0; c < 3; ++c) gi[c] = grad_plain_bcc(kp, tp.inside, w3[c], r3[c]);
+                            } else if (ss) {
                                 const size_t xs[3] = {il - (i - x), (size_t)x, ir - (i - x)}, ys[3] = {iu - x, i - x, id - x};   // clamped columns, rows
                                 // the window sum of a * b2 (b2 == nullptr: of a) at the pixel, as table_loss_ssim_host forms it
                                 auto G = [&](const double *a, const double *b2) {
@@ -837,7 +994,7 @@ static void table_loss_grad_host_impl(const float *const *table, int L, bool pas
                                 for (int c = 0; c < 3; ++c) {
                                     const double *ty = tv[0][c].data(), *tx = tv[1 + d][c].data();
                                     const GradSsimChannel ch = grad_ssim_channel(ks, tx[i], ty[i], G(tx, nullptr), G(ty, nullptr), G(tx, tx), G(ty, ty), G(tx, ty));
-                                    gi[c] = grad_ssim_image(ks, tp.inside, ch.t, o[(size_t)(1 - d) * hw + i]);
+                                    gi[c] = ss->plain ? grad_plain_ssim(kp, tp.inside, ch.t) : grad_ssim_image(ks, tp.inside, ch.t, o[(size_t)(1 - d) * hw + i]);
                                     S = c == 0 ? ch.s : S + ch.s;
                                     B = c == 0 ? ch.e : B + ch.e;
                                 }
@@ -865,7 +1022,7 @@ static void table_loss_grad_host_impl(const float *const *table, int L, bool pas
                     }
                     for (int c = 0; c < 2; ++c) {
                         const double so = (k.on & kGradSmoothOcc) ? S2(o + c * hw) : 0.0;
-                        go[c * hw + i] = grad_occ(k, po[c], so, o[(size_t)(1 - c) * hw + i]);
+                        go[c * hw + i] = ss && ss->plain ? grad_plain_occ(k, so, o[(size_t)(1 - c) * hw + i]) : grad_occ(k, po[c], so, o[(size_t)(1 - c) * hw + i]);
                     }
                 }
         }

@@ -141,6 +141,28 @@ void ssim_ranges_host(const float *const *table, int L, bool past, int n, int H,
 // the coefficients of level j of h x w (include/b2f.h: k_s .. k_pr) and which terms are evaluated
 void loss_grad_coef(const b2f_loss_grad_opts &o, int j, int h, int w, GradCoef *k);
 }  // namespace b2f
+struct b2f_loss_grad_plain_opts;
+namespace b2f {
+struct GradPlainCoef;
+// table_loss_host with records of B2F_LOSS_PLAIN_WORDS words, and in words 16 .. 29 the photometric sums without occlusion masking of
+// criterions/MBCCriterion.lua:35-102 and MSSIML1Criterion.lua:45-153 and the ranges of the latter's lines 63-68 (b2f_tableloss_plain.h
+// per pixel; b2f_table_loss_plain_host)
+void table_loss_plain_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                           int range_mode, const float *ranges, unsigned long long *loss);
+// words RANGE_OWN and RANGE_USED of records of B2F_LOSS_PLAIN_WORDS words: the range over R_j, the warped images, the occlusions and, on
+// Soft tables, the past flow (MSSIML1Criterion.lua:63-68); every other word left alone
+void plain_ranges_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, int range_mode, const float *ranges,
+                       unsigned long long *loss);
+// The gradient table with those photometric terms (MBCCriterion.lua:104-186, MSSIML1Criterion.lua:155-261; b2f_tableloss_plain.h per
+// element; b2f_table_loss_grad_plain_host): opts as for table_loss_grad_ssim_host, criterion B2F_PLAIN_*, penalty B2F_PLAIN_*
+void table_loss_grad_plain_host(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, double flow_scale,
+                                const b2f_loss_grad_ft_opts &opts, int criterion, int penalty, double ssim_alpha, int range_mode, const float *ranges,
+                                float *const *grad);
+// nullptr, or why (as loss_grad_ssim_refusal, a criterion or penalty that is none of B2F_PLAIN_*, the quadratic penalty without BCC)
+const char *loss_grad_plain_refusal(const b2f_loss_grad_plain_opts &o);
+b2f_loss_grad_ft_opts loss_grad_plain_base(const b2f_loss_grad_plain_opts &o);
+void loss_grad_plain_coef(const b2f_loss_grad_ft_opts &o, int criterion, int penalty, double ssim_alpha, int j, int h, int w, GradPlainCoef *k);
+}  // namespace b2f
 struct b2f_loss_epe_opts;
 namespace b2f {
 // The supervised objective on the CPU (train.lua:296-334, criterions/L2Criterion.lua:27-71; b2f_tableloss_epe.h per pixel;

@@ -406,8 +406,10 @@ hipError_t launch_table_loss_ft_terms(const float *const *table, int L, bool pas
 // b2f_tableloss_ssim.hip: the ranges of criterions/OSSIML1Criterion.lua:62-67 into words 22 .. 25 of records of B2F_LOSS_SSIM_WORDS words,
 // which the records' launch has zeroed (range_mode: B2F_SSIM_RANGE_*; ranges: L x 2 host floats with B2F_SSIM_RANGE_GIVEN), and behind
 // them the SSIM + L1 sums of lines 69-151 into words 16 .. 21
+// plain: records of B2F_LOSS_PLAIN_WORDS words instead, words 26 .. 29, and the range of MSSIML1Criterion.lua:63-68 (`for i = 2,#input`:
+// over the occlusions and, on Soft tables, the past flow as well)
 hipError_t launch_table_loss_range(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, const float *pyr,
-                                   int range_mode, const float *ranges, unsigned long long *loss, hipStream_t s);
+                                   int range_mode, const float *ranges, unsigned long long *loss, hipStream_t s, bool plain = false);
 hipError_t launch_table_loss_ssim_terms(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
                                         const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s);
 // b2f_tableloss_grad.hip: the gradient table of train.lua:428-468 (include/b2f.h: G_f, G_p, G_o, G_iw_d): grad = L x (4 | 5) device
@@ -428,6 +430,19 @@ struct GradSsimCoef;
 hipError_t launch_table_loss_grad_ssim(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref,
                                        size_t ref_stride, const float *pyr, double flow_scale, const GradSsimCoef *coef, const unsigned long long *rec,
                                        hipStream_t s);
+// b2f_tableloss_plain.hip: the photometric sums without occlusion masking (criterions/MBCCriterion.lua:35-102,
+// MSSIML1Criterion.lua:45-153; b2f_tableloss_plain.h) into words 16 .. 25 of records of B2F_LOSS_PLAIN_WORDS words, which the records'
+// launch has zeroed and whose words 26 / 27 launch_table_loss_range(.., plain = true) has filled on s before
+hipError_t launch_table_loss_plain_terms(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
+                                         const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s);
+// b2f_tableloss_grad_plain.hip: the occlusion and image planes of the gradient table with those photometric terms
+// (MBCCriterion.lua:104-186, MSSIML1Criterion.lua:155-261).  rec: records of B2F_LOSS_PLAIN_WORDS words whose words
+// B2F_LOSS_PLAIN_RANGE_USED hold the ranges, read with the SSIM criterion and a non-zero pme only (else it may be null).  The flow
+// planes are not touched; occlusion planes without a term are set to zero by a memset on s.
+struct GradPlainCoef;
+hipError_t launch_table_loss_grad_plain(const float *const *table, float *const *grad, int L, bool past, int n, int H, int W, const float *ref,
+                                        size_t ref_stride, const float *pyr, double flow_scale, const GradPlainCoef *coef, const unsigned long long *rec,
+                                        hipStream_t s);
 }  // namespace b2f
 // b2f_tableloss_epe.hip: the supervised objective of train.lua:296-334 (criterions/L2Criterion.lua:27-71; include/b2f.h, the *_epe
 // entries): the records (loss: n x L x B2F_LOSS_EPE_WORDS words, zeroed on s first, or nullptr) and / or the gradient table (grad as

@@ -411,7 +411,7 @@ static int multi_forward_loss(const std::string &w, const LossKind &k, b2f_multi
     if (!m) return api_fail(w + ": null context");
     if (!x || !loss || n <= 0 || H <= 0 || W <= 0) return api_fail(w + ": bad arguments");
     // (a shard's batch range would depend on how the request is split over the GPUs)
-    if (k.ssim() && k.range_mode == B2F_SSIM_RANGE_BATCH)
+    if (k.ranged() && k.range_mode == B2F_SSIM_RANGE_BATCH)
         return api_fail(w + ": B2F_SSIM_RANGE_BATCH is not served over several GPUs: the images of a request are split; use B2F_SSIM_RANGE_IMAGE or "
                             "B2F_SSIM_RANGE_GIVEN");
     const b2f_ctx *c0 = m->ctx[0];
@@ -444,6 +444,14 @@ int b2f_multi_forward_loss_ssim(b2f_multi *m, const float *x, int n, int H, int 
     return multi_forward_loss(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, m, x, n, H, W, flow_scale, loss);
 }
 B2F_CATCH("b2f_multi_forward_loss_ssim")
+
+// ... with the photometric sums without occlusion masking (MBCCriterion.lua, MSSIML1Criterion.lua) in words 16 .. 29; the batch range is refused
+int b2f_multi_forward_loss_plain(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, int range_mode,
+                                 const float *ranges) try
+{
+    return multi_forward_loss(__func__, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}, m, x, n, H, W, flow_scale, loss);
+}
+B2F_CATCH("b2f_multi_forward_loss_plain")
 
 // the supervised objective of train.lua:296-334 behind model:forward over several GPUs; the batch's counts are refused
 int b2f_multi_forward_loss_epe(b2f_multi *m, const float *x, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
@@ -483,7 +491,7 @@ static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const flo
     if (!m) return api_fail((w + ": null context").c_str());
     if (!x || !grad || n <= 0 || H <= 0 || W <= 0) return api_fail((w + ": bad arguments").c_str());
     // (a shard's batch range would depend on how the request is split over the GPUs)
-    if (a.kind == kGradKindSsim && a.range_mode == B2F_SSIM_RANGE_BATCH)
+    if (a.ranged() && a.range_mode == B2F_SSIM_RANGE_BATCH)
         return api_fail(w + ": B2F_SSIM_RANGE_BATCH is not served over several GPUs: the images of a request are split; use B2F_SSIM_RANGE_IMAGE or "
                             "B2F_SSIM_RANGE_GIVEN");
     const b2f_ctx *c0 = m->ctx[0];
@@ -525,5 +533,13 @@ int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H,
     return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs);
 }
 B2F_CATCH("b2f_multi_forward_loss_grad_ssim")
+
+// ... with the photometric terms without occlusion masking; the batch range is refused
+int b2f_multi_forward_loss_grad_plain(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_plain_opts *opts,
+                                      unsigned long long *loss, float *const *grad, int n_outs, int range_mode, const float *ranges) try
+{
+    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs);
+}
+B2F_CATCH("b2f_multi_forward_loss_grad_plain")
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "b2f_tableloss.h"
 #include "b2f_tableloss_grad_ft.h"
 #include "b2f_tableloss_ssim.h"
+#include "b2f_tableloss_plain.h"
 #include "b2f_tableloss_grad_ssim.h"
 #include "b2f_tableloss_dev.h"
 
@@ -255,8 +256,15 @@ int level_size(const b2f_ctx *c, int n_outs)
 // what the *_ssim entries check of their range
 int check_loss_kind(const std::string &w, const LossKind &k)
 {
-    const char *why = k.ssim() ? ssim_range_refusal(k.range_mode, k.ranges) : nullptr;
+    const char *why = k.ranged() ? ssim_range_refusal(k.range_mode, k.ranges) : nullptr;
     return why ? fail(w + ": " + why) : 0;
+}
+
+// what the *_plain entries with a context refuse beside: a two_frame model (MBCCriterion.lua:39-42: without occlusions the tensors of a
+// level shift, and the table has none of the words 0 .. 15)
+int check_plain_context(const std::string &w, const b2f_ctx *c, bool plain)
+{
+    return plain && c->g.two_frame ? fail(w + ": a two_frame model has no occlusions in its table; the *_plain entries are not defined for it") : 0;
 }
 
 // b2f_table_loss_device / b2f_table_loss_ft_device / b2f_table_loss_ssim_device (k: which records)
@@ -269,6 +277,7 @@ int table_loss_device(const std::string &w, const LossKind &k, b2f_ctx *c, const
     int L = 0;
     CHK(check_table_loss(w, dev_table, n_outs, per, n, H, W, dev_ref, flow_scale, dev_loss, &L));
     CHK(check_loss_kind(w, k));
+    CHK(check_plain_context(w, c, k.plain()));
     if (n > 65535) return fail(w + ": at most 65535 images per call");
     uintptr_t bits = (uintptr_t)dev_ref | (uintptr_t)dev_loss;
     for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i];
@@ -291,6 +300,7 @@ int op_table_loss(const std::string &w, const LossKind &k, b2f_ctx *c, const flo
     int L = 0;
     CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, loss, &L));
     CHK(check_loss_kind(w, k));
+    CHK(check_plain_context(w, c, k.plain()));
     std::vector<const float *> ptrs((size_t)n_outs);
     float *dr;
     for (int i = 0; i < n_outs; ++i) {
@@ -328,7 +338,17 @@ int b2f::resolve_grad_opts(const std::string &w, const GradArgs &a, GradOpts *o)
     o->ssim_alpha = 0.0;
     o->rec = a.rec();
     const char *why = nullptr;
-    if (a.kind == kGradKindSsim) {
+    if (a.kind == kGradKindPlain) {
+        b2f_loss_grad_plain_opts t;
+        if (a.opts) t = *static_cast<const b2f_loss_grad_plain_opts *>(a.opts);
+        else (void)b2f_loss_grad_plain_defaults(&t);
+        o->o = loss_grad_plain_base(t);
+        o->ssim_alpha = t.ssim_alpha;
+        o->plain_criterion = t.criterion;
+        o->plain_penalty = t.penalty;
+        why = loss_grad_plain_refusal(t);
+        if (!why) why = ssim_range_refusal(a.range_mode, a.ranges);
+    } else if (a.kind == kGradKindSsim) {
         b2f_loss_grad_ssim_opts t;
         if (a.opts) t = *static_cast<const b2f_loss_grad_ssim_opts *>(a.opts);
         else (void)b2f_loss_grad_ssim_defaults(&t);
@@ -386,6 +406,14 @@ int b2f::table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table
             return launch_table_loss_ssim_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
         });
     }
+    if (k.plain()) {
+        CHK(timed_launch(c, s, "table_loss_range", [&] {
+            return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, k.range_mode, k.ranges, dev_loss, s, true);
+        }));
+        return timed_launch(c, s, "table_loss_plain", [&] {
+            return launch_table_loss_plain_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
+        });
+    }
     if (words != B2F_LOSS_FT_WORDS) return 0;
     return timed_launch(c, s, "table_loss_ft", [&] {
         return launch_table_loss_ft_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
@@ -408,6 +436,26 @@ int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_
     CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
     if (!dev_loss) HIPCHK(launch_table_loss_pyramid(L, n, H, W, dev_ref, ref_stride, (float *)c->loss_pyr.dev, s));
     const float *pyr = (const float *)c->loss_pyr.dev;
+    if (o.kind == kGradKindPlain) {
+        GradPlainCoef plain[kLossMaxLevels];
+        for (int j = 0; j < L; ++j) loss_grad_plain_coef(o.o, o.plain_criterion, o.plain_penalty, o.ssim_alpha, j, H >> j, W >> j, &plain[j]);
+        const unsigned long long *rec = dev_loss;
+        // no records asked for: the ranges, where the criterion reads them, into a zeroed record buffer of the context
+        if (!rec && o.plain_criterion == B2F_PLAIN_SSIM && o.o.pme != 0.0) {
+            const size_t bytes = (size_t)n * L * B2F_LOSS_PLAIN_WORDS * sizeof(unsigned long long);
+            CHK(ensure_dev_work(c->loss_rec, bytes));
+            unsigned long long *scratch = (unsigned long long *)c->loss_rec.dev;
+            HIPCHK(hipMemsetAsync(scratch, 0, bytes, s));
+            CHK(timed_launch(c, s, "table_loss_range", [&] {
+                return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, o.rec.range_mode, o.rec.ranges, scratch, s, true);
+            }));
+            rec = scratch;
+        }
+        return timed_launch(c, s, "table_loss_grad_plain", [&] {
+            const hipError_t e = launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s, true);
+            return e != hipSuccess ? e : launch_table_loss_grad_plain(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, plain, rec, s);
+        });
+    }
     if (o.kind == kGradKindSsim) {
         const unsigned long long *rec = dev_loss;
         if (!rec) {   // no records asked for: the ranges into a zeroed record buffer of the context, by the same two kernels
@@ -444,12 +492,14 @@ int table_loss_grad_device(const std::string &w, b2f_ctx *c, const float *const 
     int L = 0;
     CHK(check_table_loss(w, dev_table, n_outs, per, n, H, W, dev_ref, flow_scale, dev_grad, &L));
     CHK(check_grad_table(w, dev_table, n_outs, dev_ref, dev_grad));
+    CHK(check_plain_context(w, c, o.kind == kGradKindPlain));
     if (n > 65535) return fail(w + ": at most 65535 images per call");
     uintptr_t bits = (uintptr_t)dev_ref;
     for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i] | (uintptr_t)dev_grad[i];
     if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
-    const std::string use = o.kind == kGradKindSsim ? "b2f_op_table_loss_grad_ssim / b2f_table_loss_grad_ssim_host"
+    const std::string use = o.kind == kGradKindPlain ? "b2f_op_table_loss_grad_plain / b2f_table_loss_grad_plain_host"
+                            : o.kind == kGradKindSsim ? "b2f_op_table_loss_grad_ssim / b2f_table_loss_grad_ssim_host"
                             : o.kind == kGradKindFt ? "b2f_op_table_loss_grad_ft / b2f_table_loss_grad_ft_host"
                                                     : "b2f_op_table_loss_grad / b2f_table_loss_grad_host";
     if (host_memory(dev_ref)) return fail(w + ": host memory passed to a device entry point (use " + use + ")");
@@ -468,7 +518,10 @@ int table_loss_grad_host_entry(const std::string &w, const float *const *table, 
     CHK(check_grad_table(w, table, n_outs, ref, grad));
     GradOpts o;
     CHK(resolve_grad_opts(w, a, &o));
-    if (o.kind == kGradKindSsim)
+    if (o.kind == kGradKindPlain)
+        table_loss_grad_plain_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, o.plain_criterion, o.plain_penalty, o.ssim_alpha, o.rec.range_mode,
+                                   o.rec.ranges, grad);
+    else if (o.kind == kGradKindSsim)
         table_loss_grad_ssim_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, o.ssim_alpha, o.rec.range_mode, o.rec.ranges, grad);
     else
         table_loss_grad_ft_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, grad);
@@ -488,6 +541,7 @@ int op_table_loss_grad(const std::string &w, b2f_ctx *c, const float *const *tab
     CHK(check_grad_table(w, table, n_outs, ref, grad));
     GradOpts o;
     CHK(resolve_grad_opts(w, a, &o));
+    CHK(check_plain_context(w, c, o.kind == kGradKindPlain));
     std::vector<const float *> ptrs((size_t)n_outs);
     std::vector<float *> gptrs((size_t)n_outs);
     std::vector<size_t> floats((size_t)n_outs);
@@ -695,6 +749,72 @@ int b2f_op_table_loss_ssim(b2f_ctx *c, const float *const *table, int n_outs, in
     return op_table_loss(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, c, table, n_outs, n, H, W, ref, flow_scale, loss);
 }
 B2F_CATCH("b2f_op_table_loss_ssim")
+
+// ---- the photometric terms without occlusion masking (criterions/MBCCriterion.lua, MSSIML1Criterion.lua): records of 40 words
+// (b2f_tableloss_plain.hip) and the gradient table (b2f_tableloss_grad_plain.hip) ----
+int b2f_table_loss_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                              unsigned long long *loss, int range_mode, const float *ranges) try
+{
+    int L = 0;
+    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
+    CHK(check_loss_kind(__func__, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}));
+    table_loss_plain_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, range_mode, ranges, loss);
+    return 0;
+}
+B2F_CATCH("b2f_table_loss_plain_host")
+
+int b2f_table_loss_plain_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                                unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges) try
+{
+    return table_loss_device(__func__, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
+}
+B2F_CATCH("b2f_table_loss_plain_device")
+
+int b2f_op_table_loss_plain(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                            unsigned long long *loss, int range_mode, const float *ranges) try
+{
+    return op_table_loss(__func__, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}, c, table, n_outs, n, H, W, ref, flow_scale, loss);
+}
+B2F_CATCH("b2f_op_table_loss_plain")
+
+// opts.lua:61-73,85; model.lua:149-159,189-190
+int b2f_loss_grad_plain_defaults(b2f_loss_grad_plain_opts *o)
+{
+    if (!o) return fail("b2f_loss_grad_plain_defaults: null argument");
+    b2f_loss_grad_opts t;
+    (void)b2f_loss_grad_defaults(&t);
+    o->smooth_flow = t.smooth_flow; o->const_vel = t.const_vel; o->pme = t.pme; o->smooth_occ = t.smooth_occ; o->prior_occ = t.prior_occ;
+    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = t.level_weights[j];
+    o->size_average = t.size_average;
+    o->smooth_second_order = 0;
+    o->criterion = B2F_PLAIN_BCC;
+    o->penalty = B2F_PLAIN_L1;
+    o->ssim_alpha = 0.85;
+    return 0;
+}
+
+int b2f_table_loss_grad_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                                   const b2f_loss_grad_plain_opts *opts, float *const *grad, int range_mode, const float *ranges) try
+{
+    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, grad_args(opts, range_mode, ranges), grad);
+}
+B2F_CATCH("b2f_table_loss_grad_plain_host")
+
+int b2f_table_loss_grad_plain_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                                     const b2f_loss_grad_plain_opts *opts, float *const *dev_grad, void *stream, int range_mode, const float *ranges) try
+{
+    GradOpts o;
+    CHK(resolve_grad_opts(__func__, grad_args(opts, range_mode, ranges), &o));
+    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
+}
+B2F_CATCH("b2f_table_loss_grad_plain_device")
+
+int b2f_op_table_loss_grad_plain(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                                 const b2f_loss_grad_plain_opts *opts, float *const *grad, int range_mode, const float *ranges) try
+{
+    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, grad_args(opts, range_mode, ranges), grad);
+}
+B2F_CATCH("b2f_op_table_loss_grad_plain")
 
 // ge, gc of the window (b2f_tableloss_ssim.h)
 int b2f_loss_ssim_weights(double out[2]) try

@@ -5,7 +5,8 @@
 //     loads where the address allows, a wave reduction, the waves of a block through LDS, then one integer atomicMax per block and
 //     word on the order-preserving encoding of the float (b2f_tableloss_ssim.h: ssim_enc) -- exact, whatever the order.
 //     table_loss_range_finish_kernel decodes them into words 24 / 25 and writes the range the pixels use into words 22 / 23: the
-//     image's own, the batch's (combined here, on the device) or the caller's.
+//     image's own, the batch's (combined here, on the device) or the caller's.  Both kernels have a second instantiation for the records
+//     of b2f_tableloss_plain.hip: other words, and the occlusions and the past flow as further planes (MSSIML1Criterion.lua:63-68).
 //   table_loss_ssim_kernel has the structure of table_loss_ft_kernel -- a thread covers four consecutive pixels of a row, the rows
 //     above and below come through the cache (DESIGN.md 7.9 says why no LDS tile), counters in registers, the same block reduction,
 //     at most one 64-bit atomicAdd per non-zero word per block, the same capped grid -- on the 3 x 3 window with replication: per
@@ -49,16 +50,32 @@ __device__ __forceinline__ void range_of(const float *p, size_t len, size_t t0, 
     for (size_t i = tail + t0; i < len; i += stride) take(p[i]);
 }
 
+// where the two pairs of a record lie and how long it is: the SSIM records, or (Plain) those of the terms without occlusion masking
+template <bool Plain>
+struct RangeRec {
+    static constexpr int kOwn = Plain ? B2F_LOSS_PLAIN_RANGE_OWN : B2F_LOSS_SSIM_RANGE_OWN;
+    static constexpr int kUsed = Plain ? B2F_LOSS_PLAIN_RANGE_USED : B2F_LOSS_SSIM_RANGE_USED;
+    static constexpr int kWords = Plain ? B2F_LOSS_PLAIN_WORDS : B2F_LOSS_SSIM_WORDS;
+};
+
 // Image blockIdx.y of one level: words OWN_MIN / OWN_MAX of its record (zero before) gather the complement of the encoded minimum and
-// the encoded maximum, so that zero is the identity of both and one atomicMax serves each.
+// the encoded maximum, so that zero is the identity of both and one atomicMax serves each.  Plain: the range of
+// MSSIML1Criterion.lua:63-68, whose loop starts at input[2]: the two occlusion planes and, where lp.p is not null, the two planes of
+// the past flow are part of it.
+template <bool Plain>
 __global__ void __launch_bounds__(kThreads) table_loss_range_kernel(LevelPtrs lp, int h, int w, unsigned long long *loss, size_t rec_stride)
 {
+    constexpr int kOwn = RangeRec<Plain>::kOwn;
     const size_t b = blockIdx.y, hw = (size_t)h * w;
     const float *seg[3] = {lp.ref + b * lp.ref_stride, lp.iw1 + b * 3 * hw, lp.iw3 + b * 3 * hw};   // three planes each, contiguous
     unsigned lo = 0xffffffffu, hi = 0u;
     const size_t t0 = (size_t)blockIdx.x * kThreads + threadIdx.x, stride = (size_t)gridDim.x * kThreads;
 #pragma unroll
     for (int k = 0; k < 3; ++k) range_of(seg[k], 3 * hw, t0, stride, lo, hi);
+    if (Plain) {
+        range_of(lp.o + b * 2 * hw, 2 * hw, t0, stride, lo, hi);
+        if (lp.p) range_of(lp.p + b * 2 * hw, 2 * hw, t0, stride, lo, hi);
+    }
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) {
         const unsigned l2 = __shfl_down(lo, off, kWave), h2 = __shfl_down(hi, off, kWave);
@@ -78,8 +95,8 @@ __global__ void __launch_bounds__(kThreads) table_loss_range_kernel(LevelPtrs lp
             hi = part[k][1] > hi ? part[k][1] : hi;
         }
         unsigned long long *rec = loss + b * rec_stride;
-        if (~lo) atomicMax(rec + B2F_LOSS_SSIM_RANGE_OWN, (unsigned long long)(~lo));
-        if (hi) atomicMax(rec + B2F_LOSS_SSIM_RANGE_OWN + 1, (unsigned long long)hi);
+        if (~lo) atomicMax(rec + kOwn, (unsigned long long)(~lo));
+        if (hi) atomicMax(rec + kOwn + 1, (unsigned long long)hi);
     }
 }
 
@@ -90,8 +107,10 @@ struct GivenRanges {
 // Level blockIdx.x of all n images: words RANGE_OWN of every record from what table_loss_range_kernel gathered to the float bits of
 // the image's own minimum and maximum, words RANGE_USED to the float bits of the range of `mode`.  One block: the batch's range is
 // complete before the first record is rewritten.
+template <bool Plain>
 __global__ void __launch_bounds__(kThreads) table_loss_range_finish_kernel(unsigned long long *loss, int n, int L, int mode, GivenRanges given)
 {
+    constexpr int kOwn = RangeRec<Plain>::kOwn, kUsed = RangeRec<Plain>::kUsed, kRec = RangeRec<Plain>::kWords;
     const int j = blockIdx.x;
     __shared__ unsigned all[2];
     if (threadIdx.x == 0) {
@@ -102,7 +121,7 @@ __global__ void __launch_bounds__(kThreads) table_loss_range_finish_kernel(unsig
     unsigned lo = 0xffffffffu, hi = 0u;
     for (int b = threadIdx.x; b < n; b += kThreads) {
         const unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
-        const unsigned l2 = ~(unsigned)rec[B2F_LOSS_SSIM_RANGE_OWN], h2 = (unsigned)rec[B2F_LOSS_SSIM_RANGE_OWN + 1];
+        const unsigned l2 = ~(unsigned)rec[kOwn], h2 = (unsigned)rec[kOwn + 1];
         lo = l2 < lo ? l2 : lo;
         hi = h2 > hi ? h2 : hi;
     }
@@ -111,10 +130,10 @@ __global__ void __launch_bounds__(kThreads) table_loss_range_finish_kernel(unsig
     __syncthreads();
     for (int b = threadIdx.x; b < n; b += kThreads) {
         unsigned long long *rec = loss + ((size_t)b * L + j) * kRec;
-        const unsigned own_lo = ~(unsigned)rec[B2F_LOSS_SSIM_RANGE_OWN], own_hi = (unsigned)rec[B2F_LOSS_SSIM_RANGE_OWN + 1];
+        const unsigned own_lo = ~(unsigned)rec[kOwn], own_hi = (unsigned)rec[kOwn + 1];
         unsigned mn = ssim_dec_bits(own_lo), mx = ssim_dec_bits(own_hi);
-        rec[B2F_LOSS_SSIM_RANGE_OWN] = mn;
-        rec[B2F_LOSS_SSIM_RANGE_OWN + 1] = mx;
+        rec[kOwn] = mn;
+        rec[kOwn + 1] = mx;
         if (mode == B2F_SSIM_RANGE_BATCH) {
             mn = ssim_dec_bits(all[0]);
             mx = ssim_dec_bits(all[1]);
@@ -122,8 +141,8 @@ __global__ void __launch_bounds__(kThreads) table_loss_range_finish_kernel(unsig
             mn = __float_as_uint(given.r[j][0]);
             mx = __float_as_uint(given.r[j][1]);
         }
-        rec[B2F_LOSS_SSIM_RANGE_USED] = mn;
-        rec[B2F_LOSS_SSIM_RANGE_USED + 1] = mx;
+        rec[kUsed] = mn;
+        rec[kUsed + 1] = mx;
     }
 }
 
@@ -254,8 +273,9 @@ __global__ void __launch_bounds__(kThreads) table_loss_ssim_kernel(LevelPtrs lp,
 }  // namespace
 
 hipError_t launch_table_loss_range(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride, const float *pyr,
-                                   int range_mode, const float *ranges, unsigned long long *loss, hipStream_t s)
+                                   int range_mode, const float *ranges, unsigned long long *loss, hipStream_t s, bool plain)
 {
+    const int words = plain ? B2F_LOSS_PLAIN_WORDS : kRec;
     LossLevel lv[kLossMaxLevels];
     if (!loss || range_mode < B2F_SSIM_RANGE_BATCH || range_mode > B2F_SSIM_RANGE_GIVEN || (range_mode == B2F_SSIM_RANGE_GIVEN && !ranges) ||
         !loss_levels(table, nullptr, L, past, n, H, W, ref, ref_stride, pyr, 1.0, lv))
@@ -267,11 +287,17 @@ hipError_t launch_table_loss_range(const float *const *table, int L, bool past, 
             given.r[j][0] = ranges[2 * j];
             given.r[j][1] = ranges[2 * j + 1];
         }
-        hipLaunchKernelGGL(table_loss_range_kernel, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, loss + (size_t)j * kRec, (size_t)L * kRec);
+        if (plain)
+            hipLaunchKernelGGL(table_loss_range_kernel<true>, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, loss + (size_t)j * words, (size_t)L * words);
+        else
+            hipLaunchKernelGGL(table_loss_range_kernel<false>, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, loss + (size_t)j * words, (size_t)L * words);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(table_loss_range_finish_kernel, dim3((unsigned)L), dim3(kThreads), 0, s, loss, n, L, range_mode, given);
+    if (plain)
+        hipLaunchKernelGGL(table_loss_range_finish_kernel<true>, dim3((unsigned)L), dim3(kThreads), 0, s, loss, n, L, range_mode, given);
+    else
+        hipLaunchKernelGGL(table_loss_range_finish_kernel<false>, dim3((unsigned)L), dim3(kThreads), 0, s, loss, n, L, range_mode, given);
     return hipGetLastError();
 }
 

@@ -273,7 +273,11 @@ def table_loss(table, ref, flow_scale=20.0, model=None, objective="pme", ssim_ra
     gradient-constancy sums the Soft models were fine-tuned on (back2future.LOSS_FT_*).  objective="ssim" returns (n, L, 32)
     (b2f_table_loss_ssim_host / b2f_op_table_loss_ssim): the same 16 words, then the SSIM + L1 sums of -pme_criterion OSSIM | OSSIML1
     (criterions/OSSIML1Criterion.lua; back2future.LOSS_SSIM_*) on values normalised by ssim_range: "batch", the minimum and maximum
-    over the n images of the call as in the reference; "image", each image's own; or an L x 2 array of (mn, mx) per level."""
+    over the n images of the call as in the reference; "image", each image's own; or an L x 2 array of (mn, mx) per level.
+    objective="plain" returns (n, L, 40) (b2f_table_loss_plain_host / b2f_op_table_loss_plain): the same 16 words, then the sums of the
+    photometric terms that do not mask occlusions, -pme_criterion BCC | SSIM | SSIML1 (criterions/MBCCriterion.lua,
+    criterions/MSSIML1Criterion.lua; back2future.LOSS_PLAIN_*), with ssim_range as above; the range reaches over the occlusions and, on a
+    Soft table, the past flow, as the Lua's does."""
     from .back2future import loss_words, loss_entry, ssim_range_args
     words = loss_words(objective)
     r = np.asarray(ref)
@@ -314,7 +318,9 @@ def table_loss_grad(table, ref, flow_scale=20.0, options=None, model=None, ssim_
     with second-order smoothness and / or OBGCC (b2f_table_loss_grad_ft_host, b2f_op_table_loss_grad_ft) -> a list of float32 arrays
     with the table's shapes.  With the options of back2future.loss_grad_ssim_options the photometric term is the occlusion-aware SSIM +
     L1 of criterions/OSSIML1Criterion.lua:165-302 (b2f_table_loss_grad_ssim_host, b2f_op_table_loss_grad_ssim) on values normalised by
-    ssim_range, as for table_loss; ssim_range is not read otherwise.
+    ssim_range, as for table_loss; ssim_range is not read otherwise.  With the options of back2future.loss_grad_plain_options it is that of
+    criterions/MBCCriterion.lua:104-186 or MSSIML1Criterion.lua:155-261, which do not mask occlusions (b2f_table_loss_grad_plain_host,
+    b2f_op_table_loss_grad_plain), with ssim_range likewise.
     model=None computes on the CPU (b2f_table_loss_grad_host), a Model on its GPU (b2f_op_table_loss_grad): the bits are the same."""
     from .back2future import _grad_opts_ptr, _grad_entry, _grad_range_args
     r = np.asarray(ref)

@@ -17,6 +17,11 @@ does the same with the gradients of SecondOrderSmoothnessCriterion and OBGCCrite
 --objective NAME, or without one both criteria with alpha = beta = gamma = 1; its loss lines come from the 192-byte records.
 --grad-ssim does the same with the gradient of the SSIM (+ L1) term (back2future.loss_grad_ssim_options; OSSIML1Criterion.lua:165-302):
 --pme-criterion OSSIM | OSSIML1 (the default) and --ssim-range as above; its loss lines come from the 256-byte records of the same pass.
+--plain-criterion BCC | SSIM | SSIML1 takes the photometric terms that do not mask occlusions instead (the reference's -pme_criterion
+BCC | SSIM | SSIML1: criterions/MBCCriterion.lua, criterions/MSSIML1Criterion.lua, the paper's baseline), from records of 320 bytes
+(objective="plain"); --pme-penalty Quadratic leaves MBCCriterion's own penalty in place (BCC only); --no-occ drops the occlusions'
+smoothness and prior from the sum (opts.lua:85); --grad-plain also computes the gradient under these options
+(back2future.loss_grad_plain_options) in the same pass.  (--pme-criterion keeps the two occlusion-aware names it had.)
 --objective epe --gt GT_DIR prints the supervised objective instead (-optimize epe, train.lua:296-334: the masked end-point error of
 the future flow of every level against ground truth; Model.forwardLoss(objective="epe"), 64 bytes per level and centre frame come
 back).  GT_DIR holds, per centre frame NAME, what examples/evaluate.py reads: NAME.flo, and optionally NAME_valid.png and NAME_occ.png
@@ -27,6 +32,8 @@ back).  GT_DIR holds, per centre frame NAME, what examples/evaluate.py reads: NA
 
 Usage: python examples/validate.py FRAMES_DIR MODEL [--scale S] [--like test|train] [--size-average] [--objective NAME]
        [--pme-criterion OSSIM|OSSIML1 [--ssim-range image|batch]] [--grad | --grad-ft | --grad-ssim]
+       python examples/validate.py FRAMES_DIR MODEL --plain-criterion BCC|SSIM|SSIML1 [--pme-penalty Quadratic] [--no-occ] [--grad-plain]
+       [--scale S] [--like test|train] [--size-average] [--ssim-range image|batch]
        python examples/validate.py FRAMES_DIR MODEL --objective epe --gt GT_DIR [--scale S] [--occ-weight W] [--size-average] [--grad]
 FRAMES_DIR: 8-bit frames, sorted by name; they are cropped (top left) to multiples of 64 and normalized with
 back2future.normalize.  MODEL as for examples/run_sequence.py.  --scale: pixels per unit of raw network flow (default 20).
@@ -122,13 +129,15 @@ def main_epe(src, model, gt_dir, scale, occ_weight, size_average, grad):
 def main():
     args = list(sys.argv[1:])
     scale, like, objective, criterion, ssim_range = 20.0, "test", None, None, "image"
-    gt_dir, occ_weight = None, 0.0
+    gt_dir, occ_weight, penalty = None, 0.0, "L1"
     size_average, grad_ft, grad_ssim = "--size-average" in args, "--grad-ft" in args, "--grad-ssim" in args
-    grad = "--grad" in args or grad_ft or grad_ssim
-    if ("--grad" in args) + grad_ft + grad_ssim > 1:
-        sys.exit("--grad, --grad-ft and --grad-ssim exclude one another")
-    args = [a for a in args if a not in ("--size-average", "--grad", "--grad-ft", "--grad-ssim")]
-    for flag in ("--scale", "--like", "--objective", "--pme-criterion", "--ssim-range", "--gt", "--occ-weight"):
+    grad_plain, no_occ = "--grad-plain" in args, "--no-occ" in args
+    grad = "--grad" in args or grad_ft or grad_ssim or grad_plain
+    if ("--grad" in args) + grad_ft + grad_ssim + grad_plain > 1:
+        sys.exit("--grad, --grad-ft, --grad-ssim and --grad-plain exclude one another")
+    args = [a for a in args if a not in ("--size-average", "--grad", "--grad-ft", "--grad-ssim", "--grad-plain", "--no-occ")]
+    plain_criterion = None
+    for flag in ("--scale", "--like", "--objective", "--pme-criterion", "--plain-criterion", "--pme-penalty", "--ssim-range", "--gt", "--occ-weight"):
         if flag in args:
             i = args.index(flag)
             try:
@@ -138,6 +147,10 @@ def main():
                     like = args[i + 1]
                 elif flag == "--pme-criterion":
                     criterion = args[i + 1]
+                elif flag == "--plain-criterion":
+                    plain_criterion = args[i + 1]
+                elif flag == "--pme-penalty":
+                    penalty = args[i + 1]
                 elif flag == "--ssim-range":
                     ssim_range = args[i + 1]
                 elif flag == "--gt":
@@ -152,23 +165,40 @@ def main():
     if len(args) != 2 or like not in ("test", "train"):
         sys.exit(__doc__)
     if objective == "epe":
-        if gt_dir is None or criterion is not None or grad_ft or grad_ssim or like != "test" or not (occ_weight >= 0.0 and np.isfinite(occ_weight)):
+        if gt_dir is None or criterion is not None or plain_criterion is not None or grad_ft or grad_ssim or grad_plain or no_occ or like != "test" or not (occ_weight >= 0.0 and np.isfinite(occ_weight)):
             sys.exit("--objective epe: needs --gt GT_DIR, takes --scale, --occ-weight W >= 0, --size-average and --grad")
         return main_epe(args[0], args[1], gt_dir, scale, occ_weight, size_average, grad)
     if gt_dir is not None or occ_weight != 0.0:
         sys.exit("--gt and --occ-weight go with --objective epe")
     if objective is not None and objective not in back2future.LOSS_OBJECTIVES:
         sys.exit("--objective: epe, or one of " + ", ".join(sorted(back2future.LOSS_OBJECTIVES)))
+    unmasked = ("BCC", "SSIM", "SSIML1")
     if criterion is not None and criterion not in back2future.SSIM_ALPHA:
-        sys.exit("--pme-criterion: one of " + ", ".join(sorted(back2future.SSIM_ALPHA)))
+        sys.exit("--pme-criterion: one of " + ", ".join(sorted(back2future.SSIM_ALPHA)) + " (the criteria that do not mask occlusions: --plain-criterion)")
+    if plain_criterion is not None and plain_criterion not in unmasked:
+        sys.exit("--plain-criterion: one of " + ", ".join(unmasked))
+    if plain_criterion is not None and criterion is not None:
+        sys.exit("--pme-criterion and --plain-criterion exclude one another")
     if ssim_range not in ("image", "batch"):
         sys.exit("--ssim-range: image or batch")
-    if grad_ssim and criterion is None:
+    if grad_ssim and criterion is None and plain_criterion is None:
         criterion = "OSSIML1"
-    if criterion is not None and (objective is not None or (grad and not grad_ssim)):
-        sys.exit("--pme-criterion goes without --objective, --grad and --grad-ft (the gradient of this criterion is that of --grad-ssim)")
+    if grad_plain and plain_criterion is None and criterion is None:
+        plain_criterion = "BCC"
+    plain = plain_criterion is not None
+    if plain:
+        criterion = plain_criterion
+    if penalty not in ("L1", "Quadratic") or (penalty == "Quadratic" and plain_criterion != "BCC"):
+        sys.exit("--pme-penalty: L1, or Quadratic with --plain-criterion BCC")
+    if (grad_plain or no_occ) and not plain:
+        sys.exit("--grad-plain and --no-occ go with --plain-criterion BCC, SSIM or SSIML1")
+    if criterion is not None and (objective is not None or (grad and not (grad_plain if plain else grad_ssim))):
+        sys.exit("--pme-criterion and --plain-criterion go without --objective, --grad and --grad-ft (the gradient of a --pme-criterion is that of "
+                 "--grad-ssim, of a --plain-criterion that of --grad-plain)")
     options = None
-    if grad_ssim:
+    if grad_plain:
+        options = back2future.loss_grad_plain_options(size_average=size_average, pme_criterion=criterion, pme_penalty=penalty, no_occ=no_occ)
+    elif grad_ssim:
         options = back2future.loss_grad_ssim_options(size_average=size_average, pme_criterion=criterion)
     elif grad:
         try:
@@ -198,12 +228,14 @@ def main():
             sumsq = sq if sumsq is None else [a + b for a, b in zip(sumsq, sq)]
             largest = mx if largest is None else [max(a, b) if a == a and b == b else float("nan") for a, b in zip(largest, mx)]
         elif criterion is not None:
-            records.append(m.forwardLoss(x, flow_scale=scale, objective="ssim", ssim_range=ssim_range))
+            records.append(m.forwardLoss(x, flow_scale=scale, objective="plain" if plain else "ssim", ssim_range=ssim_range))
         else:
             records.append(m.forwardLoss(x, flow_scale=scale, objective="pme" if objective is None else "finetune"))
     tensors = ("f", "p", "o", "iw1", "iw3") if m.past_flow else ("f", "o", "iw1", "iw3")
     m.close()
-    if criterion is not None:
+    if plain:
+        s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, pme_criterion=criterion, pme_penalty=penalty, no_occ=no_occ)
+    elif criterion is not None:
         s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, pme_criterion=criterion)
     elif grad_ft and objective is None:     # the defaults of loss_grad_ft_options
         s = back2future.loss_summary(np.concatenate(records), like=like, size_average=size_average, smooth_second_order=True, pme_criterion="OBGCC")

@@ -834,6 +834,92 @@ B2F_API int b2f_forward_loss_grad_ssim_device(b2f_ctx *ctx, const void *dev_in, 
 B2F_API int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
                                      const b2f_loss_grad_ssim_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
                                      int range_mode, const float *ranges);
+/* ---- the photometric terms without occlusion masking: -pme_criterion BCC | SSIM | SSIML1, and -no_occ (b2f_version() >= 1013) ----
+ * opts.lua:62,85, model.lua:149-159: criterions/MBCCriterion.lua and criterions/MSSIML1Criterion.lua, the paper's baseline without
+ * occlusion reasoning.  The *_plain entries return records of 40 words per image and level: words 0 .. 15 are those of
+ * b2f_table_loss*, bit for bit; words 16 .. 29 the sums below; words 30 .. 39 are 0.  Inputs, R_j, the target coordinate, its inside
+ * test and the level scale are those of words 6 .. 9 (MBCCriterion.lua:70-87 and MSSIML1Criterion.lua:120-138 state the test as
+ * OBCCriterion.lua:78-100 does); fp64 without fused multiply-adds, the same P1, D1, q, window G, ge, gc, C1, C2 and t(v) as above.
+ * A pixel-direction whose target leaves the image contributes nothing, in value and in gradient: there is no penalty_out.
+ *   BCC (MBCCriterion.lua:35-102), per direction d and channel c on the raw planes: delta_c = iw_d[c] - R_j[c],
+ *     B1 = (P1(delta_0) + P1(delta_1)) + P1(delta_2)     (-pme_penalty L1, model.lua:189-190)
+ *     B2 = (delta_0^2 + delta_1^2) + delta_2^2           (the criterion's own QuadraticPenalty; -pme_penalty Quadratic)
+ *   SSIM / SSIML1 (MSSIML1Criterion.lua:45-153), on the range-normalised planes x = t(iw_d[c]), y = t(R_j[c]):
+ *     S = sum over c of (1.0 - l * cs), B = sum over c of P1(x_c - y_c), as for the *_ssim entries but without the factor o[1 - d]
+ *   range: MSSIML1Criterion.lua:63-68 runs `for i = 2,#input` and not from warp_start, so (mn, mx) cover R_j, iw1, iw3, AND the two
+ *     occlusion planes, and on Soft tables the two planes of the past flow.  The quirk is kept: the own range of words 28 / 29 is taken
+ *     over those planes.  range_mode and ranges as for the *_ssim entries, with the same refusals.
+ * A pixel-direction that counts in PHOTO_INSIDE adds q(B1) to PLAIN_L1_Q30[d] and q(B2) to PLAIN_SQ_Q30[d] (q saturates at 16), and,
+ * on a usable range and with S and B not NaN, q(S) to PLAIN_SSIM_Q30[d] and q(B) to PLAIN_L1N_Q30[d]; otherwise it adds to neither of
+ * these two and counts in PLAIN_SSIM_NONFINITE[d].  The criterion's value at a level is
+ *   BCC:            sum over d of PLAIN_L1_Q30[d] (or PLAIN_SQ_Q30[d]) / 2^30 / (3 * 2)
+ *   SSIM / SSIML1:  sum over d of (alpha * PLAIN_SSIM_Q30[d] + (1 - alpha) * PLAIN_L1N_Q30[d]) / 2^30 / (3 * 2), alpha = 1 / 0.85
+ * times 1 / (h w) under size_average (back2future.loss_summary, which with no_occ drops the occlusions' smoothness and prior as
+ * train.lua:456 and test.lua:289 do).                                                                                          */
+B2F_API int b2f_table_loss_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                              double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
+B2F_API int b2f_table_loss_plain_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                                double flow_scale, unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges);
+B2F_API int b2f_op_table_loss_plain(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                            double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
+B2F_API int b2f_forward_loss_plain(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                           float **outs, int n_outs, int range_mode, const float *ranges);
+B2F_API int b2f_forward_loss_plain_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                  unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges);
+B2F_API int b2f_multi_forward_loss_plain(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                                 int range_mode, const float *ranges);
+#define B2F_LOSS_PLAIN_L1_Q30 16           /* [2] sum over PHOTO_INSIDE of q(B1), past / future, 2^-30 */
+#define B2F_LOSS_PLAIN_SQ_Q30 18           /* [2] of q(B2) */
+#define B2F_LOSS_PLAIN_SSIM_Q30 20         /* [2] of q(S) */
+#define B2F_LOSS_PLAIN_L1N_Q30 22          /* [2] of q(B) */
+#define B2F_LOSS_PLAIN_SSIM_NONFINITE 24   /* [2] pixel-directions of PHOTO_INSIDE with a NaN S or B or an unusable range */
+#define B2F_LOSS_PLAIN_RANGE_USED 26       /* [2] float bits, zero-extended, of the mn / mx used for this image and level */
+#define B2F_LOSS_PLAIN_RANGE_OWN 28        /* [2] float bits of this image's own minimum / maximum at this level, occlusions included */
+#define B2F_LOSS_PLAIN_WORDS 40            /* words 30 .. 39 are reserved, always 0 */
+/* The gradient with respect to the output table (MBCCriterion.lua:104-186, MSSIML1Criterion.lua:155-261, combined with the other
+ * criteria as train.lua:428-468 does; -no_occ: smooth_occ = prior_occ = 0).  Everything not named is as for the *_grad_ssim entries.
+ *   BCC:   G_iw_d[c] = m_d ? k_p * D1(delta_c) : +0.0    (penalty L1)       or    m_d ? k_p * (2.0 * delta_c) : +0.0    (QUADRATIC)
+ *   SSIM:  G_iw_d[c] = m_d ? k_p * T_c : +0.0, T_c as for the *_grad_ssim entries: quirks 1 - 3 there (centre tap only, gw = gc^2 on
+ *          the border, no 1 / (mx - mn)) hold here too; a term whose weight is exactly 0 is not evaluated
+ *   G_o[c] = k_so * S(o[c],D2) + k_pr * (1.0 - (double)o[1-c]): the photometric criterion gives the occlusions exactly zero
+ *          (gradInput[1]:fill(0)); with both weights 0 the planes are +0.0
+ *   G_f, G_p: the photometric criteria do not reach the flows; those of the *_grad entries, with smooth_second_order of *_grad_ft.   */
+#define B2F_PLAIN_BCC 0
+#define B2F_PLAIN_SSIM 1
+#define B2F_PLAIN_L1 0
+#define B2F_PLAIN_QUADRATIC 1
+typedef struct b2f_loss_grad_plain_opts {
+    double smooth_flow, const_vel, pme, smooth_occ, prior_occ;   /* as b2f_loss_grad_opts */
+    double level_weights[7];
+    int size_average;
+    int smooth_second_order;                                     /* -smooth_second_order: 0 | 1 */
+    int criterion;                                               /* B2F_PLAIN_BCC | B2F_PLAIN_SSIM */
+    int penalty;                                                 /* B2F_PLAIN_L1 | B2F_PLAIN_QUADRATIC; QUADRATIC with BCC only */
+    double ssim_alpha;                                           /* finite, in [0, 1]: 1 is SSIM, 0.85 SSIML1; read with B2F_PLAIN_SSIM */
+} b2f_loss_grad_plain_opts;
+/* b2f_loss_grad_defaults, smooth_second_order = 0, criterion BCC, penalty L1, ssim_alpha = 0.85 */
+B2F_API int b2f_loss_grad_plain_defaults(b2f_loss_grad_plain_opts *opts);
+/* The six *_grad_ssim entries with these options: their checks and refusals, plus a bad criterion or penalty and, where there is a
+ * context, a two_frame model; a refusal writes nothing and launches nothing.  The optional records of the forward entries are the 40
+ * words of b2f_forward_loss_plain.  With B2F_PLAIN_BCC the range is still checked and, where records are asked for, computed.     */
+B2F_API int b2f_table_loss_grad_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                                   double flow_scale, const b2f_loss_grad_plain_opts *opts, float *const *grad, int range_mode,
+                                   const float *ranges);
+B2F_API int b2f_table_loss_grad_plain_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W,
+                                     const float *dev_ref, double flow_scale, const b2f_loss_grad_plain_opts *opts,
+                                     float *const *dev_grad, void *stream, int range_mode, const float *ranges);
+B2F_API int b2f_op_table_loss_grad_plain(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                                 double flow_scale, const b2f_loss_grad_plain_opts *opts, float *const *grad, int range_mode,
+                                 const float *ranges);
+B2F_API int b2f_forward_loss_grad_plain(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale,
+                                const b2f_loss_grad_plain_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                                float *const *outs, int range_mode, const float *ranges);
+B2F_API int b2f_forward_loss_grad_plain_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                       const b2f_loss_grad_plain_opts *opts, unsigned long long *dev_loss, float *const *dev_grad,
+                                       int n_outs, void *stream, int range_mode, const float *ranges);
+B2F_API int b2f_multi_forward_loss_grad_plain(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
+                                      const b2f_loss_grad_plain_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                                      int range_mode, const float *ranges);
 /* ---- the supervised objective: -optimize epe (opts.lua:56; b2f_version() >= 1012) ----
  * The supervised branch of train.lua:295-335 at the output table: the masked end-point error of the future flow of every level against
  * ground truth (criterion = nn.L2Criterion, model.lua:145-146,249-251; criterions/L2Criterion.lua:27-71) as integer records per image

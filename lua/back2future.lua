@@ -239,6 +239,41 @@ int b2f_forward_loss_grad_ssim(b2f_ctx *ctx, const float *x, int n, int H, int W
 int b2f_forward_loss_grad_ssim_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                                       const b2f_loss_grad_ssim_opts *opts, unsigned long long *dev_loss, float *const *dev_grad,
                                       int n_outs, void *stream, int range_mode, const float *ranges);
+int b2f_table_loss_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                              double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
+int b2f_table_loss_plain_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                                double flow_scale, unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges);
+int b2f_op_table_loss_plain(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                            double flow_scale, unsigned long long *loss, int range_mode, const float *ranges);
+int b2f_forward_loss_plain(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                           float **outs, int n_outs, int range_mode, const float *ranges);
+int b2f_forward_loss_plain_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                  unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges);
+typedef struct b2f_loss_grad_plain_opts {
+    double smooth_flow, const_vel, pme, smooth_occ, prior_occ;
+    double level_weights[7];
+    int size_average;
+    int smooth_second_order;
+    int criterion;
+    int penalty;
+    double ssim_alpha;
+} b2f_loss_grad_plain_opts;
+int b2f_loss_grad_plain_defaults(b2f_loss_grad_plain_opts *opts);
+int b2f_table_loss_grad_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                                   double flow_scale, const b2f_loss_grad_plain_opts *opts, float *const *grad, int range_mode,
+                                   const float *ranges);
+int b2f_table_loss_grad_plain_device(b2f_ctx *ctx, const float *const *dev_table, int n_outs, int n, int H, int W,
+                                     const float *dev_ref, double flow_scale, const b2f_loss_grad_plain_opts *opts,
+                                     float *const *dev_grad, void *stream, int range_mode, const float *ranges);
+int b2f_op_table_loss_grad_plain(b2f_ctx *ctx, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                                 double flow_scale, const b2f_loss_grad_plain_opts *opts, float *const *grad, int range_mode,
+                                 const float *ranges);
+int b2f_forward_loss_grad_plain(b2f_ctx *ctx, const float *x, int n, int H, int W, double flow_scale,
+                                const b2f_loss_grad_plain_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                                float *const *outs, int range_mode, const float *ranges);
+int b2f_forward_loss_grad_plain_device(b2f_ctx *ctx, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
+                                       const b2f_loss_grad_plain_opts *opts, unsigned long long *dev_loss, float *const *dev_grad,
+                                       int n_outs, void *stream, int range_mode, const float *ranges);
 typedef struct b2f_loss_epe_opts {
     double epe;
     double occ;
@@ -317,6 +352,11 @@ int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, i
 int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
                                      const b2f_loss_grad_ssim_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
                                      int range_mode, const float *ranges);
+int b2f_multi_forward_loss_plain(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss,
+                                 int range_mode, const float *ranges);
+int b2f_multi_forward_loss_grad_plain(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
+                                      const b2f_loss_grad_plain_opts *opts, unsigned long long *loss, float *const *grad, int n_outs,
+                                      int range_mode, const float *ranges);
 int b2f_multi_forward_loss_epe(b2f_multi *m, const float *x, int n, int H, int W, const float *gt_flow, const unsigned char *valid,
                                const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode,
                                const double *counts, unsigned long long *loss, float *const *grad, int n_outs);
