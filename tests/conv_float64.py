@@ -1,6 +1,7 @@
 """A float64 restatement of the 3x3 convolutions (nn.SpatialConvolution(Ci, Co, 3, 3, s, s, 1, 1) + LeakyReLU(0.2), pwc.lua:58-65,76-85), the
 yardsticks their kernels are held to against it on ANY input, float32 emulations of the algorithms, and the inputs and shapes of the tests
-that use them (tests/test_conv_float64_cpu.py, tests/test_gpu_conv_float64.py).  Helper, no test; numpy / torch on the CPU only.
+that use them (tests/test_conv_float64_cpu.py, tests/test_gpu_conv_float64.py, and the tile-geometry sweep of tests/test_gpu_conv_edges.py:
+GEOMETRY, edge_shapes below).  Helper, no test; numpy / torch on the CPU only.
 
 Yardsticks.  u = 2^-24.  S_direct = conv64(|x|, |w|, |b|): the sum of the absolute products of one output.  S_wino(alg) = the same Winograd
 algorithm evaluated in float64 on absolute values, |A^T| [sum_ci (|G| |g| |G^T|) .* (|B^T| |d| |B|)] |A| + |b| per output tile (zero padding,
@@ -104,10 +105,38 @@ def _mutate_x(x, mutate):
     return x
 
 
+EDGE_MUTATIONS = ("edge-leak", "edge-stale")          # wrong only where the map cuts a tile: see _mutate_halo, _mutate_last_column
+
+
+def ragged(h, w, tile):
+    """(rows, columns): does an h x w OUTPUT map cut its last tile of tile = (th, tw) pixels?"""
+    return h % tile[0] != 0, w % tile[1] != 0
+
+
+def _mutate_halo(xp, H, W, cut, mutate):
+    """edge-leak on the zero-padded input xp (the H x W map at [1 : H + 1, 1 : W + 1]): where the last tile is cut (cut = ragged(...) of the
+    output map), the first out-of-map column / row holds the clamped in-map value -- the last column / row again -- instead of zero, as a
+    loader that clamps its address and forgets the mask leaves it.  The corner stays zero."""
+    if mutate == "edge-leak":
+        if cut[1]:
+            xp[:, :, 1:H + 1, W + 1] = xp[:, :, 1:H + 1, W]
+        if cut[0]:
+            xp[:, :, H + 1, 1:W + 1] = xp[:, :, H, 1:W + 1]
+
+
+def _mutate_last_column(out, cut, mutate):
+    """edge-stale on the output: the last valid column of a cut last tile takes its left neighbour's output (zero in a one-column map), as a
+    store loop that stops one column early leaves it"""
+    if mutate == "edge-stale" and cut[1]:
+        out[..., -1] = out[..., -2] if out.shape[-1] > 1 else 0
+    return out
+
+
 def winograd(x, w, b, alg, mode, leaky=False, mutate=None):
     """The Winograd algorithm alg ('F2', 'F4', 'F6', '1D') at stride 1 on x: B x Ci x H x W.  mode '64': float64 (reproduces conv64);
     'abs': S_wino; '32': the float32 emulation (U = G g G^T in double rounded once, as the packers; transforms rows first; the K sum in
-    channel order, product and sum rounded; bias, then max(v, 0.2f v)).  mutate (mode '32' only): 'bf16' U rounded to bf16, 'tap', 'swap'."""
+    channel order, product and sum rounded; bias, then max(v, 0.2f v)).  mutate (mode '32' only): 'bf16' U rounded to bf16, 'tap', 'swap',
+    and the two of EDGE_MUTATIONS on the algorithm's own tile (m x m; '1D': 1 x 4)."""
     BT, G, AT = matrices(alg)
     m, n = AT.shape
     one_d = alg == "1D"
@@ -121,6 +150,9 @@ def winograd(x, w, b, alg, mode, leaky=False, mutate=None):
     hp = H + 2 if one_d else ty * m + 2
     xp = np.zeros((B, Ci, hp, tx * m + 2), wd)
     xp[:, :, 1:H + 1, 1:W + 1] = xs
+    cut = ragged(H, W, (1 if one_d else m, m))
+    if mode == "32":
+        _mutate_halo(xp, H, W, cut, mutate)
     Gm = np.abs(G) if mode == "abs" else G
     if one_d:
         # V[b, c, r, t, xi] = sum_j BT[xi, j] xp[b, c, r, 4 t + j];  Uk[o, c, ky, xi] = sum_kx G[xi, kx] w[o, c, ky, kx]
@@ -158,7 +190,7 @@ def winograd(x, w, b, alg, mode, leaky=False, mutate=None):
         Y = _lin(AT, _lin(AT, M, 5, mode), 4, mode)                            # columns (in registers) first, then rows
         out = np.moveaxis(Y, 4, 3).reshape(B, Co, ty * m, tx * m)[:, :, :H, :W]
     if mode == "32":
-        v = (out + bs.astype(f32)[None, :, None, None]).astype(f32)
+        v = _mutate_last_column((out + bs.astype(f32)[None, :, None, None]).astype(f32), cut, mutate)
         return np.maximum(v, (f32(0.2) * v).astype(f32)) if leaky else v
     v = out + bs[None, :, None, None]
     return np.where(v > 0, v, 0.2 * v) if (leaky and mode == "64") else v
@@ -168,17 +200,20 @@ def S_wino(x, w, b, alg):
     return winograd(x, w, b, alg, "abs")
 
 
-def direct32(x, w, b, stride=1, leaky=False, mutate=None, bias_first=False):
+def direct32(x, w, b, stride=1, leaky=False, mutate=None, bias_first=False, tile=None):
     """float32 accumulation in channel order (then taps), product and sum rounded: the emulation of the direct kernels.  bias_first: the
     chain starts at the bias instead of ending with it, as conv3x3_mfma's accumulators do (b2f_conv.hip:162-192, "same order as y = b + sum
-    in nn"): every partial sum then carries the bias, and with |b| ~ the output's deviation the rounding of the chain about doubles."""
+    in nn"): every partial sum then carries the bias, and with |b| ~ the output's deviation the rounding of the chain about doubles.
+    tile = (th, tw) of output pixels: what EDGE_MUTATIONS call a tile here (a direct kernel has none of its own; without it they do nothing)."""
     x, w, b = _mutate_x(np.asarray(x, f32), mutate), _mutate_w(np.asarray(w, f32), mutate), np.asarray(b, f32)
     if mutate == "bf16":
         w = _bf16(w)
     B, Ci, H, W = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    cut = ragged(Ho, Wo, tile) if tile else (False, False)
     xp = np.zeros((B, Ci, H + 2, W + 2), f32)
     xp[:, :, 1:-1, 1:-1] = x
+    _mutate_halo(xp, H, W, cut, mutate)
     acc = np.zeros((B, w.shape[0], Ho, Wo), f32)
     if bias_first:
         acc += b[None, :, None, None]
@@ -188,13 +223,13 @@ def direct32(x, w, b, stride=1, leaky=False, mutate=None, bias_first=False):
             for kx in range(3):
                 win = xp[:, c, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride]
                 acc = (acc + (w[None, :, c, ky, kx, None, None] * win[:, None]).astype(f32)).astype(f32)
-    v = (acc + b[None, :, None, None]).astype(f32)
+    v = _mutate_last_column((acc + b[None, :, None, None]).astype(f32), cut, mutate)
     return np.maximum(v, (f32(0.2) * v).astype(f32)) if leaky else v
 
 
-def emulate(alg, x, w, b, stride=1, leaky=False, mutate=None):
+def emulate(alg, x, w, b, stride=1, leaky=False, mutate=None, tile=None):
     if alg in ("direct", "direct-b"):
-        return direct32(x, w, b, stride, leaky, mutate, alg == "direct-b")
+        return direct32(x, w, b, stride, leaky, mutate, alg == "direct-b", tile)
     return winograd(x, w, b, alg, "32", leaky, mutate)
 
 
@@ -333,6 +368,98 @@ EMULATED = {
 EMU_TAG = {"direct": "D1", "direct-b": "D1", "F2": "W2", "F4": "W4", "F6": "W6"}      # the fp32 kernel whose bound the emulation of an algorithm must meet
 SEED = 20
 
+# ---- tile geometry: the sweep of tests/test_gpu_conv_edges.py -------------------------------------------------------------------------------
+# id (CONFIGS of tests/test_gpu_conv_float64.py, 'HEAD', 'F1') -> (th, tw, bh, bw, where it is read), in OUTPUT pixels.  (th, tw): the tile --
+# the Winograd tile, or the finest unit the kernel's inner loop cuts a block into, 1 where it has none; (bh, bw): what one block or work item
+# computes.  UPDATE THIS TABLE when a kernel's tile or footprint changes: the sweep is generated from it.
+GEOMETRY = {
+    # conv3x3_mfma: at these sizes the four-wave forms, 4 x 32 or 8 x 16, whichever pads the map less: unit = what both cut, footprint = their hull
+    "D1": (4, 16, 8, 32, "b2f_conv.hip:42,339-358"), "D2": (4, 16, 8, 32, "b2f_conv.hip:42,339-358"),
+    "N2": (1, 1, 16, 16, "b2f_glue.hip:328,342"),
+    "C16": (1, 16, 16, 32, "b2f_conv16.hip:6-7,30"),                 # 16-pixel M tiles of a row
+    "S16": (1, 16, 4, 32, "b2f_conv16.hip:197-201,210"),
+    "W2": (2, 2, 8, 16, "b2f_wino.hip:29,50"),
+    "W4": (4, 4, 16, 32, "b2f_wino4.hip:19,76"),
+    "W6": (6, 6, 12, 48, "b2f_wino6.hip:20,46"),
+    "V1-1": (1, 4, 16, 32, "b2f_w1b.hip:16,25,55"), "V1-2": (1, 4, 16, 32, "b2f_w1b.hip:16,25,55"),      # F(4,3) along x: tiles of 4 columns
+    "E1": (2, 1, 8, 32, "b2f_convb.hip:12,35"), "E1-direct": (2, 1, 8, 32, "b2f_convb.hip:12,35"),       # a wave owns rows 2 w, 2 w + 1
+    "E2": (2, 1, 8, 32, "b2f_convb.hip:12,35"),
+    "L2": (2, 1, 8, 16, "b2f_s2b.hip:9,13,31"),                      # pixel tiles of 2 rows x 16 columns
+    "HEAD": (1, 16, 16, 30, "b2f_head.hip:8,15,36,299-303"),         # strips of 30 columns in 16-column tiles, cut into row blocks above 16 rows
+    "F1": (1, 1, 8, 32, "b2f_glue.hip:226-227,233"),
+    # experiments build (tools/experiments/csrc); a last n-block of <= 32 outputs of the three split forms is W4's
+    "W4S": (4, 4, 16, 32, "b2f_wino4s.hip:28,50"), "W4H": (4, 4, 16, 32, "b2f_wino4.hip:19,76"),
+    "W2S": (2, 2, 16, 16, "b2f_wino2s.hip:15,46"), "B16": (1, 16, 16, 32, "b2f_conv16b.hip:28"),
+}
+# (Ci, Co) per id: the smallest counts that run the kernel in each of its block forms (choose_kernel, csrc/b2f_api.hip, and the launchers)
+_WIDE_CH = [(32, 64), (32, 32), (32, 96)]          # a 64-output n-block; the 32-output form; one launch holding both.  Ci 32: wino6's four chunks
+EDGE_CHANNELS = {
+    "D1": [(5, 7), (8, 12)],                                         # Co < 16, one N tile: scalar and 16-byte stores (b2f_conv.hip:121)
+    "D2": [(8, 32), (8, 36), (8, 96), (8, 160)],                     # N tiles per block 1, 2 (ragged), 3, 4 x two n-blocks (conv_choose_tiles)
+    "N2": [(8, 2), (40, 2)],                                         # two chunks per pass; four per pass, twice, the second partly (b2f_glue.hip:414)
+    "C16": [(16, 16)], "S16": [(16, 32)], "B16": [(16, 16)],
+    "W2": [(16, 24), (16, 70), (16, 64)],                            # one N tile; a two-tile block + a one-tile remainder; split into 32-output blocks
+    "W4": _WIDE_CH, "W6": _WIDE_CH, "V1-1": _WIDE_CH, "V1-2": _WIDE_CH, "E1": _WIDE_CH, "W4S": _WIDE_CH, "W4H": _WIDE_CH, "W2S": _WIDE_CH,
+    "E1-direct": [(5, 8), (8, 12)],
+    "E2": [(16, 36), (16, 64), (16, 96)],                            # the one-tile kernel alone; the two-tile kernel; both (b2f_convb.hip:288-291)
+    "L2": [(32, 32), (32, 64), (32, 160)],                           # 1, 2 and 5 output tiles of 32: one launch per four (b2f_s2b.hip:359-370)
+    "HEAD": [(16, 32)], "F1": [(3, 16)],
+}
+EDGE_FAMILIES = ("gauss", "dc", "integers")
+
+
+def edge_sizes(t, b):
+    """every residue of the tile (1 .. t + 1), one under / on / one over the footprint, over two footprints, every multiple of 8 below it"""
+    return sorted(s for s in set(range(1, t + 2)) | {b - 1, b, b + 1, 2 * b + 1} | set(range(8, b, 8)) if s > 0)
+
+
+def edge_shapes(th, tw, bh, bw):
+    """OUTPUT sizes (h, w) of the sweep: every height at one column over the footprint, every width at one row over it, and the small corners"""
+    shapes = {(h, bw + 1) for h in edge_sizes(th, bh)} | {(bh + 1, w) for w in edge_sizes(tw, bw)}
+    shapes |= {(h, w) for h in (1, th - 1, th + 1) for w in (1, tw - 1, tw + 1)}
+    return sorted(s for s in shapes if s[0] > 0 and s[1] > 0)
+
+
+def edge_inputs(cid, stride):
+    """[(input H, input W, output h, output w)] of an id's sweep.  Stride 2: both input sizes that give an output size, 2 h - 1 and 2 h (the
+    odd one reads the padding on the right / below, the even one does not); the first layer serves even maps only; the head's sizes are those
+    of its stride-2 output"""
+    out = []
+    for h, w in edge_shapes(*GEOMETRY[cid][:4]):
+        if stride == 1 and cid != "HEAD":
+            out.append((h, w, h, w))
+        else:
+            out += [(2 * h - d, 2 * w - d, h, w) for d in ((0,) if cid == "F1" else (1, 0))]
+    return out
+
+
+def mutation_tile(cid):
+    """the (th, tw) EDGE_MUTATIONS cut for an id: its tile, the footprint in a dimension where the tile is a single pixel"""
+    th, tw, bh, bw = GEOMETRY[cid][:4]
+    return (th if th > 1 else bh, tw if tw > 1 else bw)
+
+
+def border_mask(h, w, th, tw):
+    """h x w bool: the pixels whose tile is ragged or touches the map's edge (the first and last tile row and column)"""
+    ty, tx = np.arange(h) // th, np.arange(w) // tw
+    return ((ty == 0) | (ty == ty[-1]))[:, None] | ((tx == 0) | (tx == tx[-1]))[None, :]
+
+
+def edge_case(family, ci, co, H, W, stride):
+    """(x, w, b, conv64 with LeakyReLU, S_direct) of a sweep shape; not cached: the sweep holds thousands"""
+    x, w, b = make_case(family, SEED, BATCH, ci, co, H, W)
+    return x, w, b, conv64(x, w, b, stride, True), S_direct(x, w, b, stride)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_emulation_case(alg, family, ci, co, H, W, stride, mutate=None, tile=None):
+    """the float32 emulation of an algorithm on a sweep shape: (worst err / (u S of the algorithm), bit-exact against the float64 value --
+    meaningful on `integers` only)"""
+    x, w, b, val, Sd = edge_case(family, ci, co, H, W, stride)
+    got = emulate(alg, x, w, b, stride, True, mutate, tile)
+    S = Sd if alg in ("direct", "direct-b") else S_wino(x, w, b, alg)
+    return measure(got, val, S)[0], bool(np.array_equal(got, round32_leaky(conv64(x, w, b, stride, False), True)))
+
 
 def measure(got, val, S):
     """(worst |got - val| / (u S) over S > 0, its mean, worst |got - val|); a NaN in got gives an infinite ratio"""
@@ -364,16 +491,19 @@ def wino_yardstick(family, shape, alg):
     return s
 
 
+def emulation_n(alg, ci_padded):
+    """n of the float32 emulation of an algorithm: the fp32 kernel's count"""
+    if alg == "1D":
+        return 3 * ci_padded + 8              # the fp32 form of b2f_w1b.hip's algorithm: 3 Ci products, the roundings of ROUNDINGS['V1']
+    return n_roundings(EMU_TAG[alg], ci_padded)
+
+
 def emulation_case(alg, family, shape, stride, mutate=None):
     """One emulation run: (worst err / (u S_direct), worst err / (u S of the algorithm), n of the fp32 kernel, exact zeros hold)"""
     x, w, b, val, Sd = reference(family, shape, stride)
     got = emulate(alg, x, w, b, stride, True, mutate)
     Sa = Sd if alg in ("direct", "direct-b") else wino_yardstick(family, shape, alg)
-    if alg == "1D":
-        n = 3 * padded(shape[0]) + 8          # the fp32 form of b2f_w1b.hip's algorithm: 3 Ci products, the roundings of ROUNDINGS['V1']
-    else:
-        n = n_roundings(EMU_TAG[alg], padded(shape[0]))
-    return measure(got, val, Sd)[0], measure(got, val, Sa)[0], n
+    return measure(got, val, Sd)[0], measure(got, val, Sa)[0], emulation_n(alg, padded(shape[0]))
 
 
 def head_case(family, H, W):

@@ -3,7 +3,11 @@
 The float64 Winograd of every algorithm reproduces conv64 (the matrices are right); the float32 emulation of every algorithm stays inside
 bound() on every family and every shape the GPU file runs (the reference alone meets the bar) and its worst err / (u S_direct) per algorithm
 and family is the recorded table the GPU file reads; three mutations of the emulation -- U rounded to bf16, one tap dropped, two input
-channels of a chunk swapped -- turn the check red; S = 0 gives exactly 0 and an all-zero image exactly the bias."""
+channels of a chunk swapped -- turn the check red; S = 0 gives exactly 0 and an all-zero image exactly the bias.  The tile-geometry sweep
+of tests/test_gpu_conv_edges.py: the shapes generated from conv_float64.GEOMETRY hold every residue and block edge, the emulations meet
+the bound on them, and two mutations confined to a ragged last tile (edge-leak, edge-stale) fail it exactly where a tile is ragged."""
+import os
+
 import numpy as np
 import pytest
 
@@ -108,6 +112,140 @@ def test_integers_are_exact_on_the_dyadic_paths():
         assert (exact.astype(np.float32).astype(np.float64) == exact).all()
         for leaky in (False, True):
             np.testing.assert_array_equal(F.emulate(alg, x, w, b, stride, leaky), F.round32_leaky(exact, leaky), err_msg=alg)
+
+
+# ---- the tile-geometry sweep (conv_float64.GEOMETRY, edge_shapes): what tests/test_gpu_conv_edges.py runs on the GPU --------------------------
+
+def _edge_ids():
+    from tests.test_gpu_conv_float64 import CONFIGS
+    # id -> (tag of ROUNDINGS, stride); the split forms of the experiments build carry W4's profile tag and a count of their own
+    return {**{cid: (cid if cid in ("W4S", "W4H", "W2S") else c[0], c[1]) for cid, c in CONFIGS.items()}, "HEAD": ("HEAD", 2), "F1": ("F1", 2)}
+
+
+EDGE_IDS = _edge_ids()
+SWEPT = [cid for cid in EDGE_IDS if cid != "HEAD"]          # the head's emulation is two chained convolutions: its own test below
+
+
+def _edge_alg_tile_n(cid):
+    """(emulation algorithm, the tile the edge mutations cut, n) of an id on its first channel configuration"""
+    tag = EDGE_IDS[cid][0]
+    alg = F.emulation_of(tag)
+    cp = 3 if cid == "F1" else F.padded(F.EDGE_CHANNELS[cid][0][0])
+    th, tw = F.GEOMETRY[cid][:2]
+    if alg in WINO:
+        m = F.matrices(alg)[2].shape[0]
+        assert (th, tw) == ((1, m) if alg == "1D" else (m, m)), "GEOMETRY[%s]: not the tile of %s" % (cid, alg)
+        tile = (th, tw)
+    else:
+        tile = F.mutation_tile(cid)
+    return alg, tile, min(F.n_roundings(tag, cp), F.emulation_n(alg, cp))
+
+
+def test_geometry_table_names_every_kernel_and_cites_its_source():
+    assert set(F.GEOMETRY) == set(EDGE_IDS) == set(F.EDGE_CHANNELS)
+    for cid, (th, tw, bh, bw, where) in F.GEOMETRY.items():
+        assert 1 <= th <= bh and 1 <= tw <= bw, cid
+        name, lines = where.split(":")
+        paths = [os.path.join(F.ROOT, d, name) for d in ("back2future_amd/csrc", "tools/experiments/csrc")]
+        path = [p for p in paths if os.path.exists(p)]
+        assert path, "%s: no %s" % (cid, name)
+        with open(path[0]) as f:
+            n_lines = len(f.readlines())
+        assert all(1 <= int(x) <= n_lines for part in lines.split(",") for x in part.split("-")), (cid, where)
+        assert all(1 <= ci <= 40 and co >= 1 for ci, co in F.EDGE_CHANNELS[cid]), cid
+    assert {co for _, co in F.EDGE_CHANNELS["W4"]} >= {32, 64, 96}          # a 64-output block, the 32-output form, one launch with both
+
+
+@pytest.mark.parametrize("cid", sorted(EDGE_IDS))
+def test_sweep_covers_every_residue_and_block_edge(cid):
+    th, tw, bh, bw, _ = F.GEOMETRY[cid]
+    shapes = F.edge_shapes(th, tw, bh, bw)
+    assert len(shapes) == len(set(shapes)) and all(h > 0 and w > 0 for h, w in shapes)
+    for sizes, t, b in (({h for h, _ in shapes}, th, bh), ({w for _, w in shapes}, tw, bw)):
+        assert {s % t for s in sizes} == set(range(t)), "%s: a residue mod %d never runs" % (cid, t)
+        assert {s for s in (b - 1, b, b + 1) if s > 0} <= sizes, "%s: one under / on / one over %d" % (cid, b)
+        assert any(s > 2 * b for s in sizes), "%s: nothing over two blocks of %d" % (cid, b)
+        assert set(range(8, b, 8)) <= sizes, "%s: a multiple of 8 below %d is missing" % (cid, b)
+    assert max(h for h, _ in shapes) == 2 * bh + 1 and max(w for _, w in shapes) == 2 * bw + 1          # nothing larger than two footprints
+    stride = EDGE_IDS[cid][1]
+    inputs = F.edge_inputs(cid, stride)
+    assert {(h, w) for _, _, h, w in inputs} == set(shapes)
+    for H, W, h, w in inputs:
+        assert ((H - 1) // stride + 1, (W - 1) // stride + 1) == (h, w) or cid == "HEAD"
+        if cid == "HEAD":
+            assert ((H - 1) // 2 + 1, (W - 1) // 2 + 1) == (h, w)
+    if stride == 2:
+        assert {(H % 2, W % 2) for H, W, _, _ in inputs} == ({(0, 0)} if cid == "F1" else {(0, 0), (1, 1)})
+
+
+@pytest.mark.parametrize("cid", SWEPT)
+def test_emulation_meets_the_bound_on_the_sweep(cid):
+    """the reference alone stays inside n u S on every sweep shape (gauss, dc, integers), bit-exact on integers on the dyadic paths"""
+    alg, _, n = _edge_alg_tile_n(cid)
+    stride = EDGE_IDS[cid][1]
+    ci, co = F.EDGE_CHANNELS[cid][0]
+    failures, worst = [], 0.0
+    for H, W, h, w in F.edge_inputs(cid, stride):
+        for family in F.EDGE_FAMILIES:
+            r, exact = F.edge_emulation_case(alg, family, ci, co, H, W, stride)
+            worst = max(worst, r)
+            if not r <= n:
+                failures.append("%s %s %s %dx%d: err = %.2f u S, bound n = %d" % (cid, alg, family, H, W, r, n))
+            if family == "integers" and alg in ("direct", "direct-b", "F2") and not exact:
+                failures.append("%s %s integers %dx%d: not bit-exact" % (cid, alg, H, W))
+    print("%-10s %-8s worst err / (u S) = %8.3f (n = %d)" % (cid, alg, worst, n))
+    assert not failures, "\n".join(failures)
+
+
+def test_head_emulation_meets_its_bound_on_the_sweep():
+    failures = []
+    for H, W, h, w in F.edge_inputs("HEAD", 2):
+        for family in F.EDGE_FAMILIES:
+            x, w1, b1, w2, b2 = F.head_case(family, H, W)
+            got = F.direct32(F.direct32(x, w1, b1, 1, True), w2, b2, 2, True)
+            assert got.shape[2:] == (h, w)
+            r_bound = F.head_measure(got, x, w1, b1, w2, b2)[2]
+            if not r_bound <= 1.0:
+                failures.append("head %s %dx%d: the emulation is at %.3f of the bound" % (family, H, W, r_bound))
+            if family == "integers":
+                t = F.conv64(x, w1, b1, 1, False)
+                if t.min() < 0 or not np.array_equal(got, F.round32_leaky(F.conv64(t, w2, b2, 2, False), True)):
+                    failures.append("head integers %dx%d: not bit-exact" % (H, W))
+    assert not failures, "\n".join(failures)
+
+
+def _edge_mutation_shows(mutate, cut, H, W, stride):
+    """does the mutation change a valid output?  edge-leak at stride 2: only where the input size is odd -- the last output of an even map
+    never reads past it"""
+    if mutate == "edge-stale":
+        return cut[1]
+    return (cut[0] and (stride == 1 or H % 2 == 1)) or (cut[1] and (stride == 1 or W % 2 == 1))
+
+
+@pytest.mark.parametrize("mutate", F.EDGE_MUTATIONS)
+@pytest.mark.parametrize("cid", SWEPT)
+def test_edge_mutations_turn_the_check_red_only_where_a_tile_is_ragged(cid, mutate):
+    """an error confined to a ragged last tile fails the bound on every sweep shape that has one (in that dimension), gauss and dc; where
+    no tile is ragged the mutation changes nothing"""
+    alg, tile, n = _edge_alg_tile_n(cid)
+    stride = EDGE_IDS[cid][1]
+    ci, co = F.EDGE_CHANNELS[cid][0]
+    failures, red, green = [], 0, 0
+    for H, W, h, w in F.edge_inputs(cid, stride):
+        shows = _edge_mutation_shows(mutate, F.ragged(h, w, tile), H, W, stride)
+        for family in ("gauss", "dc"):
+            good = F.edge_emulation_case(alg, family, ci, co, H, W, stride)[0]
+            bad = F.edge_emulation_case(alg, family, ci, co, H, W, stride, mutate, tile)[0]
+            if shows and not bad > n:
+                failures.append("%s %s %s %dx%d: err = %.2f u S passes n = %d" % (cid, mutate, family, H, W, bad, n))
+            if not shows and not (bad == good and good <= n):
+                failures.append("%s %s %s %dx%d: no ragged tile, yet err = %.2f u S against %.2f" % (cid, mutate, family, H, W, bad, good))
+        red, green = red + shows, green + (not shows)
+    # (edge-leak at stride 1 has no green shape: the sweep holds every height at a ragged width and every width at a ragged height)
+    # and none red on the first layer: it serves even maps only, whose last output never reads past the map)
+    assert red > 0 or (mutate == "edge-leak" and cid == "F1"), (cid, mutate, red, green)
+    assert green > 0 or (mutate == "edge-leak" and stride == 1), (cid, mutate, red, green)
+    assert not failures, "%d failures:\n" % len(failures) + "\n".join(failures)
 
 
 def test_normalised_first_layer_emulation_meets_its_bound_and_is_the_recorded_table():
