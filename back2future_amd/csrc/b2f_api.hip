@@ -1512,18 +1512,19 @@ B2F_CATCH("b2f_forward")
 
 }  // extern "C"
 
-// ---- model:forward followed by the unsupervised validation loss of test.lua:266-297 -------------------------------
+// ---- model:forward followed by an objective of the table-loss family (b2f_ctx.h: LossSpec) --------
+// Every b2f_forward_loss* entry builds the descriptor of its objective and outputs and calls forward_loss_host or forward_loss_device;
+// both cut the request into sub-batches, and forward_loss_run hands each one's table to table_loss_dispatch (b2f_tableloss.hip).
 namespace {
 
 // what a b2f_forward_loss* call needs from the context's loss workspace for sub-batches of nb triplets
 struct LossPlan {
     int L = 0, per = 0, n_outs = 0;
-    LossKind kind;                  // of a record: words, and the range of the SSIM sums
-    int words = B2F_LOSS_WORDS;     // kind.words: B2F_LOSS_FT_WORDS with the fine-tuning terms of README.md:89-102, B2F_LOSS_SSIM_WORDS with OSSIML1Criterion's
+    int words = B2F_LOSS_WORDS;     // of a record of the objective (LossSpec::words)
     std::vector<size_t> cnt, off;   // floats and byte offset of every tensor of the table
-    std::vector<size_t> goff;       // byte offset of every tensor of the gradient table (b2f_forward_loss_grad only)
+    std::vector<size_t> goff;       // byte offset of every tensor of the gradient table (with_grad)
     size_t in_off = 0, loss_off = 0, bytes = 0;
-    size_t gt_off = 0, valid_off = 0, occ_off = 0;   // the ground truth of a sub-batch (b2f_forward_loss_epe only)
+    size_t gt_off = 0, valid_off = 0, occ_off = 0;   // the ground truth of a sub-batch (kLossEpe from host memory)
 };
 
 int check_forward_loss(const b2f_ctx *c, const std::string &w, int n, int H, int W, double flow_scale)
@@ -1538,11 +1539,12 @@ int check_forward_loss(const b2f_ctx *c, const std::string &w, int n, int H, int
     return 0;
 }
 
-LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input, const LossKind &kind, bool with_grad = false, bool with_truth = false)
+// from_host: the sub-batch's frames, and kLossEpe's ground truth, are uploaded into the workspace; with_grad: so is the gradient table kept there
+LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, const LossSpec &d, bool from_host, bool with_grad)
 {
+    const bool with_input = from_host, with_truth = from_host && d.is_epe();
     LossPlan p;
-    p.kind = kind;
-    p.words = kind.words;
+    p.words = d.words();
     p.per = c->past_flow ? 5 : 4;
     p.n_outs = c->g.n_outputs();
     p.L = p.n_outs / p.per;
@@ -1553,8 +1555,7 @@ LossPlan make_loss_plan(const b2f_ctx *c, int nb, int H, int W, bool with_input,
     p.valid_off = take(with_truth ? (size_t)nb * H * W : 0);
     p.occ_off = take(with_truth ? (size_t)nb * H * W : 0);
     for (int i = 0; i < p.n_outs; ++i) {
-        const int j = i / p.per, ch = (i % p.per) >= p.per - 2 ? 3 : 2;
-        p.cnt.push_back((size_t)nb * ch * (H >> j) * (W >> j));
+        p.cnt.push_back(table_floats(i, p.per, nb, H, W));
         p.off.push_back(take(p.cnt.back() * sizeof(float)));
     }
     p.loss_off = take((size_t)nb * p.L * p.words * sizeof(unsigned long long));
@@ -1587,20 +1588,15 @@ int forward_table_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int 
     return 0;
 }
 
-// the table of nb triplets into tab, its records into d_loss where wanted (else nullptr), its gradient table (train.lua:428-468) from the
-// checked options *o into grad where wanted; all on s.  The pyramid of R is built once: by the records' launch where there is one.
-// epe: the supervised objective of train.lua:296-334 instead, against the device ground truth of these nb triplets (o is not read).
-int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const GradOpts *o, const LossPlan &lp,
-                     float *const *tab, unsigned long long *d_loss, float *const *grad, const EpeArgs *epe = nullptr)
+// the table of nb triplets into tab, then the objective of the resolved d on it: its records into d_loss and its gradient table into grad,
+// each where wanted (else nullptr); all on s.  The reference image is the centre frame; d's ground truth is the device memory of these nb
+// triplets.
+int forward_loss_run(b2f_ctx *c, hipStream_t s, const float *d_in, int nb, int H, int W, double flow_scale, const LossSpec &d, const LossPlan &lp,
+                     float *const *tab, unsigned long long *d_loss, float *const *grad)
 {
     CHK(forward_table_run(c, s, d_in, nb, H, W, lp, tab));
-    if (epe)
-        return table_loss_epe_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, epe->gt_flow, epe->valid, epe->gt_occ, flow_scale, epe->o, epe->count_mode,
-                                  epe->counts, d_loss);
     const size_t hw = (size_t)H * W;
-    if (d_loss) CHK(table_loss_run(c, s, tab, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, d_loss, lp.kind));
-    if (grad) CHK(table_loss_grad_run(c, s, tab, grad, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale, *o, d_loss));
-    return 0;
+    return table_loss_dispatch(c, s, tab, grad, d_loss, d, lp.L, c->past_flow, nb, H, W, d_in + 3 * hw, 9 * hw, flow_scale);
 }
 
 // triplets per sub-batch of a b2f_forward_loss* call: the host_subbatch_pixels budget, within the launchers' limit of images
@@ -1611,12 +1607,12 @@ int loss_subbatch(const b2f_ctx *c, int n, int H, int W)
 
 // what b2f_forward_loss_ssim* check beyond check_forward_loss: the range, and that the batch's range is asked of one sub-batch only (a
 // record would depend on where the request is cut otherwise)
-int check_forward_loss_kind(const b2f_ctx *c, const std::string &w, const LossKind &k, int n, int H, int W)
+int check_forward_loss_kind(const b2f_ctx *c, const std::string &w, const LossSpec &d, int n, int H, int W)
 {
-    if (!k.ranged()) return 0;
-    const char *why = ssim_range_refusal(k.range_mode, k.ranges);
+    if (!d.ranged()) return 0;
+    const char *why = d.range_refusal();
     if (why) return fail(w + ": " + why);
-    if (k.range_mode == B2F_SSIM_RANGE_BATCH && loss_subbatch(c, n, H, W) < n)
+    if (d.range_mode == B2F_SSIM_RANGE_BATCH && loss_subbatch(c, n, H, W) < n)
         return fail(w + ": B2F_SSIM_RANGE_BATCH needs the request in one sub-batch and this one would be cut (host_subbatch_pixels): use "
                         "B2F_SSIM_RANGE_IMAGE or B2F_SSIM_RANGE_GIVEN, which do not depend on the cut");
     return 0;
@@ -1633,16 +1629,40 @@ int loss_work_tables(b2f_ctx *c, const LossPlan &lp, std::vector<float *> &tab, 
     return 0;
 }
 
-// what b2f_forward_loss_grad* check beyond check_forward_loss: the options (into *o) and the gradient table's pointers
-int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, const GradArgs &a, float *const *grad, int n_outs, GradOpts *o)
+// what the b2f_forward_loss_grad* and b2f_forward_loss_epe* entries check beyond check_forward_loss: d.resolve -- the supervised objective
+// in front of the gradient table's pointers, the others behind them --, and those pointers where there is a gradient table
+int check_forward_loss_grad(const b2f_ctx *c, const std::string &w, LossSpec &d, float *const *grad, int n_outs)
 {
-    if (n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
-    for (int i = 0; i < n_outs; ++i) {
+    const char *why = d.is_epe() ? d.resolve(c->g.n_outputs() / (c->past_flow ? 5 : 4)) : nullptr;
+    if (why) return fail(w + ": " + why);
+    if (grad && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
+    for (int i = 0; grad && i < n_outs; ++i) {
         if (!grad[i]) return fail(w + ": null tensor in the gradient table");
+        if (d.is_epe() && ((const void *)grad[i] == (const void *)d.gt_flow || (const void *)grad[i] == (const void *)d.valid || (const void *)grad[i] == (const void *)d.gt_occ))
+            return fail(w + ": the gradient table must not alias the ground truth");
         for (int k = 0; k < i; ++k)
             if (grad[i] == grad[k]) return fail(w + ": the gradient table must not alias itself");
     }
-    return resolve_grad_opts(w, a, o);
+    if (!d.is_epe() && (why = d.resolve(0))) return fail(w + ": " + why);
+    return 0;
+}
+
+// kLossEpe from host memory with size_average, a gradient table and the batch's counts, on a request that is cut: N_j, N'_j over the
+// caller's whole n first, into `whole`, and given to every sub-batch -- the cut changes nothing
+void whole_request_counts(const b2f_ctx *c, LossSpec &d, bool with_grad, int n, int H, int W, std::vector<double> &whole)
+{
+    if (!d.is_epe() || !with_grad || !d.epe.size_average || d.count_mode != B2F_EPE_COUNT_BATCH || loss_subbatch(c, n, H, W) >= n) return;
+    const int L = c->g.n_outputs() / (c->past_flow ? 5 : 4);
+    std::vector<unsigned long long> cnt((size_t)n * L * 2);
+    epe_counts_host(d.valid, d.epe.occ > 0.0 ? d.gt_occ : nullptr, L, n, H, W, cnt.data());
+    whole.assign((size_t)L * 2, 0.0);
+    for (int j = 0; j < 2 * L; ++j) {
+        unsigned long long all = 0;
+        for (int b = 0; b < n; ++b) all += cnt[(size_t)b * L * 2 + j];
+        whole[(size_t)j] = (double)all;
+    }
+    d.count_mode = B2F_EPE_COUNT_GIVEN;
+    d.counts = whole.data();
 }
 
 struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub-batches run (b2f_ctx::req_batch)
@@ -1651,16 +1671,16 @@ struct ReqBatchScope {   // the kernel rule follows the caller's n while its sub
     ~ReqBatchScope() { c->req_batch = 0; }
 };
 
-// the sub-batch loop of b2f_forward_loss* and b2f_forward_loss_grad* on checked arguments: upload, forward_loss_run, download of the
-// records (loss), the gradient table (grad, from *o) and the table (outs), each where not null
-// epe: the supervised objective instead, against host ground truth of the n triplets, uploaded with the frames of each sub-batch
-int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const LossKind &k, const GradOpts *o,
-                          unsigned long long *loss, float *const *grad, float *const *outs, const EpeArgs *epe = nullptr)
+// the sub-batch loop of the b2f_forward_loss* entries of every objective on checked arguments: upload, forward_loss_run, download of the
+// records (loss), the gradient table (grad) and the table (outs), each where not null.  kLossEpe: the host ground truth of the n triplets
+// is uploaded with the frames of each sub-batch.
+int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const LossSpec &d, unsigned long long *loss,
+                          float *const *grad, float *const *outs)
 {
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
     const int sb = loss_subbatch(c, n, H, W);
-    const LossPlan lp = make_loss_plan(c, sb, H, W, true, k, grad != nullptr, epe != nullptr);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, d, true, grad != nullptr);
     std::vector<float *> tab, gr;
     CHK(loss_work_tables(c, lp, tab, grad ? &gr : nullptr));
     float *d_in = (float *)(c->loss_work.dev + lp.in_off);
@@ -1670,20 +1690,20 @@ int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int
     for (int b0 = 0; b0 < n; b0 += sb) {
         const int nb = std::min(sb, n - b0);
         HIPCHK(hipMemcpyAsync(d_in, x + (size_t)b0 * 9 * hw, (size_t)nb * 9 * hw * sizeof(float), hipMemcpyHostToDevice, s));
-        EpeArgs de;
-        if (epe) {   // the sub-batch's ground truth, behind its frames on the same stream
-            de = *epe;
+        LossSpec dd = d;
+        if (d.is_epe()) {   // the sub-batch's ground truth, behind its frames on the same stream
+            const LossSpec h = d.at_image((size_t)b0, hw);
             float *d_gt = (float *)(c->loss_work.dev + lp.gt_off);
             unsigned char *d_valid = (unsigned char *)(c->loss_work.dev + lp.valid_off), *d_occ = (unsigned char *)(c->loss_work.dev + lp.occ_off);
-            HIPCHK(hipMemcpyAsync(d_gt, epe->gt_flow + (size_t)b0 * 2 * hw, (size_t)nb * 2 * hw * sizeof(float), hipMemcpyHostToDevice, s));
-            if (epe->valid) HIPCHK(hipMemcpyAsync(d_valid, epe->valid + (size_t)b0 * hw, (size_t)nb * hw, hipMemcpyHostToDevice, s));
-            if (epe->gt_occ) HIPCHK(hipMemcpyAsync(d_occ, epe->gt_occ + (size_t)b0 * hw, (size_t)nb * hw, hipMemcpyHostToDevice, s));
-            de.gt_flow = d_gt;
-            de.valid = epe->valid ? d_valid : nullptr;
-            de.gt_occ = epe->gt_occ ? d_occ : nullptr;
+            HIPCHK(hipMemcpyAsync(d_gt, h.gt_flow, (size_t)nb * 2 * hw * sizeof(float), hipMemcpyHostToDevice, s));
+            if (h.valid) HIPCHK(hipMemcpyAsync(d_valid, h.valid, (size_t)nb * hw, hipMemcpyHostToDevice, s));
+            if (h.gt_occ) HIPCHK(hipMemcpyAsync(d_occ, h.gt_occ, (size_t)nb * hw, hipMemcpyHostToDevice, s));
+            dd.gt_flow = d_gt;
+            dd.valid = h.valid ? d_valid : nullptr;
+            dd.gt_occ = h.gt_occ ? d_occ : nullptr;
         }
         // (a shorter last sub-batch lays its tensors out for nb images in the same buffers)
-        CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, o, lp, tab.data(), d_loss, grad ? gr.data() : nullptr, epe ? &de : nullptr));
+        CHK(forward_loss_run(c, s, d_in, nb, H, W, flow_scale, dd, lp, tab.data(), d_loss, grad ? gr.data() : nullptr));
         if (loss)
             HIPCHK(hipMemcpyAsync(loss + (size_t)b0 * lp.L * lp.words, d_loss, (size_t)nb * lp.L * lp.words * sizeof(unsigned long long),
                                   hipMemcpyDeviceToHost, s));
@@ -1699,100 +1719,32 @@ int forward_loss_host_run(b2f_ctx *c, const float *x, int n, int req, int H, int
 
 }  // namespace
 
-// b2f_forward_loss on a shard: `req` is the caller's n (b2f_multi_forward_loss passes its own down)
-int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
-                           const LossKind &k)
+// the b2f_forward_loss* entries of every objective from host memory, and a shard of theirs: `req` is the caller's n
+int b2f::forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, LossSpec d, unsigned long long *loss, float *const *grad,
+                           int n_outs, float *const *outs)
 {
-    const std::string w = std::string("b2f_forward_loss") + k.suffix();
-    if (!c || !x || !loss) return fail(w + ": null argument");
-    CHK(check_forward_loss(c, w, n, H, W, flow_scale));
-    CHK(check_forward_loss_kind(c, w, k, n, H, W));
-    if ((outs == nullptr) != (n_outs == 0)) return fail(w + ": outs and n_outs go together (NULL and 0: the table is not downloaded)");
-    if (outs && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be 0 or (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
-    for (int i = 0; i < n_outs; ++i)
-        if (!outs[i]) return fail(w + ": null tensor in outs");
-    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, k, nullptr, loss, nullptr, outs);
-}
-
-// b2f_forward_loss_grad, b2f_forward_loss_grad_ft or b2f_forward_loss_grad_ssim on a shard: `req` is the caller's n
-// (b2f_multi_forward_loss_grad* pass their own down)
-int b2f::forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const GradArgs &a, unsigned long long *loss,
-                                float *const *grad, int n_outs, float *const *outs)
-{
-    const std::string w = std::string("b2f_forward_loss") + a.suffix();
-    if (!c || !x || !grad) return fail(w + ": null argument");
-    CHK(check_forward_loss(c, w, n, H, W, flow_scale));
-    CHK(check_forward_loss_kind(c, w, a.rec(), n, H, W));
-    GradOpts o;
-    CHK(check_forward_loss_grad(c, w, a, grad, n_outs, &o));
-    for (int i = 0; outs && i < n_outs; ++i) {
-        if (!outs[i]) return fail(w + ": null tensor in outs");
-        for (int k = 0; k < n_outs; ++k)
-            if (outs[i] == grad[k]) return fail(w + ": the gradient table must not alias outs");
-    }
-    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, o.rec, &o, loss, grad, outs);
-}
-
-namespace {
-
-// what the b2f_forward_loss_epe* entries check beyond check_forward_loss: the options (into e->o), the ground truth, the counts and the
-// optional gradient table's pointers
-int check_forward_loss_epe(const b2f_ctx *c, const std::string &w, const b2f_loss_epe_opts *opts, float *const *grad, int n_outs, EpeArgs *e)
-{
-    if (opts) e->o = *opts;
-    else (void)b2f_loss_epe_defaults(&e->o);
-    const int L = c->g.n_outputs() / (c->past_flow ? 5 : 4);
-    const char *why = loss_epe_refusal(e->o, e->gt_flow, e->gt_occ, e->count_mode, e->counts, L);
+    const std::string w = std::string("b2f_forward_loss") + d.suffix();
+    const char *why = !c || !x ? "null argument" : d.outputs_refusal(loss, grad);
     if (why) return fail(w + ": " + why);
-    if (!grad) return 0;
-    if (n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
-    for (int i = 0; i < n_outs; ++i) {
-        if (!grad[i]) return fail(w + ": null tensor in the gradient table");
-        if ((const void *)grad[i] == (const void *)e->gt_flow || (const void *)grad[i] == (const void *)e->valid || (const void *)grad[i] == (const void *)e->gt_occ)
-            return fail(w + ": the gradient table must not alias the ground truth");
-        for (int k = 0; k < i; ++k)
-            if (grad[i] == grad[k]) return fail(w + ": the gradient table must not alias itself");
-    }
-    return 0;
-}
-
-const LossKind kEpeRecords = LossKind{B2F_LOSS_EPE_WORDS, 0, nullptr};
-
-}  // namespace
-
-// b2f_forward_loss_epe on a shard: `req` is the caller's n (b2f_multi_forward_loss_epe passes its own down, and counts of its own)
-int b2f::forward_loss_epe_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, const float *gt_flow, const unsigned char *valid,
-                               const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
-                               unsigned long long *loss, float *const *grad, int n_outs, float *const *outs)
-{
-    const std::string w = "b2f_forward_loss_epe";
-    if (!c || !x) return fail(w + ": null argument");
-    if (!loss && !grad) return fail(w + ": loss and grad are both null: nothing to compute");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
-    EpeArgs e = {gt_flow, valid, gt_occ, {}, count_mode, counts};
-    CHK(check_forward_loss_epe(c, w, opts, grad, n_outs, &e));
-    if (!grad && outs && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
-    for (int i = 0; outs && i < n_outs; ++i) {
-        if (!outs[i]) return fail(w + ": null tensor in outs");
-        for (int k = 0; grad && k < n_outs; ++k)
-            if (outs[i] == grad[k]) return fail(w + ": the gradient table must not alias outs");
-    }
-    // N_j, N'_j of the batch over the caller's whole n first: a cut into sub-batches changes nothing
-    const int L = c->g.n_outputs() / (c->past_flow ? 5 : 4);
-    std::vector<double> whole;
-    if (grad && e.o.size_average && count_mode == B2F_EPE_COUNT_BATCH && loss_subbatch(c, n, H, W) < n) {
-        std::vector<unsigned long long> cnt((size_t)n * L * 2);
-        epe_counts_host(valid, e.o.occ > 0.0 ? gt_occ : nullptr, L, n, H, W, cnt.data());
-        whole.assign((size_t)L * 2, 0.0);
-        for (int j = 0; j < 2 * L; ++j) {
-            unsigned long long all = 0;
-            for (int b = 0; b < n; ++b) all += cnt[(size_t)b * L * 2 + j];
-            whole[(size_t)j] = (double)all;
+    CHK(check_forward_loss_kind(c, w, d, n, H, W));
+    if (!d.is_epe() && !d.grad_entry) {   // the records alone: the table is downloaded with n_outs, or not at all
+        if ((outs == nullptr) != (n_outs == 0)) return fail(w + ": outs and n_outs go together (NULL and 0: the table is not downloaded)");
+        if (outs && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be 0 or (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
+        for (int i = 0; i < n_outs; ++i)
+            if (!outs[i]) return fail(w + ": null tensor in outs");
+    } else {
+        CHK(check_forward_loss_grad(c, w, d, grad, n_outs));
+        if (!grad && outs && n_outs != c->g.n_outputs()) return fail(w + ": n_outs must be (levels - skip) x 4 (5 with past-flow decoders): 20 / 25 for the shipped models");
+        for (int i = 0; outs && i < n_outs; ++i) {
+            if (!outs[i]) return fail(w + ": null tensor in outs");
+            for (int k = 0; grad && k < n_outs; ++k)
+                if (outs[i] == grad[k]) return fail(w + ": the gradient table must not alias outs");
         }
-        e.count_mode = B2F_EPE_COUNT_GIVEN;
-        e.counts = whole.data();
     }
-    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, kEpeRecords, nullptr, loss, grad, outs, &e);
+    std::vector<double> whole;
+    whole_request_counts(c, d, grad != nullptr, n, H, W, whole);
+    return forward_loss_host_run(c, x, n, req, H, W, flow_scale, d, loss, grad, outs);
 }
 
 extern "C" {
@@ -1801,7 +1753,7 @@ extern "C" {
 int b2f_forward_loss_grad(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts, unsigned long long *loss,
                           float *const *grad, int n_outs, float *const *outs) try
 {
-    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, grad_args(opts), loss, grad, n_outs, outs);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_grad(opts), loss, grad, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_grad")
 
@@ -1809,56 +1761,40 @@ B2F_CATCH("b2f_forward_loss_grad")
 int b2f_forward_loss_grad_ft(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ft_opts *opts,
                              unsigned long long *loss, float *const *grad, int n_outs, float *const *outs) try
 {
-    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, grad_args(opts), loss, grad, n_outs, outs);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_grad(opts), loss, grad, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_grad_ft")
 
 extern "C++" {
-// the six device entries: b2f_forward_loss_device / _ft_device / _ssim_device (a == nullptr: dev_loss required, no gradient table; k:
-// which records) and b2f_forward_loss_grad_device / _grad_ft_device / _grad_ssim_device (a: dev_grad required, dev_loss optional, k = a->rec())
-static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
-                               const GradArgs *a, const LossKind &k, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream,
-                               const EpeArgs *epe = nullptr)
+// every b2f_forward_loss*_device entry; d's ground truth is the device memory of the n triplets
+static int forward_loss_device(const std::string &w, b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, LossSpec d,
+                               unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream)
 {
-    // (b2f_forward_loss_epe_device: a == nullptr, epe the device ground truth of the n triplets; dev_loss and dev_grad each optional)
-    const bool with_grad = epe ? dev_grad != nullptr : a != nullptr;
-    if (!c || !dev_in || (epe ? (!dev_grad && !dev_loss) : with_grad ? !dev_grad : !dev_loss)) return fail(w + ": null argument");
+    if (!c || !dev_in || d.outputs_refusal(dev_loss, dev_grad)) return fail(w + ": null argument");
     if (in_kind != B2F_IN_NORMALIZED) return fail(w + ": in_kind must be B2F_IN_NORMALIZED (the reference image of the loss is the normalized centre frame)");
     CHK(check_forward_loss(c, w, n, H, W, flow_scale));
-    CHK(check_forward_loss_kind(c, w, k, n, H, W));
-    GradOpts o;
-    EpeArgs e = {};
+    CHK(check_forward_loss_kind(c, w, d, n, H, W));
     const int sb = loss_subbatch(c, n, H, W);
-    if (epe) {
-        e = *epe;
-        CHK(check_forward_loss_epe(c, w, &epe->o, dev_grad, n_outs, &e));
-        if (with_grad && e.o.size_average && e.count_mode == B2F_EPE_COUNT_BATCH && sb < n)
-            return fail(w + ": B2F_EPE_COUNT_BATCH needs the request in one sub-batch and this one would be cut (host_subbatch_pixels): use "
-                            "B2F_EPE_COUNT_IMAGE or B2F_EPE_COUNT_GIVEN, which do not depend on the cut");
-        if ((uintptr_t)e.gt_flow & 15) return fail(w + ": device buffers must be 16-byte aligned");
-    } else if (with_grad) CHK(check_forward_loss_grad(c, w, *a, dev_grad, n_outs, &o));
-    uintptr_t bits = (uintptr_t)dev_in | (uintptr_t)dev_loss;
-    for (int i = 0; with_grad && i < n_outs; ++i) bits |= (uintptr_t)dev_grad[i];
+    if (d.is_epe() || d.grad_entry) CHK(check_forward_loss_grad(c, w, d, dev_grad, n_outs));
+    // (the host entry counts over the whole request instead: whole_request_counts)
+    if (d.is_epe() && dev_grad && d.epe.size_average && d.count_mode == B2F_EPE_COUNT_BATCH && sb < n)
+        return fail(w + ": B2F_EPE_COUNT_BATCH needs the request in one sub-batch and this one would be cut (host_subbatch_pixels): use "
+                        "B2F_EPE_COUNT_IMAGE or B2F_EPE_COUNT_GIVEN, which do not depend on the cut");
+    uintptr_t bits = (uintptr_t)dev_in | (uintptr_t)dev_loss | (uintptr_t)d.gt_flow;
+    for (int i = 0; dev_grad && i < n_outs; ++i) bits |= (uintptr_t)dev_grad[i];
     if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
     const size_t hw = (size_t)H * W;
-    const LossPlan lp = make_loss_plan(c, sb, H, W, false, k);
+    const LossPlan lp = make_loss_plan(c, sb, H, W, d, false, false);
     std::vector<float *> tab, gr((size_t)lp.n_outs);
     CHK(loss_work_tables(c, lp, tab, nullptr));
     ReqBatchScope rb(c, n);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     for (int b0 = 0; b0 < n; b0 += sb) {
-        // the sub-batch's part of the caller's gradient tensors: image b0 of every one
-        for (int i = 0; with_grad && i < lp.n_outs; ++i) gr[(size_t)i] = dev_grad[i] + (size_t)b0 * (lp.cnt[(size_t)i] / (size_t)sb);
-        // (without a gradient table o is unresolved and forward_loss_run does not read it)
-        EpeArgs de = e;
-        if (epe) {   // the sub-batch's part of the ground truth: image b0
-            de.gt_flow = e.gt_flow + (size_t)b0 * 2 * hw;
-            de.valid = e.valid ? e.valid + (size_t)b0 * hw : nullptr;
-            de.gt_occ = e.gt_occ ? e.gt_occ + (size_t)b0 * hw : nullptr;
-        }
-        CHK(forward_loss_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, &o, lp, tab.data(),
-                             dev_loss ? dev_loss + (size_t)b0 * lp.L * lp.words : nullptr, with_grad ? gr.data() : nullptr, epe ? &de : nullptr));
+        // the sub-batch's part of the caller's gradient tensors, and of the ground truth: image b0 of every one
+        for (int i = 0; dev_grad && i < lp.n_outs; ++i) gr[(size_t)i] = dev_grad[i] + (size_t)b0 * (lp.cnt[(size_t)i] / (size_t)sb);
+        CHK(forward_loss_run(c, s, (const float *)dev_in + (size_t)b0 * 9 * hw, std::min(sb, n - b0), H, W, flow_scale, d.at_image((size_t)b0, hw), lp, tab.data(),
+                             dev_loss ? dev_loss + (size_t)b0 * lp.L * lp.words : nullptr, dev_grad ? gr.data() : nullptr));
     }
     return 0;
 }
@@ -1869,7 +1805,7 @@ int b2f_forward_loss_epe(b2f_ctx *c, const float *x, int n, int H, int W, const 
                          double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts, unsigned long long *loss,
                          float *const *grad, int n_outs, float *const *outs) try
 {
-    return forward_loss_epe_host(c, x, n, 0, H, W, gt_flow, valid, gt_occ, flow_scale, opts, count_mode, counts, loss, grad, n_outs, outs);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_epe(gt_flow, valid, gt_occ, opts, count_mode, counts), loss, grad, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_epe")
 
@@ -1878,10 +1814,8 @@ int b2f_forward_loss_epe_device(b2f_ctx *c, const void *dev_in, int in_kind, int
                                 const unsigned char *dev_valid, const unsigned char *dev_gt_occ, double flow_scale, const b2f_loss_epe_opts *opts,
                                 int count_mode, const double *counts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    EpeArgs e = {dev_gt_flow, dev_valid, dev_gt_occ, {}, count_mode, counts};
-    if (opts) e.o = *opts;
-    else (void)b2f_loss_epe_defaults(&e.o);
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, kEpeRecords, dev_loss, dev_grad, n_outs, stream, &e);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_epe(dev_gt_flow, dev_valid, dev_gt_occ, opts, count_mode, counts), dev_loss,
+                               dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_epe_device")
 
@@ -1889,16 +1823,14 @@ B2F_CATCH("b2f_forward_loss_epe_device")
 int b2f_forward_loss_grad_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
                                  unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    const GradArgs a = grad_args(opts);
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_grad(opts), dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_device")
 
 int b2f_forward_loss_grad_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale,
                                     const b2f_loss_grad_ft_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream) try
 {
-    const GradArgs a = grad_args(opts);
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_grad(opts), dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_ft_device")
 
@@ -1906,7 +1838,7 @@ B2F_CATCH("b2f_forward_loss_grad_ft_device")
 int b2f_forward_loss_grad_ssim(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ssim_opts *opts,
                                unsigned long long *loss, float *const *grad, int n_outs, float *const *outs, int range_mode, const float *ranges) try
 {
-    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs, outs);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_grad(opts, range_mode, ranges), loss, grad, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_grad_ssim")
 
@@ -1914,8 +1846,7 @@ int b2f_forward_loss_grad_ssim_device(b2f_ctx *c, const void *dev_in, int in_kin
                                       const b2f_loss_grad_ssim_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream,
                                       int range_mode, const float *ranges) try
 {
-    const GradArgs a = grad_args(opts, range_mode, ranges);
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_grad(opts, range_mode, ranges), dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_ssim_device")
 
@@ -1923,7 +1854,7 @@ B2F_CATCH("b2f_forward_loss_grad_ssim_device")
 int b2f_forward_loss_grad_plain(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_plain_opts *opts,
                                 unsigned long long *loss, float *const *grad, int n_outs, float *const *outs, int range_mode, const float *ranges) try
 {
-    return forward_loss_grad_host(c, x, n, 0, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs, outs);
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_grad(opts, range_mode, ranges), loss, grad, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_grad_plain")
 
@@ -1931,8 +1862,7 @@ int b2f_forward_loss_grad_plain_device(b2f_ctx *c, const void *dev_in, int in_ki
                                        const b2f_loss_grad_plain_opts *opts, unsigned long long *dev_loss, float *const *dev_grad, int n_outs, void *stream,
                                        int range_mode, const float *ranges) try
 {
-    const GradArgs a = grad_args(opts, range_mode, ranges);
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, &a, a.rec(), dev_loss, dev_grad, n_outs, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_grad(opts, range_mode, ranges), dev_loss, dev_grad, n_outs, stream);
 }
 B2F_CATCH("b2f_forward_loss_grad_plain_device")
 
@@ -1941,7 +1871,7 @@ B2F_CATCH("b2f_forward_loss_grad_plain_device")
 int b2f_forward_loss_plain(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
                            int range_mode, const float *ranges) try
 {
-    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges});
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_records(kLossPlain, range_mode, ranges), loss, nullptr, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_plain")
 
@@ -1949,22 +1879,21 @@ B2F_CATCH("b2f_forward_loss_plain")
 int b2f_forward_loss_plain_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                                   void *stream, int range_mode, const float *ranges) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}, dev_loss,
-                               nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_records(kLossPlain, range_mode, ranges), dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_plain_device")
 
 // model:forward + test.lua:266-297 from host memory
 int b2f_forward_loss(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try
 {
-    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, loss_kind(false));
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_records(kLossPme), loss, nullptr, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss")
 
 // model:forward + test.lua:266-297 + the fine-tuning terms of README.md:89-102 from host memory
 int b2f_forward_loss_ft(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs) try
 {
-    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, loss_kind(true));
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_records(kLossFt), loss, nullptr, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_ft")
 
@@ -1972,7 +1901,7 @@ B2F_CATCH("b2f_forward_loss_ft")
 int b2f_forward_loss_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                             void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, loss_kind(false), dev_loss, nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_records(kLossPme), dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_device")
 
@@ -1980,7 +1909,7 @@ B2F_CATCH("b2f_forward_loss_device")
 int b2f_forward_loss_ft_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                                void *stream) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, loss_kind(true), dev_loss, nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_records(kLossFt), dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_ft_device")
 
@@ -1988,7 +1917,7 @@ B2F_CATCH("b2f_forward_loss_ft_device")
 int b2f_forward_loss_ssim(b2f_ctx *c, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
                           int range_mode, const float *ranges) try
 {
-    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss, outs, n_outs, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges});
+    return forward_loss_host(c, x, n, 0, H, W, flow_scale, loss_records(kLossSsim, range_mode, ranges), loss, nullptr, n_outs, outs);
 }
 B2F_CATCH("b2f_forward_loss_ssim")
 
@@ -1996,8 +1925,7 @@ B2F_CATCH("b2f_forward_loss_ssim")
 int b2f_forward_loss_ssim_device(b2f_ctx *c, const void *dev_in, int in_kind, int n, int H, int W, double flow_scale, unsigned long long *dev_loss,
                                  void *stream, int range_mode, const float *ranges) try
 {
-    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, nullptr, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, dev_loss,
-                               nullptr, 0, stream);
+    return forward_loss_device(__func__, c, dev_in, in_kind, n, H, W, flow_scale, loss_records(kLossSsim, range_mode, ranges), dev_loss, nullptr, 0, stream);
 }
 B2F_CATCH("b2f_forward_loss_ssim_device")
 
@@ -2107,6 +2035,30 @@ catch (const std::exception &e) { fail(std::string("b2f_arena_plan: ") + e.what(
 catch (...) { fail("b2f_arena_plan: unknown exception"); return -1; }
 
 }  // extern "C"
+
+// ---- what kind of memory a caller's pointer is: the one place that asks the runtime ----
+int b2f::pointer_kind(const void *p)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeArray) return -1;
+    return a.type == hipMemoryTypeHost ? 1 : 0;
+}
+
+int b2f::check_device_pointers(const std::string &w, const b2f_ctx *c, const char *use, const void *const *ptrs, size_t count, size_t aligned)
+{
+    uintptr_t bits = 0;
+    for (size_t i = 0; i < aligned; ++i) bits |= (uintptr_t)ptrs[i];
+    if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
+    if (!c) return fail(w + ": null context");
+    HIPCHK(hipSetDevice(c->device));
+    for (size_t i = 0; i < count; ++i)
+        if (ptrs[i] && host_memory(ptrs[i])) return fail(w + ": host memory passed to a device entry point (use " + use + ")");
+    return 0;
+}
 
 // The profile bracket for launches outside this file (the score stage of b2f_pipeline.hip): with profile = 1, a row `name` of
 // b2f_profile_read timed by HIP events on the launch stream, like the rows of the forward pass

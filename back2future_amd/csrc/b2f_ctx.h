@@ -627,98 +627,188 @@ int check_request(const FlowRequest &r);
 // b2f_pipeline.hip: a request on host buffers (the upload / kernels / download pipeline) and on device buffers (the kernels alone,
 // asynchronous on `stream`, nullptr: the context's)
 int compute_flow_host(b2f_ctx *c, const FlowRequest &r);
-// which records a table-loss entry writes: words = B2F_LOSS_WORDS (test.lua:266-297), B2F_LOSS_FT_WORDS (with the fine-tuning terms of
-// README.md:89-102 behind them) or B2F_LOSS_SSIM_WORDS (with the SSIM + L1 sums of OSSIML1Criterion.lua and their range: range_mode
-// B2F_SSIM_RANGE_*, ranges L x 2 host floats with B2F_SSIM_RANGE_GIVEN)
-struct LossKind {
-    int words = B2F_LOSS_WORDS;
-    int range_mode = 0;
+// b2f_api.hip: what the HIP runtime knows of p: -1 device (managed, array) memory, 1 page-locked host memory, 0 anything else, which is
+// pageable host memory
+int pointer_kind(const void *p);
+inline bool host_memory(const void *p) { return pointer_kind(p) >= 0; }
+// b2f_api.hip: the pointer checks of the device entry w, null pointers skipped: all 16-byte aligned, then the context (null: refused
+// here, for the entries that have not looked yet) and hipSetDevice, then none of them host memory -- "(use <use>)" names the entries for that
+// aligned: so many of them, the first ones, have to be (byte planes need not)
+int check_device_pointers(const std::string &w, const b2f_ctx *c, const char *use, const void *const *ptrs, size_t count, size_t aligned);
+inline int check_device_pointers(const std::string &w, const b2f_ctx *c, const char *use, std::initializer_list<const void *> ptrs)
+{
+    return check_device_pointers(w, c, use, ptrs.begin(), ptrs.size(), ptrs.size());
+}
+
+// ---- the table-loss family ----
+// The objective of a table-loss entry: the records of test.lua:266-297 alone (B2F_LOSS_WORDS), with the fine-tuning terms of
+// README.md:89-102 behind them (B2F_LOSS_FT_WORDS), with the SSIM + L1 sums of OSSIML1Criterion.lua and their range (B2F_LOSS_SSIM_WORDS),
+// with the photometric sums without occlusion masking of MBCCriterion.lua / MSSIML1Criterion.lua and their range (B2F_LOSS_PLAIN_WORDS),
+// or the supervised objective of train.lua:296-334 (B2F_LOSS_EPE_WORDS)
+enum LossObjective { kLossPme = 0, kLossFt = 1, kLossSsim = 2, kLossPlain = 3, kLossEpe = 4 };
+
+// Which objective and which outputs: what every layer of the family takes, from the extern "C" one-liner that builds it (loss_records,
+// loss_grad, loss_epe below) down to the launchers' callers.  The first part is what the entry was given; resolve() checks it and fills
+// the second part.  The four unsupervised objectives require the records in their plain entries and the gradient table in their *_grad*
+// entries (grad_entry), where the forward entries take the records too; the supervised one takes either or both everywhere.
+struct LossSpec {
+    LossObjective obj = kLossPme;
+    bool grad_entry = false;
+    // opts: b2f_loss_grad_opts / _ft_opts / _ssim_opts / _plain_opts of a *_grad* entry by obj, b2f_loss_epe_opts of kLossEpe; nullptr:
+    // the defaults
+    const void *opts = nullptr;
+    int range_mode = 0;              // kLossSsim, kLossPlain: B2F_SSIM_RANGE_*, and L x 2 host floats with B2F_SSIM_RANGE_GIVEN
     const float *ranges = nullptr;
-    bool ssim() const { return words == B2F_LOSS_SSIM_WORDS; }
-    // B2F_LOSS_PLAIN_WORDS: with the photometric sums without occlusion masking of MBCCriterion.lua / MSSIML1Criterion.lua and their range
-    bool plain() const { return words == B2F_LOSS_PLAIN_WORDS; }
-    bool ranged() const { return ssim() || plain(); }   // range_mode and ranges are read
-    const char *suffix() const { return words == B2F_LOSS_FT_WORDS ? "_ft" : ssim() ? "_ssim" : plain() ? "_plain" : ""; }
-};
-inline LossKind loss_kind(bool ft) { return LossKind{ft ? B2F_LOSS_FT_WORDS : B2F_LOSS_WORDS, 0, nullptr}; }
-// b2f_api.hip: b2f_forward_loss (test.lua:266-297 behind model:forward) on n of a request of `req` triplets (0: n)
-// k: the records of b2f_forward_loss, b2f_forward_loss_ft or b2f_forward_loss_ssim
-int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, unsigned long long *loss, float **outs, int n_outs,
-                      const LossKind &k = LossKind());
-// which gradient table an entry writes: the *_grad entries (b2f_loss_grad_opts, table_loss_grad_kernel, 16-word records), the *_grad_ft
-// entries (b2f_loss_grad_ft_opts, table_loss_grad_ft_kernel, 24-word records) or the *_grad_ssim entries (b2f_loss_grad_ssim_opts,
-// table_loss_grad_ft_kernel's flow planes + table_loss_grad_ssim_kernel, 32-word records)
-// or the *_grad_plain entries (b2f_loss_grad_plain_opts, the flow planes likewise + table_loss_grad_plain_kernel, 40-word records)
-enum GradKind { kGradKindFirst = 0, kGradKindFt = 1, kGradKindSsim = 2, kGradKindPlain = 3 };
-// the options an entry was given: opts points at the struct of `kind` (nullptr: that kind's defaults); range_mode / ranges: the
-// trailing arguments of the *_grad_ssim entries
-struct GradArgs {
-    GradKind kind;
-    const void *opts;
-    int range_mode;
-    const float *ranges;
-    // the records that go with this gradient table
-    LossKind rec() const
+    // kLossEpe: the ground truth of image 0 (valid and gt_occ may be null), host or device memory as the entry has it; B2F_EPE_COUNT_*
+    // and L x 2 host doubles with B2F_EPE_COUNT_GIVEN
+    const float *gt_flow = nullptr;
+    const unsigned char *valid = nullptr, *gt_occ = nullptr;
+    int count_mode = 0;
+    const double *counts = nullptr;
+    // resolved: the first-order fields and smooth_second_order of every *_grad* kind in o (pme: both flags 0; ssim, plain: pme_criterion 0,
+    // unused), the rest of ssim and plain beside it; the options of kLossEpe
+    b2f_loss_grad_ft_opts o = {};
+    double ssim_alpha = 0.0;
+    int plain_criterion = 0, plain_penalty = 0;   // B2F_PLAIN_*
+    b2f_loss_epe_opts epe = {};
+
+    bool is_epe() const { return obj == kLossEpe; }
+    bool ranged() const { return obj == kLossSsim || obj == kLossPlain; }   // range_mode and ranges are read
+    int words() const   // of a record
     {
-        return kind == kGradKindSsim    ? LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}
-               : kind == kGradKindPlain ? LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}
-                                        : loss_kind(kind == kGradKindFt);
+        static const int kWords[5] = {B2F_LOSS_WORDS, B2F_LOSS_FT_WORDS, B2F_LOSS_SSIM_WORDS, B2F_LOSS_PLAIN_WORDS, B2F_LOSS_EPE_WORDS};
+        return kWords[obj];
     }
-    bool ranged() const { return kind == kGradKindSsim || kind == kGradKindPlain; }
+    // b2f_table_loss<suffix>_device, b2f_forward_loss<suffix>, ...
     const char *suffix() const
     {
-        return kind == kGradKindFt ? "_grad_ft" : kind == kGradKindSsim ? "_grad_ssim" : kind == kGradKindPlain ? "_grad_plain" : "_grad";
+        static const char *const kSuffix[2][5] = {{"", "_ft", "_ssim", "_plain", "_epe"}, {"_grad", "_grad_ft", "_grad_ssim", "_grad_plain", "_epe"}};
+        return kSuffix[grad_entry][obj];
+    }
+    // the rows of b2f_profile_read behind table_loss (and table_loss_range): of the kernel that adds an objective's words to the
+    // records (nullptr: pme has none) and of the gradient table's kernels; kLossEpe has the one row for both
+    const char *terms_row() const
+    {
+        static const char *const kRow[5] = {nullptr, "table_loss_ft", "table_loss_ssim", "table_loss_plain", "table_loss_epe"};
+        return kRow[obj];
+    }
+    const char *grad_row() const
+    {
+        static const char *const kRow[5] = {"table_loss_grad", "table_loss_grad_ft", "table_loss_grad_ssim", "table_loss_grad_plain", "table_loss_epe"};
+        return kRow[obj];
+    }
+    // the entries a device entry points a caller with host memory to
+    const char *host_entries() const
+    {
+        static const char *const kRecords = "b2f_op_table_loss / b2f_table_loss_host", *const kEpe = "b2f_op_table_loss_epe / b2f_table_loss_epe_host";
+        static const char *const kUse[2][5] = {{kRecords, kRecords, kRecords, kRecords, kEpe},
+                                               {"b2f_op_table_loss_grad / b2f_table_loss_grad_host", "b2f_op_table_loss_grad_ft / b2f_table_loss_grad_ft_host",
+                                                "b2f_op_table_loss_grad_ssim / b2f_table_loss_grad_ssim_host",
+                                                "b2f_op_table_loss_grad_plain / b2f_table_loss_grad_plain_host", kEpe}};
+        return kUse[grad_entry][obj];
+    }
+    // nullptr, or why these outputs are refused
+    const char *outputs_refusal(const void *loss, const void *grad) const
+    {
+        if (is_epe()) return !loss && !grad ? "loss and grad are both null: nothing to compute" : nullptr;
+        return (grad_entry ? !grad : !loss) ? "null argument" : nullptr;
+    }
+    // b2f_tableloss.hip: nullptr, or why the range is refused; nullptr and the second part filled (the defaults where opts is null), or why
+    // the options, then the range, or the ground truth and the counts of a table of L levels, are refused, as include/b2f.h says
+    const char *range_refusal() const;
+    const char *resolve(int L);
+    // nullptr, or why a table entry with a context refuses this objective on its model: a two_frame model has no occlusions in its table
+    // (MBCCriterion.lua:39-42: the tensors of a level shift, and the table has none of the words 0 .. 15)
+    const char *model_refusal(const b2f_ctx *c) const
+    {
+        if (!c->g.two_frame) return nullptr;
+        return obj == kLossPlain ? "a two_frame model has no occlusions in its table; the *_plain entries are not defined for it"
+               : is_epe()        ? "a two_frame model has no occlusions in its table; the table loss is not defined for it"
+                                 : nullptr;
+    }
+    // nullptr, or why a request that is split over several GPUs refuses this (a shard's batch range, or its counts, would depend on the split)
+    const char *sharded_refusal() const
+    {
+        if (ranged() && range_mode == B2F_SSIM_RANGE_BATCH)
+            return "B2F_SSIM_RANGE_BATCH is not served over several GPUs: the images of a request are split; use B2F_SSIM_RANGE_IMAGE or "
+                   "B2F_SSIM_RANGE_GIVEN";
+        if (is_epe() && count_mode == B2F_EPE_COUNT_BATCH)
+            return "B2F_EPE_COUNT_BATCH is not served over several GPUs: the images of a request are split; use B2F_EPE_COUNT_IMAGE or "
+                   "B2F_EPE_COUNT_GIVEN";
+        return nullptr;
+    }
+    // the same for the images from `image` on of a request of H x W = hw pixels: the ground truth moves on, on the host and on the device alike
+    LossSpec at_image(size_t image, size_t hw) const
+    {
+        LossSpec d = *this;
+        if (gt_flow) d.gt_flow = gt_flow + image * 2 * hw;
+        if (valid) d.valid = valid + image * hw;
+        if (gt_occ) d.gt_occ = gt_occ + image * hw;
+        return d;
     }
 };
-inline GradArgs grad_args(const b2f_loss_grad_opts *o) { return GradArgs{kGradKindFirst, o, 0, nullptr}; }
-inline GradArgs grad_args(const b2f_loss_grad_ft_opts *o) { return GradArgs{kGradKindFt, o, 0, nullptr}; }
-inline GradArgs grad_args(const b2f_loss_grad_ssim_opts *o, int range_mode, const float *ranges) { return GradArgs{kGradKindSsim, o, range_mode, ranges}; }
-inline GradArgs grad_args(const b2f_loss_grad_plain_opts *o, int range_mode, const float *ranges) { return GradArgs{kGradKindPlain, o, range_mode, ranges}; }
-// checked options of a gradient table: o holds the first-order fields and smooth_second_order of every kind (the *_grad entries: both
-// flags 0; the *_grad_ssim entries: pme_criterion 0, unused), ssim_alpha and rec the rest of kGradKindSsim
-struct GradOpts {
-    b2f_loss_grad_ft_opts o;
-    GradKind kind;
-    double ssim_alpha;
-    LossKind rec;
-    int plain_criterion = 0, plain_penalty = 0;   // kGradKindPlain: B2F_PLAIN_*
-};
-// b2f_tableloss.hip: the options of a, or its kind's defaults where they are null, into *o; refused as include/b2f.h says (the range
-// of kGradKindSsim included)
-int resolve_grad_opts(const std::string &w, const GradArgs &a, GradOpts *o);
-// b2f_tableloss.hip: the records of test.lua:266-297 of n images on s, under the profile row table_loss; k.words = B2F_LOSS_WORDS,
-// B2F_LOSS_FT_WORDS with the fine-tuning terms behind them (table_loss_ft), or B2F_LOSS_SSIM_WORDS with the ranges and the SSIM + L1
-// sums (table_loss_range, table_loss_ssim).  Builds R_1 .. R_{L-1} in c->loss_pyr first.
+inline LossSpec loss_spec(LossObjective obj, bool grad_entry, const void *opts, int range_mode, const float *ranges)
+{
+    LossSpec d;
+    d.obj = obj; d.grad_entry = grad_entry; d.opts = opts; d.range_mode = range_mode; d.ranges = ranges;
+    return d;
+}
+inline LossSpec loss_records(LossObjective obj, int range_mode = 0, const float *ranges = nullptr) { return loss_spec(obj, false, nullptr, range_mode, ranges); }
+inline LossSpec loss_grad(const b2f_loss_grad_opts *o) { return loss_spec(kLossPme, true, o, 0, nullptr); }
+inline LossSpec loss_grad(const b2f_loss_grad_ft_opts *o) { return loss_spec(kLossFt, true, o, 0, nullptr); }
+inline LossSpec loss_grad(const b2f_loss_grad_ssim_opts *o, int range_mode, const float *ranges) { return loss_spec(kLossSsim, true, o, range_mode, ranges); }
+inline LossSpec loss_grad(const b2f_loss_grad_plain_opts *o, int range_mode, const float *ranges) { return loss_spec(kLossPlain, true, o, range_mode, ranges); }
+inline LossSpec loss_epe(const float *gt_flow, const unsigned char *valid, const unsigned char *gt_occ, const b2f_loss_epe_opts *o, int count_mode,
+                         const double *counts)
+{
+    LossSpec d = loss_spec(kLossEpe, false, o, 0, nullptr);
+    d.gt_flow = gt_flow; d.valid = valid; d.gt_occ = gt_occ; d.count_mode = count_mode; d.counts = counts;
+    return d;
+}
+
+// b2f_tableloss.hip: tensors per level of a table of n_outs tensors on this context: its own kind where that divides n_outs, else the
+// other one; 0: neither (kTableSizeRefusal)
+int level_size(const b2f_ctx *c, int n_outs);
+// b2f_tableloss.hip: what every entry on a table checks without a HIP call, for all five objectives: the outputs asked for, the shape
+// (table_loss_refusal, into *L), null tensors, d.resolve, and that no output -- loss (or null), the gradient table (or null) -- is an
+// input or another output.  per: tensors per level; ref is not read by kLossEpe
+int check_table(const std::string &w, LossSpec &d, const float *const *table, float *const *grad, const unsigned long long *loss, const float *ref, int n_outs,
+                int per, int n, int H, int W, double flow_scale, int *L);
+// b2f_tableloss.hip: the one body behind b2f_table_loss*_device, b2f_table_loss_grad*_device and b2f_table_loss_epe_device, and the one
+// behind the b2f_op_table_loss* entries, which stages host tensors in a guarded OpStage and calls the former
+int table_loss_device(const std::string &w, LossSpec d, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                      double flow_scale, unsigned long long *dev_loss, float *const *dev_grad, void *stream);
+int table_loss_op(const std::string &w, LossSpec d, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                  double flow_scale, unsigned long long *loss, float *const *grad);
+// b2f_tableloss.hip: the one body behind the b2f_table_loss*_host entries: check_table, then the objective's implementation on the CPU
+// (b2f_host.cpp); rescale: kLossEpe's
+int table_loss_host_entry(const std::string &w, LossSpec d, const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                          double flow_scale, unsigned long long *loss, float *const *grad, int rescale = 0);
+// b2f_tableloss.hip: records and / or gradient table of n images of a resolved d on s, by one of the three below: kLossEpe by
+// table_loss_epe_run; else the records, where asked for, by table_loss_run and then the gradient table, where asked for, by
+// table_loss_grad_run, which finds the pyramid (and the ranges) the records' launch has left
+int table_loss_dispatch(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, unsigned long long *dev_loss, const LossSpec &d, int L,
+                        bool past, int n, int H, int W, const float *dev_ref, size_t ref_stride, double flow_scale);
+// b2f_tableloss.hip: the records of test.lua:266-297 of n images on s, under the profile row table_loss; then, by d.obj, the fine-tuning
+// terms behind them (table_loss_ft), the ranges and the SSIM + L1 sums (table_loss_range, table_loss_ssim) or the ranges and the sums
+// without occlusion masking (table_loss_range, table_loss_plain).  Builds R_1 .. R_{L-1} in c->loss_pyr first.
 int table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, int L, bool past, int n, int H, int W, const float *dev_ref,
-                   size_t ref_stride, double flow_scale, unsigned long long *dev_loss, const LossKind &k);
-// b2f_tableloss.hip: the gradient table of train.lua:428-468 of n images on s, from checked options; dev_loss: the records
-// table_loss_run(.., o.rec) has written on s with R_1 .. R_{L-1}, or nullptr: the pyramid is built first, and with kGradKindSsim the
-// ranges into a zeroed record buffer of the context (c->loss_rec)
+                   size_t ref_stride, double flow_scale, unsigned long long *dev_loss, const LossSpec &d);
+// b2f_tableloss.hip: the gradient table of train.lua:428-468 of n images on s, from a resolved d; dev_loss: the records
+// table_loss_run(.., d) has written on s with R_1 .. R_{L-1}, or nullptr: the pyramid is built first, and where the objective reads
+// them the ranges into a zeroed record buffer of the context (c->loss_rec)
 int table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
-                        const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, unsigned long long *dev_loss);
+                        const float *dev_ref, size_t ref_stride, double flow_scale, const LossSpec &d, unsigned long long *dev_loss);
 // b2f_tableloss_epe.hip: the records (dev_loss, or nullptr) and / or the gradient table (dev_grad, or nullptr) of the supervised objective
-// of train.lua:296-334 of n images on s, from checked options and counts, under the profile row table_loss_epe; rescale is the context's
-// rescale_flow; the counting pass of size_average goes into c->loss_rec
+// of train.lua:296-334 of n images on s, from a resolved d whose ground truth is device memory, under the profile row table_loss_epe;
+// rescale is the context's rescale_flow; the counting pass of size_average goes into c->loss_rec
 int table_loss_epe_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
-                       const float *dev_gt_flow, const unsigned char *dev_valid, const unsigned char *dev_gt_occ, double flow_scale,
-                       const b2f_loss_epe_opts &o, int count_mode, const double *counts, unsigned long long *dev_loss);
-// what the b2f_forward_loss_epe* entries hand down beside the input: the ground truth of image 0 of the request (host memory for the host
-// entries, device memory for the device entry; valid and gt_occ may be null), the checked options and the counts
-struct EpeArgs {
-    const float *gt_flow;
-    const unsigned char *valid, *gt_occ;
-    b2f_loss_epe_opts o;
-    int count_mode;
-    const double *counts;
-};
-// b2f_api.hip: b2f_forward_loss_epe on n of a request of `req` triplets (0: n); loss, grad and outs may each be null, loss and grad not both
-int forward_loss_epe_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, const float *gt_flow, const unsigned char *valid,
-                          const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
-                          unsigned long long *loss, float *const *grad, int n_outs, float *const *outs);
-// b2f_api.hip: b2f_forward_loss_grad, b2f_forward_loss_grad_ft or b2f_forward_loss_grad_ssim (a.kind) on n of a request of `req`
-// triplets (0: n)
-int forward_loss_grad_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, const GradArgs &a, unsigned long long *loss,
-                           float *const *grad, int n_outs, float *const *outs);
+                       double flow_scale, const LossSpec &d, unsigned long long *dev_loss);
+// b2f_api.hip: model:forward and the objective d on n of a request of `req` triplets (0: n) from host memory -- the b2f_forward_loss*
+// entries of every objective, and a shard of b2f_multi_forward_loss*, which passes the caller's n down as req.  loss, grad and outs as
+// d.outputs_refusal has them; n_outs counts grad, and outs where there is no grad.
+int forward_loss_host(b2f_ctx *c, const float *x, int n, int req, int H, int W, double flow_scale, LossSpec d, unsigned long long *loss, float *const *grad,
+                      int n_outs, float *const *outs);
 int compute_flow_device(b2f_ctx *c, const FlowRequest &r, void *stream);
 // b2f_pipeline.hip: a push (r.stream) on host buffers, synchronous, and on device buffers, asynchronous on `stream`; *ready = 1 when
 // the outputs were written (from the third push on)

@@ -680,7 +680,7 @@ const char *table_loss_refusal(int n_outs, int per, int n, int H, int W, double 
 {
     if (n <= 0 || H <= 0 || W <= 0) return "bad shape";
     if (per != 4 && per != 5) return "a level holds 4 (Hard) or 5 (Soft) tensors";
-    if (n_outs <= 0 || n_outs % per) return "n_outs must be L x 4 (Hard) or L x 5 (Soft)";
+    if (n_outs <= 0 || n_outs % per) return kTableSizeRefusal;
     const int lv = n_outs / per;
     if (lv < 1 || lv > kLossMaxLevels) return "the table must have 1 .. 7 levels (the level weights of test.lua:29-31)";
     if ((long long)H * W >= kPhotoMaxPixels) return "images of 2^28 pixels or more are refused (the Q30 sums could overflow)";
@@ -1113,7 +1113,7 @@ void table_loss_epe_host(const float *const *table, int L, bool past, int n, int
             if (grad)
                 for (int t = 0; t < per; ++t) {
                     float *g = grad[(size_t)j * per + t];
-                    const size_t cnt = (t >= per - 2 ? 3 : 2) * hw;
+                    const size_t cnt = table_planes(t, per) * hw;
                     for (size_t i = 0; i < cnt; ++i) g[(size_t)b * cnt + i] = 0.0f;
                 }
             float *gf = grad ? grad[(size_t)j * per] + (size_t)b * 2 * hw : nullptr, *go = grad ? grad[(size_t)j * per + per - 3] + (size_t)b * 2 * hw : nullptr;

@@ -98,6 +98,14 @@ void table_loss_ssim_host(const float *const *table, int L, bool past, int n, in
 const char *ssim_range_refusal(int range_mode, const float *ranges);
 // the argument checks every table-loss entry shares (test.lua:266-297; no HIP call): nullptr and *L = n_outs / per, or why not
 const char *table_loss_refusal(int n_outs, int per, int n, int H, int W, double flow_scale, int *L);
+// what table_loss_refusal, and an entry that takes `per` from its context (b2f_ctx.h: level_size), says of a table of another size
+constexpr char kTableSizeRefusal[] = "n_outs must be L x 4 (Hard) or L x 5 (Soft)";
+// tensor t of a table of `per` tensors per level (f, [p,] o, iw1, iw3): its planes -- two for flows and occlusions, three for the warped
+// images -- and its floats for n images of a table of H x W
+inline int table_planes(int t, int per) { return t % per >= per - 2 ? 3 : 2; }
+inline size_t table_floats(int t, int per, int n, int H, int W) { return (size_t)n * table_planes(t, per) * (H >> (t / per)) * (W >> (t / per)); }
+// the level weights of opts.lua:61-73 (test.lua:29-31), the defaults of every objective's options
+constexpr double kLossLevelWeights[7] = {0.005, 0.01, 0.02, 0.08, 0.32, 0.64, 1.28};
 }  // namespace b2f
 struct b2f_loss_grad_opts;
 namespace b2f {

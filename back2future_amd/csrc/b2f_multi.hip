@@ -405,19 +405,26 @@ B2F_CATCH("b2f_multi_compute_flow_sequence_warp_past")
 
 }  // extern "C"
 
-// b2f_multi_forward_loss / b2f_multi_forward_loss_ft / b2f_multi_forward_loss_ssim
-static int multi_forward_loss(const std::string &w, const LossKind &k, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss)
+// every b2f_multi_forward_loss* entry: the images of the request are split over the contexts, each of which runs forward_loss_host on its
+// part of x, of the ground truth, of the records and of every tensor of the gradient table
+static int multi_forward_loss(const std::string &w, const LossSpec &d, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale,
+                              unsigned long long *loss, float *const *grad, int n_outs)
 {
     if (!m) return api_fail(w + ": null context");
-    if (!x || !loss || n <= 0 || H <= 0 || W <= 0) return api_fail(w + ": bad arguments");
-    // (a shard's batch range would depend on how the request is split over the GPUs)
-    if (k.ranged() && k.range_mode == B2F_SSIM_RANGE_BATCH)
-        return api_fail(w + ": B2F_SSIM_RANGE_BATCH is not served over several GPUs: the images of a request are split; use B2F_SSIM_RANGE_IMAGE or "
-                            "B2F_SSIM_RANGE_GIVEN");
+    if (!x || (d.is_epe() && !d.gt_flow) || d.outputs_refusal(loss, grad) || n <= 0 || H <= 0 || W <= 0) return api_fail(w + ": bad arguments");
+    const char *why = d.sharded_refusal();
+    if (why) return api_fail(w + ": " + why);
     const b2f_ctx *c0 = m->ctx[0];
-    const size_t rec = (size_t)(c0->g.n_outputs() / (c0->past_flow ? 5 : 4)) * k.words;
+    const int per = c0->past_flow ? 5 : 4, n_tab = c0->g.n_outputs();
+    if (grad && n_outs != n_tab) return api_fail(w + ": n_outs must be the contexts' n_outputs");
+    for (int i = 0; grad && i < n_outs; ++i)
+        if (!grad[i]) return api_fail(w + ": null tensor in the gradient table");
+    const size_t rec = (size_t)(n_tab / per) * d.words(), hw = (size_t)H * W;
     return run_sharded(m, n, [&](int i, int lo, int hi) {
-        return forward_loss_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, loss + (size_t)lo * rec, nullptr, 0, k);
+        std::vector<float *> g((size_t)n_tab);   // the shard's part of every tensor: image lo
+        for (int t = 0; grad && t < n_tab; ++t) g[(size_t)t] = grad[t] + table_floats(t, per, lo, H, W);
+        return forward_loss_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * hw, hi - lo, n, H, W, flow_scale, d.at_image((size_t)lo, hw),
+                                 loss ? loss + (size_t)lo * rec : nullptr, grad ? g.data() : nullptr, n_outs, nullptr);
     });
 }
 
@@ -426,14 +433,14 @@ extern "C" {
 // test.lua:266-297 behind model:forward over several GPUs
 int b2f_multi_forward_loss(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss) try
 {
-    return multi_forward_loss(__func__, loss_kind(false), m, x, n, H, W, flow_scale, loss);
+    return multi_forward_loss(__func__, loss_records(kLossPme), m, x, n, H, W, flow_scale, loss, nullptr, 0);
 }
 B2F_CATCH("b2f_multi_forward_loss")
 
 // ... with the fine-tuning terms of README.md:89-102 in words 16 .. 23
 int b2f_multi_forward_loss_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss) try
 {
-    return multi_forward_loss(__func__, loss_kind(true), m, x, n, H, W, flow_scale, loss);
+    return multi_forward_loss(__func__, loss_records(kLossFt), m, x, n, H, W, flow_scale, loss, nullptr, 0);
 }
 B2F_CATCH("b2f_multi_forward_loss_ft")
 
@@ -441,7 +448,7 @@ B2F_CATCH("b2f_multi_forward_loss_ft")
 int b2f_multi_forward_loss_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, int range_mode,
                                 const float *ranges) try
 {
-    return multi_forward_loss(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, m, x, n, H, W, flow_scale, loss);
+    return multi_forward_loss(__func__, loss_records(kLossSsim, range_mode, ranges), m, x, n, H, W, flow_scale, loss, nullptr, 0);
 }
 B2F_CATCH("b2f_multi_forward_loss_ssim")
 
@@ -449,7 +456,7 @@ B2F_CATCH("b2f_multi_forward_loss_ssim")
 int b2f_multi_forward_loss_plain(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, unsigned long long *loss, int range_mode,
                                  const float *ranges) try
 {
-    return multi_forward_loss(__func__, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}, m, x, n, H, W, flow_scale, loss);
+    return multi_forward_loss(__func__, loss_records(kLossPlain, range_mode, ranges), m, x, n, H, W, flow_scale, loss, nullptr, 0);
 }
 B2F_CATCH("b2f_multi_forward_loss_plain")
 
@@ -458,71 +465,22 @@ int b2f_multi_forward_loss_epe(b2f_multi *m, const float *x, int n, int H, int W
                                const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
                                unsigned long long *loss, float *const *grad, int n_outs) try
 {
-    const std::string w = __func__;
-    if (!m) return api_fail(w + ": null context");
-    if (!x || !gt_flow || (!loss && !grad) || n <= 0 || H <= 0 || W <= 0) return api_fail(w + ": bad arguments");
-    // (a shard's counts would depend on how the request is split over the GPUs)
-    if (count_mode == B2F_EPE_COUNT_BATCH)
-        return api_fail(w + ": B2F_EPE_COUNT_BATCH is not served over several GPUs: the images of a request are split; use B2F_EPE_COUNT_IMAGE or "
-                            "B2F_EPE_COUNT_GIVEN");
-    const b2f_ctx *c0 = m->ctx[0];
-    const int per = c0->past_flow ? 5 : 4, n_tab = c0->g.n_outputs();
-    if (grad && n_outs != n_tab) return api_fail(w + ": n_outs must be the contexts' n_outputs");
-    for (int i = 0; grad && i < n_outs; ++i)
-        if (!grad[i]) return api_fail(w + ": null tensor in the gradient table");
-    const size_t rec = (size_t)(n_tab / per) * B2F_LOSS_EPE_WORDS, hw = (size_t)H * W;
-    return run_sharded(m, n, [&](int i, int lo, int hi) {
-        std::vector<float *> g((size_t)n_tab);   // the shard's part of every tensor: image lo
-        for (int t = 0; grad && t < n_tab; ++t) {
-            const int j = t / per, ch = (t % per) >= per - 2 ? 3 : 2;
-            g[(size_t)t] = grad[t] + (size_t)lo * ch * (H >> j) * (W >> j);
-        }
-        return forward_loss_epe_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * hw, hi - lo, n, H, W, gt_flow + (size_t)lo * 2 * hw,
-                                     valid ? valid + (size_t)lo * hw : nullptr, gt_occ ? gt_occ + (size_t)lo * hw : nullptr, flow_scale, opts, count_mode,
-                                     counts, loss ? loss + (size_t)lo * rec : nullptr, grad ? g.data() : nullptr, n_outs, nullptr);
-    });
+    return multi_forward_loss(__func__, loss_epe(gt_flow, valid, gt_occ, opts, count_mode, counts), m, x, n, H, W, flow_scale, loss, grad, n_outs);
 }
 B2F_CATCH("b2f_multi_forward_loss_epe")
-
-// b2f_multi_forward_loss_grad, b2f_multi_forward_loss_grad_ft and b2f_multi_forward_loss_grad_ssim
-static int multi_forward_loss_grad(const std::string &w, b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const GradArgs &a,
-                                   unsigned long long *loss, float *const *grad, int n_outs)
-{
-    if (!m) return api_fail((w + ": null context").c_str());
-    if (!x || !grad || n <= 0 || H <= 0 || W <= 0) return api_fail((w + ": bad arguments").c_str());
-    // (a shard's batch range would depend on how the request is split over the GPUs)
-    if (a.ranged() && a.range_mode == B2F_SSIM_RANGE_BATCH)
-        return api_fail(w + ": B2F_SSIM_RANGE_BATCH is not served over several GPUs: the images of a request are split; use B2F_SSIM_RANGE_IMAGE or "
-                            "B2F_SSIM_RANGE_GIVEN");
-    const b2f_ctx *c0 = m->ctx[0];
-    if (n_outs != c0->g.n_outputs()) return api_fail((w + ": n_outs must be the contexts' n_outputs").c_str());
-    const int per = c0->past_flow ? 5 : 4;
-    const size_t rec = (size_t)(n_outs / per) * a.rec().words;
-    for (int i = 0; i < n_outs; ++i)
-        if (!grad[i]) return api_fail((w + ": null tensor in the gradient table").c_str());
-    return run_sharded(m, n, [&](int i, int lo, int hi) {
-        std::vector<float *> g((size_t)n_outs);   // the shard's part of every tensor: image lo
-        for (int t = 0; t < n_outs; ++t) {
-            const int j = t / per, ch = (t % per) >= per - 2 ? 3 : 2;
-            g[(size_t)t] = grad[t] + (size_t)lo * ch * (H >> j) * (W >> j);
-        }
-        return forward_loss_grad_host(m->ctx[(size_t)i], x + (size_t)lo * 9 * H * W, hi - lo, n, H, W, flow_scale, a,
-                                      loss ? loss + (size_t)lo * rec : nullptr, g.data(), n_outs, nullptr);
-    });
-}
 
 // the gradient table of train.lua:428-468 behind model:forward over several GPUs
 int b2f_multi_forward_loss_grad(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_opts *opts,
                                 unsigned long long *loss, float *const *grad, int n_outs) try
 {
-    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts), loss, grad, n_outs);
+    return multi_forward_loss(__func__, loss_grad(opts), m, x, n, H, W, flow_scale, loss, grad, n_outs);
 }
 B2F_CATCH("b2f_multi_forward_loss_grad")
 
 int b2f_multi_forward_loss_grad_ft(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ft_opts *opts,
                                    unsigned long long *loss, float *const *grad, int n_outs) try
 {
-    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts), loss, grad, n_outs);
+    return multi_forward_loss(__func__, loss_grad(opts), m, x, n, H, W, flow_scale, loss, grad, n_outs);
 }
 B2F_CATCH("b2f_multi_forward_loss_grad_ft")
 
@@ -530,7 +488,7 @@ B2F_CATCH("b2f_multi_forward_loss_grad_ft")
 int b2f_multi_forward_loss_grad_ssim(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_ssim_opts *opts,
                                      unsigned long long *loss, float *const *grad, int n_outs, int range_mode, const float *ranges) try
 {
-    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs);
+    return multi_forward_loss(__func__, loss_grad(opts, range_mode, ranges), m, x, n, H, W, flow_scale, loss, grad, n_outs);
 }
 B2F_CATCH("b2f_multi_forward_loss_grad_ssim")
 
@@ -538,7 +496,7 @@ B2F_CATCH("b2f_multi_forward_loss_grad_ssim")
 int b2f_multi_forward_loss_grad_plain(b2f_multi *m, const float *x, int n, int H, int W, double flow_scale, const b2f_loss_grad_plain_opts *opts,
                                       unsigned long long *loss, float *const *grad, int n_outs, int range_mode, const float *ranges) try
 {
-    return multi_forward_loss_grad(__func__, m, x, n, H, W, flow_scale, grad_args(opts, range_mode, ranges), loss, grad, n_outs);
+    return multi_forward_loss(__func__, loss_grad(opts, range_mode, ranges), m, x, n, H, W, flow_scale, loss, grad, n_outs);
 }
 B2F_CATCH("b2f_multi_forward_loss_grad_plain")
 

@@ -20,14 +20,9 @@ int mem_kind(const void *p, size_t bytes)
 {
     int kind = 1;
     for (const char *q : {(const char *)p, (const char *)p + bytes - 1}) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, q) != hipSuccess) {
-            (void)hipGetLastError();
-            kind = 0;
-            continue;
-        }
-        if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeArray) return -1;
-        if (a.type != hipMemoryTypeHost) kind = 0;
+        const int k = pointer_kind(q);
+        if (k < 0) return -1;
+        kind = std::min(kind, k);
     }
     return kind;
 }

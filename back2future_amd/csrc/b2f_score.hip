@@ -166,17 +166,6 @@ int check_flow_score(const std::string &w, const void *flow, int n, int H, int W
     return 0;
 }
 
-// 1 when p is memory the host can read (pageable or page-locked), 0 for device memory
-bool host_memory(const void *p)
-{
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;
-    }
-    return !(a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeArray);
-}
-
 }  // namespace
 
 extern "C" {
@@ -196,14 +185,7 @@ int b2f_flow_score_device(b2f_ctx *c, const float *dev_flow, const float *dev_oc
 {
     const std::string w(__func__);
     CHK(check_flow_score(w, dev_flow, n, H, W, flow_scale, dev_gt_flow, dev_scores));
-    if (((uintptr_t)dev_flow | (uintptr_t)dev_occ_prob | (uintptr_t)dev_gt_flow | (uintptr_t)dev_valid | (uintptr_t)dev_gt_occ |
-         (uintptr_t)dev_scores) & 15)
-        return fail(w + ": device buffers must be 16-byte aligned");
-    if (!c) return fail(w + ": null context");
-    HIPCHK(hipSetDevice(c->device));
-    for (const void *p : {(const void *)dev_flow, (const void *)dev_occ_prob, (const void *)dev_gt_flow, (const void *)dev_valid,
-                          (const void *)dev_gt_occ, (const void *)dev_scores})
-        if (p && host_memory(p)) return fail(w + ": host memory passed to a device entry point (use b2f_op_flow_score / b2f_flow_score_host)");
+    CHK(check_device_pointers(w, c, "b2f_op_flow_score / b2f_flow_score_host", {dev_flow, dev_occ_prob, dev_gt_flow, dev_valid, dev_gt_occ, dev_scores}));
     HIPCHK(launch_flow_score(dev_flow, dev_occ_prob, n, H, W, flow_scale, dev_gt_flow, dev_valid, dev_gt_occ, dev_scores,
                              stream ? (hipStream_t)stream : c->stream));
     return 0;

@@ -5,6 +5,9 @@
 // counters in registers, a wave reduction, the waves of a block through LDS, then at most one 64-bit atomicAdd per non-zero word per
 // block.  The reference image of level j + 1 comes from a small pooling pass over that of level j (ref_pool_kernel), into a workspace
 // of the context.
+// The host half of this file is the plumbing of the whole family: the checks of the descriptor (LossSpec of b2f_ctx.h:
+// which objective, which outputs), check_table, the three run paths behind table_loss_dispatch, and one body each for the *_host, *_device
+// and b2f_op_* entries of all five objectives, which the one-line entries below and in b2f_tableloss_epe.hip call.
 #include "b2f_ctx.h"
 #include "b2f_tableloss.h"
 #include "b2f_tableloss_grad_ft.h"
@@ -221,153 +224,82 @@ int ensure_dev_work(DevWork &dw, size_t bytes)
 
 }  // namespace b2f
 
-namespace {
+// ---- the descriptor's checks (b2f_ctx.h: LossSpec) ----
+const char *b2f::LossSpec::range_refusal() const { return ranged() ? ssim_range_refusal(range_mode, ranges) : nullptr; }
 
-// 1 when p is memory the host can read (pageable or page-locked), 0 for device memory
-bool host_memory(const void *p)
+const char *b2f::LossSpec::resolve(int L)
 {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;
+    if (is_epe()) {
+        if (opts) epe = *static_cast<const b2f_loss_epe_opts *>(opts);
+        else (void)b2f_loss_epe_defaults(&epe);
+        return loss_epe_refusal(epe, gt_flow, gt_occ, count_mode, counts, L);
     }
-    return !(a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeArray);
+    if (!grad_entry) return range_refusal();
+    const char *why = nullptr;
+    if (obj == kLossPlain) {
+        b2f_loss_grad_plain_opts t;
+        if (opts) t = *static_cast<const b2f_loss_grad_plain_opts *>(opts);
+        else (void)b2f_loss_grad_plain_defaults(&t);
+        o = loss_grad_plain_base(t);
+        ssim_alpha = t.ssim_alpha;
+        plain_criterion = t.criterion;
+        plain_penalty = t.penalty;
+        why = loss_grad_plain_refusal(t);
+    } else if (obj == kLossSsim) {
+        b2f_loss_grad_ssim_opts t;
+        if (opts) t = *static_cast<const b2f_loss_grad_ssim_opts *>(opts);
+        else (void)b2f_loss_grad_ssim_defaults(&t);
+        o = loss_grad_ssim_base(t);
+        ssim_alpha = t.ssim_alpha;
+        why = loss_grad_ssim_refusal(t);
+    } else if (obj == kLossFt) {
+        if (opts) o = *static_cast<const b2f_loss_grad_ft_opts *>(opts);
+        else (void)b2f_loss_grad_ft_defaults(&o);
+        why = loss_grad_ft_refusal(o);
+    } else {
+        b2f_loss_grad_opts t;
+        if (opts) t = *static_cast<const b2f_loss_grad_opts *>(opts);
+        else (void)b2f_loss_grad_defaults(&t);
+        o = loss_grad_ft_from(t);
+        why = loss_grad_refusal(t);
+    }
+    return why ? why : range_refusal();
 }
 
-// the checks of test.lua:266-297's entries that need no HIP call; per: tensors per level
-int check_table_loss(const std::string &w, const float *const *table, int n_outs, int per, int n, int H, int W, const float *ref, double flow_scale,
-                     const void *loss, int *L)
-{
-    if (!table || !ref || !loss) return fail(w + ": null argument");
-    const char *why = table_loss_refusal(n_outs, per, n, H, W, flow_scale, L);
-    if (why) return fail(w + ": " + why);
-    for (int i = 0; i < n_outs; ++i)
-        if (!table[i]) return fail(w + ": null tensor in the table");
-    return 0;
-}
-
-// tensors per level of a table of n_outs tensors on this context: its own kind where that divides n_outs, else the other one
-int level_size(const b2f_ctx *c, int n_outs)
+int b2f::level_size(const b2f_ctx *c, int n_outs)
 {
     const int own = c->past_flow ? 5 : 4, other = 9 - own;
     return (n_outs > 0 && n_outs % own == 0) ? own : (n_outs > 0 && n_outs % other == 0) ? other : 0;
 }
 
-// what the *_ssim entries check of their range
-int check_loss_kind(const std::string &w, const LossKind &k)
+int b2f::check_table(const std::string &w, LossSpec &d, const float *const *table, float *const *grad, const unsigned long long *loss, const float *ref,
+                     int n_outs, int per, int n, int H, int W, double flow_scale, int *L)
 {
-    const char *why = k.ranged() ? ssim_range_refusal(k.range_mode, k.ranges) : nullptr;
-    return why ? fail(w + ": " + why) : 0;
-}
-
-// what the *_plain entries with a context refuse beside: a two_frame model (MBCCriterion.lua:39-42: without occlusions the tensors of a
-// level shift, and the table has none of the words 0 .. 15)
-int check_plain_context(const std::string &w, const b2f_ctx *c, bool plain)
-{
-    return plain && c->g.two_frame ? fail(w + ": a two_frame model has no occlusions in its table; the *_plain entries are not defined for it") : 0;
-}
-
-// b2f_table_loss_device / b2f_table_loss_ft_device / b2f_table_loss_ssim_device (k: which records)
-int table_loss_device(const std::string &w, const LossKind &k, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
-                      double flow_scale, unsigned long long *dev_loss, void *stream)
-{
-    if (!c) return fail(w + ": null context");
-    const int per = level_size(c, n_outs);
-    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
-    int L = 0;
-    CHK(check_table_loss(w, dev_table, n_outs, per, n, H, W, dev_ref, flow_scale, dev_loss, &L));
-    CHK(check_loss_kind(w, k));
-    CHK(check_plain_context(w, c, k.plain()));
-    if (n > 65535) return fail(w + ": at most 65535 images per call");
-    uintptr_t bits = (uintptr_t)dev_ref | (uintptr_t)dev_loss;
-    for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i];
-    if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    if (host_memory(dev_ref) || host_memory(dev_loss)) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss / b2f_table_loss_host)");
+    const bool epe = d.is_epe();
+    if (!table || (!epe && !ref)) return fail(w + ": null argument");
+    const char *why = d.outputs_refusal(loss, grad);
+    if (!why) why = table_loss_refusal(n_outs, per, n, H, W, flow_scale, L);
+    if (why) return fail(w + ": " + why);
     for (int i = 0; i < n_outs; ++i)
-        if (host_memory(dev_table[i])) return fail(w + ": host memory passed to a device entry point (use b2f_op_table_loss / b2f_table_loss_host)");
-    return table_loss_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, flow_scale, dev_loss, k);
-}
-
-// b2f_op_table_loss / b2f_op_table_loss_ft / b2f_op_table_loss_ssim
-int op_table_loss(const std::string &w, const LossKind &k, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
-                  unsigned long long *loss)
-{
-    OpStage st(c, w);
-    CHK(st.begin(true, "null context"));
-    const int per = level_size(c, n_outs);
-    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
-    int L = 0;
-    CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, loss, &L));
-    CHK(check_loss_kind(w, k));
-    CHK(check_plain_context(w, c, k.plain()));
-    std::vector<const float *> ptrs((size_t)n_outs);
-    float *dr;
+        if (!table[i]) return fail(w + ": null tensor in the table");
+    // (the supervised objective says what it has to say of its options before the aliases, the others behind them)
+    if (epe && (why = d.resolve(*L))) return fail(w + ": " + why);
+    const void *truth[3] = {d.gt_flow, d.valid, d.gt_occ};   // null but for kLossEpe, which alone gets loss beside a gradient table here
+    for (int k = 0; k < 3; ++k)
+        if (epe && loss && truth[k] == (const void *)loss) return fail(w + ": loss must not alias an input");
     for (int i = 0; i < n_outs; ++i) {
-        const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
-        CHK(st.in(table[i], (size_t)n * ch * (H >> j) * (W >> j), "table", &dr));
-        ptrs[(size_t)i] = dr;
-    }
-    unsigned long long *dl;
-    const size_t nl = (size_t)n * L * k.words;
-    CHK(st.in(ref, (size_t)n * 3 * H * W, "ref", &dr)); CHK(st.out(nl, "loss", &dl));
-    CHK(table_loss_device(w, k, c, ptrs.data(), n_outs, n, H, W, dr, flow_scale, dl, nullptr));
-    CHK(st.finish());
-    return st.get(loss, dl, nl);
-}
-
-// ---- the gradient table of train.lua:428-468 (b2f_tableloss_grad.hip) ----
-// grad: n_outs tensors, none null, none a tensor of the table, ref or another one of grad
-int check_grad_table(const std::string &w, const float *const *table, int n_outs, const float *ref, float *const *grad)
-{
-    if (!grad) return fail(w + ": null argument");
-    for (int i = 0; i < n_outs; ++i) {
+        if (epe && loss && (const void *)table[i] == (const void *)loss) return fail(w + ": loss must not alias an input");
+        if (!grad) continue;
         if (!grad[i]) return fail(w + ": null tensor in the gradient table");
-        if (grad[i] == ref) return fail(w + ": the gradient table must not alias ref");
+        if (!epe && grad[i] == ref) return fail(w + ": the gradient table must not alias ref");
+        if (epe && (const void *)grad[i] == (const void *)loss) return fail(w + ": the gradient table must not alias loss");
+        for (int k = 0; k < 3; ++k)
+            if (epe && (const void *)grad[i] == truth[k]) return fail(w + ": the gradient table must not alias the ground truth");
         for (int k = 0; k < n_outs; ++k)
-            if ((table && grad[i] == table[k]) || (k != i && grad[i] == grad[k])) return fail(w + ": the gradient table must not alias the table or itself");
+            if (grad[i] == table[k] || (k != i && grad[i] == grad[k])) return fail(w + ": the gradient table must not alias the table or itself");
     }
+    if (!epe && (why = d.resolve(*L))) return fail(w + ": " + why);
     return 0;
-}
-
-}  // namespace
-
-int b2f::resolve_grad_opts(const std::string &w, const GradArgs &a, GradOpts *o)
-{
-    o->kind = a.kind;
-    o->ssim_alpha = 0.0;
-    o->rec = a.rec();
-    const char *why = nullptr;
-    if (a.kind == kGradKindPlain) {
-        b2f_loss_grad_plain_opts t;
-        if (a.opts) t = *static_cast<const b2f_loss_grad_plain_opts *>(a.opts);
-        else (void)b2f_loss_grad_plain_defaults(&t);
-        o->o = loss_grad_plain_base(t);
-        o->ssim_alpha = t.ssim_alpha;
-        o->plain_criterion = t.criterion;
-        o->plain_penalty = t.penalty;
-        why = loss_grad_plain_refusal(t);
-        if (!why) why = ssim_range_refusal(a.range_mode, a.ranges);
-    } else if (a.kind == kGradKindSsim) {
-        b2f_loss_grad_ssim_opts t;
-        if (a.opts) t = *static_cast<const b2f_loss_grad_ssim_opts *>(a.opts);
-        else (void)b2f_loss_grad_ssim_defaults(&t);
-        o->o = loss_grad_ssim_base(t);
-        o->ssim_alpha = t.ssim_alpha;
-        why = loss_grad_ssim_refusal(t);
-        if (!why) why = ssim_range_refusal(a.range_mode, a.ranges);
-    } else if (a.kind == kGradKindFt) {
-        if (a.opts) o->o = *static_cast<const b2f_loss_grad_ft_opts *>(a.opts);
-        else (void)b2f_loss_grad_ft_defaults(&o->o);
-        why = loss_grad_ft_refusal(o->o);
-    } else {
-        b2f_loss_grad_opts t;
-        if (a.opts) t = *static_cast<const b2f_loss_grad_opts *>(a.opts);
-        else (void)b2f_loss_grad_defaults(&t);
-        o->o = loss_grad_ft_from(t);
-        why = loss_grad_refusal(t);
-    }
-    return why ? fail(w + ": " + why) : 0;
 }
 
 namespace {
@@ -386,221 +318,248 @@ int timed_launch(b2f_ctx *c, hipStream_t s, const char *name, Launch launch)
 
 }  // namespace
 
-// the records of n images on s: k.words = B2F_LOSS_WORDS, B2F_LOSS_FT_WORDS with the fine-tuning terms behind them, or B2F_LOSS_SSIM_WORDS
-// with the ranges and the SSIM + L1 sums behind them.  Builds R_1 .. R_{L-1} in the context's workspace, where
-// table_loss_grad_run(..., with_pyr = false) on the same arguments and stream finds them.
 int b2f::table_loss_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, int L, bool past, int n, int H, int W, const float *dev_ref,
-                        size_t ref_stride, double flow_scale, unsigned long long *dev_loss, const LossKind &k)
+                        size_t ref_stride, double flow_scale, unsigned long long *dev_loss, const LossSpec &d)
 {
-    const int words = k.words;
     CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
     float *pyr = (float *)c->loss_pyr.dev;
     CHK(timed_launch(c, s, "table_loss", [&] {
-        return launch_table_loss(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s, words);
+        return launch_table_loss(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s, d.words());
     }));
-    if (k.ssim()) {
+    if (d.ranged())
         CHK(timed_launch(c, s, "table_loss_range", [&] {
-            return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, k.range_mode, k.ranges, dev_loss, s);
+            return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, d.range_mode, d.ranges, dev_loss, s, d.obj == kLossPlain);
         }));
-        return timed_launch(c, s, "table_loss_ssim", [&] {
-            return launch_table_loss_ssim_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
-        });
-    }
-    if (k.plain()) {
-        CHK(timed_launch(c, s, "table_loss_range", [&] {
-            return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, k.range_mode, k.ranges, dev_loss, s, true);
-        }));
-        return timed_launch(c, s, "table_loss_plain", [&] {
-            return launch_table_loss_plain_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
-        });
-    }
-    if (words != B2F_LOSS_FT_WORDS) return 0;
-    return timed_launch(c, s, "table_loss_ft", [&] {
-        return launch_table_loss_ft_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
+    if (d.obj == kLossPme) return 0;
+    return timed_launch(c, s, d.terms_row(), [&] {
+        return d.obj == kLossSsim    ? launch_table_loss_ssim_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s)
+               : d.obj == kLossPlain ? launch_table_loss_plain_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s)
+                                     : launch_table_loss_ft_terms(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, dev_loss, s);
     });
 }
 
-// b2f_table_loss_grad_device / _grad_ft_device / _grad_ssim_device on checked options; dev_loss: the records table_loss_run has written
-// on s (it has built R_1 .. R_{L-1}, and with kGradKindSsim the ranges), or nullptr: both are made here
 int b2f::table_loss_grad_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
-                             const float *dev_ref, size_t ref_stride, double flow_scale, const GradOpts &o, unsigned long long *dev_loss)
+                             const float *dev_ref, size_t ref_stride, double flow_scale, const LossSpec &d, unsigned long long *dev_loss)
 {
+    const bool plain = d.obj == kLossPlain;
     GradFtCoef coef[kLossMaxLevels];
     GradCoef first[kLossMaxLevels];
     GradSsimCoef ssim[kLossMaxLevels];
+    GradPlainCoef plainc[kLossMaxLevels];
     for (int j = 0; j < L; ++j) {
-        loss_grad_ft_coef(o.o, j, H >> j, W >> j, &coef[j]);
+        loss_grad_ft_coef(d.o, j, H >> j, W >> j, &coef[j]);
         first[j] = coef[j].k;
-        loss_grad_ssim_coef(o.o, o.ssim_alpha, j, H >> j, W >> j, &ssim[j]);
+        loss_grad_ssim_coef(d.o, d.ssim_alpha, j, H >> j, W >> j, &ssim[j]);
+        if (plain) loss_grad_plain_coef(d.o, d.plain_criterion, d.plain_penalty, d.ssim_alpha, j, H >> j, W >> j, &plainc[j]);
     }
     CHK(ensure_dev_work(c->loss_pyr, table_loss_pyramid_floats(L, n, H, W) * sizeof(float)));
     if (!dev_loss) HIPCHK(launch_table_loss_pyramid(L, n, H, W, dev_ref, ref_stride, (float *)c->loss_pyr.dev, s));
     const float *pyr = (const float *)c->loss_pyr.dev;
-    if (o.kind == kGradKindPlain) {
-        GradPlainCoef plain[kLossMaxLevels];
-        for (int j = 0; j < L; ++j) loss_grad_plain_coef(o.o, o.plain_criterion, o.plain_penalty, o.ssim_alpha, j, H >> j, W >> j, &plain[j]);
-        const unsigned long long *rec = dev_loss;
-        // no records asked for: the ranges, where the criterion reads them, into a zeroed record buffer of the context
-        if (!rec && o.plain_criterion == B2F_PLAIN_SSIM && o.o.pme != 0.0) {
-            const size_t bytes = (size_t)n * L * B2F_LOSS_PLAIN_WORDS * sizeof(unsigned long long);
-            CHK(ensure_dev_work(c->loss_rec, bytes));
-            unsigned long long *scratch = (unsigned long long *)c->loss_rec.dev;
-            HIPCHK(hipMemsetAsync(scratch, 0, bytes, s));
-            CHK(timed_launch(c, s, "table_loss_range", [&] {
-                return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, o.rec.range_mode, o.rec.ranges, scratch, s, true);
-            }));
-            rec = scratch;
-        }
-        return timed_launch(c, s, "table_loss_grad_plain", [&] {
-            const hipError_t e = launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s, true);
-            return e != hipSuccess ? e : launch_table_loss_grad_plain(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, plain, rec, s);
-        });
+    const unsigned long long *rec = dev_loss;
+    // no records asked for: the ranges, where the criterion reads them (the SSIM + L1 term always, the plain terms with B2F_PLAIN_SSIM and a
+    // pme weight), into a zeroed record buffer of the context, by the same two kernels
+    if (d.ranged() && !rec && (!plain || (d.plain_criterion == B2F_PLAIN_SSIM && d.o.pme != 0.0))) {
+        const size_t bytes = (size_t)n * L * d.words() * sizeof(unsigned long long);
+        CHK(ensure_dev_work(c->loss_rec, bytes));
+        unsigned long long *scratch = (unsigned long long *)c->loss_rec.dev;
+        HIPCHK(hipMemsetAsync(scratch, 0, bytes, s));
+        CHK(timed_launch(c, s, "table_loss_range", [&] {
+            return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, d.range_mode, d.ranges, scratch, s, plain);
+        }));
+        rec = scratch;
     }
-    if (o.kind == kGradKindSsim) {
-        const unsigned long long *rec = dev_loss;
-        if (!rec) {   // no records asked for: the ranges into a zeroed record buffer of the context, by the same two kernels
-            const size_t bytes = (size_t)n * L * B2F_LOSS_SSIM_WORDS * sizeof(unsigned long long);
-            CHK(ensure_dev_work(c->loss_rec, bytes));
-            unsigned long long *scratch = (unsigned long long *)c->loss_rec.dev;
-            HIPCHK(hipMemsetAsync(scratch, 0, bytes, s));
-            CHK(timed_launch(c, s, "table_loss_range", [&] {
-                return launch_table_loss_range(dev_table, L, past, n, H, W, dev_ref, ref_stride, pyr, o.rec.range_mode, o.rec.ranges, scratch, s);
-            }));
-            rec = scratch;
-        }
-        return timed_launch(c, s, "table_loss_grad_ssim", [&] {
-            const hipError_t e = launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s, true);
-            return e != hipSuccess ? e : launch_table_loss_grad_ssim(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, ssim, rec, s);
-        });
-    }
-    const bool ft = o.kind == kGradKindFt;
-    return timed_launch(c, s, ft ? "table_loss_grad_ft" : "table_loss_grad", [&] {
-        return ft ? launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s)
-                  : launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, first, s);
+    return timed_launch(c, s, d.grad_row(), [&] {
+        if (d.obj == kLossPme) return launch_table_loss_grad(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, first, s);
+        // (ssim, plain: the flow planes by the fine-tuning kernel, the other planes by the objective's own)
+        const hipError_t e = launch_table_loss_grad_ft(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, coef, s, d.ranged());
+        if (e != hipSuccess || !d.ranged()) return e;
+        return plain ? launch_table_loss_grad_plain(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, plainc, rec, s)
+                     : launch_table_loss_grad_ssim(dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, pyr, flow_scale, ssim, rec, s);
     });
+}
+
+int b2f::table_loss_dispatch(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, unsigned long long *dev_loss, const LossSpec &d,
+                             int L, bool past, int n, int H, int W, const float *dev_ref, size_t ref_stride, double flow_scale)
+{
+    if (d.is_epe()) return table_loss_epe_run(c, s, dev_table, dev_grad, L, past, n, H, W, flow_scale, d, dev_loss);
+    if (dev_loss) CHK(table_loss_run(c, s, dev_table, L, past, n, H, W, dev_ref, ref_stride, flow_scale, dev_loss, d));
+    if (dev_grad) CHK(table_loss_grad_run(c, s, dev_table, dev_grad, L, past, n, H, W, dev_ref, ref_stride, flow_scale, d, dev_loss));
+    return 0;
+}
+
+int b2f::table_loss_device(const std::string &w, LossSpec d, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
+                           double flow_scale, unsigned long long *dev_loss, float *const *dev_grad, void *stream)
+{
+    const bool epe = d.is_epe();
+    const char *why;
+    // (two refusals keep the place they had when the entries were written one by one: a *_grad* entry looks at its options before its
+    // context, and the supervised one at the model before the table)
+    if (!epe && d.grad_entry && (why = d.resolve(0))) return fail(w + ": " + why);
+    if (!c) return fail(w + ": null context");
+    if (epe && (why = d.model_refusal(c))) return fail(w + ": " + why);
+    const int per = level_size(c, n_outs);
+    if (!per) return fail(w + ": " + kTableSizeRefusal);
+    int L = 0;
+    CHK(check_table(w, d, dev_table, dev_grad, dev_loss, dev_ref, n_outs, per, n, H, W, flow_scale, &L));
+    if (!epe && (why = d.model_refusal(c))) return fail(w + ": " + why);
+    if (n > 65535) return fail(w + ": at most 65535 images per call");
+    std::vector<const void *> ptrs = {dev_ref, dev_loss, d.gt_flow};
+    for (int i = 0; i < n_outs; ++i) {
+        ptrs.push_back(dev_table[i]);
+        if (dev_grad) ptrs.push_back(dev_grad[i]);
+    }
+    const size_t aligned = ptrs.size();   // the byte planes may lie anywhere
+    ptrs.push_back(d.valid);
+    ptrs.push_back(d.gt_occ);
+    CHK(check_device_pointers(w, c, d.host_entries(), ptrs.data(), ptrs.size(), aligned));
+    return table_loss_dispatch(c, stream ? (hipStream_t)stream : c->stream, dev_table, dev_grad, dev_loss, d, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W,
+                               flow_scale);
+}
+
+int b2f::table_loss_op(const std::string &w, LossSpec d, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref,
+                       double flow_scale, unsigned long long *loss, float *const *grad)
+{
+    const bool epe = d.is_epe();
+    OpStage st(c, w);
+    CHK(st.begin(true, "null context"));
+    const int per = level_size(c, n_outs);
+    if (!per) return fail(w + ": " + kTableSizeRefusal);
+    int L = 0;
+    CHK(check_table(w, d, table, grad, loss, ref, n_outs, per, n, H, W, flow_scale, &L));
+    const char *why = epe ? nullptr : d.model_refusal(c);   // (the supervised objective leaves the model to the device entry below)
+    if (why) return fail(w + ": " + why);
+    // the table and, where there is one, the gradient table, tensor by tensor; then the other inputs; then the records
+    std::vector<const float *> ptrs((size_t)n_outs);
+    std::vector<float *> gptrs((size_t)n_outs);
+    float *df;
+    for (int i = 0; i < n_outs; ++i) {
+        CHK(st.in(table[i], table_floats(i, per, n, H, W), "table", &df));
+        ptrs[(size_t)i] = df;
+        if (grad) CHK(st.out(table_floats(i, per, n, H, W), "grad", &gptrs[(size_t)i]));
+    }
+    const size_t HW = (size_t)H * W, nl = (size_t)n * L * d.words();
+    unsigned char *dv = nullptr, *dl = nullptr;
+    unsigned long long *dloss = nullptr;
+    LossSpec dd = d;
+    if (epe) {
+        CHK(st.in(d.gt_flow, (size_t)n * 2 * HW, "gt_flow", &df));
+        if (d.valid) CHK(st.in(d.valid, (size_t)n * HW, "valid", &dv));
+        if (d.gt_occ) CHK(st.in(d.gt_occ, (size_t)n * HW, "gt_occ", &dl));
+        dd.gt_flow = df; dd.valid = dv; dd.gt_occ = dl;
+    } else {
+        CHK(st.in(ref, (size_t)n * 3 * HW, "ref", &df));
+    }
+    if (loss) CHK(st.out(nl, "loss", &dloss));
+    // (the supervised objective's op entry has always spoken as its device entry from here on)
+    CHK(table_loss_device(epe ? "b2f_table_loss_epe_device" : w, dd, c, ptrs.data(), n_outs, n, H, W, epe ? nullptr : df, flow_scale, dloss,
+                          grad ? gptrs.data() : nullptr, nullptr));
+    CHK(st.finish());
+    if (loss) CHK(st.get(loss, dloss, nl));
+    for (int i = 0; grad && i < n_outs; ++i) CHK(st.get(grad[i], gptrs[(size_t)i], table_floats(i, per, n, H, W)));
+    return 0;
+}
+
+// every b2f_table_loss*_host entry: the checks, then the objective's host implementation (b2f_host.cpp)
+int b2f::table_loss_host_entry(const std::string &w, LossSpec d, const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
+                               double flow_scale, unsigned long long *loss, float *const *grad, int rescale)
+{
+    int L = 0;
+    const bool past = past_flow != 0;
+    CHK(check_table(w, d, table, grad, loss, ref, n_outs, past ? 5 : 4, n, H, W, flow_scale, &L));
+    if (d.is_epe())
+        table_loss_epe_host(table, L, past, n, H, W, d.gt_flow, d.valid, d.gt_occ, flow_scale, rescale != 0, d.epe, d.count_mode, d.counts, loss, grad);
+    else if (d.grad_entry && d.obj == kLossPlain)
+        table_loss_grad_plain_host(table, L, past, n, H, W, ref, flow_scale, d.o, d.plain_criterion, d.plain_penalty, d.ssim_alpha, d.range_mode, d.ranges, grad);
+    else if (d.grad_entry && d.obj == kLossSsim)
+        table_loss_grad_ssim_host(table, L, past, n, H, W, ref, flow_scale, d.o, d.ssim_alpha, d.range_mode, d.ranges, grad);
+    else if (d.grad_entry)
+        table_loss_grad_ft_host(table, L, past, n, H, W, ref, flow_scale, d.o, grad);
+    else if (d.obj == kLossPlain)
+        table_loss_plain_host(table, L, past, n, H, W, ref, flow_scale, d.range_mode, d.ranges, loss);
+    else if (d.obj == kLossSsim)
+        table_loss_ssim_host(table, L, past, n, H, W, ref, flow_scale, d.range_mode, d.ranges, loss);
+    else if (d.obj == kLossFt)
+        table_loss_ft_host(table, L, past, n, H, W, ref, flow_scale, loss);
+    else
+        table_loss_host(table, L, past, n, H, W, ref, flow_scale, loss);
+    return 0;
 }
 
 namespace {
 
-// b2f_table_loss_grad_device, _grad_ft_device and _grad_ssim_device on checked options (resolve_grad_opts)
-int table_loss_grad_device(const std::string &w, b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref,
-                           double flow_scale, const GradOpts &o, float *const *dev_grad, void *stream)
+// the first-order fields of the *_grad_ssim / *_grad_plain options from the defaults of b2f_loss_grad_opts
+template <class Opts>
+void first_order_defaults(Opts *o)
 {
-    if (!c) return fail(w + ": null context");
-    const int per = level_size(c, n_outs);
-    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
-    int L = 0;
-    CHK(check_table_loss(w, dev_table, n_outs, per, n, H, W, dev_ref, flow_scale, dev_grad, &L));
-    CHK(check_grad_table(w, dev_table, n_outs, dev_ref, dev_grad));
-    CHK(check_plain_context(w, c, o.kind == kGradKindPlain));
-    if (n > 65535) return fail(w + ": at most 65535 images per call");
-    uintptr_t bits = (uintptr_t)dev_ref;
-    for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i] | (uintptr_t)dev_grad[i];
-    if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    const std::string use = o.kind == kGradKindPlain ? "b2f_op_table_loss_grad_plain / b2f_table_loss_grad_plain_host"
-                            : o.kind == kGradKindSsim ? "b2f_op_table_loss_grad_ssim / b2f_table_loss_grad_ssim_host"
-                            : o.kind == kGradKindFt ? "b2f_op_table_loss_grad_ft / b2f_table_loss_grad_ft_host"
-                                                    : "b2f_op_table_loss_grad / b2f_table_loss_grad_host";
-    if (host_memory(dev_ref)) return fail(w + ": host memory passed to a device entry point (use " + use + ")");
-    for (int i = 0; i < n_outs; ++i)
-        if (host_memory(dev_table[i]) || host_memory(dev_grad[i])) return fail(w + ": host memory passed to a device entry point (use " + use + ")");
-    return table_loss_grad_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, dev_grad, L, per == 5, n, H, W, dev_ref, (size_t)3 * H * W, flow_scale,
-                               o, nullptr);
-}
-
-// b2f_table_loss_grad_host, b2f_table_loss_grad_ft_host and b2f_table_loss_grad_ssim_host
-int table_loss_grad_host_entry(const std::string &w, const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref,
-                               double flow_scale, const GradArgs &a, float *const *grad)
-{
-    int L = 0;
-    CHK(check_table_loss(w, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, grad, &L));
-    CHK(check_grad_table(w, table, n_outs, ref, grad));
-    GradOpts o;
-    CHK(resolve_grad_opts(w, a, &o));
-    if (o.kind == kGradKindPlain)
-        table_loss_grad_plain_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, o.plain_criterion, o.plain_penalty, o.ssim_alpha, o.rec.range_mode,
-                                   o.rec.ranges, grad);
-    else if (o.kind == kGradKindSsim)
-        table_loss_grad_ssim_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, o.ssim_alpha, o.rec.range_mode, o.rec.ranges, grad);
-    else
-        table_loss_grad_ft_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, o.o, grad);
-    return 0;
-}
-
-// b2f_op_table_loss_grad, b2f_op_table_loss_grad_ft and b2f_op_table_loss_grad_ssim
-int op_table_loss_grad(const std::string &w, b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
-                       const GradArgs &a, float *const *grad)
-{
-    OpStage st(c, w);
-    CHK(st.begin(true, "null context"));
-    const int per = level_size(c, n_outs);
-    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
-    int L = 0;
-    CHK(check_table_loss(w, table, n_outs, per, n, H, W, ref, flow_scale, grad, &L));
-    CHK(check_grad_table(w, table, n_outs, ref, grad));
-    GradOpts o;
-    CHK(resolve_grad_opts(w, a, &o));
-    CHK(check_plain_context(w, c, o.kind == kGradKindPlain));
-    std::vector<const float *> ptrs((size_t)n_outs);
-    std::vector<float *> gptrs((size_t)n_outs);
-    std::vector<size_t> floats((size_t)n_outs);
-    float *dr;
-    for (int i = 0; i < n_outs; ++i) {
-        const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
-        floats[(size_t)i] = (size_t)n * ch * (H >> j) * (W >> j);
-        CHK(st.in(table[i], floats[(size_t)i], "table", &dr)); CHK(st.out(floats[(size_t)i], "grad", &gptrs[(size_t)i]));
-        ptrs[(size_t)i] = dr;
-    }
-    CHK(st.in(ref, (size_t)n * 3 * H * W, "ref", &dr));
-    CHK(table_loss_grad_device(w, c, ptrs.data(), n_outs, n, H, W, dr, flow_scale, o, gptrs.data(), nullptr));
-    CHK(st.finish());
-    for (int i = 0; i < n_outs; ++i) CHK(st.get(grad[i], gptrs[(size_t)i], floats[(size_t)i]));
-    return 0;
+    b2f_loss_grad_opts t;
+    (void)b2f_loss_grad_defaults(&t);
+    o->smooth_flow = t.smooth_flow; o->const_vel = t.const_vel; o->pme = t.pme; o->smooth_occ = t.smooth_occ; o->prior_occ = t.prior_occ;
+    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = t.level_weights[j];
+    o->size_average = t.size_average;
+    o->smooth_second_order = 0;
 }
 
 }  // namespace
 
+// Every entry below builds its descriptor and calls the shared body.  *_host: on the CPU; *_device: on device pointers; b2f_op_*: on host
+// pointers through the GPU.
 extern "C" {
 
+// ---- test.lua:266-297, and its gradient table of train.lua:428-468 (b2f_tableloss_grad.hip) ----
 // opts.lua:61-73, test.lua:29-31
 int b2f_loss_grad_defaults(b2f_loss_grad_opts *o)
 {
     if (!o) return fail("b2f_loss_grad_defaults: null argument");
-    const double lw[kLossMaxLevels] = {0.005, 0.01, 0.02, 0.08, 0.32, 0.64, 1.28};
     o->smooth_flow = 1.0; o->const_vel = 1.0; o->pme = 1.0; o->smooth_occ = 0.1; o->prior_occ = 0.1;
-    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = lw[j];
+    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = kLossLevelWeights[j];
     o->size_average = 0;
     return 0;
 }
 
-// train.lua:428-468 on the CPU
+int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                        unsigned long long *loss) try
+{
+    return table_loss_host_entry(__func__, loss_records(kLossPme), table, n_outs, n, H, W, past_flow, ref, flow_scale, loss, nullptr);
+}
+B2F_CATCH("b2f_table_loss_host")
+
+int b2f_table_loss_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                          unsigned long long *dev_loss, void *stream) try
+{
+    return table_loss_device(__func__, loss_records(kLossPme), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, nullptr, stream);
+}
+B2F_CATCH("b2f_table_loss_device")
+
+int b2f_op_table_loss(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                      unsigned long long *loss) try
+{
+    return table_loss_op(__func__, loss_records(kLossPme), c, table, n_outs, n, H, W, ref, flow_scale, loss, nullptr);
+}
+B2F_CATCH("b2f_op_table_loss")
+
 int b2f_table_loss_grad_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
                              const b2f_loss_grad_opts *opts, float *const *grad) try
 {
-    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, grad_args(opts), grad);
+    return table_loss_host_entry(__func__, loss_grad(opts), table, n_outs, n, H, W, past_flow, ref, flow_scale, nullptr, grad);
 }
 B2F_CATCH("b2f_table_loss_grad_host")
 
-// train.lua:428-468 on device pointers
 int b2f_table_loss_grad_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
                                const b2f_loss_grad_opts *opts, float *const *dev_grad, void *stream) try
 {
-    GradOpts o;
-    CHK(resolve_grad_opts(__func__, grad_args(opts), &o));
-    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
+    return table_loss_device(__func__, loss_grad(opts), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, nullptr, dev_grad, stream);
 }
 B2F_CATCH("b2f_table_loss_grad_device")
 
-// train.lua:428-468 on host pointers through the GPU
 int b2f_op_table_loss_grad(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                            const b2f_loss_grad_opts *opts, float *const *grad) try
 {
-    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, grad_args(opts), grad);
+    return table_loss_op(__func__, loss_grad(opts), c, table, n_outs, n, H, W, ref, flow_scale, nullptr, grad);
 }
 B2F_CATCH("b2f_op_table_loss_grad")
 
-// ---- the same with the fine-tuning criteria of README.md:89-102 (b2f_tableloss_grad_ft.hip) ----
+// ---- with the fine-tuning terms of README.md:89-102 in words 16 .. 23 (b2f_tableloss_ft.hip) and their criteria in the gradient
+// (b2f_tableloss_grad_ft.hip) ----
 int b2f_loss_grad_ft_defaults(b2f_loss_grad_ft_opts *o)
 {
     if (!o) return fail("b2f_loss_grad_ft_defaults: null argument");
@@ -612,207 +571,152 @@ int b2f_loss_grad_ft_defaults(b2f_loss_grad_ft_opts *o)
     return 0;
 }
 
-int b2f_table_loss_grad_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
-                                const b2f_loss_grad_ft_opts *opts, float *const *grad) try
-{
-    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, grad_args(opts), grad);
-}
-B2F_CATCH("b2f_table_loss_grad_ft_host")
-
-int b2f_table_loss_grad_ft_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
-                                  const b2f_loss_grad_ft_opts *opts, float *const *dev_grad, void *stream) try
-{
-    GradOpts o;
-    CHK(resolve_grad_opts(__func__, grad_args(opts), &o));
-    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
-}
-B2F_CATCH("b2f_table_loss_grad_ft_device")
-
-int b2f_op_table_loss_grad_ft(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
-                              const b2f_loss_grad_ft_opts *opts, float *const *grad) try
-{
-    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, grad_args(opts), grad);
-}
-B2F_CATCH("b2f_op_table_loss_grad_ft")
-
-// ---- the same with the SSIM + L1 photometric term of criterions/OSSIML1Criterion.lua:165-302 (b2f_tableloss_grad_ssim.hip) ----
-int b2f_loss_grad_ssim_defaults(b2f_loss_grad_ssim_opts *o)
-{
-    if (!o) return fail("b2f_loss_grad_ssim_defaults: null argument");
-    b2f_loss_grad_opts t;
-    (void)b2f_loss_grad_defaults(&t);
-    o->smooth_flow = t.smooth_flow; o->const_vel = t.const_vel; o->pme = t.pme; o->smooth_occ = t.smooth_occ; o->prior_occ = t.prior_occ;
-    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = t.level_weights[j];
-    o->size_average = t.size_average;
-    o->smooth_second_order = 0;
-    o->ssim_alpha = 0.85;
-    return 0;
-}
-
-int b2f_table_loss_grad_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
-                                  const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode, const float *ranges) try
-{
-    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, grad_args(opts, range_mode, ranges), grad);
-}
-B2F_CATCH("b2f_table_loss_grad_ssim_host")
-
-int b2f_table_loss_grad_ssim_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
-                                    const b2f_loss_grad_ssim_opts *opts, float *const *dev_grad, void *stream, int range_mode, const float *ranges) try
-{
-    GradOpts o;
-    CHK(resolve_grad_opts(__func__, grad_args(opts, range_mode, ranges), &o));
-    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
-}
-B2F_CATCH("b2f_table_loss_grad_ssim_device")
-
-int b2f_op_table_loss_grad_ssim(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
-                                const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode, const float *ranges) try
-{
-    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, grad_args(opts, range_mode, ranges), grad);
-}
-B2F_CATCH("b2f_op_table_loss_grad_ssim")
-
-// test.lua:266-297 on the CPU
-int b2f_table_loss_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
-                        unsigned long long *loss) try
-{
-    int L = 0;
-    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
-    table_loss_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, loss);
-    return 0;
-}
-B2F_CATCH("b2f_table_loss_host")
-
-// test.lua:266-297 on device pointers
-int b2f_table_loss_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
-                          unsigned long long *dev_loss, void *stream) try
-{
-    return table_loss_device(__func__, loss_kind(false), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
-}
-B2F_CATCH("b2f_table_loss_device")
-
-// test.lua:266-297 on host pointers through the GPU
-int b2f_op_table_loss(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
-                      unsigned long long *loss) try
-{
-    return op_table_loss(__func__, loss_kind(false), c, table, n_outs, n, H, W, ref, flow_scale, loss);
-}
-B2F_CATCH("b2f_op_table_loss")
-
-// ---- the same three with the fine-tuning terms of README.md:89-102 in words 16 .. 23 (b2f_tableloss_ft.hip) ----
 int b2f_table_loss_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
                            unsigned long long *loss) try
 {
-    int L = 0;
-    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
-    table_loss_ft_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, loss);
-    return 0;
+    return table_loss_host_entry(__func__, loss_records(kLossFt), table, n_outs, n, H, W, past_flow, ref, flow_scale, loss, nullptr);
 }
 B2F_CATCH("b2f_table_loss_ft_host")
 
 int b2f_table_loss_ft_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
                              unsigned long long *dev_loss, void *stream) try
 {
-    return table_loss_device(__func__, loss_kind(true), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
+    return table_loss_device(__func__, loss_records(kLossFt), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, nullptr, stream);
 }
 B2F_CATCH("b2f_table_loss_ft_device")
 
 int b2f_op_table_loss_ft(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                          unsigned long long *loss) try
 {
-    return op_table_loss(__func__, loss_kind(true), c, table, n_outs, n, H, W, ref, flow_scale, loss);
+    return table_loss_op(__func__, loss_records(kLossFt), c, table, n_outs, n, H, W, ref, flow_scale, loss, nullptr);
 }
 B2F_CATCH("b2f_op_table_loss_ft")
 
-// ---- the same three with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua:47-163 in words 16 .. 25 (b2f_tableloss_ssim.hip) ----
+int b2f_table_loss_grad_ft_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                                const b2f_loss_grad_ft_opts *opts, float *const *grad) try
+{
+    return table_loss_host_entry(__func__, loss_grad(opts), table, n_outs, n, H, W, past_flow, ref, flow_scale, nullptr, grad);
+}
+B2F_CATCH("b2f_table_loss_grad_ft_host")
+
+int b2f_table_loss_grad_ft_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                                  const b2f_loss_grad_ft_opts *opts, float *const *dev_grad, void *stream) try
+{
+    return table_loss_device(__func__, loss_grad(opts), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, nullptr, dev_grad, stream);
+}
+B2F_CATCH("b2f_table_loss_grad_ft_device")
+
+int b2f_op_table_loss_grad_ft(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                              const b2f_loss_grad_ft_opts *opts, float *const *grad) try
+{
+    return table_loss_op(__func__, loss_grad(opts), c, table, n_outs, n, H, W, ref, flow_scale, nullptr, grad);
+}
+B2F_CATCH("b2f_op_table_loss_grad_ft")
+
+// ---- with the SSIM + L1 sums of criterions/OSSIML1Criterion.lua:47-163 in words 16 .. 25 (b2f_tableloss_ssim.hip) and that term in the
+// gradient (lines 165-302; b2f_tableloss_grad_ssim.hip) ----
+int b2f_loss_grad_ssim_defaults(b2f_loss_grad_ssim_opts *o)
+{
+    if (!o) return fail("b2f_loss_grad_ssim_defaults: null argument");
+    first_order_defaults(o);
+    o->ssim_alpha = 0.85;
+    return 0;
+}
+
 int b2f_table_loss_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
                              unsigned long long *loss, int range_mode, const float *ranges) try
 {
-    int L = 0;
-    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
-    CHK(check_loss_kind(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}));
-    table_loss_ssim_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, range_mode, ranges, loss);
-    return 0;
+    return table_loss_host_entry(__func__, loss_records(kLossSsim, range_mode, ranges), table, n_outs, n, H, W, past_flow, ref, flow_scale, loss, nullptr);
 }
 B2F_CATCH("b2f_table_loss_ssim_host")
 
 int b2f_table_loss_ssim_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
                                unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges) try
 {
-    return table_loss_device(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
+    return table_loss_device(__func__, loss_records(kLossSsim, range_mode, ranges), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, nullptr, stream);
 }
 B2F_CATCH("b2f_table_loss_ssim_device")
 
 int b2f_op_table_loss_ssim(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                            unsigned long long *loss, int range_mode, const float *ranges) try
 {
-    return op_table_loss(__func__, LossKind{B2F_LOSS_SSIM_WORDS, range_mode, ranges}, c, table, n_outs, n, H, W, ref, flow_scale, loss);
+    return table_loss_op(__func__, loss_records(kLossSsim, range_mode, ranges), c, table, n_outs, n, H, W, ref, flow_scale, loss, nullptr);
 }
 B2F_CATCH("b2f_op_table_loss_ssim")
 
-// ---- the photometric terms without occlusion masking (criterions/MBCCriterion.lua, MSSIML1Criterion.lua): records of 40 words
+int b2f_table_loss_grad_ssim_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                                  const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode, const float *ranges) try
+{
+    return table_loss_host_entry(__func__, loss_grad(opts, range_mode, ranges), table, n_outs, n, H, W, past_flow, ref, flow_scale, nullptr, grad);
+}
+B2F_CATCH("b2f_table_loss_grad_ssim_host")
+
+int b2f_table_loss_grad_ssim_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                                    const b2f_loss_grad_ssim_opts *opts, float *const *dev_grad, void *stream, int range_mode, const float *ranges) try
+{
+    return table_loss_device(__func__, loss_grad(opts, range_mode, ranges), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, nullptr, dev_grad, stream);
+}
+B2F_CATCH("b2f_table_loss_grad_ssim_device")
+
+int b2f_op_table_loss_grad_ssim(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                                const b2f_loss_grad_ssim_opts *opts, float *const *grad, int range_mode, const float *ranges) try
+{
+    return table_loss_op(__func__, loss_grad(opts, range_mode, ranges), c, table, n_outs, n, H, W, ref, flow_scale, nullptr, grad);
+}
+B2F_CATCH("b2f_op_table_loss_grad_ssim")
+
+// ---- with the photometric terms without occlusion masking (criterions/MBCCriterion.lua, MSSIML1Criterion.lua): records of 40 words
 // (b2f_tableloss_plain.hip) and the gradient table (b2f_tableloss_grad_plain.hip) ----
-int b2f_table_loss_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
-                              unsigned long long *loss, int range_mode, const float *ranges) try
-{
-    int L = 0;
-    CHK(check_table_loss(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, ref, flow_scale, loss, &L));
-    CHK(check_loss_kind(__func__, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}));
-    table_loss_plain_host(table, L, past_flow != 0, n, H, W, ref, flow_scale, range_mode, ranges, loss);
-    return 0;
-}
-B2F_CATCH("b2f_table_loss_plain_host")
-
-int b2f_table_loss_plain_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
-                                unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges) try
-{
-    return table_loss_device(__func__, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, stream);
-}
-B2F_CATCH("b2f_table_loss_plain_device")
-
-int b2f_op_table_loss_plain(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
-                            unsigned long long *loss, int range_mode, const float *ranges) try
-{
-    return op_table_loss(__func__, LossKind{B2F_LOSS_PLAIN_WORDS, range_mode, ranges}, c, table, n_outs, n, H, W, ref, flow_scale, loss);
-}
-B2F_CATCH("b2f_op_table_loss_plain")
-
 // opts.lua:61-73,85; model.lua:149-159,189-190
 int b2f_loss_grad_plain_defaults(b2f_loss_grad_plain_opts *o)
 {
     if (!o) return fail("b2f_loss_grad_plain_defaults: null argument");
-    b2f_loss_grad_opts t;
-    (void)b2f_loss_grad_defaults(&t);
-    o->smooth_flow = t.smooth_flow; o->const_vel = t.const_vel; o->pme = t.pme; o->smooth_occ = t.smooth_occ; o->prior_occ = t.prior_occ;
-    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = t.level_weights[j];
-    o->size_average = t.size_average;
-    o->smooth_second_order = 0;
+    first_order_defaults(o);
     o->criterion = B2F_PLAIN_BCC;
     o->penalty = B2F_PLAIN_L1;
     o->ssim_alpha = 0.85;
     return 0;
 }
 
+int b2f_table_loss_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
+                              unsigned long long *loss, int range_mode, const float *ranges) try
+{
+    return table_loss_host_entry(__func__, loss_records(kLossPlain, range_mode, ranges), table, n_outs, n, H, W, past_flow, ref, flow_scale, loss, nullptr);
+}
+B2F_CATCH("b2f_table_loss_plain_host")
+
+int b2f_table_loss_plain_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
+                                unsigned long long *dev_loss, void *stream, int range_mode, const float *ranges) try
+{
+    return table_loss_device(__func__, loss_records(kLossPlain, range_mode, ranges), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, dev_loss, nullptr, stream);
+}
+B2F_CATCH("b2f_table_loss_plain_device")
+
+int b2f_op_table_loss_plain(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
+                            unsigned long long *loss, int range_mode, const float *ranges) try
+{
+    return table_loss_op(__func__, loss_records(kLossPlain, range_mode, ranges), c, table, n_outs, n, H, W, ref, flow_scale, loss, nullptr);
+}
+B2F_CATCH("b2f_op_table_loss_plain")
+
 int b2f_table_loss_grad_plain_host(const float *const *table, int n_outs, int n, int H, int W, int past_flow, const float *ref, double flow_scale,
                                    const b2f_loss_grad_plain_opts *opts, float *const *grad, int range_mode, const float *ranges) try
 {
-    return table_loss_grad_host_entry(__func__, table, n_outs, n, H, W, past_flow, ref, flow_scale, grad_args(opts, range_mode, ranges), grad);
+    return table_loss_host_entry(__func__, loss_grad(opts, range_mode, ranges), table, n_outs, n, H, W, past_flow, ref, flow_scale, nullptr, grad);
 }
 B2F_CATCH("b2f_table_loss_grad_plain_host")
 
 int b2f_table_loss_grad_plain_device(b2f_ctx *c, const float *const *dev_table, int n_outs, int n, int H, int W, const float *dev_ref, double flow_scale,
                                      const b2f_loss_grad_plain_opts *opts, float *const *dev_grad, void *stream, int range_mode, const float *ranges) try
 {
-    GradOpts o;
-    CHK(resolve_grad_opts(__func__, grad_args(opts, range_mode, ranges), &o));
-    return table_loss_grad_device(__func__, c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, o, dev_grad, stream);
+    return table_loss_device(__func__, loss_grad(opts, range_mode, ranges), c, dev_table, n_outs, n, H, W, dev_ref, flow_scale, nullptr, dev_grad, stream);
 }
 B2F_CATCH("b2f_table_loss_grad_plain_device")
 
 int b2f_op_table_loss_grad_plain(b2f_ctx *c, const float *const *table, int n_outs, int n, int H, int W, const float *ref, double flow_scale,
                                  const b2f_loss_grad_plain_opts *opts, float *const *grad, int range_mode, const float *ranges) try
 {
-    return op_table_loss_grad(__func__, c, table, n_outs, n, H, W, ref, flow_scale, grad_args(opts, range_mode, ranges), grad);
+    return table_loss_op(__func__, loss_grad(opts, range_mode, ranges), c, table, n_outs, n, H, W, ref, flow_scale, nullptr, grad);
 }
 B2F_CATCH("b2f_op_table_loss_grad_plain")
 

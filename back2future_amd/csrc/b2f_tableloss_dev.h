@@ -162,4 +162,24 @@ inline bool loss_levels(const float *const *table, float *const *grad, int L, bo
     return true;
 }
 
+// The launcher of the kernels that add their own words to records of record_words words the records' launch has zeroed (the
+// fine-tuning terms, the SSIM + L1 sums, the sums without occlusion masking): one launch per level, of kernel_true on a table with past
+// flows and of kernel_false on one without.  Both are (LevelPtrs, h, w, kd, the level's record of image 0, words from one image to the next).
+template <class Kernel>
+hipError_t launch_terms(Kernel kernel_true, Kernel kernel_false, int record_words, const float *const *table, int L, bool past, int n, int H, int W,
+                        const float *ref, size_t ref_stride, const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s)
+{
+    LossLevel lv[kLossMaxLevels];
+    if (!loss || !loss_levels(table, nullptr, L, past, n, H, W, ref, ref_stride, pyr, flow_scale, lv)) return hipErrorInvalidValue;
+    const Kernel kernel = past ? kernel_true : kernel_false;
+    for (int j = 0; j < L; ++j) {
+        const LossLevel &v = lv[j];
+        hipLaunchKernelGGL(kernel, v.grid, dim3(kLossThreads), 0, s, v.lp, v.h, v.w, v.kd, loss + (size_t)j * record_words,
+                           (size_t)L * record_words);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 }  // namespace b2f

@@ -221,7 +221,7 @@ hipError_t launch_table_loss_epe(const float *const *table, float *const *grad, 
         // the planes of the gradient table that no kernel writes: +0.0
         for (int t = 1; grad && t < per; ++t) {
             if (t == per - 3 && with_occ) continue;
-            if ((e = hipMemsetAsync(grad[(size_t)j * per + t], 0, (size_t)n * (t >= per - 2 ? 3 : 2) * hw * sizeof(float), s)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(grad[(size_t)j * per + t], 0, (size_t)n * table_planes(t, per) * hw * sizeof(float), s)) != hipSuccess) return e;
         }
         EpeLevel a;
         a.f = v.lp.f; a.o = v.lp.o; a.gt = gt_flow; a.valid = valid; a.occ = gt_occ;
@@ -246,80 +246,33 @@ hipError_t launch_table_loss_epe(const float *const *table, float *const *grad, 
 
 }  // namespace b2f
 
-namespace {
-
-// 1 when p is memory the host can read (pageable or page-locked), 0 for device memory
-bool host_memory(const void *p)
-{
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;
-    }
-    return !(a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeArray);
-}
-
-// what the three table entries check without a HIP call: the shape, the table, the options (into *o), the ground truth, the counts, and
-// that no output is an input or another output
-int check_table_loss_epe(const std::string &w, const float *const *table, int n_outs, int per, int n, int H, int W, const float *gt_flow,
-                         const unsigned char *valid, const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode,
-                         const double *counts, const unsigned long long *loss, float *const *grad, b2f_loss_epe_opts *o, int *L)
-{
-    if (!table) return fail(w + ": null argument");
-    if (!loss && !grad) return fail(w + ": loss and grad are both null: nothing to compute");
-    const char *why = table_loss_refusal(n_outs, per, n, H, W, flow_scale, L);
-    if (why) return fail(w + ": " + why);
-    for (int i = 0; i < n_outs; ++i)
-        if (!table[i]) return fail(w + ": null tensor in the table");
-    if (opts) *o = *opts;
-    else (void)b2f_loss_epe_defaults(o);
-    if ((why = loss_epe_refusal(*o, gt_flow, gt_occ, count_mode, counts, *L))) return fail(w + ": " + why);
-    const void *ins[4] = {gt_flow, valid, gt_occ, nullptr};
-    for (int k = 0; k < 3; ++k)
-        if (loss && ins[k] == (const void *)loss) return fail(w + ": loss must not alias an input");
-    for (int i = 0; i < n_outs; ++i) {
-        if (loss && (const void *)table[i] == (const void *)loss) return fail(w + ": loss must not alias an input");
-        if (!grad) continue;
-        if (!grad[i]) return fail(w + ": null tensor in the gradient table");
-        if ((const void *)grad[i] == (const void *)loss) return fail(w + ": the gradient table must not alias loss");
-        for (int k = 0; k < 3; ++k)
-            if ((const void *)grad[i] == ins[k]) return fail(w + ": the gradient table must not alias the ground truth");
-        for (int k = 0; k < n_outs; ++k)
-            if (grad[i] == table[k] || (k != i && grad[i] == grad[k])) return fail(w + ": the gradient table must not alias the table or itself");
-    }
-    return 0;
-}
-
-}  // namespace
-
 // records and / or gradient of n images on s under the profile row table_loss_epe; the counting pass, where one is needed, into c->loss_rec
 int b2f::table_loss_epe_run(b2f_ctx *c, hipStream_t s, const float *const *dev_table, float *const *dev_grad, int L, bool past, int n, int H, int W,
-                            const float *dev_gt_flow, const unsigned char *dev_valid, const unsigned char *dev_gt_occ, double flow_scale,
-                            const b2f_loss_epe_opts &o, int count_mode, const double *counts, unsigned long long *dev_loss)
+                            double flow_scale, const LossSpec &d, unsigned long long *dev_loss)
 {
     unsigned long long *cnt = nullptr;
-    if (dev_grad && o.size_average && count_mode != B2F_EPE_COUNT_GIVEN) {
+    if (dev_grad && d.epe.size_average && d.count_mode != B2F_EPE_COUNT_GIVEN) {
         CHK(ensure_dev_work(c->loss_rec, (size_t)n * L * 2 * sizeof(unsigned long long)));
         cnt = (unsigned long long *)c->loss_rec.dev;
     }
     ProfEvent pe;
-    const bool timed = prof_open(c, s, "table_loss_epe", &pe);
-    const hipError_t e = launch_table_loss_epe(dev_table, dev_grad, L, past, n, H, W, dev_gt_flow, dev_valid, dev_gt_occ, flow_scale, c->g.rescale_flow != 0,
-                                               o, count_mode, counts, cnt, dev_loss, s);
+    const bool timed = prof_open(c, s, d.terms_row(), &pe);
+    const hipError_t e = launch_table_loss_epe(dev_table, dev_grad, L, past, n, H, W, d.gt_flow, d.valid, d.gt_occ, flow_scale, c->g.rescale_flow != 0, d.epe,
+                                               d.count_mode, d.counts, cnt, dev_loss, s);
     if (timed) prof_close(c, s, pe);
     HIPCHK(e);
     return 0;
 }
 
+// The entries build their descriptor and call the bodies every objective shares (b2f_tableloss.hip).
 extern "C" {
 
 // opts.lua (-epe), train.lua:56-58
 int b2f_loss_epe_defaults(b2f_loss_epe_opts *o)
 {
     if (!o) return fail("b2f_loss_epe_defaults: null argument");
-    const double lw[kLossMaxLevels] = {0.005, 0.01, 0.02, 0.08, 0.32, 0.64, 1.28};
     o->epe = 1.0; o->occ = 0.0; o->size_average = 0;
-    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = lw[j];
+    for (int j = 0; j < kLossMaxLevels; ++j) o->level_weights[j] = kLossLevelWeights[j];
     return 0;
 }
 
@@ -328,12 +281,8 @@ int b2f_table_loss_epe_host(const float *const *table, int n_outs, int n, int H,
                             const unsigned char *gt_occ, double flow_scale, int rescale, const b2f_loss_epe_opts *opts, int count_mode,
                             const double *counts, unsigned long long *loss, float *const *grad) try
 {
-    int L = 0;
-    b2f_loss_epe_opts o;
-    CHK(check_table_loss_epe(__func__, table, n_outs, past_flow ? 5 : 4, n, H, W, gt_flow, valid, gt_occ, flow_scale, opts, count_mode, counts, loss, grad,
-                             &o, &L));
-    table_loss_epe_host(table, L, past_flow != 0, n, H, W, gt_flow, valid, gt_occ, flow_scale, rescale != 0, o, count_mode, counts, loss, grad);
-    return 0;
+    return table_loss_host_entry(__func__, loss_epe(gt_flow, valid, gt_occ, opts, count_mode, counts), table, n_outs, n, H, W, past_flow, nullptr, flow_scale,
+                                 loss, grad, rescale);
 }
 B2F_CATCH("b2f_table_loss_epe_host")
 
@@ -342,28 +291,8 @@ int b2f_table_loss_epe_device(b2f_ctx *c, const float *const *dev_table, int n_o
                               const unsigned char *dev_valid, const unsigned char *dev_gt_occ, double flow_scale, const b2f_loss_epe_opts *opts,
                               int count_mode, const double *counts, unsigned long long *dev_loss, float *const *dev_grad, void *stream) try
 {
-    const std::string w = __func__;
-    if (!c) return fail(w + ": null context");
-    if (c->g.two_frame) return fail(w + ": a two_frame model has no occlusions in its table; the table loss is not defined for it");
-    const int own = c->past_flow ? 5 : 4, other = 9 - own;
-    const int per = (n_outs > 0 && n_outs % own == 0) ? own : (n_outs > 0 && n_outs % other == 0) ? other : 0;
-    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
-    int L = 0;
-    b2f_loss_epe_opts o;
-    CHK(check_table_loss_epe(w, dev_table, n_outs, per, n, H, W, dev_gt_flow, dev_valid, dev_gt_occ, flow_scale, opts, count_mode, counts, dev_loss,
-                             dev_grad, &o, &L));
-    if (n > 65535) return fail(w + ": at most 65535 images per call");
-    uintptr_t bits = (uintptr_t)dev_gt_flow | (uintptr_t)dev_loss;
-    for (int i = 0; i < n_outs; ++i) bits |= (uintptr_t)dev_table[i] | (dev_grad ? (uintptr_t)dev_grad[i] : 0);
-    if (bits & 15) return fail(w + ": device buffers must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    const char *use = ": host memory passed to a device entry point (use b2f_op_table_loss_epe / b2f_table_loss_epe_host)";
-    if (host_memory(dev_gt_flow) || (dev_valid && host_memory(dev_valid)) || (dev_gt_occ && host_memory(dev_gt_occ)) || (dev_loss && host_memory(dev_loss)))
-        return fail(w + use);
-    for (int i = 0; i < n_outs; ++i)
-        if (host_memory(dev_table[i]) || (dev_grad && host_memory(dev_grad[i]))) return fail(w + use);
-    return table_loss_epe_run(c, stream ? (hipStream_t)stream : c->stream, dev_table, dev_grad, L, per == 5, n, H, W, dev_gt_flow, dev_valid, dev_gt_occ,
-                              flow_scale, o, count_mode, counts, dev_loss);
+    return table_loss_device(__func__, loss_epe(dev_gt_flow, dev_valid, dev_gt_occ, opts, count_mode, counts), c, dev_table, n_outs, n, H, W, nullptr,
+                             flow_scale, dev_loss, dev_grad, stream);
 }
 B2F_CATCH("b2f_table_loss_epe_device")
 
@@ -372,38 +301,7 @@ int b2f_op_table_loss_epe(b2f_ctx *c, const float *const *table, int n_outs, int
                           const unsigned char *gt_occ, double flow_scale, const b2f_loss_epe_opts *opts, int count_mode, const double *counts,
                           unsigned long long *loss, float *const *grad) try
 {
-    const std::string w = __func__;
-    OpStage st(c, w);
-    CHK(st.begin(true, "null context"));
-    const int own = c->past_flow ? 5 : 4, other = 9 - own;
-    const int per = (n_outs > 0 && n_outs % own == 0) ? own : (n_outs > 0 && n_outs % other == 0) ? other : 0;
-    if (!per) return fail(w + ": n_outs must be L x 4 (Hard) or L x 5 (Soft)");
-    int L = 0;
-    b2f_loss_epe_opts o;
-    CHK(check_table_loss_epe(w, table, n_outs, per, n, H, W, gt_flow, valid, gt_occ, flow_scale, opts, count_mode, counts, loss, grad, &o, &L));
-    std::vector<const float *> ptrs((size_t)n_outs);
-    std::vector<float *> gptrs((size_t)n_outs);
-    std::vector<size_t> floats((size_t)n_outs);
-    float *df;
-    for (int i = 0; i < n_outs; ++i) {
-        const int j = i / per, ch = (i % per) >= per - 2 ? 3 : 2;
-        floats[(size_t)i] = (size_t)n * ch * (H >> j) * (W >> j);
-        CHK(st.in(table[i], floats[(size_t)i], "table", &df));
-        ptrs[(size_t)i] = df;
-        if (grad) CHK(st.out(floats[(size_t)i], "grad", &gptrs[(size_t)i]));
-    }
-    const size_t HW = (size_t)H * W, nl = (size_t)n * L * B2F_LOSS_EPE_WORDS;
-    unsigned char *dv = nullptr, *dl = nullptr;
-    unsigned long long *dloss = nullptr;
-    CHK(st.in(gt_flow, (size_t)n * 2 * HW, "gt_flow", &df));
-    if (valid) CHK(st.in(valid, (size_t)n * HW, "valid", &dv));
-    if (gt_occ) CHK(st.in(gt_occ, (size_t)n * HW, "gt_occ", &dl));
-    if (loss) CHK(st.out(nl, "loss", &dloss));
-    CHK(b2f_table_loss_epe_device(c, ptrs.data(), n_outs, n, H, W, df, dv, dl, flow_scale, &o, count_mode, counts, dloss, grad ? gptrs.data() : nullptr, nullptr));
-    CHK(st.finish());
-    if (loss) CHK(st.get(loss, dloss, nl));
-    for (int i = 0; grad && i < n_outs; ++i) CHK(st.get(grad[i], gptrs[(size_t)i], floats[(size_t)i]));
-    return 0;
+    return table_loss_op(__func__, loss_epe(gt_flow, valid, gt_occ, opts, count_mode, counts), c, table, n_outs, n, H, W, nullptr, flow_scale, loss, grad);
 }
 B2F_CATCH("b2f_op_table_loss_epe")
 

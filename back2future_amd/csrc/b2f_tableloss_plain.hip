@@ -162,19 +162,7 @@ __global__ void __launch_bounds__(kThreads) table_loss_plain_kernel(LevelPtrs lp
 hipError_t launch_table_loss_plain_terms(const float *const *table, int L, bool past, int n, int H, int W, const float *ref, size_t ref_stride,
                                          const float *pyr, double flow_scale, unsigned long long *loss, hipStream_t s)
 {
-    LossLevel lv[kLossMaxLevels];
-    if (!loss || !loss_levels(table, nullptr, L, past, n, H, W, ref, ref_stride, pyr, flow_scale, lv)) return hipErrorInvalidValue;
-    for (int j = 0; j < L; ++j) {
-        const LossLevel &v = lv[j];
-        unsigned long long *rec = loss + (size_t)j * kRec;
-        if (past)
-            hipLaunchKernelGGL(table_loss_plain_kernel<true>, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, v.kd, rec, (size_t)L * kRec);
-        else
-            hipLaunchKernelGGL(table_loss_plain_kernel<false>, v.grid, dim3(kThreads), 0, s, v.lp, v.h, v.w, v.kd, rec, (size_t)L * kRec);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_terms(table_loss_plain_kernel<true>, table_loss_plain_kernel<false>, kRec, table, L, past, n, H, W, ref, ref_stride, pyr, flow_scale, loss, s);
 }
 
 }  // namespace b2f

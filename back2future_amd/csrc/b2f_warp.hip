@@ -273,17 +273,6 @@ int check_flow_warp(const std::string &w, const void *flow, int n, int H, int W,
     return 0;
 }
 
-// 1 when p is memory the host can read (pageable or page-locked), 0 for device memory
-bool host_memory(const void *p)
-{
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;
-    }
-    return !(a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeArray);
-}
-
 int warp_device(const char *who, b2f_ctx *c, const float *dev_flow, const float *dev_past_flow, const float *dev_occ_prob, int n, int H, int W,
                 double flow_scale, int in_kind, const void *dev_im1, const void *dev_im2, const void *dev_im3, void *dev_warped,
                 unsigned long long *dev_photo, void *stream);
@@ -358,14 +347,8 @@ int warp_device(const char *who, b2f_ctx *c, const float *dev_flow, const float 
 {
     const std::string w(who);
     CHK(check_flow_warp(w, dev_flow, n, H, W, flow_scale, in_kind, dev_im1, dev_im2, dev_im3, dev_warped, dev_photo));
-    if (((uintptr_t)dev_flow | (uintptr_t)dev_past_flow | (uintptr_t)dev_occ_prob | (uintptr_t)dev_im1 | (uintptr_t)dev_im2 | (uintptr_t)dev_im3 | (uintptr_t)dev_warped |
-         (uintptr_t)dev_photo) & 15)
-        return fail(w + ": device buffers must be 16-byte aligned");
-    if (!c) return fail(w + ": null context");
-    HIPCHK(hipSetDevice(c->device));
-    for (const void *p : {(const void *)dev_flow, (const void *)dev_past_flow, (const void *)dev_occ_prob, dev_im1, dev_im2, dev_im3, (const void *)dev_warped,
-                          (const void *)dev_photo})
-        if (p && host_memory(p)) return fail(w + ": host memory passed to a device entry point (use b2f_op_flow_warp / b2f_flow_warp_host)");
+    CHK(check_device_pointers(w, c, "b2f_op_flow_warp / b2f_flow_warp_host",
+                              {dev_flow, dev_past_flow, dev_occ_prob, dev_im1, dev_im2, dev_im3, dev_warped, dev_photo}));
     HIPCHK(launch_flow_warp(dev_flow, dev_occ_prob, n, H, W, flow_scale, dev_im1, dev_im2, dev_im3, (size_t)3 * H * W, in_kind, dev_warped,
                             in_kind, dev_photo, stream ? (hipStream_t)stream : c->stream, dev_past_flow));
     return 0;

@@ -273,6 +273,35 @@ def test_malformed_requests_are_refused_with_nothing_written():
         back2future.loss_grad_options(weights={"entropy": 1.0})
 
 
+def test_which_refusal_is_reported_when_two_apply():
+    """The order of an entry's checks is part of what a caller sees.  The host entry looks at the table before the options; the device
+    entry looks at its options before its context, while the entries of the records and of the supervised objective look at the context
+    first (a null context: no GPU is touched)."""
+    table, ref = TL.tables(16, 16, 2, False, tame=True)
+    grad = [np.full(t.shape, 7.0, np.float32) for t in table]
+    bad = back2future.loss_grad_options()
+    bad.pme = -1.0
+    with pytest.raises(_lib.B2FError, match="b2f_table_loss_grad_host: n_outs"):
+        _lib.check(_call_host(table[:7], ref, grad[:7], False, opts=bad))
+    with pytest.raises(_lib.B2FError, match="b2f_table_loss_grad_host: the gradient table must not alias"):
+        _lib.check(_call_host(table, ref, [table[0]] + grad[1:], False, opts=bad))
+    with pytest.raises(_lib.B2FError, match="b2f_table_loss_grad_host: .*finite and >= 0"):
+        _lib.check(_call_host(table, ref, grad, False, opts=bad))
+    lib = _lib.lib()
+    tp = (C.c_void_p * len(table))(*[t.ctypes.data for t in table])
+    gp = (C.c_void_p * len(grad))(*[g.ctypes.data for g in grad])
+    with pytest.raises(_lib.B2FError, match="b2f_table_loss_grad_device: .*finite and >= 0"):
+        _lib.check(lib.b2f_table_loss_grad_device(None, tp, len(table), 2, 16, 16, ref.ctypes.data, 20.0, C.byref(bad), gp, None))
+    with pytest.raises(_lib.B2FError, match="b2f_table_loss_grad_device: null context"):
+        _lib.check(lib.b2f_table_loss_grad_device(None, tp, 7, 2, 16, 16, ref.ctypes.data, 20.0, None, gp, None))
+    loss = np.full((2, 2, back2future.LOSS_SSIM_WORDS), 7, np.uint64)
+    with pytest.raises(_lib.B2FError, match="b2f_table_loss_ssim_device: null context"):      # a range_mode that does not exist
+        _lib.check(lib.b2f_table_loss_ssim_device(None, tp, len(table), 2, 16, 16, ref.ctypes.data, 20.0, loss.ctypes.data, None, 9, None))
+    with pytest.raises(_lib.B2FError, match="b2f_table_loss_epe_device: null context"):       # a count_mode that does not exist
+        _lib.check(lib.b2f_table_loss_epe_device(None, tp, len(table), 2, 16, 16, ref.ctypes.data, None, None, 20.0, None, 9, None, loss.ctypes.data, gp, None))
+    assert all((g == 7.0).all() for g in grad) and (loss == 7).all()
+
+
 @pytest.mark.parametrize("name", ["Ours-Soft-ft-KITTI", "Ours-Soft-ft-Sintel"])
 def test_the_fine_tuning_objectives_are_refused(name):
     with pytest.raises(ValueError, match="gradient of objective %r is not provided.*SecondOrderSmoothnessCriterion.*OBGCCriterion" % name):
