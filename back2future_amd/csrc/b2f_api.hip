@@ -919,6 +919,7 @@ const OptRow kOptions[] = {
     {"wino4_min_pixels", &b2f_ctx::wino4_min_pixels, OPT_ENV | OPT_SYNC, 0},
     {"adaptive_kernels", &b2f_ctx::adaptive_kernels, OPT_ENV | OPT_SYNC, 0},
     {"op_wino_split", &b2f_ctx::op_wino_split, OPT_ENV, 0},
+    {"op_gradw_partials", &b2f_ctx::op_gradw_partials, OPT_ENV, 0},
     {"op_hole_fill", &b2f_ctx::op_hole_fill, 0, 0},
     {"host_subbatch_pixels", nullptr, OPT_ENV, 0},   // long long b2f_ctx::host_subbatch_pixels
     {"host_threads", &b2f_ctx::host_threads, OPT_ENV, 0},
@@ -963,7 +964,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1013; }
+int b2f_version(void) { return 1014; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 

@@ -1165,6 +1165,23 @@ B2F_API int b2f_op_warp_costvol(b2f_ctx *ctx, const float *ref, const float *nbr
  * x: B x Ci x H x W, w: Co x Ci x 3 x 3, y: B x Co x Ho x Wo.                       */
 B2F_API int b2f_op_conv3x3(b2f_ctx *ctx, const float *x, int B, int Ci, int H, int W, const float *w,
                    const float *bias, int Co, int stride, int leaky, float *y);
+/* nn.SpatialConvolution(Ci,Co,3,3,1,1,1,1) [+ LeakyReLU(0.2)] :backward -- x: B x Ci x H x W, w: Co x Ci x 3 x 3,
+ * y: the layer's output (read only when leaky; NULL otherwise), grad_y: B x Co x H x W.  Any of grad_x (B x Ci x H x W),
+ * grad_w (Co x Ci x 3 x 3), grad_b (Co) may be NULL: not computed.  layout 0: NHWC strides on the device (as b2f_op_conv3x3),
+ * 1: the forward's chunk-planar strides.  stride != 1 is refused.  Host pointers, planar.
+ * g' = grad_y * (y > 0 ? 1 : 0.2f) with leaky (y == 0 takes the slope), else grad_y; grad_x = conv3x3(g', w rotated by 180 degrees and
+ * channel-transposed) on the forward's own kernels (the profile row is the forward kernel's); grad_w[co][ci][ky][kx] = sum over
+ * (b, oy, ox) of g'[b][co][oy][ox] * x[b][ci][oy + ky - 1][ox + kx - 1] on the fp32 MFMA and grad_b[co] = sum of g'[b][co], both as
+ * partial sums over disjoint pixel ranges that are added in index order: no atomics, the same bits on any device and in any run.
+ * grad_w and grad_b are written, not accumulated.  Refused, with b2f_last_error naming the argument and nothing written: NULL x, w or
+ * grad_y; leaky without y; all three outputs NULL; stride != 1; a layout other than 0 / 1; non-positive sizes (b2f_version() >= 1014). */
+B2F_API int b2f_op_conv3x3_backward(b2f_ctx *ctx, const float *x, int B, int Ci, int H, int W, const float *w, int Co,
+                                    int stride, int leaky, const float *y, const float *grad_y, int layout,
+                                    float *grad_x, float *grad_w, float *grad_b);
+/* What a b2f_op_conv3x3_backward call of these sizes does to grad_w and grad_b under the context's options: the number of partial sums
+ * (a function of B, Ci, H, W, Co alone unless option op_gradw_partials > 0 forces it) and the most pixels one partial sum adds up.
+ * Either pointer may be NULL.  Makes no HIP call.                                                                                */
+B2F_API int b2f_op_conv3x3_backward_plan(b2f_ctx *ctx, int B, int Ci, int H, int W, int Co, int *partials, long long *longest_chain);
 /* Two entries that run a piece of the loaded model in the forward pass's own layout (chunk-planar buffers, the context's packed
  * weights and options), for the tests of tests/test_gpu_in_place.py.
  * b2f_op_layer: conv (kind, level, idx) of the context's packed table -- kind 0 feature pyramid (level 2..7, idx 1..2; not feat2.conv1),

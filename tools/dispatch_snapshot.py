@@ -26,7 +26,7 @@ HARD, SOFT = "random:hard:2:1.0", "random:soft:2:1.0"
 KEYS = ["use_graph", "host_graph", "profile", "profile_layers", "bf16_direct", "bf16_conv", "bf16_conv_min_pixels", "wino1d", "wino6",
         "wino6_min_pixels", "wino2_split", "wino4_split", "wino4_hybrid", "s2_tiles_per_block", "wino4_persistent", "s2_loader",
         "s2_tile_groups", "wino_split_pixels", "wino8", "wino4_min_pixels", "adaptive_kernels", "corr_variant", "corr_ablate",
-        "op_wino_split", "op_hole_fill", "host_subbatch_pixels", "host_threads", "host_u8", "host_ramp", "debug_fail_next"]
+        "op_wino_split", "op_gradw_partials", "op_hole_fill", "host_subbatch_pixels", "host_threads", "host_u8", "host_ramp", "debug_fail_next"]
 UNSEEDED = ["bf16_conv_min_pixels", "op_hole_fill", "debug_fail_next"]
 EXPERIMENT_ONLY = ["wino2_split", "wino4_split", "wino4_hybrid"]
 OPTION_MATRIX = [
