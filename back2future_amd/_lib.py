@@ -365,6 +365,10 @@ SIGNATURES = {
                                           c_float_p, c_float_p, C.c_int, c_float_p, c_float_p, c_float_p]),
     "b2f_op_conv3x3_backward_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                                C.POINTER(C.c_longlong)]),
+    "b2f_op_conv3x3s2_backward": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int,
+                                            c_float_p, c_float_p, C.c_int, c_float_p, c_float_p, c_float_p]),
+    "b2f_op_conv3x3s2_backward_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_longlong)]),
     "b2f_op_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p]),
     "b2f_op_cv_record": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_float, C.c_int, C.c_int, C.c_int,
                                    C.c_int, c_float_p]),

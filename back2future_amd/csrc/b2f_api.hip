@@ -964,7 +964,7 @@ const char *experiment_value(const OptRow &r, int value)
 extern "C" {
 
 const char *b2f_last_error(void) { return g_err.c_str(); }
-int b2f_version(void) { return 1014; }
+int b2f_version(void) { return 1015; }
 
 long long b2f_param_count(int past_flow) { return param_count(past_flow != 0); }
 

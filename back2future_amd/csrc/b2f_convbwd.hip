@@ -34,7 +34,15 @@
 //   * longest chain: the most in-map pixels any partial sums (padding pixels add an exact zero); b2f_op_conv3x3_backward_plan reports it
 //     with P, and the tests' bound is (longest chain + P + 2) u S.
 // Every kernel takes (img_stride, chunk_stride, pix_stride) in floats for x and g' like the forward's kernels: NHWC (chunk 8, pix C) and
-// the forward's chunk-planar layout are both expressible.  Stride-2 layers are refused.
+// the forward's chunk-planar layout are both expressible.
+//
+// The stride-2 layers (nn.SpatialConvolution(Ci,Co,3,3,2,2,1,1), the first conv of a convUnit) have entries of their own,
+// b2f_op_conv3x3s2_backward[_plan]; b2f_op_conv3x3_backward refuses them.  x and gx are H x W, y, gy and g' Ho x Wo = ((H - 1) / 2 + 1) x
+// ((W - 1) / 2 + 1).  leaky_mask, gradb_partials and gradw_reduce are the same kernels on the Ho x Wo map; conv3x3_gradw is instantiated
+// with ST = 2: strips of kGradwBandRows x kGradwS2StripCols output pixels, an x strip of 5 x (2 kGradwS2StripCols + 1) input pixels with
+// the halo on the low side only, tap (ky, kx) of output pixel (r, j) at x strip pixel (2 r + ky, 2 j + kx), the pixel pair member two
+// input pixels on; the ST = 1 instances are the code they were.  gradInput is a transposed convolution no forward kernel computes:
+// conv3x3s2_gradx below.
 #include "b2f_ctx.h"
 
 #include <cstdio>
@@ -47,6 +55,10 @@ constexpr int kGradwRuleCUs = 256;       // the split aims at one round of block
 constexpr int kGradwWavesPerCU = 8;      // ... with this many waves each: 144 accumulator registers leave two waves per SIMD
 constexpr int kGradwMinStrips = 8;       // a partial of the rule holds at least this many strips ...
 constexpr int kGradwMaxPartials = 256;   // ... and there are at most this many
+constexpr int kGradwS2StripCols = 16;    // output columns of a strip of a stride-2 layer (its x strip: 5 x 33 input pixels)
+constexpr int kGradxS2Rows = 4;          // conv3x3s2_gradx: output rows of a block's tile of g', one per wave
+constexpr int kGradxS2Cols = 32;         // ... and its output columns, the pixel dimension of a wave's MFMA tile
+constexpr int kGradxS2Co = 32;           // ... and the output channels staged in LDS at a time
 
 namespace {
 
@@ -113,7 +125,8 @@ struct GradwLaunch {
     const float *g;       // g', g_chunks chunks
     long g_img, g_chunk;
     int g_pix, g_chunks;
-    int H, W;
+    int H, W;             // the map of g'
+    int xH, xW;           // the map of x: H, W at stride 1
     int bands, nsx;       // strips per image column, per image row
     int strips, q;        // all strips; strips per partial
     int n_co_tiles;       // block tiles along Co (blockIdx.x = ci tile * n_co_tiles + co tile)
@@ -121,12 +134,14 @@ struct GradwLaunch {
     float *ws;            // [partial][tap 9][co_pad][ci_pad]
 };
 
-template <int MC, int NC>
+// ST: the layer's stride, 1 or 2.  The x strip of an RB x SW strip of g' is (ST (RB - 1) + 3) x (ST (SW - 1) + 3) input pixels from
+// (ST oy0 - 1, ST ox0 - 1): a halo on both sides at stride 1, on the low side only at stride 2.
+template <int MC, int NC, int ST>
 __global__ __launch_bounds__(MC * NC * 64) void conv3x3_gradw(const GradwLaunch p)
 {
     constexpr int NTHR = MC * NC * 64;
-    constexpr int RB = kGradwBandRows, SW = kGradwStripCols;
-    constexpr int GPIX = RB * SW, XW = SW + 2, XPIX = (RB + 2) * XW;
+    constexpr int RB = kGradwBandRows, SW = ST == 1 ? kGradwStripCols : kGradwS2StripCols;
+    constexpr int GPIX = RB * SW, XW = ST * (SW - 1) + 3, XPIX = (ST * (RB - 1) + 3) * XW;
     constexpr int GNP = GPIX | 1, XNP = XPIX | 1;             // pixels per LDS plane: odd
     constexpr int G_ITEMS = MC * 8 * GPIX, X_ITEMS = NC * 8 * XPIX;   // float4 items of a strip
     constexpr int G_ITER = (G_ITEMS + NTHR - 1) / NTHR, X_ITER = (X_ITEMS + NTHR - 1) / NTHR;
@@ -151,7 +166,7 @@ __global__ __launch_bounds__(MC * NC * 64) void conv3x3_gradw(const GradwLaunch 
 
     // this lane's operands: channel n of the wave's 32, pixel pair member `half`
     const float *Gf = reinterpret_cast<const float *>(G) + ((mc * 8 + (n >> 2)) * GNP + half) * 4 + (n & 3);
-    const float *Xf = reinterpret_cast<const float *>(X) + ((nc * 8 + (n >> 2)) * XNP + half) * 4 + (n & 3);
+    const float *Xf = reinterpret_cast<const float *>(X) + ((nc * 8 + (n >> 2)) * XNP + half * ST) * 4 + (n & 3);
 
     for (int s = s0; s < s1; ++s) {
         const int sx = s % p.nsx;
@@ -177,10 +192,10 @@ __global__ __launch_bounds__(MC * NC * 64) void conv3x3_gradw(const GradwLaunch 
             const int idx = tid + i * NTHR;
             const bool in = (X_ITEMS % NTHR == 0) || idx < X_ITEMS;
             const int hf = idx & 1, pix = (idx >> 1) % XPIX, ch = min((idx >> 1) / XPIX, NC * 4 - 1);
-            const int iy = oy0 - 1 + pix / XW, ix = ox0 - 1 + pix % XW;
+            const int iy = ST * oy0 - 1 + pix / XW, ix = ST * ox0 - 1 + pix % XW;
             const int chunk = cit * (NC * 4) + ch;
-            const bool ok = in && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W && chunk < p.x_chunks;
-            const size_t off = ok ? (size_t)chunk * p.x_chunk + (size_t)(iy * p.W + ix) * p.x_pix + hf * 4 : 0;
+            const bool ok = in && iy >= 0 && iy < p.xH && ix >= 0 && ix < p.xW && chunk < p.x_chunks;
+            const size_t off = ok ? (size_t)chunk * p.x_chunk + (size_t)(iy * p.xW + ix) * p.x_pix + hf * 4 : 0;
             const f32x4 v = *reinterpret_cast<const f32x4 *>(xb + off);
             if (in) X[(ch * 2 + hf) * XNP + pix] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -190,7 +205,7 @@ __global__ __launch_bounds__(MC * NC * 64) void conv3x3_gradw(const GradwLaunch 
 #pragma unroll 4
             for (int j = 0; j < SW / 2; ++j) {
                 const float a = Gf[(r * SW + 2 * j) * 4];
-                const float *xp = Xf + (r * XW + 2 * j) * 4;
+                const float *xp = Xf + ST * (r * XW + 2 * j) * 4;
                 float b[9];
 #pragma unroll
                 for (int tap = 0; tap < 9; ++tap) b[tap] = xp[((tap / 3) * XW + tap % 3) * 4];
@@ -212,9 +227,10 @@ __global__ __launch_bounds__(MC * NC * 64) void conv3x3_gradw(const GradwLaunch 
 
 // gb's partial sums: block (chunk of 8 channels, partial), thread = (sub 0..7, channel): thread `sub` adds the strip positions
 // sub, sub + 8, .. of every strip of the partial in order, then thread 0 of a channel adds the eight sums in order.  wsb: [partial][chunks * 8]
+template <int SW>
 __global__ __launch_bounds__(64) void gradb_partials(const GradwLaunch p, float *wsb)
 {
-    constexpr int RB = kGradwBandRows, SW = kGradwStripCols;
+    constexpr int RB = kGradwBandRows;
     __shared__ float sums[64];
     const int ch = threadIdx.x & 7, sub = threadIdx.x >> 3;
     const int chunk = blockIdx.x, part = blockIdx.y;
@@ -268,6 +284,122 @@ __global__ __launch_bounds__(256) void gradw_reduce(const float *ws, const float
     }
 }
 
+struct GradxS2Launch {
+    const float *g;       // g' on the Ho x Wo map, g_chunks chunks of 8 channels
+    long g_img, g_chunk;
+    int g_pix, g_chunks;
+    const float *wp;      // [tap 9][co_pad][ci_pad]: w[co][ci][tap], zero in the padding
+    int co_pad, ci_pad;   // multiples of kGradxS2Co and of 32
+    int Ho, Wo, H, W;     // the maps of g' and of gx
+    int tiles_x, tiles_y; // tiles of kGradxS2Rows x kGradxS2Cols pixels of g' per image (blockIdx.x = (image * tiles_y + ty) * tiles_x + tx)
+    float *out;           // gx, out_chunks chunks of 8 channels
+    long out_img, out_chunk;
+    int out_pix, out_chunks;
+};
+
+// gradInput of a stride-2 layer, a transposed convolution: the pixel (2 oy + py, 2 ox + px) of gx takes, by its parity class (py, px),
+//   (0, 0): g'(oy, ox) w[1][1]                                  (0, 1): g'(oy, ox + 1) w[1][0] + g'(oy, ox) w[1][2]
+//   (1, 0): g'(oy + 1, ox) w[0][1] + g'(oy, ox) w[2][1]         (1, 1): g'(oy + 1, ox + 1) w[0][0] + g'(oy + 1, ox) w[0][2]
+//                                                                       + g'(oy, ox + 1) w[2][0] + g'(oy, ox) w[2][2]
+// summed over co: nine taps per 2 x 2 pixels of gx, the forward layer's MAC count; no zero-inserted g' exists anywhere.
+// A GEMM per class with M = ci, N = pixel, K = co on v_mfma_f32_32x32x2_f32: A = one VGPR w[tap][co = k + (lane >> 5)][ci = lane & 31],
+// B = one VGPR g'[co = k + (lane >> 5)][row, column + (lane & 31)] at the class's neighbour.  Block = 4 waves = 32 input channels x a tile
+// of kGradxS2Rows x kGradxS2Cols pixels of g' of one image; wave v owns row v of the tile and the four classes' 32 ci x 32 pixel
+// accumulators (64 registers); per pair of output channels it reads four B and nine A operands and issues nine MFMAs, a class's taps in
+// the order above, the pairs in the order of co: every element of gx is one fmaf chain over (co pair, tap, co of the pair).
+// Per kGradxS2Co output channels the block stages in LDS g' of the tile with one halo row below and one halo column right, zero
+// outside the map and the channel count by masking the load, as [co][172 floats: 5 x 33 pixels + 7] -- the operand read of 32 pixels
+// and the four one-float stores of a loaded float4 (lane pairs 4 x 172 = 16 mod 32 banks apart) are free of bank conflicts -- and the
+// weights as [tap][co][32 ci]: 22 016 + 36 864 bytes, two blocks per CU; 78 + 64 registers, no scratch.  D: a lane holds ci = 8 (r >> 2) + 4 (lane >> 5) + (r & 3) of
+// pixel lane & 31: one float4 store per half chunk, masked at iy >= H and ix >= W (the odd / odd pixel past an odd H or W does not exist).
+__global__ __launch_bounds__(256) void conv3x3s2_gradx(const GradxS2Launch p)
+{
+    constexpr int TH = kGradxS2Rows, TW = kGradxS2Cols, KC = kGradxS2Co;
+    constexpr int GW = TW + 1, GPIX = (TH + 1) * GW, GP = 172;
+    constexpr int G_ITEMS = (KC / 8) * GPIX * 2, W_ITEMS = 9 * KC * 8;   // float4 items
+    static_assert(GP >= GPIX && GP % 8 == 4, "a row of the g' tile holds its pixels; 4 rows are 16 banks apart");
+    static_assert(TH == 4 && TW == 32 && KC % 8 == 0 && W_ITEMS % 256 == 0, "one wave per row, 32 pixels per MFMA tile");
+    __shared__ float Gs[KC * GP];
+    __shared__ __attribute__((aligned(16))) float Ws[9 * KC * 32];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 31, half = lane >> 5;
+    const int tx = blockIdx.x % p.tiles_x, t = blockIdx.x / p.tiles_x;
+    const int ty = t % p.tiles_y, img = t / p.tiles_y;
+    const int cit = blockIdx.y;
+    const int oy0 = ty * TH, ox0 = tx * TW;
+    const float *gb = p.g + (size_t)img * p.g_img;
+
+    f32x16 acc[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+
+    const float *gr = Gs + half * GP + wave * GW + n;
+    const float *wr = Ws + half * 32 + n;
+    const bool row_in = oy0 + wave < p.Ho;   // wave-uniform
+
+    for (int k0 = 0; k0 < p.co_pad; k0 += KC) {
+        __syncthreads();   // every wave has read the channels before
+        // item = (chunk, pixel, half chunk), half fastest: a lane pair loads the 32 bytes of one pixel's chunk
+        for (int idx = tid; idx < G_ITEMS; idx += 256) {
+            const int hf = idx & 1, pix = (idx >> 1) % GPIX, ch = (idx >> 1) / GPIX;
+            const int oy = oy0 + pix / GW, ox = ox0 + pix % GW;
+            const int chunk = k0 / 8 + ch;
+            const bool ok = oy < p.Ho && ox < p.Wo && chunk < p.g_chunks;
+            const size_t off = ok ? (size_t)chunk * p.g_chunk + (size_t)(oy * p.Wo + ox) * p.g_pix + hf * 4 : 0;   // masked: the base
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(gb + off);
+            float *d = Gs + (ch * 8 + hf * 4) * GP + pix;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[j * GP] = ok ? v[j] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < W_ITEMS / 256; ++i) {
+            const int idx = tid + i * 256;
+            const int c4 = idx & 7, row = idx >> 3;   // row = tap * KC + co of the stage
+            const int tap = row / KC, k = row % KC;
+            *reinterpret_cast<f32x4 *>(Ws + row * 32 + c4 * 4) =
+                *reinterpret_cast<const f32x4 *>(p.wp + ((size_t)tap * p.co_pad + k0 + k) * p.ci_pad + cit * 32 + c4 * 4);
+        }
+        __syncthreads();
+        if (row_in) {
+#pragma unroll 2
+            for (int k = 0; k < KC; k += 2) {
+                const float b00 = gr[k * GP], b01 = gr[k * GP + 1], b10 = gr[k * GP + GW], b11 = gr[k * GP + GW + 1];
+                float a[9];
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) a[tap] = wr[(tap * KC + k) * 32];
+                // the four classes interleaved: no MFMA reads the accumulator the one before it writes
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], b11, acc[3], 0, 0, 0);
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4], b00, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], b01, acc[1], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], b10, acc[3], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], b10, acc[2], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[5], b00, acc[1], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[6], b01, acc[3], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[7], b00, acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[8], b00, acc[3], 0, 0, 0);
+            }
+        }
+    }
+    // C/D layout: column = lane & 31 (pixel), row = (r & 3) + 8 * (r >> 2) + 4 * half (ci): the half chunk `half` of chunk r >> 2
+    const int oy = oy0 + wave, ox = ox0 + n;
+    float *ob = p.out + (size_t)img * p.out_img + half * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int iy = 2 * oy + (c >> 1), ix = 2 * ox + (c & 1);
+        if (!row_in || iy >= p.H || ix >= p.W) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int chunk = cit * 4 + q;
+            if (chunk >= p.out_chunks) continue;
+            const f32x4 v = {acc[c][4 * q], acc[c][4 * q + 1], acc[c][4 * q + 2], acc[c][4 * q + 3]};
+            *reinterpret_cast<f32x4 *>(ob + (size_t)chunk * p.out_chunk + (size_t)(iy * p.W + ix) * p.out_pix) = v;
+        }
+    }
+}
+
 // The split and the tiles of a call: everything from (B, Ci, H, W, Co) and the forced partial count (0 = the rule); no HIP call
 struct GradwPlan {
     int mc, nc;                  // 32-channel tiles per block along Co, Ci
@@ -288,7 +420,8 @@ int pick_tiles(int n32, int most)
     return best;
 }
 
-GradwPlan gradw_plan(int B, int Ci, int H, int W, int Co, int forced)
+// H, W: the map of g'; sw: the strip's columns (kGradwStripCols, or kGradwS2StripCols for a stride-2 layer)
+GradwPlan gradw_plan(int B, int Ci, int H, int W, int Co, int forced, int sw = kGradwStripCols)
 {
     GradwPlan g{};
     g.mc = pick_tiles((Co + 31) / 32, 3);
@@ -298,7 +431,7 @@ GradwPlan gradw_plan(int B, int Ci, int H, int W, int Co, int forced)
     g.co_pad = g.n_co_tiles * g.mc * 32;
     g.ci_pad = g.n_ci_tiles * g.nc * 32;
     g.bands = (H + kGradwBandRows - 1) / kGradwBandRows;
-    g.nsx = (W + kGradwStripCols - 1) / kGradwStripCols;
+    g.nsx = (W + sw - 1) / sw;
     g.strips = B * g.bands * g.nsx;
     const int tiles = g.n_co_tiles * g.n_ci_tiles;
     int p0;
@@ -314,33 +447,36 @@ GradwPlan gradw_plan(int B, int Ci, int H, int W, int Co, int forced)
         long long n = 0;
         for (int s = part * g.q; s < std::min((part + 1) * g.q, g.strips); ++s) {
             const int sx = s % g.nsx, band = (s / g.nsx) % g.bands;
-            n += (long long)std::min(kGradwBandRows, H - band * kGradwBandRows) * std::min(kGradwStripCols, W - sx * kGradwStripCols);
+            n += (long long)std::min(kGradwBandRows, H - band * kGradwBandRows) * std::min(sw, W - sx * sw);
         }
         g.longest_chain = std::max(g.longest_chain, n);
     }
     return g;
 }
 
-template <int MC, int NC>
+template <int MC, int NC, int ST>
 hipError_t launch_gradw_t(const GradwLaunch &L, int n_ci_tiles, int P, hipStream_t s)
 {
-    constexpr int GNP = (kGradwBandRows * kGradwStripCols) | 1, XNP = ((kGradwBandRows + 2) * (kGradwStripCols + 2)) | 1;
-    constexpr size_t lds = sizeof(f32x4) * (MC * 8 * GNP + NC * 8 * XNP);   // the largest, MC = 3 and NC = 2: 60 032 bytes
+    constexpr int RB = kGradwBandRows, SW = ST == 1 ? kGradwStripCols : kGradwS2StripCols;
+    constexpr int GNP = (RB * SW) | 1, XNP = ((ST * (RB - 1) + 3) * (ST * (SW - 1) + 3)) | 1;
+    // the largest, MC = 3 and NC = 2: 60 032 bytes at stride 1, 54 912 at stride 2
+    constexpr size_t lds = sizeof(f32x4) * (MC * 8 * GNP + NC * 8 * XNP);
     static LdsOnce once;   // one per template instance
-    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_gradw<MC, NC>), (int)lds)) return e;
-    hipLaunchKernelGGL((conv3x3_gradw<MC, NC>), dim3((unsigned)(L.n_co_tiles * n_ci_tiles), (unsigned)P), dim3(MC * NC * 64), lds, s, L);
+    if (hipError_t e = once.ensure(reinterpret_cast<const void *>(&conv3x3_gradw<MC, NC, ST>), (int)lds)) return e;
+    hipLaunchKernelGGL((conv3x3_gradw<MC, NC, ST>), dim3((unsigned)(L.n_co_tiles * n_ci_tiles), (unsigned)P), dim3(MC * NC * 64), lds, s, L);
     return hipGetLastError();
 }
 
+template <int ST>
 hipError_t launch_gradw(const GradwPlan &g, const GradwLaunch &L, hipStream_t s)
 {
     switch (g.mc * 10 + g.nc) {
-        case 11: return launch_gradw_t<1, 1>(L, g.n_ci_tiles, g.P, s);
-        case 12: return launch_gradw_t<1, 2>(L, g.n_ci_tiles, g.P, s);
-        case 21: return launch_gradw_t<2, 1>(L, g.n_ci_tiles, g.P, s);
-        case 22: return launch_gradw_t<2, 2>(L, g.n_ci_tiles, g.P, s);
-        case 31: return launch_gradw_t<3, 1>(L, g.n_ci_tiles, g.P, s);
-        case 32: return launch_gradw_t<3, 2>(L, g.n_ci_tiles, g.P, s);
+        case 11: return launch_gradw_t<1, 1, ST>(L, g.n_ci_tiles, g.P, s);
+        case 12: return launch_gradw_t<1, 2, ST>(L, g.n_ci_tiles, g.P, s);
+        case 21: return launch_gradw_t<2, 1, ST>(L, g.n_ci_tiles, g.P, s);
+        case 22: return launch_gradw_t<2, 2, ST>(L, g.n_ci_tiles, g.P, s);
+        case 31: return launch_gradw_t<3, 1, ST>(L, g.n_ci_tiles, g.P, s);
+        case 32: return launch_gradw_t<3, 2, ST>(L, g.n_ci_tiles, g.P, s);
     }
     return hipErrorInvalidValue;
 }
@@ -388,50 +524,44 @@ const char *size_refusal(int B, int Ci, int H, int W, int Co)
 
 using namespace b2f;
 
-extern "C" {
+namespace {
 
-int b2f_op_conv3x3_backward_plan(b2f_ctx *c, int B, int Ci, int H, int W, int Co, int *partials, long long *longest_chain) try
+// the argument checks both backward entries share, in the order they are made; nullptr: none applies
+const char *argument_refusal(const float *x, const float *w, const float *y, const float *grad_y, int leaky, const float *grad_x,
+                             const float *grad_w, const float *grad_b)
 {
-    const std::string fn = "b2f_op_conv3x3_backward_plan: ";
-    if (!c) return api_fail(fn + "ctx is null");
-    if (const char *why = size_refusal(B, Ci, H, W, Co)) return api_fail(fn + why);
-    const GradwPlan g = gradw_plan(B, Ci, H, W, Co, c->op_gradw_partials);
-    if (partials) *partials = g.P;
-    if (longest_chain) *longest_chain = g.longest_chain;
-    return 0;
+    if (!x) return "x is null";
+    if (!w) return "w is null";
+    if (!grad_y) return "grad_y is null";
+    if (leaky && !y) return "y is null: with leaky the layer's output is needed";
+    if (!grad_x && !grad_w && !grad_b) return "grad_x, grad_w and grad_b are all null: nothing to compute";
+    return nullptr;
 }
-B2F_CATCH("b2f_op_conv3x3_backward_plan")
 
-int b2f_op_conv3x3_backward(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, const float *w, int Co, int stride, int leaky, const float *y,
-                            const float *grad_y, int layout, float *grad_x, float *grad_w, float *grad_b) try
+// The body of both backward entries behind their argument checks.  ST: the layer's stride; H x W: the map of x and gx; y, gy and g' are
+// Ho x Wo = ((H - 1) / ST + 1) x ((W - 1) / ST + 1).
+template <int ST>
+int run_backward(b2f_ctx *c, const char *entry, const float *x, int B, int Ci, int H, int W, const float *w, int Co, int leaky, const float *y,
+                 const float *grad_y, int layout, float *grad_x, float *grad_w, float *grad_b)
 {
-    const std::string fn = "b2f_op_conv3x3_backward: ";
-    if (!c) return api_fail(fn + "ctx is null");
-    if (!x) return api_fail(fn + "x is null");
-    if (!w) return api_fail(fn + "w is null");
-    if (!grad_y) return api_fail(fn + "grad_y is null");
-    if (leaky && !y) return api_fail(fn + "y is null: with leaky the layer's output is needed");
-    if (!grad_x && !grad_w && !grad_b) return api_fail(fn + "grad_x, grad_w and grad_b are all null: nothing to compute");
-    if (stride != 1) return api_fail(fn + "stride must be 1 (the backward of the stride-2 layers is not implemented)");
-    if (layout != 0 && layout != 1) return api_fail(fn + "layout must be 0 (NHWC strides) or 1 (chunk-planar)");
-    if (const char *why = size_refusal(B, Ci, H, W, Co)) return api_fail(fn + why);
-    OpStage st(c, __func__);
+    OpStage st(c, entry);
     CHK(st.begin());
     hipStream_t s = c->stream;
-    const size_t hw = (size_t)H * W;
+    const int Ho = (H - 1) / ST + 1, Wo = (W - 1) / ST + 1;
+    const size_t hw = (size_t)H * W, hwo = (size_t)Ho * Wo;
     const int xch = (Ci + kCK - 1) / kCK, gch = (Co + kCK - 1) / kCK, Cip = xch * kCK, Cop = gch * kCK;
-    const size_t nx = (size_t)B * Ci * hw, ny = (size_t)B * Co * hw, nxp = (size_t)B * Cip * hw, nyp = (size_t)B * Cop * hw;
+    const size_t nx = (size_t)B * Ci * hw, ny = (size_t)B * Co * hwo, nxp = (size_t)B * Cip * hw, nyp = (size_t)B * Cop * hwo;
     const size_t nw = (size_t)Co * Ci * 9;
-    // strides of a C-channel tensor in the entry's layout: NHWC on padded channels, or chunk-planar
-    auto strides = [&](int Cpad, long *img, long *chunk, int *pix) {
-        *img = (long)(hw * Cpad);
+    // strides of a C-channel tensor of n pixels in the entry's layout: NHWC on padded channels, or chunk-planar
+    auto strides = [&](int Cpad, size_t n, long *img, long *chunk, int *pix) {
+        *img = (long)(n * Cpad);
         if (layout == 0) { *chunk = 8; *pix = Cpad; }
-        else { *chunk = (long)(hw * 8); *pix = 8; }
+        else { *chunk = (long)(n * 8); *pix = 8; }
     };
     long x_img, x_chunk, g_img, g_chunk;
     int x_pix, g_pix;
-    strides(Cip, &x_img, &x_chunk, &x_pix);
-    strides(Cop, &g_img, &g_chunk, &g_pix);
+    strides(Cip, hw, &x_img, &x_chunk, &x_pix);
+    strides(Cop, hwo, &g_img, &g_chunk, &g_pix);
 
     // ---- g' = the masked output gradient, once, in the layout both consumers read ----
     float *dgy, *dyy = nullptr, *dg;
@@ -440,18 +570,18 @@ int b2f_op_conv3x3_backward(b2f_ctx *c, const float *x, int B, int Ci, int H, in
     if (layout == 0) {   // the caller's planar tensors, read through their strides
         CHK(st.in(grad_y, ny, "grad_y", &dgy));
         if (leaky) CHK(st.in(y, ny, "y", &dyy));
-        sg = {dgy, (long)(hw * Co), (long)(hw * 8), (long)hw, 1};
-        sy = {dyy, (long)(hw * Co), (long)(hw * 8), (long)hw, 1};
+        sg = {dgy, (long)(hwo * Co), (long)(hwo * 8), (long)hwo, 1};
+        sy = {dyy, (long)(hwo * Co), (long)(hwo * 8), (long)hwo, 1};
     } else {             // chunk-planar, as a graph walk would hold them
         std::vector<float> host(nyp);
-        planar_to_cp8_host(grad_y, (size_t)B, Co, hw, host.data());
+        planar_to_cp8_host(grad_y, (size_t)B, Co, hwo, host.data());
         CHK(st.in(host.data(), nyp, "grad_y", &dgy));
         if (leaky) {
-            planar_to_cp8_host(y, (size_t)B, Co, hw, host.data());
+            planar_to_cp8_host(y, (size_t)B, Co, hwo, host.data());
             CHK(st.in(host.data(), nyp, "y", &dyy));
         }
-        sg = {dgy, (long)(hw * Cop), (long)(hw * 8), 1, 8};
-        sy = {dyy, (long)(hw * Cop), (long)(hw * 8), 1, 8};
+        sg = {dgy, (long)(hwo * Cop), (long)(hwo * 8), 1, 8};
+        sy = {dyy, (long)(hwo * Cop), (long)(hwo * 8), 1, 8};
         vec = Co % 4 == 0;
     }
     CHK(st.out(nyp, "masked grad_y", &dg));
@@ -468,14 +598,37 @@ int b2f_op_conv3x3_backward(b2f_ctx *c, const float *x, int B, int Ci, int H, in
         }
     }
     CHK(timed(c, s, "convbwd_mask", [&] {
-        const size_t total = (size_t)B * gch * hw * 2;
-        hipLaunchKernelGGL(leaky_mask, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sg, sy, Co, B, (int)hw, vec, dg, g_img, g_chunk, g_pix);
+        const size_t total = (size_t)B * gch * hwo * 2;
+        hipLaunchKernelGGL(leaky_mask, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sg, sy, Co, B, (int)hwo, vec, dg, g_img, g_chunk, g_pix);
         return hipGetLastError();
     }));
 
     // ---- gradInput: the forward's kernels on (g', w~), packed as b2f_op_conv3x3 packs a layer ----
+    //      (stride 2: conv3x3s2_gradx on a [tap][co][ci] packing, gx in the layout's strides on padded channels) ----
     float *dgx = nullptr, *dgxp = nullptr;
-    if (grad_x) {
+    if (grad_x && ST == 2) {
+        GradxS2Launch L{};
+        L.co_pad = (Co + kGradxS2Co - 1) / kGradxS2Co * kGradxS2Co;
+        L.ci_pad = (Ci + 31) / 32 * 32;
+        std::vector<float> wpk((size_t)9 * L.co_pad * L.ci_pad, 0.f);
+        for (int co = 0; co < Co; ++co)
+            for (int ci = 0; ci < Ci; ++ci)
+                for (int t = 0; t < 9; ++t) wpk[((size_t)t * L.co_pad + co) * L.ci_pad + ci] = w[((size_t)co * Ci + ci) * 9 + t];
+        float *dw;
+        CHK(st.in(wpk.data(), wpk.size(), "weights by tap", &dw));
+        CHK(st.out(nxp, "grad_x", &dgx)); CHK(st.out(nx, "grad_x planar", &dgxp));
+        L.g = dg; L.g_img = g_img; L.g_chunk = g_chunk; L.g_pix = g_pix; L.g_chunks = gch;
+        L.wp = dw;
+        L.Ho = Ho; L.Wo = Wo; L.H = H; L.W = W;
+        L.tiles_x = (Wo + kGradxS2Cols - 1) / kGradxS2Cols; L.tiles_y = (Ho + kGradxS2Rows - 1) / kGradxS2Rows;
+        L.out = dgx; L.out_img = x_img; L.out_chunk = x_chunk; L.out_pix = x_pix; L.out_chunks = xch;
+        CHK(timed(c, s, "convbwd_gradx_s2", [&] {
+            hipLaunchKernelGGL(conv3x3s2_gradx, dim3((unsigned)(B * L.tiles_y * L.tiles_x), (unsigned)(L.ci_pad / 32)), dim3(256), 0, s, L);
+            return hipGetLastError();
+        }));
+        if (layout == 0) HIPCHK(launch_nhwc_to_planar(dgx, Cip, Ci, B, H, W, dgxp, s));
+        else HIPCHK(launch_cp8_to_planar(dgx, Ci, B, H, W, dgxp, s));
+    } else if (grad_x) {
         std::vector<float> wt(nw), zero((size_t)Ci, 0.f);
         for (int co = 0; co < Co; ++co)
             for (int ci = 0; ci < Ci; ++ci)
@@ -509,11 +662,12 @@ int b2f_op_conv3x3_backward(b2f_ctx *c, const float *x, int B, int Ci, int H, in
     // ---- gradWeight and gradBias: partial sums per (tile, partial), then the partials in index order ----
     float *dgw = nullptr, *dgb = nullptr;
     if (grad_w || grad_b) {
-        const GradwPlan g = gradw_plan(B, Ci, H, W, Co, c->op_gradw_partials);
+        constexpr int SW = ST == 1 ? kGradwStripCols : kGradwS2StripCols;
+        const GradwPlan g = gradw_plan(B, Ci, Ho, Wo, Co, c->op_gradw_partials, SW);
         GradwLaunch L{};
         L.x = dx; L.x_img = x_img; L.x_chunk = x_chunk; L.x_pix = x_pix; L.x_chunks = xch;
         L.g = dg; L.g_img = g_img; L.g_chunk = g_chunk; L.g_pix = g_pix; L.g_chunks = gch;
-        L.H = H; L.W = W; L.bands = g.bands; L.nsx = g.nsx; L.strips = g.strips; L.q = g.q;
+        L.H = Ho; L.W = Wo; L.xH = H; L.xW = W; L.bands = g.bands; L.nsx = g.nsx; L.strips = g.strips; L.q = g.q;
         L.n_co_tiles = g.n_co_tiles; L.co_pad = g.co_pad; L.ci_pad = g.ci_pad;
         float *ws = nullptr, *wsb = nullptr;
         if (grad_w) { CHK(st.out((size_t)g.P * 9 * g.co_pad * g.ci_pad, "gradw partials", &ws)); CHK(st.out(nw, "grad_w", &dgw)); }
@@ -521,8 +675,8 @@ int b2f_op_conv3x3_backward(b2f_ctx *c, const float *x, int B, int Ci, int H, in
         L.ws = ws;
         CHK(timed(c, s, "convbwd_gradw", [&] {
             if (grad_w)
-                if (hipError_t e = launch_gradw(g, L, s)) return e;
-            if (grad_b) hipLaunchKernelGGL(gradb_partials, dim3((unsigned)gch, (unsigned)g.P), dim3(64), 0, s, L, wsb);
+                if (hipError_t e = launch_gradw<ST>(g, L, s)) return e;
+            if (grad_b) hipLaunchKernelGGL(gradb_partials<SW>, dim3((unsigned)gch, (unsigned)g.P), dim3(64), 0, s, L, wsb);
             return hipGetLastError();
         }));
         CHK(timed(c, s, "convbwd_reduce", [&] {
@@ -537,6 +691,58 @@ int b2f_op_conv3x3_backward(b2f_ctx *c, const float *x, int B, int Ci, int H, in
     if (grad_b) CHK(st.get(grad_b, dgb, (size_t)Co));
     return 0;
 }
+
+}  // namespace
+
+extern "C" {
+
+int b2f_op_conv3x3_backward_plan(b2f_ctx *c, int B, int Ci, int H, int W, int Co, int *partials, long long *longest_chain) try
+{
+    const std::string fn = "b2f_op_conv3x3_backward_plan: ";
+    if (!c) return api_fail(fn + "ctx is null");
+    if (const char *why = size_refusal(B, Ci, H, W, Co)) return api_fail(fn + why);
+    const GradwPlan g = gradw_plan(B, Ci, H, W, Co, c->op_gradw_partials);
+    if (partials) *partials = g.P;
+    if (longest_chain) *longest_chain = g.longest_chain;
+    return 0;
+}
+B2F_CATCH("b2f_op_conv3x3_backward_plan")
+
+int b2f_op_conv3x3_backward(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, const float *w, int Co, int stride, int leaky, const float *y,
+                            const float *grad_y, int layout, float *grad_x, float *grad_w, float *grad_b) try
+{
+    const std::string fn = "b2f_op_conv3x3_backward: ";
+    if (!c) return api_fail(fn + "ctx is null");
+    if (const char *why = argument_refusal(x, w, y, grad_y, leaky, grad_x, grad_w, grad_b)) return api_fail(fn + why);
+    if (stride != 1) return api_fail(fn + "stride must be 1 (the stride-2 layers: b2f_op_conv3x3s2_backward)");
+    if (layout != 0 && layout != 1) return api_fail(fn + "layout must be 0 (NHWC strides) or 1 (chunk-planar)");
+    if (const char *why = size_refusal(B, Ci, H, W, Co)) return api_fail(fn + why);
+    return run_backward<1>(c, __func__, x, B, Ci, H, W, w, Co, leaky, y, grad_y, layout, grad_x, grad_w, grad_b);
+}
 B2F_CATCH("b2f_op_conv3x3_backward")
+
+int b2f_op_conv3x3s2_backward_plan(b2f_ctx *c, int B, int Ci, int H, int W, int Co, int *partials, long long *longest_chain) try
+{
+    const std::string fn = "b2f_op_conv3x3s2_backward_plan: ";
+    if (!c) return api_fail(fn + "ctx is null");
+    if (const char *why = size_refusal(B, Ci, H, W, Co)) return api_fail(fn + why);
+    const GradwPlan g = gradw_plan(B, Ci, (H - 1) / 2 + 1, (W - 1) / 2 + 1, Co, c->op_gradw_partials, kGradwS2StripCols);
+    if (partials) *partials = g.P;
+    if (longest_chain) *longest_chain = g.longest_chain;
+    return 0;
+}
+B2F_CATCH("b2f_op_conv3x3s2_backward_plan")
+
+int b2f_op_conv3x3s2_backward(b2f_ctx *c, const float *x, int B, int Ci, int H, int W, const float *w, int Co, int leaky, const float *y,
+                              const float *grad_y, int layout, float *grad_x, float *grad_w, float *grad_b) try
+{
+    const std::string fn = "b2f_op_conv3x3s2_backward: ";
+    if (!c) return api_fail(fn + "ctx is null");
+    if (const char *why = argument_refusal(x, w, y, grad_y, leaky, grad_x, grad_w, grad_b)) return api_fail(fn + why);
+    if (layout != 0 && layout != 1) return api_fail(fn + "layout must be 0 (NHWC strides) or 1 (chunk-planar)");
+    if (const char *why = size_refusal(B, Ci, H, W, Co)) return api_fail(fn + why);
+    return run_backward<2>(c, __func__, x, B, Ci, H, W, w, Co, leaky, y, grad_y, layout, grad_x, grad_w, grad_b);
+}
+B2F_CATCH("b2f_op_conv3x3s2_backward")
 
 }  // extern "C"

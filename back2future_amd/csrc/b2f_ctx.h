@@ -555,7 +555,7 @@ struct b2f_ctx : b2f::KernelOpts {
     int corr_ablate = 0;           // profiling only, see CorrLaunch::ablate
     int corr_variant = -1;         // warp + cost volume: -1 auto, 0 regular, 1 latency variant (bit-identical results)
     int op_wino_split = 0;         // b2f_op_conv3x3: F(2x2) kernel with one block per 32-output N tile (tests)
-    int op_gradw_partials = 0;     // b2f_op_conv3x3_backward: > 0 cuts the pixels into (at most) this many partial sums instead of the rule's (tests)
+    int op_gradw_partials = 0;     // b2f_op_conv3x3[s2]_backward: > 0 cuts the pixels into (at most) this many partial sums instead of the rule's (tests)
     int op_hole_fill = 0;          // b2f_op_layer: the input channels the layer does not read hold 1 + op_hole_fill + slot / 256 (tests)
     int profile_layers = 0;        // one profile row per (layer shape, map size)
     long long host_subbatch_pixels = 16ll << 20;

@@ -85,6 +85,38 @@ def conv3x3_backward_plan(model, B, ci, H, W, co):
     return partials.value, chain.value
 
 
+def conv3x3s2_backward(model, x, w, grad_y, y=None, leaky=False, layout=0, want=("x", "w", "b")):
+    """nn.SpatialConvolution(Ci, Co, 3, 3, 2, 2, 1, 1) [+ LeakyReLU(0.2)] :backward.  x: B x Ci x H x W, w: Co x Ci x 3 x 3, grad_y and
+    y (the layer's output, needed with leaky): B x Co x Ho x Wo with Ho = (H - 1) // 2 + 1, Wo = (W - 1) // 2 + 1.  layout and the returned
+    dict as conv3x3_backward."""
+    x, w, grad_y = _lib.f32(x), _lib.f32(w), _lib.f32(grad_y)
+    y = _lib.f32(y) if y is not None else None
+    B, ci, H, W = x.shape
+    co = w.shape[0]
+    if w.shape != (co, ci, 3, 3) or grad_y.shape != (B, co, (H - 1) // 2 + 1, (W - 1) // 2 + 1) or (y is not None and y.shape != grad_y.shape):
+        raise ValueError("ops.conv3x3s2_backward: shapes %s, %s, %s do not belong to one stride-2 layer" % (x.shape, w.shape, grad_y.shape))
+    out = {}
+    if "x" in want:
+        out["x"] = np.empty_like(x)
+    if "w" in want:
+        out["w"] = np.empty_like(w)
+    if "b" in want:
+        out["b"] = np.empty(co, np.float32)
+    ptr = lambda k: _lib.fptr(out[k]) if k in out else None
+    _lib.check(_lib.lib().b2f_op_conv3x3s2_backward(_h(model), _lib.fptr(x), B, ci, H, W, _lib.fptr(w), co, int(bool(leaky)),
+                                                    _lib.fptr(y) if y is not None else None, _lib.fptr(grad_y), int(layout), ptr("x"),
+                                                    ptr("w"), ptr("b")))
+    return out
+
+
+def conv3x3s2_backward_plan(model, B, ci, H, W, co):
+    """conv3x3_backward_plan for conv3x3s2_backward; H, W are the input map's, the chain counts output pixels.  Launches nothing."""
+    partials, chain = C.c_int(0), C.c_longlong(0)
+    _lib.check(_lib.lib().b2f_op_conv3x3s2_backward_plan(_h(model), int(B), int(ci), int(H), int(W), int(co), C.byref(partials),
+                                                         C.byref(chain)))
+    return partials.value, chain.value
+
+
 KINDS = {"feat": 0, "occ": 1, "flow": 2, "past": 3}
 
 

@@ -1182,6 +1182,19 @@ B2F_API int b2f_op_conv3x3_backward(b2f_ctx *ctx, const float *x, int B, int Ci,
  * (a function of B, Ci, H, W, Co alone unless option op_gradw_partials > 0 forces it) and the most pixels one partial sum adds up.
  * Either pointer may be NULL.  Makes no HIP call.                                                                                */
 B2F_API int b2f_op_conv3x3_backward_plan(b2f_ctx *ctx, int B, int Ci, int H, int W, int Co, int *partials, long long *longest_chain);
+/* nn.SpatialConvolution(Ci,Co,3,3,2,2,1,1) [+ LeakyReLU(0.2)] :backward -- pwc.lua:58-65, the first conv of a convUnit.  x: B x Ci x H x W
+ * (H, W: the INPUT map), w: Co x Ci x 3 x 3, y (read only when leaky) and grad_y: B x Co x Ho x Wo, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.
+ * Outputs, layout, g', the partial sums of grad_w / grad_b and the refusals are b2f_op_conv3x3_backward's (there is no stride argument).
+ * grad_x[b][ci][iy][ix] = sum over (co, ky, kx) with iy + 1 - ky and ix + 1 - kx even and inside 2 Ho x 2 Wo of
+ * g'[b][co][(iy + 1 - ky) / 2][(ix + 1 - kx) / 2] * w[co][ci][ky][kx]: a transposed convolution on a kernel of its own (profile row
+ * convbwd_gradx_s2) that multiplies the nine taps a 2 x 2 block of input pixels has; grad_w[co][ci][ky][kx] = sum over (b, oy, ox) of
+ * g'[b][co][oy][ox] * x[b][ci][2 oy + ky - 1][2 ox + kx - 1], zero outside the map (b2f_version() >= 1015).                            */
+B2F_API int b2f_op_conv3x3s2_backward(b2f_ctx *ctx, const float *x, int B, int Ci, int H, int W, const float *w, int Co,
+                                      int leaky, const float *y, const float *grad_y, int layout,
+                                      float *grad_x, float *grad_w, float *grad_b);
+/* b2f_op_conv3x3_backward_plan for a b2f_op_conv3x3s2_backward call: H, W are the input map's, the chain counts in-map OUTPUT pixels.
+ * Either pointer may be NULL.  Makes no HIP call.                                                                                */
+B2F_API int b2f_op_conv3x3s2_backward_plan(b2f_ctx *ctx, int B, int Ci, int H, int W, int Co, int *partials, long long *longest_chain);
 /* Two entries that run a piece of the loaded model in the forward pass's own layout (chunk-planar buffers, the context's packed
  * weights and options), for the tests of tests/test_gpu_in_place.py.
  * b2f_op_layer: conv (kind, level, idx) of the context's packed table -- kind 0 feature pyramid (level 2..7, idx 1..2; not feat2.conv1),
