@@ -14,11 +14,11 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libb2f.so")
 BUILD = os.path.join(HERE, "build")
 SOURCES = ["b2f_conv.hip", "b2f_wino.hip", "b2f_wino4.hip", "b2f_wino6.hip", "b2f_w1b.hip", "b2f_s2b.hip", "b2f_conv16.hip", "b2f_head.hip", "b2f_convb.hip", "b2f_corr.hip", "b2f_corr5.hip", "b2f_glue.hip", "b2f_seq.hip", "b2f_boundary.hip", "b2f_vis.hip", "b2f_score.hip", "b2f_warp.hip", "b2f_tableloss.hip", "b2f_tableloss_ft.hip", "b2f_tableloss_ssim.hip", "b2f_tableloss_grad.hip", "b2f_tableloss_grad_ft.hip", "b2f_tableloss_grad_ssim.hip", "b2f_tableloss_plain.hip", "b2f_tableloss_grad_plain.hip", "b2f_tableloss_epe.hip", "b2f_api.hip", "b2f_ops.hip", "b2f_graph.hip", "b2f_backward.hip", "b2f_convbwd.hip", "b2f_pipeline.hip", "b2f_multi.hip", "b2f_host.cpp", "b2f_t7.cpp"]
-HEADERS = ["b2f_internal.h", "b2f_host.h", "b2f_ctx.h", "b2f_flowcolor.h", "b2f_flowscore.h", "b2f_flowwarp.h", "b2f_tableloss.h", "b2f_tableloss_ft.h", "b2f_tableloss_ssim.h", "b2f_tableloss_grad.h", "b2f_tableloss_grad_ft.h", "b2f_tableloss_grad_ssim.h", "b2f_tableloss_plain.h", "b2f_tableloss_epe.h", "b2f_tableloss_dev.h", "b2f_tableloss_ssim_dev.h", "b2f_corr5_loop.inc", os.path.join("..", "..", "include", "b2f.h")]
+HEADERS = ["b2f_internal.h", "b2f_host.h", "b2f_ctx.h", "b2f_flowcolor.h", "b2f_flowscore.h", "b2f_flowwarp.h", "b2f_tableloss.h", "b2f_tableloss_ft.h", "b2f_tableloss_ssim.h", "b2f_tableloss_grad.h", "b2f_tableloss_grad_ft.h", "b2f_tableloss_grad_ssim.h", "b2f_tableloss_plain.h", "b2f_tableloss_epe.h", "b2f_tableloss_dev.h", "b2f_tableloss_ssim_dev.h", "b2f_corr5_loop.inc", "b2f_corr_tile.h", "b2f_corr5.h", os.path.join("..", "..", "include", "b2f.h")]
 # tools/experiments/csrc: kernels that were built, tested and measured no faster than the defaults; `--experiments` builds them and
 # the options that select them into libb2f_exp.so (B2F_LIB=<that file>); the product library does not contain them
 EXP_DIR = os.path.join(os.path.dirname(HERE), "tools", "experiments", "csrc")
-EXP_SOURCES = ["b2f_wino4s.hip", "b2f_wino2s.hip", "b2f_conv16b.hip"]
+EXP_SOURCES = ["b2f_wino4s.hip", "b2f_wino2s.hip", "b2f_conv16b.hip", "b2f_corr_exp.hip", "b2f_corr6.hip"]
 EXP_OUT = os.path.join(HERE, "libb2f_exp.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -26,7 +26,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # b2f_corr: the SLP vectorizer packs the 81 independent FMA chains into v_pk_fma_f32 pairs whose
 # operands are not register-adjacent, which costs ~2 v_mov per FMA; plain v_fmac is faster here.
 # b2f_wino4s: packed fp32 ops do not overlap the bf16 MFMAs (tools/mfma_bf16_chain.hip); its VALU work is written scalar on purpose.
-EXTRA = {"b2f_corr.hip": ["-fno-slp-vectorize"], "b2f_corr5.hip": ["-fno-slp-vectorize"], "b2f_wino4s.hip": ["-fno-slp-vectorize"], "b2f_wino2s.hip": ["-fno-slp-vectorize"], "b2f_conv16b.hip": ["-fno-slp-vectorize"], "b2f_head.hip": ["-fno-slp-vectorize"], "b2f_convb.hip": ["-fno-slp-vectorize"], "b2f_w1b.hip": ["-fno-slp-vectorize"], "b2f_s2b.hip": ["-fno-slp-vectorize"]}
+EXTRA = {"b2f_corr.hip": ["-fno-slp-vectorize"], "b2f_corr5.hip": ["-fno-slp-vectorize"], "b2f_corr_exp.hip": ["-fno-slp-vectorize"], "b2f_corr6.hip": ["-fno-slp-vectorize"], "b2f_wino4s.hip": ["-fno-slp-vectorize"], "b2f_wino2s.hip": ["-fno-slp-vectorize"], "b2f_conv16b.hip": ["-fno-slp-vectorize"], "b2f_head.hip": ["-fno-slp-vectorize"], "b2f_convb.hip": ["-fno-slp-vectorize"], "b2f_w1b.hip": ["-fno-slp-vectorize"], "b2f_s2b.hip": ["-fno-slp-vectorize"]}
 
 
 

@@ -4,8 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 // B2F_EXPERIMENTS=1 (python -m back2future_amd.build --experiments -> libb2f_exp.so): the kernels of tools/experiments/csrc -- forms that
-// were built, tested and measured no faster than the defaults (profiles/r04_*_notes.txt) -- and the options that select them.  The
-// product library is built without them.
+// were built, tested and measured no faster than the defaults (profiles/r04_*_notes.txt; the cost-volume variants 4, 6, 8: r02_corr_
+// experiments, r03_corr_unit_kernel, r05_corr_notes) -- and the options that select them.  The product library is built without them.
+// In csrc the macro guards launcher hooks, option handling and instantiations of shipped templates (cost-volume variant 2, the F(4x4)
+// hybrid steps), never a kernel of its own.
 #ifndef B2F_EXPERIMENTS
 #define B2F_EXPERIMENTS 0
 #endif
@@ -300,8 +302,14 @@ int choose_corr_variant(const CorrLaunch &p);
 // b2f_corr5.hip: the persistent "unit" form (variant 5; C a multiple of 32), same bits as the others
 bool warp_costvol_unit_supported(const CorrLaunch &p);
 hipError_t launch_warp_costvol_unit(const CorrLaunch &p, hipStream_t s);
-// the role-specialised form of it (variant 6): FMA waves and gather waves, source window by LDS-DMA
+#if B2F_EXPERIMENTS
+// tools/experiments/csrc/b2f_corr6.hip: the role-specialised form of it (variant 6): FMA waves and gather waves, source window by LDS-DMA
 hipError_t launch_warp_costvol_spec(const CorrLaunch &p, hipStream_t s);
+// tools/experiments/csrc/b2f_corr_exp.hip: variant 3 with the source window staged by LDS-DMA (variant 4); four pixels x three qx
+// columns per thread (variant 8)
+hipError_t launch_warp_costvol_win(const CorrLaunch &p, hipStream_t s);
+hipError_t launch_warp_costvol_4px(const CorrLaunch &p, hipStream_t s);
+#endif
 // ten unit waves + six gather waves per block (variant 7)
 hipError_t launch_warp_costvol_gw(const CorrLaunch &p, hipStream_t s);
 // generic (any odd win) single-direction cost volume, NHWC in, B x h x w x win*win out

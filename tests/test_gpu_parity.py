@@ -201,7 +201,7 @@ def test_conv3x3_transpose_detecting(hard):
 def corr_variant(request, hard):
     """Every instantiation of the warp + cost-volume kernel (the launcher would pick by map / launch size; variants 5 and 6, the
     persistent unit kernel and its role-specialised form, serve channel counts that are multiples of 16 and hand the others to
-    variant 3).  Variants 2, 4, 6 are experiments (tools/experiments): they run with the experiments build only."""
+    variant 3).  Variants 2, 4, 6 and 8 are experiments (tools/experiments): they run with the experiments build only."""
     if request.param in (2, 4, 6, 8):
         _need_experiments(hard)
     with hard.options(corr_variant=request.param):

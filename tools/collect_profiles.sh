@@ -8,13 +8,16 @@ R=${GRAFT_REPO_ROOT:?set GRAFT_REPO_ROOT}
 OUT=${B2F_OUT:?set B2F_OUT to the directory the results go to}/profiles_$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-timeout 280 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o b2f -- \
+timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o b2f -- \
   python3 $R/bench.py --full --steps 5 --warmup 2 --no-extras > $OUT/bench_under_rocprof.log 2>&1
-echo "stats rc=$?"
+rc=$?; echo "stats rc=$rc"
+# a pass that failed or ran into its time limit ends the script: nothing more is started on a GPU that may have faulted
+[ $rc -eq 0 ] || exit $rc
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -o b2f -- \
+  timeout -k 10 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -o b2f -- \
     python3 $R/bench.py --full --steps 1 --warmup 1 --no-extras > $OUT/pmc_$c.log 2>&1
-  echo "$c rc=$?"
+  rc=$?; echo "$c rc=$rc"
+  [ $rc -eq 0 ] || exit $rc
 done
 cd $R
 grep '^{"metric"' $OUT/bench_under_rocprof.log | tail -1 > $OUT/${TAG}_bench_under_rocprof.json

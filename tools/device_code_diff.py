@@ -5,6 +5,7 @@
 Compiles every .hip of build.SOURCES (product flags) and of build.EXP_SOURCES (-DB2F_EXPERIMENTS=1) of both trees for the
 device only, with the flags and the per-file EXTRA of <this tree>'s back2future_amd/build.py, copies .text, .rodata and .note
 out of each device ELF and compares their hashes.  Prints `same` or `DIFFERENT` per file; exit status 1 on any difference.
+A file that only one tree has is compiled there and printed as `new` (this tree's) or `gone` (the parent's); it is no difference.
 
 The sections are compared, not the files, and both trees' builds of a file get the same -cuid.  By default hipcc hashes the paths
 (the output's included) into a symbol __hip_cuid_<hex>, printed without leading zeros: besides making the whole ELFs differ, a
@@ -69,7 +70,7 @@ def main():
     ap.add_argument("--keep", help="keep the device ELFs and section files in this directory")
     a = ap.parse_args()
     trees = [os.path.abspath(a.parent), os.path.abspath(a.this)]
-    b = load_build(trees[1])
+    b, b_parent = load_build(trees[1]), load_build(trees[0])
     objcopy = find_objcopy(b.HIPCC)
     csrc_rel = os.path.join("back2future_amd", "csrc")
     exp_rel = os.path.relpath(b.EXP_DIR, trees[1])
@@ -77,6 +78,10 @@ def main():
     units = [("product", csrc_rel, s, False) for s in b.SOURCES if s.endswith(".hip")]
     units += [("experiments", csrc_rel, s, True) for s in b.SOURCES if s.endswith(".hip")]
     units += [("experiments", exp_rel, s, True) for s in b.EXP_SOURCES if s.endswith(".hip")]
+    # files only the parent lists (`gone`), after this tree's
+    units += [("product", csrc_rel, s, False) for s in b_parent.SOURCES if s.endswith(".hip") and s not in b.SOURCES]
+    units += [("experiments", csrc_rel, s, True) for s in b_parent.SOURCES if s.endswith(".hip") and s not in b.SOURCES]
+    units += [("experiments", exp_rel, s, True) for s in b_parent.EXP_SOURCES if s.endswith(".hip") and s not in b.EXP_SOURCES]
     work = a.keep or tempfile.mkdtemp(prefix="device_code_diff_")
     different = 0
     try:
@@ -87,9 +92,14 @@ def main():
                 for i, tree in enumerate(trees):
                     d = os.path.join(work, "parent" if i == 0 else "this", label)
                     os.makedirs(d, exist_ok=True)
-                    fut.append(pool.submit(section_hashes, b, objcopy, tree, rel, src, exp, d))
+                    there = os.path.exists(os.path.join(tree, rel, src))
+                    fut.append(pool.submit(section_hashes, b, objcopy, tree, rel, src, exp, d) if there else None)
                 jobs.append((label, src, fut))
             for label, src, (fa, fb) in jobs:
+                if fa is None or fb is None:
+                    (fa or fb).result()
+                    print("%-12s %-28s %s" % (label, src, "new" if fa is None else "gone"), flush=True)
+                    continue
                 ha, hb = fa.result(), fb.result()
                 diff = [s for s in SECTIONS if ha[s] != hb[s]]
                 different += bool(diff)
